@@ -16,13 +16,20 @@ the timed region starts.  Rank 0 prints one JSON line; ``value`` is whole-job la
 ``--workload cfg4`` runs BASELINE configs[3] instead (Lumina-Next-SFT 2B GQA at 2048x2048 = 16384 latent tokens per image,
 time-aware RoPE scaling, one image per GPU: its BASELINE form "batch = 8 sharded over 8 GPUs" is ``--gpus 8``).
 
+A plain run sets up, warms up, times the K steps and prints the line (headline fields, `comm`); ``--dump-outputs DIR`` then
+writes the last timed step's result (the final latent of the trajectory, both CFG rows, float32) as ``DIR/final_latent.npy``.
+Inputs and weights are drawn from fixed seeds, so two builds run with the same arguments can be compared output for output.
+
+``--full`` adds everything else, as before:
 ``roofline`` is measured live with HIP events around every launch of the dominant kernel class (the bf16 MFMA GEMMs,
 76 % of the algorithmic FLOPs) on the launch stream; ``cpu_baseline`` times the CPU oracle (fp32, host
 cores) on ONE complete forward_with_cfg of the bench workload (all 24 layers: 30-70 s of CPU time, measured, not
 extrapolated); the TRUE reference timing (unmodified reference module, authoring container, min of 3 with the host load
-stated) is quoted beside it from profiles/.  ``power`` is the socket power sampled over the timed region.
+stated) is quoted beside it from profiles/.  ``power`` is the socket power sampled over the timed region; ``--repeats``
+timed regions, the per-class kernel breakdown (``kernel_time_ms_per_step``, ``roofline_attention``) and the ``box`` probe.
 """
 import argparse
+import contextlib
 import json
 import os
 import socket
@@ -445,15 +452,20 @@ def main():
     ap.add_argument("--steps", type=int, default=29, help="timed denoising steps (NFE); 29 = one 30-point Euler grid")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="cfg2")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="measure more than the headline: GEMM events in the timed region (roofline), socket power, --repeats timed "
+                         "regions, the per-class kernel breakdown, the box probe and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's result (final latent, float32) as DIR/final_latent.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--opt", action="append", default=[], help="engine A/B knob name=value (lt_set_option), repeatable")
     ap.add_argument("--event-steps", type=float, default=0.5,
-                    help="NFEs of the timed region whose GEMM launches carry HIP start/stop events (0 = all).  A timed launch "
+                    help="with --full: NFEs of the timed region whose GEMM launches carry HIP start/stop events (0 = all).  A timed launch "
                          "costs ~0.1 ms of queue idle time on this stack (the host waits on the dispatch signal), so the default "
                          "samples the first half NFE = embedder + every GEMM shape x 12 layers (every layer and every NFE has the "
                          "same shapes)")
     ap.add_argument("--profile-classes", type=int, default=1,
-                    help="bit mask of kernel classes bracketed by HIP events IN THE TIMED REGION: 1 GEMM (the roofline kernel, "
+                    help="with --full: bit mask of kernel classes bracketed by HIP events IN THE TIMED REGION: 1 GEMM (the roofline kernel, "
                          "default), 2 attention, 4 other.  Every bracketed launch costs two event packets (all classes: +4 %% "
                          "wall), so the attention / other breakdown is taken in a short untimed pass after the timed region")
     ap.add_argument("--share-device", action="store_true",
@@ -461,12 +473,14 @@ def main():
                          "self-launch / rank / shard / max-over-ranks / JSON relay logic with the real engine on a ONE-GPU box; it is NOT "
                          "a scaling measurement (the line says n_gpus 1, ranks N, shared_device true) and says nothing about RCCL")
     ap.add_argument("--repeats", type=int, default=3,
-                    help="timed regions run back to back in this process: `value` / `ms_per_step` are the FIRST (the contract's K steps); "
+                    help="with --full: timed regions run back to back in this process: `value` / `ms_per_step` are the FIRST (the contract's K steps); "
                          "`ms_per_step_repeats` lists all of them so that a round-over-round delta can be told from run-to-run noise")
     ap.add_argument("--gqa", action="store_true", help="shorthand for --workload cfg2-gqa")
     ap.add_argument("--attn-variant", type=int, default=None, help="A/B knob: 1 baseline, 2 VALU-diet, 3 ping-pong, 4 one wave per SIMD (default)")
     ap.add_argument("--gemm-variant", type=int, default=None, help="A/B knob: 0 auto (default), 1 256x256, 2 256x288")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     maybe_self_launch(args, sys.argv[1:])
 
     import torch
@@ -531,21 +545,22 @@ def main():
     if args.warmup > 0:
         run(args.warmup)
     torch.cuda.synchronize()
-    eng = model._engine
-    eng.profile_enable(args.profile_classes)
-    # HIP start/stop events on the GEMM dispatches of the first --event-steps NFE of the timed region (every NFE has the
-    # same launch mix; timing all of them costs ~2.5 ms per NFE of queue idle time, which would be charged to `value`)
-    hd0 = model.dim // model.n_heads
-    gemm_label, gemm_per_layer = gemm_kernel_label(_lib.load(), 2 * n_tokens, model.dim, model.ffn_hidden, model.n_kv_heads * hd0, n_tokens, hd0)
-    gemm_launches_per_nfe = gemm_per_layer * model.n_layers + 2
-    event_launches = -1 if args.event_steps <= 0 else max(1, int(round(args.event_steps * gemm_launches_per_nfe)))
-    # ... taken from the middle of the region (the first launches after the barrier meet an idle chip in another power state)
-    skip = gemm_launches_per_nfe * (args.steps // 2) if event_launches > 0 else 0
-    eng.profile_set_window(0, skip, event_launches)
-    eng.profile_reset()
+    if args.full:
+        eng = model._engine
+        eng.profile_enable(args.profile_classes)
+        # HIP start/stop events on the GEMM dispatches of the first --event-steps NFE of the timed region (every NFE has the
+        # same launch mix; timing all of them costs ~2.5 ms per NFE of queue idle time, which would be charged to `value`)
+        hd0 = model.dim // model.n_heads
+        gemm_label, gemm_per_layer = gemm_kernel_label(_lib.load(), 2 * n_tokens, model.dim, model.ffn_hidden, model.n_kv_heads * hd0, n_tokens, hd0)
+        gemm_launches_per_nfe = gemm_per_layer * model.n_layers + 2
+        event_launches = -1 if args.event_steps <= 0 else max(1, int(round(args.event_steps * gemm_launches_per_nfe)))
+        # ... taken from the middle of the region (the first launches after the barrier meet an idle chip in another power state)
+        skip = gemm_launches_per_nfe * (args.steps // 2) if event_launches > 0 else 0
+        eng.profile_set_window(0, skip, event_launches)
+        eng.profile_reset()
     parallel.barrier()
     torch.cuda.synchronize()
-    power = PowerSampler(local)
+    power = PowerSampler(local) if args.full else contextlib.nullcontext()
     with power:
         t0 = time.perf_counter()
         traj = run(args.steps)
@@ -554,58 +569,50 @@ def main():
         dt = time.perf_counter() - t0
     comm = parallel.comm_report(dt / args.steps * 1e3, dev)  # (after the timed region: its collectives are not part of `value`)
     dt = parallel.max_over_ranks(dt, dev)
-    eng.profile_enable(False)
+    eng = model._engine
     assert eng.last_nfe() == args.steps
-    gemm_prof = eng.profile_read(0)
-    # further timed regions, same process, same bracket: not part of `value`
-    repeats_ms = [dt / args.steps * 1e3]
-    for _ in range(max(0, args.repeats - 1)):
-        parallel.barrier()
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        run(args.steps)
-        torch.cuda.synchronize()
-        parallel.barrier()
-        repeats_ms.append(parallel.max_over_ranks(time.perf_counter() - t0, dev) / args.steps * 1e3)
-    # untimed pass for the per-class breakdown (events around every launch)
-    nb = min(4, args.steps)
-    eng.profile_set_budget(0, -1)
-    eng.profile_enable(7)
-    eng.profile_reset()
-    run(nb)
-    torch.cuda.synchronize()
-    eng.profile_enable(False)
-    breakdown = {k: eng.profile_read(i)[0] / nb for i, k in enumerate(("gemm", "attention", "other"))}
-    attn_ms_b, _, attn_fl_b = eng.profile_read(1)
     assert torch.isfinite(traj[-1].float()).all(), "non-finite latent"
+    if args.dump_outputs:
+        # every rank's final latent (its image's cond + uncond rows) gathered on rank 0 in image order: [images, 2, C, H, W]
+        final = parallel.gather_latents(traj[-1][None], n_img, dst=0)
+        if rank == 0:
+            import numpy as np
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            np.save(os.path.join(args.dump_outputs, "final_latent.npy"), final.float().cpu().numpy())
+    if args.full:
+        eng.profile_enable(False)
+        gemm_prof = eng.profile_read(0)
+        # further timed regions, same process, same bracket: not part of `value`
+        repeats_ms = [dt / args.steps * 1e3]
+        for _ in range(max(0, args.repeats - 1)):
+            parallel.barrier()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            run(args.steps)
+            torch.cuda.synchronize()
+            parallel.barrier()
+            repeats_ms.append(parallel.max_over_ranks(time.perf_counter() - t0, dev) / args.steps * 1e3)
+        # untimed pass for the per-class breakdown (events around every launch)
+        nb = min(4, args.steps)
+        eng.profile_set_budget(0, -1)
+        eng.profile_enable(7)
+        eng.profile_reset()
+        run(nb)
+        torch.cuda.synchronize()
+        eng.profile_enable(False)
+        breakdown = {k: eng.profile_read(i)[0] / nb for i, k in enumerate(("gemm", "attention", "other"))}
+        attn_ms_b, _, attn_fl_b = eng.profile_read(1)
 
     if rank == 0:
         hd = model.dim // model.n_heads
         nfe_flops = flops_per_nfe(dim=model.dim, n_layers=model.n_layers, n_heads=model.n_heads, n_kv_heads=model.n_kv_heads,
                                   ffn=model.ffn_hidden, cap_feat_dim=model.cap_feat_dim, n_tokens=n_tokens, text_len=TEXT_LEN, batch=2)
-        gemm_ms, gemm_n, gemm_fl = gemm_prof
-        achieved = gemm_fl / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0
-        pmc_g, traffic_src = pmc_summary("pmc_gemm.json")
-        traffic = None if pmc_g is None else float(pmc_g["hbm_bytes_per_launch"])
-        pmc_a, attn_src = pmc_summary("pmc_attn.json")
-        attn_tf = attn_fl_b / (attn_ms_b * 1e-3) / 1e12 if attn_ms_b > 0 else 0.0
-        attn_launches = model.n_layers * nb
-        # hd 72 on 32x32x16 MFMAs (csrc/attention_v4.hip): QK^T runs 5 k-steps = 80 of depth for 72 (the 8 pad slots carry the running max and
-        # the text mask), P V writes 96 rows of O^T for 72 + the row of ones (row sum): executed / useful = (80 + 96) / (2 x 72)
-        attn_exec = (80.0 + 96.0) / (2.0 * 72.0)
-        rows_attn, dkv_attn = 2 * n_tokens, model.n_kv_heads * hd
-        # bf16: q read + out written ([rows, d] each), k + v read ([rows, dkv] each), the text keys / values of the pair
-        attn_alg_bytes = 2.0 * (2 * rows_attn * model.dim + 2 * rows_attn * dkv_attn + 2 * 2 * TEXT_LEN * dkv_attn)
-        rp_ms, rp_src = rocprof_gemm_time_per_nfe()
-        gemm_fl_per_nfe = gemm_fl / args.steps
         out = {
             "metric": "denoising-steps/s & latent-tokens/s, Next-DiT 2B %d^2 CFG" % res,
             "value": world * n_tokens * args.steps / dt,
             "unit": "latent-tokens/s",
             "n_gpus": 1 if share else world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": dt / args.steps * 1e3,
-            "ms_per_step_repeats": repeats_ms,
-            "box": None,  # filled below (needs the power report)
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "bf16", "data": "synthetic",
             "config": {"workload": (wl["desc"] + ", text T=128, CFG=4 (cond+uncond B=2), proportional attention, "
@@ -614,62 +621,81 @@ def main():
             "denoising_steps_per_s": world * args.steps / dt,
             "model_tflops_per_s_per_gpu": nfe_flops * args.steps / dt / 1e12,
             "mfma_roofline_frac_whole_step": nfe_flops * args.steps / dt / 1e12 / MFMA_BF16_PEAK_TFLOPS,
-            "roofline": {
-                "bound": "mfma",
-                "kernel": "all bf16 GEMM launches of the timed region - " + gemm_label,
-                "achieved": achieved, "peak": MFMA_BF16_PEAK_TFLOPS, "unit": "TFLOP/s",
-                "frac": achieved / MFMA_BF16_PEAK_TFLOPS, "traffic": traffic,
-                "traffic_unit": "bytes/launch on the L2's FABRIC side (rocprofv3 FETCH_SIZE x 2 + WRITE_SIZE = TCC_EA read / write requests, "
-                                "the guide's gfx950 correction applied): includes Infinity-Cache hits, so it is an upper bound on HBM bytes",
-                "traffic_source": traffic_src,
-                # A + W + C of every GEMM launch of one layer (QKV, O, W1|W3 + SwiGLU, W2), bf16, averaged over the launches
-                "algorithmic_bytes_per_launch": algorithmic_gemm_bytes_per_launch(2 * n_tokens, model.dim, model.ffn_hidden,
-                                                                                   model.n_kv_heads * hd),
-                "traffic_over_algorithmic": (None if traffic is None else traffic / algorithmic_gemm_bytes_per_launch(
-                    2 * n_tokens, model.dim, model.ffn_hidden, model.n_kv_heads * hd)),
-                "launches": gemm_n, "avg_launch_ms": gemm_ms / max(gemm_n, 1),
-                "event_bracketed_launches": (gemm_n if event_launches < 0 else min(gemm_n, event_launches)),
-                "algorithmic_flops_per_launch": gemm_fl / max(gemm_n, 1),
-                # the dispatch-attached event pairs include a few microseconds of packet processing per launch; the committed rocprofv3
-                # kernel trace of the same command gives the pure kernel durations
-                "rocprofv3_cross_check": (None if rp_ms is None else {
-                    "gemm_ms_per_step": rp_ms, "achieved": gemm_fl_per_nfe / (rp_ms * 1e-3) / 1e12,
-                    "frac": gemm_fl_per_nfe / (rp_ms * 1e-3) / 1e12 / MFMA_BF16_PEAK_TFLOPS, "source": rp_src,
-                    "box": "builder's profiling box (a committed file), NOT this run's box"}),
-            },
-            # the kernel furthest below its roof: the fused self + text attention launch, 24 per NFE
-            "roofline_attention": {
-                "bound": "mfma",
-                "kernel": "attn_fwd_kernel_v4<72>: flash_attn_varlen_func + the gated text SDPA of model.py:392-434 in one launch, q_norm + RoPE of the queries in its prologue",
-                "achieved": attn_tf, "peak": MFMA_BF16_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": attn_tf / MFMA_BF16_PEAK_TFLOPS,
-                "achieved_is": "ALGORITHMIC flops 4 B H N (N + T) hd per launch / average launch duration from HIP events around every launch of an "
-                               f"untimed pass of {nb} NFE right after the timed region (events around every launch cost the timed region 4 %)",
-                "executed_over_algorithmic_mfma": attn_exec,
-                "executed_mfma_frac": attn_tf * attn_exec / MFMA_BF16_PEAK_TFLOPS,
-                "padding": "head_dim 72: QK^T at depth 80 (5 x 16; pad slots = running max + text mask), P V on 96 O^T rows (72 + the row of ones + zeros)",
-                "launches": attn_launches, "avg_launch_ms": attn_ms_b / max(attn_launches, 1),
-                "algorithmic_flops_per_launch": attn_fl_b / max(attn_launches, 1),
-                "algorithmic_bytes_per_launch": attn_alg_bytes,
-                "traffic": None if pmc_a is None else float(pmc_a["hbm_bytes_per_launch"]),
-                "traffic_over_algorithmic": None if pmc_a is None else float(pmc_a["hbm_bytes_per_launch"]) / attn_alg_bytes,
-                "mfma_duty_pmc": None if pmc_a is None else pmc_a.get("mfma_duty"),
-                "traffic_unit": "bytes/launch on the L2's fabric side, as in `roofline`",
-                "traffic_source": attn_src,
-            },
-            "kernel_time_ms_per_step": dict(breakdown, note=f"untimed pass of {nb} NFE with events around every launch"),
-            "attention_tflops_per_s": attn_tf,
             "kernel_variants": {"attention": args.attn_variant or 4, "gemm": args.gemm_variant or 0,
                                 # round 6: the persistent GEMM's A / W operands (and the four weights of every layer) in the row-pair-interleaved layout:
                                 # whole 128-byte lines per LDS-DMA request (include/lumina_dit.h, lt_op_pair_layout); bit-identical results
                                 "gemm_operand_layout": "row-major" if "pair_layout=0" in args.opt else "row-pair-interleaved"},
             "hip_graph_replays": eng.graph_replays(),
-            "power": power.report(dt, nfe_flops * args.steps / 1e12),
             "parity_fixture": wl["parity"],
             "ode_stepping_parity": "euler (this run) and midpoint pinned to the reference's in-tree midpoint_solver (visual_anagrams/"
                                    "generate.py:212-219, tests/golden/solver_kat.npz); rk4 / dopri5 restate torchdiffeq (absent "
                                    "everywhere) and stay unpinned, DESIGN.md 6",
         }
-        out["box"] = box_probe(_lib.load(), torch, out["power"])
+        if args.full:
+            gemm_ms, gemm_n, gemm_fl = gemm_prof
+            achieved = gemm_fl / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0
+            pmc_g, traffic_src = pmc_summary("pmc_gemm.json")
+            traffic = None if pmc_g is None else float(pmc_g["hbm_bytes_per_launch"])
+            pmc_a, attn_src = pmc_summary("pmc_attn.json")
+            attn_tf = attn_fl_b / (attn_ms_b * 1e-3) / 1e12 if attn_ms_b > 0 else 0.0
+            attn_launches = model.n_layers * nb
+            # hd 72 on 32x32x16 MFMAs (csrc/attention_v4.hip): QK^T runs 5 k-steps = 80 of depth for 72 (the 8 pad slots carry the running max and
+            # the text mask), P V writes 96 rows of O^T for 72 + the row of ones (row sum): executed / useful = (80 + 96) / (2 x 72)
+            attn_exec = (80.0 + 96.0) / (2.0 * 72.0)
+            rows_attn, dkv_attn = 2 * n_tokens, model.n_kv_heads * hd
+            # bf16: q read + out written ([rows, d] each), k + v read ([rows, dkv] each), the text keys / values of the pair
+            attn_alg_bytes = 2.0 * (2 * rows_attn * model.dim + 2 * rows_attn * dkv_attn + 2 * 2 * TEXT_LEN * dkv_attn)
+            rp_ms, rp_src = rocprof_gemm_time_per_nfe()
+            gemm_fl_per_nfe = gemm_fl / args.steps
+            out.update({
+                "ms_per_step_repeats": repeats_ms,
+                "roofline": {
+                    "bound": "mfma",
+                    "kernel": "all bf16 GEMM launches of the timed region - " + gemm_label,
+                    "achieved": achieved, "peak": MFMA_BF16_PEAK_TFLOPS, "unit": "TFLOP/s",
+                    "frac": achieved / MFMA_BF16_PEAK_TFLOPS, "traffic": traffic,
+                    "traffic_unit": "bytes/launch on the L2's FABRIC side (rocprofv3 FETCH_SIZE x 2 + WRITE_SIZE = TCC_EA read / write requests, "
+                                    "the guide's gfx950 correction applied): includes Infinity-Cache hits, so it is an upper bound on HBM bytes",
+                    "traffic_source": traffic_src,
+                    # A + W + C of every GEMM launch of one layer (QKV, O, W1|W3 + SwiGLU, W2), bf16, averaged over the launches
+                    "algorithmic_bytes_per_launch": algorithmic_gemm_bytes_per_launch(2 * n_tokens, model.dim, model.ffn_hidden,
+                                                                                       model.n_kv_heads * hd),
+                    "traffic_over_algorithmic": (None if traffic is None else traffic / algorithmic_gemm_bytes_per_launch(
+                        2 * n_tokens, model.dim, model.ffn_hidden, model.n_kv_heads * hd)),
+                    "launches": gemm_n, "avg_launch_ms": gemm_ms / max(gemm_n, 1),
+                    "event_bracketed_launches": (gemm_n if event_launches < 0 else min(gemm_n, event_launches)),
+                    "algorithmic_flops_per_launch": gemm_fl / max(gemm_n, 1),
+                    # the dispatch-attached event pairs include a few microseconds of packet processing per launch; the committed rocprofv3
+                    # kernel trace of the same command gives the pure kernel durations
+                    "rocprofv3_cross_check": (None if rp_ms is None else {
+                        "gemm_ms_per_step": rp_ms, "achieved": gemm_fl_per_nfe / (rp_ms * 1e-3) / 1e12,
+                        "frac": gemm_fl_per_nfe / (rp_ms * 1e-3) / 1e12 / MFMA_BF16_PEAK_TFLOPS, "source": rp_src,
+                        "box": "builder's profiling box (a committed file), NOT this run's box"}),
+                },
+                # the kernel furthest below its roof: the fused self + text attention launch, 24 per NFE
+                "roofline_attention": {
+                    "bound": "mfma",
+                    "kernel": "attn_fwd_kernel_v4<72>: flash_attn_varlen_func + the gated text SDPA of model.py:392-434 in one launch, q_norm + RoPE of the queries in its prologue",
+                    "achieved": attn_tf, "peak": MFMA_BF16_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": attn_tf / MFMA_BF16_PEAK_TFLOPS,
+                    "achieved_is": "ALGORITHMIC flops 4 B H N (N + T) hd per launch / average launch duration from HIP events around every launch of an "
+                                   f"untimed pass of {nb} NFE right after the timed region (events around every launch cost the timed region 4 %)",
+                    "executed_over_algorithmic_mfma": attn_exec,
+                    "executed_mfma_frac": attn_tf * attn_exec / MFMA_BF16_PEAK_TFLOPS,
+                    "padding": "head_dim 72: QK^T at depth 80 (5 x 16; pad slots = running max + text mask), P V on 96 O^T rows (72 + the row of ones + zeros)",
+                    "launches": attn_launches, "avg_launch_ms": attn_ms_b / max(attn_launches, 1),
+                    "algorithmic_flops_per_launch": attn_fl_b / max(attn_launches, 1),
+                    "algorithmic_bytes_per_launch": attn_alg_bytes,
+                    "traffic": None if pmc_a is None else float(pmc_a["hbm_bytes_per_launch"]),
+                    "traffic_over_algorithmic": None if pmc_a is None else float(pmc_a["hbm_bytes_per_launch"]) / attn_alg_bytes,
+                    "mfma_duty_pmc": None if pmc_a is None else pmc_a.get("mfma_duty"),
+                    "traffic_unit": "bytes/launch on the L2's fabric side, as in `roofline`",
+                    "traffic_source": attn_src,
+                },
+                "kernel_time_ms_per_step": dict(breakdown, note=f"untimed pass of {nb} NFE with events around every launch"),
+                "attention_tflops_per_s": attn_tf,
+                "power": power.report(dt, nfe_flops * args.steps / 1e12),
+            })
+            out["box"] = box_probe(_lib.load(), torch, out["power"])
         # evidence that the collective layer saw every rank: backend, RCCL version, an all-reduce of ones, each rank's own ms / step
         out["comm"] = dict(comm, ms_per_step_per_rank=comm["per_rank"], collective_in_timed_region=False,
                            note="value = images x tokens x NFE / max-over-ranks wall; no scaling curve has been measured on hardware "
@@ -681,7 +707,7 @@ def main():
             out.update(ranks=world, shared_device=True,
                        note="ranks share GPU 0 over gloo: exercises launcher / rank / shard / relay logic with the real engine; NOT a scaling "
                             "measurement and no evidence about RCCL or xGMI")
-        if world == 1 and not args.no_cpu_baseline and args.workload == "cfg2":
+        if args.full and world == 1 and not args.no_cpu_baseline and args.workload == "cfg2":
             try:
                 out["cpu_baseline"] = cpu_baseline(latent, n_tokens)
             except Exception as exc:  # the CPU leg is a reported baseline, not the product: its failure must not cost the measured line

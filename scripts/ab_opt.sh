@@ -3,7 +3,7 @@
 set -u
 OPT=$1; VALS=$2; ROUNDS=${3:-2}; LOG=${4:-/dev/null}
 for i in $(seq $ROUNDS); do for v in $VALS; do
-  timeout 600 python bench.py --no-cpu-baseline --opt $OPT=$v > /tmp/ab.tmp 2>/dev/null
+  timeout 600 python bench.py --full --no-cpu-baseline --opt $OPT=$v > /tmp/ab.tmp 2>/dev/null
   python - /tmp/ab.tmp "$OPT=$v" <<'PY' | tee -a $LOG
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

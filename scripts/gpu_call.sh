@@ -6,7 +6,7 @@
 #
 # steps (run in the order given):
 #   tests[:<pytest -k expr>]   python -m pytest tests -m gpu -q -x [-k expr]          -> pytest_gpu.log
-#   bench[:<extra args>]       python bench.py <extra>                                 -> bench.json (+ one-line digest)
+#   bench[:<extra args>]       python bench.py --full <extra>                          -> bench.json (+ one-line digest)
 #   ab:<opt>=<v0>,<v1>[,...]   interleaved same-box A/B of one lt_set_option knob, 2 rounds  -> ab_<opt>.log
 #   ablib:<path>[,<path>...]   interleaved A/B of the default and other builds of the library (LUMINA_DIT_LIB)  -> ab_lib.log
 #   configs:<names>            scripts/bench_configs.py <names: cfg1 cfg3 cfg4 cfg5, space separated by '+'>
@@ -46,15 +46,15 @@ for step in "$@"; do
       echo "pytest exit $?"; tail -8 $OUT/pytest_gpu.log; grep -E "engine vs reference|routing" $OUT/pytest_gpu.log | cut -c1-330 ;;
     bench)
       n=$(ls $OUT/bench*.json 2>/dev/null | wc -l)
-      timeout 900 python bench.py $arg > $OUT/bench$n.json 2> $OUT/bench$n.err; echo "bench exit $?"; digest $OUT/bench$n.json "bench $arg" ;;
+      timeout 900 python bench.py --full $arg > $OUT/bench$n.json 2> $OUT/bench$n.err; echo "bench exit $?"; digest $OUT/bench$n.json "bench $arg" ;;
     ab)
       opt=${arg%%=*}; vals=${arg#*=}
       for i in 1 2; do for v in ${vals//,/ }; do
-        timeout 600 python bench.py --no-cpu-baseline --opt $opt=$v > $OUT/ab.tmp 2>/dev/null; digest $OUT/ab.tmp "$opt=$v" | tee -a $OUT/ab_$opt.log
+        timeout 600 python bench.py --full --no-cpu-baseline --opt $opt=$v > $OUT/ab.tmp 2>/dev/null; digest $OUT/ab.tmp "$opt=$v" | tee -a $OUT/ab_$opt.log
       done; done ;;
     ablib)
       for i in 1 2; do for lib in "" ${arg//,/ }; do
-        LUMINA_DIT_LIB=$lib timeout 600 python bench.py --no-cpu-baseline > $OUT/ab.tmp 2>/dev/null; digest $OUT/ab.tmp "lib=${lib:-default}" | tee -a $OUT/ab_lib.log
+        LUMINA_DIT_LIB=$lib timeout 600 python bench.py --full --no-cpu-baseline > $OUT/ab.tmp 2>/dev/null; digest $OUT/ab.tmp "lib=${lib:-default}" | tee -a $OUT/ab_lib.log
       done; done ;;
     configs) timeout 1200 python scripts/bench_configs.py $arg > $OUT/bench_configs.log 2>&1; echo "exit $?"; tail -12 $OUT/bench_configs.log ;;
     opbench) timeout 1200 python scripts/opbench.py $arg > $OUT/opbench_$(echo $arg | tr ' /' '__' | cut -c1-60).log 2>&1; echo "exit $?"; tail -30 $OUT/opbench_*.log | cut -c1-220 ;;

@@ -11,5 +11,5 @@ bash scripts/gpu_trace_wall.sh cfg1 cfg5 2>&1 | tail -30 | cut -c1-200; cp -r gp
 PMC_OUT=$OUT/pmc_w13_pd3 PMC_PASSES="p1 p4 p6" LT_PMC_VENDOR=1 bash scripts/gpu_pmc_gemm_stalls.sh; cat $OUT/pmc_w13_pd3/summary.txt | cut -c1-400
 LUMINA_DIT_LIB=$R/lumina-t2x_amd/lib/pd4/liblumina_dit.so PMC_OUT=$OUT/pmc_w13_pd4 PMC_PASSES="p1 p4 p6" LT_PMC_VENDOR=0 bash scripts/gpu_pmc_gemm_stalls.sh; cat $OUT/pmc_w13_pd4/summary.txt | cut -c1-400
 LT_PMC_SHAPE=8192,2304,2304,16 PMC_OUT=$OUT/pmc_o_pd3 PMC_PASSES="p1 p4 p6" LT_PMC_VENDOR=0 bash scripts/gpu_pmc_gemm_stalls.sh; cat $OUT/pmc_o_pd3/summary.txt | cut -c1-400
-timeout 900 python bench.py > $OUT/bench_full.json 2> $OUT/bench_full.err; echo "bench exit $?"; cut -c1-600 $OUT/bench_full.json
+timeout 900 python bench.py --full > $OUT/bench_full.json 2> $OUT/bench_full.err; echo "bench exit $?"; cut -c1-600 $OUT/bench_full.json
 du -sh $OUT

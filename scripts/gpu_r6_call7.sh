@@ -9,7 +9,7 @@ PL=$R/lumina-t2x_amd/lib/pl/liblumina_dit.so
 for i in 1 2; do for lib in "" $PL; do echo "lib=${lib:-default}"; LUMINA_DIT_LIB=$lib timeout 600 python scripts/opbench.py gemm --gemm-variants 0 --rounds 7 2>&1 | grep -E "^gemm" | cut -c1-120; done; done | tee $OUT/opbench_pairline.log
 timeout 600 python scripts/opbench.py gemm_vendor --rounds 7 2>&1 | grep vendor-cmp | cut -c1-140 | tee $OUT/opbench_vendor.log
 for i in 1 2; do for lib in "" $PL; do
-  LUMINA_DIT_LIB=$lib timeout 600 python bench.py --no-cpu-baseline > $OUT/ab.tmp 2>$OUT/ab.err; python - $OUT/ab.tmp "lib=${lib:-default}" <<'PY'
+  LUMINA_DIT_LIB=$lib timeout 600 python bench.py --full --no-cpu-baseline > $OUT/ab.tmp 2>$OUT/ab.err; python - $OUT/ab.tmp "lib=${lib:-default}" <<'PY'
 import json, sys
 try:
     d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$R/gpurun_out/r6/call8; mkdir -p $OUT
 cd $R
 timeout 1500 python -m pytest tests/test_gpu_ops.py tests/test_gpu_model.py -m gpu -q -x -k "pair or path_switches or full_width" > $OUT/pytest_pair.log 2>&1; echo "pytest exit $?"; tail -15 $OUT/pytest_pair.log
-for i in 1 2; do for v in 0 1; do timeout 600 python bench.py --no-cpu-baseline --opt pair_layout=$v > $OUT/ab.tmp 2>$OUT/ab.err; python - $OUT/ab.tmp "pair_layout=$v" <<'PY'
+for i in 1 2; do for v in 0 1; do timeout 600 python bench.py --full --no-cpu-baseline --opt pair_layout=$v > $OUT/ab.tmp 2>$OUT/ab.err; python - $OUT/ab.tmp "pair_layout=$v" <<'PY'
 import json, sys
 try:
     d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
