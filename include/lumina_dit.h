@@ -323,6 +323,11 @@ int lt_op_attention(const void* q_dev, const void* k_dev, const void* vt_dev, co
                     void* out_dev, const void* gate_dev, int32_t accumulate, int32_t B, int32_t H,
                     int32_t Hkv, int32_t N, int32_t Nk, int32_t Nkpad, int32_t hd, float scale,
                     int32_t k_prescaled, void* stream);
+/* name of the kernel lt_op_attention would launch for these arguments under the current options (has_bias: bias_dev != NULL), "none" when
+ * no kernel is built for them.  head_dim 128: "attn_fwd_kernel_hd128" for whole 64-key tiles without bias / accumulate (Nk % 64 == 0, Nk == Nkpad),
+ * "attn_fwd_kernel<128>" otherwise. */
+int lt_op_attention_describe(int32_t has_bias, int32_t accumulate, int32_t B, int32_t H, int32_t Hkv, int32_t N, int32_t Nk, int32_t Nkpad,
+                             int32_t hd, char* out, int32_t cap);
 /* The two launches of a layer of the class-conditional 600M models at <= 512 tokens (round 5, option attn_small_fused): the QKV
  * projection on the small-M GEMM tiles, whose epilogue also leaves per-row (sum, sum of squares) of every 128-column tile in
  * rowstat_ws ([M][ceil(3 widths / 128)] float2), then ONE kernel that does q_norm / k_norm (affine LayerNorm over the full width, fp32),

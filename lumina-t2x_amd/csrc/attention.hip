@@ -1,4 +1,4 @@
-// Non-causal flash attention for gfx950, head_dim 48 / 72 / 96 (Next-DiT 600M / 2B, Flag-DiT 5B).
+// Non-causal flash attention for gfx950, head_dim 48 / 72 / 96 / 128 (Next-DiT 600M / 2B, Flag-DiT 5B, the 7B models).
 //
 // Replaces flash_attn_varlen_func on the all-ones mask (lumina_next_t2i/models/model.py:378-405; the
 // unpad/pad gathers are identities in sampling, model.py:781) and, in accumulate mode, the zero-init
@@ -22,7 +22,8 @@
 
 namespace {
 
-// ---- v1: straightforward online softmax (kept for A/B and as the fallback for head_dim % 32 == 0) -------
+// ---- v1: straightforward online softmax (kept for A/B and as the fallback for head_dim % 32 == 0: hd 96 with a key bias, and the
+//      general path of hd 128 - key bias, partial last tile, accumulate, per-sample key counts; whole tiles go to attention_hd128.hip) -------
 template <int HD>
 __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnArgs p) {
     constexpr int KS = (HD + 15) / 16;   // QK^T k-steps
@@ -78,7 +79,10 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnArgs p) {
         for (int i = 0; i < (CPR + 3) / 4; ++i) {
             const int j = wave + 4 * i;
             if (j < CPR) {
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rK, LDS_PTR(kb + j * 1024), 16, j * 1024 + lane * 16, k0 * HD * 2, 0, 0);
+                // hd 128: K rows are 256 bytes = all 64 banks, so chunk c of row r lives at position c ^ (r & 15); the LDS image of a DMA is
+                // lane-linear, so the swizzle goes on the per-lane SOURCE address (position 64 j + lane = row 4 j + lane / 16, position lane % 16)
+                const int ksrc = (HD == 128) ? (4 * j + (lane >> 4)) * 256 + (((lane & 15) ^ ((4 * j + (lane >> 4)) & 15)) << 4) : j * 1024 + lane * 16;
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rK, LDS_PTR(kb + j * 1024), 16, ksrc, k0 * HD * 2, 0, 0);
                 const int d = 8 * j + (lane >> 3);
                 const int sc = (lane & 7) ^ ((d >> 1) & 7);
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(rV, LDS_PTR(vb + j * 1024), 16, d * p.Nkpad * 2 + sc * 16, k0 * 2, 0, 0);
@@ -92,7 +96,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnArgs p) {
     for (int s = 0; s < KS; ++s) {
         int ch = 2 * s + hi;
         if (ch > CPR - 1) ch = CPR - 1;  // hd=72: pad chunk re-reads valid data, multiplied by Q's zero tail
-        koff[s] = l31 * HD * 2 + ch * 16;
+        koff[s] = l31 * HD * 2 + ((HD == 128 ? ch ^ (l31 & 15) : ch) << 4);  // (rows 32 apart share l31 & 15: one offset serves both sub-tiles)
     }
     int voff[DT][4];
 #pragma unroll
@@ -974,7 +978,8 @@ bool attention_takes_raw_q(const AttnArgs& a) {
 }
 
 // launch_attention would run this call on one of the one-wave-per-SIMD kernels (hd 72 / 48 / 96: the ones that can write their output in the
-// pair layout, AttnArgs::out_pair) - the same expressions as the dispatch below
+// pair layout, AttnArgs::out_pair) - the same expressions as the dispatch below.  hd 128 is not among them: attention_hd128.hip's kernel
+// (two waves per SIMD) writes row-major rows, so the 7B's dense block keeps row-major GEMM operands (run_forward's `pair` stays false)
 bool attention_is_one_wave(const AttnArgs& a) {
     const int g_attn_variant = lt_opt(OPT_ATTENTION_VARIANT);
     if (g_attn_variant >= 4 && a.hd == 72 && a.bias == nullptr && !a.accumulate && !a.nk_batch && a.Nk % 64 == 0 && (!a.tk || a.Tkpad <= 256)) return true;
@@ -1018,6 +1023,8 @@ int launch_attention(const AttnArgs& a, hipStream_t stream) {
     if (g_attn_variant >= 4 && a.hd == 96 && a.bias == nullptr && !a.accumulate && !a.nk_batch && !a.trace && a.Nk % 64 == 0 && a.Nk == a.Nkpad &&
         (!a.tk || (a.Tkpad <= 256 && a.Tkpad % 64 == 0)))
         return launch_attention_v4_hd96(a, stream);
+    // head_dim 128 (the 7B models), whole tiles: attention_hd128.hip; everything else at this head dim falls to attn_fwd_kernel<128> below
+    if (attention_takes_hd128_fast(a)) return launch_attention_hd128(a, stream);
     if (g_attn_variant >= 3 && (a.hd == 72 || a.hd == 96) && a.bias == nullptr && !a.accumulate) {
         constexpr int SMEM72 = 4 * (72 * 128 + 128) + 4 * (64 * 72 * 2) + 16, SMEM96 = 4 * (96 * 128) + 4 * (64 * 96 * 2) + 16;
         if (ensure_dynamic_lds((const void*)attn_fwd_kernel_v3<72>, SMEM72) || ensure_dynamic_lds((const void*)attn_fwd_kernel_v3<96>, SMEM96)) return 1;
@@ -1045,10 +1052,29 @@ int launch_attention(const AttnArgs& a, hipStream_t stream) {
         case 48: if (v2) LAUNCH_V2(48); else LAUNCH_V1(48); break;
         case 72: if (v2) LAUNCH_V2(72); else LAUNCH_V1(72); break;
         case 96: LAUNCH_V1(96); break;
-        default: lt_set_error("attention: head_dim %d not built (48, 72, 96)", a.hd); return 2;
+        case 128:  // exactly 64 KiB of dynamic LDS
+            if (ensure_dynamic_lds((const void*)attn_fwd_kernel<128>, 2 * (64 * 128 * 2) + 2 * (128 * 128))) return 1;
+            LAUNCH_V1(128);
+            break;
+        default: lt_set_error("attention: head_dim %d not built (48, 72, 96, 128)", a.hd); return 2;
     }
 #undef LAUNCH_V1
 #undef LAUNCH_V2
     LT_CHECK_HIP(hipGetLastError());
     return 0;
+}
+
+// name of the kernel launch_attention() would launch for `a` under the current options: the dispatch above, expression by expression
+const char* attention_describe(const AttnArgs& a) {
+    const int g_attn_variant = lt_opt(OPT_ATTENTION_VARIANT);
+    if (a.hd != 48 && a.hd != 72 && a.hd != 96 && a.hd != 128) return "none";
+    if (g_attn_variant >= 4 && a.hd == 72 && a.bias == nullptr && !a.accumulate && !a.nk_batch && a.Nk % 64 == 0 && (!a.tk || a.Tkpad <= 256)) return "attn_fwd_kernel_v4<72>";
+    if (attention_is_one_wave(a)) return a.hd == 48 ? "attn_fwd_kernel_v4h48" : "attn_fwd_kernel_v4h96";
+    if (attention_takes_hd128_fast(a)) return "attn_fwd_kernel_hd128";
+    if (g_attn_variant >= 3 && (a.hd == 72 || a.hd == 96) && a.bias == nullptr && !a.accumulate) return a.hd == 72 ? "attn_fwd_kernel_v3<72>" : "attn_fwd_kernel_v3<96>";
+    if (a.tk) return "none";
+    if (a.hd == 96) return "attn_fwd_kernel<96>";
+    if (a.hd == 128) return "attn_fwd_kernel<128>";
+    if (g_attn_variant >= 2) return a.hd == 48 ? "attn_fwd_kernel_v2<48>" : "attn_fwd_kernel_v2<72>";
+    return a.hd == 48 ? "attn_fwd_kernel<48>" : "attn_fwd_kernel<72>";
 }

@@ -1041,7 +1041,10 @@ extern "C" int lt_create(const lt_config* cfg, lt_engine** out) {
     LT_REQUIRE(cfg->dim % cfg->n_heads == 0, "dim %% n_heads != 0");
     LT_REQUIRE(cfg->n_heads % cfg->n_kv_heads == 0, "n_heads %% n_kv_heads != 0");
     const int hd = cfg->dim / cfg->n_heads;
-    LT_REQUIRE(hd == 48 || hd == 72 || hd == 96, "head_dim %d not built (48, 72, 96)", hd);
+    LT_REQUIRE(hd == 48 || hd == 72 || hd == 96 || hd == 128, "head_dim %d not built (48, 72, 96, 128)", hd);
+    // hd 128 = the 7B factories of the class-conditional and MoE families; no reference model pairs it with a text branch, the attention
+    // kernels have no text phase at this head dim and there is no fixture to hold one to
+    LT_REQUIRE(hd != 128 || !vd.text, "head_dim 128 with text cross-attention not built (the class-conditional and MoE variants run at head_dim 128)");
     LT_REQUIRE(cfg->dim % 64 == 0 && cfg->ffn_hidden % 64 == 0, "dim and ffn_hidden must be multiples of 64");
     LT_REQUIRE(!vd.text || (cfg->cap_feat_dim % 64 == 0 && cfg->cap_feat_dim > 0), "cap_feat_dim must be a positive multiple of 64");
     LT_REQUIRE(!vd.labels || cfg->num_classes > 0, "class-conditional variant needs num_classes > 0");
@@ -1944,6 +1947,16 @@ extern "C" int lt_op_attention(const void* q, const void* k, const void* vt, con
     a.gate = (const u16*)gate; a.accumulate = accumulate; a.B = B; a.H = H; a.Hkv = Hkv; a.N = N; a.Nk = Nk;
     a.Nkpad = Nkpad; a.hd = hd; a.scale = scale; a.k_prescaled = k_prescaled;
     return launch_attention(a, (hipStream_t)stream);
+}
+
+extern "C" int lt_op_attention_describe(int32_t has_bias, int32_t accumulate, int32_t B, int32_t H, int32_t Hkv, int32_t N, int32_t Nk, int32_t Nkpad,
+                                        int32_t hd, char* out, int32_t cap) {
+    LT_REQUIRE(out && cap > 0, "lt_op_attention_describe: null buffer");
+    AttnArgs a;
+    a.q = nullptr; a.k = nullptr; a.vt = nullptr; a.bias = has_bias ? (const float*)out : nullptr; a.out = nullptr; a.gate = nullptr;  // (bias: only its nullness is looked at)
+    a.accumulate = accumulate; a.B = B; a.H = H; a.Hkv = Hkv; a.N = N; a.Nk = Nk; a.Nkpad = Nkpad; a.hd = hd; a.scale = 1.f;
+    snprintf(out, (size_t)cap, "%s", attention_describe(a));
+    return 0;
 }
 
 // self-attention whose queries come straight from the QKV projection (AttnArgs::q_raw): q_norm + 2-D RoPE in the kernel's prologue

@@ -263,8 +263,11 @@ int launch_attention_small(const AttnSmallArgs& a, hipStream_t stream);
 int launch_attention_v4(const AttnArgs& a, hipStream_t stream);  // hd 72, 4 waves x 64 query rows (attention_v4.hip)
 int launch_attention_v4_hd48(const AttnArgs& a, hipStream_t stream);  // hd 48, the same structure, softmax-bound (attention_v4_48.hip)
 int launch_attention_v4_hd96(const AttnArgs& a, hipStream_t stream);  // hd 96, the same structure without pad slots (attention_v4_96.hip)
+int launch_attention_hd128(const AttnArgs& a, hipStream_t stream);  // hd 128, whole 64-key tiles: 8 waves x 32 query rows, two-group ping-pong in plain HIP (attention_hd128.hip)
+bool attention_takes_hd128_fast(const AttnArgs& a);  // launch_attention would run this call on attention_hd128.hip's kernel (else hd 128 runs attn_fwd_kernel<128>)
+const char* attention_describe(const AttnArgs& a);  // name of the kernel launch_attention would launch (the same expressions as its dispatch), or "none"
 size_t attention_tail_ws_floats(int heads, int parts, int rows);  // AttnArgs::tail_ws of launch_attention_v4_hd96's tail split, in floats
-bool attention_is_one_wave(const AttnArgs& a);  // launch_attention would run this call on a one-wave-per-SIMD kernel (hd 72 / 48 / 96): these write AttnArgs::out_pair
+bool attention_is_one_wave(const AttnArgs& a);  // launch_attention would run this call on a one-wave-per-SIMD kernel (hd 72 / 48 / 96): these write AttnArgs::out_pair.  False at hd 128: its whole-tile kernel writes row-major rows only
 bool attention_takes_raw_q(const AttnArgs& a);  // launch_attention would run this call on attn_fwd_kernel_v4<72> (the kernel with the q_raw prologue)
 bool attention_fuses_text(int hd);  // hd-72 ping-pong kernel: text cross-attention rides in the self-attention launch
 int ensure_dynamic_lds(const void* fn, int bytes);  // hipFuncSetAttribute(MaxDynamicSharedMemorySize) per (device, kernel), raised whenever a larger size is asked for; records the pair only on success

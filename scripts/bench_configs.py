@@ -9,6 +9,7 @@ cfg3  Flag-DiT 5B (lumina_t2i), 1024x1024 (64 x 65 tokens incl. eol), text T=128
 cfg4  Next-DiT 2B GQA, 2048x2048 (16384 tokens), time-aware scaling 2.0 / watershed 0.3, proportional attention
 cfg5  Next-DiT-MoE 600M "Both" (4 time + 4 space experts, top-2), 256x256
 cfg5-1024  the same model at BASELINE configs[4]'s stated 1024x1024: 4096 tokens, 8192 rows, 16 384 routed rows per MoE FFN
+7b-256 / 7b-1024  Next-DiT-ImageNet 7B (dim 4096, 32 heads = head_dim 128, 32 layers), 256 / 1024 tokens, class-conditional CFG pair
 Synthetic weights drawn on the GPU (SURVEY.md 8d statistics), inputs resident in HBM, wall clock around the sampler call.
 """
 import argparse
@@ -95,6 +96,17 @@ def main():
             ms = timed(m.eval(), z, a.nfe, 2, y=y, cfg_scale=4.0)
             fl = flops_per_nfe(dim=1536, n_layers=16, n_heads=32, n_tokens=4096, batch=2, adaln_chunks=6, ffn_visits=4)
             toks = 4096
+        elif which in ("7b-256", "7b-1024"):
+            # Next-DiT-ImageNet DiT_Llama_7B_patch2 (dim 4096, 32 heads: head_dim 128, ffn 11008), class-conditional CFG pair
+            toks = 256 if which == "7b-256" else 1024
+            side = 32 if toks == 256 else 64
+            with torch.device(dev):
+                m = models.imagenet.DiT_Llama_7B_patch2(qk_norm=True).to(torch.bfloat16)
+            random_init_(m, 0)
+            z = torch.randn(1, 4, side, side, device=dev, generator=g).to(torch.bfloat16).repeat(2, 1, 1, 1)
+            y = torch.tensor([207, 1000], device=dev)
+            ms = timed(m.eval(), z, a.nfe, 2, y=y, cfg_scale=4.0)
+            fl = flops_per_nfe(dim=4096, n_layers=32, n_heads=32, n_tokens=toks, batch=2)
         elif which == "cfg4":
             with torch.device(dev):
                 m = models.NextDiT_2B_GQA_patch2(qk_norm=True, cap_feat_dim=2048).to(torch.bfloat16)

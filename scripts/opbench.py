@@ -168,7 +168,7 @@ def bench_attn(rounds, variants, shape=(2, 32, 4096, 72)):
     ok(L.lt_op_qk_norm_rope(P(qkv), 3 * H * hd, H * hd, P(None), P(None), C.c_float(1e-5), P(k), B, N, H, hd, 0, P(None), 64, 1.0, stream()))
     ok(L.lt_op_v_transpose(P(qkv), 3 * H * hd, 2 * H * hd, P(vt), B, N, N, H, hd, stream()))
     scale = 1.0 / math.sqrt(hd)
-    variants = [v for v in variants if not (hd == 96 and v == 2)]  # v2 needs a spare O^T row (hd % 32 != 0)
+    variants = [v for v in variants if not (hd % 32 == 0 and v == 2)]  # v2 needs a spare O^T row (hd % 32 != 0)
     outs, cases = {}, {}
     for v in variants:
         out = torch.empty(B, N, H * hd, device="cuda", dtype=torch.bfloat16)
@@ -332,6 +332,8 @@ if __name__ == "__main__":
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--gemm-variants", type=str, default="1,2,3,4")
     ap.add_argument("--attn-variants", type=str, default="1,2")
+    ap.add_argument("--attn-shape", type=str, default="2,32,4096,72", help="attn: B,H,N,hd; several shapes separated by ':' run one after the other "
+                    "(e.g. 2,32,1024,96:2,32,1024,128 - hd 128: variant 1 = the general kernel, 4 = the whole-tile kernel)")
     ap.add_argument("--cold", type=int, default=0, help="gemm_small: rotate through this many weight copies (HBM-cold weights)")
     ap.add_argument("--gemm-zeros", action="store_true", help="all-zero operands (power / clock probe)")
     ap.add_argument("--gemm-stagger", type=int, default=0, help="4-wave GEMM kernels (variants 10, 13, 14): start-phase spread per XCD in "
@@ -355,7 +357,8 @@ if __name__ == "__main__":
     if "insitu" in a.what:
         bench_insitu(a.rounds)
     if "attn" in a.what:
-        bench_attn(a.rounds, [int(v) for v in a.attn_variants.split(",")])
+        for shp in a.attn_shape.split(":"):
+            bench_attn(a.rounds, [int(v) for v in a.attn_variants.split(",")], shape=tuple(int(v) for v in shp.split(",")))
     if "gemm_probe" in a.what:  # per-tile fixed cost vs per-slab cost: same N, two K; plain vs SwiGLU epilogue on the same shape
         probe = [("n12k_k2304_e0", 8192, 12288, 2304, 0), ("n12k_k2304_e1", 8192, 12288, 2304, 1), ("n12k_k4608_e0", 8192, 12288, 4608, 0),
                  ("n12k_k4608_e1", 8192, 12288, 4608, 1), ("n6912_k2304", 8192, 6912, 2304, 0), ("n6912_k4608", 8192, 6912, 4608, 0),
