@@ -158,7 +158,25 @@ int lt_sample_ode(lt_engine* e, const void* z_dev, void* traj_dev, void* final_d
                   const float* tgrid_host, int32_t n_grid, int32_t method, int32_t use_cfg,
                   int32_t t_round_to_state_dtype, const lt_step_args* a, void* stream);
 
-/* number of model evaluations issued by the last lt_sample_ode call */
+/* ---- multi-view (visual-anagram) sampling: visual_anagrams/generate.py:389-414, Phase Init ------------------------------------------
+ * ONE latent; per time interval every view v sees view_v(latent) with its own prompt, takes one ODE step of forward_with_cfg, and the mean
+ * over the views of inverse_view_v(-increment) is subtracted from the latent.  A view is data: view_v(x)[c, i] = vsign[v][c] * x[c, perm[v][i]],
+ * inverse_view_v(n)[c, i] = isign[v][c] * n[c, iperm[v][i]] over the H*W pixels of a channel.
+ * lt_set_views: perm_dev int32 [V][latent_h * latent_w] (device), vsign_host / isign_host float [V][in_channels] of +-1 (host).  The tables
+ * are copied into engine-owned memory, iperm is built on the device and the call SYNCHRONISES the stream to report a table that is not a
+ * bijection.  Refused: V < 1, 2 V > max_batch, a latent that is not a multiple of the patch size or exceeds max_tokens, any variant other
+ * than LT_VARIANT_NEXT_T2I.  V = 0 (perm_dev NULL) drops the tables.
+ * lt_sample_views: z [1, C, H, W]; traj_dev (may be NULL) receives the n_grid latents [n_grid, C, H, W], final_dev (may be NULL) the last.
+ * The prompt was prepared with lt_prepare_prompt at B = 2 V: rows 0..V-1 the view prompts, rows V..2V-1 the negative prompt; a->batch = 2 V
+ * and a->latent_h / latent_w equal the tables'.  method LT_ODE_MIDPOINT (the reference's midpoint_solver, generate.py:212-219) or LT_ODE_EULER
+ * (one stage: the increment is f(t0) dt); LT_ODE_RK4 is refused.  Every stage is ONE forward_with_cfg of 2 V rows (lt_last_nfe: 2 per
+ * interval for midpoint).  dt and dt / 2 multiply in fp32 (Python floats in the reference), t is fp32.  No synchronisation, no host read. */
+int lt_set_views(lt_engine* e, const int32_t* perm_dev, const float* vsign_host, const float* isign_host, int32_t V, int32_t latent_h,
+                 int32_t latent_w, void* stream);
+int lt_sample_views(lt_engine* e, const void* z_dev, void* traj_dev, void* final_dev, const float* tgrid_host, int32_t n_grid,
+                    int32_t method, const lt_step_args* a, void* stream);
+
+/* number of model evaluations issued by the last lt_sample_ode / lt_sample_views call */
 int64_t lt_last_nfe(lt_engine* e);
 /* model evaluations served by replaying a captured HIP graph since lt_create (0 with lt_set_option("graph", 0), and below 1025 rows under the default "graph" 2) */
 int64_t lt_graph_replays(lt_engine* e);
@@ -347,6 +365,17 @@ int lt_op_attention_fused(const void* q_dev, const void* k_dev, const void* vt_d
                           const void* tvt_dev, const float* tbias_dev, const void* tgate_dev, void* out_dev, int32_t B,
                           int32_t H, int32_t Hkv, int32_t N, int32_t Nk, int32_t Nkpad, int32_t Tk, int32_t Tkpad,
                           int32_t hd, void* stream);
+/* the three kernels of lt_sample_views on caller-owned buffers.  perm / iperm int32 [V][HW], vsign / isign float [V][C] (DEVICE here),
+ * HW = H * W (gather / reduce: a multiple of 4), dtype LT_F32 or LT_BF16.  Indices are clamped into [0, HW) before use.
+ *   invert: iperm from perm; hits int32 [V * HW + 1] (zeroed by the call) counts the hits per target, its last word the entries that are
+ *           out of range or name a target twice: 0 <=> every perm[v] is a bijection
+ *   gather: out [V, C, HW] = view_v(y [C, HW]); f0 [V, C, HW] != NULL: the midpoint stage R(view_v(y) + R(f0 * half_dt)) (R: round to dtype)
+ *   reduce: out [C, HW] = R(y - R((sum_v inverse_view_v(-R(f [V, C, HW] * dt))) / V)), fp32 sum in view order */
+int lt_op_views_invert(const int32_t* perm_dev, int32_t* iperm_dev, int32_t* hits_dev, int32_t V, int32_t HW, void* stream);
+int lt_op_views_gather(const void* y_dev, const int32_t* perm_dev, const float* vsign_dev, const void* f0_dev, void* out_dev, float half_dt,
+                       int32_t V, int32_t C, int32_t HW, int32_t dtype, void* stream);
+int lt_op_views_reduce(const void* y_dev, const void* f_dev, const int32_t* iperm_dev, const float* isign_dev, void* out_dev, float dt,
+                       int32_t V, int32_t C, int32_t HW, int32_t dtype, void* stream);
 /* y[m,n] = sum_k act(a[m,k]) w[n,k] + b[n], m < M <= 8 (GEMV-style; adaLN / embedders).
  * act_in 0 none, 1 SiLU.  a bf16 [M,K], w bf16 [N,K], b bf16 [N] or NULL, y bf16 [M,N]. */
 int lt_op_linear_small_m(const void* a_dev, const void* w_dev, const void* b_dev, void* y_dev,

@@ -83,6 +83,8 @@ _SIGNATURES: Dict[str, tuple] = {
     "lt_forward_packed": (_i32, [_vp, C.POINTER(_vp), C.POINTER(_i32), _vp, C.POINTER(_vp), C.POINTER(LtStepArgs), _vp]),
     "lt_forward_cfg": (_i32, [_vp, _vp, _vp, _vp, C.POINTER(LtStepArgs), _vp]),
     "lt_sample_ode": (_i32, [_vp, _vp, _vp, _vp, C.POINTER(_f32), _i32, _i32, _i32, _i32, C.POINTER(LtStepArgs), _vp]),
+    "lt_set_views": (_i32, [_vp, _vp, C.POINTER(_f32), C.POINTER(_f32), _i32, _i32, _i32, _vp]),
+    "lt_sample_views": (_i32, [_vp, _vp, _vp, _vp, C.POINTER(_f32), _i32, _i32, C.POINTER(LtStepArgs), _vp]),
     "lt_last_nfe": (_i64, [_vp]),
     "lt_graph_replays": (_i64, [_vp]),
     "lt_moe_routing_record": (_i32, [_vp, _i32]),
@@ -118,6 +120,9 @@ _SIGNATURES: Dict[str, tuple] = {
     "lt_op_attention_describe": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, C.c_char_p, _i32]),
     "lt_op_attention_fused": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "lt_op_attention_trace": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp]),
+    "lt_op_views_invert": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp]),
+    "lt_op_views_gather": (_i32, [_vp, _vp, _vp, _vp, _vp, _f32, _i32, _i32, _i32, _i32, _vp]),
+    "lt_op_views_reduce": (_i32, [_vp, _vp, _vp, _vp, _vp, _f32, _i32, _i32, _i32, _i32, _vp]),
     "lt_op_linear_small_m": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "lt_op_rope_table_2d": (_i32, [_vp, _i32, _i32, _f32, _f32, _vp]),
     "lt_op_rope_table_2d_pair": (_i32, [_vp, _vp, _i32, _i32, _f32, _f32, _vp]),

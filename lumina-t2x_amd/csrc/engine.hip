@@ -186,6 +186,10 @@ struct lt_engine {
     int* pk_dev = nullptr;     // packed batches: [0,64) token counts, [64,128) grid widths
     int pk_host[128] = {0};
     long long last_nfe = 0;
+    // multi-view sampling (lt_set_views / lt_sample_views, views.hip): engine-owned tables of the V views over an h x w latent
+    int *vw_perm = nullptr, *vw_iperm = nullptr, *vw_hits = nullptr;  // [V][h w], [V][h w], [V h w + 1]
+    float *vw_vsign = nullptr, *vw_isign = nullptr;                   // [V][in_channels]
+    int vw_V = 0, vw_h = 0, vw_w = 0;
     // HIP graphs of one model evaluation (forward_graphed): fixed staging buffers the captured kernels read / write, a private
     // stream to capture on (the caller's stream may be the legacy null stream, which cannot capture), cached executables
     struct GraphTally { double flops[3] = {0, 0, 0}; long long launches[3] = {0, 0, 0}; };  // what one replay stands for, per kernel class
@@ -1241,6 +1245,17 @@ extern "C" int lt_create(const lt_config* cfg, lt_engine** out) {
     return 0;
 }
 
+static void drop_views(lt_engine* e) {
+    if (e->vw_perm) (void)hipFree(e->vw_perm);
+    if (e->vw_iperm) (void)hipFree(e->vw_iperm);
+    if (e->vw_hits) (void)hipFree(e->vw_hits);
+    if (e->vw_vsign) (void)hipFree(e->vw_vsign);
+    if (e->vw_isign) (void)hipFree(e->vw_isign);
+    e->vw_perm = e->vw_iperm = e->vw_hits = nullptr;
+    e->vw_vsign = e->vw_isign = nullptr;
+    e->vw_V = e->vw_h = e->vw_w = 0;
+}
+
 extern "C" void lt_destroy(lt_engine* e) {
     if (!e) return;
     for (auto& ge : e->graphs) if (ge.exec) (void)hipGraphExecDestroy(ge.exec);
@@ -1252,6 +1267,7 @@ extern "C" void lt_destroy(lt_engine* e) {
     if (e->pk_dev) (void)hipFree(e->pk_dev);
     if (e->reg_txt) (void)hipFree(e->reg_txt);
     if (e->reg_qmap) (void)hipFree(e->reg_qmap);
+    drop_views(e);
     if (e->moe_rec) (void)hipFree(e->moe_rec);
     if (e->moe_force) (void)hipFree(e->moe_force);
     for (int k = 0; k < 3; ++k)
@@ -1512,6 +1528,151 @@ extern "C" int lt_sample_ode(lt_engine* e, const void* z_dev, void* traj_dev, vo
     if (final_dev) LT_CHECK_HIP(hipMemcpyAsync(final_dev, e->ys[cur], sbytes, hipMemcpyDeviceToDevice, s));
     e->last_nfe = nfe;
     return 0;
+}
+
+// ---- multi-view (visual-anagram) sampling ------------------------------------------------------------------------------------------
+extern "C" int lt_set_views(lt_engine* e, const int32_t* perm_dev, const float* vsign_host, const float* isign_host, int32_t V, int32_t latent_h,
+                            int32_t latent_w, void* stream) {
+    LT_REQUIRE(e, "lt_set_views: null engine");
+    hipStream_t s = (hipStream_t)stream;
+    const lt_config& c = e->cfg;
+    LT_REQUIRE(c.variant == LT_VARIANT_NEXT_T2I, "lt_set_views: multi-view sampling drives the text-conditional Next-DiT (LT_VARIANT_NEXT_T2I) only; "
+               "this engine is variant %d", c.variant);
+    if (V == 0 && !perm_dev) {  // drop the tables (kernels of an earlier trajectory may still read them)
+        LT_CHECK_HIP(hipStreamSynchronize(s));
+        drop_views(e);
+        return 0;
+    }
+    LT_REQUIRE(perm_dev && vsign_host && isign_host, "lt_set_views: null argument");
+    LT_REQUIRE(V >= 1, "lt_set_views: V = %d views (need at least 1)", V);
+    LT_REQUIRE(2 * (long long)V <= c.max_batch, "lt_set_views: %d views need a batch of 2 V = %d rows (view prompts + negative prompts), max_batch is %d", V,
+               2 * V, c.max_batch);
+    LT_REQUIRE(latent_h > 0 && latent_w > 0 && latent_h % c.patch_size == 0 && latent_w % c.patch_size == 0 &&
+                   (long long)(latent_h / c.patch_size) * (latent_w / c.patch_size) <= c.max_tokens,
+               "lt_set_views: latent %dx%d is not a positive multiple of the patch size %d or exceeds max_tokens %d x patch_size^2", latent_h, latent_w,
+               c.patch_size, c.max_tokens);
+    const int C = c.in_channels, HW = latent_h * latent_w;
+    LT_REQUIRE(HW % 4 == 0, "lt_set_views: H * W = %d must be a multiple of 4", HW);
+    for (int i = 0; i < V * C; ++i)
+        LT_REQUIRE((vsign_host[i] == 1.f || vsign_host[i] == -1.f) && (isign_host[i] == 1.f || isign_host[i] == -1.f),
+                   "lt_set_views: sign of view %d, channel %d is not +1 / -1", i / C, i % C);
+    LT_CHECK_HIP(hipStreamSynchronize(s));  // table upload may synchronise; kernels of an earlier trajectory may still read the old tables
+    drop_views(e);
+    const size_t tb = (size_t)V * HW * sizeof(int);
+    auto fail = [&]() { drop_views(e); return 1; };
+    if (hipMalloc((void**)&e->vw_perm, tb) != hipSuccess || hipMalloc((void**)&e->vw_iperm, tb) != hipSuccess ||
+        hipMalloc((void**)&e->vw_hits, tb + sizeof(int)) != hipSuccess || hipMalloc((void**)&e->vw_vsign, (size_t)V * C * sizeof(float)) != hipSuccess ||
+        hipMalloc((void**)&e->vw_isign, (size_t)V * C * sizeof(float)) != hipSuccess) {
+        lt_set_error("lt_set_views: out of device memory for the tables of %d views of %d pixels", V, HW);
+        return fail();
+    }
+    int bad = -1;
+    if (hipMemcpyAsync(e->vw_perm, perm_dev, tb, hipMemcpyDeviceToDevice, s) != hipSuccess ||
+        hipMemsetAsync(e->vw_iperm, 0, tb, s) != hipSuccess ||
+        hipMemcpyAsync(e->vw_vsign, vsign_host, (size_t)V * C * sizeof(float), hipMemcpyHostToDevice, s) != hipSuccess ||
+        hipMemcpyAsync(e->vw_isign, isign_host, (size_t)V * C * sizeof(float), hipMemcpyHostToDevice, s) != hipSuccess ||
+        launch_views_invert(e->vw_perm, e->vw_iperm, e->vw_hits, V, HW, s) ||
+        hipMemcpyAsync(&bad, e->vw_hits + (size_t)V * HW, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess) {
+        lt_set_error("lt_set_views: uploading the view tables failed");
+        return fail();
+    }
+    if (bad != 0) {
+        lt_set_error("lt_set_views: a view table is not a bijection on [0, %d): %d entries are out of range or name a pixel a second time", HW, bad);
+        return fail();
+    }
+    e->vw_V = V; e->vw_h = latent_h; e->vw_w = latent_w;
+    return 0;
+}
+
+extern "C" int lt_sample_views(lt_engine* e, const void* z_dev, void* traj_dev, void* final_dev, const float* tgrid_host, int32_t n_grid,
+                               int32_t method, const lt_step_args* a, void* stream) {
+    LT_REQUIRE(e && z_dev && tgrid_host && a, "lt_sample_views: null argument");
+    LtOptScope opt_scope(&e->opts);
+    LT_REQUIRE(e->cfg.variant == LT_VARIANT_NEXT_T2I, "lt_sample_views: multi-view sampling drives the text-conditional Next-DiT (LT_VARIANT_NEXT_T2I) "
+               "only; this engine is variant %d", e->cfg.variant);
+    LT_REQUIRE(n_grid >= 2, "lt_sample_views: need at least 2 grid points");
+    LT_REQUIRE(method != LT_ODE_RK4, "lt_sample_views: rk4 is not a multi-view method (the reference steps views with its midpoint_solver; euler is the "
+               "one-stage form)");
+    LT_REQUIRE(method == LT_ODE_EULER || method == LT_ODE_MIDPOINT, "lt_sample_views: unknown method %d", method);
+    LT_REQUIRE(e->vw_V >= 1, "lt_sample_views: no view tables (call lt_set_views first)");
+    const int V = e->vw_V, B = 2 * V, C = e->cfg.in_channels, HW = e->vw_h * e->vw_w;
+    LT_REQUIRE(a->batch == B, "lt_sample_views: %d views need a->batch = 2 V = %d (view prompts + negative prompts), got %d", V, B, a->batch);
+    LT_REQUIRE(a->latent_h == e->vw_h && a->latent_w == e->vw_w, "lt_sample_views: the view tables are for a %dx%d latent, the call has %dx%d", e->vw_h,
+               e->vw_w, a->latent_h, a->latent_w);
+    LT_REQUIRE(a->io_dtype == LT_BF16 || a->io_dtype == LT_F32, "io_dtype must be bf16 or f32");
+    LT_REQUIRE(B <= e->cfg.max_batch, "lt_sample_views: batch %d exceeds max_batch %d", B, e->cfg.max_batch);
+    LT_REQUIRE(e->reg_Y == 0 && e->prompt_B == B, "lt_prepare_prompt was called for batch %d, step has batch %d (multi-view sampling needs the V view "
+               "prompts followed by V rows of the negative prompt)", e->prompt_B, B);
+    hipStream_t s = (hipStream_t)stream;
+    const int stages = method == LT_ODE_EULER ? 1 : 2;
+    const int ncalls = (n_grid - 1) * stages;
+    const bool bf = a->io_dtype == LT_BF16;
+    const size_t sbytes = (size_t)C * HW * (bf ? 2 : 4);  // ONE latent
+    if (e->t_cap < ncalls * B) {  // (as lt_sample_ode: the one case in which this call synchronises)
+        LT_CHECK_HIP(hipStreamSynchronize(s));
+        if (e->t_dev) LT_CHECK_HIP(hipFree(e->t_dev));
+        if (e->t_pinned) LT_CHECK_HIP(hipHostFree(e->t_pinned));
+        e->t_dev = nullptr; e->t_pinned = nullptr; e->t_cap = 0;
+        LT_CHECK_HIP(hipMalloc((void**)&e->t_dev, (size_t)ncalls * B * sizeof(float)));
+        LT_CHECK_HIP(hipHostMalloc((void**)&e->t_pinned, (size_t)ncalls * B * sizeof(float), hipHostMallocDefault));
+        e->t_cap = ncalls * B;
+    }
+    LT_CHECK_HIP(hipEventSynchronize(e->t_copied));
+    // generate.py:212-219: t0, t1 are Python floats (the fp32 grid's values as doubles); dt = t1 - t0 and half_dt = 0.5 dt are doubles that
+    // multiply a tensor as fp32 scalars; the stage times are torch.full((2,), t0) and torch.full((2,), t0 + half_dt): fp32 of the double
+    std::vector<float> dts(n_grid - 1), hdts(n_grid - 1);
+    for (int i = 0; i + 1 < n_grid; ++i) {
+        const double t0 = tgrid_host[i], dt = (double)tgrid_host[i + 1] - t0, half_dt = 0.5 * dt;
+        dts[i] = (float)dt;
+        hdts[i] = (float)half_dt;
+        const float ts[2] = {(float)t0, (float)(t0 + half_dt)};
+        for (int k = 0; k < stages; ++k)
+            for (int b = 0; b < B; ++b) e->t_pinned[((size_t)i * stages + k) * B + b] = ts[k];
+    }
+    LT_CHECK_HIP(hipMemcpyAsync(e->t_dev, e->t_pinned, (size_t)ncalls * B * sizeof(float), hipMemcpyHostToDevice, s));
+    LT_CHECK_HIP(hipEventRecord(e->t_copied, s));
+    LT_CHECK_HIP(hipMemcpyAsync(e->ys[0], z_dev, sbytes, hipMemcpyDeviceToDevice, s));
+    if (traj_dev) LT_CHECK_HIP(hipMemcpyAsync(traj_dev, z_dev, sbytes, hipMemcpyDeviceToDevice, s));
+    int cur = 0;
+    long long nfe = 0;
+    // one evaluation of ALL views: forward_with_cfg on 2 V rows, rows 0..V-1 = the viewed latents (it reads the first half only)
+    auto model = [&](int call, void* out) {
+        ++nfe;
+        return forward_graphed(e, e->ymid, e->t_dev + (size_t)call * B, out, a, 1, s);
+    };
+    const int dt_code = bf ? 1 : 0;
+    for (int i = 0; i + 1 < n_grid; ++i) {
+        void* y0 = e->ys[cur];
+        void* y1 = e->ys[cur ^ 1];
+        const int c0 = i * stages;
+        const void* slope = e->kbuf[0];
+        if (launch_views_gather(y0, e->vw_perm, e->vw_vsign, nullptr, e->ymid, 0.f, V, C, HW, dt_code, s)) return 1;
+        if (model(c0, e->kbuf[0])) return 1;
+        if (method == LT_ODE_MIDPOINT) {
+            if (launch_views_gather(y0, e->vw_perm, e->vw_vsign, e->kbuf[0], e->ymid, hdts[i], V, C, HW, dt_code, s)) return 1;
+            if (model(c0 + 1, e->kbuf[1])) return 1;
+            slope = e->kbuf[1];
+        }
+        if (launch_views_reduce(y0, slope, e->vw_iperm, e->vw_isign, y1, dts[i], V, C, HW, dt_code, s)) return 1;
+        if (traj_dev) LT_CHECK_HIP(hipMemcpyAsync((char*)traj_dev + (size_t)(i + 1) * sbytes, y1, sbytes, hipMemcpyDeviceToDevice, s));
+        cur ^= 1;
+    }
+    if (final_dev) LT_CHECK_HIP(hipMemcpyAsync(final_dev, e->ys[cur], sbytes, hipMemcpyDeviceToDevice, s));
+    e->last_nfe = nfe;
+    return 0;
+}
+
+extern "C" int lt_op_views_invert(const int32_t* perm_dev, int32_t* iperm_dev, int32_t* hits_dev, int32_t V, int32_t HW, void* stream) {
+    return launch_views_invert(perm_dev, iperm_dev, hits_dev, V, HW, (hipStream_t)stream);
+}
+extern "C" int lt_op_views_gather(const void* y_dev, const int32_t* perm_dev, const float* vsign_dev, const void* f0_dev, void* out_dev, float half_dt,
+                                  int32_t V, int32_t C, int32_t HW, int32_t dtype, void* stream) {
+    return launch_views_gather(y_dev, perm_dev, vsign_dev, f0_dev, out_dev, half_dt, V, C, HW, dtype, (hipStream_t)stream);
+}
+extern "C" int lt_op_views_reduce(const void* y_dev, const void* f_dev, const int32_t* iperm_dev, const float* isign_dev, void* out_dev, float dt,
+                                  int32_t V, int32_t C, int32_t HW, int32_t dtype, void* stream) {
+    return launch_views_reduce(y_dev, f_dev, iperm_dev, isign_dev, out_dev, dt, V, C, HW, dtype, (hipStream_t)stream);
 }
 
 extern "C" int64_t lt_last_nfe(lt_engine* e) { return e ? e->last_nfe : -1; }

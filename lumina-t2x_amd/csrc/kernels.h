@@ -349,6 +349,15 @@ int launch_unpatchify_cfg(const u16* rows, int ld, void* out, int out_dtype, int
 // torchdiffeq fixed-grid state arithmetic (modes documented in misc.hip)
 int launch_ode_combine(int mode, const void* y0, const void* k1, const void* k2, const void* k3, const void* k4,
                        void* out, int dtype, float dt, long long n, hipStream_t stream);
+// multi-view sampling (views.hip): view tables perm / iperm int32 [V][HW], vsign / isign float [V][C]; state dtype 0 f32, 1 bf16
+//   invert: iperm from perm; hits int32 [V * HW + 1] is zeroed, then counts the hits per target, last word = entries out of range or repeated
+//   gather: out [V, C, HW] = view_v(y [C, HW]); with f0 [V, C, HW]: R(view_v(y) + R(f0 * half_dt))
+//   reduce: out [C, HW] = R(y - R(mean_v inverse_view_v(-R(f [V, C, HW] * dt))))
+int launch_views_invert(const int* perm, int* iperm, int* hits, int V, int HW, hipStream_t stream);
+int launch_views_gather(const void* y, const int* perm, const float* vsign, const void* f0, void* out, float half_dt, int V, int C, int HW,
+                        int dtype, hipStream_t stream);
+int launch_views_reduce(const void* y, const void* f, const int* iperm, const float* isign, void* out, float dt, int V, int C, int HW, int dtype,
+                        hipStream_t stream);
 // weight upload: cast rows of src [rows, cols] to bf16 at dst rows (row_map 0: r0 + r; 1/2: w1/w3 slots of
 // the 32-row interleaved SwiGLU layout), row stride dst_ld (>= cols; padding left untouched)
 int launch_upload_rows(const void* src, int dtype, u16* dst, int rows, int cols, int dst_ld, int r0, int row_map,

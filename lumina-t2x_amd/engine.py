@@ -272,6 +272,72 @@ class DiTEngine:
         _lib.check(rc, "lt_sample_ode")
         return out
 
+    # ---- multi-view (visual-anagram) sampling -------------------------------------------------------------------
+    def set_views(self, views, latent_h: int, latent_w: int) -> None:
+        """upload the tables of a list of ``views.BaseView`` objects (or a ready ``(perm [V, h*w], vsign [V, C], isign [V, C])`` triple) for
+        an ``latent_h x latent_w`` latent; the engine builds the inverse permutations and rejects a table that is not a bijection.
+        ``views=None`` drops them.  May synchronise the stream (table upload), unlike the sampling loop."""
+        from . import views as _views
+        s = C.c_void_p(_stream_ptr(self.device))
+        if views is None:
+            with torch.cuda.device(self.device):
+                _lib.check(self.lib.lt_set_views(self.handle, None, None, None, 0, 0, 0, s), "lt_set_views")
+            self._views_key = None
+            return
+        if isinstance(views, tuple) and len(views) == 3 and all(isinstance(t, torch.Tensor) for t in views):
+            perm, vsign, isign = views
+        else:
+            perm, vsign, isign = _views.stack_tables(list(views), latent_h, latent_w, self.in_channels)
+        if perm.dim() != 2 or perm.shape[1] != latent_h * latent_w:
+            raise LuminaLibError(f"set_views: view tables of shape {tuple(perm.shape)} do not match a {latent_h}x{latent_w} latent "
+                                 f"([V, {latent_h * latent_w}] expected)")
+        V = perm.shape[0]
+        if tuple(vsign.shape) != (V, self.in_channels) or tuple(isign.shape) != (V, self.in_channels):
+            raise LuminaLibError(f"set_views: signs must be [V = {V}, C = {self.in_channels}], got {tuple(vsign.shape)} / {tuple(isign.shape)}")
+        perm_d = perm.to(device=self.device, dtype=torch.int32).contiguous()
+        vs = vsign.detach().to("cpu", torch.float32).contiguous()
+        isg = isign.detach().to("cpu", torch.float32).contiguous()
+        self._views_key = None
+        with torch.cuda.device(self.device):
+            rc = self.lib.lt_set_views(self.handle, C.c_void_p(perm_d.data_ptr()), C.cast(vs.data_ptr(), C.POINTER(C.c_float)),
+                                       C.cast(isg.data_ptr(), C.POINTER(C.c_float)), V, int(latent_h), int(latent_w), s)
+        _lib.check(rc, "lt_set_views")
+        self._views_key = (V, int(latent_h), int(latent_w))
+
+    def sample_views(self, z: torch.Tensor, tgrid, method: str = "midpoint", *, cfg_scale: float = 1.0, scale_factor: float = 1.0,
+                     scale_watershed: float = 1.0, base_seqlen: Optional[int] = None, proportional_attn: bool = False,
+                     return_trajectory: bool = True) -> torch.Tensor:
+        """Phase Init of the reference's visual_anagrams/generate.py:389-414 in ONE call: ``z`` is one latent ``[1, C, H, W]``; every stage
+        of every interval evaluates all V views as one ``forward_with_cfg`` of 2 V rows.  Needs ``set_views`` and a prompt prepared at
+        B = 2 V (rows 0..V-1 the view prompts, rows V..2V-1 the negative prompt).  Returns ``[n_grid, C, H, W]`` (or the last latent
+        ``[1, C, H, W]``)."""
+        _require_gpu(z, "z")
+        if method not in _lib.ODE_METHODS:
+            raise LuminaLibError(f"fixed-grid method '{method}' not in {sorted(_lib.ODE_METHODS)}")
+        if z.dim() != 4 or z.shape[0] != 1:
+            raise LuminaLibError(f"sample_views takes ONE latent [1, C, H, W], got {tuple(z.shape)}")
+        key = getattr(self, "_views_key", None)
+        if key is None:
+            raise LuminaLibError("sample_views: no views uploaded (call set_views first)")
+        z = z.contiguous()
+        grid = [float(v) for v in (tgrid.detach().to("cpu", torch.float32).tolist() if isinstance(tgrid, torch.Tensor) else
+                                   torch.tensor(list(tgrid), dtype=torch.float32).tolist())]
+        n = len(grid)
+        garr = (C.c_float * n)(*grid)
+        a = self._step_args(z, cfg_scale, scale_factor, scale_watershed, base_seqlen, proportional_attn)
+        a.batch = 2 * key[0]
+        if return_trajectory:
+            out = torch.empty((n,) + tuple(z.shape[1:]), dtype=z.dtype, device=z.device)
+            traj_ptr, fin_ptr = C.c_void_p(out.data_ptr()), C.c_void_p(0)
+        else:
+            out = torch.empty_like(z)
+            traj_ptr, fin_ptr = C.c_void_p(0), C.c_void_p(out.data_ptr())
+        with torch.cuda.device(self.device):
+            rc = self.lib.lt_sample_views(self.handle, C.c_void_p(z.data_ptr()), traj_ptr, fin_ptr, garr, n, _lib.ODE_METHODS[method],
+                                          C.byref(a), C.c_void_p(_stream_ptr(self.device)))
+        _lib.check(rc, "lt_sample_views")
+        return out
+
     def last_nfe(self) -> int:
         return int(self.lib.lt_last_nfe(self.handle))
 

@@ -236,6 +236,25 @@ class NextDiT(WeightWatch, nn.Module):
         eng.prepare_prompt(cap_feats, cap_mask)
         return eng.sample_ode(x, tgrid, method, use_cfg=use_cfg, t_round_to_state_dtype=t_round, **args)
 
+    @torch.no_grad()
+    def sample_views(self, z, tgrid, views, cap_feats, cap_mask, method: str = "midpoint", *, cfg_scale: float = 4.0,
+                     return_trajectory: bool = True):
+        """Multi-view (visual-anagram) sampling, Phase Init of the reference's visual_anagrams/generate.py:389-414, on the engine: ONE latent
+        ``z [1, C, H, W]``, V ``views`` (``lumina_t2x_amd.views``), ``cap_feats [2V, T, D]`` / ``cap_mask [2V, T]`` with rows 0..V-1 the view
+        prompts and rows V..2V-1 the negative prompt.  Every stage of every interval is one forward_with_cfg of 2 V rows.  Phase Init
+        passes ``cfg_scale`` only (scale_factor 1, no proportional attention); Phase Upscale is not implemented."""
+        V = len(views)
+        if cap_feats.shape[0] != 2 * V:
+            raise _lib.LuminaLibError(f"sample_views: {V} views need 2 V = {2 * V} prompt rows (view prompts, then the negative prompt per "
+                                      f"view), got {cap_feats.shape[0]}")
+        for layer in self.layers:  # what a forward_with_cfg without proportional attention leaves on the module
+            layer.attention.base_seqlen = None
+            layer.attention.proportional_attn = False
+        eng = self.engine(z.expand(2 * V, -1, -1, -1), cap_feats.shape[1])
+        eng.prepare_prompt(cap_feats, cap_mask)
+        eng.set_views(views, z.shape[2], z.shape[3])
+        return eng.sample_views(z, tgrid, method, cfg_scale=cfg_scale, return_trajectory=return_trajectory)
+
     def parameter_count(self) -> int:
         return sum(p.numel() for p in self.parameters())
 
