@@ -329,7 +329,8 @@ int lt_op_qk_norm_rope(const void* src_dev, int32_t ld_src, int32_t col0, const 
                        const void* ln_b_dev, float ln_eps, void* dst_dev, int32_t B, int32_t N,
                        int32_t heads, int32_t hd, int32_t rope_mode, const void* cs_table_dev,
                        int32_t grid_w, float out_scale, void* stream);
-/* V -> transposed, key-permuted layout the attention kernel consumes: [B,kvh,hd,Npad] */
+/* V -> transposed, key-permuted layout the attention kernel consumes: [B,kvh,hd,Npad]; key n of a sample sits at position
+ * (n & ~12) | ((n & 4) << 1) | ((n & 8) >> 1) (bits 2 and 3 of the key index swapped inside every 16 keys), keys >= N are zero */
 int lt_op_v_transpose(const void* src_dev, int32_t ld_src, int32_t col0, void* dst_dev, int32_t B,
                       int32_t N, int32_t Npad, int32_t kv_heads, int32_t hd, void* stream);
 /* non-causal softmax(q k^T * scale + bias) v  (model.py:392-405 / 427-432).

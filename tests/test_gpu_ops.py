@@ -3,6 +3,10 @@
 Tolerances (stated here, justified in DESIGN.md): GEMM / attention outputs are bf16, so one output ulp is
 2^-8 relative; we require rel-L2 <= 4e-3 against an fp32-accumulated reference rounded once to bf16 and a
 max-abs error of a few ulp of the largest output.  Pure data-movement kernels must be bit exact.
+
+The GEMM family has a second, exact tier in test_gpu_gemm_exact.py (helpers in exact_operands.py, CPU part in
+test_exact_operands_cpu.py): bit exact on integer operands, every output word compared; the rel-L2 figures on random operands in
+this file measure rounding only - a global norm cannot see a local fault.
 """
 import math
 import os
@@ -12,6 +16,7 @@ import torch
 import torch.nn.functional as F
 
 from gpu_util import P, bf, lib, max_abs, ok, r16, rel_l2, set_option, stream
+from grouped_plans import expert_table, filled_row_map, ragged_row_map
 
 pytestmark = pytest.mark.gpu
 
@@ -158,14 +163,8 @@ def test_gemm_grouped_gather_on_load(variant, epilogue):
     g = torch.Generator().manual_seed(41 + variant + epilogue)
     X = bf(torch.randn(T, K, generator=g))
     W = bf(torch.randn(E, N, K, generator=g) / math.sqrt(K))
-    row_map = torch.full((M,), -1, dtype=torch.int32)
     fill = {0: 256, 1: 256, 2: 200, 4: 131, 5: 256, 6: 97}  # entries per real tile
-    perm = torch.randperm(T, generator=g)
-    cursor = 0
-    for t_, cnt in fill.items():
-        idx = torch.cat([perm, perm])[cursor:cursor + cnt]
-        cursor += cnt
-        row_map[256 * t_: 256 * t_ + cnt] = idx.to(torch.int32)
+    row_map, cursor = filled_row_map(len(te), fill, T, g)
     assert cursor == 2 * T - 4  # (almost) every token twice
     gathered = torch.zeros(M, K, device="cuda", dtype=torch.bfloat16)
     valid = row_map >= 0
@@ -331,23 +330,12 @@ def test_gemm_grouped_persistent_kernel(K, N, ntile, gather, epilogue):
     gathered and the copy form of the SAME kernel are bit-identical."""
     E = 4
     g = torch.Generator().manual_seed(K + N + ntile + epilogue)
-    te = torch.randint(0, E, (ntile,), generator=g).tolist()
-    for hole in (1, ntile // 2, ntile - 1):
-        te[hole] = -1
+    te = expert_table(E, ntile, (1, ntile // 2, ntile - 1), g)
     M = 256 * ntile
     T = M // 2 - 37
     X = bf(torch.randn(T, K, generator=g))
     W = bf(torch.randn(E, N, K, generator=g) / math.sqrt(K))
-    row_map = torch.full((M,), -1, dtype=torch.int32)
-    src = torch.cat([torch.randperm(T, generator=g), torch.randperm(T, generator=g)]).to(torch.int32)
-    cursor = 0
-    for t_, ex in enumerate(te):
-        if ex < 0:
-            continue
-        cnt = 256 if t_ % 3 else 256 - 7 * (t_ % 11) - 1  # ragged fill: padding rows behind the entries of some real tiles
-        cnt = min(cnt, src.numel() - cursor)
-        row_map[256 * t_: 256 * t_ + cnt] = src[cursor:cursor + cnt]
-        cursor += cnt
+    row_map = ragged_row_map(te, T, g)
     valid = (row_map >= 0).cuda()
     gathered = torch.zeros(M, K, device="cuda", dtype=torch.bfloat16)
     gathered[valid] = X[row_map[row_map >= 0].long().cuda()]
@@ -387,9 +375,7 @@ def test_gemm_grouped_tail_split(K, N, ntile, holes):
     does not enter; the counters are back at zero) and with padding segments left untouched."""
     E = 4
     g = torch.Generator().manual_seed(K + N + ntile)
-    te = torch.randint(0, E, (ntile,), generator=g).tolist()
-    for h in range(holes):
-        te[(h * 37 + 1) % ntile] = -1
+    te = expert_table(E, ntile, [(h * 37 + 1) % ntile for h in range(holes)], g)
     M = 256 * ntile
     A = bf(torch.randn(M, K, generator=g))
     W = bf(torch.randn(E, N, K, generator=g) / math.sqrt(K))
