@@ -46,6 +46,22 @@ extern "C" {
 #define LT_ODE_EULER 0
 #define LT_ODE_MIDPOINT 1
 #define LT_ODE_RK4 2
+/* lt_sample_sde: method, last step, and the length (floats) of one stage record */
+#define LT_SDE_EULER 0
+#define LT_SDE_HEUN 1
+#define LT_SDE_LAST_NONE 0
+#define LT_SDE_LAST_MEAN 1
+#define LT_SDE_LAST_TWEEDIE 2
+#define LT_SDE_LAST_EULER 3
+#define LT_SDE_REC 8
+/* lt_op_sde_step: the fused kernels of lt_sample_sde */
+#define LT_SDE_OP_EULER 0
+#define LT_SDE_OP_HEUN_XHAT 1
+#define LT_SDE_OP_HEUN_K1 2
+#define LT_SDE_OP_HEUN_OUT 3
+#define LT_SDE_OP_LAST_MEAN 4
+#define LT_SDE_OP_LAST_TWEEDIE 5
+#define LT_SDE_OP_LAST_EULER 6
 
 typedef struct lt_engine lt_engine;
 
@@ -176,7 +192,28 @@ int lt_set_views(lt_engine* e, const int32_t* perm_dev, const float* vsign_host,
 int lt_sample_views(lt_engine* e, const void* z_dev, void* traj_dev, void* final_dev, const float* tgrid_host, int32_t n_grid,
                     int32_t method, const lt_step_args* a, void* stream);
 
-/* number of model evaluations issued by the last lt_sample_ode / lt_sample_views call */
+/* ---- SDE sampling: sde.sample + the last step of Sampler.sample_sde (integrators.py:5-76, transport.py:285-344), velocity prediction ---------
+ * The whole trajectory in one call, ONE model evaluation per stage: the reference's sde_drift = drift + D * score evaluates the model twice
+ * on the same (x, t) (transport.py:172-173); the engine is deterministic, so the fused step kernels read the one output twice.
+ * z [B,C,H,W] in the state dtype (a->io_dtype).  noise_dev [n_steps - 1, B,C,H,W], state dtype: the caller's draws, step by step (the engine
+ * owns no RNG).  traj_dev (may be NULL) receives the n_steps - 1 loop states [n_steps - 1, B,C,H,W] (state 0 is the state AFTER the first
+ * step, as in the reference).  final_dev receives the last-step state: fp32 [B,C,H,W] for LT_SDE_LAST_MEAN / _TWEEDIE whatever the state dtype
+ * (the reference's last step runs at an fp32 time vector and type promotion makes the result fp32), the state dtype for LT_SDE_LAST_EULER;
+ * with LT_SDE_LAST_NONE no last step runs and final_dev (may be NULL) receives a copy of the last loop state.
+ * steps_host: (n_steps - 1) * stages records of LT_SDE_REC floats, stages = 1 (LT_SDE_EULER) or 2 (LT_SDE_HEUN: the stage at t, then the stage
+ * at t + dt).  Record: { t, r, var, D, q, dt, sqrt_dt, hdt } - t the stage time handed to the model; r = alpha / alpha', var = sigma^2 - r sigma'
+ * sigma and D the diffusion coefficient at t, q = sqrt(2 D): the VALUES of the [B,1,1,1] state-dtype tensors the path plan produces (same
+ * contract as tgrid_host: already rounded); dt, sqrt_dt, hdt = 0.5 dt are fp32 and multiply in fp32.  A Heun step reads q, dt, sqrt_dt from
+ * its first record and hdt from its second.  last_coef_host (LT_SDE_LAST_NONE: may be NULL): one record { t, r, var, D, h, a, c, 0 } at the
+ * last time, all fp32 - h the last step size, a = alpha rounded to the state dtype and c = sigma^2 / alpha (Tweedie only).
+ * Rounding points: csrc/sde.hip.  lt_last_nfe = (n_steps - 1) * stages + (last_step != LT_SDE_LAST_NONE).
+ * Refused by name: unknown method / last_step, n_steps < 2, a var that is not finite and positive.  Score / noise prediction is not served
+ * here (the Python sampler keeps its host loop for them).  Like lt_sample_ode: no synchronisation, no host read, the caller's stream. */
+int lt_sample_sde(lt_engine* e, const void* z_dev, const void* noise_dev, void* traj_dev, void* final_dev, const float* steps_host,
+                  int32_t n_steps, int32_t method, int32_t last_step, const float* last_coef_host, int32_t use_cfg, const lt_step_args* a,
+                  void* stream);
+
+/* number of model evaluations issued by the last lt_sample_ode / lt_sample_views / lt_sample_sde call */
 int64_t lt_last_nfe(lt_engine* e);
 /* model evaluations served by replaying a captured HIP graph since lt_create (0 with lt_set_option("graph", 0), and below 1025 rows under the default "graph" 2) */
 int64_t lt_graph_replays(lt_engine* e);
@@ -377,6 +414,16 @@ int lt_op_views_gather(const void* y_dev, const int32_t* perm_dev, const float* 
                        int32_t V, int32_t C, int32_t HW, int32_t dtype, void* stream);
 int lt_op_views_reduce(const void* y_dev, const void* f_dev, const int32_t* iperm_dev, const float* isign_dev, void* out_dev, float dt,
                        int32_t V, int32_t C, int32_t HW, int32_t dtype, void* stream);
+/* one fused step kernel of lt_sample_sde on caller-owned buffers of n elements (any n >= 1; buffers that are not 16-byte aligned take the
+ * one-element-per-thread form).  op = LT_SDE_OP_*, rec_host = the stage's LT_SDE_REC floats, dtype LT_F32 or LT_BF16 (R: round to dtype):
+ *   EULER      out = R(R(x + R(drift(x, v) * dt)) + R(q * R(w * sqrt_dt)))       drift(x, v) = R(v + R(D * R(R(R(r * v) - x) / var)))
+ *   HEUN_XHAT  out = R(x + R(q * R(w * sqrt_dt)))
+ *   HEUN_K1    out2 = K1 = drift(x, v),  out = R(x + R(dt * K1))                  (x = xhat)
+ *   HEUN_OUT   out = R(x + R(hdt * R(k1 + drift(xp, v))))                         (x = xhat, v = the model at xp, rec = the second stage's)
+ *   LAST_MEAN / LAST_TWEEDIE / LAST_EULER: the last-step rules of lt_sample_sde; out is fp32 for the first two.
+ * Operands an op does not read may be NULL. */
+int lt_op_sde_step(int32_t op, const void* x_dev, const void* v_dev, const void* w_dev, const void* k1_dev, const void* xp_dev, void* out_dev,
+                   void* out2_dev, const float* rec_host, int64_t n, int32_t dtype, void* stream);
 /* y[m,n] = sum_k act(a[m,k]) w[n,k] + b[n], m < M <= 8 (GEMV-style; adaLN / embedders).
  * act_in 0 none, 1 SiLU.  a bf16 [M,K], w bf16 [N,K], b bf16 [N] or NULL, y bf16 [M,N]. */
 int lt_op_linear_small_m(const void* a_dev, const void* w_dev, const void* b_dev, void* y_dev,

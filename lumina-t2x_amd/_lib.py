@@ -23,6 +23,13 @@ LT_VARIANT_NEXT_T2I, LT_VARIANT_NEXT_IMAGENET, LT_VARIANT_FLAG_T2I, LT_VARIANT_N
 LT_VARIANT_NEXT_MOE_TIME, LT_VARIANT_NEXT_MOE_SPACE = 4, 5
 LT_ODE_EULER, LT_ODE_MIDPOINT, LT_ODE_RK4 = 0, 1, 2
 ODE_METHODS = {"euler": LT_ODE_EULER, "midpoint": LT_ODE_MIDPOINT, "rk4": LT_ODE_RK4}
+LT_SDE_EULER, LT_SDE_HEUN = 0, 1
+SDE_METHODS = {"Euler": LT_SDE_EULER, "Heun": LT_SDE_HEUN}
+LT_SDE_LAST_NONE, LT_SDE_LAST_MEAN, LT_SDE_LAST_TWEEDIE, LT_SDE_LAST_EULER = 0, 1, 2, 3
+SDE_LAST_STEPS = {None: LT_SDE_LAST_NONE, "Mean": LT_SDE_LAST_MEAN, "Tweedie": LT_SDE_LAST_TWEEDIE, "Euler": LT_SDE_LAST_EULER}
+LT_SDE_REC = 8  # floats per stage record: t, r, var, D, q, dt, sqrt_dt, hdt (last step: t, r, var, D, h, a, c, 0)
+(LT_SDE_OP_EULER, LT_SDE_OP_HEUN_XHAT, LT_SDE_OP_HEUN_K1, LT_SDE_OP_HEUN_OUT, LT_SDE_OP_LAST_MEAN, LT_SDE_OP_LAST_TWEEDIE,
+ LT_SDE_OP_LAST_EULER) = range(7)
 
 
 class LtConfig(C.Structure):
@@ -85,6 +92,7 @@ _SIGNATURES: Dict[str, tuple] = {
     "lt_sample_ode": (_i32, [_vp, _vp, _vp, _vp, C.POINTER(_f32), _i32, _i32, _i32, _i32, C.POINTER(LtStepArgs), _vp]),
     "lt_set_views": (_i32, [_vp, _vp, C.POINTER(_f32), C.POINTER(_f32), _i32, _i32, _i32, _vp]),
     "lt_sample_views": (_i32, [_vp, _vp, _vp, _vp, C.POINTER(_f32), _i32, _i32, C.POINTER(LtStepArgs), _vp]),
+    "lt_sample_sde": (_i32, [_vp, _vp, _vp, _vp, _vp, C.POINTER(_f32), _i32, _i32, _i32, C.POINTER(_f32), _i32, C.POINTER(LtStepArgs), _vp]),
     "lt_last_nfe": (_i64, [_vp]),
     "lt_graph_replays": (_i64, [_vp]),
     "lt_moe_routing_record": (_i32, [_vp, _i32]),
@@ -123,6 +131,7 @@ _SIGNATURES: Dict[str, tuple] = {
     "lt_op_views_invert": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp]),
     "lt_op_views_gather": (_i32, [_vp, _vp, _vp, _vp, _vp, _f32, _i32, _i32, _i32, _i32, _vp]),
     "lt_op_views_reduce": (_i32, [_vp, _vp, _vp, _vp, _vp, _f32, _i32, _i32, _i32, _i32, _vp]),
+    "lt_op_sde_step": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_f32), _i64, _i32, _vp]),
     "lt_op_linear_small_m": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "lt_op_rope_table_2d": (_i32, [_vp, _i32, _i32, _f32, _f32, _vp]),
     "lt_op_rope_table_2d_pair": (_i32, [_vp, _vp, _i32, _i32, _f32, _f32, _vp]),

@@ -1675,6 +1675,103 @@ extern "C" int lt_op_views_reduce(const void* y_dev, const void* f_dev, const in
     return launch_views_reduce(y_dev, f_dev, iperm_dev, isign_dev, out_dev, dt, V, C, HW, dtype, (hipStream_t)stream);
 }
 
+// ---- SDE sampling (sde.hip) --------------------------------------------------------------------------------------------------------
+extern "C" int lt_sample_sde(lt_engine* e, const void* z_dev, const void* noise_dev, void* traj_dev, void* final_dev, const float* steps_host,
+                             int32_t n_steps, int32_t method, int32_t last_step, const float* last_coef_host, int32_t use_cfg,
+                             const lt_step_args* a, void* stream) {
+    LT_REQUIRE(e && z_dev && noise_dev && steps_host && a, "lt_sample_sde: null argument");
+    LtOptScope opt_scope(&e->opts);
+    LT_REQUIRE(n_steps >= 2, "lt_sample_sde: n_steps %d (need at least 2: one loop step and the last step)", n_steps);
+    LT_REQUIRE(method == LT_SDE_EULER || method == LT_SDE_HEUN, "lt_sample_sde: unknown method %d", method);
+    LT_REQUIRE(last_step >= LT_SDE_LAST_NONE && last_step <= LT_SDE_LAST_EULER, "lt_sample_sde: unknown last_step %d", last_step);
+    LT_REQUIRE(last_step == LT_SDE_LAST_NONE || (last_coef_host && final_dev), "lt_sample_sde: null argument (a last step needs last_coef_host and "
+               "final_dev)");
+    hipStream_t s = (hipStream_t)stream;
+    const int B = a->batch;
+    LT_REQUIRE(B >= 1 && B <= e->cfg.max_batch, "lt_sample_sde: batch %d outside 1..max_batch %d", B, e->cfg.max_batch);
+    LT_REQUIRE(a->latent_h > 0 && a->latent_w > 0 && a->latent_h % e->cfg.patch_size == 0 && a->latent_w % e->cfg.patch_size == 0 &&
+                   (long long)(a->latent_h / e->cfg.patch_size) * (a->latent_w / e->cfg.patch_size) <= e->cfg.max_tokens,
+               "lt_sample_sde: latent %dx%d is not a positive multiple of the patch size or exceeds max_tokens %d", a->latent_h, a->latent_w,
+               e->cfg.max_tokens);
+    LT_REQUIRE(a->io_dtype == LT_BF16 || a->io_dtype == LT_F32, "io_dtype must be bf16 or f32");
+    const int stages = method == LT_SDE_EULER ? 1 : 2;
+    const int nloop = n_steps - 1;
+    const int nrec = nloop * stages;
+    const int has_last = last_step != LT_SDE_LAST_NONE;
+    const int ncalls = nrec + has_last;
+    // the score divides by var = sigma^2 - r sigma' sigma (path.py: get_score_from_velocity); the last-step rule Euler has no score
+    for (int i = 0; i < nrec; ++i) {
+        const float var = steps_host[(size_t)i * LT_SDE_REC + 2];
+        LT_REQUIRE(std::isfinite(var) && var > 0.f, "lt_sample_sde: var %g of stage %d (step %d) is not finite and positive", (double)var, i % stages,
+                   i / stages);
+    }
+    if (last_step == LT_SDE_LAST_MEAN || last_step == LT_SDE_LAST_TWEEDIE)
+        LT_REQUIRE(std::isfinite(last_coef_host[2]) && last_coef_host[2] > 0.f, "lt_sample_sde: var %g of the last step is not finite and positive",
+                   (double)last_coef_host[2]);
+    const long long n = (long long)B * e->cfg.in_channels * a->latent_h * a->latent_w;
+    const bool bf = a->io_dtype == LT_BF16;
+    const size_t sbytes = (size_t)n * (bf ? 2 : 4);
+    if (e->t_cap < ncalls * B) {  // (as lt_sample_ode: the one case in which this call synchronises)
+        LT_CHECK_HIP(hipStreamSynchronize(s));
+        if (e->t_dev) LT_CHECK_HIP(hipFree(e->t_dev));
+        if (e->t_pinned) LT_CHECK_HIP(hipHostFree(e->t_pinned));
+        e->t_dev = nullptr; e->t_pinned = nullptr; e->t_cap = 0;
+        LT_CHECK_HIP(hipMalloc((void**)&e->t_dev, (size_t)ncalls * B * sizeof(float)));
+        LT_CHECK_HIP(hipHostMalloc((void**)&e->t_pinned, (size_t)ncalls * B * sizeof(float), hipHostMallocDefault));
+        e->t_cap = ncalls * B;
+    }
+    LT_CHECK_HIP(hipEventSynchronize(e->t_copied));
+    // stage times: the loop hands the model a [B] vector of the state dtype (integrators.py: th.ones(B).to(x) * t), the last step an fp32 one
+    for (int i = 0; i < ncalls; ++i) {
+        const float tv = i < nrec ? steps_host[(size_t)i * LT_SDE_REC] : last_coef_host[0];
+        for (int b = 0; b < B; ++b) e->t_pinned[(size_t)i * B + b] = tv;
+    }
+    LT_CHECK_HIP(hipMemcpyAsync(e->t_dev, e->t_pinned, (size_t)ncalls * B * sizeof(float), hipMemcpyHostToDevice, s));
+    LT_CHECK_HIP(hipEventRecord(e->t_copied, s));
+    LT_CHECK_HIP(hipMemcpyAsync(e->ys[0], z_dev, sbytes, hipMemcpyDeviceToDevice, s));
+    int cur = 0;
+    long long nfe = 0;
+    auto model = [&](const void* y, int call, void* out) {
+        ++nfe;
+        return forward_graphed(e, y, e->t_dev + (size_t)call * B, out, a, use_cfg, s);
+    };
+    const int dt_code = bf ? 1 : 0;
+    for (int i = 0; i < nloop; ++i) {
+        void* y0 = e->ys[cur];
+        void* y1 = e->ys[cur ^ 1];
+        const void* w = (const char*)noise_dev + (size_t)i * sbytes;
+        const float* rec = steps_host + (size_t)i * stages * LT_SDE_REC;
+        const int c0 = i * stages;
+        if (method == LT_SDE_EULER) {
+            if (model(y0, c0, e->kbuf[0])) return 1;
+            if (launch_sde_step(LT_SDE_OP_EULER, y0, e->kbuf[0], w, nullptr, nullptr, y1, nullptr, rec, n, dt_code, s)) return 1;
+        } else {  // xhat in ymid, K1 in kbuf[1], the predictor state in kbuf[2]
+            if (launch_sde_step(LT_SDE_OP_HEUN_XHAT, y0, nullptr, w, nullptr, nullptr, e->ymid, nullptr, rec, n, dt_code, s)) return 1;
+            if (model(e->ymid, c0, e->kbuf[0])) return 1;
+            if (launch_sde_step(LT_SDE_OP_HEUN_K1, e->ymid, e->kbuf[0], nullptr, nullptr, nullptr, e->kbuf[2], e->kbuf[1], rec, n, dt_code, s)) return 1;
+            if (model(e->kbuf[2], c0 + 1, e->kbuf[3])) return 1;
+            if (launch_sde_step(LT_SDE_OP_HEUN_OUT, e->ymid, e->kbuf[3], nullptr, e->kbuf[1], e->kbuf[2], y1, nullptr, rec + LT_SDE_REC, n, dt_code, s))
+                return 1;
+        }
+        if (traj_dev) LT_CHECK_HIP(hipMemcpyAsync((char*)traj_dev + (size_t)i * sbytes, y1, sbytes, hipMemcpyDeviceToDevice, s));
+        cur ^= 1;
+    }
+    if (has_last) {
+        const int op = last_step == LT_SDE_LAST_MEAN ? LT_SDE_OP_LAST_MEAN : (last_step == LT_SDE_LAST_TWEEDIE ? LT_SDE_OP_LAST_TWEEDIE : LT_SDE_OP_LAST_EULER);
+        if (model(e->ys[cur], nrec, e->kbuf[0])) return 1;
+        if (launch_sde_step(op, e->ys[cur], e->kbuf[0], nullptr, nullptr, nullptr, final_dev, nullptr, last_coef_host, n, dt_code, s)) return 1;
+    } else if (final_dev) {
+        LT_CHECK_HIP(hipMemcpyAsync(final_dev, e->ys[cur], sbytes, hipMemcpyDeviceToDevice, s));
+    }
+    e->last_nfe = nfe;
+    return 0;
+}
+
+extern "C" int lt_op_sde_step(int32_t op, const void* x_dev, const void* v_dev, const void* w_dev, const void* k1_dev, const void* xp_dev,
+                              void* out_dev, void* out2_dev, const float* rec_host, int64_t n, int32_t dtype, void* stream) {
+    return launch_sde_step(op, x_dev, v_dev, w_dev, k1_dev, xp_dev, out_dev, out2_dev, rec_host, (long long)n, dtype, (hipStream_t)stream);
+}
+
 extern "C" int64_t lt_last_nfe(lt_engine* e) { return e ? e->last_nfe : -1; }
 extern "C" int64_t lt_graph_replays(lt_engine* e) { return e ? e->graph_replays : -1; }
 

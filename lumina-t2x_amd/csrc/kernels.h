@@ -358,6 +358,10 @@ int launch_views_gather(const void* y, const int* perm, const float* vsign, cons
                         int dtype, hipStream_t stream);
 int launch_views_reduce(const void* y, const void* f, const int* iperm, const float* isign, void* out, float dt, int V, int C, int HW, int dtype,
                         hipStream_t stream);
+// SDE sampling (sde.hip): one fused elementwise step on n elements, op = LT_SDE_OP_*, rec = the stage's 8-float record (host), state dtype
+// 0 f32, 1 bf16; operands an op does not read may be null.  out is fp32 for LT_SDE_OP_LAST_MEAN / LAST_TWEEDIE, the state dtype otherwise
+int launch_sde_step(int op, const void* x, const void* v, const void* w, const void* k1, const void* xp, void* out, void* out2, const float* rec,
+                    long long n, int dtype, hipStream_t stream);
 // weight upload: cast rows of src [rows, cols] to bf16 at dst rows (row_map 0: r0 + r; 1/2: w1/w3 slots of
 // the 32-row interleaved SwiGLU layout), row stride dst_ld (>= cols; padding left untouched)
 int launch_upload_rows(const void* src, int dtype, u16* dst, int rows, int cols, int dst_ld, int r0, int row_map,

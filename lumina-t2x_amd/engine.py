@@ -272,6 +272,48 @@ class DiTEngine:
         _lib.check(rc, "lt_sample_ode")
         return out
 
+    def sample_sde(self, z: torch.Tensor, noise: torch.Tensor, steps: torch.Tensor, last_coef: Optional[torch.Tensor], method: str,
+                   last_step: Optional[str], *, use_cfg: bool, cfg_scale: float = 1.0, scale_factor: float = 1.0,
+                   scale_watershed: float = 1.0, base_seqlen: Optional[int] = None, proportional_attn: bool = False,
+                   ntk_factor: float = 1.0) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+        """Euler-Maruyama / Heun SDE sampling with a last-step rule in ONE call (lt_sample_sde; one model evaluation per stage).
+        ``noise`` [n_steps - 1, *z.shape] on the device in the state dtype (the caller's draws), ``steps`` fp32 [(n_steps - 1) * stages,
+        LT_SDE_REC] and ``last_coef`` fp32 [LT_SDE_REC] on the host (``transport.integrators.sde_table``).  Returns (loop states
+        [n_steps - 1, *z.shape], last-step state) - the latter fp32 for "Mean" / "Tweedie" as in the reference, None for ``last_step=None``."""
+        _require_gpu(z, "z")
+        _require_gpu(noise, "noise")
+        if method not in _lib.SDE_METHODS:
+            raise LuminaLibError(f"SDE method '{method}' not in {sorted(_lib.SDE_METHODS)}")
+        if last_step not in _lib.SDE_LAST_STEPS:
+            raise LuminaLibError(f"SDE last step '{last_step}' not in {list(_lib.SDE_LAST_STEPS)}")
+        z = z.contiguous()
+        stages = 2 if method == "Heun" else 1
+        steps = steps.detach().to("cpu", torch.float32).contiguous()
+        if steps.dim() != 2 or steps.shape[1] != _lib.LT_SDE_REC or steps.shape[0] % stages:
+            raise LuminaLibError(f"sample_sde: steps must be [(n_steps - 1) * {stages}, {_lib.LT_SDE_REC}], got {tuple(steps.shape)}")
+        n_loop = steps.shape[0] // stages
+        if noise.dtype != z.dtype or noise.device != z.device or tuple(noise.shape) != (n_loop,) + tuple(z.shape):
+            raise LuminaLibError(f"sample_sde: noise must be {(n_loop,) + tuple(z.shape)} {z.dtype} on {z.device}, got {tuple(noise.shape)} "
+                                 f"{noise.dtype} on {noise.device}")
+        noise = noise.contiguous()
+        a = self._step_args(z, cfg_scale, scale_factor, scale_watershed, base_seqlen, proportional_attn, ntk_factor=ntk_factor)
+        traj = torch.empty_like(noise)
+        final, fin_ptr, last_ptr = None, C.c_void_p(0), None
+        if last_step is not None:
+            if last_coef is None:
+                raise LuminaLibError("sample_sde: a last step needs its coefficient record")
+            last_coef = last_coef.detach().to("cpu", torch.float32).contiguous()
+            if last_coef.numel() != _lib.LT_SDE_REC:
+                raise LuminaLibError(f"sample_sde: last_coef must hold {_lib.LT_SDE_REC} floats, got {last_coef.numel()}")
+            final = torch.empty_like(z, dtype=z.dtype if last_step == "Euler" else torch.float32)
+            fin_ptr, last_ptr = C.c_void_p(final.data_ptr()), C.cast(last_coef.data_ptr(), C.POINTER(C.c_float))
+        with torch.cuda.device(self.device):
+            rc = self.lib.lt_sample_sde(self.handle, C.c_void_p(z.data_ptr()), C.c_void_p(noise.data_ptr()), C.c_void_p(traj.data_ptr()), fin_ptr,
+                                        C.cast(steps.data_ptr(), C.POINTER(C.c_float)), n_loop + 1, _lib.SDE_METHODS[method],
+                                        _lib.SDE_LAST_STEPS[last_step], last_ptr, int(use_cfg), C.byref(a), C.c_void_p(_stream_ptr(self.device)))
+        _lib.check(rc, "lt_sample_sde")
+        return traj, final
+
     # ---- multi-view (visual-anagram) sampling -------------------------------------------------------------------
     def set_views(self, views, latent_h: int, latent_w: int) -> None:
         """upload the tables of a list of ``views.BaseView`` objects (or a ready ``(perm [V, h*w], vsign [V, C], isign [V, C])`` triple) for

@@ -70,7 +70,27 @@ class WeightWatch:
                      for m in self._watch_modules for p in m._parameters.values() if p is not None)
 
 
-class EngineBackedModel(WeightWatch, nn.Module):
+class EngineSamplers:
+    """transport fast paths (integrators.ode.sample / integrators.sde.sample): a whole trajectory in one C-ABI call.  Each model class maps
+    the kwargs of ITS forward / forward_with_cfg onto the engine once, in ``_engine_sampler_args(x, use_cfg, kw) -> (engine, step kwargs)``
+    (every reference sub-project has a different kwarg set); both samplers share that mapping."""
+
+    def _engine_sampler_args(self, x, use_cfg, kw):
+        raise NotImplementedError
+
+    def _engine_sample_ode(self, x, tgrid, method, use_cfg, t_round, kw):
+        """kwargs of forward_with_cfg / forward -> lt_sample_ode"""
+        eng, args = self._engine_sampler_args(x, use_cfg, kw)
+        return eng.sample_ode(x, tgrid, method, use_cfg=use_cfg, t_round_to_state_dtype=t_round, **args)
+
+    def _engine_sample_sde(self, x, noise, steps, last_coef, method, last_step, use_cfg, kw):
+        """kwargs of forward_with_cfg / forward -> lt_sample_sde; returns (engine, loop states [n_steps - 1, *x.shape], last-step state or None)"""
+        eng, args = self._engine_sampler_args(x, use_cfg, kw)
+        traj, final = eng.sample_sde(x, noise, steps, last_coef, method, last_step, use_cfg=use_cfg, **args)
+        return eng, traj, final
+
+
+class EngineBackedModel(EngineSamplers, WeightWatch, nn.Module):
     """Mixin-style base: subclasses set ``_variant`` and implement ``_engine_kwargs()``."""
 
     _variant: int = _lib.LT_VARIANT_NEXT_T2I

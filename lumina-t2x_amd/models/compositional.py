@@ -57,11 +57,11 @@ class NextDiT(_base.NextDiT):
         return eng.forward(x, t, use_cfg=True, cfg_scale=cfg_scale, scale_factor=scale_factor, scale_watershed=scale_watershed,
                            base_seqlen=base_seqlen, proportional_attn=proportional_attn)
 
-    def _engine_sample_ode(self, x, tgrid, method, use_cfg, t_round, kw):
+    def _engine_sampler_args(self, x, use_cfg, kw):
         if kw.get("global_cap_feats") is None:
             for k in ("global_cap_feats", "global_cap_mask", "h_split_num", "w_split_num"):
                 kw.pop(k, None)
-            return super()._engine_sample_ode(x, tgrid, method, use_cfg, t_round, kw)
+            return super()._engine_sampler_args(x, use_cfg, kw)
         eng = self._regional_engine(x, kw.pop("cap_feats"), kw.pop("cap_mask"), kw.pop("global_cap_feats"),
                                     kw.pop("global_cap_mask"), kw.pop("h_split_num", 1), kw.pop("w_split_num", 1))
         if use_cfg:
@@ -72,7 +72,7 @@ class NextDiT(_base.NextDiT):
             args = self._plain_forward_args()
         if kw:
             raise TypeError(f"unexpected model kwargs for the engine path: {sorted(kw)}")
-        return eng.sample_ode(x, tgrid, method, use_cfg=use_cfg, t_round_to_state_dtype=t_round, **args)
+        return eng, args
 
 
 def NextDiT_2B_patch2(**kwargs):

@@ -81,8 +81,8 @@ class DiT_Llama(EngineBackedModel):
         eng.prepare_prompt(cap_feats, cap_mask)
         return eng.forward(x, t, use_cfg=use_cfg, scale_factor=self.rope_scaling_factor, ntk_factor=self.ntk_factor, **kw)
 
-    def _engine_sample_ode(self, x, tgrid, method, use_cfg, t_round, kw):
-        """transport fast path (integrators.ode.sample): kwargs of forward_with_cfg / forward -> lt_sample_ode"""
+    def _engine_sampler_args(self, x, use_cfg, kw):
+        """transport fast paths (models/_base.py: EngineSamplers): kwargs of forward_with_cfg / forward -> engine + step kwargs"""
         cap_feats, cap_mask = kw.pop("cap_feats"), kw.pop("cap_mask")
         args = {}
         if use_cfg:
@@ -96,8 +96,7 @@ class DiT_Llama(EngineBackedModel):
             raise TypeError(f"unexpected model kwargs for the engine path: {sorted(kw)}")
         eng = self.engine(x, cap_feats.shape[1])
         eng.prepare_prompt(cap_feats, cap_mask)
-        return eng.sample_ode(x, tgrid, method, use_cfg=use_cfg, scale_factor=self.rope_scaling_factor,
-                              ntk_factor=self.ntk_factor, t_round_to_state_dtype=t_round, **args)
+        return eng, dict(scale_factor=self.rope_scaling_factor, ntk_factor=self.ntk_factor, **args)
 
     @torch.no_grad()
     def forward(self, x, t, cap_feats, cap_mask):

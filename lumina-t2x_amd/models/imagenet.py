@@ -110,8 +110,8 @@ class DiT_Llama(EngineBackedModel):
         eng.prepare_labels(y)
         return eng.forward(x, t, use_cfg=use_cfg, cfg_scale=cfg_scale, scale_factor=self._rope[0], ntk_factor=self._rope[1])
 
-    def _engine_sample_ode(self, x, tgrid, method, use_cfg, t_round, kw):
-        """transport fast path (integrators.ode.sample): kwargs of forward_with_cfg / forward -> lt_sample_ode"""
+    def _engine_sampler_args(self, x, use_cfg, kw):
+        """transport fast paths (models/_base.py: EngineSamplers): kwargs of forward_with_cfg / forward -> engine + step kwargs"""
         y = kw.pop("y")
         cfg_scale = kw.pop("cfg_scale") if use_cfg else 1.0
         rs, ntk = kw.pop("rope_scaling_factor", None), kw.pop("ntk_factor", None)
@@ -122,8 +122,7 @@ class DiT_Llama(EngineBackedModel):
             self._rope = (float(rs), float(ntk))
         eng = self.engine(x)
         eng.prepare_labels(y)
-        return eng.sample_ode(x, tgrid, method, use_cfg=use_cfg, cfg_scale=cfg_scale, scale_factor=self._rope[0],
-                              ntk_factor=self._rope[1], t_round_to_state_dtype=t_round)
+        return eng, dict(cfg_scale=cfg_scale, scale_factor=self._rope[0], ntk_factor=self._rope[1])
 
     @torch.no_grad()
     def forward(self, x, t, y):

@@ -19,7 +19,7 @@ import torch.nn as nn
 
 from .. import _lib
 from ..engine import DiTEngine, EngineLimits, ffn_hidden_dim
-from ._base import WeightWatch
+from ._base import EngineSamplers, WeightWatch
 from .components import AffineNorm, Linear, RMSNorm
 
 _normal002 = functools.partial(nn.init.normal_, std=0.02)
@@ -110,7 +110,7 @@ class CapEmbedder(nn.Sequential):
     pass
 
 
-class NextDiT(WeightWatch, nn.Module):
+class NextDiT(EngineSamplers, WeightWatch, nn.Module):
     """Diffusion transformer whose forward passes execute on the MI355X engine.
 
     Constructor signature and defaults follow the reference (model.py:670-685).  Extra, engine-only knobs
@@ -221,8 +221,8 @@ class NextDiT(WeightWatch, nn.Module):
         return self._call(x, t, cap_feats, cap_mask, True, cfg_scale=cfg_scale, scale_factor=scale_factor,
                           scale_watershed=scale_watershed, base_seqlen=base_seqlen, proportional_attn=proportional_attn)
 
-    def _engine_sample_ode(self, x, tgrid, method, use_cfg, t_round, kw):
-        """transport fast path (integrators.ode.sample): kwargs of forward_with_cfg / forward -> lt_sample_ode"""
+    def _engine_sampler_args(self, x, use_cfg, kw):
+        """transport fast paths (models/_base.py: EngineSamplers): kwargs of forward_with_cfg / forward -> engine + step kwargs"""
         cap_feats, cap_mask = kw.pop("cap_feats"), kw.pop("cap_mask")
         if use_cfg:
             args = dict(cfg_scale=kw.pop("cfg_scale"), scale_factor=kw.pop("scale_factor", 1.0),
@@ -234,7 +234,7 @@ class NextDiT(WeightWatch, nn.Module):
             raise TypeError(f"unexpected model kwargs for the engine path: {sorted(kw)}")
         eng = self.engine(x, cap_feats.shape[1])
         eng.prepare_prompt(cap_feats, cap_mask)
-        return eng.sample_ode(x, tgrid, method, use_cfg=use_cfg, t_round_to_state_dtype=t_round, **args)
+        return eng, args
 
     @torch.no_grad()
     def sample_views(self, z, tgrid, views, cap_feats, cap_mask, method: str = "midpoint", *, cfg_scale: float = 4.0,

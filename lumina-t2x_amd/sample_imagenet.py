@@ -11,6 +11,8 @@ there is no network here) - without it the final latents are written as ``.pt`` 
 ``--likelihood`` (sample.py:134-141; needs ``--cfg_scale 1``) integrates the likelihood ODE with the divergence taken by central
 differences through the forward-only engine (``Sampler.sample_ode_likelihood(divergence="fd")``) where the reference uses autograd;
 like the reference, the run then takes ``[-1]`` of the returned (logp, z) pair = the latent carried to the noise end.
+``SDE``: the whole Euler-Maruyama / Heun trajectory and its last step are ONE engine call (``lt_sample_sde``, one model evaluation per
+stage) - the sampler recognises ``model.forward_with_cfg``; nothing in this file changes for it.
 
     python -m lumina_t2x_amd.sample_imagenet ODE --ckpt /ckpts/next-dit-imagenet --sampling-method euler --num_sampling_steps 50
 """

@@ -18,6 +18,10 @@ not vendored).  Here:
   ``lumina_next_t2i/sample.py:77`` -> ``integrators.py:115``): fixed-grid ``heun2`` / ``heun3`` and adaptive ``bosh3`` /
   ``fehlberg2`` / ``adaptive_heun`` run on the same two host loops with their Butcher tableaus (restated from torchdiffeq 0.2.x,
   unpinned like the rest).  ``dopri8``, the Adams multistep family and ``scipy_solver`` are NOT built and say so by name.
+
+The SDE samplers (``class sde``: Euler-Maruyama / Heun, the reference's own code) run inside the engine as well when the model callable is
+engine-backed and predicts a velocity (``lt_sample_sde``: one evaluation per stage, coefficients from ``sde_table``); otherwise through the
+model callable, step by step, as the reference does.
 """
 import torch as th
 
@@ -318,10 +322,65 @@ class ode:
         return owner._engine_sample_ode(x, self.t, self.sampler_type, use_cfg, self.t_round_to_state_dtype, dict(kw))
 
 
-class sde:
-    """Euler-Maruyama / Heun SDE sampler (reference integrators.py:5-76); runs through the model callable."""
+_SDE_TENSOR_FORMS = ("SBDM", "sigma", "linear", "decreasing", "inccreasing-decreasing")  # "constant" yields a Python float (fails in th.sqrt)
 
-    def __init__(self, drift, diffusion, *, t0, t1, num_steps, sampler_type):
+
+def sde_table(plan, form, norm, t, dt, sampler_type, like, last_step=None, last_step_size=0.0, t1=None):
+    """Per-stage scalar coefficients of the SDE loop for ``lt_sample_sde``: every row of the batch carries the same t, so the
+    ``[B,1,1,1]`` tensors the path plan produces inside ``sde_drift`` are one value per stage.  They are computed HERE by the plan's own
+    functions on tensors of the state's dtype on the state's device (``like``), one row per step instead of one row per sample - the
+    same elementwise torch kernels the host loop runs, so the rounding is torch's, not a re-derivation - and read back once.
+
+    Returns ``(steps, last)``: ``steps`` fp32 CPU ``[(len(t) - 1) * stages, 8]`` with records ``t, r, var, D, q, dt, sqrt_dt, hdt``
+    (stages = 2 for Heun: the stage at t, then the stage at t + dt), ``last`` fp32 CPU ``[8]`` = ``t, r, var, D, h, a, c, 0`` at the fp32
+    time ``t1`` (None without a last step).  r = alpha / alpha', var = sigma^2 - r sigma' sigma (``get_score_from_velocity``), D the
+    diffusion coefficient, q = sqrt(2 D); dt, sqrt_dt and hdt = 0.5 dt are the fp32 values of the loop's 0-dim CPU tensors, which
+    PyTorch multiplies with a device tensor in fp32 whatever its dtype (they are NOT rounded to the state dtype)."""
+    dev, dtype = like.device, like.dtype
+    n = len(t) - 1
+    stages = 2 if sampler_type == "Heun" else 1
+
+    def coeffs(tvec, xl):
+        r, sigma_t, d_sigma_t = plan._ratio_and_coeffs(xl, tvec)
+        var = sigma_t**2 - r * d_sigma_t * sigma_t  # the denominator of ICPlan.get_score_from_velocity, same expression
+        D = plan.compute_diffusion(xl, tvec, form=form, norm=norm)
+        return [v.reshape(-1).float() for v in (r, var, D, th.sqrt(2 * D))]
+
+    with th.no_grad():
+        xl = th.zeros((n, 1, 1, 1), dtype=dtype, device=dev)
+        tvec = t[:-1].to(dev).to(dtype)  # th.ones(B).to(x) * t of the loop: the fp32 grid value rounded to the state dtype
+        rows = []
+        for k in range(stages):
+            tk = tvec if k == 0 else tvec + dt  # _heun: tvec + self.dt (state-dtype tensor + 0-dim CPU fp32 tensor)
+            rows.append(th.stack([tk.float()] + coeffs(tk, xl), dim=1))
+        last = None
+        if last_step is not None:
+            ts = th.ones(1, device=dev) * t1  # fp32, as Sampler.sample_sde builds it
+            r, var, D, _ = coeffs(ts, xl[:1])
+            a = plan.compute_alpha_t(ts)[0][0]
+            sg = plan.compute_sigma_t(ts)[0][0]
+            h = th.tensor([last_step_size], dtype=th.float32, device=dev)
+            last = th.cat([ts, r, var, D, h, a.to(dtype).float().reshape(1), ((sg**2) / a).reshape(1), th.zeros(1, device=dev)])
+        dev_rows = th.stack(rows, dim=1).reshape(n * stages, 5)  # step-major: stage 0, stage 1 of step 0, ...
+        packed = th.cat([dev_rows.reshape(-1)] + ([last] if last is not None else [])).cpu()  # the ONE read-back
+    steps = th.empty((n * stages, 8), dtype=th.float32)
+    steps[:, :5] = packed[: n * stages * 5].reshape(n * stages, 5)
+    steps[:, 5] = float(dt)
+    steps[:, 6] = float(th.sqrt(dt))
+    steps[:, 7] = float(0.5 * dt)
+    return steps, (packed[n * stages * 5:].clone() if last is not None else None)
+
+
+class sde:
+    """Euler-Maruyama / Heun SDE sampler (reference integrators.py:5-76).
+
+    With an engine-backed model callable, velocity prediction, a state on the GPU and a diffusion form that yields tensors the whole
+    trajectory - and, through ``sample_with_last_step``, the last-step rule - runs inside the C-ABI engine (``lt_sample_sde``: one host
+    loop in C++, ONE model evaluation per stage instead of the two of ``drift + diffusion * score``, the noise uploaded once).  Anything
+    else (another callable, score / noise prediction, a CPU state, the ``"constant"`` form) runs the reference's loop below through the
+    model callable, unchanged.  ``use_engine = False`` switches back to that loop."""
+
+    def __init__(self, drift, diffusion, *, t0, t1, num_steps, sampler_type, engine_plan=None, finish=None):
         assert t0 < t1, "SDE sampler has to be in forward time"
         self.num_timesteps = num_steps
         self.t = th.linspace(t0, t1, num_steps)
@@ -330,6 +389,10 @@ class sde:
         if sampler_type not in ("Euler", "Heun"):
             raise NotImplementedError("Smapler type not implemented.")
         self.sampler_type = sampler_type
+        # what Sampler.sample_sde knows and the engine path needs: dict(plan, form, norm, velocity, last_step, last_step_size, t1)
+        self.engine_plan = engine_plan
+        self.finish = finish
+        self.use_engine = True
 
     def _euler_maruyama(self, x, mean_x, t, model, **kw):
         noise = th.randn(x.size()).to(x)
@@ -347,7 +410,39 @@ class sde:
         k2 = self.drift(xhat + self.dt * k1, tvec + self.dt, model, **kw)
         return xhat + 0.5 * self.dt * (k1 + k2), xhat
 
+    def _engine_target(self, init, model):
+        ep = self.engine_plan
+        if not self.use_engine or ep is None or not ep["velocity"] or ep["form"] not in _SDE_TENSOR_FORMS:
+            return None
+        if not th.is_tensor(init) or not init.is_cuda or init.dtype not in (th.float32, th.bfloat16) or len(self.t) < 2:
+            return None
+        target = _engine_target(model)
+        return target if target is not None and hasattr(target[0], "_engine_sample_sde") else None
+
+    def _sample_on_engine(self, init, target, kw, with_last):
+        """the loop (and the last step) in one C-ABI call; the noise is drawn exactly as the loop draws it - one th.randn(x.size()) per
+        step from torch's CPU generator, in step order - into one pinned buffer that is uploaded once"""
+        owner, use_cfg = target
+        ep = self.engine_plan
+        last_step = ep["last_step"] if with_last else None
+        n = len(self.t) - 1
+        with th.no_grad():
+            steps, last = sde_table(ep["plan"], ep["form"], ep["norm"], self.t, self.dt, self.sampler_type, init, last_step,
+                                    ep["last_step_size"], ep["t1"])
+            draws = th.empty((n,) + tuple(init.shape), dtype=th.float32, pin_memory=True)
+            for i in range(n):
+                draws[i] = th.randn(init.size())
+            noise = draws.to(init.device, non_blocking=True).to(init.dtype)
+            _, traj, final = owner._engine_sample_sde(init, noise, steps, last, self.sampler_type, last_step, use_cfg, dict(kw))
+        xs = list(traj.unbind(0))
+        if with_last:
+            xs.append(final if final is not None else xs[-1])
+        return xs
+
     def sample(self, init, model, **model_kwargs):
+        target = self._engine_target(init, model)
+        if target is not None:
+            return self._sample_on_engine(init, target, model_kwargs, with_last=False)
         step = self._euler_maruyama if self.sampler_type == "Euler" else self._heun
         x = mean_x = init
         samples = []
@@ -356,3 +451,14 @@ class sde:
                 x, mean_x = step(x, mean_x, ti, model, **model_kwargs)
                 samples.append(x)
         return samples
+
+    def sample_with_last_step(self, init, model, **model_kwargs):
+        """``sample`` followed by the last-step rule ``finish`` at t1 (Sampler.sample_sde, reference transport.py:331-342): the list of
+        ``num_steps`` states"""
+        target = self._engine_target(init, model)
+        if target is not None:
+            return self._sample_on_engine(init, target, model_kwargs, with_last=True)
+        xs = self.sample(init, model, **model_kwargs)
+        ts = th.ones(init.size(0), device=init.device) * self.engine_plan["t1"]
+        xs.append(self.finish(xs[-1], ts, model, **model_kwargs))
+        return xs

@@ -199,16 +199,18 @@ class Sampler:
         tr = self.transport
         t0, t1 = tr.check_interval(tr.train_eps, tr.sample_eps, diffusion_form=diffusion_form, sde=True, eval=True,
                                    reverse=False, last_step_size=last_step_size)
-        solver = sde(sde_drift, sde_diffusion, t0=t0, t1=t1, num_steps=num_steps, sampler_type=sampling_method)
-        finish = self._last_step(sde_drift, last_step, last_step_size)
+        # what sde needs to run the loop and the last step inside the engine (integrators.py: sde_table / lt_sample_sde)
+        plan = dict(plan=tr.path_sampler, form=diffusion_form, norm=diffusion_norm, velocity=tr.model_type == ModelType.VELOCITY,
+                    last_step=last_step, last_step_size=last_step_size, t1=t1)
+        solver = sde(sde_drift, sde_diffusion, t0=t0, t1=t1, num_steps=num_steps, sampler_type=sampling_method, engine_plan=plan)
+        solver.finish = self._last_step(sde_drift, last_step, last_step_size)
 
         def _sample(init, model, **kw):
-            xs = solver.sample(init, model, **kw)
-            ts = th.ones(init.size(0), device=init.device) * t1
-            xs.append(finish(xs[-1], ts, model, **kw))
+            xs = solver.sample_with_last_step(init, model, **kw)
             assert len(xs) == num_steps, "Samples does not match the number of steps"
             return xs
 
+        _sample.solver = solver  # (solver.use_engine = False: back to the host loop through the model callable)
         return _sample
 
     def sample_ode_likelihood(self, *, sampling_method="dopri5", num_steps=50, atol=1e-6, rtol=1e-3, divergence="auto",
