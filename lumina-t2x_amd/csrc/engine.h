@@ -1,0 +1,191 @@
+// Internal to the host side of the library (engine.hip, samplers.hip): the engine object and what the whole-trajectory samplers need of
+// it.  Not a public header - include/lumina_dit.h is the ABI.
+#pragma once
+#include <map>
+#include <string>
+#include <vector>
+
+#include "../../include/lumina_dit.h"
+#include "common.h"
+#include "options.h"
+
+struct DevBuf {
+    void* p = nullptr;
+    size_t bytes = 0;
+};
+
+struct LayerW {
+    u16 *wqkv = nullptr, *wo = nullptr, *w13 = nullptr, *w2 = nullptr, *wkvy = nullptr;
+    u16 *q_norm_w = nullptr, *q_norm_b = nullptr, *k_norm_w = nullptr, *k_norm_b = nullptr;
+    u16 *ky_norm_w = nullptr, *ky_norm_b = nullptr, *gate = nullptr;
+    u16 *attn_norm1 = nullptr, *attn_norm2 = nullptr, *ffn_norm1 = nullptr, *ffn_norm2 = nullptr, *y_norm = nullptr;
+    u16 *ky = nullptr, *vty = nullptr;  // hoisted text K / V^T of the current prompt
+    // MoE family (models2.py:731-745): E experts per branch, w13 packed per expert [E][2F, d], w2 [E][d, F]
+    u16 *w13_t = nullptr, *w2_t = nullptr, *w13_s = nullptr, *w2_s = nullptr, *gate_t = nullptr, *gate_s = nullptr;
+    u16 *norm_time = nullptr, *norm_space = nullptr;
+};
+
+struct ProfClass {
+    double flops = 0;
+    long long launches = 0;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;
+    size_t used = 0;
+    size_t budget = (size_t)-1;  // bracket at most this many launches with events, count the rest (same launch mix every step)
+    long long skip = 0;          // ... starting with launch number `skip` after a reset (a window in the middle of a timed region)
+};
+
+// What differs between the reference's model families on this path (everything else is shared code):
+//                    NEXT_T2I (model.py:573-662)   NEXT_IMAGENET (models.py:759-833)   FLAG_T2I (lumina_t2i model.py:572-658)
+//  adaLN chunks      scale,gate | scale,gate       scale,gate | scale,gate             shift,scale,gate | shift,scale,gate
+//  pre-norm weight   attention_norm1 / ffn_norm1   none (PFRMSNorm)                    attention_norm / ffn_norm
+//  post-norm         attention_norm2 / ffn_norm2   attention_norm / ffn_norm           none
+//  gate              tanh                          tanh                                plain
+//  conditioning      text (cross-attn + pooled)    class label embedding               text (cross-attn + pooled)
+//  RoPE              2-D, watershed branches       2-D, (rope_scaling, ntk) at once    1-D over the flattened rows, eol tokens
+//  final layer       scale                         shift, scale                        shift, scale
+struct VariantDesc {
+    int chunks;                  // adaLN chunks per layer
+    int i_shift[2], i_scale[2], i_gate[2];  // chunk index of {attention, ffn} branch; -1 = absent
+    bool pre_w, post, gate_tanh, text, labels, rope_1d, eol;
+    int final_chunks;            // 1: scale;  2: shift, scale
+};
+
+// Stage times of a whole-trajectory call (samplers.hip).  The host fills a page-locked buffer (an async copy from pageable memory
+// synchronises), ONE async copy takes it to the device and evaluation number `call` of a batch of B rows reads dev + call * B.
+struct StageTimes {
+    float *dev = nullptr, *pinned = nullptr;
+    hipEvent_t copied = nullptr;  // the previous call's copy out of `pinned` has executed
+    int cap = 0;                  // floats
+    int reserve(int count) {
+        LT_CHECK_HIP(hipMalloc((void**)&dev, (size_t)count * sizeof(float)));
+        LT_CHECK_HIP(hipHostMalloc((void**)&pinned, (size_t)count * sizeof(float), hipHostMallocDefault));
+        cap = count;
+        return 0;
+    }
+    int create(int count) {  // lt_create
+        if (reserve(count)) return 1;
+        LT_CHECK_HIP(hipEventCreateWithFlags(&copied, hipEventDisableTiming));
+        return 0;
+    }
+    void release() {  // lt_destroy
+        if (dev) (void)hipFree(dev);
+        if (pinned) (void)hipHostFree(pinned);
+        if (copied) (void)hipEventDestroy(copied);
+        dev = nullptr; pinned = nullptr; copied = nullptr; cap = 0;
+    }
+    int ready(int count, hipStream_t s) {
+        if (cap < count) {  // beyond lt_create's 1024 times per batch row (a 257-point rk4 grid): the one case in which a sampler synchronises
+            LT_CHECK_HIP(hipStreamSynchronize(s));
+            if (dev) LT_CHECK_HIP(hipFree(dev));
+            if (pinned) LT_CHECK_HIP(hipHostFree(pinned));
+            dev = nullptr; pinned = nullptr; cap = 0;
+            if (reserve(count)) return 1;
+        }
+        LT_CHECK_HIP(hipEventSynchronize(copied));  // the previous trajectory's copy has left the staging buffer (normally long ago)
+        return 0;
+    }
+    // room for `count` times and `pinned` free to be written: the buffer to fill (nullptr after lt_set_error); commit sends it on its way
+    float* begin(int count, hipStream_t s) { return ready(count, s) ? nullptr : pinned; }
+    int commit(int count, hipStream_t s) {
+        LT_CHECK_HIP(hipMemcpyAsync(dev, pinned, (size_t)count * sizeof(float), hipMemcpyHostToDevice, s));
+        LT_CHECK_HIP(hipEventRecord(copied, s));
+        return 0;
+    }
+};
+
+struct lt_engine {
+    lt_config cfg;
+    LtEngineOptions opts;  // per-engine option overrides (lt_engine_set_option); LT_OPT_INHERIT slots follow the process defaults
+    VariantDesc v;
+    int d, L, H, Hkv, hd, F, dkv, qkvn, A, cap, nfinal, kpad, chunks, ld_mod;
+    std::vector<DevBuf> allocs;
+    std::vector<LayerW> lw;
+    // globals
+    u16 *xemb_w = nullptr, *xemb_b = nullptr, *t0_w = nullptr, *t0_b = nullptr, *t2_w = nullptr, *t2_b = nullptr;
+    u16 *capln_w = nullptr, *capln_b = nullptr, *cape_w = nullptr, *cape_b = nullptr, *pad_token = nullptr;
+    u16 *adaln_w = nullptr, *adaln_b = nullptr;  // [L*chunks*d + d, A], [L*chunks*d + d]
+    u16 *final_w = nullptr, *final_b = nullptr;
+    u16 *label_table = nullptr, *eol_token = nullptr;
+    int label_rows = 0;
+    std::map<std::string, bool> need;
+    bool weights_ok = false;
+    // round 6: the dense blocks' four GEMM weights (wqkv, wo, w13, w2 of every layer) are held either row-major or in the row-pair-interleaved
+    // layout the persistent GEMM reads with whole-line requests (GemmArgs::pair_ab); ensure_weight_layout converts all of them in place when an
+    // evaluation needs the other one (a change of regime: >= one tile per CU <-> the small-M kernels).  last_pair: what the last run_forward used.
+    bool w_pair = false, last_pair = false;
+    // workspace
+    u16 *x = nullptr, *h = nullptr, *qkv = nullptr, *q = nullptr, *k = nullptr, *vt = nullptr, *attn = nullptr;
+    u16 *o = nullptr, *u = nullptr, *patches = nullptr, *frows = nullptr, *mod = nullptr;
+    u16 *tfeat = nullptr, *t1 = nullptr, *temb = nullptr, *cap_ln = nullptr, *cap_emb = nullptr, *adaln_in = nullptr;
+    // MoE workspace: expert-sorted rows (moe.hip)
+    int E = 0, moe_tiles = 0;
+    int moe_mode = 0;  // 0: time + space MoE per block (models2.py), 1: time-routed MoE only (models.py), 2: token-routed only (models1.py)
+    u16 *moe_us = nullptr, *moe_ys = nullptr, *moe_logits = nullptr, *moe_wts = nullptr;
+    u16* gate_t_all = nullptr;  // [L * E, A]: every layer's time-router weight, contiguous (LayerW::gate_t point into it)
+    int *moe_sel = nullptr, *moe_pos = nullptr, *moe_tile_expert = nullptr, *moe_src = nullptr;
+    // round 5 (option moe_time_plan_hoist): one plan per layer for the time router, all written by ONE launch at the top of the evaluation
+    int *moe_tp_sel = nullptr, *moe_tp_pos = nullptr, *moe_tp_tile_expert = nullptr, *moe_tp_src = nullptr;
+    u16* moe_tp_wts = nullptr;
+    size_t moe_tp_stride_rows = 0, moe_tp_stride_src = 0;
+    bool moe_tp_live = false;  // this evaluation's time plans were hoisted (set by run_forward, read by moe_ffn / moe_y)
+    // parity hooks (lt_moe_routing_*): [L][2 branches][max rows][2] expert ids, recorded from / forced onto moe_route_kernel
+    int *moe_rec = nullptr, *moe_force = nullptr;
+    int moe_rec_on = 0, moe_force_rows = 0, moe_rec_rows = 0;
+    int qstat_slots = 32;
+    float* qstat = nullptr;  // [rows][qstat_slots] float2: LayerNorm partial sums of the Q columns, written by the fused QKV GEMM (GemmArgs::qstat)
+    float* ystat = nullptr;  // [rows][ystat_cap] floats: per-row sum-of-squares partials of the O / W2 projection's output (GemmArgs::ystat -> GatedResArgs::ystat)
+    int ystat_cap = 0;
+    float* attn_tail_ws = nullptr;  // hd 96 only: partials of the attention launch's split last query block (AttnArgs::tail_ws)
+    size_t attn_tail_ws_bytes = 0;
+    float* qmr = nullptr;    // [rows] float2 (mean, rstd) of the Q rows, reduced from qstat by the K pass of qk_norm_rope (AttnArgs::q_stat)
+    float* rope_tr = nullptr;  // the 2-D rotary table once more as [branch][freq][pos] (AttnArgs::rope_cs_t)
+    // split-K workspace of the 512-row-class GEMMs (GemmArgs::splitk_*): 128 tiles = one round of half the CUs
+    float* splitk_part = nullptr;
+    unsigned* splitk_cnt = nullptr;
+    // tail split of the grouped persistent GEMM (GemmArgs::tail_*; MoE engines with >= 4096 rows): fp32 parts + arrival counters
+    float* tail_part = nullptr;
+    unsigned* tail_cnt = nullptr;
+    long long tail_cap_parts = 0;
+    int splitk_tiles = 0;
+    u16 *capb = nullptr, *capn = nullptr, *kvy = nullptr;
+    float* txt_bias = nullptr;
+    float* rope = nullptr;
+    float rope_scale = -1.f, rope_ntk = -1.f;
+    int rope_len = 0;
+    int prompt_B = 0, prompt_T = 0, prompt_Tpad = 0;
+    // ode
+    void *ys[2] = {nullptr, nullptr}, *ymid = nullptr, *kbuf[4] = {nullptr, nullptr, nullptr, nullptr};
+    StageTimes times;  // stage times of a whole-trajectory call (samplers.hip)
+    // compositional (regional) text conditioning (lt_prepare_prompt_regional): Y captions, the first Y-1 belong to regions of
+    // the cond row, the last to the uncond row; 0 = off
+    int reg_Y = 0, reg_h = 1, reg_w = 1;
+    u16* reg_txt = nullptr;    // [Y, max_tokens, d] per-caption text attention outputs
+    size_t reg_txt_elems = 0;
+    int* reg_qmap = nullptr;   // [max_batch] query batch of each caption
+    int* pk_dev = nullptr;     // packed batches: [0,64) token counts, [64,128) grid widths
+    int pk_host[128] = {0};
+    long long last_nfe = 0;
+    // multi-view sampling (lt_set_views / lt_sample_views, views.hip): engine-owned tables of the V views over an h x w latent
+    int *vw_perm = nullptr, *vw_iperm = nullptr, *vw_hits = nullptr;  // [V][h w], [V][h w], [V h w + 1]
+    float *vw_vsign = nullptr, *vw_isign = nullptr;                   // [V][in_channels]
+    int vw_V = 0, vw_h = 0, vw_w = 0;
+    // HIP graphs of one model evaluation (forward_graphed): fixed staging buffers the captured kernels read / write, a private
+    // stream to capture on (the caller's stream may be the legacy null stream, which cannot capture), cached executables
+    struct GraphTally { double flops[3] = {0, 0, 0}; long long launches[3] = {0, 0, 0}; };  // what one replay stands for, per kernel class
+    struct GraphEntry { std::vector<char> key; hipGraphExec_t exec = nullptr; int uses = 0; bool failed = false; bool pair = false; GraphTally tally; };
+    GraphTally* tally = nullptr;  // set while a graph is being captured: ProfScope counts into it instead of timing
+    std::vector<GraphEntry> graphs;
+    void *g_x = nullptr, *g_out = nullptr;
+    float* g_t = nullptr;
+    hipStream_t cap_stream = nullptr;
+    long long graph_replays = 0;
+    // profiling
+    int prof_mask = 0;  // bit k: class k launches are bracketed by HIP events
+    bool prof_on = false;
+    ProfClass prof[3];
+};
+
+// one model evaluation [+ CFG combine], through a cached HIP graph where that pays (engine.hip)
+int forward_graphed(lt_engine* e, const void* x_in, const float* t_dev, void* out, const lt_step_args* a, int use_cfg, hipStream_t s);
+// frees the tables of lt_set_views (samplers.hip)
+void drop_views(lt_engine* e);

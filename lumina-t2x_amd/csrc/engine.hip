@@ -1,6 +1,7 @@
-// Host side of the C ABI (include/lumina_dit.h): engine object, weight arena, workspace, the per-NFE
-// launch sequence of NextDiT.forward / forward_with_cfg (lumina_next_t2i/models/model.py:836-913) and the
-// fixed-grid ODE loop of transport/integrators.py:104-116 (torchdiffeq euler / midpoint / rk4).
+// Host side of the C ABI (include/lumina_dit.h): engine object, weight arena, workspace, prompt preparation and ONE model evaluation - the
+// per-NFE launch sequence of NextDiT.forward / forward_with_cfg (lumina_next_t2i/models/model.py:836-913) and its HIP-graph cache - plus
+// the MoE routing, profiling and option hooks.  The whole-trajectory samplers (lt_sample_*) are in samplers.hip, the operator-level
+// entry points (lt_op_*) in ops_abi.hip, which needs no engine state; engine.h holds what this file and samplers.hip share.
 //
 // Everything here is asynchronous on the caller's stream: no host<->device sync inside a step (the
 // reference syncs >= 25 times per NFE: t[0].item() model.py:888, nonzero/.item() per layer :288-289).
@@ -13,14 +14,9 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <map>
-#include <string>
-#include <vector>
 
-#include "../../include/lumina_dit.h"
-#include "common.h"
+#include "engine.h"
 #include "kernels.h"
-#include "options.h"
 
 // ------------------------------------------------------------------------------------------------
 static thread_local char g_err[1024] = "";
@@ -50,50 +46,7 @@ constexpr float LOG2E = 1.44269504088896340736f;
 //                    1024 rows only (forward_graphed).  Every option
 //                    change moves lt_opt_generation(), which is part of the graph key (kernel selection is baked into a captured graph).
 
-struct DevBuf {
-    void* p = nullptr;
-    size_t bytes = 0;
-};
-
-struct LayerW {
-    u16 *wqkv = nullptr, *wo = nullptr, *w13 = nullptr, *w2 = nullptr, *wkvy = nullptr;
-    u16 *q_norm_w = nullptr, *q_norm_b = nullptr, *k_norm_w = nullptr, *k_norm_b = nullptr;
-    u16 *ky_norm_w = nullptr, *ky_norm_b = nullptr, *gate = nullptr;
-    u16 *attn_norm1 = nullptr, *attn_norm2 = nullptr, *ffn_norm1 = nullptr, *ffn_norm2 = nullptr, *y_norm = nullptr;
-    u16 *ky = nullptr, *vty = nullptr;  // hoisted text K / V^T of the current prompt
-    // MoE family (models2.py:731-745): E experts per branch, w13 packed per expert [E][2F, d], w2 [E][d, F]
-    u16 *w13_t = nullptr, *w2_t = nullptr, *w13_s = nullptr, *w2_s = nullptr, *gate_t = nullptr, *gate_s = nullptr;
-    u16 *norm_time = nullptr, *norm_space = nullptr;
-};
-
-struct ProfClass {
-    double flops = 0;
-    long long launches = 0;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;
-    size_t used = 0;
-    size_t budget = (size_t)-1;  // bracket at most this many launches with events, count the rest (same launch mix every step)
-    long long skip = 0;          // ... starting with launch number `skip` after a reset (a window in the middle of a timed region)
-};
-
-}  // namespace
-
-// What differs between the reference's model families on this path (everything else is shared code):
-//                    NEXT_T2I (model.py:573-662)   NEXT_IMAGENET (models.py:759-833)   FLAG_T2I (lumina_t2i model.py:572-658)
-//  adaLN chunks      scale,gate | scale,gate       scale,gate | scale,gate             shift,scale,gate | shift,scale,gate
-//  pre-norm weight   attention_norm1 / ffn_norm1   none (PFRMSNorm)                    attention_norm / ffn_norm
-//  post-norm         attention_norm2 / ffn_norm2   attention_norm / ffn_norm           none
-//  gate              tanh                          tanh                                plain
-//  conditioning      text (cross-attn + pooled)    class label embedding               text (cross-attn + pooled)
-//  RoPE              2-D, watershed branches       2-D, (rope_scaling, ntk) at once    1-D over the flattened rows, eol tokens
-//  final layer       scale                         shift, scale                        shift, scale
-struct VariantDesc {
-    int chunks;                  // adaLN chunks per layer
-    int i_shift[2], i_scale[2], i_gate[2];  // chunk index of {attention, ffn} branch; -1 = absent
-    bool pre_w, post, gate_tanh, text, labels, rope_1d, eol;
-    int final_chunks;            // 1: scale;  2: shift, scale
-};
-
-static VariantDesc variant_desc(int variant) {
+VariantDesc variant_desc(int variant) {
     VariantDesc v{};
     if (variant == LT_VARIANT_NEXT_T2I) {
         v = {4, {-1, -1}, {0, 2}, {1, 3}, true, true, true, true, false, false, false, 1};
@@ -110,103 +63,6 @@ static VariantDesc variant_desc(int variant) {
     }
     return v;
 }
-
-struct lt_engine {
-    lt_config cfg;
-    LtEngineOptions opts;  // per-engine option overrides (lt_engine_set_option); LT_OPT_INHERIT slots follow the process defaults
-    VariantDesc v;
-    int d, L, H, Hkv, hd, F, dkv, qkvn, A, cap, nfinal, kpad, chunks, ld_mod;
-    std::vector<DevBuf> allocs;
-    std::vector<LayerW> lw;
-    // globals
-    u16 *xemb_w = nullptr, *xemb_b = nullptr, *t0_w = nullptr, *t0_b = nullptr, *t2_w = nullptr, *t2_b = nullptr;
-    u16 *capln_w = nullptr, *capln_b = nullptr, *cape_w = nullptr, *cape_b = nullptr, *pad_token = nullptr;
-    u16 *adaln_w = nullptr, *adaln_b = nullptr;  // [L*chunks*d + d, A], [L*chunks*d + d]
-    u16 *final_w = nullptr, *final_b = nullptr;
-    u16 *label_table = nullptr, *eol_token = nullptr;
-    int label_rows = 0;
-    std::map<std::string, bool> need;
-    bool weights_ok = false;
-    // round 6: the dense blocks' four GEMM weights (wqkv, wo, w13, w2 of every layer) are held either row-major or in the row-pair-interleaved
-    // layout the persistent GEMM reads with whole-line requests (GemmArgs::pair_ab); ensure_weight_layout converts all of them in place when an
-    // evaluation needs the other one (a change of regime: >= one tile per CU <-> the small-M kernels).  last_pair: what the last run_forward used.
-    bool w_pair = false, last_pair = false;
-    // workspace
-    u16 *x = nullptr, *h = nullptr, *qkv = nullptr, *q = nullptr, *k = nullptr, *vt = nullptr, *attn = nullptr;
-    u16 *o = nullptr, *u = nullptr, *patches = nullptr, *frows = nullptr, *mod = nullptr;
-    u16 *tfeat = nullptr, *t1 = nullptr, *temb = nullptr, *cap_ln = nullptr, *cap_emb = nullptr, *adaln_in = nullptr;
-    // MoE workspace: expert-sorted rows (moe.hip)
-    int E = 0, moe_tiles = 0;
-    int moe_mode = 0;  // 0: time + space MoE per block (models2.py), 1: time-routed MoE only (models.py), 2: token-routed only (models1.py)
-    u16 *moe_us = nullptr, *moe_ys = nullptr, *moe_logits = nullptr, *moe_wts = nullptr;
-    u16* gate_t_all = nullptr;  // [L * E, A]: every layer's time-router weight, contiguous (LayerW::gate_t point into it)
-    int *moe_sel = nullptr, *moe_pos = nullptr, *moe_tile_expert = nullptr, *moe_src = nullptr;
-    // round 5 (option moe_time_plan_hoist): one plan per layer for the time router, all written by ONE launch at the top of the evaluation
-    int *moe_tp_sel = nullptr, *moe_tp_pos = nullptr, *moe_tp_tile_expert = nullptr, *moe_tp_src = nullptr;
-    u16* moe_tp_wts = nullptr;
-    size_t moe_tp_stride_rows = 0, moe_tp_stride_src = 0;
-    bool moe_tp_live = false;  // this evaluation's time plans were hoisted (set by run_forward, read by moe_ffn / moe_y)
-    // parity hooks (lt_moe_routing_*): [L][2 branches][max rows][2] expert ids, recorded from / forced onto moe_route_kernel
-    int *moe_rec = nullptr, *moe_force = nullptr;
-    int moe_rec_on = 0, moe_force_rows = 0, moe_rec_rows = 0;
-    int qstat_slots = 32;
-    float* qstat = nullptr;  // [rows][qstat_slots] float2: LayerNorm partial sums of the Q columns, written by the fused QKV GEMM (GemmArgs::qstat)
-    float* ystat = nullptr;  // [rows][ystat_cap] floats: per-row sum-of-squares partials of the O / W2 projection's output (GemmArgs::ystat -> GatedResArgs::ystat)
-    int ystat_cap = 0;
-    float* attn_tail_ws = nullptr;  // hd 96 only: partials of the attention launch's split last query block (AttnArgs::tail_ws)
-    size_t attn_tail_ws_bytes = 0;
-    float* qmr = nullptr;    // [rows] float2 (mean, rstd) of the Q rows, reduced from qstat by the K pass of qk_norm_rope (AttnArgs::q_stat)
-    float* rope_tr = nullptr;  // the 2-D rotary table once more as [branch][freq][pos] (AttnArgs::rope_cs_t)
-    // split-K workspace of the 512-row-class GEMMs (GemmArgs::splitk_*): 128 tiles = one round of half the CUs
-    float* splitk_part = nullptr;
-    unsigned* splitk_cnt = nullptr;
-    // tail split of the grouped persistent GEMM (GemmArgs::tail_*; MoE engines with >= 4096 rows): fp32 parts + arrival counters
-    float* tail_part = nullptr;
-    unsigned* tail_cnt = nullptr;
-    long long tail_cap_parts = 0;
-    int splitk_tiles = 0;
-    u16 *capb = nullptr, *capn = nullptr, *kvy = nullptr;
-    float* txt_bias = nullptr;
-    float* rope = nullptr;
-    float rope_scale = -1.f, rope_ntk = -1.f;
-    int rope_len = 0;
-    int prompt_B = 0, prompt_T = 0, prompt_Tpad = 0;
-    // ode
-    void *ys[2] = {nullptr, nullptr}, *ymid = nullptr, *kbuf[4] = {nullptr, nullptr, nullptr, nullptr};
-    float* t_dev = nullptr;
-    float* t_pinned = nullptr;       // page-locked staging of the stage times (an async copy from pageable memory synchronises)
-    hipEvent_t t_copied = nullptr;   // the previous call's copy out of t_pinned has executed
-    int t_cap = 0;
-    // compositional (regional) text conditioning (lt_prepare_prompt_regional): Y captions, the first Y-1 belong to regions of
-    // the cond row, the last to the uncond row; 0 = off
-    int reg_Y = 0, reg_h = 1, reg_w = 1;
-    u16* reg_txt = nullptr;    // [Y, max_tokens, d] per-caption text attention outputs
-    size_t reg_txt_elems = 0;
-    int* reg_qmap = nullptr;   // [max_batch] query batch of each caption
-    int* pk_dev = nullptr;     // packed batches: [0,64) token counts, [64,128) grid widths
-    int pk_host[128] = {0};
-    long long last_nfe = 0;
-    // multi-view sampling (lt_set_views / lt_sample_views, views.hip): engine-owned tables of the V views over an h x w latent
-    int *vw_perm = nullptr, *vw_iperm = nullptr, *vw_hits = nullptr;  // [V][h w], [V][h w], [V h w + 1]
-    float *vw_vsign = nullptr, *vw_isign = nullptr;                   // [V][in_channels]
-    int vw_V = 0, vw_h = 0, vw_w = 0;
-    // HIP graphs of one model evaluation (forward_graphed): fixed staging buffers the captured kernels read / write, a private
-    // stream to capture on (the caller's stream may be the legacy null stream, which cannot capture), cached executables
-    struct GraphTally { double flops[3] = {0, 0, 0}; long long launches[3] = {0, 0, 0}; };  // what one replay stands for, per kernel class
-    struct GraphEntry { std::vector<char> key; hipGraphExec_t exec = nullptr; int uses = 0; bool failed = false; bool pair = false; GraphTally tally; };
-    GraphTally* tally = nullptr;  // set while a graph is being captured: ProfScope counts into it instead of timing
-    std::vector<GraphEntry> graphs;
-    void *g_x = nullptr, *g_out = nullptr;
-    float* g_t = nullptr;
-    hipStream_t cap_stream = nullptr;
-    long long graph_replays = 0;
-    // profiling
-    int prof_mask = 0;  // bit k: class k launches are bracketed by HIP events
-    bool prof_on = false;
-    ProfClass prof[3];
-};
-
-namespace {
 
 int dev_alloc(lt_engine* e, void** out, size_t bytes, bool zero = true) {
     void* p = nullptr;
@@ -939,6 +795,8 @@ bool profiling_wants_events(const lt_engine* e) {
     return false;
 }
 
+}  // namespace
+
 int forward_graphed(lt_engine* e, const void* x_in, const float* t_dev, void* out, const lt_step_args* a, int use_cfg, hipStream_t s) {
     if (!lt_opt(OPT_GRAPH) || profiling_wants_events(e) || e->moe_rec_on || e->moe_force_rows) return run_forward(e, x_in, t_dev, out, a, use_cfg, s);
     const int B = a->batch;
@@ -1018,17 +876,6 @@ int forward_graphed(lt_engine* e, const void* x_in, const float* t_dev, void* ou
             if ((e->prof_mask >> k) & 1) { e->prof[k].flops += ge->tally.flops[k]; e->prof[k].launches += ge->tally.launches[k]; }
     return 0;
 }
-
-float bf16_round_host(float f) {
-    uint32_t u;
-    memcpy(&u, &f, 4);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    u &= 0xffff0000u;
-    memcpy(&f, &u, 4);
-    return f;
-}
-
-}  // namespace
 
 // =====================================================================================================
 extern "C" int lt_create(const lt_config* cfg, lt_engine** out) {
@@ -1226,11 +1073,8 @@ extern "C" int lt_create(const lt_config* cfg, lt_engine** out) {
         const size_t state = Bm * cfg->in_channels * Nm * cfg->patch_size * cfg->patch_size * sizeof(float);
         for (int i = 0; i < 2; ++i) { if (dev_alloc(e, &e->ys[i], state)) return fail(); }
         if (dev_alloc(e, &e->ymid, state)) return fail();
-        // stage times of lt_sample_ode: room for a 256-point grid of 4-stage steps without a (synchronising) reallocation
-        if (hipMalloc((void**)&e->t_dev, (size_t)1024 * Bm * sizeof(float)) != hipSuccess) return fail();
-        if (hipHostMalloc((void**)&e->t_pinned, (size_t)1024 * Bm * sizeof(float), hipHostMallocDefault) != hipSuccess) return fail();
-        if (hipEventCreateWithFlags(&e->t_copied, hipEventDisableTiming) != hipSuccess) return fail();
-        e->t_cap = (int)(1024 * Bm);
+        // stage times of the samplers: room for a 256-point grid of 4-stage steps without a (synchronising) reallocation
+        if (e->times.create((int)(1024 * Bm))) return fail();
         if (dev_alloc(e, &e->g_x, state)) return fail();
         if (dev_alloc(e, &e->g_out, state)) return fail();
         {
@@ -1245,25 +1089,12 @@ extern "C" int lt_create(const lt_config* cfg, lt_engine** out) {
     return 0;
 }
 
-static void drop_views(lt_engine* e) {
-    if (e->vw_perm) (void)hipFree(e->vw_perm);
-    if (e->vw_iperm) (void)hipFree(e->vw_iperm);
-    if (e->vw_hits) (void)hipFree(e->vw_hits);
-    if (e->vw_vsign) (void)hipFree(e->vw_vsign);
-    if (e->vw_isign) (void)hipFree(e->vw_isign);
-    e->vw_perm = e->vw_iperm = e->vw_hits = nullptr;
-    e->vw_vsign = e->vw_isign = nullptr;
-    e->vw_V = e->vw_h = e->vw_w = 0;
-}
-
 extern "C" void lt_destroy(lt_engine* e) {
     if (!e) return;
     for (auto& ge : e->graphs) if (ge.exec) (void)hipGraphExecDestroy(ge.exec);
     if (e->cap_stream) (void)hipStreamDestroy(e->cap_stream);
     for (auto& b : e->allocs) (void)hipFree(b.p);
-    if (e->t_dev) (void)hipFree(e->t_dev);
-    if (e->t_pinned) (void)hipHostFree(e->t_pinned);
-    if (e->t_copied) (void)hipEventDestroy(e->t_copied);
+    e->times.release();
     if (e->pk_dev) (void)hipFree(e->pk_dev);
     if (e->reg_txt) (void)hipFree(e->reg_txt);
     if (e->reg_qmap) (void)hipFree(e->reg_qmap);
@@ -1434,345 +1265,6 @@ extern "C" int lt_forward_cfg(lt_engine* e, const void* x_dev, const float* t_de
     return forward_graphed(e, x_dev, t_dev, out_dev, a, 1, (hipStream_t)stream);
 }
 
-extern "C" int lt_sample_ode(lt_engine* e, const void* z_dev, void* traj_dev, void* final_dev, const float* tgrid_host,
-                             int32_t n_grid, int32_t method, int32_t use_cfg, int32_t t_round, const lt_step_args* a,
-                             void* stream) {
-    LT_REQUIRE(e && z_dev && tgrid_host && a, "lt_sample_ode: null argument");
-    LtOptScope opt_scope(&e->opts);
-    LT_REQUIRE(n_grid >= 2, "lt_sample_ode: need at least 2 grid points");
-    LT_REQUIRE(method >= LT_ODE_EULER && method <= LT_ODE_RK4, "lt_sample_ode: unknown method %d", method);
-    hipStream_t s = (hipStream_t)stream;
-    const int B = a->batch;
-    // the state buffers were sized by lt_create for max_batch x max_tokens; check before the first copy into them (the model
-    // calls below validate the same things, but only after z has been copied)
-    LT_REQUIRE(B >= 1 && B <= e->cfg.max_batch, "lt_sample_ode: batch %d outside 1..max_batch %d", B, e->cfg.max_batch);
-    LT_REQUIRE(a->latent_h > 0 && a->latent_w > 0 && a->latent_h % e->cfg.patch_size == 0 && a->latent_w % e->cfg.patch_size == 0 &&
-                   (long long)(a->latent_h / e->cfg.patch_size) * (a->latent_w / e->cfg.patch_size) <= e->cfg.max_tokens,
-               "lt_sample_ode: latent %dx%d is not a positive multiple of the patch size or exceeds max_tokens %d", a->latent_h, a->latent_w,
-               e->cfg.max_tokens);
-    LT_REQUIRE(a->io_dtype == LT_BF16 || a->io_dtype == LT_F32, "io_dtype must be bf16 or f32");
-    const int stages = method == LT_ODE_EULER ? 1 : (method == LT_ODE_MIDPOINT ? 2 : 4);
-    const int ncalls = (n_grid - 1) * stages;
-    const long long n = (long long)B * e->cfg.in_channels * a->latent_h * a->latent_w;
-    const size_t esz = a->io_dtype == LT_BF16 ? 2 : 4;
-    const size_t sbytes = (size_t)n * esz;
-    const bool bf = a->io_dtype == LT_BF16;
-    // stage times; torchdiffeq's _PerturbFunc casts t to the state dtype before calling the model, then
-    // integrators.py:108 broadcasts it to an fp32 [B] vector
-    // (grids beyond the staging buffers' 1024 stage times per batch row - a 257-point rk4 grid - grow them: the one case in which
-    //  this call synchronises)
-    if (e->t_cap < ncalls * B) {
-        LT_CHECK_HIP(hipStreamSynchronize(s));
-        if (e->t_dev) LT_CHECK_HIP(hipFree(e->t_dev));
-        if (e->t_pinned) LT_CHECK_HIP(hipHostFree(e->t_pinned));
-        e->t_dev = nullptr; e->t_pinned = nullptr; e->t_cap = 0;
-        LT_CHECK_HIP(hipMalloc((void**)&e->t_dev, (size_t)ncalls * B * sizeof(float)));
-        LT_CHECK_HIP(hipHostMalloc((void**)&e->t_pinned, (size_t)ncalls * B * sizeof(float), hipHostMallocDefault));
-        e->t_cap = ncalls * B;
-    }
-    LT_CHECK_HIP(hipEventSynchronize(e->t_copied));  // the previous trajectory's copy has left the staging buffer (normally long ago)
-    std::vector<float> dts(n_grid - 1);
-    for (int i = 0; i + 1 < n_grid; ++i) {
-        const float t0 = tgrid_host[i], t1 = tgrid_host[i + 1];
-        const float dt = t1 - t0;
-        dts[i] = dt;
-        float ts[4];
-        if (method == LT_ODE_EULER) ts[0] = t0;
-        else if (method == LT_ODE_MIDPOINT) { ts[0] = t0; ts[1] = t0 + 0.5f * dt; }
-        else { ts[0] = t0; ts[1] = t0 + dt * (float)(1.0 / 3.0); ts[2] = t0 + dt * (float)(2.0 / 3.0); ts[3] = t1; }
-        for (int k = 0; k < stages; ++k) {
-            const float tv = (t_round && bf) ? bf16_round_host(ts[k]) : ts[k];
-            for (int b = 0; b < B; ++b) e->t_pinned[((size_t)i * stages + k) * B + b] = tv;
-        }
-    }
-    LT_CHECK_HIP(hipMemcpyAsync(e->t_dev, e->t_pinned, (size_t)ncalls * B * sizeof(float), hipMemcpyHostToDevice, s));
-    LT_CHECK_HIP(hipEventRecord(e->t_copied, s));
-    LT_CHECK_HIP(hipMemcpyAsync(e->ys[0], z_dev, sbytes, hipMemcpyDeviceToDevice, s));
-    if (traj_dev) LT_CHECK_HIP(hipMemcpyAsync(traj_dev, z_dev, sbytes, hipMemcpyDeviceToDevice, s));
-    int cur = 0;
-    long long nfe = 0;
-    auto model = [&](const void* y, int call, void* out) {
-        ++nfe;
-        return forward_graphed(e, y, e->t_dev + (size_t)call * B, out, a, use_cfg, s);
-    };
-    const int dt_code = bf ? 1 : 0;
-    for (int i = 0; i + 1 < n_grid; ++i) {
-        void* y0 = e->ys[cur];
-        void* y1 = e->ys[cur ^ 1];
-        // torchdiffeq multiplies the 0-dim DEVICE tensor dt = t1 - t0 (fp32) with the bf16 state / slopes; PyTorch's type
-        // promotion keeps bf16 and casts the 0-dim operand to it first, so with a bf16 state every `dt * k` of the reference
-        // sees bf16(dt) (0.5 dt is exact after that).  The stage TIMES above stay fp32 (t0 + dt / 2 is fp32 arithmetic).
-        const float dt = bf ? bf16_round_host(dts[i]) : dts[i];
-        const int c0 = i * stages;
-        if (method == LT_ODE_EULER) {
-            if (model(y0, c0, e->kbuf[0])) return 1;
-            if (launch_ode_combine(0, y0, e->kbuf[0], nullptr, nullptr, nullptr, y1, dt_code, dt, n, s)) return 1;
-        } else if (method == LT_ODE_MIDPOINT) {
-            if (model(y0, c0, e->kbuf[0])) return 1;
-            if (launch_ode_combine(0, y0, e->kbuf[0], nullptr, nullptr, nullptr, e->ymid, dt_code, 0.5f * dt, n, s)) return 1;
-            if (model(e->ymid, c0 + 1, e->kbuf[1])) return 1;
-            if (launch_ode_combine(0, y0, e->kbuf[1], nullptr, nullptr, nullptr, y1, dt_code, dt, n, s)) return 1;
-        } else {
-            if (model(y0, c0, e->kbuf[0])) return 1;
-            if (launch_ode_combine(1, y0, e->kbuf[0], nullptr, nullptr, nullptr, e->ymid, dt_code, dt, n, s)) return 1;
-            if (model(e->ymid, c0 + 1, e->kbuf[1])) return 1;
-            if (launch_ode_combine(2, y0, e->kbuf[0], e->kbuf[1], nullptr, nullptr, e->ymid, dt_code, dt, n, s)) return 1;
-            if (model(e->ymid, c0 + 2, e->kbuf[2])) return 1;
-            if (launch_ode_combine(3, y0, e->kbuf[0], e->kbuf[1], e->kbuf[2], nullptr, e->ymid, dt_code, dt, n, s)) return 1;
-            if (model(e->ymid, c0 + 3, e->kbuf[3])) return 1;
-            if (launch_ode_combine(4, y0, e->kbuf[0], e->kbuf[1], e->kbuf[2], e->kbuf[3], y1, dt_code, dt, n, s)) return 1;
-        }
-        if (traj_dev) LT_CHECK_HIP(hipMemcpyAsync((char*)traj_dev + (size_t)(i + 1) * sbytes, y1, sbytes, hipMemcpyDeviceToDevice, s));
-        cur ^= 1;
-    }
-    if (final_dev) LT_CHECK_HIP(hipMemcpyAsync(final_dev, e->ys[cur], sbytes, hipMemcpyDeviceToDevice, s));
-    e->last_nfe = nfe;
-    return 0;
-}
-
-// ---- multi-view (visual-anagram) sampling ------------------------------------------------------------------------------------------
-extern "C" int lt_set_views(lt_engine* e, const int32_t* perm_dev, const float* vsign_host, const float* isign_host, int32_t V, int32_t latent_h,
-                            int32_t latent_w, void* stream) {
-    LT_REQUIRE(e, "lt_set_views: null engine");
-    hipStream_t s = (hipStream_t)stream;
-    const lt_config& c = e->cfg;
-    LT_REQUIRE(c.variant == LT_VARIANT_NEXT_T2I, "lt_set_views: multi-view sampling drives the text-conditional Next-DiT (LT_VARIANT_NEXT_T2I) only; "
-               "this engine is variant %d", c.variant);
-    if (V == 0 && !perm_dev) {  // drop the tables (kernels of an earlier trajectory may still read them)
-        LT_CHECK_HIP(hipStreamSynchronize(s));
-        drop_views(e);
-        return 0;
-    }
-    LT_REQUIRE(perm_dev && vsign_host && isign_host, "lt_set_views: null argument");
-    LT_REQUIRE(V >= 1, "lt_set_views: V = %d views (need at least 1)", V);
-    LT_REQUIRE(2 * (long long)V <= c.max_batch, "lt_set_views: %d views need a batch of 2 V = %d rows (view prompts + negative prompts), max_batch is %d", V,
-               2 * V, c.max_batch);
-    LT_REQUIRE(latent_h > 0 && latent_w > 0 && latent_h % c.patch_size == 0 && latent_w % c.patch_size == 0 &&
-                   (long long)(latent_h / c.patch_size) * (latent_w / c.patch_size) <= c.max_tokens,
-               "lt_set_views: latent %dx%d is not a positive multiple of the patch size %d or exceeds max_tokens %d x patch_size^2", latent_h, latent_w,
-               c.patch_size, c.max_tokens);
-    const int C = c.in_channels, HW = latent_h * latent_w;
-    LT_REQUIRE(HW % 4 == 0, "lt_set_views: H * W = %d must be a multiple of 4", HW);
-    for (int i = 0; i < V * C; ++i)
-        LT_REQUIRE((vsign_host[i] == 1.f || vsign_host[i] == -1.f) && (isign_host[i] == 1.f || isign_host[i] == -1.f),
-                   "lt_set_views: sign of view %d, channel %d is not +1 / -1", i / C, i % C);
-    LT_CHECK_HIP(hipStreamSynchronize(s));  // table upload may synchronise; kernels of an earlier trajectory may still read the old tables
-    drop_views(e);
-    const size_t tb = (size_t)V * HW * sizeof(int);
-    auto fail = [&]() { drop_views(e); return 1; };
-    if (hipMalloc((void**)&e->vw_perm, tb) != hipSuccess || hipMalloc((void**)&e->vw_iperm, tb) != hipSuccess ||
-        hipMalloc((void**)&e->vw_hits, tb + sizeof(int)) != hipSuccess || hipMalloc((void**)&e->vw_vsign, (size_t)V * C * sizeof(float)) != hipSuccess ||
-        hipMalloc((void**)&e->vw_isign, (size_t)V * C * sizeof(float)) != hipSuccess) {
-        lt_set_error("lt_set_views: out of device memory for the tables of %d views of %d pixels", V, HW);
-        return fail();
-    }
-    int bad = -1;
-    if (hipMemcpyAsync(e->vw_perm, perm_dev, tb, hipMemcpyDeviceToDevice, s) != hipSuccess ||
-        hipMemsetAsync(e->vw_iperm, 0, tb, s) != hipSuccess ||
-        hipMemcpyAsync(e->vw_vsign, vsign_host, (size_t)V * C * sizeof(float), hipMemcpyHostToDevice, s) != hipSuccess ||
-        hipMemcpyAsync(e->vw_isign, isign_host, (size_t)V * C * sizeof(float), hipMemcpyHostToDevice, s) != hipSuccess ||
-        launch_views_invert(e->vw_perm, e->vw_iperm, e->vw_hits, V, HW, s) ||
-        hipMemcpyAsync(&bad, e->vw_hits + (size_t)V * HW, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipStreamSynchronize(s) != hipSuccess) {
-        lt_set_error("lt_set_views: uploading the view tables failed");
-        return fail();
-    }
-    if (bad != 0) {
-        lt_set_error("lt_set_views: a view table is not a bijection on [0, %d): %d entries are out of range or name a pixel a second time", HW, bad);
-        return fail();
-    }
-    e->vw_V = V; e->vw_h = latent_h; e->vw_w = latent_w;
-    return 0;
-}
-
-extern "C" int lt_sample_views(lt_engine* e, const void* z_dev, void* traj_dev, void* final_dev, const float* tgrid_host, int32_t n_grid,
-                               int32_t method, const lt_step_args* a, void* stream) {
-    LT_REQUIRE(e && z_dev && tgrid_host && a, "lt_sample_views: null argument");
-    LtOptScope opt_scope(&e->opts);
-    LT_REQUIRE(e->cfg.variant == LT_VARIANT_NEXT_T2I, "lt_sample_views: multi-view sampling drives the text-conditional Next-DiT (LT_VARIANT_NEXT_T2I) "
-               "only; this engine is variant %d", e->cfg.variant);
-    LT_REQUIRE(n_grid >= 2, "lt_sample_views: need at least 2 grid points");
-    LT_REQUIRE(method != LT_ODE_RK4, "lt_sample_views: rk4 is not a multi-view method (the reference steps views with its midpoint_solver; euler is the "
-               "one-stage form)");
-    LT_REQUIRE(method == LT_ODE_EULER || method == LT_ODE_MIDPOINT, "lt_sample_views: unknown method %d", method);
-    LT_REQUIRE(e->vw_V >= 1, "lt_sample_views: no view tables (call lt_set_views first)");
-    const int V = e->vw_V, B = 2 * V, C = e->cfg.in_channels, HW = e->vw_h * e->vw_w;
-    LT_REQUIRE(a->batch == B, "lt_sample_views: %d views need a->batch = 2 V = %d (view prompts + negative prompts), got %d", V, B, a->batch);
-    LT_REQUIRE(a->latent_h == e->vw_h && a->latent_w == e->vw_w, "lt_sample_views: the view tables are for a %dx%d latent, the call has %dx%d", e->vw_h,
-               e->vw_w, a->latent_h, a->latent_w);
-    LT_REQUIRE(a->io_dtype == LT_BF16 || a->io_dtype == LT_F32, "io_dtype must be bf16 or f32");
-    LT_REQUIRE(B <= e->cfg.max_batch, "lt_sample_views: batch %d exceeds max_batch %d", B, e->cfg.max_batch);
-    LT_REQUIRE(e->reg_Y == 0 && e->prompt_B == B, "lt_prepare_prompt was called for batch %d, step has batch %d (multi-view sampling needs the V view "
-               "prompts followed by V rows of the negative prompt)", e->prompt_B, B);
-    hipStream_t s = (hipStream_t)stream;
-    const int stages = method == LT_ODE_EULER ? 1 : 2;
-    const int ncalls = (n_grid - 1) * stages;
-    const bool bf = a->io_dtype == LT_BF16;
-    const size_t sbytes = (size_t)C * HW * (bf ? 2 : 4);  // ONE latent
-    if (e->t_cap < ncalls * B) {  // (as lt_sample_ode: the one case in which this call synchronises)
-        LT_CHECK_HIP(hipStreamSynchronize(s));
-        if (e->t_dev) LT_CHECK_HIP(hipFree(e->t_dev));
-        if (e->t_pinned) LT_CHECK_HIP(hipHostFree(e->t_pinned));
-        e->t_dev = nullptr; e->t_pinned = nullptr; e->t_cap = 0;
-        LT_CHECK_HIP(hipMalloc((void**)&e->t_dev, (size_t)ncalls * B * sizeof(float)));
-        LT_CHECK_HIP(hipHostMalloc((void**)&e->t_pinned, (size_t)ncalls * B * sizeof(float), hipHostMallocDefault));
-        e->t_cap = ncalls * B;
-    }
-    LT_CHECK_HIP(hipEventSynchronize(e->t_copied));
-    // generate.py:212-219: t0, t1 are Python floats (the fp32 grid's values as doubles); dt = t1 - t0 and half_dt = 0.5 dt are doubles that
-    // multiply a tensor as fp32 scalars; the stage times are torch.full((2,), t0) and torch.full((2,), t0 + half_dt): fp32 of the double
-    std::vector<float> dts(n_grid - 1), hdts(n_grid - 1);
-    for (int i = 0; i + 1 < n_grid; ++i) {
-        const double t0 = tgrid_host[i], dt = (double)tgrid_host[i + 1] - t0, half_dt = 0.5 * dt;
-        dts[i] = (float)dt;
-        hdts[i] = (float)half_dt;
-        const float ts[2] = {(float)t0, (float)(t0 + half_dt)};
-        for (int k = 0; k < stages; ++k)
-            for (int b = 0; b < B; ++b) e->t_pinned[((size_t)i * stages + k) * B + b] = ts[k];
-    }
-    LT_CHECK_HIP(hipMemcpyAsync(e->t_dev, e->t_pinned, (size_t)ncalls * B * sizeof(float), hipMemcpyHostToDevice, s));
-    LT_CHECK_HIP(hipEventRecord(e->t_copied, s));
-    LT_CHECK_HIP(hipMemcpyAsync(e->ys[0], z_dev, sbytes, hipMemcpyDeviceToDevice, s));
-    if (traj_dev) LT_CHECK_HIP(hipMemcpyAsync(traj_dev, z_dev, sbytes, hipMemcpyDeviceToDevice, s));
-    int cur = 0;
-    long long nfe = 0;
-    // one evaluation of ALL views: forward_with_cfg on 2 V rows, rows 0..V-1 = the viewed latents (it reads the first half only)
-    auto model = [&](int call, void* out) {
-        ++nfe;
-        return forward_graphed(e, e->ymid, e->t_dev + (size_t)call * B, out, a, 1, s);
-    };
-    const int dt_code = bf ? 1 : 0;
-    for (int i = 0; i + 1 < n_grid; ++i) {
-        void* y0 = e->ys[cur];
-        void* y1 = e->ys[cur ^ 1];
-        const int c0 = i * stages;
-        const void* slope = e->kbuf[0];
-        if (launch_views_gather(y0, e->vw_perm, e->vw_vsign, nullptr, e->ymid, 0.f, V, C, HW, dt_code, s)) return 1;
-        if (model(c0, e->kbuf[0])) return 1;
-        if (method == LT_ODE_MIDPOINT) {
-            if (launch_views_gather(y0, e->vw_perm, e->vw_vsign, e->kbuf[0], e->ymid, hdts[i], V, C, HW, dt_code, s)) return 1;
-            if (model(c0 + 1, e->kbuf[1])) return 1;
-            slope = e->kbuf[1];
-        }
-        if (launch_views_reduce(y0, slope, e->vw_iperm, e->vw_isign, y1, dts[i], V, C, HW, dt_code, s)) return 1;
-        if (traj_dev) LT_CHECK_HIP(hipMemcpyAsync((char*)traj_dev + (size_t)(i + 1) * sbytes, y1, sbytes, hipMemcpyDeviceToDevice, s));
-        cur ^= 1;
-    }
-    if (final_dev) LT_CHECK_HIP(hipMemcpyAsync(final_dev, e->ys[cur], sbytes, hipMemcpyDeviceToDevice, s));
-    e->last_nfe = nfe;
-    return 0;
-}
-
-extern "C" int lt_op_views_invert(const int32_t* perm_dev, int32_t* iperm_dev, int32_t* hits_dev, int32_t V, int32_t HW, void* stream) {
-    return launch_views_invert(perm_dev, iperm_dev, hits_dev, V, HW, (hipStream_t)stream);
-}
-extern "C" int lt_op_views_gather(const void* y_dev, const int32_t* perm_dev, const float* vsign_dev, const void* f0_dev, void* out_dev, float half_dt,
-                                  int32_t V, int32_t C, int32_t HW, int32_t dtype, void* stream) {
-    return launch_views_gather(y_dev, perm_dev, vsign_dev, f0_dev, out_dev, half_dt, V, C, HW, dtype, (hipStream_t)stream);
-}
-extern "C" int lt_op_views_reduce(const void* y_dev, const void* f_dev, const int32_t* iperm_dev, const float* isign_dev, void* out_dev, float dt,
-                                  int32_t V, int32_t C, int32_t HW, int32_t dtype, void* stream) {
-    return launch_views_reduce(y_dev, f_dev, iperm_dev, isign_dev, out_dev, dt, V, C, HW, dtype, (hipStream_t)stream);
-}
-
-// ---- SDE sampling (sde.hip) --------------------------------------------------------------------------------------------------------
-extern "C" int lt_sample_sde(lt_engine* e, const void* z_dev, const void* noise_dev, void* traj_dev, void* final_dev, const float* steps_host,
-                             int32_t n_steps, int32_t method, int32_t last_step, const float* last_coef_host, int32_t use_cfg,
-                             const lt_step_args* a, void* stream) {
-    LT_REQUIRE(e && z_dev && noise_dev && steps_host && a, "lt_sample_sde: null argument");
-    LtOptScope opt_scope(&e->opts);
-    LT_REQUIRE(n_steps >= 2, "lt_sample_sde: n_steps %d (need at least 2: one loop step and the last step)", n_steps);
-    LT_REQUIRE(method == LT_SDE_EULER || method == LT_SDE_HEUN, "lt_sample_sde: unknown method %d", method);
-    LT_REQUIRE(last_step >= LT_SDE_LAST_NONE && last_step <= LT_SDE_LAST_EULER, "lt_sample_sde: unknown last_step %d", last_step);
-    LT_REQUIRE(last_step == LT_SDE_LAST_NONE || (last_coef_host && final_dev), "lt_sample_sde: null argument (a last step needs last_coef_host and "
-               "final_dev)");
-    hipStream_t s = (hipStream_t)stream;
-    const int B = a->batch;
-    LT_REQUIRE(B >= 1 && B <= e->cfg.max_batch, "lt_sample_sde: batch %d outside 1..max_batch %d", B, e->cfg.max_batch);
-    LT_REQUIRE(a->latent_h > 0 && a->latent_w > 0 && a->latent_h % e->cfg.patch_size == 0 && a->latent_w % e->cfg.patch_size == 0 &&
-                   (long long)(a->latent_h / e->cfg.patch_size) * (a->latent_w / e->cfg.patch_size) <= e->cfg.max_tokens,
-               "lt_sample_sde: latent %dx%d is not a positive multiple of the patch size or exceeds max_tokens %d", a->latent_h, a->latent_w,
-               e->cfg.max_tokens);
-    LT_REQUIRE(a->io_dtype == LT_BF16 || a->io_dtype == LT_F32, "io_dtype must be bf16 or f32");
-    const int stages = method == LT_SDE_EULER ? 1 : 2;
-    const int nloop = n_steps - 1;
-    const int nrec = nloop * stages;
-    const int has_last = last_step != LT_SDE_LAST_NONE;
-    const int ncalls = nrec + has_last;
-    // the score divides by var = sigma^2 - r sigma' sigma (path.py: get_score_from_velocity); the last-step rule Euler has no score
-    for (int i = 0; i < nrec; ++i) {
-        const float var = steps_host[(size_t)i * LT_SDE_REC + 2];
-        LT_REQUIRE(std::isfinite(var) && var > 0.f, "lt_sample_sde: var %g of stage %d (step %d) is not finite and positive", (double)var, i % stages,
-                   i / stages);
-    }
-    if (last_step == LT_SDE_LAST_MEAN || last_step == LT_SDE_LAST_TWEEDIE)
-        LT_REQUIRE(std::isfinite(last_coef_host[2]) && last_coef_host[2] > 0.f, "lt_sample_sde: var %g of the last step is not finite and positive",
-                   (double)last_coef_host[2]);
-    const long long n = (long long)B * e->cfg.in_channels * a->latent_h * a->latent_w;
-    const bool bf = a->io_dtype == LT_BF16;
-    const size_t sbytes = (size_t)n * (bf ? 2 : 4);
-    if (e->t_cap < ncalls * B) {  // (as lt_sample_ode: the one case in which this call synchronises)
-        LT_CHECK_HIP(hipStreamSynchronize(s));
-        if (e->t_dev) LT_CHECK_HIP(hipFree(e->t_dev));
-        if (e->t_pinned) LT_CHECK_HIP(hipHostFree(e->t_pinned));
-        e->t_dev = nullptr; e->t_pinned = nullptr; e->t_cap = 0;
-        LT_CHECK_HIP(hipMalloc((void**)&e->t_dev, (size_t)ncalls * B * sizeof(float)));
-        LT_CHECK_HIP(hipHostMalloc((void**)&e->t_pinned, (size_t)ncalls * B * sizeof(float), hipHostMallocDefault));
-        e->t_cap = ncalls * B;
-    }
-    LT_CHECK_HIP(hipEventSynchronize(e->t_copied));
-    // stage times: the loop hands the model a [B] vector of the state dtype (integrators.py: th.ones(B).to(x) * t), the last step an fp32 one
-    for (int i = 0; i < ncalls; ++i) {
-        const float tv = i < nrec ? steps_host[(size_t)i * LT_SDE_REC] : last_coef_host[0];
-        for (int b = 0; b < B; ++b) e->t_pinned[(size_t)i * B + b] = tv;
-    }
-    LT_CHECK_HIP(hipMemcpyAsync(e->t_dev, e->t_pinned, (size_t)ncalls * B * sizeof(float), hipMemcpyHostToDevice, s));
-    LT_CHECK_HIP(hipEventRecord(e->t_copied, s));
-    LT_CHECK_HIP(hipMemcpyAsync(e->ys[0], z_dev, sbytes, hipMemcpyDeviceToDevice, s));
-    int cur = 0;
-    long long nfe = 0;
-    auto model = [&](const void* y, int call, void* out) {
-        ++nfe;
-        return forward_graphed(e, y, e->t_dev + (size_t)call * B, out, a, use_cfg, s);
-    };
-    const int dt_code = bf ? 1 : 0;
-    for (int i = 0; i < nloop; ++i) {
-        void* y0 = e->ys[cur];
-        void* y1 = e->ys[cur ^ 1];
-        const void* w = (const char*)noise_dev + (size_t)i * sbytes;
-        const float* rec = steps_host + (size_t)i * stages * LT_SDE_REC;
-        const int c0 = i * stages;
-        if (method == LT_SDE_EULER) {
-            if (model(y0, c0, e->kbuf[0])) return 1;
-            if (launch_sde_step(LT_SDE_OP_EULER, y0, e->kbuf[0], w, nullptr, nullptr, y1, nullptr, rec, n, dt_code, s)) return 1;
-        } else {  // xhat in ymid, K1 in kbuf[1], the predictor state in kbuf[2]
-            if (launch_sde_step(LT_SDE_OP_HEUN_XHAT, y0, nullptr, w, nullptr, nullptr, e->ymid, nullptr, rec, n, dt_code, s)) return 1;
-            if (model(e->ymid, c0, e->kbuf[0])) return 1;
-            if (launch_sde_step(LT_SDE_OP_HEUN_K1, e->ymid, e->kbuf[0], nullptr, nullptr, nullptr, e->kbuf[2], e->kbuf[1], rec, n, dt_code, s)) return 1;
-            if (model(e->kbuf[2], c0 + 1, e->kbuf[3])) return 1;
-            if (launch_sde_step(LT_SDE_OP_HEUN_OUT, e->ymid, e->kbuf[3], nullptr, e->kbuf[1], e->kbuf[2], y1, nullptr, rec + LT_SDE_REC, n, dt_code, s))
-                return 1;
-        }
-        if (traj_dev) LT_CHECK_HIP(hipMemcpyAsync((char*)traj_dev + (size_t)i * sbytes, y1, sbytes, hipMemcpyDeviceToDevice, s));
-        cur ^= 1;
-    }
-    if (has_last) {
-        const int op = last_step == LT_SDE_LAST_MEAN ? LT_SDE_OP_LAST_MEAN : (last_step == LT_SDE_LAST_TWEEDIE ? LT_SDE_OP_LAST_TWEEDIE : LT_SDE_OP_LAST_EULER);
-        if (model(e->ys[cur], nrec, e->kbuf[0])) return 1;
-        if (launch_sde_step(op, e->ys[cur], e->kbuf[0], nullptr, nullptr, nullptr, final_dev, nullptr, last_coef_host, n, dt_code, s)) return 1;
-    } else if (final_dev) {
-        LT_CHECK_HIP(hipMemcpyAsync(final_dev, e->ys[cur], sbytes, hipMemcpyDeviceToDevice, s));
-    }
-    e->last_nfe = nfe;
-    return 0;
-}
-
-extern "C" int lt_op_sde_step(int32_t op, const void* x_dev, const void* v_dev, const void* w_dev, const void* k1_dev, const void* xp_dev,
-                              void* out_dev, void* out2_dev, const float* rec_host, int64_t n, int32_t dtype, void* stream) {
-    return launch_sde_step(op, x_dev, v_dev, w_dev, k1_dev, xp_dev, out_dev, out2_dev, rec_host, (long long)n, dtype, (hipStream_t)stream);
-}
-
-extern "C" int64_t lt_last_nfe(lt_engine* e) { return e ? e->last_nfe : -1; }
 extern "C" int64_t lt_graph_replays(lt_engine* e) { return e ? e->graph_replays : -1; }
 
 // ---- MoE routing parity hooks -------------------------------------------------------------------------
@@ -1964,335 +1456,4 @@ extern "C" int lt_engine_get_option(lt_engine* e, const char* name, int32_t* val
     LtOptScope opt_scope(e ? &e->opts : nullptr);  // e == NULL: the process default
     *value = lt_opt(id);
     return 0;
-}
-
-// ---- operator-level entry points ---------------------------------------------------------------------------
-extern "C" int lt_op_gemm_bf16(const void* A, const void* W, const void* bias, int32_t bias_dtype, void* C, int32_t M,
-                               int32_t N, int32_t K, int32_t epilogue, int32_t variant, void* stream) {
-    LT_REQUIRE(A && W && C, "lt_op_gemm_bf16: null pointer");
-    GemmArgs g;
-    g.A = (const u16*)A; g.W = (const u16*)W; g.C = (u16*)C; g.bias = bias; g.M = M; g.N = N; g.K = K;
-    g.lda = K; g.ldw = K; g.ldc = epilogue == 1 ? N / 2 : N; g.bias_dtype = bias ? bias_dtype : -1;
-    return launch_gemm_bf16(g, epilogue, variant, (hipStream_t)stream);
-}
-
-// round 6: the row-pair-interleaved operand layout of the persistent GEMM (GemmArgs::pair_ab) at the op level
-extern "C" int lt_op_pair_layout(void* m, int64_t rows, int32_t cols, int32_t to_pair, void* stream) {
-    LT_REQUIRE(m, "lt_op_pair_layout: null pointer");
-    return launch_pair_layout((u16*)m, rows, cols, to_pair, (hipStream_t)stream);
-}
-extern "C" int lt_op_gemm_bf16_pair(const void* A, const void* W, void* C, int32_t M, int32_t N, int32_t K, int32_t epilogue, int32_t pair_c,
-                                    void* stream) {
-    LT_REQUIRE(A && W && C, "lt_op_gemm_bf16_pair: null pointer");
-    GemmArgs g;
-    g.A = (const u16*)A; g.W = (const u16*)W; g.C = (u16*)C; g.bias = nullptr; g.M = M; g.N = N; g.K = K;
-    g.lda = K; g.ldw = K; g.ldc = epilogue == 1 ? N / 2 : N; g.bias_dtype = -1; g.pair_ab = 3; g.pair_c = pair_c;
-    return launch_gemm_bf16(g, epilogue, 0, (hipStream_t)stream);
-}
-
-extern "C" int lt_op_gemm_vt(const void* A, const void* W, void* vt, int32_t M, int32_t N, int32_t K, int32_t tokens, int32_t hd,
-                             int32_t variant, void* stream) {
-    LT_REQUIRE(A && W && vt, "lt_op_gemm_vt: null pointer");
-    GemmArgs g;
-    g.A = (const u16*)A; g.W = (const u16*)W; g.C = (u16*)vt; g.bias = nullptr; g.M = M; g.N = N; g.K = K;
-    g.lda = K; g.ldw = K; g.ldc = 0; g.bias_dtype = -1; g.vt_tokens = tokens; g.vt_hd = hd; g.vt_npad = tokens;
-    return launch_gemm_bf16(g, 2, variant, (hipStream_t)stream);
-}
-
-extern "C" int lt_op_gemm_qkv(const void* A, const void* W, void* C, void* vt, int32_t M, int32_t N, int32_t K, int32_t split,
-                              int32_t tokens, int32_t hd, void* stream) {
-    LT_REQUIRE(A && W && C && vt, "lt_op_gemm_qkv: null pointer");
-    GemmArgs g;
-    g.A = (const u16*)A; g.W = (const u16*)W; g.C = (u16*)C; g.bias = nullptr; g.bias_dtype = -1; g.M = M; g.N = N; g.K = K;
-    g.lda = K; g.ldw = K; g.ldc = N; g.VT = (u16*)vt; g.vt_split = split; g.vt_tokens = tokens; g.vt_hd = hd; g.vt_npad = tokens;
-    return launch_gemm_bf16(g, 3, 0, (hipStream_t)stream);
-}
-
-// The fused QKV launch with the Q columns' LayerNorm partials (GemmArgs::qstat) followed by the K pass of qk_norm_rope that reduces
-// them (QkPostArgs::qstat_in): exactly the two launches the engine makes per layer on the attn_q_fused path.
-extern "C" int lt_op_qkv_qstat(const void* A, const void* W, void* C, void* vt, int32_t M, int32_t N, int32_t K, int32_t split, int32_t tokens,
-                               int32_t hd, int32_t q_cols, const void* k_ln_w, const void* k_ln_b, const void* cs_table, int32_t grid_w,
-                               float k_out_scale, void* k_out, void* qstat_ws, void* q_mean_rstd, void* stream) {
-    LT_REQUIRE(A && W && C && vt && k_ln_w && k_ln_b && cs_table && k_out && qstat_ws && q_mean_rstd, "lt_op_qkv_qstat: null pointer");
-    LT_REQUIRE(hd > 0 && q_cols > 0 && q_cols % hd == 0 && split > q_cols && (split - q_cols) % hd == 0 && M % tokens == 0,
-               "lt_op_qkv_qstat: bad column split (q %d | k | v at %d, head_dim %d)", q_cols, split, hd);
-    GemmArgs g;
-    g.A = (const u16*)A; g.W = (const u16*)W; g.C = (u16*)C; g.bias = nullptr; g.bias_dtype = -1; g.M = M; g.N = N; g.K = K;
-    g.lda = K; g.ldw = K; g.ldc = N; g.VT = (u16*)vt; g.vt_split = split; g.vt_tokens = tokens; g.vt_hd = hd; g.vt_npad = tokens;
-    const int bn = gemm_qkv_tile_width(g);
-    LT_REQUIRE(bn > 0 && q_cols % bn == 0 && 2 * q_cols / bn <= 32, "lt_op_qkv_qstat: the problem does not take the fused QKV launch with whole Q tiles");
-    g.qstat = (float*)qstat_ws; g.qstat_cols = q_cols; g.qstat_slots = 2 * q_cols / bn;  // qstat_ws: [M][qstat_slots] float2, <= [M][32]
-    if (int rc = launch_gemm_bf16(g, 3, 0, (hipStream_t)stream)) return rc;
-    QkPostArgs q;
-    q.src = (const u16*)C; q.ld_src = N; q.col0 = q_cols; q.ln_w = (const u16*)k_ln_w; q.ln_b = (const u16*)k_ln_b; q.ln_eps = 1e-5f;
-    q.dst = (u16*)k_out; q.B = M / tokens; q.N = tokens; q.heads = (split - q_cols) / hd; q.hd = hd; q.rope_mode = 1;
-    q.cs = (const float*)cs_table; q.t = nullptr; q.grid_w = grid_w; q.cs_len = 0; q.watershed = 0.f; q.out_scale = k_out_scale;  // (one branch's table, as lt_op_qk_norm_rope)
-    q.qstat_in = (const float*)qstat_ws; q.qstat_out = (float*)q_mean_rstd; q.qstat_slots = g.qstat_slots; q.qstat_width = q_cols;
-    return launch_qk_norm_rope(q, (hipStream_t)stream);
-}
-
-extern "C" int lt_op_gemm_qkv_fusable(int32_t M, int32_t N, int32_t K, int32_t split, int32_t tokens, int32_t hd) {
-    GemmArgs g;
-    g.A = nullptr; g.W = nullptr; g.C = nullptr; g.bias = nullptr; g.bias_dtype = -1; g.M = M; g.N = N; g.K = K;
-    g.lda = K; g.ldw = K; g.ldc = N; g.VT = (u16*)1; g.vt_split = split; g.vt_tokens = tokens; g.vt_hd = hd; g.vt_npad = tokens;
-    return lt_opt(OPT_QKV_FUSED_GEMM) && lt_opt(OPT_QKV_VT_EPILOGUE) && gemm_qkv_fusable(g) ? 1 : 0;
-}
-
-extern "C" int lt_op_gemm_describe(int32_t M, int32_t N, int32_t K, int32_t epilogue, int32_t variant, char* out, int32_t cap) {
-    LT_REQUIRE(out && cap > 0, "lt_op_gemm_describe: null buffer");
-    GemmArgs g;
-    g.A = nullptr; g.W = nullptr; g.C = nullptr; g.bias = nullptr; g.M = M; g.N = N; g.K = K;
-    g.lda = K; g.ldw = K; g.ldc = epilogue == 1 ? N / 2 : N; g.bias_dtype = -1;
-    snprintf(out, (size_t)cap, "%s", lt_gemm_describe(g, epilogue, variant));
-    return 0;
-}
-
-extern "C" int lt_op_moe_plan(void* sel, const void* sample_logits, void* wts, int32_t rows, int32_t rows_per_sample, int32_t E, void* pos,
-                              void* src, void* tile_expert, int32_t max_tiles, void* stream) {
-    LT_REQUIRE(sel && pos && src && tile_expert, "lt_op_moe_plan: null pointer");
-    LT_REQUIRE(sample_logits == nullptr || wts != nullptr, "lt_op_moe_plan: routing from per-sample logits writes the weights too");
-    MoeArgs m;
-    m.x = nullptr; m.gate_w = nullptr; m.sample_logits = (const u16*)sample_logits; m.forced = nullptr;
-    m.rows = rows; m.rows_per_sample = rows_per_sample > 0 ? rows_per_sample : rows; m.d = 8; m.E = E;
-    m.sel = (int*)sel; m.wts = (u16*)wts; m.pos = (int*)pos; m.src = (int*)src; m.tile_expert = (int*)tile_expert; m.max_tiles = max_tiles;
-    return launch_moe_plan(m, (hipStream_t)stream);
-}
-
-extern "C" int lt_op_gemm_splitk(const void* A, const void* W, void* C, int32_t M, int32_t N, int32_t K, void* part_f32, void* counters_u32,
-                                 int32_t tiles, void* stream) {
-    LT_REQUIRE(A && W && C && part_f32 && counters_u32, "lt_op_gemm_splitk: null pointer");
-    LT_REQUIRE(M > 0 && N > 0 && K > 0, "lt_op_gemm_splitk: empty problem");
-    GemmArgs g;
-    g.A = (const u16*)A; g.W = (const u16*)W; g.C = (u16*)C; g.bias = nullptr; g.bias_dtype = -1; g.M = M; g.N = N; g.K = K; g.lda = K; g.ldw = K; g.ldc = N;
-    g.splitk_part = (float*)part_f32; g.splitk_cnt = (unsigned*)counters_u32; g.splitk_tiles = tiles;
-    return launch_gemm_bf16(g, 0, 8, (hipStream_t)stream);  // variant 8 = the 64 x 128 tile, the only one that splits
-}
-
-// the same workspace with the kernel and the split left to the launcher, as in the engine (variant 0): two ways on 64 x 128 tiles, or - round 5,
-// K >= 4096 - four ways on 128 x 128 tiles, or none
-extern "C" int lt_op_gemm_splitk_auto(const void* A, const void* W, void* C, int32_t M, int32_t N, int32_t K, void* part_f32, void* counters_u32,
-                                      int32_t slots, void* stream) {
-    LT_REQUIRE(A && W && C && part_f32 && counters_u32, "lt_op_gemm_splitk_auto: null pointer");
-    LT_REQUIRE(M > 0 && N > 0 && K > 0, "lt_op_gemm_splitk_auto: empty problem");
-    GemmArgs g;
-    g.A = (const u16*)A; g.W = (const u16*)W; g.C = (u16*)C; g.bias = nullptr; g.bias_dtype = -1; g.M = M; g.N = N; g.K = K; g.lda = K; g.ldw = K; g.ldc = N;
-    g.splitk_part = (float*)part_f32; g.splitk_cnt = (unsigned*)counters_u32; g.splitk_tiles = slots;
-    return launch_gemm_bf16(g, 0, 0, (hipStream_t)stream);
-}
-
-extern "C" int lt_op_gemm_grouped(const void* A, const void* W, const void* tile_expert, int64_t w_expert_stride, void* C,
-                                  int32_t M, int32_t N, int32_t K, int32_t epilogue, int32_t variant, void* stream) {
-    LT_REQUIRE(A && W && C && tile_expert, "lt_op_gemm_grouped: null pointer");
-    LT_REQUIRE(M > 0 && M % 256 == 0, "lt_op_gemm_grouped: M=%d must be a positive multiple of 256 (expert segments)", M);
-    GemmArgs g;
-    g.A = (const u16*)A; g.W = (const u16*)W; g.C = (u16*)C; g.bias = nullptr; g.M = M; g.N = N; g.K = K;
-    g.lda = K; g.ldw = K; g.ldc = epilogue == 1 ? N / 2 : N; g.bias_dtype = -1;
-    g.tile_expert = (const int*)tile_expert; g.w_expert_stride = w_expert_stride;
-    return launch_gemm_bf16(g, epilogue, variant, (hipStream_t)stream);
-}
-
-// lt_op_gemm_grouped on the persistent kernel (variant 15) with the tail split of round 6: the tiles of a partial last round of the walk are cut
-// along K into 2 / 4 parts that hand fp32 accumulators through tail_part_f32 ([cap_parts][256 x 256] floats) and count in on counters_u32
-// ([number of CUs] words, zero before the first launch; every launch leaves them zero)
-extern "C" int lt_op_gemm_grouped_tail(const void* A, const void* W, const void* tile_expert, int64_t w_expert_stride, void* C, int32_t M, int32_t N,
-                                       int32_t K, void* tail_part_f32, void* counters_u32, int32_t cap_parts, void* stream) {
-    LT_REQUIRE(A && W && C && tile_expert && tail_part_f32 && counters_u32 && cap_parts > 0, "lt_op_gemm_grouped_tail: null pointer");
-    LT_REQUIRE(M > 0 && M % 256 == 0, "lt_op_gemm_grouped_tail: M=%d must be a positive multiple of 256 (expert segments)", M);
-    GemmArgs g;
-    g.A = (const u16*)A; g.W = (const u16*)W; g.C = (u16*)C; g.bias = nullptr; g.M = M; g.N = N; g.K = K;
-    g.lda = K; g.ldw = K; g.ldc = N; g.bias_dtype = -1;
-    g.tile_expert = (const int*)tile_expert; g.w_expert_stride = w_expert_stride;
-    g.tail_part = (float*)tail_part_f32; g.tail_cnt = (unsigned*)counters_u32; g.tail_cap_parts = cap_parts;
-    return launch_gemm_bf16(g, 0, 15, (hipStream_t)stream);
-}
-
-extern "C" int lt_op_gemm_grouped_gather(const void* A, int32_t a_rows, const void* row_map, const void* W, const void* tile_expert,
-                                         int64_t w_expert_stride, void* C, int32_t M, int32_t N, int32_t K, int32_t epilogue, int32_t variant,
-                                         void* stream) {
-    LT_REQUIRE(A && W && C && tile_expert && row_map, "lt_op_gemm_grouped_gather: null pointer");
-    LT_REQUIRE(M > 0 && M % 256 == 0 && a_rows > 0, "lt_op_gemm_grouped_gather: M=%d must be a positive multiple of 256, a_rows > 0", M);
-    GemmArgs g;
-    g.A = (const u16*)A; g.W = (const u16*)W; g.C = (u16*)C; g.bias = nullptr; g.M = M; g.N = N; g.K = K;
-    g.lda = K; g.ldw = K; g.ldc = epilogue == 1 ? N / 2 : N; g.bias_dtype = -1;
-    g.tile_expert = (const int*)tile_expert; g.w_expert_stride = w_expert_stride;
-    g.a_row_map = (const int*)row_map; g.a_map_rows = a_rows;
-    return launch_gemm_bf16(g, epilogue, variant, (hipStream_t)stream);
-}
-
-extern "C" int lt_op_pack_w13(const void* w1, const void* w3, void* out, int32_t F, int32_t K, void* stream) {
-    LT_REQUIRE(w1 && w3 && out, "lt_op_pack_w13: null pointer");
-    return launch_pack_w13((const u16*)w1, (const u16*)w3, (u16*)out, F, K, (hipStream_t)stream);
-}
-
-extern "C" int lt_op_rmsnorm_mod(const void* x, const void* w, const void* scale, const void* shift, int32_t ld_mod,
-                                 void* out, int32_t B, int32_t N, int32_t d, float eps, int32_t scale_pre, void* stream) {
-    LT_REQUIRE(x && out, "lt_op_rmsnorm_mod: null pointer");
-    NormModArgs n;
-    n.x = (const u16*)x; n.w = (const u16*)w; n.scale = (const u16*)scale; n.shift = (const u16*)shift; n.out = (u16*)out;
-    n.rows = B * N; n.rows_per_batch = N; n.d = d; n.ld_mod = ld_mod; n.eps = eps; n.scale_pre = scale_pre;
-    return launch_rmsnorm_mod(n, (hipStream_t)stream);
-}
-
-extern "C" int lt_op_gated_residual_norm(void* x, const void* y, const void* post_w, const void* gate, int32_t post_mode,
-                                         int32_t gate_mode, const void* next_w, const void* next_scale,
-                                         const void* next_shift, int32_t next_mode, int32_t ld_mod, void* h, int32_t B,
-                                         int32_t N, int32_t d, float eps, float eps_next, int32_t scale_pre, void* stream) {
-    LT_REQUIRE(x && y, "lt_op_gated_residual_norm: null pointer");
-    GatedResArgs g;
-    g.x = (u16*)x; g.y = (const u16*)y; g.post_w = (const u16*)post_w; g.gate = (const u16*)gate;
-    g.next_w = (const u16*)next_w; g.next_scale = (const u16*)next_scale; g.next_shift = (const u16*)next_shift;
-    g.h = (u16*)h; g.rows = B * N; g.rows_per_batch = N; g.d = d; g.ld_mod = ld_mod; g.post_mode = post_mode;
-    g.gate_mode = gate_mode; g.next_mode = next_mode; g.eps = eps; g.eps_next = eps_next; g.scale_pre = scale_pre;
-    return launch_gated_residual_norm(g, (hipStream_t)stream);
-}
-
-// The O / W2 projection followed by the sandwich-norm row step - exactly the two launches the engine makes per branch.  use_ystat 1: the
-// GEMM's epilogue leaves the rows' sum-of-squares partials in ystat_ws and the row kernel runs its streaming form on them (option grn_ystat's
-// path; refused when the problem does not take the persistent kernel's plain dense tiles); 0: the row kernel reduces y itself.
-extern "C" int lt_op_proj_gated_residual_norm(const void* A, const void* W, void* y, void* ystat_ws, int32_t ystat_cap, int32_t K, void* x,
-                                              const void* post_w, const void* gate, const void* next_w, const void* next_scale, int32_t ld_mod,
-                                              void* h, int32_t B, int32_t N, int32_t d, float eps, int32_t use_ystat, void* stream) {
-    LT_REQUIRE(A && W && y && x && post_w && gate && next_w && next_scale && h, "lt_op_proj_gated_residual_norm: null pointer");
-    GemmArgs g;
-    g.A = (const u16*)A; g.W = (const u16*)W; g.C = (u16*)y; g.bias = nullptr; g.M = B * N; g.N = d; g.K = K; g.lda = K; g.ldw = K; g.ldc = d;
-    g.bias_dtype = -1;
-    GatedResArgs r;
-    if (use_ystat) {
-        const int ys = gemm_ystat_slots(g, 0);
-        LT_REQUIRE(ys > 0, "lt_op_proj_gated_residual_norm: this problem does not run on the persistent kernel's plain dense tiles (no ystat)");
-        LT_REQUIRE(ystat_ws && ystat_cap >= ys, "lt_op_proj_gated_residual_norm: ystat workspace of %d floats per row, the launch fills %d", ystat_cap, ys);
-        g.ystat = (float*)ystat_ws; g.ystat_slots = ys;
-        r.ystat = (const float*)ystat_ws; r.ystat_slots = ys;
-    }
-    if (int rc = launch_gemm_bf16(g, 0, 0, (hipStream_t)stream)) return rc;
-    r.x = (u16*)x; r.y = (const u16*)y; r.post_w = (const u16*)post_w; r.gate = (const u16*)gate; r.next_w = (const u16*)next_w;
-    r.next_scale = (const u16*)next_scale; r.next_shift = nullptr; r.h = (u16*)h; r.rows = B * N; r.rows_per_batch = N; r.d = d; r.ld_mod = ld_mod;
-    r.post_mode = 1; r.gate_mode = 0; r.next_mode = 1; r.eps = eps; r.eps_next = 1e-6f; r.scale_pre = 1;
-    return launch_gated_residual_norm(r, (hipStream_t)stream);
-}
-
-extern "C" int lt_op_prep_mod(void* mod, int32_t B, int32_t ld_mod, int32_t L, int32_t chunks, int32_t d, uint32_t tanh_mask,
-                              uint32_t scale_mask, int32_t final_scale_chunk, void* stream) {
-    LT_REQUIRE(mod, "lt_op_prep_mod: null pointer");
-    return launch_prep_mod((u16*)mod, B, ld_mod, L, chunks, d, tanh_mask, scale_mask, final_scale_chunk, (hipStream_t)stream);
-}
-
-extern "C" int lt_op_qk_norm_rope(const void* src, int32_t ld_src, int32_t col0, const void* ln_w, const void* ln_b,
-                                  float ln_eps, void* dst, int32_t B, int32_t N, int32_t heads, int32_t hd,
-                                  int32_t rope_mode, const void* cs_table, int32_t grid_w, float out_scale, void* stream) {
-    LT_REQUIRE(src && dst, "lt_op_qk_norm_rope: null pointer");
-    QkPostArgs q;
-    q.src = (const u16*)src; q.ld_src = ld_src; q.col0 = col0; q.ln_w = (const u16*)ln_w; q.ln_b = (const u16*)ln_b;
-    q.ln_eps = ln_eps; q.dst = (u16*)dst; q.B = B; q.N = N; q.heads = heads; q.hd = hd; q.rope_mode = rope_mode;
-    q.cs = (const float*)cs_table; q.t = nullptr; q.grid_w = grid_w > 0 ? grid_w : 1; q.watershed = 0.f;
-    q.out_scale = out_scale;
-    q.cs_len = 0;  // op level: the caller hands over the single branch table it wants (no branch offset)
-    return launch_qk_norm_rope(q, (hipStream_t)stream);
-}
-
-extern "C" int lt_op_v_transpose(const void* src, int32_t ld_src, int32_t col0, void* dst, int32_t B, int32_t N,
-                                 int32_t Npad, int32_t kv_heads, int32_t hd, void* stream) {
-    LT_REQUIRE(src && dst, "lt_op_v_transpose: null pointer");
-    return launch_v_transpose((const u16*)src, ld_src, col0, (u16*)dst, B, N, Npad, kv_heads, hd, (hipStream_t)stream);
-}
-
-extern "C" int lt_op_attention(const void* q, const void* k, const void* vt, const float* bias, void* out, const void* gate,
-                               int32_t accumulate, int32_t B, int32_t H, int32_t Hkv, int32_t N, int32_t Nk, int32_t Nkpad,
-                               int32_t hd, float scale, int32_t k_prescaled, void* stream) {
-    LT_REQUIRE(q && k && vt && out, "lt_op_attention: null pointer");
-    AttnArgs a;
-    a.q = (const u16*)q; a.k = (const u16*)k; a.vt = (const u16*)vt; a.bias = bias; a.out = (u16*)out;
-    a.gate = (const u16*)gate; a.accumulate = accumulate; a.B = B; a.H = H; a.Hkv = Hkv; a.N = N; a.Nk = Nk;
-    a.Nkpad = Nkpad; a.hd = hd; a.scale = scale; a.k_prescaled = k_prescaled;
-    return launch_attention(a, (hipStream_t)stream);
-}
-
-extern "C" int lt_op_attention_describe(int32_t has_bias, int32_t accumulate, int32_t B, int32_t H, int32_t Hkv, int32_t N, int32_t Nk, int32_t Nkpad,
-                                        int32_t hd, char* out, int32_t cap) {
-    LT_REQUIRE(out && cap > 0, "lt_op_attention_describe: null buffer");
-    AttnArgs a;
-    a.q = nullptr; a.k = nullptr; a.vt = nullptr; a.bias = has_bias ? (const float*)out : nullptr; a.out = nullptr; a.gate = nullptr;  // (bias: only its nullness is looked at)
-    a.accumulate = accumulate; a.B = B; a.H = H; a.Hkv = Hkv; a.N = N; a.Nk = Nk; a.Nkpad = Nkpad; a.hd = hd; a.scale = 1.f;
-    snprintf(out, (size_t)cap, "%s", attention_describe(a));
-    return 0;
-}
-
-// self-attention whose queries come straight from the QKV projection (AttnArgs::q_raw): q_norm + 2-D RoPE in the kernel's prologue
-extern "C" int lt_op_attention_qraw(const void* qkv, int32_t ld, int32_t q_col0, const void* q_mean_rstd, const void* q_ln_w, const void* q_ln_b,
-                                    const void* cs_table, const void* cs_table_t, int32_t table_len, int32_t grid_w, const void* k,
-                                    const void* vt, void* out, int32_t B, int32_t H, int32_t Hkv, int32_t N, int32_t Nkpad, int32_t hd,
-                                    void* stream) {
-    LT_REQUIRE(qkv && q_mean_rstd && q_ln_w && q_ln_b && cs_table && cs_table_t && k && vt && out, "lt_op_attention_qraw: null pointer");
-    AttnArgs a;
-    a.q = nullptr; a.k = (const u16*)k; a.vt = (const u16*)vt; a.bias = nullptr; a.out = (u16*)out; a.gate = nullptr; a.accumulate = 0;
-    a.B = B; a.H = H; a.Hkv = Hkv; a.N = N; a.Nk = N; a.Nkpad = Nkpad; a.hd = hd; a.scale = 1.f; a.k_prescaled = 1;
-    a.q_raw = (const u16*)qkv; a.q_ld = ld; a.q_col0 = q_col0; a.q_stat = (const float*)q_mean_rstd;
-    a.q_ln_w = (const u16*)q_ln_w; a.q_ln_b = (const u16*)q_ln_b;
-    a.rope_cs = (const float*)cs_table; a.rope_cs_t = (const float*)cs_table_t; a.rope_t = nullptr; a.rope_watershed = 0.f;  // branch 1
-    a.rope_cs_len = table_len; a.rope_grid_w = grid_w;
-    return launch_attention(a, (hipStream_t)stream);
-}
-
-// The small-M QKV projection with the per-tile LayerNorm partials (GemmArgs::rowstat) followed by the fused q / k post-processing +
-// attention launch (AttnSmallArgs): exactly the two launches the engine makes per layer on the attn_small_fused path.
-extern "C" int lt_op_qkv_attention_small(const void* A, const void* W, void* qkv, int32_t M, int32_t K, int32_t H, int32_t Hkv, int32_t tokens,
-                                         int32_t hd, const void* q_ln_w, const void* q_ln_b, const void* k_ln_w, const void* k_ln_b,
-                                         const void* cs_table, int32_t table_len, int32_t grid_w, float k_scale, void* rowstat_ws,
-                                         void* out, void* stream) {
-    LT_REQUIRE(A && W && qkv && q_ln_w && q_ln_b && k_ln_w && k_ln_b && cs_table && rowstat_ws && out, "lt_op_qkv_attention_small: null pointer");
-    LT_REQUIRE(H > 0 && Hkv > 0 && hd > 0 && tokens > 0 && M > 0 && M % tokens == 0, "lt_op_qkv_attention_small: bad shape");
-    const int d = H * hd, dkv = Hkv * hd, N = d + 2 * dkv;
-    LT_REQUIRE(attention_small_fusable(hd, tokens, H, Hkv, d, dkv), "lt_op_qkv_attention_small: head_dim 48, 64 <= tokens <= 512 in whole tiles, widths %% 128 == 0");
-    GemmArgs g;
-    g.A = (const u16*)A; g.W = (const u16*)W; g.C = (u16*)qkv; g.bias = nullptr; g.bias_dtype = -1; g.M = M; g.N = N; g.K = K;
-    g.lda = K; g.ldw = K; g.ldc = N;
-    LT_REQUIRE(gemm_is_small_m(g, 0), "lt_op_qkv_attention_small: %d x %d x %d does not run on the small-M tiles", M, N, K);
-    g.rowstat = (float*)rowstat_ws; g.rowstat_slots = (N + 127) / 128;  // rowstat_ws: [M][ceil(N / 128)] float2
-    if (launch_gemm_bf16(g, 0, 0, (hipStream_t)stream)) return 1;
-    AttnSmallArgs a;
-    a.qkv = (const u16*)qkv; a.ld = N; a.q_col0 = 0; a.k_col0 = d; a.v_col0 = d + dkv;
-    a.rowstat = (const float*)rowstat_ws; a.slots = g.rowstat_slots; a.q_slot0 = 0; a.q_nslot = d / 128; a.k_slot0 = d / 128; a.k_nslot = dkv / 128;
-    a.q_ln_w = (const u16*)q_ln_w; a.q_ln_b = (const u16*)q_ln_b; a.k_ln_w = (const u16*)k_ln_w; a.k_ln_b = (const u16*)k_ln_b; a.ln_eps = 1e-5f;
-    a.cs = (const float*)cs_table; a.t = nullptr; a.watershed = 0.f; a.cs_len = table_len; a.grid_w = grid_w;  // branch 1
-    a.k_scale = k_scale; a.out = (u16*)out; a.B = M / tokens; a.H = H; a.Hkv = Hkv; a.N = tokens; a.hd = hd;
-    return launch_attention_small(a, (hipStream_t)stream);
-}
-
-extern "C" int lt_op_attention_fused(const void* q, const void* k, const void* vt, const void* tk, const void* tvt,
-                                     const float* tbias, const void* tgate, void* out, int32_t B, int32_t H, int32_t Hkv, int32_t N,
-                                     int32_t Nk, int32_t Nkpad, int32_t Tk, int32_t Tkpad, int32_t hd, void* stream) {
-    LT_REQUIRE(q && k && vt && tk && tvt && tbias && tgate && out, "lt_op_attention_fused: null pointer");
-    LT_REQUIRE(attention_fuses_text(hd), "lt_op_attention_fused: needs head_dim 72 or 96 and attention_variant 3 or 4");
-    AttnArgs a;
-    a.q = (const u16*)q; a.k = (const u16*)k; a.vt = (const u16*)vt; a.bias = nullptr; a.out = (u16*)out; a.gate = nullptr;
-    a.accumulate = 0; a.B = B; a.H = H; a.Hkv = Hkv; a.N = N; a.Nk = Nk; a.Nkpad = Nkpad; a.hd = hd; a.scale = 1.f; a.k_prescaled = 1;
-    a.tk = (const u16*)tk; a.tvt = (const u16*)tvt; a.tbias = tbias; a.tgate = (const u16*)tgate; a.Tk = Tk; a.Tkpad = Tkpad;
-    return launch_attention(a, (hipStream_t)stream);
-}
-
-extern "C" int lt_op_attention_trace(const void* q, const void* k, const void* vt, void* out, int32_t B, int32_t H, int32_t Hkv,
-                                     int32_t N, int32_t Nk, int32_t Nkpad, int32_t hd, float scale, void* trace_dev,
-                                     void* stream) {
-    LT_REQUIRE(q && k && vt && out && trace_dev, "lt_op_attention_trace: null pointer");
-    AttnArgs a;
-    a.q = (const u16*)q; a.k = (const u16*)k; a.vt = (const u16*)vt; a.bias = nullptr; a.out = (u16*)out;
-    a.gate = nullptr; a.accumulate = 0; a.B = B; a.H = H; a.Hkv = Hkv; a.N = N; a.Nk = Nk;
-    a.Nkpad = Nkpad; a.hd = hd; a.scale = scale; a.trace = (unsigned long long*)trace_dev;
-    return launch_attention(a, (hipStream_t)stream);
-}
-
-extern "C" int lt_op_linear_small_m(const void* a, const void* w, const void* b, void* y, int32_t M, int32_t N, int32_t K,
-                                    int32_t act_in, void* stream) {
-    LT_REQUIRE(a && w && y, "lt_op_linear_small_m: null pointer");
-    return launch_linear_small_m((const u16*)a, (const u16*)w, (const u16*)b, (u16*)y, M, N, K, act_in, (hipStream_t)stream);
-}
-
-extern "C" int lt_op_rope_table_2d_pair(void* out, void* out_t, int32_t len, int32_t hd, float theta, float scale_factor, void* stream) {
-    LT_REQUIRE(out && out_t, "lt_op_rope_table_2d_pair: null pointer");
-    return launch_rope_table_2d((float*)out, len, hd, theta, scale_factor, (hipStream_t)stream, (float*)out_t);
-}
-
-extern "C" int lt_op_rope_table_2d(void* out, int32_t len, int32_t hd, float theta, float scale_factor, void* stream) {
-    LT_REQUIRE(out, "lt_op_rope_table_2d: null pointer");
-    return launch_rope_table_2d((float*)out, len, hd, theta, scale_factor, (hipStream_t)stream);
 }

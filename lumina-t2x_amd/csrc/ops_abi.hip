@@ -1,0 +1,357 @@
+// Operator-level entry points of the C ABI (lt_op_*, include/lumina_dit_debug.h): each one fills the argument struct of ONE launcher (or of
+// the two launches the engine makes back to back) from plain arguments, for the parity tests and the operator benchmarks.  None of them
+// touches an engine object; they see the process-default options (lt_set_option).
+#include <cstdio>
+
+#include "../../include/lumina_dit.h"
+#include "common.h"
+#include "kernels.h"
+#include "options.h"
+
+extern "C" int lt_op_gemm_bf16(const void* A, const void* W, const void* bias, int32_t bias_dtype, void* C, int32_t M,
+                               int32_t N, int32_t K, int32_t epilogue, int32_t variant, void* stream) {
+    LT_REQUIRE(A && W && C, "lt_op_gemm_bf16: null pointer");
+    GemmArgs g;
+    g.A = (const u16*)A; g.W = (const u16*)W; g.C = (u16*)C; g.bias = bias; g.M = M; g.N = N; g.K = K;
+    g.lda = K; g.ldw = K; g.ldc = epilogue == 1 ? N / 2 : N; g.bias_dtype = bias ? bias_dtype : -1;
+    return launch_gemm_bf16(g, epilogue, variant, (hipStream_t)stream);
+}
+
+// round 6: the row-pair-interleaved operand layout of the persistent GEMM (GemmArgs::pair_ab) at the op level
+extern "C" int lt_op_pair_layout(void* m, int64_t rows, int32_t cols, int32_t to_pair, void* stream) {
+    LT_REQUIRE(m, "lt_op_pair_layout: null pointer");
+    return launch_pair_layout((u16*)m, rows, cols, to_pair, (hipStream_t)stream);
+}
+extern "C" int lt_op_gemm_bf16_pair(const void* A, const void* W, void* C, int32_t M, int32_t N, int32_t K, int32_t epilogue, int32_t pair_c,
+                                    void* stream) {
+    LT_REQUIRE(A && W && C, "lt_op_gemm_bf16_pair: null pointer");
+    GemmArgs g;
+    g.A = (const u16*)A; g.W = (const u16*)W; g.C = (u16*)C; g.bias = nullptr; g.M = M; g.N = N; g.K = K;
+    g.lda = K; g.ldw = K; g.ldc = epilogue == 1 ? N / 2 : N; g.bias_dtype = -1; g.pair_ab = 3; g.pair_c = pair_c;
+    return launch_gemm_bf16(g, epilogue, 0, (hipStream_t)stream);
+}
+
+extern "C" int lt_op_gemm_vt(const void* A, const void* W, void* vt, int32_t M, int32_t N, int32_t K, int32_t tokens, int32_t hd,
+                             int32_t variant, void* stream) {
+    LT_REQUIRE(A && W && vt, "lt_op_gemm_vt: null pointer");
+    GemmArgs g;
+    g.A = (const u16*)A; g.W = (const u16*)W; g.C = (u16*)vt; g.bias = nullptr; g.M = M; g.N = N; g.K = K;
+    g.lda = K; g.ldw = K; g.ldc = 0; g.bias_dtype = -1; g.vt_tokens = tokens; g.vt_hd = hd; g.vt_npad = tokens;
+    return launch_gemm_bf16(g, 2, variant, (hipStream_t)stream);
+}
+
+extern "C" int lt_op_gemm_qkv(const void* A, const void* W, void* C, void* vt, int32_t M, int32_t N, int32_t K, int32_t split,
+                              int32_t tokens, int32_t hd, void* stream) {
+    LT_REQUIRE(A && W && C && vt, "lt_op_gemm_qkv: null pointer");
+    GemmArgs g;
+    g.A = (const u16*)A; g.W = (const u16*)W; g.C = (u16*)C; g.bias = nullptr; g.bias_dtype = -1; g.M = M; g.N = N; g.K = K;
+    g.lda = K; g.ldw = K; g.ldc = N; g.VT = (u16*)vt; g.vt_split = split; g.vt_tokens = tokens; g.vt_hd = hd; g.vt_npad = tokens;
+    return launch_gemm_bf16(g, 3, 0, (hipStream_t)stream);
+}
+
+// The fused QKV launch with the Q columns' LayerNorm partials (GemmArgs::qstat) followed by the K pass of qk_norm_rope that reduces
+// them (QkPostArgs::qstat_in): exactly the two launches the engine makes per layer on the attn_q_fused path.
+extern "C" int lt_op_qkv_qstat(const void* A, const void* W, void* C, void* vt, int32_t M, int32_t N, int32_t K, int32_t split, int32_t tokens,
+                               int32_t hd, int32_t q_cols, const void* k_ln_w, const void* k_ln_b, const void* cs_table, int32_t grid_w,
+                               float k_out_scale, void* k_out, void* qstat_ws, void* q_mean_rstd, void* stream) {
+    LT_REQUIRE(A && W && C && vt && k_ln_w && k_ln_b && cs_table && k_out && qstat_ws && q_mean_rstd, "lt_op_qkv_qstat: null pointer");
+    LT_REQUIRE(hd > 0 && q_cols > 0 && q_cols % hd == 0 && split > q_cols && (split - q_cols) % hd == 0 && M % tokens == 0,
+               "lt_op_qkv_qstat: bad column split (q %d | k | v at %d, head_dim %d)", q_cols, split, hd);
+    GemmArgs g;
+    g.A = (const u16*)A; g.W = (const u16*)W; g.C = (u16*)C; g.bias = nullptr; g.bias_dtype = -1; g.M = M; g.N = N; g.K = K;
+    g.lda = K; g.ldw = K; g.ldc = N; g.VT = (u16*)vt; g.vt_split = split; g.vt_tokens = tokens; g.vt_hd = hd; g.vt_npad = tokens;
+    const int bn = gemm_qkv_tile_width(g);
+    LT_REQUIRE(bn > 0 && q_cols % bn == 0 && 2 * q_cols / bn <= 32, "lt_op_qkv_qstat: the problem does not take the fused QKV launch with whole Q tiles");
+    g.qstat = (float*)qstat_ws; g.qstat_cols = q_cols; g.qstat_slots = 2 * q_cols / bn;  // qstat_ws: [M][qstat_slots] float2, <= [M][32]
+    if (int rc = launch_gemm_bf16(g, 3, 0, (hipStream_t)stream)) return rc;
+    QkPostArgs q;
+    q.src = (const u16*)C; q.ld_src = N; q.col0 = q_cols; q.ln_w = (const u16*)k_ln_w; q.ln_b = (const u16*)k_ln_b; q.ln_eps = 1e-5f;
+    q.dst = (u16*)k_out; q.B = M / tokens; q.N = tokens; q.heads = (split - q_cols) / hd; q.hd = hd; q.rope_mode = 1;
+    q.cs = (const float*)cs_table; q.t = nullptr; q.grid_w = grid_w; q.cs_len = 0; q.watershed = 0.f; q.out_scale = k_out_scale;  // (one branch's table, as lt_op_qk_norm_rope)
+    q.qstat_in = (const float*)qstat_ws; q.qstat_out = (float*)q_mean_rstd; q.qstat_slots = g.qstat_slots; q.qstat_width = q_cols;
+    return launch_qk_norm_rope(q, (hipStream_t)stream);
+}
+
+extern "C" int lt_op_gemm_qkv_fusable(int32_t M, int32_t N, int32_t K, int32_t split, int32_t tokens, int32_t hd) {
+    GemmArgs g;
+    g.A = nullptr; g.W = nullptr; g.C = nullptr; g.bias = nullptr; g.bias_dtype = -1; g.M = M; g.N = N; g.K = K;
+    g.lda = K; g.ldw = K; g.ldc = N; g.VT = (u16*)1; g.vt_split = split; g.vt_tokens = tokens; g.vt_hd = hd; g.vt_npad = tokens;
+    return lt_opt(OPT_QKV_FUSED_GEMM) && lt_opt(OPT_QKV_VT_EPILOGUE) && gemm_qkv_fusable(g) ? 1 : 0;
+}
+
+extern "C" int lt_op_gemm_describe(int32_t M, int32_t N, int32_t K, int32_t epilogue, int32_t variant, char* out, int32_t cap) {
+    LT_REQUIRE(out && cap > 0, "lt_op_gemm_describe: null buffer");
+    GemmArgs g;
+    g.A = nullptr; g.W = nullptr; g.C = nullptr; g.bias = nullptr; g.M = M; g.N = N; g.K = K;
+    g.lda = K; g.ldw = K; g.ldc = epilogue == 1 ? N / 2 : N; g.bias_dtype = -1;
+    snprintf(out, (size_t)cap, "%s", lt_gemm_describe(g, epilogue, variant));
+    return 0;
+}
+
+extern "C" int lt_op_moe_plan(void* sel, const void* sample_logits, void* wts, int32_t rows, int32_t rows_per_sample, int32_t E, void* pos,
+                              void* src, void* tile_expert, int32_t max_tiles, void* stream) {
+    LT_REQUIRE(sel && pos && src && tile_expert, "lt_op_moe_plan: null pointer");
+    LT_REQUIRE(sample_logits == nullptr || wts != nullptr, "lt_op_moe_plan: routing from per-sample logits writes the weights too");
+    MoeArgs m;
+    m.x = nullptr; m.gate_w = nullptr; m.sample_logits = (const u16*)sample_logits; m.forced = nullptr;
+    m.rows = rows; m.rows_per_sample = rows_per_sample > 0 ? rows_per_sample : rows; m.d = 8; m.E = E;
+    m.sel = (int*)sel; m.wts = (u16*)wts; m.pos = (int*)pos; m.src = (int*)src; m.tile_expert = (int*)tile_expert; m.max_tiles = max_tiles;
+    return launch_moe_plan(m, (hipStream_t)stream);
+}
+
+extern "C" int lt_op_gemm_splitk(const void* A, const void* W, void* C, int32_t M, int32_t N, int32_t K, void* part_f32, void* counters_u32,
+                                 int32_t tiles, void* stream) {
+    LT_REQUIRE(A && W && C && part_f32 && counters_u32, "lt_op_gemm_splitk: null pointer");
+    LT_REQUIRE(M > 0 && N > 0 && K > 0, "lt_op_gemm_splitk: empty problem");
+    GemmArgs g;
+    g.A = (const u16*)A; g.W = (const u16*)W; g.C = (u16*)C; g.bias = nullptr; g.bias_dtype = -1; g.M = M; g.N = N; g.K = K; g.lda = K; g.ldw = K; g.ldc = N;
+    g.splitk_part = (float*)part_f32; g.splitk_cnt = (unsigned*)counters_u32; g.splitk_tiles = tiles;
+    return launch_gemm_bf16(g, 0, 8, (hipStream_t)stream);  // variant 8 = the 64 x 128 tile, the only one that splits
+}
+
+// the same workspace with the kernel and the split left to the launcher, as in the engine (variant 0): two ways on 64 x 128 tiles, or - round 5,
+// K >= 4096 - four ways on 128 x 128 tiles, or none
+extern "C" int lt_op_gemm_splitk_auto(const void* A, const void* W, void* C, int32_t M, int32_t N, int32_t K, void* part_f32, void* counters_u32,
+                                      int32_t slots, void* stream) {
+    LT_REQUIRE(A && W && C && part_f32 && counters_u32, "lt_op_gemm_splitk_auto: null pointer");
+    LT_REQUIRE(M > 0 && N > 0 && K > 0, "lt_op_gemm_splitk_auto: empty problem");
+    GemmArgs g;
+    g.A = (const u16*)A; g.W = (const u16*)W; g.C = (u16*)C; g.bias = nullptr; g.bias_dtype = -1; g.M = M; g.N = N; g.K = K; g.lda = K; g.ldw = K; g.ldc = N;
+    g.splitk_part = (float*)part_f32; g.splitk_cnt = (unsigned*)counters_u32; g.splitk_tiles = slots;
+    return launch_gemm_bf16(g, 0, 0, (hipStream_t)stream);
+}
+
+extern "C" int lt_op_gemm_grouped(const void* A, const void* W, const void* tile_expert, int64_t w_expert_stride, void* C,
+                                  int32_t M, int32_t N, int32_t K, int32_t epilogue, int32_t variant, void* stream) {
+    LT_REQUIRE(A && W && C && tile_expert, "lt_op_gemm_grouped: null pointer");
+    LT_REQUIRE(M > 0 && M % 256 == 0, "lt_op_gemm_grouped: M=%d must be a positive multiple of 256 (expert segments)", M);
+    GemmArgs g;
+    g.A = (const u16*)A; g.W = (const u16*)W; g.C = (u16*)C; g.bias = nullptr; g.M = M; g.N = N; g.K = K;
+    g.lda = K; g.ldw = K; g.ldc = epilogue == 1 ? N / 2 : N; g.bias_dtype = -1;
+    g.tile_expert = (const int*)tile_expert; g.w_expert_stride = w_expert_stride;
+    return launch_gemm_bf16(g, epilogue, variant, (hipStream_t)stream);
+}
+
+// lt_op_gemm_grouped on the persistent kernel (variant 15) with the tail split of round 6: the tiles of a partial last round of the walk are cut
+// along K into 2 / 4 parts that hand fp32 accumulators through tail_part_f32 ([cap_parts][256 x 256] floats) and count in on counters_u32
+// ([number of CUs] words, zero before the first launch; every launch leaves them zero)
+extern "C" int lt_op_gemm_grouped_tail(const void* A, const void* W, const void* tile_expert, int64_t w_expert_stride, void* C, int32_t M, int32_t N,
+                                       int32_t K, void* tail_part_f32, void* counters_u32, int32_t cap_parts, void* stream) {
+    LT_REQUIRE(A && W && C && tile_expert && tail_part_f32 && counters_u32 && cap_parts > 0, "lt_op_gemm_grouped_tail: null pointer");
+    LT_REQUIRE(M > 0 && M % 256 == 0, "lt_op_gemm_grouped_tail: M=%d must be a positive multiple of 256 (expert segments)", M);
+    GemmArgs g;
+    g.A = (const u16*)A; g.W = (const u16*)W; g.C = (u16*)C; g.bias = nullptr; g.M = M; g.N = N; g.K = K;
+    g.lda = K; g.ldw = K; g.ldc = N; g.bias_dtype = -1;
+    g.tile_expert = (const int*)tile_expert; g.w_expert_stride = w_expert_stride;
+    g.tail_part = (float*)tail_part_f32; g.tail_cnt = (unsigned*)counters_u32; g.tail_cap_parts = cap_parts;
+    return launch_gemm_bf16(g, 0, 15, (hipStream_t)stream);
+}
+
+extern "C" int lt_op_gemm_grouped_gather(const void* A, int32_t a_rows, const void* row_map, const void* W, const void* tile_expert,
+                                         int64_t w_expert_stride, void* C, int32_t M, int32_t N, int32_t K, int32_t epilogue, int32_t variant,
+                                         void* stream) {
+    LT_REQUIRE(A && W && C && tile_expert && row_map, "lt_op_gemm_grouped_gather: null pointer");
+    LT_REQUIRE(M > 0 && M % 256 == 0 && a_rows > 0, "lt_op_gemm_grouped_gather: M=%d must be a positive multiple of 256, a_rows > 0", M);
+    GemmArgs g;
+    g.A = (const u16*)A; g.W = (const u16*)W; g.C = (u16*)C; g.bias = nullptr; g.M = M; g.N = N; g.K = K;
+    g.lda = K; g.ldw = K; g.ldc = epilogue == 1 ? N / 2 : N; g.bias_dtype = -1;
+    g.tile_expert = (const int*)tile_expert; g.w_expert_stride = w_expert_stride;
+    g.a_row_map = (const int*)row_map; g.a_map_rows = a_rows;
+    return launch_gemm_bf16(g, epilogue, variant, (hipStream_t)stream);
+}
+
+extern "C" int lt_op_pack_w13(const void* w1, const void* w3, void* out, int32_t F, int32_t K, void* stream) {
+    LT_REQUIRE(w1 && w3 && out, "lt_op_pack_w13: null pointer");
+    return launch_pack_w13((const u16*)w1, (const u16*)w3, (u16*)out, F, K, (hipStream_t)stream);
+}
+
+extern "C" int lt_op_rmsnorm_mod(const void* x, const void* w, const void* scale, const void* shift, int32_t ld_mod,
+                                 void* out, int32_t B, int32_t N, int32_t d, float eps, int32_t scale_pre, void* stream) {
+    LT_REQUIRE(x && out, "lt_op_rmsnorm_mod: null pointer");
+    NormModArgs n;
+    n.x = (const u16*)x; n.w = (const u16*)w; n.scale = (const u16*)scale; n.shift = (const u16*)shift; n.out = (u16*)out;
+    n.rows = B * N; n.rows_per_batch = N; n.d = d; n.ld_mod = ld_mod; n.eps = eps; n.scale_pre = scale_pre;
+    return launch_rmsnorm_mod(n, (hipStream_t)stream);
+}
+
+extern "C" int lt_op_gated_residual_norm(void* x, const void* y, const void* post_w, const void* gate, int32_t post_mode,
+                                         int32_t gate_mode, const void* next_w, const void* next_scale,
+                                         const void* next_shift, int32_t next_mode, int32_t ld_mod, void* h, int32_t B,
+                                         int32_t N, int32_t d, float eps, float eps_next, int32_t scale_pre, void* stream) {
+    LT_REQUIRE(x && y, "lt_op_gated_residual_norm: null pointer");
+    GatedResArgs g;
+    g.x = (u16*)x; g.y = (const u16*)y; g.post_w = (const u16*)post_w; g.gate = (const u16*)gate;
+    g.next_w = (const u16*)next_w; g.next_scale = (const u16*)next_scale; g.next_shift = (const u16*)next_shift;
+    g.h = (u16*)h; g.rows = B * N; g.rows_per_batch = N; g.d = d; g.ld_mod = ld_mod; g.post_mode = post_mode;
+    g.gate_mode = gate_mode; g.next_mode = next_mode; g.eps = eps; g.eps_next = eps_next; g.scale_pre = scale_pre;
+    return launch_gated_residual_norm(g, (hipStream_t)stream);
+}
+
+// The O / W2 projection followed by the sandwich-norm row step - exactly the two launches the engine makes per branch.  use_ystat 1: the
+// GEMM's epilogue leaves the rows' sum-of-squares partials in ystat_ws and the row kernel runs its streaming form on them (option grn_ystat's
+// path; refused when the problem does not take the persistent kernel's plain dense tiles); 0: the row kernel reduces y itself.
+extern "C" int lt_op_proj_gated_residual_norm(const void* A, const void* W, void* y, void* ystat_ws, int32_t ystat_cap, int32_t K, void* x,
+                                              const void* post_w, const void* gate, const void* next_w, const void* next_scale, int32_t ld_mod,
+                                              void* h, int32_t B, int32_t N, int32_t d, float eps, int32_t use_ystat, void* stream) {
+    LT_REQUIRE(A && W && y && x && post_w && gate && next_w && next_scale && h, "lt_op_proj_gated_residual_norm: null pointer");
+    GemmArgs g;
+    g.A = (const u16*)A; g.W = (const u16*)W; g.C = (u16*)y; g.bias = nullptr; g.M = B * N; g.N = d; g.K = K; g.lda = K; g.ldw = K; g.ldc = d;
+    g.bias_dtype = -1;
+    GatedResArgs r;
+    if (use_ystat) {
+        const int ys = gemm_ystat_slots(g, 0);
+        LT_REQUIRE(ys > 0, "lt_op_proj_gated_residual_norm: this problem does not run on the persistent kernel's plain dense tiles (no ystat)");
+        LT_REQUIRE(ystat_ws && ystat_cap >= ys, "lt_op_proj_gated_residual_norm: ystat workspace of %d floats per row, the launch fills %d", ystat_cap, ys);
+        g.ystat = (float*)ystat_ws; g.ystat_slots = ys;
+        r.ystat = (const float*)ystat_ws; r.ystat_slots = ys;
+    }
+    if (int rc = launch_gemm_bf16(g, 0, 0, (hipStream_t)stream)) return rc;
+    r.x = (u16*)x; r.y = (const u16*)y; r.post_w = (const u16*)post_w; r.gate = (const u16*)gate; r.next_w = (const u16*)next_w;
+    r.next_scale = (const u16*)next_scale; r.next_shift = nullptr; r.h = (u16*)h; r.rows = B * N; r.rows_per_batch = N; r.d = d; r.ld_mod = ld_mod;
+    r.post_mode = 1; r.gate_mode = 0; r.next_mode = 1; r.eps = eps; r.eps_next = 1e-6f; r.scale_pre = 1;
+    return launch_gated_residual_norm(r, (hipStream_t)stream);
+}
+
+extern "C" int lt_op_prep_mod(void* mod, int32_t B, int32_t ld_mod, int32_t L, int32_t chunks, int32_t d, uint32_t tanh_mask,
+                              uint32_t scale_mask, int32_t final_scale_chunk, void* stream) {
+    LT_REQUIRE(mod, "lt_op_prep_mod: null pointer");
+    return launch_prep_mod((u16*)mod, B, ld_mod, L, chunks, d, tanh_mask, scale_mask, final_scale_chunk, (hipStream_t)stream);
+}
+
+extern "C" int lt_op_qk_norm_rope(const void* src, int32_t ld_src, int32_t col0, const void* ln_w, const void* ln_b,
+                                  float ln_eps, void* dst, int32_t B, int32_t N, int32_t heads, int32_t hd,
+                                  int32_t rope_mode, const void* cs_table, int32_t grid_w, float out_scale, void* stream) {
+    LT_REQUIRE(src && dst, "lt_op_qk_norm_rope: null pointer");
+    QkPostArgs q;
+    q.src = (const u16*)src; q.ld_src = ld_src; q.col0 = col0; q.ln_w = (const u16*)ln_w; q.ln_b = (const u16*)ln_b;
+    q.ln_eps = ln_eps; q.dst = (u16*)dst; q.B = B; q.N = N; q.heads = heads; q.hd = hd; q.rope_mode = rope_mode;
+    q.cs = (const float*)cs_table; q.t = nullptr; q.grid_w = grid_w > 0 ? grid_w : 1; q.watershed = 0.f;
+    q.out_scale = out_scale;
+    q.cs_len = 0;  // op level: the caller hands over the single branch table it wants (no branch offset)
+    return launch_qk_norm_rope(q, (hipStream_t)stream);
+}
+
+extern "C" int lt_op_v_transpose(const void* src, int32_t ld_src, int32_t col0, void* dst, int32_t B, int32_t N,
+                                 int32_t Npad, int32_t kv_heads, int32_t hd, void* stream) {
+    LT_REQUIRE(src && dst, "lt_op_v_transpose: null pointer");
+    return launch_v_transpose((const u16*)src, ld_src, col0, (u16*)dst, B, N, Npad, kv_heads, hd, (hipStream_t)stream);
+}
+
+extern "C" int lt_op_attention(const void* q, const void* k, const void* vt, const float* bias, void* out, const void* gate,
+                               int32_t accumulate, int32_t B, int32_t H, int32_t Hkv, int32_t N, int32_t Nk, int32_t Nkpad,
+                               int32_t hd, float scale, int32_t k_prescaled, void* stream) {
+    LT_REQUIRE(q && k && vt && out, "lt_op_attention: null pointer");
+    AttnArgs a;
+    a.q = (const u16*)q; a.k = (const u16*)k; a.vt = (const u16*)vt; a.bias = bias; a.out = (u16*)out;
+    a.gate = (const u16*)gate; a.accumulate = accumulate; a.B = B; a.H = H; a.Hkv = Hkv; a.N = N; a.Nk = Nk;
+    a.Nkpad = Nkpad; a.hd = hd; a.scale = scale; a.k_prescaled = k_prescaled;
+    return launch_attention(a, (hipStream_t)stream);
+}
+
+extern "C" int lt_op_attention_describe(int32_t has_bias, int32_t accumulate, int32_t B, int32_t H, int32_t Hkv, int32_t N, int32_t Nk, int32_t Nkpad,
+                                        int32_t hd, char* out, int32_t cap) {
+    LT_REQUIRE(out && cap > 0, "lt_op_attention_describe: null buffer");
+    AttnArgs a;
+    a.q = nullptr; a.k = nullptr; a.vt = nullptr; a.bias = has_bias ? (const float*)out : nullptr; a.out = nullptr; a.gate = nullptr;  // (bias: only its nullness is looked at)
+    a.accumulate = accumulate; a.B = B; a.H = H; a.Hkv = Hkv; a.N = N; a.Nk = Nk; a.Nkpad = Nkpad; a.hd = hd; a.scale = 1.f;
+    snprintf(out, (size_t)cap, "%s", attention_describe(a));
+    return 0;
+}
+
+// self-attention whose queries come straight from the QKV projection (AttnArgs::q_raw): q_norm + 2-D RoPE in the kernel's prologue
+extern "C" int lt_op_attention_qraw(const void* qkv, int32_t ld, int32_t q_col0, const void* q_mean_rstd, const void* q_ln_w, const void* q_ln_b,
+                                    const void* cs_table, const void* cs_table_t, int32_t table_len, int32_t grid_w, const void* k,
+                                    const void* vt, void* out, int32_t B, int32_t H, int32_t Hkv, int32_t N, int32_t Nkpad, int32_t hd,
+                                    void* stream) {
+    LT_REQUIRE(qkv && q_mean_rstd && q_ln_w && q_ln_b && cs_table && cs_table_t && k && vt && out, "lt_op_attention_qraw: null pointer");
+    AttnArgs a;
+    a.q = nullptr; a.k = (const u16*)k; a.vt = (const u16*)vt; a.bias = nullptr; a.out = (u16*)out; a.gate = nullptr; a.accumulate = 0;
+    a.B = B; a.H = H; a.Hkv = Hkv; a.N = N; a.Nk = N; a.Nkpad = Nkpad; a.hd = hd; a.scale = 1.f; a.k_prescaled = 1;
+    a.q_raw = (const u16*)qkv; a.q_ld = ld; a.q_col0 = q_col0; a.q_stat = (const float*)q_mean_rstd;
+    a.q_ln_w = (const u16*)q_ln_w; a.q_ln_b = (const u16*)q_ln_b;
+    a.rope_cs = (const float*)cs_table; a.rope_cs_t = (const float*)cs_table_t; a.rope_t = nullptr; a.rope_watershed = 0.f;  // branch 1
+    a.rope_cs_len = table_len; a.rope_grid_w = grid_w;
+    return launch_attention(a, (hipStream_t)stream);
+}
+
+// The small-M QKV projection with the per-tile LayerNorm partials (GemmArgs::rowstat) followed by the fused q / k post-processing +
+// attention launch (AttnSmallArgs): exactly the two launches the engine makes per layer on the attn_small_fused path.
+extern "C" int lt_op_qkv_attention_small(const void* A, const void* W, void* qkv, int32_t M, int32_t K, int32_t H, int32_t Hkv, int32_t tokens,
+                                         int32_t hd, const void* q_ln_w, const void* q_ln_b, const void* k_ln_w, const void* k_ln_b,
+                                         const void* cs_table, int32_t table_len, int32_t grid_w, float k_scale, void* rowstat_ws,
+                                         void* out, void* stream) {
+    LT_REQUIRE(A && W && qkv && q_ln_w && q_ln_b && k_ln_w && k_ln_b && cs_table && rowstat_ws && out, "lt_op_qkv_attention_small: null pointer");
+    LT_REQUIRE(H > 0 && Hkv > 0 && hd > 0 && tokens > 0 && M > 0 && M % tokens == 0, "lt_op_qkv_attention_small: bad shape");
+    const int d = H * hd, dkv = Hkv * hd, N = d + 2 * dkv;
+    LT_REQUIRE(attention_small_fusable(hd, tokens, H, Hkv, d, dkv), "lt_op_qkv_attention_small: head_dim 48, 64 <= tokens <= 512 in whole tiles, widths %% 128 == 0");
+    GemmArgs g;
+    g.A = (const u16*)A; g.W = (const u16*)W; g.C = (u16*)qkv; g.bias = nullptr; g.bias_dtype = -1; g.M = M; g.N = N; g.K = K;
+    g.lda = K; g.ldw = K; g.ldc = N;
+    LT_REQUIRE(gemm_is_small_m(g, 0), "lt_op_qkv_attention_small: %d x %d x %d does not run on the small-M tiles", M, N, K);
+    g.rowstat = (float*)rowstat_ws; g.rowstat_slots = (N + 127) / 128;  // rowstat_ws: [M][ceil(N / 128)] float2
+    if (launch_gemm_bf16(g, 0, 0, (hipStream_t)stream)) return 1;
+    AttnSmallArgs a;
+    a.qkv = (const u16*)qkv; a.ld = N; a.q_col0 = 0; a.k_col0 = d; a.v_col0 = d + dkv;
+    a.rowstat = (const float*)rowstat_ws; a.slots = g.rowstat_slots; a.q_slot0 = 0; a.q_nslot = d / 128; a.k_slot0 = d / 128; a.k_nslot = dkv / 128;
+    a.q_ln_w = (const u16*)q_ln_w; a.q_ln_b = (const u16*)q_ln_b; a.k_ln_w = (const u16*)k_ln_w; a.k_ln_b = (const u16*)k_ln_b; a.ln_eps = 1e-5f;
+    a.cs = (const float*)cs_table; a.t = nullptr; a.watershed = 0.f; a.cs_len = table_len; a.grid_w = grid_w;  // branch 1
+    a.k_scale = k_scale; a.out = (u16*)out; a.B = M / tokens; a.H = H; a.Hkv = Hkv; a.N = tokens; a.hd = hd;
+    return launch_attention_small(a, (hipStream_t)stream);
+}
+
+extern "C" int lt_op_attention_fused(const void* q, const void* k, const void* vt, const void* tk, const void* tvt,
+                                     const float* tbias, const void* tgate, void* out, int32_t B, int32_t H, int32_t Hkv, int32_t N,
+                                     int32_t Nk, int32_t Nkpad, int32_t Tk, int32_t Tkpad, int32_t hd, void* stream) {
+    LT_REQUIRE(q && k && vt && tk && tvt && tbias && tgate && out, "lt_op_attention_fused: null pointer");
+    LT_REQUIRE(attention_fuses_text(hd), "lt_op_attention_fused: needs head_dim 72 or 96 and attention_variant 3 or 4");
+    AttnArgs a;
+    a.q = (const u16*)q; a.k = (const u16*)k; a.vt = (const u16*)vt; a.bias = nullptr; a.out = (u16*)out; a.gate = nullptr;
+    a.accumulate = 0; a.B = B; a.H = H; a.Hkv = Hkv; a.N = N; a.Nk = Nk; a.Nkpad = Nkpad; a.hd = hd; a.scale = 1.f; a.k_prescaled = 1;
+    a.tk = (const u16*)tk; a.tvt = (const u16*)tvt; a.tbias = tbias; a.tgate = (const u16*)tgate; a.Tk = Tk; a.Tkpad = Tkpad;
+    return launch_attention(a, (hipStream_t)stream);
+}
+
+extern "C" int lt_op_attention_trace(const void* q, const void* k, const void* vt, void* out, int32_t B, int32_t H, int32_t Hkv,
+                                     int32_t N, int32_t Nk, int32_t Nkpad, int32_t hd, float scale, void* trace_dev,
+                                     void* stream) {
+    LT_REQUIRE(q && k && vt && out && trace_dev, "lt_op_attention_trace: null pointer");
+    AttnArgs a;
+    a.q = (const u16*)q; a.k = (const u16*)k; a.vt = (const u16*)vt; a.bias = nullptr; a.out = (u16*)out;
+    a.gate = nullptr; a.accumulate = 0; a.B = B; a.H = H; a.Hkv = Hkv; a.N = N; a.Nk = Nk;
+    a.Nkpad = Nkpad; a.hd = hd; a.scale = scale; a.trace = (unsigned long long*)trace_dev;
+    return launch_attention(a, (hipStream_t)stream);
+}
+
+extern "C" int lt_op_linear_small_m(const void* a, const void* w, const void* b, void* y, int32_t M, int32_t N, int32_t K,
+                                    int32_t act_in, void* stream) {
+    LT_REQUIRE(a && w && y, "lt_op_linear_small_m: null pointer");
+    return launch_linear_small_m((const u16*)a, (const u16*)w, (const u16*)b, (u16*)y, M, N, K, act_in, (hipStream_t)stream);
+}
+
+extern "C" int lt_op_rope_table_2d_pair(void* out, void* out_t, int32_t len, int32_t hd, float theta, float scale_factor, void* stream) {
+    LT_REQUIRE(out && out_t, "lt_op_rope_table_2d_pair: null pointer");
+    return launch_rope_table_2d((float*)out, len, hd, theta, scale_factor, (hipStream_t)stream, (float*)out_t);
+}
+
+extern "C" int lt_op_rope_table_2d(void* out, int32_t len, int32_t hd, float theta, float scale_factor, void* stream) {
+    LT_REQUIRE(out, "lt_op_rope_table_2d: null pointer");
+    return launch_rope_table_2d((float*)out, len, hd, theta, scale_factor, (hipStream_t)stream);
+}
+
+// ---- multi-view sampling (views.hip) and SDE steps (sde.hip) --------------------------------------------------------------------------
+extern "C" int lt_op_views_invert(const int32_t* perm_dev, int32_t* iperm_dev, int32_t* hits_dev, int32_t V, int32_t HW, void* stream) {
+    return launch_views_invert(perm_dev, iperm_dev, hits_dev, V, HW, (hipStream_t)stream);
+}
+extern "C" int lt_op_views_gather(const void* y_dev, const int32_t* perm_dev, const float* vsign_dev, const void* f0_dev, void* out_dev, float half_dt,
+                                  int32_t V, int32_t C, int32_t HW, int32_t dtype, void* stream) {
+    return launch_views_gather(y_dev, perm_dev, vsign_dev, f0_dev, out_dev, half_dt, V, C, HW, dtype, (hipStream_t)stream);
+}
+extern "C" int lt_op_views_reduce(const void* y_dev, const void* f_dev, const int32_t* iperm_dev, const float* isign_dev, void* out_dev, float dt,
+                                  int32_t V, int32_t C, int32_t HW, int32_t dtype, void* stream) {
+    return launch_views_reduce(y_dev, f_dev, iperm_dev, isign_dev, out_dev, dt, V, C, HW, dtype, (hipStream_t)stream);
+}
+
+extern "C" int lt_op_sde_step(int32_t op, const void* x_dev, const void* v_dev, const void* w_dev, const void* k1_dev, const void* xp_dev,
+                              void* out_dev, void* out2_dev, const float* rec_host, int64_t n, int32_t dtype, void* stream) {
+    return launch_sde_step(op, x_dev, v_dev, w_dev, k1_dev, xp_dev, out_dev, out2_dev, rec_host, (long long)n, dtype, (hipStream_t)stream);
+}

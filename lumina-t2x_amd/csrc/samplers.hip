@@ -1,0 +1,327 @@
+// Whole-trajectory samplers of the C ABI (include/lumina_dit.h): the fixed-grid ODE loop of transport/integrators.py:104-116 (torchdiffeq
+// euler / midpoint / rk4), multi-view (visual-anagram) sampling and the SDE loop.  One call per trajectory, no host<->device sync inside it.  All three
+// are written against one scaffold - check_step_shape, StageTimes (engine.h), Trajectory - and a new sampler is too: what a sampler
+// owns is its stage-time fill loop and its stepping body, where the reference's rounding points are.
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "engine.h"
+#include "kernels.h"
+
+namespace {
+
+// the state buffers were sized by lt_create for max_batch x max_tokens; checked before the first copy into them (the model calls validate
+// the same things, but only after z has been copied)
+int check_latent(const lt_engine* e, const char* who, int h, int w) {
+    const int p = e->cfg.patch_size;
+    LT_REQUIRE(h > 0 && w > 0 && h % p == 0 && w % p == 0 && (long long)(h / p) * (w / p) <= e->cfg.max_tokens,
+               "%s: latent %dx%d is not a positive multiple of the patch size or exceeds max_tokens %d", who, h, w, e->cfg.max_tokens);
+    return 0;
+}
+
+int check_step_shape(const lt_engine* e, const char* who, const lt_step_args* a) {
+    LT_REQUIRE(a->batch >= 1 && a->batch <= e->cfg.max_batch, "%s: batch %d outside 1..max_batch %d", who, a->batch, e->cfg.max_batch);
+    if (check_latent(e, who, a->latent_h, a->latent_w)) return 2;
+    LT_REQUIRE(a->io_dtype == LT_BF16 || a->io_dtype == LT_F32, "io_dtype must be bf16 or f32");
+    return 0;
+}
+
+// The state of one trajectory: the ping-pong pair e->ys, the caller's record of the states (if any), the evaluation count.
+struct Trajectory {
+    lt_engine* e; const lt_step_args* a; int use_cfg; hipStream_t s;
+    size_t sbytes;  // one state
+    void* traj = nullptr;
+    int cur = 0;
+    long long nfe = 0;
+    int start(const void* z, void* traj_dev, bool z_in_slot0) {
+        traj = traj_dev;
+        LT_CHECK_HIP(hipMemcpyAsync(e->ys[0], z, sbytes, hipMemcpyDeviceToDevice, s));
+        if (traj && z_in_slot0) LT_CHECK_HIP(hipMemcpyAsync(traj, z, sbytes, hipMemcpyDeviceToDevice, s));
+        return 0;
+    }
+    void* y0() const { return e->ys[cur]; }      // the current state
+    void* y1() const { return e->ys[cur ^ 1]; }  // where the step writes the next one
+    // one model evaluation at stage time number `call` of the committed table
+    int eval(const void* y, int call, void* out) { ++nfe; return forward_graphed(e, y, e->times.dev + (size_t)call * a->batch, out, a, use_cfg, s); }
+    int advance(int traj_slot) {  // y1 is the current state now [and slot `traj_slot` of the record]
+        if (traj) LT_CHECK_HIP(hipMemcpyAsync((char*)traj + (size_t)traj_slot * sbytes, y1(), sbytes, hipMemcpyDeviceToDevice, s));
+        cur ^= 1;
+        return 0;
+    }
+    int finish(void* final_dev) {  // (null: not asked for, or the last step's kernel wrote it)
+        if (final_dev) LT_CHECK_HIP(hipMemcpyAsync(final_dev, y0(), sbytes, hipMemcpyDeviceToDevice, s));
+        e->last_nfe = nfe;
+        return 0;
+    }
+};
+
+float bf16_round_host(float f) {
+    uint32_t u;
+    memcpy(&u, &f, 4);
+    u += 0x7fffu + ((u >> 16) & 1u);
+    u &= 0xffff0000u;
+    memcpy(&f, &u, 4);
+    return f;
+}
+
+}  // namespace
+
+extern "C" int lt_sample_ode(lt_engine* e, const void* z_dev, void* traj_dev, void* final_dev, const float* tgrid_host,
+                             int32_t n_grid, int32_t method, int32_t use_cfg, int32_t t_round, const lt_step_args* a,
+                             void* stream) {
+    LT_REQUIRE(e && z_dev && tgrid_host && a, "lt_sample_ode: null argument");
+    LtOptScope opt_scope(&e->opts);
+    LT_REQUIRE(n_grid >= 2, "lt_sample_ode: need at least 2 grid points");
+    LT_REQUIRE(method >= LT_ODE_EULER && method <= LT_ODE_RK4, "lt_sample_ode: unknown method %d", method);
+    hipStream_t s = (hipStream_t)stream;
+    const int B = a->batch;
+    if (check_step_shape(e, "lt_sample_ode", a)) return 2;
+    const int stages = method == LT_ODE_EULER ? 1 : (method == LT_ODE_MIDPOINT ? 2 : 4);
+    const int ncalls = (n_grid - 1) * stages;
+    const long long n = (long long)B * e->cfg.in_channels * a->latent_h * a->latent_w;
+    const bool bf = a->io_dtype == LT_BF16;
+    // stage times; torchdiffeq's _PerturbFunc casts t to the state dtype before calling the model, then
+    // integrators.py:108 broadcasts it to an fp32 [B] vector
+    float* tp = e->times.begin(ncalls * B, s);
+    if (!tp) return 1;
+    std::vector<float> dts(n_grid - 1);
+    for (int i = 0; i + 1 < n_grid; ++i) {
+        const float t0 = tgrid_host[i], t1 = tgrid_host[i + 1];
+        const float dt = t1 - t0;
+        dts[i] = dt;
+        float ts[4];
+        if (method == LT_ODE_EULER) ts[0] = t0;
+        else if (method == LT_ODE_MIDPOINT) { ts[0] = t0; ts[1] = t0 + 0.5f * dt; }
+        else { ts[0] = t0; ts[1] = t0 + dt * (float)(1.0 / 3.0); ts[2] = t0 + dt * (float)(2.0 / 3.0); ts[3] = t1; }
+        for (int k = 0; k < stages; ++k) {
+            const float tv = (t_round && bf) ? bf16_round_host(ts[k]) : ts[k];
+            for (int b = 0; b < B; ++b) tp[((size_t)i * stages + k) * B + b] = tv;
+        }
+    }
+    if (e->times.commit(ncalls * B, s)) return 1;
+    Trajectory tr{e, a, use_cfg, s, (size_t)n * (bf ? 2 : 4)};
+    if (tr.start(z_dev, traj_dev, true)) return 1;
+    const int dt_code = bf ? 1 : 0;
+    for (int i = 0; i + 1 < n_grid; ++i) {
+        void *y0 = tr.y0(), *y1 = tr.y1();
+        // torchdiffeq multiplies the 0-dim DEVICE tensor dt = t1 - t0 (fp32) with the bf16 state / slopes; PyTorch's type
+        // promotion keeps bf16 and casts the 0-dim operand to it first, so with a bf16 state every `dt * k` of the reference
+        // sees bf16(dt) (0.5 dt is exact after that).  The stage TIMES above stay fp32 (t0 + dt / 2 is fp32 arithmetic).
+        const float dt = bf ? bf16_round_host(dts[i]) : dts[i];
+        const int c0 = i * stages;
+        if (method == LT_ODE_EULER) {
+            if (tr.eval(y0, c0, e->kbuf[0])) return 1;
+            if (launch_ode_combine(0, y0, e->kbuf[0], nullptr, nullptr, nullptr, y1, dt_code, dt, n, s)) return 1;
+        } else if (method == LT_ODE_MIDPOINT) {
+            if (tr.eval(y0, c0, e->kbuf[0])) return 1;
+            if (launch_ode_combine(0, y0, e->kbuf[0], nullptr, nullptr, nullptr, e->ymid, dt_code, 0.5f * dt, n, s)) return 1;
+            if (tr.eval(e->ymid, c0 + 1, e->kbuf[1])) return 1;
+            if (launch_ode_combine(0, y0, e->kbuf[1], nullptr, nullptr, nullptr, y1, dt_code, dt, n, s)) return 1;
+        } else {
+            if (tr.eval(y0, c0, e->kbuf[0])) return 1;
+            if (launch_ode_combine(1, y0, e->kbuf[0], nullptr, nullptr, nullptr, e->ymid, dt_code, dt, n, s)) return 1;
+            if (tr.eval(e->ymid, c0 + 1, e->kbuf[1])) return 1;
+            if (launch_ode_combine(2, y0, e->kbuf[0], e->kbuf[1], nullptr, nullptr, e->ymid, dt_code, dt, n, s)) return 1;
+            if (tr.eval(e->ymid, c0 + 2, e->kbuf[2])) return 1;
+            if (launch_ode_combine(3, y0, e->kbuf[0], e->kbuf[1], e->kbuf[2], nullptr, e->ymid, dt_code, dt, n, s)) return 1;
+            if (tr.eval(e->ymid, c0 + 3, e->kbuf[3])) return 1;
+            if (launch_ode_combine(4, y0, e->kbuf[0], e->kbuf[1], e->kbuf[2], e->kbuf[3], y1, dt_code, dt, n, s)) return 1;
+        }
+        if (tr.advance(i + 1)) return 1;
+    }
+    return tr.finish(final_dev);
+}
+
+// ---- multi-view (visual-anagram) sampling ------------------------------------------------------------------------------------------
+void drop_views(lt_engine* e) {
+    if (e->vw_perm) (void)hipFree(e->vw_perm);
+    if (e->vw_iperm) (void)hipFree(e->vw_iperm);
+    if (e->vw_hits) (void)hipFree(e->vw_hits);
+    if (e->vw_vsign) (void)hipFree(e->vw_vsign);
+    if (e->vw_isign) (void)hipFree(e->vw_isign);
+    e->vw_perm = e->vw_iperm = e->vw_hits = nullptr;
+    e->vw_vsign = e->vw_isign = nullptr;
+    e->vw_V = e->vw_h = e->vw_w = 0;
+}
+
+extern "C" int lt_set_views(lt_engine* e, const int32_t* perm_dev, const float* vsign_host, const float* isign_host, int32_t V, int32_t latent_h,
+                            int32_t latent_w, void* stream) {
+    LT_REQUIRE(e, "lt_set_views: null engine");
+    hipStream_t s = (hipStream_t)stream;
+    const lt_config& c = e->cfg;
+    LT_REQUIRE(c.variant == LT_VARIANT_NEXT_T2I, "lt_set_views: multi-view sampling drives the text-conditional Next-DiT (LT_VARIANT_NEXT_T2I) only; "
+               "this engine is variant %d", c.variant);
+    if (V == 0 && !perm_dev) {  // drop the tables (kernels of an earlier trajectory may still read them)
+        LT_CHECK_HIP(hipStreamSynchronize(s));
+        drop_views(e);
+        return 0;
+    }
+    LT_REQUIRE(perm_dev && vsign_host && isign_host, "lt_set_views: null argument");
+    LT_REQUIRE(V >= 1, "lt_set_views: V = %d views (need at least 1)", V);
+    LT_REQUIRE(2 * (long long)V <= c.max_batch, "lt_set_views: %d views need a batch of 2 V = %d rows (view prompts + negative prompts), max_batch is %d", V,
+               2 * V, c.max_batch);
+    if (check_latent(e, "lt_set_views", latent_h, latent_w)) return 2;
+    const int C = c.in_channels, HW = latent_h * latent_w;
+    LT_REQUIRE(HW % 4 == 0, "lt_set_views: H * W = %d must be a multiple of 4", HW);
+    for (int i = 0; i < V * C; ++i)
+        LT_REQUIRE((vsign_host[i] == 1.f || vsign_host[i] == -1.f) && (isign_host[i] == 1.f || isign_host[i] == -1.f),
+                   "lt_set_views: sign of view %d, channel %d is not +1 / -1", i / C, i % C);
+    LT_CHECK_HIP(hipStreamSynchronize(s));  // table upload may synchronise; kernels of an earlier trajectory may still read the old tables
+    drop_views(e);
+    const size_t tb = (size_t)V * HW * sizeof(int);
+    auto fail = [&]() { drop_views(e); return 1; };
+    if (hipMalloc((void**)&e->vw_perm, tb) != hipSuccess || hipMalloc((void**)&e->vw_iperm, tb) != hipSuccess ||
+        hipMalloc((void**)&e->vw_hits, tb + sizeof(int)) != hipSuccess || hipMalloc((void**)&e->vw_vsign, (size_t)V * C * sizeof(float)) != hipSuccess ||
+        hipMalloc((void**)&e->vw_isign, (size_t)V * C * sizeof(float)) != hipSuccess) {
+        lt_set_error("lt_set_views: out of device memory for the tables of %d views of %d pixels", V, HW);
+        return fail();
+    }
+    int bad = -1;
+    if (hipMemcpyAsync(e->vw_perm, perm_dev, tb, hipMemcpyDeviceToDevice, s) != hipSuccess ||
+        hipMemsetAsync(e->vw_iperm, 0, tb, s) != hipSuccess ||
+        hipMemcpyAsync(e->vw_vsign, vsign_host, (size_t)V * C * sizeof(float), hipMemcpyHostToDevice, s) != hipSuccess ||
+        hipMemcpyAsync(e->vw_isign, isign_host, (size_t)V * C * sizeof(float), hipMemcpyHostToDevice, s) != hipSuccess ||
+        launch_views_invert(e->vw_perm, e->vw_iperm, e->vw_hits, V, HW, s) ||
+        hipMemcpyAsync(&bad, e->vw_hits + (size_t)V * HW, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess) {
+        lt_set_error("lt_set_views: uploading the view tables failed");
+        return fail();
+    }
+    if (bad != 0) {
+        lt_set_error("lt_set_views: a view table is not a bijection on [0, %d): %d entries are out of range or name a pixel a second time", HW, bad);
+        return fail();
+    }
+    e->vw_V = V; e->vw_h = latent_h; e->vw_w = latent_w;
+    return 0;
+}
+
+extern "C" int lt_sample_views(lt_engine* e, const void* z_dev, void* traj_dev, void* final_dev, const float* tgrid_host, int32_t n_grid,
+                               int32_t method, const lt_step_args* a, void* stream) {
+    LT_REQUIRE(e && z_dev && tgrid_host && a, "lt_sample_views: null argument");
+    LtOptScope opt_scope(&e->opts);
+    LT_REQUIRE(e->cfg.variant == LT_VARIANT_NEXT_T2I, "lt_sample_views: multi-view sampling drives the text-conditional Next-DiT (LT_VARIANT_NEXT_T2I) "
+               "only; this engine is variant %d", e->cfg.variant);
+    LT_REQUIRE(n_grid >= 2, "lt_sample_views: need at least 2 grid points");
+    LT_REQUIRE(method != LT_ODE_RK4, "lt_sample_views: rk4 is not a multi-view method (the reference steps views with its midpoint_solver; euler is the "
+               "one-stage form)");
+    LT_REQUIRE(method == LT_ODE_EULER || method == LT_ODE_MIDPOINT, "lt_sample_views: unknown method %d", method);
+    LT_REQUIRE(e->vw_V >= 1, "lt_sample_views: no view tables (call lt_set_views first)");
+    const int V = e->vw_V, B = 2 * V, C = e->cfg.in_channels, HW = e->vw_h * e->vw_w;
+    LT_REQUIRE(a->batch == B, "lt_sample_views: %d views need a->batch = 2 V = %d (view prompts + negative prompts), got %d", V, B, a->batch);
+    LT_REQUIRE(a->latent_h == e->vw_h && a->latent_w == e->vw_w, "lt_sample_views: the view tables are for a %dx%d latent, the call has %dx%d", e->vw_h,
+               e->vw_w, a->latent_h, a->latent_w);
+    // (not check_step_shape: batch and latent are checked against the view tables first, in this order - the tests pin the first error)
+    LT_REQUIRE(a->io_dtype == LT_BF16 || a->io_dtype == LT_F32, "io_dtype must be bf16 or f32");
+    LT_REQUIRE(B <= e->cfg.max_batch, "lt_sample_views: batch %d exceeds max_batch %d", B, e->cfg.max_batch);
+    LT_REQUIRE(e->reg_Y == 0 && e->prompt_B == B, "lt_prepare_prompt was called for batch %d, step has batch %d (multi-view sampling needs the V view "
+               "prompts followed by V rows of the negative prompt)", e->prompt_B, B);
+    hipStream_t s = (hipStream_t)stream;
+    const int stages = method == LT_ODE_EULER ? 1 : 2;
+    const int ncalls = (n_grid - 1) * stages;
+    const bool bf = a->io_dtype == LT_BF16;
+    float* tp = e->times.begin(ncalls * B, s);
+    if (!tp) return 1;
+    // generate.py:212-219: t0, t1 are Python floats (the fp32 grid's values as doubles); dt = t1 - t0 and half_dt = 0.5 dt are doubles that
+    // multiply a tensor as fp32 scalars; the stage times are torch.full((2,), t0) and torch.full((2,), t0 + half_dt): fp32 of the double
+    std::vector<float> dts(n_grid - 1), hdts(n_grid - 1);
+    for (int i = 0; i + 1 < n_grid; ++i) {
+        const double t0 = tgrid_host[i], dt = (double)tgrid_host[i + 1] - t0, half_dt = 0.5 * dt;
+        dts[i] = (float)dt;
+        hdts[i] = (float)half_dt;
+        const float ts[2] = {(float)t0, (float)(t0 + half_dt)};
+        for (int k = 0; k < stages; ++k)
+            for (int b = 0; b < B; ++b) tp[((size_t)i * stages + k) * B + b] = ts[k];
+    }
+    if (e->times.commit(ncalls * B, s)) return 1;
+    // the state is ONE latent; one evaluation is ALL views: forward_with_cfg on 2 V rows, rows 0..V-1 = the viewed latents in ymid (it
+    // reads the first half only)
+    Trajectory tr{e, a, 1, s, (size_t)C * HW * (bf ? 2 : 4)};
+    if (tr.start(z_dev, traj_dev, true)) return 1;
+    const int dt_code = bf ? 1 : 0;
+    for (int i = 0; i + 1 < n_grid; ++i) {
+        void *y0 = tr.y0(), *y1 = tr.y1();
+        const int c0 = i * stages;
+        const void* slope = e->kbuf[0];
+        if (launch_views_gather(y0, e->vw_perm, e->vw_vsign, nullptr, e->ymid, 0.f, V, C, HW, dt_code, s)) return 1;
+        if (tr.eval(e->ymid, c0, e->kbuf[0])) return 1;
+        if (method == LT_ODE_MIDPOINT) {
+            if (launch_views_gather(y0, e->vw_perm, e->vw_vsign, e->kbuf[0], e->ymid, hdts[i], V, C, HW, dt_code, s)) return 1;
+            if (tr.eval(e->ymid, c0 + 1, e->kbuf[1])) return 1;
+            slope = e->kbuf[1];
+        }
+        if (launch_views_reduce(y0, slope, e->vw_iperm, e->vw_isign, y1, dts[i], V, C, HW, dt_code, s)) return 1;
+        if (tr.advance(i + 1)) return 1;
+    }
+    return tr.finish(final_dev);
+}
+
+// ---- SDE sampling (sde.hip) --------------------------------------------------------------------------------------------------------
+extern "C" int lt_sample_sde(lt_engine* e, const void* z_dev, const void* noise_dev, void* traj_dev, void* final_dev, const float* steps_host,
+                             int32_t n_steps, int32_t method, int32_t last_step, const float* last_coef_host, int32_t use_cfg,
+                             const lt_step_args* a, void* stream) {
+    LT_REQUIRE(e && z_dev && noise_dev && steps_host && a, "lt_sample_sde: null argument");
+    LtOptScope opt_scope(&e->opts);
+    LT_REQUIRE(n_steps >= 2, "lt_sample_sde: n_steps %d (need at least 2: one loop step and the last step)", n_steps);
+    LT_REQUIRE(method == LT_SDE_EULER || method == LT_SDE_HEUN, "lt_sample_sde: unknown method %d", method);
+    LT_REQUIRE(last_step >= LT_SDE_LAST_NONE && last_step <= LT_SDE_LAST_EULER, "lt_sample_sde: unknown last_step %d", last_step);
+    LT_REQUIRE(last_step == LT_SDE_LAST_NONE || (last_coef_host && final_dev), "lt_sample_sde: null argument (a last step needs last_coef_host and "
+               "final_dev)");
+    hipStream_t s = (hipStream_t)stream;
+    const int B = a->batch;
+    if (check_step_shape(e, "lt_sample_sde", a)) return 2;
+    const int stages = method == LT_SDE_EULER ? 1 : 2;
+    const int nloop = n_steps - 1;
+    const int nrec = nloop * stages;
+    const int has_last = last_step != LT_SDE_LAST_NONE;
+    const int ncalls = nrec + has_last;
+    // the score divides by var = sigma^2 - r sigma' sigma (path.py: get_score_from_velocity); the last-step rule Euler has no score
+    for (int i = 0; i < nrec; ++i) {
+        const float var = steps_host[(size_t)i * LT_SDE_REC + 2];
+        LT_REQUIRE(std::isfinite(var) && var > 0.f, "lt_sample_sde: var %g of stage %d (step %d) is not finite and positive", (double)var, i % stages,
+                   i / stages);
+    }
+    if (last_step == LT_SDE_LAST_MEAN || last_step == LT_SDE_LAST_TWEEDIE)
+        LT_REQUIRE(std::isfinite(last_coef_host[2]) && last_coef_host[2] > 0.f, "lt_sample_sde: var %g of the last step is not finite and positive",
+                   (double)last_coef_host[2]);
+    const long long n = (long long)B * e->cfg.in_channels * a->latent_h * a->latent_w;
+    const bool bf = a->io_dtype == LT_BF16;
+    const size_t sbytes = (size_t)n * (bf ? 2 : 4);
+    float* tp = e->times.begin(ncalls * B, s);
+    if (!tp) return 1;
+    // stage times: the loop hands the model a [B] vector of the state dtype (integrators.py: th.ones(B).to(x) * t), the last step an fp32 one
+    for (int i = 0; i < ncalls; ++i) {
+        const float tv = i < nrec ? steps_host[(size_t)i * LT_SDE_REC] : last_coef_host[0];
+        for (int b = 0; b < B; ++b) tp[(size_t)i * B + b] = tv;
+    }
+    if (e->times.commit(ncalls * B, s)) return 1;
+    Trajectory tr{e, a, use_cfg, s, sbytes};
+    if (tr.start(z_dev, traj_dev, false)) return 1;  // the record holds loop state i in slot i: z is not part of it
+    const int dt_code = bf ? 1 : 0;
+    for (int i = 0; i < nloop; ++i) {
+        void *y0 = tr.y0(), *y1 = tr.y1();
+        const void* w = (const char*)noise_dev + (size_t)i * sbytes;
+        const float* rec = steps_host + (size_t)i * stages * LT_SDE_REC;
+        const int c0 = i * stages;
+        if (method == LT_SDE_EULER) {
+            if (tr.eval(y0, c0, e->kbuf[0])) return 1;
+            if (launch_sde_step(LT_SDE_OP_EULER, y0, e->kbuf[0], w, nullptr, nullptr, y1, nullptr, rec, n, dt_code, s)) return 1;
+        } else {  // xhat in ymid, K1 in kbuf[1], the predictor state in kbuf[2]
+            if (launch_sde_step(LT_SDE_OP_HEUN_XHAT, y0, nullptr, w, nullptr, nullptr, e->ymid, nullptr, rec, n, dt_code, s)) return 1;
+            if (tr.eval(e->ymid, c0, e->kbuf[0])) return 1;
+            if (launch_sde_step(LT_SDE_OP_HEUN_K1, e->ymid, e->kbuf[0], nullptr, nullptr, nullptr, e->kbuf[2], e->kbuf[1], rec, n, dt_code, s)) return 1;
+            if (tr.eval(e->kbuf[2], c0 + 1, e->kbuf[3])) return 1;
+            if (launch_sde_step(LT_SDE_OP_HEUN_OUT, e->ymid, e->kbuf[3], nullptr, e->kbuf[1], e->kbuf[2], y1, nullptr, rec + LT_SDE_REC, n, dt_code, s))
+                return 1;
+        }
+        if (tr.advance(i)) return 1;
+    }
+    if (has_last) {  // the last step's kernel writes final_dev itself
+        const int op = last_step == LT_SDE_LAST_MEAN ? LT_SDE_OP_LAST_MEAN : (last_step == LT_SDE_LAST_TWEEDIE ? LT_SDE_OP_LAST_TWEEDIE : LT_SDE_OP_LAST_EULER);
+        if (tr.eval(tr.y0(), nrec, e->kbuf[0])) return 1;
+        if (launch_sde_step(op, tr.y0(), e->kbuf[0], nullptr, nullptr, nullptr, final_dev, nullptr, last_coef_host, n, dt_code, s)) return 1;
+    }
+    return tr.finish(has_last ? nullptr : final_dev);
+}
+
+extern "C" int64_t lt_last_nfe(lt_engine* e) { return e ? e->last_nfe : -1; }

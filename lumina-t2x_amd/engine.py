@@ -30,6 +30,21 @@ def _require_gpu(t: torch.Tensor, name: str) -> None:
         )
 
 
+def _grid_array(tgrid):
+    """a fixed time grid (tensor or sequence) as a C float array of its fp32 values, and its length"""
+    t = tgrid if isinstance(tgrid, torch.Tensor) else torch.tensor(list(tgrid), dtype=torch.float32)
+    grid = [float(v) for v in t.detach().to("cpu", torch.float32).tolist()]
+    return (C.c_float * len(grid))(*grid), len(grid)
+
+
+def _traj_or_final(z: torch.Tensor, n: int, state_shape, return_trajectory: bool):
+    """the output buffer of a whole-trajectory call and its (trajectory, final) pointers: all ``n`` states ``[n, *state_shape]`` or the
+    last one alone, shaped like ``z`` - the other pointer is null"""
+    out = torch.empty((n,) + tuple(state_shape), dtype=z.dtype, device=z.device) if return_trajectory else torch.empty_like(z)
+    ptr, null = C.c_void_p(out.data_ptr()), C.c_void_p(0)
+    return (out, ptr, null) if return_trajectory else (out, null, ptr)
+
+
 class _SourceCache:
     """Remembers WHICH tensors the engine's conditioning was prepared from, so that the per-step calls of an ODE solve (same
     ``model_kwargs`` objects every step) do not redo the caption work.  A hit needs the very same tensor objects, unmodified
@@ -255,16 +270,9 @@ class DiTEngine:
         if method not in _lib.ODE_METHODS:
             raise LuminaLibError(f"fixed-grid method '{method}' not in {sorted(_lib.ODE_METHODS)}")
         z = z.contiguous()
-        grid = [float(v) for v in tgrid.detach().to("cpu", torch.float32).tolist()]
-        n = len(grid)
-        garr = (C.c_float * n)(*grid)
+        garr, n = _grid_array(tgrid)
         a = self._step_args(z, cfg_scale, scale_factor, scale_watershed, base_seqlen, proportional_attn, ntk_factor=ntk_factor)
-        if return_trajectory:
-            out = torch.empty((n,) + tuple(z.shape), dtype=z.dtype, device=z.device)
-            traj_ptr, fin_ptr = C.c_void_p(out.data_ptr()), C.c_void_p(0)
-        else:
-            out = torch.empty_like(z)
-            traj_ptr, fin_ptr = C.c_void_p(0), C.c_void_p(out.data_ptr())
+        out, traj_ptr, fin_ptr = _traj_or_final(z, n, z.shape, return_trajectory)
         with torch.cuda.device(self.device):
             rc = self.lib.lt_sample_ode(self.handle, C.c_void_p(z.data_ptr()), traj_ptr, fin_ptr, garr, n,
                                         _lib.ODE_METHODS[method], int(use_cfg), int(t_round_to_state_dtype), C.byref(a),
@@ -362,18 +370,10 @@ class DiTEngine:
         if key is None:
             raise LuminaLibError("sample_views: no views uploaded (call set_views first)")
         z = z.contiguous()
-        grid = [float(v) for v in (tgrid.detach().to("cpu", torch.float32).tolist() if isinstance(tgrid, torch.Tensor) else
-                                   torch.tensor(list(tgrid), dtype=torch.float32).tolist())]
-        n = len(grid)
-        garr = (C.c_float * n)(*grid)
+        garr, n = _grid_array(tgrid)
         a = self._step_args(z, cfg_scale, scale_factor, scale_watershed, base_seqlen, proportional_attn)
         a.batch = 2 * key[0]
-        if return_trajectory:
-            out = torch.empty((n,) + tuple(z.shape[1:]), dtype=z.dtype, device=z.device)
-            traj_ptr, fin_ptr = C.c_void_p(out.data_ptr()), C.c_void_p(0)
-        else:
-            out = torch.empty_like(z)
-            traj_ptr, fin_ptr = C.c_void_p(0), C.c_void_p(out.data_ptr())
+        out, traj_ptr, fin_ptr = _traj_or_final(z, n, z.shape[1:], return_trajectory)
         with torch.cuda.device(self.device):
             rc = self.lib.lt_sample_views(self.handle, C.c_void_p(z.data_ptr()), traj_ptr, fin_ptr, garr, n, _lib.ODE_METHODS[method],
                                           C.byref(a), C.c_void_p(_stream_ptr(self.device)))
