@@ -2,7 +2,7 @@
  *
  * NOT part of the drop-in boundary (include/lumina_dit.h): nothing here is needed to run the reference's path.  This header names
  * the options lt_set_option / lt_engine_set_option accept (A/B measurements, tests; every default is the measured-best setting) and
- * declares the one instrumented-kernel entry point.  The option table itself lives in lumina-t2x_amd/csrc/options.hip;
+ * declares the instrumented-kernel entry point and the row kernels' full-argument test entry points.  The option table itself lives in lumina-t2x_amd/csrc/options.hip;
  * tests/test_abi.py keeps this text and the table in step (every name, its range and default).
  */
 #ifndef LUMINA_DIT_DEBUG_H
@@ -107,6 +107,44 @@ extern "C" {
 int lt_op_attention_trace(const void* q_dev, const void* k_dev, const void* vt_dev, void* out_dev, int32_t B,
                           int32_t H, int32_t Hkv, int32_t N, int32_t Nk, int32_t Nkpad, int32_t hd, float scale,
                           void* trace_dev, void* stream);
+
+/* The row kernels (csrc/norm.hip, csrc/qkv_post.hip) with every argument of their launchers, for tests/test_gpu_rows_exact.py.  Pointer
+ * arguments that a form does not use are NULL.  Layouts: lumina_dit.h (lt_op_rmsnorm_mod, lt_op_gated_residual_norm, lt_op_qk_norm_rope,
+ * lt_op_v_transpose, lt_op_pair_layout).
+ *   out_pair / h_pair: the output in the row-pair-interleaved layout (even row count, d % 32 == 0).
+ *   ystat: [B * N][ystat_slots] float partial sums of squares of the rows of y, as a plain input: the streaming kernel without a GEMM.
+ *   moe_ys [sorted rows, d], moe_pos int32 [B * N][2], moe_wts bf16 [B * N][2]: y is the top-2 combine formed on load (y may be NULL).
+ *   route_w bf16 [route_E, d], route_sel int32 [B * N][2], route_wts bf16 [B * N][2], route_forced int32 [B * N][2] or NULL: the MoE kernel with
+ *   next_mode 1 routes h on its way out.
+ *   cs_table: [2][cs_len][hd / 4 (rope_mode 1) or hd / 2 (rope_mode 2)] float (cos, sin); branch 0 is read when t[0] < watershed, branch 1
+ *   otherwise and when t is NULL.  n_tok_b / grid_w_b: int32 [B] of a packed batch (rows n >= n_tok_b[b] rotate like the sample's last token).
+ *   qstat_in: [B * N][qstat_slots] float2 (sum, sum of squares) over qstat_width columns -> qstat_out [B * N] float2 (mean, rstd).
+ * lt_op_gated_residual_norm_describe writes the name of the kernel the launcher would pick (the same expressions as the dispatch). */
+int lt_op_rmsnorm_mod_ex(const void* x, const void* w, const void* scale, const void* shift, int32_t ld_mod, void* out, int32_t B,
+                         int32_t N, int32_t d, float eps, int32_t scale_pre, int32_t out_pair, void* stream);
+int lt_op_gated_residual_norm_ex(void* x, const void* y, const void* post_w, const void* gate, int32_t post_mode, int32_t gate_mode,
+                                 const void* next_w, const void* next_scale, const void* next_shift, int32_t next_mode, int32_t ld_mod,
+                                 void* h, int32_t B, int32_t N, int32_t d, float eps, float eps_next, int32_t scale_pre, int32_t h_pair,
+                                 const void* ystat, int32_t ystat_slots, const void* moe_ys, const void* moe_pos, const void* moe_wts,
+                                 const void* route_w, int32_t route_E, void* route_sel, void* route_wts, const void* route_forced,
+                                 void* stream);
+int lt_op_gated_residual_norm_describe(int32_t post_mode, int32_t gate_mode, int32_t next_mode, int32_t d, int32_t has_next_w,
+                                       int32_t has_next_scale, int32_t has_next_shift, int32_t scale_pre, int32_t has_ystat,
+                                       int32_t ystat_slots, int32_t has_moe, char* out, int32_t cap);
+int lt_op_qk_norm_rope_ex(const void* src, int32_t ld_src, int32_t col0, const void* ln_w, const void* ln_b, float ln_eps, void* dst,
+                          int32_t B, int32_t N, int32_t heads, int32_t hd, int32_t rope_mode, const void* cs_table, int32_t cs_len,
+                          const void* t, float watershed, int32_t grid_w, const void* n_tok_b, const void* grid_w_b, float out_scale,
+                          const void* qstat_in, void* qstat_out, int32_t qstat_slots, int32_t qstat_width, void* stream);
+int lt_op_qk_norm_rope_pair(const void* qkv, int32_t ld, int32_t q_col0, int32_t k_col0, const void* q_ln_w, const void* q_ln_b,
+                            const void* k_ln_w, const void* k_ln_b, float ln_eps, void* q_dst, void* k_dst, int32_t B, int32_t N,
+                            int32_t heads, int32_t kv_heads, int32_t hd, int32_t rope_mode, const void* cs_table, int32_t cs_len,
+                            const void* t, float watershed, int32_t grid_w, const void* n_tok_b, const void* grid_w_b, float q_out_scale,
+                            float k_out_scale, void* stream);
+int lt_op_qkv_post(const void* qkv, int32_t ld, int32_t q_col0, int32_t k_col0, int32_t v_col0, const void* q_ln_w, const void* q_ln_b,
+                   const void* k_ln_w, const void* k_ln_b, float ln_eps, void* q_dst, void* k_dst, void* vt_dst, int32_t B, int32_t N,
+                   int32_t Npad, int32_t heads, int32_t kv_heads, int32_t hd, int32_t rope_mode, const void* cs_table, int32_t cs_len,
+                   const void* t, float watershed, int32_t grid_w, const void* n_tok_b, const void* grid_w_b, float q_out_scale,
+                   float k_out_scale, void* stream);
 
 #ifdef __cplusplus
 }

@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # LUMINA_DIT_LIB: an alternate build of the same C ABI (A/B measurements of two kernel versions on one box); still no fallback
 LIB_PATH = os.environ.get("LUMINA_DIT_LIB") or os.path.join(_HERE, "lib", "liblumina_dit.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "lumina_dit.h")
-DEBUG_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "lumina_dit_debug.h")  # options' documentation + one trace entry point
+DEBUG_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "lumina_dit_debug.h")  # options' documentation, the trace entry point, the row kernels' test entry points
 LT_OPTION_INHERIT = -2 ** 31
 
 LT_F32, LT_BF16, LT_F16 = 0, 1, 2
@@ -138,6 +138,16 @@ _SIGNATURES: Dict[str, tuple] = {
     "lt_op_proj_gated_residual_norm": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _f32, _i32, _vp]),
     "lt_op_qkv_qstat": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _f32, _vp, _vp, _vp, _vp]),
     "lt_op_attention_qraw": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "lt_op_rmsnorm_mod_ex": (_i32, [_vp, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _f32, _i32, _i32, _vp]),
+    "lt_op_gated_residual_norm_ex": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _f32, _f32, _i32, _i32,
+                                            _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "lt_op_gated_residual_norm_describe": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, C.c_char_p, _i32]),
+    "lt_op_qk_norm_rope_ex": (_i32, [_vp, _i32, _i32, _vp, _vp, _f32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _f32, _i32, _vp, _vp, _f32,
+                                     _vp, _vp, _i32, _i32, _vp]),
+    "lt_op_qk_norm_rope_pair": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp,
+                                       _f32, _i32, _vp, _vp, _f32, _f32, _vp]),
+    "lt_op_qkv_post": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp,
+                              _i32, _vp, _f32, _i32, _vp, _vp, _f32, _f32, _vp]),
 }
 
 _lib = None

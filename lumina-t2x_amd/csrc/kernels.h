@@ -142,6 +142,7 @@ struct GatedResArgs {
     int h_pair = 0;  // next_mode 1: `h` in the row-pair-interleaved layout (GemmArgs::pair_ab); rows even, d % 32 == 0
 };
 int launch_gated_residual_norm(const GatedResArgs& a, hipStream_t stream);
+const char* gated_residual_norm_describe(const GatedResArgs& a);  // name of the kernel launch_gated_residual_norm would launch (the same expressions as its dispatch), or "none"
 
 // ---- q/k/v post-processing (qkv_post.hip) ------------------------------------------------------
 struct QkPostArgs {

@@ -8,6 +8,8 @@
 //
 // Rows are held in registers between the statistics pass and the apply pass (16-byte loads, 8 bf16 per
 // lane per chunk; wave shuffles for the reductions; no LDS, no barrier).
+#include <cstdio>
+
 #include "common.h"
 #include "kernels.h"
 #include "moe_route.h"
@@ -449,3 +451,39 @@ int launch_gated_residual_norm(const GatedResArgs& a_in, hipStream_t stream) {
     return 0;
 }
 
+
+// name of the kernel launch_gated_residual_norm would launch for these arguments: the same expressions as its dispatch above, in the same
+// order (only the pointers' nullness is looked at), or "none" where the launcher refuses.  For the tests, which assert the form a case means.
+const char* gated_residual_norm_describe(const GatedResArgs& a_in) {
+    static thread_local char name[64];
+    GatedResArgs a = a_in;
+    a.apex = lt_opt(OPT_RMSNORM_APEX);
+    if (!(a.d % 8 == 0 && a.d > 0 && a.d <= 64 * 8 * MAXCH_LIMIT) || (a.y == nullptr && a.moe_pos == nullptr)) return "none";
+    const int nch64 = ((a.d >> 3) + 63) / 64;
+    const int mc = nch64 == 7 ? 8 : nch64;  // LT_DISPATCH_CHUNKS: 1..6, else 8
+    if (a.moe_pos) {
+        if (a.apex) return "none";
+        if (lt_opt(OPT_NORM_SPECIALIZE) && !a.apex && a.gate_mode == 0 && a.post_mode == 1 && (a.next_mode == 1 || a.next_mode == 2) && ((a.d >> 3) + 63) / 64 == 3) {
+            snprintf(name, sizeof name, "gated_residual_norm_kernel<3,1,0,%d,moe>", a.next_mode);
+            return name;
+        }
+        snprintf(name, sizeof name, "gated_residual_norm_kernel<%d,-1,-1,-1,moe>", mc);
+        return name;
+    }
+    if (a.ystat && lt_opt(OPT_NORM_SPECIALIZE) && !a.apex && a.gate_mode == 0 && a.post_mode == 1 && a.next_mode == 1 && a.pf.blocks == 0 &&
+        a.next_w && a.next_scale && a.scale_pre && !a.next_shift && a.y && a.d % 256 == 0 && a.ystat_slots > 0 && a.ystat_slots % 2 == 0) {
+        const int nh = a.d / 256;
+        if (nh == 6 || nh == 9) {
+            snprintf(name, sizeof name, "gated_residual_norm_ys_kernel<%d,%d>", nh, lt_opt(OPT_GRN_YSTAT) == 2 ? 2 : 1);
+            return name;
+        }
+    }
+    if (lt_opt(OPT_NORM_SPECIALIZE) && !a.apex && a.gate_mode == 0 && (a.post_mode == 0 || a.post_mode == 1) && (a.next_mode == 1 || a.next_mode == 2)) {
+        if (nch64 == 3 || nch64 == 5 || nch64 == 6) {
+            snprintf(name, sizeof name, "gated_residual_norm_kernel<%d,%d,0,%d>", nch64, a.post_mode, a.next_mode);
+            return name;
+        }
+    }
+    snprintf(name, sizeof name, "gated_residual_norm_kernel<%d>", mc);
+    return name;
+}

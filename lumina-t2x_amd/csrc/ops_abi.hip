@@ -4,6 +4,7 @@
 #include <cstdio>
 
 #include "../../include/lumina_dit.h"
+#include "../../include/lumina_dit_debug.h"
 #include "common.h"
 #include "kernels.h"
 #include "options.h"
@@ -229,6 +230,130 @@ extern "C" int lt_op_qk_norm_rope(const void* src, int32_t ld_src, int32_t col0,
     q.out_scale = out_scale;
     q.cs_len = 0;  // op level: the caller hands over the single branch table it wants (no branch offset)
     return launch_qk_norm_rope(q, (hipStream_t)stream);
+}
+
+// ---- the row kernels with every argument of their launchers exposed (include/lumina_dit_debug.h; tests/test_gpu_rows_exact.py) ---------
+extern "C" int lt_op_rmsnorm_mod_ex(const void* x, const void* w, const void* scale, const void* shift, int32_t ld_mod, void* out, int32_t B,
+                                    int32_t N, int32_t d, float eps, int32_t scale_pre, int32_t out_pair, void* stream) {
+    LT_REQUIRE(x && out, "lt_op_rmsnorm_mod_ex: null pointer");
+    NormModArgs n;
+    n.x = (const u16*)x; n.w = (const u16*)w; n.scale = (const u16*)scale; n.shift = (const u16*)shift; n.out = (u16*)out;
+    n.rows = B * N; n.rows_per_batch = N; n.d = d; n.ld_mod = ld_mod; n.eps = eps; n.scale_pre = scale_pre; n.out_pair = out_pair;
+    return launch_rmsnorm_mod(n, (hipStream_t)stream);
+}
+
+static void fill_gated_res(GatedResArgs& g, void* x, const void* y, const void* post_w, const void* gate, int post_mode, int gate_mode,
+                           const void* next_w, const void* next_scale, const void* next_shift, int next_mode, int ld_mod, void* h, int B, int N,
+                           int d, float eps, float eps_next, int scale_pre, int h_pair, const void* ystat, int ystat_slots, const void* moe_ys,
+                           const void* moe_pos, const void* moe_wts, const void* route_w, int route_E, void* route_sel, void* route_wts,
+                           const void* route_forced) {
+    g.x = (u16*)x; g.y = (const u16*)y; g.post_w = (const u16*)post_w; g.gate = (const u16*)gate;
+    g.next_w = (const u16*)next_w; g.next_scale = (const u16*)next_scale; g.next_shift = (const u16*)next_shift;
+    g.h = (u16*)h; g.rows = B * N; g.rows_per_batch = N; g.d = d; g.ld_mod = ld_mod; g.post_mode = post_mode;
+    g.gate_mode = gate_mode; g.next_mode = next_mode; g.eps = eps; g.eps_next = eps_next; g.scale_pre = scale_pre; g.h_pair = h_pair;
+    g.ystat = (const float*)ystat; g.ystat_slots = ystat_slots;
+    g.moe_ys = (const u16*)moe_ys; g.moe_pos = (const int*)moe_pos; g.moe_wts = (const u16*)moe_wts;
+    g.route_w = (const u16*)route_w; g.route_E = route_E; g.route_sel = (int*)route_sel; g.route_wts = (u16*)route_wts;
+    g.route_forced = (const int*)route_forced;
+}
+
+// ystat: [B * N][ystat_slots] floats, the partial sums of squares of y's rows as a plain input (the streaming kernel without a GEMM in front);
+// moe_*: the combine-on-load; route_*: routing on the way out (GatedResArgs)
+extern "C" int lt_op_gated_residual_norm_ex(void* x, const void* y, const void* post_w, const void* gate, int32_t post_mode, int32_t gate_mode,
+                                            const void* next_w, const void* next_scale, const void* next_shift, int32_t next_mode, int32_t ld_mod,
+                                            void* h, int32_t B, int32_t N, int32_t d, float eps, float eps_next, int32_t scale_pre, int32_t h_pair,
+                                            const void* ystat, int32_t ystat_slots, const void* moe_ys, const void* moe_pos, const void* moe_wts,
+                                            const void* route_w, int32_t route_E, void* route_sel, void* route_wts, const void* route_forced,
+                                            void* stream) {
+    LT_REQUIRE(x && (y || moe_pos), "lt_op_gated_residual_norm_ex: null pointer");
+    GatedResArgs g;
+    fill_gated_res(g, x, y, post_w, gate, post_mode, gate_mode, next_w, next_scale, next_shift, next_mode, ld_mod, h, B, N, d, eps, eps_next, scale_pre,
+                   h_pair, ystat, ystat_slots, moe_ys, moe_pos, moe_wts, route_w, route_E, route_sel, route_wts, route_forced);
+    return launch_gated_residual_norm(g, (hipStream_t)stream);
+}
+
+// has_*: only the nullness of the pointers takes part in the dispatch
+extern "C" int lt_op_gated_residual_norm_describe(int32_t post_mode, int32_t gate_mode, int32_t next_mode, int32_t d, int32_t has_next_w,
+                                                  int32_t has_next_scale, int32_t has_next_shift, int32_t scale_pre, int32_t has_ystat,
+                                                  int32_t ystat_slots, int32_t has_moe, char* out, int32_t cap) {
+    LT_REQUIRE(out && cap > 0, "lt_op_gated_residual_norm_describe: null buffer");
+    const void* some = out;
+    GatedResArgs g;
+    fill_gated_res(g, out, has_moe ? nullptr : some, some, some, post_mode, gate_mode, has_next_w ? some : nullptr, has_next_scale ? some : nullptr,
+                   has_next_shift ? some : nullptr, next_mode, d, out, 1, 1, d, 1e-5f, 1e-6f, scale_pre, 0, has_ystat ? some : nullptr, ystat_slots,
+                   has_moe ? some : nullptr, has_moe ? some : nullptr, has_moe ? some : nullptr, nullptr, 0, nullptr, nullptr, nullptr);
+    snprintf(out, (size_t)cap, "%s", gated_residual_norm_describe(g));
+    return 0;
+}
+
+// launch_qkv_post trusts the engine's arguments; at the op level they get the checks of the single and the pair launcher (qkv_post.hip)
+static int validate_qk_post_abi(const QkPostArgs& a, const char* who) {
+    const int width = a.heads * a.hd;
+    LT_REQUIRE(a.B > 0 && a.N > 0 && a.heads > 0 && a.hd > 0 && a.hd % 8 == 0 && a.hd <= 128 && width <= 4096, "%s: bad shape (%d x %d heads x %d)", who, a.B * a.N, a.heads, a.hd);
+    LT_REQUIRE(a.ld_src % 8 == 0 && a.col0 % 8 == 0 && a.col0 >= 0 && a.col0 + width <= a.ld_src, "%s: ld_src / col0 must be multiples of 8 and hold the columns", who);
+    LT_REQUIRE(a.rope_mode >= 0 && a.rope_mode <= 2 && (a.rope_mode == 0 || a.cs != nullptr), "%s: rotary table missing", who);
+    LT_REQUIRE(a.rope_mode != 1 || (a.hd % 4 == 0 && a.grid_w > 0), "%s: 2-D rope needs hd %% 4 == 0 and grid_w > 0", who);
+    LT_REQUIRE((a.ln_w == nullptr) == (a.ln_b == nullptr), "%s: LayerNorm weight and bias must come together", who);
+    return 0;
+}
+
+static void fill_qk_post(QkPostArgs& q, const void* src, int ld_src, int col0, const void* ln_w, const void* ln_b, float ln_eps, void* dst, int B,
+                         int N, int heads, int hd, int rope_mode, const void* cs_table, int cs_len, const void* t, float watershed, int grid_w,
+                         const void* n_tok_b, const void* grid_w_b, float out_scale) {
+    q.src = (const u16*)src; q.ld_src = ld_src; q.col0 = col0; q.ln_w = (const u16*)ln_w; q.ln_b = (const u16*)ln_b;
+    q.ln_eps = ln_eps; q.dst = (u16*)dst; q.B = B; q.N = N; q.heads = heads; q.hd = hd; q.rope_mode = rope_mode;
+    q.cs = (const float*)cs_table; q.cs_len = cs_len; q.t = (const float*)t; q.watershed = watershed; q.grid_w = grid_w > 0 ? grid_w : 1;
+    q.n_tok_b = (const int*)n_tok_b; q.grid_w_b = (const int*)grid_w_b; q.out_scale = out_scale;
+}
+
+// cs_table: [2][cs_len][hd / 4 (rope_mode 1) | hd / 2 (rope_mode 2)] (cos, sin), branch 0 below the watershed; t: device float (branch 1 when null);
+// n_tok_b / grid_w_b: device int [B] of a packed batch or null; qstat_in: [B * N][qstat_slots] float2 (sum, sum of squares) -> qstat_out [B * N] float2
+extern "C" int lt_op_qk_norm_rope_ex(const void* src, int32_t ld_src, int32_t col0, const void* ln_w, const void* ln_b, float ln_eps, void* dst,
+                                     int32_t B, int32_t N, int32_t heads, int32_t hd, int32_t rope_mode, const void* cs_table, int32_t cs_len,
+                                     const void* t, float watershed, int32_t grid_w, const void* n_tok_b, const void* grid_w_b, float out_scale,
+                                     const void* qstat_in, void* qstat_out, int32_t qstat_slots, int32_t qstat_width, void* stream) {
+    LT_REQUIRE(src && dst, "lt_op_qk_norm_rope_ex: null pointer");
+    QkPostArgs q;
+    fill_qk_post(q, src, ld_src, col0, ln_w, ln_b, ln_eps, dst, B, N, heads, hd, rope_mode, cs_table, cs_len, t, watershed, grid_w, n_tok_b, grid_w_b,
+                 out_scale);
+    q.qstat_in = (const float*)qstat_in; q.qstat_out = (float*)qstat_out; q.qstat_slots = qstat_slots; q.qstat_width = qstat_width;
+    return launch_qk_norm_rope(q, (hipStream_t)stream);
+}
+
+// q and k of one projection output qkv [B * N, ld] (q at q_col0: heads x hd, k at k_col0: kv_heads x hd) in one persistent launch, as the engine
+// calls it at >= 2048 rows
+extern "C" int lt_op_qk_norm_rope_pair(const void* qkv, int32_t ld, int32_t q_col0, int32_t k_col0, const void* q_ln_w, const void* q_ln_b,
+                                       const void* k_ln_w, const void* k_ln_b, float ln_eps, void* q_dst, void* k_dst, int32_t B, int32_t N,
+                                       int32_t heads, int32_t kv_heads, int32_t hd, int32_t rope_mode, const void* cs_table, int32_t cs_len,
+                                       const void* t, float watershed, int32_t grid_w, const void* n_tok_b, const void* grid_w_b, float q_out_scale,
+                                       float k_out_scale, void* stream) {
+    LT_REQUIRE(qkv && q_dst && k_dst, "lt_op_qk_norm_rope_pair: null pointer");
+    QkPostArgs q, k;
+    fill_qk_post(q, qkv, ld, q_col0, q_ln_w, q_ln_b, ln_eps, q_dst, B, N, heads, hd, rope_mode, cs_table, cs_len, t, watershed, grid_w, n_tok_b, grid_w_b,
+                 q_out_scale);
+    fill_qk_post(k, qkv, ld, k_col0, k_ln_w, k_ln_b, ln_eps, k_dst, B, N, kv_heads, hd, rope_mode, cs_table, cs_len, t, watershed, grid_w, n_tok_b,
+                 grid_w_b, k_out_scale);
+    return launch_qk_norm_rope_pair(q, k, (hipStream_t)stream);
+}
+
+// the same plus the V transpose (v at v_col0 -> vt_dst [B, kv_heads, hd, Npad]) in ONE launch, as the engine calls it below 2048 rows
+extern "C" int lt_op_qkv_post(const void* qkv, int32_t ld, int32_t q_col0, int32_t k_col0, int32_t v_col0, const void* q_ln_w, const void* q_ln_b,
+                              const void* k_ln_w, const void* k_ln_b, float ln_eps, void* q_dst, void* k_dst, void* vt_dst, int32_t B, int32_t N,
+                              int32_t Npad, int32_t heads, int32_t kv_heads, int32_t hd, int32_t rope_mode, const void* cs_table, int32_t cs_len,
+                              const void* t, float watershed, int32_t grid_w, const void* n_tok_b, const void* grid_w_b, float q_out_scale,
+                              float k_out_scale, void* stream) {
+    LT_REQUIRE(qkv && q_dst && k_dst && vt_dst, "lt_op_qkv_post: null pointer");
+    QkvPostArgs a;
+    fill_qk_post(a.q, qkv, ld, q_col0, q_ln_w, q_ln_b, ln_eps, q_dst, B, N, heads, hd, rope_mode, cs_table, cs_len, t, watershed, grid_w, n_tok_b,
+                 grid_w_b, q_out_scale);
+    fill_qk_post(a.k, qkv, ld, k_col0, k_ln_w, k_ln_b, ln_eps, k_dst, B, N, kv_heads, hd, rope_mode, cs_table, cs_len, t, watershed, grid_w, n_tok_b,
+                 grid_w_b, k_out_scale);
+    if (int rc = validate_qk_post_abi(a.q, "lt_op_qkv_post (q)")) return rc;
+    if (int rc = validate_qk_post_abi(a.k, "lt_op_qkv_post (k)")) return rc;
+    LT_REQUIRE(ld % 8 == 0 && v_col0 % 8 == 0 && hd % 8 == 0, "lt_op_qkv_post: ld / v_col0 / hd must be multiples of 8");
+    a.v_src = (const u16*)qkv; a.v_dst = (u16*)vt_dst; a.v_ld_src = ld; a.v_col0 = v_col0; a.v_B = B; a.v_N = N; a.v_Npad = Npad;
+    a.v_kv_heads = kv_heads; a.v_hd = hd;
+    return launch_qkv_post(a, (hipStream_t)stream);
 }
 
 extern "C" int lt_op_v_transpose(const void* src, int32_t ld_src, int32_t col0, void* dst, int32_t B, int32_t N,
