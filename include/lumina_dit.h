@@ -46,6 +46,14 @@ extern "C" {
 #define LT_ODE_EULER 0
 #define LT_ODE_MIDPOINT 1
 #define LT_ODE_RK4 2
+/* adaptive Runge-Kutta methods of lt_sample_ode_adaptive, torchdiffeq names */
+#define LT_ODE_DOPRI5 3
+#define LT_ODE_BOSH3 4
+#define LT_ODE_FEHLBERG2 5
+#define LT_ODE_ADAPTIVE_HEUN 6
+/* lt_op_rk_*: most slopes a chain runs over (dopri5: 7), and the bytes of device workspace a norm needs */
+#define LT_RK_MAX_SLOPES 7
+#define LT_RK_WS_BYTES 8192
 /* lt_sample_sde: method, last step, and the length (floats) of one stage record */
 #define LT_SDE_EULER 0
 #define LT_SDE_HEUN 1
@@ -213,7 +221,39 @@ int lt_sample_sde(lt_engine* e, const void* z_dev, const void* noise_dev, void* 
                   int32_t n_steps, int32_t method, int32_t last_step, const float* last_coef_host, int32_t use_cfg, const lt_step_args* a,
                   void* stream);
 
-/* number of model evaluations issued by the last lt_sample_ode / lt_sample_views / lt_sample_sde call */
+/* ---- adaptive ODE sampling: ode.sample with torchdiffeq's dopri5 / bosh3 / fehlberg2 / adaptive_heun (transport/integrators.py: adaptive_odeint) ----
+ * The whole trajectory in one call: stage arithmetic, error estimate, tolerance, norm, dense output and interpolation are fused kernels
+ * (csrc/ode_adaptive.hip, rounding points there), the step-size controller runs on the host in C++.  z [B,C,H,W] in the state dtype
+ * (a->io_dtype); traj_dev receives the n_grid states [n_grid,B,C,H,W], row 0 = z; tgrid_host: the fp32 grid, strictly increasing, at least 2
+ * points.  Steps are the controller's own and may overshoot a grid point: the state there is the quartic dense output of the accepted step
+ * that contains it.  Every model call is forward_with_cfg when use_cfg != 0, else forward; t_round_to_state_dtype as in lt_sample_ode.
+ * Controller: what the host loop holds in 0-dim fp32 tensors is fp32 here (tcur + dt, tcur + fp32(alpha) dt, dt fp32(factor), the
+ * interpolation argument (next_t - tprev) / (tcur - tprev)); what it computes in Python floats is double (factor = min(10, max(0.9 /
+ * ratio^(1 / order), 0.2 or 1)), ratio == 0 -> factor 10).  The error ratio is the fp32 rounding of a float64 tree sum (the host loop reduces
+ * in fp32), so dt may differ from the host loop's by fp32 ulps.
+ * first_step > 0 is the first dt as given (ONE evaluation in front of the first step); first_step == 0 selects it by torchdiffeq's heuristic
+ * (two evaluations, three norms); its (0.01 / max(d1, d2))^(1 / order) is computed in double and rounded to fp32, which may differ by an fp32
+ * ulp from torch's device pow.  lt_last_nfe = (1 or 2) + stages * attempted steps.
+ * stats (may be NULL): evaluation and step counts, the first dt used, and - when dt_host is set - the dt of every attempted step, at most
+ * dt_cap of them (dt_count is the number of attempts, whatever dt_cap).
+ * Refused by name, with no partial result: an unknown method; rtol or atol <= 0 or not finite; first_step < 0 or not finite; max_steps < 1;
+ * n_grid < 2 or a grid that is not strictly increasing; "step size underflow" (tcur + dt == tcur, torchdiffeq's own assertion); more than
+ * max_steps attempted steps inside one grid interval ("max_steps"); an error ratio that is not finite.
+ * UNLIKE lt_sample_ode this call SYNCHRONISES the stream once per attempted step (and up to three times for the initial step): the host
+ * reads the 4-byte error ratio, which adaptive stepping cannot avoid. */
+typedef struct lt_ode_adaptive_stats {
+    int64_t nfe;
+    int32_t accepted, rejected;
+    float   first_step;  /* the first dt: the given one, or the heuristic's */
+    int32_t dt_cap;      /* in: floats dt_host has room for                */
+    int32_t dt_count;    /* out: attempted steps                            */
+    float*  dt_host;     /* in: may be NULL                                 */
+} lt_ode_adaptive_stats;
+int lt_sample_ode_adaptive(lt_engine* e, const void* z_dev, void* traj_dev, const float* tgrid_host, int32_t n_grid, int32_t method, float rtol,
+                           float atol, float first_step, int32_t max_steps, int32_t use_cfg, int32_t t_round_to_state_dtype,
+                           const lt_step_args* a, void* stream, lt_ode_adaptive_stats* stats);
+
+/* number of model evaluations issued by the last lt_sample_ode / lt_sample_views / lt_sample_sde / lt_sample_ode_adaptive call */
 int64_t lt_last_nfe(lt_engine* e);
 /* model evaluations served by replaying a captured HIP graph since lt_create (0 with lt_set_option("graph", 0), and below 1025 rows under the default "graph" 2) */
 int64_t lt_graph_replays(lt_engine* e);

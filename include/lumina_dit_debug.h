@@ -146,6 +146,27 @@ int lt_op_qkv_post(const void* qkv, int32_t ld, int32_t q_col0, int32_t k_col0, 
                    const void* t, float watershed, int32_t grid_w, const void* n_tok_b, const void* grid_w_b, float q_out_scale,
                    float k_out_scale, void* stream);
 
+/* The kernels of lt_sample_ode_adaptive (csrc/ode_adaptive.hip, where the rounding points are written out) on caller-owned buffers of n
+ * elements, any n >= 1; buffers that are not 16-byte aligned take the one-element form.  dtype LT_F32 or LT_BF16 (R: round to dtype).  None reads
+ * engine state.  k_ptrs_host: HOST array of nk <= LT_RK_MAX_SLOPES device pointers (the slopes), coef_host their nk coefficients (the fp32 of
+ * the tableau's doubles); dt is rounded to dtype by the kernel.  ws_dev: LT_RK_WS_BYTES of device memory, 8-byte aligned; norm_dev: one device
+ * float; q_dev (may be NULL) receives the quotients the norm is taken of.
+ *   lt_op_rk_stage       out = R(y + R(dt chain(coef)))
+ *   lt_op_rk_error_norm  q = R(R(dt chain(coef)) / R(atol + R(rtol max(|y|, |y1|)))),  *norm_dev = fp32(sqrt(mean(q^2)))
+ *   lt_op_rk_dense       c1 = R(dt fy) and the dense-output coefficients c, b, a of the step (y, y1, ymid, fy, f1)
+ *   lt_op_rk_interp      the quartic through coef_ptrs_host = { y, c1, c, b, a } (HOST array of 5 device pointers) at x
+ *   lt_op_rms_norm       *norm_dev = fp32(sqrt(mean(q^2))) in float64, a fixed two-level tree: q = x;  with y0: q = R(x / R(atol + R(|y0| rtol)));
+ *                        with sub and y0: q = R(R(x - sub) / scale) */
+int lt_op_rk_stage(const void* y_dev, const void* const* k_ptrs_host, const float* coef_host, int32_t nk, float dt, void* out_dev, int64_t n,
+                   int32_t dtype, void* stream);
+int lt_op_rk_error_norm(const void* y_dev, const void* y1_dev, const void* const* k_ptrs_host, const float* coef_host, int32_t nk, float dt,
+                        float rtol, float atol, void* q_dev, void* ws_dev, float* norm_dev, int64_t n, int32_t dtype, void* stream);
+int lt_op_rk_dense(const void* y_dev, const void* y1_dev, const void* ymid_dev, const void* fy_dev, const void* f1_dev, float dt, void* c1_dev,
+                   void* c_dev, void* b_dev, void* a_dev, int64_t n, int32_t dtype, void* stream);
+int lt_op_rk_interp(const void* const* coef_ptrs_host, float x, void* out_dev, int64_t n, int32_t dtype, void* stream);
+int lt_op_rms_norm(const void* x_dev, const void* sub_dev, const void* y0_dev, float rtol, float atol, void* q_dev, void* ws_dev, float* norm_dev,
+                   int64_t n, int32_t dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

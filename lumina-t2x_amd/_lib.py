@@ -23,6 +23,9 @@ LT_VARIANT_NEXT_T2I, LT_VARIANT_NEXT_IMAGENET, LT_VARIANT_FLAG_T2I, LT_VARIANT_N
 LT_VARIANT_NEXT_MOE_TIME, LT_VARIANT_NEXT_MOE_SPACE = 4, 5
 LT_ODE_EULER, LT_ODE_MIDPOINT, LT_ODE_RK4 = 0, 1, 2
 ODE_METHODS = {"euler": LT_ODE_EULER, "midpoint": LT_ODE_MIDPOINT, "rk4": LT_ODE_RK4}
+LT_ODE_DOPRI5, LT_ODE_BOSH3, LT_ODE_FEHLBERG2, LT_ODE_ADAPTIVE_HEUN = 3, 4, 5, 6
+ODE_ADAPTIVE_METHODS = {"dopri5": LT_ODE_DOPRI5, "bosh3": LT_ODE_BOSH3, "fehlberg2": LT_ODE_FEHLBERG2, "adaptive_heun": LT_ODE_ADAPTIVE_HEUN}
+LT_RK_MAX_SLOPES, LT_RK_WS_BYTES = 7, 8192
 LT_SDE_EULER, LT_SDE_HEUN = 0, 1
 SDE_METHODS = {"Euler": LT_SDE_EULER, "Heun": LT_SDE_HEUN}
 LT_SDE_LAST_NONE, LT_SDE_LAST_MEAN, LT_SDE_LAST_TWEEDIE, LT_SDE_LAST_EULER = 0, 1, 2, 3
@@ -49,6 +52,13 @@ class LtStepArgs(C.Structure):
         ("base_seqlen", C.c_int32), ("proportional_attn", C.c_int32), ("latent_h", C.c_int32),
         ("latent_w", C.c_int32), ("batch", C.c_int32), ("io_dtype", C.c_int32), ("cfg_channels", C.c_int32),
         ("ntk_factor", C.c_float),
+    ]
+
+
+class LtOdeAdaptiveStats(C.Structure):
+    _fields_ = [
+        ("nfe", C.c_int64), ("accepted", C.c_int32), ("rejected", C.c_int32), ("first_step", C.c_float), ("dt_cap", C.c_int32),
+        ("dt_count", C.c_int32), ("dt_host", C.POINTER(C.c_float)),
     ]
 
 
@@ -93,6 +103,8 @@ _SIGNATURES: Dict[str, tuple] = {
     "lt_set_views": (_i32, [_vp, _vp, C.POINTER(_f32), C.POINTER(_f32), _i32, _i32, _i32, _vp]),
     "lt_sample_views": (_i32, [_vp, _vp, _vp, _vp, C.POINTER(_f32), _i32, _i32, C.POINTER(LtStepArgs), _vp]),
     "lt_sample_sde": (_i32, [_vp, _vp, _vp, _vp, _vp, C.POINTER(_f32), _i32, _i32, _i32, C.POINTER(_f32), _i32, C.POINTER(LtStepArgs), _vp]),
+    "lt_sample_ode_adaptive": (_i32, [_vp, _vp, _vp, C.POINTER(_f32), _i32, _i32, _f32, _f32, _f32, _i32, _i32, _i32, C.POINTER(LtStepArgs), _vp,
+                                      C.POINTER(LtOdeAdaptiveStats)]),
     "lt_last_nfe": (_i64, [_vp]),
     "lt_graph_replays": (_i64, [_vp]),
     "lt_moe_routing_record": (_i32, [_vp, _i32]),
@@ -132,6 +144,11 @@ _SIGNATURES: Dict[str, tuple] = {
     "lt_op_views_gather": (_i32, [_vp, _vp, _vp, _vp, _vp, _f32, _i32, _i32, _i32, _i32, _vp]),
     "lt_op_views_reduce": (_i32, [_vp, _vp, _vp, _vp, _vp, _f32, _i32, _i32, _i32, _i32, _vp]),
     "lt_op_sde_step": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_f32), _i64, _i32, _vp]),
+    "lt_op_rk_stage": (_i32, [_vp, C.POINTER(_vp), C.POINTER(_f32), _i32, _f32, _vp, _i64, _i32, _vp]),
+    "lt_op_rk_error_norm": (_i32, [_vp, _vp, C.POINTER(_vp), C.POINTER(_f32), _i32, _f32, _f32, _f32, _vp, _vp, _vp, _i64, _i32, _vp]),
+    "lt_op_rk_dense": (_i32, [_vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _i64, _i32, _vp]),
+    "lt_op_rk_interp": (_i32, [C.POINTER(_vp), _f32, _vp, _i64, _i32, _vp]),
+    "lt_op_rms_norm": (_i32, [_vp, _vp, _vp, _f32, _f32, _vp, _vp, _vp, _i64, _i32, _vp]),
     "lt_op_linear_small_m": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "lt_op_rope_table_2d": (_i32, [_vp, _i32, _i32, _f32, _f32, _vp]),
     "lt_op_rope_table_2d_pair": (_i32, [_vp, _vp, _i32, _i32, _f32, _f32, _vp]),

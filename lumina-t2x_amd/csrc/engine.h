@@ -93,6 +93,30 @@ struct StageTimes {
     }
 };
 
+// What lt_sample_ode_adaptive needs beyond ys / ymid / kbuf, allocated by its first call: three more slopes (dopri5 holds seven), the four
+// dense-output coefficients, the norm's partial sums and result word, and the page-locked word the host reads the error ratio from.
+struct RkWork {
+    void *k[3] = {nullptr, nullptr, nullptr}, *coef[4] = {nullptr, nullptr, nullptr, nullptr}, *ws = nullptr;
+    float *norm_dev = nullptr, *norm_host = nullptr;
+    int reserve(size_t state_bytes) {
+        if (norm_host) return 0;
+        for (auto& p : k) LT_CHECK_HIP(hipMalloc(&p, state_bytes));
+        for (auto& p : coef) LT_CHECK_HIP(hipMalloc(&p, state_bytes));
+        LT_CHECK_HIP(hipMalloc(&ws, LT_RK_WS_BYTES));
+        LT_CHECK_HIP(hipMalloc((void**)&norm_dev, 4 * sizeof(float)));
+        LT_CHECK_HIP(hipHostMalloc((void**)&norm_host, 4 * sizeof(float), hipHostMallocDefault));
+        return 0;
+    }
+    void release() {  // lt_destroy (also after a reserve that failed half way)
+        for (auto& p : k) { if (p) (void)hipFree(p); p = nullptr; }
+        for (auto& p : coef) { if (p) (void)hipFree(p); p = nullptr; }
+        if (ws) (void)hipFree(ws);
+        if (norm_dev) (void)hipFree(norm_dev);
+        if (norm_host) (void)hipHostFree(norm_host);
+        ws = nullptr; norm_dev = nullptr; norm_host = nullptr;
+    }
+};
+
 struct lt_engine {
     lt_config cfg;
     LtEngineOptions opts;  // per-engine option overrides (lt_engine_set_option); LT_OPT_INHERIT slots follow the process defaults
@@ -156,6 +180,7 @@ struct lt_engine {
     // ode
     void *ys[2] = {nullptr, nullptr}, *ymid = nullptr, *kbuf[4] = {nullptr, nullptr, nullptr, nullptr};
     StageTimes times;  // stage times of a whole-trajectory call (samplers.hip)
+    RkWork rk;         // lt_sample_ode_adaptive
     // compositional (regional) text conditioning (lt_prepare_prompt_regional): Y captions, the first Y-1 belong to regions of
     // the cond row, the last to the uncond row; 0 = off
     int reg_Y = 0, reg_h = 1, reg_w = 1;

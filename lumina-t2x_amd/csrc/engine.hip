@@ -1095,6 +1095,7 @@ extern "C" void lt_destroy(lt_engine* e) {
     if (e->cap_stream) (void)hipStreamDestroy(e->cap_stream);
     for (auto& b : e->allocs) (void)hipFree(b.p);
     e->times.release();
+    e->rk.release();
     if (e->pk_dev) (void)hipFree(e->pk_dev);
     if (e->reg_txt) (void)hipFree(e->reg_txt);
     if (e->reg_qmap) (void)hipFree(e->reg_qmap);

@@ -363,6 +363,20 @@ int launch_views_reduce(const void* y, const void* f, const int* iperm, const fl
 // 0 f32, 1 bf16; operands an op does not read may be null.  out is fp32 for LT_SDE_OP_LAST_MEAN / LAST_TWEEDIE, the state dtype otherwise
 int launch_sde_step(int op, const void* x, const void* v, const void* w, const void* k1, const void* xp, void* out, void* out2, const float* rec,
                     long long n, int dtype, hipStream_t stream);
+// adaptive Runge-Kutta stepping (ode_adaptive.hip; rounding points there).  k: host array of nk device pointers (the slopes), coef: the nk
+// coefficients of the chain (host); state dtype 0 f32, 1 bf16; ws: LT_RK_WS_BYTES of device memory for the norm's partial sums; norm_out: one
+// device float; q_out (may be null) receives the quotients the norm is taken of
+int launch_rk_stage(const void* y, const void* const* k, const float* coef, int nk, float dt, void* out, long long n, int dtype,
+                    hipStream_t stream);
+int launch_rk_error_norm(const void* y, const void* y1, const void* const* k, const float* c_err, int nk, float dt, float rtol, float atol,
+                         void* q_out, void* ws, float* norm_out, long long n, int dtype, hipStream_t stream);
+// rms(q): q = x, or x / scale(y0) with y0, or (x - sub) / scale(y0) with sub and y0 (the three norms of the initial-step heuristic)
+int launch_rms_norm(const void* x, const void* sub, const void* y0, float rtol, float atol, void* q_out, void* ws, float* norm_out, long long n,
+                    int dtype, hipStream_t stream);
+int launch_rk_dense(const void* y, const void* y1, const void* ymid, const void* fy, const void* f1, float dt, void* c1, void* c, void* b, void* a,
+                    long long n, int dtype, hipStream_t stream);
+// coeffs: host array of the five device pointers y, c1, c, b, a
+int launch_rk_interp(const void* const* coeffs, float x, void* out, long long n, int dtype, hipStream_t stream);
 // weight upload: cast rows of src [rows, cols] to bf16 at dst rows (row_map 0: r0 + r; 1/2: w1/w3 slots of
 // the 32-row interleaved SwiGLU layout), row stride dst_ld (>= cols; padding left untouched)
 int launch_upload_rows(const void* src, int dtype, u16* dst, int rows, int cols, int dst_ld, int r0, int row_map,

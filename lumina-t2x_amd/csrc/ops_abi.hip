@@ -480,3 +480,26 @@ extern "C" int lt_op_sde_step(int32_t op, const void* x_dev, const void* v_dev, 
                               void* out_dev, void* out2_dev, const float* rec_host, int64_t n, int32_t dtype, void* stream) {
     return launch_sde_step(op, x_dev, v_dev, w_dev, k1_dev, xp_dev, out_dev, out2_dev, rec_host, (long long)n, dtype, (hipStream_t)stream);
 }
+
+// ---- adaptive Runge-Kutta stepping (ode_adaptive.hip) ---------------------------------------------------------------------------------
+extern "C" int lt_op_rk_stage(const void* y_dev, const void* const* k_ptrs_host, const float* coef_host, int32_t nk, float dt, void* out_dev,
+                              int64_t n, int32_t dtype, void* stream) {
+    return launch_rk_stage(y_dev, k_ptrs_host, coef_host, nk, dt, out_dev, (long long)n, dtype, (hipStream_t)stream);
+}
+extern "C" int lt_op_rk_error_norm(const void* y_dev, const void* y1_dev, const void* const* k_ptrs_host, const float* coef_host, int32_t nk,
+                                   float dt, float rtol, float atol, void* q_dev, void* ws_dev, float* norm_dev, int64_t n, int32_t dtype,
+                                   void* stream) {
+    return launch_rk_error_norm(y_dev, y1_dev, k_ptrs_host, coef_host, nk, dt, rtol, atol, q_dev, ws_dev, norm_dev, (long long)n, dtype,
+                                (hipStream_t)stream);
+}
+extern "C" int lt_op_rk_dense(const void* y_dev, const void* y1_dev, const void* ymid_dev, const void* fy_dev, const void* f1_dev, float dt,
+                              void* c1_dev, void* c_dev, void* b_dev, void* a_dev, int64_t n, int32_t dtype, void* stream) {
+    return launch_rk_dense(y_dev, y1_dev, ymid_dev, fy_dev, f1_dev, dt, c1_dev, c_dev, b_dev, a_dev, (long long)n, dtype, (hipStream_t)stream);
+}
+extern "C" int lt_op_rk_interp(const void* const* coef_ptrs_host, float x, void* out_dev, int64_t n, int32_t dtype, void* stream) {
+    return launch_rk_interp(coef_ptrs_host, x, out_dev, (long long)n, dtype, (hipStream_t)stream);
+}
+extern "C" int lt_op_rms_norm(const void* x_dev, const void* sub_dev, const void* y0_dev, float rtol, float atol, void* q_dev, void* ws_dev,
+                              float* norm_dev, int64_t n, int32_t dtype, void* stream) {
+    return launch_rms_norm(x_dev, sub_dev, y0_dev, rtol, atol, q_dev, ws_dev, norm_dev, (long long)n, dtype, (hipStream_t)stream);
+}

@@ -1,5 +1,6 @@
 // Whole-trajectory samplers of the C ABI (include/lumina_dit.h): the fixed-grid ODE loop of transport/integrators.py:104-116 (torchdiffeq
-// euler / midpoint / rk4), multi-view (visual-anagram) sampling and the SDE loop.  One call per trajectory, no host<->device sync inside it.  All three
+// euler / midpoint / rk4), multi-view (visual-anagram) sampling, the SDE loop and the adaptive Runge-Kutta loop.  One call per trajectory, no
+// host<->device sync inside it (the adaptive loop reads one error ratio per attempted step).  All
 // are written against one scaffold - check_step_shape, StageTimes (engine.h), Trajectory - and a new sampler is too: what a sampler
 // owns is its stage-time fill loop and its stepping body, where the reference's rounding points are.
 #include <cmath>
@@ -322,6 +323,203 @@ extern "C" int lt_sample_sde(lt_engine* e, const void* z_dev, const void* noise_
         if (launch_sde_step(op, tr.y0(), e->kbuf[0], nullptr, nullptr, nullptr, final_dev, nullptr, last_coef_host, n, dt_code, s)) return 1;
     }
     return tr.finish(has_last ? nullptr : final_dev);
+}
+
+// ---- adaptive Runge-Kutta sampling (ode_adaptive.hip) ------------------------------------------------------------------------------
+namespace {
+
+// torchdiffeq's tableaus as transport/integrators.py states them (_TABLEAUS): the same double expressions, handed to the kernels as fp32
+struct RkTableau {
+    int stages, order;
+    bool fsal;  // the last stage's state IS the solution (c_sol == the last beta row)
+    double alpha[6], beta[6][6], c_sol[7], c_err[7], c_mid[7];
+};
+const RkTableau kRkTableaus[4] = {
+    {6, 5, true,  // dopri5
+     {1.0 / 5, 3.0 / 10, 4.0 / 5, 8.0 / 9, 1.0, 1.0},
+     {{1.0 / 5},
+      {3.0 / 40, 9.0 / 40},
+      {44.0 / 45, -56.0 / 15, 32.0 / 9},
+      {19372.0 / 6561, -25360.0 / 2187, 64448.0 / 6561, -212.0 / 729},
+      {9017.0 / 3168, -355.0 / 33, 46732.0 / 5247, 49.0 / 176, -5103.0 / 18656},
+      {35.0 / 384, 0.0, 500.0 / 1113, 125.0 / 192, -2187.0 / 6784, 11.0 / 84}},
+     {35.0 / 384, 0.0, 500.0 / 1113, 125.0 / 192, -2187.0 / 6784, 11.0 / 84, 0.0},
+     {35.0 / 384 - 1951.0 / 21600, 0.0, 500.0 / 1113 - 22642.0 / 50085, 125.0 / 192 - 451.0 / 720, -2187.0 / 6784 + 12231.0 / 42400,
+      11.0 / 84 - 649.0 / 6300, -1.0 / 60},
+     {6025192743.0 / 30085553152.0 / 2, 0.0, 51252292925.0 / 65400821598.0 / 2, -2691868925.0 / 45128329728.0 / 2,
+      187940372067.0 / 1594534317056.0 / 2, -1776094331.0 / 19743644256.0 / 2, 11237099.0 / 235043384.0 / 2}},
+    {3, 3, true,  // bosh3
+     {1.0 / 2, 3.0 / 4, 1.0},
+     {{1.0 / 2}, {0.0, 3.0 / 4}, {2.0 / 9, 1.0 / 3, 4.0 / 9}},
+     {2.0 / 9, 1.0 / 3, 4.0 / 9, 0.0},
+     {2.0 / 9 - 7.0 / 24, 1.0 / 3 - 1.0 / 4, 4.0 / 9 - 1.0 / 3, -1.0 / 8},
+     {0.0, 0.5, 0.0, 0.0}},
+    {2, 2, false,  // fehlberg2
+     {1.0 / 2, 1.0},
+     {{1.0 / 2}, {1.0 / 256, 255.0 / 256}},
+     {1.0 / 512, 255.0 / 256, 1.0 / 512},
+     {-1.0 / 512, 0.0, 1.0 / 512},
+     {0.0, 0.5, 0.0}},
+    {1, 2, false,  // adaptive_heun
+     {1.0},
+     {{1.0}},
+     {0.5, 0.5},
+     {0.5, -0.5},
+     {0.5, 0.0}},
+};
+
+void to_f32(const double* c, int n, float* out) { for (int j = 0; j < n; ++j) out[j] = (float)c[j]; }
+
+}  // namespace
+
+extern "C" int lt_sample_ode_adaptive(lt_engine* e, const void* z_dev, void* traj_dev, const float* tgrid_host, int32_t n_grid, int32_t method,
+                                      float rtol, float atol, float first_step, int32_t max_steps, int32_t use_cfg, int32_t t_round,
+                                      const lt_step_args* a, void* stream, lt_ode_adaptive_stats* stats) {
+#pragma clang fp contract(off)
+    LT_REQUIRE(e && z_dev && traj_dev && tgrid_host && a, "lt_sample_ode_adaptive: null argument");
+    LtOptScope opt_scope(&e->opts);
+    LT_REQUIRE(method >= LT_ODE_DOPRI5 && method <= LT_ODE_ADAPTIVE_HEUN, "lt_sample_ode_adaptive: unknown method %d", method);
+    LT_REQUIRE(std::isfinite(rtol) && rtol > 0.f && std::isfinite(atol) && atol > 0.f,
+               "lt_sample_ode_adaptive: rtol %g and atol %g must be finite and positive", (double)rtol, (double)atol);
+    LT_REQUIRE(std::isfinite(first_step) && first_step >= 0.f, "lt_sample_ode_adaptive: first_step %g must be finite and >= 0", (double)first_step);
+    LT_REQUIRE(max_steps >= 1, "lt_sample_ode_adaptive: max_steps %d (need at least 1)", max_steps);
+    LT_REQUIRE(n_grid >= 2, "lt_sample_ode_adaptive: need at least 2 grid points");
+    for (int i = 0; i + 1 < n_grid; ++i)
+        LT_REQUIRE(std::isfinite(tgrid_host[i]) && std::isfinite(tgrid_host[i + 1]) && tgrid_host[i + 1] > tgrid_host[i],
+                   "lt_sample_ode_adaptive: the grid is not strictly increasing at point %d (%g, then %g)", i, (double)tgrid_host[i],
+                   (double)tgrid_host[i + 1]);
+    hipStream_t s = (hipStream_t)stream;
+    const int B = a->batch;
+    if (check_step_shape(e, "lt_sample_ode_adaptive", a)) return 2;
+    const RkTableau& T = kRkTableaus[method - LT_ODE_DOPRI5];
+    const int S = T.stages;
+    const long long n = (long long)B * e->cfg.in_channels * a->latent_h * a->latent_w;
+    const bool bf = a->io_dtype == LT_BF16;
+    const int dtc = bf ? 1 : 0;
+    const size_t sbytes = (size_t)n * (bf ? 2 : 4);
+    if (e->rk.reserve((size_t)e->cfg.max_batch * e->cfg.in_channels * e->cfg.max_tokens * e->cfg.patch_size * e->cfg.patch_size * sizeof(float))) {
+        e->rk.release();
+        return 1;
+    }
+    RkWork& W = e->rk;
+    void* kp[LT_RK_MAX_SLOPES] = {e->kbuf[0], e->kbuf[1], e->kbuf[2], e->kbuf[3], W.k[0], W.k[1], W.k[2]};  // kp[0] = f(tcur, y)
+    float beta[6][LT_RK_MAX_SLOPES], c_sol[LT_RK_MAX_SLOPES], c_err[LT_RK_MAX_SLOPES], c_mid[LT_RK_MAX_SLOPES];
+    for (int i = 0; i < S; ++i) to_f32(T.beta[i], i + 1, beta[i]);
+    to_f32(T.c_sol, S + 1, c_sol);
+    to_f32(T.c_err, S + 1, c_err);
+    to_f32(T.c_mid, S + 1, c_mid);
+
+    Trajectory tr{e, a, use_cfg, s, sbytes};
+    // `count` stage times for the evaluations that follow (the stream is idle: every round below ends with a synchronisation)
+    auto send_times = [&](const float* ts, int count) -> int {
+        float* tp = e->times.begin(count * B, s);
+        if (!tp) return 1;
+        for (int k = 0; k < count; ++k) {
+            const float tv = (t_round && bf) ? bf16_round_host(ts[k]) : ts[k];
+            for (int b = 0; b < B; ++b) tp[(size_t)k * B + b] = tv;
+        }
+        return e->times.commit(count * B, s);
+    };
+    // the host reads `count` norms: the one synchronisation of a round
+    auto read_norms = [&](int count) -> int {
+        LT_CHECK_HIP(hipMemcpyAsync(W.norm_host, W.norm_dev, (size_t)count * sizeof(float), hipMemcpyDeviceToHost, s));
+        LT_CHECK_HIP(hipStreamSynchronize(s));
+        return 0;
+    };
+    auto const_k = [&]() { return (const void* const*)kp; };
+
+    if (tr.start(z_dev, traj_dev, true)) return 1;
+    float tcur = tgrid_host[0], tprev = tcur;
+    if (send_times(&tcur, 1)) return 1;
+    if (tr.eval(tr.y0(), 0, kp[0])) return 1;
+    float dt = first_step;
+    if (!(first_step > 0.f)) {  // torchdiffeq's _select_initial_step (integrators.py:150-162)
+        if (launch_rms_norm(tr.y0(), nullptr, tr.y0(), rtol, atol, nullptr, W.ws, W.norm_dev, n, dtc, s)) return 1;
+        if (launch_rms_norm(kp[0], nullptr, tr.y0(), rtol, atol, nullptr, W.ws, W.norm_dev + 1, n, dtc, s)) return 1;
+        if (read_norms(2)) return 1;
+        const float d0 = W.norm_host[0], d1 = W.norm_host[1];
+        const float h0 = ((double)d0 >= 1e-5 && (double)d1 >= 1e-5) ? (0.01f * d0) / d1 : 1e-6f;
+        const float th = tcur + h0;
+        const float one = 1.f;
+        if (send_times(&th, 1)) return 1;
+        if (launch_rk_stage(tr.y0(), const_k(), &one, 1, h0, e->ymid, n, dtc, s)) return 1;
+        if (tr.eval(e->ymid, 0, kp[1])) return 1;
+        if (launch_rms_norm(kp[1], kp[0], tr.y0(), rtol, atol, nullptr, W.ws, W.norm_dev, n, dtc, s)) return 1;
+        if (read_norms(1)) return 1;
+        const float d2 = W.norm_host[0] / h0;
+        float h1;
+        if ((double)d1 <= 1e-15 && (double)d2 <= 1e-15) {
+            h1 = std::max(1e-6f, h0 * 1e-3f);
+        } else {
+            const float base = (1.f / std::max(d1, d2)) * 0.01f;  // 0.01 / tensor is reciprocal(tensor) * 0.01 in torch
+            h1 = (float)std::pow((double)base, 1.0 / (double)T.order);
+        }
+        dt = std::min(100.f * h0, h1);
+        LT_REQUIRE(std::isfinite(dt) && dt > 0.f, "lt_sample_ode_adaptive: the initial step heuristic gave dt = %g (norms %g, %g, %g): the model "
+                   "output is not finite", (double)dt, (double)d0, (double)d1, (double)d2);
+    }
+    const float dt_first = dt;
+    int accepted = 0, rejected = 0, attempts = 0;
+    const void* cf[5] = {nullptr, W.coef[0], W.coef[1], W.coef[2], W.coef[3]};  // dense output of the last accepted step with a grid point in it
+    for (int gi = 1; gi < n_grid; ++gi) {
+        const float next_t = tgrid_host[gi];
+        int steps = 0;
+        while (next_t > tcur) {
+            LT_REQUIRE(steps < max_steps, "lt_sample_ode_adaptive: max_steps %d exceeded between grid points %d and %d (t = %g, dt = %g)", max_steps,
+                       gi - 1, gi, (double)tcur, (double)dt);
+            ++steps;
+            const float t1 = tcur + dt;
+            LT_REQUIRE(t1 > tcur, "lt_sample_ode_adaptive: step size underflow (t = %g, dt = %g)", (double)tcur, (double)dt);
+            if (stats && stats->dt_host && attempts < stats->dt_cap) stats->dt_host[attempts] = dt;
+            ++attempts;
+            float ts[6];
+            for (int i = 0; i < S; ++i) ts[i] = T.alpha[i] == 1.0 ? t1 : tcur + (float)T.alpha[i] * dt;
+            if (send_times(ts, S)) return 1;
+            void *y = tr.y0(), *y1 = tr.y1();
+            for (int i = 0; i < S; ++i) {
+                void* yi = (T.fsal && i == S - 1) ? y1 : e->ymid;
+                if (launch_rk_stage(y, const_k(), beta[i], i + 1, dt, yi, n, dtc, s)) return 1;
+                if (tr.eval(yi, i, kp[i + 1])) return 1;
+            }
+            if (!T.fsal && launch_rk_stage(y, const_k(), c_sol, S + 1, dt, y1, n, dtc, s)) return 1;
+            if (launch_rk_error_norm(y, y1, const_k(), c_err, S + 1, dt, rtol, atol, nullptr, W.ws, W.norm_dev, n, dtc, s)) return 1;
+            if (read_norms(1)) return 1;
+            const double ratio = (double)W.norm_host[0];
+            LT_REQUIRE(std::isfinite(ratio), "lt_sample_ode_adaptive: the error ratio of the step at t = %g, dt = %g is not finite", (double)tcur,
+                       (double)dt);
+            if (ratio <= 1.0) {
+                if (next_t <= t1) {  // a grid point lies in this step: its dense output (a step without one is never interpolated)
+                    if (launch_rk_stage(y, const_k(), c_mid, S + 1, dt, e->ymid, n, dtc, s)) return 1;
+                    if (launch_rk_dense(y, y1, e->ymid, kp[0], kp[S], dt, W.coef[0], W.coef[1], W.coef[2], W.coef[3], n, dtc, s)) return 1;
+                    cf[0] = y;  // (stays intact until the next attempted step writes its y1 there)
+                }
+                tprev = tcur;
+                tcur = t1;
+                tr.cur ^= 1;
+                std::swap(kp[0], kp[S]);  // like torchdiffeq, the last stage's slope stands in for f(t1, y1) whatever the tableau
+                ++accepted;
+            } else {
+                ++rejected;
+            }
+            // _optimal_step_size(dt, ratio, safety 0.9, ifactor 10, dfactor 0.2, order): the factor in double, dt in fp32
+            double factor = 10.0;
+            if (ratio != 0.0) {
+                const double dfactor = ratio < 1.0 ? 1.0 : 0.2;
+                factor = std::min(10.0, std::max(0.9 / std::pow(ratio, 1.0 / (double)T.order), dfactor));
+            }
+            dt = dt * (float)factor;
+        }
+        const float x = (next_t - tprev) / (tcur - tprev);  // _interp_evaluate
+        if (launch_rk_interp(cf, x, (char*)traj_dev + (size_t)gi * sbytes, n, dtc, s)) return 1;
+    }
+    if (stats) {
+        stats->nfe = tr.nfe;
+        stats->accepted = accepted;
+        stats->rejected = rejected;
+        stats->first_step = dt_first;
+        stats->dt_count = attempts;
+    }
+    return tr.finish(nullptr);
 }
 
 extern "C" int64_t lt_last_nfe(lt_engine* e) { return e ? e->last_nfe : -1; }

@@ -280,6 +280,35 @@ class DiTEngine:
         _lib.check(rc, "lt_sample_ode")
         return out
 
+    def sample_ode_adaptive(self, z: torch.Tensor, tgrid: torch.Tensor, method: str, *, rtol: float, atol: float,
+                            first_step: Optional[float] = None, max_steps: int = 2 ** 31 - 1, use_cfg: bool, cfg_scale: float = 1.0,
+                            scale_factor: float = 1.0, scale_watershed: float = 1.0, base_seqlen: Optional[int] = None,
+                            proportional_attn: bool = False, t_round_to_state_dtype: bool = True, ntk_factor: float = 1.0,
+                            max_recorded_steps: int = 4096):
+        """torchdiffeq's adaptive dopri5 / bosh3 / fehlberg2 / adaptive_heun in ONE call (lt_sample_ode_adaptive): the states at every point
+        of ``tgrid`` ``[len(tgrid), *z.shape]`` and a dict ``nfe, accepted, rejected, first_step, dt`` (``dt``: the step size of every
+        attempted step, the first ``max_recorded_steps`` of them).  ``first_step=None`` selects the first step by torchdiffeq's heuristic.
+        Synchronises the stream once per attempted step (the host reads the error ratio)."""
+        _require_gpu(z, "z")
+        if method not in _lib.ODE_ADAPTIVE_METHODS:
+            raise LuminaLibError(f"adaptive method '{method}' not in {sorted(_lib.ODE_ADAPTIVE_METHODS)}")
+        z = z.contiguous()
+        garr, n = _grid_array(tgrid)
+        a = self._step_args(z, cfg_scale, scale_factor, scale_watershed, base_seqlen, proportional_attn, ntk_factor=ntk_factor)
+        out = torch.empty((max(n, 1),) + tuple(z.shape), dtype=z.dtype, device=z.device)
+        dts = (C.c_float * max_recorded_steps)()
+        st = _lib.LtOdeAdaptiveStats(dt_cap=max_recorded_steps, dt_host=C.cast(dts, C.POINTER(C.c_float)))
+        with torch.cuda.device(self.device):
+            rc = self.lib.lt_sample_ode_adaptive(self.handle, C.c_void_p(z.data_ptr()), C.c_void_p(out.data_ptr()), garr, n,
+                                                 _lib.ODE_ADAPTIVE_METHODS[method], float(rtol), float(atol),
+                                                 0.0 if first_step is None else float(first_step), int(min(max_steps, 2 ** 31 - 1)),
+                                                 int(use_cfg), int(t_round_to_state_dtype), C.byref(a),
+                                                 C.c_void_p(_stream_ptr(self.device)), C.byref(st))
+        _lib.check(rc, "lt_sample_ode_adaptive")
+        stats = dict(nfe=int(st.nfe), accepted=int(st.accepted), rejected=int(st.rejected), first_step=float(st.first_step),
+                     dt=[float(dts[i]) for i in range(min(st.dt_count, max_recorded_steps))])
+        return out, stats
+
     def sample_sde(self, z: torch.Tensor, noise: torch.Tensor, steps: torch.Tensor, last_coef: Optional[torch.Tensor], method: str,
                    last_step: Optional[str], *, use_cfg: bool, cfg_scale: float = 1.0, scale_factor: float = 1.0,
                    scale_watershed: float = 1.0, base_seqlen: Optional[int] = None, proportional_attn: bool = False,

@@ -83,6 +83,12 @@ class EngineSamplers:
         eng, args = self._engine_sampler_args(x, use_cfg, kw)
         return eng.sample_ode(x, tgrid, method, use_cfg=use_cfg, t_round_to_state_dtype=t_round, **args)
 
+    def _engine_sample_ode_adaptive(self, x, tgrid, method, use_cfg, t_round, kw, *, rtol, atol, first_step=None, max_steps=2 ** 31 - 1):
+        """kwargs of forward_with_cfg / forward -> lt_sample_ode_adaptive; returns (states [len(tgrid), *x.shape], stats dict)"""
+        eng, args = self._engine_sampler_args(x, use_cfg, kw)
+        return eng.sample_ode_adaptive(x, tgrid, method, rtol=rtol, atol=atol, first_step=first_step, max_steps=max_steps, use_cfg=use_cfg,
+                                       t_round_to_state_dtype=t_round, **args)
+
     def _engine_sample_sde(self, x, noise, steps, last_coef, method, last_step, use_cfg, kw):
         """kwargs of forward_with_cfg / forward -> lt_sample_sde; returns (engine, loop states [n_steps - 1, *x.shape], last-step state or None)"""
         eng, args = self._engine_sampler_args(x, use_cfg, kw)

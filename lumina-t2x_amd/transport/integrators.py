@@ -11,8 +11,12 @@ not vendored).  Here:
   model-callable protocol (transport.py:192-195), not a fallback of the HIP path;
 * ``dopri5`` (the default ``--solver`` of ``Next-DiT-ImageNet/sample.py:48`` and of ``Sampler.sample_ode``,
   transport.py:349) is torchdiffeq's adaptive Dormand-Prince 5(4) solver, restated below: the step-size controller
-  lives on the host (one scalar device->host read per attempted step is inherent to adaptive stepping), every
-  model evaluation still runs on the engine through the model callable.  PARITY UNPINNED like the fixed-grid
+  lives on the host (one scalar device->host read per attempted step is inherent to adaptive stepping).  With an
+  engine-backed bound method, the plain velocity as drift and a bf16 / fp32 state on the GPU the whole loop is ONE
+  C-ABI call (``lt_sample_ode_adaptive``: fused stage / error / norm / dense-output kernels, the controller in C++);
+  ``solver.use_engine = False`` keeps the host loop below, which every other callable, tuple states and CPU states run anyway.
+  The engine's error norm is a float64 tree sum rounded once to fp32, the host loop's is torch's fp32 reduction: dt may differ by
+  fp32 ulps between the two and the step sequences may drift apart.  PARITY UNPINNED like the fixed-grid
   solvers (torchdiffeq is neither vendored nor installed); anchored on closed-form ODEs in the tests;
 * the other tableau-defined methods ``--solver`` can name (the reference forwards ANY torchdiffeq method string,
   ``lumina_next_t2i/sample.py:77`` -> ``integrators.py:115``): fixed-grid ``heun2`` / ``heun3`` and adaptive ``bosh3`` /
@@ -27,7 +31,7 @@ import torch as th
 
 FIXED_GRID_METHODS = ("euler", "midpoint", "rk4")           # also built inside the engine (lt_sample_ode): one C-ABI call per trajectory
 HOST_FIXED_GRID_METHODS = ("heun2", "heun3")                  # fixed grid, host loop only
-ADAPTIVE_METHODS = ("dopri5", "bosh3", "fehlberg2", "adaptive_heun")
+ADAPTIVE_METHODS = ("dopri5", "bosh3", "fehlberg2", "adaptive_heun")  # also inside the engine (lt_sample_ode_adaptive)
 NOT_BUILT_METHODS = ("dopri8", "explicit_adams", "implicit_adams", "fixed_adams", "scipy_solver")
 ALL_METHODS = FIXED_GRID_METHODS + HOST_FIXED_GRID_METHODS + ADAPTIVE_METHODS
 
@@ -121,7 +125,7 @@ def dopri5_odeint(func, y0, t, **kw):
     return adaptive_odeint(func, y0, t, method="dopri5", **kw)
 
 
-def adaptive_odeint(func, y0, t, *, method="dopri5", rtol=1e-3, atol=1e-6, max_num_steps=2 ** 31 - 1, stats=None, norm=None):
+def adaptive_odeint(func, y0, t, *, method="dopri5", rtol=1e-3, atol=1e-6, max_num_steps=2 ** 31 - 1, stats=None, norm=None, first_step=None):
     """torchdiffeq.odeint(func, y0, t, rtol=rtol, atol=atol, method=...) for the adaptive Runge-Kutta family (rk_common.
     RKAdaptiveStepsizeODESolver): solution at every point of ``t`` (dense output through the quartic fitted to y0, y1, a mid-point
     value and the end slopes), steps chosen by the embedded error estimate.  ``method``: dopri5 (5(4), FSAL), bosh3 (3(2), FSAL),
@@ -130,8 +134,12 @@ def adaptive_odeint(func, y0, t, *, method="dopri5", rtol=1e-3, atol=1e-6, max_n
 
     Follows torchdiffeq's controller: initial step from Hairer's heuristic (``_select_initial_step``), error ratio =
     rms(err / (atol + rtol max(|y0|, |y1|))), accept if <= 1, next step = dt * min(10, max(0.9 ratio^-1/5, 0.2 or 1)).
-    ``stats`` (optional dict) receives the number of function evaluations and accepted / rejected steps; ``norm`` replaces the
-    rms norm of the controller (tuple states use torchdiffeq's mixed norm, see ``tuple_odeint``)."""
+    ``stats`` (optional dict) receives the number of function evaluations, accepted / rejected steps, the first step size and the
+    list of attempted step sizes (``first_step``, ``dt``: Python floats of the fp32 values); ``norm`` replaces the rms norm of the
+    controller (tuple states use torchdiffeq's mixed norm, see ``tuple_odeint``); ``first_step`` (torchdiffeq's option of that name)
+    is used instead of the heuristic when given - the heuristic's second evaluation is then not made.
+
+    With an engine-backed model callable ``ode.sample`` runs this loop inside the engine instead (``lt_sample_ode_adaptive``)."""
     if method not in _TABLEAUS:
         raise _unknown_method(method)
     ALPHA, BETA, C_SOL, C_ERR, C_MID, order = _TABLEAUS[method]
@@ -147,19 +155,23 @@ def adaptive_odeint(func, y0, t, *, method="dopri5", rtol=1e-3, atol=1e-6, max_n
     t0 = t[0]
     f0 = f(t0, y0)
     nfe += 1
-    # _select_initial_step(func, t0, y0, order - 1, ...)
-    scale = atol + y0.abs() * rtol
-    d0, d1 = nrm(y0 / scale), nrm(f0 / scale)
-    h0 = 0.01 * d0 / d1 if (float(d0) >= 1e-5 and float(d1) >= 1e-5) else th.tensor(1e-6, device=y0.device)
-    h0 = h0.to(tdt)
-    f1 = f(t0 + h0, y0 + h0.to(y0.dtype) * f0)
-    nfe += 1
-    d2 = nrm((f1 - f0) / scale) / h0
-    if float(d1) <= 1e-15 and float(d2) <= 1e-15:
-        h1 = th.max(th.tensor(1e-6, dtype=tdt, device=y0.device), h0 * 1e-3)
+    if first_step is not None:
+        dt = th.as_tensor(first_step, dtype=tdt, device=y0.device)
     else:
-        h1 = (0.01 / th.max(d1, d2)) ** (1.0 / float(order))
-    dt = th.min(100 * h0, h1.to(tdt)).to(tdt)
+        # _select_initial_step(func, t0, y0, order - 1, ...)
+        scale = atol + y0.abs() * rtol
+        d0, d1 = nrm(y0 / scale), nrm(f0 / scale)
+        h0 = 0.01 * d0 / d1 if (float(d0) >= 1e-5 and float(d1) >= 1e-5) else th.tensor(1e-6, device=y0.device)
+        h0 = h0.to(tdt)
+        f1 = f(t0 + h0, y0 + h0.to(y0.dtype) * f0)
+        nfe += 1
+        d2 = nrm((f1 - f0) / scale) / h0
+        if float(d1) <= 1e-15 and float(d2) <= 1e-15:
+            h1 = th.max(th.tensor(1e-6, dtype=tdt, device=y0.device), h0 * 1e-3)
+        else:
+            h1 = (0.01 / th.max(d1, d2)) ** (1.0 / float(order))
+        dt = th.min(100 * h0, h1.to(tdt)).to(tdt)
+    dt_first, dts = dt, []
 
     out = th.empty((len(t),) + tuple(y0.shape), dtype=y0.dtype, device=y0.device)
     out[0] = y0
@@ -173,6 +185,8 @@ def adaptive_odeint(func, y0, t, *, method="dopri5", rtol=1e-3, atol=1e-6, max_n
         while float(next_t) > float(tcur):
             assert steps < max_num_steps, "max_num_steps exceeded"
             steps += 1
+            if stats is not None:
+                dts.append(dt)
             t1 = tcur + dt
             dty = dt.to(y.dtype)
             k = [fy]
@@ -231,7 +245,8 @@ def adaptive_odeint(func, y0, t, *, method="dopri5", rtol=1e-3, atol=1e-6, max_n
             total = total + xp * cf
         out[i] = total
     if stats is not None:
-        stats.update(nfe=nfe, accepted=accepted, rejected=rejected)
+        stats.update(nfe=nfe, accepted=accepted, rejected=rejected, first_step=float(dt_first),
+                     dt=th.stack(dts).tolist() if dts else [])
     return out
 
 
@@ -291,6 +306,10 @@ class ode:
         self.sampler_type = sampler_type
         # torchdiffeq >= 0.2 casts t to the state dtype inside its function wrapper; keep switchable
         self.t_round_to_state_dtype = True
+        self.use_engine = True    # adaptive methods: False keeps the host loop (adaptive_odeint) for an engine-backed callable too
+        self.first_step = None    # adaptive methods: torchdiffeq's option of that name (None: the initial-step heuristic)
+        self.max_num_steps = 2 ** 31 - 1
+        self.stats = None         # adaptive methods: nfe / accepted / rejected / first_step / dt of the last sample() call
 
     def sample(self, x, model, **model_kwargs):
         if isinstance(x, tuple):  # the likelihood ODE (reference integrators.py:105-115 with a tuple state)
@@ -304,6 +323,14 @@ class ode:
         if (target is not None and getattr(self.drift, "is_plain_velocity", False) and x.is_cuda
                 and self.sampler_type in FIXED_GRID_METHODS):
             return self._sample_on_engine(x, target, model_kwargs)
+        if (target is not None and getattr(self.drift, "is_plain_velocity", False) and x.is_cuda and self.use_engine
+                and x.dtype in (th.float32, th.bfloat16) and self.sampler_type in ADAPTIVE_METHODS
+                and hasattr(target[0], "_engine_sample_ode_adaptive")):
+            owner, use_cfg = target
+            out, self.stats = owner._engine_sample_ode_adaptive(
+                x, self.t, self.sampler_type, use_cfg, self.t_round_to_state_dtype, dict(model_kwargs), rtol=self.rtol, atol=self.atol,
+                first_step=self.first_step, max_steps=self.max_num_steps)
+            return out
 
         device = x.device
 
@@ -312,7 +339,9 @@ class ode:
             return self.drift(y, tvec, model, **model_kwargs)
 
         if self.sampler_type in ADAPTIVE_METHODS:
-            return adaptive_odeint(_fn, x, self.t.to(device), method=self.sampler_type, rtol=self.rtol, atol=self.atol)
+            self.stats = {}
+            return adaptive_odeint(_fn, x, self.t.to(device), method=self.sampler_type, rtol=self.rtol, atol=self.atol,
+                                   first_step=self.first_step, max_num_steps=self.max_num_steps, stats=self.stats)
         return fixed_grid_odeint(_fn, x, self.t.to(device), method=self.sampler_type)
 
     def _sample_on_engine(self, x, target, kw):
