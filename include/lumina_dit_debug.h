@@ -167,6 +167,39 @@ int lt_op_rk_interp(const void* const* coef_ptrs_host, float x, void* out_dev, i
 int lt_op_rms_norm(const void* x_dev, const void* sub_dev, const void* y0_dev, float rtol, float atol, void* q_dev, void* ws_dev, float* norm_dev,
                    int64_t n, int32_t dtype, void* stream);
 
+/* The boundary kernels of a model evaluation (csrc/misc.hip) and the stand-alone space router (csrc/moe.hip), for tests/test_gpu_misc_exact.py.
+ * Each entry forwards the arguments of its launcher (csrc/kernels.h, where the layouts are described) unchanged, plus the stream.  dtype
+ * arguments: 0 fp32, 1 bf16, 2 fp16 (sources of the casts); the ODE state and the unpatchify output: 0 fp32, 1 bf16.  Pointers are device memory.
+ *   linear_small_m_ext: t, a2, pm_L, pm_chunks, pm_d, pm_final, pm_tanh, pm_scale are the fields of LinearSmallMExtra (NULL / 0 / -1: not used).
+ *   moe_route: x, gate_w, forced (or NULL), rows, rows_per_sample, d, E are the fields of MoeArgs the router reads, sel and wts the ones it writes;
+ *   max_tiles takes part in the launchers' shared shape check only (max_tiles * 256 >= 2 rows + 255 E). */
+int lt_op_patchify(const void* x, int32_t x_dtype, void* out, int32_t B, int32_t C, int32_t H, int32_t W, int32_t patch, int32_t kpad,
+                   int32_t dup_first_half, int32_t wp_stride, void* stream);
+int lt_op_eol_fill(void* x, const void* eol, int32_t rows_total, int32_t Wp, int32_t d, void* stream);
+int lt_op_fill_rows_bf16(void* dst, const void* row, int64_t rows, int32_t d, void* stream);
+int lt_op_label_gather(const void* table, const void* labels, void* out, int32_t B, int32_t rows, int32_t d, void* stream);
+int lt_op_cast_to_bf16(const void* src, int32_t dtype, void* dst, int64_t n, void* stream);
+int lt_op_upload_rows(const void* src, int32_t dtype, void* dst, int32_t rows, int32_t cols, int32_t dst_ld, int32_t r0, int32_t row_map,
+                      void* stream);
+int lt_op_mask_to_bias(const void* mask, void* bias, int32_t B, int32_t T, int32_t Tpad, void* stream);
+int lt_op_add_bf16(const void* a, const void* b, void* c, int64_t n, void* stream);
+int lt_op_timestep_features(const void* t, int32_t t_index, void* out, int32_t B, int32_t dim, void* stream);
+int lt_op_cap_pool_ln(const void* cap, int32_t cap_dtype, const void* mask, const void* ln_w, const void* ln_b, void* out, int32_t B, int32_t T,
+                      int32_t C, void* stream);
+int lt_op_unpatchify_cfg(const void* rows, int32_t ld, void* out, int32_t out_dtype, int32_t B, int32_t C, int32_t out_ch, int32_t H, int32_t W,
+                         int32_t patch, int32_t use_cfg, float cfg_scale, int32_t cfg_channels, int32_t wp_stride, void* stream);
+int lt_op_region_text_combine(void* out, const void* txt, const void* gate, int32_t Y, int32_t N, int32_t H, int32_t hd, int32_t Hp, int32_t Wp,
+                              int32_t h_split, int32_t w_split, void* stream);
+int lt_op_ode_combine(int32_t mode, const void* y0, const void* k1, const void* k2, const void* k3, const void* k4, void* out, int32_t dtype,
+                      float dt, int64_t n, void* stream);
+int lt_op_rope_table(void* out, int32_t len, int32_t hd, int32_t step, float theta0, float lin0, float theta1, float lin1, int32_t lin_on_pos,
+                     void* stream, void* out_t);
+int lt_op_linear_small_m_ext(const void* a, const void* w, const void* b, void* y, int32_t M, int32_t N, int32_t K, int32_t act_in, const void* t,
+                             const void* a2, int32_t pm_L, int32_t pm_chunks, int32_t pm_d, int32_t pm_final, uint32_t pm_tanh, uint32_t pm_scale,
+                             void* stream);
+int lt_op_moe_route(const void* x, const void* gate_w, const void* forced, int32_t rows, int32_t rows_per_sample, int32_t d, int32_t E, void* sel,
+                    void* wts, int32_t max_tiles, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

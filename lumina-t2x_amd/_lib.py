@@ -150,6 +150,22 @@ _SIGNATURES: Dict[str, tuple] = {
     "lt_op_rk_interp": (_i32, [C.POINTER(_vp), _f32, _vp, _i64, _i32, _vp]),
     "lt_op_rms_norm": (_i32, [_vp, _vp, _vp, _f32, _f32, _vp, _vp, _vp, _i64, _i32, _vp]),
     "lt_op_linear_small_m": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
+    "lt_op_patchify": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "lt_op_eol_fill": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp]),
+    "lt_op_fill_rows_bf16": (_i32, [_vp, _vp, _i64, _i32, _vp]),
+    "lt_op_label_gather": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _vp]),
+    "lt_op_cast_to_bf16": (_i32, [_vp, _i32, _vp, _i64, _vp]),
+    "lt_op_upload_rows": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "lt_op_mask_to_bias": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp]),
+    "lt_op_add_bf16": (_i32, [_vp, _vp, _vp, _i64, _vp]),
+    "lt_op_timestep_features": (_i32, [_vp, _i32, _vp, _i32, _i32, _vp]),
+    "lt_op_cap_pool_ln": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
+    "lt_op_unpatchify_cfg": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _i32, _vp]),
+    "lt_op_region_text_combine": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "lt_op_ode_combine": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _f32, _i64, _vp]),
+    "lt_op_rope_table": (_i32, [_vp, _i32, _i32, _i32, _f32, _f32, _f32, _f32, _i32, _vp, _vp]),
+    "lt_op_linear_small_m_ext": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, C.c_uint32, C.c_uint32, _vp]),
+    "lt_op_moe_route": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp]),
     "lt_op_rope_table_2d": (_i32, [_vp, _i32, _i32, _f32, _f32, _vp]),
     "lt_op_rope_table_2d_pair": (_i32, [_vp, _vp, _i32, _i32, _f32, _f32, _vp]),
     "lt_op_proj_gated_residual_norm": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _f32, _i32, _vp]),

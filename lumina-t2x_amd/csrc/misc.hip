@@ -260,6 +260,7 @@ __global__ void mask_to_bias_kernel(const int32_t* mask, float* bias, int B, int
 __global__ void unpatchify_cfg_kernel(const u16* __restrict__ rows, int ld, void* __restrict__ out, int out_dtype, int B,
                                       int C, int out_ch, int H, int W, int patch, int use_cfg, float cfg_scale,
                                       int cfg_channels, int wp_stride) {
+#pragma clang fp contract(off)  // every step of the guidance chain rounds on its own, as the tensor expression does
     const long long total = (long long)B * C * H * W;
     const int Hp = H / patch;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
@@ -293,9 +294,11 @@ __global__ void unpatchify_cfg_kernel(const u16* __restrict__ rows, int ld, void
 //   mode 2: y0 + R(dt R(k2 - R(k1 / 3)))                rk4 stage-3 input
 //   mode 3: y0 + R(dt R(R(k1 - k2) + k3))               rk4 stage-4 input
 //   mode 4: y0 + R(R(R(R(k1 + R(3 R(k2 + k3))) + k4) dt) 0.125)
+// Every product, sum and quotient rounds on its own: no contraction (the fp32 state is torchdiffeq's arithmetic operation by operation).
 template <bool BF>
 __global__ void ode_combine_kernel(int mode, const void* y0, const void* k1, const void* k2, const void* k3,
                                    const void* k4, void* out, float dt, long long n) {
+#pragma clang fp contract(off)  // torch rounds every product before the sum that takes it: no fma (matters at an fp32 state)
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     auto ld = [&](const void* p) { return BF ? bf2f(((const u16*)p)[i]) : ((const float*)p)[i]; };

@@ -503,3 +503,74 @@ extern "C" int lt_op_rms_norm(const void* x_dev, const void* sub_dev, const void
                               float* norm_dev, int64_t n, int32_t dtype, void* stream) {
     return launch_rms_norm(x_dev, sub_dev, y0_dev, rtol, atol, q_dev, ws_dev, norm_dev, (long long)n, dtype, (hipStream_t)stream);
 }
+
+// ---- the boundary kernels of a model evaluation (misc.hip) and the stand-alone space router (moe.hip) for tests/test_gpu_misc_exact.py: every
+// argument of the launcher, unchanged, plus the stream ----------------------------------------------------------------------------------------
+extern "C" int lt_op_patchify(const void* x, int32_t x_dtype, void* out, int32_t B, int32_t C, int32_t H, int32_t W, int32_t patch, int32_t kpad,
+                              int32_t dup_first_half, int32_t wp_stride, void* stream) {
+    return launch_patchify(x, x_dtype, (u16*)out, B, C, H, W, patch, kpad, dup_first_half, wp_stride, (hipStream_t)stream);
+}
+extern "C" int lt_op_eol_fill(void* x, const void* eol, int32_t rows_total, int32_t Wp, int32_t d, void* stream) {
+    return launch_eol_fill((u16*)x, (const u16*)eol, rows_total, Wp, d, (hipStream_t)stream);
+}
+extern "C" int lt_op_fill_rows_bf16(void* dst, const void* row, int64_t rows, int32_t d, void* stream) {
+    return launch_fill_rows_bf16((u16*)dst, (const u16*)row, (long long)rows, d, (hipStream_t)stream);
+}
+extern "C" int lt_op_label_gather(const void* table, const void* labels, void* out, int32_t B, int32_t rows, int32_t d, void* stream) {
+    return launch_label_gather((const u16*)table, (const int32_t*)labels, (u16*)out, B, rows, d, (hipStream_t)stream);
+}
+extern "C" int lt_op_cast_to_bf16(const void* src, int32_t dtype, void* dst, int64_t n, void* stream) {
+    return launch_cast_to_bf16(src, dtype, (u16*)dst, (long long)n, (hipStream_t)stream);
+}
+extern "C" int lt_op_upload_rows(const void* src, int32_t dtype, void* dst, int32_t rows, int32_t cols, int32_t dst_ld, int32_t r0, int32_t row_map,
+                                 void* stream) {
+    return launch_upload_rows(src, dtype, (u16*)dst, rows, cols, dst_ld, r0, row_map, (hipStream_t)stream);
+}
+extern "C" int lt_op_mask_to_bias(const void* mask, void* bias, int32_t B, int32_t T, int32_t Tpad, void* stream) {
+    return launch_mask_to_bias((const int32_t*)mask, (float*)bias, B, T, Tpad, (hipStream_t)stream);
+}
+extern "C" int lt_op_add_bf16(const void* a, const void* b, void* c, int64_t n, void* stream) {
+    return launch_add_bf16((const u16*)a, (const u16*)b, (u16*)c, (long long)n, (hipStream_t)stream);
+}
+extern "C" int lt_op_timestep_features(const void* t, int32_t t_index, void* out, int32_t B, int32_t dim, void* stream) {
+    return launch_timestep_features((const float*)t, t_index, (u16*)out, B, dim, (hipStream_t)stream);
+}
+extern "C" int lt_op_cap_pool_ln(const void* cap, int32_t cap_dtype, const void* mask, const void* ln_w, const void* ln_b, void* out, int32_t B,
+                                 int32_t T, int32_t C, void* stream) {
+    return launch_cap_pool_ln(cap, cap_dtype, (const int32_t*)mask, (const u16*)ln_w, (const u16*)ln_b, (u16*)out, B, T, C, (hipStream_t)stream);
+}
+extern "C" int lt_op_unpatchify_cfg(const void* rows, int32_t ld, void* out, int32_t out_dtype, int32_t B, int32_t C, int32_t out_ch, int32_t H,
+                                    int32_t W, int32_t patch, int32_t use_cfg, float cfg_scale, int32_t cfg_channels, int32_t wp_stride,
+                                    void* stream) {
+    return launch_unpatchify_cfg((const u16*)rows, ld, out, out_dtype, B, C, out_ch, H, W, patch, use_cfg, cfg_scale, cfg_channels, wp_stride,
+                                 (hipStream_t)stream);
+}
+extern "C" int lt_op_region_text_combine(void* out, const void* txt, const void* gate, int32_t Y, int32_t N, int32_t H, int32_t hd, int32_t Hp,
+                                         int32_t Wp, int32_t h_split, int32_t w_split, void* stream) {
+    return launch_region_text_combine((u16*)out, (const u16*)txt, (const u16*)gate, Y, N, H, hd, Hp, Wp, h_split, w_split, (hipStream_t)stream);
+}
+extern "C" int lt_op_ode_combine(int32_t mode, const void* y0, const void* k1, const void* k2, const void* k3, const void* k4, void* out,
+                                 int32_t dtype, float dt, int64_t n, void* stream) {
+    return launch_ode_combine(mode, y0, k1, k2, k3, k4, out, dtype, dt, (long long)n, (hipStream_t)stream);
+}
+extern "C" int lt_op_rope_table(void* out, int32_t len, int32_t hd, int32_t step, float theta0, float lin0, float theta1, float lin1,
+                                int32_t lin_on_pos, void* stream, void* out_t) {
+    return launch_rope_table((float*)out, len, hd, step, theta0, lin0, theta1, lin1, lin_on_pos, (hipStream_t)stream, (float*)out_t);
+}
+extern "C" int lt_op_linear_small_m_ext(const void* a, const void* w, const void* b, void* y, int32_t M, int32_t N, int32_t K, int32_t act_in,
+                                        const void* t, const void* a2, int32_t pm_L, int32_t pm_chunks, int32_t pm_d, int32_t pm_final,
+                                        uint32_t pm_tanh, uint32_t pm_scale, void* stream) {
+    LinearSmallMExtra x;
+    x.t = (const float*)t; x.a2 = (const u16*)a2; x.pm_L = pm_L; x.pm_chunks = pm_chunks; x.pm_d = pm_d; x.pm_final = pm_final;
+    x.pm_tanh = pm_tanh; x.pm_scale = pm_scale;
+    return launch_linear_small_m_ext((const u16*)a, (const u16*)w, (const u16*)b, (u16*)y, M, N, K, act_in, x, (hipStream_t)stream);
+}
+// the fields of MoeArgs the router reads (x, gate_w, forced, rows, d, E; rows_per_sample and max_tiles for the shared shape check) and writes (sel, wts)
+extern "C" int lt_op_moe_route(const void* x, const void* gate_w, const void* forced, int32_t rows, int32_t rows_per_sample, int32_t d, int32_t E,
+                               void* sel, void* wts, int32_t max_tiles, void* stream) {
+    MoeArgs m;
+    m.x = (const u16*)x; m.gate_w = (const u16*)gate_w; m.sample_logits = nullptr; m.forced = (const int*)forced;
+    m.rows = rows; m.rows_per_sample = rows_per_sample; m.d = d; m.E = E;
+    m.sel = (int*)sel; m.wts = (u16*)wts; m.pos = nullptr; m.src = nullptr; m.tile_expert = nullptr; m.max_tiles = max_tiles;
+    return launch_moe_route(m, (hipStream_t)stream);
+}
