@@ -43,6 +43,10 @@ extern "C" {
 #define LT_VARIANT_NEXT_MOE_SPACE 5 /* Next-DiT-MoE/models/models1.py:802 DiT_Llama: ONE MoE FFN per block, routed per token   */
 
 /* fixed-grid ODE methods, torchdiffeq names (lumina_next_t2i/transport/integrators.py:115) */
+/* lt_set_softmax_rule: the self-attention softmax scale under proportional attention */
+#define LT_SOFTMAX_T2I 0     /* sqrt(log(N, base_seqlen) / head_dim)   lumina_next_t2i/models/model.py:374 (default)   */
+#define LT_SOFTMAX_ANAGRAM 1 /* log(N, base_seqlen) / sqrt(head_dim)   visual_anagrams/models/nextdit.py:333           */
+
 #define LT_ODE_EULER 0
 #define LT_ODE_MIDPOINT 1
 #define LT_ODE_RK4 2
@@ -200,6 +204,35 @@ int lt_set_views(lt_engine* e, const int32_t* perm_dev, const float* vsign_host,
 int lt_sample_views(lt_engine* e, const void* z_dev, void* traj_dev, void* final_dev, const float* tgrid_host, int32_t n_grid,
                     int32_t method, const lt_step_args* a, void* stream);
 
+/* ---- multi-view sampling, Phase Upscale: visual_anagrams/generate.py:465-494 with midpoint_solver_extra (:222-262) -------------------------
+ * lt_set_softmax_rule: the model of that phase is visual_anagrams/models/nextdit.py, which differs from LT_VARIANT_NEXT_T2I's model in ONE
+ * scalar: under proportional_attn its self-attention softmax scale is log(N, base_seqlen) / sqrt(head_dim) (LT_SOFTMAX_ANAGRAM) where the T2I
+ * model has sqrt(log(N, base_seqlen) / head_dim) (LT_SOFTMAX_T2I, the default); computed in double, cast once.  Without proportional_attn both
+ * are sqrt(1 / head_dim).  The rule is engine state: it holds for every later evaluation on this engine until it is set again, and is part of
+ * the HIP-graph key.  The fork's RoPE ("ntk_v1", nextdit.py:1014-1018: theta * scale_factor at every timestep) is the NTK branch of the T2I
+ * table: pass scale_watershed = 0 in lt_step_args.  The fork walks the queries in int(N / base_seqlen + 0.99) chunks of base_seqlen rows, each
+ * against all keys: the same result row by row, except where the chunks end before the rows do - under LT_SOFTMAX_ANAGRAM with
+ * proportional_attn a shape with int(N / base_seqlen + 0.99) * base_seqlen < N is refused by name.  Refused too: any variant other than
+ * LT_VARIANT_NEXT_T2I, an unknown rule.
+ * lt_sample_views_guided: z, guidance, noise [1, C, H, W] in a->io_dtype (noise_dev may alias z_dev; none is written).  Prompt layout and view
+ * tables as for lt_sample_views (lt_prepare_prompt at B = 2 V, lt_set_views).  Per interval [t0, t1], with dt = t1 - t0, half_dt = dt / 2 and
+ * R = round to the state dtype, p = perm[v][i]:
+ *   stage at t0:            s = y
+ *   stage at t0 + half_dt:  s[c,p] = R(y[c,p] + isign[v][c] * R(f0[v][c,i] * half_dt))            f0: the first stage's output, per view
+ *   model input of view v:  vsign[v][c] * R(R(k1c * s[c,p]) + R(kc * R(R(ft * guidance[c,p]) + R(f1t * noise[c,p]))))
+ *   closing update:         y' = R(y - R((sum_v inverse_view_v(-R(f1_v * dt))) / V))               as lt_sample_views
+ * Every stage is ONE forward_with_cfg of 2 V rows; lt_last_nfe = 2 per interval.  Stage times are the fp32 of the doubles t0 and t0 + half_dt.
+ * coef_host float [(n_grid - 1)][2 stages][4] = { ft, f1t, kc, k1c } at the stage's time t: ft = fp32(t), f1t = fp32(1 - t) (the reference
+ * multiplies by Python floats), kc = c, k1c = 1 - c with c = 0.5 (1 + cos(pi t)) evaluated in fp32 as the reference does.  Whether c and 1 - c
+ * are rounded to the state dtype before the multiply is the caller's choice (PyTorch's CPU kernels do round such a 0-dim tensor operand,
+ * its GPU kernels are expected to keep it in fp32; transport.integrators.views_guided_table offers both).  Midpoint is the only stepping rule
+ * the reference has for this phase.  No synchronisation, no host read.  Refused by name, with no partial result, in this order: null
+ * arguments; a variant other than LT_VARIANT_NEXT_T2I; n_grid < 2; no view tables; a->batch != 2 V; a latent that differs from the tables';
+ * a batch or token count over the engine's limits; a coefficient that is not finite; (with LT_SOFTMAX_ANAGRAM) a shape the chunks do not cover. */
+int lt_set_softmax_rule(lt_engine* e, int32_t rule);
+int lt_sample_views_guided(lt_engine* e, const void* z_dev, const void* guidance_dev, const void* noise_dev, void* traj_dev, void* final_dev,
+                           const float* tgrid_host, const float* coef_host, int32_t n_grid, const lt_step_args* a, void* stream);
+
 /* ---- SDE sampling: sde.sample + the last step of Sampler.sample_sde (integrators.py:5-76, transport.py:285-344), velocity prediction ---------
  * The whole trajectory in one call, ONE model evaluation per stage: the reference's sde_drift = drift + D * score evaluates the model twice
  * on the same (x, t) (transport.py:172-173); the engine is deterministic, so the fused step kernels read the one output twice.
@@ -253,7 +286,7 @@ int lt_sample_ode_adaptive(lt_engine* e, const void* z_dev, void* traj_dev, cons
                            float atol, float first_step, int32_t max_steps, int32_t use_cfg, int32_t t_round_to_state_dtype,
                            const lt_step_args* a, void* stream, lt_ode_adaptive_stats* stats);
 
-/* number of model evaluations issued by the last lt_sample_ode / lt_sample_views / lt_sample_sde / lt_sample_ode_adaptive call */
+/* number of model evaluations issued by the last lt_sample_ode / lt_sample_views / lt_sample_views_guided / lt_sample_sde / lt_sample_ode_adaptive call */
 int64_t lt_last_nfe(lt_engine* e);
 /* model evaluations served by replaying a captured HIP graph since lt_create (0 with lt_set_option("graph", 0), and below 1025 rows under the default "graph" 2) */
 int64_t lt_graph_replays(lt_engine* e);

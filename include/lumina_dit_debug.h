@@ -200,6 +200,14 @@ int lt_op_linear_small_m_ext(const void* a, const void* w, const void* b, void* 
 int lt_op_moe_route(const void* x, const void* gate_w, const void* forced, int32_t rows, int32_t rows_per_sample, int32_t d, int32_t E, void* sel,
                     void* wts, int32_t max_tiles, void* stream);
 
+
+/* The guided view gather of lt_sample_views_guided (csrc/views.hip, where the chain is written out) on caller-owned buffers: a plain forward of
+ * the launcher's arguments.  y, guidance, noise [C, HW]; perm int32 [V][HW], vsign / isign float [V][C] (DEVICE); f0 [V, C, HW] or NULL (stage 0);
+ * out [V, C, HW]; coef_host = { ft, f1t, kc, k1c } (HOST); HW a multiple of 4; dtype LT_F32 or LT_BF16.  Indices are clamped into [0, HW). */
+int lt_op_views_guided_gather(const void* y_dev, const void* guidance_dev, const void* noise_dev, const int32_t* perm_dev, const float* vsign_dev,
+                              const float* isign_dev, const void* f0_dev, void* out_dev, float half_dt, const float* coef_host, int32_t V,
+                              int32_t C, int32_t HW, int32_t dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

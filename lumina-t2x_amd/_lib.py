@@ -21,6 +21,8 @@ LT_OPTION_INHERIT = -2 ** 31
 LT_F32, LT_BF16, LT_F16 = 0, 1, 2
 LT_VARIANT_NEXT_T2I, LT_VARIANT_NEXT_IMAGENET, LT_VARIANT_FLAG_T2I, LT_VARIANT_NEXT_MOE = 0, 1, 2, 3
 LT_VARIANT_NEXT_MOE_TIME, LT_VARIANT_NEXT_MOE_SPACE = 4, 5
+LT_SOFTMAX_T2I, LT_SOFTMAX_ANAGRAM = 0, 1
+SOFTMAX_RULES = {"t2i": LT_SOFTMAX_T2I, "anagram": LT_SOFTMAX_ANAGRAM}
 LT_ODE_EULER, LT_ODE_MIDPOINT, LT_ODE_RK4 = 0, 1, 2
 ODE_METHODS = {"euler": LT_ODE_EULER, "midpoint": LT_ODE_MIDPOINT, "rk4": LT_ODE_RK4}
 LT_ODE_DOPRI5, LT_ODE_BOSH3, LT_ODE_FEHLBERG2, LT_ODE_ADAPTIVE_HEUN = 3, 4, 5, 6
@@ -102,6 +104,8 @@ _SIGNATURES: Dict[str, tuple] = {
     "lt_sample_ode": (_i32, [_vp, _vp, _vp, _vp, C.POINTER(_f32), _i32, _i32, _i32, _i32, C.POINTER(LtStepArgs), _vp]),
     "lt_set_views": (_i32, [_vp, _vp, C.POINTER(_f32), C.POINTER(_f32), _i32, _i32, _i32, _vp]),
     "lt_sample_views": (_i32, [_vp, _vp, _vp, _vp, C.POINTER(_f32), _i32, _i32, C.POINTER(LtStepArgs), _vp]),
+    "lt_set_softmax_rule": (_i32, [_vp, _i32]),
+    "lt_sample_views_guided": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_f32), C.POINTER(_f32), _i32, C.POINTER(LtStepArgs), _vp]),
     "lt_sample_sde": (_i32, [_vp, _vp, _vp, _vp, _vp, C.POINTER(_f32), _i32, _i32, _i32, C.POINTER(_f32), _i32, C.POINTER(LtStepArgs), _vp]),
     "lt_sample_ode_adaptive": (_i32, [_vp, _vp, _vp, C.POINTER(_f32), _i32, _i32, _f32, _f32, _f32, _i32, _i32, _i32, C.POINTER(LtStepArgs), _vp,
                                       C.POINTER(LtOdeAdaptiveStats)]),
@@ -143,6 +147,7 @@ _SIGNATURES: Dict[str, tuple] = {
     "lt_op_views_invert": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp]),
     "lt_op_views_gather": (_i32, [_vp, _vp, _vp, _vp, _vp, _f32, _i32, _i32, _i32, _i32, _vp]),
     "lt_op_views_reduce": (_i32, [_vp, _vp, _vp, _vp, _vp, _f32, _i32, _i32, _i32, _i32, _vp]),
+    "lt_op_views_guided_gather": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, C.POINTER(_f32), _i32, _i32, _i32, _i32, _vp]),
     "lt_op_sde_step": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_f32), _i64, _i32, _vp]),
     "lt_op_rk_stage": (_i32, [_vp, C.POINTER(_vp), C.POINTER(_f32), _i32, _f32, _vp, _i64, _i32, _vp]),
     "lt_op_rk_error_norm": (_i32, [_vp, _vp, C.POINTER(_vp), C.POINTER(_f32), _i32, _f32, _f32, _f32, _vp, _vp, _vp, _i64, _i32, _vp]),

@@ -177,6 +177,7 @@ struct lt_engine {
     float rope_scale = -1.f, rope_ntk = -1.f;
     int rope_len = 0;
     int prompt_B = 0, prompt_T = 0, prompt_Tpad = 0;
+    int softmax_rule = LT_SOFTMAX_T2I;  // lt_set_softmax_rule: which reference's proportional-attention scale (part of the graph key)
     // ode
     void *ys[2] = {nullptr, nullptr}, *ymid = nullptr, *kbuf[4] = {nullptr, nullptr, nullptr, nullptr};
     StageTimes times;  // stage times of a whole-trajectory call (samplers.hip)
@@ -212,5 +213,8 @@ struct lt_engine {
 
 // one model evaluation [+ CFG combine], through a cached HIP graph where that pays (engine.hip)
 int forward_graphed(lt_engine* e, const void* x_in, const float* t_dev, void* out, const lt_step_args* a, int use_cfg, hipStream_t s);
+// the softmax scale of an evaluation of N tokens under the engine's rule (model.py:373-376, visual_anagrams/models/nextdit.py:331-335), and the
+// refusal of a shape the anagram fork's query chunks do not cover; non-zero after lt_set_error (engine.hip)
+int softmax_scale_for(const lt_engine* e, const lt_step_args* a, int N, float* scale);
 // frees the tables of lt_set_views (samplers.hip)
 void drop_views(lt_engine* e);

@@ -429,13 +429,7 @@ int run_forward(lt_engine* e, const void* x_in, const float* t_dev, void* out, c
 
     if (ensure_rope(e, a, s)) return 1;
     float sm_scale;
-    if (a->proportional_attn && !v.labels) {
-        LT_REQUIRE(a->base_seqlen > 1, "proportional_attn needs base_seqlen");
-        // math.sqrt(math.log(seqlen, base_seqlen) / head_dim)  (model.py:374; seqlen counts the eol tokens for Flag-DiT)
-        sm_scale = (float)std::sqrt(std::log((double)N) / std::log((double)a->base_seqlen) / (double)hd);
-    } else {
-        sm_scale = (float)std::sqrt(1.0 / (double)hd);  // model.py:376; flash_attn_func default (models.py:389)
-    }
+    if (softmax_scale_for(e, a, N, &sm_scale)) return 1;
 
     // patchify + x_embedder (model.py:777-779) [+ eol token per row]
     const int *ntok_dev = nullptr, *gw_dev = nullptr;
@@ -797,6 +791,29 @@ bool profiling_wants_events(const lt_engine* e) {
 
 }  // namespace
 
+int softmax_scale_for(const lt_engine* e, const lt_step_args* a, int N, float* scale) {
+    const int hd = e->hd;
+    if (a->proportional_attn && !e->v.labels) {
+        LT_REQUIRE(a->base_seqlen > 1, "proportional_attn needs base_seqlen");
+        const double lg = std::log((double)N) / std::log((double)a->base_seqlen);
+        if (e->softmax_rule == LT_SOFTMAX_ANAGRAM) {
+            // the fork walks the queries in int(seqlen / base_seqlen + 0.99) chunks of base_seqlen rows (nextdit.py:336-352, :390); every chunk
+            // sees all keys, so a row's result does not depend on the chunking - unless the chunks end before the rows do
+            const long long chunks = (long long)((double)N / (double)a->base_seqlen + 0.99);
+            LT_REQUIRE(chunks * a->base_seqlen >= N, "LT_SOFTMAX_ANAGRAM: %lld query chunks of base_seqlen %d do not cover %d tokens (the reference's "
+                       "chunk loop drops the last %lld query rows at this shape)", chunks, a->base_seqlen, N, (long long)N - chunks * a->base_seqlen);
+            // math.log(seqlen, base_seqlen) / math.sqrt(head_dim)  (nextdit.py:333)
+            *scale = (float)(lg / std::sqrt((double)hd));
+        } else {
+            // math.sqrt(math.log(seqlen, base_seqlen) / head_dim)  (model.py:374; seqlen counts the eol tokens for Flag-DiT)
+            *scale = (float)std::sqrt(lg / (double)hd);
+        }
+    } else {
+        *scale = (float)std::sqrt(1.0 / (double)hd);  // model.py:376; flash_attn_func default (models.py:389)
+    }
+    return 0;
+}
+
 int forward_graphed(lt_engine* e, const void* x_in, const float* t_dev, void* out, const lt_step_args* a, int use_cfg, hipStream_t s) {
     if (!lt_opt(OPT_GRAPH) || profiling_wants_events(e) || e->moe_rec_on || e->moe_force_rows) return run_forward(e, x_in, t_dev, out, a, use_cfg, s);
     const int B = a->batch;
@@ -813,7 +830,9 @@ int forward_graphed(lt_engine* e, const void* x_in, const float* t_dev, void* ou
     const size_t cap_bytes = (size_t)e->cfg.max_batch * e->cfg.in_channels * e->cfg.max_tokens * e->cfg.patch_size * e->cfg.patch_size * 4;
     if (sbytes > cap_bytes) return run_forward(e, x_in, t_dev, out, a, use_cfg, s);
     // (both option generations: the process defaults' and this engine's overrides' - kernel selection is baked into a captured graph)
-    const int extra[9] = {use_cfg, e->prompt_B, e->prompt_T, e->prompt_Tpad, e->reg_Y, e->reg_h, e->reg_w, lt_opt_generation(), lt_opt_engine_generation()};
+    // ... and the softmax rule: the scale it selects is a kernel argument (qa.out_scale / at.scale)
+    const int extra[10] = {use_cfg, e->prompt_B, e->prompt_T, e->prompt_Tpad, e->reg_Y, e->reg_h, e->reg_w, lt_opt_generation(), lt_opt_engine_generation(),
+                           e->softmax_rule};
     std::vector<char> key(sizeof(lt_step_args) + sizeof(extra));
     memcpy(key.data(), a, sizeof(lt_step_args));
     memcpy(key.data() + sizeof(lt_step_args), extra, sizeof(extra));
@@ -1267,6 +1286,16 @@ extern "C" int lt_forward_cfg(lt_engine* e, const void* x_dev, const float* t_de
 }
 
 extern "C" int64_t lt_graph_replays(lt_engine* e) { return e ? e->graph_replays : -1; }
+
+extern "C" int lt_set_softmax_rule(lt_engine* e, int32_t rule) {
+    LT_REQUIRE(e, "lt_set_softmax_rule: null engine");
+    LT_REQUIRE(e->cfg.variant == LT_VARIANT_NEXT_T2I, "lt_set_softmax_rule: the softmax rule belongs to the text-conditional Next-DiT "
+               "(LT_VARIANT_NEXT_T2I) only; this engine is variant %d", e->cfg.variant);
+    LT_REQUIRE(rule == LT_SOFTMAX_T2I || rule == LT_SOFTMAX_ANAGRAM, "lt_set_softmax_rule: unknown softmax rule %d (LT_SOFTMAX_T2I = 0, "
+               "LT_SOFTMAX_ANAGRAM = 1)", rule);
+    e->softmax_rule = rule;
+    return 0;
+}
 
 // ---- MoE routing parity hooks -------------------------------------------------------------------------
 namespace {

@@ -359,6 +359,10 @@ int launch_views_gather(const void* y, const int* perm, const float* vsign, cons
                         int dtype, hipStream_t stream);
 int launch_views_reduce(const void* y, const void* f, const int* iperm, const float* isign, void* out, float dt, int V, int C, int HW, int dtype,
                         hipStream_t stream);
+//   guided gather (Phase Upscale): out [V, C, HW] = view_v(R(R(k1c s) + R(kc R(R(ft G) + R(f1t Z))))), s = y or (f0 != null) the mid-state
+//   R(y + inverse_view_v(R(f0 * half_dt))); guidance / noise [C, HW] like y; coef = { ft, f1t, kc, k1c } on the HOST
+int launch_views_guided_gather(const void* y, const void* guidance, const void* noise, const int* perm, const float* vsign, const float* isign,
+                               const void* f0, void* out, float half_dt, const float* coef, int V, int C, int HW, int dtype, hipStream_t stream);
 // SDE sampling (sde.hip): one fused elementwise step on n elements, op = LT_SDE_OP_*, rec = the stage's 8-float record (host), state dtype
 // 0 f32, 1 bf16; operands an op does not read may be null.  out is fp32 for LT_SDE_OP_LAST_MEAN / LAST_TWEEDIE, the state dtype otherwise
 int launch_sde_step(int op, const void* x, const void* v, const void* w, const void* k1, const void* xp, void* out, void* out2, const float* rec,

@@ -475,6 +475,12 @@ extern "C" int lt_op_views_reduce(const void* y_dev, const void* f_dev, const in
                                   int32_t V, int32_t C, int32_t HW, int32_t dtype, void* stream) {
     return launch_views_reduce(y_dev, f_dev, iperm_dev, isign_dev, out_dev, dt, V, C, HW, dtype, (hipStream_t)stream);
 }
+extern "C" int lt_op_views_guided_gather(const void* y_dev, const void* guidance_dev, const void* noise_dev, const int32_t* perm_dev,
+                                         const float* vsign_dev, const float* isign_dev, const void* f0_dev, void* out_dev, float half_dt,
+                                         const float* coef_host, int32_t V, int32_t C, int32_t HW, int32_t dtype, void* stream) {
+    return launch_views_guided_gather(y_dev, guidance_dev, noise_dev, perm_dev, vsign_dev, isign_dev, f0_dev, out_dev, half_dt, coef_host, V, C, HW, dtype,
+                                      (hipStream_t)stream);
+}
 
 extern "C" int lt_op_sde_step(int32_t op, const void* x_dev, const void* v_dev, const void* w_dev, const void* k1_dev, const void* xp_dev,
                               void* out_dev, void* out2_dev, const float* rec_host, int64_t n, int32_t dtype, void* stream) {

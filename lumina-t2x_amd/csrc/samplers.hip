@@ -257,6 +257,69 @@ extern "C" int lt_sample_views(lt_engine* e, const void* z_dev, void* traj_dev, 
     return tr.finish(final_dev);
 }
 
+// Phase Upscale of the reference (generate.py:465-494): lt_sample_views' loop with midpoint_solver_extra (:222-262) as the stepping rule - the
+// model input of each stage is the guided blend of views.hip, the interval's closing update is the same views_reduce
+extern "C" int lt_sample_views_guided(lt_engine* e, const void* z_dev, const void* guidance_dev, const void* noise_dev, void* traj_dev, void* final_dev,
+                                      const float* tgrid_host, const float* coef_host, int32_t n_grid, const lt_step_args* a, void* stream) {
+    LT_REQUIRE(e && z_dev && guidance_dev && noise_dev && tgrid_host && coef_host && a, "lt_sample_views_guided: null argument");
+    LtOptScope opt_scope(&e->opts);
+    LT_REQUIRE(e->cfg.variant == LT_VARIANT_NEXT_T2I, "lt_sample_views_guided: multi-view sampling drives the text-conditional Next-DiT "
+               "(LT_VARIANT_NEXT_T2I) only; this engine is variant %d", e->cfg.variant);
+    LT_REQUIRE(n_grid >= 2, "lt_sample_views_guided: need at least 2 grid points");
+    LT_REQUIRE(e->vw_V >= 1, "lt_sample_views_guided: no view tables (call lt_set_views first)");
+    const int V = e->vw_V, B = 2 * V, C = e->cfg.in_channels, HW = e->vw_h * e->vw_w;
+    LT_REQUIRE(a->batch == B, "lt_sample_views_guided: %d views need a->batch = 2 V = %d (view prompts + negative prompts), got %d", V, B, a->batch);
+    LT_REQUIRE(a->latent_h == e->vw_h && a->latent_w == e->vw_w, "lt_sample_views_guided: the view tables are for a %dx%d latent, the call has %dx%d",
+               e->vw_h, e->vw_w, a->latent_h, a->latent_w);
+    LT_REQUIRE(a->io_dtype == LT_BF16 || a->io_dtype == LT_F32, "io_dtype must be bf16 or f32");
+    LT_REQUIRE(B <= e->cfg.max_batch, "lt_sample_views_guided: batch %d exceeds max_batch %d", B, e->cfg.max_batch);
+    if (check_latent(e, "lt_sample_views_guided", a->latent_h, a->latent_w)) return 2;
+    const int ncalls = (n_grid - 1) * 2;
+    for (int i = 0; i < ncalls * 4; ++i)
+        LT_REQUIRE(std::isfinite(coef_host[i]), "lt_sample_views_guided: coefficient %d of stage %d (interval %d) is not finite", i % 4, (i / 4) % 2, i / 8);
+    LT_REQUIRE(e->reg_Y == 0 && e->prompt_B == B, "lt_prepare_prompt was called for batch %d, step has batch %d (multi-view sampling needs the V view "
+               "prompts followed by V rows of the negative prompt)", e->prompt_B, B);
+    {  // the model's own refusal of this shape, before anything is copied (no partial result)
+        const int p = e->cfg.patch_size;
+        float unused;
+        if (softmax_scale_for(e, a, (a->latent_h / p) * (a->latent_w / p), &unused)) return 1;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const bool bf = a->io_dtype == LT_BF16;
+    float* tp = e->times.begin(ncalls * B, s);
+    if (!tp) return 1;
+    // generate.py:232-237, :253: t0, t1 are Python floats (the fp32 grid's values as doubles); dt, half_dt and t_mid = t0 + half_dt are doubles;
+    // dt / half_dt multiply a tensor as fp32 scalars, the stage times are torch.full((2,), t0) and torch.full((2,), t_mid): fp32 of the double
+    std::vector<float> dts(n_grid - 1), hdts(n_grid - 1);
+    for (int i = 0; i + 1 < n_grid; ++i) {
+        const double t0 = tgrid_host[i], dt = (double)tgrid_host[i + 1] - t0, half_dt = 0.5 * dt;
+        dts[i] = (float)dt;
+        hdts[i] = (float)half_dt;
+        const float ts[2] = {(float)t0, (float)(t0 + half_dt)};
+        for (int k = 0; k < 2; ++k)
+            for (int b = 0; b < B; ++b) tp[((size_t)i * 2 + k) * B + b] = ts[k];
+    }
+    if (e->times.commit(ncalls * B, s)) return 1;
+    Trajectory tr{e, a, 1, s, (size_t)C * HW * (bf ? 2 : 4)};
+    if (tr.start(z_dev, traj_dev, true)) return 1;
+    const int dt_code = bf ? 1 : 0;
+    for (int i = 0; i + 1 < n_grid; ++i) {
+        void *y0 = tr.y0(), *y1 = tr.y1();
+        const int c0 = i * 2;
+        const float* coef = coef_host + (size_t)i * 8;
+        if (launch_views_guided_gather(y0, guidance_dev, noise_dev, e->vw_perm, e->vw_vsign, e->vw_isign, nullptr, e->ymid, 0.f, coef, V, C, HW, dt_code, s))
+            return 1;
+        if (tr.eval(e->ymid, c0, e->kbuf[0])) return 1;
+        if (launch_views_guided_gather(y0, guidance_dev, noise_dev, e->vw_perm, e->vw_vsign, e->vw_isign, e->kbuf[0], e->ymid, hdts[i], coef + 4, V, C, HW,
+                                       dt_code, s))
+            return 1;
+        if (tr.eval(e->ymid, c0 + 1, e->kbuf[1])) return 1;
+        if (launch_views_reduce(y0, e->kbuf[1], e->vw_iperm, e->vw_isign, y1, dts[i], V, C, HW, dt_code, s)) return 1;
+        if (tr.advance(i + 1)) return 1;
+    }
+    return tr.finish(final_dev);
+}
+
 // ---- SDE sampling (sde.hip) --------------------------------------------------------------------------------------------------------
 extern "C" int lt_sample_sde(lt_engine* e, const void* z_dev, const void* noise_dev, void* traj_dev, void* final_dev, const float* steps_host,
                              int32_t n_steps, int32_t method, int32_t last_step, const float* last_coef_host, int32_t use_cfg,

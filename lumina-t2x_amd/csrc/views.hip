@@ -18,6 +18,17 @@
 //   reduce:          n_v = inverse_view_v(-R(f * dt))                              (generate.py:219, :402, :407)
 //                    y'  = R(y - R((n_0 + n_1 + ... + n_{V-1}) / V))               (generate.py:410-414; fp32 sum in view order, ONE division)
 // Negation, sign and permutation are exact.
+//
+// Phase Upscale (generate.py:465-494, midpoint_solver_extra :222-262): the model input of a stage is a time-dependent blend of the state, the
+// guidance latent G and the initial noise Z, formed in the UN-VIEWED frame and viewed per view - views_guided_gather_kernel, with p = perm[v][i]:
+//   stage 0:  s = y[c,p]                                                           (y0, :241)
+//   stage 1:  s = R(y[c,p] + isign[v][c] * R(f0[v][c,i] * half_dt))                (:247-250: y_mid = y0 - inverse_view_v(-f0 * half_dt), read at p:
+//                                                                                   iperm[v][p] = i, so f0 is read where it is written; the two negations are exact)
+//   g = R(R(ft * G[c,p]) + R(f1t * Z[c,p]))                                        (:240 / :256; the anchor is all ones, the division exact)
+//   m = R(R(k1c * s) + R(kc * g))                                                  (:241 / :257)
+//   out[v][c,i] = vsign[v][c] * m                                                  (:242 / :258)
+// ft = fp32(t), f1t = fp32(1 - t), kc = c, k1c = 1 - c are DATA (the host computes them with the reference's own expressions and decides whether
+// c is rounded to the state dtype first: lumina_dit.h).  Every product and sum is one fp32 operation.  The interval's closing update is views_reduce.
 #include "common.h"
 #include "kernels.h"
 
@@ -128,6 +139,50 @@ __global__ void views_reduce_kernel(const void* __restrict__ y, const void* __re
     st4<BF>(out, o, yv);
 }
 
+// out[v][c][i] = vsign[v][c] * R(R(k1c * s) + R(kc * R(R(ft * G[c][p]) + R(f1t * Z[c][p])))),  p = perm[v][i],
+// s = y[c][p]  (f0 == nullptr)   or   R(y[c][p] + isign[v][c] * R(f0[v][c][i] * half_dt))
+template <bool BF>
+__global__ void views_guided_gather_kernel(const void* __restrict__ y, const void* __restrict__ G, const void* __restrict__ Z,
+                                           const int* __restrict__ perm, const float* __restrict__ vsign, const float* __restrict__ isign,
+                                           const void* __restrict__ f0, void* __restrict__ out, float half_dt, float ft, float f1t, float kc,
+                                           float k1c, int V, int C, int HW) {
+#pragma clang fp contract(off)  // every product rounds before its sum, as the tensor expressions do: no fma (matters at an fp32 state)
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const int q = HW / 4;
+    if (t >= (long long)V * C * q) return;
+    const int i = (int)(t % q) * 4;
+    const int c = (int)((t / q) % C), v = (int)(t / ((long long)q * C));
+    const int4 p = *(const int4*)(perm + (long long)v * HW + i);
+    const int pj[4] = {inb(p.x, HW), inb(p.y, HW), inb(p.z, HW), inb(p.w, HW)};
+    const float sg = vsign[v * C + c];
+    const long long row = (long long)c * HW;
+    const long long o = ((long long)v * C + c) * HW + i;
+    float s[4], k[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) s[j] = ld1<BF>(y, row + pj[j]);
+    if (f0) {
+        const float isg = isign[v * C + c];
+        ld4<BF>(f0, o, k);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float h = k[j] * half_dt;
+            const float ym = s[j] + isg * (BF ? bfr(h) : h);
+            s[j] = BF ? bfr(ym) : ym;
+        }
+    }
+    float m[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const float a = ft * ld1<BF>(G, row + pj[j]), b = f1t * ld1<BF>(Z, row + pj[j]);
+        const float gsum = BF ? bfr(a) + bfr(b) : a + b;
+        const float g = BF ? bfr(gsum) : gsum;
+        const float ms = k1c * s[j], mg = kc * g;
+        const float msum = BF ? bfr(ms) + bfr(mg) : ms + mg;
+        m[j] = sg * (BF ? bfr(msum) : msum);
+    }
+    st4<BF>(out, o, m);
+}
+
 inline int nblk(long long n, int bs) { return (int)((n + bs - 1) / bs); }
 
 int check_shape(const char* who, int V, int C, int HW) {
@@ -167,6 +222,22 @@ int launch_views_reduce(const void* y, const void* f, const int* iperm, const fl
     const long long n = (long long)C * (HW / 4);
     if (dtype == 1) hipLaunchKernelGGL(views_reduce_kernel<true>, dim3(nblk(n, 256)), dim3(256), 0, stream, y, f, iperm, isign, out, dt, V, C, HW);
     else hipLaunchKernelGGL(views_reduce_kernel<false>, dim3(nblk(n, 256)), dim3(256), 0, stream, y, f, iperm, isign, out, dt, V, C, HW);
+    LT_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+int launch_views_guided_gather(const void* y, const void* guidance, const void* noise, const int* perm, const float* vsign, const float* isign,
+                               const void* f0, void* out, float half_dt, const float* coef, int V, int C, int HW, int dtype, hipStream_t stream) {
+    LT_REQUIRE(y && guidance && noise && perm && vsign && isign && out && coef, "views_guided_gather: null argument");
+    LT_REQUIRE(dtype == 0 || dtype == 1, "views_guided_gather: state dtype must be f32 or bf16");
+    if (check_shape("views_guided_gather", V, C, HW)) return 1;
+    const long long n = (long long)V * C * (HW / 4);
+    if (dtype == 1)
+        hipLaunchKernelGGL(views_guided_gather_kernel<true>, dim3(nblk(n, 256)), dim3(256), 0, stream, y, guidance, noise, perm, vsign, isign, f0, out,
+                           half_dt, coef[0], coef[1], coef[2], coef[3], V, C, HW);
+    else
+        hipLaunchKernelGGL(views_guided_gather_kernel<false>, dim3(nblk(n, 256)), dim3(256), 0, stream, y, guidance, noise, perm, vsign, isign, f0, out,
+                           half_dt, coef[0], coef[1], coef[2], coef[3], V, C, HW);
     LT_CHECK_HIP(hipGetLastError());
     return 0;
 }

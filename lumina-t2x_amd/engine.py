@@ -409,6 +409,50 @@ class DiTEngine:
         _lib.check(rc, "lt_sample_views")
         return out
 
+    def set_softmax_rule(self, rule) -> None:
+        """which reference's proportional-attention softmax scale this engine evaluates from now on (``lt_set_softmax_rule``): ``"t2i"`` /
+        ``LT_SOFTMAX_T2I`` (default) or ``"anagram"`` / ``LT_SOFTMAX_ANAGRAM``, the rule of visual_anagrams/models/nextdit.py:333"""
+        code = _lib.SOFTMAX_RULES.get(rule, rule) if isinstance(rule, str) else rule
+        if isinstance(code, str):
+            raise LuminaLibError(f"softmax rule '{rule}' not in {sorted(_lib.SOFTMAX_RULES)}")
+        _lib.check(self.lib.lt_set_softmax_rule(self.handle, int(code)), "lt_set_softmax_rule")
+        self.softmax_rule = int(code)
+
+    def sample_views_guided(self, z: torch.Tensor, guidance: torch.Tensor, tgrid, coef: torch.Tensor, *, noise: Optional[torch.Tensor] = None,
+                            cfg_scale: float = 1.0, scale_factor: float = 1.0, scale_watershed: float = 0.0, base_seqlen: Optional[int] = None,
+                            proportional_attn: bool = False, return_trajectory: bool = True) -> torch.Tensor:
+        """Phase Upscale of the reference's visual_anagrams/generate.py:465-494 in ONE call (``lt_sample_views_guided``): ``z``, ``guidance`` and
+        ``noise`` (default: ``z``) are ``[1, C, H, W]`` in one dtype; ``coef`` is the fp32 CPU table ``[len(tgrid) - 1, 2, 4]`` of
+        ``transport.integrators.views_guided_table``.  Needs ``set_views`` and a prompt prepared at B = 2 V, as ``sample_views``; the softmax
+        rule is whatever ``set_softmax_rule`` left on the engine.  Returns ``[n_grid, C, H, W]`` (or the last latent ``[1, C, H, W]``)."""
+        _require_gpu(z, "z")
+        _require_gpu(guidance, "guidance")
+        noise = z if noise is None else noise
+        _require_gpu(noise, "noise")
+        if z.dim() != 4 or z.shape[0] != 1:
+            raise LuminaLibError(f"sample_views_guided takes ONE latent [1, C, H, W], got {tuple(z.shape)}")
+        for name, t in (("guidance", guidance), ("noise", noise)):
+            if tuple(t.shape) != tuple(z.shape) or t.dtype != z.dtype or t.device != z.device:
+                raise LuminaLibError(f"sample_views_guided: {name} must be {tuple(z.shape)} {z.dtype} on {z.device}, got {tuple(t.shape)} {t.dtype} "
+                                     f"on {t.device}")
+        key = getattr(self, "_views_key", None)
+        if key is None:
+            raise LuminaLibError("sample_views_guided: no views uploaded (call set_views first)")
+        z, guidance, noise = z.contiguous(), guidance.contiguous(), noise.contiguous()
+        garr, n = _grid_array(tgrid)
+        coef = coef.detach().to("cpu", torch.float32).contiguous()
+        if tuple(coef.shape) != (max(n - 1, 0), 2, 4):
+            raise LuminaLibError(f"sample_views_guided: coef must be [{max(n - 1, 0)}, 2, 4] (intervals, stages, ft f1t kc k1c), got {tuple(coef.shape)}")
+        a = self._step_args(z, cfg_scale, scale_factor, scale_watershed, base_seqlen, proportional_attn)
+        a.batch = 2 * key[0]
+        out, traj_ptr, fin_ptr = _traj_or_final(z, n, z.shape[1:], return_trajectory)
+        with torch.cuda.device(self.device):
+            rc = self.lib.lt_sample_views_guided(self.handle, C.c_void_p(z.data_ptr()), C.c_void_p(guidance.data_ptr()), C.c_void_p(noise.data_ptr()),
+                                                 traj_ptr, fin_ptr, garr, C.cast(coef.data_ptr(), C.POINTER(C.c_float)), n, C.byref(a),
+                                                 C.c_void_p(_stream_ptr(self.device)))
+        _lib.check(rc, "lt_sample_views_guided")
+        return out
+
     def last_nfe(self) -> int:
         return int(self.lib.lt_last_nfe(self.handle))
 
@@ -468,8 +512,16 @@ def ffn_hidden_dim(dim: int, multiple_of: int, ffn_dim_multiplier: Optional[floa
     return multiple_of * ((hidden + multiple_of - 1) // multiple_of)
 
 
-def softmax_scale(seqlen: int, head_dim: int, proportional_attn: bool, base_seqlen: Optional[int]) -> float:
-    """model.py:373-376"""
+def softmax_scale(seqlen: int, head_dim: int, proportional_attn: bool, base_seqlen: Optional[int], rule: int = _lib.LT_SOFTMAX_T2I) -> float:
+    """model.py:373-376; ``rule=LT_SOFTMAX_ANAGRAM``: visual_anagrams/models/nextdit.py:331-335"""
     if proportional_attn:
+        if rule == _lib.LT_SOFTMAX_ANAGRAM:
+            return math.log(seqlen, base_seqlen) / math.sqrt(head_dim)
         return math.sqrt(math.log(seqlen, base_seqlen) / head_dim)
     return math.sqrt(1 / head_dim)
+
+
+def anagram_chunks_cover(seqlen: int, base_seqlen: int) -> bool:
+    """visual_anagrams/models/nextdit.py:336-352: the fork walks the queries in ``int(seqlen / base_seqlen + 0.99)`` chunks of ``base_seqlen``
+    rows; False where they end before the rows do (the engine refuses such a shape under LT_SOFTMAX_ANAGRAM)"""
+    return int(seqlen / base_seqlen + 0.99) * base_seqlen >= seqlen

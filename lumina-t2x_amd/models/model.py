@@ -242,7 +242,7 @@ class NextDiT(EngineSamplers, WeightWatch, nn.Module):
         """Multi-view (visual-anagram) sampling, Phase Init of the reference's visual_anagrams/generate.py:389-414, on the engine: ONE latent
         ``z [1, C, H, W]``, V ``views`` (``lumina_t2x_amd.views``), ``cap_feats [2V, T, D]`` / ``cap_mask [2V, T]`` with rows 0..V-1 the view
         prompts and rows V..2V-1 the negative prompt.  Every stage of every interval is one forward_with_cfg of 2 V rows.  Phase Init
-        passes ``cfg_scale`` only (scale_factor 1, no proportional attention); Phase Upscale is not implemented."""
+        passes ``cfg_scale`` only (scale_factor 1, no proportional attention); Phase Upscale is ``sample_views_guided``."""
         V = len(views)
         if cap_feats.shape[0] != 2 * V:
             raise _lib.LuminaLibError(f"sample_views: {V} views need 2 V = {2 * V} prompt rows (view prompts, then the negative prompt per "
@@ -254,6 +254,40 @@ class NextDiT(EngineSamplers, WeightWatch, nn.Module):
         eng.prepare_prompt(cap_feats, cap_mask)
         eng.set_views(views, z.shape[2], z.shape[3])
         return eng.sample_views(z, tgrid, method, cfg_scale=cfg_scale, return_trajectory=return_trajectory)
+
+    @torch.no_grad()
+    def sample_views_guided(self, z, guidance, tgrid, views, cap_feats, cap_mask, *, noise=None, cfg_scale: float = 4.0,
+                            scale_factor: float = 1.0, scale_watershed=None, base_seqlen: Optional[int] = None, proportional_attn: bool = False,
+                            coef_rounding: str = "fp32", return_trajectory: bool = True):
+        """Phase Upscale of the reference's visual_anagrams/generate.py:465-494 on the engine, all V views of a stage in one forward_with_cfg of
+        2 V rows and the whole phase in ONE call: the stepping rule is ``midpoint_solver_extra`` (:222-262), whose model input blends the state
+        with the ``guidance`` latent and the initial ``noise`` (default: ``z``).  Prompt layout as ``sample_views``.  The model is the anagram
+        fork's (visual_anagrams/models/nextdit.py): its softmax rule and its ``ntk_v1`` RoPE (``scale_watershed = 0``) are set for this call and
+        restored afterwards; a caller's ``scale_watershed`` is ignored, as the fork ignores it.  ``coef_rounding``: ``"fp32"`` (default) keeps
+        the decay factor ``c`` in fp32 when it multiplies the state - the expected behaviour of the reference's GPU run, not verified on one;
+        ``"state"`` rounds it to the state dtype first, which is what the reference's CPU bf16 run does (``views_guided_table``)."""
+        from ..transport.integrators import views_guided_table
+        V = len(views)
+        if cap_feats.shape[0] != 2 * V:
+            raise _lib.LuminaLibError(f"sample_views_guided: {V} views need 2 V = {2 * V} prompt rows (view prompts, then the negative prompt per "
+                                      f"view), got {cap_feats.shape[0]}")
+        if proportional_attn:
+            assert base_seqlen is not None
+        for layer in self.layers:  # mirrored attributes (nextdit.py:889-897)
+            layer.attention.base_seqlen = base_seqlen if proportional_attn else None
+            layer.attention.proportional_attn = proportional_attn
+        coef = views_guided_table(tgrid, z.dtype, coef_rounding)
+        eng = self.engine(z.expand(2 * V, -1, -1, -1), cap_feats.shape[1])
+        eng.prepare_prompt(cap_feats, cap_mask)
+        eng.set_views(views, z.shape[2], z.shape[3])
+        before = getattr(eng, "softmax_rule", _lib.LT_SOFTMAX_T2I)
+        eng.set_softmax_rule(_lib.LT_SOFTMAX_ANAGRAM)
+        try:
+            return eng.sample_views_guided(z, guidance, tgrid, coef, noise=noise, cfg_scale=cfg_scale, scale_factor=scale_factor,
+                                           scale_watershed=0.0, base_seqlen=base_seqlen, proportional_attn=proportional_attn,
+                                           return_trajectory=return_trajectory)
+        finally:
+            eng.set_softmax_rule(before)
 
     def parameter_count(self) -> int:
         return sum(p.numel() for p in self.parameters())

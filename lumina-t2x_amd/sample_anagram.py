@@ -1,4 +1,5 @@
-"""Multi-view (visual-anagram) illusions on the MI355X engine: Phase Init of the reference's ``visual_anagrams/generate.py`` (:341-418).
+"""Multi-view (visual-anagram) illusions on the MI355X engine: Phase Init of the reference's ``visual_anagrams/generate.py`` (:341-418) and,
+with ``--upscale``, its Phase Upscale (:416-498).
 
     prompt_j (style + description), negative prompt --[text encoder, hidden_states[-2]]--> rows j and V + j of cap_feats [2V, T, D]
     z ~ N(0, I) [1, 4, w/8, h/8] --[NextDiT.sample_views: ONE lt_sample_views call, every stage one forward_with_cfg of 2 V rows]--> latent
@@ -9,9 +10,16 @@ Argument names follow the reference (``--prompts --views --view_args --style --n
 injected (``run(args, encode_fn=..., decode_fn=..., model=...)``) exactly as ``sample.py`` allows; without a VAE the latent is written as
 ``latent_<size>.pt`` and no image.  The latent is always written.
 
-Not built, and refused by name: Phase Upscale of generate.py (:437-494, ``--upscale``) - it needs the tiled VAE and switches on
-proportional attention / time-aware scaling, where the anagram fork of the model is a different function from every model the engine
-implements; animation (animate.py); views that are not pixel permutations (``lumina_t2x_amd.views``).
+``--upscale`` continues as generate.py:416-498 does:
+    latent --[VAE decoder]--> image --[bicubic F.interpolate to (h, w), fp32]--> --[VAE encoder]--> guidance latent [1, 4, h/8, w/8]
+    z' ~ N(0, I) like it --[NextDiT.sample_views_guided: ONE lt_sample_views_guided call, the anagram fork's attention rule]--> latent
+    --[VAE decoder]--> upscaled_<size>.png, upscaled_<size>.views.png, upscaled_latent_<size>.pt
+with ``--proportional_attn``, ``--scaling_method`` and ``--scaling_watershed`` read as generate.py:420-435 reads them (the fork's model ignores
+the watershed).  The VAE stays third-party here as everywhere in this project: the codec encodes and decodes the WHOLE image - the reference's
+tiled passes (``tiled_encode`` / ``tiled_decode``, generate.py:60-173) are not rebuilt.  Phase Upscale needs a VAE encoder (``--vae`` with
+diffusers, or ``vae_encode_fn``); without one ``--upscale`` is refused by name.
+
+Not built, and refused by name: animation (animate.py); views that are not pixel permutations (``lumina_t2x_amd.views``).
 
     python -m lumina_t2x_amd.sample_anagram --name duck_rabbit --ckpt /ckpts/Lumina-Next-SFT --text_encoder /ckpts/gemma-2b \\
         --vae /ckpts/sdxl-vae --prompts "a duck" "a rabbit" --views identity rotate_cw --style "an oil painting of" \\
@@ -21,10 +29,12 @@ from __future__ import annotations
 
 import argparse
 import json
+import math
 import os
 from typing import List
 
 import torch
+import torch.nn.functional as F
 
 from . import models
 from .sample import VAE_SCALE, load_checkpoint, load_train_args, make_text_encoder, make_vae_decoder, parse_resolution, save_png
@@ -52,13 +62,41 @@ def encode_views(encode_fn, prompts: List[str], style: str, negative: str):
     return feats[rows].contiguous(), mask[rows].contiguous()
 
 
-def run(args, *, encode_fn=None, cap_feat_dim=None, decode_fn=None, model=None, train_args=None) -> List[dict]:
-    """``encode_fn`` / ``decode_fn`` / ``model`` / ``train_args`` (the namespace of ``model_args.pth``: ``model``, ``qk_norm``, ``image_size``,
-    ``vae``) can be injected; otherwise they are built from the command-line paths."""
+def make_vae_encoder(path, device):
+    """image in [-1, 1] -> a sample of the latent distribution (NOT yet multiplied by the scale factor), as generate.py:91 draws it; None when
+    diffusers / the weights are unavailable.  The whole image in one pass (no tiling)."""
+    if not path:
+        return None
+    try:
+        from diffusers.models import AutoencoderKL
+    except ImportError:
+        return None
+    vae = AutoencoderKL.from_pretrained(path, torch_dtype=torch.float32).to(device).eval()
+
+    @torch.no_grad()
+    def encode(image):
+        return vae.encode(image.float()).latent_dist.sample()
+
+    return encode
+
+
+def upscale_model_kwargs(args, cat: int, w: int, h: int, image_size: int) -> dict:
+    """generate.py:420-435 (and :369: do_extrapolation); the fork's model ignores scale_watershed, so it is not handed on"""
+    kw = dict(proportional_attn=bool(args.proportional_attn), base_seqlen=(image_size // 16) ** 2 if args.proportional_attn else None, scale_factor=1.0)
+    if cat > image_size and args.scaling_method == "Time-aware":
+        kw["scale_factor"] = math.sqrt(w * h / image_size ** 2)
+    return kw
+
+
+def run(args, *, encode_fn=None, cap_feat_dim=None, decode_fn=None, model=None, train_args=None, vae_encode_fn=None) -> List[dict]:
+    """``encode_fn`` / ``decode_fn`` / ``vae_encode_fn`` / ``model`` / ``train_args`` (the namespace of ``model_args.pth``: ``model``, ``qk_norm``,
+    ``image_size``, ``vae``) can be injected; otherwise they are built from the command-line paths.  ``vae_encode_fn``: image ``[1, 3, h, w]`` in
+    [-1, 1] -> latent ``[1, 4, h / 8, w / 8]`` before the scale factor (``--upscale`` only; the whole image, no tiling)."""
     torch.set_grad_enabled(False)
-    if getattr(args, "upscale", False):
-        raise NotImplementedError("Phase Upscale (generate.py:437-494, midpoint_solver_extra) is not built: it needs the tiled VAE and the anagram "
-                                  "fork's proportional-attention / time-aware-scaling model, which the engine does not implement")
+    upscale = bool(getattr(args, "upscale", False))
+    if upscale and vae_encode_fn is None and not args.vae:
+        raise NotImplementedError("Phase Upscale (generate.py:437-494) needs a VAE encoder for the guidance latent and none is available: pass --vae "
+                                  "(a local diffusers AutoencoderKL) or inject vae_encode_fn")
     if len(args.prompts) != len(args.views):
         raise ValueError("Number of prompts must match number of views")
     device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
@@ -78,6 +116,12 @@ def run(args, *, encode_fn=None, cap_feat_dim=None, decode_fn=None, model=None, 
         decode_fn = make_vae_decoder(args.vae, device)
         if decode_fn is None:
             print("[sample_anagram] no VAE decoder (diffusers or --vae missing): writing latents only", flush=True)
+    if upscale:
+        if vae_encode_fn is None:
+            vae_encode_fn = make_vae_encoder(args.vae, device)
+        if vae_encode_fn is None or decode_fn is None:
+            raise NotImplementedError("Phase Upscale (generate.py:437-494) needs a VAE encoder and decoder for the guidance latent and diffusers or the "
+                                      "--vae weights are missing")
     factor = VAE_SCALE.get(getattr(train_args, "vae", "sdxl"), 0.18215)
     views = get_anagrams_views(args.views, view_args=args.view_args)
     cap_feats, cap_mask = encode_views(encode_fn, list(args.prompts), args.style, args.negative_prompt)
@@ -109,6 +153,22 @@ def run(args, *, encode_fn=None, cap_feat_dim=None, decode_fn=None, model=None, 
                 # the image under every view, side by side (utils.save_illusion)
                 entry["views_image"] = os.path.join(sample_dir, f"sample_{size}.views.png")
                 save_png(torch.cat([v.view(image[0].float() * 2 - 1) / 2 + 0.5 for v in views], dim=2), entry["views_image"])
+            if upscale:
+                # generate.py:442-463: the decoded illusion, bicubic to (h, w) in fp32, rounded to bf16, encoded: the guidance latent; a fresh z
+                guidance = F.interpolate(image.float() * 2 - 1, size=(h, w), mode="bicubic").to(torch.bfloat16)
+                guidance = (vae_encode_fn(guidance) * factor).to(dtype)
+                z = torch.randn_like(guidance[:1]).to(dtype)
+                kw = upscale_model_kwargs(args, cat, w, h, image_size)
+                up = model.sample_views_guided(z, guidance, grid, views, cap_feats, cap_mask, cfg_scale=args.cfg_scale,
+                                               coef_rounding=args.coef_rounding, return_trajectory=False, **kw)
+                usize = up.shape[-1] * 8
+                entry.update(upscale=kw, upscaled_latent=os.path.join(sample_dir, f"upscaled_latent_{usize}.pt"),
+                             upscaled_image=os.path.join(sample_dir, f"upscaled_{usize}.png"),
+                             upscaled_views_image=os.path.join(sample_dir, f"upscaled_{usize}.views.png"))
+                torch.save(up.cpu(), entry["upscaled_latent"])
+                image = decode_fn(up / factor)
+                save_png(image[0], entry["upscaled_image"])
+                save_png(torch.cat([v.view(image[0].float() * 2 - 1) / 2 + 0.5 for v in views], dim=2), entry["upscaled_views_image"])
             info.append(entry)
     with open(os.path.join(save_dir, "metadata.json"), "w") as f:
         json.dump(info, f, indent=1)
@@ -137,7 +197,13 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--debug", action="store_true", help="random-init weights (no checkpoint load), as in the reference")
     p.add_argument("--text_encoder", type=str, default="google/gemma-2b", help="local path of the text encoder (no network)")
     p.add_argument("--vae", type=str, default="", help="local path of the diffusers AutoencoderKL weights; empty: latents only")
-    p.add_argument("--upscale", action="store_true", help="Phase Upscale of the reference: refused (not built)")
+    p.add_argument("--upscale", action="store_true", help="continue with Phase Upscale of the reference (needs --vae: encoder and decoder)")
+    p.add_argument("--proportional_attn", type=lambda v: str(v).lower() not in ("0", "false", "no", ""), default=True,
+                   help="Phase Upscale: proportional attention with base_seqlen (image_size / 16)^2")
+    p.add_argument("--scaling_method", type=str, default="Time-aware", help="Phase Upscale: 'Time-aware' scales the RoPE above the training size")
+    p.add_argument("--scaling_watershed", type=float, default=0.3, help="accepted for the reference's command lines; its model ignores it")
+    p.add_argument("--coef_rounding", type=str, choices=["fp32", "state"], default="fp32",
+                   help="Phase Upscale: the decay factor multiplies the state in fp32 (expected of the reference's GPU run) or rounded to the state dtype")
     return p
 
 

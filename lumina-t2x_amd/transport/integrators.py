@@ -400,6 +400,33 @@ def sde_table(plan, form, norm, t, dt, sampler_type, like, last_step=None, last_
     return steps, (packed[n * stages * 5:].clone() if last is not None else None)
 
 
+def views_guided_table(tgrid, state_dtype, coef_rounding="fp32"):
+    """Per-stage scalar coefficients of ``lt_sample_views_guided`` (Phase Upscale of the reference's visual_anagrams/generate.py:232-257): fp32
+    CPU ``[len(tgrid) - 1, 2, 4]`` with records ``ft, f1t, kc, k1c`` for the stage at ``t0`` and the stage at ``t_mid = t0 + 0.5 (t1 - t0)``.
+
+    ``ft = fp32(t)``, ``f1t = fp32(1 - t)``: ``t0 * guidance`` and ``(1 - t0) * noise`` have a Python float on the left, which PyTorch multiplies
+    into a tensor in fp32 whatever its dtype.  ``kc = c`` and ``k1c = 1 - c`` with ``c = 0.5 * (1 + torch.cos(torch.pi * torch.tensor(t)))``, the
+    reference's own expression evaluated here by torch: a 0-dim fp32 CPU tensor.  ``coef_rounding="state"`` rounds ``c`` and ``1 - c`` to
+    ``state_dtype`` before the upload - what PyTorch's CPU kernels do with a 0-dim operand of a bf16 tensor; ``"fp32"`` keeps them, which is what
+    its GPU kernels are expected to do with a CPU scalar."""
+    if coef_rounding not in ("fp32", "state"):
+        raise ValueError(f"coef_rounding '{coef_rounding}' not in ('fp32', 'state')")
+    t = tgrid if isinstance(tgrid, th.Tensor) else th.tensor(list(tgrid), dtype=th.float32)
+    grid = [float(v) for v in t.detach().to("cpu", th.float32).tolist()]  # the fp32 grid's values as Python floats (generate.py:385)
+    out = th.empty((max(len(grid) - 1, 0), 2, 4), dtype=th.float32)
+    for i in range(len(grid) - 1):
+        t0, t1 = grid[i], grid[i + 1]
+        dt = t1 - t0
+        half_dt = 0.5 * dt
+        for k, tk in enumerate((t0, t0 + half_dt)):
+            c = 0.5 * (1 + th.cos(th.pi * th.tensor(tk)))
+            k1c = 1 - c
+            if coef_rounding == "state":
+                c, k1c = c.to(state_dtype).float(), k1c.to(state_dtype).float()
+            out[i, k] = th.stack([th.tensor(tk, dtype=th.float32), th.tensor(1 - tk, dtype=th.float32), c.float(), k1c.float()])
+    return out
+
+
 class sde:
     """Euler-Maruyama / Heun SDE sampler (reference integrators.py:5-76).
 
