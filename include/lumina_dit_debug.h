@@ -200,6 +200,23 @@ int lt_op_linear_small_m_ext(const void* a, const void* w, const void* b, void* 
 int lt_op_moe_route(const void* x, const void* gate_w, const void* forced, int32_t rows, int32_t rows_per_sample, int32_t d, int32_t E, void* sel,
                     void* wts, int32_t max_tiles, void* stream);
 
+/* The two attention launches that build their operands themselves, with every argument the engine fills, for tests/test_gpu_prologue_exact.py.
+ *   lt_op_attention_qraw_ex = lt_op_attention_qraw (lumina_dit.h) plus the table-branch select - cs_table / cs_table_t hold two branches,
+ *   [2][table_len][hd / 4] (cos, sin) and its transpose [2][hd / 4][table_len]; branch 0 is read when t_dev[0] < watershed, branch 1 otherwise
+ *   and when t_dev is NULL - and, optionally, the fused text keys of lt_op_attention_fused (tk NULL: none).
+ *   lt_op_attention_small: launch_attention_small alone (csrc/kernels.h, AttnSmallArgs: qkv [B * tokens, ld] with the q / k / v column blocks at
+ *   q_col0 / k_col0 / v_col0, rowstat [B * tokens][slots] float2 (sum, sum of squares) per 128-column tile, q / k in slots [q_slot0, + q_nslot) /
+ *   [k_slot0, + k_nslot), cs_table [2][table_len][hd / 4] (cos, sin), branch as above, out [B, tokens, H * hd]); ln_eps 1e-5, no prefetch rider. */
+int lt_op_attention_qraw_ex(const void* qkv_dev, int32_t ld, int32_t q_col0, const void* q_mean_rstd_dev, const void* q_ln_w_dev,
+                            const void* q_ln_b_dev, const void* cs_table_dev, const void* cs_table_t_dev, int32_t table_len, int32_t grid_w,
+                            const void* t_dev, float watershed, const void* k_dev, const void* vt_dev, const void* tk_dev, const void* tvt_dev,
+                            const float* tbias_dev, const void* tgate_dev, int32_t Tk, int32_t Tkpad, void* out_dev, int32_t B, int32_t H,
+                            int32_t Hkv, int32_t N, int32_t Nkpad, int32_t hd, void* stream);
+int lt_op_attention_small(const void* qkv_dev, int32_t ld, int32_t q_col0, int32_t k_col0, int32_t v_col0, const void* rowstat_dev, int32_t slots,
+                          int32_t q_slot0, int32_t q_nslot, int32_t k_slot0, int32_t k_nslot, const void* q_ln_w_dev, const void* q_ln_b_dev,
+                          const void* k_ln_w_dev, const void* k_ln_b_dev, const void* cs_table_dev, int32_t table_len, int32_t grid_w,
+                          const void* t_dev, float watershed, float k_scale, void* out_dev, int32_t B, int32_t H, int32_t Hkv, int32_t tokens,
+                          int32_t hd, void* stream);
 
 /* The guided view gather of lt_sample_views_guided (csrc/views.hip, where the chain is written out) on caller-owned buffers: a plain forward of
  * the launcher's arguments.  y, guidance, noise [C, HW]; perm int32 [V][HW], vsign / isign float [V][C] (DEVICE); f0 [V, C, HW] or NULL (stage 0);

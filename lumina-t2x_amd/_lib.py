@@ -176,6 +176,10 @@ _SIGNATURES: Dict[str, tuple] = {
     "lt_op_proj_gated_residual_norm": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _f32, _i32, _vp]),
     "lt_op_qkv_qstat": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _f32, _vp, _vp, _vp, _vp]),
     "lt_op_attention_qraw": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "lt_op_attention_qraw_ex": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp,
+                                       _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "lt_op_attention_small": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _f32,
+                                     _f32, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "lt_op_rmsnorm_mod_ex": (_i32, [_vp, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _f32, _i32, _i32, _vp]),
     "lt_op_gated_residual_norm_ex": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _f32, _f32, _i32, _i32,
                                             _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),

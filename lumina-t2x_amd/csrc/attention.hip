@@ -995,6 +995,8 @@ int launch_attention(const AttnArgs& a, hipStream_t stream) {
     LT_REQUIRE(a.H % a.Hkv == 0, "attention: H=%d not a multiple of Hkv=%d", a.H, a.Hkv);
     LT_REQUIRE(a.q_raw == nullptr || (attention_takes_raw_q(a) && a.q_stat && a.q_ln_w && a.q_ln_b && a.rope_cs && a.rope_cs_t && a.rope_grid_w > 0 && a.rope_cs_len > 0),
                "attention: q_raw (q_norm + RoPE in the prologue) needs the head_dim-72 one-wave kernel's conditions and the LayerNorm / RoPE inputs");
+    LT_REQUIRE(a.q_raw == nullptr || ((a.N - 1) / a.rope_grid_w < a.rope_cs_len && a.rope_grid_w <= a.rope_cs_len),
+               "attention: q_raw token grid exceeds the RoPE table (%d)", a.rope_cs_len);
     LT_REQUIRE(a.q != nullptr || a.q_raw != nullptr, "attention: no query tensor");
     LT_REQUIRE(a.Nkpad % 64 == 0 && a.Nkpad >= a.Nk && a.Nk > 0 && a.N > 0, "attention: bad key counts Nk=%d Nkpad=%d", a.Nk, a.Nkpad);
     LT_REQUIRE(!a.accumulate || a.gate != nullptr, "attention: accumulate mode needs a gate");

@@ -399,6 +399,42 @@ extern "C" int lt_op_attention_qraw(const void* qkv, int32_t ld, int32_t q_col0,
     return launch_attention(a, (hipStream_t)stream);
 }
 
+// lt_op_attention_qraw with the AttnArgs fields the engine fills besides (engine.hip, the attn_q_fused path): the table-branch select (t_dev,
+// watershed) and, optionally, the fused text keys (tk == NULL: none).  tests/test_gpu_prologue_exact.py
+extern "C" int lt_op_attention_qraw_ex(const void* qkv, int32_t ld, int32_t q_col0, const void* q_mean_rstd, const void* q_ln_w, const void* q_ln_b,
+                                       const void* cs_table, const void* cs_table_t, int32_t table_len, int32_t grid_w, const void* t_dev,
+                                       float watershed, const void* k, const void* vt, const void* tk, const void* tvt, const float* tbias,
+                                       const void* tgate, int32_t Tk, int32_t Tkpad, void* out, int32_t B, int32_t H, int32_t Hkv, int32_t N,
+                                       int32_t Nkpad, int32_t hd, void* stream) {
+    LT_REQUIRE(qkv && q_mean_rstd && q_ln_w && q_ln_b && cs_table && cs_table_t && k && vt && out, "lt_op_attention_qraw_ex: null pointer");
+    AttnArgs a;
+    a.q = nullptr; a.k = (const u16*)k; a.vt = (const u16*)vt; a.bias = nullptr; a.out = (u16*)out; a.gate = nullptr; a.accumulate = 0;
+    a.B = B; a.H = H; a.Hkv = Hkv; a.N = N; a.Nk = N; a.Nkpad = Nkpad; a.hd = hd; a.scale = 1.f; a.k_prescaled = 1;
+    if (tk) { a.tk = (const u16*)tk; a.tvt = (const u16*)tvt; a.tbias = tbias; a.tgate = (const u16*)tgate; a.Tk = Tk; a.Tkpad = Tkpad; }
+    a.q_raw = (const u16*)qkv; a.q_ld = ld; a.q_col0 = q_col0; a.q_stat = (const float*)q_mean_rstd;
+    a.q_ln_w = (const u16*)q_ln_w; a.q_ln_b = (const u16*)q_ln_b;
+    a.rope_cs = (const float*)cs_table; a.rope_cs_t = (const float*)cs_table_t; a.rope_t = (const float*)t_dev; a.rope_watershed = watershed;
+    a.rope_cs_len = table_len; a.rope_grid_w = grid_w;
+    return launch_attention(a, (hipStream_t)stream);
+}
+
+// launch_attention_small alone (no GEMM in front, no prefetch rider): every field of AttnSmallArgs as a plain argument; ln_eps 1e-5 as in the engine
+extern "C" int lt_op_attention_small(const void* qkv, int32_t ld, int32_t q_col0, int32_t k_col0, int32_t v_col0, const void* rowstat, int32_t slots,
+                                     int32_t q_slot0, int32_t q_nslot, int32_t k_slot0, int32_t k_nslot, const void* q_ln_w, const void* q_ln_b,
+                                     const void* k_ln_w, const void* k_ln_b, const void* cs_table, int32_t table_len, int32_t grid_w,
+                                     const void* t_dev, float watershed, float k_scale, void* out, int32_t B, int32_t H, int32_t Hkv,
+                                     int32_t tokens, int32_t hd, void* stream) {
+    LT_REQUIRE(qkv && rowstat && q_ln_w && q_ln_b && k_ln_w && k_ln_b && cs_table && out, "lt_op_attention_small: null pointer");
+    LT_REQUIRE(B > 0 && H > 0 && Hkv > 0 && hd > 0 && tokens > 0, "lt_op_attention_small: bad shape");
+    AttnSmallArgs a;
+    a.qkv = (const u16*)qkv; a.ld = ld; a.q_col0 = q_col0; a.k_col0 = k_col0; a.v_col0 = v_col0;
+    a.rowstat = (const float*)rowstat; a.slots = slots; a.q_slot0 = q_slot0; a.q_nslot = q_nslot; a.k_slot0 = k_slot0; a.k_nslot = k_nslot;
+    a.q_ln_w = (const u16*)q_ln_w; a.q_ln_b = (const u16*)q_ln_b; a.k_ln_w = (const u16*)k_ln_w; a.k_ln_b = (const u16*)k_ln_b; a.ln_eps = 1e-5f;
+    a.cs = (const float*)cs_table; a.t = (const float*)t_dev; a.watershed = watershed; a.cs_len = table_len; a.grid_w = grid_w;
+    a.k_scale = k_scale; a.out = (u16*)out; a.B = B; a.H = H; a.Hkv = Hkv; a.N = tokens; a.hd = hd;
+    return launch_attention_small(a, (hipStream_t)stream);
+}
+
 // The small-M QKV projection with the per-tile LayerNorm partials (GemmArgs::rowstat) followed by the fused q / k post-processing +
 // attention launch (AttnSmallArgs): exactly the two launches the engine makes per layer on the attn_small_fused path.
 extern "C" int lt_op_qkv_attention_small(const void* A, const void* W, void* qkv, int32_t M, int32_t K, int32_t H, int32_t Hkv, int32_t tokens,
