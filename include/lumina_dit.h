@@ -173,6 +173,18 @@ int lt_forward(lt_engine* e, const void* x_dev, const float* t_dev, void* out_de
  * Next-DiT, plain forward only (the reference's forward_with_cfg takes tensors only). */
 int lt_forward_packed(lt_engine* e, const void* const* x_ptrs, const int32_t* hw_host, const float* t_dev,
                       void* const* out_ptrs, const lt_step_args* a, void* stream);
+/* Guidance on a LIST of differently sized samples, by composition of two unmodified pieces of the reference: NextDiT.forward on the list
+ * [x_0 .. x_{B'-1}, x_0 .. x_{B'-1}] (captions cond_0 .. cond_{B'-1}, uncond_0 .. uncond_{B'-1}; t with 2 B' entries) and the guidance
+ * expression of model.py:901-913 per sample (cfg_channels quirk included).  a->batch = 2 B'; hw_host = [a->batch][2] latent sizes with
+ * hw[b] == hw[b + B'] (a->latent_h / latent_w are ignored).  x_flat_dev / out_flat_dev: ONE buffer each in a->io_dtype, sample b =
+ * [in_channels, H_b, W_b] at element offset sum_{j<b} in_channels H_j W_j; the second half of x is not read (its pixels are the first
+ * half's), both halves of out are written.  Padding, key mask, rotary grid width and the proportional-attention length as lt_forward_packed.
+ * Evaluations go through the HIP-graph cache; the size list is part of the key.
+ * Refused by name, leaving out untouched: a null argument; an odd batch; halves of different sizes; more than 64 samples or more than
+ * max_batch; a size that is not a positive multiple of the patch size; a longest sequence above max_tokens or a grid above the RoPE
+ * table; any variant other than LT_VARIANT_NEXT_T2I; a regional prompt. */
+int lt_forward_cfg_packed(lt_engine* e, const void* x_flat_dev, const int32_t* hw_host, const float* t_dev, void* out_flat_dev,
+                          const lt_step_args* a, void* stream);
 /* NextDiT.forward_with_cfg (model.py:866-913): duplicates the first half, CFG on cfg_channels. */
 int lt_forward_cfg(lt_engine* e, const void* x_dev, const float* t_dev, void* out_dev,
                    const lt_step_args* a, void* stream);
@@ -185,6 +197,15 @@ int lt_forward_cfg(lt_engine* e, const void* x_dev, const float* t_dev, void* ou
 int lt_sample_ode(lt_engine* e, const void* z_dev, void* traj_dev, void* final_dev,
                   const float* tgrid_host, int32_t n_grid, int32_t method, int32_t use_cfg,
                   int32_t t_round_to_state_dtype, const lt_step_args* a, void* stream);
+
+/* lt_sample_ode on a packed batch: z, each of the n_grid trajectory slots (traj_flat_dev, may be NULL) and the final state (final_flat_dev,
+ * may be NULL) are flat buffers in the layout of lt_forward_cfg_packed.  Every model call is the packed forward_with_cfg when use_cfg != 0,
+ * else the packed forward (any batch); stage times, stage arithmetic and rounding points are lt_sample_ode's, statement for statement.
+ * lt_last_nfe = (n_grid - 1) * stages.  No synchronisation, no host read.  Refused by name with no partial result: what
+ * lt_forward_cfg_packed refuses (the odd batch and the unequal halves under use_cfg only), an unknown method, n_grid < 2. */
+int lt_sample_ode_packed(lt_engine* e, const void* z_flat_dev, const int32_t* hw_host, void* traj_flat_dev, void* final_flat_dev,
+                         const float* tgrid_host, int32_t n_grid, int32_t method, int32_t use_cfg, int32_t t_round_to_state_dtype,
+                         const lt_step_args* a, void* stream);
 
 /* ---- multi-view (visual-anagram) sampling: visual_anagrams/generate.py:389-414, Phase Init ------------------------------------------
  * ONE latent; per time interval every view v sees view_v(latent) with its own prompt, takes one ODE step of forward_with_cfg, and the mean
@@ -286,7 +307,7 @@ int lt_sample_ode_adaptive(lt_engine* e, const void* z_dev, void* traj_dev, cons
                            float atol, float first_step, int32_t max_steps, int32_t use_cfg, int32_t t_round_to_state_dtype,
                            const lt_step_args* a, void* stream, lt_ode_adaptive_stats* stats);
 
-/* number of model evaluations issued by the last lt_sample_ode / lt_sample_views / lt_sample_views_guided / lt_sample_sde / lt_sample_ode_adaptive call */
+/* number of model evaluations issued by the last lt_sample_ode / lt_sample_ode_packed / lt_sample_views / lt_sample_views_guided / lt_sample_sde / lt_sample_ode_adaptive call */
 int64_t lt_last_nfe(lt_engine* e);
 /* model evaluations served by replaying a captured HIP graph since lt_create (0 with lt_set_option("graph", 0), and below 1025 rows under the default "graph" 2) */
 int64_t lt_graph_replays(lt_engine* e);

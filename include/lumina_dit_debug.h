@@ -188,6 +188,22 @@ int lt_op_cap_pool_ln(const void* cap, int32_t cap_dtype, const void* mask, cons
                       int32_t C, void* stream);
 int lt_op_unpatchify_cfg(const void* rows, int32_t ld, void* out, int32_t out_dtype, int32_t B, int32_t C, int32_t out_ch, int32_t H, int32_t W,
                          int32_t patch, int32_t use_cfg, float cfg_scale, int32_t cfg_channels, int32_t wp_stride, void* stream);
+/* The ragged boundary kernels of a packed batch (csrc/packed.hip): one launch for all samples.  hw_host = [B][2] latent sizes (host); the
+ * flat state holds sample b = [C, H_b, W_b] at element offset sum_{j<b} C H_j W_j; N = token rows per sample in the row buffers (>= the longest
+ * sequence).  Each launching entry builds the table of the size list, stores it at tab_dev (5 * 64 ints of device memory) and runs its kernel.
+ *   packed_table: the host-side table alone - table_host receives 5 rows of 64 ints (element offset, H_b, W_b, token count, grid width; row r
+ *   of sample b at [r * 64 + b]), elems the length of the flat state, n_max the longest sequence (each may be NULL).  Needs no device.
+ *   patchify_packed: flat state -> out [B * N, kpad]; rows behind a sample's last token are not written.  dup_first_half as lt_op_patchify.
+ *   fill_pad_packed: rows ntok_b .. N - 1 of every sample of x [B * N, d] = pad_token [d] (C plays no part: sizes and patch give the counts).
+ *   unpatchify_packed: rows [B * N, ld] -> flat state, lt_op_unpatchify_cfg's arithmetic per sample (use_cfg 0: plain, sigma half dropped). */
+int lt_op_packed_table(const int32_t* hw_host, int32_t B, int32_t C, int32_t patch, int32_t* table_host, int64_t* elems, int32_t* n_max);
+int lt_op_patchify_packed(const void* x_flat, int32_t x_dtype, void* out, const int32_t* hw_host, void* tab_dev, int32_t B, int32_t C,
+                          int32_t patch, int32_t kpad, int32_t N, int32_t dup_first_half, void* stream);
+int lt_op_fill_pad_packed(void* x, const void* pad_token, const int32_t* hw_host, void* tab_dev, int32_t B, int32_t patch, int32_t N, int32_t d,
+                          void* stream);
+int lt_op_unpatchify_packed(const void* rows, int32_t ld, void* out_flat, int32_t out_dtype, const int32_t* hw_host, void* tab_dev, int32_t B,
+                            int32_t C, int32_t out_ch, int32_t patch, int32_t N, int32_t use_cfg, float cfg_scale, int32_t cfg_channels,
+                            void* stream);
 int lt_op_region_text_combine(void* out, const void* txt, const void* gate, int32_t Y, int32_t N, int32_t H, int32_t hd, int32_t Hp, int32_t Wp,
                               int32_t h_split, int32_t w_split, void* stream);
 int lt_op_ode_combine(int32_t mode, const void* y0, const void* k1, const void* k2, const void* k3, const void* k4, void* out, int32_t dtype,

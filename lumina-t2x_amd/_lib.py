@@ -100,6 +100,8 @@ _SIGNATURES: Dict[str, tuple] = {
     "lt_prepare_labels": (_i32, [_vp, _vp, _i32, _vp]),
     "lt_forward": (_i32, [_vp, _vp, _vp, _vp, C.POINTER(LtStepArgs), _vp]),
     "lt_forward_packed": (_i32, [_vp, C.POINTER(_vp), C.POINTER(_i32), _vp, C.POINTER(_vp), C.POINTER(LtStepArgs), _vp]),
+    "lt_forward_cfg_packed": (_i32, [_vp, _vp, C.POINTER(_i32), _vp, _vp, C.POINTER(LtStepArgs), _vp]),
+    "lt_sample_ode_packed": (_i32, [_vp, _vp, C.POINTER(_i32), _vp, _vp, C.POINTER(_f32), _i32, _i32, _i32, _i32, C.POINTER(LtStepArgs), _vp]),
     "lt_forward_cfg": (_i32, [_vp, _vp, _vp, _vp, C.POINTER(LtStepArgs), _vp]),
     "lt_sample_ode": (_i32, [_vp, _vp, _vp, _vp, C.POINTER(_f32), _i32, _i32, _i32, _i32, C.POINTER(LtStepArgs), _vp]),
     "lt_set_views": (_i32, [_vp, _vp, C.POINTER(_f32), C.POINTER(_f32), _i32, _i32, _i32, _vp]),
@@ -166,6 +168,10 @@ _SIGNATURES: Dict[str, tuple] = {
     "lt_op_timestep_features": (_i32, [_vp, _i32, _vp, _i32, _i32, _vp]),
     "lt_op_cap_pool_ln": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "lt_op_unpatchify_cfg": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _i32, _vp]),
+    "lt_op_packed_table": (_i32, [C.POINTER(_i32), _i32, _i32, _i32, C.POINTER(_i32), C.POINTER(_i64), C.POINTER(_i32)]),
+    "lt_op_patchify_packed": (_i32, [_vp, _i32, _vp, C.POINTER(_i32), _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "lt_op_fill_pad_packed": (_i32, [_vp, _vp, C.POINTER(_i32), _vp, _i32, _i32, _i32, _i32, _vp]),
+    "lt_op_unpatchify_packed": (_i32, [_vp, _i32, _vp, _i32, C.POINTER(_i32), _vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _vp]),
     "lt_op_region_text_combine": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "lt_op_ode_combine": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _f32, _i64, _vp]),
     "lt_op_rope_table": (_i32, [_vp, _i32, _i32, _i32, _f32, _f32, _f32, _f32, _i32, _vp, _vp]),

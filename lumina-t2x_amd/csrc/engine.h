@@ -190,6 +190,7 @@ struct lt_engine {
     int* reg_qmap = nullptr;   // [max_batch] query batch of each caption
     int* pk_dev = nullptr;     // packed batches: [0,64) token counts, [64,128) grid widths
     int pk_host[128] = {0};
+    int* pk_tab = nullptr;     // packed batches on a flat state (lt_forward_cfg_packed / lt_sample_ode_packed): the device PackedTable (kernels.h)
     long long last_nfe = 0;
     // multi-view sampling (lt_set_views / lt_sample_views, views.hip): engine-owned tables of the V views over an h x w latent
     int *vw_perm = nullptr, *vw_iperm = nullptr, *vw_hits = nullptr;  // [V][h w], [V][h w], [V h w + 1]
@@ -211,8 +212,20 @@ struct lt_engine {
     ProfClass prof[3];
 };
 
-// one model evaluation [+ CFG combine], through a cached HIP graph where that pays (engine.hip)
-int forward_graphed(lt_engine* e, const void* x_in, const float* t_dev, void* out, const lt_step_args* a, int use_cfg, hipStream_t s);
+// A packed batch on one flat state buffer (packed.hip): what an evaluation needs of the size list.  The device table e->pk_tab holds the
+// same list (packed_call_begin stored it on the call's stream).
+struct PackedCall {
+    const int32_t* hw;  // [a->batch][2] latent (H_b, W_b), host
+    long long elems;    // length of the flat state
+    int n_max;          // longest sequence
+};
+// validates a size list against the engine and the step arguments (refusals by name), fills `pc` and stores the device table on stream s
+// (engine.hip)
+int packed_call_begin(lt_engine* e, const char* who, const int32_t* hw_host, const lt_step_args* a, int use_cfg, PackedCall* pc, hipStream_t s);
+// one model evaluation [+ CFG combine], through a cached HIP graph where that pays (engine.hip); pc: x_in / out are the flat state of a
+// packed batch
+int forward_graphed(lt_engine* e, const void* x_in, const float* t_dev, void* out, const lt_step_args* a, int use_cfg, hipStream_t s,
+                    const PackedCall* pc = nullptr);
 // the softmax scale of an evaluation of N tokens under the engine's rule (model.py:373-376, visual_anagrams/models/nextdit.py:331-335), and the
 // refusal of a shape the anagram fork's query chunks do not cover; non-zero after lt_set_error (engine.hip)
 int softmax_scale_for(const lt_engine* e, const lt_step_args* a, int N, float* scale);

@@ -367,6 +367,10 @@ struct PackedDesc {
     const void* const* x_ptrs;  // [B] device pointers
     void* const* out_ptrs;      // [B] device pointers, each [in_channels, H_b, W_b]
     const int32_t* hw;          // [B][2] latent (H_b, W_b), host
+    // the flat form (lt_forward_cfg_packed / lt_sample_ode_packed; x_ptrs / out_ptrs null): one state buffer, the ragged kernels of packed.hip
+    const void* x_flat = nullptr;
+    void* out_flat = nullptr;
+    const int* tab = nullptr;   // device PackedTable (kernels.h) of the same size list
 };
 
 // all four GEMM weights of every dense block -> the row-pair-interleaved layout (want) or back to row-major, in place, on stream s
@@ -394,7 +398,9 @@ int run_forward(lt_engine* e, const void* x_in, const float* t_dev, void* out, c
     const VariantDesc& v = e->v;
     const int B = a->batch, p = c.patch_size;
     if (pk) {
-        LT_REQUIRE(c.variant == LT_VARIANT_NEXT_T2I && !use_cfg, "packed batches: plain forward of the text-conditional Next-DiT only");
+        LT_REQUIRE(c.variant == LT_VARIANT_NEXT_T2I, "packed batches: the text-conditional Next-DiT (LT_VARIANT_NEXT_T2I) only; this engine is variant %d",
+                   c.variant);
+        LT_REQUIRE(pk->tab || !use_cfg, "packed batches: lt_forward_packed is the plain forward (guidance on a size list: lt_forward_cfg_packed)");
         LT_REQUIRE(B >= 1 && B <= c.max_batch && B <= 64, "packed batch of %d exceeds max_batch %d (or 64)", B, c.max_batch);
     }
     LT_REQUIRE(B >= 1 && B <= c.max_batch, "batch %d exceeds max_batch %d", B, c.max_batch);
@@ -404,6 +410,7 @@ int run_forward(lt_engine* e, const void* x_in, const float* t_dev, void* out, c
     const int Wrow = v.eol ? Wp + 1 : Wp;  // tokens per latent row (Flag-DiT appends one eol token, model.py:779-786)
     int N = Hp * Wrow;
     int pk_ntok[64], pk_gw[64];
+    bool pk_full = true;  // no sample is shorter than the longest one: no padded keys to mask
     if (pk) {  // N = the longest sequence; a->latent_h / latent_w are ignored
         N = 0; Hp = 0; Wp = 0;
         for (int b = 0; b < B; ++b) {
@@ -413,6 +420,7 @@ int run_forward(lt_engine* e, const void* x_in, const float* t_dev, void* out, c
             pk_gw[b] = wb / p;
             N = std::max(N, pk_ntok[b]); Hp = std::max(Hp, hb / p); Wp = std::max(Wp, wb / p);
         }
+        for (int b = 0; b < B; ++b) pk_full = pk_full && pk_ntok[b] == N;
     }
     const int M = B * N;
     LT_REQUIRE(N <= c.max_tokens, "%d latent tokens exceed max_tokens %d", N, c.max_tokens);
@@ -436,6 +444,10 @@ int run_forward(lt_engine* e, const void* x_in, const float* t_dev, void* out, c
     if (!pk) {
         ProfScope ps(e, 2, 0, s);
         if (launch_patchify(x_in, a->io_dtype, e->patches, B, c.in_channels, a->latent_h, a->latent_w, p, e->kpad, use_cfg, Wrow, s)) return 1;
+    } else if (pk->tab) {  // one launch for all samples; the table was stored by the entry point
+        ProfScope ps(e, 2, 0, s);
+        if (launch_patchify_packed(pk->x_flat, a->io_dtype, e->patches, pk->tab, B, c.in_channels, p, e->kpad, N, use_cfg, s)) return 1;
+        ntok_dev = pk->tab + LT_PK_NTOK * LT_PK_MAX; gw_dev = pk->tab + LT_PK_GW * LT_PK_MAX;
     } else {
         ProfScope ps(e, 2, 0, s);
         for (int b = 0; b < B; ++b)
@@ -448,7 +460,10 @@ int run_forward(lt_engine* e, const void* x_in, const float* t_dev, void* out, c
         ntok_dev = e->pk_dev; gw_dev = e->pk_dev + 64;
     }
     if (gemm(e, e->patches, e->kpad, e->xemb_w, e->kpad, e->x, d, M, d, e->kpad, e->xemb_b, 0, s)) return 1;
-    if (pk) {  // padded positions hold the learned pad_token, not an embedded patch (model.py:811-817)
+    if (pk && pk->tab) {
+        ProfScope ps(e, 2, 0, s);
+        if (!pk_full && launch_fill_pad_packed(e->x, e->pad_token, pk->tab, B, N, d, s)) return 1;
+    } else if (pk) {  // padded positions hold the learned pad_token, not an embedded patch (model.py:811-817)
         ProfScope ps(e, 2, 0, s);
         for (int b = 0; b < B; ++b)
             if (pk_ntok[b] < N && launch_fill_rows_bf16(e->x + ((size_t)b * N + pk_ntok[b]) * d, e->pad_token, N - pk_ntok[b], d, s)) return 1;
@@ -587,7 +602,7 @@ int run_forward(lt_engine* e, const void* x_in, const float* t_dev, void* out, c
         at.q = e->q; at.k = e->k; at.vt = e->vt; at.bias = nullptr; at.out = e->attn; at.gate = nullptr; at.accumulate = 0;
         at.B = B; at.H = H; at.Hkv = Hkv; at.N = N; at.Nk = N; at.Nkpad = Npad; at.hd = hd; at.scale = sm_scale;
         at.k_prescaled = 1;
-        at.nk_batch = ntok_dev;
+        at.nk_batch = pk && pk->tab && pk_full ? nullptr : ntok_dev;  // (flat form, every sample of the longest length: no key to mask)
         at.tail_ws = e->attn_tail_ws; at.tail_ws_bytes = e->attn_tail_ws_bytes;
         if (fuse_text) {  // zero-init gated text cross-attention (model.py:420-434) inside the same launch
             at.tk = w.ky; at.tvt = w.vty; at.tbias = e->txt_bias; at.tgate = w.gate; at.Tk = e->prompt_T; at.Tkpad = e->prompt_Tpad;
@@ -762,6 +777,9 @@ int run_forward(lt_engine* e, const void* x_in, const float* t_dev, void* out, c
         if (!pk) {
             if (launch_unpatchify_cfg(e->frows, e->nfinal, out, a->io_dtype, B, c.in_channels, c.out_channels, a->latent_h,
                                       a->latent_w, p, use_cfg, a->cfg_scale, cfg_ch, Wrow, s)) return 1;
+        } else if (pk->tab) {
+            if (launch_unpatchify_packed(e->frows, e->nfinal, pk->out_flat, a->io_dtype, pk->tab, B, c.in_channels, c.out_channels, p, N, use_cfg,
+                                         a->cfg_scale, cfg_ch, s)) return 1;
         } else {
             for (int b = 0; b < B; ++b)  // x[i][:L] -> [C, H_b, W_b], sigma half dropped (model.py:757-768, :859-864)
                 if (launch_unpatchify_cfg(e->frows + (size_t)b * N * e->nfinal, e->nfinal, pk->out_ptrs[b], a->io_dtype, 1, c.in_channels,
@@ -814,21 +832,30 @@ int softmax_scale_for(const lt_engine* e, const lt_step_args* a, int N, float* s
     return 0;
 }
 
-int forward_graphed(lt_engine* e, const void* x_in, const float* t_dev, void* out, const lt_step_args* a, int use_cfg, hipStream_t s) {
-    if (!lt_opt(OPT_GRAPH) || profiling_wants_events(e) || e->moe_rec_on || e->moe_force_rows) return run_forward(e, x_in, t_dev, out, a, use_cfg, s);
+int forward_graphed(lt_engine* e, const void* x_in, const float* t_dev, void* out, const lt_step_args* a, int use_cfg, hipStream_t s,
+                    const PackedCall* pc) {
+    // one evaluation as plain launches; a packed batch's flat state goes through the ragged kernels
+    auto run = [&](const void* x, const float* t, void* o, hipStream_t st) {
+        if (!pc) return run_forward(e, x, t, o, a, use_cfg, st);
+        PackedDesc pk{nullptr, nullptr, pc->hw};
+        pk.x_flat = x; pk.out_flat = o; pk.tab = e->pk_tab;
+        return run_forward(e, nullptr, t, nullptr, a, use_cfg, st, &pk);
+    };
+    if (!lt_opt(OPT_GRAPH) || profiling_wants_events(e) || e->moe_rec_on || e->moe_force_rows) return run(x_in, t_dev, out, s);
     const int B = a->batch;
     // "graph" 2 (default): replay above 1024 rows only.  At 512 rows a replay (three staging copies + the graph launch) costs more than it
     // saves - plain launches are 1.5-4.6 % faster for the 600M ImageNet model, same box (profiles/r05/bench_ab_hip_graph_on_off_cfg1_cfg5.log:
     // 1.652 against 1.68-1.73 ms per NFE; the MoE model is neutral) - and the host issues its ~125 launches per evaluation in a quarter of
     // the time the GPU needs for them.  Above that the two are equal and the graph keeps a busy host out of the picture.
-    if (lt_opt(OPT_GRAPH) == 2 && a->latent_h > 0 && a->latent_w > 0 && e->cfg.patch_size > 0 &&
+    if (lt_opt(OPT_GRAPH) == 2 && pc && (long long)B * pc->n_max <= 1024) return run(x_in, t_dev, out, s);
+    if (lt_opt(OPT_GRAPH) == 2 && !pc && a->latent_h > 0 && a->latent_w > 0 && e->cfg.patch_size > 0 &&
         (long long)B * (a->latent_h / e->cfg.patch_size) * (a->latent_w / e->cfg.patch_size) <= 1024)
-        return run_forward(e, x_in, t_dev, out, a, use_cfg, s);
-    if (B < 1 || B > e->cfg.max_batch || a->latent_h <= 0 || a->latent_w <= 0 || (a->io_dtype != LT_BF16 && a->io_dtype != LT_F32))
-        return run_forward(e, x_in, t_dev, out, a, use_cfg, s);  // let the eager path produce the error message
-    const size_t sbytes = (size_t)B * e->cfg.in_channels * a->latent_h * a->latent_w * (a->io_dtype == LT_BF16 ? 2 : 4);
+        return run(x_in, t_dev, out, s);
+    if (B < 1 || B > e->cfg.max_batch || (!pc && (a->latent_h <= 0 || a->latent_w <= 0)) || (a->io_dtype != LT_BF16 && a->io_dtype != LT_F32))
+        return run(x_in, t_dev, out, s);  // let the eager path produce the error message
+    const size_t sbytes = (pc ? (size_t)pc->elems : (size_t)B * e->cfg.in_channels * a->latent_h * a->latent_w) * (a->io_dtype == LT_BF16 ? 2 : 4);
     const size_t cap_bytes = (size_t)e->cfg.max_batch * e->cfg.in_channels * e->cfg.max_tokens * e->cfg.patch_size * e->cfg.patch_size * 4;
-    if (sbytes > cap_bytes) return run_forward(e, x_in, t_dev, out, a, use_cfg, s);
+    if (sbytes > cap_bytes) return run(x_in, t_dev, out, s);
     // (both option generations: the process defaults' and this engine's overrides' - kernel selection is baked into a captured graph)
     // ... and the softmax rule: the scale it selects is a kernel argument (qa.out_scale / at.scale)
     const int extra[10] = {use_cfg, e->prompt_B, e->prompt_T, e->prompt_Tpad, e->reg_Y, e->reg_h, e->reg_w, lt_opt_generation(), lt_opt_engine_generation(),
@@ -836,6 +863,7 @@ int forward_graphed(lt_engine* e, const void* x_in, const float* t_dev, void* ou
     std::vector<char> key(sizeof(lt_step_args) + sizeof(extra));
     memcpy(key.data(), a, sizeof(lt_step_args));
     memcpy(key.data() + sizeof(lt_step_args), extra, sizeof(extra));
+    if (pc) key.insert(key.end(), (const char*)pc->hw, (const char*)(pc->hw + 2 * B));  // the size list: grids and the table's contents depend on it
     lt_engine::GraphEntry* ge = nullptr;
     for (auto& g : e->graphs) if (g.key == key) { ge = &g; break; }
     if (!ge) {
@@ -848,7 +876,7 @@ int forward_graphed(lt_engine* e, const void* x_in, const float* t_dev, void* ou
         ge->key = key;
     }
     if (ge->failed || ge->uses++ == 0) {
-        const int rc = run_forward(e, x_in, t_dev, out, a, use_cfg, s);
+        const int rc = run(x_in, t_dev, out, s);
         ge->pair = e->last_pair;  // (the weight layout this key's evaluations run on; a function of the key)
         return rc;
     }
@@ -856,7 +884,7 @@ int forward_graphed(lt_engine* e, const void* x_in, const float* t_dev, void* ou
     // from inside: hand it plain launches, which its own capture records
     hipStreamCaptureStatus caller_cap = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(s, &caller_cap) != hipSuccess) { (void)hipGetLastError(); caller_cap = hipStreamCaptureStatusNone; }
-    if (caller_cap != hipStreamCaptureStatusNone) return run_forward(e, x_in, t_dev, out, a, use_cfg, s);
+    if (caller_cap != hipStreamCaptureStatusNone) return run(x_in, t_dev, out, s);
     // the RoPE table is ONE shared buffer outside every graph (it is rebuilt only when scale / ntk change): a replay of key A after
     // key B changed the table must rebuild it first - before every replay, not only before the capture
     if (ensure_rope(e, a, s)) return 1;
@@ -870,7 +898,7 @@ int forward_graphed(lt_engine* e, const void* x_in, const float* t_dev, void* ou
         if (ok) {
             ge->tally = lt_engine::GraphTally();
             e->tally = &ge->tally;
-            rc = run_forward(e, e->g_x, e->g_t, e->g_out, a, use_cfg, e->cap_stream);
+            rc = run(e->g_x, e->g_t, e->g_out, e->cap_stream);
             e->tally = nullptr;
             if (rc == 0 && e->last_pair != ge->pair) { lt_set_error("graph capture: the evaluation's operand layout changed between the eager run and the capture"); rc = 1; }
             ok = hipStreamEndCapture(e->cap_stream, &graph) == hipSuccess && rc == 0 && graph != nullptr;
@@ -882,7 +910,7 @@ int forward_graphed(lt_engine* e, const void* x_in, const float* t_dev, void* ou
             ge->exec = nullptr;
             ge->failed = true;
             if (rc) return rc;
-            return run_forward(e, x_in, t_dev, out, a, use_cfg, s);
+            return run(x_in, t_dev, out, s);
         }
     }
     LT_CHECK_HIP(hipMemcpyAsync(e->g_x, x_in, sbytes, hipMemcpyDeviceToDevice, s));
@@ -1116,6 +1144,7 @@ extern "C" void lt_destroy(lt_engine* e) {
     e->times.release();
     e->rk.release();
     if (e->pk_dev) (void)hipFree(e->pk_dev);
+    if (e->pk_tab) (void)hipFree(e->pk_tab);
     if (e->reg_txt) (void)hipFree(e->reg_txt);
     if (e->reg_qmap) (void)hipFree(e->reg_qmap);
     drop_views(e);
@@ -1277,6 +1306,43 @@ extern "C" int lt_forward_packed(lt_engine* e, const void* const* x_ptrs, const 
     if (!e->pk_dev) LT_CHECK_HIP(hipMalloc((void**)&e->pk_dev, 128 * sizeof(int)));
     PackedDesc pk{x_ptrs, out_ptrs, hw_host};
     return run_forward(e, nullptr, t_dev, nullptr, a, 0, (hipStream_t)stream, &pk);
+}
+
+// The flat form of a packed batch: the refusals of a size list, by name, before anything is launched or copied; then the device table.
+int packed_call_begin(lt_engine* e, const char* who, const int32_t* hw_host, const lt_step_args* a, int use_cfg, PackedCall* pc, hipStream_t s) {
+    const lt_config& c = e->cfg;
+    const int B = a->batch;
+    LT_REQUIRE(c.variant == LT_VARIANT_NEXT_T2I, "%s: packed batches run on the text-conditional Next-DiT (LT_VARIANT_NEXT_T2I) only; this engine is variant %d",
+               who, c.variant);
+    LT_REQUIRE(B >= 1 && B <= LT_PK_MAX && B <= c.max_batch, "%s: packed batch of %d samples exceeds max_batch %d (or %d)", who, B, c.max_batch, LT_PK_MAX);
+    LT_REQUIRE(!use_cfg || B % 2 == 0, "%s: guidance needs an even batch (cond + uncond rows), got %d", who, B);
+    LT_REQUIRE(a->io_dtype == LT_BF16 || a->io_dtype == LT_F32, "%s: io_dtype must be bf16 or f32", who);
+    PackedTable t;
+    int hp = 0, wp = 0;
+    if (int rc = packed_table_build(hw_host, B, c.in_channels, c.patch_size, &t, &pc->elems, &pc->n_max, &hp, &wp)) return rc;
+    if (use_cfg)
+        for (int b = 0; b < B / 2; ++b)
+            LT_REQUIRE(hw_host[2 * b] == hw_host[2 * (b + B / 2)] && hw_host[2 * b + 1] == hw_host[2 * (b + B / 2) + 1],
+                       "%s: the two halves differ in size: sample %d is %dx%d, sample %d is %dx%d", who, b, hw_host[2 * b], hw_host[2 * b + 1], b + B / 2,
+                       hw_host[2 * (b + B / 2)], hw_host[2 * (b + B / 2) + 1]);
+    LT_REQUIRE(pc->n_max <= c.max_tokens, "%s: the longest sample has %d latent tokens, max_tokens is %d", who, pc->n_max, c.max_tokens);
+    LT_REQUIRE(hp <= e->rope_len && wp <= e->rope_len, "%s: a latent grid of %dx%d tokens exceeds the RoPE table (%d)", who, hp, wp, e->rope_len);
+    LT_REQUIRE(e->reg_Y == 0, "%s: a regional prompt is prepared (lt_prepare_prompt_regional): regional captions take one image per call, tensor input", who);
+    LT_REQUIRE(e->prompt_B == B, "%s: lt_prepare_prompt was called for batch %d, step has batch %d", who, e->prompt_B, B);
+    float unused;
+    if (softmax_scale_for(e, a, pc->n_max, &unused)) return 1;
+    pc->hw = hw_host;
+    if (!e->pk_tab) LT_CHECK_HIP(hipMalloc((void**)&e->pk_tab, sizeof(PackedTable)));
+    return launch_packed_table_store(t, e->pk_tab, s);
+}
+
+extern "C" int lt_forward_cfg_packed(lt_engine* e, const void* x_flat_dev, const int32_t* hw_host, const float* t_dev, void* out_flat_dev,
+                                     const lt_step_args* a, void* stream) {
+    LT_REQUIRE(e && x_flat_dev && hw_host && t_dev && out_flat_dev && a, "lt_forward_cfg_packed: null argument");
+    LtOptScope opt_scope(&e->opts);
+    PackedCall pc{};
+    if (int rc = packed_call_begin(e, "lt_forward_cfg_packed", hw_host, a, 1, &pc, (hipStream_t)stream)) return rc;
+    return forward_graphed(e, x_flat_dev, t_dev, out_flat_dev, a, 1, (hipStream_t)stream, &pc);
 }
 
 extern "C" int lt_forward_cfg(lt_engine* e, const void* x_dev, const float* t_dev, void* out_dev, const lt_step_args* a, void* stream) {

@@ -390,5 +390,24 @@ int launch_rope_table_2d(float* out, int len, int hd, float theta, float scale_f
 int launch_rope_table(float* out, int len, int hd, int step, float theta0, float lin0, float theta1, float lin1,
                       int lin_on_pos, hipStream_t stream, float* out_t = nullptr);  // out_t: the same as [b][fi][pos]
 int launch_fill_rows_bf16(u16* dst, const u16* row, long long rows, int d, hipStream_t stream);
+// packed (variable-resolution) batches on one flat state buffer (packed.hip): sample b = [C, H_b, W_b] at element offset sum_{j<b} C H_j W_j.
+// The table: LT_PK_ROWS rows of LT_PK_MAX ints, row r of sample b at v[r * LT_PK_MAX + b].
+constexpr int LT_PK_MAX = 64, LT_PK_ROWS = 5;
+constexpr int LT_PK_OFF = 0, LT_PK_H = 1, LT_PK_W = 2, LT_PK_NTOK = 3, LT_PK_GW = 4;  // element offset, H_b, W_b, token count, grid width
+struct PackedTable { int v[LT_PK_ROWS * LT_PK_MAX]; };
+// host: the table of hw = [B][2] latent sizes (refuses B outside 1..LT_PK_MAX and a size that is not a positive multiple of the patch size);
+// elems = length of the flat state, n_max = longest sequence, hp_max / wp_max = largest token grid (each may be null)
+int packed_table_build(const int32_t* hw, int B, int C, int patch, PackedTable* t, long long* elems, int* n_max, int* hp_max, int* wp_max);
+// the table -> LT_PK_ROWS * LT_PK_MAX ints of device memory, as one launch (the table is the kernel's argument)
+int launch_packed_table_store(const PackedTable& t, int* tab_dev, hipStream_t stream);
+// one launch for all samples each; N = token rows per sample (>= the longest sequence), tab_dev = the device table
+//   patchify: flat state -> patch rows [B * N, kpad] (rows behind a sample's last token untouched); dup_first_half as launch_patchify
+//   fill_pad: rows ntok_b .. N - 1 of every sample of x [B * N, d] = pad_token
+//   unpatchify: launch_unpatchify_cfg's arithmetic and rounding points, written to the flat layout
+int launch_patchify_packed(const void* x, int x_dtype, u16* out, const int* tab_dev, int B, int C, int patch, int kpad, int N, int dup_first_half,
+                           hipStream_t stream);
+int launch_fill_pad_packed(u16* x, const u16* pad_token, const int* tab_dev, int B, int N, int d, hipStream_t stream);
+int launch_unpatchify_packed(const u16* rows, int ld, void* out, int out_dtype, const int* tab_dev, int B, int C, int out_ch, int patch, int N,
+                             int use_cfg, float cfg_scale, int cfg_channels, hipStream_t stream);
 // in-place conversion of a dense [rows][cols] bf16 matrix to (to_pair 1) / from (0) the row-pair-interleaved layout of GemmArgs::pair_ab
 int launch_pair_layout(u16* m, long long rows, int cols, int to_pair, hipStream_t stream);

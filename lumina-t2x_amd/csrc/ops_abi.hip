@@ -2,6 +2,7 @@
 // the two launches the engine makes back to back) from plain arguments, for the parity tests and the operator benchmarks.  None of them
 // touches an engine object; they see the process-default options (lt_set_option).
 #include <cstdio>
+#include <cstring>
 
 #include "../../include/lumina_dit.h"
 #include "../../include/lumina_dit_debug.h"
@@ -615,4 +616,53 @@ extern "C" int lt_op_moe_route(const void* x, const void* gate_w, const void* fo
     m.rows = rows; m.rows_per_sample = rows_per_sample; m.d = d; m.E = E;
     m.sel = (int*)sel; m.wts = (u16*)wts; m.pos = nullptr; m.src = nullptr; m.tile_expert = nullptr; m.max_tiles = max_tiles;
     return launch_moe_route(m, (hipStream_t)stream);
+}
+
+// ---- the ragged boundary kernels of a packed batch (packed.hip) for tests/test_gpu_packed_ops.py.  hw_host = [B][2] latent sizes; the entry
+// builds the table, stores it at tab_dev (LT_PK_ROWS * LT_PK_MAX ints of device memory) and launches the kernel on it.  N = token rows per sample.
+extern "C" int lt_op_packed_table(const int32_t* hw_host, int32_t B, int32_t C, int32_t patch, int32_t* table_host, int64_t* elems, int32_t* n_max) {
+    LT_REQUIRE(hw_host && table_host, "lt_op_packed_table: null argument");
+    PackedTable t;
+    long long n = 0;
+    int nm = 0;
+    if (int rc = packed_table_build(hw_host, B, C, patch, &t, &n, &nm, nullptr, nullptr)) return rc;
+    memcpy(table_host, t.v, sizeof(t.v));
+    if (elems) *elems = n;
+    if (n_max) *n_max = nm;
+    return 0;
+}
+namespace {
+int packed_op_table(const char* who, const int32_t* hw_host, int B, int C, int patch, int N, void* tab_dev, hipStream_t s) {
+    LT_REQUIRE(hw_host && tab_dev, "%s: null argument", who);
+    PackedTable t;
+    int nm = 0;
+    if (int rc = packed_table_build(hw_host, B, C, patch, &t, nullptr, &nm, nullptr, nullptr)) return rc;
+    LT_REQUIRE(N >= nm, "%s: %d token rows per sample, the longest sample has %d", who, N, nm);
+    return launch_packed_table_store(t, (int*)tab_dev, s);
+}
+}  // namespace
+extern "C" int lt_op_patchify_packed(const void* x_flat, int32_t x_dtype, void* out, const int32_t* hw_host, void* tab_dev, int32_t B, int32_t C,
+                                     int32_t patch, int32_t kpad, int32_t N, int32_t dup_first_half, void* stream) {
+    if (int rc = packed_op_table("lt_op_patchify_packed", hw_host, B, C, patch, N, tab_dev, (hipStream_t)stream)) return rc;
+    if (dup_first_half)
+        for (int b = 0; b < B / 2; ++b)
+            LT_REQUIRE(hw_host[2 * b] == hw_host[2 * (b + B / 2)] && hw_host[2 * b + 1] == hw_host[2 * (b + B / 2) + 1],
+                       "lt_op_patchify_packed: samples %d and %d of the two halves differ in size", b, b + B / 2);
+    return launch_patchify_packed(x_flat, x_dtype, (u16*)out, (const int*)tab_dev, B, C, patch, kpad, N, dup_first_half, (hipStream_t)stream);
+}
+extern "C" int lt_op_fill_pad_packed(void* x, const void* pad_token, const int32_t* hw_host, void* tab_dev, int32_t B, int32_t patch, int32_t N,
+                                     int32_t d, void* stream) {
+    if (int rc = packed_op_table("lt_op_fill_pad_packed", hw_host, B, 1, patch, N, tab_dev, (hipStream_t)stream)) return rc;
+    return launch_fill_pad_packed((u16*)x, (const u16*)pad_token, (const int*)tab_dev, B, N, d, (hipStream_t)stream);
+}
+extern "C" int lt_op_unpatchify_packed(const void* rows, int32_t ld, void* out_flat, int32_t out_dtype, const int32_t* hw_host, void* tab_dev,
+                                       int32_t B, int32_t C, int32_t out_ch, int32_t patch, int32_t N, int32_t use_cfg, float cfg_scale,
+                                       int32_t cfg_channels, void* stream) {
+    if (int rc = packed_op_table("lt_op_unpatchify_packed", hw_host, B, C, patch, N, tab_dev, (hipStream_t)stream)) return rc;
+    if (use_cfg)
+        for (int b = 0; b < B / 2; ++b)
+            LT_REQUIRE(hw_host[2 * b] == hw_host[2 * (b + B / 2)] && hw_host[2 * b + 1] == hw_host[2 * (b + B / 2) + 1],
+                       "lt_op_unpatchify_packed: samples %d and %d of the two halves differ in size", b, b + B / 2);
+    return launch_unpatchify_packed((const u16*)rows, ld, out_flat, out_dtype, (const int*)tab_dev, B, C, out_ch, patch, N, use_cfg, cfg_scale,
+                                    cfg_channels, (hipStream_t)stream);
 }

@@ -35,6 +35,7 @@ struct Trajectory {
     void* traj = nullptr;
     int cur = 0;
     long long nfe = 0;
+    const PackedCall* pc = nullptr;  // a packed batch: the states are flat buffers (lt_sample_ode_packed)
     int start(const void* z, void* traj_dev, bool z_in_slot0) {
         traj = traj_dev;
         LT_CHECK_HIP(hipMemcpyAsync(e->ys[0], z, sbytes, hipMemcpyDeviceToDevice, s));
@@ -44,7 +45,7 @@ struct Trajectory {
     void* y0() const { return e->ys[cur]; }      // the current state
     void* y1() const { return e->ys[cur ^ 1]; }  // where the step writes the next one
     // one model evaluation at stage time number `call` of the committed table
-    int eval(const void* y, int call, void* out) { ++nfe; return forward_graphed(e, y, e->times.dev + (size_t)call * a->batch, out, a, use_cfg, s); }
+    int eval(const void* y, int call, void* out) { ++nfe; return forward_graphed(e, y, e->times.dev + (size_t)call * a->batch, out, a, use_cfg, s, pc); }
     int advance(int traj_slot) {  // y1 is the current state now [and slot `traj_slot` of the record]
         if (traj) LT_CHECK_HIP(hipMemcpyAsync((char*)traj + (size_t)traj_slot * sbytes, y1(), sbytes, hipMemcpyDeviceToDevice, s));
         cur ^= 1;
@@ -66,21 +67,14 @@ float bf16_round_host(float f) {
     return f;
 }
 
-}  // namespace
-
-extern "C" int lt_sample_ode(lt_engine* e, const void* z_dev, void* traj_dev, void* final_dev, const float* tgrid_host,
-                             int32_t n_grid, int32_t method, int32_t use_cfg, int32_t t_round, const lt_step_args* a,
-                             void* stream) {
-    LT_REQUIRE(e && z_dev && tgrid_host && a, "lt_sample_ode: null argument");
-    LtOptScope opt_scope(&e->opts);
-    LT_REQUIRE(n_grid >= 2, "lt_sample_ode: need at least 2 grid points");
-    LT_REQUIRE(method >= LT_ODE_EULER && method <= LT_ODE_RK4, "lt_sample_ode: unknown method %d", method);
-    hipStream_t s = (hipStream_t)stream;
+// The fixed-grid loop of lt_sample_ode and lt_sample_ode_packed: stage-time fill and the euler / midpoint / rk4 stepping body on a state of
+// n elements (the stage arithmetic is elementwise, so a packed batch's flat state runs through it as it is).  The callers have validated
+// the grid, the method and the shape.
+int ode_fixed_grid(lt_engine* e, const void* z_dev, void* traj_dev, void* final_dev, const float* tgrid_host, int n_grid, int method, int use_cfg,
+                   int t_round, const lt_step_args* a, hipStream_t s, long long n, const PackedCall* pc) {
     const int B = a->batch;
-    if (check_step_shape(e, "lt_sample_ode", a)) return 2;
     const int stages = method == LT_ODE_EULER ? 1 : (method == LT_ODE_MIDPOINT ? 2 : 4);
     const int ncalls = (n_grid - 1) * stages;
-    const long long n = (long long)B * e->cfg.in_channels * a->latent_h * a->latent_w;
     const bool bf = a->io_dtype == LT_BF16;
     // stage times; torchdiffeq's _PerturbFunc casts t to the state dtype before calling the model, then
     // integrators.py:108 broadcasts it to an fp32 [B] vector
@@ -102,6 +96,7 @@ extern "C" int lt_sample_ode(lt_engine* e, const void* z_dev, void* traj_dev, vo
     }
     if (e->times.commit(ncalls * B, s)) return 1;
     Trajectory tr{e, a, use_cfg, s, (size_t)n * (bf ? 2 : 4)};
+    tr.pc = pc;
     if (tr.start(z_dev, traj_dev, true)) return 1;
     const int dt_code = bf ? 1 : 0;
     for (int i = 0; i + 1 < n_grid; ++i) {
@@ -132,6 +127,34 @@ extern "C" int lt_sample_ode(lt_engine* e, const void* z_dev, void* traj_dev, vo
         if (tr.advance(i + 1)) return 1;
     }
     return tr.finish(final_dev);
+}
+
+}  // namespace
+
+extern "C" int lt_sample_ode(lt_engine* e, const void* z_dev, void* traj_dev, void* final_dev, const float* tgrid_host,
+                             int32_t n_grid, int32_t method, int32_t use_cfg, int32_t t_round, const lt_step_args* a,
+                             void* stream) {
+    LT_REQUIRE(e && z_dev && tgrid_host && a, "lt_sample_ode: null argument");
+    LtOptScope opt_scope(&e->opts);
+    LT_REQUIRE(n_grid >= 2, "lt_sample_ode: need at least 2 grid points");
+    LT_REQUIRE(method >= LT_ODE_EULER && method <= LT_ODE_RK4, "lt_sample_ode: unknown method %d", method);
+    if (check_step_shape(e, "lt_sample_ode", a)) return 2;
+    const long long n = (long long)a->batch * e->cfg.in_channels * a->latent_h * a->latent_w;
+    return ode_fixed_grid(e, z_dev, traj_dev, final_dev, tgrid_host, n_grid, method, use_cfg, t_round, a, (hipStream_t)stream, n, nullptr);
+}
+
+// lt_sample_ode on a packed batch: z, every trajectory slot and the final state are flat buffers of the size list's layout (packed.hip)
+extern "C" int lt_sample_ode_packed(lt_engine* e, const void* z_flat_dev, const int32_t* hw_host, void* traj_flat_dev, void* final_flat_dev,
+                                    const float* tgrid_host, int32_t n_grid, int32_t method, int32_t use_cfg, int32_t t_round, const lt_step_args* a,
+                                    void* stream) {
+    LT_REQUIRE(e && z_flat_dev && hw_host && tgrid_host && a, "lt_sample_ode_packed: null argument");
+    LtOptScope opt_scope(&e->opts);
+    LT_REQUIRE(n_grid >= 2, "lt_sample_ode_packed: need at least 2 grid points");
+    LT_REQUIRE(method >= LT_ODE_EULER && method <= LT_ODE_RK4, "lt_sample_ode_packed: unknown method %d", method);
+    PackedCall pc{};
+    if (int rc = packed_call_begin(e, "lt_sample_ode_packed", hw_host, a, use_cfg, &pc, (hipStream_t)stream)) return rc;
+    return ode_fixed_grid(e, z_flat_dev, traj_flat_dev, final_flat_dev, tgrid_host, n_grid, method, use_cfg, t_round, a, (hipStream_t)stream, pc.elems,
+                          &pc);
 }
 
 // ---- multi-view (visual-anagram) sampling ------------------------------------------------------------------------------------------

@@ -261,6 +261,44 @@ class DiTEngine:
         _lib.check(rc, "lt_forward_packed")
         return outs
 
+    def _pack(self, xs, what: str):
+        """a list of [C, H_b, W_b] samples as ONE flat buffer in the engine's packed layout (sample b at element offset
+        sum_{j<b} C H_j W_j), the host size list [B][2] and the (offset, shape) of every sample"""
+        xs = list(xs)
+        if not xs:
+            raise LuminaLibError(f"{what}: empty sample list")
+        for x in xs:
+            _require_gpu(x, "x")
+            if x.dim() != 3 or x.shape[0] != self.in_channels or x.dtype != xs[0].dtype or x.device != xs[0].device:
+                raise LuminaLibError(f"{what}: every sample must be a [{self.in_channels}, H, W] tensor of one dtype on one device")
+        flat = torch.cat([x.reshape(-1) for x in xs])
+        hw = (C.c_int32 * (2 * len(xs)))(*[int(v) for x in xs for v in x.shape[1:]])
+        spans, off = [], 0
+        for x in xs:
+            spans.append((off, tuple(x.shape)))
+            off += x.numel()
+        return flat, hw, spans
+
+    def _packed_step_args(self, flat: torch.Tensor, B: int, cfg_scale, scale_factor, scale_watershed, base_seqlen, proportional_attn) -> LtStepArgs:
+        a = self._step_args(flat.view(1, 1, 1, -1), cfg_scale, scale_factor, scale_watershed, base_seqlen, proportional_attn)
+        a.batch, a.latent_h, a.latent_w = B, 0, 0
+        return a
+
+    def forward_cfg_packed(self, xs, t: torch.Tensor, *, cfg_scale: float = 1.0, scale_factor: float = 1.0, scale_watershed: float = 1.0,
+                           base_seqlen: Optional[int] = None, proportional_attn: bool = False):
+        """forward_with_cfg on a LIST of 2 B' samples ``[C, H_b, W_b]`` with ``xs[b].shape == xs[b + B'].shape`` (lt_forward_cfg_packed): the
+        reference's list ``forward`` on ``[x_0 .. x_{B'-1}] * 2`` followed by the guidance expression of model.py:901-913 per sample.
+        Returns a list of 2 B' tensors, views of one allocation."""
+        flat, hw, spans = self._pack(xs, "forward_cfg_packed")
+        t32 = t.to(device=flat.device, dtype=torch.float32).contiguous()
+        out = torch.empty_like(flat)
+        a = self._packed_step_args(flat, len(spans), cfg_scale, scale_factor, scale_watershed, base_seqlen, proportional_attn)
+        with torch.cuda.device(self.device):
+            rc = self.lib.lt_forward_cfg_packed(self.handle, C.c_void_p(flat.data_ptr()), hw, C.c_void_p(t32.data_ptr()),
+                                                C.c_void_p(out.data_ptr()), C.byref(a), C.c_void_p(_stream_ptr(self.device)))
+        _lib.check(rc, "lt_forward_cfg_packed")
+        return [out[off:off + math.prod(shape)].view(shape) for off, shape in spans]
+
     # ---- whole trajectory -------------------------------------------------------------------------
     def sample_ode(self, z: torch.Tensor, tgrid: torch.Tensor, method: str, *, use_cfg: bool, cfg_scale: float = 1.0,
                    scale_factor: float = 1.0, scale_watershed: float = 1.0, base_seqlen: Optional[int] = None,
@@ -279,6 +317,26 @@ class DiTEngine:
                                         C.c_void_p(_stream_ptr(self.device)))
         _lib.check(rc, "lt_sample_ode")
         return out
+
+    def sample_ode_packed(self, zs, tgrid, method: str, *, use_cfg: bool, cfg_scale: float = 1.0, scale_factor: float = 1.0,
+                          scale_watershed: float = 1.0, base_seqlen: Optional[int] = None, proportional_attn: bool = False,
+                          t_round_to_state_dtype: bool = True, return_trajectory: bool = True):
+        """the fixed-grid trajectory of a LIST of differently sized latents in ONE call (lt_sample_ode_packed): every evaluation is the packed
+        forward_with_cfg (``use_cfg``: 2 B' samples, halves of equal sizes) or the packed forward.  Returns one tensor per sample -
+        ``[n_grid, C, H_b, W_b]`` or the last state ``[C, H_b, W_b]`` - all views of one allocation."""
+        if method not in _lib.ODE_METHODS:
+            raise LuminaLibError(f"fixed-grid method '{method}' not in {sorted(_lib.ODE_METHODS)}")
+        flat, hw, spans = self._pack(zs, "sample_ode_packed")
+        garr, n = _grid_array(tgrid)
+        a = self._packed_step_args(flat, len(spans), cfg_scale, scale_factor, scale_watershed, base_seqlen, proportional_attn)
+        out, traj_ptr, fin_ptr = _traj_or_final(flat, n, flat.shape, return_trajectory)
+        with torch.cuda.device(self.device):
+            rc = self.lib.lt_sample_ode_packed(self.handle, C.c_void_p(flat.data_ptr()), hw, traj_ptr, fin_ptr, garr, n, _lib.ODE_METHODS[method],
+                                               int(use_cfg), int(t_round_to_state_dtype), C.byref(a), C.c_void_p(_stream_ptr(self.device)))
+        _lib.check(rc, "lt_sample_ode_packed")
+        if return_trajectory:
+            return [out[:, off:off + math.prod(shape)].view((n,) + shape) for off, shape in spans]
+        return [out[off:off + math.prod(shape)].view(shape) for off, shape in spans]
 
     def sample_ode_adaptive(self, z: torch.Tensor, tgrid: torch.Tensor, method: str, *, rtol: float, atol: float,
                             first_step: Optional[float] = None, max_steps: int = 2 ** 31 - 1, use_cfg: bool, cfg_scale: float = 1.0,

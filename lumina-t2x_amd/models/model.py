@@ -221,6 +221,39 @@ class NextDiT(EngineSamplers, WeightWatch, nn.Module):
         return self._call(x, t, cap_feats, cap_mask, True, cfg_scale=cfg_scale, scale_factor=scale_factor,
                           scale_watershed=scale_watershed, base_seqlen=base_seqlen, proportional_attn=proportional_attn)
 
+    def _packed_cfg_engine(self, xs, cap_feats, cap_mask, base_seqlen, proportional_attn):
+        xs = list(xs)
+        if len(xs) != cap_feats.shape[0]:
+            raise _lib.LuminaLibError(f"packed guidance: {len(xs)} samples (cond rows, then uncond rows) need as many prompt rows, got "
+                                      f"{cap_feats.shape[0]}")
+        if proportional_attn:
+            assert base_seqlen is not None
+        for layer in self.layers:  # mirrored attributes (reference model.py:891-899)
+            layer.attention.base_seqlen = base_seqlen if proportional_attn else None
+            layer.attention.proportional_attn = proportional_attn
+        eng = self.engine(xs, cap_feats.shape[1])
+        eng.prepare_prompt(cap_feats, cap_mask)
+        return eng, xs
+
+    @torch.no_grad()
+    def forward_with_cfg_packed(self, xs, t, cap_feats, cap_mask, cfg_scale, scale_factor=1.0, scale_watershed=1.0,
+                                base_seqlen: Optional[int] = None, proportional_attn: bool = False):
+        """forward_with_cfg on a LIST of 2 B' latents ``[C, H_b, W_b]`` (cond rows, then uncond rows of the same sizes): the reference's list
+        ``forward`` (model.py:789-834) on ``[x_0 .. x_{B'-1}] * 2`` and the guidance expression of :901-913 per sample.  Returns a list."""
+        eng, xs = self._packed_cfg_engine(xs, cap_feats, cap_mask, base_seqlen, proportional_attn)
+        return eng.forward_cfg_packed(xs, t, cfg_scale=cfg_scale, scale_factor=scale_factor, scale_watershed=scale_watershed,
+                                      base_seqlen=base_seqlen, proportional_attn=proportional_attn)
+
+    @torch.no_grad()
+    def sample_ode_packed(self, zs, tgrid, cap_feats, cap_mask, cfg_scale, method: str = "midpoint", return_trajectory: bool = False,
+                          scale_factor=1.0, scale_watershed=1.0, base_seqlen: Optional[int] = None, proportional_attn: bool = False):
+        """the fixed-grid ODE trajectory of a LIST of differently sized latents in ONE engine call, every evaluation
+        ``forward_with_cfg_packed``.  Returns one tensor per sample: the last state, or ``[len(tgrid), C, H_b, W_b]``."""
+        eng, zs = self._packed_cfg_engine(zs, cap_feats, cap_mask, base_seqlen, proportional_attn)
+        return eng.sample_ode_packed(zs, tgrid, method, use_cfg=True, cfg_scale=cfg_scale, scale_factor=scale_factor,
+                                     scale_watershed=scale_watershed, base_seqlen=base_seqlen, proportional_attn=proportional_attn,
+                                     return_trajectory=return_trajectory)
+
     def _engine_sampler_args(self, x, use_cfg, kw):
         """transport fast paths (models/_base.py: EngineSamplers): kwargs of forward_with_cfg / forward -> engine + step kwargs"""
         cap_feats, cap_mask = kw.pop("cap_feats"), kw.pop("cap_mask")
