@@ -478,6 +478,26 @@ int lt_op_attention(const void* q_dev, const void* k_dev, const void* vt_dev, co
  * "attn_fwd_kernel<128>" otherwise. */
 int lt_op_attention_describe(int32_t has_bias, int32_t accumulate, int32_t B, int32_t H, int32_t Hkv, int32_t N, int32_t Nk, int32_t Nkpad,
                              int32_t hd, char* out, int32_t cap);
+/* lt_op_attention / lt_op_attention_fused / lt_op_attention_describe with per-sample key counts (the packed variable-resolution batches of
+ * lt_forward_packed) and the pair layout of the output.
+ *   nk_dev   DEVICE int32 [B] or NULL (NULL: the plain entry's launch): sample b attends its first nk_dev[b] image keys; Nk stays the layout
+ *            stride of k [B,Hkv,Nk,hd] and vt [B,Hkv,hd,Nkpad] and must be a multiple of 64 here.  The caller's contract (a launch cannot
+ *            read a device array): 1 <= nk_dev[b] <= Nk, and the K rows / V^T columns of the masked keys hold FINITE words - a masked key's
+ *            weight is an exact zero, but 0 x NaN is not zero.  The text keys of the fused form keep tbias; nk_dev bounds the image keys only.
+ *            head_dim 72 under attention_variant 4: the one-wave kernel (bit-identical to attention_variant 3); other head dims: the
+ *            kernels that take a key bias.
+ *   out_pair != 0: out [B*N, H*hd] in the row-pair-interleaved layout of lt_op_pair_layout (one-wave kernels only; B*N even).
+ *   describe: has_nk / has_text as nk_dev != NULL / text keys given (Tkpad of them, padded); the kernel name under the current options.
+ *            Both instantiations of the head_dim-72 one-wave kernel are named "attn_fwd_kernel_v4<72>". */
+int lt_op_attention_nk(const void* q_dev, const void* k_dev, const void* vt_dev, const float* bias_dev, void* out_dev, const void* gate_dev,
+                       int32_t accumulate, int32_t B, int32_t H, int32_t Hkv, int32_t N, int32_t Nk, int32_t Nkpad, int32_t hd, float scale,
+                       int32_t k_prescaled, const int32_t* nk_dev, int32_t out_pair, void* stream);
+int lt_op_attention_fused_nk(const void* q_dev, const void* k_dev, const void* vt_dev, const void* tk_dev, const void* tvt_dev,
+                             const float* tbias_dev, const void* tgate_dev, void* out_dev, int32_t B, int32_t H, int32_t Hkv, int32_t N,
+                             int32_t Nk, int32_t Nkpad, int32_t Tk, int32_t Tkpad, int32_t hd, const int32_t* nk_dev, int32_t out_pair,
+                             void* stream);
+int lt_op_attention_nk_describe(int32_t has_bias, int32_t accumulate, int32_t B, int32_t H, int32_t Hkv, int32_t N, int32_t Nk, int32_t Nkpad,
+                                int32_t hd, int32_t has_nk, int32_t has_text, int32_t Tkpad, char* out, int32_t cap);
 /* The two launches of a layer of the class-conditional 600M models at <= 512 tokens (round 5, option attn_small_fused): the QKV
  * projection on the small-M GEMM tiles, whose epilogue also leaves per-row (sum, sum of squares) of every 128-column tile in
  * rowstat_ws ([M][ceil(3 widths / 128)] float2), then ONE kernel that does q_norm / k_norm (affine LayerNorm over the full width, fp32),

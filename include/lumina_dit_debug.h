@@ -96,7 +96,10 @@ extern "C" {
  *                       lt_op_pair_layout): the LDS-DMA stream then fetches whole 128-byte lines - half the requests into the L2, the
  *                       counter that separated this kernel from the vendor's (round 6).  The weights are converted in place when the
  *                       regime changes (a 256-token call after a 4096-token one) and before every lt_set_weight; bit-identical results
- *                       | 0: row-major everywhere
+ *                       | 0: row-major everywhere.  Packed batches (lt_forward_packed and its kin) take the regime too when their
+ *                       attention runs on the head_dim-72 one-wave kernel (longest sequence a multiple of 64).
+ *                       lt_engine_get_option(e, "last_pair", &v) - read-only, no option, e != NULL - says whether the engine's last
+ *                       evaluation ran in this regime (1) or row-major (0)
  * (the round-1 names gemm_pipeline / gemm_pp_tail / gemm_persist are accepted with value 0 only: the study kernels they selected were
  *  deleted with csrc/experimental/ in round 5) */
 
@@ -228,6 +231,14 @@ int lt_op_attention_qraw_ex(const void* qkv_dev, int32_t ld, int32_t q_col0, con
                             const void* t_dev, float watershed, const void* k_dev, const void* vt_dev, const void* tk_dev, const void* tvt_dev,
                             const float* tbias_dev, const void* tgate_dev, int32_t Tk, int32_t Tkpad, void* out_dev, int32_t B, int32_t H,
                             int32_t Hkv, int32_t N, int32_t Nkpad, int32_t hd, void* stream);
+/* lt_op_attention_qraw_ex plus per-sample key counts (nk_dev as lt_op_attention_nk, lumina_dit.h).  The combination is REFUSED by name: the
+ * prologue takes one grid_w, a packed batch has a grid width per sample (the engine keeps lt_op_qk_norm_rope's per-sample form for Q there).
+ * nk_dev NULL: lt_op_attention_qraw_ex.  The entry exists so that tests/test_gpu_attention_nk.py can reach that refusal; nothing else calls it. */
+int lt_op_attention_qraw_nk(const void* qkv_dev, int32_t ld, int32_t q_col0, const void* q_mean_rstd_dev, const void* q_ln_w_dev,
+                            const void* q_ln_b_dev, const void* cs_table_dev, const void* cs_table_t_dev, int32_t table_len, int32_t grid_w,
+                            const void* t_dev, float watershed, const void* k_dev, const void* vt_dev, const void* tk_dev, const void* tvt_dev,
+                            const float* tbias_dev, const void* tgate_dev, int32_t Tk, int32_t Tkpad, void* out_dev, int32_t B, int32_t H,
+                            int32_t Hkv, int32_t N, int32_t Nkpad, int32_t hd, const int32_t* nk_dev, void* stream);
 int lt_op_attention_small(const void* qkv_dev, int32_t ld, int32_t q_col0, int32_t k_col0, int32_t v_col0, const void* rowstat_dev, int32_t slots,
                           int32_t q_slot0, int32_t q_nslot, int32_t k_slot0, int32_t k_nslot, const void* q_ln_w_dev, const void* q_ln_b_dev,
                           const void* k_ln_w_dev, const void* k_ln_b_dev, const void* cs_table_dev, int32_t table_len, int32_t grid_w,

@@ -145,6 +145,9 @@ _SIGNATURES: Dict[str, tuple] = {
     "lt_op_qkv_attention_small": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _f32, _vp, _vp, _vp]),
     "lt_op_attention_describe": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, C.c_char_p, _i32]),
     "lt_op_attention_fused": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "lt_op_attention_nk": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _vp, _i32, _vp]),
+    "lt_op_attention_fused_nk": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp]),
+    "lt_op_attention_nk_describe": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, C.c_char_p, _i32]),
     "lt_op_attention_trace": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp]),
     "lt_op_views_invert": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp]),
     "lt_op_views_gather": (_i32, [_vp, _vp, _vp, _vp, _vp, _f32, _i32, _i32, _i32, _i32, _vp]),
@@ -184,6 +187,8 @@ _SIGNATURES: Dict[str, tuple] = {
     "lt_op_attention_qraw": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "lt_op_attention_qraw_ex": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp,
                                        _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "lt_op_attention_qraw_nk": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp,
+                                       _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "lt_op_attention_small": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _f32,
                                      _f32, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "lt_op_rmsnorm_mod_ex": (_i32, [_vp, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _f32, _i32, _i32, _vp]),

@@ -971,18 +971,22 @@ using lt_attn::attn_fwd_kernel_v3;
 // true when launch_attention() can take the text keys along with the image keys (one kernel instead of two)
 bool attention_fuses_text(int hd) { return lt_opt(OPT_ATTENTION_VARIANT) >= 3 && (hd == 72 || hd == 96); }
 
-// the dispatch condition of attn_fwd_kernel_v4<72> (launch_attention below uses the same expression)
-bool attention_takes_raw_q(const AttnArgs& a) {
-    return lt_opt(OPT_ATTENTION_VARIANT) >= 4 && a.hd == 72 && a.bias == nullptr && !a.accumulate && !a.nk_batch && a.Nk % 64 == 0 &&
-           (!a.tk || a.Tkpad <= 256);
+// THE dispatch condition of attn_fwd_kernel_v4<72>, with or without per-sample key counts (launch_attention, attention_is_one_wave, attention_describe
+// and launch_attention_v4 all ask this one function)
+bool attention_one_wave_hd72(const AttnArgs& a) {
+    return lt_opt(OPT_ATTENTION_VARIANT) >= 4 && a.hd == 72 && a.bias == nullptr && !a.accumulate && a.Nk % 64 == 0 && (!a.tk || a.Tkpad <= 256);
 }
+
+// ... and without per-sample key counts: the
+// prologue takes ONE rope_grid_w, a packed batch has a grid width per sample (qk_norm_rope keeps doing Q there: QkPostArgs::grid_w_b)
+bool attention_takes_raw_q(const AttnArgs& a) { return attention_one_wave_hd72(a) && !a.nk_batch; }
 
 // launch_attention would run this call on one of the one-wave-per-SIMD kernels (hd 72 / 48 / 96: the ones that can write their output in the
 // pair layout, AttnArgs::out_pair) - the same expressions as the dispatch below.  hd 128 is not among them: attention_hd128.hip's kernel
 // (two waves per SIMD) writes row-major rows, so the 7B's dense block keeps row-major GEMM operands (run_forward's `pair` stays false)
 bool attention_is_one_wave(const AttnArgs& a) {
     const int g_attn_variant = lt_opt(OPT_ATTENTION_VARIANT);
-    if (g_attn_variant >= 4 && a.hd == 72 && a.bias == nullptr && !a.accumulate && !a.nk_batch && a.Nk % 64 == 0 && (!a.tk || a.Tkpad <= 256)) return true;
+    if (attention_one_wave_hd72(a)) return true;
     if (g_attn_variant >= 4 && a.hd == 48 && a.bias == nullptr && !a.accumulate && !a.nk_batch && !a.trace && a.Nk % 64 == 0 && !a.tk &&
         (g_attn_variant == 6 || (long long)a.B * a.H * ((a.N + 255) / 256) >= 200)) return true;
     if (g_attn_variant >= 4 && a.hd == 96 && a.bias == nullptr && !a.accumulate && !a.nk_batch && !a.trace && a.Nk % 64 == 0 && a.Nk == a.Nkpad &&
@@ -993,6 +997,8 @@ bool attention_is_one_wave(const AttnArgs& a) {
 int launch_attention(const AttnArgs& a, hipStream_t stream) {
     const int g_attn_variant = lt_opt(OPT_ATTENTION_VARIANT);
     LT_REQUIRE(a.H % a.Hkv == 0, "attention: H=%d not a multiple of Hkv=%d", a.H, a.Hkv);
+    LT_REQUIRE(a.q_raw == nullptr || a.nk_batch == nullptr,
+               "attention: q_raw with nk_batch (per-sample key counts) is not built: the prologue takes one rope_grid_w, packed batches have one per sample");
     LT_REQUIRE(a.q_raw == nullptr || (attention_takes_raw_q(a) && a.q_stat && a.q_ln_w && a.q_ln_b && a.rope_cs && a.rope_cs_t && a.rope_grid_w > 0 && a.rope_cs_len > 0),
                "attention: q_raw (q_norm + RoPE in the prologue) needs the head_dim-72 one-wave kernel's conditions and the LayerNorm / RoPE inputs");
     LT_REQUIRE(a.q_raw == nullptr || ((a.N - 1) / a.rope_grid_w < a.rope_cs_len && a.rope_grid_w <= a.rope_cs_len),
@@ -1012,7 +1018,8 @@ int launch_attention(const AttnArgs& a, hipStream_t stream) {
                    "attention: incomplete fused text arguments");
     }
     // variant 4: one wave per SIMD, 64 query rows per wave (attention_v4.hip); whole 64-key tiles and <= 256 text keys, else the ping-pong kernel
-    if (g_attn_variant >= 4 && a.hd == 72 && a.bias == nullptr && !a.accumulate && !a.nk_batch && a.Nk % 64 == 0 && (!a.tk || a.Tkpad <= 256))
+    // (nk_batch, per-sample key counts: its second instantiation; the hd 48 / 96 / 128 one-wave kernels below have none and keep refusing it)
+    if (attention_one_wave_hd72(a))
         return launch_attention_v4(a, stream);
     // ... its head_dim 48 form (attention_v4_48.hip, round 4: the 600M ImageNet / MoE models)
     // (no text keys: no head_dim 48 model of the reference has a text branch, and the kernel's inherited text phase has no test)
@@ -1070,7 +1077,7 @@ int launch_attention(const AttnArgs& a, hipStream_t stream) {
 const char* attention_describe(const AttnArgs& a) {
     const int g_attn_variant = lt_opt(OPT_ATTENTION_VARIANT);
     if (a.hd != 48 && a.hd != 72 && a.hd != 96 && a.hd != 128) return "none";
-    if (g_attn_variant >= 4 && a.hd == 72 && a.bias == nullptr && !a.accumulate && !a.nk_batch && a.Nk % 64 == 0 && (!a.tk || a.Tkpad <= 256)) return "attn_fwd_kernel_v4<72>";
+    if (attention_one_wave_hd72(a)) return "attn_fwd_kernel_v4<72>";  // (both instantiations: with nk_batch its PerSampleKeys one)
     if (attention_is_one_wave(a)) return a.hd == 48 ? "attn_fwd_kernel_v4h48" : "attn_fwd_kernel_v4h96";
     if (attention_takes_hd128_fast(a)) return "attn_fwd_kernel_hd128";
     if (g_attn_variant >= 3 && (a.hd == 72 || a.hd == 96) && a.bias == nullptr && !a.accumulate) return a.hd == 72 ? "attn_fwd_kernel_v3<72>" : "attn_fwd_kernel_v3<96>";

@@ -524,8 +524,21 @@ int run_forward(lt_engine* e, const void* x_in, const float* t_dev, void* out, c
     // O, W1 | W3, W2) and the attention on a one-wave kernel, their A operands (h, the attention output, the SwiGLU output) and the four
     // weights are kept in the row-pair-interleaved layout (GemmArgs::pair_ab): the GEMM's LDS-DMA stream then asks the L2 for whole 128-byte
     // lines - half the requests.  Same products in the same order: bit-identical to the row-major path.
+    // Packed batches take both this regime and the V^T epilogue below when their attention call runs on a one-wave kernel (hd 72: the
+    // PerSampleKeys instantiation of attention_v4.hip) and the longest sequence is whole 64-key tiles: the pad rows' K / V words are
+    // pad_token pushed through finite weights, and the kernel gives a masked key an exact zero weight (0 x finite = 0), so nothing has
+    // to zero them.  raw_q stays off for packed batches (one rope_grid_w per launch): qk_norm_rope does Q with n_tok_b / grid_w_b.
+    AttnArgs at0;  // the layer loop's self-attention call, as far as the dispatch looks at it
+    at0.q = e->q; at0.k = e->k; at0.vt = e->vt; at0.bias = nullptr; at0.out = e->attn; at0.gate = nullptr; at0.accumulate = 0;
+    at0.B = B; at0.H = H; at0.Hkv = Hkv; at0.N = N; at0.Nk = N; at0.Nkpad = Npad; at0.hd = hd; at0.scale = sm_scale; at0.k_prescaled = 1;
+    at0.nk_batch = pk && pk->tab && pk_full ? nullptr : ntok_dev;
+    if (v.text && !(e->reg_Y > 0) && attention_fuses_text(hd)) {
+        at0.tk = e->lw[0].ky; at0.tvt = e->lw[0].vty; at0.tbias = e->txt_bias; at0.tgate = e->lw[0].gate; at0.Tk = e->prompt_T; at0.Tkpad = e->prompt_Tpad;
+    }
+    // (head_dim 72 only: a packed batch at another head dim keeps the launches it had, also when every sample has the longest length)
+    const bool pk_one_wave = pk && hd == 72 && N % 64 == 0 && attention_one_wave_hd72(at0);
     bool pair = false;
-    if (lt_opt(OPT_PAIR_LAYOUT) && e->E == 0 && !pk && M % 2 == 0 && d % 32 == 0 && F % 32 == 0 && F <= 16384 && d <= 16384 && !(v.text && e->reg_Y > 0) &&
+    if (lt_opt(OPT_PAIR_LAYOUT) && e->E == 0 && (!pk || pk_one_wave) && M % 2 == 0 && d % 32 == 0 && F % 32 == 0 && F <= 16384 && d <= 16384 && !(v.text && e->reg_Y > 0) &&
         (!v.text || attention_fuses_text(hd))) {
         GemmArgs gq;
         gq.A = e->h; gq.W = e->lw[0].wqkv; gq.C = e->qkv; gq.bias = nullptr; gq.bias_dtype = -1; gq.M = M; gq.N = d + 2 * dkv; gq.K = d;
@@ -535,11 +548,6 @@ int run_forward(lt_engine* e, const void* x_in, const float* t_dev, void* out, c
         go.A = e->attn; go.W = e->lw[0].wo; go.C = e->o; go.bias = nullptr; go.bias_dtype = -1; go.M = M; go.N = d; go.K = d; go.lda = d; go.ldw = d; go.ldc = d;
         g13 = go; g13.A = e->h; g13.W = e->lw[0].w13; g13.C = e->u; g13.N = 2 * F; g13.ldc = F;
         g2 = go; g2.A = e->u; g2.W = e->lw[0].w2; g2.K = F; g2.lda = F; g2.ldw = F;
-        AttnArgs at0;
-        at0.q = e->q; at0.k = e->k; at0.vt = e->vt; at0.bias = nullptr; at0.out = e->attn; at0.gate = nullptr; at0.accumulate = 0;
-        at0.B = B; at0.H = H; at0.Hkv = Hkv; at0.N = N; at0.Nk = N; at0.Nkpad = Npad; at0.hd = hd; at0.scale = sm_scale; at0.k_prescaled = 1;
-        at0.nk_batch = ntok_dev;
-        if (v.text) { at0.tk = e->lw[0].ky; at0.tvt = e->lw[0].vty; at0.tbias = e->txt_bias; at0.tgate = e->lw[0].gate; at0.Tk = e->prompt_T; at0.Tkpad = e->prompt_Tpad; }
         pair = vt_epi0 && lt_opt(OPT_QKV_FUSED_GEMM) && gemm_qkv_fusable(gq) && gemm_runs_w4q_dense(go, 0) && gemm_runs_w4q_dense(g13, 1) &&
                gemm_runs_w4q_dense(g2, 0) && attention_is_one_wave(at0);
     }
@@ -586,8 +594,9 @@ int run_forward(lt_engine* e, const void* x_in, const float* t_dev, void* out, c
         LayerW& w = e->lw[l];
         // V^T epilogue path: q | k columns in one GEMM, the V columns in a second one that writes e->vt directly.  Large problems
         // only (a second launch of a latency-bound 512-row GEMM costs more than the transpose), whole 64-key tiles per sample
-        // (no key padding to zero), and not for packed batches (their padded rows must read as zero keys)
-        const bool vt_epi = lt_opt(OPT_QKV_VT_EPILOGUE) && !pk && N % 64 == 0 && (long long)((M + 255) / 256) * ((dkv + 255) / 256) >= 128;
+        // (no key padding to zero); packed batches: when the attention masks their pad rows' keys itself (pk_one_wave above), else the
+        // transpose kernels
+        const bool vt_epi = lt_opt(OPT_QKV_VT_EPILOGUE) && (!pk || pk_one_wave) && N % 64 == 0 && (long long)((M + 255) / 256) * ((dkv + 255) / 256) >= 128;
         // ... and ONE launch for all three when the shapes are whole tiles of the persistent 256 x 288 kernel (lt_set_option
         // "qkv_fused_gemm"): Q | K tiles with the plain epilogue, V tiles with swapped MFMA operands and the V^T epilogue
         GemmArgs gq;
@@ -916,6 +925,7 @@ int forward_graphed(lt_engine* e, const void* x_in, const float* t_dev, void* ou
     LT_CHECK_HIP(hipMemcpyAsync(e->g_x, x_in, sbytes, hipMemcpyDeviceToDevice, s));
     LT_CHECK_HIP(hipMemcpyAsync(e->g_t, t_dev, (size_t)B * sizeof(float), hipMemcpyDeviceToDevice, s));
     LT_CHECK_HIP(hipGraphLaunch(ge->exec, s));
+    e->last_pair = ge->pair;  // (a replay is an evaluation too: "last_pair" of lt_engine_get_option names the regime of the last one)
     LT_CHECK_HIP(hipMemcpyAsync(out, e->g_out, sbytes, hipMemcpyDeviceToDevice, s));
     ++e->graph_replays;
     if (e->prof_on)
@@ -1547,6 +1557,11 @@ extern "C" int lt_engine_set_option(lt_engine* e, const char* name, int32_t valu
 
 extern "C" int lt_engine_get_option(lt_engine* e, const char* name, int32_t* value) {
     LT_REQUIRE(name && value, "lt_engine_get_option: null argument");
+    if (strcmp(name, "last_pair") == 0) {  // read-only, no option: the operand layout regime of the engine's last evaluation (lumina_dit_debug.h)
+        LT_REQUIRE(e, "lt_engine_get_option: last_pair: null engine");
+        *value = e->last_pair ? 1 : 0;
+        return 0;
+    }
     const int id = lt_opt_find(name);
     LT_REQUIRE(id >= 0, "lt_engine_get_option: unknown option '%s'", name);
     LtOptScope opt_scope(e ? &e->opts : nullptr);  // e == NULL: the process default

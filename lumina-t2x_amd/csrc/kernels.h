@@ -229,7 +229,11 @@ struct AttnArgs {
     const float* rope_t = nullptr;    // branch = rope_t[0] < rope_watershed ? 0 : 1
     float rope_watershed = 0.f;
     int rope_cs_len = 0, rope_grid_w = 0;
-    // packed variable-resolution batches (model.py:789-834): valid keys of sample b = nk_batch[b] <= Nk (device array, or null)
+    // packed variable-resolution batches (model.py:789-834): valid keys of sample b = nk_batch[b] (device array [B], or null); Nk stays
+    // the layout stride.  The caller's contract - launch_attention cannot read a device array: 1 <= nk_batch[b] <= Nk, and the K rows /
+    // V^T columns of the masked keys (nk_batch[b] .. Nk - 1) hold FINITE words: a masked key's weight is an exact zero, but 0 x NaN is
+    // not zero.  Taken by attn_fwd_kernel / _v2 / _v3 (Nk_eff) and by the hd-72 one-wave kernel (attention_v4.hip: Nk % 64 == 0, not with
+    // q_raw); the hd 48 / 96 / 128 one-wave kernels have no key count and leave such calls to the kernels above.
     const int* nk_batch = nullptr;
     // regional (compositional) text attention: key/value/bias/output batch b attends the queries of batch q_batch_map[b]
     // (several captions share one image's queries); device array [B] or null.  Masked (bias != null) kernels only.
@@ -240,6 +244,7 @@ struct AttnArgs {
 int launch_region_text_combine(u16* out, const u16* txt, const u16* gate, int Y, int N, int H, int hd, int Hp, int Wp,
                                int h_split, int w_split, hipStream_t stream);
 int launch_attention(const AttnArgs& a, hipStream_t stream);
+bool attention_one_wave_hd72(const AttnArgs& a);  // the dispatch condition of attention_v4.hip's kernel (attention.hip)
 // Fused q / k post-processing + V^T staging + attention for short sequences (attention_small.hip, round 5): one launch instead of
 // qkv_post + attention at the 600M class-conditional models' 256 tokens.  Reads the QKV projection's row-major output and the per-tile
 // LayerNorm partials its GEMM left (GemmArgs::rowstat).

@@ -384,6 +384,56 @@ extern "C" int lt_op_attention_describe(int32_t has_bias, int32_t accumulate, in
     return 0;
 }
 
+// lt_op_attention / lt_op_attention_fused with per-sample image key counts (AttnArgs::nk_batch, the packed batches of the engine) and the
+// pair layout of the output (AttnArgs::out_pair): tests/test_gpu_attention_nk.py.  nk NULL: the plain entries' launches.
+static int attention_nk_checks(const char* who, const int32_t* nk, int32_t B, int32_t H, int32_t Hkv, int32_t N, int32_t Nk, int32_t Nkpad, int32_t hd) {
+    LT_REQUIRE(B > 0 && H > 0 && Hkv > 0 && N > 0 && Nk > 0 && hd > 0 && Nkpad >= Nk, "%s: bad shape B=%d H=%d Hkv=%d N=%d Nk=%d Nkpad=%d hd=%d", who, B, H, Hkv, N,
+               Nk, Nkpad, hd);
+    LT_REQUIRE(!nk || Nk % 64 == 0, "%s: per-sample key counts need a layout of whole 64-key tiles, Nk %% 64 == 0 (Nk = %d)", who, Nk);
+    return 0;
+}
+
+extern "C" int lt_op_attention_nk(const void* q, const void* k, const void* vt, const float* bias, void* out, const void* gate, int32_t accumulate,
+                                  int32_t B, int32_t H, int32_t Hkv, int32_t N, int32_t Nk, int32_t Nkpad, int32_t hd, float scale,
+                                  int32_t k_prescaled, const int32_t* nk, int32_t out_pair, void* stream) {
+    LT_REQUIRE(q && k && vt && out, "lt_op_attention_nk: null pointer");
+    if (attention_nk_checks("lt_op_attention_nk", nk, B, H, Hkv, N, Nk, Nkpad, hd)) return 1;
+    AttnArgs a;
+    a.q = (const u16*)q; a.k = (const u16*)k; a.vt = (const u16*)vt; a.bias = bias; a.out = (u16*)out;
+    a.gate = (const u16*)gate; a.accumulate = accumulate; a.B = B; a.H = H; a.Hkv = Hkv; a.N = N; a.Nk = Nk;
+    a.Nkpad = Nkpad; a.hd = hd; a.scale = scale; a.k_prescaled = k_prescaled; a.nk_batch = nk; a.out_pair = out_pair;
+    return launch_attention(a, (hipStream_t)stream);
+}
+
+extern "C" int lt_op_attention_fused_nk(const void* q, const void* k, const void* vt, const void* tk, const void* tvt, const float* tbias,
+                                        const void* tgate, void* out, int32_t B, int32_t H, int32_t Hkv, int32_t N, int32_t Nk, int32_t Nkpad,
+                                        int32_t Tk, int32_t Tkpad, int32_t hd, const int32_t* nk, int32_t out_pair, void* stream) {
+    LT_REQUIRE(q && k && vt && tk && tvt && tbias && tgate && out, "lt_op_attention_fused_nk: null pointer");
+    if (attention_nk_checks("lt_op_attention_fused_nk", nk, B, H, Hkv, N, Nk, Nkpad, hd)) return 1;
+    LT_REQUIRE(attention_fuses_text(hd), "lt_op_attention_fused_nk: needs head_dim 72 or 96 and attention_variant 3 or 4");
+    AttnArgs a;
+    a.q = (const u16*)q; a.k = (const u16*)k; a.vt = (const u16*)vt; a.bias = nullptr; a.out = (u16*)out; a.gate = nullptr;
+    a.accumulate = 0; a.B = B; a.H = H; a.Hkv = Hkv; a.N = N; a.Nk = Nk; a.Nkpad = Nkpad; a.hd = hd; a.scale = 1.f; a.k_prescaled = 1;
+    a.tk = (const u16*)tk; a.tvt = (const u16*)tvt; a.tbias = tbias; a.tgate = (const u16*)tgate; a.Tk = Tk; a.Tkpad = Tkpad;
+    a.nk_batch = nk; a.out_pair = out_pair;
+    return launch_attention(a, (hipStream_t)stream);
+}
+
+// lt_op_attention_describe with the two arguments it lacks: per-sample key counts given, fused text keys given (Tkpad of them)
+extern "C" int lt_op_attention_nk_describe(int32_t has_bias, int32_t accumulate, int32_t B, int32_t H, int32_t Hkv, int32_t N, int32_t Nk, int32_t Nkpad,
+                                           int32_t hd, int32_t has_nk, int32_t has_text, int32_t Tkpad, char* out, int32_t cap) {
+    LT_REQUIRE(out && cap > 0, "lt_op_attention_nk_describe: null buffer");
+    LT_REQUIRE(!has_text || (Tkpad > 0 && Tkpad % 64 == 0), "lt_op_attention_nk_describe: has_text needs Tkpad > 0 in whole 64-key tiles (Tkpad = %d)", Tkpad);
+    AttnArgs a;
+    // (bias, nk_batch, tk: only their nullness is looked at)
+    a.q = nullptr; a.k = nullptr; a.vt = nullptr; a.bias = has_bias ? (const float*)out : nullptr; a.out = nullptr; a.gate = nullptr;
+    a.accumulate = accumulate; a.B = B; a.H = H; a.Hkv = Hkv; a.N = N; a.Nk = Nk; a.Nkpad = Nkpad; a.hd = hd; a.scale = 1.f;
+    a.nk_batch = has_nk ? (const int*)out : nullptr;
+    if (has_text) { a.tk = (const u16*)out; a.Tk = Tkpad; a.Tkpad = Tkpad; a.k_prescaled = 1; }
+    snprintf(out, (size_t)cap, "%s", attention_describe(a));
+    return 0;
+}
+
 // self-attention whose queries come straight from the QKV projection (AttnArgs::q_raw): q_norm + 2-D RoPE in the kernel's prologue
 extern "C" int lt_op_attention_qraw(const void* qkv, int32_t ld, int32_t q_col0, const void* q_mean_rstd, const void* q_ln_w, const void* q_ln_b,
                                     const void* cs_table, const void* cs_table_t, int32_t table_len, int32_t grid_w, const void* k,
@@ -402,13 +452,14 @@ extern "C" int lt_op_attention_qraw(const void* qkv, int32_t ld, int32_t q_col0,
 
 // lt_op_attention_qraw with the AttnArgs fields the engine fills besides (engine.hip, the attn_q_fused path): the table-branch select (t_dev,
 // watershed) and, optionally, the fused text keys (tk == NULL: none).  tests/test_gpu_prologue_exact.py
-extern "C" int lt_op_attention_qraw_ex(const void* qkv, int32_t ld, int32_t q_col0, const void* q_mean_rstd, const void* q_ln_w, const void* q_ln_b,
-                                       const void* cs_table, const void* cs_table_t, int32_t table_len, int32_t grid_w, const void* t_dev,
-                                       float watershed, const void* k, const void* vt, const void* tk, const void* tvt, const float* tbias,
-                                       const void* tgate, int32_t Tk, int32_t Tkpad, void* out, int32_t B, int32_t H, int32_t Hkv, int32_t N,
-                                       int32_t Nkpad, int32_t hd, void* stream) {
-    LT_REQUIRE(qkv && q_mean_rstd && q_ln_w && q_ln_b && cs_table && cs_table_t && k && vt && out, "lt_op_attention_qraw_ex: null pointer");
+static int attention_qraw_ex(const char* who, const void* qkv, int32_t ld, int32_t q_col0, const void* q_mean_rstd, const void* q_ln_w, const void* q_ln_b,
+                            const void* cs_table, const void* cs_table_t, int32_t table_len, int32_t grid_w, const void* t_dev,
+                            float watershed, const void* k, const void* vt, const void* tk, const void* tvt, const float* tbias,
+                            const void* tgate, int32_t Tk, int32_t Tkpad, void* out, int32_t B, int32_t H, int32_t Hkv, int32_t N,
+                            int32_t Nkpad, int32_t hd, const int32_t* nk, void* stream) {
+    LT_REQUIRE(qkv && q_mean_rstd && q_ln_w && q_ln_b && cs_table && cs_table_t && k && vt && out, "%s: null pointer", who);
     AttnArgs a;
+    a.nk_batch = nk;
     a.q = nullptr; a.k = (const u16*)k; a.vt = (const u16*)vt; a.bias = nullptr; a.out = (u16*)out; a.gate = nullptr; a.accumulate = 0;
     a.B = B; a.H = H; a.Hkv = Hkv; a.N = N; a.Nk = N; a.Nkpad = Nkpad; a.hd = hd; a.scale = 1.f; a.k_prescaled = 1;
     if (tk) { a.tk = (const u16*)tk; a.tvt = (const u16*)tvt; a.tbias = tbias; a.tgate = (const u16*)tgate; a.Tk = Tk; a.Tkpad = Tkpad; }
@@ -417,6 +468,26 @@ extern "C" int lt_op_attention_qraw_ex(const void* qkv, int32_t ld, int32_t q_co
     a.rope_cs = (const float*)cs_table; a.rope_cs_t = (const float*)cs_table_t; a.rope_t = (const float*)t_dev; a.rope_watershed = watershed;
     a.rope_cs_len = table_len; a.rope_grid_w = grid_w;
     return launch_attention(a, (hipStream_t)stream);
+}
+
+extern "C" int lt_op_attention_qraw_ex(const void* qkv, int32_t ld, int32_t q_col0, const void* q_mean_rstd, const void* q_ln_w, const void* q_ln_b,
+                                       const void* cs_table, const void* cs_table_t, int32_t table_len, int32_t grid_w, const void* t_dev,
+                                       float watershed, const void* k, const void* vt, const void* tk, const void* tvt, const float* tbias,
+                                       const void* tgate, int32_t Tk, int32_t Tkpad, void* out, int32_t B, int32_t H, int32_t Hkv, int32_t N,
+                                       int32_t Nkpad, int32_t hd, void* stream) {
+    return attention_qraw_ex("lt_op_attention_qraw_ex", qkv, ld, q_col0, q_mean_rstd, q_ln_w, q_ln_b, cs_table, cs_table_t, table_len, grid_w, t_dev, watershed, k, vt,
+                             tk, tvt, tbias, tgate, Tk, Tkpad, out, B, H, Hkv, N, Nkpad, hd, nullptr, stream);
+}
+
+// ... plus AttnArgs::nk_batch: the combination launch_attention refuses by name (one rope_grid_w, a packed batch has one per sample); nk NULL:
+// lt_op_attention_qraw_ex
+extern "C" int lt_op_attention_qraw_nk(const void* qkv, int32_t ld, int32_t q_col0, const void* q_mean_rstd, const void* q_ln_w, const void* q_ln_b,
+                                       const void* cs_table, const void* cs_table_t, int32_t table_len, int32_t grid_w, const void* t_dev,
+                                       float watershed, const void* k, const void* vt, const void* tk, const void* tvt, const float* tbias,
+                                       const void* tgate, int32_t Tk, int32_t Tkpad, void* out, int32_t B, int32_t H, int32_t Hkv, int32_t N,
+                                       int32_t Nkpad, int32_t hd, const int32_t* nk, void* stream) {
+    return attention_qraw_ex("lt_op_attention_qraw_nk", qkv, ld, q_col0, q_mean_rstd, q_ln_w, q_ln_b, cs_table, cs_table_t, table_len, grid_w, t_dev, watershed, k, vt,
+                             tk, tvt, tbias, tgate, Tk, Tkpad, out, B, H, Hkv, N, Nkpad, hd, nk, stream);
 }
 
 // launch_attention_small alone (no GEMM in front, no prefetch rider): every field of AttnSmallArgs as a plain argument; ln_eps 1e-5 as in the engine

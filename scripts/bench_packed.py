@@ -8,9 +8,12 @@ Measures the wall time (ms, between two device synchronisations) of the three tr
   (a) packed       ONE sample_ode_packed call: 6 rows padded to the longest sequence
   (b) sequential   three sample_ode calls of batch 2, one after the other on the same engine (a new prompt each)
 alternating a, b, a, b, ... `--repeats` times each after one warm-up of both, then (a) once more per repeat with the engine's
-`attention_variant` option forced to 3 (the ping-pong kernel of attention.hip).  Prints the padding ratio B' N_max / sum N_b and one JSON
+`attention_variant` option forced to 3 (the ping-pong kernel of attention.hip; packed batches then also keep row-major GEMM operands) and
+once more under `pair_layout` 0 (the one-wave kernel on row-major operands).  Beside each (a) leg it prints the attention kernel
+lt_op_attention_nk_describe names for the shape and whether the engine ran in the pair-layout regime.  Prints the padding ratio B' N_max / sum N_b and one JSON
 line; --out also writes it to a file.  Random-init weights (timing only)."""
 import argparse
+import ctypes as C
 import json
 import os
 import sys
@@ -72,17 +75,51 @@ def main():
     _, pa = timed(packed)  # warm-up: engine, weight upload, graphs
     _, pb = timed(sequential)
     eng = model._engine
-    ta, tb, tc = [], [], []
+    L = _lib.load()
+
+    def leg_kernel(name):
+        """the attention kernel of the packed self-attention call under the engine's current options, and the operand layout regime of its last evaluation"""
+        buf = C.create_string_buffer(64)
+        opts = ("attention_variant",)
+        saved = {n: eng.get_option(n) for n in opts}
+        glob = {}
+        for n in opts:  # the describe entry reads the process defaults: mirror the engine's values for the question
+            v = C.c_int32(0)
+            _lib.check(L.lt_engine_get_option(None, n.encode(), C.byref(v)), n)
+            glob[n] = v.value
+            _lib.check(L.lt_set_option(n.encode(), saved[n]), n)
+        try:
+            _lib.check(L.lt_op_attention_nk_describe(0, 0, 2 * half, model.n_heads, model.n_kv_heads, max(ntok), max(ntok), max(ntok), model.dim // model.n_heads,
+                                                     1, 1, (args.text + 63) // 64 * 64, buf, 64), "describe")
+        finally:
+            for n in opts:
+                _lib.check(L.lt_set_option(n.encode(), glob[n]), n)
+        info = {"attention": buf.value.decode(), "last_pair": eng.get_option("last_pair")}
+        print(f"leg {name}: attention kernel {info['attention']}, pair-layout regime {info['last_pair']}")
+        return info
+
+    ta, tb, tc, td = [], [], [], []
     for _ in range(args.repeats):
         ta.append(timed(packed)[0])
         tb.append(timed(sequential)[0])
+    timed(packed)
+    legs = {"packed": leg_kernel("(a) packed")}
     eng.set_option("attention_variant", 3)
     try:
         timed(packed)
         for _ in range(args.repeats):
             tc.append(timed(packed)[0])
+        legs["packed_attention_variant_3"] = leg_kernel("(a) packed, attention_variant 3")
     finally:
         eng.set_option("attention_variant", None)
+    eng.set_option("pair_layout", 0)
+    try:
+        timed(packed)
+        for _ in range(args.repeats):
+            td.append(timed(packed)[0])
+        legs["packed_pair_layout_0"] = leg_kernel("(a) packed, pair_layout 0")
+    finally:
+        eng.set_option("pair_layout", None)
     ratio = half * max(ntok) / sum(ntok)
     print(f"padding ratio B' N_max / sum N_b = {half} x {max(ntok)} / {sum(ntok)} = {ratio:.4f}")
     med = lambda v: sorted(v)[len(v) // 2]  # noqa: E731
@@ -90,6 +127,8 @@ def main():
     res = {"bench": "packed_cfg", "model": "NextDiT_2B_GQA_patch2", "latents": SIZES, "tokens": ntok, "padding_ratio": round(ratio, 4), "cfg_scale": 4.0,
            "method": "euler", "grid_points": args.points, "repeats": args.repeats,
            "packed_ms": [round(v, 2) for v in ta], "sequential_ms": [round(v, 2) for v in tb], "packed_attention_variant_3_ms": [round(v, 2) for v in tc],
+           "packed_pair_layout_0_ms": [round(v, 2) for v in td], "packed_pair_layout_0_median": round(med(td), 2),
+           "packed_pair_layout_0_spread": round(max(td) - min(td), 2), "legs": legs,
            "packed_median": round(med(ta), 2), "sequential_median": round(med(tb), 2), "packed_attention_variant_3_median": round(med(tc), 2),
            "packed_spread": round(max(ta) - min(ta), 2), "sequential_spread": round(max(tb) - min(tb), 2),
            "packed_attention_variant_3_spread": round(max(tc) - min(tc), 2), "packed_over_sequential": round(med(ta) / med(tb), 4),
