@@ -207,6 +207,24 @@ int lt_sample_ode_packed(lt_engine* e, const void* z_flat_dev, const int32_t* hw
                          const float* tgrid_host, int32_t n_grid, int32_t method, int32_t use_cfg, int32_t t_round_to_state_dtype,
                          const lt_step_args* a, void* stream);
 
+/* Inpainting: lt_sample_ode with a per-element blend after every full step.  mask_dev (1 = generate, 0 = keep), x1_dev (the
+ * source latent) and noise_dev (the noise the trajectory started from) have the layout and dtype of the state.  After the step that ends at
+ * grid point i + 1 (the last one included) the state becomes, every tensor op rounding to the state dtype R(),
+ *     R(R(step mask) + R(R(R(noise (1 - t)) + R(x1 t)) R(1 - mask))),   t = tgrid[i + 1] and 1 - t (formed in double) multiplying in fp32,
+ * in the kernel of the step's closing combine: no launch is added.  Stage-internal states (the midpoint half step, rk4 stages 2-4) are not
+ * blended and z is taken as it is.  Stage times, dt, trajectory slots and lt_last_nfe are lt_sample_ode's.  The mask's values are not read
+ * by the host: outside [0, 1] the blend extrapolates.  mask = 1 everywhere gives lt_sample_ode's states (up to the sign of a zero), mask = 0
+ * everywhere the known path noise (1 - t) + x1 t, x1 at t = 1.  Every model variant.  No synchronisation, no host read.  Refused by name
+ * with nothing written: what lt_sample_ode refuses; a null mask, source or noise. */
+int lt_sample_ode_masked(lt_engine* e, const void* z_dev, const void* mask_dev, const void* x1_dev, const void* noise_dev, void* traj_dev,
+                         void* final_dev, const float* tgrid_host, int32_t n_grid, int32_t method, int32_t use_cfg,
+                         int32_t t_round_to_state_dtype, const lt_step_args* a, void* stream);
+/* lt_sample_ode_masked on a packed batch: mask, source and noise are flat buffers of the layout of lt_forward_cfg_packed, like the state.
+ * Refused by name with nothing written: what lt_sample_ode_packed refuses; a null mask, source or noise. */
+int lt_sample_ode_masked_packed(lt_engine* e, const void* z_flat_dev, const int32_t* hw_host, const void* mask_flat_dev, const void* x1_flat_dev,
+                                const void* noise_flat_dev, void* traj_flat_dev, void* final_flat_dev, const float* tgrid_host, int32_t n_grid,
+                                int32_t method, int32_t use_cfg, int32_t t_round_to_state_dtype, const lt_step_args* a, void* stream);
+
 /* ---- multi-view (visual-anagram) sampling: visual_anagrams/generate.py:389-414, Phase Init ------------------------------------------
  * ONE latent; per time interval every view v sees view_v(latent) with its own prompt, takes one ODE step of forward_with_cfg, and the mean
  * over the views of inverse_view_v(-increment) is subtracted from the latent.  A view is data: view_v(x)[c, i] = vsign[v][c] * x[c, perm[v][i]],

@@ -211,6 +211,11 @@ int lt_op_region_text_combine(void* out, const void* txt, const void* gate, int3
                               int32_t h_split, int32_t w_split, void* stream);
 int lt_op_ode_combine(int32_t mode, const void* y0, const void* k1, const void* k2, const void* k3, const void* k4, void* out, int32_t dtype,
                       float dt, int64_t n, void* stream);
+/* lt_op_ode_combine mode 0 or 4, its result rounded to the state dtype, then the inpainting blend of lt_sample_ode_masked in the same thread:
+ * out = R(R(step mask) + R(R(R(noise one_minus_t) + R(x1 t)) R(1 - mask))); mask, x1, noise: n words of the state dtype. */
+int lt_op_ode_combine_masked(int32_t mode, const void* y0, const void* k1, const void* k2, const void* k3, const void* k4, const void* mask,
+                             const void* x1, const void* noise, void* out, int32_t dtype, float dt, float t, float one_minus_t, int64_t n,
+                             void* stream);
 int lt_op_rope_table(void* out, int32_t len, int32_t hd, int32_t step, float theta0, float lin0, float theta1, float lin1, int32_t lin_on_pos,
                      void* stream, void* out_t);
 int lt_op_linear_small_m_ext(const void* a, const void* w, const void* b, void* y, int32_t M, int32_t N, int32_t K, int32_t act_in, const void* t,

@@ -104,6 +104,9 @@ _SIGNATURES: Dict[str, tuple] = {
     "lt_sample_ode_packed": (_i32, [_vp, _vp, C.POINTER(_i32), _vp, _vp, C.POINTER(_f32), _i32, _i32, _i32, _i32, C.POINTER(LtStepArgs), _vp]),
     "lt_forward_cfg": (_i32, [_vp, _vp, _vp, _vp, C.POINTER(LtStepArgs), _vp]),
     "lt_sample_ode": (_i32, [_vp, _vp, _vp, _vp, C.POINTER(_f32), _i32, _i32, _i32, _i32, C.POINTER(LtStepArgs), _vp]),
+    "lt_sample_ode_masked": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_f32), _i32, _i32, _i32, _i32, C.POINTER(LtStepArgs), _vp]),
+    "lt_sample_ode_masked_packed": (_i32, [_vp, _vp, C.POINTER(_i32), _vp, _vp, _vp, _vp, _vp, C.POINTER(_f32), _i32, _i32, _i32, _i32,
+                                           C.POINTER(LtStepArgs), _vp]),
     "lt_set_views": (_i32, [_vp, _vp, C.POINTER(_f32), C.POINTER(_f32), _i32, _i32, _i32, _vp]),
     "lt_sample_views": (_i32, [_vp, _vp, _vp, _vp, C.POINTER(_f32), _i32, _i32, C.POINTER(LtStepArgs), _vp]),
     "lt_set_softmax_rule": (_i32, [_vp, _i32]),
@@ -177,6 +180,7 @@ _SIGNATURES: Dict[str, tuple] = {
     "lt_op_unpatchify_packed": (_i32, [_vp, _i32, _vp, _i32, C.POINTER(_i32), _vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _vp]),
     "lt_op_region_text_combine": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "lt_op_ode_combine": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _f32, _i64, _vp]),
+    "lt_op_ode_combine_masked": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _f32, _f32, _f32, _i64, _vp]),
     "lt_op_rope_table": (_i32, [_vp, _i32, _i32, _i32, _f32, _f32, _f32, _f32, _i32, _vp, _vp]),
     "lt_op_linear_small_m_ext": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, C.c_uint32, C.c_uint32, _vp]),
     "lt_op_moe_route": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp]),

@@ -355,6 +355,11 @@ int launch_unpatchify_cfg(const u16* rows, int ld, void* out, int out_dtype, int
 // torchdiffeq fixed-grid state arithmetic (modes documented in misc.hip)
 int launch_ode_combine(int mode, const void* y0, const void* k1, const void* k2, const void* k3, const void* k4,
                        void* out, int dtype, float dt, long long n, hipStream_t stream);
+// the closing combine of a step (mode 0 or 4) with the inpainting blend in the same thread: out = R(R(step m) + R(known R(1 - m))),
+// known = R(R(noise one_minus_t) + R(x1 t)); mask / x1 / noise in the state's layout and dtype (misc.hip)
+int launch_ode_combine_masked(int mode, const void* y0, const void* k1, const void* k2, const void* k3, const void* k4, const void* mask,
+                              const void* x1, const void* noise, void* out, int dtype, float dt, float t, float one_minus_t, long long n,
+                              hipStream_t stream);
 // multi-view sampling (views.hip): view tables perm / iperm int32 [V][HW], vsign / isign float [V][C]; state dtype 0 f32, 1 bf16
 //   invert: iperm from perm; hits int32 [V * HW + 1] is zeroed, then counts the hits per target, last word = entries out of range or repeated
 //   gather: out [V, C, HW] = view_v(y [C, HW]); with f0 [V, C, HW]: R(view_v(y) + R(f0 * half_dt))

@@ -314,6 +314,34 @@ __global__ void ode_combine_kernel(int mode, const void* y0, const void* k1, con
     else ((float*)out)[i] = r;
 }
 
+// The closing combine of a fixed-grid step (mode 0: euler, the midpoint full step; mode 4: rk4) followed, in the same thread, by the inpainting
+// blend of the masked sampler (transport/masked.py):
+//   step  = R(ode_combine_kernel's result)                        the state as the unmasked step would store it
+//   known = R(R(noise one_minus_t) + R(x1 t))                     noise * (1 - t) + x1 * t, t a Python float: the scalars multiply in fp32
+//   out   = R(R(step m) + R(known R(1 - m)))                      step * m + known * (1 - m), every tensor op rounding to the state dtype
+// mask, x1 and noise have the state's layout and dtype; the mask's values are not inspected (outside [0, 1] it extrapolates).  The step
+// arithmetic restates ode_combine_kernel statement for statement; nothing is contracted.
+template <bool BF>
+__global__ void ode_combine_masked_kernel(int mode, const void* y0, const void* k1, const void* k2, const void* k3, const void* k4,
+                                          const void* mask, const void* x1, const void* noise, void* out, float dt, float t,
+                                          float one_minus_t, long long n) {
+#pragma clang fp contract(off)  // as its sibling: torch rounds every product before the sum that takes it
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    auto ld = [&](const void* p) { return BF ? bf2f(((const u16*)p)[i]) : ((const float*)p)[i]; };
+    auto R = [](float x) { return BF ? bfr(x) : x; };
+    const float y = ld(y0);
+    float r;
+    if (mode == 0) r = y + R(dt * ld(k1));
+    else r = y + R(R(R(R(ld(k1) + R(3.0f * R(ld(k2) + ld(k3)))) + ld(k4)) * dt) * 0.125f);
+    const float step = R(r);
+    const float m = ld(mask);
+    const float known = R(R(ld(noise) * one_minus_t) + R(ld(x1) * t));
+    const float v = R(step * m) + R(known * R(1.0f - m));
+    if (BF) ((u16*)out)[i] = f2bf(v);
+    else ((float*)out)[i] = v;
+}
+
 // precompute_freqs_cis of every sub-project reduced to 1-D factor tables: out[branch][pos][fi] = cis(angle), with
 //   f_fi = theta_b^(-step fi / hd), step = 4 (2-D RoPE: hd/4 frequencies per axis; lumina_next_t2i/models/model.py:915-963,
 //   Next-DiT-ImageNet/models/models.py:977-1012) or 2 (1-D: hd/2 frequencies; lumina_t2i/models/model.py:924-960);
@@ -527,6 +555,25 @@ int launch_ode_combine(int mode, const void* y0, const void* k1, const void* k2,
         hipLaunchKernelGGL(ode_combine_kernel<true>, dim3(nblk(n, 256)), dim3(256), 0, stream, mode, y0, k1, k2, k3, k4, out, dt, n);
     else
         hipLaunchKernelGGL(ode_combine_kernel<false>, dim3(nblk(n, 256)), dim3(256), 0, stream, mode, y0, k1, k2, k3, k4, out, dt, n);
+    LT_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+int launch_ode_combine_masked(int mode, const void* y0, const void* k1, const void* k2, const void* k3, const void* k4, const void* mask,
+                              const void* x1, const void* noise, void* out, int dtype, float dt, float t, float one_minus_t, long long n,
+                              hipStream_t stream) {
+    LT_REQUIRE(mode == 0 || mode == 4, "ode_combine_masked: bad mode %d (0: euler / midpoint full step, 4: rk4)", mode);
+    LT_REQUIRE(dtype == 0 || dtype == 1, "ode_combine_masked: state dtype must be f32 or bf16");
+    LT_REQUIRE(y0 && k1 && out && (mode == 0 || (k2 && k3 && k4)), "ode_combine_masked: null state or slope");
+    LT_REQUIRE(mask && x1 && noise, "ode_combine_masked: null mask, source or noise");
+    LT_REQUIRE(n >= 0 && n <= 0x7fffffffLL * 256, "ode_combine_masked: n %lld out of range", n);
+    if (n == 0) return 0;
+    if (dtype == 1)
+        hipLaunchKernelGGL(ode_combine_masked_kernel<true>, dim3(nblk(n, 256)), dim3(256), 0, stream, mode, y0, k1, k2, k3, k4, mask, x1, noise, out,
+                           dt, t, one_minus_t, n);
+    else
+        hipLaunchKernelGGL(ode_combine_masked_kernel<false>, dim3(nblk(n, 256)), dim3(256), 0, stream, mode, y0, k1, k2, k3, k4, mask, x1, noise, out,
+                           dt, t, one_minus_t, n);
     LT_CHECK_HIP(hipGetLastError());
     return 0;
 }

@@ -667,6 +667,11 @@ extern "C" int lt_op_ode_combine(int32_t mode, const void* y0, const void* k1, c
                                  int32_t dtype, float dt, int64_t n, void* stream) {
     return launch_ode_combine(mode, y0, k1, k2, k3, k4, out, dtype, dt, (long long)n, (hipStream_t)stream);
 }
+extern "C" int lt_op_ode_combine_masked(int32_t mode, const void* y0, const void* k1, const void* k2, const void* k3, const void* k4,
+                                        const void* mask, const void* x1, const void* noise, void* out, int32_t dtype, float dt, float t,
+                                        float one_minus_t, int64_t n, void* stream) {
+    return launch_ode_combine_masked(mode, y0, k1, k2, k3, k4, mask, x1, noise, out, dtype, dt, t, one_minus_t, (long long)n, (hipStream_t)stream);
+}
 extern "C" int lt_op_rope_table(void* out, int32_t len, int32_t hd, int32_t step, float theta0, float lin0, float theta1, float lin1,
                                 int32_t lin_on_pos, void* stream, void* out_t) {
     return launch_rope_table((float*)out, len, hd, step, theta0, lin0, theta1, lin1, lin_on_pos, (hipStream_t)stream, (float*)out_t);

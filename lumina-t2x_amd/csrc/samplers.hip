@@ -69,9 +69,12 @@ float bf16_round_host(float f) {
 
 // The fixed-grid loop of lt_sample_ode and lt_sample_ode_packed: stage-time fill and the euler / midpoint / rk4 stepping body on a state of
 // n elements (the stage arithmetic is elementwise, so a packed batch's flat state runs through it as it is).  The callers have validated
-// the grid, the method and the shape.
+// the grid, the method and the shape.  With `mb` (lt_sample_ode_masked) the LAST combine of every step is the masked launcher - the same
+// arithmetic followed by the inpainting blend at the step's end time - and nothing else changes.
+struct MaskedBlend { const void *mask, *x1, *noise; };
+
 int ode_fixed_grid(lt_engine* e, const void* z_dev, void* traj_dev, void* final_dev, const float* tgrid_host, int n_grid, int method, int use_cfg,
-                   int t_round, const lt_step_args* a, hipStream_t s, long long n, const PackedCall* pc) {
+                   int t_round, const lt_step_args* a, hipStream_t s, long long n, const PackedCall* pc, const MaskedBlend* mb = nullptr) {
     const int B = a->batch;
     const int stages = method == LT_ODE_EULER ? 1 : (method == LT_ODE_MIDPOINT ? 2 : 4);
     const int ncalls = (n_grid - 1) * stages;
@@ -106,14 +109,21 @@ int ode_fixed_grid(lt_engine* e, const void* z_dev, void* traj_dev, void* final_
         // sees bf16(dt) (0.5 dt is exact after that).  The stage TIMES above stay fp32 (t0 + dt / 2 is fp32 arithmetic).
         const float dt = bf ? bf16_round_host(dts[i]) : dts[i];
         const int c0 = i * stages;
+        // the step's closing combine: y1 = y0 + ... [then blended with the known path at t1: the host loop's Python floats t1 and 1 - t1, the
+        // latter formed in double, enter torch's fp32 op-math]
+        auto close = [&](int mode, const void* k1, const void* k2, const void* k3, const void* k4) -> int {
+            if (!mb) return launch_ode_combine(mode, y0, k1, k2, k3, k4, y1, dt_code, dt, n, s);
+            const float t1 = tgrid_host[i + 1];
+            return launch_ode_combine_masked(mode, y0, k1, k2, k3, k4, mb->mask, mb->x1, mb->noise, y1, dt_code, dt, t1, (float)(1.0 - (double)t1), n, s);
+        };
         if (method == LT_ODE_EULER) {
             if (tr.eval(y0, c0, e->kbuf[0])) return 1;
-            if (launch_ode_combine(0, y0, e->kbuf[0], nullptr, nullptr, nullptr, y1, dt_code, dt, n, s)) return 1;
+            if (close(0, e->kbuf[0], nullptr, nullptr, nullptr)) return 1;
         } else if (method == LT_ODE_MIDPOINT) {
             if (tr.eval(y0, c0, e->kbuf[0])) return 1;
             if (launch_ode_combine(0, y0, e->kbuf[0], nullptr, nullptr, nullptr, e->ymid, dt_code, 0.5f * dt, n, s)) return 1;
             if (tr.eval(e->ymid, c0 + 1, e->kbuf[1])) return 1;
-            if (launch_ode_combine(0, y0, e->kbuf[1], nullptr, nullptr, nullptr, y1, dt_code, dt, n, s)) return 1;
+            if (close(0, e->kbuf[1], nullptr, nullptr, nullptr)) return 1;
         } else {
             if (tr.eval(y0, c0, e->kbuf[0])) return 1;
             if (launch_ode_combine(1, y0, e->kbuf[0], nullptr, nullptr, nullptr, e->ymid, dt_code, dt, n, s)) return 1;
@@ -122,7 +132,7 @@ int ode_fixed_grid(lt_engine* e, const void* z_dev, void* traj_dev, void* final_
             if (tr.eval(e->ymid, c0 + 2, e->kbuf[2])) return 1;
             if (launch_ode_combine(3, y0, e->kbuf[0], e->kbuf[1], e->kbuf[2], nullptr, e->ymid, dt_code, dt, n, s)) return 1;
             if (tr.eval(e->ymid, c0 + 3, e->kbuf[3])) return 1;
-            if (launch_ode_combine(4, y0, e->kbuf[0], e->kbuf[1], e->kbuf[2], e->kbuf[3], y1, dt_code, dt, n, s)) return 1;
+            if (close(4, e->kbuf[0], e->kbuf[1], e->kbuf[2], e->kbuf[3])) return 1;
         }
         if (tr.advance(i + 1)) return 1;
     }
@@ -155,6 +165,39 @@ extern "C" int lt_sample_ode_packed(lt_engine* e, const void* z_flat_dev, const 
     if (int rc = packed_call_begin(e, "lt_sample_ode_packed", hw_host, a, use_cfg, &pc, (hipStream_t)stream)) return rc;
     return ode_fixed_grid(e, z_flat_dev, traj_flat_dev, final_flat_dev, tgrid_host, n_grid, method, use_cfg, t_round, a, (hipStream_t)stream, pc.elems,
                           &pc);
+}
+
+// ---- inpainting: the fixed-grid loop with the blend in each step's closing combine --------------------------------------
+extern "C" int lt_sample_ode_masked(lt_engine* e, const void* z_dev, const void* mask_dev, const void* x1_dev, const void* noise_dev, void* traj_dev,
+                                    void* final_dev, const float* tgrid_host, int32_t n_grid, int32_t method, int32_t use_cfg, int32_t t_round,
+                                    const lt_step_args* a, void* stream) {
+    LT_REQUIRE(mask_dev && x1_dev && noise_dev, "lt_sample_ode_masked: null mask, source or noise");
+    LT_REQUIRE(e && z_dev && tgrid_host && a, "lt_sample_ode_masked: null argument");
+    LtOptScope opt_scope(&e->opts);
+    LT_REQUIRE(n_grid >= 2, "lt_sample_ode_masked: need at least 2 grid points");
+    LT_REQUIRE(method >= LT_ODE_EULER && method <= LT_ODE_RK4, "lt_sample_ode_masked: unknown method %d", method);
+    if (check_step_shape(e, "lt_sample_ode_masked", a)) return 2;
+    // (lt_sample_ode leaves this to the first evaluation, after z has been copied; here nothing is written)
+    LT_REQUIRE(!use_cfg || a->batch % 2 == 0, "lt_sample_ode_masked: guidance needs an even batch (cond + uncond rows), got %d", a->batch);
+    const long long n = (long long)a->batch * e->cfg.in_channels * a->latent_h * a->latent_w;
+    const MaskedBlend mb{mask_dev, x1_dev, noise_dev};
+    return ode_fixed_grid(e, z_dev, traj_dev, final_dev, tgrid_host, n_grid, method, use_cfg, t_round, a, (hipStream_t)stream, n, nullptr, &mb);
+}
+
+extern "C" int lt_sample_ode_masked_packed(lt_engine* e, const void* z_flat_dev, const int32_t* hw_host, const void* mask_flat_dev,
+                                           const void* x1_flat_dev, const void* noise_flat_dev, void* traj_flat_dev, void* final_flat_dev,
+                                           const float* tgrid_host, int32_t n_grid, int32_t method, int32_t use_cfg, int32_t t_round,
+                                           const lt_step_args* a, void* stream) {
+    LT_REQUIRE(mask_flat_dev && x1_flat_dev && noise_flat_dev, "lt_sample_ode_masked_packed: null mask, source or noise");
+    LT_REQUIRE(e && z_flat_dev && hw_host && tgrid_host && a, "lt_sample_ode_masked_packed: null argument");
+    LtOptScope opt_scope(&e->opts);
+    LT_REQUIRE(n_grid >= 2, "lt_sample_ode_masked_packed: need at least 2 grid points");
+    LT_REQUIRE(method >= LT_ODE_EULER && method <= LT_ODE_RK4, "lt_sample_ode_masked_packed: unknown method %d", method);
+    PackedCall pc{};
+    if (int rc = packed_call_begin(e, "lt_sample_ode_masked_packed", hw_host, a, use_cfg, &pc, (hipStream_t)stream)) return rc;
+    const MaskedBlend mb{mask_flat_dev, x1_flat_dev, noise_flat_dev};
+    return ode_fixed_grid(e, z_flat_dev, traj_flat_dev, final_flat_dev, tgrid_host, n_grid, method, use_cfg, t_round, a, (hipStream_t)stream, pc.elems,
+                          &pc, &mb);
 }
 
 // ---- multi-view (visual-anagram) sampling ------------------------------------------------------------------------------------------

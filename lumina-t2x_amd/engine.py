@@ -338,6 +338,71 @@ class DiTEngine:
             return [out[:, off:off + math.prod(shape)].view((n,) + shape) for off, shape in spans]
         return [out[off:off + math.prod(shape)].view(shape) for off, shape in spans]
 
+    # ---- inpainting: the fixed-grid trajectory with a per-element blend after every step -------------
+    @staticmethod
+    def _masked_operands(state: torch.Tensor, mask, x1, noise, what: str):
+        """mask / source / noise as the engine reads them: the state's shape, dtype and device, contiguous (the callers broadcast)"""
+        ops = []
+        for name, v in (("mask", mask), ("x1", x1), ("noise", noise)):
+            if not isinstance(v, torch.Tensor):
+                raise LuminaLibError(f"{what}: {name} must be a tensor of the state's shape {tuple(state.shape)}")
+            if tuple(v.shape) != tuple(state.shape) or v.dtype != state.dtype or v.device != state.device:
+                raise LuminaLibError(f"{what}: {name} {tuple(v.shape)} {v.dtype} on {v.device} does not have the layout and dtype of the state "
+                                     f"{tuple(state.shape)} {state.dtype} on {state.device}")
+            ops.append(v.contiguous())
+        return ops
+
+    def sample_ode_masked(self, z: torch.Tensor, tgrid, mask: torch.Tensor, x1: torch.Tensor, noise: torch.Tensor, method: str, *, use_cfg: bool,
+                          cfg_scale: float = 1.0, scale_factor: float = 1.0, scale_watershed: float = 1.0, base_seqlen: Optional[int] = None,
+                          proportional_attn: bool = False, t_round_to_state_dtype: bool = True, return_trajectory: bool = True,
+                          ntk_factor: float = 1.0) -> torch.Tensor:
+        """``sample_ode`` with the inpainting blend after every full step (lt_sample_ode_masked): ``mask`` (1 = generate, 0 = keep), the
+        source latent ``x1`` and the ``noise`` the trajectory started from, all shaped and typed like ``z``"""
+        _require_gpu(z, "z")
+        if method not in _lib.ODE_METHODS:
+            raise LuminaLibError(f"fixed-grid method '{method}' not in {sorted(_lib.ODE_METHODS)}")
+        z = z.contiguous()
+        m, src, nz = self._masked_operands(z, mask, x1, noise, "sample_ode_masked")
+        garr, n = _grid_array(tgrid)
+        a = self._step_args(z, cfg_scale, scale_factor, scale_watershed, base_seqlen, proportional_attn, ntk_factor=ntk_factor)
+        out, traj_ptr, fin_ptr = _traj_or_final(z, n, z.shape, return_trajectory)
+        with torch.cuda.device(self.device):
+            rc = self.lib.lt_sample_ode_masked(self.handle, C.c_void_p(z.data_ptr()), C.c_void_p(m.data_ptr()), C.c_void_p(src.data_ptr()),
+                                               C.c_void_p(nz.data_ptr()), traj_ptr, fin_ptr, garr, n, _lib.ODE_METHODS[method], int(use_cfg),
+                                               int(t_round_to_state_dtype), C.byref(a), C.c_void_p(_stream_ptr(self.device)))
+        _lib.check(rc, "lt_sample_ode_masked")
+        return out
+
+    def sample_ode_masked_packed(self, zs, tgrid, masks, x1s, noises, method: str, *, use_cfg: bool, cfg_scale: float = 1.0,
+                                 scale_factor: float = 1.0, scale_watershed: float = 1.0, base_seqlen: Optional[int] = None,
+                                 proportional_attn: bool = False, t_round_to_state_dtype: bool = True, return_trajectory: bool = True):
+        """``sample_ode_packed`` with the inpainting blend (lt_sample_ode_masked_packed): ``masks``, ``x1s`` and ``noises`` are lists like
+        ``zs``, sample b of each shaped like ``zs[b]``"""
+        if method not in _lib.ODE_METHODS:
+            raise LuminaLibError(f"fixed-grid method '{method}' not in {sorted(_lib.ODE_METHODS)}")
+        zs = list(zs)
+        flat, hw, spans = self._pack(zs, "sample_ode_masked_packed")
+        flats = []
+        for name, vs in (("mask", masks), ("x1", x1s), ("noise", noises)):
+            vs = list(vs)
+            if len(vs) != len(zs) or any(not isinstance(v, torch.Tensor) or tuple(v.shape) != tuple(z.shape) or v.dtype != z.dtype
+                                         or v.device != z.device for v, z in zip(vs, zs)):
+                raise LuminaLibError(f"sample_ode_masked_packed: {name} must be a list of {len(zs)} tensors, each with the shape, dtype and "
+                                     "device of its sample")
+            flats.append(torch.cat([v.reshape(-1) for v in vs]))
+        garr, n = _grid_array(tgrid)
+        a = self._packed_step_args(flat, len(spans), cfg_scale, scale_factor, scale_watershed, base_seqlen, proportional_attn)
+        out, traj_ptr, fin_ptr = _traj_or_final(flat, n, flat.shape, return_trajectory)
+        with torch.cuda.device(self.device):
+            rc = self.lib.lt_sample_ode_masked_packed(self.handle, C.c_void_p(flat.data_ptr()), hw, C.c_void_p(flats[0].data_ptr()),
+                                                      C.c_void_p(flats[1].data_ptr()), C.c_void_p(flats[2].data_ptr()), traj_ptr, fin_ptr, garr, n,
+                                                      _lib.ODE_METHODS[method], int(use_cfg), int(t_round_to_state_dtype), C.byref(a),
+                                                      C.c_void_p(_stream_ptr(self.device)))
+        _lib.check(rc, "lt_sample_ode_masked_packed")
+        if return_trajectory:
+            return [out[:, off:off + math.prod(shape)].view((n,) + shape) for off, shape in spans]
+        return [out[off:off + math.prod(shape)].view(shape) for off, shape in spans]
+
     def sample_ode_adaptive(self, z: torch.Tensor, tgrid: torch.Tensor, method: str, *, rtol: float, atol: float,
                             first_step: Optional[float] = None, max_steps: int = 2 ** 31 - 1, use_cfg: bool, cfg_scale: float = 1.0,
                             scale_factor: float = 1.0, scale_watershed: float = 1.0, base_seqlen: Optional[int] = None,

@@ -83,6 +83,11 @@ class EngineSamplers:
         eng, args = self._engine_sampler_args(x, use_cfg, kw)
         return eng.sample_ode(x, tgrid, method, use_cfg=use_cfg, t_round_to_state_dtype=t_round, **args)
 
+    def _engine_sample_ode_masked(self, x, tgrid, method, use_cfg, t_round, mask, x1, noise, kw):
+        """kwargs of forward_with_cfg / forward -> lt_sample_ode_masked (inpainting; mask / x1 / noise shaped and typed like x)"""
+        eng, args = self._engine_sampler_args(x, use_cfg, kw)
+        return eng.sample_ode_masked(x, tgrid, mask, x1, noise, method, use_cfg=use_cfg, t_round_to_state_dtype=t_round, **args)
+
     def _engine_sample_ode_adaptive(self, x, tgrid, method, use_cfg, t_round, kw, *, rtol, atol, first_step=None, max_steps=2 ** 31 - 1):
         """kwargs of forward_with_cfg / forward -> lt_sample_ode_adaptive; returns (states [len(tgrid), *x.shape], stats dict)"""
         eng, args = self._engine_sampler_args(x, use_cfg, kw)

@@ -254,6 +254,45 @@ class NextDiT(EngineSamplers, WeightWatch, nn.Module):
                                      scale_watershed=scale_watershed, base_seqlen=base_seqlen, proportional_attn=proportional_attn,
                                      return_trajectory=return_trajectory)
 
+    @torch.no_grad()
+    def sample_ode_masked(self, z, tgrid, mask, x1, noise, cap_feats, cap_mask, cfg_scale, method: str = "midpoint",
+                          return_trajectory: bool = False, scale_factor=1.0, scale_watershed=1.0, base_seqlen: Optional[int] = None,
+                          proportional_attn: bool = False):
+        """Inpainting in ONE engine call (lt_sample_ode_masked): the fixed-grid trajectory of ``z [B, C, H, W]`` over ``tgrid`` with
+        ``y = y * mask + (noise * (1 - t) + x1 * t) * (1 - mask)`` after every full step.  ``mask`` (1 = generate, 0 = keep; ``[H, W]`` or
+        ``[1|B, 1, H, W]``), the source latent ``x1`` and the ``noise`` the trajectory started from (``[1|B', C, H, W]``) are broadcast to the
+        state and repeated for the uncond half (``transport.masked.expand_operands``).  Every evaluation is ``forward_with_cfg``; with
+        ``cfg_scale=None`` it is the plain ``forward``.  Returns the last state, or all ``len(tgrid)`` states."""
+        from ..transport.masked import expand_operands
+        use_cfg = cfg_scale is not None
+        kw = dict(cap_feats=cap_feats, cap_mask=cap_mask)
+        if use_cfg:
+            if proportional_attn:
+                assert base_seqlen is not None
+            for layer in self.layers:  # mirrored attributes (reference model.py:891-899)
+                layer.attention.base_seqlen = base_seqlen if proportional_attn else None
+                layer.attention.proportional_attn = proportional_attn
+            kw.update(cfg_scale=cfg_scale, scale_factor=scale_factor, scale_watershed=scale_watershed, base_seqlen=base_seqlen,
+                      proportional_attn=proportional_attn)
+        m, src, nz = expand_operands(z, mask, x1, noise)
+        eng, args = self._engine_sampler_args(z, use_cfg, kw)
+        return eng.sample_ode_masked(z, tgrid, m, src, nz, method, use_cfg=use_cfg, return_trajectory=return_trajectory, **args)
+
+    @torch.no_grad()
+    def sample_ode_masked_packed(self, zs, tgrid, masks, x1s, noises, cap_feats, cap_mask, cfg_scale, method: str = "midpoint",
+                                 return_trajectory: bool = False, scale_factor=1.0, scale_watershed=1.0, base_seqlen: Optional[int] = None,
+                                 proportional_attn: bool = False):
+        """``sample_ode_masked`` on a LIST of differently sized latents (lt_sample_ode_masked_packed), every evaluation
+        ``forward_with_cfg_packed``: ``masks`` / ``x1s`` / ``noises`` are lists with one entry per sample, or one per sample of the cond half
+        (repeated for the uncond half), each broadcasting to its sample ``[C, H_b, W_b]``.  Returns one tensor per sample."""
+        from ..transport.masked import expand_operands_packed
+        zs = list(zs)
+        ms, srcs, nzs = expand_operands_packed(zs, masks, x1s, noises)
+        eng, zs = self._packed_cfg_engine(zs, cap_feats, cap_mask, base_seqlen, proportional_attn)
+        return eng.sample_ode_masked_packed(zs, tgrid, ms, srcs, nzs, method, use_cfg=True, cfg_scale=cfg_scale, scale_factor=scale_factor,
+                                            scale_watershed=scale_watershed, base_seqlen=base_seqlen, proportional_attn=proportional_attn,
+                                            return_trajectory=return_trajectory)
+
     def _engine_sampler_args(self, x, use_cfg, kw):
         """transport fast paths (models/_base.py: EngineSamplers): kwargs of forward_with_cfg / forward -> engine + step kwargs"""
         cap_feats, cap_mask = kw.pop("cap_feats"), kw.pop("cap_mask")

@@ -8,6 +8,10 @@
 
 The step arithmetic is the flat ``ODE`` of the mini package (``transport/mini.py``, grids pinned to the reference class in
 tests/golden/mini_ode.npz): a bound ``forward_with_cfg`` of an engine-backed model runs the cut trajectory as ONE ``lt_sample_ode`` call.
+``--mask`` (not in the reference) makes it inpainting: the mask image becomes one channel (white = regenerate, black = keep), is area-resized to
+the latent grid (``--mask_threshold`` binarises it there; default: soft) and the cut trajectory runs as ONE ``lt_sample_ode_masked`` call, which
+after every step puts ``noise * (1 - t) + x1 * t`` back where the mask says keep (transport/masked.py) - the drawn noise is handed on for that.
+Without ``--mask`` nothing changes.
 Third-party stages stay third-party, as in the reference: text encoder (``transformers.AutoModel``), VAE (``diffusers.AutoencoderKL``,
 both directions here), image decoding (PIL).  They can be injected (tests; callers that already hold them).  One process per GPU under
 ``python -m torch.distributed.run``; captions shard round-robin, no collective on the data path.
@@ -40,6 +44,25 @@ def load_image(path: str, w: int, h: int, device) -> torch.Tensor:
     return arr.sub_(0.5).div_(0.5).to(device)
 
 
+def load_mask(path: str, w: int, h: int, device) -> torch.Tensor:
+    """PIL image -> one channel, resized to (w, h), [h, w] in [0, 1]: white = regenerate, black = keep"""
+    import numpy as np
+    from PIL import Image
+    img = Image.open(path).convert("L").resize((w, h))
+    return torch.from_numpy(np.asarray(img).copy()).float().div_(255.0).to(device)
+
+
+def latent_mask(mask: torch.Tensor, lh: int, lw: int, threshold: Optional[float] = None) -> torch.Tensor:
+    """a pixel mask ``[h, w]`` (or ``[1, h, w]`` / ``[1, 1, h, w]``) in [0, 1] on the latent grid: ``[1, 1, lh, lw]`` fp32, each latent pixel the
+    mean of the pixels it covers (area resize); with ``threshold`` it is binarised there (1 where the mean exceeds it)"""
+    m = mask.float().reshape((1, 1) + tuple(mask.shape[-2:]))
+    if tuple(m.shape[-2:]) != (lh, lw):
+        m = torch.nn.functional.interpolate(m, size=(lh, lw), mode="area")
+    if threshold is not None:
+        m = (m > float(threshold)).float()
+    return m.clamp_(0.0, 1.0)
+
+
 def make_vae(path: Optional[str], device):
     """(encode(image [1,3,h,w] in [-1,1]) -> latent sample, decode(latent) -> image in [0,1]) or (None, None)"""
     if not path:
@@ -62,7 +85,7 @@ def make_vae(path: Optional[str], device):
 
 
 def run(args, *, encode_fn=None, cap_feat_dim=None, vae_encode_fn: Optional[Callable] = None, decode_fn=None, model=None,
-        image: Optional[torch.Tensor] = None) -> List[dict]:
+        image: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None) -> List[dict]:
     torch.set_grad_enabled(False)
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
@@ -107,6 +130,11 @@ def run(args, *, encode_fn=None, cap_feat_dim=None, vae_encode_fn: Optional[Call
         z = torch.randn([1, 4, h // 8, w // 8], device=device).to(dtype)
         if tuple(x1.shape[-2:]) != (h // 8, w // 8):
             raise ValueError(f"VAE latent {tuple(x1.shape)} does not match the requested resolution {w}x{h} (expected [..., {h // 8}, {w // 8}])")
+        inpaint = None
+        if mask is not None or getattr(args, "mask", ""):
+            pix = mask if mask is not None else load_mask(args.mask, w, h, device)
+            # the blend needs the noise the trajectory starts from and the source in the state dtype, as the mix below reads them
+            inpaint = dict(mask=latent_mask(pix.to(device), h // 8, w // 8, getattr(args, "mask_threshold", None)), x1=x1.to(dtype), noise=z)
         t0 = float(ode.t[0])
         z = z * (1 - t0) + x1.to(dtype) * t0                                          # :190
         z = z.repeat(2, 1, 1, 1)
@@ -118,7 +146,7 @@ def run(args, *, encode_fn=None, cap_feat_dim=None, vae_encode_fn: Optional[Call
             kw.update(scale_factor=math.sqrt(w * h / train_args.image_size ** 2), scale_watershed=args.scaling_watershed)
         else:
             kw.update(scale_factor=1.0, scale_watershed=1.0)
-        latent = ode.sample(z, model.forward_with_cfg, **kw)[-1][:1]
+        latent = ode.sample(z, model.forward_with_cfg, **(inpaint or {}), **kw)[-1][:1]
         stem = os.path.join(out_dir, "images", f"{args.solver}_{args.num_sampling_steps}_{idx}_{res.split(':')[-1]}")
         if decode_fn is not None:
             save_png(decode_fn(latent / factor)[0], stem + ".png")
@@ -142,6 +170,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--solver", type=str, default="euler")
     p.add_argument("--strength", type=float, default=0.6)
     p.add_argument("--image", type=str, required=True)
+    p.add_argument("--mask", type=str, default="", help="inpainting mask image: white = regenerate, black = keep the input image (default: none, "
+                   "plain img2img)")
+    p.add_argument("--mask_threshold", type=float, default=None, help="binarise the mask on the latent grid (1 where the area mean exceeds it); "
+                   "default: keep it soft")
     p.add_argument("--precision", type=str, choices=["fp32", "bf16"], default="bf16")
     p.add_argument("--ema", action="store_true", default=True)
     p.add_argument("--no-ema", dest="ema", action="store_false")

@@ -2,6 +2,8 @@
 sample_img2img.py:146-216) uses instead of Sampler/ode, including the img2img ``strength`` cut of the time grid
 (transport.py:79-80).  The model-callable protocol and the engine fast path are those of transport.integrators.ode:
 a bound ``forward_with_cfg`` of one of our engine-backed models runs the whole trajectory in one ``lt_sample_ode`` call.
+``sample(..., mask=, x1=, noise=)`` is the inpainting form (transport/masked.py; not in the reference): one ``lt_sample_ode_masked`` call
+for an engine-backed callable, the host loop ``sample_masked`` otherwise.
 
 Not mirrored: ``use_sd3=True`` (drives a diffusers SD3Transformer2DModel, not a Lumina model - out of scope)."""
 from __future__ import annotations
@@ -9,6 +11,7 @@ from __future__ import annotations
 import torch as th
 
 from .integrators import ADAPTIVE_METHODS, FIXED_GRID_METHODS, _engine_target, adaptive_odeint, fixed_grid_odeint
+from .masked import expand_operands, sample_masked
 
 
 class ODE:
@@ -27,10 +30,30 @@ class ODE:
         self.use_sd3 = use_sd3
         self.sampler_type = sampler_type
         self.t_round_to_state_dtype = True  # torchdiffeq casts t to the state dtype (see integrators.ode)
+        self.use_engine = True  # masked sampling: False keeps the host loop (sample_masked) for an engine-backed callable too
 
-    def sample(self, x, model, **model_kwargs):
+    def _sample_masked(self, x, model, mask, x1, noise, model_kwargs):
+        """inpainting (transport/masked.py): the blend after every full step; one engine call when the callable is engine-backed"""
+        if mask is None or x1 is None or noise is None:
+            raise ValueError("masked sampling needs mask, x1 and noise together")
+        if self.sampler_type not in FIXED_GRID_METHODS:
+            raise NotImplementedError(f"masked sampling is built for the fixed-grid methods {', '.join(FIXED_GRID_METHODS)}, not "
+                                      f"'{self.sampler_type}'")
+        if len(self.t) < 2:
+            raise ValueError("masked sampling needs at least 2 grid points")
+        mask, x1, noise = expand_operands(x, mask, x1, noise)
+        target = _engine_target(model)
+        if target is not None and x.is_cuda and self.use_engine and hasattr(target[0], "_engine_sample_ode_masked"):
+            owner, use_cfg = target
+            return owner._engine_sample_ode_masked(x, self.t, self.sampler_type, use_cfg, self.t_round_to_state_dtype, mask, x1, noise,
+                                                   dict(model_kwargs))
+        return sample_masked(model, x, self.t, mask, x1, noise, self.sampler_type, **model_kwargs)
+
+    def sample(self, x, model, mask=None, x1=None, noise=None, **model_kwargs):
         if isinstance(x, tuple):
             raise NotImplementedError("tuple states are not part of the sampling path")
+        if mask is not None or x1 is not None or noise is not None:
+            return self._sample_masked(x, model, mask, x1, noise, model_kwargs)
         target = _engine_target(model)
         if target is not None and x.is_cuda and self.sampler_type in FIXED_GRID_METHODS and len(self.t) >= 2:
             owner, use_cfg = target
