@@ -325,8 +325,30 @@ int lt_sample_ode_adaptive(lt_engine* e, const void* z_dev, void* traj_dev, cons
                            float atol, float first_step, int32_t max_steps, int32_t use_cfg, int32_t t_round_to_state_dtype,
                            const lt_step_args* a, void* stream, lt_ode_adaptive_stats* stats);
 
+/* Guidance schedules: lt_sample_ode with guidance whose scale changes from stage to stage.  cfg_host holds (n_grid - 1) *
+ * stages fp32 scales (stages = 1 euler, 2 midpoint, 4 rk4): stage k of interval i uses w = cfg_host[i * stages + k].  The state has a->batch =
+ * 2 B' rows (cond rows, then uncond rows); the prompt / the labels were prepared for all 2 B' rows, once.
+ *   w != 1:  the stage's slope is forward_with_cfg at scale w - lt_forward_cfg's arithmetic, the scale read from device memory;
+ *   w == 1 exactly:  the slope is the plain forward o of the B' cond rows on the cond half of the conditioning - bit for bit lt_forward at
+ *            batch B' after a preparation of those rows alone - written to both halves of the slope (cat([o, o])): B' rows are evaluated, not
+ *            2 B'.  (Under cfg_channels < in_channels the channels past cfg_channels of the second half then hold the cond rows' output where
+ *            forward_with_cfg at scale 1 would hold the uncond rows'; the first half is the sample.)
+ * Stage times, dt, rounding points, trajectory slots and lt_last_nfe = (n_grid - 1) * stages are lt_sample_ode's; lt_last_eval_rows =
+ * 2 B' G + B' C for G guided and C conditional-only stages.  a->cfg_scale is ignored.  The scales are committed with the stage times and
+ * every evaluation finds its own in a fixed device word, so a trajectory uses at most two HIP-graph keys (the 2 B'-row guided evaluation,
+ * the B'-row conditional one) whatever the table holds.  Where the two sizes fall on different sides of the pair-layout threshold every
+ * change between them converts all GEMM weights (lt_engine_get_option "layout_flips" counts the conversions of the last call).
+ * No synchronisation, no host read.  Every variant lt_sample_ode serves with guidance.  Packed batches, inpainting masks and views are not
+ * served by this call.  Refused by name with nothing written: a null argument; an unknown method; n_grid < 2; what lt_sample_ode refuses of
+ * the shape; an odd batch; a scale that is not finite; a regional prompt (lt_prepare_prompt_regional); a conditioning prepared for another
+ * batch. */
+int lt_sample_ode_cfg_schedule(lt_engine* e, const void* z_dev, void* traj_dev, void* final_dev, const float* tgrid_host, int32_t n_grid,
+                               int32_t method, const float* cfg_host, int32_t t_round_to_state_dtype, const lt_step_args* a, void* stream);
+
 /* number of model evaluations issued by the last lt_sample_ode / lt_sample_ode_packed / lt_sample_views / lt_sample_views_guided / lt_sample_sde / lt_sample_ode_adaptive call */
 int64_t lt_last_nfe(lt_engine* e);
+/* the rows those evaluations ran, summed: nfe * batch for every sampler but lt_sample_ode_cfg_schedule, whose conditional-only stages run half */
+int64_t lt_last_eval_rows(lt_engine* e);
 /* model evaluations served by replaying a captured HIP graph since lt_create (0 with lt_set_option("graph", 0), and below 1025 rows under the default "graph" 2) */
 int64_t lt_graph_replays(lt_engine* e);
 

@@ -99,7 +99,10 @@ extern "C" {
  *                       | 0: row-major everywhere.  Packed batches (lt_forward_packed and its kin) take the regime too when their
  *                       attention runs on the head_dim-72 one-wave kernel (longest sequence a multiple of 64).
  *                       lt_engine_get_option(e, "last_pair", &v) - read-only, no option, e != NULL - says whether the engine's last
- *                       evaluation ran in this regime (1) or row-major (0)
+ *                       evaluation ran in this regime (1) or row-major (0); "layout_flips" - read-only too - is the number of times the
+ *                       weights were converted between the two layouts during the engine's last whole-trajectory sampler call (each
+ *                       conversion rewrites every GEMM weight once; a guidance schedule that alternates between a 2 B'-row and a B'-row
+ *                       evaluation on different sides of the threshold pays it at every change)
  * (the round-1 names gemm_pipeline / gemm_pp_tail / gemm_persist are accepted with value 0 only: the study kernels they selected were
  *  deleted with csrc/experimental/ in round 5) */
 
@@ -191,6 +194,12 @@ int lt_op_cap_pool_ln(const void* cap, int32_t cap_dtype, const void* mask, cons
                       int32_t C, void* stream);
 int lt_op_unpatchify_cfg(const void* rows, int32_t ld, void* out, int32_t out_dtype, int32_t B, int32_t C, int32_t out_ch, int32_t H, int32_t W,
                          int32_t patch, int32_t use_cfg, float cfg_scale, int32_t cfg_channels, int32_t wp_stride, void* stream);
+/* lt_op_unpatchify_cfg with the scale read from one float of device memory (cfg_scale_dev; may be NULL with use_cfg 0 or dup) and, with dup != 0,
+ * the conditional-only form: rows holds B / 2 samples, sample b is written, all channels, to rows b and b + B / 2 of out (use_cfg and the scale
+ * play no part).  B counts the rows of out.  Same guidance chain and rounding points as lt_op_unpatchify_cfg. */
+int lt_op_unpatchify_cfg_dev(const void* rows, int32_t ld, void* out, int32_t out_dtype, int32_t B, int32_t C, int32_t out_ch, int32_t H, int32_t W,
+                             int32_t patch, int32_t use_cfg, const float* cfg_scale_dev, int32_t cfg_channels, int32_t wp_stride, int32_t dup,
+                             void* stream);
 /* The ragged boundary kernels of a packed batch (csrc/packed.hip): one launch for all samples.  hw_host = [B][2] latent sizes (host); the
  * flat state holds sample b = [C, H_b, W_b] at element offset sum_{j<b} C H_j W_j; N = token rows per sample in the row buffers (>= the longest
  * sequence).  Each launching entry builds the table of the size list, stores it at tab_dev (5 * 64 ints of device memory) and runs its kernel.

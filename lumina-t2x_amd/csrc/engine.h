@@ -137,6 +137,9 @@ struct lt_engine {
     // layout the persistent GEMM reads with whole-line requests (GemmArgs::pair_ab); ensure_weight_layout converts all of them in place when an
     // evaluation needs the other one (a change of regime: >= one tile per CU <-> the small-M kernels).  last_pair: what the last run_forward used.
     bool w_pair = false, last_pair = false;
+    // conversions of the weights between the two layouts: since lt_create, and during the last whole-trajectory sampler call
+    // (lt_engine_get_option "layout_flips"; DESIGN 7g: a guidance schedule whose two evaluation sizes fall into different regimes)
+    long long layout_flips_total = 0, layout_flips = 0;
     // workspace
     u16 *x = nullptr, *h = nullptr, *qkv = nullptr, *q = nullptr, *k = nullptr, *vt = nullptr, *attn = nullptr;
     u16 *o = nullptr, *u = nullptr, *patches = nullptr, *frows = nullptr, *mod = nullptr;
@@ -192,6 +195,7 @@ struct lt_engine {
     int pk_host[128] = {0};
     int* pk_tab = nullptr;     // packed batches on a flat state (lt_forward_cfg_packed / lt_sample_ode_packed): the device PackedTable (kernels.h)
     long long last_nfe = 0;
+    long long last_eval_rows = 0;  // lt_last_eval_rows: the rows the last sampler call's evaluations ran, summed
     // multi-view sampling (lt_set_views / lt_sample_views, views.hip): engine-owned tables of the V views over an h x w latent
     int *vw_perm = nullptr, *vw_iperm = nullptr, *vw_hits = nullptr;  // [V][h w], [V][h w], [V h w + 1]
     float *vw_vsign = nullptr, *vw_isign = nullptr;                   // [V][in_channels]
@@ -204,6 +208,7 @@ struct lt_engine {
     std::vector<GraphEntry> graphs;
     void *g_x = nullptr, *g_out = nullptr;
     float* g_t = nullptr;
+    float* g_cfg = nullptr;  // the guidance scale of an evaluation that reads it from device memory (lt_sample_ode_cfg_schedule)
     hipStream_t cap_stream = nullptr;
     long long graph_replays = 0;
     // profiling
@@ -224,8 +229,12 @@ struct PackedCall {
 int packed_call_begin(lt_engine* e, const char* who, const int32_t* hw_host, const lt_step_args* a, int use_cfg, PackedCall* pc, hipStream_t s);
 // one model evaluation [+ CFG combine], through a cached HIP graph where that pays (engine.hip); pc: x_in / out are the flat state of a
 // packed batch
+// cfg_dev (lt_sample_ode_cfg_schedule; tensor input only): the evaluation's guidance scale, one float of device memory; it is staged into
+// e->g_cfg, which the closing kernel reads, so the scale is no part of the graph key and a->cfg_scale is ignored.  With cond_only the
+// evaluation is the plain forward of the first a->batch / 2 rows of x_in on the first a->batch / 2 rows of the conditioning that was prepared
+// for a->batch rows, and its output is written to both halves of `out` (a->batch rows)
 int forward_graphed(lt_engine* e, const void* x_in, const float* t_dev, void* out, const lt_step_args* a, int use_cfg, hipStream_t s,
-                    const PackedCall* pc = nullptr);
+                    const PackedCall* pc = nullptr, const float* cfg_dev = nullptr, bool cond_only = false);
 // the softmax scale of an evaluation of N tokens under the engine's rule (model.py:373-376, visual_anagrams/models/nextdit.py:331-335), and the
 // refusal of a shape the anagram fork's query chunks do not cover; non-zero after lt_set_error (engine.hip)
 int softmax_scale_for(const lt_engine* e, const lt_step_args* a, int N, float* scale);

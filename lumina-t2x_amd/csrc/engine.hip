@@ -389,11 +389,16 @@ int ensure_weight_layout(lt_engine* e, bool want, hipStream_t s) {
         }
     }
     e->w_pair = want;
+    ++e->layout_flips_total;
     return 0;
 }
 
+// An evaluation of the guidance schedule (forward_graphed's cfg_dev): the closing kernel reads its scale from `scale` (device memory); dup:
+// the conditional-only evaluation - a->batch rows on the first a->batch rows of a conditioning prepared for 2 a->batch, written twice
+struct CfgFromDev { const float* scale; bool dup; };
+
 int run_forward(lt_engine* e, const void* x_in, const float* t_dev, void* out, const lt_step_args* a, int use_cfg,
-                hipStream_t s, const PackedDesc* pk = nullptr) {
+                hipStream_t s, const PackedDesc* pk = nullptr, const CfgFromDev* gs = nullptr) {
     const lt_config& c = e->cfg;
     const VariantDesc& v = e->v;
     const int B = a->batch, p = c.patch_size;
@@ -427,8 +432,9 @@ int run_forward(lt_engine* e, const void* x_in, const float* t_dev, void* out, c
     if (v.rope_1d) LT_REQUIRE(N <= e->rope_len, "sequence of %d tokens exceeds the 1-D RoPE table (%d)", N, e->rope_len);
     else LT_REQUIRE(Hp <= e->rope_len && Wp <= e->rope_len, "latent grid exceeds the RoPE table (%d)", e->rope_len);
     LT_REQUIRE(a->io_dtype == LT_BF16 || a->io_dtype == LT_F32, "io_dtype must be bf16 or f32");
-    LT_REQUIRE(e->prompt_B == B, "%s was called for batch %d, step has batch %d", v.labels ? "lt_prepare_labels" : "lt_prepare_prompt",
-               e->prompt_B, B);
+    // (the conditioning buffers are batch-major: the first B rows of one prepared for 2 B are what a preparation of those rows alone leaves)
+    LT_REQUIRE(e->prompt_B == B || (gs && gs->dup && !pk && e->prompt_B == 2 * B), "%s was called for batch %d, step has batch %d",
+               v.labels ? "lt_prepare_labels" : "lt_prepare_prompt", e->prompt_B, gs && gs->dup ? 2 * B : B);
     LT_REQUIRE(e->reg_Y == 0 || (B == 2 && !pk), "regional captions: one image per call (batch 2 = cond + uncond row), tensor input");
     if (!e->weights_ok && lt_weights_ready(e)) return 2;
     const int d = e->d, L = e->L, H = e->H, Hkv = e->Hkv, hd = e->hd, F = e->F, dkv = e->dkv, A = e->A;
@@ -783,7 +789,10 @@ int run_forward(lt_engine* e, const void* x_in, const float* t_dev, void* out, c
     {
         ProfScope ps(e, 2, 0, s);
         const int cfg_ch = a->cfg_channels > 0 ? a->cfg_channels : 3;
-        if (!pk) {
+        if (!pk && gs) {
+            if (launch_unpatchify_cfg_dev(e->frows, e->nfinal, out, a->io_dtype, gs->dup ? 2 * B : B, c.in_channels, c.out_channels, a->latent_h,
+                                          a->latent_w, p, use_cfg, gs->scale, cfg_ch, Wrow, gs->dup ? 1 : 0, s)) return 1;
+        } else if (!pk) {
             if (launch_unpatchify_cfg(e->frows, e->nfinal, out, a->io_dtype, B, c.in_channels, c.out_channels, a->latent_h,
                                       a->latent_w, p, use_cfg, a->cfg_scale, cfg_ch, Wrow, s)) return 1;
         } else if (pk->tab) {
@@ -842,10 +851,25 @@ int softmax_scale_for(const lt_engine* e, const lt_step_args* a, int N, float* s
 }
 
 int forward_graphed(lt_engine* e, const void* x_in, const float* t_dev, void* out, const lt_step_args* a, int use_cfg, hipStream_t s,
-                    const PackedCall* pc) {
+                    const PackedCall* pc, const float* cfg_dev, bool cond_only) {
+    // a stage of the guidance schedule: the scale travels through e->g_cfg - on the eager path too, so both run one kernel - and the key
+    // holds a zeroed cfg_scale; the conditional-only evaluation has a->batch / 2 rows
+    lt_step_args own;
+    const CfgFromDev cfd{e->g_cfg, cond_only};
+    const CfgFromDev* cd = nullptr;
+    if (cfg_dev) {
+        LT_REQUIRE(!pc && a->batch % 2 == 0, "a guidance schedule needs a tensor state with an even batch");
+        own = *a;
+        own.cfg_scale = 0.f;
+        if (cond_only) own.batch = a->batch / 2;
+        else LT_CHECK_HIP(hipMemcpyAsync(e->g_cfg, cfg_dev, sizeof(float), hipMemcpyDeviceToDevice, s));
+        a = &own;
+        use_cfg = cond_only ? 0 : 1;
+        cd = &cfd;
+    }
     // one evaluation as plain launches; a packed batch's flat state goes through the ragged kernels
     auto run = [&](const void* x, const float* t, void* o, hipStream_t st) {
-        if (!pc) return run_forward(e, x, t, o, a, use_cfg, st);
+        if (!pc) return run_forward(e, x, t, o, a, use_cfg, st, nullptr, cd);
         PackedDesc pk{nullptr, nullptr, pc->hw};
         pk.x_flat = x; pk.out_flat = o; pk.tab = e->pk_tab;
         return run_forward(e, nullptr, t, nullptr, a, use_cfg, st, &pk);
@@ -864,11 +888,12 @@ int forward_graphed(lt_engine* e, const void* x_in, const float* t_dev, void* ou
         return run(x_in, t_dev, out, s);  // let the eager path produce the error message
     const size_t sbytes = (pc ? (size_t)pc->elems : (size_t)B * e->cfg.in_channels * a->latent_h * a->latent_w) * (a->io_dtype == LT_BF16 ? 2 : 4);
     const size_t cap_bytes = (size_t)e->cfg.max_batch * e->cfg.in_channels * e->cfg.max_tokens * e->cfg.patch_size * e->cfg.patch_size * 4;
-    if (sbytes > cap_bytes) return run(x_in, t_dev, out, s);
+    if ((cond_only ? 2 * sbytes : sbytes) > cap_bytes) return run(x_in, t_dev, out, s);
     // (both option generations: the process defaults' and this engine's overrides' - kernel selection is baked into a captured graph)
     // ... and the softmax rule: the scale it selects is a kernel argument (qa.out_scale / at.scale)
-    const int extra[10] = {use_cfg, e->prompt_B, e->prompt_T, e->prompt_Tpad, e->reg_Y, e->reg_h, e->reg_w, lt_opt_generation(), lt_opt_engine_generation(),
-                           e->softmax_rule};
+    // ... and whether the scale comes from device memory / the evaluation is the conditional-only one: other closing kernels
+    const int extra[12] = {use_cfg, e->prompt_B, e->prompt_T, e->prompt_Tpad, e->reg_Y, e->reg_h, e->reg_w, lt_opt_generation(), lt_opt_engine_generation(),
+                           e->softmax_rule, cd ? 1 : 0, cond_only ? 1 : 0};
     std::vector<char> key(sizeof(lt_step_args) + sizeof(extra));
     memcpy(key.data(), a, sizeof(lt_step_args));
     memcpy(key.data() + sizeof(lt_step_args), extra, sizeof(extra));
@@ -926,7 +951,7 @@ int forward_graphed(lt_engine* e, const void* x_in, const float* t_dev, void* ou
     LT_CHECK_HIP(hipMemcpyAsync(e->g_t, t_dev, (size_t)B * sizeof(float), hipMemcpyDeviceToDevice, s));
     LT_CHECK_HIP(hipGraphLaunch(ge->exec, s));
     e->last_pair = ge->pair;  // (a replay is an evaluation too: "last_pair" of lt_engine_get_option names the regime of the last one)
-    LT_CHECK_HIP(hipMemcpyAsync(out, e->g_out, sbytes, hipMemcpyDeviceToDevice, s));
+    LT_CHECK_HIP(hipMemcpyAsync(out, e->g_out, cond_only ? 2 * sbytes : sbytes, hipMemcpyDeviceToDevice, s));
     ++e->graph_replays;
     if (e->prof_on)
         for (int k = 0; k < 3; ++k)
@@ -1138,6 +1163,8 @@ extern "C" int lt_create(const lt_config* cfg, lt_engine** out) {
             void* q;
             if (dev_alloc(e, &q, Bm * sizeof(float))) return fail();
             e->g_t = (float*)q;
+            if (dev_alloc(e, &q, sizeof(float))) return fail();
+            e->g_cfg = (float*)q;
         }
         for (int i = 0; i < 4; ++i) { if (dev_alloc(e, &e->kbuf[i], state)) return fail(); }
     }
@@ -1560,6 +1587,11 @@ extern "C" int lt_engine_get_option(lt_engine* e, const char* name, int32_t* val
     if (strcmp(name, "last_pair") == 0) {  // read-only, no option: the operand layout regime of the engine's last evaluation (lumina_dit_debug.h)
         LT_REQUIRE(e, "lt_engine_get_option: last_pair: null engine");
         *value = e->last_pair ? 1 : 0;
+        return 0;
+    }
+    if (strcmp(name, "layout_flips") == 0) {  // read-only, no option: weight layout conversions during the last sampler call (lumina_dit_debug.h)
+        LT_REQUIRE(e, "lt_engine_get_option: layout_flips: null engine");
+        *value = (int32_t)std::min<long long>(e->layout_flips, INT32_MAX);
         return 0;
     }
     const int id = lt_opt_find(name);

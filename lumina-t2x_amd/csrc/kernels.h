@@ -352,6 +352,10 @@ int launch_mask_to_bias(const int32_t* mask, float* bias, int B, int T, int Tpad
 // optional CFG combine on cfg_channels (model.py:908-913); out [B,C,H,W] bf16/f32
 int launch_unpatchify_cfg(const u16* rows, int ld, void* out, int out_dtype, int B, int C, int out_ch, int H, int W,
                           int patch, int use_cfg, float cfg_scale, int cfg_channels, int wp_stride, hipStream_t stream);
+// the same with the scale read from device memory (a captured graph serves every scale) and, with `dup`, a conditional-only evaluation:
+// B / 2 rows read, each written to rows b and b + B / 2 of the output.  B counts output rows.  (lt_sample_ode_cfg_schedule)
+int launch_unpatchify_cfg_dev(const u16* rows, int ld, void* out, int out_dtype, int B, int C, int out_ch, int H, int W, int patch, int use_cfg,
+                              const float* cfg_scale_dev, int cfg_channels, int wp_stride, int dup, hipStream_t stream);
 // torchdiffeq fixed-grid state arithmetic (modes documented in misc.hip)
 int launch_ode_combine(int mode, const void* y0, const void* k1, const void* k2, const void* k3, const void* k4,
                        void* out, int dtype, float dt, long long n, hipStream_t stream);

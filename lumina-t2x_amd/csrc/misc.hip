@@ -285,6 +285,40 @@ __global__ void unpatchify_cfg_kernel(const u16* __restrict__ rows, int ld, void
     }
 }
 
+// unpatchify_cfg_kernel for the guidance schedule (lt_sample_ode_cfg_schedule): the scale is read from device memory, so a captured
+// graph serves every scale, and with `dup` a conditional-only evaluation's B / 2 rows are written to rows b and b + B / 2 of the output - the
+// stage's cat([o, o]) without a copy.  B counts OUTPUT rows.  Same index walk, same guidance chain and rounding points as the kernel above.
+__global__ void unpatchify_cfg_dev_kernel(const u16* __restrict__ rows, int ld, void* __restrict__ out, int out_dtype, int B, int C, int out_ch,
+                                          int H, int W, int patch, int use_cfg, const float* __restrict__ cfg_scale_dev, int cfg_channels,
+                                          int wp_stride, int dup) {
+#pragma clang fp contract(off)  // every step of the guidance chain rounds on its own, as the tensor expression does
+    const long long total = (long long)B * C * H * W;
+    const int Hp = H / patch;
+    const int half = B / 2;
+    const float cfg_scale = (use_cfg && !dup) ? cfg_scale_dev[0] : 0.f;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const int w = (int)(i % W);
+        const int hh = (int)((i / W) % H);
+        const int c = (int)((i / ((long long)W * H)) % C);
+        const int b = (int)(i / ((long long)W * H * C));
+        const int e = ((hh % patch) * patch + (w % patch)) * out_ch + c;
+        const long long tok = (long long)(hh / patch) * wp_stride + (w / patch);  // eol column (if any) is skipped
+        auto rd = [&](int bb) { return bf2f(rows[((long long)bb * Hp * wp_stride + tok) * ld + e]); };
+        float v;
+        if (dup) {
+            v = rd(b % half);
+        } else if (use_cfg && c < cfg_channels) {
+            const int bc = b % half;
+            const float cond = rd(bc), unc = rd(bc + half);
+            v = bfr(unc + bfr(cfg_scale * bfr(cond - unc)));
+        } else {
+            v = rd(b);
+        }
+        if (out_dtype == 0) ((float*)out)[i] = v;
+        else ((u16*)out)[i] = f2bf(v);
+    }
+}
+
 // torchdiffeq fixed-grid solver arithmetic on the ODE state (euler / midpoint / rk4 "3/8 rule",
 // torchdiffeq rk_common.rk4_alt_step_func).  With a bf16 state every tensor op of the Python expression
 // rounds to bf16 (a 0-dim fp32 dt times a bf16 tensor stays bf16 AND sees dt cast to bf16 first - the caller passes
@@ -533,6 +567,22 @@ int launch_unpatchify_cfg(const u16* rows, int ld, void* out, int out_dtype, int
     if (g > 8192) g = 8192;
     hipLaunchKernelGGL(unpatchify_cfg_kernel, dim3(g), dim3(256), 0, stream, rows, ld, out, out_dtype, B, C, out_ch, H,
                        W, patch, use_cfg, cfg_scale, cfg_channels, wp_stride > 0 ? wp_stride : W / patch);
+    LT_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+int launch_unpatchify_cfg_dev(const u16* rows, int ld, void* out, int out_dtype, int B, int C, int out_ch, int H, int W, int patch, int use_cfg,
+                              const float* cfg_scale_dev, int cfg_channels, int wp_stride, int dup, hipStream_t stream) {
+    LT_REQUIRE(rows && out, "unpatchify_cfg_dev: null argument");
+    LT_REQUIRE(B >= 1 && C >= 1 && out_ch >= C && patch >= 1 && H >= patch && W >= patch && H % patch == 0 && W % patch == 0 &&
+               ld >= patch * patch * out_ch, "unpatchify_cfg_dev: bad shape");
+    LT_REQUIRE(!(use_cfg || dup) || B % 2 == 0, "unpatchify_cfg_dev: guidance and dup need an even count of output rows");
+    LT_REQUIRE(dup || !use_cfg || cfg_scale_dev, "unpatchify_cfg_dev: null scale");
+    const long long total = (long long)B * C * H * W;
+    int g = nblk(total, 256);
+    if (g > 8192) g = 8192;
+    hipLaunchKernelGGL(unpatchify_cfg_dev_kernel, dim3(g), dim3(256), 0, stream, rows, ld, out, out_dtype, B, C, out_ch, H, W, patch, use_cfg,
+                       cfg_scale_dev, cfg_channels, wp_stride > 0 ? wp_stride : W / patch, dup);
     LT_CHECK_HIP(hipGetLastError());
     return 0;
 }

@@ -1,5 +1,6 @@
 // Whole-trajectory samplers of the C ABI (include/lumina_dit.h): the fixed-grid ODE loop of transport/integrators.py:104-116 (torchdiffeq
-// euler / midpoint / rk4), multi-view (visual-anagram) sampling, the SDE loop and the adaptive Runge-Kutta loop.  One call per trajectory, no
+// euler / midpoint / rk4; with an inpainting mask; with a guidance scale per stage), multi-view (visual-anagram) sampling, the SDE loop and the
+// adaptive Runge-Kutta loop.  One call per trajectory, no
 // host<->device sync inside it (the adaptive loop reads one error ratio per attempted step).  All
 // are written against one scaffold - check_step_shape, StageTimes (engine.h), Trajectory - and a new sampler is too: what a sampler
 // owns is its stage-time fill loop and its stepping body, where the reference's rounding points are.
@@ -28,16 +29,19 @@ int check_step_shape(const lt_engine* e, const char* who, const lt_step_args* a)
     return 0;
 }
 
-// The state of one trajectory: the ping-pong pair e->ys, the caller's record of the states (if any), the evaluation count.
+// The state of one trajectory: the ping-pong pair e->ys, the caller's record of the states (if any), the evaluation and row counts.
 struct Trajectory {
     lt_engine* e; const lt_step_args* a; int use_cfg; hipStream_t s;
     size_t sbytes;  // one state
     void* traj = nullptr;
     int cur = 0;
-    long long nfe = 0;
+    long long nfe = 0, rows = 0, flips0 = 0;
     const PackedCall* pc = nullptr;  // a packed batch: the states are flat buffers (lt_sample_ode_packed)
+    // a guidance schedule (lt_sample_ode_cfg_schedule): the scale of evaluation number `call`, on the host and where commit sent it
+    const float *cfg_host = nullptr, *cfg_dev = nullptr;
     int start(const void* z, void* traj_dev, bool z_in_slot0) {
         traj = traj_dev;
+        flips0 = e->layout_flips_total;
         LT_CHECK_HIP(hipMemcpyAsync(e->ys[0], z, sbytes, hipMemcpyDeviceToDevice, s));
         if (traj && z_in_slot0) LT_CHECK_HIP(hipMemcpyAsync(traj, z, sbytes, hipMemcpyDeviceToDevice, s));
         return 0;
@@ -45,7 +49,15 @@ struct Trajectory {
     void* y0() const { return e->ys[cur]; }      // the current state
     void* y1() const { return e->ys[cur ^ 1]; }  // where the step writes the next one
     // one model evaluation at stage time number `call` of the committed table
-    int eval(const void* y, int call, void* out) { ++nfe; return forward_graphed(e, y, e->times.dev + (size_t)call * a->batch, out, a, use_cfg, s, pc); }
+    int eval(const void* y, int call, void* out) {
+        ++nfe;
+        const float* t = e->times.dev + (size_t)call * a->batch;
+        if (!cfg_host) { rows += a->batch; return forward_graphed(e, y, t, out, a, use_cfg, s, pc); }
+        // scale 1 exactly: the guided output is the conditional one - the cond rows alone, written to both halves
+        const bool cond_only = cfg_host[call] == 1.0f;
+        rows += cond_only ? a->batch / 2 : a->batch;
+        return forward_graphed(e, y, t, out, a, 1, s, nullptr, cfg_dev + call, cond_only);
+    }
     int advance(int traj_slot) {  // y1 is the current state now [and slot `traj_slot` of the record]
         if (traj) LT_CHECK_HIP(hipMemcpyAsync((char*)traj + (size_t)traj_slot * sbytes, y1(), sbytes, hipMemcpyDeviceToDevice, s));
         cur ^= 1;
@@ -54,6 +66,8 @@ struct Trajectory {
     int finish(void* final_dev) {  // (null: not asked for, or the last step's kernel wrote it)
         if (final_dev) LT_CHECK_HIP(hipMemcpyAsync(final_dev, y0(), sbytes, hipMemcpyDeviceToDevice, s));
         e->last_nfe = nfe;
+        e->last_eval_rows = rows;
+        e->layout_flips = e->layout_flips_total - flips0;
         return 0;
     }
 };
@@ -70,18 +84,22 @@ float bf16_round_host(float f) {
 // The fixed-grid loop of lt_sample_ode and lt_sample_ode_packed: stage-time fill and the euler / midpoint / rk4 stepping body on a state of
 // n elements (the stage arithmetic is elementwise, so a packed batch's flat state runs through it as it is).  The callers have validated
 // the grid, the method and the shape.  With `mb` (lt_sample_ode_masked) the LAST combine of every step is the masked launcher - the same
-// arithmetic followed by the inpainting blend at the step's end time - and nothing else changes.
+// arithmetic followed by the inpainting blend at the step's end time - and nothing else changes.  With `cs` (lt_sample_ode_cfg_schedule)
+// evaluation i * stages + k takes its guidance scale from cs->table: the scales are committed behind the stage times, one float per stage.
 struct MaskedBlend { const void *mask, *x1, *noise; };
+struct CfgSchedule { const float* table; };  // host, (n_grid - 1) * stages
 
 int ode_fixed_grid(lt_engine* e, const void* z_dev, void* traj_dev, void* final_dev, const float* tgrid_host, int n_grid, int method, int use_cfg,
-                   int t_round, const lt_step_args* a, hipStream_t s, long long n, const PackedCall* pc, const MaskedBlend* mb = nullptr) {
+                   int t_round, const lt_step_args* a, hipStream_t s, long long n, const PackedCall* pc, const MaskedBlend* mb = nullptr,
+                   const CfgSchedule* cs = nullptr) {
     const int B = a->batch;
     const int stages = method == LT_ODE_EULER ? 1 : (method == LT_ODE_MIDPOINT ? 2 : 4);
     const int ncalls = (n_grid - 1) * stages;
     const bool bf = a->io_dtype == LT_BF16;
     // stage times; torchdiffeq's _PerturbFunc casts t to the state dtype before calling the model, then
     // integrators.py:108 broadcasts it to an fp32 [B] vector
-    float* tp = e->times.begin(ncalls * B, s);
+    const int nsent = ncalls * B + (cs ? ncalls : 0);
+    float* tp = e->times.begin(nsent, s);
     if (!tp) return 1;
     std::vector<float> dts(n_grid - 1);
     for (int i = 0; i + 1 < n_grid; ++i) {
@@ -97,9 +115,11 @@ int ode_fixed_grid(lt_engine* e, const void* z_dev, void* traj_dev, void* final_
             for (int b = 0; b < B; ++b) tp[((size_t)i * stages + k) * B + b] = tv;
         }
     }
-    if (e->times.commit(ncalls * B, s)) return 1;
+    if (cs) memcpy(tp + (size_t)ncalls * B, cs->table, (size_t)ncalls * sizeof(float));
+    if (e->times.commit(nsent, s)) return 1;
     Trajectory tr{e, a, use_cfg, s, (size_t)n * (bf ? 2 : 4)};
     tr.pc = pc;
+    if (cs) { tr.cfg_host = cs->table; tr.cfg_dev = e->times.dev + (size_t)ncalls * B; }
     if (tr.start(z_dev, traj_dev, true)) return 1;
     const int dt_code = bf ? 1 : 0;
     for (int i = 0; i + 1 < n_grid; ++i) {
@@ -198,6 +218,27 @@ extern "C" int lt_sample_ode_masked_packed(lt_engine* e, const void* z_flat_dev,
     const MaskedBlend mb{mask_flat_dev, x1_flat_dev, noise_flat_dev};
     return ode_fixed_grid(e, z_flat_dev, traj_flat_dev, final_flat_dev, tgrid_host, n_grid, method, use_cfg, t_round, a, (hipStream_t)stream, pc.elems,
                           &pc, &mb);
+}
+
+// ---- guidance schedules: a scale per stage, conditional-only stages at half the rows --------------------------------------
+extern "C" int lt_sample_ode_cfg_schedule(lt_engine* e, const void* z_dev, void* traj_dev, void* final_dev, const float* tgrid_host, int32_t n_grid,
+                                          int32_t method, const float* cfg_host, int32_t t_round, const lt_step_args* a, void* stream) {
+    LT_REQUIRE(e && z_dev && tgrid_host && cfg_host && a, "lt_sample_ode_cfg_schedule: null argument");
+    LtOptScope opt_scope(&e->opts);
+    LT_REQUIRE(n_grid >= 2, "lt_sample_ode_cfg_schedule: need at least 2 grid points");
+    LT_REQUIRE(method >= LT_ODE_EULER && method <= LT_ODE_RK4, "lt_sample_ode_cfg_schedule: unknown method %d", method);
+    if (check_step_shape(e, "lt_sample_ode_cfg_schedule", a)) return 2;
+    LT_REQUIRE(a->batch % 2 == 0, "lt_sample_ode_cfg_schedule: guidance needs an even batch (cond + uncond rows), got %d", a->batch);
+    const int stages = method == LT_ODE_EULER ? 1 : (method == LT_ODE_MIDPOINT ? 2 : 4);
+    for (int i = 0; i < (n_grid - 1) * stages; ++i)
+        LT_REQUIRE(std::isfinite(cfg_host[i]), "lt_sample_ode_cfg_schedule: the scale of stage %d of interval %d is not finite", i % stages, i / stages);
+    LT_REQUIRE(e->reg_Y == 0, "lt_sample_ode_cfg_schedule: a regional prompt is prepared (lt_prepare_prompt_regional): its captions belong to "
+               "one cond and one uncond row, there is no conditional half to evaluate alone");
+    LT_REQUIRE(e->prompt_B == a->batch, "lt_sample_ode_cfg_schedule: %s was called for batch %d, step has batch %d",
+               e->v.labels ? "lt_prepare_labels" : "lt_prepare_prompt", e->prompt_B, a->batch);
+    const long long n = (long long)a->batch * e->cfg.in_channels * a->latent_h * a->latent_w;
+    const CfgSchedule cs{cfg_host};
+    return ode_fixed_grid(e, z_dev, traj_dev, final_dev, tgrid_host, n_grid, method, 1, t_round, a, (hipStream_t)stream, n, nullptr, nullptr, &cs);
 }
 
 // ---- multi-view (visual-anagram) sampling ------------------------------------------------------------------------------------------
@@ -652,3 +693,4 @@ extern "C" int lt_sample_ode_adaptive(lt_engine* e, const void* z_dev, void* tra
 }
 
 extern "C" int64_t lt_last_nfe(lt_engine* e) { return e ? e->last_nfe : -1; }
+extern "C" int64_t lt_last_eval_rows(lt_engine* e) { return e ? e->last_eval_rows : -1; }

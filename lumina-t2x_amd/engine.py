@@ -403,6 +403,33 @@ class DiTEngine:
             return [out[:, off:off + math.prod(shape)].view((n,) + shape) for off, shape in spans]
         return [out[off:off + math.prod(shape)].view(shape) for off, shape in spans]
 
+    # ---- guidance schedules: a scale per stage, conditional-only stages at half the rows -------------
+    def sample_ode_cfg_schedule(self, z: torch.Tensor, tgrid, table, method: str, *, scale_factor: float = 1.0, scale_watershed: float = 1.0,
+                                base_seqlen: Optional[int] = None, proportional_attn: bool = False, t_round_to_state_dtype: bool = True,
+                                return_trajectory: bool = True, ntk_factor: float = 1.0, cfg_scale=None) -> torch.Tensor:
+        """``sample_ode`` with guidance whose scale is ``table[i * stages + k]`` at stage k of interval i (lt_sample_ode_cfg_schedule): stages
+        at scale 1 exactly evaluate the ``z.size(0) / 2`` cond rows alone.  ``table``: ``(len(tgrid) - 1) * stages`` fp32 values (a tensor or a
+        sequence; ``transport.guidance.cfg_table`` builds one).  The conditioning was prepared for all rows, once.  ``cfg_scale`` is ignored."""
+        _require_gpu(z, "z")
+        if method not in _lib.ODE_METHODS:
+            raise LuminaLibError(f"fixed-grid method '{method}' not in {sorted(_lib.ODE_METHODS)}")
+        z = z.contiguous()
+        garr, n = _grid_array(tgrid)
+        tab = table if isinstance(table, torch.Tensor) else torch.tensor(list(table), dtype=torch.float32)
+        tab = tab.detach().to("cpu", torch.float32).reshape(-1).contiguous()
+        stages = {"euler": 1, "midpoint": 2, "rk4": 4}[method]
+        if tab.numel() != max(n - 1, 0) * stages:
+            raise LuminaLibError(f"sample_ode_cfg_schedule: the table has {tab.numel()} entries, a {n}-point {method} grid has "
+                                 f"{max(n - 1, 0) * stages} stages")
+        a = self._step_args(z, 0.0, scale_factor, scale_watershed, base_seqlen, proportional_attn, ntk_factor=ntk_factor)
+        out, traj_ptr, fin_ptr = _traj_or_final(z, max(n, 1), z.shape, return_trajectory)
+        with torch.cuda.device(self.device):
+            rc = self.lib.lt_sample_ode_cfg_schedule(self.handle, C.c_void_p(z.data_ptr()), traj_ptr, fin_ptr, garr, n, _lib.ODE_METHODS[method],
+                                                     C.cast(tab.data_ptr(), C.POINTER(C.c_float)), int(t_round_to_state_dtype), C.byref(a),
+                                                     C.c_void_p(_stream_ptr(self.device)))
+        _lib.check(rc, "lt_sample_ode_cfg_schedule")
+        return out
+
     def sample_ode_adaptive(self, z: torch.Tensor, tgrid: torch.Tensor, method: str, *, rtol: float, atol: float,
                             first_step: Optional[float] = None, max_steps: int = 2 ** 31 - 1, use_cfg: bool, cfg_scale: float = 1.0,
                             scale_factor: float = 1.0, scale_watershed: float = 1.0, base_seqlen: Optional[int] = None,
@@ -578,6 +605,10 @@ class DiTEngine:
 
     def last_nfe(self) -> int:
         return int(self.lib.lt_last_nfe(self.handle))
+
+    def last_eval_rows(self) -> int:
+        """the rows the last sampler call's evaluations ran, summed (``last_nfe() * batch`` unless conditional-only stages ran half)"""
+        return int(self.lib.lt_last_eval_rows(self.handle))
 
     def graph_replays(self) -> int:
         """model evaluations served by a captured HIP graph so far"""

@@ -105,6 +105,8 @@ class DiT_Llama(EngineBackedModel):
                     out_channels=self.out_channels, cap_feat_dim=0, qk_norm=self.qk_norm, norm_eps=self.norm_eps,
                     num_classes=self.y_embedder.embedding_table.weight.shape[0] - 1)
 
+    _cond_names = ("y",)
+
     def _call(self, x, t, y, use_cfg, cfg_scale=1.0):
         eng = self.engine(x)
         eng.prepare_labels(y)

@@ -170,7 +170,11 @@ def run(args, *, encode_fn=None, cap_feat_dim=None, decode_fn=None, model=None) 
             kw.update(scale_factor=math.sqrt(w * h / train_args.image_size ** 2), scale_watershed=args.scaling_watershed)
         else:
             kw.update(scale_factor=1.0, scale_watershed=1.0)
-        latent = sample_fn(z, model.forward_with_cfg, **kw)[-1][:1]
+        table = guidance_table(args, sample_fn.__self__.t)
+        if table is None:
+            latent = sample_fn(z, model.forward_with_cfg, **kw)[-1][:1]
+        else:  # a scale per stage; stages at scale 1 evaluate the cond row alone (transport/guidance.py)
+            latent = sample_fn(z, model.forward_with_cfg, cfg_table=table, **kw)[-1][:1]
         stem = os.path.join(out_dir, "images", f"{args.sampling_method}_{args.num_sampling_steps}_{idx}_{res.split(':')[-1]}")
         if decode_fn is not None:
             save_png(decode_fn(latent / factor)[0], stem + ".png")
@@ -185,12 +189,29 @@ def run(args, *, encode_fn=None, cap_feat_dim=None, decode_fn=None, model=None) 
     return info
 
 
+def guidance_table(args, tgrid):
+    """``--cfg_interval`` / ``--cfg_schedule`` as the scale table of ``transport.guidance.cfg_table``; None: one scale for every stage (the
+    sampler's plain path)"""
+    interval, kind = getattr(args, "cfg_interval", None), getattr(args, "cfg_schedule", "constant")
+    if interval is None and kind == "constant":
+        return None
+    from .transport import guidance
+    t0, t1 = float(tgrid[0]), float(tgrid[-1])
+    schedule = {"constant": None, "linear": guidance.linear_schedule(args.cfg_scale, t0, t1),
+                "cosine": guidance.cosine_schedule(args.cfg_scale, t0, t1)}[kind]
+    return guidance.cfg_table(tgrid, args.sampling_method, args.cfg_scale, interval=interval, schedule=schedule)
+
+
 def build_parser() -> argparse.ArgumentParser:
     def none_or_str(v):
         return None if v == "None" else v
 
     p = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     p.add_argument("--cfg_scale", type=float, default=4.0)
+    p.add_argument("--cfg_interval", type=float, nargs=2, default=None, metavar=("LO", "HI"),
+                   help="guide only the stages with LO <= t < HI (t = 0 noise, 1 data); the others evaluate the prompt row alone")
+    p.add_argument("--cfg_schedule", type=str, default="constant", choices=["constant", "linear", "cosine"],
+                   help="how the scale moves from --cfg_scale at the first grid point to 1 at the last")
     p.add_argument("--num_sampling_steps", type=int, default=250)
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--ckpt", type=str, required=True)

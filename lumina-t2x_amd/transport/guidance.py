@@ -1,0 +1,178 @@
+"""Guidance schedules: fixed-grid ODE sampling whose classifier-free-guidance scale changes from stage to stage, and whose stages at scale 1
+evaluate the conditional rows alone.
+
+The state has ``B = 2 B'`` rows, cond rows then uncond rows, as every guided sampler here has; its first half is the sample (the reference's
+``samples[:1]``).  ``table`` holds one fp32 scale per model evaluation: stage ``k`` of interval ``i`` uses ``w = table[i * stages + k]``
+(``stages`` = 1 euler, 2 midpoint, 4 rk4)::
+
+    w != 1   slope = model.forward_with_cfg(x, t, <conditioning>, cfg_scale=w, ...)          # B rows
+    w == 1   o = model.forward(x[:B'], t[:B'], <cond half of the conditioning>)               # B' rows: half the cost
+             slope = cat([o, o])
+
+At ``w = 1`` the guided expression ``unc + 1 * (cond - unc)`` is the conditional output, so a guidance INTERVAL (guidance for ``lo <= t < hi``
+only) is a table that holds 1 outside the interval - ``cfg_table`` builds it - and a guidance SCHEDULE (ramp, cosine, any function of t) is any
+other table.  Under the reference's ``cfg_channels = 3`` quirk (guidance on the first three latent channels, the rest passed through row by
+row) channel 3 of the SECOND half of a ``w == 1`` stage holds the cond rows' output where ``forward_with_cfg(cfg_scale=1)`` would leave the
+uncond rows' own; the first half, the sample, does not see the difference within that stage.  It is written down here, not worked around.
+
+``sample_cfg_schedule`` below IS that text in plain torch ops, as ``transport/masked.py`` is for inpainting: it defines the feature, runs
+models that are not engine-backed and CPU states, and is what the engine call (``lt_sample_ode_cfg_schedule``) is held to, state for state.
+It restates the loop of ``fixed_grid_odeint`` - same stage times, same ``dt`` handling, same rounding points.  The engine evaluates the
+conditional rows with the step arguments of the guided evaluation; an engine-backed model's plain ``forward`` reads its RoPE arguments off
+the module instead (``NextDiT._plain_forward_args``), so the two agree where those select the same table - ``scale_factor`` 1, or the
+families whose factors persist on the module."""
+from __future__ import annotations
+
+import math
+
+import torch as th
+
+from .integrators import FIXED_GRID_METHODS, _call
+
+_STAGES = {"euler": 1, "midpoint": 2, "rk4": 4}
+
+
+def _check_method(method):
+    if method not in FIXED_GRID_METHODS:
+        raise ValueError(f"guidance schedules are built for the fixed-grid methods {', '.join(FIXED_GRID_METHODS)}, not '{method}'")
+    return _STAGES[method]
+
+
+def _grid32(tgrid):
+    t = tgrid if isinstance(tgrid, th.Tensor) else th.tensor(list(tgrid), dtype=th.float32)
+    t = t.detach().to("cpu", th.float32)
+    if t.dim() != 1 or len(t) < 2:
+        raise ValueError("a guidance schedule needs a 1-D grid of at least 2 points")
+    return t
+
+
+def stage_times(tgrid, method, state_dtype=th.float32, t_round=True):
+    """The fp32 stage times ``[(len(tgrid) - 1) * stages]`` the engine hands the model, in evaluation order: ``t0``, for midpoint ``t0 + 0.5 dt``,
+    for rk4 ``t0 + dt * fp32(1/3)``, ``t0 + dt * fp32(2/3)`` and ``t1`` - fp32 arithmetic on the fp32 grid, as ``fixed_grid_odeint`` forms them
+    on 0-dim tensors.  With a bf16 state and ``t_round`` each is rounded to bf16 (torchdiffeq casts the time to the state dtype)."""
+    stages = _check_method(method)
+    t = _grid32(tgrid)
+    t0, t1 = t[:-1], t[1:]
+    dt = t1 - t0
+    if method == "euler":
+        cols = [t0]
+    elif method == "midpoint":
+        cols = [t0, t0 + 0.5 * dt]
+    else:
+        # a Python float times an fp32 tensor multiplies by the fp32 rounding of the float
+        cols = [t0, t0 + dt * (1.0 / 3.0), t0 + dt * (2.0 / 3.0), t1]
+    out = th.stack(cols, dim=1).reshape(-1)
+    assert out.numel() == (len(t) - 1) * stages
+    if t_round and state_dtype == th.bfloat16:
+        out = out.to(th.bfloat16).to(th.float32)
+    return out.contiguous()
+
+
+def linear_schedule(cfg_scale, t0=0.0, t1=1.0):
+    """``w(t)`` falling linearly from ``cfg_scale`` at ``t0`` (noise) to 1 at ``t1`` (data)"""
+    return lambda t: cfg_scale + (1.0 - cfg_scale) * min(max((t - t0) / (t1 - t0), 0.0), 1.0)
+
+
+def cosine_schedule(cfg_scale, t0=0.0, t1=1.0):
+    """``w(t)`` falling from ``cfg_scale`` at ``t0`` to 1 at ``t1`` along half a cosine"""
+    return lambda t: 1.0 + (cfg_scale - 1.0) * 0.5 * (1.0 + math.cos(math.pi * min(max((t - t0) / (t1 - t0), 0.0), 1.0)))
+
+
+def cfg_table(tgrid, method, cfg_scale, interval=None, schedule=None):
+    """The fp32 scale table of a trajectory.  ``interval=(lo, hi)``: ``cfg_scale`` where ``lo <= t_stage < hi``, 1 elsewhere; ``schedule``: a
+    callable ``w(t)`` of the stage time as a Python float (inside the interval, when both are given); neither: ``cfg_scale`` everywhere.
+    ``t_stage`` is the UNROUNDED fp32 stage time, so a table does not depend on the state dtype."""
+    ts = stage_times(tgrid, method, th.float32, False).tolist()
+    lo, hi = (-math.inf, math.inf) if interval is None else (float(interval[0]), float(interval[1]))
+    if not lo <= hi:
+        raise ValueError(f"guidance interval [{lo}, {hi}) is empty or not ordered")
+    vals = []
+    for t in ts:
+        w = 1.0
+        if lo <= t < hi:
+            w = float(schedule(t)) if schedule is not None else float(cfg_scale)
+        vals.append(w)
+    table = th.tensor(vals, dtype=th.float32)
+    if not bool(th.isfinite(table).all()):
+        raise ValueError("guidance table has an entry that is not finite")
+    return table
+
+
+def check_table(table, tgrid, method):
+    """``table`` as an fp32 CPU tensor of ``(len(tgrid) - 1) * stages`` finite entries"""
+    stages = _check_method(method)
+    n = len(_grid32(tgrid))
+    t = table if isinstance(table, th.Tensor) else th.tensor(list(table), dtype=th.float32)
+    t = t.detach().to("cpu", th.float32).reshape(-1).contiguous()
+    if t.numel() != (n - 1) * stages:
+        raise ValueError(f"guidance table has {t.numel()} entries, a {n}-point {method} grid has {(n - 1) * stages} stages")
+    if not bool(th.isfinite(t).all()):
+        raise ValueError("guidance table has an entry that is not finite")
+    return t
+
+
+def _cond_half(v, B):
+    """the cond half of one conditioning argument: tensors with a leading axis of B rows are cut, everything else passes"""
+    if isinstance(v, th.Tensor) and v.dim() >= 1 and v.shape[0] == B:
+        return v[: B // 2]
+    return v
+
+
+def sample_cfg_schedule(model, z, tgrid, table, method="euler", *, cond=None, t_round=True, **kw):
+    """The scheduled trajectory on the host: every state ``[len(tgrid), *z.shape]``.
+
+    ``model`` has ``forward_with_cfg(x, t, **cond, cfg_scale=w, **kw)`` and ``forward(x, t, **cond)``.  ``cond`` names the conditioning kwargs
+    (default: every tensor in ``kw`` whose leading axis has ``z.size(0)`` rows); the rest of ``kw`` goes to ``forward_with_cfg`` alone, as the
+    reference's plain ``forward`` takes no such arguments.  ``t`` is the fp32 ``[B]`` vector of the fixed-grid samplers, holding the stage time
+    rounded to the state dtype (``t_round``)."""
+    stages = _check_method(method)
+    table = check_table(table, tgrid, method)
+    B = z.size(0)
+    if B % 2:
+        raise ValueError(f"guidance needs an even batch (cond + uncond rows), got {B}")
+    kw = dict(kw)
+    kw.pop("cfg_scale", None)  # the table is the scale
+    if cond is None:
+        cond = [k for k, v in kw.items() if isinstance(v, th.Tensor) and v.dim() >= 1 and v.shape[0] == B]
+    cond_kw = {k: kw.pop(k) for k in cond}
+    half_kw = {k: _cond_half(v, B) for k, v in cond_kw.items()}
+    device = z.device
+    t = _grid32(tgrid).to(device)
+    w = table.tolist()
+    call = [0]
+
+    def func(tt, y):
+        scale = w[call[0]]
+        call[0] += 1
+        tvec = th.ones(B).to(device) * tt  # fp32 [B] (reference integrators.py:108)
+        if scale != 1.0:
+            return model.forward_with_cfg(y, tvec, **cond_kw, cfg_scale=scale, **kw)
+        o = model.forward(y[: B // 2], tvec[: B // 2], **half_kw)
+        return th.cat([o, o])
+
+    def f(tt, y):
+        return _call(func, tt, y) if t_round else func(tt, y)
+
+    # fixed_grid_odeint's loop (integrators.py), statement for statement
+    out = th.empty((len(t),) + tuple(z.shape), dtype=z.dtype, device=device)
+    out[0] = z
+    y = z
+    third, two_thirds = 1.0 / 3.0, 2.0 / 3.0
+    for j in range(len(t) - 1):
+        t0, t1 = t[j], t[j + 1]
+        dt = t1 - t0
+        k1 = f(t0, y)
+        if method == "euler":
+            dy = dt * k1
+        elif method == "midpoint":
+            half = 0.5 * dt
+            dy = dt * f(t0 + half, y + k1 * half)
+        else:
+            k2 = f(t0 + dt * third, y + dt * k1 * third)
+            k3 = f(t0 + dt * two_thirds, y + dt * (k2 - k1 * third))
+            k4 = f(t1, y + dt * (k1 - k2 + k3))
+            dy = (k1 + 3 * (k2 + k3) + k4) * dt * 0.125
+        y = y + dy
+        out[j + 1] = y
+    assert call[0] == (len(t) - 1) * stages
+    return out

@@ -311,7 +311,22 @@ class ode:
         self.max_num_steps = 2 ** 31 - 1
         self.stats = None         # adaptive methods: nfe / accepted / rejected / first_step / dt of the last sample() call
 
-    def sample(self, x, model, **model_kwargs):
+    def _sample_cfg_schedule(self, x, model, table, model_kwargs):
+        """a guidance schedule (transport/guidance.py): one engine call for an engine-backed forward_with_cfg, else the host loop"""
+        from .guidance import sample_cfg_schedule
+        if isinstance(x, tuple) or not getattr(self.drift, "is_plain_velocity", False) or self.sampler_type not in FIXED_GRID_METHODS:
+            raise NotImplementedError("guidance schedules are built for the fixed-grid methods on a tensor state with the plain velocity as drift")
+        target = _engine_target(model)
+        if target is not None and target[1] and x.is_cuda and self.use_engine and hasattr(target[0], "_engine_sample_ode_cfg_schedule"):
+            return target[0]._engine_sample_ode_cfg_schedule(x, self.t, self.sampler_type, self.t_round_to_state_dtype, table, dict(model_kwargs))
+        owner = getattr(model, "__self__", None)
+        if owner is None or getattr(model, "__name__", "") != "forward_with_cfg" or not hasattr(owner, "forward"):
+            raise TypeError("cfg_table needs the bound forward_with_cfg of a model that also has forward (the conditional-only stages call it)")
+        return sample_cfg_schedule(owner, x, self.t, table, self.sampler_type, t_round=self.t_round_to_state_dtype, **model_kwargs)
+
+    def sample(self, x, model, cfg_table=None, **model_kwargs):
+        if cfg_table is not None:
+            return self._sample_cfg_schedule(x, model, cfg_table, model_kwargs)
         if isinstance(x, tuple):  # the likelihood ODE (reference integrators.py:105-115 with a tuple state)
             device = x[0].device
 

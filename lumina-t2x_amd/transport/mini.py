@@ -3,7 +3,8 @@ sample_img2img.py:146-216) uses instead of Sampler/ode, including the img2img ``
 (transport.py:79-80).  The model-callable protocol and the engine fast path are those of transport.integrators.ode:
 a bound ``forward_with_cfg`` of one of our engine-backed models runs the whole trajectory in one ``lt_sample_ode`` call.
 ``sample(..., mask=, x1=, noise=)`` is the inpainting form (transport/masked.py; not in the reference): one ``lt_sample_ode_masked`` call
-for an engine-backed callable, the host loop ``sample_masked`` otherwise.
+for an engine-backed callable, the host loop ``sample_masked`` otherwise.  ``sample(..., cfg_table=)`` is a guidance schedule
+(transport/guidance.py; not in the reference either): one ``lt_sample_ode_cfg_schedule`` call, or the host loop ``sample_cfg_schedule``.
 
 Not mirrored: ``use_sd3=True`` (drives a diffusers SD3Transformer2DModel, not a Lumina model - out of scope)."""
 from __future__ import annotations
@@ -11,6 +12,7 @@ from __future__ import annotations
 import torch as th
 
 from .integrators import ADAPTIVE_METHODS, FIXED_GRID_METHODS, _engine_target, adaptive_odeint, fixed_grid_odeint
+from .guidance import sample_cfg_schedule
 from .masked import expand_operands, sample_masked
 
 
@@ -49,9 +51,26 @@ class ODE:
                                                    dict(model_kwargs))
         return sample_masked(model, x, self.t, mask, x1, noise, self.sampler_type, **model_kwargs)
 
-    def sample(self, x, model, mask=None, x1=None, noise=None, **model_kwargs):
+    def _sample_cfg_schedule(self, x, model, table, model_kwargs):
+        """a guidance schedule (transport/guidance.py): a scale per stage; one engine call when the callable is an engine-backed forward_with_cfg"""
+        if self.sampler_type not in FIXED_GRID_METHODS:
+            raise NotImplementedError(f"guidance schedules are built for the fixed-grid methods {', '.join(FIXED_GRID_METHODS)}, not "
+                                      f"'{self.sampler_type}'")
+        target = _engine_target(model)
+        if target is not None and target[1] and x.is_cuda and self.use_engine and hasattr(target[0], "_engine_sample_ode_cfg_schedule"):
+            return target[0]._engine_sample_ode_cfg_schedule(x, self.t, self.sampler_type, self.t_round_to_state_dtype, table, dict(model_kwargs))
+        owner = getattr(model, "__self__", None)
+        if owner is None or getattr(model, "__name__", "") != "forward_with_cfg" or not hasattr(owner, "forward"):
+            raise TypeError("cfg_table needs the bound forward_with_cfg of a model that also has forward (the conditional-only stages call it)")
+        return sample_cfg_schedule(owner, x, self.t, table, self.sampler_type, t_round=self.t_round_to_state_dtype, **model_kwargs)
+
+    def sample(self, x, model, mask=None, x1=None, noise=None, cfg_table=None, **model_kwargs):
         if isinstance(x, tuple):
             raise NotImplementedError("tuple states are not part of the sampling path")
+        if cfg_table is not None:
+            if mask is not None or x1 is not None or noise is not None:
+                raise NotImplementedError("a guidance schedule and an inpainting mask are not served together")
+            return self._sample_cfg_schedule(x, model, cfg_table, model_kwargs)
         if mask is not None or x1 is not None or noise is not None:
             return self._sample_masked(x, model, mask, x1, noise, model_kwargs)
         target = _engine_target(model)
