@@ -103,6 +103,12 @@ extern "C" {
  *                       weights were converted between the two layouts during the engine's last whole-trajectory sampler call (each
  *                       conversion rewrites every GEMM weight once; a guidance schedule that alternates between a 2 B'-row and a B'-row
  *                       evaluation on different sides of the threshold pays it at every change)
+ *                       "layout_pinned" - read-only as well - is 1 once an evaluation was recorded on a stream the CALLER was capturing
+ *                       (torch.cuda.graph / hipStreamBeginCapture around lt_forward / lt_forward_cfg): that graph holds row-major kernels and
+ *                       replays without the engine hearing of it, so from then on, for the engine's life, no evaluation takes the pair
+ *                       regime ("last_pair" stays 0), the weights stay row-major and the shared RoPE table is rebuilt before every
+ *                       evaluation (the row-major persistent GEMM is the slower one: an engine that is never captured pays
+ *                       nothing)
  * (the round-1 names gemm_pipeline / gemm_pp_tail / gemm_persist are accepted with value 0 only: the study kernels they selected were
  *  deleted with csrc/experimental/ in round 5) */
 

@@ -140,6 +140,14 @@ struct lt_engine {
     // conversions of the weights between the two layouts: since lt_create, and during the last whole-trajectory sampler call
     // (lt_engine_get_option "layout_flips"; DESIGN 7g: a guidance schedule whose two evaluation sizes fall into different regimes)
     long long layout_flips_total = 0, layout_flips = 0;
+    // caller capture: the first evaluation recorded on a stream the CALLER is capturing latches layout_pinned for the engine's
+    // life - that graph holds row-major kernels and replays without the engine hearing of it, so no evaluation chooses the pair regime any
+    // more, and the shared RoPE table is rebuilt before every evaluation (a replay rewrites it behind the host's back).
+    // w_pair_dev: 1 while the weights ARE in the pair layout, written in stream order behind every conversion.  A conversion recorded into a
+    // caller's graph reads it (launch_pair_layout only_if), so that it converts once however often the graph replays; w_owed: such a
+    // conversion was recorded, not run - the next eager call enqueues the same conditional conversion before it trusts w_pair.
+    bool layout_pinned = false, w_owed = false;
+    int* w_pair_dev = nullptr;
     // workspace
     u16 *x = nullptr, *h = nullptr, *qkv = nullptr, *q = nullptr, *k = nullptr, *vt = nullptr, *attn = nullptr;
     u16 *o = nullptr, *u = nullptr, *patches = nullptr, *frows = nullptr, *mod = nullptr;
@@ -235,6 +243,14 @@ int packed_call_begin(lt_engine* e, const char* who, const int32_t* hw_host, con
 // for a->batch rows, and its output is written to both halves of `out` (a->batch rows)
 int forward_graphed(lt_engine* e, const void* x_in, const float* t_dev, void* out, const lt_step_args* a, int use_cfg, hipStream_t s,
                     const PackedCall* pc = nullptr, const float* cfg_dev = nullptr, bool cond_only = false);
+// true while stream s records into a graph (the caller's torch.cuda.graph / hipStreamBeginCapture, or the engine's own cache)
+bool stream_capturing(hipStream_t s);
+// the entry points that allocate, synchronise or copy from host memory cannot be recorded into a caller's graph: non-zero after
+// lt_set_error("<who>: ... capture ...") when s is capturing - called before anything is launched, so the capture stays valid (engine.hip)
+int refuse_if_capturing(hipStream_t s, const char* who);
+// ... and while lt_profile_enable is on, the calls that are otherwise recordable (a model evaluation, lt_prepare_prompt / _labels): the
+// profile brackets launches with HIP events.  Costs no stream query while the profile is off (engine.hip)
+int refuse_profile_if_capturing(const lt_engine* e, hipStream_t s, const char* who);
 // the softmax scale of an evaluation of N tokens under the engine's rule (model.py:373-376, visual_anagrams/models/nextdit.py:331-335), and the
 // refusal of a shape the anagram fork's query chunks do not cover; non-zero after lt_set_error (engine.hip)
 int softmax_scale_for(const lt_engine* e, const lt_step_args* a, int N, float* scale);

@@ -263,11 +263,13 @@ int find_slot(lt_engine* e, const std::string& key, Slot* s) {
     return 2;
 }
 
-// (cos,sin) factor table(s) for this call's RoPE arguments; rebuilt only when they change
+// (cos,sin) factor table(s) for this call's RoPE arguments; rebuilt only when they change - or always once a caller has recorded an
+// evaluation into a graph of its own (layout_pinned): that graph rebuilds the table for ITS arguments on every replay, which the host
+// does not see, and a rebuild recorded during the capture has not run at all
 int ensure_rope(lt_engine* e, const lt_step_args* a, hipStream_t s) {
     const float ntk = a->ntk_factor > 0.f ? a->ntk_factor : 1.0f;
     const float sf = a->scale_factor > 0.f ? a->scale_factor : 1.0f;
-    if (e->rope_scale == sf && e->rope_ntk == ntk) return 0;
+    if (!e->layout_pinned && e->rope_scale == sf && e->rope_ntk == ntk) return 0;
     if (e->cfg.variant == LT_VARIANT_NEXT_T2I) {
         if (launch_rope_table_2d(e->rope, e->rope_len, e->hd, 10000.0f, sf, s, e->rope_tr)) return 1;
     } else {
@@ -373,22 +375,29 @@ struct PackedDesc {
     const int* tab = nullptr;   // device PackedTable (kernels.h) of the same size list
 };
 
-// all four GEMM weights of every dense block -> the row-pair-interleaved layout (want) or back to row-major, in place, on stream s
-int ensure_weight_layout(lt_engine* e, bool want, hipStream_t s) {
-    if (e->w_pair == want) return 0;
+// all four GEMM weights of every dense block -> the row-pair-interleaved layout (want) or back to row-major, in place, on stream s.
+// recording: s is the caller's capturing stream (want is false there).  These launches run at every replay of the caller's graph and not now,
+// so they are conditional on the device word e->w_pair_dev (whoever comes first converts, everyone after finds 0 and does nothing), and the
+// next eager call owes the same conditional conversion (w_owed) before its own kernels read the weights.
+int ensure_weight_layout(lt_engine* e, bool want, hipStream_t s, bool recording = false) {
+    if (e->w_pair == want && !e->w_owed) return 0;
+    LT_REQUIRE(!want || (!e->layout_pinned && !recording), "pair layout: the weights are pinned row-major (a caller's graph holds row-major kernels)");
+    const int* only_if = recording || e->w_owed ? e->w_pair_dev : nullptr;
     for (int l = 0; l < e->L; ++l) {
         LayerW& w = e->lw[l];
         if (e->E == 0) {
-            if (launch_pair_layout(w.wqkv, e->qkvn, e->d, want, s)) return 1;
-            if (launch_pair_layout(w.wo, e->d, e->d, want, s)) return 1;
-            if (launch_pair_layout(w.w13, 2LL * e->F, e->d, want, s)) return 1;
-            if (launch_pair_layout(w.w2, e->d, e->F, want, s)) return 1;
+            if (launch_pair_layout(w.wqkv, e->qkvn, e->d, want, s, only_if)) return 1;
+            if (launch_pair_layout(w.wo, e->d, e->d, want, s, only_if)) return 1;
+            if (launch_pair_layout(w.w13, 2LL * e->F, e->d, want, s, only_if)) return 1;
+            if (launch_pair_layout(w.w2, e->d, e->F, want, s, only_if)) return 1;
         } else {  // MoE families: the experts' weights only ([E][2 F][d] / [E][d][F]: an expert's rows are an even count, pairs stay inside it)
-            for (u16* w13 : {w.w13_t, w.w13_s}) if (w13 && launch_pair_layout(w13, 2LL * e->E * e->F, e->d, want, s)) return 1;
-            for (u16* w2 : {w.w2_t, w.w2_s}) if (w2 && launch_pair_layout(w2, (long long)e->E * e->d, e->F, want, s)) return 1;
+            for (u16* w13 : {w.w13_t, w.w13_s}) if (w13 && launch_pair_layout(w13, 2LL * e->E * e->F, e->d, want, s, only_if)) return 1;
+            for (u16* w2 : {w.w2_t, w.w2_s}) if (w2 && launch_pair_layout(w2, (long long)e->E * e->d, e->F, want, s, only_if)) return 1;
         }
     }
+    LT_CHECK_HIP(hipMemsetAsync(e->w_pair_dev, want ? 1 : 0, sizeof(int), s));  // (behind the last conversion, in stream order)
     e->w_pair = want;
+    e->w_owed = recording;
     ++e->layout_flips_total;
     return 0;
 }
@@ -440,10 +449,16 @@ int run_forward(lt_engine* e, const void* x_in, const float* t_dev, void* out, c
     const int d = e->d, L = e->L, H = e->H, Hkv = e->Hkv, hd = e->hd, F = e->F, dkv = e->dkv, A = e->A;
     const int Npad = round_up(N, 64);
     const int cd = e->chunks * d;
-
-    if (ensure_rope(e, a, s)) return 1;
+    // the CALLER is recording this evaluation into a graph of its own (e->tally: the capture is the engine's, forward_graphed).  Nothing was
+    // launched yet: what cannot be recorded is refused here, and the capture stays valid
+    const bool caller_cap = !e->tally && stream_capturing(s);
+    if (caller_cap && refuse_profile_if_capturing(e, s, "model evaluation")) return 2;
     float sm_scale;
     if (softmax_scale_for(e, a, N, &sm_scale)) return 1;
+    // the last refusal is behind us and the first launch ahead: only an evaluation that IS recorded pins the engine (and before ensure_rope:
+    // the table's rebuild is recorded whatever the host believes the table holds)
+    if (caller_cap) e->layout_pinned = true;
+    if (ensure_rope(e, a, s)) return 1;
 
     // patchify + x_embedder (model.py:777-779) [+ eol token per row]
     const int *ntok_dev = nullptr, *gw_dev = nullptr;
@@ -572,19 +587,12 @@ int run_forward(lt_engine* e, const void* x_in, const float* t_dev, void* out, c
         g2.N = d; g2.K = F; g2.lda = F; g2.ldw = F; g2.ldc = d; g2.w_expert_stride = (long long)d * F;
         pair_moe = gemm_runs_w4q_grouped(g13, 1) && gemm_runs_w4q_grouped(g2, 0);
     }
-    const bool pair_any = pair || pair_moe;
-    if (e->w_pair != pair_any) {
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(s, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusNone; }
-        if (cs == hipStreamCaptureStatusNone) {
-            if (ensure_weight_layout(e, pair_any, s)) return 1;
-        } else {
-            // inside a capture (the caller's own graph) a layout change would be baked into every replay: run on the layout the weights are in
-            LT_REQUIRE(!e->w_pair, "this evaluation runs on the small-M kernels, which read row-major weights, but the engine's weights are in the "
-                                   "pair layout of the last large evaluation and the stream is capturing: run one eager evaluation of this shape first");
-            pair = false; pair_moe = false;
-        }
-    }
+    // a graph the caller recorded replays without the engine hearing of it, so it must never meet weights in the other layout: a recorded
+    // evaluation runs on row-major weights, and from the first one on (layout_pinned, set above) so does every other evaluation - the weights
+    // stay row-major for the engine's life.  Weights found in the pair layout by the recording are converted by the graph itself, once
+    // (ensure_weight_layout, recording).  The engine's own graphs are captured after their key's eager run and follow the same rule.
+    if (e->layout_pinned) { pair = false; pair_moe = false; }
+    if (ensure_weight_layout(e, pair || pair_moe, s, caller_cap)) return 1;
     e->last_pair = pair || pair_moe;
     // first pre-norm: modulate(attention_norm(x), [shift,] scale) (model.py:599 / models.py:785 / lumina_t2i model.py:600)
     {
@@ -827,6 +835,25 @@ bool profiling_wants_events(const lt_engine* e) {
 
 }  // namespace
 
+bool stream_capturing(hipStream_t s) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &cs) != hipSuccess) { (void)hipGetLastError(); return false; }
+    return cs != hipStreamCaptureStatusNone;
+}
+
+int refuse_if_capturing(hipStream_t s, const char* who) {
+    LT_REQUIRE(!stream_capturing(s), "%s: refused on a stream under capture: the call allocates, synchronises or copies from host memory, which a "
+               "graph cannot replay (and which would end the capture with an error) - make it before the capture begins", who);
+    return 0;
+}
+
+int refuse_profile_if_capturing(const lt_engine* e, hipStream_t s, const char* who) {
+    if (!(e->prof_on && e->prof_mask)) return 0;
+    LT_REQUIRE(!stream_capturing(s), "%s: refused on a stream under capture while lt_profile_enable is on (the profile brackets launches with "
+               "events, which a graph cannot carry): switch the profile off before the capture", who);
+    return 0;
+}
+
 int softmax_scale_for(const lt_engine* e, const lt_step_args* a, int N, float* scale) {
     const int hd = e->hd;
     if (a->proportional_attn && !e->v.labels) {
@@ -889,6 +916,10 @@ int forward_graphed(lt_engine* e, const void* x_in, const float* t_dev, void* ou
     const size_t sbytes = (pc ? (size_t)pc->elems : (size_t)B * e->cfg.in_channels * a->latent_h * a->latent_w) * (a->io_dtype == LT_BF16 ? 2 : 4);
     const size_t cap_bytes = (size_t)e->cfg.max_batch * e->cfg.in_channels * e->cfg.max_tokens * e->cfg.patch_size * e->cfg.patch_size * 4;
     if ((cond_only ? 2 * sbytes : sbytes) > cap_bytes) return run(x_in, t_dev, out, s);
+    // a caller that is capturing ITS stream (torch.cuda.graph around the sampler) cannot launch a graph or start a second capture
+    // from inside: hand it plain launches, which its own capture records.  The cache is not touched: a key first seen here would be pinned to
+    // the row-major regime of a recorded evaluation (ge->pair) for callers that never capture
+    if (stream_capturing(s)) return run(x_in, t_dev, out, s);
     // (both option generations: the process defaults' and this engine's overrides' - kernel selection is baked into a captured graph)
     // ... and the softmax rule: the scale it selects is a kernel argument (qa.out_scale / at.scale)
     // ... and whether the scale comes from device memory / the evaluation is the conditional-only one: other closing kernels
@@ -909,16 +940,15 @@ int forward_graphed(lt_engine* e, const void* x_in, const float* t_dev, void* ou
         ge = &e->graphs.back();
         ge->key = key;
     }
+    if (e->layout_pinned && ge->pair) {  // recorded on pair-layout weights, which the engine no longer holds: start the key over
+        if (ge->exec) (void)hipGraphExecDestroy(ge->exec);
+        ge->exec = nullptr; ge->uses = 0; ge->failed = false; ge->pair = false;
+    }
     if (ge->failed || ge->uses++ == 0) {
         const int rc = run(x_in, t_dev, out, s);
         ge->pair = e->last_pair;  // (the weight layout this key's evaluations run on; a function of the key)
         return rc;
     }
-    // a caller that is capturing ITS stream (torch.cuda.graph around the sampler) cannot launch a graph or start a second capture
-    // from inside: hand it plain launches, which its own capture records
-    hipStreamCaptureStatus caller_cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &caller_cap) != hipSuccess) { (void)hipGetLastError(); caller_cap = hipStreamCaptureStatusNone; }
-    if (caller_cap != hipStreamCaptureStatusNone) return run(x_in, t_dev, out, s);
     // the RoPE table is ONE shared buffer outside every graph (it is rebuilt only when scale / ntk change): a replay of key A after
     // key B changed the table must rebuild it first - before every replay, not only before the capture
     if (ensure_rope(e, a, s)) return 1;
@@ -1165,6 +1195,8 @@ extern "C" int lt_create(const lt_config* cfg, lt_engine** out) {
             e->g_t = (float*)q;
             if (dev_alloc(e, &q, sizeof(float))) return fail();
             e->g_cfg = (float*)q;
+            if (dev_alloc(e, &q, sizeof(int))) return fail();  // (zeroed: the weights start row-major)
+            e->w_pair_dev = (int*)q;
         }
         for (int i = 0; i < 4; ++i) { if (dev_alloc(e, &e->kbuf[i], state)) return fail(); }
     }
@@ -1197,13 +1229,15 @@ extern "C" int lt_set_weight(lt_engine* e, const char* key, const void* src_dev,
     LT_REQUIRE(e && key && src_dev && shape, "lt_set_weight: null argument");
     LT_REQUIRE(ndim >= 1 && ndim <= 8, "lt_set_weight: ndim %d outside 1..8", ndim);
     for (int i = 0; i < ndim; ++i) LT_REQUIRE(shape[i] > 0, "weight '%s': shape[%d] = %lld", key, i, (long long)shape[i]);
+    if (refuse_if_capturing((hipStream_t)stream, "lt_set_weight")) return 2;  // (a recorded upload would replay from a source long gone)
     Slot s;
     if (find_slot(e, key, &s)) return 2;
-    if (ensure_weight_layout(e, false, (hipStream_t)stream)) return 1;  // uploads write row-major rows
     long long n = 1;
     for (int i = 0; i < ndim; ++i) n *= shape[i];
     LT_REQUIRE(n == (long long)s.rows * s.cols, "weight '%s': %lld elements given, %lld expected (%d x %d)", key, n,
                (long long)s.rows * s.cols, s.rows, s.cols);
+    // uploads write row-major rows - after the refusals: a refused upload converts nothing
+    if (ensure_weight_layout(e, false, (hipStream_t)stream)) return 1;
     if (launch_upload_rows(src_dev, dtype, s.dst, s.rows, s.cols, s.dst_ld, s.r0, s.row_map, (hipStream_t)stream)) return 1;
     auto it = e->need.find(key);
     if (it != e->need.end()) it->second = true;
@@ -1258,6 +1292,7 @@ extern "C" int lt_prepare_prompt(lt_engine* e, const void* cap_feats_dev, int32_
     LT_REQUIRE(T >= 1 && T <= Tmax, "text length %d exceeds max_text %d", T, Tmax);
     LT_REQUIRE(cap_dtype == LT_BF16 || cap_dtype == LT_F32, "cap_feats dtype must be bf16 or f32");
     if (lt_weights_ready(e)) return 2;
+    if (refuse_profile_if_capturing(e, s, "lt_prepare_prompt")) return 2;
     const int Tpad = round_up(T, 64), cap = e->cap, A = e->A;
     ProfScope ps(e, 2, 0, s);
     if (launch_cast_to_bf16(cap_feats_dev, cap_dtype, e->capb, (long long)B * T * cap, s)) return 1;
@@ -1274,6 +1309,7 @@ extern "C" int lt_prepare_prompt_regional(lt_engine* e, const void* cap_feats_de
                                           int32_t Y, int32_t T, const void* global_feats_dev, const int32_t* global_mask_dev,
                                           int32_t Tg, int32_t h_split, int32_t w_split, void* stream) {
     LT_REQUIRE(e && cap_feats_dev && cap_mask_dev && global_feats_dev && global_mask_dev, "lt_prepare_prompt_regional: null argument");
+    if (refuse_if_capturing((hipStream_t)stream, "lt_prepare_prompt_regional")) return 2;  // (allocates, uploads a host table, synchronises)
     LtOptScope opt_scope(&e->opts);
     LT_REQUIRE(e->cfg.variant == LT_VARIANT_NEXT_T2I, "lt_prepare_prompt_regional: text-conditional Next-DiT only");
     hipStream_t s = (hipStream_t)stream;
@@ -1321,6 +1357,7 @@ extern "C" int lt_prepare_labels(lt_engine* e, const int32_t* labels_dev, int32_
     LT_REQUIRE(e->v.labels, "lt_prepare_labels: this variant is text-conditional (use lt_prepare_prompt)");
     LT_REQUIRE(B >= 1 && B <= e->cfg.max_batch, "label batch %d exceeds max_batch %d", B, e->cfg.max_batch);
     if (lt_weights_ready(e)) return 2;
+    if (refuse_profile_if_capturing(e, (hipStream_t)stream, "lt_prepare_labels")) return 2;
     ProfScope ps(e, 2, 0, (hipStream_t)stream);
     // y_embedder(y) in eval mode (models.py:216-221) -> the label half of adaln_input (models.py:937-939)
     if (launch_label_gather(e->label_table, labels_dev, e->cap_emb, B, e->label_rows, e->A, (hipStream_t)stream)) return 1;
@@ -1337,6 +1374,7 @@ extern "C" int lt_forward(lt_engine* e, const void* x_dev, const float* t_dev, v
 extern "C" int lt_forward_packed(lt_engine* e, const void* const* x_ptrs, const int32_t* hw_host, const float* t_dev,
                                  void* const* out_ptrs, const lt_step_args* a, void* stream) {
     LT_REQUIRE(e && x_ptrs && hw_host && t_dev && out_ptrs && a, "lt_forward_packed: null argument");
+    if (refuse_if_capturing((hipStream_t)stream, "lt_forward_packed")) return 2;  // (the size table is copied from pageable host memory)
     LtOptScope opt_scope(&e->opts);
     LT_REQUIRE(a->batch >= 1 && a->batch <= e->cfg.max_batch, "lt_forward_packed: batch %d outside 1..max_batch %d", a->batch, e->cfg.max_batch);
     for (int b = 0; b < a->batch; ++b) LT_REQUIRE(x_ptrs[b] && out_ptrs[b], "lt_forward_packed: null sample pointer %d", b);
@@ -1369,6 +1407,8 @@ int packed_call_begin(lt_engine* e, const char* who, const int32_t* hw_host, con
     float unused;
     if (softmax_scale_for(e, a, pc->n_max, &unused)) return 1;
     pc->hw = hw_host;
+    // (the table itself travels as a kernel argument and is recordable; the first packed call of an engine allocates its device copy)
+    if (!e->pk_tab && refuse_if_capturing(s, who)) return 2;
     if (!e->pk_tab) LT_CHECK_HIP(hipMalloc((void**)&e->pk_tab, sizeof(PackedTable)));
     return launch_packed_table_store(t, e->pk_tab, s);
 }
@@ -1592,6 +1632,11 @@ extern "C" int lt_engine_get_option(lt_engine* e, const char* name, int32_t* val
     if (strcmp(name, "layout_flips") == 0) {  // read-only, no option: weight layout conversions during the last sampler call (lumina_dit_debug.h)
         LT_REQUIRE(e, "lt_engine_get_option: layout_flips: null engine");
         *value = (int32_t)std::min<long long>(e->layout_flips, INT32_MAX);
+        return 0;
+    }
+    if (strcmp(name, "layout_pinned") == 0) {  // read-only, no option: a caller's graph holds an evaluation, the weights stay row-major (lumina_dit_debug.h)
+        LT_REQUIRE(e, "lt_engine_get_option: layout_pinned: null engine");
+        *value = e->layout_pinned ? 1 : 0;
         return 0;
     }
     const int id = lt_opt_find(name);

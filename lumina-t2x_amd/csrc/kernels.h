@@ -424,4 +424,4 @@ int launch_fill_pad_packed(u16* x, const u16* pad_token, const int* tab_dev, int
 int launch_unpatchify_packed(const u16* rows, int ld, void* out, int out_dtype, const int* tab_dev, int B, int C, int out_ch, int patch, int N,
                              int use_cfg, float cfg_scale, int cfg_channels, hipStream_t stream);
 // in-place conversion of a dense [rows][cols] bf16 matrix to (to_pair 1) / from (0) the row-pair-interleaved layout of GemmArgs::pair_ab
-int launch_pair_layout(u16* m, long long rows, int cols, int to_pair, hipStream_t stream);
+int launch_pair_layout(u16* m, long long rows, int cols, int to_pair, hipStream_t stream, const int* only_if = nullptr);

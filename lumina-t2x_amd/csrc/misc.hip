@@ -664,8 +664,11 @@ int launch_label_gather(const u16* table, const int32_t* labels, u16* out, int B
 // In place, one workgroup per pair of rows of a dense [rows][cols] matrix: element (r, k) <-> (r >> 1) * 2 cols + (k >> 5) * 64 + (r & 1) * 32 +
 // (k & 31).  A 16-byte chunk c of row rr sits at chunk rr * (cols / 8) + c of the pair's row-major image and at chunk (c >> 2) * 8 + rr * 4 +
 // (c & 3) of its interleaved one.  The whole pair is read into registers before the first store (cols <= 16384: 16 chunks per thread).
+// only_if (optional, device memory): the launch does nothing when the word is 0 - a conversion recorded into a caller's graph runs on every
+// replay, and must convert once (engine.hip: ensure_weight_layout; the word is rewritten behind the last conversion, in stream order)
 namespace {
-__global__ __launch_bounds__(256) void pair_layout_kernel(u16* __restrict__ m, int cols, int to_pair) {
+__global__ __launch_bounds__(256) void pair_layout_kernel(u16* __restrict__ m, int cols, int to_pair, const int* __restrict__ only_if) {
+    if (only_if && *only_if == 0) return;
     u16* base = m + (size_t)blockIdx.x * 2 * cols;
     const int cpr = cols >> 3, n = 2 * cpr;
     bf8_t v[16];
@@ -688,10 +691,10 @@ __global__ __launch_bounds__(256) void pair_layout_kernel(u16* __restrict__ m, i
 }
 }  // namespace
 
-int launch_pair_layout(u16* m, long long rows, int cols, int to_pair, hipStream_t stream) {
+int launch_pair_layout(u16* m, long long rows, int cols, int to_pair, hipStream_t stream, const int* only_if) {
     LT_REQUIRE(m && rows > 0 && rows % 2 == 0 && cols > 0 && cols % 32 == 0 && cols <= 16384 && rows / 2 < 0x7fffffffLL,
                "pair_layout: an even number of rows of 32 k <= 16384 columns (got %lld x %d)", rows, cols);
-    hipLaunchKernelGGL(pair_layout_kernel, dim3((unsigned)(rows / 2)), dim3(256), 0, stream, m, cols, to_pair);
+    hipLaunchKernelGGL(pair_layout_kernel, dim3((unsigned)(rows / 2)), dim3(256), 0, stream, m, cols, to_pair, only_if);
     LT_CHECK_HIP(hipGetLastError());
     return 0;
 }

@@ -165,6 +165,7 @@ extern "C" int lt_sample_ode(lt_engine* e, const void* z_dev, void* traj_dev, vo
                              int32_t n_grid, int32_t method, int32_t use_cfg, int32_t t_round, const lt_step_args* a,
                              void* stream) {
     LT_REQUIRE(e && z_dev && tgrid_host && a, "lt_sample_ode: null argument");
+    if (refuse_if_capturing((hipStream_t)stream, "lt_sample_ode")) return 2;  // (the stage times travel through a host staging buffer that the next call rewrites)
     LtOptScope opt_scope(&e->opts);
     LT_REQUIRE(n_grid >= 2, "lt_sample_ode: need at least 2 grid points");
     LT_REQUIRE(method >= LT_ODE_EULER && method <= LT_ODE_RK4, "lt_sample_ode: unknown method %d", method);
@@ -178,6 +179,7 @@ extern "C" int lt_sample_ode_packed(lt_engine* e, const void* z_flat_dev, const 
                                     const float* tgrid_host, int32_t n_grid, int32_t method, int32_t use_cfg, int32_t t_round, const lt_step_args* a,
                                     void* stream) {
     LT_REQUIRE(e && z_flat_dev && hw_host && tgrid_host && a, "lt_sample_ode_packed: null argument");
+    if (refuse_if_capturing((hipStream_t)stream, "lt_sample_ode_packed")) return 2;  // (the stage times travel through a host staging buffer that the next call rewrites)
     LtOptScope opt_scope(&e->opts);
     LT_REQUIRE(n_grid >= 2, "lt_sample_ode_packed: need at least 2 grid points");
     LT_REQUIRE(method >= LT_ODE_EULER && method <= LT_ODE_RK4, "lt_sample_ode_packed: unknown method %d", method);
@@ -193,6 +195,7 @@ extern "C" int lt_sample_ode_masked(lt_engine* e, const void* z_dev, const void*
                                     const lt_step_args* a, void* stream) {
     LT_REQUIRE(mask_dev && x1_dev && noise_dev, "lt_sample_ode_masked: null mask, source or noise");
     LT_REQUIRE(e && z_dev && tgrid_host && a, "lt_sample_ode_masked: null argument");
+    if (refuse_if_capturing((hipStream_t)stream, "lt_sample_ode_masked")) return 2;  // (the stage times travel through a host staging buffer that the next call rewrites)
     LtOptScope opt_scope(&e->opts);
     LT_REQUIRE(n_grid >= 2, "lt_sample_ode_masked: need at least 2 grid points");
     LT_REQUIRE(method >= LT_ODE_EULER && method <= LT_ODE_RK4, "lt_sample_ode_masked: unknown method %d", method);
@@ -210,6 +213,7 @@ extern "C" int lt_sample_ode_masked_packed(lt_engine* e, const void* z_flat_dev,
                                            const lt_step_args* a, void* stream) {
     LT_REQUIRE(mask_flat_dev && x1_flat_dev && noise_flat_dev, "lt_sample_ode_masked_packed: null mask, source or noise");
     LT_REQUIRE(e && z_flat_dev && hw_host && tgrid_host && a, "lt_sample_ode_masked_packed: null argument");
+    if (refuse_if_capturing((hipStream_t)stream, "lt_sample_ode_masked_packed")) return 2;  // (the stage times travel through a host staging buffer that the next call rewrites)
     LtOptScope opt_scope(&e->opts);
     LT_REQUIRE(n_grid >= 2, "lt_sample_ode_masked_packed: need at least 2 grid points");
     LT_REQUIRE(method >= LT_ODE_EULER && method <= LT_ODE_RK4, "lt_sample_ode_masked_packed: unknown method %d", method);
@@ -224,6 +228,7 @@ extern "C" int lt_sample_ode_masked_packed(lt_engine* e, const void* z_flat_dev,
 extern "C" int lt_sample_ode_cfg_schedule(lt_engine* e, const void* z_dev, void* traj_dev, void* final_dev, const float* tgrid_host, int32_t n_grid,
                                           int32_t method, const float* cfg_host, int32_t t_round, const lt_step_args* a, void* stream) {
     LT_REQUIRE(e && z_dev && tgrid_host && cfg_host && a, "lt_sample_ode_cfg_schedule: null argument");
+    if (refuse_if_capturing((hipStream_t)stream, "lt_sample_ode_cfg_schedule")) return 2;  // (the stage times travel through a host staging buffer that the next call rewrites)
     LtOptScope opt_scope(&e->opts);
     LT_REQUIRE(n_grid >= 2, "lt_sample_ode_cfg_schedule: need at least 2 grid points");
     LT_REQUIRE(method >= LT_ODE_EULER && method <= LT_ODE_RK4, "lt_sample_ode_cfg_schedule: unknown method %d", method);
@@ -256,6 +261,7 @@ void drop_views(lt_engine* e) {
 extern "C" int lt_set_views(lt_engine* e, const int32_t* perm_dev, const float* vsign_host, const float* isign_host, int32_t V, int32_t latent_h,
                             int32_t latent_w, void* stream) {
     LT_REQUIRE(e, "lt_set_views: null engine");
+    if (refuse_if_capturing((hipStream_t)stream, "lt_set_views")) return 2;  // (allocates, uploads host tables, synchronises)
     hipStream_t s = (hipStream_t)stream;
     const lt_config& c = e->cfg;
     LT_REQUIRE(c.variant == LT_VARIANT_NEXT_T2I, "lt_set_views: multi-view sampling drives the text-conditional Next-DiT (LT_VARIANT_NEXT_T2I) only; "
@@ -307,6 +313,7 @@ extern "C" int lt_set_views(lt_engine* e, const int32_t* perm_dev, const float* 
 extern "C" int lt_sample_views(lt_engine* e, const void* z_dev, void* traj_dev, void* final_dev, const float* tgrid_host, int32_t n_grid,
                                int32_t method, const lt_step_args* a, void* stream) {
     LT_REQUIRE(e && z_dev && tgrid_host && a, "lt_sample_views: null argument");
+    if (refuse_if_capturing((hipStream_t)stream, "lt_sample_views")) return 2;  // (the stage times travel through a host staging buffer that the next call rewrites)
     LtOptScope opt_scope(&e->opts);
     LT_REQUIRE(e->cfg.variant == LT_VARIANT_NEXT_T2I, "lt_sample_views: multi-view sampling drives the text-conditional Next-DiT (LT_VARIANT_NEXT_T2I) "
                "only; this engine is variant %d", e->cfg.variant);
@@ -369,6 +376,7 @@ extern "C" int lt_sample_views(lt_engine* e, const void* z_dev, void* traj_dev, 
 extern "C" int lt_sample_views_guided(lt_engine* e, const void* z_dev, const void* guidance_dev, const void* noise_dev, void* traj_dev, void* final_dev,
                                       const float* tgrid_host, const float* coef_host, int32_t n_grid, const lt_step_args* a, void* stream) {
     LT_REQUIRE(e && z_dev && guidance_dev && noise_dev && tgrid_host && coef_host && a, "lt_sample_views_guided: null argument");
+    if (refuse_if_capturing((hipStream_t)stream, "lt_sample_views_guided")) return 2;  // (the stage times travel through a host staging buffer that the next call rewrites)
     LtOptScope opt_scope(&e->opts);
     LT_REQUIRE(e->cfg.variant == LT_VARIANT_NEXT_T2I, "lt_sample_views_guided: multi-view sampling drives the text-conditional Next-DiT "
                "(LT_VARIANT_NEXT_T2I) only; this engine is variant %d", e->cfg.variant);
@@ -432,6 +440,7 @@ extern "C" int lt_sample_sde(lt_engine* e, const void* z_dev, const void* noise_
                              int32_t n_steps, int32_t method, int32_t last_step, const float* last_coef_host, int32_t use_cfg,
                              const lt_step_args* a, void* stream) {
     LT_REQUIRE(e && z_dev && noise_dev && steps_host && a, "lt_sample_sde: null argument");
+    if (refuse_if_capturing((hipStream_t)stream, "lt_sample_sde")) return 2;  // (the stage times travel through a host staging buffer that the next call rewrites)
     LtOptScope opt_scope(&e->opts);
     LT_REQUIRE(n_steps >= 2, "lt_sample_sde: n_steps %d (need at least 2: one loop step and the last step)", n_steps);
     LT_REQUIRE(method == LT_SDE_EULER || method == LT_SDE_HEUN, "lt_sample_sde: unknown method %d", method);
@@ -547,6 +556,7 @@ extern "C" int lt_sample_ode_adaptive(lt_engine* e, const void* z_dev, void* tra
                                       const lt_step_args* a, void* stream, lt_ode_adaptive_stats* stats) {
 #pragma clang fp contract(off)
     LT_REQUIRE(e && z_dev && traj_dev && tgrid_host && a, "lt_sample_ode_adaptive: null argument");
+    if (refuse_if_capturing((hipStream_t)stream, "lt_sample_ode_adaptive")) return 2;  // (the host reads an error norm at every step)
     LtOptScope opt_scope(&e->opts);
     LT_REQUIRE(method >= LT_ODE_DOPRI5 && method <= LT_ODE_ADAPTIVE_HEUN, "lt_sample_ode_adaptive: unknown method %d", method);
     LT_REQUIRE(std::isfinite(rtol) && rtol > 0.f && std::isfinite(atol) && atol > 0.f,

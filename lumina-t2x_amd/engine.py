@@ -22,6 +22,14 @@ def _stream_ptr(device: torch.device) -> int:
     return torch.cuda.current_stream(device).cuda_stream
 
 
+def _refuse_if_capturing(who: str) -> None:
+    """the calls that create an engine or upload weights allocate and synchronise: inside the caller's ``torch.cuda.graph`` they would end
+    the capture with an error, so they are refused by name before they touch the device"""
+    if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+        raise LuminaLibError(f"{who}: refused on a stream under capture: it allocates and synchronises, which a graph cannot record - run one "
+                             "eager evaluation of this shape before the capture begins")
+
+
 def _require_gpu(t: torch.Tensor, name: str) -> None:
     if not t.is_cuda:
         raise LuminaLibError(
@@ -92,6 +100,7 @@ class DiTEngine:
                  patch_size: int, in_channels: int, out_channels: int, cap_feat_dim: int, qk_norm: bool,
                  norm_eps: float, num_classes: int = 0, num_experts: int = 0, limits: Optional[EngineLimits] = None,
                  device: Optional[torch.device] = None):
+        _refuse_if_capturing("DiTEngine (lt_create)")
         self.lib = _lib.load()
         self.device = torch.device(device if device is not None else "cuda")
         if not torch.cuda.is_available():
@@ -143,6 +152,7 @@ class DiTEngine:
         """Upload every tensor of a reference-format state_dict into the engine."""
         # the hoisted conditioning (text K / V of every layer, caption / label embedding) was computed from the OLD weights:
         # forget which tensors it came from, so the next call prepares it again (lt_set_weight also invalidates it engine-side)
+        _refuse_if_capturing("load_state_dict (lt_set_weight)")
         self._prompt.clear()
         s = _stream_ptr(self.device)
         skip = set(skip)

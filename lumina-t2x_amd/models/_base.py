@@ -9,7 +9,7 @@ import torch
 import torch.nn as nn
 
 from .. import _lib
-from ..engine import DiTEngine, EngineLimits
+from ..engine import DiTEngine, EngineLimits, _refuse_if_capturing
 
 
 # Any (re-)registration of a Parameter OR of a sub-module anywhere (setattr of an nn.Parameter, load_state_dict(assign=True),
@@ -152,6 +152,8 @@ class EngineBackedModel(EngineSamplers, WeightWatch, nn.Module):
         lim = self.engine_limits
         need = EngineLimits(max(lim.max_batch, B), max(lim.max_tokens, self._tokens(H, W)), max(lim.max_text, text_len))
         if self._engine is None or need != self._engine.limits or self._engine.device != x.device:
+            # (before the old engine is dropped: its buffers may be what a graph the caller recorded earlier reads)
+            _refuse_if_capturing(f"{type(self).__name__}: a new engine for this call's shapes (lt_create)")
             self._engine = None
             self._engine = DiTEngine(variant=self._variant, limits=need, device=x.device, **self._engine_kwargs())
             self.engine_limits = need

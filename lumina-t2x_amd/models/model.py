@@ -18,7 +18,7 @@ import torch
 import torch.nn as nn
 
 from .. import _lib
-from ..engine import DiTEngine, EngineLimits, ffn_hidden_dim
+from ..engine import DiTEngine, EngineLimits, _refuse_if_capturing, ffn_hidden_dim
 from ._base import EngineSamplers, WeightWatch
 from .components import AffineNorm, Linear, RMSNorm
 
@@ -169,6 +169,8 @@ class NextDiT(EngineSamplers, WeightWatch, nn.Module):
         lim = self.engine_limits
         need = EngineLimits(max(lim.max_batch, B), max(lim.max_tokens, n_tok), max(lim.max_text, text_len))
         if self._engine is None or need != self._engine.limits or self._engine.device != x.device:
+            # (before the old engine is dropped: its buffers may be what a graph the caller recorded earlier reads)
+            _refuse_if_capturing(f"{type(self).__name__}: a new engine for this call's shapes (lt_create)")
             self._engine = None
             self._engine = DiTEngine(
                 variant=_lib.LT_VARIANT_NEXT_T2I, dim=self.dim, n_layers=self.n_layers, n_heads=self.n_heads,

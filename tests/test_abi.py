@@ -217,3 +217,25 @@ def test_options_validate_ranges_and_engine_overrides_do_not_leak(lib):
     assert lib.lt_set_option(b"gemm_persist", 0) == 0 and lib.lt_set_option(b"gemm_persist", 1) != 0
     assert lib.lt_engine_set_option(None, b"graph", 0) != 0 and b"null engine" in lib.lt_last_error()
     assert lib.lt_engine_get_option(None, b"no_such", C.byref(val)) != 0
+
+
+READ_ONLY_NAMES = ("last_pair", "layout_flips", "layout_pinned")
+
+
+def test_read_only_engine_values_are_documented_and_are_no_options(lib):
+    """lt_engine_get_option also answers three names that are no options: what the engine did last (``last_pair``, ``layout_flips``) and
+    the latch a caller's graph sets (``layout_pinned``).  Each is documented in the debug header, answered by name in
+    csrc/engine.hip, absent from the option table (so it cannot be set), and needs an engine."""
+    debug = open(_lib.DEBUG_HEADER_PATH).read()
+    engine = open(os.path.join(REPO, "lumina-t2x_amd", "csrc", "engine.hip")).read()
+    getter = engine[engine.index('extern "C" int lt_engine_get_option'):]
+    answered = set(re.findall(r'strcmp\(name, "([a-z_]+)"\) == 0', getter))
+    assert answered == set(READ_ONLY_NAMES), answered
+    table = {r[0] for r in _option_table()}
+    val = C.c_int32(-7)
+    for n in READ_ONLY_NAMES:
+        assert re.search(r'"%s"[^"]*read-only' % n, debug, flags=re.S), f'"{n}" is not documented as read-only in lumina_dit_debug.h'
+        assert n not in table
+        assert lib.lt_set_option(n.encode(), 1) != 0 and b"unknown option" in lib.lt_last_error()
+        assert lib.lt_engine_get_option(None, n.encode(), C.byref(val)) != 0 and b"null engine" in lib.lt_last_error() and n.encode() in lib.lt_last_error()
+        assert val.value == -7
