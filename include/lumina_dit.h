@@ -345,6 +345,32 @@ int lt_sample_ode_adaptive(lt_engine* e, const void* z_dev, void* traj_dev, cons
 int lt_sample_ode_cfg_schedule(lt_engine* e, const void* z_dev, void* traj_dev, void* final_dev, const float* tgrid_host, int32_t n_grid,
                                int32_t method, const float* cfg_host, int32_t t_round_to_state_dtype, const lt_step_args* a, void* stream);
 
+/* Rescaled and norm-limited guidance: lt_sample_ode_cfg_schedule / lt_forward_cfg whose guided output is multiplied, per
+ * sample, by one factor f.  With c and u the cond and uncond rows' outputs on the first cfg_channels channels, g = u + w (c - u) with the
+ * bf16 rounding points of lt_forward_cfg, and the sums over one sample's n = cfg_channels H W elements taken in float64:
+ *   vc = sum c^2 / n - (sum c / n)^2, vg likewise;  ratio = sqrt(vc / vg) if vg > 0 and vc >= 0, else 1
+ *   fr = rescale ratio + (1 - rescale)                                   ("guidance rescale": the std of g pulled towards that of c)
+ *   fl = min(1, norm_limit sqrt(sum c^2) / (fr sqrt(sum g^2))) if norm_limit < inf and fr sqrt(sum g^2) > 0, else 1     (the norm of g at
+ *        most norm_limit times that of c)
+ *   f = fp32(fr fl), everything before it float64 without contraction; the guided channels become bf16(g f), one fp32 multiply.
+ * The channels at or past cfg_channels pass through row by row, as in lt_forward_cfg.  rescale in [0, 1]; norm_limit > 0, +inf = off; at
+ * (0, +inf) f is 1 and the results are lt_sample_ode_cfg_schedule's / lt_forward_cfg's bit for bit (through other kernels: callers that
+ * want the rule off call those).
+ * lt_sample_ode_cfg_rule: lt_sample_ode_cfg_schedule's arguments and behaviour plus the rule on every stage whose scale is not 1.  A stage
+ * at scale 1 exactly is that call's conditional-only stage, WITHOUT the rule (with norm_limit < 1 the rule would have scaled it).  The two
+ * parameters are committed with the scale table and read from device memory: a trajectory uses at most two HIP-graph keys (the guided
+ * evaluation with the rule, the conditional one) whatever the table, rescale and norm_limit hold.  No synchronisation, no host read.
+ * lt_forward_cfg_rule: ONE evaluation, always guided, at a->cfg_scale (any finite value, 1 included).  Both calls are refused on a stream
+ * under capture (the trajectory for the reason lt_sample_ode is; the single evaluation because no test records it yet).
+ * Not served: packed batches, regional prompts, views.  Refused by name with nothing written: what lt_sample_ode_cfg_schedule refuses (for
+ * lt_forward_cfg_rule: a null argument, the shape, an odd batch, a scale that is not finite, a regional prompt, a conditioning prepared for
+ * another batch); rescale outside [0, 1] or not finite; norm_limit not above 0, or NaN. */
+int lt_sample_ode_cfg_rule(lt_engine* e, const void* z_dev, void* traj_dev, void* final_dev, const float* tgrid_host, int32_t n_grid,
+                           int32_t method, const float* cfg_host, float rescale, float norm_limit, int32_t t_round_to_state_dtype,
+                           const lt_step_args* a, void* stream);
+int lt_forward_cfg_rule(lt_engine* e, const void* x_dev, const float* t_dev, void* out_dev, float rescale, float norm_limit, const lt_step_args* a,
+                        void* stream);
+
 /* number of model evaluations issued by the last lt_sample_ode / lt_sample_ode_packed / lt_sample_views / lt_sample_views_guided / lt_sample_sde / lt_sample_ode_adaptive call */
 int64_t lt_last_nfe(lt_engine* e);
 /* the rows those evaluations ran, summed: nfe * batch for every sampler but lt_sample_ode_cfg_schedule, whose conditional-only stages run half */

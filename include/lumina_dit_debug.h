@@ -206,6 +206,22 @@ int lt_op_unpatchify_cfg(const void* rows, int32_t ld, void* out, int32_t out_dt
 int lt_op_unpatchify_cfg_dev(const void* rows, int32_t ld, void* out, int32_t out_dtype, int32_t B, int32_t C, int32_t out_ch, int32_t H, int32_t W,
                              int32_t patch, int32_t use_cfg, const float* cfg_scale_dev, int32_t cfg_channels, int32_t wp_stride, int32_t dup,
                              void* stream);
+/* Rescaled / norm-limited guidance (csrc/guidance.hip), for tests/test_gpu_cfg_rule.py.  B counts the 2 B' rows of the evaluation.
+ *   guidance_slices: S, the slices a sample's sums are cut into - a constant of the build, the same on every device.
+ *   guidance_stats: partials_dev [B' * S * 4] doubles; { sum c, sum c^2, sum g, sum g^2 } of slice s of sample b at [(b * S + s) * 4], over the
+ *   first cfg_channels channels of the rows (lt_op_unpatchify_cfg's index walk), g the guided value at the scale in cfg_scale_dev, products and
+ *   sums in float64 in an order the launch fixes.  Every one of the B' * S * 4 words is written (an empty slice: zeros), nothing behind them.
+ *   unpatchify_cfg_rule: lt_op_unpatchify_cfg_dev with the guided values multiplied in fp32 by the sample's factor f and rounded to bf16; f is
+ *   formed in float64 from the partials summed in slice order, the blend in rescale_dev and the limit in norm_limit_dev (one float of device
+ *   memory each; +inf: no limit), and rounded once to fp32.  With dup, or with use_cfg 0, the three may be NULL and the result is
+ *   lt_op_unpatchify_cfg_dev's.  factor_out_dev (may be NULL): B' floats, the factors.  Refused: an odd B, more than 256 samples. */
+int32_t lt_op_guidance_slices(void);
+int lt_op_guidance_stats(const void* rows, int32_t ld, int32_t B, int32_t out_ch, int32_t H, int32_t W, int32_t patch, const float* cfg_scale_dev,
+                         int32_t cfg_channels, int32_t wp_stride, double* partials_dev, void* stream);
+int lt_op_unpatchify_cfg_rule(const void* rows, int32_t ld, void* out, int32_t out_dtype, int32_t B, int32_t C, int32_t out_ch, int32_t H, int32_t W,
+                              int32_t patch, int32_t use_cfg, const float* cfg_scale_dev, int32_t cfg_channels, int32_t wp_stride, int32_t dup,
+                              const double* partials_dev, const float* rescale_dev, const float* norm_limit_dev, float* factor_out_dev,
+                              void* stream);
 /* The ragged boundary kernels of a packed batch (csrc/packed.hip): one launch for all samples.  hw_host = [B][2] latent sizes (host); the
  * flat state holds sample b = [C, H_b, W_b] at element offset sum_{j<b} C H_j W_j; N = token rows per sample in the row buffers (>= the longest
  * sequence).  Each launching entry builds the table of the size list, stores it at tab_dev (5 * 64 ints of device memory) and runs its kernel.

@@ -115,6 +115,8 @@ _SIGNATURES: Dict[str, tuple] = {
     "lt_sample_ode_adaptive": (_i32, [_vp, _vp, _vp, C.POINTER(_f32), _i32, _i32, _f32, _f32, _f32, _i32, _i32, _i32, C.POINTER(LtStepArgs), _vp,
                                       C.POINTER(LtOdeAdaptiveStats)]),
     "lt_sample_ode_cfg_schedule": (_i32, [_vp, _vp, _vp, _vp, C.POINTER(_f32), _i32, _i32, C.POINTER(_f32), _i32, C.POINTER(LtStepArgs), _vp]),
+    "lt_sample_ode_cfg_rule": (_i32, [_vp, _vp, _vp, _vp, C.POINTER(_f32), _i32, _i32, C.POINTER(_f32), _f32, _f32, _i32, C.POINTER(LtStepArgs), _vp]),
+    "lt_forward_cfg_rule": (_i32, [_vp, _vp, _vp, _vp, _f32, _f32, C.POINTER(LtStepArgs), _vp]),
     "lt_last_nfe": (_i64, [_vp]),
     "lt_last_eval_rows": (_i64, [_vp]),
     "lt_graph_replays": (_i64, [_vp]),
@@ -176,6 +178,9 @@ _SIGNATURES: Dict[str, tuple] = {
     "lt_op_timestep_features": (_i32, [_vp, _i32, _vp, _i32, _i32, _vp]),
     "lt_op_cap_pool_ln": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "lt_op_unpatchify_cfg_dev": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _vp]),
+    "lt_op_guidance_slices": (_i32, []),
+    "lt_op_guidance_stats": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _vp, _vp]),
+    "lt_op_unpatchify_cfg_rule": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "lt_op_unpatchify_cfg": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _i32, _vp]),
     "lt_op_packed_table": (_i32, [C.POINTER(_i32), _i32, _i32, _i32, C.POINTER(_i32), C.POINTER(_i64), C.POINTER(_i32)]),
     "lt_op_patchify_packed": (_i32, [_vp, _i32, _vp, C.POINTER(_i32), _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),

@@ -216,7 +216,10 @@ struct lt_engine {
     std::vector<GraphEntry> graphs;
     void *g_x = nullptr, *g_out = nullptr;
     float* g_t = nullptr;
-    float* g_cfg = nullptr;  // the guidance scale of an evaluation that reads it from device memory (lt_sample_ode_cfg_schedule)
+    // [3]: the guidance scale of an evaluation that reads it from device memory (lt_sample_ode_cfg_schedule), then the rescale blend and the
+    // norm limit of a guidance rule (lt_sample_ode_cfg_rule / lt_forward_cfg_rule)
+    float* g_cfg = nullptr;
+    double* g_stats = nullptr;  // the rule's partial sums: max_batch / 2 samples x LT_GUIDANCE_SLICES x 4 (guidance_stats -> unpatchify_cfg_rule)
     hipStream_t cap_stream = nullptr;
     long long graph_replays = 0;
     // profiling
@@ -240,9 +243,11 @@ int packed_call_begin(lt_engine* e, const char* who, const int32_t* hw_host, con
 // cfg_dev (lt_sample_ode_cfg_schedule; tensor input only): the evaluation's guidance scale, one float of device memory; it is staged into
 // e->g_cfg, which the closing kernel reads, so the scale is no part of the graph key and a->cfg_scale is ignored.  With cond_only the
 // evaluation is the plain forward of the first a->batch / 2 rows of x_in on the first a->batch / 2 rows of the conditioning that was prepared
-// for a->batch rows, and its output is written to both halves of `out` (a->batch rows)
+// for a->batch rows, and its output is written to both halves of `out` (a->batch rows).  rule (with cfg_dev): the guided evaluation scales
+// its guided channels by the per-sample factor of the rescale / norm-limit rule whose two parameters the caller has put behind the scale,
+// in e->g_cfg[1..2]; one more bit of the key, and no change to a conditional-only evaluation.  cfg_dev == e->g_cfg: the scale is in place
 int forward_graphed(lt_engine* e, const void* x_in, const float* t_dev, void* out, const lt_step_args* a, int use_cfg, hipStream_t s,
-                    const PackedCall* pc = nullptr, const float* cfg_dev = nullptr, bool cond_only = false);
+                    const PackedCall* pc = nullptr, const float* cfg_dev = nullptr, bool cond_only = false, bool rule = false);
 // true while stream s records into a graph (the caller's torch.cuda.graph / hipStreamBeginCapture, or the engine's own cache)
 bool stream_capturing(hipStream_t s);
 // the entry points that allocate, synchronise or copy from host memory cannot be recorded into a caller's graph: non-zero after

@@ -403,8 +403,10 @@ int ensure_weight_layout(lt_engine* e, bool want, hipStream_t s, bool recording 
 }
 
 // An evaluation of the guidance schedule (forward_graphed's cfg_dev): the closing kernel reads its scale from `scale` (device memory); dup:
-// the conditional-only evaluation - a->batch rows on the first a->batch rows of a conditioning prepared for 2 a->batch, written twice
-struct CfgFromDev { const float* scale; bool dup; };
+// the conditional-only evaluation - a->batch rows on the first a->batch rows of a conditioning prepared for 2 a->batch, written twice;
+// rule (may be null): rule[0] the rescale blend, rule[1] the norm limit - a guided evaluation then runs guidance_stats and the
+// closing kernel that multiplies by the per-sample factor
+struct CfgFromDev { const float* scale; bool dup; const float* rule = nullptr; };
 
 int run_forward(lt_engine* e, const void* x_in, const float* t_dev, void* out, const lt_step_args* a, int use_cfg,
                 hipStream_t s, const PackedDesc* pk = nullptr, const CfgFromDev* gs = nullptr) {
@@ -797,7 +799,12 @@ int run_forward(lt_engine* e, const void* x_in, const float* t_dev, void* out, c
     {
         ProfScope ps(e, 2, 0, s);
         const int cfg_ch = a->cfg_channels > 0 ? a->cfg_channels : 3;
-        if (!pk && gs) {
+        if (!pk && gs && gs->rule && !gs->dup) {
+            const int rule_ch = cfg_ch < c.in_channels ? cfg_ch : c.in_channels;  // (the channels the closing kernel guides)
+            if (launch_guidance_stats(e->frows, e->nfinal, B, c.out_channels, a->latent_h, a->latent_w, p, gs->scale, rule_ch, Wrow, e->g_stats, s)) return 1;
+            if (launch_unpatchify_cfg_rule(e->frows, e->nfinal, out, a->io_dtype, B, c.in_channels, c.out_channels, a->latent_h, a->latent_w, p,
+                                           use_cfg, gs->scale, rule_ch, Wrow, 0, e->g_stats, gs->rule, gs->rule + 1, nullptr, s)) return 1;
+        } else if (!pk && gs) {
             if (launch_unpatchify_cfg_dev(e->frows, e->nfinal, out, a->io_dtype, gs->dup ? 2 * B : B, c.in_channels, c.out_channels, a->latent_h,
                                           a->latent_w, p, use_cfg, gs->scale, cfg_ch, Wrow, gs->dup ? 1 : 0, s)) return 1;
         } else if (!pk) {
@@ -878,18 +885,18 @@ int softmax_scale_for(const lt_engine* e, const lt_step_args* a, int N, float* s
 }
 
 int forward_graphed(lt_engine* e, const void* x_in, const float* t_dev, void* out, const lt_step_args* a, int use_cfg, hipStream_t s,
-                    const PackedCall* pc, const float* cfg_dev, bool cond_only) {
+                    const PackedCall* pc, const float* cfg_dev, bool cond_only, bool rule) {
     // a stage of the guidance schedule: the scale travels through e->g_cfg - on the eager path too, so both run one kernel - and the key
     // holds a zeroed cfg_scale; the conditional-only evaluation has a->batch / 2 rows
     lt_step_args own;
-    const CfgFromDev cfd{e->g_cfg, cond_only};
+    const CfgFromDev cfd{e->g_cfg, cond_only, rule && !cond_only ? e->g_cfg + 1 : nullptr};
     const CfgFromDev* cd = nullptr;
     if (cfg_dev) {
         LT_REQUIRE(!pc && a->batch % 2 == 0, "a guidance schedule needs a tensor state with an even batch");
         own = *a;
         own.cfg_scale = 0.f;
         if (cond_only) own.batch = a->batch / 2;
-        else LT_CHECK_HIP(hipMemcpyAsync(e->g_cfg, cfg_dev, sizeof(float), hipMemcpyDeviceToDevice, s));
+        else if (cfg_dev != e->g_cfg) LT_CHECK_HIP(hipMemcpyAsync(e->g_cfg, cfg_dev, sizeof(float), hipMemcpyDeviceToDevice, s));
         a = &own;
         use_cfg = cond_only ? 0 : 1;
         cd = &cfd;
@@ -922,9 +929,10 @@ int forward_graphed(lt_engine* e, const void* x_in, const float* t_dev, void* ou
     if (stream_capturing(s)) return run(x_in, t_dev, out, s);
     // (both option generations: the process defaults' and this engine's overrides' - kernel selection is baked into a captured graph)
     // ... and the softmax rule: the scale it selects is a kernel argument (qa.out_scale / at.scale)
-    // ... and whether the scale comes from device memory / the evaluation is the conditional-only one: other closing kernels
-    const int extra[12] = {use_cfg, e->prompt_B, e->prompt_T, e->prompt_Tpad, e->reg_Y, e->reg_h, e->reg_w, lt_opt_generation(), lt_opt_engine_generation(),
-                           e->softmax_rule, cd ? 1 : 0, cond_only ? 1 : 0};
+    // ... and whether the scale comes from device memory / the evaluation is the conditional-only one / the guided one under a rescale or
+    // norm-limit rule: other closing kernels (the rule's parameters are read from device memory, like the scale)
+    const int extra[13] = {use_cfg, e->prompt_B, e->prompt_T, e->prompt_Tpad, e->reg_Y, e->reg_h, e->reg_w, lt_opt_generation(), lt_opt_engine_generation(),
+                           e->softmax_rule, cd ? 1 : 0, cond_only ? 1 : 0, cd && cd->rule ? 1 : 0};
     std::vector<char> key(sizeof(lt_step_args) + sizeof(extra));
     memcpy(key.data(), a, sizeof(lt_step_args));
     memcpy(key.data() + sizeof(lt_step_args), extra, sizeof(extra));
@@ -1193,8 +1201,10 @@ extern "C" int lt_create(const lt_config* cfg, lt_engine** out) {
             void* q;
             if (dev_alloc(e, &q, Bm * sizeof(float))) return fail();
             e->g_t = (float*)q;
-            if (dev_alloc(e, &q, sizeof(float))) return fail();
+            if (dev_alloc(e, &q, 3 * sizeof(float))) return fail();  // (the scale; the rescale blend and the norm limit of a rule)
             e->g_cfg = (float*)q;
+            if (dev_alloc(e, &q, (size_t)((cfg->max_batch + 1) / 2) * LT_GUIDANCE_SLICES * 4 * sizeof(double))) return fail();
+            e->g_stats = (double*)q;
             if (dev_alloc(e, &q, sizeof(int))) return fail();  // (zeroed: the weights start row-major)
             e->w_pair_dev = (int*)q;
         }

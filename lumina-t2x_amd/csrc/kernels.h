@@ -356,6 +356,19 @@ int launch_unpatchify_cfg(const u16* rows, int ld, void* out, int out_dtype, int
 // B / 2 rows read, each written to rows b and b + B / 2 of the output.  B counts output rows.  (lt_sample_ode_cfg_schedule)
 int launch_unpatchify_cfg_dev(const u16* rows, int ld, void* out, int out_dtype, int B, int C, int out_ch, int H, int W, int patch, int use_cfg,
                               const float* cfg_scale_dev, int cfg_channels, int wp_stride, int dup, hipStream_t stream);
+// rescaled / norm-limited guidance (guidance.hip).  B counts the 2 B' rows of the evaluation; partials: B' * LT_GUIDANCE_SLICES * 4
+// doubles, { sum c, sum c^2, sum g, sum g^2 } of slice s of sample b at [(b * LT_GUIDANCE_SLICES + s) * 4], every one written by every launch
+//   guidance_stats: the sums over the first cfg_channels channels of the final-layer rows, g the guided value at the scale in cfg_scale_dev
+//   unpatchify_cfg_rule: launch_unpatchify_cfg_dev whose guided values are multiplied by the sample's factor (formed from the partials, the
+//   rescale blend and the norm limit, one float of device memory each) and rounded; factor_out (may be null) receives the B' factors
+//   guidance_params_store: dst[0..2] = scale, rescale, limit
+constexpr int LT_GUIDANCE_SLICES = 32;
+int launch_guidance_stats(const u16* rows, int ld, int B, int out_ch, int H, int W, int patch, const float* cfg_scale_dev, int cfg_channels,
+                          int wp_stride, double* partials, hipStream_t stream);
+int launch_unpatchify_cfg_rule(const u16* rows, int ld, void* out, int out_dtype, int B, int C, int out_ch, int H, int W, int patch, int use_cfg,
+                               const float* cfg_scale_dev, int cfg_channels, int wp_stride, int dup, const double* partials,
+                               const float* rescale_dev, const float* limit_dev, float* factor_out, hipStream_t stream);
+int launch_guidance_params_store(float* dst, float scale, float rescale, float limit, hipStream_t stream);
 // torchdiffeq fixed-grid state arithmetic (modes documented in misc.hip)
 int launch_ode_combine(int mode, const void* y0, const void* k1, const void* k2, const void* k3, const void* k4,
                        void* out, int dtype, float dt, long long n, hipStream_t stream);

@@ -39,6 +39,7 @@ struct Trajectory {
     const PackedCall* pc = nullptr;  // a packed batch: the states are flat buffers (lt_sample_ode_packed)
     // a guidance schedule (lt_sample_ode_cfg_schedule): the scale of evaluation number `call`, on the host and where commit sent it
     const float *cfg_host = nullptr, *cfg_dev = nullptr;
+    bool cfg_rule = false;  // ... under a rescale / norm-limit rule (lt_sample_ode_cfg_rule): its parameters are in e->g_cfg[1..2]
     int start(const void* z, void* traj_dev, bool z_in_slot0) {
         traj = traj_dev;
         flips0 = e->layout_flips_total;
@@ -56,7 +57,7 @@ struct Trajectory {
         // scale 1 exactly: the guided output is the conditional one - the cond rows alone, written to both halves
         const bool cond_only = cfg_host[call] == 1.0f;
         rows += cond_only ? a->batch / 2 : a->batch;
-        return forward_graphed(e, y, t, out, a, 1, s, nullptr, cfg_dev + call, cond_only);
+        return forward_graphed(e, y, t, out, a, 1, s, nullptr, cfg_dev + call, cond_only, cfg_rule);
     }
     int advance(int traj_slot) {  // y1 is the current state now [and slot `traj_slot` of the record]
         if (traj) LT_CHECK_HIP(hipMemcpyAsync((char*)traj + (size_t)traj_slot * sbytes, y1(), sbytes, hipMemcpyDeviceToDevice, s));
@@ -85,9 +86,10 @@ float bf16_round_host(float f) {
 // n elements (the stage arithmetic is elementwise, so a packed batch's flat state runs through it as it is).  The callers have validated
 // the grid, the method and the shape.  With `mb` (lt_sample_ode_masked) the LAST combine of every step is the masked launcher - the same
 // arithmetic followed by the inpainting blend at the step's end time - and nothing else changes.  With `cs` (lt_sample_ode_cfg_schedule)
-// evaluation i * stages + k takes its guidance scale from cs->table: the scales are committed behind the stage times, one float per stage.
+// evaluation i * stages + k takes its guidance scale from cs->table: the scales are committed behind the stage times, one float per stage;
+// cs->rule (lt_sample_ode_cfg_rule): the rescale blend and the norm limit travel behind the scales and are put into e->g_cfg[1..2] once.
 struct MaskedBlend { const void *mask, *x1, *noise; };
-struct CfgSchedule { const float* table; };  // host, (n_grid - 1) * stages
+struct CfgSchedule { const float* table; const float* rule = nullptr; };  // host: (n_grid - 1) * stages scales; { rescale, norm limit } or null
 
 int ode_fixed_grid(lt_engine* e, const void* z_dev, void* traj_dev, void* final_dev, const float* tgrid_host, int n_grid, int method, int use_cfg,
                    int t_round, const lt_step_args* a, hipStream_t s, long long n, const PackedCall* pc, const MaskedBlend* mb = nullptr,
@@ -98,7 +100,7 @@ int ode_fixed_grid(lt_engine* e, const void* z_dev, void* traj_dev, void* final_
     const bool bf = a->io_dtype == LT_BF16;
     // stage times; torchdiffeq's _PerturbFunc casts t to the state dtype before calling the model, then
     // integrators.py:108 broadcasts it to an fp32 [B] vector
-    const int nsent = ncalls * B + (cs ? ncalls : 0);
+    const int nsent = ncalls * B + (cs ? ncalls : 0) + (cs && cs->rule ? 2 : 0);
     float* tp = e->times.begin(nsent, s);
     if (!tp) return 1;
     std::vector<float> dts(n_grid - 1);
@@ -116,10 +118,13 @@ int ode_fixed_grid(lt_engine* e, const void* z_dev, void* traj_dev, void* final_
         }
     }
     if (cs) memcpy(tp + (size_t)ncalls * B, cs->table, (size_t)ncalls * sizeof(float));
+    if (cs && cs->rule) memcpy(tp + (size_t)ncalls * B + ncalls, cs->rule, 2 * sizeof(float));
     if (e->times.commit(nsent, s)) return 1;
+    if (cs && cs->rule)
+        LT_CHECK_HIP(hipMemcpyAsync(e->g_cfg + 1, e->times.dev + (size_t)ncalls * B + ncalls, 2 * sizeof(float), hipMemcpyDeviceToDevice, s));
     Trajectory tr{e, a, use_cfg, s, (size_t)n * (bf ? 2 : 4)};
     tr.pc = pc;
-    if (cs) { tr.cfg_host = cs->table; tr.cfg_dev = e->times.dev + (size_t)ncalls * B; }
+    if (cs) { tr.cfg_host = cs->table; tr.cfg_dev = e->times.dev + (size_t)ncalls * B; tr.cfg_rule = cs->rule != nullptr; }
     if (tr.start(z_dev, traj_dev, true)) return 1;
     const int dt_code = bf ? 1 : 0;
     for (int i = 0; i + 1 < n_grid; ++i) {
@@ -225,25 +230,76 @@ extern "C" int lt_sample_ode_masked_packed(lt_engine* e, const void* z_flat_dev,
 }
 
 // ---- guidance schedules: a scale per stage, conditional-only stages at half the rows --------------------------------------
-extern "C" int lt_sample_ode_cfg_schedule(lt_engine* e, const void* z_dev, void* traj_dev, void* final_dev, const float* tgrid_host, int32_t n_grid,
-                                          int32_t method, const float* cfg_host, int32_t t_round, const lt_step_args* a, void* stream) {
-    LT_REQUIRE(e && z_dev && tgrid_host && cfg_host && a, "lt_sample_ode_cfg_schedule: null argument");
-    if (refuse_if_capturing((hipStream_t)stream, "lt_sample_ode_cfg_schedule")) return 2;  // (the stage times travel through a host staging buffer that the next call rewrites)
+namespace {
+
+// what a guided evaluation on the two halves of a prepared conditioning needs, refused by name before anything is written
+int check_guided_halves(const lt_engine* e, const char* who, const lt_step_args* a) {
+    LT_REQUIRE(a->batch % 2 == 0, "%s: guidance needs an even batch (cond + uncond rows), got %d", who, a->batch);
+    LT_REQUIRE(e->reg_Y == 0, "%s: a regional prompt is prepared (lt_prepare_prompt_regional): its captions belong to "
+               "one cond and one uncond row, there is no conditional half to evaluate alone", who);
+    LT_REQUIRE(e->prompt_B == a->batch, "%s: %s was called for batch %d, step has batch %d", who,
+               e->v.labels ? "lt_prepare_labels" : "lt_prepare_prompt", e->prompt_B, a->batch);
+    return 0;
+}
+
+// the parameters of the rescale / norm-limit rule
+int check_rule(const char* who, float rescale, float norm_limit) {
+    LT_REQUIRE(std::isfinite(rescale) && rescale >= 0.f && rescale <= 1.f, "%s: rescale %g is not a blend in [0, 1]", who, (double)rescale);
+    LT_REQUIRE(!std::isnan(norm_limit) && norm_limit > 0.f, "%s: norm_limit %g is not above 0 (+inf switches the limit off)", who, (double)norm_limit);
+    return 0;
+}
+
+// lt_sample_ode_cfg_schedule, and with `rule` = { rescale, norm limit } lt_sample_ode_cfg_rule
+int sample_cfg_table(lt_engine* e, const char* who, const void* z_dev, void* traj_dev, void* final_dev, const float* tgrid_host, int n_grid, int method,
+                     const float* cfg_host, const float* rule, int t_round, const lt_step_args* a, hipStream_t s) {
+    LT_REQUIRE(e && z_dev && tgrid_host && cfg_host && a, "%s: null argument", who);
+    if (refuse_if_capturing(s, who)) return 2;  // (the stage times travel through a host staging buffer that the next call rewrites)
     LtOptScope opt_scope(&e->opts);
-    LT_REQUIRE(n_grid >= 2, "lt_sample_ode_cfg_schedule: need at least 2 grid points");
-    LT_REQUIRE(method >= LT_ODE_EULER && method <= LT_ODE_RK4, "lt_sample_ode_cfg_schedule: unknown method %d", method);
-    if (check_step_shape(e, "lt_sample_ode_cfg_schedule", a)) return 2;
-    LT_REQUIRE(a->batch % 2 == 0, "lt_sample_ode_cfg_schedule: guidance needs an even batch (cond + uncond rows), got %d", a->batch);
+    LT_REQUIRE(n_grid >= 2, "%s: need at least 2 grid points", who);
+    LT_REQUIRE(method >= LT_ODE_EULER && method <= LT_ODE_RK4, "%s: unknown method %d", who, method);
+    if (check_step_shape(e, who, a)) return 2;
+    LT_REQUIRE(a->batch % 2 == 0, "%s: guidance needs an even batch (cond + uncond rows), got %d", who, a->batch);
     const int stages = method == LT_ODE_EULER ? 1 : (method == LT_ODE_MIDPOINT ? 2 : 4);
     for (int i = 0; i < (n_grid - 1) * stages; ++i)
-        LT_REQUIRE(std::isfinite(cfg_host[i]), "lt_sample_ode_cfg_schedule: the scale of stage %d of interval %d is not finite", i % stages, i / stages);
-    LT_REQUIRE(e->reg_Y == 0, "lt_sample_ode_cfg_schedule: a regional prompt is prepared (lt_prepare_prompt_regional): its captions belong to "
-               "one cond and one uncond row, there is no conditional half to evaluate alone");
-    LT_REQUIRE(e->prompt_B == a->batch, "lt_sample_ode_cfg_schedule: %s was called for batch %d, step has batch %d",
-               e->v.labels ? "lt_prepare_labels" : "lt_prepare_prompt", e->prompt_B, a->batch);
+        LT_REQUIRE(std::isfinite(cfg_host[i]), "%s: the scale of stage %d of interval %d is not finite", who, i % stages, i / stages);
+    if (rule && check_rule(who, rule[0], rule[1])) return 2;
+    if (check_guided_halves(e, who, a)) return 2;
     const long long n = (long long)a->batch * e->cfg.in_channels * a->latent_h * a->latent_w;
-    const CfgSchedule cs{cfg_host};
-    return ode_fixed_grid(e, z_dev, traj_dev, final_dev, tgrid_host, n_grid, method, 1, t_round, a, (hipStream_t)stream, n, nullptr, nullptr, &cs);
+    const CfgSchedule cs{cfg_host, rule};
+    return ode_fixed_grid(e, z_dev, traj_dev, final_dev, tgrid_host, n_grid, method, 1, t_round, a, s, n, nullptr, nullptr, &cs);
+}
+
+}  // namespace
+
+extern "C" int lt_sample_ode_cfg_schedule(lt_engine* e, const void* z_dev, void* traj_dev, void* final_dev, const float* tgrid_host, int32_t n_grid,
+                                          int32_t method, const float* cfg_host, int32_t t_round, const lt_step_args* a, void* stream) {
+    return sample_cfg_table(e, "lt_sample_ode_cfg_schedule", z_dev, traj_dev, final_dev, tgrid_host, n_grid, method, cfg_host, nullptr, t_round, a,
+                            (hipStream_t)stream);
+}
+
+// ---- rescaled and norm-limited guidance: a per-sample factor on every guided stage -------------------------------------------
+extern "C" int lt_sample_ode_cfg_rule(lt_engine* e, const void* z_dev, void* traj_dev, void* final_dev, const float* tgrid_host, int32_t n_grid,
+                                      int32_t method, const float* cfg_host, float rescale, float norm_limit, int32_t t_round, const lt_step_args* a,
+                                      void* stream) {
+    const float rule[2] = {rescale, norm_limit};
+    return sample_cfg_table(e, "lt_sample_ode_cfg_rule", z_dev, traj_dev, final_dev, tgrid_host, n_grid, method, cfg_host, rule, t_round, a,
+                            (hipStream_t)stream);
+}
+
+// One guided evaluation under the rule, at a->cfg_scale.  The three parameters reach the engine's fixed device words through a launch in
+// front of the evaluation.  Refused on a capturing stream: a recorded evaluation of this kind has no test behind it yet.
+extern "C" int lt_forward_cfg_rule(lt_engine* e, const void* x_dev, const float* t_dev, void* out_dev, float rescale, float norm_limit,
+                                   const lt_step_args* a, void* stream) {
+    const char* who = "lt_forward_cfg_rule";
+    LT_REQUIRE(e && x_dev && t_dev && out_dev && a, "%s: null argument", who);
+    if (refuse_if_capturing((hipStream_t)stream, who)) return 2;
+    LtOptScope opt_scope(&e->opts);
+    if (check_step_shape(e, who, a)) return 2;
+    LT_REQUIRE(std::isfinite(a->cfg_scale), "%s: the scale is not finite", who);
+    if (check_rule(who, rescale, norm_limit)) return 2;
+    if (check_guided_halves(e, who, a)) return 2;
+    if (launch_guidance_params_store(e->g_cfg, a->cfg_scale, rescale, norm_limit, (hipStream_t)stream)) return 1;
+    return forward_graphed(e, x_dev, t_dev, out_dev, a, 1, (hipStream_t)stream, nullptr, e->g_cfg, false, true);
 }
 
 // ---- multi-view (visual-anagram) sampling ------------------------------------------------------------------------------------------

@@ -440,6 +440,61 @@ class DiTEngine:
         _lib.check(rc, "lt_sample_ode_cfg_schedule")
         return out
 
+    # ---- rescaled and norm-limited guidance: a per-sample factor on every guided stage -------------
+    @staticmethod
+    def _rule(rescale, norm_limit, what: str):
+        from .transport.guidance import check_rule
+        try:
+            return check_rule(rescale, norm_limit)
+        except ValueError as exc:
+            raise LuminaLibError(f"{what}: {exc}") from None
+
+    def sample_ode_cfg_rule(self, z: torch.Tensor, tgrid, table, method: str, *, rescale: float = 0.0, norm_limit: float = math.inf,
+                            scale_factor: float = 1.0, scale_watershed: float = 1.0, base_seqlen: Optional[int] = None,
+                            proportional_attn: bool = False, t_round_to_state_dtype: bool = True, return_trajectory: bool = True,
+                            ntk_factor: float = 1.0, cfg_scale=None) -> torch.Tensor:
+        """``sample_ode_cfg_schedule`` whose guided stages multiply their guided channels by the per-sample factor of
+        ``transport.guidance.guided_rule`` (lt_sample_ode_cfg_rule): ``rescale`` in [0, 1] pulls the guided output's std towards the conditional
+        output's, ``norm_limit`` (> 0, inf: off) caps its L2 norm at that multiple of the conditional output's.  Stages at scale 1 exactly are
+        conditional-only and skip the rule.  This IS the rule call, at any parameters; ``model.sample_ode_cfg_schedule`` routes the defaults to
+        the schedule call."""
+        _require_gpu(z, "z")
+        if method not in _lib.ODE_METHODS:
+            raise LuminaLibError(f"fixed-grid method '{method}' not in {sorted(_lib.ODE_METHODS)}")
+        rescale, norm_limit = self._rule(rescale, norm_limit, "sample_ode_cfg_rule")
+        z = z.contiguous()
+        garr, n = _grid_array(tgrid)
+        tab = table if isinstance(table, torch.Tensor) else torch.tensor(list(table), dtype=torch.float32)
+        tab = tab.detach().to("cpu", torch.float32).reshape(-1).contiguous()
+        stages = {"euler": 1, "midpoint": 2, "rk4": 4}[method]
+        if tab.numel() != max(n - 1, 0) * stages:
+            raise LuminaLibError(f"sample_ode_cfg_rule: the table has {tab.numel()} entries, a {n}-point {method} grid has "
+                                 f"{max(n - 1, 0) * stages} stages")
+        a = self._step_args(z, 0.0, scale_factor, scale_watershed, base_seqlen, proportional_attn, ntk_factor=ntk_factor)
+        out, traj_ptr, fin_ptr = _traj_or_final(z, max(n, 1), z.shape, return_trajectory)
+        with torch.cuda.device(self.device):
+            rc = self.lib.lt_sample_ode_cfg_rule(self.handle, C.c_void_p(z.data_ptr()), traj_ptr, fin_ptr, garr, n, _lib.ODE_METHODS[method],
+                                                 C.cast(tab.data_ptr(), C.POINTER(C.c_float)), rescale, norm_limit, int(t_round_to_state_dtype),
+                                                 C.byref(a), C.c_void_p(_stream_ptr(self.device)))
+        _lib.check(rc, "lt_sample_ode_cfg_rule")
+        return out
+
+    def forward_cfg_rule(self, x: torch.Tensor, t: torch.Tensor, *, cfg_scale: float, rescale: float = 0.0, norm_limit: float = math.inf,
+                         scale_factor: float = 1.0, scale_watershed: float = 1.0, base_seqlen: Optional[int] = None,
+                         proportional_attn: bool = False, ntk_factor: float = 1.0) -> torch.Tensor:
+        """one guided evaluation at ``cfg_scale`` under the rule (lt_forward_cfg_rule): ``guided_rule`` on the model's output of all rows"""
+        _require_gpu(x, "x")
+        rescale, norm_limit = self._rule(rescale, norm_limit, "forward_cfg_rule")
+        x = x.contiguous()
+        t32 = t.to(device=x.device, dtype=torch.float32).contiguous()
+        out = torch.empty_like(x)
+        a = self._step_args(x, cfg_scale, scale_factor, scale_watershed, base_seqlen, proportional_attn, ntk_factor=ntk_factor)
+        with torch.cuda.device(self.device):
+            rc = self.lib.lt_forward_cfg_rule(self.handle, C.c_void_p(x.data_ptr()), C.c_void_p(t32.data_ptr()), C.c_void_p(out.data_ptr()),
+                                              rescale, norm_limit, C.byref(a), C.c_void_p(_stream_ptr(self.device)))
+        _lib.check(rc, "lt_forward_cfg_rule")
+        return out
+
     def sample_ode_adaptive(self, z: torch.Tensor, tgrid: torch.Tensor, method: str, *, rtol: float, atol: float,
                             first_step: Optional[float] = None, max_steps: int = 2 ** 31 - 1, use_cfg: bool, cfg_scale: float = 1.0,
                             scale_factor: float = 1.0, scale_watershed: float = 1.0, base_seqlen: Optional[int] = None,

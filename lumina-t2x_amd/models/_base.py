@@ -3,6 +3,7 @@ reference's state_dict keys; a forward call hands them to the HIP engine (csrc/)
 PyTorch implementation of the forward pass and no CPU fallback."""
 from __future__ import annotations
 
+import math
 from typing import Optional
 
 import torch
@@ -88,30 +89,60 @@ class EngineSamplers:
         eng, args = self._engine_sampler_args(x, use_cfg, kw)
         return eng.sample_ode_masked(x, tgrid, mask, x1, noise, method, use_cfg=use_cfg, t_round_to_state_dtype=t_round, **args)
 
-    def _engine_sample_ode_cfg_schedule(self, x, tgrid, method, t_round, table, kw, return_trajectory=True):
-        """kwargs of forward_with_cfg -> lt_sample_ode_cfg_schedule (guidance schedules; ``cfg_scale`` in kw is ignored)"""
+    def _engine_sample_ode_cfg_schedule(self, x, tgrid, method, t_round, table, kw, return_trajectory=True, rescale=0.0, norm_limit=math.inf):
+        """kwargs of forward_with_cfg -> lt_sample_ode_cfg_schedule (guidance schedules; ``cfg_scale`` in kw is ignored), or - with a
+        rescale blend or a norm limit - lt_sample_ode_cfg_rule"""
+        from ..transport.guidance import rule_is_off
         kw.setdefault("cfg_scale", 1.0)
         eng, args = self._engine_sampler_args(x, True, kw)
         args.pop("cfg_scale", None)
-        return eng.sample_ode_cfg_schedule(x, tgrid, table, method, t_round_to_state_dtype=t_round, return_trajectory=return_trajectory, **args)
+        if rule_is_off(rescale, norm_limit):  # the call it was before the rule existed
+            return eng.sample_ode_cfg_schedule(x, tgrid, table, method, t_round_to_state_dtype=t_round, return_trajectory=return_trajectory, **args)
+        return eng.sample_ode_cfg_rule(x, tgrid, table, method, rescale=rescale, norm_limit=norm_limit, t_round_to_state_dtype=t_round,
+                                       return_trajectory=return_trajectory, **args)
 
     _cond_names = ("cap_feats", "cap_mask")  # the conditioning arguments of forward / forward_with_cfg, in call order
 
     @torch.no_grad()
-    def sample_ode_cfg_schedule(self, z, tgrid, table, *cond, method: str = "midpoint", return_trajectory: bool = False, **step_kw):
+    def sample_ode_cfg_schedule(self, z, tgrid, table, *cond, method: str = "midpoint", return_trajectory: bool = False, rescale: float = 0.0,
+                                norm_limit: float = math.inf, **step_kw):
         """A guided fixed-grid trajectory with a scale per stage in ONE engine call (lt_sample_ode_cfg_schedule): stage k of interval
         i evaluates ``forward_with_cfg`` at ``table[i * stages + k]``, or - at scale 1 exactly - the plain forward of the cond rows alone, at
         half the rows.  ``cond``: the family's conditioning as ``forward_with_cfg`` takes it (``cap_feats, cap_mask`` or ``y``) for all
         ``z.size(0)`` rows; ``step_kw``: its other keyword arguments (``cfg_scale`` is ignored).  ``transport.guidance.cfg_table`` builds tables
-        for guidance intervals and schedules.  Returns the last state, or all ``len(tgrid)`` states."""
+        for guidance intervals and schedules.  ``rescale`` (a blend in [0, 1]) / ``norm_limit`` (> 0; inf: off): the guided stages multiply
+        their guided channels by the per-sample factor of ``transport.guidance.guided_rule`` (lt_sample_ode_cfg_rule); at the
+        defaults the call is the schedule call.  Returns the last state, or all ``len(tgrid)`` states."""
         if len(cond) > len(self._cond_names):
             raise TypeError(f"sample_ode_cfg_schedule takes the conditioning {self._cond_names}, got {len(cond)} positional arguments")
         kw = dict(zip(self._cond_names, cond), **step_kw)
+        self._mirror_attention_flags(kw)
+        return self._engine_sample_ode_cfg_schedule(z, tgrid, method, True, table, kw, return_trajectory=return_trajectory, rescale=rescale,
+                                                    norm_limit=norm_limit)
+
+    def _mirror_attention_flags(self, kw):
         if hasattr(self, "layers") and "proportional_attn" in kw and len(self.layers) and hasattr(self.layers[0], "attention"):
             for layer in self.layers:  # what forward_with_cfg leaves on the module (reference model.py:891-899)
                 layer.attention.base_seqlen = kw.get("base_seqlen") if kw["proportional_attn"] else None
                 layer.attention.proportional_attn = kw["proportional_attn"]
-        return self._engine_sample_ode_cfg_schedule(z, tgrid, method, True, table, kw, return_trajectory=return_trajectory)
+
+    @torch.no_grad()
+    def forward_with_cfg_rule(self, x, t, *cond, rescale: float = 0.0, norm_limit: float = math.inf, **step_kw):
+        """``forward_with_cfg(x, t, <conditioning>, cfg_scale, **step_kw)`` under a rescale blend and / or a norm limit in ONE engine call
+        (lt_forward_cfg_rule): ``transport.guidance.guided_rule`` on the model's output of all rows.  ``cond``: the conditioning,
+        then ``cfg_scale`` (or ``cfg_scale=`` by keyword).  At the defaults the call is ``forward_with_cfg``.  Tensor states only."""
+        from ..transport.guidance import rule_is_off
+        if not isinstance(x, torch.Tensor):
+            raise _lib.LuminaLibError("forward_with_cfg_rule: a packed batch (a list of latents) is not served under a guidance rule")
+        names = self._cond_names + ("cfg_scale",)
+        if len(cond) > len(names):
+            raise TypeError(f"forward_with_cfg_rule takes {names}, got {len(cond)} positional arguments")
+        kw = dict(zip(names, cond), **step_kw)
+        if rule_is_off(rescale, norm_limit):
+            return self.forward_with_cfg(x, t, **kw)
+        self._mirror_attention_flags(kw)
+        eng, args = self._engine_sampler_args(x, True, kw)
+        return eng.forward_cfg_rule(x, t, rescale=rescale, norm_limit=norm_limit, **args)
 
     def _engine_sample_ode_adaptive(self, x, tgrid, method, use_cfg, t_round, kw, *, rtol, atol, first_step=None, max_steps=2 ** 31 - 1):
         """kwargs of forward_with_cfg / forward -> lt_sample_ode_adaptive; returns (states [len(tgrid), *x.shape], stats dict)"""

@@ -171,10 +171,13 @@ def run(args, *, encode_fn=None, cap_feat_dim=None, decode_fn=None, model=None) 
         else:
             kw.update(scale_factor=1.0, scale_watershed=1.0)
         table = guidance_table(args, sample_fn.__self__.t)
-        if table is None:
+        rule = guidance_rule(args)
+        if table is None and not rule:
             latent = sample_fn(z, model.forward_with_cfg, **kw)[-1][:1]
-        else:  # a scale per stage; stages at scale 1 evaluate the cond row alone (transport/guidance.py)
+        elif not rule:  # a scale per stage; stages at scale 1 evaluate the cond row alone (transport/guidance.py)
             latent = sample_fn(z, model.forward_with_cfg, cfg_table=table, **kw)[-1][:1]
+        else:  # ... and the guided stages rescaled / norm-limited per sample (without a table: --cfg_scale at every stage)
+            latent = sample_fn(z, model.forward_with_cfg, cfg_table=table, **rule, **kw)[-1][:1]
         stem = os.path.join(out_dir, "images", f"{args.sampling_method}_{args.num_sampling_steps}_{idx}_{res.split(':')[-1]}")
         if decode_fn is not None:
             save_png(decode_fn(latent / factor)[0], stem + ".png")
@@ -202,6 +205,17 @@ def guidance_table(args, tgrid):
     return guidance.cfg_table(tgrid, args.sampling_method, args.cfg_scale, interval=interval, schedule=schedule)
 
 
+def guidance_rule(args) -> dict:
+    """``--cfg_rescale`` / ``--cfg_norm_limit`` as the sampler's keyword arguments; empty at the defaults: no rule, the call it was"""
+    rescale, limit = float(getattr(args, "cfg_rescale", 0.0)), getattr(args, "cfg_norm_limit", None)
+    limit = math.inf if limit is None else float(limit)
+    if rescale == 0.0 and limit == math.inf:
+        return {}
+    from .transport import guidance
+    rescale, limit = guidance.check_rule(rescale, limit)
+    return dict(cfg_rescale=rescale, cfg_norm_limit=limit)
+
+
 def build_parser() -> argparse.ArgumentParser:
     def none_or_str(v):
         return None if v == "None" else v
@@ -212,6 +226,10 @@ def build_parser() -> argparse.ArgumentParser:
                    help="guide only the stages with LO <= t < HI (t = 0 noise, 1 data); the others evaluate the prompt row alone")
     p.add_argument("--cfg_schedule", type=str, default="constant", choices=["constant", "linear", "cosine"],
                    help="how the scale moves from --cfg_scale at the first grid point to 1 at the last")
+    p.add_argument("--cfg_rescale", type=float, default=0.0, metavar="PHI",
+                   help="guidance rescale: blend PHI in [0, 1] of the guided output's std towards the prompt row's (0: off)")
+    p.add_argument("--cfg_norm_limit", type=float, default=None, metavar="R",
+                   help="cap the guided output's L2 norm per sample at R times the prompt row's (default: no limit)")
     p.add_argument("--num_sampling_steps", type=int, default=250)
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--ckpt", type=str, required=True)

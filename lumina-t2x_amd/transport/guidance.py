@@ -20,7 +20,11 @@ models that are not engine-backed and CPU states, and is what the engine call (`
 It restates the loop of ``fixed_grid_odeint`` - same stage times, same ``dt`` handling, same rounding points.  The engine evaluates the
 conditional rows with the step arguments of the guided evaluation; an engine-backed model's plain ``forward`` reads its RoPE arguments off
 the module instead (``NextDiT._plain_forward_args``), so the two agree where those select the same table - ``scale_factor`` 1, or the
-families whose factors persist on the module."""
+families whose factors persist on the module.
+
+Rescaled and norm-limited guidance multiplies the guided output of every stage whose scale is not 1 by one factor per sample:
+``guided_rule`` is the rule, ``sample_cfg_rule`` the loop around it - ``sample_cfg_schedule`` with another ``func`` - and
+``lt_sample_ode_cfg_rule`` / ``lt_forward_cfg_rule`` are held to them word for word."""
 from __future__ import annotations
 
 import math
@@ -147,6 +151,136 @@ def sample_cfg_schedule(model, z, tgrid, table, method="euler", *, cond=None, t_
         tvec = th.ones(B).to(device) * tt  # fp32 [B] (reference integrators.py:108)
         if scale != 1.0:
             return model.forward_with_cfg(y, tvec, **cond_kw, cfg_scale=scale, **kw)
+        o = model.forward(y[: B // 2], tvec[: B // 2], **half_kw)
+        return th.cat([o, o])
+
+    def f(tt, y):
+        return _call(func, tt, y) if t_round else func(tt, y)
+
+    # fixed_grid_odeint's loop (integrators.py), statement for statement
+    out = th.empty((len(t),) + tuple(z.shape), dtype=z.dtype, device=device)
+    out[0] = z
+    y = z
+    third, two_thirds = 1.0 / 3.0, 2.0 / 3.0
+    for j in range(len(t) - 1):
+        t0, t1 = t[j], t[j + 1]
+        dt = t1 - t0
+        k1 = f(t0, y)
+        if method == "euler":
+            dy = dt * k1
+        elif method == "midpoint":
+            half = 0.5 * dt
+            dy = dt * f(t0 + half, y + k1 * half)
+        else:
+            k2 = f(t0 + dt * third, y + dt * k1 * third)
+            k3 = f(t0 + dt * two_thirds, y + dt * (k2 - k1 * third))
+            k4 = f(t1, y + dt * (k1 - k2 + k3))
+            dy = (k1 + 3 * (k2 + k3) + k4) * dt * 0.125
+        y = y + dy
+        out[j + 1] = y
+    assert call[0] == (len(t) - 1) * stages
+    return out
+
+
+# ---- rescaled and norm-limited guidance ---------------------------------------------------------------------------------------
+def check_rule(rescale, norm_limit):
+    """``(rescale, norm_limit)`` as the fp32 values the engine reads, as Python floats; refuses a blend outside [0, 1] and a limit that is not
+    above 0 (``inf``: no limit)"""
+    rescale, norm_limit = float(rescale), float(norm_limit)
+    if not (math.isfinite(rescale) and 0.0 <= rescale <= 1.0):
+        raise ValueError(f"guidance rescale {rescale} is not a blend in [0, 1]")
+    if math.isnan(norm_limit) or not norm_limit > 0.0:
+        raise ValueError(f"guidance norm_limit {norm_limit} is not above 0 (inf switches the limit off)")
+    return float(th.tensor(rescale, dtype=th.float32)), float(th.tensor(norm_limit, dtype=th.float32))
+
+
+def rule_is_off(rescale, norm_limit):
+    """the defaults: no rescale, no limit - callers then make the call they made before the rule existed"""
+    return float(rescale) == 0.0 and float(norm_limit) == math.inf
+
+
+def rule_factor(Sc, Scc, Sg, Sgg, n, rescale, norm_limit):
+    """``(f, fr, fl)`` of one sample from its four float64 sums: float64 arithmetic operation by operation (Python floats: no fused
+    multiply-add), ``f`` rounded once to fp32"""
+    mc, mg = Sc / n, Sg / n
+    vc = Scc / n - mc * mc
+    vg = Sgg / n - mg * mg
+    ratio = math.sqrt(vc / vg) if (vg > 0.0 and vc >= 0.0) else 1.0
+    fr = rescale * ratio + (1.0 - rescale)
+    fl = 1.0
+    den = fr * math.sqrt(Sgg)
+    if norm_limit < math.inf and den > 0.0:
+        fl = min(1.0, norm_limit * math.sqrt(Scc) / den)
+    return float(th.tensor(fr * fl, dtype=th.float64).to(th.float32)), fr, fl
+
+
+def guided_rule(o, w, ch, rescale=0.0, norm_limit=math.inf, parts=None):
+    """The rule at scale ``w`` on a model output ``o [B, C, H, W]`` (cond rows, then uncond rows; taken as bf16, returned in its own dtype): ``(out, f)``.
+
+    ``g = u + w (c - u)`` on the first ``ch`` channels in bf16 tensor ops (every op rounds: the closing kernel's chain); per sample the float64
+    sums of ``c``, ``c^2``, ``g``, ``g^2``; ``f = fp32(fr * fl)`` with ``fr = rescale * sqrt(var c / var g) + (1 - rescale)`` and ``fl = min(1,
+    norm_limit * |c| / (fr * |g|))`` (``rule_factor``); ``gg = bf16(fp32(g) * f)``; the channels past ``ch`` pass through row by row.  ``fr``
+    is the single-factor form of the published ``phi * g * ratio + (1 - phi) * g``, and the limit acts on ``fr * |g|``, the norm before the
+    last rounding, so one reduction serves both.  ``rescale`` / ``norm_limit`` are taken as fp32 values.  ``f``: fp32 ``[B / 2]`` on ``o``'s
+    device.  ``parts`` (a list): receives ``(fr, fl)`` per sample."""
+    rescale, norm_limit = check_rule(rescale, norm_limit)
+    B = o.size(0)
+    if B % 2:
+        raise ValueError(f"guidance needs an even batch (cond + uncond rows), got {B}")
+    half = B // 2
+    ch = min(int(ch), o.size(1))
+    dtype = o.dtype
+    o = o.to(th.bfloat16)  # the model's output is bf16 (an engine-backed model hands an fp32 state the same values in fp32)
+    c, u = o[:half, :ch], o[half:, :ch]
+    g = u + w * (c - u)
+    n = float(ch * o.size(2) * o.size(3))
+    cd, gd = c.double().reshape(half, -1), g.double().reshape(half, -1)
+    sums = th.stack([cd.sum(1), (cd * cd).sum(1), gd.sum(1), (gd * gd).sum(1)], dim=1).tolist()
+    fs = []
+    for Sc, Scc, Sg, Sgg in sums:
+        f, fr, fl = rule_factor(Sc, Scc, Sg, Sgg, n, rescale, norm_limit)
+        fs.append(f)
+        if parts is not None:
+            parts.append((fr, fl))
+    f = th.tensor(fs, dtype=th.float32, device=o.device)
+    gg = (g.float() * f.view(-1, 1, 1, 1)).to(th.bfloat16)
+    out = th.cat([th.cat([gg, o[:half, ch:]], 1), th.cat([gg, o[half:, ch:]], 1)])
+    return out.to(dtype), f
+
+
+def sample_cfg_rule(model, z, tgrid, table, method="euler", *, rescale=0.0, norm_limit=math.inf, cond=None, t_round=True, factors=None, parts=None, **kw):
+    """``sample_cfg_schedule`` whose stages at a scale other than 1 run ``guided_rule`` on ``model.forward`` of all ``B`` rows (both halves of
+    the input are the first half, as ``forward_with_cfg`` makes them); a stage at scale 1 exactly is the conditional-only stage, without the
+    rule.  ``model.cfg_channels`` (default 3) names the guided channels.  ``factors`` (a list): receives the fp32 ``[B / 2]`` factors of every
+    guided stage, in evaluation order, ``parts`` (a list) their ``(fr, fl)`` per sample.  Stage times, table handling and the loop are ``sample_cfg_schedule``'s, statement for statement."""
+    stages = _check_method(method)
+    table = check_table(table, tgrid, method)
+    rescale, norm_limit = check_rule(rescale, norm_limit)
+    B = z.size(0)
+    if B % 2:
+        raise ValueError(f"guidance needs an even batch (cond + uncond rows), got {B}")
+    kw = dict(kw)
+    kw.pop("cfg_scale", None)  # the table is the scale
+    if cond is None:
+        cond = [k for k, v in kw.items() if isinstance(v, th.Tensor) and v.dim() >= 1 and v.shape[0] == B]
+    cond_kw = {k: kw.pop(k) for k in cond}
+    half_kw = {k: _cond_half(v, B) for k, v in cond_kw.items()}
+    ch = int(getattr(model, "cfg_channels", 3))
+    device = z.device
+    t = _grid32(tgrid).to(device)
+    w = table.tolist()
+    call = [0]
+
+    def func(tt, y):
+        scale = w[call[0]]
+        call[0] += 1
+        tvec = th.ones(B).to(device) * tt  # fp32 [B] (reference integrators.py:108)
+        if scale != 1.0:
+            o = model.forward(th.cat([y[: B // 2]] * 2), tvec, **cond_kw)
+            out, f = guided_rule(o, scale, ch, rescale, norm_limit, parts)
+            if factors is not None:
+                factors.append(f)
+            return out.to(y.dtype)
         o = model.forward(y[: B // 2], tvec[: B // 2], **half_kw)
         return th.cat([o, o])
 

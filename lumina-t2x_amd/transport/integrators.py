@@ -27,6 +27,8 @@ The SDE samplers (``class sde``: Euler-Maruyama / Heun, the reference's own code
 engine-backed and predicts a velocity (``lt_sample_sde``: one evaluation per stage, coefficients from ``sde_table``); otherwise through the
 model callable, step by step, as the reference does.
 """
+import math
+
 import torch as th
 
 FIXED_GRID_METHODS = ("euler", "midpoint", "rk4")           # also built inside the engine (lt_sample_ode): one C-ABI call per trajectory
@@ -311,22 +313,31 @@ class ode:
         self.max_num_steps = 2 ** 31 - 1
         self.stats = None         # adaptive methods: nfe / accepted / rejected / first_step / dt of the last sample() call
 
-    def _sample_cfg_schedule(self, x, model, table, model_kwargs):
+    def _sample_cfg_schedule(self, x, model, table, model_kwargs, rescale=0.0, norm_limit=math.inf):
         """a guidance schedule (transport/guidance.py): one engine call for an engine-backed forward_with_cfg, else the host loop"""
-        from .guidance import sample_cfg_schedule
+        from .guidance import cfg_table, rule_is_off, sample_cfg_rule, sample_cfg_schedule
         if isinstance(x, tuple) or not getattr(self.drift, "is_plain_velocity", False) or self.sampler_type not in FIXED_GRID_METHODS:
             raise NotImplementedError("guidance schedules are built for the fixed-grid methods on a tensor state with the plain velocity as drift")
+        rule_off = rule_is_off(rescale, norm_limit)
+        if table is None:  # a rule without a table: one scale for every stage
+            table = cfg_table(self.t, self.sampler_type, model_kwargs.get("cfg_scale", 1.0))
         target = _engine_target(model)
         if target is not None and target[1] and x.is_cuda and self.use_engine and hasattr(target[0], "_engine_sample_ode_cfg_schedule"):
-            return target[0]._engine_sample_ode_cfg_schedule(x, self.t, self.sampler_type, self.t_round_to_state_dtype, table, dict(model_kwargs))
+            if rule_off:  # the call it was before the rule existed
+                return target[0]._engine_sample_ode_cfg_schedule(x, self.t, self.sampler_type, self.t_round_to_state_dtype, table, dict(model_kwargs))
+            return target[0]._engine_sample_ode_cfg_schedule(x, self.t, self.sampler_type, self.t_round_to_state_dtype, table, dict(model_kwargs),
+                                                             rescale=rescale, norm_limit=norm_limit)
         owner = getattr(model, "__self__", None)
         if owner is None or getattr(model, "__name__", "") != "forward_with_cfg" or not hasattr(owner, "forward"):
             raise TypeError("cfg_table needs the bound forward_with_cfg of a model that also has forward (the conditional-only stages call it)")
-        return sample_cfg_schedule(owner, x, self.t, table, self.sampler_type, t_round=self.t_round_to_state_dtype, **model_kwargs)
+        if rule_off:
+            return sample_cfg_schedule(owner, x, self.t, table, self.sampler_type, t_round=self.t_round_to_state_dtype, **model_kwargs)
+        return sample_cfg_rule(owner, x, self.t, table, self.sampler_type, rescale=rescale, norm_limit=norm_limit,
+                               t_round=self.t_round_to_state_dtype, **model_kwargs)
 
-    def sample(self, x, model, cfg_table=None, **model_kwargs):
-        if cfg_table is not None:
-            return self._sample_cfg_schedule(x, model, cfg_table, model_kwargs)
+    def sample(self, x, model, cfg_table=None, cfg_rescale=0.0, cfg_norm_limit=math.inf, **model_kwargs):
+        if cfg_table is not None or not (float(cfg_rescale) == 0.0 and float(cfg_norm_limit) == math.inf):
+            return self._sample_cfg_schedule(x, model, cfg_table, model_kwargs, cfg_rescale, cfg_norm_limit)
         if isinstance(x, tuple):  # the likelihood ODE (reference integrators.py:105-115 with a tuple state)
             device = x[0].device
 

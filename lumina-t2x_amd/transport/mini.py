@@ -4,15 +4,19 @@ sample_img2img.py:146-216) uses instead of Sampler/ode, including the img2img ``
 a bound ``forward_with_cfg`` of one of our engine-backed models runs the whole trajectory in one ``lt_sample_ode`` call.
 ``sample(..., mask=, x1=, noise=)`` is the inpainting form (transport/masked.py; not in the reference): one ``lt_sample_ode_masked`` call
 for an engine-backed callable, the host loop ``sample_masked`` otherwise.  ``sample(..., cfg_table=)`` is a guidance schedule
-(transport/guidance.py; not in the reference either): one ``lt_sample_ode_cfg_schedule`` call, or the host loop ``sample_cfg_schedule``.
+(transport/guidance.py; not in the reference either): one ``lt_sample_ode_cfg_schedule`` call, or the host loop ``sample_cfg_schedule``;
+``cfg_rescale=`` / ``cfg_norm_limit=`` add the per-sample factor of ``guided_rule`` to the guided stages (``lt_sample_ode_cfg_rule`` /
+``sample_cfg_rule``; without ``cfg_table`` the table holds ``cfg_scale`` at every stage).
 
 Not mirrored: ``use_sd3=True`` (drives a diffusers SD3Transformer2DModel, not a Lumina model - out of scope)."""
 from __future__ import annotations
 
+import math
+
 import torch as th
 
 from .integrators import ADAPTIVE_METHODS, FIXED_GRID_METHODS, _engine_target, adaptive_odeint, fixed_grid_odeint
-from .guidance import sample_cfg_schedule
+from .guidance import cfg_table, rule_is_off, sample_cfg_rule, sample_cfg_schedule
 from .masked import expand_operands, sample_masked
 
 
@@ -51,26 +55,35 @@ class ODE:
                                                    dict(model_kwargs))
         return sample_masked(model, x, self.t, mask, x1, noise, self.sampler_type, **model_kwargs)
 
-    def _sample_cfg_schedule(self, x, model, table, model_kwargs):
+    def _sample_cfg_schedule(self, x, model, table, model_kwargs, rescale=0.0, norm_limit=math.inf):
         """a guidance schedule (transport/guidance.py): a scale per stage; one engine call when the callable is an engine-backed forward_with_cfg"""
         if self.sampler_type not in FIXED_GRID_METHODS:
             raise NotImplementedError(f"guidance schedules are built for the fixed-grid methods {', '.join(FIXED_GRID_METHODS)}, not "
                                       f"'{self.sampler_type}'")
+        rule_off = rule_is_off(rescale, norm_limit)
+        if table is None:  # a rule without a table: one scale for every stage
+            table = cfg_table(self.t, self.sampler_type, model_kwargs.get("cfg_scale", 1.0))
         target = _engine_target(model)
         if target is not None and target[1] and x.is_cuda and self.use_engine and hasattr(target[0], "_engine_sample_ode_cfg_schedule"):
-            return target[0]._engine_sample_ode_cfg_schedule(x, self.t, self.sampler_type, self.t_round_to_state_dtype, table, dict(model_kwargs))
+            if rule_off:  # the call it was before the rule existed
+                return target[0]._engine_sample_ode_cfg_schedule(x, self.t, self.sampler_type, self.t_round_to_state_dtype, table, dict(model_kwargs))
+            return target[0]._engine_sample_ode_cfg_schedule(x, self.t, self.sampler_type, self.t_round_to_state_dtype, table, dict(model_kwargs),
+                                                             rescale=rescale, norm_limit=norm_limit)
         owner = getattr(model, "__self__", None)
         if owner is None or getattr(model, "__name__", "") != "forward_with_cfg" or not hasattr(owner, "forward"):
             raise TypeError("cfg_table needs the bound forward_with_cfg of a model that also has forward (the conditional-only stages call it)")
-        return sample_cfg_schedule(owner, x, self.t, table, self.sampler_type, t_round=self.t_round_to_state_dtype, **model_kwargs)
+        if rule_off:
+            return sample_cfg_schedule(owner, x, self.t, table, self.sampler_type, t_round=self.t_round_to_state_dtype, **model_kwargs)
+        return sample_cfg_rule(owner, x, self.t, table, self.sampler_type, rescale=rescale, norm_limit=norm_limit,
+                               t_round=self.t_round_to_state_dtype, **model_kwargs)
 
-    def sample(self, x, model, mask=None, x1=None, noise=None, cfg_table=None, **model_kwargs):
+    def sample(self, x, model, mask=None, x1=None, noise=None, cfg_table=None, cfg_rescale=0.0, cfg_norm_limit=math.inf, **model_kwargs):
         if isinstance(x, tuple):
             raise NotImplementedError("tuple states are not part of the sampling path")
-        if cfg_table is not None:
+        if cfg_table is not None or not rule_is_off(cfg_rescale, cfg_norm_limit):
             if mask is not None or x1 is not None or noise is not None:
                 raise NotImplementedError("a guidance schedule and an inpainting mask are not served together")
-            return self._sample_cfg_schedule(x, model, cfg_table, model_kwargs)
+            return self._sample_cfg_schedule(x, model, cfg_table, model_kwargs, cfg_rescale, cfg_norm_limit)
         if mask is not None or x1 is not None or noise is not None:
             return self._sample_masked(x, model, mask, x1, noise, model_kwargs)
         target = _engine_target(model)
