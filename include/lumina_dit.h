@@ -55,6 +55,12 @@ extern "C" {
 #define LT_ODE_BOSH3 4
 #define LT_ODE_FEHLBERG2 5
 #define LT_ODE_ADAPTIVE_HEUN 6
+/* the linear multistep methods of lt_sample_ode_multistep.  That call takes no method code - its weight table is the method; the codes name
+ * the methods where another call refuses them (lt_sample_ode_masked and its packed form) */
+#define LT_ODE_AB2 32
+#define LT_ODE_AB3 33
+#define LT_ODE_ABM2 34
+#define LT_ODE_ABM3 35
 /* lt_op_rk_*: most slopes a chain runs over (dopri5: 7), and the bytes of device workspace a norm needs */
 #define LT_RK_MAX_SLOPES 7
 #define LT_RK_WS_BYTES 8192
@@ -370,6 +376,37 @@ int lt_sample_ode_cfg_rule(lt_engine* e, const void* z_dev, void* traj_dev, void
                            const lt_step_args* a, void* stream);
 int lt_forward_cfg_rule(lt_engine* e, const void* x_dev, const float* t_dev, void* out_dev, float rescale, float norm_limit, const lt_step_args* a,
                         void* stream);
+
+/* Linear multistep sampling (transport/multistep.py states the loop in torch ops and the engine is held to it bit for bit):
+ * Adams-Bashforth predictors of 2 or 3 slopes (ab2, ab3) and the same with an Adams-Moulton corrector that costs no evaluation (abm2, abm3).
+ * Exactly N = n_grid - 1 model evaluations, one per interval, none at the last grid point (lt_last_nfe).  With f_i = model(p_i, t_i):
+ *   p_0 = y_0 = z
+ *   y_i     = y_{i-1} + sum_j a_{i,j} f_{i-j}      where row i of the table has a corrector weight that is not 0, else y_i = p_i (any row,
+ *                                                   not only row 0: a table may switch the corrector off for single intervals)
+ *   p_{i+1} = y_i     + sum_j b_{i,j} f_{i-j}
+ * and the result is p_N.  traj_dev (may be null) receives n_grid states: z, then y_i for 0 < i < N, then p_N; final_dev (may be null) p_N.
+ * coef_host: N rows of 8 floats, a_{i,0..3} then b_{i,0..3}, j = 0 the newest slope; a sum runs over the entries of its half row up to the
+ * last one that is not 0, and a row may name at most min(i + 1, 4) slopes.  The engine computes no weight: the caller fills the table, with q
+ * the slopes kept (2 or 3) and L_j the Lagrange basis polynomials on the nodes named,
+ *   b_{i,j} = integral over [t_i, t_{i+1}] of L_j(t) dt,  nodes t_i, t_{i-1}, .., t_{i-m+1},  m  = min(q, i + 1)      (step 0 is Euler)
+ *   a_{i,j} = integral over [t_{i-1}, t_i] of L_j(t) dt,  nodes t_i, t_{i-1}, .., t_{i-m'},   m' = min(q, i), i >= 1  (i = 1: trapezoid rule)
+ * in float64, rounded once to fp32.  corrector: 1 the a halves are used, 0 they are ignored (plain Adams-Bashforth).
+ * Rounding, R = round to the state dtype (identity at fp32): acc = R(c_0 k_0); acc = R(acc + R(c_j k_j)); out = R(y + acc), no contraction;
+ * the stage time of evaluation i is tgrid[i], rounded to the state dtype under t_round_to_state_dtype as in lt_sample_ode.
+ * Guidance: use_cfg 0 the plain forward; 1 lt_forward_cfg at a->cfg_scale (cfg_host null) or at cfg_host[i] for evaluation i, N values, a
+ * scale of 1 exactly being the conditional-only evaluation of lt_sample_ode_cfg_schedule; rescale / norm_limit other than (0, +inf) put the
+ * rule of lt_sample_ode_cfg_rule on the guided evaluations (a null cfg_host then stands for a->cfg_scale at every evaluation).
+ * lt_sample_ode_multistep_packed: the same loop on the flat state of a packed batch (lt_sample_ode_packed's layout), without a table or rule.
+ * Refused by name with nothing written: a null argument; a stream under capture; n_grid < 2; a weight that is not finite or a row that names
+ * more slopes than exist; corrector not 0 or 1; a guidance table or a rule with use_cfg = 0; what lt_sample_ode refuses of the shape; and
+ * with a table or a rule what lt_sample_ode_cfg_rule refuses.  Inpainting with a multistep method is refused (lt_sample_ode_masked given
+ * LT_ODE_AB2 .. LT_ODE_ABM3): the blend makes the state discontinuous, so the history's slopes no longer belong to it. */
+int lt_sample_ode_multistep(lt_engine* e, const void* z_dev, void* traj_dev, void* final_dev, const float* tgrid_host, int32_t n_grid,
+                            const float* coef_host, int32_t corrector, const float* cfg_host, float rescale, float norm_limit, int32_t use_cfg,
+                            int32_t t_round_to_state_dtype, const lt_step_args* a, void* stream);
+int lt_sample_ode_multistep_packed(lt_engine* e, const void* z_flat_dev, const int32_t* hw_host, void* traj_flat_dev, void* final_flat_dev,
+                                   const float* tgrid_host, int32_t n_grid, const float* coef_host, int32_t corrector, int32_t use_cfg,
+                                   int32_t t_round_to_state_dtype, const lt_step_args* a, void* stream);
 
 /* number of model evaluations issued by the last lt_sample_ode / lt_sample_ode_packed / lt_sample_views / lt_sample_views_guided / lt_sample_sde / lt_sample_ode_adaptive call */
 int64_t lt_last_nfe(lt_engine* e);

@@ -247,6 +247,11 @@ int lt_op_ode_combine(int32_t mode, const void* y0, const void* k1, const void* 
 int lt_op_ode_combine_masked(int32_t mode, const void* y0, const void* k1, const void* k2, const void* k3, const void* k4, const void* mask,
                              const void* x1, const void* noise, void* out, int32_t dtype, float dt, float t, float one_minus_t, int64_t n,
                              void* stream);
+/* one step of lt_sample_ode_multistep on n words: y_out = R(y_prev + S(a, k)) (has_corr), p_out = R(y + S(b, k)) from the stored y (has_corr 0:
+ * y = y_prev, y_out is not written); k: host array of nslopes device pointers, newest slope first; a, b: 4 host floats each, a sum running up
+ * to the last weight that is not 0; S(c, k): acc = R(c_0 k_0), acc = R(acc + R(c_j k_j)).  dtype 0 f32, 1 bf16. */
+int lt_op_ode_multistep(const void* y_prev, const void* const* k, int32_t nslopes, const float* a, const float* b, int32_t has_corr, void* y_out,
+                        void* p_out, int64_t n, int32_t dtype, void* stream);
 int lt_op_rope_table(void* out, int32_t len, int32_t hd, int32_t step, float theta0, float lin0, float theta1, float lin1, int32_t lin_on_pos,
                      void* stream, void* out_t);
 int lt_op_linear_small_m_ext(const void* a, const void* w, const void* b, void* y, int32_t M, int32_t N, int32_t K, int32_t act_in, const void* t,

@@ -27,6 +27,8 @@ LT_ODE_EULER, LT_ODE_MIDPOINT, LT_ODE_RK4 = 0, 1, 2
 ODE_METHODS = {"euler": LT_ODE_EULER, "midpoint": LT_ODE_MIDPOINT, "rk4": LT_ODE_RK4}
 LT_ODE_DOPRI5, LT_ODE_BOSH3, LT_ODE_FEHLBERG2, LT_ODE_ADAPTIVE_HEUN = 3, 4, 5, 6
 ODE_ADAPTIVE_METHODS = {"dopri5": LT_ODE_DOPRI5, "bosh3": LT_ODE_BOSH3, "fehlberg2": LT_ODE_FEHLBERG2, "adaptive_heun": LT_ODE_ADAPTIVE_HEUN}
+LT_ODE_AB2, LT_ODE_AB3, LT_ODE_ABM2, LT_ODE_ABM3 = 32, 33, 34, 35  # named where a call refuses them; lt_sample_ode_multistep takes the weight table
+ODE_MULTISTEP_METHODS = {"ab2": LT_ODE_AB2, "ab3": LT_ODE_AB3, "abm2": LT_ODE_ABM2, "abm3": LT_ODE_ABM3}
 LT_RK_MAX_SLOPES, LT_RK_WS_BYTES = 7, 8192
 LT_SDE_EULER, LT_SDE_HEUN = 0, 1
 SDE_METHODS = {"Euler": LT_SDE_EULER, "Heun": LT_SDE_HEUN}
@@ -117,6 +119,10 @@ _SIGNATURES: Dict[str, tuple] = {
     "lt_sample_ode_cfg_schedule": (_i32, [_vp, _vp, _vp, _vp, C.POINTER(_f32), _i32, _i32, C.POINTER(_f32), _i32, C.POINTER(LtStepArgs), _vp]),
     "lt_sample_ode_cfg_rule": (_i32, [_vp, _vp, _vp, _vp, C.POINTER(_f32), _i32, _i32, C.POINTER(_f32), _f32, _f32, _i32, C.POINTER(LtStepArgs), _vp]),
     "lt_forward_cfg_rule": (_i32, [_vp, _vp, _vp, _vp, _f32, _f32, C.POINTER(LtStepArgs), _vp]),
+    "lt_sample_ode_multistep": (_i32, [_vp, _vp, _vp, _vp, C.POINTER(_f32), _i32, C.POINTER(_f32), _i32, C.POINTER(_f32), _f32, _f32, _i32, _i32,
+                                       C.POINTER(LtStepArgs), _vp]),
+    "lt_sample_ode_multistep_packed": (_i32, [_vp, _vp, C.POINTER(_i32), _vp, _vp, C.POINTER(_f32), _i32, C.POINTER(_f32), _i32, _i32, _i32,
+                                              C.POINTER(LtStepArgs), _vp]),
     "lt_last_nfe": (_i64, [_vp]),
     "lt_last_eval_rows": (_i64, [_vp]),
     "lt_graph_replays": (_i64, [_vp]),
@@ -189,6 +195,7 @@ _SIGNATURES: Dict[str, tuple] = {
     "lt_op_region_text_combine": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "lt_op_ode_combine": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _f32, _i64, _vp]),
     "lt_op_ode_combine_masked": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _f32, _f32, _f32, _i64, _vp]),
+    "lt_op_ode_multistep": (_i32, [_vp, C.POINTER(_vp), _i32, C.POINTER(_f32), C.POINTER(_f32), _i32, _vp, _vp, _i64, _i32, _vp]),
     "lt_op_rope_table": (_i32, [_vp, _i32, _i32, _i32, _f32, _f32, _f32, _f32, _i32, _vp, _vp]),
     "lt_op_linear_small_m_ext": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, C.c_uint32, C.c_uint32, _vp]),
     "lt_op_moe_route": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp]),

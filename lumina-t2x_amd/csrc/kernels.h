@@ -377,6 +377,13 @@ int launch_ode_combine(int mode, const void* y0, const void* k1, const void* k2,
 int launch_ode_combine_masked(int mode, const void* y0, const void* k1, const void* k2, const void* k3, const void* k4, const void* mask,
                               const void* x1, const void* noise, void* out, int dtype, float dt, float t, float one_minus_t, long long n,
                               hipStream_t stream);
+// linear multistep stepping (multistep.hip; rounding points there): y_out = R(y_prev + S(a, k)) with has_corr, p_out = R(y + S(b, k)); k: host
+// array of nslopes device pointers, newest first; a, b: 4 host weights each; state dtype 0 f32, 1 bf16
+// the entries of a half row of the weight table (4 floats) that a sum runs over: up to the last one that is not 0 - part of the ABI of
+// lt_sample_ode_multistep, and the one statement of it on this side (transport/multistep.py: used)
+int multistep_used(const float* c);
+int launch_ode_multistep(const void* y_prev, const void* const* k, int nslopes, const float* a, const float* b, int has_corr, void* y_out,
+                         void* p_out, long long n, int dtype, hipStream_t stream);
 // multi-view sampling (views.hip): view tables perm / iperm int32 [V][HW], vsign / isign float [V][C]; state dtype 0 f32, 1 bf16
 //   invert: iperm from perm; hits int32 [V * HW + 1] is zeroed, then counts the hits per target, last word = entries out of range or repeated
 //   gather: out [V, C, HW] = view_v(y [C, HW]); with f0 [V, C, HW]: R(view_v(y) + R(f0 * half_dt))

@@ -685,6 +685,10 @@ extern "C" int lt_op_ode_combine(int32_t mode, const void* y0, const void* k1, c
                                  int32_t dtype, float dt, int64_t n, void* stream) {
     return launch_ode_combine(mode, y0, k1, k2, k3, k4, out, dtype, dt, (long long)n, (hipStream_t)stream);
 }
+extern "C" int lt_op_ode_multistep(const void* y_prev, const void* const* k, int32_t nslopes, const float* a, const float* b, int32_t has_corr,
+                                   void* y_out, void* p_out, int64_t n, int32_t dtype, void* stream) {
+    return launch_ode_multistep(y_prev, k, nslopes, a, b, has_corr, y_out, p_out, (long long)n, dtype, (hipStream_t)stream);
+}
 extern "C" int lt_op_ode_combine_masked(int32_t mode, const void* y0, const void* k1, const void* k2, const void* k3, const void* k4,
                                         const void* mask, const void* x1, const void* noise, void* out, int32_t dtype, float dt, float t,
                                         float one_minus_t, int64_t n, void* stream) {

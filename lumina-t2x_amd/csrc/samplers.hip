@@ -4,6 +4,7 @@
 // host<->device sync inside it (the adaptive loop reads one error ratio per attempted step).  All
 // are written against one scaffold - check_step_shape, StageTimes (engine.h), Trajectory - and a new sampler is too: what a sampler
 // owns is its stage-time fill loop and its stepping body, where the reference's rounding points are.
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -203,6 +204,8 @@ extern "C" int lt_sample_ode_masked(lt_engine* e, const void* z_dev, const void*
     if (refuse_if_capturing((hipStream_t)stream, "lt_sample_ode_masked")) return 2;  // (the stage times travel through a host staging buffer that the next call rewrites)
     LtOptScope opt_scope(&e->opts);
     LT_REQUIRE(n_grid >= 2, "lt_sample_ode_masked: need at least 2 grid points");
+    LT_REQUIRE(!(method >= LT_ODE_AB2 && method <= LT_ODE_ABM3), "%s: masked sampling with a multistep method (ab2, ab3, abm2, abm3) is refused: the blend "
+               "makes the state discontinuous, so the history's slopes no longer belong to it", "lt_sample_ode_masked");
     LT_REQUIRE(method >= LT_ODE_EULER && method <= LT_ODE_RK4, "lt_sample_ode_masked: unknown method %d", method);
     if (check_step_shape(e, "lt_sample_ode_masked", a)) return 2;
     // (lt_sample_ode leaves this to the first evaluation, after z has been copied; here nothing is written)
@@ -221,6 +224,8 @@ extern "C" int lt_sample_ode_masked_packed(lt_engine* e, const void* z_flat_dev,
     if (refuse_if_capturing((hipStream_t)stream, "lt_sample_ode_masked_packed")) return 2;  // (the stage times travel through a host staging buffer that the next call rewrites)
     LtOptScope opt_scope(&e->opts);
     LT_REQUIRE(n_grid >= 2, "lt_sample_ode_masked_packed: need at least 2 grid points");
+    LT_REQUIRE(!(method >= LT_ODE_AB2 && method <= LT_ODE_ABM3), "%s: masked sampling with a multistep method (ab2, ab3, abm2, abm3) is refused: the blend "
+               "makes the state discontinuous, so the history's slopes no longer belong to it", "lt_sample_ode_masked_packed");
     LT_REQUIRE(method >= LT_ODE_EULER && method <= LT_ODE_RK4, "lt_sample_ode_masked_packed: unknown method %d", method);
     PackedCall pc{};
     if (int rc = packed_call_begin(e, "lt_sample_ode_masked_packed", hw_host, a, use_cfg, &pc, (hipStream_t)stream)) return rc;
@@ -249,6 +254,16 @@ int check_rule(const char* who, float rescale, float norm_limit) {
     return 0;
 }
 
+// what every call with a scale per evaluation checks behind the shape, before anything is written: the batch, the `intervals * stages` scales,
+// the rule's parameters (`rule` = { rescale, norm limit } or null) and the prepared conditioning
+int check_guided_table(const lt_engine* e, const char* who, const lt_step_args* a, const float* cfg_host, int intervals, int stages, const float* rule) {
+    LT_REQUIRE(a->batch % 2 == 0, "%s: guidance needs an even batch (cond + uncond rows), got %d", who, a->batch);
+    for (int i = 0; i < intervals * stages; ++i)
+        LT_REQUIRE(std::isfinite(cfg_host[i]), "%s: the scale of stage %d of interval %d is not finite", who, i % stages, i / stages);
+    if (rule && check_rule(who, rule[0], rule[1])) return 2;
+    return check_guided_halves(e, who, a);
+}
+
 // lt_sample_ode_cfg_schedule, and with `rule` = { rescale, norm limit } lt_sample_ode_cfg_rule
 int sample_cfg_table(lt_engine* e, const char* who, const void* z_dev, void* traj_dev, void* final_dev, const float* tgrid_host, int n_grid, int method,
                      const float* cfg_host, const float* rule, int t_round, const lt_step_args* a, hipStream_t s) {
@@ -258,12 +273,8 @@ int sample_cfg_table(lt_engine* e, const char* who, const void* z_dev, void* tra
     LT_REQUIRE(n_grid >= 2, "%s: need at least 2 grid points", who);
     LT_REQUIRE(method >= LT_ODE_EULER && method <= LT_ODE_RK4, "%s: unknown method %d", who, method);
     if (check_step_shape(e, who, a)) return 2;
-    LT_REQUIRE(a->batch % 2 == 0, "%s: guidance needs an even batch (cond + uncond rows), got %d", who, a->batch);
     const int stages = method == LT_ODE_EULER ? 1 : (method == LT_ODE_MIDPOINT ? 2 : 4);
-    for (int i = 0; i < (n_grid - 1) * stages; ++i)
-        LT_REQUIRE(std::isfinite(cfg_host[i]), "%s: the scale of stage %d of interval %d is not finite", who, i % stages, i / stages);
-    if (rule && check_rule(who, rule[0], rule[1])) return 2;
-    if (check_guided_halves(e, who, a)) return 2;
+    if (check_guided_table(e, who, a, cfg_host, n_grid - 1, stages, rule)) return 2;
     const long long n = (long long)a->batch * e->cfg.in_channels * a->latent_h * a->latent_w;
     const CfgSchedule cs{cfg_host, rule};
     return ode_fixed_grid(e, z_dev, traj_dev, final_dev, tgrid_host, n_grid, method, 1, t_round, a, s, n, nullptr, nullptr, &cs);
@@ -300,6 +311,125 @@ extern "C" int lt_forward_cfg_rule(lt_engine* e, const void* x_dev, const float*
     if (check_guided_halves(e, who, a)) return 2;
     if (launch_guidance_params_store(e->g_cfg, a->cfg_scale, rescale, norm_limit, (hipStream_t)stream)) return 1;
     return forward_graphed(e, x_dev, t_dev, out_dev, a, 1, (hipStream_t)stream, nullptr, e->g_cfg, false, true);
+}
+
+// ---- linear multistep sampling: one evaluation per interval, the earlier slopes reused (multistep.hip) -------------------------
+namespace {
+
+// what both multistep calls check of the grid and the weight table, before anything is written
+int check_multistep(const char* who, int n_grid, const float* coef_host, int corrector) {
+    LT_REQUIRE(n_grid >= 2, "%s: need at least 2 grid points", who);
+    LT_REQUIRE(corrector == 0 || corrector == 1, "%s: corrector %d is not 0 (Adams-Bashforth) or 1 (with the Adams-Moulton corrector)", who, corrector);
+    for (int i = 0; i + 1 < n_grid; ++i) {
+        const float* row = coef_host + (size_t)i * 8;
+        for (int j = 0; j < 8; ++j)
+            LT_REQUIRE(std::isfinite(row[j]), "%s: weight %c[%d] of interval %d is not finite", who, j < 4 ? 'a' : 'b', j % 4, i);
+        const int need = std::max(corrector ? multistep_used(row) : 0, multistep_used(row + 4));
+        LT_REQUIRE(need <= std::min(i + 1, 4), "%s: interval %d names %d slopes, %d evaluations have been made by then", who, i, need, i + 1);
+    }
+    return 0;
+}
+
+// The multistep loop on a state of n elements (elementwise, so a packed batch's flat state runs through it as it is).  Evaluation i runs at
+// tgrid[i] on the predicted state and overwrites ring slot i % 4 of e->kbuf, the slot of f_{i-4}.  Without a corrector the state ping-pongs
+// through e->ys like a fixed-grid step; with one, ys holds the corrected states y_i and e->ymid the predictor p_{i+1} the next evaluation
+// reads.  Guidance scales and rule parameters are committed behind the stage times exactly as ode_fixed_grid does (stages = 1).
+int ode_multistep(lt_engine* e, const void* z_dev, void* traj_dev, void* final_dev, const float* tgrid_host, int n_grid, const float* coef_host,
+                  int corrector, int use_cfg, int t_round, const lt_step_args* a, hipStream_t s, long long n, const PackedCall* pc,
+                  const CfgSchedule* cs = nullptr) {
+    const int B = a->batch;
+    const int ncalls = n_grid - 1;
+    const bool bf = a->io_dtype == LT_BF16;
+    const int nsent = ncalls * B + (cs ? ncalls : 0) + (cs && cs->rule ? 2 : 0);
+    float* tp = e->times.begin(nsent, s);
+    if (!tp) return 1;
+    for (int i = 0; i < ncalls; ++i) {
+        const float tv = (t_round && bf) ? bf16_round_host(tgrid_host[i]) : tgrid_host[i];
+        for (int b = 0; b < B; ++b) tp[(size_t)i * B + b] = tv;
+    }
+    if (cs) memcpy(tp + (size_t)ncalls * B, cs->table, (size_t)ncalls * sizeof(float));
+    if (cs && cs->rule) memcpy(tp + (size_t)ncalls * B + ncalls, cs->rule, 2 * sizeof(float));
+    if (e->times.commit(nsent, s)) return 1;
+    if (cs && cs->rule)
+        LT_CHECK_HIP(hipMemcpyAsync(e->g_cfg + 1, e->times.dev + (size_t)ncalls * B + ncalls, 2 * sizeof(float), hipMemcpyDeviceToDevice, s));
+    Trajectory tr{e, a, use_cfg, s, (size_t)n * (bf ? 2 : 4)};
+    tr.pc = pc;
+    if (cs) { tr.cfg_host = cs->table; tr.cfg_dev = e->times.dev + (size_t)ncalls * B; tr.cfg_rule = cs->rule != nullptr; }
+    if (tr.start(z_dev, traj_dev, true)) return 1;
+    const int dt_code = bf ? 1 : 0;
+    const void* p = tr.y0();  // p_i, the state evaluation i reads: p_0 = z
+    for (int i = 0; i < ncalls; ++i) {
+        const float* row = coef_host + (size_t)i * 8;
+        if (tr.eval(p, i, e->kbuf[i % 4])) return 1;
+        const int nslopes = std::max(1, std::max(corrector ? multistep_used(row) : 0, multistep_used(row + 4)));  // (<= min(i + 1, 4): check_multistep)
+        const void* k[4] = {nullptr, nullptr, nullptr, nullptr};
+        for (int j = 0; j < nslopes; ++j) k[j] = e->kbuf[(i - j) % 4];  // newest first
+        if (!corrector) {  // y_i = p_i; p_{i+1} is the next recorded state
+            if (launch_ode_multistep(tr.y0(), k, nslopes, nullptr, row + 4, 0, nullptr, tr.y1(), n, dt_code, s)) return 1;
+            if (tr.advance(i + 1)) return 1;
+            p = tr.y0();
+        } else if (multistep_used(row) == 0) {  // a row without corrector weights: y_i = p_i
+            if (i > 0) {  // p_i lies in ymid, ys[cur] holds y_{i-1}: p_i becomes the stored y_i, recorded in slot i (at step 0 ys[0] = z is both)
+                LT_CHECK_HIP(hipMemcpyAsync(tr.y1(), e->ymid, tr.sbytes, hipMemcpyDeviceToDevice, s));
+                if (tr.advance(i)) return 1;
+            }
+            if (launch_ode_multistep(tr.y0(), k, nslopes, nullptr, row + 4, 0, nullptr, e->ymid, n, dt_code, s)) return 1;
+            p = e->ymid;
+        } else {  // y_i from y_{i-1}, recorded in slot i; p_{i+1} from the stored y_i
+            if (launch_ode_multistep(tr.y0(), k, nslopes, row, row + 4, 1, tr.y1(), e->ymid, n, dt_code, s)) return 1;
+            if (tr.advance(i)) return 1;
+            p = e->ymid;
+        }
+    }
+    if (!corrector) return tr.finish(final_dev);
+    // the result p_N lies in ymid: the last slot of the record, and the final state
+    if (traj_dev) LT_CHECK_HIP(hipMemcpyAsync((char*)traj_dev + (size_t)ncalls * tr.sbytes, e->ymid, tr.sbytes, hipMemcpyDeviceToDevice, s));
+    if (final_dev) LT_CHECK_HIP(hipMemcpyAsync(final_dev, e->ymid, tr.sbytes, hipMemcpyDeviceToDevice, s));
+    return tr.finish(nullptr);
+}
+
+}  // namespace
+
+extern "C" int lt_sample_ode_multistep(lt_engine* e, const void* z_dev, void* traj_dev, void* final_dev, const float* tgrid_host, int32_t n_grid,
+                                       const float* coef_host, int32_t corrector, const float* cfg_host, float rescale, float norm_limit,
+                                       int32_t use_cfg, int32_t t_round, const lt_step_args* a, void* stream) {
+    const char* who = "lt_sample_ode_multistep";
+    LT_REQUIRE(e && z_dev && tgrid_host && coef_host && a, "%s: null argument", who);
+    if (check_multistep(who, n_grid, coef_host, corrector)) return 2;  // (the table and the flags first: host arguments, no engine state read)
+    const bool rule_on = !(rescale == 0.f && norm_limit == INFINITY);
+    LT_REQUIRE(use_cfg || !cfg_host, "%s: a guidance table with use_cfg = 0 (the table scales forward_with_cfg)", who);
+    LT_REQUIRE(use_cfg || !rule_on, "%s: a rescale / norm-limit rule with use_cfg = 0 (the rule acts on guided evaluations)", who);
+    if (refuse_if_capturing((hipStream_t)stream, who)) return 2;  // (the stage times travel through a host staging buffer that the next call rewrites)
+    LtOptScope opt_scope(&e->opts);
+    if (check_step_shape(e, who, a)) return 2;
+    const long long n = (long long)a->batch * e->cfg.in_channels * a->latent_h * a->latent_w;
+    if (!cfg_host && !rule_on)
+        return ode_multistep(e, z_dev, traj_dev, final_dev, tgrid_host, n_grid, coef_host, corrector, use_cfg, t_round, a, (hipStream_t)stream, n, nullptr);
+    // a scale per evaluation [and the rule]: the checks of sample_cfg_table
+    std::vector<float> constant;
+    if (!cfg_host) {  // the rule at one scale
+        constant.assign(n_grid - 1, a->cfg_scale);
+        cfg_host = constant.data();
+    }
+    const float rule[2] = {rescale, norm_limit};
+    if (check_guided_table(e, who, a, cfg_host, n_grid - 1, 1, rule_on ? rule : nullptr)) return 2;
+    const CfgSchedule cs{cfg_host, rule_on ? rule : nullptr};
+    return ode_multistep(e, z_dev, traj_dev, final_dev, tgrid_host, n_grid, coef_host, corrector, 1, t_round, a, (hipStream_t)stream, n, nullptr, &cs);
+}
+
+// lt_sample_ode_multistep on a packed batch: z, every trajectory slot and the final state are flat buffers of the size list's layout (packed.hip)
+extern "C" int lt_sample_ode_multistep_packed(lt_engine* e, const void* z_flat_dev, const int32_t* hw_host, void* traj_flat_dev, void* final_flat_dev,
+                                              const float* tgrid_host, int32_t n_grid, const float* coef_host, int32_t corrector, int32_t use_cfg,
+                                              int32_t t_round, const lt_step_args* a, void* stream) {
+    const char* who = "lt_sample_ode_multistep_packed";
+    LT_REQUIRE(e && z_flat_dev && hw_host && tgrid_host && coef_host && a, "%s: null argument", who);
+    if (check_multistep(who, n_grid, coef_host, corrector)) return 2;
+    if (refuse_if_capturing((hipStream_t)stream, who)) return 2;  // (the stage times travel through a host staging buffer that the next call rewrites)
+    LtOptScope opt_scope(&e->opts);
+    PackedCall pc{};
+    if (int rc = packed_call_begin(e, who, hw_host, a, use_cfg, &pc, (hipStream_t)stream)) return rc;
+    return ode_multistep(e, z_flat_dev, traj_flat_dev, final_flat_dev, tgrid_host, n_grid, coef_host, corrector, use_cfg, t_round, a, (hipStream_t)stream,
+                         pc.elems, &pc);
 }
 
 // ---- multi-view (visual-anagram) sampling ------------------------------------------------------------------------------------------

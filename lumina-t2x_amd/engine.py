@@ -362,6 +362,12 @@ class DiTEngine:
             ops.append(v.contiguous())
         return ops
 
+    @staticmethod
+    def _refuse_masked_multistep(method: str, what: str) -> None:
+        if method in _lib.ODE_MULTISTEP_METHODS:
+            from .transport.multistep import MASKED_REFUSAL
+            raise LuminaLibError(f"{what}: {MASKED_REFUSAL.format(method)}")
+
     def sample_ode_masked(self, z: torch.Tensor, tgrid, mask: torch.Tensor, x1: torch.Tensor, noise: torch.Tensor, method: str, *, use_cfg: bool,
                           cfg_scale: float = 1.0, scale_factor: float = 1.0, scale_watershed: float = 1.0, base_seqlen: Optional[int] = None,
                           proportional_attn: bool = False, t_round_to_state_dtype: bool = True, return_trajectory: bool = True,
@@ -369,6 +375,7 @@ class DiTEngine:
         """``sample_ode`` with the inpainting blend after every full step (lt_sample_ode_masked): ``mask`` (1 = generate, 0 = keep), the
         source latent ``x1`` and the ``noise`` the trajectory started from, all shaped and typed like ``z``"""
         _require_gpu(z, "z")
+        self._refuse_masked_multistep(method, "sample_ode_masked")
         if method not in _lib.ODE_METHODS:
             raise LuminaLibError(f"fixed-grid method '{method}' not in {sorted(_lib.ODE_METHODS)}")
         z = z.contiguous()
@@ -388,6 +395,7 @@ class DiTEngine:
                                  proportional_attn: bool = False, t_round_to_state_dtype: bool = True, return_trajectory: bool = True):
         """``sample_ode_packed`` with the inpainting blend (lt_sample_ode_masked_packed): ``masks``, ``x1s`` and ``noises`` are lists like
         ``zs``, sample b of each shaped like ``zs[b]``"""
+        self._refuse_masked_multistep(method, "sample_ode_masked_packed")
         if method not in _lib.ODE_METHODS:
             raise LuminaLibError(f"fixed-grid method '{method}' not in {sorted(_lib.ODE_METHODS)}")
         zs = list(zs)
@@ -494,6 +502,80 @@ class DiTEngine:
                                               rescale, norm_limit, C.byref(a), C.c_void_p(_stream_ptr(self.device)))
         _lib.check(rc, "lt_forward_cfg_rule")
         return out
+
+    # ---- linear multistep sampling: one evaluation per interval -------------
+    @staticmethod
+    def _multistep_table(tgrid, method: str, n: int, what: str, coef=None):
+        """the weight table of ``transport.multistep`` for this grid as the engine reads it, and whether the corrector halves are used;
+        ``coef``: the caller's own fp32 ``[n - 1, 8]`` table instead (``multistep_odeint(..., table=)`` is its host loop)"""
+        from .transport import multistep
+        if coef is not None:
+            tab = torch.as_tensor(coef).detach().to("cpu", torch.float32).contiguous()
+            if tuple(tab.shape) != (max(n - 1, 0), 8):
+                raise LuminaLibError(f"{what}: coef must be [{max(n - 1, 0)}, 8] (a_0..3, b_0..3 per interval), got {tuple(tab.shape)}")
+            if n < 2:
+                raise LuminaLibError(f"{what}: need at least 2 grid points")
+            return tab, int(bool((tab[:, :4] != 0).any()))
+        if method not in multistep.MULTISTEP_METHODS:
+            raise LuminaLibError(f"{what}: multistep method '{method}' not in {list(multistep.MULTISTEP_METHODS)}")
+        if n < 2:
+            raise LuminaLibError(f"{what}: need at least 2 grid points")
+        try:
+            tab = multistep.multistep_table(tgrid, method).contiguous()
+        except ValueError as exc:
+            raise LuminaLibError(f"{what}: {exc}") from None
+        return tab, int(multistep.is_corrector(method))
+
+    def sample_ode_multistep(self, z: torch.Tensor, tgrid, method: Optional[str], *, use_cfg: bool, cfg_scale: float = 1.0, table=None, coef=None,
+                             rescale: float = 0.0,
+                             norm_limit: float = math.inf, scale_factor: float = 1.0, scale_watershed: float = 1.0,
+                             base_seqlen: Optional[int] = None, proportional_attn: bool = False, t_round_to_state_dtype: bool = True,
+                             return_trajectory: bool = True, ntk_factor: float = 1.0) -> torch.Tensor:
+        """``ab2`` / ``ab3`` / ``abm2`` / ``abm3`` of ``transport.multistep`` in ONE call (lt_sample_ode_multistep): ``len(tgrid) - 1`` model
+        evaluations, the weights from ``multistep_table``.  ``table`` (optional): a guidance scale per evaluation, ``len(tgrid) - 1`` values,
+        as ``sample_ode_cfg_schedule`` takes one per stage; ``rescale`` / ``norm_limit``: the rule of ``sample_ode_cfg_rule`` on the guided
+        evaluations.  ``coef`` (optional): the caller's own weight table ``[len(tgrid) - 1, 8]`` in place of the method's - the table is
+        the contract (``method`` is then not read); a row whose corrector half is all 0 takes ``y_i = p_i``.  Returns all ``len(tgrid)``
+        recorded states or the last one."""
+        _require_gpu(z, "z")
+        z = z.contiguous()
+        garr, n = _grid_array(tgrid)
+        coef, corrector = self._multistep_table(tgrid, method, n, "sample_ode_multistep", coef)
+        rescale, norm_limit = self._rule(rescale, norm_limit, "sample_ode_multistep")
+        tab_ptr = None
+        if table is not None:
+            tab = table if isinstance(table, torch.Tensor) else torch.tensor(list(table), dtype=torch.float32)
+            tab = tab.detach().to("cpu", torch.float32).reshape(-1).contiguous()
+            if tab.numel() != n - 1:
+                raise LuminaLibError(f"sample_ode_multistep: the guidance table has {tab.numel()} entries, a {n}-point grid has {n - 1} evaluations")
+            tab_ptr = C.cast(tab.data_ptr(), C.POINTER(C.c_float))
+        a = self._step_args(z, cfg_scale, scale_factor, scale_watershed, base_seqlen, proportional_attn, ntk_factor=ntk_factor)
+        out, traj_ptr, fin_ptr = _traj_or_final(z, n, z.shape, return_trajectory)
+        with torch.cuda.device(self.device):
+            rc = self.lib.lt_sample_ode_multistep(self.handle, C.c_void_p(z.data_ptr()), traj_ptr, fin_ptr, garr, n,
+                                                  C.cast(coef.data_ptr(), C.POINTER(C.c_float)), corrector, tab_ptr, rescale, norm_limit, int(use_cfg),
+                                                  int(t_round_to_state_dtype), C.byref(a), C.c_void_p(_stream_ptr(self.device)))
+        _lib.check(rc, "lt_sample_ode_multistep")
+        return out
+
+    def sample_ode_multistep_packed(self, zs, tgrid, method: str, *, use_cfg: bool, cfg_scale: float = 1.0, scale_factor: float = 1.0,
+                                    scale_watershed: float = 1.0, base_seqlen: Optional[int] = None, proportional_attn: bool = False,
+                                    t_round_to_state_dtype: bool = True, return_trajectory: bool = True):
+        """``sample_ode_multistep`` on a LIST of differently sized latents (lt_sample_ode_multistep_packed), every evaluation the packed
+        forward_with_cfg (``use_cfg``) or the packed forward.  Returns one tensor per sample, all views of one allocation."""
+        flat, hw, spans = self._pack(zs, "sample_ode_multistep_packed")
+        garr, n = _grid_array(tgrid)
+        coef, corrector = self._multistep_table(tgrid, method, n, "sample_ode_multistep_packed")
+        a = self._packed_step_args(flat, len(spans), cfg_scale, scale_factor, scale_watershed, base_seqlen, proportional_attn)
+        out, traj_ptr, fin_ptr = _traj_or_final(flat, n, flat.shape, return_trajectory)
+        with torch.cuda.device(self.device):
+            rc = self.lib.lt_sample_ode_multistep_packed(self.handle, C.c_void_p(flat.data_ptr()), hw, traj_ptr, fin_ptr, garr, n,
+                                                         C.cast(coef.data_ptr(), C.POINTER(C.c_float)), corrector, int(use_cfg),
+                                                         int(t_round_to_state_dtype), C.byref(a), C.c_void_p(_stream_ptr(self.device)))
+        _lib.check(rc, "lt_sample_ode_multistep_packed")
+        if return_trajectory:
+            return [out[:, off:off + math.prod(shape)].view((n,) + shape) for off, shape in spans]
+        return [out[off:off + math.prod(shape)].view(shape) for off, shape in spans]
 
     def sample_ode_adaptive(self, z: torch.Tensor, tgrid: torch.Tensor, method: str, *, rtol: float, atol: float,
                             first_step: Optional[float] = None, max_steps: int = 2 ** 31 - 1, use_cfg: bool, cfg_scale: float = 1.0,

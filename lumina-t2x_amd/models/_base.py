@@ -84,6 +84,11 @@ class EngineSamplers:
         eng, args = self._engine_sampler_args(x, use_cfg, kw)
         return eng.sample_ode(x, tgrid, method, use_cfg=use_cfg, t_round_to_state_dtype=t_round, **args)
 
+    def _engine_sample_ode_multistep(self, x, tgrid, method, use_cfg, t_round, kw):
+        """kwargs of forward_with_cfg / forward -> lt_sample_ode_multistep (ab2 / ab3 / abm2 / abm3)"""
+        eng, args = self._engine_sampler_args(x, use_cfg, kw)
+        return eng.sample_ode_multistep(x, tgrid, method, use_cfg=use_cfg, t_round_to_state_dtype=t_round, **args)
+
     def _engine_sample_ode_masked(self, x, tgrid, method, use_cfg, t_round, mask, x1, noise, kw):
         """kwargs of forward_with_cfg / forward -> lt_sample_ode_masked (inpainting; mask / x1 / noise shaped and typed like x)"""
         eng, args = self._engine_sampler_args(x, use_cfg, kw)
@@ -96,6 +101,9 @@ class EngineSamplers:
         kw.setdefault("cfg_scale", 1.0)
         eng, args = self._engine_sampler_args(x, True, kw)
         args.pop("cfg_scale", None)
+        if method in _lib.ODE_MULTISTEP_METHODS:  # one evaluation per interval: the table has len(tgrid) - 1 entries
+            return eng.sample_ode_multistep(x, tgrid, method, use_cfg=True, table=table, rescale=rescale, norm_limit=norm_limit,
+                                            t_round_to_state_dtype=t_round, return_trajectory=return_trajectory, **args)
         if rule_is_off(rescale, norm_limit):  # the call it was before the rule existed
             return eng.sample_ode_cfg_schedule(x, tgrid, table, method, t_round_to_state_dtype=t_round, return_trajectory=return_trajectory, **args)
         return eng.sample_ode_cfg_rule(x, tgrid, table, method, rescale=rescale, norm_limit=norm_limit, t_round_to_state_dtype=t_round,
@@ -110,7 +118,8 @@ class EngineSamplers:
         i evaluates ``forward_with_cfg`` at ``table[i * stages + k]``, or - at scale 1 exactly - the plain forward of the cond rows alone, at
         half the rows.  ``cond``: the family's conditioning as ``forward_with_cfg`` takes it (``cap_feats, cap_mask`` or ``y``) for all
         ``z.size(0)`` rows; ``step_kw``: its other keyword arguments (``cfg_scale`` is ignored).  ``transport.guidance.cfg_table`` builds tables
-        for guidance intervals and schedules.  ``rescale`` (a blend in [0, 1]) / ``norm_limit`` (> 0; inf: off): the guided stages multiply
+        for guidance intervals and schedules.  ``method``: euler / midpoint / rk4, or a multistep method ab2 / ab3 / abm2 / abm3 (one evaluation
+        per interval, so a table of ``len(tgrid) - 1`` entries; lt_sample_ode_multistep).  ``rescale`` (a blend in [0, 1]) / ``norm_limit`` (> 0; inf: off): the guided stages multiply
         their guided channels by the per-sample factor of ``transport.guidance.guided_rule`` (lt_sample_ode_cfg_rule); at the
         defaults the call is the schedule call.  Returns the last state, or all ``len(tgrid)`` states."""
         if len(cond) > len(self._cond_names):

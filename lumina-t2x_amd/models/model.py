@@ -250,8 +250,13 @@ class NextDiT(EngineSamplers, WeightWatch, nn.Module):
     def sample_ode_packed(self, zs, tgrid, cap_feats, cap_mask, cfg_scale, method: str = "midpoint", return_trajectory: bool = False,
                           scale_factor=1.0, scale_watershed=1.0, base_seqlen: Optional[int] = None, proportional_attn: bool = False):
         """the fixed-grid ODE trajectory of a LIST of differently sized latents in ONE engine call, every evaluation
-        ``forward_with_cfg_packed``.  Returns one tensor per sample: the last state, or ``[len(tgrid), C, H_b, W_b]``."""
+        ``forward_with_cfg_packed``.  ``method``: euler / midpoint / rk4 (lt_sample_ode_packed) or a multistep method ab2 / ab3 / abm2 / abm3
+        (lt_sample_ode_multistep_packed).  Returns one tensor per sample: the last state, or ``[len(tgrid), C, H_b, W_b]``."""
         eng, zs = self._packed_cfg_engine(zs, cap_feats, cap_mask, base_seqlen, proportional_attn)
+        if method in _lib.ODE_MULTISTEP_METHODS:
+            return eng.sample_ode_multistep_packed(zs, tgrid, method, use_cfg=True, cfg_scale=cfg_scale, scale_factor=scale_factor,
+                                                   scale_watershed=scale_watershed, base_seqlen=base_seqlen, proportional_attn=proportional_attn,
+                                                   return_trajectory=return_trajectory)
         return eng.sample_ode_packed(zs, tgrid, method, use_cfg=True, cfg_scale=cfg_scale, scale_factor=scale_factor,
                                      scale_watershed=scale_watershed, base_seqlen=base_seqlen, proportional_attn=proportional_attn,
                                      return_trajectory=return_trajectory)

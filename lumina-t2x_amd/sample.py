@@ -253,7 +253,9 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument("--sample-eps", type=float)
     g.add_argument("--train-eps", type=float)
     g = p.add_argument_group("ODE arguments")
-    g.add_argument("--sampling-method", type=str, default="euler")
+    g.add_argument("--sampling-method", "--solver", type=str, default="euler",
+                   help="euler, midpoint, rk4, heun2, heun3, the adaptive dopri5 family, or a multistep method ab2 / ab3 / abm2 / abm3 (one model "
+                        "evaluation per step)")
     g.add_argument("--atol", type=float, default=1e-6)
     g.add_argument("--rtol", type=float, default=1e-3)
     g.add_argument("--reverse", action="store_true")

@@ -32,11 +32,14 @@ import math
 import torch as th
 
 from .integrators import FIXED_GRID_METHODS, _call
+from .multistep import MULTISTEP_METHODS
 
 _STAGES = {"euler": 1, "midpoint": 2, "rk4": 4}
 
 
-def _check_method(method):
+def _check_method(method, multistep=False):
+    if multistep and method in MULTISTEP_METHODS:  # one evaluation per interval, at t0 (transport/multistep.py)
+        return 1
     if method not in FIXED_GRID_METHODS:
         raise ValueError(f"guidance schedules are built for the fixed-grid methods {', '.join(FIXED_GRID_METHODS)}, not '{method}'")
     return _STAGES[method]
@@ -54,11 +57,11 @@ def stage_times(tgrid, method, state_dtype=th.float32, t_round=True):
     """The fp32 stage times ``[(len(tgrid) - 1) * stages]`` the engine hands the model, in evaluation order: ``t0``, for midpoint ``t0 + 0.5 dt``,
     for rk4 ``t0 + dt * fp32(1/3)``, ``t0 + dt * fp32(2/3)`` and ``t1`` - fp32 arithmetic on the fp32 grid, as ``fixed_grid_odeint`` forms them
     on 0-dim tensors.  With a bf16 state and ``t_round`` each is rounded to bf16 (torchdiffeq casts the time to the state dtype)."""
-    stages = _check_method(method)
+    stages = _check_method(method, multistep=True)
     t = _grid32(tgrid)
     t0, t1 = t[:-1], t[1:]
     dt = t1 - t0
-    if method == "euler":
+    if stages == 1:  # euler, and the multistep methods
         cols = [t0]
     elif method == "midpoint":
         cols = [t0, t0 + 0.5 * dt]
@@ -104,7 +107,7 @@ def cfg_table(tgrid, method, cfg_scale, interval=None, schedule=None):
 
 def check_table(table, tgrid, method):
     """``table`` as an fp32 CPU tensor of ``(len(tgrid) - 1) * stages`` finite entries"""
-    stages = _check_method(method)
+    stages = _check_method(method, multistep=True)
     n = len(_grid32(tgrid))
     t = table if isinstance(table, th.Tensor) else th.tensor(list(table), dtype=th.float32)
     t = t.detach().to("cpu", th.float32).reshape(-1).contiguous()
@@ -309,4 +312,50 @@ def sample_cfg_rule(model, z, tgrid, table, method="euler", *, rescale=0.0, norm
         y = y + dy
         out[j + 1] = y
     assert call[0] == (len(t) - 1) * stages
+    return out
+
+
+# ---- a scale per evaluation of a multistep method -------------------------------------------------------------------------------
+def sample_cfg_multistep(model, z, tgrid, table, method="abm2", *, rescale=0.0, norm_limit=math.inf, cond=None, t_round=True, factors=None,
+                         parts=None, **kw):
+    """``transport.multistep.multistep_odeint`` whose evaluation ``i`` is guided at ``table[i]`` (``len(tgrid) - 1`` entries): the evaluation of
+    ``sample_cfg_schedule`` at the defaults, of ``sample_cfg_rule`` under a rescale blend or a norm limit - ``guided_rule`` per guided
+    evaluation, the conditional rows alone at scale 1 exactly.  What ``lt_sample_ode_multistep`` with a table is held to, state for state."""
+    from .multistep import multistep_odeint
+    if method not in MULTISTEP_METHODS:
+        raise ValueError(f"unknown multistep method '{method}' (built: {', '.join(MULTISTEP_METHODS)})")
+    table = check_table(table, tgrid, method)
+    rule_off = rule_is_off(rescale, norm_limit)
+    rescale, norm_limit = check_rule(rescale, norm_limit)
+    B = z.size(0)
+    if B % 2:
+        raise ValueError(f"guidance needs an even batch (cond + uncond rows), got {B}")
+    kw = dict(kw)
+    kw.pop("cfg_scale", None)  # the table is the scale
+    if cond is None:
+        cond = [k for k, v in kw.items() if isinstance(v, th.Tensor) and v.dim() >= 1 and v.shape[0] == B]
+    cond_kw = {k: kw.pop(k) for k in cond}
+    half_kw = {k: _cond_half(v, B) for k, v in cond_kw.items()}
+    ch = int(getattr(model, "cfg_channels", 3))
+    device = z.device
+    w = table.tolist()
+    call = [0]
+
+    def func(tt, y):
+        scale = w[call[0]]
+        call[0] += 1
+        tvec = th.ones(B).to(device) * tt  # fp32 [B] (reference integrators.py:108)
+        if scale == 1.0:
+            o = model.forward(y[: B // 2], tvec[: B // 2], **half_kw)
+            return th.cat([o, o])
+        if rule_off:
+            return model.forward_with_cfg(y, tvec, **cond_kw, cfg_scale=scale, **kw)
+        o = model.forward(th.cat([y[: B // 2]] * 2), tvec, **cond_kw)
+        out, f = guided_rule(o, scale, ch, rescale, norm_limit, parts)
+        if factors is not None:
+            factors.append(f)
+        return out.to(y.dtype)
+
+    out = multistep_odeint(func, z, _grid32(tgrid), method, t_round=t_round)
+    assert call[0] == len(w)
     return out

@@ -21,7 +21,11 @@ not vendored).  Here:
 * the other tableau-defined methods ``--solver`` can name (the reference forwards ANY torchdiffeq method string,
   ``lumina_next_t2i/sample.py:77`` -> ``integrators.py:115``): fixed-grid ``heun2`` / ``heun3`` and adaptive ``bosh3`` /
   ``fehlberg2`` / ``adaptive_heun`` run on the same two host loops with their Butcher tableaus (restated from torchdiffeq 0.2.x,
-  unpinned like the rest).  ``dopri8``, the Adams multistep family and ``scipy_solver`` are NOT built and say so by name.
+  unpinned like the rest).  ``dopri8``, torchdiffeq's Adams family (``explicit_adams`` / ``implicit_adams`` / ``fixed_adams``) and ``scipy_solver`` are NOT built and say
+  so by name;
+* the linear multistep methods ``ab2`` / ``ab3`` / ``abm2`` / ``abm3`` (``transport/multistep.py``: variable-step Adams-Bashforth predictors, with
+  an Adams-Moulton corrector that costs no evaluation; ONE model evaluation per grid interval) are this project's own, not torchdiffeq's: one
+  ``lt_sample_ode_multistep`` call for an engine-backed callable, ``multistep_odeint`` otherwise or with ``use_engine = False``.
 
 The SDE samplers (``class sde``: Euler-Maruyama / Heun, the reference's own code) run inside the engine as well when the model callable is
 engine-backed and predicts a velocity (``lt_sample_sde``: one evaluation per stage, coefficients from ``sde_table``); otherwise through the
@@ -31,17 +35,21 @@ import math
 
 import torch as th
 
+from .multistep import MULTISTEP_METHODS, multistep_odeint  # ab2 / ab3 / abm2 / abm3: ours, not torchdiffeq's Adams family
+
 FIXED_GRID_METHODS = ("euler", "midpoint", "rk4")           # also built inside the engine (lt_sample_ode): one C-ABI call per trajectory
 HOST_FIXED_GRID_METHODS = ("heun2", "heun3")                  # fixed grid, host loop only
 ADAPTIVE_METHODS = ("dopri5", "bosh3", "fehlberg2", "adaptive_heun")  # also inside the engine (lt_sample_ode_adaptive)
 NOT_BUILT_METHODS = ("dopri8", "explicit_adams", "implicit_adams", "fixed_adams", "scipy_solver")
-ALL_METHODS = FIXED_GRID_METHODS + HOST_FIXED_GRID_METHODS + ADAPTIVE_METHODS
+ALL_METHODS = FIXED_GRID_METHODS + HOST_FIXED_GRID_METHODS + ADAPTIVE_METHODS  # the torchdiffeq names built here
+BUILT_METHODS = ALL_METHODS + MULTISTEP_METHODS  # ... and this project's own multistep methods (transport/multistep.py)
 
 
 def _unknown_method(method):
     if method in NOT_BUILT_METHODS:
-        return NotImplementedError(f"ODE method '{method}' of torchdiffeq is not built here (built: {', '.join(ALL_METHODS)})")
-    return ValueError(f"unknown ODE method '{method}' (torchdiffeq names built here: {', '.join(ALL_METHODS)})")
+        return NotImplementedError(f"ODE method '{method}' of torchdiffeq is not built here (built: {', '.join(BUILT_METHODS)})")
+    return ValueError(f"unknown ODE method '{method}' (torchdiffeq names built here: {', '.join(ALL_METHODS)}; multistep methods: "
+                      f"{', '.join(MULTISTEP_METHODS)})")
 
 
 def _call(func, t, y):
@@ -308,15 +316,16 @@ class ode:
         self.sampler_type = sampler_type
         # torchdiffeq >= 0.2 casts t to the state dtype inside its function wrapper; keep switchable
         self.t_round_to_state_dtype = True
-        self.use_engine = True    # adaptive methods: False keeps the host loop (adaptive_odeint) for an engine-backed callable too
+        self.use_engine = True    # adaptive and multistep methods: False keeps the host loop (adaptive_odeint) for an engine-backed callable too
         self.first_step = None    # adaptive methods: torchdiffeq's option of that name (None: the initial-step heuristic)
         self.max_num_steps = 2 ** 31 - 1
         self.stats = None         # adaptive methods: nfe / accepted / rejected / first_step / dt of the last sample() call
 
     def _sample_cfg_schedule(self, x, model, table, model_kwargs, rescale=0.0, norm_limit=math.inf):
         """a guidance schedule (transport/guidance.py): one engine call for an engine-backed forward_with_cfg, else the host loop"""
-        from .guidance import cfg_table, rule_is_off, sample_cfg_rule, sample_cfg_schedule
-        if isinstance(x, tuple) or not getattr(self.drift, "is_plain_velocity", False) or self.sampler_type not in FIXED_GRID_METHODS:
+        from .guidance import cfg_table, rule_is_off, sample_cfg_multistep, sample_cfg_rule, sample_cfg_schedule
+        if (isinstance(x, tuple) or not getattr(self.drift, "is_plain_velocity", False)
+                or self.sampler_type not in FIXED_GRID_METHODS + MULTISTEP_METHODS):
             raise NotImplementedError("guidance schedules are built for the fixed-grid methods on a tensor state with the plain velocity as drift")
         rule_off = rule_is_off(rescale, norm_limit)
         if table is None:  # a rule without a table: one scale for every stage
@@ -330,6 +339,9 @@ class ode:
         owner = getattr(model, "__self__", None)
         if owner is None or getattr(model, "__name__", "") != "forward_with_cfg" or not hasattr(owner, "forward"):
             raise TypeError("cfg_table needs the bound forward_with_cfg of a model that also has forward (the conditional-only stages call it)")
+        if self.sampler_type in MULTISTEP_METHODS:
+            return sample_cfg_multistep(owner, x, self.t, table, self.sampler_type, rescale=rescale, norm_limit=norm_limit,
+                                        t_round=self.t_round_to_state_dtype, **model_kwargs)
         if rule_off:
             return sample_cfg_schedule(owner, x, self.t, table, self.sampler_type, t_round=self.t_round_to_state_dtype, **model_kwargs)
         return sample_cfg_rule(owner, x, self.t, table, self.sampler_type, rescale=rescale, norm_limit=norm_limit,
@@ -344,8 +356,16 @@ class ode:
             def _fn_tuple(t, y):
                 return self.drift(y, th.ones(y[0].size(0)).to(device) * t, model, **model_kwargs)
 
+            if self.sampler_type in MULTISTEP_METHODS:
+                raise NotImplementedError(f"the multistep method '{self.sampler_type}' is built for tensor states (the likelihood ODE runs the "
+                                          "Runge-Kutta methods)")
             return tuple_odeint(_fn_tuple, x, self.t.to(device), method=self.sampler_type, rtol=self.rtol, atol=self.atol)
         target = _engine_target(model)
+        if (target is not None and getattr(self.drift, "is_plain_velocity", False) and x.is_cuda and self.use_engine
+                and x.dtype in (th.float32, th.bfloat16) and self.sampler_type in MULTISTEP_METHODS and len(self.t) >= 2
+                and hasattr(target[0], "_engine_sample_ode_multistep")):
+            owner, use_cfg = target
+            return owner._engine_sample_ode_multistep(x, self.t, self.sampler_type, use_cfg, self.t_round_to_state_dtype, dict(model_kwargs))
         if (target is not None and getattr(self.drift, "is_plain_velocity", False) and x.is_cuda
                 and self.sampler_type in FIXED_GRID_METHODS):
             return self._sample_on_engine(x, target, model_kwargs)
@@ -364,6 +384,8 @@ class ode:
             tvec = th.ones(y.size(0)).to(device) * t  # fp32 [B] (reference integrators.py:108)
             return self.drift(y, tvec, model, **model_kwargs)
 
+        if self.sampler_type in MULTISTEP_METHODS:
+            return multistep_odeint(_fn, x, self.t.to(device), self.sampler_type, t_round=self.t_round_to_state_dtype)
         if self.sampler_type in ADAPTIVE_METHODS:
             self.stats = {}
             return adaptive_odeint(_fn, x, self.t.to(device), method=self.sampler_type, rtol=self.rtol, atol=self.atol,

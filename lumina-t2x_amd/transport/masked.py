@@ -17,6 +17,7 @@ from __future__ import annotations
 import torch as th
 
 from .integrators import FIXED_GRID_METHODS, fixed_grid_odeint
+from .multistep import MASKED_REFUSAL, MULTISTEP_METHODS
 
 
 def known(noise, x1, t: float):
@@ -91,6 +92,8 @@ def sample_masked(model_fn, z, tgrid, mask, x1, noise, method="euler", *, batch=
     samplers evaluate it (``tvec`` an fp32 vector of ``batch`` entries, default ``z.size(0)``, holding the stage time rounded to the state
     dtype); each step is ``fixed_grid_odeint`` over one interval, then the blend at the interval's end.  ``mask``, ``x1`` and ``noise`` have the
     shape and dtype of ``z`` (``expand_operands``)."""
+    if method in MULTISTEP_METHODS:
+        raise NotImplementedError(MASKED_REFUSAL.format(method))
     if method not in FIXED_GRID_METHODS:
         raise ValueError(f"masked sampling is built for the fixed-grid methods {', '.join(FIXED_GRID_METHODS)}, not '{method}'")
     for name, v in (("mask", mask), ("x1", x1), ("noise", noise)):

@@ -6,7 +6,9 @@ a bound ``forward_with_cfg`` of one of our engine-backed models runs the whole t
 for an engine-backed callable, the host loop ``sample_masked`` otherwise.  ``sample(..., cfg_table=)`` is a guidance schedule
 (transport/guidance.py; not in the reference either): one ``lt_sample_ode_cfg_schedule`` call, or the host loop ``sample_cfg_schedule``;
 ``cfg_rescale=`` / ``cfg_norm_limit=`` add the per-sample factor of ``guided_rule`` to the guided stages (``lt_sample_ode_cfg_rule`` /
-``sample_cfg_rule``; without ``cfg_table`` the table holds ``cfg_scale`` at every stage).
+``sample_cfg_rule``; without ``cfg_table`` the table holds ``cfg_scale`` at every stage).  ``sampler_type`` ab2 / ab3 / abm2 / abm3
+(transport/multistep.py; not in the reference): one model evaluation per interval, one ``lt_sample_ode_multistep`` call or the host loop
+``multistep_odeint``; with an inpainting mask they are refused by name.
 
 Not mirrored: ``use_sd3=True`` (drives a diffusers SD3Transformer2DModel, not a Lumina model - out of scope)."""
 from __future__ import annotations
@@ -16,7 +18,8 @@ import math
 import torch as th
 
 from .integrators import ADAPTIVE_METHODS, FIXED_GRID_METHODS, _engine_target, adaptive_odeint, fixed_grid_odeint
-from .guidance import cfg_table, rule_is_off, sample_cfg_rule, sample_cfg_schedule
+from .guidance import cfg_table, rule_is_off, sample_cfg_multistep, sample_cfg_rule, sample_cfg_schedule
+from .multistep import MASKED_REFUSAL, MULTISTEP_METHODS, multistep_odeint
 from .masked import expand_operands, sample_masked
 
 
@@ -36,12 +39,14 @@ class ODE:
         self.use_sd3 = use_sd3
         self.sampler_type = sampler_type
         self.t_round_to_state_dtype = True  # torchdiffeq casts t to the state dtype (see integrators.ode)
-        self.use_engine = True  # masked sampling: False keeps the host loop (sample_masked) for an engine-backed callable too
+        self.use_engine = True  # masked and multistep sampling: False keeps the host loop (sample_masked) for an engine-backed callable too
 
     def _sample_masked(self, x, model, mask, x1, noise, model_kwargs):
         """inpainting (transport/masked.py): the blend after every full step; one engine call when the callable is engine-backed"""
         if mask is None or x1 is None or noise is None:
             raise ValueError("masked sampling needs mask, x1 and noise together")
+        if self.sampler_type in MULTISTEP_METHODS:
+            raise NotImplementedError(MASKED_REFUSAL.format(self.sampler_type))
         if self.sampler_type not in FIXED_GRID_METHODS:
             raise NotImplementedError(f"masked sampling is built for the fixed-grid methods {', '.join(FIXED_GRID_METHODS)}, not "
                                       f"'{self.sampler_type}'")
@@ -57,7 +62,7 @@ class ODE:
 
     def _sample_cfg_schedule(self, x, model, table, model_kwargs, rescale=0.0, norm_limit=math.inf):
         """a guidance schedule (transport/guidance.py): a scale per stage; one engine call when the callable is an engine-backed forward_with_cfg"""
-        if self.sampler_type not in FIXED_GRID_METHODS:
+        if self.sampler_type not in FIXED_GRID_METHODS + MULTISTEP_METHODS:
             raise NotImplementedError(f"guidance schedules are built for the fixed-grid methods {', '.join(FIXED_GRID_METHODS)}, not "
                                       f"'{self.sampler_type}'")
         rule_off = rule_is_off(rescale, norm_limit)
@@ -72,6 +77,9 @@ class ODE:
         owner = getattr(model, "__self__", None)
         if owner is None or getattr(model, "__name__", "") != "forward_with_cfg" or not hasattr(owner, "forward"):
             raise TypeError("cfg_table needs the bound forward_with_cfg of a model that also has forward (the conditional-only stages call it)")
+        if self.sampler_type in MULTISTEP_METHODS:
+            return sample_cfg_multistep(owner, x, self.t, table, self.sampler_type, rescale=rescale, norm_limit=norm_limit,
+                                        t_round=self.t_round_to_state_dtype, **model_kwargs)
         if rule_off:
             return sample_cfg_schedule(owner, x, self.t, table, self.sampler_type, t_round=self.t_round_to_state_dtype, **model_kwargs)
         return sample_cfg_rule(owner, x, self.t, table, self.sampler_type, rescale=rescale, norm_limit=norm_limit,
@@ -87,6 +95,10 @@ class ODE:
         if mask is not None or x1 is not None or noise is not None:
             return self._sample_masked(x, model, mask, x1, noise, model_kwargs)
         target = _engine_target(model)
+        if (target is not None and x.is_cuda and self.use_engine and self.sampler_type in MULTISTEP_METHODS and len(self.t) >= 2
+                and x.dtype in (th.float32, th.bfloat16) and hasattr(target[0], "_engine_sample_ode_multistep")):
+            owner, use_cfg = target
+            return owner._engine_sample_ode_multistep(x, self.t, self.sampler_type, use_cfg, self.t_round_to_state_dtype, dict(model_kwargs))
         if target is not None and x.is_cuda and self.sampler_type in FIXED_GRID_METHODS and len(self.t) >= 2:
             owner, use_cfg = target
             return owner._engine_sample_ode(x, self.t, self.sampler_type, use_cfg, self.t_round_to_state_dtype,
@@ -97,6 +109,8 @@ class ODE:
             tvec = th.ones(y.size(0)).to(device) * t  # transport.py:87
             return model(y, tvec, **model_kwargs)
 
+        if self.sampler_type in MULTISTEP_METHODS:
+            return multistep_odeint(_fn, x, self.t.to(device), self.sampler_type, t_round=self.t_round_to_state_dtype)
         if self.sampler_type in ADAPTIVE_METHODS:
             return adaptive_odeint(_fn, x, self.t.to(device), method=self.sampler_type)
         return fixed_grid_odeint(_fn, x, self.t.to(device), method=self.sampler_type)
