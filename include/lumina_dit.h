@@ -408,7 +408,39 @@ int lt_sample_ode_multistep_packed(lt_engine* e, const void* z_flat_dev, const i
                                    const float* tgrid_host, int32_t n_grid, const float* coef_host, int32_t corrector, int32_t use_cfg,
                                    int32_t t_round_to_state_dtype, const lt_step_args* a, void* stream);
 
-/* number of model evaluations issued by the last lt_sample_ode / lt_sample_ode_packed / lt_sample_views / lt_sample_views_guided / lt_sample_sde / lt_sample_ode_adaptive call */
+/* Guidance reuse (transport/guidance.py: sample_cfg_reuse is the definition): a guided trajectory that takes the difference
+ * d = cond - uncond on some evaluations (refresh) and reuses it on the others, which then evaluate the B' cond rows alone.  Per evaluation
+ * the caller gives the scale w (cfg_host, as in lt_sample_ode_cfg_schedule) and a flag (reuse_host, int32, 0 / 1).  ch = min(cfg_channels,
+ * in_channels), R = rounding to bf16, no contraction:
+ *   w == 1 exactly (either flag): the conditional-only stage of lt_sample_ode_cfg_schedule, bit for bit; d is neither read nor written.
+ *   w != 1, flag 0 (refresh): all 2 B' rows are evaluated; with c, u the bf16 final rows of a sample and its uncond partner d = R(c - u) and
+ *            the output on the channels < ch is R(u + R(w d)) - lt_forward_cfg at scale w word for word, both halves, all channels - and d
+ *            is stored in an engine-owned bf16 buffer [B', ch, H, W].
+ *   w != 1, flag 1 (reuse): the B' cond rows are evaluated as the conditional-only stage evaluates them; with c' their bf16 output the
+ *            channels < ch become R(R(c' - d) + R(w d)), w multiplying in fp32, the channels >= ch are the cond rows'; the result is written
+ *            to rows b and b + B'.  d is not modified.
+ * lt_sample_ode_cfg_reuse: lt_sample_ode_cfg_schedule's arguments, behaviour and refusals plus the flag table, one int32 per stage.  Stage
+ * times, dt, rounding points and trajectory slots are lt_sample_ode's; lt_last_nfe = (n_grid - 1) * stages; lt_last_eval_rows = 2 B' G +
+ * B' (R + C) for G refresh, R reuse and C conditional-only stages.  A trajectory replays at most three HIP-graph keys (refresh, reuse,
+ * conditional-only) whatever the tables hold.  The buffer (max_batch / 2 * in_channels * max_tokens * patch^2 bf16) is allocated by the first
+ * call that needs it, before anything is launched.
+ * lt_sample_ode_multistep_cfg_reuse: lt_sample_ode_multistep with a table and without a rule, plus one flag per evaluation.
+ * lt_forward_cfg_reuse: ONE evaluation at a->cfg_scale.  mode 0 is lt_forward_cfg and stores d (also at scale 1: a single call always guides);
+ * mode 1 evaluates the cond rows and reuses d.  x has 2 B' rows in both modes, both halves of out are written.  The engine remembers the
+ * stored d's signature (B', H, W, ch); every lt_prepare_prompt* / lt_prepare_labels call forgets it.  mode 1 without a stored d of this
+ * signature is refused by name.
+ * Not served: packed batches, regional prompts, views, inpainting, the rescale / norm-limit rule.  No synchronisation, no host read.
+ * Refused by name with nothing written: everything lt_sample_ode_cfg_schedule refuses; a null reuse_host; a flag other than 0 / 1; a reuse
+ * flag at a scale other than 1 with no refresh stage before it in the same call; a stream under capture; a mode other than 0 / 1. */
+int lt_sample_ode_cfg_reuse(lt_engine* e, const void* z_dev, void* traj_dev, void* final_dev, const float* tgrid_host, int32_t n_grid,
+                            int32_t method, const float* cfg_host, const int32_t* reuse_host, int32_t t_round_to_state_dtype,
+                            const lt_step_args* a, void* stream);
+int lt_sample_ode_multistep_cfg_reuse(lt_engine* e, const void* z_dev, void* traj_dev, void* final_dev, const float* tgrid_host, int32_t n_grid,
+                                      const float* coef_host, int32_t corrector, const float* cfg_host, const int32_t* reuse_host,
+                                      int32_t t_round_to_state_dtype, const lt_step_args* a, void* stream);
+int lt_forward_cfg_reuse(lt_engine* e, const void* x_dev, const float* t_dev, void* out_dev, int32_t mode, const lt_step_args* a, void* stream);
+
+/* number of model evaluations issued by the last lt_sample_ode /lt_sample_ode_packed / lt_sample_views / lt_sample_views_guided / lt_sample_sde / lt_sample_ode_adaptive call */
 int64_t lt_last_nfe(lt_engine* e);
 /* the rows those evaluations ran, summed: nfe * batch for every sampler but lt_sample_ode_cfg_schedule, whose conditional-only stages run half */
 int64_t lt_last_eval_rows(lt_engine* e);

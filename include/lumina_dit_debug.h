@@ -222,6 +222,14 @@ int lt_op_unpatchify_cfg_rule(const void* rows, int32_t ld, void* out, int32_t o
                               int32_t patch, int32_t use_cfg, const float* cfg_scale_dev, int32_t cfg_channels, int32_t wp_stride, int32_t dup,
                               const double* partials_dev, const float* rescale_dev, const float* norm_limit_dev, float* factor_out_dev,
                               void* stream);
+/* Guidance reuse (csrc/guidance_reuse.hip), for tests/test_gpu_cfg_reuse.py.  B counts the 2 B' rows of out; delta_dev: bf16
+ * [B', cfg_channels, H, W]; the scale is one float of device memory.  mode 0: lt_op_unpatchify_cfg_dev at use_cfg 1, dup 0 on the 2 B' rows,
+ * and delta = bf16(c - u) of the channels < cfg_channels is written.  mode 1: rows holds B' samples; the channels < cfg_channels become
+ * bf16(bf16(c' - delta) + bf16(scale * delta)), the others pass, sample b is written to rows b and b + B' of out; delta is only read.
+ * Refused: a null argument, an odd B, cfg_channels outside 1..C, a mode other than 0 / 1. */
+int lt_op_unpatchify_cfg_reuse(const void* rows, int32_t ld, void* out, int32_t out_dtype, int32_t B, int32_t C, int32_t out_ch, int32_t H, int32_t W,
+                               int32_t patch, const float* cfg_scale_dev, int32_t cfg_channels, int32_t wp_stride, void* delta_dev, int32_t mode,
+                               void* stream);
 /* The ragged boundary kernels of a packed batch (csrc/packed.hip): one launch for all samples.  hw_host = [B][2] latent sizes (host); the
  * flat state holds sample b = [C, H_b, W_b] at element offset sum_{j<b} C H_j W_j; N = token rows per sample in the row buffers (>= the longest
  * sequence).  Each launching entry builds the table of the size list, stores it at tab_dev (5 * 64 ints of device memory) and runs its kernel.

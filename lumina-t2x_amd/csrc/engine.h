@@ -220,6 +220,11 @@ struct lt_engine {
     // norm limit of a guidance rule (lt_sample_ode_cfg_rule / lt_forward_cfg_rule)
     float* g_cfg = nullptr;
     double* g_stats = nullptr;  // the rule's partial sums: max_batch / 2 samples x LT_GUIDANCE_SLICES x 4 (guidance_stats -> unpatchify_cfg_rule)
+    // guidance reuse: d = bfr(cond - uncond) of the last refresh evaluation, bf16 [B', ch, H, W]; max_batch / 2 x in_channels x
+    // max_tokens x patch^2 words, allocated by the first call that needs it (ensure_delta) and kept for the engine's life - captured graphs hold
+    // the pointer.  delta_sig: { B', H, W, ch } of what it holds, B' = 0: nothing; every lt_prepare_prompt* / lt_prepare_labels call zeroes it
+    u16* g_delta = nullptr;
+    int delta_sig[4] = {0, 0, 0, 0};
     hipStream_t cap_stream = nullptr;
     long long graph_replays = 0;
     // profiling
@@ -246,8 +251,16 @@ int packed_call_begin(lt_engine* e, const char* who, const int32_t* hw_host, con
 // for a->batch rows, and its output is written to both halves of `out` (a->batch rows).  rule (with cfg_dev): the guided evaluation scales
 // its guided channels by the per-sample factor of the rescale / norm-limit rule whose two parameters the caller has put behind the scale,
 // in e->g_cfg[1..2]; one more bit of the key, and no change to a conditional-only evaluation.  cfg_dev == e->g_cfg: the scale is in place
+// reuse (with cfg_dev, without cond_only and rule): LT_EVAL_STORE - the guided evaluation also stores the cond - uncond difference
+// of its guided channels in e->g_delta; LT_EVAL_REUSE - the first a->batch / 2 rows are evaluated as cond_only evaluates them and the closing
+// kernel guides them with the stored difference, both halves of `out` written.  One more word of the key.  The caller has run ensure_delta
+// and answers for the difference being there
+enum { LT_EVAL_PLAIN = 0, LT_EVAL_STORE = 1, LT_EVAL_REUSE = 2 };
 int forward_graphed(lt_engine* e, const void* x_in, const float* t_dev, void* out, const lt_step_args* a, int use_cfg, hipStream_t s,
-                    const PackedCall* pc = nullptr, const float* cfg_dev = nullptr, bool cond_only = false, bool rule = false);
+                    const PackedCall* pc = nullptr, const float* cfg_dev = nullptr, bool cond_only = false, bool rule = false,
+                    int reuse = LT_EVAL_PLAIN);
+// the difference buffer of guidance reuse: allocated on the first call, before anything is launched (engine.hip)
+int ensure_delta(lt_engine* e);
 // true while stream s records into a graph (the caller's torch.cuda.graph / hipStreamBeginCapture, or the engine's own cache)
 bool stream_capturing(hipStream_t s);
 // the entry points that allocate, synchronise or copy from host memory cannot be recorded into a caller's graph: non-zero after

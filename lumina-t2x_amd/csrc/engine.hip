@@ -406,7 +406,12 @@ int ensure_weight_layout(lt_engine* e, bool want, hipStream_t s, bool recording 
 // the conditional-only evaluation - a->batch rows on the first a->batch rows of a conditioning prepared for 2 a->batch, written twice;
 // rule (may be null): rule[0] the rescale blend, rule[1] the norm limit - a guided evaluation then runs guidance_stats and the
 // closing kernel that multiplies by the per-sample factor
-struct CfgFromDev { const float* scale; bool dup; const float* rule = nullptr; };
+// reuse: LT_EVAL_STORE - the guided evaluation's closing kernel also stores the difference; LT_EVAL_REUSE - a->batch rows on the
+// first half of the conditioning like dup, closed by the kernel that guides them with the stored difference
+struct CfgFromDev {
+    const float* scale; bool dup; const float* rule = nullptr; int reuse = LT_EVAL_PLAIN;
+    bool half() const { return dup || reuse == LT_EVAL_REUSE; }  // the evaluation has half the rows its output has
+};
 
 int run_forward(lt_engine* e, const void* x_in, const float* t_dev, void* out, const lt_step_args* a, int use_cfg,
                 hipStream_t s, const PackedDesc* pk = nullptr, const CfgFromDev* gs = nullptr) {
@@ -444,8 +449,8 @@ int run_forward(lt_engine* e, const void* x_in, const float* t_dev, void* out, c
     else LT_REQUIRE(Hp <= e->rope_len && Wp <= e->rope_len, "latent grid exceeds the RoPE table (%d)", e->rope_len);
     LT_REQUIRE(a->io_dtype == LT_BF16 || a->io_dtype == LT_F32, "io_dtype must be bf16 or f32");
     // (the conditioning buffers are batch-major: the first B rows of one prepared for 2 B are what a preparation of those rows alone leaves)
-    LT_REQUIRE(e->prompt_B == B || (gs && gs->dup && !pk && e->prompt_B == 2 * B), "%s was called for batch %d, step has batch %d",
-               v.labels ? "lt_prepare_labels" : "lt_prepare_prompt", e->prompt_B, gs && gs->dup ? 2 * B : B);
+    LT_REQUIRE(e->prompt_B == B || (gs && gs->half() && !pk && e->prompt_B == 2 * B), "%s was called for batch %d, step has batch %d",
+               v.labels ? "lt_prepare_labels" : "lt_prepare_prompt", e->prompt_B, gs && gs->half() ? 2 * B : B);
     LT_REQUIRE(e->reg_Y == 0 || (B == 2 && !pk), "regional captions: one image per call (batch 2 = cond + uncond row), tensor input");
     if (!e->weights_ok && lt_weights_ready(e)) return 2;
     const int d = e->d, L = e->L, H = e->H, Hkv = e->Hkv, hd = e->hd, F = e->F, dkv = e->dkv, A = e->A;
@@ -804,6 +809,11 @@ int run_forward(lt_engine* e, const void* x_in, const float* t_dev, void* out, c
             if (launch_guidance_stats(e->frows, e->nfinal, B, c.out_channels, a->latent_h, a->latent_w, p, gs->scale, rule_ch, Wrow, e->g_stats, s)) return 1;
             if (launch_unpatchify_cfg_rule(e->frows, e->nfinal, out, a->io_dtype, B, c.in_channels, c.out_channels, a->latent_h, a->latent_w, p,
                                            use_cfg, gs->scale, rule_ch, Wrow, 0, e->g_stats, gs->rule, gs->rule + 1, nullptr, s)) return 1;
+        } else if (!pk && gs && gs->reuse != LT_EVAL_PLAIN) {  // (B: the rows evaluated - 2 B' storing, B' reusing; the kernel counts output rows)
+            const bool again = gs->reuse == LT_EVAL_REUSE;
+            if (launch_unpatchify_cfg_reuse(e->frows, e->nfinal, out, a->io_dtype, again ? 2 * B : B, c.in_channels, c.out_channels, a->latent_h,
+                                            a->latent_w, p, gs->scale, cfg_ch < c.in_channels ? cfg_ch : c.in_channels, Wrow, e->g_delta,
+                                            again ? 1 : 0, s)) return 1;
         } else if (!pk && gs) {
             if (launch_unpatchify_cfg_dev(e->frows, e->nfinal, out, a->io_dtype, gs->dup ? 2 * B : B, c.in_channels, c.out_channels, a->latent_h,
                                           a->latent_w, p, use_cfg, gs->scale, cfg_ch, Wrow, gs->dup ? 1 : 0, s)) return 1;
@@ -854,6 +864,17 @@ int refuse_if_capturing(hipStream_t s, const char* who) {
     return 0;
 }
 
+int ensure_delta(lt_engine* e) {
+    if (e->g_delta) return 0;
+    const lt_config& c = e->cfg;
+    const size_t words = (size_t)(c.max_batch / 2) * c.in_channels * c.max_tokens * c.patch_size * c.patch_size;
+    LT_REQUIRE(words > 0, "guidance reuse: an engine of max_batch %d holds no cond + uncond pair", c.max_batch);
+    void* q = nullptr;
+    if (dev_alloc(e, &q, words * sizeof(u16), false)) return 1;  // (never read before a refresh evaluation wrote it: delta_sig)
+    e->g_delta = (u16*)q;
+    return 0;
+}
+
 int refuse_profile_if_capturing(const lt_engine* e, hipStream_t s, const char* who) {
     if (!(e->prof_on && e->prof_mask)) return 0;
     LT_REQUIRE(!stream_capturing(s), "%s: refused on a stream under capture while lt_profile_enable is on (the profile brackets launches with "
@@ -885,20 +906,24 @@ int softmax_scale_for(const lt_engine* e, const lt_step_args* a, int N, float* s
 }
 
 int forward_graphed(lt_engine* e, const void* x_in, const float* t_dev, void* out, const lt_step_args* a, int use_cfg, hipStream_t s,
-                    const PackedCall* pc, const float* cfg_dev, bool cond_only, bool rule) {
+                    const PackedCall* pc, const float* cfg_dev, bool cond_only, bool rule, int reuse) {
     // a stage of the guidance schedule: the scale travels through e->g_cfg - on the eager path too, so both run one kernel - and the key
     // holds a zeroed cfg_scale; the conditional-only evaluation has a->batch / 2 rows
     lt_step_args own;
-    const CfgFromDev cfd{e->g_cfg, cond_only, rule && !cond_only ? e->g_cfg + 1 : nullptr};
+    const CfgFromDev cfd{e->g_cfg, cond_only, rule && !cond_only ? e->g_cfg + 1 : nullptr, reuse};
     const CfgFromDev* cd = nullptr;
+    const bool half = cfd.half();  // B' rows evaluated, 2 B' written
+    if (reuse != LT_EVAL_PLAIN)
+        LT_REQUIRE(cfg_dev && !cond_only && !rule && e->g_delta, "guidance reuse: an evaluation that stores or reuses the difference reads its scale "
+                   "from device memory, runs without a rule, and finds the buffer allocated");
     if (cfg_dev) {
         LT_REQUIRE(!pc && a->batch % 2 == 0, "a guidance schedule needs a tensor state with an even batch");
         own = *a;
         own.cfg_scale = 0.f;
-        if (cond_only) own.batch = a->batch / 2;
-        else if (cfg_dev != e->g_cfg) LT_CHECK_HIP(hipMemcpyAsync(e->g_cfg, cfg_dev, sizeof(float), hipMemcpyDeviceToDevice, s));
+        if (half) own.batch = a->batch / 2;
+        if (!cond_only && cfg_dev != e->g_cfg) LT_CHECK_HIP(hipMemcpyAsync(e->g_cfg, cfg_dev, sizeof(float), hipMemcpyDeviceToDevice, s));
         a = &own;
-        use_cfg = cond_only ? 0 : 1;
+        use_cfg = half ? 0 : 1;
         cd = &cfd;
     }
     // one evaluation as plain launches; a packed batch's flat state goes through the ragged kernels
@@ -922,7 +947,7 @@ int forward_graphed(lt_engine* e, const void* x_in, const float* t_dev, void* ou
         return run(x_in, t_dev, out, s);  // let the eager path produce the error message
     const size_t sbytes = (pc ? (size_t)pc->elems : (size_t)B * e->cfg.in_channels * a->latent_h * a->latent_w) * (a->io_dtype == LT_BF16 ? 2 : 4);
     const size_t cap_bytes = (size_t)e->cfg.max_batch * e->cfg.in_channels * e->cfg.max_tokens * e->cfg.patch_size * e->cfg.patch_size * 4;
-    if ((cond_only ? 2 * sbytes : sbytes) > cap_bytes) return run(x_in, t_dev, out, s);
+    if ((half ? 2 * sbytes : sbytes) > cap_bytes) return run(x_in, t_dev, out, s);
     // a caller that is capturing ITS stream (torch.cuda.graph around the sampler) cannot launch a graph or start a second capture
     // from inside: hand it plain launches, which its own capture records.  The cache is not touched: a key first seen here would be pinned to
     // the row-major regime of a recorded evaluation (ge->pair) for callers that never capture
@@ -931,8 +956,9 @@ int forward_graphed(lt_engine* e, const void* x_in, const float* t_dev, void* ou
     // ... and the softmax rule: the scale it selects is a kernel argument (qa.out_scale / at.scale)
     // ... and whether the scale comes from device memory / the evaluation is the conditional-only one / the guided one under a rescale or
     // norm-limit rule: other closing kernels (the rule's parameters are read from device memory, like the scale)
-    const int extra[13] = {use_cfg, e->prompt_B, e->prompt_T, e->prompt_Tpad, e->reg_Y, e->reg_h, e->reg_w, lt_opt_generation(), lt_opt_engine_generation(),
-                           e->softmax_rule, cd ? 1 : 0, cond_only ? 1 : 0, cd && cd->rule ? 1 : 0};
+    // ... and whether the evaluation stores or reuses the cond - uncond difference: the third closing kernel, in its two modes
+    const int extra[14] = {use_cfg, e->prompt_B, e->prompt_T, e->prompt_Tpad, e->reg_Y, e->reg_h, e->reg_w, lt_opt_generation(), lt_opt_engine_generation(),
+                           e->softmax_rule, cd ? 1 : 0, cond_only ? 1 : 0, cd && cd->rule ? 1 : 0, reuse};
     std::vector<char> key(sizeof(lt_step_args) + sizeof(extra));
     memcpy(key.data(), a, sizeof(lt_step_args));
     memcpy(key.data() + sizeof(lt_step_args), extra, sizeof(extra));
@@ -989,7 +1015,7 @@ int forward_graphed(lt_engine* e, const void* x_in, const float* t_dev, void* ou
     LT_CHECK_HIP(hipMemcpyAsync(e->g_t, t_dev, (size_t)B * sizeof(float), hipMemcpyDeviceToDevice, s));
     LT_CHECK_HIP(hipGraphLaunch(ge->exec, s));
     e->last_pair = ge->pair;  // (a replay is an evaluation too: "last_pair" of lt_engine_get_option names the regime of the last one)
-    LT_CHECK_HIP(hipMemcpyAsync(out, e->g_out, cond_only ? 2 * sbytes : sbytes, hipMemcpyDeviceToDevice, s));
+    LT_CHECK_HIP(hipMemcpyAsync(out, e->g_out, half ? 2 * sbytes : sbytes, hipMemcpyDeviceToDevice, s));
     ++e->graph_replays;
     if (e->prof_on)
         for (int k = 0; k < 3; ++k)
@@ -1293,6 +1319,7 @@ static int prepare_caption_kv(lt_engine* e, int Bc, int T, int Tpad, hipStream_t
 extern "C" int lt_prepare_prompt(lt_engine* e, const void* cap_feats_dev, int32_t cap_dtype, const int32_t* cap_mask_dev,
                                  int32_t B, int32_t T, void* stream) {
     LT_REQUIRE(e && cap_feats_dev && cap_mask_dev, "lt_prepare_prompt: null argument");
+    e->delta_sig[0] = 0;  // (guidance reuse: a stored difference belongs to the conditioning it was taken on)
     LtOptScope opt_scope(&e->opts);
     LT_REQUIRE(e->v.text, "lt_prepare_prompt: this variant is class-conditional (use lt_prepare_labels)");
     hipStream_t s = (hipStream_t)stream;
@@ -1319,6 +1346,7 @@ extern "C" int lt_prepare_prompt_regional(lt_engine* e, const void* cap_feats_de
                                           int32_t Y, int32_t T, const void* global_feats_dev, const int32_t* global_mask_dev,
                                           int32_t Tg, int32_t h_split, int32_t w_split, void* stream) {
     LT_REQUIRE(e && cap_feats_dev && cap_mask_dev && global_feats_dev && global_mask_dev, "lt_prepare_prompt_regional: null argument");
+    e->delta_sig[0] = 0;  // (guidance reuse: a stored difference belongs to the conditioning it was taken on)
     if (refuse_if_capturing((hipStream_t)stream, "lt_prepare_prompt_regional")) return 2;  // (allocates, uploads a host table, synchronises)
     LtOptScope opt_scope(&e->opts);
     LT_REQUIRE(e->cfg.variant == LT_VARIANT_NEXT_T2I, "lt_prepare_prompt_regional: text-conditional Next-DiT only");
@@ -1363,6 +1391,7 @@ extern "C" int lt_prepare_prompt_regional(lt_engine* e, const void* cap_feats_de
 
 extern "C" int lt_prepare_labels(lt_engine* e, const int32_t* labels_dev, int32_t B, void* stream) {
     LT_REQUIRE(e && labels_dev, "lt_prepare_labels: null argument");
+    e->delta_sig[0] = 0;  // (guidance reuse: a stored difference belongs to the conditioning it was taken on)
     LtOptScope opt_scope(&e->opts);
     LT_REQUIRE(e->v.labels, "lt_prepare_labels: this variant is text-conditional (use lt_prepare_prompt)");
     LT_REQUIRE(B >= 1 && B <= e->cfg.max_batch, "label batch %d exceeds max_batch %d", B, e->cfg.max_batch);

@@ -369,6 +369,12 @@ int launch_unpatchify_cfg_rule(const u16* rows, int ld, void* out, int out_dtype
                                const float* cfg_scale_dev, int cfg_channels, int wp_stride, int dup, const double* partials,
                                const float* rescale_dev, const float* limit_dev, float* factor_out, hipStream_t stream);
 int launch_guidance_params_store(float* dst, float scale, float rescale, float limit, hipStream_t stream);
+// guidance reuse (guidance_reuse.hip).  B counts the 2 B' OUTPUT rows; delta: bf16 [B', cfg_channels, H, W]; the scale is read
+// from device memory.  mode 0: launch_unpatchify_cfg_dev at use_cfg = 1, dup = 0 on 2 B' rows, and d = bfr(cond - uncond) of the guided
+// channels is stored; mode 1: `rows` holds the B' cond rows, the guided channels become bfr(bfr(c' - d) + bfr(w d)) with the stored d (not
+// modified), the others pass, and each row is written to rows b and b + B' of the output
+int launch_unpatchify_cfg_reuse(const u16* rows, int ld, void* out, int out_dtype, int B, int C, int out_ch, int H, int W, int patch,
+                                const float* cfg_scale_dev, int cfg_channels, int wp_stride, u16* delta, int mode, hipStream_t stream);
 // torchdiffeq fixed-grid state arithmetic (modes documented in misc.hip)
 int launch_ode_combine(int mode, const void* y0, const void* k1, const void* k2, const void* k3, const void* k4,
                        void* out, int dtype, float dt, long long n, hipStream_t stream);

@@ -41,6 +41,8 @@ struct Trajectory {
     // a guidance schedule (lt_sample_ode_cfg_schedule): the scale of evaluation number `call`, on the host and where commit sent it
     const float *cfg_host = nullptr, *cfg_dev = nullptr;
     bool cfg_rule = false;  // ... under a rescale / norm-limit rule (lt_sample_ode_cfg_rule): its parameters are in e->g_cfg[1..2]
+    // guidance reuse (lt_sample_ode_cfg_reuse): the flag of evaluation number `call` - 0 take and store the cond - uncond difference, 1 reuse it
+    const int32_t* reuse_host = nullptr;
     int start(const void* z, void* traj_dev, bool z_in_slot0) {
         traj = traj_dev;
         flips0 = e->layout_flips_total;
@@ -57,9 +59,26 @@ struct Trajectory {
         if (!cfg_host) { rows += a->batch; return forward_graphed(e, y, t, out, a, use_cfg, s, pc); }
         // scale 1 exactly: the guided output is the conditional one - the cond rows alone, written to both halves
         const bool cond_only = cfg_host[call] == 1.0f;
+        if (reuse_host && !cond_only) return eval_reuse(y, t, call, out);
         rows += cond_only ? a->batch / 2 : a->batch;
         return forward_graphed(e, y, t, out, a, 1, s, nullptr, cfg_dev + call, cond_only, cfg_rule);
     }
+    // a guided evaluation of a reuse table: all rows and the difference stored, or the cond rows and the stored difference (the caller has
+    // checked that a refresh comes first and has run ensure_delta)
+    int eval_reuse(const void* y, const float* t, int call, void* out) {
+        const bool again = reuse_host[call] != 0;
+        rows += again ? a->batch / 2 : a->batch;
+        if (!again) e->delta_sig[0] = 0;  // (until the evaluation that rewrites it has been issued whole)
+        if (int rc = forward_graphed(e, y, t, out, a, 1, s, nullptr, cfg_dev + call, false, false, again ? LT_EVAL_REUSE : LT_EVAL_STORE)) return rc;
+        if (!again) set_delta_sig(e, a);
+        return 0;
+    }
+    // what the difference buffer holds after a refresh evaluation of these step arguments: { B', H, W, ch }
+    static void delta_sig_of(const lt_engine* e, const lt_step_args* a, int sig[4]) {
+        const int cfg_ch = a->cfg_channels > 0 ? a->cfg_channels : 3;
+        sig[0] = a->batch / 2; sig[1] = a->latent_h; sig[2] = a->latent_w; sig[3] = std::min(cfg_ch, (int)e->cfg.in_channels);
+    }
+    static void set_delta_sig(lt_engine* e, const lt_step_args* a) { delta_sig_of(e, a, e->delta_sig); }
     int advance(int traj_slot) {  // y1 is the current state now [and slot `traj_slot` of the record]
         if (traj) LT_CHECK_HIP(hipMemcpyAsync((char*)traj + (size_t)traj_slot * sbytes, y1(), sbytes, hipMemcpyDeviceToDevice, s));
         cur ^= 1;
@@ -90,7 +109,8 @@ float bf16_round_host(float f) {
 // evaluation i * stages + k takes its guidance scale from cs->table: the scales are committed behind the stage times, one float per stage;
 // cs->rule (lt_sample_ode_cfg_rule): the rescale blend and the norm limit travel behind the scales and are put into e->g_cfg[1..2] once.
 struct MaskedBlend { const void *mask, *x1, *noise; };
-struct CfgSchedule { const float* table; const float* rule = nullptr; };  // host: (n_grid - 1) * stages scales; { rescale, norm limit } or null
+// host: (n_grid - 1) * stages scales; { rescale, norm limit } or null; the reuse flags of lt_sample_ode_cfg_reuse, one per scale, or null
+struct CfgSchedule { const float* table; const float* rule = nullptr; const int32_t* reuse = nullptr; };
 
 int ode_fixed_grid(lt_engine* e, const void* z_dev, void* traj_dev, void* final_dev, const float* tgrid_host, int n_grid, int method, int use_cfg,
                    int t_round, const lt_step_args* a, hipStream_t s, long long n, const PackedCall* pc, const MaskedBlend* mb = nullptr,
@@ -125,7 +145,7 @@ int ode_fixed_grid(lt_engine* e, const void* z_dev, void* traj_dev, void* final_
         LT_CHECK_HIP(hipMemcpyAsync(e->g_cfg + 1, e->times.dev + (size_t)ncalls * B + ncalls, 2 * sizeof(float), hipMemcpyDeviceToDevice, s));
     Trajectory tr{e, a, use_cfg, s, (size_t)n * (bf ? 2 : 4)};
     tr.pc = pc;
-    if (cs) { tr.cfg_host = cs->table; tr.cfg_dev = e->times.dev + (size_t)ncalls * B; tr.cfg_rule = cs->rule != nullptr; }
+    if (cs) { tr.cfg_host = cs->table; tr.cfg_dev = e->times.dev + (size_t)ncalls * B; tr.cfg_rule = cs->rule != nullptr; tr.reuse_host = cs->reuse; }
     if (tr.start(z_dev, traj_dev, true)) return 1;
     const int dt_code = bf ? 1 : 0;
     for (int i = 0; i + 1 < n_grid; ++i) {
@@ -264,10 +284,26 @@ int check_guided_table(const lt_engine* e, const char* who, const lt_step_args* 
     return check_guided_halves(e, who, a);
 }
 
-// lt_sample_ode_cfg_schedule, and with `rule` = { rescale, norm limit } lt_sample_ode_cfg_rule
+// the flag table of guidance reuse, one flag per scale: 0 / 1, and at the scales other than 1 a refresh before the first reuse
+// (at scale 1 exactly the stage is conditional-only under either flag)
+int check_reuse_flags(const char* who, const float* cfg_host, const int32_t* reuse_host, int ncalls) {
+    bool stored = false;
+    for (int i = 0; i < ncalls; ++i) {
+        LT_REQUIRE(reuse_host[i] == 0 || reuse_host[i] == 1, "%s: reuse flag %d of evaluation %d is not 0 (refresh) or 1 (reuse)", who, reuse_host[i], i);
+        if (cfg_host[i] == 1.0f) continue;
+        if (reuse_host[i] == 0) stored = true;
+        LT_REQUIRE(stored, "%s: evaluation %d reuses the cond - uncond difference, but no refresh evaluation (flag 0 at a scale other than 1) comes "
+                   "before it in this call", who, i);
+    }
+    return 0;
+}
+
+// lt_sample_ode_cfg_schedule, with `rule` = { rescale, norm limit } lt_sample_ode_cfg_rule, with `reuse_call` lt_sample_ode_cfg_reuse
 int sample_cfg_table(lt_engine* e, const char* who, const void* z_dev, void* traj_dev, void* final_dev, const float* tgrid_host, int n_grid, int method,
-                     const float* cfg_host, const float* rule, int t_round, const lt_step_args* a, hipStream_t s) {
+                     const float* cfg_host, const float* rule, int t_round, const lt_step_args* a, hipStream_t s, const int32_t* reuse_host = nullptr,
+                     bool reuse_call = false) {
     LT_REQUIRE(e && z_dev && tgrid_host && cfg_host && a, "%s: null argument", who);
+    LT_REQUIRE(!reuse_call || reuse_host, "%s: null argument (reuse_host: one int32 flag per stage)", who);
     if (refuse_if_capturing(s, who)) return 2;  // (the stage times travel through a host staging buffer that the next call rewrites)
     LtOptScope opt_scope(&e->opts);
     LT_REQUIRE(n_grid >= 2, "%s: need at least 2 grid points", who);
@@ -275,8 +311,10 @@ int sample_cfg_table(lt_engine* e, const char* who, const void* z_dev, void* tra
     if (check_step_shape(e, who, a)) return 2;
     const int stages = method == LT_ODE_EULER ? 1 : (method == LT_ODE_MIDPOINT ? 2 : 4);
     if (check_guided_table(e, who, a, cfg_host, n_grid - 1, stages, rule)) return 2;
+    if (reuse_call && check_reuse_flags(who, cfg_host, reuse_host, (n_grid - 1) * stages)) return 2;
+    if (reuse_call && ensure_delta(e)) return 1;
     const long long n = (long long)a->batch * e->cfg.in_channels * a->latent_h * a->latent_w;
-    const CfgSchedule cs{cfg_host, rule};
+    const CfgSchedule cs{cfg_host, rule, reuse_host};
     return ode_fixed_grid(e, z_dev, traj_dev, final_dev, tgrid_host, n_grid, method, 1, t_round, a, s, n, nullptr, nullptr, &cs);
 }
 
@@ -311,6 +349,46 @@ extern "C" int lt_forward_cfg_rule(lt_engine* e, const void* x_dev, const float*
     if (check_guided_halves(e, who, a)) return 2;
     if (launch_guidance_params_store(e->g_cfg, a->cfg_scale, rescale, norm_limit, (hipStream_t)stream)) return 1;
     return forward_graphed(e, x_dev, t_dev, out_dev, a, 1, (hipStream_t)stream, nullptr, e->g_cfg, false, true);
+}
+
+// ---- guidance reuse: the cond - uncond difference taken on refresh stages, reused on half-row stages in between ----------------
+extern "C" int lt_sample_ode_cfg_reuse(lt_engine* e, const void* z_dev, void* traj_dev, void* final_dev, const float* tgrid_host, int32_t n_grid,
+                                       int32_t method, const float* cfg_host, const int32_t* reuse_host, int32_t t_round, const lt_step_args* a,
+                                       void* stream) {
+    return sample_cfg_table(e, "lt_sample_ode_cfg_reuse", z_dev, traj_dev, final_dev, tgrid_host, n_grid, method, cfg_host, nullptr, t_round, a,
+                            (hipStream_t)stream, reuse_host, true);
+}
+
+// One guided evaluation at a->cfg_scale that stores the difference (mode 0: lt_forward_cfg's result) or evaluates the cond rows and reuses it
+// (mode 1).  The scale reaches the engine's fixed device word through a launch in front of the evaluation, as in lt_forward_cfg_rule.
+extern "C" int lt_forward_cfg_reuse(lt_engine* e, const void* x_dev, const float* t_dev, void* out_dev, int32_t mode, const lt_step_args* a,
+                                    void* stream) {
+    const char* who = "lt_forward_cfg_reuse";
+    LT_REQUIRE(e && x_dev && t_dev && out_dev && a, "%s: null argument", who);
+    if (refuse_if_capturing((hipStream_t)stream, who)) return 2;  // (the first call allocates the difference buffer)
+    LtOptScope opt_scope(&e->opts);
+    LT_REQUIRE(mode == 0 || mode == 1, "%s: mode %d is not 0 (guide and store the difference) or 1 (reuse it)", who, mode);
+    if (check_step_shape(e, who, a)) return 2;
+    LT_REQUIRE(std::isfinite(a->cfg_scale), "%s: the scale is not finite", who);
+    if (check_guided_halves(e, who, a)) return 2;
+    if (mode == 1) {
+        int want[4];
+        Trajectory::delta_sig_of(e, a, want);
+        const int* have = e->delta_sig;
+        LT_REQUIRE(have[0] != 0, "%s: no stored cond - uncond difference to reuse: none was taken (mode 0), or lt_prepare_prompt / "
+                   "lt_prepare_labels was called since", who);
+        LT_REQUIRE(have[0] == want[0] && have[1] == want[1] && have[2] == want[2] && have[3] == want[3],
+                   "%s: the stored cond - uncond difference is of another shape: %d samples of %d channels at %dx%d, the call has %d samples of %d "
+                   "channels at %dx%d", who, have[0], have[3], have[1], have[2], want[0], want[3], want[1], want[2]);
+    }
+    if (ensure_delta(e)) return 1;
+    if (launch_guidance_params_store(e->g_cfg, a->cfg_scale, 0.f, INFINITY, (hipStream_t)stream)) return 1;
+    if (mode == 0) e->delta_sig[0] = 0;  // (until the evaluation that rewrites it has been issued whole)
+    if (int rc = forward_graphed(e, x_dev, t_dev, out_dev, a, 1, (hipStream_t)stream, nullptr, e->g_cfg, false, false,
+                                 mode ? LT_EVAL_REUSE : LT_EVAL_STORE))
+        return rc;
+    if (mode == 0) Trajectory::set_delta_sig(e, a);
+    return 0;
 }
 
 // ---- linear multistep sampling: one evaluation per interval, the earlier slopes reused (multistep.hip) -------------------------
@@ -354,7 +432,7 @@ int ode_multistep(lt_engine* e, const void* z_dev, void* traj_dev, void* final_d
         LT_CHECK_HIP(hipMemcpyAsync(e->g_cfg + 1, e->times.dev + (size_t)ncalls * B + ncalls, 2 * sizeof(float), hipMemcpyDeviceToDevice, s));
     Trajectory tr{e, a, use_cfg, s, (size_t)n * (bf ? 2 : 4)};
     tr.pc = pc;
-    if (cs) { tr.cfg_host = cs->table; tr.cfg_dev = e->times.dev + (size_t)ncalls * B; tr.cfg_rule = cs->rule != nullptr; }
+    if (cs) { tr.cfg_host = cs->table; tr.cfg_dev = e->times.dev + (size_t)ncalls * B; tr.cfg_rule = cs->rule != nullptr; tr.reuse_host = cs->reuse; }
     if (tr.start(z_dev, traj_dev, true)) return 1;
     const int dt_code = bf ? 1 : 0;
     const void* p = tr.y0();  // p_i, the state evaluation i reads: p_0 = z
@@ -414,6 +492,25 @@ extern "C" int lt_sample_ode_multistep(lt_engine* e, const void* z_dev, void* tr
     const float rule[2] = {rescale, norm_limit};
     if (check_guided_table(e, who, a, cfg_host, n_grid - 1, 1, rule_on ? rule : nullptr)) return 2;
     const CfgSchedule cs{cfg_host, rule_on ? rule : nullptr};
+    return ode_multistep(e, z_dev, traj_dev, final_dev, tgrid_host, n_grid, coef_host, corrector, 1, t_round, a, (hipStream_t)stream, n, nullptr, &cs);
+}
+
+// lt_sample_ode_multistep with a scale and a reuse flag per evaluation: the same body, the checks of lt_sample_ode_cfg_reuse
+extern "C" int lt_sample_ode_multistep_cfg_reuse(lt_engine* e, const void* z_dev, void* traj_dev, void* final_dev, const float* tgrid_host,
+                                                 int32_t n_grid, const float* coef_host, int32_t corrector, const float* cfg_host,
+                                                 const int32_t* reuse_host, int32_t t_round, const lt_step_args* a, void* stream) {
+    const char* who = "lt_sample_ode_multistep_cfg_reuse";
+    LT_REQUIRE(e && z_dev && tgrid_host && coef_host && cfg_host && a, "%s: null argument", who);
+    LT_REQUIRE(reuse_host, "%s: null argument (reuse_host: one int32 flag per evaluation)", who);
+    if (check_multistep(who, n_grid, coef_host, corrector)) return 2;
+    if (refuse_if_capturing((hipStream_t)stream, who)) return 2;  // (the stage times travel through a host staging buffer that the next call rewrites)
+    LtOptScope opt_scope(&e->opts);
+    if (check_step_shape(e, who, a)) return 2;
+    if (check_guided_table(e, who, a, cfg_host, n_grid - 1, 1, nullptr)) return 2;
+    if (check_reuse_flags(who, cfg_host, reuse_host, n_grid - 1)) return 2;
+    if (ensure_delta(e)) return 1;
+    const long long n = (long long)a->batch * e->cfg.in_channels * a->latent_h * a->latent_w;
+    const CfgSchedule cs{cfg_host, nullptr, reuse_host};
     return ode_multistep(e, z_dev, traj_dev, final_dev, tgrid_host, n_grid, coef_host, corrector, 1, t_round, a, (hipStream_t)stream, n, nullptr, &cs);
 }
 

@@ -503,6 +503,89 @@ class DiTEngine:
         _lib.check(rc, "lt_forward_cfg_rule")
         return out
 
+    # ---- guidance reuse: the cond - uncond difference taken on refresh stages, reused on half-row stages -------------
+    @staticmethod
+    def _reuse_tables(table, reuse, count: int, what: str):
+        """the scale table and the flag table as contiguous fp32 / int32 CPU tensors of ``count`` entries (their contents are the C entry's to
+        check)"""
+        tab = table if isinstance(table, torch.Tensor) else torch.tensor(list(table), dtype=torch.float32)
+        tab = tab.detach().to("cpu", torch.float32).reshape(-1).contiguous()
+        if reuse is None:
+            raise LuminaLibError(f"{what}: reuse is None (one 0 / 1 flag per evaluation; transport.guidance.cfg_reuse_table builds one)")
+        flg = reuse if isinstance(reuse, torch.Tensor) else torch.tensor(list(reuse))
+        if flg.is_floating_point() and not bool((flg == flg.round()).all()):
+            raise LuminaLibError(f"{what}: a reuse flag is not 0 (refresh) or 1 (reuse)")
+        flg = flg.detach().to("cpu", torch.int32).reshape(-1).contiguous()
+        if tab.numel() != count or flg.numel() != count:
+            raise LuminaLibError(f"{what}: the guidance table has {tab.numel()} entries and the reuse table {flg.numel()}, the grid has {count} "
+                                 "evaluations")
+        return tab, flg
+
+    def sample_ode_cfg_reuse(self, z: torch.Tensor, tgrid, table, reuse, method: str, *, scale_factor: float = 1.0, scale_watershed: float = 1.0,
+                             base_seqlen: Optional[int] = None, proportional_attn: bool = False, t_round_to_state_dtype: bool = True,
+                             return_trajectory: bool = True, ntk_factor: float = 1.0, cfg_scale=None) -> torch.Tensor:
+        """``sample_ode_cfg_schedule`` with a flag per stage (lt_sample_ode_cfg_reuse): a guided stage with flag 0 evaluates all rows and keeps
+        the cond - uncond difference of its guided channels, one with flag 1 evaluates the ``z.size(0) / 2`` cond rows alone and guides them
+        with the difference kept.  ``transport.guidance.sample_cfg_reuse`` is the definition, ``cfg_reuse_table`` builds flag tables."""
+        if isinstance(z, (list, tuple)):
+            raise LuminaLibError("sample_ode_cfg_reuse: a packed batch (a list of latents) is not served")
+        _require_gpu(z, "z")
+        if method not in _lib.ODE_METHODS:
+            raise LuminaLibError(f"fixed-grid method '{method}' not in {sorted(_lib.ODE_METHODS)}")
+        z = z.contiguous()
+        garr, n = _grid_array(tgrid)
+        stages = {"euler": 1, "midpoint": 2, "rk4": 4}[method]
+        tab, flg = self._reuse_tables(table, reuse, max(n - 1, 0) * stages, "sample_ode_cfg_reuse")
+        a = self._step_args(z, 0.0, scale_factor, scale_watershed, base_seqlen, proportional_attn, ntk_factor=ntk_factor)
+        out, traj_ptr, fin_ptr = _traj_or_final(z, max(n, 1), z.shape, return_trajectory)
+        with torch.cuda.device(self.device):
+            rc = self.lib.lt_sample_ode_cfg_reuse(self.handle, C.c_void_p(z.data_ptr()), traj_ptr, fin_ptr, garr, n, _lib.ODE_METHODS[method],
+                                                  C.cast(tab.data_ptr(), C.POINTER(C.c_float)), C.cast(flg.data_ptr(), C.POINTER(C.c_int32)),
+                                                  int(t_round_to_state_dtype), C.byref(a), C.c_void_p(_stream_ptr(self.device)))
+        _lib.check(rc, "lt_sample_ode_cfg_reuse")
+        return out
+
+    def sample_ode_multistep_cfg_reuse(self, z: torch.Tensor, tgrid, method: Optional[str], table, reuse, *, coef=None, scale_factor: float = 1.0,
+                                       scale_watershed: float = 1.0, base_seqlen: Optional[int] = None, proportional_attn: bool = False,
+                                       t_round_to_state_dtype: bool = True, return_trajectory: bool = True, ntk_factor: float = 1.0,
+                                       cfg_scale=None) -> torch.Tensor:
+        """``sample_ode_multistep`` with a guidance scale and a reuse flag per evaluation (lt_sample_ode_multistep_cfg_reuse);
+        ``transport.guidance.sample_cfg_reuse_multistep`` is the definition."""
+        _require_gpu(z, "z")
+        z = z.contiguous()
+        garr, n = _grid_array(tgrid)
+        coef, corrector = self._multistep_table(tgrid, method, n, "sample_ode_multistep_cfg_reuse", coef)
+        tab, flg = self._reuse_tables(table, reuse, n - 1, "sample_ode_multistep_cfg_reuse")
+        a = self._step_args(z, 0.0, scale_factor, scale_watershed, base_seqlen, proportional_attn, ntk_factor=ntk_factor)
+        out, traj_ptr, fin_ptr = _traj_or_final(z, n, z.shape, return_trajectory)
+        with torch.cuda.device(self.device):
+            rc = self.lib.lt_sample_ode_multistep_cfg_reuse(self.handle, C.c_void_p(z.data_ptr()), traj_ptr, fin_ptr, garr, n,
+                                                            C.cast(coef.data_ptr(), C.POINTER(C.c_float)), corrector,
+                                                            C.cast(tab.data_ptr(), C.POINTER(C.c_float)), C.cast(flg.data_ptr(), C.POINTER(C.c_int32)),
+                                                            int(t_round_to_state_dtype), C.byref(a), C.c_void_p(_stream_ptr(self.device)))
+        _lib.check(rc, "lt_sample_ode_multistep_cfg_reuse")
+        return out
+
+    def forward_cfg_reuse(self, x: torch.Tensor, t: torch.Tensor, *, cfg_scale: float, reuse: bool = False, scale_factor: float = 1.0,
+                          scale_watershed: float = 1.0, base_seqlen: Optional[int] = None, proportional_attn: bool = False,
+                          ntk_factor: float = 1.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """one guided evaluation at ``cfg_scale`` (lt_forward_cfg_reuse): ``reuse=False`` is ``forward_with_cfg`` and keeps the cond - uncond
+        difference, ``reuse=True`` evaluates the cond rows alone and guides them with the difference kept - refused by name when none of this
+        shape is there.  ``out`` (optional): the tensor to write, shaped and typed like ``x``."""
+        _require_gpu(x, "x")
+        x = x.contiguous()
+        t32 = t.to(device=x.device, dtype=torch.float32).contiguous()
+        if out is None:
+            out = torch.empty_like(x)
+        elif out.shape != x.shape or out.dtype != x.dtype or out.device != x.device or not out.is_contiguous():
+            raise LuminaLibError("forward_cfg_reuse: out must be contiguous and shaped and typed like x")
+        a = self._step_args(x, cfg_scale, scale_factor, scale_watershed, base_seqlen, proportional_attn, ntk_factor=ntk_factor)
+        with torch.cuda.device(self.device):
+            rc = self.lib.lt_forward_cfg_reuse(self.handle, C.c_void_p(x.data_ptr()), C.c_void_p(t32.data_ptr()), C.c_void_p(out.data_ptr()),
+                                               int(bool(reuse)), C.byref(a), C.c_void_p(_stream_ptr(self.device)))
+        _lib.check(rc, "lt_forward_cfg_reuse")
+        return out
+
     # ---- linear multistep sampling: one evaluation per interval (DESIGN 7j) -------------
     @staticmethod
     def _multistep_table(tgrid, method: str, n: int, what: str, coef=None):

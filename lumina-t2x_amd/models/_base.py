@@ -94,13 +94,26 @@ class EngineSamplers:
         eng, args = self._engine_sampler_args(x, use_cfg, kw)
         return eng.sample_ode_masked(x, tgrid, mask, x1, noise, method, use_cfg=use_cfg, t_round_to_state_dtype=t_round, **args)
 
-    def _engine_sample_ode_cfg_schedule(self, x, tgrid, method, t_round, table, kw, return_trajectory=True, rescale=0.0, norm_limit=math.inf):
+    def _engine_sample_ode_cfg_schedule(self, x, tgrid, method, t_round, table, kw, return_trajectory=True, rescale=0.0, norm_limit=math.inf,
+                                        reuse=None):
         """kwargs of forward_with_cfg -> lt_sample_ode_cfg_schedule (guidance schedules; ``cfg_scale`` in kw is ignored), or - with a
-        rescale blend or a norm limit - lt_sample_ode_cfg_rule"""
-        from ..transport.guidance import rule_is_off
+        rescale blend or a norm limit - lt_sample_ode_cfg_rule, or - with a reuse table - lt_sample_ode_cfg_reuse"""
+        from ..transport.guidance import refuse_rule_with_reuse, rule_is_off
+        if reuse is not None:
+            if not isinstance(x, torch.Tensor):
+                raise _lib.LuminaLibError("guidance reuse: a packed batch (a list of latents) is not served")
+            try:
+                refuse_rule_with_reuse(rescale, norm_limit)
+            except ValueError as exc:
+                raise _lib.LuminaLibError(str(exc)) from None
         kw.setdefault("cfg_scale", 1.0)
         eng, args = self._engine_sampler_args(x, True, kw)
         args.pop("cfg_scale", None)
+        if reuse is not None and method in _lib.ODE_MULTISTEP_METHODS:
+            return eng.sample_ode_multistep_cfg_reuse(x, tgrid, method, table, reuse, t_round_to_state_dtype=t_round,
+                                                      return_trajectory=return_trajectory, **args)
+        if reuse is not None:
+            return eng.sample_ode_cfg_reuse(x, tgrid, table, reuse, method, t_round_to_state_dtype=t_round, return_trajectory=return_trajectory, **args)
         if method in _lib.ODE_MULTISTEP_METHODS:  # one evaluation per interval: the table has len(tgrid) - 1 entries (DESIGN 7j)
             return eng.sample_ode_multistep(x, tgrid, method, use_cfg=True, table=table, rescale=rescale, norm_limit=norm_limit,
                                             t_round_to_state_dtype=t_round, return_trajectory=return_trajectory, **args)
@@ -113,7 +126,7 @@ class EngineSamplers:
 
     @torch.no_grad()
     def sample_ode_cfg_schedule(self, z, tgrid, table, *cond, method: str = "midpoint", return_trajectory: bool = False, rescale: float = 0.0,
-                                norm_limit: float = math.inf, **step_kw):
+                                norm_limit: float = math.inf, reuse=None, **step_kw):
         """A guided fixed-grid trajectory with a scale per stage in ONE engine call (lt_sample_ode_cfg_schedule): stage k of interval
         i evaluates ``forward_with_cfg`` at ``table[i * stages + k]``, or - at scale 1 exactly - the plain forward of the cond rows alone, at
         half the rows.  ``cond``: the family's conditioning as ``forward_with_cfg`` takes it (``cap_feats, cap_mask`` or ``y``) for all
@@ -121,13 +134,15 @@ class EngineSamplers:
         for guidance intervals and schedules.  ``method``: euler / midpoint / rk4, or a multistep method ab2 / ab3 / abm2 / abm3 (one evaluation
         per interval, so a table of ``len(tgrid) - 1`` entries; lt_sample_ode_multistep).  ``rescale`` (a blend in [0, 1]) / ``norm_limit`` (> 0; inf: off): the guided stages multiply
         their guided channels by the per-sample factor of ``transport.guidance.guided_rule`` (lt_sample_ode_cfg_rule); at the
-        defaults the call is the schedule call.  Returns the last state, or all ``len(tgrid)`` states."""
+        defaults the call is the schedule call.  ``reuse`` (one 0 / 1 flag per table entry; ``transport.guidance.cfg_reuse_table``): guided stages
+        with flag 1 evaluate the cond rows alone and reuse the cond - uncond difference of the last stage with flag 0 (lt_sample_ode_cfg_reuse,
+        DESIGN 7k; refused together with a rule); ``None``: the call made without it.  Returns the last state, or all ``len(tgrid)`` states."""
         if len(cond) > len(self._cond_names):
             raise TypeError(f"sample_ode_cfg_schedule takes the conditioning {self._cond_names}, got {len(cond)} positional arguments")
         kw = dict(zip(self._cond_names, cond), **step_kw)
         self._mirror_attention_flags(kw)
         return self._engine_sample_ode_cfg_schedule(z, tgrid, method, True, table, kw, return_trajectory=return_trajectory, rescale=rescale,
-                                                    norm_limit=norm_limit)
+                                                    norm_limit=norm_limit, reuse=reuse)
 
     def _mirror_attention_flags(self, kw):
         if hasattr(self, "layers") and "proportional_attn" in kw and len(self.layers) and hasattr(self.layers[0], "attention"):
@@ -152,6 +167,24 @@ class EngineSamplers:
         self._mirror_attention_flags(kw)
         eng, args = self._engine_sampler_args(x, True, kw)
         return eng.forward_cfg_rule(x, t, rescale=rescale, norm_limit=norm_limit, **args)
+
+    @torch.no_grad()
+    def forward_with_cfg_reuse(self, x, t, *cond, reuse: bool = False, **step_kw):
+        """``forward_with_cfg(x, t, <conditioning>, cfg_scale, **step_kw)`` in ONE engine call that keeps (``reuse=False``: the result is
+        ``forward_with_cfg``'s) or reuses (``reuse=True``: the cond rows alone are evaluated) the cond - uncond difference of the guided channels
+        (lt_forward_cfg_reuse).  ``cond``: the conditioning for all ``x.size(0)`` rows, then ``cfg_scale`` (or ``cfg_scale=`` by
+        keyword).  A reuse with no difference of this shape kept since the conditioning was last prepared is refused by name.  Tensor states only."""
+        if not isinstance(x, torch.Tensor):
+            raise _lib.LuminaLibError("forward_with_cfg_reuse: a packed batch (a list of latents) is not served by guidance reuse")
+        names = self._cond_names + ("cfg_scale",)
+        if len(cond) > len(names):
+            raise TypeError(f"forward_with_cfg_reuse takes {names}, got {len(cond)} positional arguments")
+        kw = dict(zip(names, cond), **step_kw)
+        if "cfg_scale" not in kw:
+            raise TypeError("forward_with_cfg_reuse needs cfg_scale")
+        self._mirror_attention_flags(kw)
+        eng, args = self._engine_sampler_args(x, True, kw)
+        return eng.forward_cfg_reuse(x, t, reuse=reuse, **args)
 
     def _engine_sample_ode_adaptive(self, x, tgrid, method, use_cfg, t_round, kw, *, rtol, atol, first_step=None, max_steps=2 ** 31 - 1):
         """kwargs of forward_with_cfg / forward -> lt_sample_ode_adaptive; returns (states [len(tgrid), *x.shape], stats dict)"""

@@ -172,7 +172,10 @@ def run(args, *, encode_fn=None, cap_feat_dim=None, decode_fn=None, model=None) 
             kw.update(scale_factor=1.0, scale_watershed=1.0)
         table = guidance_table(args, sample_fn.__self__.t)
         rule = guidance_rule(args)
-        if table is None and not rule:
+        reuse = guidance_reuse(args, sample_fn.__self__.t, table)
+        if reuse is not None:  # guided stages that reuse the last refresh stage's cond - uncond difference at half the rows
+            latent = sample_fn(z, model.forward_with_cfg, cfg_table=table, cfg_reuse=reuse, **kw)[-1][:1]
+        elif table is None and not rule:
             latent = sample_fn(z, model.forward_with_cfg, **kw)[-1][:1]
         elif not rule:  # a scale per stage; stages at scale 1 evaluate the cond row alone (transport/guidance.py)
             latent = sample_fn(z, model.forward_with_cfg, cfg_table=table, **kw)[-1][:1]
@@ -216,6 +219,23 @@ def guidance_rule(args) -> dict:
     return dict(cfg_rescale=rescale, cfg_norm_limit=limit)
 
 
+def guidance_reuse(args, tgrid, table):
+    """``--cfg_reuse K`` / ``--cfg_reuse_per_step`` as the flag table of ``transport.guidance.cfg_reuse_table`` over the scale table (None: one
+    scale for every stage); None at the defaults: no reuse, the call it was.  Refused together with ``--cfg_rescale`` / ``--cfg_norm_limit``."""
+    every, per_step = int(getattr(args, "cfg_reuse", 0) or 0), bool(getattr(args, "cfg_reuse_per_step", False))
+    if every == 0 and not per_step:
+        return None
+    if guidance_rule(args):
+        raise SystemExit("--cfg_reuse / --cfg_reuse_per_step are not served together with --cfg_rescale / --cfg_norm_limit: the rule's sums "
+                         "need the prompt and the negative row of every guided stage")
+    if every < 0 or every == 1:
+        raise SystemExit(f"--cfg_reuse {every}: K >= 2 refreshes the guidance difference on every K-th guided stage (0: off)")
+    from .transport import guidance
+    if table is None:
+        table = guidance.cfg_table(tgrid, args.sampling_method, args.cfg_scale)
+    return guidance.cfg_reuse_table(tgrid, args.sampling_method, table, every=max(every, 2), per_step=per_step)
+
+
 def build_parser() -> argparse.ArgumentParser:
     def none_or_str(v):
         return None if v == "None" else v
@@ -230,6 +250,11 @@ def build_parser() -> argparse.ArgumentParser:
                    help="guidance rescale: blend PHI in [0, 1] of the guided output's std towards the prompt row's (0: off)")
     p.add_argument("--cfg_norm_limit", type=float, default=None, metavar="R",
                    help="cap the guided output's L2 norm per sample at R times the prompt row's (default: no limit)")
+    p.add_argument("--cfg_reuse", type=int, default=0, metavar="K",
+                   help="take the guidance difference (prompt row - negative row) on every K-th guided stage and reuse it on the stages in "
+                        "between, which then evaluate the prompt row alone (0: off)")
+    p.add_argument("--cfg_reuse_per_step", action="store_true",
+                   help="... instead on the first guided stage of every step (midpoint, rk4), reused on the step's other stages")
     p.add_argument("--num_sampling_steps", type=int, default=250)
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--ckpt", type=str, required=True)

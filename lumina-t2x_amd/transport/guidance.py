@@ -24,7 +24,11 @@ families whose factors persist on the module.
 
 Rescaled and norm-limited guidance multiplies the guided output of every stage whose scale is not 1 by one factor per sample:
 ``guided_rule`` is the rule, ``sample_cfg_rule`` the loop around it - ``sample_cfg_schedule`` with another ``func`` - and
-``lt_sample_ode_cfg_rule`` / ``lt_forward_cfg_rule`` are held to them word for word."""
+``lt_sample_ode_cfg_rule`` / ``lt_forward_cfg_rule`` are held to them word for word.
+
+Guidance reuse takes the difference ``cond - uncond`` of the guided channels on some guided stages and reuses it on the others,
+which evaluate the cond rows alone: ``sample_cfg_reuse`` / ``sample_cfg_reuse_multistep`` are the definition ``lt_sample_ode_cfg_reuse`` /
+``lt_sample_ode_multistep_cfg_reuse`` are held to, ``cfg_reuse_table`` builds the flag tables and ``check_reuse`` refuses what the engine refuses."""
 from __future__ import annotations
 
 import math
@@ -358,4 +362,181 @@ def sample_cfg_multistep(model, z, tgrid, table, method="abm2", *, rescale=0.0, 
 
     out = multistep_odeint(func, z, _grid32(tgrid), method, t_round=t_round)
     assert call[0] == len(w)
+    return out
+
+
+# ---- guidance reuse: the cond - uncond difference taken on refresh stages, reused in between -----------------------------------
+def check_reuse(reuse, table, tgrid, method):
+    """``(table, flags)``: the scale table of ``check_table`` and the reuse table as a list of 0 / 1, one per evaluation.  Refused: a wrong
+    length, a flag other than 0 / 1, and - among the evaluations whose scale is not 1 - a reuse before the first refresh (at scale 1 exactly
+    the evaluation is conditional-only under either flag)."""
+    table = check_table(table, tgrid, method)
+    r = reuse if isinstance(reuse, th.Tensor) else th.tensor(list(reuse))
+    r = r.detach().to("cpu").reshape(-1)
+    if r.numel() != table.numel():
+        raise ValueError(f"reuse table has {r.numel()} entries, the guidance table has {table.numel()}")
+    flags = []
+    for i, v in enumerate(r.tolist()):
+        if v not in (0, 1):  # (True / False included)
+            raise ValueError(f"reuse flag {v} of evaluation {i} is not 0 (refresh) or 1 (reuse)")
+        flags.append(int(v))
+    stored = False
+    for i, (w, f) in enumerate(zip(table.tolist(), flags)):
+        if w == 1.0:
+            continue
+        stored = stored or f == 0
+        if not stored:
+            raise ValueError(f"evaluation {i} reuses the cond - uncond difference, but no refresh evaluation (flag 0 at a scale other than 1) "
+                             "comes before it")
+    return table, flags
+
+
+def cfg_reuse_table(tgrid, method, table, every=2, interval=None, per_step=False):
+    """The int32 flag table of a trajectory.  Among the evaluations with ``table != 1`` whose UNROUNDED stage time lies in ``interval = (lo, hi)``
+    (``lo <= t < hi``; default: all of them) evaluation number ``j`` is a refresh (0) when ``j % every == 0``, else a reuse (1);
+    ``per_step``: the first such evaluation of each grid interval is the refresh, its other stages reuse.  Entries at scale 1 are 0, guided
+    entries outside the interval are refreshes, and the first guided evaluation of the trajectory is always a refresh."""
+    stages = _check_method(method, multistep=True)
+    table = check_table(table, tgrid, method)
+    every = int(every)
+    if every < 1:
+        raise ValueError(f"cfg_reuse_table: every = {every} (1: refresh every guided evaluation)")
+    lo, hi = (-math.inf, math.inf) if interval is None else (float(interval[0]), float(interval[1]))
+    if not lo <= hi:
+        raise ValueError(f"reuse interval [{lo}, {hi}) is empty or not ordered")
+    ts = stage_times(tgrid, method, th.float32, False).tolist()
+    flags, j, stored, last_step = [], 0, False, -1
+    for i, (w, t) in enumerate(zip(table.tolist(), ts)):
+        flag = 0
+        if w != 1.0 and lo <= t < hi:
+            if per_step:
+                flag = 0 if i // stages != last_step else 1
+                last_step = i // stages
+            else:
+                flag = 0 if j % every == 0 else 1
+            j += 1
+        if w != 1.0:
+            if not stored:
+                flag = 0
+            stored = True
+        flags.append(flag)
+    return th.tensor(flags, dtype=th.int32)
+
+
+def refuse_rule_with_reuse(rescale, norm_limit):
+    """a reuse table together with a rescale blend or a norm limit is not served: the rule's sums need both halves of every guided stage"""
+    if not rule_is_off(rescale, norm_limit):
+        raise ValueError("guidance reuse (a reuse table) together with a rescale / norm_limit rule is not served: the rule's sums need the "
+                         "cond and the uncond rows of every guided stage")
+
+
+def _reuse_func(model, B, w, flags, cond_kw, half_kw, device, deltas=None):
+    """the evaluation of ``sample_cfg_reuse`` / ``sample_cfg_reuse_multistep`` and its call counter"""
+    ch_model = int(getattr(model, "cfg_channels", 3))
+    call = [0]
+    held = [None]  # d of the last refresh evaluation, bf16 [B', ch, H, W]
+
+    def func(tt, y):
+        scale, again = w[call[0]], flags[call[0]]
+        call[0] += 1
+        half = B // 2
+        tvec = th.ones(B).to(device) * tt  # fp32 [B] (reference integrators.py:108)
+        if scale == 1.0:  # the conditional-only stage of sample_cfg_schedule; d is neither read nor written
+            o = model.forward(y[:half], tvec[:half], **half_kw)
+            return th.cat([o, o])
+        if not again:
+            o = model.forward(th.cat([y[:half]] * 2), tvec, **cond_kw).to(th.bfloat16)  # (taken as bf16, as guided_rule takes it)
+            ch = min(ch_model, o.size(1))
+            c, u = o[:half, :ch], o[half:, :ch]
+            d = c - u
+            g = u + scale * d
+            held[0] = d
+            if deltas is not None:
+                deltas.append(d)
+            return th.cat([th.cat([g, o[:half, ch:]], 1), th.cat([g, o[half:, ch:]], 1)]).to(y.dtype)
+        o = model.forward(y[:half], tvec[:half], **half_kw).to(th.bfloat16)
+        d = held[0]
+        ch = d.size(1)
+        g = (o[:, :ch] - d) + scale * d
+        r = th.cat([g, o[:, ch:]], 1)
+        return th.cat([r, r]).to(y.dtype)
+
+    return func, call
+
+
+def _reuse_setup(z, kw, cond):
+    B = z.size(0)
+    if B % 2:
+        raise ValueError(f"guidance needs an even batch (cond + uncond rows), got {B}")
+    kw = dict(kw)
+    kw.pop("cfg_scale", None)  # the table is the scale
+    refuse_rule_with_reuse(kw.pop("rescale", 0.0), kw.pop("norm_limit", math.inf))
+    if cond is None:
+        cond = [k for k, v in kw.items() if isinstance(v, th.Tensor) and v.dim() >= 1 and v.shape[0] == B]
+    cond_kw = {k: kw.pop(k) for k in cond}
+    half_kw = {k: _cond_half(v, B) for k, v in cond_kw.items()}
+    return B, cond_kw, half_kw
+
+
+def sample_cfg_reuse(model, z, tgrid, table, reuse, method="euler", *, cond=None, t_round=True, deltas=None, **kw):
+    """The trajectory of guidance reuse on the host: every state ``[len(tgrid), *z.shape]``.  This IS the definition ``lt_sample_ode_cfg_reuse``
+    is held to, state for state.  Per evaluation ``table`` gives the scale ``w`` and ``reuse`` a flag:
+
+        w == 1            o = model.forward(x[:B'], t[:B'], <cond half>);  slope = cat([o, o])                     # sample_cfg_schedule's
+        w != 1, flag 0    o = bf16(model.forward(cat([x[:B']] * 2), t, <conditioning>));  d = c - u;  g = u + w * d   # B rows; d is kept
+        w != 1, flag 1    o = bf16(model.forward(x[:B'], t[:B'], <cond half>));  g = (o - d) + w * d                  # B' rows; d is read
+
+    on the first ``min(model.cfg_channels, C)`` channels in bf16 tensor ops (every op rounds), the other channels passing through row by row
+    (refresh) or from the cond rows (reuse), ``g`` written to both halves, the result cast to the state dtype.  The loop is
+    ``fixed_grid_odeint``'s, statement for statement.  ``deltas`` (a list): receives ``d`` of every refresh stage."""
+    if isinstance(z, (list, tuple)):
+        raise ValueError("guidance reuse takes a tensor state; a packed batch (a list of latents) is not served")
+    stages = _check_method(method)
+    table, flags = check_reuse(reuse, table, tgrid, method)
+    B, cond_kw, half_kw = _reuse_setup(z, kw, cond)
+    device = z.device
+    t = _grid32(tgrid).to(device)
+    func, call = _reuse_func(model, B, table.tolist(), flags, cond_kw, half_kw, device, deltas)
+
+    def f(tt, y):
+        return _call(func, tt, y) if t_round else func(tt, y)
+
+    # fixed_grid_odeint's loop (integrators.py), statement for statement
+    out = th.empty((len(t),) + tuple(z.shape), dtype=z.dtype, device=device)
+    out[0] = z
+    y = z
+    third, two_thirds = 1.0 / 3.0, 2.0 / 3.0
+    for j in range(len(t) - 1):
+        t0, t1 = t[j], t[j + 1]
+        dt = t1 - t0
+        k1 = f(t0, y)
+        if method == "euler":
+            dy = dt * k1
+        elif method == "midpoint":
+            half = 0.5 * dt
+            dy = dt * f(t0 + half, y + k1 * half)
+        else:
+            k2 = f(t0 + dt * third, y + dt * k1 * third)
+            k3 = f(t0 + dt * two_thirds, y + dt * (k2 - k1 * third))
+            k4 = f(t1, y + dt * (k1 - k2 + k3))
+            dy = (k1 + 3 * (k2 + k3) + k4) * dt * 0.125
+        y = y + dy
+        out[j + 1] = y
+    assert call[0] == (len(t) - 1) * stages
+    return out
+
+
+def sample_cfg_reuse_multistep(model, z, tgrid, table, reuse, method="abm2", *, cond=None, t_round=True, deltas=None, **kw):
+    """``transport.multistep.multistep_odeint`` around the evaluation of ``sample_cfg_reuse`` (``len(tgrid) - 1`` scales and flags): what
+    ``lt_sample_ode_multistep_cfg_reuse`` is held to, state for state."""
+    from .multistep import multistep_odeint
+    if isinstance(z, (list, tuple)):
+        raise ValueError("guidance reuse takes a tensor state; a packed batch (a list of latents) is not served")
+    if method not in MULTISTEP_METHODS:
+        raise ValueError(f"unknown multistep method '{method}' (built: {', '.join(MULTISTEP_METHODS)})")
+    table, flags = check_reuse(reuse, table, tgrid, method)
+    B, cond_kw, half_kw = _reuse_setup(z, kw, cond)
+    func, call = _reuse_func(model, B, table.tolist(), flags, cond_kw, half_kw, z.device, deltas)
+    out = multistep_odeint(func, z, _grid32(tgrid), method, t_round=t_round)
+    assert call[0] == len(flags)
     return out

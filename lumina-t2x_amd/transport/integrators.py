@@ -321,17 +321,25 @@ class ode:
         self.max_num_steps = 2 ** 31 - 1
         self.stats = None         # adaptive methods: nfe / accepted / rejected / first_step / dt of the last sample() call
 
-    def _sample_cfg_schedule(self, x, model, table, model_kwargs, rescale=0.0, norm_limit=math.inf):
+    def _sample_cfg_schedule(self, x, model, table, model_kwargs, rescale=0.0, norm_limit=math.inf, reuse=None):
         """a guidance schedule (transport/guidance.py): one engine call for an engine-backed forward_with_cfg, else the host loop"""
-        from .guidance import cfg_table, rule_is_off, sample_cfg_multistep, sample_cfg_rule, sample_cfg_schedule
+        from .guidance import (cfg_table, refuse_rule_with_reuse, rule_is_off, sample_cfg_multistep, sample_cfg_reuse, sample_cfg_reuse_multistep,
+                               sample_cfg_rule, sample_cfg_schedule)
         if (isinstance(x, tuple) or not getattr(self.drift, "is_plain_velocity", False)
                 or self.sampler_type not in FIXED_GRID_METHODS + MULTISTEP_METHODS):
             raise NotImplementedError("guidance schedules are built for the fixed-grid methods on a tensor state with the plain velocity as drift")
         rule_off = rule_is_off(rescale, norm_limit)
         if table is None:  # a rule without a table: one scale for every stage
             table = cfg_table(self.t, self.sampler_type, model_kwargs.get("cfg_scale", 1.0))
+        if reuse is not None:  # guidance reuse (DESIGN 7k): refused together with a rule and on a packed list, by name
+            if isinstance(x, (list, tuple)):
+                raise ValueError("guidance reuse (cfg_reuse) takes a tensor state; a packed batch (a list of latents) is not served")
+            refuse_rule_with_reuse(rescale, norm_limit)
         target = _engine_target(model)
         if target is not None and target[1] and x.is_cuda and self.use_engine and hasattr(target[0], "_engine_sample_ode_cfg_schedule"):
+            if reuse is not None:
+                return target[0]._engine_sample_ode_cfg_schedule(x, self.t, self.sampler_type, self.t_round_to_state_dtype, table, dict(model_kwargs),
+                                                                 reuse=reuse)
             if rule_off:  # the call it was before the rule existed
                 return target[0]._engine_sample_ode_cfg_schedule(x, self.t, self.sampler_type, self.t_round_to_state_dtype, table, dict(model_kwargs))
             return target[0]._engine_sample_ode_cfg_schedule(x, self.t, self.sampler_type, self.t_round_to_state_dtype, table, dict(model_kwargs),
@@ -339,6 +347,10 @@ class ode:
         owner = getattr(model, "__self__", None)
         if owner is None or getattr(model, "__name__", "") != "forward_with_cfg" or not hasattr(owner, "forward"):
             raise TypeError("cfg_table needs the bound forward_with_cfg of a model that also has forward (the conditional-only stages call it)")
+        if reuse is not None and self.sampler_type in MULTISTEP_METHODS:
+            return sample_cfg_reuse_multistep(owner, x, self.t, table, reuse, self.sampler_type, t_round=self.t_round_to_state_dtype, **model_kwargs)
+        if reuse is not None:
+            return sample_cfg_reuse(owner, x, self.t, table, reuse, self.sampler_type, t_round=self.t_round_to_state_dtype, **model_kwargs)
         if self.sampler_type in MULTISTEP_METHODS:
             return sample_cfg_multistep(owner, x, self.t, table, self.sampler_type, rescale=rescale, norm_limit=norm_limit,
                                         t_round=self.t_round_to_state_dtype, **model_kwargs)
@@ -347,9 +359,9 @@ class ode:
         return sample_cfg_rule(owner, x, self.t, table, self.sampler_type, rescale=rescale, norm_limit=norm_limit,
                                t_round=self.t_round_to_state_dtype, **model_kwargs)
 
-    def sample(self, x, model, cfg_table=None, cfg_rescale=0.0, cfg_norm_limit=math.inf, **model_kwargs):
-        if cfg_table is not None or not (float(cfg_rescale) == 0.0 and float(cfg_norm_limit) == math.inf):
-            return self._sample_cfg_schedule(x, model, cfg_table, model_kwargs, cfg_rescale, cfg_norm_limit)
+    def sample(self, x, model, cfg_table=None, cfg_rescale=0.0, cfg_norm_limit=math.inf, cfg_reuse=None, **model_kwargs):
+        if cfg_table is not None or cfg_reuse is not None or not (float(cfg_rescale) == 0.0 and float(cfg_norm_limit) == math.inf):
+            return self._sample_cfg_schedule(x, model, cfg_table, model_kwargs, cfg_rescale, cfg_norm_limit, cfg_reuse)
         if isinstance(x, tuple):  # the likelihood ODE (reference integrators.py:105-115 with a tuple state)
             device = x[0].device
 

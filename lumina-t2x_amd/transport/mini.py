@@ -8,7 +8,8 @@ for an engine-backed callable, the host loop ``sample_masked`` otherwise.  ``sam
 ``cfg_rescale=`` / ``cfg_norm_limit=`` add the per-sample factor of ``guided_rule`` to the guided stages (``lt_sample_ode_cfg_rule`` /
 ``sample_cfg_rule``; without ``cfg_table`` the table holds ``cfg_scale`` at every stage).  ``sampler_type`` ab2 / ab3 / abm2 / abm3
 (transport/multistep.py; not in the reference): one model evaluation per interval, one ``lt_sample_ode_multistep`` call or the host loop
-``multistep_odeint``; with an inpainting mask they are refused by name.
+``multistep_odeint``; with an inpainting mask they are refused by name.  ``cfg_reuse=`` (one 0 / 1 flag per evaluation, ``guidance.cfg_reuse_table``)
+is guidance reuse: one ``lt_sample_ode_cfg_reuse`` call or the host loop ``sample_cfg_reuse``; refused together with a rescale / norm limit.
 
 Not mirrored: ``use_sd3=True`` (drives a diffusers SD3Transformer2DModel, not a Lumina model - out of scope)."""
 from __future__ import annotations
@@ -18,7 +19,8 @@ import math
 import torch as th
 
 from .integrators import ADAPTIVE_METHODS, FIXED_GRID_METHODS, _engine_target, adaptive_odeint, fixed_grid_odeint
-from .guidance import cfg_table, rule_is_off, sample_cfg_multistep, sample_cfg_rule, sample_cfg_schedule
+from .guidance import (cfg_table, refuse_rule_with_reuse, rule_is_off, sample_cfg_multistep, sample_cfg_reuse, sample_cfg_reuse_multistep,
+                       sample_cfg_rule, sample_cfg_schedule)
 from .multistep import MASKED_REFUSAL, MULTISTEP_METHODS, multistep_odeint
 from .masked import expand_operands, sample_masked
 
@@ -60,7 +62,7 @@ class ODE:
                                                    dict(model_kwargs))
         return sample_masked(model, x, self.t, mask, x1, noise, self.sampler_type, **model_kwargs)
 
-    def _sample_cfg_schedule(self, x, model, table, model_kwargs, rescale=0.0, norm_limit=math.inf):
+    def _sample_cfg_schedule(self, x, model, table, model_kwargs, rescale=0.0, norm_limit=math.inf, reuse=None):
         """a guidance schedule (transport/guidance.py): a scale per stage; one engine call when the callable is an engine-backed forward_with_cfg"""
         if self.sampler_type not in FIXED_GRID_METHODS + MULTISTEP_METHODS:
             raise NotImplementedError(f"guidance schedules are built for the fixed-grid methods {', '.join(FIXED_GRID_METHODS)}, not "
@@ -68,8 +70,15 @@ class ODE:
         rule_off = rule_is_off(rescale, norm_limit)
         if table is None:  # a rule without a table: one scale for every stage
             table = cfg_table(self.t, self.sampler_type, model_kwargs.get("cfg_scale", 1.0))
+        if reuse is not None:  # guidance reuse: refused together with a rule and on a packed list, by name
+            if isinstance(x, (list, tuple)):
+                raise ValueError("guidance reuse (cfg_reuse) takes a tensor state; a packed batch (a list of latents) is not served")
+            refuse_rule_with_reuse(rescale, norm_limit)
         target = _engine_target(model)
         if target is not None and target[1] and x.is_cuda and self.use_engine and hasattr(target[0], "_engine_sample_ode_cfg_schedule"):
+            if reuse is not None:
+                return target[0]._engine_sample_ode_cfg_schedule(x, self.t, self.sampler_type, self.t_round_to_state_dtype, table, dict(model_kwargs),
+                                                                 reuse=reuse)
             if rule_off:  # the call it was before the rule existed
                 return target[0]._engine_sample_ode_cfg_schedule(x, self.t, self.sampler_type, self.t_round_to_state_dtype, table, dict(model_kwargs))
             return target[0]._engine_sample_ode_cfg_schedule(x, self.t, self.sampler_type, self.t_round_to_state_dtype, table, dict(model_kwargs),
@@ -77,6 +86,10 @@ class ODE:
         owner = getattr(model, "__self__", None)
         if owner is None or getattr(model, "__name__", "") != "forward_with_cfg" or not hasattr(owner, "forward"):
             raise TypeError("cfg_table needs the bound forward_with_cfg of a model that also has forward (the conditional-only stages call it)")
+        if reuse is not None and self.sampler_type in MULTISTEP_METHODS:
+            return sample_cfg_reuse_multistep(owner, x, self.t, table, reuse, self.sampler_type, t_round=self.t_round_to_state_dtype, **model_kwargs)
+        if reuse is not None:
+            return sample_cfg_reuse(owner, x, self.t, table, reuse, self.sampler_type, t_round=self.t_round_to_state_dtype, **model_kwargs)
         if self.sampler_type in MULTISTEP_METHODS:
             return sample_cfg_multistep(owner, x, self.t, table, self.sampler_type, rescale=rescale, norm_limit=norm_limit,
                                         t_round=self.t_round_to_state_dtype, **model_kwargs)
@@ -85,13 +98,14 @@ class ODE:
         return sample_cfg_rule(owner, x, self.t, table, self.sampler_type, rescale=rescale, norm_limit=norm_limit,
                                t_round=self.t_round_to_state_dtype, **model_kwargs)
 
-    def sample(self, x, model, mask=None, x1=None, noise=None, cfg_table=None, cfg_rescale=0.0, cfg_norm_limit=math.inf, **model_kwargs):
+    def sample(self, x, model, mask=None, x1=None, noise=None, cfg_table=None, cfg_rescale=0.0, cfg_norm_limit=math.inf, cfg_reuse=None,
+               **model_kwargs):
         if isinstance(x, tuple):
             raise NotImplementedError("tuple states are not part of the sampling path")
-        if cfg_table is not None or not rule_is_off(cfg_rescale, cfg_norm_limit):
+        if cfg_table is not None or cfg_reuse is not None or not rule_is_off(cfg_rescale, cfg_norm_limit):
             if mask is not None or x1 is not None or noise is not None:
                 raise NotImplementedError("a guidance schedule and an inpainting mask are not served together")
-            return self._sample_cfg_schedule(x, model, cfg_table, model_kwargs, cfg_rescale, cfg_norm_limit)
+            return self._sample_cfg_schedule(x, model, cfg_table, model_kwargs, cfg_rescale, cfg_norm_limit, cfg_reuse)
         if mask is not None or x1 is not None or noise is not None:
             return self._sample_masked(x, model, mask, x1, noise, model_kwargs)
         target = _engine_target(model)
