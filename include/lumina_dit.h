@@ -440,6 +440,30 @@ int lt_sample_ode_multistep_cfg_reuse(lt_engine* e, const void* z_dev, void* tra
                                       int32_t t_round_to_state_dtype, const lt_step_args* a, void* stream);
 int lt_forward_cfg_reuse(lt_engine* e, const void* x_dev, const float* t_dev, void* out_dev, int32_t mode, const lt_step_args* a, void* stream);
 
+/* ---- prompt-driven image editing: FlowEdit's inversion-free rule (Kulikov et al., 2024) as one call ---------------------------
+ * transport/edit.py: sample_flowedit is the definition; the reference has no such sampler.  Lumina's path x_t = t x1 + (1 - t) x0, noise at
+ * t = 0, the grid ascends.  The state is B' edits; a->batch = 4 B' rows per evaluation, conditioning prepared for them in the order
+ * [src_0 .. src_{B'-1}, tgt_*, neg_src_*, neg_tgt_*].  x_src_dev [B',C,H,W]: the source latent; z_dev [B',C,H,W]: the edit at tgrid[0]
+ * (normally x_src itself; may be the same buffer); noise_dev [n_grid - 1, B',C,H,W]: the caller's draws, one per interval (the engine owns no
+ * RNG); scales_host: n_grid - 1 fp32 pairs (w_s, w_t), the guidance scale of the source and of the target branch - all tensors in the state
+ * dtype a->io_dtype (bf16 or f32).  ch = a->cfg_channels, R = rounding to the state dtype, every scalar multiplies in fp32, nothing is
+ * contracted.  Per interval i, with t = tgrid[i], omt = fp32(1 - double(t)), dt = fp32(double(tgrid[i+1]) - double(tgrid[i])):
+ *   zs  = R(R(x_src t) + R(noise[i] omt))                        the source on the path
+ *   zt  = R(zs + R(z - x_src))                                   the edit, shifted by the same amount: z == x_src gives zt == zs exactly (the
+ *                                                                left-to-right (z + zs) - x_src would round the small edit delta away)
+ *   [c_s, c_t, u_s, u_t] = the PLAIN forward of [zs, zt, zs, zt] at the fp32 time t (lt_forward on 4 B' rows, through the graph cache: one key)
+ *   channels <  ch:  v_s = R(u_s + R(w_s R(c_s - u_s)))          v_t = R(u_t + R(w_t R(c_t - u_t)))       forward_with_cfg's expression per branch
+ *   channels >= ch:  v_s = c_s                                   v_t = c_t
+ *   z' = R(z + R(R(v_t - v_s) dt))
+ * Euler only: the rule has no higher-order form.  traj_dev (may be NULL) receives every state [n_grid, B',C,H,W], slot 0 = z; final_dev (may
+ * be NULL) the last one.  lt_last_nfe = n_grid - 1, lt_last_eval_rows = 4 B' (n_grid - 1).  Serves every variant lt_forward serves.  No
+ * synchronisation, no host read, the caller's stream.  Averaging over several noise draws per interval (n_avg of the paper) is not served.
+ * Refused by name with nothing written: a null argument other than traj_dev / final_dev; a stream under capture; n_grid < 2; a->batch that is
+ * not a positive multiple of 4 or exceeds max_batch; a latent or io_dtype lt_sample_ode refuses; cfg_channels outside 1..in_channels; a grid
+ * value or scale that is not finite; a regional prompt; conditioning prepared for another batch. */
+int lt_sample_flowedit(lt_engine* e, const void* z_dev, const void* x_src_dev, const void* noise_dev, void* traj_dev, void* final_dev,
+                       const float* tgrid_host, const float* scales_host, int32_t n_grid, const lt_step_args* a, void* stream);
+
 /* number of model evaluations issued by the last lt_sample_ode /lt_sample_ode_packed / lt_sample_views / lt_sample_views_guided / lt_sample_sde / lt_sample_ode_adaptive call */
 int64_t lt_last_nfe(lt_engine* e);
 /* the rows those evaluations ran, summed: nfe * batch for every sampler but lt_sample_ode_cfg_schedule, whose conditional-only stages run half */
@@ -673,6 +697,14 @@ int lt_op_views_reduce(const void* y_dev, const void* f_dev, const int32_t* iper
  * Operands an op does not read may be NULL. */
 int lt_op_sde_step(int32_t op, const void* x_dev, const void* v_dev, const void* w_dev, const void* k1_dev, const void* xp_dev, void* out_dev,
                    void* out2_dev, const float* rec_host, int64_t n, int32_t dtype, void* stream);
+/* the two state kernels of lt_sample_flowedit on caller-owned buffers (csrc/flowedit.hip; the chains are stated there and above), dtype LT_F32 or
+ * LT_BF16, n_half = B' C H W elements per row group:
+ *   mix:     out4 [4 B',C,H,W] = [zs, zt, zs, zt] from x_src, z (may be x_src; neither is written) and one interval's noise
+ *   combine: z_next [B',C,HW] from z and the evaluation's rows out4 = [c_s, c_t, u_s, u_t]; z_next may be z, not inside out4 */
+int lt_op_flowedit_mix(const void* x_src_dev, const void* z_dev, const void* noise_dev, void* out4_dev, float t, float one_minus_t, int64_t n_half,
+                       int32_t dtype, void* stream);
+int lt_op_flowedit_combine(const void* z_dev, const void* out4_dev, void* z_next_dev, float w_s, float w_t, float dt, int32_t Bp, int32_t C, int32_t HW,
+                           int32_t ch, int32_t dtype, void* stream);
 /* y[m,n] = sum_k act(a[m,k]) w[n,k] + b[n], m < M <= 8 (GEMV-style; adaLN / embedders).
  * act_in 0 none, 1 SiLU.  a bf16 [M,K], w bf16 [N,K], b bf16 [N] or NULL, y bf16 [M,N]. */
 int lt_op_linear_small_m(const void* a_dev, const void* w_dev, const void* b_dev, void* y_dev,

@@ -128,6 +128,9 @@ _SIGNATURES: Dict[str, tuple] = {
     "lt_sample_ode_multistep_cfg_reuse": (_i32, [_vp, _vp, _vp, _vp, C.POINTER(_f32), _i32, C.POINTER(_f32), _i32, C.POINTER(_f32), C.POINTER(_i32),
                                                  _i32, C.POINTER(LtStepArgs), _vp]),
     "lt_forward_cfg_reuse": (_i32, [_vp, _vp, _vp, _vp, _i32, C.POINTER(LtStepArgs), _vp]),
+    "lt_sample_flowedit": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_f32), C.POINTER(_f32), _i32, C.POINTER(LtStepArgs), _vp]),
+    "lt_op_flowedit_mix": (_i32, [_vp, _vp, _vp, _vp, _f32, _f32, _i64, _i32, _vp]),
+    "lt_op_flowedit_combine": (_i32, [_vp, _vp, _vp, _f32, _f32, _f32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "lt_last_nfe": (_i64, [_vp]),
     "lt_last_eval_rows": (_i64, [_vp]),
     "lt_graph_replays": (_i64, [_vp]),

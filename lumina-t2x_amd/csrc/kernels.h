@@ -407,6 +407,14 @@ int launch_views_guided_gather(const void* y, const void* guidance, const void* 
 // 0 f32, 1 bf16; operands an op does not read may be null.  out is fp32 for LT_SDE_OP_LAST_MEAN / LAST_TWEEDIE, the state dtype otherwise
 int launch_sde_step(int op, const void* x, const void* v, const void* w, const void* k1, const void* xp, void* out, void* out2, const float* rec,
                     long long n, int dtype, hipStream_t stream);
+// prompt-driven editing (flowedit.hip; rounding points there), state dtype 0 f32, 1 bf16, n_half = B' C H W elements per row group
+//   mix: out4 [4 B', C, H, W] = [zs, zt, zs, zt] from the source x_src, the edit z (may be x_src) and the interval's noise, at t and omt = 1 - t
+//   combine: z_next = R(z + R(R(v_t - v_s) dt)) from the evaluation's rows out4 = [c_s, c_t, u_s, u_t], guided on the channels < ch at w_s / w_t;
+//   z_next may be z, not out4
+int launch_flowedit_mix(const void* x_src, const void* z, const void* noise, void* out4, float t, float omt, long long n_half, int dtype,
+                        hipStream_t stream);
+int launch_flowedit_combine(const void* z, const void* out4, void* z_next, float w_s, float w_t, float dt, int Bp, int C, int HW, int ch, int dtype,
+                            hipStream_t stream);
 // adaptive Runge-Kutta stepping (ode_adaptive.hip; rounding points there).  k: host array of nk device pointers (the slopes), coef: the nk
 // coefficients of the chain (host); state dtype 0 f32, 1 bf16; ws: LT_RK_WS_BYTES of device memory for the norm's partial sums; norm_out: one
 // device float; q_out (may be null) receives the quotients the norm is taken of

@@ -595,6 +595,16 @@ extern "C" int lt_op_sde_step(int32_t op, const void* x_dev, const void* v_dev, 
     return launch_sde_step(op, x_dev, v_dev, w_dev, k1_dev, xp_dev, out_dev, out2_dev, rec_host, (long long)n, dtype, (hipStream_t)stream);
 }
 
+// ---- prompt-driven editing (flowedit.hip) ---------------------------------------------------------------------------------------------
+extern "C" int lt_op_flowedit_mix(const void* x_src_dev, const void* z_dev, const void* noise_dev, void* out4_dev, float t, float one_minus_t,
+                                  int64_t n_half, int32_t dtype, void* stream) {
+    return launch_flowedit_mix(x_src_dev, z_dev, noise_dev, out4_dev, t, one_minus_t, (long long)n_half, dtype, (hipStream_t)stream);
+}
+extern "C" int lt_op_flowedit_combine(const void* z_dev, const void* out4_dev, void* z_next_dev, float w_s, float w_t, float dt, int32_t Bp, int32_t C,
+                                      int32_t HW, int32_t ch, int32_t dtype, void* stream) {
+    return launch_flowedit_combine(z_dev, out4_dev, z_next_dev, w_s, w_t, dt, Bp, C, HW, ch, dtype, (hipStream_t)stream);
+}
+
 // ---- adaptive Runge-Kutta stepping (ode_adaptive.hip) ---------------------------------------------------------------------------------
 extern "C" int lt_op_rk_stage(const void* y_dev, const void* const* k_ptrs_host, const float* coef_host, int32_t nk, float dt, void* out_dev,
                               int64_t n, int32_t dtype, void* stream) {

@@ -787,6 +787,62 @@ extern "C" int lt_sample_sde(lt_engine* e, const void* z_dev, const void* noise_
     return tr.finish(has_last ? nullptr : final_dev);
 }
 
+// ---- prompt-driven editing: FlowEdit's inversion-free rule (flowedit.hip; transport/edit.py: sample_flowedit is the definition) ----
+// a->batch = 4 B' rows per evaluation - source, target and their two negative prompts - around a state of B' rows; one plain forward per
+// interval, the guidance expression per branch in the combine kernel.  Everything is checked before the first copy
+extern "C" int lt_sample_flowedit(lt_engine* e, const void* z_dev, const void* x_src_dev, const void* noise_dev, void* traj_dev, void* final_dev,
+                                  const float* tgrid_host, const float* scales_host, int32_t n_grid, const lt_step_args* a, void* stream) {
+    const char* who = "lt_sample_flowedit";
+    LT_REQUIRE(e && z_dev && x_src_dev && noise_dev && tgrid_host && scales_host && a, "%s: null argument", who);
+    if (refuse_if_capturing((hipStream_t)stream, who)) return 2;  // (the stage times travel through a host staging buffer that the next call rewrites)
+    LtOptScope opt_scope(&e->opts);
+    LT_REQUIRE(n_grid >= 2, "%s: need at least 2 grid points", who);
+    LT_REQUIRE(a->batch >= 4 && a->batch % 4 == 0, "%s: batch %d is not a positive multiple of 4 (source, target and their two negative prompts per "
+               "image)", who, a->batch);
+    if (check_step_shape(e, who, a)) return 2;
+    const int C = e->cfg.in_channels;
+    LT_REQUIRE(a->cfg_channels >= 1 && a->cfg_channels <= C, "%s: cfg_channels %d outside 1..in_channels %d", who, a->cfg_channels, C);
+    for (int i = 0; i < n_grid; ++i) LT_REQUIRE(std::isfinite(tgrid_host[i]), "%s: grid value %d is not finite", who, i);
+    for (int i = 0; i < 2 * (n_grid - 1); ++i)
+        LT_REQUIRE(std::isfinite(scales_host[i]), "%s: the %s scale of interval %d is not finite", who, i % 2 ? "target" : "source", i / 2);
+    LT_REQUIRE(e->reg_Y == 0, "%s: a regional prompt is prepared (lt_prepare_prompt_regional): its captions belong to one cond and one uncond row, "
+               "not to the four rows of an edit", who);
+    LT_REQUIRE(e->prompt_B == a->batch, "%s: %s was called for batch %d, step has batch %d", who, e->v.labels ? "lt_prepare_labels" : "lt_prepare_prompt",
+               e->prompt_B, a->batch);
+    {  // the model's own refusal of this shape, before anything is copied (no partial result)
+        const int p = e->cfg.patch_size;
+        float unused;
+        if (softmax_scale_for(e, a, (a->latent_h / p) * (a->latent_w / p), &unused)) return 1;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const int B = a->batch, Bp = B / 4, HW = a->latent_h * a->latent_w, ncalls = n_grid - 1;
+    const long long n_half = (long long)Bp * C * HW;
+    const bool bf = a->io_dtype == LT_BF16;
+    const size_t sbytes = (size_t)n_half * (bf ? 2 : 4);
+    float* tp = e->times.begin(ncalls * B, s);
+    if (!tp) return 1;
+    // the stage time handed to the model is the fp32 grid value, as in lt_sample_views (torch.full((4 B',), float(tgrid[i])))
+    for (int i = 0; i < ncalls; ++i)
+        for (int b = 0; b < B; ++b) tp[(size_t)i * B + b] = tgrid_host[i];
+    if (e->times.commit(ncalls * B, s)) return 1;
+    Trajectory tr{e, a, 0, s, sbytes};
+    if (tr.start(z_dev, traj_dev, true)) return 1;
+    const int dt_code = bf ? 1 : 0;
+    for (int i = 0; i < ncalls; ++i) {
+        // t, 1 - t and dt are Python floats in the host loop (the fp32 grid's values as doubles, 1 - t and t1 - t0 formed in double) that enter
+        // torch's fp32 op-math
+        const double t0 = tgrid_host[i];
+        const float t = tgrid_host[i], omt = (float)(1.0 - t0), dt = (float)((double)tgrid_host[i + 1] - t0);
+        const void* w = (const char*)noise_dev + (size_t)i * sbytes;
+        if (launch_flowedit_mix(x_src_dev, tr.y0(), w, e->ymid, t, omt, n_half, dt_code, s)) return 1;
+        if (tr.eval(e->ymid, i, e->kbuf[0])) return 1;
+        if (launch_flowedit_combine(tr.y0(), e->kbuf[0], tr.y1(), scales_host[2 * i], scales_host[2 * i + 1], dt, Bp, C, HW, a->cfg_channels, dt_code, s))
+            return 1;
+        if (tr.advance(i + 1)) return 1;
+    }
+    return tr.finish(final_dev);
+}
+
 // ---- adaptive Runge-Kutta sampling (ode_adaptive.hip) ------------------------------------------------------------------------------
 namespace {
 

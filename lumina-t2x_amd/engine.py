@@ -731,6 +731,36 @@ class DiTEngine:
         _lib.check(rc, "lt_sample_sde")
         return traj, final
 
+    # ---- prompt-driven editing (FlowEdit) ---------------------------------------------------------------
+    def sample_flowedit(self, x_src: torch.Tensor, tgrid, noise: torch.Tensor, scales, *, z: Optional[torch.Tensor] = None,
+                        scale_factor: float = 1.0, scale_watershed: float = 1.0, base_seqlen: Optional[int] = None, proportional_attn: bool = False,
+                        ntk_factor: float = 1.0, cfg_channels: int = 3, return_trajectory: bool = True) -> torch.Tensor:
+        """FlowEdit's inversion-free edit in ONE call (lt_sample_flowedit; ``transport.edit.sample_flowedit`` is the definition): the source
+        ``x_src [B', C, H, W]``, the edit state ``z`` (default: ``x_src``), ``noise [len(tgrid) - 1, B', C, H, W]`` (the caller's draws) and the
+        fp32 table ``scales [len(tgrid) - 1, 2]`` of ``(w_s, w_t)`` pairs (``transport.edit.flowedit_scales``).  Needs the conditioning prepared
+        for 4 B' rows: source, target, negative source, negative target.  Returns ``[len(tgrid), B', C, H, W]`` or the last state."""
+        from .transport.edit import check_edit_operands, check_scales
+        _require_gpu(x_src, "x_src")
+        garr, n = _grid_array(tgrid)
+        if n < 2:
+            raise LuminaLibError("sample_flowedit: need at least 2 grid points")
+        try:
+            x_src, z, noise = check_edit_operands(x_src, z, noise, n - 1)
+            sc = check_scales(scales, n - 1)
+        except ValueError as exc:
+            raise LuminaLibError(f"sample_flowedit: {exc}") from None
+        x_src, z, noise = x_src.contiguous(), z.contiguous(), noise.contiguous()
+        a = self._step_args(x_src, 1.0, scale_factor, scale_watershed, base_seqlen, proportional_attn, cfg_channels=int(cfg_channels),
+                            ntk_factor=ntk_factor)
+        a.batch = 4 * x_src.shape[0]
+        out, traj_ptr, fin_ptr = _traj_or_final(x_src, n, x_src.shape, return_trajectory)
+        with torch.cuda.device(self.device):
+            rc = self.lib.lt_sample_flowedit(self.handle, C.c_void_p(z.data_ptr()), C.c_void_p(x_src.data_ptr()), C.c_void_p(noise.data_ptr()),
+                                             traj_ptr, fin_ptr, garr, C.cast(sc.data_ptr(), C.POINTER(C.c_float)), n, C.byref(a),
+                                             C.c_void_p(_stream_ptr(self.device)))
+        _lib.check(rc, "lt_sample_flowedit")
+        return out
+
     # ---- multi-view (visual-anagram) sampling -------------------------------------------------------------------
     def set_views(self, views, latent_h: int, latent_w: int) -> None:
         """upload the tables of a list of ``views.BaseView`` objects (or a ready ``(perm [V, h*w], vsign [V, C], isign [V, C])`` triple) for

@@ -150,6 +150,61 @@ class EngineSamplers:
                 layer.attention.base_seqlen = kw.get("base_seqlen") if kw["proportional_attn"] else None
                 layer.attention.proportional_attn = kw["proportional_attn"]
 
+    def _leave_step_flags(self, kw):
+        """the step flags of ``forward_with_cfg`` in ``kw`` -> what that call leaves on the module for the plain ``forward`` that follows:
+        the attention flags on every layer (``_mirror_attention_flags``) and the RoPE factors of the families that keep them.  Pops them;
+        returns ``scale_factor`` / ``scale_watershed`` of a family whose plain forward does not read them off the module (Next-DiT)."""
+        self._mirror_attention_flags(kw)
+        kw.pop("proportional_attn", None)
+        kw.pop("base_seqlen", None)
+        rs, ntk = kw.pop("rope_scaling_factor", None), kw.pop("ntk_factor", None)
+        if hasattr(self, "_rope"):  # the class-conditional families: both or neither (forward_with_cfg asserts it)
+            if rs is not None or ntk is not None:
+                assert rs is not None and ntk is not None
+                self._rope = (float(rs), float(ntk))
+        elif hasattr(self, "rope_scaling_factor"):  # Flag-DiT: each persists once overridden
+            self.rope_scaling_factor = rs if rs is not None else self.rope_scaling_factor
+            self.ntk_factor = ntk if ntk is not None else self.ntk_factor
+        elif rs is not None or ntk is not None:
+            raise TypeError(f"{type(self).__name__} takes no rope_scaling_factor / ntk_factor")
+        return {k: kw.pop(k) for k in ("scale_factor", "scale_watershed") if k in kw}
+
+    @torch.no_grad()
+    def sample_flowedit(self, x_src, tgrid, noise, *cond, src_cfg: float = 1.5, tgt_cfg: float = 5.5, z=None, return_trajectory: bool = False,
+                        cfg_channels: int = 3, **step_kw):
+        """Prompt-driven editing by FlowEdit's inversion-free rule in ONE engine call (lt_sample_flowedit, DESIGN 7l;
+        ``transport.edit.sample_flowedit`` around this model's plain ``forward`` is the definition).  ``x_src [B', C, H, W]``: the source latent;
+        ``z``: the edit state at ``tgrid[0]`` (default ``x_src``); ``noise [len(tgrid) - 1, B', C, H, W]``: one draw per interval;
+        ``cond``: the family's conditioning (``cap_feats, cap_mask`` or ``y``) for 4 B' rows ``[src_*, tgt_*, neg_src_*, neg_tgt_*]``;
+        ``src_cfg`` / ``tgt_cfg``: the guidance scale of each branch, a float or one per interval.  ``step_kw``: the step flags of
+        ``forward_with_cfg`` (``proportional_attn``, ``base_seqlen``, ``scale_factor``, ``scale_watershed``, ``rope_scaling_factor``, ``ntk_factor``),
+        left on the module as that call leaves them before the plain forward runs.  A state that is not on a ROCm device runs the host loop.
+        Returns the last state, or all ``len(tgrid)`` states."""
+        from ..transport import edit as E
+        if len(cond) > len(self._cond_names):
+            raise TypeError(f"sample_flowedit takes the conditioning {self._cond_names}, got {len(cond)} positional arguments")
+        kw = dict(zip(self._cond_names, cond), **step_kw)
+        cond_kw = {k: kw[k] for k in self._cond_names if k in kw}
+        n = len(E._grid32(tgrid)) - 1
+        scales = E.flowedit_scales(n, src_cfg, tgt_cfg)
+        x_src, z, noise = E.check_edit_operands(x_src, z, noise, n)
+        Bp = x_src.shape[0]
+        E.check_cond_rows(cond_kw, Bp)
+        override = self._leave_step_flags(kw)
+        if not x_src.is_cuda:
+            if override:
+                raise TypeError(f"sample_flowedit: {sorted(override)} reach the engine alone; the plain forward of the host loop takes none")
+            states = E.sample_flowedit(self.forward, x_src, tgrid, noise, scales, z=z, cfg_channels=cfg_channels, **cond_kw)
+            return states if return_trajectory else states[-1]
+        rows = torch.empty((E.ROWS * Bp,) + tuple(x_src.shape[1:]), dtype=x_src.dtype, device=x_src.device)  # the evaluation's shape
+        eng, args = self._engine_sampler_args(rows, False, kw)
+        args.pop("cfg_scale", None)
+        att = self.layers[0].attention if hasattr(self, "layers") and len(self.layers) and hasattr(self.layers[0], "attention") else None
+        if att is not None and hasattr(att, "proportional_attn") and "proportional_attn" not in args:  # what this family's plain forward passes on
+            args.update(proportional_attn=bool(att.proportional_attn), base_seqlen=att.base_seqlen)
+        args.update(override)
+        return eng.sample_flowedit(x_src, tgrid, noise, scales, z=z, cfg_channels=cfg_channels, return_trajectory=return_trajectory, **args)
+
     @torch.no_grad()
     def forward_with_cfg_rule(self, x, t, *cond, rescale: float = 0.0, norm_limit: float = math.inf, **step_kw):
         """``forward_with_cfg(x, t, <conditioning>, cfg_scale, **step_kw)`` under a rescale blend and / or a norm limit in ONE engine call
