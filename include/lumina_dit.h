@@ -464,6 +464,37 @@ int lt_forward_cfg_reuse(lt_engine* e, const void* x_dev, const float* t_dev, vo
 int lt_sample_flowedit(lt_engine* e, const void* z_dev, const void* x_src_dev, const void* noise_dev, void* traj_dev, void* final_dev,
                        const float* tgrid_host, const float* scales_host, int32_t n_grid, const lt_step_args* a, void* stream);
 
+/* Skip-layer guidance (transport/guidance.py: sample_cfg_slg is the definition).  An evaluation can leave out a set S of blocks,
+ * which are then the identity on the residual stream: nothing of them is launched, and the block before prepares its output for the next
+ * block that runs (the final layer, if none does).  skip_host: n_skip layer indices on the host, in any order.  The set belongs to the call:
+ * no entry point returns with one left behind, error returns included.  Refused by name, before anything is launched or written: an index
+ * outside 0 .. n_layers - 1, a repeated index, more indices than layers, a set that leaves no layer.
+ * lt_forward_skip: lt_forward with the blocks of S left out; n_skip == 0 IS lt_forward.  With a set the call is refused on a stream under
+ * capture.
+ * lt_forward_cfg_slg: ONE guided evaluation, ch = min(cfg_channels, in_channels), R = rounding to bf16, no contraction:
+ *   1. the first B' = batch / 2 rows of x are evaluated with S left out, on the first half of the conditioning (as the conditional-only stage
+ *      of lt_sample_ode_cfg_schedule evaluates them); the channels < ch of the bf16 result, k, go to an engine-owned buffer [B', ch, H, W];
+ *   2. all 2 B' rows are evaluated; with c, u a sample's cond and uncond word the channels < ch of both halves become
+ *        R(R(u + R(w R(c - u))) + R(s R(c - k)))         w = cfg_scale, s = slg_scale, both multiplying in fp32
+ *      and the other channels pass row by row.  At cfg_scale == 1 exactly the B' cond rows alone are evaluated, R(c + R(s R(c - k))), written to
+ *      rows b and b + B'; the other channels are the cond rows'.
+ *   slg_scale == 0: lt_forward_cfg at cfg_scale - its launches, its result (a->cfg_scale is ignored in every case).
+ * lt_sample_ode_cfg_slg: lt_sample_ode_cfg_schedule's arguments, behaviour and refusals plus one skip-layer scale per stage (slg_host) and
+ * the set.  A stage with s == 0 is the schedule call's stage, the half-row stage at w == 1 included; a stage with s != 0 is the two
+ * evaluations above.  lt_last_nfe counts the skip evaluation (stages + the count of s != 0), lt_last_eval_rows adds its B' rows.  A
+ * trajectory replays at most five HIP-graph keys (guided, conditional-only, skip, guided + slg, cond + slg) whatever the tables hold.  The
+ * buffer (max_batch / 2 * in_channels * max_tokens * patch^2 bf16) is allocated by the first call that needs it, before anything is launched.
+ * Not served: packed batches, regional prompts, views, inpainting, SDE, adaptive and multistep methods, a rescale / norm-limit rule, guidance
+ * reuse.  Refused by name with nothing written: everything lt_sample_ode_cfg_schedule refuses; the set's refusals; a null or non-finite
+ * slg_host / slg_scale; a regional prompt; conditioning prepared for another batch; a stream under capture. */
+int lt_forward_skip(lt_engine* e, const void* x_dev, const float* t_dev, void* out_dev, const lt_step_args* a, const int32_t* skip_host,
+                    int32_t n_skip, void* stream);
+int lt_forward_cfg_slg(lt_engine* e, const void* x_dev, const float* t_dev, void* out_dev, float cfg_scale, float slg_scale,
+                       const int32_t* skip_host, int32_t n_skip, const lt_step_args* a, void* stream);
+int lt_sample_ode_cfg_slg(lt_engine* e, const void* z_dev, void* traj_dev, void* final_dev, const float* tgrid_host, int32_t n_grid, int32_t method,
+                          const float* cfg_host, const float* slg_host, const int32_t* skip_host, int32_t n_skip, int32_t t_round_to_state_dtype,
+                          const lt_step_args* a, void* stream);
+
 /* number of model evaluations issued by the last lt_sample_ode /lt_sample_ode_packed / lt_sample_views / lt_sample_views_guided / lt_sample_sde / lt_sample_ode_adaptive call */
 int64_t lt_last_nfe(lt_engine* e);
 /* the rows those evaluations ran, summed: nfe * batch for every sampler but lt_sample_ode_cfg_schedule, whose conditional-only stages run half */

@@ -230,6 +230,15 @@ int lt_op_unpatchify_cfg_rule(const void* rows, int32_t ld, void* out, int32_t o
 int lt_op_unpatchify_cfg_reuse(const void* rows, int32_t ld, void* out, int32_t out_dtype, int32_t B, int32_t C, int32_t out_ch, int32_t H, int32_t W,
                                int32_t patch, const float* cfg_scale_dev, int32_t cfg_channels, int32_t wp_stride, void* delta_dev, int32_t mode,
                                void* stream);
+/* Skip-layer guidance (csrc/guidance_skip.hip), for tests/test_gpu_slg.py.  B counts the 2 B' rows of out; skip_dev: bf16
+ * [B', cfg_channels, H, W]; each scale is one float of device memory.  mode 0 (store): rows holds B' samples, the channels < cfg_channels are
+ * copied to skip_dev, out is not written (may be null).  mode 1 (guided): rows holds 2 B' samples; with c, u a sample's cond and uncond word
+ * and k the stored one the channels < cfg_channels of both halves become bf16(bf16(u + bf16(w bf16(c - u))) + bf16(s bf16(c - k))), the others
+ * pass row by row.  mode 2 (cond): rows holds B' samples; bf16(c + bf16(s bf16(c - k))), the others pass, sample b is written to rows b and
+ * b + B'.  Refused: a null argument the mode reads, an odd B, cfg_channels outside 1..C, a mode outside 0..2. */
+int lt_op_unpatchify_cfg_slg(const void* rows, int32_t ld, void* out, int32_t out_dtype, int32_t B, int32_t C, int32_t out_ch, int32_t H, int32_t W,
+                             int32_t patch, const float* cfg_scale_dev, const float* slg_scale_dev, int32_t cfg_channels, int32_t wp_stride,
+                             void* skip_dev, int32_t mode, void* stream);
 /* The ragged boundary kernels of a packed batch (csrc/packed.hip): one launch for all samples.  hw_host = [B][2] latent sizes (host); the
  * flat state holds sample b = [C, H_b, W_b] at element offset sum_{j<b} C H_j W_j; N = token rows per sample in the row buffers (>= the longest
  * sequence).  Each launching entry builds the table of the size list, stores it at tab_dev (5 * 64 ints of device memory) and runs its kernel.

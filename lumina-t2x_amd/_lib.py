@@ -131,6 +131,10 @@ _SIGNATURES: Dict[str, tuple] = {
     "lt_sample_flowedit": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_f32), C.POINTER(_f32), _i32, C.POINTER(LtStepArgs), _vp]),
     "lt_op_flowedit_mix": (_i32, [_vp, _vp, _vp, _vp, _f32, _f32, _i64, _i32, _vp]),
     "lt_op_flowedit_combine": (_i32, [_vp, _vp, _vp, _f32, _f32, _f32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "lt_forward_skip": (_i32, [_vp, _vp, _vp, _vp, C.POINTER(LtStepArgs), C.POINTER(_i32), _i32, _vp]),
+    "lt_forward_cfg_slg": (_i32, [_vp, _vp, _vp, _vp, _f32, _f32, C.POINTER(_i32), _i32, C.POINTER(LtStepArgs), _vp]),
+    "lt_sample_ode_cfg_slg": (_i32, [_vp, _vp, _vp, _vp, C.POINTER(_f32), _i32, _i32, C.POINTER(_f32), C.POINTER(_f32), C.POINTER(_i32), _i32, _i32,
+                                     C.POINTER(LtStepArgs), _vp]),
     "lt_last_nfe": (_i64, [_vp]),
     "lt_last_eval_rows": (_i64, [_vp]),
     "lt_graph_replays": (_i64, [_vp]),
@@ -196,6 +200,7 @@ _SIGNATURES: Dict[str, tuple] = {
     "lt_op_guidance_stats": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _vp, _vp]),
     "lt_op_unpatchify_cfg_rule": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "lt_op_unpatchify_cfg_reuse": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _vp, _i32, _vp]),
+    "lt_op_unpatchify_cfg_slg": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _i32, _vp]),
     "lt_op_unpatchify_cfg": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _i32, _vp]),
     "lt_op_packed_table": (_i32, [C.POINTER(_i32), _i32, _i32, _i32, C.POINTER(_i32), C.POINTER(_i64), C.POINTER(_i32)]),
     "lt_op_patchify_packed": (_i32, [_vp, _i32, _vp, C.POINTER(_i32), _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),

@@ -216,8 +216,8 @@ struct lt_engine {
     std::vector<GraphEntry> graphs;
     void *g_x = nullptr, *g_out = nullptr;
     float* g_t = nullptr;
-    // [3]: the guidance scale of an evaluation that reads it from device memory (lt_sample_ode_cfg_schedule), then the rescale blend and the
-    // norm limit of a guidance rule (lt_sample_ode_cfg_rule / lt_forward_cfg_rule)
+    // [4]: the guidance scale of an evaluation that reads it from device memory (lt_sample_ode_cfg_schedule), then the rescale blend and the
+    // norm limit of a guidance rule (lt_sample_ode_cfg_rule / lt_forward_cfg_rule), then the skip-layer scale
     float* g_cfg = nullptr;
     double* g_stats = nullptr;  // the rule's partial sums: max_batch / 2 samples x LT_GUIDANCE_SLICES x 4 (guidance_stats -> unpatchify_cfg_rule)
     // guidance reuse: d = bfr(cond - uncond) of the last refresh evaluation, bf16 [B', ch, H, W]; max_batch / 2 x in_channels x
@@ -225,6 +225,12 @@ struct lt_engine {
     // the pointer.  delta_sig: { B', H, W, ch } of what it holds, B' = 0: nothing; every lt_prepare_prompt* / lt_prepare_labels call zeroes it
     u16* g_delta = nullptr;
     int delta_sig[4] = {0, 0, 0, 0};
+    // skip-layer guidance: the guided channels of the last skip evaluation, bf16 [B', ch, H, W]; sized and allocated like g_delta
+    // (ensure_skip_buf).  Written and read inside one entry-point call only, so it carries no signature
+    u16* g_skip = nullptr;
+    // the layers THIS call's evaluation leaves out (ascending, distinct, inside 0 .. L-1, not all of them): an argument of the call that
+    // travels here to run_forward.  Only SkipScope writes it, and its destructor empties it on every exit path
+    std::vector<int32_t> skip;
     hipStream_t cap_stream = nullptr;
     long long graph_replays = 0;
     // profiling
@@ -255,12 +261,31 @@ int packed_call_begin(lt_engine* e, const char* who, const int32_t* hw_host, con
 // of its guided channels in e->g_delta; LT_EVAL_REUSE - the first a->batch / 2 rows are evaluated as cond_only evaluates them and the closing
 // kernel guides them with the stored difference, both halves of `out` written.  One more word of the key.  The caller has run ensure_delta
 // and answers for the difference being there
-enum { LT_EVAL_PLAIN = 0, LT_EVAL_STORE = 1, LT_EVAL_REUSE = 2 };
+// skip-layer guidance (with cfg_dev, without cond_only and rule), the three modes of unpatchify_cfg_slg_kernel:
+// LT_EVAL_SLG_STORE - the first a->batch / 2 rows are evaluated as cond_only evaluates them (the caller holds a SkipScope) and their guided
+// channels go to e->g_skip, `out` is not written (may be null); LT_EVAL_SLG_GUIDED - all rows, the closing kernel adds s (cond - skip) with s
+// from e->g_cfg[3]; LT_EVAL_SLG_COND - the cond rows alone, cond + s (cond - skip), both halves of `out` written.  The caller has run
+// ensure_skip_buf and has put s in place
+enum { LT_EVAL_PLAIN = 0, LT_EVAL_STORE = 1, LT_EVAL_REUSE = 2, LT_EVAL_SLG_STORE = 3, LT_EVAL_SLG_GUIDED = 4, LT_EVAL_SLG_COND = 5 };
 int forward_graphed(lt_engine* e, const void* x_in, const float* t_dev, void* out, const lt_step_args* a, int use_cfg, hipStream_t s,
                     const PackedCall* pc = nullptr, const float* cfg_dev = nullptr, bool cond_only = false, bool rule = false,
                     int reuse = LT_EVAL_PLAIN);
 // the difference buffer of guidance reuse: allocated on the first call, before anything is launched (engine.hip)
 int ensure_delta(lt_engine* e);
+// ... and the skip buffer of skip-layer guidance (engine.hip)
+int ensure_skip_buf(lt_engine* e);
+// The layer set of one call.  set() refuses by name - an index outside 0 .. L-1, a repeated index, more indices than L, a set that
+// leaves no layer - and otherwise stores the set in ascending order; the destructor empties it, so no entry point returns with a set left behind
+struct SkipScope {
+    lt_engine* e;
+    explicit SkipScope(lt_engine* eng) : e(eng) {}
+    SkipScope(const SkipScope&) = delete;
+    SkipScope& operator=(const SkipScope&) = delete;
+    ~SkipScope() { e->skip.clear(); }
+    int set(const char* who, const int32_t* skip_host, int n_skip);
+};
+// the refusals of SkipScope::set alone (nothing stored)
+int check_skip_set(const lt_engine* e, const char* who, const int32_t* skip_host, int n_skip);
 // true while stream s records into a graph (the caller's torch.cuda.graph / hipStreamBeginCapture, or the engine's own cache)
 bool stream_capturing(hipStream_t s);
 // the entry points that allocate, synchronise or copy from host memory cannot be recorded into a caller's graph: non-zero after

@@ -408,9 +408,12 @@ int ensure_weight_layout(lt_engine* e, bool want, hipStream_t s, bool recording 
 // closing kernel that multiplies by the per-sample factor
 // reuse: LT_EVAL_STORE - the guided evaluation's closing kernel also stores the difference; LT_EVAL_REUSE - a->batch rows on the
 // first half of the conditioning like dup, closed by the kernel that guides them with the stored difference
+// skip-layer guidance: LT_EVAL_SLG_STORE / _COND - a->batch rows on the first half of the conditioning like dup, LT_EVAL_SLG_GUIDED -
+// all rows; closed by unpatchify_cfg_slg_kernel in its three modes, the skip-layer scale behind the rule's words (scale[3])
 struct CfgFromDev {
     const float* scale; bool dup; const float* rule = nullptr; int reuse = LT_EVAL_PLAIN;
-    bool half() const { return dup || reuse == LT_EVAL_REUSE; }  // the evaluation has half the rows its output has
+    // the evaluation has half the rows its output has
+    bool half() const { return dup || reuse == LT_EVAL_REUSE || reuse == LT_EVAL_SLG_STORE || reuse == LT_EVAL_SLG_COND; }
 };
 
 int run_forward(lt_engine* e, const void* x_in, const float* t_dev, void* out, const lt_step_args* a, int use_cfg,
@@ -452,6 +455,7 @@ int run_forward(lt_engine* e, const void* x_in, const float* t_dev, void* out, c
     LT_REQUIRE(e->prompt_B == B || (gs && gs->half() && !pk && e->prompt_B == 2 * B), "%s was called for batch %d, step has batch %d",
                v.labels ? "lt_prepare_labels" : "lt_prepare_prompt", e->prompt_B, gs && gs->half() ? 2 * B : B);
     LT_REQUIRE(e->reg_Y == 0 || (B == 2 && !pk), "regional captions: one image per call (batch 2 = cond + uncond row), tensor input");
+    LT_REQUIRE(e->skip.empty() || (!pk && (int)e->skip.size() < e->L), "layer skip: a tensor input and a set that leaves a layer (SkipScope::set)");
     if (!e->weights_ok && lt_weights_ready(e)) return 2;
     const int d = e->d, L = e->L, H = e->H, Hkv = e->Hkv, hd = e->hd, F = e->F, dkv = e->dkv, A = e->A;
     const int Npad = round_up(N, 64);
@@ -601,18 +605,26 @@ int run_forward(lt_engine* e, const void* x_in, const float* t_dev, void* out, c
     if (e->layout_pinned) { pair = false; pair_moe = false; }
     if (ensure_weight_layout(e, pair || pair_moe, s, caller_cap)) return 1;
     e->last_pair = pair || pair_moe;
+    // layer skip: the blocks in e->skip (ascending; a SkipScope of the entry point stored it, checked) are the identity on e->x -
+    // they launch nothing, and whoever prepares h prepares it for nx(l), the next layer that runs (L: none does, the final layer's form).
+    // Empty set: nx(l) = l + 1, first = 0 - the launches of always.  (The lw[0] probes above ask about shapes, which all layers share.)
+    const std::vector<int32_t>& skip = e->skip;
+    auto skipped = [&](int l) { return std::binary_search(skip.begin(), skip.end(), l); };
+    auto nx = [&](int l) { int n = l + 1; while (n < L && skipped(n)) ++n; return n; };
+    const int first = nx(-1);  // (< L: the set is distinct and shorter than L, checked before the first launch)
     // first pre-norm: modulate(attention_norm(x), [shift,] scale) (model.py:599 / models.py:785 / lumina_t2i model.py:600)
     {
         ProfScope ps(e, 2, 0, s);
         NormModArgs n;
-        n.x = e->x; n.w = v.pre_w ? e->lw[0].attn_norm1 : nullptr; n.scale = chunk(0, v.i_scale[0]); n.shift = chunk(0, v.i_shift[0]);
+        n.x = e->x; n.w = v.pre_w ? e->lw[first].attn_norm1 : nullptr; n.scale = chunk(first, v.i_scale[0]); n.shift = chunk(first, v.i_shift[0]);
         n.out = e->h; n.rows = M; n.rows_per_batch = N; n.d = d; n.ld_mod = e->ld_mod; n.eps = c.norm_eps; n.scale_pre = 1;
         n.out_pair = pair;
         if (launch_rmsnorm_mod(n, s)) return 1;
     }
     const int post_mode = v.post ? 1 : 0, gate_mode = 0;  // gates arrive ready (tanh applied above where the family has it)
-    for (int l = 0; l < L; ++l) {
+    for (int l = first; l < L; l = nx(l)) {
         LayerW& w = e->lw[l];
+        const int nl = nx(l);  // the layer h is prepared for at this block's end
         // V^T epilogue path: q | k columns in one GEMM, the V columns in a second one that writes e->vt directly.  Large problems
         // only (a second launch of a latency-bound 512-row GEMM costs more than the transpose), whole 64-key tiles per sample
         // (no key padding to zero); packed batches: when the attention masks their pad rows' keys itself (pk_one_wave above), else the
@@ -787,16 +799,16 @@ int run_forward(lt_engine* e, const void* x_in, const float* t_dev, void* out, c
             if (e->E != 0) moe_y(e, g, e->moe_mode == 1 ? l : -1);
             g.post_mode = post_mode; g.gate_mode = gate_mode; g.h = e->h;
             g.rows = M; g.rows_per_batch = N; g.d = d; g.ld_mod = e->ld_mod; g.eps = c.norm_eps; g.eps_next = 1e-6f; g.scale_pre = 1;
-            if (l + 1 < L) {
-                g.next_w = v.pre_w ? e->lw[l + 1].attn_norm1 : nullptr; g.next_scale = chunk(l + 1, v.i_scale[0]);
-                g.next_shift = chunk(l + 1, v.i_shift[0]); g.next_mode = 1; g.h_pair = pair;
+            if (nl < L) {
+                g.next_w = v.pre_w ? e->lw[nl].attn_norm1 : nullptr; g.next_scale = chunk(nl, v.i_scale[0]);
+                g.next_shift = chunk(nl, v.i_shift[0]); g.next_mode = 1; g.h_pair = pair;
             } else {  // final layer: LayerNorm(no affine, 1e-6) * (1 + scale) [+ shift] (model.py:657-661 / models.py:829-832)
                 const u16* fin = e->mod + (size_t)L * cd;
                 g.next_w = nullptr; g.next_mode = 2;
                 g.next_shift = v.final_chunks == 2 ? fin : nullptr;
                 g.next_scale = v.final_chunks == 2 ? fin + d : fin;
             }
-            if (l + 1 < L) prefetch_rider(e, &g.pf, e->h, d, e->lw[l + 1].wqkv, d, e->qkv, e->qkvn, M, e->qkvn, d, 0);
+            if (nl < L) prefetch_rider(e, &g.pf, e->h, d, e->lw[nl].wqkv, d, e->qkv, e->qkvn, M, e->qkvn, d, 0);
             if (launch_gated_residual_norm(g, s)) return 1;
         }
     }
@@ -809,6 +821,10 @@ int run_forward(lt_engine* e, const void* x_in, const float* t_dev, void* out, c
             if (launch_guidance_stats(e->frows, e->nfinal, B, c.out_channels, a->latent_h, a->latent_w, p, gs->scale, rule_ch, Wrow, e->g_stats, s)) return 1;
             if (launch_unpatchify_cfg_rule(e->frows, e->nfinal, out, a->io_dtype, B, c.in_channels, c.out_channels, a->latent_h, a->latent_w, p,
                                            use_cfg, gs->scale, rule_ch, Wrow, 0, e->g_stats, gs->rule, gs->rule + 1, nullptr, s)) return 1;
+        } else if (!pk && gs && gs->reuse >= LT_EVAL_SLG_STORE) {  // skip-layer guidance (B: the rows evaluated; the kernel counts output rows)
+            if (launch_unpatchify_cfg_slg(e->frows, e->nfinal, out, a->io_dtype, gs->half() ? 2 * B : B, c.in_channels, c.out_channels, a->latent_h,
+                                          a->latent_w, p, gs->scale, gs->scale + 3, cfg_ch < c.in_channels ? cfg_ch : c.in_channels, Wrow, e->g_skip,
+                                          gs->reuse - LT_EVAL_SLG_STORE, s)) return 1;
         } else if (!pk && gs && gs->reuse != LT_EVAL_PLAIN) {  // (B: the rows evaluated - 2 B' storing, B' reusing; the kernel counts output rows)
             const bool again = gs->reuse == LT_EVAL_REUSE;
             if (launch_unpatchify_cfg_reuse(e->frows, e->nfinal, out, a->io_dtype, again ? 2 * B : B, c.in_channels, c.out_channels, a->latent_h,
@@ -864,14 +880,38 @@ int refuse_if_capturing(hipStream_t s, const char* who) {
     return 0;
 }
 
-int ensure_delta(lt_engine* e) {
-    if (e->g_delta) return 0;
+// a bf16 buffer [max_batch / 2, in_channels, max_tokens patch^2] the closing kernels of guidance reuse / skip-layer guidance keep between two
+// evaluations: allocated by the first call that needs it and kept for the engine's life (captured graphs hold the pointer)
+static int ensure_half_state(lt_engine* e, u16** buf, const char* what) {
+    if (*buf) return 0;
     const lt_config& c = e->cfg;
     const size_t words = (size_t)(c.max_batch / 2) * c.in_channels * c.max_tokens * c.patch_size * c.patch_size;
-    LT_REQUIRE(words > 0, "guidance reuse: an engine of max_batch %d holds no cond + uncond pair", c.max_batch);
+    LT_REQUIRE(words > 0, "%s: an engine of max_batch %d holds no cond + uncond pair", what, c.max_batch);
     void* q = nullptr;
-    if (dev_alloc(e, &q, words * sizeof(u16), false)) return 1;  // (never read before a refresh evaluation wrote it: delta_sig)
-    e->g_delta = (u16*)q;
+    if (dev_alloc(e, &q, words * sizeof(u16), false)) return 1;  // (never read before an evaluation of the same call wrote it)
+    *buf = (u16*)q;
+    return 0;
+}
+
+int ensure_delta(lt_engine* e) { return ensure_half_state(e, &e->g_delta, "guidance reuse"); }
+int ensure_skip_buf(lt_engine* e) { return ensure_half_state(e, &e->g_skip, "skip-layer guidance"); }
+
+int check_skip_set(const lt_engine* e, const char* who, const int32_t* skip_host, int n_skip) {
+    LT_REQUIRE(n_skip >= 0, "%s: n_skip %d is negative", who, n_skip);
+    LT_REQUIRE(n_skip == 0 || skip_host, "%s: null argument (skip_host: %d layer indices)", who, n_skip);
+    LT_REQUIRE(n_skip <= e->L, "%s: %d skip indices, the model has %d layers", who, n_skip, e->L);
+    for (int i = 0; i < n_skip; ++i) {
+        LT_REQUIRE(skip_host[i] >= 0 && skip_host[i] < e->L, "%s: skip index %d (entry %d) is outside 0..%d", who, skip_host[i], i, e->L - 1);
+        for (int j = 0; j < i; ++j) LT_REQUIRE(skip_host[j] != skip_host[i], "%s: skip index %d is repeated (entries %d and %d)", who, skip_host[i], j, i);
+    }
+    LT_REQUIRE(n_skip < e->L, "%s: the skip set leaves no layer (all %d are in it)", who, e->L);
+    return 0;
+}
+
+int SkipScope::set(const char* who, const int32_t* skip_host, int n_skip) {
+    if (check_skip_set(e, who, skip_host, n_skip)) return 2;
+    e->skip.assign(skip_host, skip_host + n_skip);
+    std::sort(e->skip.begin(), e->skip.end());
     return 0;
 }
 
@@ -913,7 +953,11 @@ int forward_graphed(lt_engine* e, const void* x_in, const float* t_dev, void* ou
     const CfgFromDev cfd{e->g_cfg, cond_only, rule && !cond_only ? e->g_cfg + 1 : nullptr, reuse};
     const CfgFromDev* cd = nullptr;
     const bool half = cfd.half();  // B' rows evaluated, 2 B' written
-    if (reuse != LT_EVAL_PLAIN)
+    if (reuse >= LT_EVAL_SLG_STORE)
+        LT_REQUIRE(reuse <= LT_EVAL_SLG_COND && cfg_dev && !cond_only && !rule && e->g_skip && (e->skip.empty() || reuse == LT_EVAL_SLG_STORE),
+                   "skip-layer guidance: an evaluation of its three kinds reads its scales from device memory, runs without a rule, finds the "
+                   "buffer allocated, and only the skip evaluation leaves layers out");
+    else if (reuse != LT_EVAL_PLAIN)
         LT_REQUIRE(cfg_dev && !cond_only && !rule && e->g_delta, "guidance reuse: an evaluation that stores or reuses the difference reads its scale "
                    "from device memory, runs without a rule, and finds the buffer allocated");
     if (cfg_dev) {
@@ -963,6 +1007,11 @@ int forward_graphed(lt_engine* e, const void* x_in, const float* t_dev, void* ou
     memcpy(key.data(), a, sizeof(lt_step_args));
     memcpy(key.data() + sizeof(lt_step_args), extra, sizeof(extra));
     if (pc) key.insert(key.end(), (const char*)pc->hw, (const char*)(pc->hw + 2 * B));  // the size list: grids and the table's contents depend on it
+    if (!e->skip.empty()) {  // the layers left out: another launch sequence.  Behind a -1 no size list holds; empty: the key of always
+        const int32_t mark[2] = {-1, (int32_t)e->skip.size()};
+        key.insert(key.end(), (const char*)mark, (const char*)(mark + 2));
+        key.insert(key.end(), (const char*)e->skip.data(), (const char*)(e->skip.data() + e->skip.size()));
+    }
     lt_engine::GraphEntry* ge = nullptr;
     for (auto& g : e->graphs) if (g.key == key) { ge = &g; break; }
     if (!ge) {
@@ -1015,7 +1064,8 @@ int forward_graphed(lt_engine* e, const void* x_in, const float* t_dev, void* ou
     LT_CHECK_HIP(hipMemcpyAsync(e->g_t, t_dev, (size_t)B * sizeof(float), hipMemcpyDeviceToDevice, s));
     LT_CHECK_HIP(hipGraphLaunch(ge->exec, s));
     e->last_pair = ge->pair;  // (a replay is an evaluation too: "last_pair" of lt_engine_get_option names the regime of the last one)
-    LT_CHECK_HIP(hipMemcpyAsync(out, e->g_out, half ? 2 * sbytes : sbytes, hipMemcpyDeviceToDevice, s));
+    if (reuse != LT_EVAL_SLG_STORE)  // (the skip evaluation's closing kernel writes e->g_skip and nothing else)
+        LT_CHECK_HIP(hipMemcpyAsync(out, e->g_out, half ? 2 * sbytes : sbytes, hipMemcpyDeviceToDevice, s));
     ++e->graph_replays;
     if (e->prof_on)
         for (int k = 0; k < 3; ++k)
@@ -1227,7 +1277,7 @@ extern "C" int lt_create(const lt_config* cfg, lt_engine** out) {
             void* q;
             if (dev_alloc(e, &q, Bm * sizeof(float))) return fail();
             e->g_t = (float*)q;
-            if (dev_alloc(e, &q, 3 * sizeof(float))) return fail();  // (the scale; the rescale blend and the norm limit of a rule)
+            if (dev_alloc(e, &q, 4 * sizeof(float))) return fail();  // (the scale; the rescale blend and the norm limit of a rule; the skip-layer scale)
             e->g_cfg = (float*)q;
             if (dev_alloc(e, &q, (size_t)((cfg->max_batch + 1) / 2) * LT_GUIDANCE_SLICES * 4 * sizeof(double))) return fail();
             e->g_stats = (double*)q;
@@ -1406,6 +1456,18 @@ extern "C" int lt_prepare_labels(lt_engine* e, const int32_t* labels_dev, int32_
 
 extern "C" int lt_forward(lt_engine* e, const void* x_dev, const float* t_dev, void* out_dev, const lt_step_args* a, void* stream) {
     LT_REQUIRE(e && x_dev && t_dev && out_dev && a, "lt_forward: null argument");
+    LtOptScope opt_scope(&e->opts);
+    return forward_graphed(e, x_dev, t_dev, out_dev, a, 0, (hipStream_t)stream);
+}
+
+// lt_forward with the blocks of a layer set left out.  Empty set: lt_forward, capturable as it is; with a set the call is refused
+// on a stream under capture (a recorded evaluation of this kind has no test behind it)
+extern "C" int lt_forward_skip(lt_engine* e, const void* x_dev, const float* t_dev, void* out_dev, const lt_step_args* a, const int32_t* skip_host,
+                               int32_t n_skip, void* stream) {
+    LT_REQUIRE(e && x_dev && t_dev && out_dev && a, "lt_forward_skip: null argument");
+    SkipScope scope(e);
+    if (scope.set("lt_forward_skip", skip_host, n_skip)) return 2;
+    if (n_skip > 0 && refuse_if_capturing((hipStream_t)stream, "lt_forward_skip")) return 2;
     LtOptScope opt_scope(&e->opts);
     return forward_graphed(e, x_dev, t_dev, out_dev, a, 0, (hipStream_t)stream);
 }

@@ -375,6 +375,15 @@ int launch_guidance_params_store(float* dst, float scale, float rescale, float l
 // modified), the others pass, and each row is written to rows b and b + B' of the output
 int launch_unpatchify_cfg_reuse(const u16* rows, int ld, void* out, int out_dtype, int B, int C, int out_ch, int H, int W, int patch,
                                 const float* cfg_scale_dev, int cfg_channels, int wp_stride, u16* delta, int mode, hipStream_t stream);
+// skip-layer guidance (guidance_skip.hip).  B counts the 2 B' OUTPUT rows; skip: bf16 [B', cfg_channels, H, W]; both scales are read
+// from device memory.  mode 0: `rows` holds the B' rows of the skip evaluation, their guided channels are stored, `out` (may be null) is not
+// written; mode 1: `rows` holds 2 B' rows, the guided channels of both halves become bfr(bfr(u + bfr(w bfr(c - u))) + bfr(s bfr(c - k))), the
+// others pass row by row; mode 2: `rows` holds the B' cond rows, bfr(c + bfr(s bfr(c - k))), each row written to rows b and b + B'
+int launch_unpatchify_cfg_slg(const u16* rows, int ld, void* out, int out_dtype, int B, int C, int out_ch, int H, int W, int patch,
+                              const float* cfg_scale_dev, const float* slg_scale_dev, int cfg_channels, int wp_stride, u16* skip, int mode,
+                              hipStream_t stream);
+// g_cfg[0] = cfg_scale, g_cfg[3] = slg_scale (the engine's four scale words, engine.h)
+int launch_slg_params_store(float* g_cfg, float cfg_scale, float slg_scale, hipStream_t stream);
 // torchdiffeq fixed-grid state arithmetic (modes documented in misc.hip)
 int launch_ode_combine(int mode, const void* y0, const void* k1, const void* k2, const void* k3, const void* k4,
                        void* out, int dtype, float dt, long long n, hipStream_t stream);

@@ -693,6 +693,12 @@ extern "C" int lt_op_unpatchify_cfg_reuse(const void* rows, int32_t ld, void* ou
     return launch_unpatchify_cfg_reuse((const u16*)rows, ld, out, out_dtype, B, C, out_ch, H, W, patch, cfg_scale_dev, cfg_channels, wp_stride,
                                        (u16*)delta_dev, mode, (hipStream_t)stream);
 }
+extern "C" int lt_op_unpatchify_cfg_slg(const void* rows, int32_t ld, void* out, int32_t out_dtype, int32_t B, int32_t C, int32_t out_ch, int32_t H,
+                                        int32_t W, int32_t patch, const float* cfg_scale_dev, const float* slg_scale_dev, int32_t cfg_channels,
+                                        int32_t wp_stride, void* skip_dev, int32_t mode, void* stream) {
+    return launch_unpatchify_cfg_slg((const u16*)rows, ld, out, out_dtype, B, C, out_ch, H, W, patch, cfg_scale_dev, slg_scale_dev, cfg_channels,
+                                     wp_stride, (u16*)skip_dev, mode, (hipStream_t)stream);
+}
 extern "C" int lt_op_region_text_combine(void* out, const void* txt, const void* gate, int32_t Y, int32_t N, int32_t H, int32_t hd, int32_t Hp,
                                          int32_t Wp, int32_t h_split, int32_t w_split, void* stream) {
     return launch_region_text_combine((u16*)out, (const u16*)txt, (const u16*)gate, Y, N, H, hd, Hp, Wp, h_split, w_split, (hipStream_t)stream);

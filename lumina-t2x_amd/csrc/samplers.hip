@@ -43,6 +43,11 @@ struct Trajectory {
     bool cfg_rule = false;  // ... under a rescale / norm-limit rule (lt_sample_ode_cfg_rule): its parameters are in e->g_cfg[1..2]
     // guidance reuse (lt_sample_ode_cfg_reuse): the flag of evaluation number `call` - 0 take and store the cond - uncond difference, 1 reuse it
     const int32_t* reuse_host = nullptr;
+    // skip-layer guidance (lt_sample_ode_cfg_slg): the scale s of evaluation number `call`, on the host and where commit sent it, and the
+    // layer set of the skip evaluations (checked by the entry point)
+    const float *slg_host = nullptr, *slg_dev = nullptr;
+    const int32_t* skip_host = nullptr;
+    int n_skip = 0;
     int start(const void* z, void* traj_dev, bool z_in_slot0) {
         traj = traj_dev;
         flips0 = e->layout_flips_total;
@@ -60,8 +65,24 @@ struct Trajectory {
         // scale 1 exactly: the guided output is the conditional one - the cond rows alone, written to both halves
         const bool cond_only = cfg_host[call] == 1.0f;
         if (reuse_host && !cond_only) return eval_reuse(y, t, call, out);
+        if (slg_host && slg_host[call] != 0.0f) return eval_slg(y, t, call, out, cond_only);
         rows += cond_only ? a->batch / 2 : a->batch;
         return forward_graphed(e, y, t, out, a, 1, s, nullptr, cfg_dev + call, cond_only, cfg_rule);
+    }
+    // a stage of skip-layer guidance with s != 0: the cond rows with the set's blocks left out, their guided channels kept; then
+    // the stage's own evaluation - all rows, or the cond rows at scale 1 - whose closing kernel adds s (cond - skip).  Two evaluations
+    int eval_slg(const void* y, const float* t, int call, void* out, bool cond_only) {
+        ++nfe;
+        rows += a->batch / 2;
+        {
+            SkipScope scope(e);
+            if (scope.set("skip-layer guidance", skip_host, n_skip)) return 2;
+            if (int rc = forward_graphed(e, y, t, nullptr, a, 1, s, nullptr, e->g_cfg, false, false, LT_EVAL_SLG_STORE)) return rc;
+        }
+        LT_CHECK_HIP(hipMemcpyAsync(e->g_cfg + 3, slg_dev + call, sizeof(float), hipMemcpyDeviceToDevice, s));
+        rows += cond_only ? a->batch / 2 : a->batch;
+        return forward_graphed(e, y, t, out, a, 1, s, nullptr, cond_only ? e->g_cfg : cfg_dev + call, false, false,
+                               cond_only ? LT_EVAL_SLG_COND : LT_EVAL_SLG_GUIDED);
     }
     // a guided evaluation of a reuse table: all rows and the difference stored, or the cond rows and the stored difference (the caller has
     // checked that a refresh comes first and has run ensure_delta)
@@ -110,7 +131,9 @@ float bf16_round_host(float f) {
 // cs->rule (lt_sample_ode_cfg_rule): the rescale blend and the norm limit travel behind the scales and are put into e->g_cfg[1..2] once.
 struct MaskedBlend { const void *mask, *x1, *noise; };
 // host: (n_grid - 1) * stages scales; { rescale, norm limit } or null; the reuse flags of lt_sample_ode_cfg_reuse, one per scale, or null
-struct CfgSchedule { const float* table; const float* rule = nullptr; const int32_t* reuse = nullptr; };
+// ... ; skip-layer guidance (lt_sample_ode_cfg_slg): one scale s per scale w and the layer set, or null
+struct SlgCall { const float* table; const int32_t* skip; int n_skip; };
+struct CfgSchedule { const float* table; const float* rule = nullptr; const int32_t* reuse = nullptr; const SlgCall* slg = nullptr; };
 
 int ode_fixed_grid(lt_engine* e, const void* z_dev, void* traj_dev, void* final_dev, const float* tgrid_host, int n_grid, int method, int use_cfg,
                    int t_round, const lt_step_args* a, hipStream_t s, long long n, const PackedCall* pc, const MaskedBlend* mb = nullptr,
@@ -121,7 +144,7 @@ int ode_fixed_grid(lt_engine* e, const void* z_dev, void* traj_dev, void* final_
     const bool bf = a->io_dtype == LT_BF16;
     // stage times; torchdiffeq's _PerturbFunc casts t to the state dtype before calling the model, then
     // integrators.py:108 broadcasts it to an fp32 [B] vector
-    const int nsent = ncalls * B + (cs ? ncalls : 0) + (cs && cs->rule ? 2 : 0);
+    const int nsent = ncalls * B + (cs ? ncalls : 0) + (cs && cs->rule ? 2 : 0) + (cs && cs->slg ? ncalls : 0);  // (a rule and slg never meet)
     float* tp = e->times.begin(nsent, s);
     if (!tp) return 1;
     std::vector<float> dts(n_grid - 1);
@@ -140,12 +163,17 @@ int ode_fixed_grid(lt_engine* e, const void* z_dev, void* traj_dev, void* final_
     }
     if (cs) memcpy(tp + (size_t)ncalls * B, cs->table, (size_t)ncalls * sizeof(float));
     if (cs && cs->rule) memcpy(tp + (size_t)ncalls * B + ncalls, cs->rule, 2 * sizeof(float));
+    if (cs && cs->slg) memcpy(tp + (size_t)ncalls * B + ncalls, cs->slg->table, (size_t)ncalls * sizeof(float));
     if (e->times.commit(nsent, s)) return 1;
     if (cs && cs->rule)
         LT_CHECK_HIP(hipMemcpyAsync(e->g_cfg + 1, e->times.dev + (size_t)ncalls * B + ncalls, 2 * sizeof(float), hipMemcpyDeviceToDevice, s));
     Trajectory tr{e, a, use_cfg, s, (size_t)n * (bf ? 2 : 4)};
     tr.pc = pc;
     if (cs) { tr.cfg_host = cs->table; tr.cfg_dev = e->times.dev + (size_t)ncalls * B; tr.cfg_rule = cs->rule != nullptr; tr.reuse_host = cs->reuse; }
+    if (cs && cs->slg) {
+        tr.slg_host = cs->slg->table; tr.slg_dev = e->times.dev + (size_t)ncalls * B + ncalls;
+        tr.skip_host = cs->slg->skip; tr.n_skip = cs->slg->n_skip;
+    }
     if (tr.start(z_dev, traj_dev, true)) return 1;
     const int dt_code = bf ? 1 : 0;
     for (int i = 0; i + 1 < n_grid; ++i) {
@@ -301,9 +329,10 @@ int check_reuse_flags(const char* who, const float* cfg_host, const int32_t* reu
 // lt_sample_ode_cfg_schedule, with `rule` = { rescale, norm limit } lt_sample_ode_cfg_rule, with `reuse_call` lt_sample_ode_cfg_reuse
 int sample_cfg_table(lt_engine* e, const char* who, const void* z_dev, void* traj_dev, void* final_dev, const float* tgrid_host, int n_grid, int method,
                      const float* cfg_host, const float* rule, int t_round, const lt_step_args* a, hipStream_t s, const int32_t* reuse_host = nullptr,
-                     bool reuse_call = false) {
+                     bool reuse_call = false, const SlgCall* slg = nullptr) {
     LT_REQUIRE(e && z_dev && tgrid_host && cfg_host && a, "%s: null argument", who);
     LT_REQUIRE(!reuse_call || reuse_host, "%s: null argument (reuse_host: one int32 flag per stage)", who);
+    LT_REQUIRE(!slg || slg->table, "%s: null argument (slg_host: one skip-layer scale per stage)", who);
     if (refuse_if_capturing(s, who)) return 2;  // (the stage times travel through a host staging buffer that the next call rewrites)
     LtOptScope opt_scope(&e->opts);
     LT_REQUIRE(n_grid >= 2, "%s: need at least 2 grid points", who);
@@ -313,8 +342,14 @@ int sample_cfg_table(lt_engine* e, const char* who, const void* z_dev, void* tra
     if (check_guided_table(e, who, a, cfg_host, n_grid - 1, stages, rule)) return 2;
     if (reuse_call && check_reuse_flags(who, cfg_host, reuse_host, (n_grid - 1) * stages)) return 2;
     if (reuse_call && ensure_delta(e)) return 1;
+    if (slg) {
+        for (int i = 0; i < (n_grid - 1) * stages; ++i)
+            LT_REQUIRE(std::isfinite(slg->table[i]), "%s: the skip-layer scale of stage %d of interval %d is not finite", who, i % stages, i / stages);
+        if (check_skip_set(e, who, slg->skip, slg->n_skip)) return 2;
+        if (ensure_skip_buf(e)) return 1;
+    }
     const long long n = (long long)a->batch * e->cfg.in_channels * a->latent_h * a->latent_w;
-    const CfgSchedule cs{cfg_host, rule, reuse_host};
+    const CfgSchedule cs{cfg_host, rule, reuse_host, slg};
     return ode_fixed_grid(e, z_dev, traj_dev, final_dev, tgrid_host, n_grid, method, 1, t_round, a, s, n, nullptr, nullptr, &cs);
 }
 
@@ -389,6 +424,43 @@ extern "C" int lt_forward_cfg_reuse(lt_engine* e, const void* x_dev, const float
         return rc;
     if (mode == 0) Trajectory::set_delta_sig(e, a);
     return 0;
+}
+
+// ---- skip-layer guidance: a third prediction with a set of blocks left out, pushed away from -----------------------------------
+extern "C" int lt_sample_ode_cfg_slg(lt_engine* e, const void* z_dev, void* traj_dev, void* final_dev, const float* tgrid_host, int32_t n_grid,
+                                     int32_t method, const float* cfg_host, const float* slg_host, const int32_t* skip_host, int32_t n_skip,
+                                     int32_t t_round, const lt_step_args* a, void* stream) {
+    const SlgCall slg{slg_host, skip_host, n_skip};
+    return sample_cfg_table(e, "lt_sample_ode_cfg_slg", z_dev, traj_dev, final_dev, tgrid_host, n_grid, method, cfg_host, nullptr, t_round, a,
+                            (hipStream_t)stream, nullptr, false, &slg);
+}
+
+// One guided evaluation at (cfg_scale, slg_scale): the skip evaluation of the cond rows, then all rows (the cond rows alone at cfg_scale 1
+// exactly).  slg_scale 0: lt_forward_cfg at cfg_scale.  The scales reach the engine's fixed device words through a launch in front.
+extern "C" int lt_forward_cfg_slg(lt_engine* e, const void* x_dev, const float* t_dev, void* out_dev, float cfg_scale, float slg_scale,
+                                  const int32_t* skip_host, int32_t n_skip, const lt_step_args* a, void* stream) {
+    const char* who = "lt_forward_cfg_slg";
+    hipStream_t s = (hipStream_t)stream;
+    LT_REQUIRE(e && x_dev && t_dev && out_dev && a, "%s: null argument", who);
+    if (refuse_if_capturing(s, who)) return 2;  // (the first call allocates the skip buffer)
+    LtOptScope opt_scope(&e->opts);
+    if (check_step_shape(e, who, a)) return 2;
+    LT_REQUIRE(std::isfinite(cfg_scale), "%s: the scale is not finite", who);
+    LT_REQUIRE(std::isfinite(slg_scale), "%s: the skip-layer scale is not finite", who);
+    if (check_guided_halves(e, who, a)) return 2;
+    if (check_skip_set(e, who, skip_host, n_skip)) return 2;
+    lt_step_args own = *a;
+    own.cfg_scale = cfg_scale;
+    if (slg_scale == 0.f) return forward_graphed(e, x_dev, t_dev, out_dev, &own, 1, s);  // lt_forward_cfg's launches and result
+    if (ensure_skip_buf(e)) return 1;
+    if (launch_slg_params_store(e->g_cfg, cfg_scale, slg_scale, s)) return 1;
+    {
+        SkipScope scope(e);
+        if (scope.set(who, skip_host, n_skip)) return 2;
+        if (int rc = forward_graphed(e, x_dev, t_dev, nullptr, &own, 1, s, nullptr, e->g_cfg, false, false, LT_EVAL_SLG_STORE)) return rc;
+    }
+    return forward_graphed(e, x_dev, t_dev, out_dev, &own, 1, s, nullptr, e->g_cfg, false, false,
+                           cfg_scale == 1.0f ? LT_EVAL_SLG_COND : LT_EVAL_SLG_GUIDED);
 }
 
 // ---- linear multistep sampling: one evaluation per interval, the earlier slopes reused (multistep.hip) -------------------------

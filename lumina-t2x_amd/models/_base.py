@@ -95,10 +95,18 @@ class EngineSamplers:
         return eng.sample_ode_masked(x, tgrid, mask, x1, noise, method, use_cfg=use_cfg, t_round_to_state_dtype=t_round, **args)
 
     def _engine_sample_ode_cfg_schedule(self, x, tgrid, method, t_round, table, kw, return_trajectory=True, rescale=0.0, norm_limit=math.inf,
-                                        reuse=None):
+                                        reuse=None, slg=None, slg_layers=()):
         """kwargs of forward_with_cfg -> lt_sample_ode_cfg_schedule (guidance schedules; ``cfg_scale`` in kw is ignored), or - with a
-        rescale blend or a norm limit - lt_sample_ode_cfg_rule, or - with a reuse table - lt_sample_ode_cfg_reuse"""
-        from ..transport.guidance import refuse_rule_with_reuse, rule_is_off
+        rescale blend or a norm limit - lt_sample_ode_cfg_rule, or - with a reuse table - lt_sample_ode_cfg_reuse, or -
+        with a table of skip-layer scales - lt_sample_ode_cfg_slg"""
+        from ..transport.guidance import refuse_rule_with_reuse, refuse_with_slg, rule_is_off
+        if slg is not None:
+            if not isinstance(x, torch.Tensor):
+                raise _lib.LuminaLibError("skip-layer guidance: a packed batch (a list of latents) is not served")
+            try:
+                refuse_with_slg(slg, method=method, rescale=rescale, norm_limit=norm_limit, reuse=reuse)
+            except ValueError as exc:
+                raise _lib.LuminaLibError(str(exc)) from None
         if reuse is not None:
             if not isinstance(x, torch.Tensor):
                 raise _lib.LuminaLibError("guidance reuse: a packed batch (a list of latents) is not served")
@@ -109,6 +117,9 @@ class EngineSamplers:
         kw.setdefault("cfg_scale", 1.0)
         eng, args = self._engine_sampler_args(x, True, kw)
         args.pop("cfg_scale", None)
+        if slg is not None:
+            return eng.sample_ode_cfg_slg(x, tgrid, table, slg, slg_layers, method, t_round_to_state_dtype=t_round,
+                                          return_trajectory=return_trajectory, **args)
         if reuse is not None and method in _lib.ODE_MULTISTEP_METHODS:
             return eng.sample_ode_multistep_cfg_reuse(x, tgrid, method, table, reuse, t_round_to_state_dtype=t_round,
                                                       return_trajectory=return_trajectory, **args)
@@ -126,7 +137,7 @@ class EngineSamplers:
 
     @torch.no_grad()
     def sample_ode_cfg_schedule(self, z, tgrid, table, *cond, method: str = "midpoint", return_trajectory: bool = False, rescale: float = 0.0,
-                                norm_limit: float = math.inf, reuse=None, **step_kw):
+                                norm_limit: float = math.inf, reuse=None, slg=None, slg_layers=(), **step_kw):
         """A guided fixed-grid trajectory with a scale per stage in ONE engine call (lt_sample_ode_cfg_schedule): stage k of interval
         i evaluates ``forward_with_cfg`` at ``table[i * stages + k]``, or - at scale 1 exactly - the plain forward of the cond rows alone, at
         half the rows.  ``cond``: the family's conditioning as ``forward_with_cfg`` takes it (``cap_feats, cap_mask`` or ``y``) for all
@@ -136,13 +147,16 @@ class EngineSamplers:
         their guided channels by the per-sample factor of ``transport.guidance.guided_rule`` (lt_sample_ode_cfg_rule); at the
         defaults the call is the schedule call.  ``reuse`` (one 0 / 1 flag per table entry; ``transport.guidance.cfg_reuse_table``): guided stages
         with flag 1 evaluate the cond rows alone and reuse the cond - uncond difference of the last stage with flag 0 (lt_sample_ode_cfg_reuse,
-        DESIGN 7k; refused together with a rule); ``None``: the call made without it.  Returns the last state, or all ``len(tgrid)`` states."""
+        DESIGN 7k; refused together with a rule); ``None``: the call made without it.  ``slg`` (one skip-layer scale per table entry;
+        ``transport.guidance.slg_table``) with ``slg_layers``: stages with ``slg != 0`` also evaluate the cond rows with those blocks left out
+        and add ``slg * (cond - skip)`` (lt_sample_ode_cfg_slg; euler / midpoint / rk4; refused together with a rule or ``reuse``).
+        Returns the last state, or all ``len(tgrid)`` states."""
         if len(cond) > len(self._cond_names):
             raise TypeError(f"sample_ode_cfg_schedule takes the conditioning {self._cond_names}, got {len(cond)} positional arguments")
         kw = dict(zip(self._cond_names, cond), **step_kw)
         self._mirror_attention_flags(kw)
         return self._engine_sample_ode_cfg_schedule(z, tgrid, method, True, table, kw, return_trajectory=return_trajectory, rescale=rescale,
-                                                    norm_limit=norm_limit, reuse=reuse)
+                                                    norm_limit=norm_limit, reuse=reuse, slg=slg, slg_layers=slg_layers)
 
     def _mirror_attention_flags(self, kw):
         if hasattr(self, "layers") and "proportional_attn" in kw and len(self.layers) and hasattr(self.layers[0], "attention"):
@@ -240,6 +254,24 @@ class EngineSamplers:
         self._mirror_attention_flags(kw)
         eng, args = self._engine_sampler_args(x, True, kw)
         return eng.forward_cfg_reuse(x, t, reuse=reuse, **args)
+
+    @torch.no_grad()
+    def forward_with_cfg_slg(self, x, t, *cond, slg_scale: float = 0.0, slg_layers=(), **step_kw):
+        """``forward_with_cfg(x, t, <conditioning>, cfg_scale, **step_kw)`` with skip-layer guidance in ONE engine call (lt_forward_cfg_slg,
+        DESIGN 7m): the cond rows are also evaluated with the blocks ``slg_layers`` left out (``k``), and the guided channels become
+        ``u + cfg_scale (c - u) + slg_scale (c - k)``.  ``cond``: the conditioning for all ``x.size(0)`` rows, then ``cfg_scale`` (or by
+        keyword).  ``slg_scale == 0`` is ``forward_with_cfg``.  Tensor states only."""
+        if not isinstance(x, torch.Tensor):
+            raise _lib.LuminaLibError("forward_with_cfg_slg: a packed batch (a list of latents) is not served by skip-layer guidance")
+        names = self._cond_names + ("cfg_scale",)
+        if len(cond) > len(names):
+            raise TypeError(f"forward_with_cfg_slg takes {names}, got {len(cond)} positional arguments")
+        kw = dict(zip(names, cond), **step_kw)
+        if "cfg_scale" not in kw:
+            raise TypeError("forward_with_cfg_slg needs cfg_scale")
+        self._mirror_attention_flags(kw)
+        eng, args = self._engine_sampler_args(x, True, kw)
+        return eng.forward_cfg_slg(x, t, slg_scale=slg_scale, slg_layers=slg_layers, **args)
 
     def _engine_sample_ode_adaptive(self, x, tgrid, method, use_cfg, t_round, kw, *, rtol, atol, first_step=None, max_steps=2 ** 31 - 1):
         """kwargs of forward_with_cfg / forward -> lt_sample_ode_adaptive; returns (states [len(tgrid), *x.shape], stats dict)"""

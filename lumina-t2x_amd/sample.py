@@ -173,7 +173,13 @@ def run(args, *, encode_fn=None, cap_feat_dim=None, decode_fn=None, model=None) 
         table = guidance_table(args, sample_fn.__self__.t)
         rule = guidance_rule(args)
         reuse = guidance_reuse(args, sample_fn.__self__.t, table)
-        if reuse is not None:  # guided stages that reuse the last refresh stage's cond - uncond difference at half the rows
+        slg = guidance_slg(args, sample_fn.__self__.t)
+        if slg is not None:  # stages that also evaluate the prompt row with some blocks left out and push away from it
+            if table is None:
+                from .transport import guidance
+                table = guidance.cfg_table(sample_fn.__self__.t, args.sampling_method, args.cfg_scale)
+            latent = sample_fn(z, model.forward_with_cfg, cfg_table=table, slg_table=slg, slg_layers=list(args.slg_layers), **kw)[-1][:1]
+        elif reuse is not None:  # guided stages that reuse the last refresh stage's cond - uncond difference at half the rows
             latent = sample_fn(z, model.forward_with_cfg, cfg_table=table, cfg_reuse=reuse, **kw)[-1][:1]
         elif table is None and not rule:
             latent = sample_fn(z, model.forward_with_cfg, **kw)[-1][:1]
@@ -236,6 +242,32 @@ def guidance_reuse(args, tgrid, table):
     return guidance.cfg_reuse_table(tgrid, args.sampling_method, table, every=max(every, 2), per_step=per_step)
 
 
+def guidance_slg(args, tgrid):
+    """``--slg_layers`` / ``--slg_scale`` / ``--slg_interval`` as the table of ``transport.guidance.slg_table``; None at the defaults (no layers,
+    or scale 0): the call it was.  Refused by name together with ``--cfg_rescale`` / ``--cfg_norm_limit``, ``--cfg_reuse*`` and a sampling
+    method that is not euler / midpoint / rk4."""
+    layers, scale = list(getattr(args, "slg_layers", None) or []), float(getattr(args, "slg_scale", 0.0) or 0.0)
+    interval = getattr(args, "slg_interval", None)
+    if not layers and scale == 0.0 and interval is None:
+        return None
+    if not layers:
+        raise SystemExit("--slg_scale / --slg_interval need --slg_layers: the blocks the skip evaluation leaves out")
+    if guidance_rule(args):
+        raise SystemExit("--slg_layers is not served together with --cfg_rescale / --cfg_norm_limit")
+    if int(getattr(args, "cfg_reuse", 0) or 0) != 0 or bool(getattr(args, "cfg_reuse_per_step", False)):
+        raise SystemExit("--slg_layers is not served together with --cfg_reuse / --cfg_reuse_per_step")
+    from .transport import guidance
+    if args.sampling_method not in guidance.FIXED_GRID_METHODS:
+        raise SystemExit(f"--slg_layers is built for the sampling methods {', '.join(guidance.FIXED_GRID_METHODS)}, not '{args.sampling_method}'")
+    try:
+        guidance.check_slg_layers(layers)
+        if scale == 0.0:
+            return None
+        return guidance.slg_table(tgrid, args.sampling_method, scale, interval=interval)
+    except ValueError as exc:
+        raise SystemExit(f"--slg_*: {exc}") from None
+
+
 def build_parser() -> argparse.ArgumentParser:
     def none_or_str(v):
         return None if v == "None" else v
@@ -255,6 +287,12 @@ def build_parser() -> argparse.ArgumentParser:
                         "between, which then evaluate the prompt row alone (0: off)")
     p.add_argument("--cfg_reuse_per_step", action="store_true",
                    help="... instead on the first guided stage of every step (midpoint, rk4), reused on the step's other stages")
+    p.add_argument("--slg_layers", type=int, nargs="+", default=None, metavar="L",
+                   help="skip-layer guidance: the blocks a third evaluation of the prompt row leaves out (default: off)")
+    p.add_argument("--slg_scale", type=float, default=0.0, metavar="S",
+                   help="... whose prediction the guided output is pushed away from: + S * (prompt row - skip row) (0: off)")
+    p.add_argument("--slg_interval", type=float, nargs=2, default=None, metavar=("LO", "HI"),
+                   help="... on the stages with LO <= t < HI only (t = 0 noise, 1 data; default: all stages)")
     p.add_argument("--num_sampling_steps", type=int, default=250)
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--ckpt", type=str, required=True)

@@ -28,7 +28,10 @@ Rescaled and norm-limited guidance multiplies the guided output o
 
 Guidance reuse takes the difference ``cond - uncond`` of the guided channels on some guided stages and reuses it on the others,
 which evaluate the cond rows alone: ``sample_cfg_reuse`` / ``sample_cfg_reuse_multistep`` are the definition ``lt_sample_ode_cfg_reuse`` /
-``lt_sample_ode_multistep_cfg_reuse`` are held to, ``cfg_reuse_table`` builds the flag tables and ``check_reuse`` refuses what the engine refuses."""
+``lt_sample_ode_multistep_cfg_reuse`` are held to, ``cfg_reuse_table`` builds the flag tables and ``check_reuse`` refuses what the engine refuses.
+
+Skip-layer guidance adds ``s (cond - skip)``, ``skip`` the cond rows evaluated with a set of blocks left out: ``sample_cfg_slg`` is
+the definition ``lt_sample_ode_cfg_slg`` is held to, ``slg_table`` builds the table of ``s`` and ``slg_combine`` is the chain of roundings."""
 from __future__ import annotations
 
 import math
@@ -539,4 +542,156 @@ def sample_cfg_reuse_multistep(model, z, tgrid, table, reuse, method="abm2", *, 
     func, call = _reuse_func(model, B, table.tolist(), flags, cond_kw, half_kw, z.device, deltas)
     out = multistep_odeint(func, z, _grid32(tgrid), method, t_round=t_round)
     assert call[0] == len(flags)
+    return out
+
+
+# ---- skip-layer guidance: a third prediction with a set of blocks left out, pushed away from -----------------------------------
+def slg_table(tgrid, method, slg_scale, interval=None):
+    """The fp32 table of skip-layer scales of a trajectory, one per evaluation: ``slg_scale`` where ``lo <= t_stage < hi`` for
+    ``interval = (lo, hi)`` (default: everywhere), 0 elsewhere.  ``t_stage`` is the UNROUNDED fp32 stage time, as in ``cfg_table``; an empty
+    interval (``lo == hi``) gives all zeros."""
+    ts = stage_times(tgrid, method, th.float32, False).tolist()
+    lo, hi = (-math.inf, math.inf) if interval is None else (float(interval[0]), float(interval[1]))
+    if not lo <= hi:
+        raise ValueError(f"skip-layer interval [{lo}, {hi}) is not ordered")
+    table = th.tensor([float(slg_scale) if lo <= t < hi else 0.0 for t in ts], dtype=th.float32)
+    if not bool(th.isfinite(table).all()):
+        raise ValueError("skip-layer table has an entry that is not finite")
+    return table
+
+
+def check_slg(slg, tgrid, method):
+    """``slg`` as an fp32 CPU tensor of ``(len(tgrid) - 1) * stages`` finite entries"""
+    stages = _check_method(method)
+    n = len(_grid32(tgrid))
+    if slg is None:
+        raise ValueError("skip-layer table is None (one scale per evaluation; slg_table builds one)")
+    t = slg if isinstance(slg, th.Tensor) else th.tensor(list(slg), dtype=th.float32)
+    t = t.detach().to("cpu", th.float32).reshape(-1).contiguous()
+    if t.numel() != (n - 1) * stages:
+        raise ValueError(f"skip-layer table has {t.numel()} entries, a {n}-point {method} grid has {(n - 1) * stages} stages")
+    if not bool(th.isfinite(t).all()):
+        raise ValueError("skip-layer table has an entry that is not finite")
+    return t
+
+
+def check_slg_layers(layers, n_layers=None):
+    """the layer set as a list of ints; refused: an entry that is no integer, a repeated index, and - when the depth is known - an index
+    outside ``0 .. n_layers - 1`` and a set that leaves no layer (what the engine refuses)"""
+    out = []
+    for v in (layers.reshape(-1).tolist() if isinstance(layers, th.Tensor) else list(layers)):
+        if isinstance(v, bool) or int(v) != v:
+            raise ValueError(f"skip layer {v!r} is not an integer index")
+        if int(v) in out:
+            raise ValueError(f"skip index {int(v)} is repeated")
+        out.append(int(v))
+    if n_layers is not None:
+        for v in out:
+            if not 0 <= v < n_layers:
+                raise ValueError(f"skip index {v} is outside 0..{n_layers - 1}")
+        if len(out) >= n_layers:
+            raise ValueError(f"the skip set leaves no layer (all {n_layers} are in it)")
+    return out
+
+
+def refuse_with_slg(slg, method="euler", rescale=0.0, norm_limit=math.inf, reuse=None):
+    """what skip-layer guidance is not served with, by name: a rescale / norm-limit rule, a reuse table, a method that is not fixed-grid"""
+    if slg is None:
+        return
+    if method not in FIXED_GRID_METHODS:
+        raise ValueError(f"skip-layer guidance is built for the fixed-grid methods {', '.join(FIXED_GRID_METHODS)}, not '{method}'")
+    if not rule_is_off(rescale, norm_limit):
+        raise ValueError("skip-layer guidance (an slg table) together with a rescale / norm_limit rule is not served")
+    if reuse is not None:
+        raise ValueError("skip-layer guidance (an slg table) together with guidance reuse (a reuse table) is not served")
+
+
+def slg_combine(c, u, k, w, s):
+    """the guided channels of one evaluation in bf16 tensor ops, every op rounding: ``(u + w (c - u)) + s (c - k)``, or - ``u`` None, the
+    stage at ``w == 1`` - ``c + s (c - k)``.  ``c``, ``u``, ``k``: bf16 tensors; ``w``, ``s``: Python floats holding fp32 values"""
+    if u is None:
+        return c + s * (c - k)
+    return (u + w * (c - u)) + s * (c - k)
+
+
+def sample_cfg_slg(model, z, tgrid, table, slg, slg_layers, method="euler", *, cond=None, t_round=True, **kw):
+    """The trajectory of skip-layer guidance on the host: every state ``[len(tgrid), *z.shape]``.  This IS the definition
+    ``lt_sample_ode_cfg_slg`` is held to, state for state.  Per evaluation ``table`` gives the scale ``w`` and ``slg`` the skip-layer scale ``s``:
+
+        s == 0            what sample_cfg_schedule does (forward_with_cfg at w, or the cond rows alone at w == 1)
+        s != 0            k = bf16(model.forward(x[:B'], t[:B'], <cond half>, skip_layers=S))
+                          o = bf16(model.forward(cat([x[:B']] * 2), t, <conditioning>))    (w == 1: the B' cond rows alone)
+                          g = (u + w * (c - u)) + s * (c - k)                                (w == 1: g = c + s * (c - k))
+
+    on the first ``min(model.cfg_channels, C)`` channels in bf16 tensor ops (every op rounds), the other channels passing through row by row
+    (from the cond rows at ``w == 1``), ``g`` written to both halves, the result cast to the state dtype.  The loop is ``sample_cfg_schedule``'s,
+    statement for statement."""
+    if isinstance(z, (list, tuple)):
+        raise ValueError("skip-layer guidance takes a tensor state; a packed batch (a list of latents) is not served")
+    stages = _check_method(method)
+    table = check_table(table, tgrid, method)
+    slg = check_slg(slg, tgrid, method)
+    layers = check_slg_layers(slg_layers, getattr(model, "n_layers", None))
+    B = z.size(0)
+    if B % 2:
+        raise ValueError(f"guidance needs an even batch (cond + uncond rows), got {B}")
+    kw = dict(kw)
+    kw.pop("cfg_scale", None)  # the table is the scale
+    refuse_with_slg(slg, method, kw.pop("rescale", 0.0), kw.pop("norm_limit", math.inf), kw.pop("reuse", None))
+    if cond is None:
+        cond = [k for k, v in kw.items() if isinstance(v, th.Tensor) and v.dim() >= 1 and v.shape[0] == B]
+    cond_kw = {k: kw.pop(k) for k in cond}
+    half_kw = {k: _cond_half(v, B) for k, v in cond_kw.items()}
+    ch_model = int(getattr(model, "cfg_channels", 3))
+    device = z.device
+    t = _grid32(tgrid).to(device)
+    w, sl = table.tolist(), slg.tolist()
+    call = [0]
+
+    def func(tt, y):
+        scale, s = w[call[0]], sl[call[0]]
+        call[0] += 1
+        half = B // 2
+        tvec = th.ones(B).to(device) * tt  # fp32 [B] (reference integrators.py:108)
+        if s == 0.0:  # sample_cfg_schedule's stage
+            if scale != 1.0:
+                return model.forward_with_cfg(y, tvec, **cond_kw, cfg_scale=scale, **kw)
+            o = model.forward(y[:half], tvec[:half], **half_kw)
+            return th.cat([o, o])
+        k = model.forward(y[:half], tvec[:half], **half_kw, skip_layers=layers).to(th.bfloat16)
+        ch = min(ch_model, k.size(1))
+        if scale != 1.0:
+            o = model.forward(th.cat([y[:half]] * 2), tvec, **cond_kw).to(th.bfloat16)
+            g = slg_combine(o[:half, :ch], o[half:, :ch], k[:, :ch], scale, s)
+            return th.cat([th.cat([g, o[:half, ch:]], 1), th.cat([g, o[half:, ch:]], 1)]).to(y.dtype)
+        o = model.forward(y[:half], tvec[:half], **half_kw).to(th.bfloat16)
+        g = slg_combine(o[:, :ch], None, k[:, :ch], scale, s)
+        r = th.cat([g, o[:, ch:]], 1)
+        return th.cat([r, r]).to(y.dtype)
+
+    def f(tt, y):
+        return _call(func, tt, y) if t_round else func(tt, y)
+
+    # fixed_grid_odeint's loop (integrators.py), statement for statement
+    out = th.empty((len(t),) + tuple(z.shape), dtype=z.dtype, device=device)
+    out[0] = z
+    y = z
+    third, two_thirds = 1.0 / 3.0, 2.0 / 3.0
+    for j in range(len(t) - 1):
+        t0, t1 = t[j], t[j + 1]
+        dt = t1 - t0
+        k1 = f(t0, y)
+        if method == "euler":
+            dy = dt * k1
+        elif method == "midpoint":
+            half = 0.5 * dt
+            dy = dt * f(t0 + half, y + k1 * half)
+        else:
+            k2 = f(t0 + dt * third, y + dt * k1 * third)
+            k3 = f(t0 + dt * two_thirds, y + dt * (k2 - k1 * third))
+            k4 = f(t1, y + dt * (k1 - k2 + k3))
+            dy = (k1 + 3 * (k2 + k3) + k4) * dt * 0.125
+        y = y + dy
+        out[j + 1] = y
+    assert call[0] == (len(t) - 1) * stages
     return out

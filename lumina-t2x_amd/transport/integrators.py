@@ -321,7 +321,7 @@ class ode:
         self.max_num_steps = 2 ** 31 - 1
         self.stats = None         # adaptive methods: nfe / accepted / rejected / first_step / dt of the last sample() call
 
-    def _sample_cfg_schedule(self, x, model, table, model_kwargs, rescale=0.0, norm_limit=math.inf, reuse=None):
+    def _sample_cfg_schedule(self, x, model, table, model_kwargs, rescale=0.0, norm_limit=math.inf, reuse=None, slg=None, slg_layers=()):
         """a guidance schedule (transport/guidance.py): one engine call for an engine-backed forward_with_cfg, else the host loop"""
         from .guidance import (cfg_table, refuse_rule_with_reuse, rule_is_off, sample_cfg_multistep, sample_cfg_reuse, sample_cfg_reuse_multistep,
                                sample_cfg_rule, sample_cfg_schedule)
@@ -335,8 +335,16 @@ class ode:
             if isinstance(x, (list, tuple)):
                 raise ValueError("guidance reuse (cfg_reuse) takes a tensor state; a packed batch (a list of latents) is not served")
             refuse_rule_with_reuse(rescale, norm_limit)
+        if slg is not None:  # skip-layer guidance: refused by name on a packed list, with a rule, a reuse table, another method
+            from .guidance import refuse_with_slg, sample_cfg_slg
+            if isinstance(x, (list, tuple)):
+                raise ValueError("skip-layer guidance (slg_table) takes a tensor state; a packed batch (a list of latents) is not served")
+            refuse_with_slg(slg, self.sampler_type, rescale, norm_limit, reuse)
         target = _engine_target(model)
         if target is not None and target[1] and x.is_cuda and self.use_engine and hasattr(target[0], "_engine_sample_ode_cfg_schedule"):
+            if slg is not None:
+                return target[0]._engine_sample_ode_cfg_schedule(x, self.t, self.sampler_type, self.t_round_to_state_dtype, table, dict(model_kwargs),
+                                                                 slg=slg, slg_layers=slg_layers)
             if reuse is not None:
                 return target[0]._engine_sample_ode_cfg_schedule(x, self.t, self.sampler_type, self.t_round_to_state_dtype, table, dict(model_kwargs),
                                                                  reuse=reuse)
@@ -347,6 +355,8 @@ class ode:
         owner = getattr(model, "__self__", None)
         if owner is None or getattr(model, "__name__", "") != "forward_with_cfg" or not hasattr(owner, "forward"):
             raise TypeError("cfg_table needs the bound forward_with_cfg of a model that also has forward (the conditional-only stages call it)")
+        if slg is not None:
+            return sample_cfg_slg(owner, x, self.t, table, slg, slg_layers, self.sampler_type, t_round=self.t_round_to_state_dtype, **model_kwargs)
         if reuse is not None and self.sampler_type in MULTISTEP_METHODS:
             return sample_cfg_reuse_multistep(owner, x, self.t, table, reuse, self.sampler_type, t_round=self.t_round_to_state_dtype, **model_kwargs)
         if reuse is not None:
@@ -359,9 +369,11 @@ class ode:
         return sample_cfg_rule(owner, x, self.t, table, self.sampler_type, rescale=rescale, norm_limit=norm_limit,
                                t_round=self.t_round_to_state_dtype, **model_kwargs)
 
-    def sample(self, x, model, cfg_table=None, cfg_rescale=0.0, cfg_norm_limit=math.inf, cfg_reuse=None, **model_kwargs):
-        if cfg_table is not None or cfg_reuse is not None or not (float(cfg_rescale) == 0.0 and float(cfg_norm_limit) == math.inf):
-            return self._sample_cfg_schedule(x, model, cfg_table, model_kwargs, cfg_rescale, cfg_norm_limit, cfg_reuse)
+    def sample(self, x, model, cfg_table=None, cfg_rescale=0.0, cfg_norm_limit=math.inf, cfg_reuse=None, slg_table=None, slg_layers=(),
+               **model_kwargs):
+        if (cfg_table is not None or cfg_reuse is not None or slg_table is not None
+                or not (float(cfg_rescale) == 0.0 and float(cfg_norm_limit) == math.inf)):
+            return self._sample_cfg_schedule(x, model, cfg_table, model_kwargs, cfg_rescale, cfg_norm_limit, cfg_reuse, slg_table, slg_layers)
         if isinstance(x, tuple):  # the likelihood ODE (reference integrators.py:105-115 with a tuple state)
             device = x[0].device
 

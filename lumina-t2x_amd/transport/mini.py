@@ -62,7 +62,7 @@ class ODE:
                                                    dict(model_kwargs))
         return sample_masked(model, x, self.t, mask, x1, noise, self.sampler_type, **model_kwargs)
 
-    def _sample_cfg_schedule(self, x, model, table, model_kwargs, rescale=0.0, norm_limit=math.inf, reuse=None):
+    def _sample_cfg_schedule(self, x, model, table, model_kwargs, rescale=0.0, norm_limit=math.inf, reuse=None, slg=None, slg_layers=()):
         """a guidance schedule (transport/guidance.py): a scale per stage; one engine call when the callable is an engine-backed forward_with_cfg"""
         if self.sampler_type not in FIXED_GRID_METHODS + MULTISTEP_METHODS:
             raise NotImplementedError(f"guidance schedules are built for the fixed-grid methods {', '.join(FIXED_GRID_METHODS)}, not "
@@ -74,8 +74,16 @@ class ODE:
             if isinstance(x, (list, tuple)):
                 raise ValueError("guidance reuse (cfg_reuse) takes a tensor state; a packed batch (a list of latents) is not served")
             refuse_rule_with_reuse(rescale, norm_limit)
+        if slg is not None:  # skip-layer guidance: refused by name on a packed list, with a rule, a reuse table, another method
+            from .guidance import refuse_with_slg, sample_cfg_slg
+            if isinstance(x, (list, tuple)):
+                raise ValueError("skip-layer guidance (slg_table) takes a tensor state; a packed batch (a list of latents) is not served")
+            refuse_with_slg(slg, self.sampler_type, rescale, norm_limit, reuse)
         target = _engine_target(model)
         if target is not None and target[1] and x.is_cuda and self.use_engine and hasattr(target[0], "_engine_sample_ode_cfg_schedule"):
+            if slg is not None:
+                return target[0]._engine_sample_ode_cfg_schedule(x, self.t, self.sampler_type, self.t_round_to_state_dtype, table, dict(model_kwargs),
+                                                                 slg=slg, slg_layers=slg_layers)
             if reuse is not None:
                 return target[0]._engine_sample_ode_cfg_schedule(x, self.t, self.sampler_type, self.t_round_to_state_dtype, table, dict(model_kwargs),
                                                                  reuse=reuse)
@@ -86,6 +94,8 @@ class ODE:
         owner = getattr(model, "__self__", None)
         if owner is None or getattr(model, "__name__", "") != "forward_with_cfg" or not hasattr(owner, "forward"):
             raise TypeError("cfg_table needs the bound forward_with_cfg of a model that also has forward (the conditional-only stages call it)")
+        if slg is not None:
+            return sample_cfg_slg(owner, x, self.t, table, slg, slg_layers, self.sampler_type, t_round=self.t_round_to_state_dtype, **model_kwargs)
         if reuse is not None and self.sampler_type in MULTISTEP_METHODS:
             return sample_cfg_reuse_multistep(owner, x, self.t, table, reuse, self.sampler_type, t_round=self.t_round_to_state_dtype, **model_kwargs)
         if reuse is not None:
@@ -99,13 +109,13 @@ class ODE:
                                t_round=self.t_round_to_state_dtype, **model_kwargs)
 
     def sample(self, x, model, mask=None, x1=None, noise=None, cfg_table=None, cfg_rescale=0.0, cfg_norm_limit=math.inf, cfg_reuse=None,
-               **model_kwargs):
+               slg_table=None, slg_layers=(), **model_kwargs):
         if isinstance(x, tuple):
             raise NotImplementedError("tuple states are not part of the sampling path")
-        if cfg_table is not None or cfg_reuse is not None or not rule_is_off(cfg_rescale, cfg_norm_limit):
+        if cfg_table is not None or cfg_reuse is not None or slg_table is not None or not rule_is_off(cfg_rescale, cfg_norm_limit):
             if mask is not None or x1 is not None or noise is not None:
-                raise NotImplementedError("a guidance schedule and an inpainting mask are not served together")
-            return self._sample_cfg_schedule(x, model, cfg_table, model_kwargs, cfg_rescale, cfg_norm_limit, cfg_reuse)
+                raise NotImplementedError("a guidance schedule (or skip-layer guidance) and an inpainting mask are not served together")
+            return self._sample_cfg_schedule(x, model, cfg_table, model_kwargs, cfg_rescale, cfg_norm_limit, cfg_reuse, slg_table, slg_layers)
         if mask is not None or x1 is not None or noise is not None:
             return self._sample_masked(x, model, mask, x1, noise, model_kwargs)
         target = _engine_target(model)
