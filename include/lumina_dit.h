@@ -62,6 +62,10 @@ extern "C" {
 #define LT_ODE_ABM2 34
 #define LT_ODE_ABM3 35
 /* lt_op_rk_*: most slopes a chain runs over (dopri5: 7), and the bytes of device workspace a norm needs */
+/* lt_forward_cached: the kinds of a single evaluation under step caching */
+#define LT_CACHE_PROBE 0
+#define LT_CACHE_RUN 1
+#define LT_CACHE_REUSE 2
 #define LT_RK_MAX_SLOPES 7
 #define LT_RK_WS_BYTES 8192
 /* lt_sample_sde: method, last step, and the length (floats) of one stage record */
@@ -494,6 +498,42 @@ int lt_forward_cfg_slg(lt_engine* e, const void* x_dev, const float* t_dev, void
 int lt_sample_ode_cfg_slg(lt_engine* e, const void* z_dev, void* traj_dev, void* final_dev, const float* tgrid_host, int32_t n_grid, int32_t method,
                           const float* cfg_host, const float* slg_host, const int32_t* skip_host, int32_t n_skip, int32_t t_round_to_state_dtype,
                           const lt_step_args* a, void* stream);
+
+/* Step caching (transport/cache.py: sample_teacache is the definition; the TeaCache rule).  An evaluation may leave the L blocks
+ * out and add the residual r = bf16(x_L - x_0) that the stack produced the last time it ran.  Evaluation j = 0 .. ncalls - 1 of a fixed-grid
+ * trajectory (ncalls = (n_grid - 1) * stages), R = rounding to bf16:
+ *   head       patchify, embedding, conditioning, the first pre-norm + modulate - lt_forward's launches.  x0_j: the token stream before block
+ *              0; h_j: the bf16 modulated input of the first block, all M = batch * tokens rows (cond and uncond together).
+ *   indicator  for 0 < j < ncalls - 1: S1 = sum |h_j - h_{j-1}|, S0 = sum |h_{j-1}| over all M d words, every difference and sum in float64;
+ *              rel = S1 / S0; acc += ((((c0 rel + c1) rel + c2) rel + c3) rel + c4), float64, no contraction.  h_{j-1} <- h_j on every evaluation.
+ *   decision   the stack runs on the first and on the last evaluation, when S0 == 0 (acc then takes nothing), and when !(acc < threshold);
+ *              whenever it runs acc = 0.  threshold == 0: it always runs.
+ *   run        the L blocks, r = R(x_L - x_0) stored, final norm + modulate, final GEMM, closing kernel: the output is lt_forward's /
+ *              lt_forward_cfg's for the same input word for word.
+ *   reuse      x = R(x0_j + r); the final layer's LayerNorm (no affine, eps 1e-6) + modulate of x with THIS evaluation's modulation, the
+ *              rounding chain of the last block's closing kernel; final GEMM, closing kernel.  No block launches anything.
+ * lt_sample_ode_cached: lt_sample_ode's arguments, stage times, dt, rounding points and trajectory slots, plus threshold (fp32, >= 0),
+ * coef_host (five float64, highest power first; (0, 0, 0, 1, 0) is the identity) and stats_host (NULL, or ncalls x 3 float64: rel, acc after
+ * the add, 1 ran / 0 reused; the first and the last evaluation report rel 0, an evaluation with S0 == 0 rel +inf).  The host reads two float64
+ * words per evaluation but the first and the last: one stream synchronisation each.  lt_last_nfe = ncalls, lt_last_eval_rows = batch * runs,
+ * lt_last_cache_hits = reuses.  A trajectory replays three HIP-graph keys (head, stack + tail, reuse + tail) whatever the threshold.  Three
+ * buffers of max_batch * max_tokens * dim bf16 (h_prev, x0, r) are allocated by the first call, before anything is launched.
+ * lt_forward_cached: the single evaluations the host loop is built from.  LT_CACHE_PROBE: the head; sums_host[0] = S1, sums_host[1] = S0
+ * against the previous probe's h (zeros before the first), out_dev unused (may be NULL).  LT_CACHE_RUN / LT_CACHE_REUSE: the rest of the
+ * evaluation whose probe was the engine's last evaluation, with the same step arguments (x_dev is not read again; t_dev is); sums_host unused.
+ * Every lt_prepare_prompt* / lt_prepare_labels call forgets the residual and the probe.
+ * Serves every variant lt_forward serves, bf16 and f32 states.  Not served, refused by name with nothing written: packed batches, regional
+ * prompts, a layer-skip set, guidance schedules / rules / reuse / skip-layer guidance, the multistep and adaptive solvers, inpainting masks,
+ * MoE routing record / force, a stream under capture; a null argument; a negative or NaN threshold; a coefficient that is not finite;
+ * conditioning prepared for another batch; LT_CACHE_RUN / _REUSE that do not follow their probe; LT_CACHE_REUSE without a stored residual
+ * of this shape.  No coefficient set is built in: none has been verified against a trained checkpoint. */
+int lt_sample_ode_cached(lt_engine* e, const void* z_dev, void* traj_dev, void* final_dev, const float* tgrid_host, int32_t n_grid, int32_t method,
+                         int32_t use_cfg, int32_t t_round_to_state_dtype, const lt_step_args* a, float threshold, const double* coef_host,
+                         double* stats_host, void* stream);
+int lt_forward_cached(lt_engine* e, const void* x_dev, const float* t_dev, void* out_dev, int32_t mode, int32_t use_cfg, const lt_step_args* a,
+                      double* sums_host, void* stream);
+/* the evaluations of the last lt_sample_ode_cached call that reused the residual */
+int64_t lt_last_cache_hits(lt_engine* e);
 
 /* number of model evaluations issued by the last lt_sample_ode /lt_sample_ode_packed / lt_sample_views / lt_sample_views_guided / lt_sample_sde / lt_sample_ode_adaptive call */
 int64_t lt_last_nfe(lt_engine* e);

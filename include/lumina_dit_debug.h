@@ -239,6 +239,22 @@ int lt_op_unpatchify_cfg_reuse(const void* rows, int32_t ld, void* out, int32_t 
 int lt_op_unpatchify_cfg_slg(const void* rows, int32_t ld, void* out, int32_t out_dtype, int32_t B, int32_t C, int32_t out_ch, int32_t H, int32_t W,
                              int32_t patch, const float* cfg_scale_dev, const float* slg_scale_dev, int32_t cfg_channels, int32_t wp_stride,
                              void* skip_dev, int32_t mode, void* stream);
+/* Step caching (csrc/step_cache.hip), for tests/test_gpu_teacache.py.  n: bf16 words, a positive multiple of 8; fixed launch
+ * geometry, so the sums are a function of the operands alone.
+ *   lt_op_cache_indicator: sums_dev[0] = sum |h - h_prev|, sums_dev[1] = sum |h_prev|, every difference and sum in float64; then h_prev <- h.
+ *     ws_dev: lt_op_cache_ws_bytes() bytes of scratch.  h and h_prev in one layout (row-major or row-pair: lt_op_pair_layout).
+ *   lt_op_cache_residual_store: r = bf16(xl - x0), fp32 from the bf16 words, one rounding.
+ *   lt_op_cache_residual_apply: x <- bf16(x + r) in place; h = bf16(LayerNorm(x) * scale1p [+ shift]) - affine-free LayerNorm with eps 1e-6
+ *     and the modulate in fp32, one rounding (gated_residual_norm's next_mode 2); scale1p_dev holds bf16(1 + scale), shift_dev may be NULL,
+ *     both [B, ld_mod]; rows = B * N. */
+/* lt_debug_cache_read: n bf16 words of one of the engine's step-cache buffers to dst_dev, in stream order - which 0: h_prev, 1: x0, 2: r,
+ * 3: the token stream e->x, 4: the GEMM input e->h.  Refused: a null argument, buffers not allocated yet, n beyond max_batch * max_tokens * dim. */
+int lt_debug_cache_read(lt_engine* e, int32_t which, void* dst_dev, int64_t n, void* stream);
+int32_t lt_op_cache_ws_bytes(void);
+int lt_op_cache_indicator(const void* h_dev, void* h_prev_dev, int64_t n, void* ws_dev, double* sums_dev, void* stream);
+int lt_op_cache_residual_store(const void* xl_dev, const void* x0_dev, void* r_dev, int64_t n, void* stream);
+int lt_op_cache_residual_apply(void* x_dev, const void* r_dev, const void* scale1p_dev, const void* shift_dev, int32_t ld_mod, void* h_dev, int32_t B,
+                               int32_t N, int32_t d, void* stream);
 /* The ragged boundary kernels of a packed batch (csrc/packed.hip): one launch for all samples.  hw_host = [B][2] latent sizes (host); the
  * flat state holds sample b = [C, H_b, W_b] at element offset sum_{j<b} C H_j W_j; N = token rows per sample in the row buffers (>= the longest
  * sequence).  Each launching entry builds the table of the size list, stores it at tab_dev (5 * 64 ints of device memory) and runs its kernel.

@@ -29,6 +29,7 @@ LT_ODE_DOPRI5, LT_ODE_BOSH3, LT_ODE_FEHLBERG2, LT_ODE_ADAPTIVE_HEUN = 3, 4, 5, 6
 ODE_ADAPTIVE_METHODS = {"dopri5": LT_ODE_DOPRI5, "bosh3": LT_ODE_BOSH3, "fehlberg2": LT_ODE_FEHLBERG2, "adaptive_heun": LT_ODE_ADAPTIVE_HEUN}
 LT_ODE_AB2, LT_ODE_AB3, LT_ODE_ABM2, LT_ODE_ABM3 = 32, 33, 34, 35  # named where a call refuses them; lt_sample_ode_multistep takes the weight table
 ODE_MULTISTEP_METHODS = {"ab2": LT_ODE_AB2, "ab3": LT_ODE_AB3, "abm2": LT_ODE_ABM2, "abm3": LT_ODE_ABM3}
+LT_CACHE_PROBE, LT_CACHE_RUN, LT_CACHE_REUSE = 0, 1, 2
 LT_RK_MAX_SLOPES, LT_RK_WS_BYTES = 7, 8192
 LT_SDE_EULER, LT_SDE_HEUN = 0, 1
 SDE_METHODS = {"Euler": LT_SDE_EULER, "Heun": LT_SDE_HEUN}
@@ -135,6 +136,15 @@ _SIGNATURES: Dict[str, tuple] = {
     "lt_forward_cfg_slg": (_i32, [_vp, _vp, _vp, _vp, _f32, _f32, C.POINTER(_i32), _i32, C.POINTER(LtStepArgs), _vp]),
     "lt_sample_ode_cfg_slg": (_i32, [_vp, _vp, _vp, _vp, C.POINTER(_f32), _i32, _i32, C.POINTER(_f32), C.POINTER(_f32), C.POINTER(_i32), _i32, _i32,
                                      C.POINTER(LtStepArgs), _vp]),
+    "lt_sample_ode_cached": (_i32, [_vp, _vp, _vp, _vp, C.POINTER(_f32), _i32, _i32, _i32, _i32, C.POINTER(LtStepArgs), _f32, C.POINTER(C.c_double),
+                                    C.POINTER(C.c_double), _vp]),
+    "lt_forward_cached": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, C.POINTER(LtStepArgs), C.POINTER(C.c_double), _vp]),
+    "lt_last_cache_hits": (_i64, [_vp]),
+    "lt_debug_cache_read": (_i32, [_vp, _i32, _vp, _i64, _vp]),
+    "lt_op_cache_ws_bytes": (_i32, []),
+    "lt_op_cache_indicator": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp]),
+    "lt_op_cache_residual_store": (_i32, [_vp, _vp, _vp, _i64, _vp]),
+    "lt_op_cache_residual_apply": (_i32, [_vp, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _vp]),
     "lt_last_nfe": (_i64, [_vp]),
     "lt_last_eval_rows": (_i64, [_vp]),
     "lt_graph_replays": (_i64, [_vp]),

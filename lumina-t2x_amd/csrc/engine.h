@@ -231,6 +231,16 @@ struct lt_engine {
     // the layers THIS call's evaluation leaves out (ascending, distinct, inside 0 .. L-1, not all of them): an argument of the call that
     // travels here to run_forward.  Only SkipScope writes it, and its destructor empties it on every exit path
     std::vector<int32_t> skip;
+    // step caching: the modulated input of the first block of the previous evaluation, the token stream before block 0 and the
+    // residual r = bfr(x_L - x_0) of the last evaluation that ran the stack - max_batch * max_tokens x d bf16 each; behind them the indicator's
+    // partial sums and its two float64 result words, and the page-locked pair the host reads them from.  Allocated by the first call that needs
+    // them (ensure_step_cache) and kept for the engine's life - captured graphs hold the pointers.
+    // cache_head: { B, H, W, io_dtype, use_cfg } of the head segment whose e->x / e->h / e->mod are in place (B = 0: none; every other evaluation
+    // overwrites them and says so); cache_res: { B, H, W, use_cfg } of what c_r holds (B = 0: nothing; every prepare call forgets it)
+    u16 *c_hprev = nullptr, *c_x0 = nullptr, *c_r = nullptr;
+    double *c_ws = nullptr, *c_sums_host = nullptr;
+    int cache_head[5] = {0, 0, 0, 0, 0}, cache_res[4] = {0, 0, 0, 0};
+    long long last_cache_hits = 0;  // lt_last_cache_hits: the evaluations of the last lt_sample_ode_cached call that reused the residual
     hipStream_t cap_stream = nullptr;
     long long graph_replays = 0;
     // profiling
@@ -266,10 +276,20 @@ int packed_call_begin(lt_engine* e, const char* who, const int32_t* hw_host, con
 // channels go to e->g_skip, `out` is not written (may be null); LT_EVAL_SLG_GUIDED - all rows, the closing kernel adds s (cond - skip) with s
 // from e->g_cfg[3]; LT_EVAL_SLG_COND - the cond rows alone, cond + s (cond - skip), both halves of `out` written.  The caller has run
 // ensure_skip_buf and has put s in place
+// segment (with nothing of the above but use_cfg): one part of an evaluation whose block stack may be left out.  The parts hand
+// e->x, e->h, e->mod and the step-cache buffers to each other; one more word of the key, so a cached trajectory replays three graphs
+//   LT_SEG_HEAD   - patchify .. the first pre-norm + modulate, then the indicator sums (e->c_ws) and x_0 kept; reads x_in and t, `out` unused
+//   LT_SEG_BLOCKS - the L blocks, r = bfr(x_L - x_0) stored, the tail: `out` is lt_forward's / lt_forward_cfg's word for word; reads t
+//   LT_SEG_APPLY  - x = bfr(x_0 + r), the final layer's norm + modulate, the tail; no block launches anything
+// The last two follow a head segment of the same step arguments with no other evaluation between (e->cache_head; refused by name otherwise);
+// the caller has run ensure_step_cache and, for LT_SEG_APPLY, answers for the residual being there
 enum { LT_EVAL_PLAIN = 0, LT_EVAL_STORE = 1, LT_EVAL_REUSE = 2, LT_EVAL_SLG_STORE = 3, LT_EVAL_SLG_GUIDED = 4, LT_EVAL_SLG_COND = 5 };
+enum { LT_SEG_WHOLE = 0, LT_SEG_HEAD = 1, LT_SEG_BLOCKS = 2, LT_SEG_APPLY = 3 };
 int forward_graphed(lt_engine* e, const void* x_in, const float* t_dev, void* out, const lt_step_args* a, int use_cfg, hipStream_t s,
                     const PackedCall* pc = nullptr, const float* cfg_dev = nullptr, bool cond_only = false, bool rule = false,
-                    int reuse = LT_EVAL_PLAIN);
+                    int reuse = LT_EVAL_PLAIN, int segment = LT_SEG_WHOLE);
+// the buffers of step caching: allocated on the first call, before anything is launched (engine.hip)
+int ensure_step_cache(lt_engine* e);
 // the difference buffer of guidance reuse: allocated on the first call, before anything is launched (engine.hip)
 int ensure_delta(lt_engine* e);
 // ... and the skip buffer of skip-layer guidance (engine.hip)

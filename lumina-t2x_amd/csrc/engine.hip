@@ -416,8 +416,10 @@ struct CfgFromDev {
     bool half() const { return dup || reuse == LT_EVAL_REUSE || reuse == LT_EVAL_SLG_STORE || reuse == LT_EVAL_SLG_COND; }
 };
 
+// seg: LT_SEG_WHOLE - the evaluation of always; otherwise one of the three parts of an evaluation under step caching, cut behind
+// the first pre-norm and behind the last block (forward_graphed's comment in engine.h)
 int run_forward(lt_engine* e, const void* x_in, const float* t_dev, void* out, const lt_step_args* a, int use_cfg,
-                hipStream_t s, const PackedDesc* pk = nullptr, const CfgFromDev* gs = nullptr) {
+                hipStream_t s, const PackedDesc* pk = nullptr, const CfgFromDev* gs = nullptr, int seg = LT_SEG_WHOLE) {
     const lt_config& c = e->cfg;
     const VariantDesc& v = e->v;
     const int B = a->batch, p = c.patch_size;
@@ -456,6 +458,18 @@ int run_forward(lt_engine* e, const void* x_in, const float* t_dev, void* out, c
                v.labels ? "lt_prepare_labels" : "lt_prepare_prompt", e->prompt_B, gs && gs->half() ? 2 * B : B);
     LT_REQUIRE(e->reg_Y == 0 || (B == 2 && !pk), "regional captions: one image per call (batch 2 = cond + uncond row), tensor input");
     LT_REQUIRE(e->skip.empty() || (!pk && (int)e->skip.size() < e->L), "layer skip: a tensor input and a set that leaves a layer (SkipScope::set)");
+    const bool do_head = seg == LT_SEG_WHOLE || seg == LT_SEG_HEAD, do_blocks = seg == LT_SEG_WHOLE || seg == LT_SEG_BLOCKS;
+    e->cache_head[0] = 0;  // (this evaluation rewrites e->x / e->h / e->mod, or uses them up; forward_graphed sets it behind a head segment)
+    if (seg != LT_SEG_WHOLE) {
+        LT_REQUIRE(seg >= LT_SEG_HEAD && seg <= LT_SEG_APPLY, "step caching: unknown segment %d", seg);
+        LT_REQUIRE(!pk, "step caching: a packed batch is not served (tensor input only)");
+        LT_REQUIRE(e->skip.empty(), "step caching: a layer-skip set is not served");
+        LT_REQUIRE(!gs, "step caching: an evaluation that reads its guidance scale from device memory (schedule, rule, reuse, skip-layer) is not served");
+        LT_REQUIRE(!e->moe_rec_on && !e->moe_force_rows, "step caching: MoE routing record / force is not served");
+        LT_REQUIRE(e->reg_Y == 0, "step caching: a regional prompt is not served");
+        if (!e->tally && refuse_if_capturing(s, "step caching")) return 2;  // (e->tally: the engine's own capture, which is how a segment replays)
+        LT_REQUIRE(e->c_hprev && e->c_x0 && e->c_r && e->c_ws, "step caching: the buffers are not allocated (ensure_step_cache)");
+    }
     if (!e->weights_ok && lt_weights_ready(e)) return 2;
     const int d = e->d, L = e->L, H = e->H, Hkv = e->Hkv, hd = e->hd, F = e->F, dkv = e->dkv, A = e->A;
     const int Npad = round_up(N, 64);
@@ -473,7 +487,8 @@ int run_forward(lt_engine* e, const void* x_in, const float* t_dev, void* out, c
 
     // patchify + x_embedder (model.py:777-779) [+ eol token per row]
     const int *ntok_dev = nullptr, *gw_dev = nullptr;
-    if (!pk) {
+    if (!do_head) {  // (a segment behind the head: x_0, h and the modulation are in place)
+    } else if (!pk) {
         ProfScope ps(e, 2, 0, s);
         if (launch_patchify(x_in, a->io_dtype, e->patches, B, c.in_channels, a->latent_h, a->latent_w, p, e->kpad, use_cfg, Wrow, s)) return 1;
     } else if (pk->tab) {  // one launch for all samples; the table was stored by the entry point
@@ -491,7 +506,7 @@ int run_forward(lt_engine* e, const void* x_in, const float* t_dev, void* out, c
         LT_CHECK_HIP(hipMemcpyAsync(e->pk_dev, e->pk_host, 128 * sizeof(int), hipMemcpyHostToDevice, s));
         ntok_dev = e->pk_dev; gw_dev = e->pk_dev + 64;
     }
-    if (gemm(e, e->patches, e->kpad, e->xemb_w, e->kpad, e->x, d, M, d, e->kpad, e->xemb_b, 0, s)) return 1;
+    if (do_head && gemm(e, e->patches, e->kpad, e->xemb_w, e->kpad, e->x, d, M, d, e->kpad, e->xemb_b, 0, s)) return 1;
     if (pk && pk->tab) {
         ProfScope ps(e, 2, 0, s);
         if (!pk_full && launch_fill_pad_packed(e->x, e->pad_token, pk->tab, B, N, d, s)) return 1;
@@ -500,12 +515,14 @@ int run_forward(lt_engine* e, const void* x_in, const float* t_dev, void* out, c
         for (int b = 0; b < B; ++b)
             if (pk_ntok[b] < N && launch_fill_rows_bf16(e->x + ((size_t)b * N + pk_ntok[b]) * d, e->pad_token, N - pk_ntok[b], d, s)) return 1;
     }
-    if (v.eol) {
+    if (v.eol && do_head) {
         ProfScope ps(e, 2, 0, s);
         if (launch_eol_fill(e->x, e->eol_token, B * Hp, Wp, d, s)) return 1;
     }
+    // (host state the blocks read: the same for every segment of an evaluation, whichever of them ran as plain launches)
+    e->moe_tp_live = e->gate_t_all && e->moe_tp_sel && lt_opt(OPT_MOE_TIME_PLAN_HOIST) && !e->moe_force_rows && B <= LT_MOE_PLAN_TIME_MAX_SAMPLES;
     // conditioning: t_embedder (model.py:84-87) + caption / label embedding (hoisted) -> adaLN vectors of every layer + final
-    {
+    if (do_head) {
         ProfScope ps(e, 2, 0, s);
         const int fused_pro = lt_opt(OPT_PROLOGUE_FUSED);  // round 6, bit mask: 1 timestep features, 2 temb + embedding, 4 prep_mod - each one launch less, bit-identical (LinearSmallMExtra)
         if (fused_pro & 1) {
@@ -518,7 +535,6 @@ int run_forward(lt_engine* e, const void* x_in, const float* t_dev, void* out, c
         }
         if (launch_linear_small_m(e->t1, e->t2_w, e->t2_b, e->temb, B, A, A, 1, s)) return 1;
         if (e->gate_t_all && launch_linear_small_m(e->temb, e->gate_t_all, nullptr, e->moe_logits, B, L * e->E, A, 0, s)) return 1;  // every layer's time-router logits
-        e->moe_tp_live = e->gate_t_all && e->moe_tp_sel && lt_opt(OPT_MOE_TIME_PLAN_HOIST) && !e->moe_force_rows && B <= LT_MOE_PLAN_TIME_MAX_SAMPLES;
         if (e->moe_tp_live) {  // ... and every layer's time plan: they depend on nothing else (one launch instead of L)
             MoeArgs m;
             m.x = nullptr; m.gate_w = nullptr; m.forced = nullptr; m.sample_logits = e->moe_logits; m.sample_ld = L * e->E;
@@ -613,7 +629,7 @@ int run_forward(lt_engine* e, const void* x_in, const float* t_dev, void* out, c
     auto nx = [&](int l) { int n = l + 1; while (n < L && skipped(n)) ++n; return n; };
     const int first = nx(-1);  // (< L: the set is distinct and shorter than L, checked before the first launch)
     // first pre-norm: modulate(attention_norm(x), [shift,] scale) (model.py:599 / models.py:785 / lumina_t2i model.py:600)
-    {
+    if (do_head) {
         ProfScope ps(e, 2, 0, s);
         NormModArgs n;
         n.x = e->x; n.w = v.pre_w ? e->lw[first].attn_norm1 : nullptr; n.scale = chunk(first, v.i_scale[0]); n.shift = chunk(first, v.i_shift[0]);
@@ -621,8 +637,14 @@ int run_forward(lt_engine* e, const void* x_in, const float* t_dev, void* out, c
         n.out_pair = pair;
         if (launch_rmsnorm_mod(n, s)) return 1;
     }
+    if (seg == LT_SEG_HEAD) {  // step caching, first cut: the indicator on h (in the layout this key's evaluations leave it in), x_0 kept
+        ProfScope ps(e, 2, 0, s);
+        if (launch_cache_indicator(e->h, e->c_hprev, (long long)M * d, e->c_ws, e->c_ws + 2 * LT_CACHE_BLOCKS, s)) return 1;
+        LT_CHECK_HIP(hipMemcpyAsync(e->c_x0, e->x, (size_t)M * d * sizeof(u16), hipMemcpyDeviceToDevice, s));
+        return 0;
+    }
     const int post_mode = v.post ? 1 : 0, gate_mode = 0;  // gates arrive ready (tanh applied above where the family has it)
-    for (int l = first; l < L; l = nx(l)) {
+    for (int l = do_blocks ? first : L; l < L; l = nx(l)) {
         LayerW& w = e->lw[l];
         const int nl = nx(l);  // the layer h is prepared for at this block's end
         // V^T epilogue path: q | k columns in one GEMM, the V columns in a second one that writes e->vt directly.  Large problems
@@ -812,6 +834,15 @@ int run_forward(lt_engine* e, const void* x_in, const float* t_dev, void* out, c
             if (launch_gated_residual_norm(g, s)) return 1;
         }
     }
+    if (seg == LT_SEG_BLOCKS) {  // step caching, second cut: r = bfr(x_L - x_0) for the evaluations that leave the stack out
+        ProfScope ps(e, 2, 0, s);
+        if (launch_cache_residual_store(e->x, e->c_x0, e->c_r, (long long)M * d, s)) return 1;
+    } else if (seg == LT_SEG_APPLY) {  // ... and such an evaluation: x = bfr(x_0 + r), then what the last block's closing kernel does to x_L
+        ProfScope ps(e, 2, 0, s);
+        const u16* fin = e->mod + (size_t)L * cd;
+        if (launch_cache_residual_apply(e->x, e->c_r, v.final_chunks == 2 ? fin + d : fin, v.final_chunks == 2 ? fin : nullptr, e->ld_mod, e->h, M, N, d, s))
+            return 1;
+    }
     if (gemm(e, e->h, d, e->final_w, d, e->frows, e->nfinal, M, e->nfinal, d, e->final_b, 0, s)) return 1;
     {
         ProfScope ps(e, 2, 0, s);
@@ -945,8 +976,8 @@ int softmax_scale_for(const lt_engine* e, const lt_step_args* a, int N, float* s
     return 0;
 }
 
-int forward_graphed(lt_engine* e, const void* x_in, const float* t_dev, void* out, const lt_step_args* a, int use_cfg, hipStream_t s,
-                    const PackedCall* pc, const float* cfg_dev, bool cond_only, bool rule, int reuse) {
+static int forward_graphed_body(lt_engine* e, const void* x_in, const float* t_dev, void* out, const lt_step_args* a, int use_cfg, hipStream_t s,
+                               const PackedCall* pc, const float* cfg_dev, bool cond_only, bool rule, int reuse, int segment) {
     // a stage of the guidance schedule: the scale travels through e->g_cfg - on the eager path too, so both run one kernel - and the key
     // holds a zeroed cfg_scale; the conditional-only evaluation has a->batch / 2 rows
     lt_step_args own;
@@ -972,7 +1003,7 @@ int forward_graphed(lt_engine* e, const void* x_in, const float* t_dev, void* ou
     }
     // one evaluation as plain launches; a packed batch's flat state goes through the ragged kernels
     auto run = [&](const void* x, const float* t, void* o, hipStream_t st) {
-        if (!pc) return run_forward(e, x, t, o, a, use_cfg, st, nullptr, cd);
+        if (!pc) return run_forward(e, x, t, o, a, use_cfg, st, nullptr, cd, segment);
         PackedDesc pk{nullptr, nullptr, pc->hw};
         pk.x_flat = x; pk.out_flat = o; pk.tab = e->pk_tab;
         return run_forward(e, nullptr, t, nullptr, a, use_cfg, st, &pk);
@@ -1001,8 +1032,9 @@ int forward_graphed(lt_engine* e, const void* x_in, const float* t_dev, void* ou
     // ... and whether the scale comes from device memory / the evaluation is the conditional-only one / the guided one under a rescale or
     // norm-limit rule: other closing kernels (the rule's parameters are read from device memory, like the scale)
     // ... and whether the evaluation stores or reuses the cond - uncond difference: the third closing kernel, in its two modes
-    const int extra[14] = {use_cfg, e->prompt_B, e->prompt_T, e->prompt_Tpad, e->reg_Y, e->reg_h, e->reg_w, lt_opt_generation(), lt_opt_engine_generation(),
-                           e->softmax_rule, cd ? 1 : 0, cond_only ? 1 : 0, cd && cd->rule ? 1 : 0, reuse};
+    // ... and the segment of an evaluation under step caching (0: the whole evaluation)
+    const int extra[15] = {use_cfg, e->prompt_B, e->prompt_T, e->prompt_Tpad, e->reg_Y, e->reg_h, e->reg_w, lt_opt_generation(), lt_opt_engine_generation(),
+                           e->softmax_rule, cd ? 1 : 0, cond_only ? 1 : 0, cd && cd->rule ? 1 : 0, reuse, segment};
     std::vector<char> key(sizeof(lt_step_args) + sizeof(extra));
     memcpy(key.data(), a, sizeof(lt_step_args));
     memcpy(key.data() + sizeof(lt_step_args), extra, sizeof(extra));
@@ -1060,16 +1092,50 @@ int forward_graphed(lt_engine* e, const void* x_in, const float* t_dev, void* ou
             return run(x_in, t_dev, out, s);
         }
     }
-    LT_CHECK_HIP(hipMemcpyAsync(e->g_x, x_in, sbytes, hipMemcpyDeviceToDevice, s));
+    // (step caching: the head segment reads the state, the other two do not; the blocks read the times again - staged for every segment, so
+    //  that no replay depends on which of the evaluation's segments ran as plain launches)
+    if (segment == LT_SEG_WHOLE || segment == LT_SEG_HEAD) LT_CHECK_HIP(hipMemcpyAsync(e->g_x, x_in, sbytes, hipMemcpyDeviceToDevice, s));
     LT_CHECK_HIP(hipMemcpyAsync(e->g_t, t_dev, (size_t)B * sizeof(float), hipMemcpyDeviceToDevice, s));
     LT_CHECK_HIP(hipGraphLaunch(ge->exec, s));
     e->last_pair = ge->pair;  // (a replay is an evaluation too: "last_pair" of lt_engine_get_option names the regime of the last one)
-    if (reuse != LT_EVAL_SLG_STORE)  // (the skip evaluation's closing kernel writes e->g_skip and nothing else)
+    if (reuse != LT_EVAL_SLG_STORE && segment != LT_SEG_HEAD)  // (the skip evaluation's closing kernel writes e->g_skip and nothing else; a head segment no output)
         LT_CHECK_HIP(hipMemcpyAsync(out, e->g_out, half ? 2 * sbytes : sbytes, hipMemcpyDeviceToDevice, s));
     ++e->graph_replays;
     if (e->prof_on)
         for (int k = 0; k < 3; ++k)
             if ((e->prof_mask >> k) & 1) { e->prof[k].flops += ge->tally.flops[k]; e->prof[k].launches += ge->tally.launches[k]; }
+    return 0;
+}
+
+int forward_graphed(lt_engine* e, const void* x_in, const float* t_dev, void* out, const lt_step_args* a, int use_cfg, hipStream_t s,
+                    const PackedCall* pc, const float* cfg_dev, bool cond_only, bool rule, int reuse, int segment) {
+    // e->cache_head (step caching): which head segment's e->x / e->h / e->mod are in place.  Kept here, not in run_forward: a replay runs none
+    // of run_forward's host code
+    const int sig[5] = {a->batch, a->latent_h, a->latent_w, a->io_dtype, use_cfg};
+    if (segment != LT_SEG_WHOLE) {
+        LT_REQUIRE(!pc, "step caching: a packed batch is not served (tensor input only)");
+        LT_REQUIRE(!cfg_dev && !cond_only && !rule && reuse == LT_EVAL_PLAIN, "step caching: an evaluation that reads its guidance scale from device "
+                   "memory (schedule, rule, reuse, skip-layer) is not served");
+        LT_REQUIRE(segment == LT_SEG_HEAD || memcmp(e->cache_head, sig, sizeof sig) == 0, "step caching: this evaluation does not follow its probe - "
+                   "the head of an evaluation of the same step arguments, with no other evaluation between");
+    }
+    e->cache_head[0] = 0;
+    const int rc = forward_graphed_body(e, x_in, t_dev, out, a, use_cfg, s, pc, cfg_dev, cond_only, rule, reuse, segment);
+    if (rc == 0 && segment == LT_SEG_HEAD) memcpy(e->cache_head, sig, sizeof sig);
+    return rc;
+}
+
+// the buffers of step caching: three token streams of the engine's largest evaluation, the indicator's partials with its two
+// result words behind them, and the page-locked pair the controller reads
+int ensure_step_cache(lt_engine* e) {
+    if (e->c_sums_host) return 0;
+    const size_t words = (size_t)e->cfg.max_batch * e->cfg.max_tokens * e->d;
+    void* q = nullptr;
+    if (!e->c_hprev) { if (dev_alloc(e, &q, words * sizeof(u16))) return 1; e->c_hprev = (u16*)q; }  // (zeroed: the first probe reads it)
+    if (!e->c_x0) { if (dev_alloc(e, &q, words * sizeof(u16), false)) return 1; e->c_x0 = (u16*)q; }
+    if (!e->c_r) { if (dev_alloc(e, &q, words * sizeof(u16), false)) return 1; e->c_r = (u16*)q; }
+    if (!e->c_ws) { if (dev_alloc(e, &q, (2 * LT_CACHE_BLOCKS + 2) * sizeof(double))) return 1; e->c_ws = (double*)q; }
+    LT_CHECK_HIP(hipHostMalloc((void**)&e->c_sums_host, 2 * sizeof(double), hipHostMallocDefault));
     return 0;
 }
 
@@ -1298,6 +1364,7 @@ extern "C" void lt_destroy(lt_engine* e) {
     for (auto& b : e->allocs) (void)hipFree(b.p);
     e->times.release();
     e->rk.release();
+    if (e->c_sums_host) (void)hipHostFree(e->c_sums_host);
     if (e->pk_dev) (void)hipFree(e->pk_dev);
     if (e->pk_tab) (void)hipFree(e->pk_tab);
     if (e->reg_txt) (void)hipFree(e->reg_txt);
@@ -1370,6 +1437,7 @@ extern "C" int lt_prepare_prompt(lt_engine* e, const void* cap_feats_dev, int32_
                                  int32_t B, int32_t T, void* stream) {
     LT_REQUIRE(e && cap_feats_dev && cap_mask_dev, "lt_prepare_prompt: null argument");
     e->delta_sig[0] = 0;  // (guidance reuse: a stored difference belongs to the conditioning it was taken on)
+    e->cache_res[0] = 0; e->cache_head[0] = 0;  // (step caching: so does a stored residual, and a probe)
     LtOptScope opt_scope(&e->opts);
     LT_REQUIRE(e->v.text, "lt_prepare_prompt: this variant is class-conditional (use lt_prepare_labels)");
     hipStream_t s = (hipStream_t)stream;
@@ -1397,6 +1465,7 @@ extern "C" int lt_prepare_prompt_regional(lt_engine* e, const void* cap_feats_de
                                           int32_t Tg, int32_t h_split, int32_t w_split, void* stream) {
     LT_REQUIRE(e && cap_feats_dev && cap_mask_dev && global_feats_dev && global_mask_dev, "lt_prepare_prompt_regional: null argument");
     e->delta_sig[0] = 0;  // (guidance reuse: a stored difference belongs to the conditioning it was taken on)
+    e->cache_res[0] = 0; e->cache_head[0] = 0;  // (step caching: so does a stored residual, and a probe)
     if (refuse_if_capturing((hipStream_t)stream, "lt_prepare_prompt_regional")) return 2;  // (allocates, uploads a host table, synchronises)
     LtOptScope opt_scope(&e->opts);
     LT_REQUIRE(e->cfg.variant == LT_VARIANT_NEXT_T2I, "lt_prepare_prompt_regional: text-conditional Next-DiT only");
@@ -1442,6 +1511,7 @@ extern "C" int lt_prepare_prompt_regional(lt_engine* e, const void* cap_feats_de
 extern "C" int lt_prepare_labels(lt_engine* e, const int32_t* labels_dev, int32_t B, void* stream) {
     LT_REQUIRE(e && labels_dev, "lt_prepare_labels: null argument");
     e->delta_sig[0] = 0;  // (guidance reuse: a stored difference belongs to the conditioning it was taken on)
+    e->cache_res[0] = 0; e->cache_head[0] = 0;  // (step caching: so does a stored residual, and a probe)
     LtOptScope opt_scope(&e->opts);
     LT_REQUIRE(e->v.labels, "lt_prepare_labels: this variant is text-conditional (use lt_prepare_prompt)");
     LT_REQUIRE(B >= 1 && B <= e->cfg.max_batch, "label batch %d exceeds max_batch %d", B, e->cfg.max_batch);

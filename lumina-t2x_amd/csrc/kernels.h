@@ -384,6 +384,17 @@ int launch_unpatchify_cfg_slg(const u16* rows, int ld, void* out, int out_dtype,
                               hipStream_t stream);
 // g_cfg[0] = cfg_scale, g_cfg[3] = slg_scale (the engine's four scale words, engine.h)
 int launch_slg_params_store(float* g_cfg, float cfg_scale, float slg_scale, hipStream_t stream);
+// step caching (step_cache.hip).  n: words, whole 16-byte chunks; the launch geometry is fixed (LT_CACHE_BLOCKS blocks of 256)
+//   cache_indicator: sums[0] = sum |h - h_prev|, sums[1] = sum |h_prev| in float64, then h_prev <- h; partials: 2 * LT_CACHE_BLOCKS doubles,
+//   every one written by every launch.  h and h_prev in the same layout (row-major or row-pair: the sums are elementwise)
+//   cache_residual_store: r = bfr(xl - x0)
+//   cache_residual_apply: x <- bfr(x + r) in place, h = the final layer's LayerNorm (no affine, eps 1e-6) + modulate of it, row-major -
+//   launch_gated_residual_norm without post-norm and gate (gate_mode 2), next_mode 2; scale holds bf16(1 + scale), shift may be null
+constexpr int LT_CACHE_BLOCKS = 512;
+int launch_cache_indicator(const u16* h, u16* h_prev, long long n, double* partials, double* sums, hipStream_t stream);
+int launch_cache_residual_store(const u16* xl, const u16* x0, u16* r, long long n, hipStream_t stream);
+int launch_cache_residual_apply(u16* x, const u16* r, const u16* scale, const u16* shift, int ld_mod, u16* h, int rows, int rows_per_batch, int d,
+                                hipStream_t stream);
 // torchdiffeq fixed-grid state arithmetic (modes documented in misc.hip)
 int launch_ode_combine(int mode, const void* y0, const void* k1, const void* k2, const void* k3, const void* k4,
                        void* out, int dtype, float dt, long long n, hipStream_t stream);

@@ -699,6 +699,19 @@ extern "C" int lt_op_unpatchify_cfg_slg(const void* rows, int32_t ld, void* out,
     return launch_unpatchify_cfg_slg((const u16*)rows, ld, out, out_dtype, B, C, out_ch, H, W, patch, cfg_scale_dev, slg_scale_dev, cfg_channels,
                                      wp_stride, (u16*)skip_dev, mode, (hipStream_t)stream);
 }
+extern "C" int32_t lt_op_cache_ws_bytes(void) { return (int32_t)(2 * LT_CACHE_BLOCKS * sizeof(double)); }
+extern "C" int lt_op_cache_indicator(const void* h_dev, void* h_prev_dev, int64_t n, void* ws_dev, double* sums_dev, void* stream) {
+    return launch_cache_indicator((const u16*)h_dev, (u16*)h_prev_dev, (long long)n, (double*)ws_dev, sums_dev, (hipStream_t)stream);
+}
+extern "C" int lt_op_cache_residual_store(const void* xl_dev, const void* x0_dev, void* r_dev, int64_t n, void* stream) {
+    return launch_cache_residual_store((const u16*)xl_dev, (const u16*)x0_dev, (u16*)r_dev, (long long)n, (hipStream_t)stream);
+}
+extern "C" int lt_op_cache_residual_apply(void* x_dev, const void* r_dev, const void* scale1p_dev, const void* shift_dev, int32_t ld_mod, void* h_dev,
+                                          int32_t B, int32_t N, int32_t d, void* stream) {
+    LT_REQUIRE(B >= 1 && N >= 1 && d >= 8 && ld_mod >= d, "lt_op_cache_residual_apply: bad shape");
+    return launch_cache_residual_apply((u16*)x_dev, (const u16*)r_dev, (const u16*)scale1p_dev, (const u16*)shift_dev, ld_mod, (u16*)h_dev, B * N, N, d,
+                                       (hipStream_t)stream);
+}
 extern "C" int lt_op_region_text_combine(void* out, const void* txt, const void* gate, int32_t Y, int32_t N, int32_t H, int32_t hd, int32_t Hp,
                                          int32_t Wp, int32_t h_split, int32_t w_split, void* stream) {
     return launch_region_text_combine((u16*)out, (const u16*)txt, (const u16*)gate, Y, N, H, hd, Hp, Wp, h_split, w_split, (hipStream_t)stream);

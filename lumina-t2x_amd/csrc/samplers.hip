@@ -30,6 +30,23 @@ int check_step_shape(const lt_engine* e, const char* who, const lt_step_args* a)
     return 0;
 }
 
+// Step caching (transport/cache.py: CacheController is the definition): the accumulator of one trajectory, in C++ doubles without
+// contraction.  step() takes the indicator sums of an evaluation that is neither the first nor the last and says whether the stack runs
+struct CacheControl {
+    double thr = 0.0, c[5] = {0, 0, 0, 1, 0}, acc = 0.0;
+    double* stats = nullptr;  // null, or ncalls x 3: rel, acc after the add, ran
+    bool step(double s1, double s0, double* rel_out) {
+#pragma clang fp contract(off)
+        if (s0 == 0.0) { *rel_out = INFINITY; return true; }  // (nothing to compare with: the stack runs, the accumulator takes nothing)
+        const double rel = s1 / s0;
+        double p = c[0];
+        for (int k = 1; k < 5; ++k) p = p * rel + c[k];
+        acc += p;
+        *rel_out = rel;
+        return !(acc < thr);
+    }
+};
+
 // The state of one trajectory: the ping-pong pair e->ys, the caller's record of the states (if any), the evaluation and row counts.
 struct Trajectory {
     lt_engine* e; const lt_step_args* a; int use_cfg; hipStream_t s;
@@ -48,6 +65,10 @@ struct Trajectory {
     const float *slg_host = nullptr, *slg_dev = nullptr;
     const int32_t* skip_host = nullptr;
     int n_skip = 0;
+    // step caching (lt_sample_ode_cached): the controller, the evaluations of the trajectory, those that reused the residual
+    CacheControl* cache = nullptr;
+    int ncalls = 0;
+    long long hits = 0;
     int start(const void* z, void* traj_dev, bool z_in_slot0) {
         traj = traj_dev;
         flips0 = e->layout_flips_total;
@@ -61,6 +82,7 @@ struct Trajectory {
     int eval(const void* y, int call, void* out) {
         ++nfe;
         const float* t = e->times.dev + (size_t)call * a->batch;
+        if (cache) return eval_cached(y, t, call, out);
         if (!cfg_host) { rows += a->batch; return forward_graphed(e, y, t, out, a, use_cfg, s, pc); }
         // scale 1 exactly: the guided output is the conditional one - the cond rows alone, written to both halves
         const bool cond_only = cfg_host[call] == 1.0f;
@@ -68,6 +90,32 @@ struct Trajectory {
         if (slg_host && slg_host[call] != 0.0f) return eval_slg(y, t, call, out, cond_only);
         rows += cond_only ? a->batch / 2 : a->batch;
         return forward_graphed(e, y, t, out, a, 1, s, nullptr, cfg_dev + call, cond_only, cfg_rule);
+    }
+    // an evaluation under step caching: the head segment, the two indicator sums to the host (one synchronisation; the first and the last
+    // evaluation run the stack whatever they are and read nothing), the controller, then the stack + tail or the stored residual + tail
+    int eval_cached(const void* y, const float* t, int call, void* out) {
+        if (int rc = forward_graphed(e, y, t, nullptr, a, use_cfg, s, nullptr, nullptr, false, false, LT_EVAL_PLAIN, LT_SEG_HEAD)) return rc;
+        bool run = true;
+        double rel = 0.0;
+        if (call > 0 && call < ncalls - 1) {
+            LT_CHECK_HIP(hipMemcpyAsync(e->c_sums_host, e->c_ws + 2 * LT_CACHE_BLOCKS, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
+            LT_CHECK_HIP(hipStreamSynchronize(s));
+            run = cache->step(e->c_sums_host[0], e->c_sums_host[1], &rel);
+        }
+        if (cache->stats) { cache->stats[3 * call] = rel; cache->stats[3 * call + 1] = cache->acc; cache->stats[3 * call + 2] = run ? 1.0 : 0.0; }
+        if (run) {
+            cache->acc = 0.0;
+            rows += a->batch;
+            e->cache_res[0] = 0;  // (until the evaluation that rewrites the residual has been issued whole)
+            if (int rc = forward_graphed(e, y, t, out, a, use_cfg, s, nullptr, nullptr, false, false, LT_EVAL_PLAIN, LT_SEG_BLOCKS)) return rc;
+            set_cache_res(e, a, use_cfg);
+            return 0;
+        }
+        ++hits;
+        return forward_graphed(e, y, t, out, a, use_cfg, s, nullptr, nullptr, false, false, LT_EVAL_PLAIN, LT_SEG_APPLY);
+    }
+    static void set_cache_res(lt_engine* e, const lt_step_args* a, int use_cfg) {
+        e->cache_res[0] = a->batch; e->cache_res[1] = a->latent_h; e->cache_res[2] = a->latent_w; e->cache_res[3] = use_cfg ? 1 : 0;
     }
     // a stage of skip-layer guidance with s != 0: the cond rows with the set's blocks left out, their guided channels kept; then
     // the stage's own evaluation - all rows, or the cond rows at scale 1 - whose closing kernel adds s (cond - skip).  Two evaluations
@@ -109,6 +157,7 @@ struct Trajectory {
         if (final_dev) LT_CHECK_HIP(hipMemcpyAsync(final_dev, y0(), sbytes, hipMemcpyDeviceToDevice, s));
         e->last_nfe = nfe;
         e->last_eval_rows = rows;
+        if (cache) e->last_cache_hits = hits;
         e->layout_flips = e->layout_flips_total - flips0;
         return 0;
     }
@@ -137,7 +186,7 @@ struct CfgSchedule { const float* table; const float* rule = nullptr; const int3
 
 int ode_fixed_grid(lt_engine* e, const void* z_dev, void* traj_dev, void* final_dev, const float* tgrid_host, int n_grid, int method, int use_cfg,
                    int t_round, const lt_step_args* a, hipStream_t s, long long n, const PackedCall* pc, const MaskedBlend* mb = nullptr,
-                   const CfgSchedule* cs = nullptr) {
+                   const CfgSchedule* cs = nullptr, CacheControl* cc = nullptr) {
     const int B = a->batch;
     const int stages = method == LT_ODE_EULER ? 1 : (method == LT_ODE_MIDPOINT ? 2 : 4);
     const int ncalls = (n_grid - 1) * stages;
@@ -169,6 +218,7 @@ int ode_fixed_grid(lt_engine* e, const void* z_dev, void* traj_dev, void* final_
         LT_CHECK_HIP(hipMemcpyAsync(e->g_cfg + 1, e->times.dev + (size_t)ncalls * B + ncalls, 2 * sizeof(float), hipMemcpyDeviceToDevice, s));
     Trajectory tr{e, a, use_cfg, s, (size_t)n * (bf ? 2 : 4)};
     tr.pc = pc;
+    tr.cache = cc; tr.ncalls = ncalls;
     if (cs) { tr.cfg_host = cs->table; tr.cfg_dev = e->times.dev + (size_t)ncalls * B; tr.cfg_rule = cs->rule != nullptr; tr.reuse_host = cs->reuse; }
     if (cs && cs->slg) {
         tr.slg_host = cs->slg->table; tr.slg_dev = e->times.dev + (size_t)ncalls * B + ncalls;
@@ -226,6 +276,71 @@ extern "C" int lt_sample_ode(lt_engine* e, const void* z_dev, void* traj_dev, vo
     if (check_step_shape(e, "lt_sample_ode", a)) return 2;
     const long long n = (long long)a->batch * e->cfg.in_channels * a->latent_h * a->latent_w;
     return ode_fixed_grid(e, z_dev, traj_dev, final_dev, tgrid_host, n_grid, method, use_cfg, t_round, a, (hipStream_t)stream, n, nullptr);
+}
+
+// Step caching: what the cached entry points refuse beyond lt_sample_ode's refusals, by name, before anything is launched
+static int check_cached_call(lt_engine* e, const char* who, const lt_step_args* a, int use_cfg) {
+    if (check_step_shape(e, who, a)) return 2;
+    LT_REQUIRE(!use_cfg || a->batch % 2 == 0, "%s: guidance needs an even batch (cond + uncond rows), got %d", who, a->batch);
+    LT_REQUIRE(e->reg_Y == 0, "%s: a regional prompt is prepared (lt_prepare_prompt_regional): step caching does not serve it", who);
+    LT_REQUIRE(!e->moe_rec_on && !e->moe_force_rows, "%s: MoE routing record / force is on: step caching does not serve it", who);
+    LT_REQUIRE(e->skip.empty(), "%s: a layer-skip set is not served", who);
+    LT_REQUIRE(e->prompt_B == a->batch, "%s: %s was called for batch %d, step has batch %d", who, e->v.labels ? "lt_prepare_labels" : "lt_prepare_prompt",
+               e->prompt_B, a->batch);
+    return 0;
+}
+
+extern "C" int lt_sample_ode_cached(lt_engine* e, const void* z_dev, void* traj_dev, void* final_dev, const float* tgrid_host, int32_t n_grid,
+                                    int32_t method, int32_t use_cfg, int32_t t_round, const lt_step_args* a, float threshold,
+                                    const double* coef_host, double* stats_host, void* stream) {
+    LT_REQUIRE(e && z_dev && tgrid_host && a && coef_host, "lt_sample_ode_cached: null argument");
+    if (refuse_if_capturing((hipStream_t)stream, "lt_sample_ode_cached")) return 2;  // (the controller reads the indicator on the host)
+    LtOptScope opt_scope(&e->opts);
+    LT_REQUIRE(n_grid >= 2, "lt_sample_ode_cached: need at least 2 grid points");
+    LT_REQUIRE(method >= LT_ODE_EULER && method <= LT_ODE_RK4, "lt_sample_ode_cached: unknown method %d (step caching serves the fixed-grid methods "
+               "euler, midpoint, rk4; not the multistep and adaptive solvers)", method);
+    LT_REQUIRE(threshold >= 0.0f, "lt_sample_ode_cached: threshold %g is not a number >= 0", (double)threshold);
+    for (int k = 0; k < 5; ++k) LT_REQUIRE(std::isfinite(coef_host[k]), "lt_sample_ode_cached: coefficient %d is not finite", k);
+    if (check_cached_call(e, "lt_sample_ode_cached", a, use_cfg)) return 2;
+    if (ensure_step_cache(e)) return 1;
+    CacheControl cc;
+    cc.thr = (double)threshold;
+    for (int k = 0; k < 5; ++k) cc.c[k] = coef_host[k];
+    cc.stats = stats_host;
+    const long long n = (long long)a->batch * e->cfg.in_channels * a->latent_h * a->latent_w;
+    return ode_fixed_grid(e, z_dev, traj_dev, final_dev, tgrid_host, n_grid, method, use_cfg, t_round, a, (hipStream_t)stream, n, nullptr, nullptr, nullptr,
+                          &cc);
+}
+
+// the single evaluations the host loop of transport/cache.py is built from
+extern "C" int lt_forward_cached(lt_engine* e, const void* x_dev, const float* t_dev, void* out_dev, int32_t mode, int32_t use_cfg, const lt_step_args* a,
+                                 double* sums_host, void* stream) {
+    LT_REQUIRE(e && x_dev && t_dev && a, "lt_forward_cached: null argument");
+    LT_REQUIRE(mode >= LT_CACHE_PROBE && mode <= LT_CACHE_REUSE, "lt_forward_cached: mode %d is not LT_CACHE_PROBE, LT_CACHE_RUN or LT_CACHE_REUSE", mode);
+    LT_REQUIRE(mode == LT_CACHE_PROBE ? sums_host != nullptr : out_dev != nullptr, "lt_forward_cached: null argument (%s)",
+               mode == LT_CACHE_PROBE ? "sums_host" : "out_dev");
+    hipStream_t s = (hipStream_t)stream;
+    if (refuse_if_capturing(s, "lt_forward_cached")) return 2;
+    LtOptScope opt_scope(&e->opts);
+    if (check_cached_call(e, "lt_forward_cached", a, use_cfg)) return 2;
+    if (mode == LT_CACHE_REUSE)
+        LT_REQUIRE(e->cache_res[0] == a->batch && e->cache_res[1] == a->latent_h && e->cache_res[2] == a->latent_w && e->cache_res[3] == (use_cfg ? 1 : 0),
+                   "lt_forward_cached: LT_CACHE_REUSE without a stored residual of this shape (batch %d, latent %dx%d, cfg %d): an LT_CACHE_RUN "
+                   "evaluation under the same conditioning comes first", a->batch, a->latent_h, a->latent_w, use_cfg ? 1 : 0);
+    if (ensure_step_cache(e)) return 1;
+    if (mode == LT_CACHE_PROBE) {
+        if (int rc = forward_graphed(e, x_dev, t_dev, nullptr, a, use_cfg, s, nullptr, nullptr, false, false, LT_EVAL_PLAIN, LT_SEG_HEAD)) return rc;
+        LT_CHECK_HIP(hipMemcpyAsync(e->c_sums_host, e->c_ws + 2 * LT_CACHE_BLOCKS, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
+        LT_CHECK_HIP(hipStreamSynchronize(s));
+        sums_host[0] = e->c_sums_host[0]; sums_host[1] = e->c_sums_host[1];
+        return 0;
+    }
+    if (mode == LT_CACHE_REUSE)
+        return forward_graphed(e, x_dev, t_dev, out_dev, a, use_cfg, s, nullptr, nullptr, false, false, LT_EVAL_PLAIN, LT_SEG_APPLY);
+    e->cache_res[0] = 0;
+    if (int rc = forward_graphed(e, x_dev, t_dev, out_dev, a, use_cfg, s, nullptr, nullptr, false, false, LT_EVAL_PLAIN, LT_SEG_BLOCKS)) return rc;
+    Trajectory::set_cache_res(e, a, use_cfg);
+    return 0;
 }
 
 // lt_sample_ode on a packed batch: z, every trajectory slot and the final state are flat buffers of the size list's layout (packed.hip)
@@ -1115,3 +1230,13 @@ extern "C" int lt_sample_ode_adaptive(lt_engine* e, const void* z_dev, void* tra
 
 extern "C" int64_t lt_last_nfe(lt_engine* e) { return e ? e->last_nfe : -1; }
 extern "C" int64_t lt_last_eval_rows(lt_engine* e) { return e ? e->last_eval_rows : -1; }
+extern "C" int lt_debug_cache_read(lt_engine* e, int32_t which, void* dst_dev, int64_t n, void* stream) {
+    LT_REQUIRE(e && dst_dev, "lt_debug_cache_read: null argument");
+    LT_REQUIRE(e->c_sums_host, "lt_debug_cache_read: the step-cache buffers are not allocated yet");
+    const u16* src[5] = {e->c_hprev, e->c_x0, e->c_r, e->x, e->h};
+    LT_REQUIRE(which >= 0 && which < 5, "lt_debug_cache_read: which %d outside 0..4", which);
+    LT_REQUIRE(n > 0 && n <= (int64_t)e->cfg.max_batch * e->cfg.max_tokens * e->d, "lt_debug_cache_read: %lld words outside the buffer", (long long)n);
+    LT_CHECK_HIP(hipMemcpyAsync(dst_dev, src[which], (size_t)n * sizeof(u16), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return 0;
+}
+extern "C" int64_t lt_last_cache_hits(lt_engine* e) { return e ? e->last_cache_hits : -1; }

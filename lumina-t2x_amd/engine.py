@@ -338,6 +338,64 @@ class DiTEngine:
         _lib.check(rc, "lt_sample_ode")
         return out
 
+    def sample_ode_cached(self, z: torch.Tensor, tgrid, method: str, *, use_cfg: bool, threshold: float, coefficients=(0.0, 0.0, 0.0, 1.0, 0.0),
+                          cfg_scale: float = 1.0, scale_factor: float = 1.0, scale_watershed: float = 1.0, base_seqlen: Optional[int] = None,
+                          proportional_attn: bool = False, t_round_to_state_dtype: bool = True, return_trajectory: bool = True,
+                          ntk_factor: float = 1.0):
+        """``sample_ode`` under step caching (lt_sample_ode_cached): an evaluation whose modulated first-block input barely moved
+        leaves the block stack out and adds the residual the stack produced the last time it ran.  ``transport.cache.sample_teacache`` is the
+        definition.  Returns ``(states or last state, stats [ncalls, 3] float64: rel, acc after the add, ran)``."""
+        from .transport.cache import check_cache_args
+        if not isinstance(z, torch.Tensor):
+            raise LuminaLibError("sample_ode_cached: a packed batch (a list of latents) is not served by step caching")
+        _require_gpu(z, "z")
+        if method not in _lib.ODE_METHODS:
+            raise LuminaLibError(f"sample_ode_cached: step caching is built for the fixed-grid methods {sorted(_lib.ODE_METHODS)}, not '{method}' "
+                                 "(the multistep and adaptive solvers are not served)")
+        try:
+            thr, coef = check_cache_args(threshold, coefficients)
+        except ValueError as exc:
+            raise LuminaLibError(f"sample_ode_cached: {exc}") from None
+        z = z.contiguous()
+        garr, n = _grid_array(tgrid)
+        a = self._step_args(z, cfg_scale, scale_factor, scale_watershed, base_seqlen, proportional_attn, ntk_factor=ntk_factor)
+        out, traj_ptr, fin_ptr = _traj_or_final(z, n, z.shape, return_trajectory)
+        ncalls = max(n - 1, 0) * {"euler": 1, "midpoint": 2, "rk4": 4}[method]
+        stats = (C.c_double * (3 * max(ncalls, 1)))()
+        with torch.cuda.device(self.device):
+            rc = self.lib.lt_sample_ode_cached(self.handle, C.c_void_p(z.data_ptr()), traj_ptr, fin_ptr, garr, n, _lib.ODE_METHODS[method],
+                                               int(use_cfg), int(t_round_to_state_dtype), C.byref(a), thr, (C.c_double * 5)(*coef), stats,
+                                               C.c_void_p(_stream_ptr(self.device)))
+        _lib.check(rc, "lt_sample_ode_cached")
+        return out, torch.tensor(list(stats)[:3 * ncalls], dtype=torch.float64).reshape(ncalls, 3)
+
+    def forward_cached(self, x: torch.Tensor, t: torch.Tensor, mode: str, *, use_cfg: bool, cfg_scale: float = 1.0, scale_factor: float = 1.0,
+                       scale_watershed: float = 1.0, base_seqlen: Optional[int] = None, proportional_attn: bool = False, ntk_factor: float = 1.0):
+        """one evaluation under step caching in its parts (lt_forward_cached).  ``mode`` ``"probe"``: the head of the evaluation; returns the
+        indicator sums ``(S1, S0)`` against the previous probe.  ``"run"`` / ``"reuse"``: the rest of the evaluation that was probed last -
+        the block stack (result: ``forward``'s, the residual kept) or the kept residual in its place; returns the output."""
+        modes = {"probe": _lib.LT_CACHE_PROBE, "run": _lib.LT_CACHE_RUN, "reuse": _lib.LT_CACHE_REUSE}
+        if mode not in modes:
+            raise LuminaLibError(f"forward_cached: mode '{mode}' not in {sorted(modes)}")
+        if not isinstance(x, torch.Tensor):
+            raise LuminaLibError("forward_cached: a packed batch (a list of latents) is not served by step caching")
+        _require_gpu(x, "x")
+        x = x.contiguous()
+        t32 = t.to(device=x.device, dtype=torch.float32).contiguous()
+        a = self._step_args(x, cfg_scale, scale_factor, scale_watershed, base_seqlen, proportional_attn, ntk_factor=ntk_factor)
+        out = None if mode == "probe" else torch.empty_like(x)
+        sums = (C.c_double * 2)()
+        with torch.cuda.device(self.device):
+            rc = self.lib.lt_forward_cached(self.handle, C.c_void_p(x.data_ptr()), C.c_void_p(t32.data_ptr()),
+                                            C.c_void_p(out.data_ptr() if out is not None else 0), modes[mode], int(use_cfg), C.byref(a), sums,
+                                            C.c_void_p(_stream_ptr(self.device)))
+        _lib.check(rc, "lt_forward_cached")
+        return (float(sums[0]), float(sums[1])) if mode == "probe" else out
+
+    def last_cache_hits(self) -> int:
+        """the evaluations of the last ``sample_ode_cached`` call that reused the residual"""
+        return int(self.lib.lt_last_cache_hits(self.handle))
+
     def sample_ode_packed(self, zs, tgrid, method: str, *, use_cfg: bool, cfg_scale: float = 1.0, scale_factor: float = 1.0,
                           scale_watershed: float = 1.0, base_seqlen: Optional[int] = None, proportional_attn: bool = False,
                           t_round_to_state_dtype: bool = True, return_trajectory: bool = True):

@@ -158,6 +158,54 @@ class EngineSamplers:
         return self._engine_sample_ode_cfg_schedule(z, tgrid, method, True, table, kw, return_trajectory=return_trajectory, rescale=rescale,
                                                     norm_limit=norm_limit, reuse=reuse, slg=slg, slg_layers=slg_layers)
 
+    @torch.no_grad()
+    def sample_ode_teacache(self, z, tgrid, *cond, method: str = "euler", threshold: float = 0.0, coefficients=(0.0, 0.0, 0.0, 1.0, 0.0),
+                            return_trajectory: bool = False, host_loop: bool = False, t_round: bool = True, **step_kw):
+        """A fixed-grid trajectory under step caching (the TeaCache rule) in ONE engine call (lt_sample_ode_cached): an evaluation
+        whose timestep-modulated first-block input moved little since the stack last ran leaves the L blocks out and adds the residual they
+        produced then.  ``cond``: the family's conditioning, then ``cfg_scale`` - given (also by keyword): every evaluation is
+        ``forward_with_cfg``'s; left out: the plain ``forward``'s.  ``threshold`` (>= 0; 0: every evaluation runs the stack, the trajectory is
+        ``sample_ode``'s) and ``coefficients`` (five, highest power first; the default is the identity): ``transport.cache`` has the definition.
+        ``host_loop``: run that definition (one probe and one evaluation call per stage) instead of the one call.  Leaves
+        ``self.last_cache_stats`` = dict(stats [ncalls, 3] float64: rel, acc after the add, ran; hits; nfe; rows).  Returns the last state, or
+        all ``len(tgrid)`` states."""
+        from ..transport import cache as TC
+        if not isinstance(z, torch.Tensor):
+            raise _lib.LuminaLibError("sample_ode_teacache: a packed batch (a list of latents) is not served by step caching")
+        names = self._cond_names + ("cfg_scale",)
+        if len(cond) > len(names):
+            raise TypeError(f"sample_ode_teacache takes {names}, got {len(cond)} positional arguments")
+        kw = dict(zip(names, cond), **step_kw)
+        try:
+            TC.check_cache_method(method)
+            TC.check_cache_args(threshold, coefficients)
+        except ValueError as exc:
+            raise _lib.LuminaLibError(str(exc)) from None
+        use_cfg = "cfg_scale" in kw
+        if use_cfg:
+            self._mirror_attention_flags(kw)
+        eng, args = self._engine_sampler_args(z, use_cfg, kw)
+        if host_loop:
+            rows = []
+            out = TC.sample_teacache(TC.EngineEvaluator(eng, use_cfg, args), z, tgrid, method, threshold=threshold, coefficients=coefficients,
+                                     t_round=t_round, stats=rows)
+            stats = torch.tensor([[r, a, float(ran)] for r, a, ran in rows], dtype=torch.float64).reshape(len(rows), 3)
+            hits = int(sum(1 for r in rows if not r[2]))
+            self.last_cache_stats = dict(stats=stats, hits=hits, nfe=len(rows), rows=(len(rows) - hits) * z.shape[0])
+            return out if return_trajectory else out[-1]
+        out, stats = eng.sample_ode_cached(z, tgrid, method, use_cfg=use_cfg, threshold=threshold, coefficients=coefficients,
+                                           t_round_to_state_dtype=t_round, return_trajectory=return_trajectory, **args)
+        self.last_cache_stats = dict(stats=stats, hits=eng.last_cache_hits(), nfe=eng.last_nfe(), rows=eng.last_eval_rows())
+        return out
+
+    def _engine_sample_ode_teacache(self, x, tgrid, method, use_cfg, t_round, kw, threshold, coefficients):
+        """kwargs of forward_with_cfg / forward -> lt_sample_ode_cached; all states"""
+        eng, args = self._engine_sampler_args(x, use_cfg, kw)
+        out, stats = eng.sample_ode_cached(x, tgrid, method, use_cfg=use_cfg, threshold=threshold, coefficients=coefficients,
+                                           t_round_to_state_dtype=t_round, **args)
+        self.last_cache_stats = dict(stats=stats, hits=eng.last_cache_hits(), nfe=eng.last_nfe(), rows=eng.last_eval_rows())
+        return out
+
     def _mirror_attention_flags(self, kw):
         if hasattr(self, "layers") and "proportional_attn" in kw and len(self.layers) and hasattr(self.layers[0], "attention"):
             for layer in self.layers:  # what forward_with_cfg leaves on the module (reference model.py:891-899)

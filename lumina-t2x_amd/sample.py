@@ -174,7 +174,10 @@ def run(args, *, encode_fn=None, cap_feat_dim=None, decode_fn=None, model=None) 
         rule = guidance_rule(args)
         reuse = guidance_reuse(args, sample_fn.__self__.t, table)
         slg = guidance_slg(args, sample_fn.__self__.t)
-        if slg is not None:  # stages that also evaluate the prompt row with some blocks left out and push away from it
+        tea = step_cache(args)
+        if tea:  # evaluations whose first-block input barely moved leave the block stack out (the TeaCache rule)
+            latent = sample_fn(z, model.forward_with_cfg, **tea, **kw)[-1][:1]
+        elif slg is not None:  # stages that also evaluate the prompt row with some blocks left out and push away from it
             if table is None:
                 from .transport import guidance
                 table = guidance.cfg_table(sample_fn.__self__.t, args.sampling_method, args.cfg_scale)
@@ -268,6 +271,29 @@ def guidance_slg(args, tgrid):
         raise SystemExit(f"--slg_*: {exc}") from None
 
 
+def step_cache(args) -> dict:
+    """``--teacache THR`` / ``--teacache_coefficients`` as the sampler's keyword arguments; empty when off: the call it was.  Refused by name
+    together with the guidance options, the multistep and adaptive solvers (combining them is later work)."""
+    thr, coef = getattr(args, "teacache", None), getattr(args, "teacache_coefficients", None)
+    if thr is None:
+        if coef is not None:
+            raise SystemExit("--teacache_coefficients needs --teacache THR")
+        return {}
+    from .transport import cache
+    rule = float(getattr(args, "cfg_rescale", 0.0) or 0.0), getattr(args, "cfg_norm_limit", None)
+    try:
+        cache.refuse_with_teacache(args.sampling_method, cfg_interval=getattr(args, "cfg_interval", None),
+                                   cfg_schedule=None if getattr(args, "cfg_schedule", "constant") == "constant" else args.cfg_schedule,
+                                   cfg_rescale=rule[0], cfg_norm_limit=rule[1],
+                                   cfg_reuse=int(getattr(args, "cfg_reuse", 0) or 0) or bool(getattr(args, "cfg_reuse_per_step", False)),
+                                   slg=getattr(args, "slg_layers", None) or float(getattr(args, "slg_scale", 0.0) or 0.0)
+                                   or getattr(args, "slg_interval", None))
+        thr, coef = cache.check_cache_args(thr, cache.IDENTITY if coef is None else coef)
+    except ValueError as exc:
+        raise SystemExit(f"--teacache: {exc}") from None
+    return dict(teacache=thr, teacache_coefficients=coef)
+
+
 def build_parser() -> argparse.ArgumentParser:
     def none_or_str(v):
         return None if v == "None" else v
@@ -293,6 +319,11 @@ def build_parser() -> argparse.ArgumentParser:
                    help="... whose prediction the guided output is pushed away from: + S * (prompt row - skip row) (0: off)")
     p.add_argument("--slg_interval", type=float, nargs=2, default=None, metavar=("LO", "HI"),
                    help="... on the stages with LO <= t < HI only (t = 0 noise, 1 data; default: all stages)")
+    p.add_argument("--teacache", type=float, default=None, metavar="THR",
+                   help="step caching (the TeaCache rule): leave the block stack out of an evaluation while the accumulated relative change of its "
+                        "first-block input stays below THR, and add the residual the stack produced the last time it ran (default: off)")
+    p.add_argument("--teacache_coefficients", type=float, nargs=5, default=None, metavar=("C4", "C3", "C2", "C1", "C0"),
+                   help="... the polynomial the relative change goes through before it is accumulated, highest power first (default: identity)")
     p.add_argument("--num_sampling_steps", type=int, default=250)
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--ckpt", type=str, required=True)

@@ -369,8 +369,27 @@ class ode:
         return sample_cfg_rule(owner, x, self.t, table, self.sampler_type, rescale=rescale, norm_limit=norm_limit,
                                t_round=self.t_round_to_state_dtype, **model_kwargs)
 
+    def _sample_teacache(self, x, model, threshold, coefficients, model_kwargs, **others):
+        """step caching (transport/cache.py): one engine call for an engine-backed forward / forward_with_cfg; everything else is
+        refused by name - the host loop needs the probe, which only the engine offers"""
+        from .cache import IDENTITY, check_cache_args, refuse_with_teacache
+        refuse_with_teacache(self.sampler_type, packed=isinstance(x, (list, tuple)), **others)
+        check_cache_args(threshold, IDENTITY if coefficients is None else coefficients)
+        target = _engine_target(model)
+        if target is None or not hasattr(target[0], "_engine_sample_ode_teacache"):
+            raise TypeError("step caching (teacache) needs the bound forward / forward_with_cfg of an engine-backed model: the rule probes the "
+                            "head of every evaluation, which only the engine offers")
+        if not getattr(self.drift, "is_plain_velocity", False):
+            raise NotImplementedError("step caching (teacache) is built for the plain velocity as drift")
+        owner, use_cfg = target
+        return owner._engine_sample_ode_teacache(x, self.t, self.sampler_type, use_cfg, self.t_round_to_state_dtype, dict(model_kwargs), threshold,
+                                                 IDENTITY if coefficients is None else coefficients)
+
     def sample(self, x, model, cfg_table=None, cfg_rescale=0.0, cfg_norm_limit=math.inf, cfg_reuse=None, slg_table=None, slg_layers=(),
-               **model_kwargs):
+               teacache=None, teacache_coefficients=None, **model_kwargs):
+        if teacache is not None:  # (None: the call made without it)
+            return self._sample_teacache(x, model, teacache, teacache_coefficients, model_kwargs, cfg_table=cfg_table, cfg_rescale=cfg_rescale,
+                                         cfg_norm_limit=cfg_norm_limit, cfg_reuse=cfg_reuse, slg=slg_table)
         if (cfg_table is not None or cfg_reuse is not None or slg_table is not None
                 or not (float(cfg_rescale) == 0.0 and float(cfg_norm_limit) == math.inf)):
             return self._sample_cfg_schedule(x, model, cfg_table, model_kwargs, cfg_rescale, cfg_norm_limit, cfg_reuse, slg_table, slg_layers)

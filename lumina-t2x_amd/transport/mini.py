@@ -109,9 +109,22 @@ class ODE:
                                t_round=self.t_round_to_state_dtype, **model_kwargs)
 
     def sample(self, x, model, mask=None, x1=None, noise=None, cfg_table=None, cfg_rescale=0.0, cfg_norm_limit=math.inf, cfg_reuse=None,
-               slg_table=None, slg_layers=(), **model_kwargs):
+               slg_table=None, slg_layers=(), teacache=None, teacache_coefficients=None, **model_kwargs):
         if isinstance(x, tuple):
             raise NotImplementedError("tuple states are not part of the sampling path")
+        if teacache is not None:  # step caching (transport/cache.py); None: the call made without it
+            from .cache import IDENTITY, check_cache_args, refuse_with_teacache
+            refuse_with_teacache(self.sampler_type, packed=isinstance(x, list), cfg_table=cfg_table, cfg_rescale=cfg_rescale,
+                                 cfg_norm_limit=cfg_norm_limit, cfg_reuse=cfg_reuse, slg=slg_table,
+                                 mask=next((m for m in (mask, x1, noise) if m is not None), None))
+            coef = IDENTITY if teacache_coefficients is None else teacache_coefficients
+            check_cache_args(teacache, coef)
+            target = _engine_target(model)
+            if target is None or not hasattr(target[0], "_engine_sample_ode_teacache"):
+                raise TypeError("step caching (teacache) needs the bound forward / forward_with_cfg of an engine-backed model: the rule probes "
+                                "the head of every evaluation, which only the engine offers")
+            return target[0]._engine_sample_ode_teacache(x, self.t, self.sampler_type, target[1], self.t_round_to_state_dtype, dict(model_kwargs),
+                                                         teacache, coef)
         if cfg_table is not None or cfg_reuse is not None or slg_table is not None or not rule_is_off(cfg_rescale, cfg_norm_limit):
             if mask is not None or x1 is not None or noise is not None:
                 raise NotImplementedError("a guidance schedule (or skip-layer guidance) and an inpainting mask are not served together")
