@@ -144,18 +144,18 @@ DEPTH = 4
 SETS = [(1,), (1, 2), (0, 1), (3,), (0, 2)]  # one block; an adjacent run; a run from layer 0 on; layer L - 1; layer 0 and a gap
 
 
-def _deep(golden_dir, family):
-    """the family's small model of tests/golden with DEPTH blocks: (cfg, state dict, conditioning)"""
-    key = ("deep", family)
+def _deep(golden_dir, family, device="cuda"):
+    """the family's small model of tests/golden with DEPTH blocks: (cfg, state dict, conditioning on ``device``)"""
+    key = ("deep", family) if device == "cuda" else ("deep", family, device)
     if key not in _CACHE:
         name, _ = FAMILIES[family]
         g = np.load(os.path.join(golden_dir, name + ".npz"), allow_pickle=False)
         cfg = dataclasses.replace(synth.NextDiTConfig(**json.loads(str(g["config"]))), n_layers=DEPTH)
         sd = synth.synth_state_dict(cfg, seed=int(g["seed_w"]))
         if cfg.has_text:
-            cond = (torch.from_numpy(g["cap"]).to("cuda", torch.bfloat16), torch.from_numpy(g["mask"]).cuda())
+            cond = (torch.from_numpy(g["cap"]).to(device, torch.bfloat16), torch.from_numpy(g["mask"]).to(device))
         else:
-            cond = (torch.from_numpy(g["y"]).cuda(),)
+            cond = (torch.from_numpy(g["y"]).to(device),)
         _CACHE[key] = (cfg, sd, cond)
     return _CACHE[key]
 
