@@ -1,0 +1,86 @@
+"""The operator chain of tests/forward_chain.py IS the model (no GPU): its float64 backend against the fp32 oracle, and every wiring mutation
+of the list against the gate.
+
+Gate.  `Torch64` has no rounding inside, the oracle (oracle/nextdit_oracle.py, oracle/variants_oracle.py, fp32, on the same bf16-valued
+weights and inputs) has fp32's: rel_l2(torch64, oracle) measures the oracle's own rounding.  MEASURED below holds the value of every case
+(profiles/forward_chain/CPU_DISTANCES.md is the same table); GATE is 4 times the largest.  A chain that states one argument differently from
+the reference moves the output by far more: the second test runs every mutation of forward_chain.mutations through the float64 backend and
+requires each to move the output by MORE than the gate - which shows both that the gate can see the argument and that the output of the
+fixture depends on it (the condition under which bit equality on the GPU, tests/test_gpu_forward_chain.py, proves anything about it)."""
+import pytest
+
+import forward_chain as FC
+
+# rel_l2(torch64, fp32 oracle), measured; the test prints the value of the run beside it
+MEASURED = {
+    "nextdit_tiny-forward": 9.871e-07, "nextdit_tiny-cfg4": 1.152e-06, "nextdit_tiny-lin2": 1.158e-06, "nextdit_tiny-ntk2": 1.079e-06,
+    "nextdit_tiny_rect-forward": 1.005e-06, "nextdit_tiny_rect-cfg4": 1.295e-06, "nextdit_tiny_rect-lin2": 1.229e-06,
+    "nextdit_tiny_rect-ntk2": 1.216e-06, "nextdit_tiny_gqa-forward": 9.629e-07, "nextdit_tiny_gqa-cfg4": 1.180e-06,
+    "nextdit_tiny_gqa-lin2": 1.080e-06, "nextdit_tiny_gqa-ntk2": 1.111e-06, "imagenet_tiny-forward": 6.833e-07, "imagenet_tiny-cfg4": 2.362e-06,
+    "flag_tiny-forward": 8.041e-07, "flag_tiny-cfg4": 8.164e-07,
+}
+GATE = 4 * max(MEASURED.values())     # 9.45e-6
+
+MODEL_CASES = [(name, mode) for fam, names in FC.GOLDENS.items() for name in names
+               for mode in ("forward", "cfg4") + (("lin2", "ntk2") if fam == "next_t2i" else ())]
+# the cases the mutations run on: guidance 4 on every fixture, both RoPE branches where the family has them, the batch of three images, and
+# the small-row cases of the eps entries
+MUTATION_CASES = [(name, "cfg4") for names in FC.GOLDENS.values() for name in names] + \
+                 [(name, mode) for name in FC.GOLDENS["next_t2i"] for mode in ("lin2", "ntk2")] + \
+                 [("nextdit_tiny", "batch6"), ("nextdit_tiny", "eps"), ("imagenet_tiny", "eps"), ("imagenet_tiny", "eps-unfused"), ("flag_tiny", "eps")]
+
+
+def make_case(golden_dir, name, mode):
+    """-> (case, paths)"""
+    if mode == "batch6":
+        return FC.batch6_case(golden_dir), {}
+    if mode.startswith("eps"):
+        return FC.eps_case(golden_dir, name), {"small_fused": mode == "eps"}
+    return FC.golden_case(golden_dir, name, mode), {}
+
+
+@pytest.mark.parametrize("name,mode", MODEL_CASES)
+def test_float64_chain_is_the_oracle(golden_dir, name, mode):
+    case, paths = make_case(golden_dir, name, mode)
+    got = FC.run(FC.Torch64(case), FC.build(case, paths))
+    err = FC.rel_l2(got, FC.oracle_fp32(case))
+    print(f"{case.name}: rel_l2(torch64, oracle fp32) = {err:.3e} (recorded {MEASURED[case.name]:.3e}, gate {GATE:.3e})")
+    assert err < GATE, (case.name, err, GATE)
+
+
+@pytest.mark.parametrize("name,mode", MUTATION_CASES)
+def test_every_mutation_moves_the_float64_chain_past_the_gate(golden_dir, name, mode):
+    case, paths = make_case(golden_dir, name, mode)
+    steps = FC.build(case, paths)
+    base = FC.run(FC.Torch64(case), steps)
+    err = FC.rel_l2(base, FC.oracle_fp32(case))
+    assert err < GATE, (case.name, "unmutated", err)     # (also the cases that are no fixture call: the batch of three, the small rows)
+    muts = FC.mutations(case, steps)
+    assert muts, case.name
+    missed = []
+    for mname, hook in muts:
+        moved = FC.rel_l2(FC.run(FC.Torch64(case), steps, hook), base)
+        print(f"{case.name}: {mname}: moved {moved:.3e}")
+        if not moved > GATE:
+            missed.append((mname, moved))
+    assert not missed, (case.name, GATE, missed)
+
+
+def test_mutation_list_covers_the_issue(golden_dir):
+    """every entry of the list appears on at least one case, in layer 0 and layer 1 where it is per layer"""
+    seen = set()
+    for name, mode in MUTATION_CASES:
+        case, paths = make_case(golden_dir, name, mode)
+        seen |= {m for m, _ in FC.mutations(case, FC.build(case, paths))}
+    per_layer = ["pre_norms_swapped", "post_norms_swapped", "q_k_norm_weight_swapped", "q_norm_bias_dropped", "qk_ln_eps_1e-6", "ky_ln_eps_1e-6",
+                 "self_scale_without_proportional", "text_scale_with_proportional", "text_gate_heads_exchanged", "rope_branch_flipped"]
+    once = ["l1.reads_layer0_pre_norm", "l1.reads_layer0_post_norm", "l1.chunk_from_layer0:l0.grn_ffn.next_scale",
+            "l1.chunk_from_layer0:l0.grn_ffn.next_shift", "l1.chunk_from_layer0:l1.grn_attn.gate", "l1.chunk_from_layer0:l1.grn_attn.next_scale",
+            "l1.chunk_from_layer0:l1.grn_attn.next_shift", "l1.chunk_from_layer0:l1.grn_ffn.gate", "final_adaln_bias_dropped",
+            "cap_embedder_ln_bias_dropped", "norm_eps_1e-6", "norm_eps_1e-6@prep.l0.ynorm", "norm_eps_1e-6@prep.l1.ynorm", "norm_eps_1e-6@l0.prenorm",
+            "norm_eps_1e-6@l0.grn_attn", "norm_eps_1e-6@l0.grn_ffn", "norm_eps_1e-6@l1.grn_attn", "norm_eps_1e-6@l1.grn_ffn", "final_ln_eps_1e-5",
+            "final_shift_scale_exchanged", "gate_without_tanh:attn", "gate_without_tanh:ffn", "one_plus_scale_as_scale:attn",
+            "one_plus_scale_as_scale:ffn", "one_plus_scale_as_scale:final", "text_bias_from_other_row", "rope_row_col_exchanged", "cfg_channels_3_4", "cfg_pairing_shifted",
+            "eol_token_omitted", "x_embedder_bias_dropped"]
+    want = {f"l{l}.{m}" for m in per_layer for l in (0, 1)} | set(once)
+    assert want <= seen, sorted(want - seen)
