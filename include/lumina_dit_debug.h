@@ -4,6 +4,11 @@
  * the options lt_set_option / lt_engine_set_option accept (A/B measurements, tests; every default is the measured-best setting) and
  * declares the instrumented-kernel entry point and the row kernels' full-argument test entry points.  The option table itself lives in lumina-t2x_amd/csrc/options.hip;
  * tests/test_abi.py keeps this text and the table in step (every name, its range and default).
+ *
+ * Threads.  The promise of lumina_dit.h - two engines can be driven from two threads - covers the ENGINE entry points only.  The operator
+ * entry points (lt_op_*) share process-wide scratch space: the head_dim-96 attention's tail-split workspace is ONE buffer per device for
+ * every stream (csrc/attention_v4_96.hip, own_tail_ws).  Op-level entries must not run concurrently on two streams of one device, from one
+ * thread or from several; calls on one stream at a time, from any thread, are fine.
  */
 #ifndef LUMINA_DIT_DEBUG_H
 #define LUMINA_DIT_DEBUG_H

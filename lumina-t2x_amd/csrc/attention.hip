@@ -1040,11 +1040,7 @@ int launch_attention(const AttnArgs& a, hipStream_t stream) {
         const int nqb3 = (a.N + 255) / 256;
         if (a.trace) {
             LT_REQUIRE(a.hd == 72, "attention trace: the hd 72 kernel is the instrumented one");
-            static bool tdone = false;
-            if (!tdone) {
-                LT_CHECK_HIP(hipFuncSetAttribute((const void*)attn_fwd_kernel_v3<72, true>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM72));
-                tdone = true;
-            }
+            if (ensure_dynamic_lds((const void*)attn_fwd_kernel_v3<72, true>, SMEM72)) return 1;  // (per device, under its mutex)
             hipLaunchKernelGGL((attn_fwd_kernel_v3<72, true>), dim3(a.B * a.H * nqb3), dim3(512), SMEM72, stream, a);
         } else if (a.hd == 72) {
             hipLaunchKernelGGL(attn_fwd_kernel_v3<72>, dim3(a.B * a.H * nqb3), dim3(512), SMEM72, stream, a);

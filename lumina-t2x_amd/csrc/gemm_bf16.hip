@@ -50,16 +50,19 @@ template __global__ void gemm_bf16_pp<2, 4, 1, 1, 0, false, 0, 1, 4>(GemmArgs); 
 }  // namespace lt_gemm
 
 int num_cus() {
-    static int per_dev[64] = {0};  // one entry per device id: a process may drive several devices
+    // one entry per device id: a process may drive several devices.  Atomic: engines on two threads come through here at once; two first
+    // calls both ask the runtime and store the same number
+    static std::atomic<int> per_dev[64];
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) { (void)hipGetLastError(); return 256; }
-    if (per_dev[dev] == 0) {
+    int n = per_dev[dev].load(std::memory_order_relaxed);
+    if (n == 0) {
         hipDeviceProp_t prop;
-        int n = 0;
         if (hipGetDeviceProperties(&prop, dev) == hipSuccess) n = prop.multiProcessorCount;
-        per_dev[dev] = n > 0 ? n : 256;
+        n = n > 0 ? n : 256;
+        per_dev[dev].store(n, std::memory_order_relaxed);
     }
-    return per_dev[dev];
+    return n;
 }
 
 

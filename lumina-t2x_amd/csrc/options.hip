@@ -90,7 +90,7 @@ void lt_opt_set_process(int id, int value) {
 
 void lt_opt_reset_process() {
     for (int i = 0; i < LT_OPT_COUNT; ++i) process().v[i].store(kLtOptDesc[i].def, std::memory_order_relaxed);
-    process().gen.fetch_add(1, std::memory_order_relaxed);
+    process().gen.fetch_add(1, std::memory_order_release);  // (values first, like lt_opt_set_process: the scope's ordering rule holds for a reset too)
 }
 
 LtOptScope::LtOptScope(const LtEngineOptions* o) : prev(tl_scope) {

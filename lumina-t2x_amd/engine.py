@@ -73,8 +73,10 @@ class _SourceCache:
         return not any(t.is_inference() for t in tensors)
 
     def hit(self, tensors, extra=()) -> bool:
-        return (self._src is not None and self._trackable(tensors) and len(self._src) == len(tensors)
-                and all(a is b for a, b in zip(self._src, tensors)) and self._key == self._describe(tensors, extra))
+        # one read of each field: set_option() on another thread may clear() between two of them (a miss then, never a TypeError)
+        src, key = self._src, self._key
+        return (src is not None and self._trackable(tensors) and len(src) == len(tensors)
+                and all(a is b for a, b in zip(src, tensors)) and key == self._describe(tensors, extra))
 
     def store(self, tensors, extra=()) -> None:
         if not self._trackable(tensors):
