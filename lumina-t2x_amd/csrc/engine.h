@@ -7,6 +7,7 @@
 
 #include "../../include/lumina_dit.h"
 #include "common.h"
+#include "eval_kind.h"
 #include "options.h"
 
 struct DevBuf {
@@ -235,7 +236,7 @@ struct lt_engine {
     // residual r = bfr(x_L - x_0) of the last evaluation that ran the stack - max_batch * max_tokens x d bf16 each; behind them the indicator's
     // partial sums and its two float64 result words, and the page-locked pair the host reads them from.  Allocated by the first call that needs
     // them (ensure_step_cache) and kept for the engine's life - captured graphs hold the pointers.
-    // cache_head: { B, H, W, io_dtype, use_cfg } of the head segment whose e->x / e->h / e->mod are in place (B = 0: none; every other evaluation
+    // cache_head: { B, H, W, io_dtype, use_cfg } of the step-caching head whose e->x / e->h / e->mod are in place (B = 0: none; every other evaluation
     // overwrites them and says so); cache_res: { B, H, W, use_cfg } of what c_r holds (B = 0: nothing; every prepare call forgets it)
     u16 *c_hprev = nullptr, *c_x0 = nullptr, *c_r = nullptr;
     double *c_ws = nullptr, *c_sums_host = nullptr;
@@ -259,35 +260,21 @@ struct PackedCall {
 // validates a size list against the engine and the step arguments (refusals by name), fills `pc` and stores the device table on stream s
 // (engine.hip)
 int packed_call_begin(lt_engine* e, const char* who, const int32_t* hw_host, const lt_step_args* a, int use_cfg, PackedCall* pc, hipStream_t s);
-// one model evaluation [+ CFG combine], through a cached HIP graph where that pays (engine.hip); pc: x_in / out are the flat state of a
-// packed batch
-// cfg_dev (lt_sample_ode_cfg_schedule; tensor input only): the evaluation's guidance scale, one float of device memory; it is staged into
-// e->g_cfg, which the closing kernel reads, so the scale is no part of the graph key and a->cfg_scale is ignored.  With cond_only the
-// evaluation is the plain forward of the first a->batch / 2 rows of x_in on the first a->batch / 2 rows of the conditioning that was prepared
-// for a->batch rows, and its output is written to both halves of `out` (a->batch rows).  rule (with cfg_dev): the guided evaluation scales
-// its guided channels by the per-sample factor of the rescale / norm-limit rule whose two parameters the caller has put behind the scale,
-// in e->g_cfg[1..2]; one more bit of the key, and no change to a conditional-only evaluation.  cfg_dev == e->g_cfg: the scale is in place
-// reuse (with cfg_dev, without cond_only and rule): LT_EVAL_STORE - the guided evaluation also stores the cond - uncond difference
-// of its guided channels in e->g_delta; LT_EVAL_REUSE - the first a->batch / 2 rows are evaluated as cond_only evaluates them and the closing
-// kernel guides them with the stored difference, both halves of `out` written.  One more word of the key.  The caller has run ensure_delta
-// and answers for the difference being there
-// skip-layer guidance (with cfg_dev, without cond_only and rule), the three modes of unpatchify_cfg_slg_kernel:
-// LT_EVAL_SLG_STORE - the first a->batch / 2 rows are evaluated as cond_only evaluates them (the caller holds a SkipScope) and their guided
-// channels go to e->g_skip, `out` is not written (may be null); LT_EVAL_SLG_GUIDED - all rows, the closing kernel adds s (cond - skip) with s
-// from e->g_cfg[3]; LT_EVAL_SLG_COND - the cond rows alone, cond + s (cond - skip), both halves of `out` written.  The caller has run
-// ensure_skip_buf and has put s in place
-// segment (with nothing of the above but use_cfg): one part of an evaluation whose block stack may be left out.  The parts hand
-// e->x, e->h, e->mod and the step-cache buffers to each other; one more word of the key, so a cached trajectory replays three graphs
-//   LT_SEG_HEAD   - patchify .. the first pre-norm + modulate, then the indicator sums (e->c_ws) and x_0 kept; reads x_in and t, `out` unused
-//   LT_SEG_BLOCKS - the L blocks, r = bfr(x_L - x_0) stored, the tail: `out` is lt_forward's / lt_forward_cfg's word for word; reads t
-//   LT_SEG_APPLY  - x = bfr(x_0 + r), the final layer's norm + modulate, the tail; no block launches anything
-// The last two follow a head segment of the same step arguments with no other evaluation between (e->cache_head; refused by name otherwise);
-// the caller has run ensure_step_cache and, for LT_SEG_APPLY, answers for the residual being there
-enum { LT_EVAL_PLAIN = 0, LT_EVAL_STORE = 1, LT_EVAL_REUSE = 2, LT_EVAL_SLG_STORE = 3, LT_EVAL_SLG_GUIDED = 4, LT_EVAL_SLG_COND = 5 };
-enum { LT_SEG_WHOLE = 0, LT_SEG_HEAD = 1, LT_SEG_BLOCKS = 2, LT_SEG_APPLY = 3 };
+// What one evaluation is: its kind (eval_kind.h: one line per kind, and what follows from it), and
+// pc - a packed batch: x_in / out are its flat state (LT_KIND_WHOLE only);
+// cfg_dev - the kinds that read their guidance scale from device memory: one float, staged into e->g_cfg, which the closing kernel reads, so
+// the scale is no part of the graph key; cfg_dev == e->g_cfg: the scale is in place.  (LT_KIND_COND_ONLY stages nothing.)
+struct EvalSpec {
+    LtEvalKind kind = LT_KIND_WHOLE;
+    const PackedCall* pc = nullptr;
+    const float* cfg_dev = nullptr;
+};
+// one model evaluation [+ CFG combine], through a cached HIP graph where that pays (engine.hip).  The caller has allocated what the kind keeps
+// (ensure_delta, ensure_skip_buf, ensure_step_cache), has put the rule's parameters / the skip-layer scale in place, and answers for a stored
+// difference or residual being there; a part behind a step-caching head follows a head of the same step arguments with no other evaluation
+// between (e->cache_head; refused by name otherwise)
 int forward_graphed(lt_engine* e, const void* x_in, const float* t_dev, void* out, const lt_step_args* a, int use_cfg, hipStream_t s,
-                    const PackedCall* pc = nullptr, const float* cfg_dev = nullptr, bool cond_only = false, bool rule = false,
-                    int reuse = LT_EVAL_PLAIN, int segment = LT_SEG_WHOLE);
+                    const EvalSpec& spec = {});
 // the buffers of step caching: allocated on the first call, before anything is launched (engine.hip)
 int ensure_step_cache(lt_engine* e);
 // the difference buffer of guidance reuse: allocated on the first call, before anything is launched (engine.hip)

@@ -402,26 +402,44 @@ int ensure_weight_layout(lt_engine* e, bool want, hipStream_t s, bool recording 
     return 0;
 }
 
-// An evaluation of the guidance schedule (forward_graphed's cfg_dev): the closing kernel reads its scale from `scale` (device memory); dup:
-// the conditional-only evaluation - a->batch rows on the first a->batch rows of a conditioning prepared for 2 a->batch, written twice;
-// rule (may be null): rule[0] the rescale blend, rule[1] the norm limit - a guided evaluation then runs guidance_stats and the
-// closing kernel that multiplies by the per-sample factor
-// reuse: LT_EVAL_STORE - the guided evaluation's closing kernel also stores the difference; LT_EVAL_REUSE - a->batch rows on the
-// first half of the conditioning like dup, closed by the kernel that guides them with the stored difference
-// skip-layer guidance: LT_EVAL_SLG_STORE / _COND - a->batch rows on the first half of the conditioning like dup, LT_EVAL_SLG_GUIDED -
-// all rows; closed by unpatchify_cfg_slg_kernel in its three modes, the skip-layer scale behind the rule's words (scale[3])
-struct CfgFromDev {
-    const float* scale; bool dup; const float* rule = nullptr; int reuse = LT_EVAL_PLAIN;
-    // the evaluation has half the rows its output has
-    bool half() const { return dup || reuse == LT_EVAL_REUSE || reuse == LT_EVAL_SLG_STORE || reuse == LT_EVAL_SLG_COND; }
-};
+// The closing step of an evaluation on a tensor state: frows -> `out` in the caller's layout, guided as the kind says.  The kinds that read
+// their scale from device memory find it in e->g_cfg[0], the rule's blend and limit in [1..2], the skip-layer scale in [3]; a half-row kind
+// ran B rows and writes 2 B (the kernels count output rows)
+int close_forward(lt_engine* e, void* out, const lt_step_args* a, int use_cfg, int B, int Wrow, LtEvalKind kind, hipStream_t s) {
+    const lt_config& c = e->cfg;
+    const int p = c.patch_size, Bout = lt_eval_traits(kind).half ? 2 * B : B;
+    const int cfg_ch = a->cfg_channels > 0 ? a->cfg_channels : 3;
+    const int guided_ch = cfg_ch < c.in_channels ? cfg_ch : c.in_channels;  // (the channels the closing kernel guides)
+    const float* g = e->g_cfg;
+    switch (kind) {
+    case LT_KIND_WHOLE: case LT_KIND_CACHE_BLOCKS: case LT_KIND_CACHE_APPLY:
+        return launch_unpatchify_cfg(e->frows, e->nfinal, out, a->io_dtype, B, c.in_channels, c.out_channels, a->latent_h, a->latent_w, p, use_cfg,
+                                     a->cfg_scale, cfg_ch, Wrow, s);
+    case LT_KIND_DEV_GUIDED: case LT_KIND_COND_ONLY:
+        return launch_unpatchify_cfg_dev(e->frows, e->nfinal, out, a->io_dtype, Bout, c.in_channels, c.out_channels, a->latent_h, a->latent_w, p,
+                                         use_cfg, g, cfg_ch, Wrow, kind == LT_KIND_COND_ONLY ? 1 : 0, s);
+    case LT_KIND_RULE:  // guidance_stats, then the kernel that multiplies by the per-sample factor
+        if (launch_guidance_stats(e->frows, e->nfinal, B, c.out_channels, a->latent_h, a->latent_w, p, g, guided_ch, Wrow, e->g_stats, s)) return 1;
+        return launch_unpatchify_cfg_rule(e->frows, e->nfinal, out, a->io_dtype, B, c.in_channels, c.out_channels, a->latent_h, a->latent_w, p,
+                                          use_cfg, g, guided_ch, Wrow, 0, e->g_stats, g + 1, g + 2, nullptr, s);
+    case LT_KIND_REUSE_STORE: case LT_KIND_REUSE_AGAIN:
+        return launch_unpatchify_cfg_reuse(e->frows, e->nfinal, out, a->io_dtype, Bout, c.in_channels, c.out_channels, a->latent_h, a->latent_w, p,
+                                           g, guided_ch, Wrow, e->g_delta, kind == LT_KIND_REUSE_AGAIN ? 1 : 0, s);
+    case LT_KIND_SLG_STORE: case LT_KIND_SLG_GUIDED: case LT_KIND_SLG_COND:
+        return launch_unpatchify_cfg_slg(e->frows, e->nfinal, out, a->io_dtype, Bout, c.in_channels, c.out_channels, a->latent_h, a->latent_w, p,
+                                         g, g + 3, guided_ch, Wrow, e->g_skip, lt_slg_kernel_mode(kind), s);
+    case LT_KIND_CACHE_HEAD: case LT_KIND_COUNT: break;  // (a head returns before the tail)
+    }
+    LT_REQUIRE(false, "model evaluation: kind %d has no closing step", (int)kind);
+}
 
-// seg: LT_SEG_WHOLE - the evaluation of always; otherwise one of the three parts of an evaluation under step caching, cut behind
-// the first pre-norm and behind the last block (forward_graphed's comment in engine.h)
+// kind (eval_kind.h): other than LT_KIND_WHOLE for a tensor state only.  The three parts of an evaluation under step caching are cut behind
+// the first pre-norm and behind the last block
 int run_forward(lt_engine* e, const void* x_in, const float* t_dev, void* out, const lt_step_args* a, int use_cfg,
-                hipStream_t s, const PackedDesc* pk = nullptr, const CfgFromDev* gs = nullptr, int seg = LT_SEG_WHOLE) {
+                hipStream_t s, const PackedDesc* pk = nullptr, LtEvalKind kind = LT_KIND_WHOLE) {
     const lt_config& c = e->cfg;
     const VariantDesc& v = e->v;
+    const LtEvalTraits kt = lt_eval_traits(kind);
     const int B = a->batch, p = c.patch_size;
     if (pk) {
         LT_REQUIRE(c.variant == LT_VARIANT_NEXT_T2I, "packed batches: the text-conditional Next-DiT (LT_VARIANT_NEXT_T2I) only; this engine is variant %d",
@@ -454,20 +472,19 @@ int run_forward(lt_engine* e, const void* x_in, const float* t_dev, void* out, c
     else LT_REQUIRE(Hp <= e->rope_len && Wp <= e->rope_len, "latent grid exceeds the RoPE table (%d)", e->rope_len);
     LT_REQUIRE(a->io_dtype == LT_BF16 || a->io_dtype == LT_F32, "io_dtype must be bf16 or f32");
     // (the conditioning buffers are batch-major: the first B rows of one prepared for 2 B are what a preparation of those rows alone leaves)
-    LT_REQUIRE(e->prompt_B == B || (gs && gs->half() && !pk && e->prompt_B == 2 * B), "%s was called for batch %d, step has batch %d",
-               v.labels ? "lt_prepare_labels" : "lt_prepare_prompt", e->prompt_B, gs && gs->half() ? 2 * B : B);
+    LT_REQUIRE(e->prompt_B == B || (kt.half && e->prompt_B == 2 * B), "%s was called for batch %d, step has batch %d",
+               v.labels ? "lt_prepare_labels" : "lt_prepare_prompt", e->prompt_B, kt.half ? 2 * B : B);
     LT_REQUIRE(e->reg_Y == 0 || (B == 2 && !pk), "regional captions: one image per call (batch 2 = cond + uncond row), tensor input");
     LT_REQUIRE(e->skip.empty() || (!pk && (int)e->skip.size() < e->L), "layer skip: a tensor input and a set that leaves a layer (SkipScope::set)");
-    const bool do_head = seg == LT_SEG_WHOLE || seg == LT_SEG_HEAD, do_blocks = seg == LT_SEG_WHOLE || seg == LT_SEG_BLOCKS;
-    e->cache_head[0] = 0;  // (this evaluation rewrites e->x / e->h / e->mod, or uses them up; forward_graphed sets it behind a head segment)
-    if (seg != LT_SEG_WHOLE) {
-        LT_REQUIRE(seg >= LT_SEG_HEAD && seg <= LT_SEG_APPLY, "step caching: unknown segment %d", seg);
-        LT_REQUIRE(!pk, "step caching: a packed batch is not served (tensor input only)");
-        LT_REQUIRE(e->skip.empty(), "step caching: a layer-skip set is not served");
-        LT_REQUIRE(!gs, "step caching: an evaluation that reads its guidance scale from device memory (schedule, rule, reuse, skip-layer) is not served");
+    LT_REQUIRE(e->skip.empty() || kt.skip_ok, "layer skip: a layer-skip set is not served by an evaluation of kind %d", (int)kind);
+    if (lt_slg_kernel_mode(kind) >= 0) LT_REQUIRE(e->g_skip, "skip-layer guidance: the buffer is not allocated (ensure_skip_buf)");
+    if (kind == LT_KIND_REUSE_STORE || kind == LT_KIND_REUSE_AGAIN) LT_REQUIRE(e->g_delta, "guidance reuse: the buffer is not allocated (ensure_delta)");
+    const bool do_head = kt.reads_x, do_blocks = kind != LT_KIND_CACHE_HEAD && kind != LT_KIND_CACHE_APPLY;
+    e->cache_head[0] = 0;  // (this evaluation rewrites e->x / e->h / e->mod, or uses them up; forward_graphed sets it behind a head)
+    if (kt.cached) {
         LT_REQUIRE(!e->moe_rec_on && !e->moe_force_rows, "step caching: MoE routing record / force is not served");
         LT_REQUIRE(e->reg_Y == 0, "step caching: a regional prompt is not served");
-        if (!e->tally && refuse_if_capturing(s, "step caching")) return 2;  // (e->tally: the engine's own capture, which is how a segment replays)
+        if (!e->tally && refuse_if_capturing(s, "step caching")) return 2;  // (e->tally: the engine's own capture, which is how a part replays)
         LT_REQUIRE(e->c_hprev && e->c_x0 && e->c_r && e->c_ws, "step caching: the buffers are not allocated (ensure_step_cache)");
     }
     if (!e->weights_ok && lt_weights_ready(e)) return 2;
@@ -487,7 +504,7 @@ int run_forward(lt_engine* e, const void* x_in, const float* t_dev, void* out, c
 
     // patchify + x_embedder (model.py:777-779) [+ eol token per row]
     const int *ntok_dev = nullptr, *gw_dev = nullptr;
-    if (!do_head) {  // (a segment behind the head: x_0, h and the modulation are in place)
+    if (!do_head) {  // (a part behind the head: x_0, h and the modulation are in place)
     } else if (!pk) {
         ProfScope ps(e, 2, 0, s);
         if (launch_patchify(x_in, a->io_dtype, e->patches, B, c.in_channels, a->latent_h, a->latent_w, p, e->kpad, use_cfg, Wrow, s)) return 1;
@@ -519,7 +536,7 @@ int run_forward(lt_engine* e, const void* x_in, const float* t_dev, void* out, c
         ProfScope ps(e, 2, 0, s);
         if (launch_eol_fill(e->x, e->eol_token, B * Hp, Wp, d, s)) return 1;
     }
-    // (host state the blocks read: the same for every segment of an evaluation, whichever of them ran as plain launches)
+    // (host state the blocks read: the same for every part of an evaluation, whichever of them ran as plain launches)
     e->moe_tp_live = e->gate_t_all && e->moe_tp_sel && lt_opt(OPT_MOE_TIME_PLAN_HOIST) && !e->moe_force_rows && B <= LT_MOE_PLAN_TIME_MAX_SAMPLES;
     // conditioning: t_embedder (model.py:84-87) + caption / label embedding (hoisted) -> adaLN vectors of every layer + final
     if (do_head) {
@@ -637,7 +654,7 @@ int run_forward(lt_engine* e, const void* x_in, const float* t_dev, void* out, c
         n.out_pair = pair;
         if (launch_rmsnorm_mod(n, s)) return 1;
     }
-    if (seg == LT_SEG_HEAD) {  // step caching, first cut: the indicator on h (in the layout this key's evaluations leave it in), x_0 kept
+    if (kind == LT_KIND_CACHE_HEAD) {  // step caching, first cut: the indicator on h (in the layout this key's evaluations leave it in), x_0 kept
         ProfScope ps(e, 2, 0, s);
         if (launch_cache_indicator(e->h, e->c_hprev, (long long)M * d, e->c_ws, e->c_ws + 2 * LT_CACHE_BLOCKS, s)) return 1;
         LT_CHECK_HIP(hipMemcpyAsync(e->c_x0, e->x, (size_t)M * d * sizeof(u16), hipMemcpyDeviceToDevice, s));
@@ -834,10 +851,10 @@ int run_forward(lt_engine* e, const void* x_in, const float* t_dev, void* out, c
             if (launch_gated_residual_norm(g, s)) return 1;
         }
     }
-    if (seg == LT_SEG_BLOCKS) {  // step caching, second cut: r = bfr(x_L - x_0) for the evaluations that leave the stack out
+    if (kind == LT_KIND_CACHE_BLOCKS) {  // step caching, second cut: r = bfr(x_L - x_0) for the evaluations that leave the stack out
         ProfScope ps(e, 2, 0, s);
         if (launch_cache_residual_store(e->x, e->c_x0, e->c_r, (long long)M * d, s)) return 1;
-    } else if (seg == LT_SEG_APPLY) {  // ... and such an evaluation: x = bfr(x_0 + r), then what the last block's closing kernel does to x_L
+    } else if (kind == LT_KIND_CACHE_APPLY) {  // ... and such an evaluation: x = bfr(x_0 + r), then what the last block's closing kernel does to x_L
         ProfScope ps(e, 2, 0, s);
         const u16* fin = e->mod + (size_t)L * cd;
         if (launch_cache_residual_apply(e->x, e->c_r, v.final_chunks == 2 ? fin + d : fin, v.final_chunks == 2 ? fin : nullptr, e->ld_mod, e->h, M, N, d, s))
@@ -847,26 +864,8 @@ int run_forward(lt_engine* e, const void* x_in, const float* t_dev, void* out, c
     {
         ProfScope ps(e, 2, 0, s);
         const int cfg_ch = a->cfg_channels > 0 ? a->cfg_channels : 3;
-        if (!pk && gs && gs->rule && !gs->dup) {
-            const int rule_ch = cfg_ch < c.in_channels ? cfg_ch : c.in_channels;  // (the channels the closing kernel guides)
-            if (launch_guidance_stats(e->frows, e->nfinal, B, c.out_channels, a->latent_h, a->latent_w, p, gs->scale, rule_ch, Wrow, e->g_stats, s)) return 1;
-            if (launch_unpatchify_cfg_rule(e->frows, e->nfinal, out, a->io_dtype, B, c.in_channels, c.out_channels, a->latent_h, a->latent_w, p,
-                                           use_cfg, gs->scale, rule_ch, Wrow, 0, e->g_stats, gs->rule, gs->rule + 1, nullptr, s)) return 1;
-        } else if (!pk && gs && gs->reuse >= LT_EVAL_SLG_STORE) {  // skip-layer guidance (B: the rows evaluated; the kernel counts output rows)
-            if (launch_unpatchify_cfg_slg(e->frows, e->nfinal, out, a->io_dtype, gs->half() ? 2 * B : B, c.in_channels, c.out_channels, a->latent_h,
-                                          a->latent_w, p, gs->scale, gs->scale + 3, cfg_ch < c.in_channels ? cfg_ch : c.in_channels, Wrow, e->g_skip,
-                                          gs->reuse - LT_EVAL_SLG_STORE, s)) return 1;
-        } else if (!pk && gs && gs->reuse != LT_EVAL_PLAIN) {  // (B: the rows evaluated - 2 B' storing, B' reusing; the kernel counts output rows)
-            const bool again = gs->reuse == LT_EVAL_REUSE;
-            if (launch_unpatchify_cfg_reuse(e->frows, e->nfinal, out, a->io_dtype, again ? 2 * B : B, c.in_channels, c.out_channels, a->latent_h,
-                                            a->latent_w, p, gs->scale, cfg_ch < c.in_channels ? cfg_ch : c.in_channels, Wrow, e->g_delta,
-                                            again ? 1 : 0, s)) return 1;
-        } else if (!pk && gs) {
-            if (launch_unpatchify_cfg_dev(e->frows, e->nfinal, out, a->io_dtype, gs->dup ? 2 * B : B, c.in_channels, c.out_channels, a->latent_h,
-                                          a->latent_w, p, use_cfg, gs->scale, cfg_ch, Wrow, gs->dup ? 1 : 0, s)) return 1;
-        } else if (!pk) {
-            if (launch_unpatchify_cfg(e->frows, e->nfinal, out, a->io_dtype, B, c.in_channels, c.out_channels, a->latent_h,
-                                      a->latent_w, p, use_cfg, a->cfg_scale, cfg_ch, Wrow, s)) return 1;
+        if (!pk) {
+            if (close_forward(e, out, a, use_cfg, B, Wrow, kind, s)) return 1;
         } else if (pk->tab) {
             if (launch_unpatchify_packed(e->frows, e->nfinal, pk->out_flat, a->io_dtype, pk->tab, B, c.in_channels, c.out_channels, p, N, use_cfg,
                                          a->cfg_scale, cfg_ch, s)) return 1;
@@ -977,33 +976,26 @@ int softmax_scale_for(const lt_engine* e, const lt_step_args* a, int N, float* s
 }
 
 static int forward_graphed_body(lt_engine* e, const void* x_in, const float* t_dev, void* out, const lt_step_args* a, int use_cfg, hipStream_t s,
-                               const PackedCall* pc, const float* cfg_dev, bool cond_only, bool rule, int reuse, int segment) {
+                               const EvalSpec& spec) {
+    const PackedCall* pc = spec.pc;
+    const LtEvalKind kind = spec.kind;
+    const LtEvalTraits kt = lt_eval_traits(kind);
     // a stage of the guidance schedule: the scale travels through e->g_cfg - on the eager path too, so both run one kernel - and the key
-    // holds a zeroed cfg_scale; the conditional-only evaluation has a->batch / 2 rows
+    // holds a zeroed cfg_scale; a half-row kind has a->batch / 2 rows (B' rows evaluated, 2 B' written)
     lt_step_args own;
-    const CfgFromDev cfd{e->g_cfg, cond_only, rule && !cond_only ? e->g_cfg + 1 : nullptr, reuse};
-    const CfgFromDev* cd = nullptr;
-    const bool half = cfd.half();  // B' rows evaluated, 2 B' written
-    if (reuse >= LT_EVAL_SLG_STORE)
-        LT_REQUIRE(reuse <= LT_EVAL_SLG_COND && cfg_dev && !cond_only && !rule && e->g_skip && (e->skip.empty() || reuse == LT_EVAL_SLG_STORE),
-                   "skip-layer guidance: an evaluation of its three kinds reads its scales from device memory, runs without a rule, finds the "
-                   "buffer allocated, and only the skip evaluation leaves layers out");
-    else if (reuse != LT_EVAL_PLAIN)
-        LT_REQUIRE(cfg_dev && !cond_only && !rule && e->g_delta, "guidance reuse: an evaluation that stores or reuses the difference reads its scale "
-                   "from device memory, runs without a rule, and finds the buffer allocated");
-    if (cfg_dev) {
+    if (kt.dev_scale) {
         LT_REQUIRE(!pc && a->batch % 2 == 0, "a guidance schedule needs a tensor state with an even batch");
         own = *a;
         own.cfg_scale = 0.f;
-        if (half) own.batch = a->batch / 2;
-        if (!cond_only && cfg_dev != e->g_cfg) LT_CHECK_HIP(hipMemcpyAsync(e->g_cfg, cfg_dev, sizeof(float), hipMemcpyDeviceToDevice, s));
+        if (kt.half) own.batch = a->batch / 2;
+        if (kind != LT_KIND_COND_ONLY && spec.cfg_dev != e->g_cfg)
+            LT_CHECK_HIP(hipMemcpyAsync(e->g_cfg, spec.cfg_dev, sizeof(float), hipMemcpyDeviceToDevice, s));
         a = &own;
-        use_cfg = half ? 0 : 1;
-        cd = &cfd;
+        use_cfg = kt.half ? 0 : 1;
     }
     // one evaluation as plain launches; a packed batch's flat state goes through the ragged kernels
     auto run = [&](const void* x, const float* t, void* o, hipStream_t st) {
-        if (!pc) return run_forward(e, x, t, o, a, use_cfg, st, nullptr, cd, segment);
+        if (!pc) return run_forward(e, x, t, o, a, use_cfg, st, nullptr, kind);
         PackedDesc pk{nullptr, nullptr, pc->hw};
         pk.x_flat = x; pk.out_flat = o; pk.tab = e->pk_tab;
         return run_forward(e, nullptr, t, nullptr, a, use_cfg, st, &pk);
@@ -1022,19 +1014,17 @@ static int forward_graphed_body(lt_engine* e, const void* x_in, const float* t_d
         return run(x_in, t_dev, out, s);  // let the eager path produce the error message
     const size_t sbytes = (pc ? (size_t)pc->elems : (size_t)B * e->cfg.in_channels * a->latent_h * a->latent_w) * (a->io_dtype == LT_BF16 ? 2 : 4);
     const size_t cap_bytes = (size_t)e->cfg.max_batch * e->cfg.in_channels * e->cfg.max_tokens * e->cfg.patch_size * e->cfg.patch_size * 4;
-    if ((half ? 2 * sbytes : sbytes) > cap_bytes) return run(x_in, t_dev, out, s);
+    if ((kt.half ? 2 * sbytes : sbytes) > cap_bytes) return run(x_in, t_dev, out, s);
     // a caller that is capturing ITS stream (torch.cuda.graph around the sampler) cannot launch a graph or start a second capture
     // from inside: hand it plain launches, which its own capture records.  The cache is not touched: a key first seen here would be pinned to
     // the row-major regime of a recorded evaluation (ge->pair) for callers that never capture
     if (stream_capturing(s)) return run(x_in, t_dev, out, s);
     // (both option generations: the process defaults' and this engine's overrides' - kernel selection is baked into a captured graph)
     // ... and the softmax rule: the scale it selects is a kernel argument (qa.out_scale / at.scale)
-    // ... and whether the scale comes from device memory / the evaluation is the conditional-only one / the guided one under a rescale or
-    // norm-limit rule: other closing kernels (the rule's parameters are read from device memory, like the scale)
-    // ... and whether the evaluation stores or reuses the cond - uncond difference: the third closing kernel, in its two modes
-    // ... and the segment of an evaluation under step caching (0: the whole evaluation)
-    const int extra[15] = {use_cfg, e->prompt_B, e->prompt_T, e->prompt_Tpad, e->reg_Y, e->reg_h, e->reg_w, lt_opt_generation(), lt_opt_engine_generation(),
-                           e->softmax_rule, cd ? 1 : 0, cond_only ? 1 : 0, cd && cd->rule ? 1 : 0, reuse, segment};
+    // ... and the kind: every kind is another launch sequence or another closing kernel (what a kind reads from device memory - the scale,
+    // the rule's parameters - is no part of the key)
+    const int extra[11] = {use_cfg, e->prompt_B, e->prompt_T, e->prompt_Tpad, e->reg_Y, e->reg_h, e->reg_w, lt_opt_generation(), lt_opt_engine_generation(),
+                           e->softmax_rule, (int)kind};
     std::vector<char> key(sizeof(lt_step_args) + sizeof(extra));
     memcpy(key.data(), a, sizeof(lt_step_args));
     memcpy(key.data() + sizeof(lt_step_args), extra, sizeof(extra));
@@ -1092,14 +1082,14 @@ static int forward_graphed_body(lt_engine* e, const void* x_in, const float* t_d
             return run(x_in, t_dev, out, s);
         }
     }
-    // (step caching: the head segment reads the state, the other two do not; the blocks read the times again - staged for every segment, so
-    //  that no replay depends on which of the evaluation's segments ran as plain launches)
-    if (segment == LT_SEG_WHOLE || segment == LT_SEG_HEAD) LT_CHECK_HIP(hipMemcpyAsync(e->g_x, x_in, sbytes, hipMemcpyDeviceToDevice, s));
+    // (step caching: the head reads the state, the other two parts do not; the blocks read the times again - staged for every part, so
+    //  that no replay depends on which of the evaluation's parts ran as plain launches)
+    if (kt.reads_x) LT_CHECK_HIP(hipMemcpyAsync(e->g_x, x_in, sbytes, hipMemcpyDeviceToDevice, s));
     LT_CHECK_HIP(hipMemcpyAsync(e->g_t, t_dev, (size_t)B * sizeof(float), hipMemcpyDeviceToDevice, s));
     LT_CHECK_HIP(hipGraphLaunch(ge->exec, s));
     e->last_pair = ge->pair;  // (a replay is an evaluation too: "last_pair" of lt_engine_get_option names the regime of the last one)
-    if (reuse != LT_EVAL_SLG_STORE && segment != LT_SEG_HEAD)  // (the skip evaluation's closing kernel writes e->g_skip and nothing else; a head segment no output)
-        LT_CHECK_HIP(hipMemcpyAsync(out, e->g_out, half ? 2 * sbytes : sbytes, hipMemcpyDeviceToDevice, s));
+    if (kt.writes_out)  // (the skip evaluation's closing kernel writes e->g_skip and nothing else; a step-caching head no output)
+        LT_CHECK_HIP(hipMemcpyAsync(out, e->g_out, kt.half ? 2 * sbytes : sbytes, hipMemcpyDeviceToDevice, s));
     ++e->graph_replays;
     if (e->prof_on)
         for (int k = 0; k < 3; ++k)
@@ -1108,20 +1098,18 @@ static int forward_graphed_body(lt_engine* e, const void* x_in, const float* t_d
 }
 
 int forward_graphed(lt_engine* e, const void* x_in, const float* t_dev, void* out, const lt_step_args* a, int use_cfg, hipStream_t s,
-                    const PackedCall* pc, const float* cfg_dev, bool cond_only, bool rule, int reuse, int segment) {
-    // e->cache_head (step caching): which head segment's e->x / e->h / e->mod are in place.  Kept here, not in run_forward: a replay runs none
-    // of run_forward's host code
+                    const EvalSpec& spec) {
+    // e->cache_head (step caching): which head's e->x / e->h / e->mod are in place.  Kept here, not in run_forward: a replay runs none of
+    // run_forward's host code
     const int sig[5] = {a->batch, a->latent_h, a->latent_w, a->io_dtype, use_cfg};
-    if (segment != LT_SEG_WHOLE) {
-        LT_REQUIRE(!pc, "step caching: a packed batch is not served (tensor input only)");
-        LT_REQUIRE(!cfg_dev && !cond_only && !rule && reuse == LT_EVAL_PLAIN, "step caching: an evaluation that reads its guidance scale from device "
-                   "memory (schedule, rule, reuse, skip-layer) is not served");
-        LT_REQUIRE(segment == LT_SEG_HEAD || memcmp(e->cache_head, sig, sizeof sig) == 0, "step caching: this evaluation does not follow its probe - "
-                   "the head of an evaluation of the same step arguments, with no other evaluation between");
+    if (lt_eval_traits(spec.kind).cached) {
+        LT_REQUIRE(!spec.pc, "step caching: a packed batch is not served (tensor input only)");
+        LT_REQUIRE(spec.kind == LT_KIND_CACHE_HEAD || memcmp(e->cache_head, sig, sizeof sig) == 0, "step caching: this evaluation does not follow "
+                   "its probe - the head of an evaluation of the same step arguments, with no other evaluation between");
     }
     e->cache_head[0] = 0;
-    const int rc = forward_graphed_body(e, x_in, t_dev, out, a, use_cfg, s, pc, cfg_dev, cond_only, rule, reuse, segment);
-    if (rc == 0 && segment == LT_SEG_HEAD) memcpy(e->cache_head, sig, sizeof sig);
+    const int rc = forward_graphed_body(e, x_in, t_dev, out, a, use_cfg, s, spec);
+    if (rc == 0 && spec.kind == LT_KIND_CACHE_HEAD) memcpy(e->cache_head, sig, sizeof sig);
     return rc;
 }
 
@@ -1590,7 +1578,7 @@ extern "C" int lt_forward_cfg_packed(lt_engine* e, const void* x_flat_dev, const
     LtOptScope opt_scope(&e->opts);
     PackedCall pc{};
     if (int rc = packed_call_begin(e, "lt_forward_cfg_packed", hw_host, a, 1, &pc, (hipStream_t)stream)) return rc;
-    return forward_graphed(e, x_flat_dev, t_dev, out_flat_dev, a, 1, (hipStream_t)stream, &pc);
+    return forward_graphed(e, x_flat_dev, t_dev, out_flat_dev, a, 1, (hipStream_t)stream, {LT_KIND_WHOLE, &pc});
 }
 
 extern "C" int lt_forward_cfg(lt_engine* e, const void* x_dev, const float* t_dev, void* out_dev, const lt_step_args* a, void* stream) {

@@ -83,18 +83,23 @@ struct Trajectory {
         ++nfe;
         const float* t = e->times.dev + (size_t)call * a->batch;
         if (cache) return eval_cached(y, t, call, out);
-        if (!cfg_host) { rows += a->batch; return forward_graphed(e, y, t, out, a, use_cfg, s, pc); }
+        if (!cfg_host) return eval_kind(LT_KIND_WHOLE, y, t, out);
         // scale 1 exactly: the guided output is the conditional one - the cond rows alone, written to both halves
         const bool cond_only = cfg_host[call] == 1.0f;
         if (reuse_host && !cond_only) return eval_reuse(y, t, call, out);
         if (slg_host && slg_host[call] != 0.0f) return eval_slg(y, t, call, out, cond_only);
-        rows += cond_only ? a->batch / 2 : a->batch;
-        return forward_graphed(e, y, t, out, a, 1, s, nullptr, cfg_dev + call, cond_only, cfg_rule);
+        return eval_kind(cond_only ? LT_KIND_COND_ONLY : cfg_rule ? LT_KIND_RULE : LT_KIND_DEV_GUIDED, y, t, out, cfg_dev + call);
     }
-    // an evaluation under step caching: the head segment, the two indicator sums to the host (one synchronisation; the first and the last
+    // an evaluation of one kind, its rows counted.  scale: where a kind that reads its guidance scale from device memory finds it
+    int eval_kind(LtEvalKind kind, const void* y, const float* t, void* out, const float* scale = nullptr) {
+        const LtEvalTraits kt = lt_eval_traits(kind);
+        rows += kt.half ? a->batch / 2 : a->batch;
+        return forward_graphed(e, y, t, out, a, kt.dev_scale ? 1 : use_cfg, s, {kind, pc, scale});
+    }
+    // an evaluation under step caching: the head, the two indicator sums to the host (one synchronisation; the first and the last
     // evaluation run the stack whatever they are and read nothing), the controller, then the stack + tail or the stored residual + tail
     int eval_cached(const void* y, const float* t, int call, void* out) {
-        if (int rc = forward_graphed(e, y, t, nullptr, a, use_cfg, s, nullptr, nullptr, false, false, LT_EVAL_PLAIN, LT_SEG_HEAD)) return rc;
+        if (int rc = forward_graphed(e, y, t, nullptr, a, use_cfg, s, {LT_KIND_CACHE_HEAD})) return rc;
         bool run = true;
         double rel = 0.0;
         if (call > 0 && call < ncalls - 1) {
@@ -105,14 +110,14 @@ struct Trajectory {
         if (cache->stats) { cache->stats[3 * call] = rel; cache->stats[3 * call + 1] = cache->acc; cache->stats[3 * call + 2] = run ? 1.0 : 0.0; }
         if (run) {
             cache->acc = 0.0;
-            rows += a->batch;
+            rows += a->batch;  // (the head and the blocks are one evaluation; a reuse counts no rows)
             e->cache_res[0] = 0;  // (until the evaluation that rewrites the residual has been issued whole)
-            if (int rc = forward_graphed(e, y, t, out, a, use_cfg, s, nullptr, nullptr, false, false, LT_EVAL_PLAIN, LT_SEG_BLOCKS)) return rc;
+            if (int rc = forward_graphed(e, y, t, out, a, use_cfg, s, {LT_KIND_CACHE_BLOCKS})) return rc;
             set_cache_res(e, a, use_cfg);
             return 0;
         }
         ++hits;
-        return forward_graphed(e, y, t, out, a, use_cfg, s, nullptr, nullptr, false, false, LT_EVAL_PLAIN, LT_SEG_APPLY);
+        return forward_graphed(e, y, t, out, a, use_cfg, s, {LT_KIND_CACHE_APPLY});
     }
     static void set_cache_res(lt_engine* e, const lt_step_args* a, int use_cfg) {
         e->cache_res[0] = a->batch; e->cache_res[1] = a->latent_h; e->cache_res[2] = a->latent_w; e->cache_res[3] = use_cfg ? 1 : 0;
@@ -121,24 +126,20 @@ struct Trajectory {
     // the stage's own evaluation - all rows, or the cond rows at scale 1 - whose closing kernel adds s (cond - skip).  Two evaluations
     int eval_slg(const void* y, const float* t, int call, void* out, bool cond_only) {
         ++nfe;
-        rows += a->batch / 2;
         {
             SkipScope scope(e);
             if (scope.set("skip-layer guidance", skip_host, n_skip)) return 2;
-            if (int rc = forward_graphed(e, y, t, nullptr, a, 1, s, nullptr, e->g_cfg, false, false, LT_EVAL_SLG_STORE)) return rc;
+            if (int rc = eval_kind(LT_KIND_SLG_STORE, y, t, nullptr, e->g_cfg)) return rc;
         }
         LT_CHECK_HIP(hipMemcpyAsync(e->g_cfg + 3, slg_dev + call, sizeof(float), hipMemcpyDeviceToDevice, s));
-        rows += cond_only ? a->batch / 2 : a->batch;
-        return forward_graphed(e, y, t, out, a, 1, s, nullptr, cond_only ? e->g_cfg : cfg_dev + call, false, false,
-                               cond_only ? LT_EVAL_SLG_COND : LT_EVAL_SLG_GUIDED);
+        return cond_only ? eval_kind(LT_KIND_SLG_COND, y, t, out, e->g_cfg) : eval_kind(LT_KIND_SLG_GUIDED, y, t, out, cfg_dev + call);
     }
     // a guided evaluation of a reuse table: all rows and the difference stored, or the cond rows and the stored difference (the caller has
     // checked that a refresh comes first and has run ensure_delta)
     int eval_reuse(const void* y, const float* t, int call, void* out) {
         const bool again = reuse_host[call] != 0;
-        rows += again ? a->batch / 2 : a->batch;
         if (!again) e->delta_sig[0] = 0;  // (until the evaluation that rewrites it has been issued whole)
-        if (int rc = forward_graphed(e, y, t, out, a, 1, s, nullptr, cfg_dev + call, false, false, again ? LT_EVAL_REUSE : LT_EVAL_STORE)) return rc;
+        if (int rc = eval_kind(again ? LT_KIND_REUSE_AGAIN : LT_KIND_REUSE_STORE, y, t, out, cfg_dev + call)) return rc;
         if (!again) set_delta_sig(e, a);
         return 0;
     }
@@ -329,16 +330,15 @@ extern "C" int lt_forward_cached(lt_engine* e, const void* x_dev, const float* t
                    "evaluation under the same conditioning comes first", a->batch, a->latent_h, a->latent_w, use_cfg ? 1 : 0);
     if (ensure_step_cache(e)) return 1;
     if (mode == LT_CACHE_PROBE) {
-        if (int rc = forward_graphed(e, x_dev, t_dev, nullptr, a, use_cfg, s, nullptr, nullptr, false, false, LT_EVAL_PLAIN, LT_SEG_HEAD)) return rc;
+        if (int rc = forward_graphed(e, x_dev, t_dev, nullptr, a, use_cfg, s, {LT_KIND_CACHE_HEAD})) return rc;
         LT_CHECK_HIP(hipMemcpyAsync(e->c_sums_host, e->c_ws + 2 * LT_CACHE_BLOCKS, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
         LT_CHECK_HIP(hipStreamSynchronize(s));
         sums_host[0] = e->c_sums_host[0]; sums_host[1] = e->c_sums_host[1];
         return 0;
     }
-    if (mode == LT_CACHE_REUSE)
-        return forward_graphed(e, x_dev, t_dev, out_dev, a, use_cfg, s, nullptr, nullptr, false, false, LT_EVAL_PLAIN, LT_SEG_APPLY);
+    if (mode == LT_CACHE_REUSE) return forward_graphed(e, x_dev, t_dev, out_dev, a, use_cfg, s, {LT_KIND_CACHE_APPLY});
     e->cache_res[0] = 0;
-    if (int rc = forward_graphed(e, x_dev, t_dev, out_dev, a, use_cfg, s, nullptr, nullptr, false, false, LT_EVAL_PLAIN, LT_SEG_BLOCKS)) return rc;
+    if (int rc = forward_graphed(e, x_dev, t_dev, out_dev, a, use_cfg, s, {LT_KIND_CACHE_BLOCKS})) return rc;
     Trajectory::set_cache_res(e, a, use_cfg);
     return 0;
 }
@@ -498,7 +498,7 @@ extern "C" int lt_forward_cfg_rule(lt_engine* e, const void* x_dev, const float*
     if (check_rule(who, rescale, norm_limit)) return 2;
     if (check_guided_halves(e, who, a)) return 2;
     if (launch_guidance_params_store(e->g_cfg, a->cfg_scale, rescale, norm_limit, (hipStream_t)stream)) return 1;
-    return forward_graphed(e, x_dev, t_dev, out_dev, a, 1, (hipStream_t)stream, nullptr, e->g_cfg, false, true);
+    return forward_graphed(e, x_dev, t_dev, out_dev, a, 1, (hipStream_t)stream, {LT_KIND_RULE, nullptr, e->g_cfg});
 }
 
 // ---- guidance reuse: the cond - uncond difference taken on refresh stages, reused on half-row stages in between ----------------
@@ -534,8 +534,7 @@ extern "C" int lt_forward_cfg_reuse(lt_engine* e, const void* x_dev, const float
     if (ensure_delta(e)) return 1;
     if (launch_guidance_params_store(e->g_cfg, a->cfg_scale, 0.f, INFINITY, (hipStream_t)stream)) return 1;
     if (mode == 0) e->delta_sig[0] = 0;  // (until the evaluation that rewrites it has been issued whole)
-    if (int rc = forward_graphed(e, x_dev, t_dev, out_dev, a, 1, (hipStream_t)stream, nullptr, e->g_cfg, false, false,
-                                 mode ? LT_EVAL_REUSE : LT_EVAL_STORE))
+    if (int rc = forward_graphed(e, x_dev, t_dev, out_dev, a, 1, (hipStream_t)stream, {mode ? LT_KIND_REUSE_AGAIN : LT_KIND_REUSE_STORE, nullptr, e->g_cfg}))
         return rc;
     if (mode == 0) Trajectory::set_delta_sig(e, a);
     return 0;
@@ -572,10 +571,9 @@ extern "C" int lt_forward_cfg_slg(lt_engine* e, const void* x_dev, const float* 
     {
         SkipScope scope(e);
         if (scope.set(who, skip_host, n_skip)) return 2;
-        if (int rc = forward_graphed(e, x_dev, t_dev, nullptr, &own, 1, s, nullptr, e->g_cfg, false, false, LT_EVAL_SLG_STORE)) return rc;
+        if (int rc = forward_graphed(e, x_dev, t_dev, nullptr, &own, 1, s, {LT_KIND_SLG_STORE, nullptr, e->g_cfg})) return rc;
     }
-    return forward_graphed(e, x_dev, t_dev, out_dev, &own, 1, s, nullptr, e->g_cfg, false, false,
-                           cfg_scale == 1.0f ? LT_EVAL_SLG_COND : LT_EVAL_SLG_GUIDED);
+    return forward_graphed(e, x_dev, t_dev, out_dev, &own, 1, s, {cfg_scale == 1.0f ? LT_KIND_SLG_COND : LT_KIND_SLG_GUIDED, nullptr, e->g_cfg});
 }
 
 // ---- linear multistep sampling: one evaluation per interval, the earlier slopes reused (multistep.hip) -------------------------
