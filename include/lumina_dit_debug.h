@@ -297,6 +297,17 @@ int lt_op_linear_small_m_ext(const void* a, const void* w, const void* b, void* 
                              void* stream);
 int lt_op_moe_route(const void* x, const void* gate_w, const void* forced, int32_t rows, int32_t rows_per_sample, int32_t d, int32_t E, void* sel,
                     void* wts, int32_t max_tiles, void* stream);
+/* lt_op_moe_plan (lumina_dit.h) with every field of MoeArgs (csrc/kernels.h), for tests/test_moe_plan.py and tests/forward_chain.py.
+ *   forced: int32 [rows][2] expert ids (0 .. E - 1, two different ones per row) that replace the top-2 choice, or NULL; with sample_logits the
+ *   weights are still the softmax of the row's own two logits, and the plan runs on the single-workgroup kernel.
+ *   sample_ld: row stride of sample_logits in elements (0 = E).
+ *   layers > 1: the all-layers form of the time router's closed-form plan - layer l reads the logit columns [l * E, l * E + E) of every sample
+ *   (sample_ld >= layers * E) and writes sel / pos / wts at + l * layer_stride_rows elements (even, >= 2 rows), src at + l * layer_stride_src
+ *   (>= 256 max_tiles), tile_expert at + l * layer_stride_tiles (>= max_tiles); words between the layers' slices are not written.  Refused by
+ *   the launcher: layers > 1 without sample_logits, with a forced table, with more than 64 samples or with rows that are not whole samples. */
+int lt_op_moe_plan_ex(void* sel, const void* sample_logits, int32_t sample_ld, const void* forced, void* wts, int32_t rows,
+                      int32_t rows_per_sample, int32_t E, void* pos, void* src, void* tile_expert, int32_t max_tiles, int32_t layers,
+                      int64_t layer_stride_rows, int64_t layer_stride_src, int64_t layer_stride_tiles, void* stream);
 
 /* The two attention launches that build their operands themselves, with every argument the engine fills, for tests/test_gpu_prologue_exact.py.
  *   lt_op_attention_qraw_ex = lt_op_attention_qraw (lumina_dit.h) plus the table-branch select - cs_table / cs_table_t hold two branches,

@@ -223,6 +223,7 @@ _SIGNATURES: Dict[str, tuple] = {
     "lt_op_rope_table": (_i32, [_vp, _i32, _i32, _i32, _f32, _f32, _f32, _f32, _i32, _vp, _vp]),
     "lt_op_linear_small_m_ext": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, C.c_uint32, C.c_uint32, _vp]),
     "lt_op_moe_route": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp]),
+    "lt_op_moe_plan_ex": (_i32, [_vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i64, _i64, _i64, _vp]),
     "lt_op_rope_table_2d": (_i32, [_vp, _i32, _i32, _f32, _f32, _vp]),
     "lt_op_rope_table_2d_pair": (_i32, [_vp, _vp, _i32, _i32, _f32, _f32, _vp]),
     "lt_op_proj_gated_residual_norm": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _f32, _i32, _vp]),

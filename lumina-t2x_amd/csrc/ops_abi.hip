@@ -101,6 +101,28 @@ extern "C" int lt_op_moe_plan(void* sel, const void* sample_logits, void* wts, i
     return launch_moe_plan(m, (hipStream_t)stream);
 }
 
+// lt_op_moe_plan with MoeArgs whole: the parity hook's forced table, the row stride of the logits and the all-layers form.  The launcher's own
+// refusals apply; what it cannot see - that the layers' slices do not overlap - is checked here
+extern "C" int lt_op_moe_plan_ex(void* sel, const void* sample_logits, int32_t sample_ld, const void* forced, void* wts, int32_t rows,
+                                 int32_t rows_per_sample, int32_t E, void* pos, void* src, void* tile_expert, int32_t max_tiles, int32_t layers,
+                                 int64_t layer_stride_rows, int64_t layer_stride_src, int64_t layer_stride_tiles, void* stream) {
+    LT_REQUIRE(sel && pos && src && tile_expert, "lt_op_moe_plan_ex: null pointer");
+    LT_REQUIRE(sample_logits == nullptr || wts != nullptr, "lt_op_moe_plan_ex: routing from per-sample logits writes the weights too");
+    LT_REQUIRE((sample_ld == 0 && layers <= 1) || (sample_logits && E > 0 && (long long)sample_ld >= (long long)(layers > 1 ? layers : 1) * E),
+               "lt_op_moe_plan_ex: sample_ld = %d is shorter than the %d logit columns of a sample", sample_ld, (layers > 1 ? layers : 1) * E);
+    LT_REQUIRE(layers >= 1, "lt_op_moe_plan_ex: layers = %d", layers);
+    LT_REQUIRE(layers == 1 || (rows > 0 && max_tiles > 0 && layer_stride_rows >= 2LL * rows && layer_stride_rows % 2 == 0 &&
+                               layer_stride_src >= 256LL * max_tiles && layer_stride_tiles >= max_tiles),
+               "lt_op_moe_plan_ex: the layer strides (%lld, %lld, %lld) are shorter than one layer's plan (even and >= %lld, >= %lld, >= %d)",
+               (long long)layer_stride_rows, (long long)layer_stride_src, (long long)layer_stride_tiles, 2LL * rows, 256LL * max_tiles, max_tiles);
+    MoeArgs m;
+    m.x = nullptr; m.gate_w = nullptr; m.sample_logits = (const u16*)sample_logits; m.sample_ld = sample_ld; m.forced = (const int*)forced;
+    m.rows = rows; m.rows_per_sample = rows_per_sample > 0 ? rows_per_sample : rows; m.d = 8; m.E = E;
+    m.sel = (int*)sel; m.wts = (u16*)wts; m.pos = (int*)pos; m.src = (int*)src; m.tile_expert = (int*)tile_expert; m.max_tiles = max_tiles;
+    m.layers = layers; m.layer_stride_rows = layer_stride_rows; m.layer_stride_src = layer_stride_src; m.layer_stride_tiles = layer_stride_tiles;
+    return launch_moe_plan(m, (hipStream_t)stream);
+}
+
 extern "C" int lt_op_gemm_splitk(const void* A, const void* W, void* C, int32_t M, int32_t N, int32_t K, void* part_f32, void* counters_u32,
                                  int32_t tiles, void* stream) {
     LT_REQUIRE(A && W && C && part_f32 && counters_u32, "lt_op_gemm_splitk: null pointer");

@@ -50,6 +50,21 @@ def _bf16_round(x: np.ndarray) -> np.ndarray:
     return u.astype(np.uint32).view(np.float32)
 
 
+def route_time_forced(logits_bf16: np.ndarray, rows_per_sample: int, forced: np.ndarray):
+    """the parity hook's form (variants_oracle.MoeRouting.force, lt_moe_routing_force): row r takes the experts forced[r] (two different ids,
+    either order) instead of its sample's top-2; the weights stay the fp32 softmax over the sample's logits of those two experts, cast to
+    bf16.  -> (sel int32 [rows, 2] ascending ids, wts float32 [rows, 2] bf16-valued, aligned with sel)"""
+    rows = forced.shape[0]
+    l = logits_bf16.astype(np.float32)[np.arange(rows) // rows_per_sample]
+    l1, l2 = l[np.arange(rows), forced[:, 0]], l[np.arange(rows), forced[:, 1]]
+    ex = np.exp((l2 - l1).astype(np.float32), dtype=np.float32)
+    wa, wb = np.float32(1.0) / (np.float32(1.0) + ex), ex / (np.float32(1.0) + ex)
+    swap = forced[:, 1] < forced[:, 0]
+    sel = np.where(swap[:, None], forced[:, ::-1], forced).astype(np.int32)
+    wts = np.where(swap[:, None], np.stack([wb, wa], 1), np.stack([wa, wb], 1)).astype(np.float32)
+    return sel, _bf16_round(wts)
+
+
 def route_time(logits_bf16: np.ndarray, rows_per_sample: int):
     """logits [B, E] (bf16-valued float32) -> (sel int32 [B * rows_per_sample, 2] ascending ids, wts float32 [.., 2] bf16-valued)"""
     B, E = logits_bf16.shape

@@ -1,4 +1,4 @@
-"""One model evaluation of a dense family as a SEQUENCE OF OPERATOR STEPS (plain module, no test in here).
+"""One model evaluation of a dense or mixture-of-experts family as a SEQUENCE OF OPERATOR STEPS (plain module, no test in here).
 
 What this is.  `build(case)` turns a reference state-dict, a config and one call's arguments into a list of `Step`s: the conditioning
 preparation (cast, mask -> bias, pool + LayerNorm, cap embedder, per layer y-norm / wk_y | wv_y / ky_norm / V transpose; or the label
@@ -25,7 +25,17 @@ Operand references inside `args`:
   ("cat", [ref, ...])      rows / elements stacked             ("w13", ref, ref)        the packed W1 | W3 operand of the SwiGLU epilogue
   ("padk", ref, k)         columns zero-padded to k            ("rows", ref, perm)      rows (or elements of a vector) permuted
   ("col", name, off)       d columns of buffer `name` (the modulation matrix) starting at column off, one row per sample
+  ("experts13", [(ref, ref), ...])  the experts' packed W1 | W3 operands stacked [E][2F][d]   ("swap2", ref)  the two words of every pair exchanged
+  ("forced", layer, branch)         the case's forced routing table of that layer and branch ([rows][2] expert ids), None without one
+
+Mixture-of-experts families.  A routed feed-forward is: router logits -> top-2 + softmax weights (`sel`, `wts`) -> plan (`pos`, `src`,
+`te`: kernels.h MoeArgs) -> grouped W1 | W3 GEMM with SwiGLU that gathers its rows of h through `src` -> grouped W2 GEMM -> the closing grn
+step, which combines the two experts' rows through `pos` / `wts` in place of reading y.  The time router's logits of ALL layers are one
+linear launch on temb (step "t.router"); a layer's plan step reads its E columns and routes.  The space router is a step of its own on h, or
+- family `moe`, paths["route_fused"] - the route_* arguments of the grn step that closes the time branch.  The plan buffers of layer l and
+branch br are named "sel.l{l}.{br}" ... "te.l{l}.{br}"; both backends keep `sel` readable (Torch64.sel / .logits, Ops.b).
 """
+import ctypes
 import math
 from collections import namedtuple
 
@@ -51,6 +61,21 @@ FAMILY = {
                      final=("shift", "scale"), text=False, eol=False, rope="2d_general", prop=False),
     # variants_oracle.flag_block: shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp = mod.chunk(6); x + gate * branch (no tanh, no
     # post-norm); pre-norm rmsnorm(x, attention_norm / ffn_norm); flag_forward: eol token per latent row, rope_table_1d over the flattened row
+    # variants_oracle.imagenet_block, family moe_time / moe_space: the imagenet entry with `feed_forward` = ONE MoeLayer - moe_time(sd, p +
+    # "feed_forward.", cfg, mod1(pf_rmsnorm(h), ch[2]), time_input, ...) resp. moe_space(... mod1(pf_rmsnorm(h), ch[2]) ...); gated(h, ch[3], f,
+    # "ffn_norm.weight").  moe_time: logits = _linear(cond, gate.weight) with cond = time_input = te (imagenet_forward hands `te`, NOT adaln_input,
+    # to the blocks), repeated over the sample's tokens; moe_space: logits = _linear(x2, gate.weight) on the FFN input.  _moe_combine: topk(logits,
+    # 2), softmax(selected logits) in fp32, results += weight * expert(rows) for e = 0, 1, ...; an expert is feed_forward(): w2(silu(w1 x) * w3 x)
+    "moe_time": dict(chunks=4, shift=(None, None), scale=(0, 2), gate=(1, 3), tanh=True, pre=(None, None), post=("attention_norm", "ffn_norm"),
+                     final=("shift", "scale"), text=False, eol=False, rope="2d_general", prop=False, moe=(("time", "feed_forward"),)),
+    "moe_space": dict(chunks=4, shift=(None, None), scale=(0, 2), gate=(1, 3), tanh=True, pre=(None, None), post=("attention_norm", "ffn_norm"),
+                      final=("shift", "scale"), text=False, eol=False, rope="2d_general", prop=False, moe=(("space", "feed_forward"),)),
+    # family moe (6 chunks): ft = moe_time(sd, p + "feed_forward_time.", cfg, mod1(pf_rmsnorm(h), ch[2]), time_input, ...); h = gated(h, ch[3], ft,
+    # "ffn_norm_time.weight"); fs = moe_space(sd, p + "feed_forward_space.", cfg, mod1(pf_rmsnorm(h), ch[4]), ...) on the UPDATED stream;
+    # return gated(h, ch[5], fs, "ffn_norm_space.weight").  scale / gate / post: (attention, first FFN branch, second FFN branch)
+    "moe": dict(chunks=6, shift=(None, None, None), scale=(0, 2, 4), gate=(1, 3, 5), tanh=True, pre=(None, None, None),
+                post=("attention_norm", "ffn_norm_time", "ffn_norm_space"), final=("shift", "scale"), text=False, eol=False, rope="2d_general",
+                prop=False, moe=(("time", "feed_forward_time"), ("space", "feed_forward_space"))),
     "flag_t2i": dict(chunks=6, shift=(0, 3), scale=(1, 4), gate=(2, 5), tanh=False, pre=("attention_norm", "ffn_norm"), post=(None, None),
                      final=("shift", "scale"), text=True, eol=True, rope="1d", prop=True),
 }
@@ -60,7 +85,7 @@ class Case:
     """one call: the config, the (bf16-valued) state-dict and inputs, and the call's keyword arguments"""
 
     def __init__(self, cfg, sd, x, t, *, cap=None, mask=None, labels=None, use_cfg=False, cfg_scale=1.0, cfg_channels=3, scale_factor=1.0,
-                 scale_watershed=1.0, ntk_factor=1.0, base_seqlen=None, proportional_attn=False, io_dtype=torch.bfloat16, name=""):
+                 scale_watershed=1.0, ntk_factor=1.0, base_seqlen=None, proportional_attn=False, io_dtype=torch.bfloat16, name="", forced=None):
         self.cfg, self.fam, self.name = cfg, FAMILY[cfg.family], name
         r = lambda v: v.detach().cpu().float().to(torch.bfloat16).float()
         self.sd = {k: r(v) for k, v in sd.items()}
@@ -78,6 +103,7 @@ class Case:
         self.Wrow = self.Wp + 1 if self.fam["eol"] else self.Wp
         self.N = self.Hp * self.Wrow
         self.T = cap.shape[1] if cap is not None else 0
+        self.forced = None if forced is None else np.ascontiguousarray(forced, dtype=np.int32)     # [L][2: time, space][B * N][2], -1: branch not run
 
 
 def softmax_scale(case):
@@ -96,8 +122,11 @@ def fold(scale):
 
 def build(case, paths=None):
     """-> [Step].  paths: {"small_fused": bool} - which launch pair runs a class-conditional layer's attention (lt_op_qkv_attention_small,
-    the default at head_dim 48 / <= 512 tokens, or projection + lt_op_qkv_post + lt_op_attention)."""
-    paths = {"small_fused": True, **(paths or {})}
+    the default at head_dim 48 / <= 512 tokens, or projection + lt_op_qkv_post + lt_op_attention); {"route_fused": bool} - family moe: the
+    space router runs inside the grn step that closes the time branch (the engine's option moe_route_fused, default on) or as a step of its own;
+    {"time_plan_hoist": bool} - the engine's option moe_time_plan_hoist: the engine then writes every layer's time plan in one launch; the chain
+    plans layer by layer either way (the key is recorded for the tests, the steps do not change)."""
+    paths = {"small_fused": True, "route_fused": True, "time_plan_hoist": True, **(paths or {})}
     cfg, fam = case.cfg, case.fam
     d, L, H, Hkv, hd, F = cfg.dim, cfg.n_layers, cfg.n_heads, cfg.kv_heads, cfg.head_dim, cfg.ffn_hidden
     A, cap, dkv, ch = min(d, 1024), cfg.cap_feat_dim, cfg.kv_heads * cfg.head_dim, fam["chunks"]
@@ -145,7 +174,16 @@ def build(case, paths=None):
     add("t.features", "timestep_features", t=("in", "t"), dst="tfeat", B=B, dim=256)
     add("t.mlp0", "linear", a=buf("tfeat"), w=w("t_embedder.mlp.0.weight"), b=w("t_embedder.mlp.0.bias"), dst="t1", M=B, N=A, K=256, act=0)
     add("t.mlp2", "linear", a=buf("t1"), w=w("t_embedder.mlp.2.weight"), b=w("t_embedder.mlp.2.bias"), dst="temb", M=B, N=A, K=A, act=1)
+    moe = fam.get("moe", ())
+    E = cfg.num_experts if moe else 0
+    tiles = (2 * M_ + E * 255 + 255) // 256      # the sorted buffers' tile bound, from the call's rows (kernels.h MoeArgs::max_tiles; moe.hip check())
+    forced = lambda l, br: None if case.forced is None else ("forced", l, 0 if br == "time" else 1)
+    time_key = next((key for br, key in moe if br == "time"), None)
     add("adaln.add", "add", a=buf("temb"), b=buf("cap_emb"), dst="adaln_in", n=B * A)
+    if time_key:     # moe_time(): logits = _linear(cond, gate.weight), cond = te for every layer: ONE launch over the layers' gates stacked
+                     # (placed behind adaln.add only so that a mutation can hand it adaln_in; it depends on temb alone)
+        add("t.router", "linear", a=buf("temb"), w=("cat", [w(f"layers.{l}.{time_key}.gate.weight") for l in range(L)]), b=None, dst="tlogits", M=B,
+            N=L * E, K=A, act=0)
     ada_w = [w(f"layers.{l}.adaLN_modulation.1.weight") for l in range(L)] + [w("final_layer.adaLN_modulation.1.weight")]
     ada_b = [w(f"layers.{l}.adaLN_modulation.1.bias") for l in range(L)] + [w("final_layer.adaLN_modulation.1.bias")]
     add("adaln.linear", "linear", a=buf("adaln_in"), w=("cat", ada_w), b=("cat", ada_b), dst="mod", M=B, N=ld_mod, K=A, act=1)
@@ -188,16 +226,47 @@ def build(case, paths=None):
         add(f"l{l}.grn_attn", "grn", x="x", y=buf("o"), post_w=lw(l, fam["post"][0]), gate=col(l, fam["gate"][0]), post_mode=int(fam["post"][0] is not None),
             next_w=lw(l, fam["pre"][1]), next_scale=col(l, fam["scale"][1]), next_shift=col(l, fam["shift"][1]), next_mode=1, ld_mod=ld_mod, h="h", B=B, N=N,
             d=d, eps=eps, eps_next=1e-6)
+        for i, (br, key) in enumerate(moe):
+            f, nm = f"layers.{l}.{key}.", f"l{l}.{br}"
+            plan = {k: f"{k}.{nm}" for k in ("sel", "wts", "pos", "src", "te")}
+            if br == "time":
+                add(f"{nm}.plan", "moe_plan", logits=buf("tlogits"), sample_ld=L * E, col0=l * E, sel_in=None, forced=forced(l, br), rows=M_, rows_per_sample=N,
+                    E=E, max_tiles=tiles, **plan)
+            else:
+                if not (i == 1 and paths["route_fused"]):      # (fused: the grn step that closed the time branch has routed h already)
+                    add(f"{nm}.route", "moe_route", x=buf("h"), gate_w=w(f + "gate.weight"), forced=forced(l, br), rows=M_, rows_per_sample=N, d=d, E=E,
+                        max_tiles=tiles, sel=plan["sel"], wts=plan["wts"])
+                add(f"{nm}.plan", "moe_plan", logits=None, sample_ld=0, col0=0, sel_in=buf(plan["sel"]), forced=None, rows=M_, rows_per_sample=N, E=E,
+                    max_tiles=tiles, **plan)
+            add(f"{nm}.w13", "gemm_grouped_gather", a=buf("h"), a_rows=M_, src=buf(plan["src"]), te=buf(plan["te"]),
+                w=("experts13", [(w(f + f"experts.{e}.w1.weight"), w(f + f"experts.{e}.w3.weight")) for e in range(E)]), E=E, dst="moe_us", M=tiles * 256,
+                N=2 * F, K=d)
+            add(f"{nm}.w2", "gemm_grouped", a=buf("moe_us"), te=buf(plan["te"]), w=("cat", [w(f + f"experts.{e}.w2.weight") for e in range(E)]), E=E,
+                dst="moe_ys", M=tiles * 256, N=d, K=F)
+            if i + 1 < len(moe):     # family moe: the time branch closes, the space branch's pre-norm (no weight) and modulation follow
+                nb, nkey = moe[i + 1]
+                route = {}
+                if paths["route_fused"]:
+                    route = dict(route_w=w(f"layers.{l}.{nkey}.gate.weight"), route_E=E, route_sel=f"sel.l{l}.{nb}", route_wts=f"wts.l{l}.{nb}",
+                                 route_forced=forced(l, nb))
+                add(f"l{l}.grn_{br}", "grn", x="x", y=None, moe_ys=buf("moe_ys"), moe_pos=buf(plan["pos"]), moe_wts=buf(plan["wts"]),
+                    post_w=lw(l, fam["post"][1 + i]), gate=col(l, fam["gate"][1 + i]), post_mode=1, next_w=None, next_scale=col(l, fam["scale"][2 + i]),
+                    next_shift=None, next_mode=1, ld_mod=ld_mod, h="h", B=B, N=N, d=d, eps=eps, eps_next=1e-6, **route)
+        if moe:
+            last = dict(y=None, moe_ys=buf("moe_ys"), moe_pos=buf(plan["pos"]), moe_wts=buf(plan["wts"]))
+        else:
+            last = dict(y=buf("o"))
         f = f"layers.{l}.feed_forward."
-        add(f"l{l}.w13", "gemm", a=buf("h"), w=("w13", w(f + "w1.weight"), w(f + "w3.weight")), bias=None, dst="u", M=M_, N=2 * F, K=d, epi=1, splitk=False)
-        add(f"l{l}.w2", "gemm", a=buf("u"), w=w(f + "w2.weight"), bias=None, dst="o", M=M_, N=d, K=F, epi=0, splitk=True)
+        if not moe:
+            add(f"l{l}.w13", "gemm", a=buf("h"), w=("w13", w(f + "w1.weight"), w(f + "w3.weight")), bias=None, dst="u", M=M_, N=2 * F, K=d, epi=1, splitk=False)
+            add(f"l{l}.w2", "gemm", a=buf("u"), w=w(f + "w2.weight"), bias=None, dst="o", M=M_, N=d, K=F, epi=0, splitk=True)
         if l + 1 < L:
             nxt = dict(next_w=lw(l + 1, fam["pre"][0]), next_scale=col(l + 1, fam["scale"][0]), next_shift=col(l + 1, fam["shift"][0]), next_mode=1)
         else:    # final layer: affine-free LayerNorm, eps 1e-6, * (1 + scale) [+ shift] (forward() :208-211, _final_shift_scale)
             fin = {nm: ("col", "mod", L * cd + i * d) for i, nm in enumerate(fam["final"])}
             nxt = dict(next_w=None, next_scale=fin["scale"], next_shift=fin.get("shift"), next_mode=2)
-        add(f"l{l}.grn_ffn", "grn", x="x", y=buf("o"), post_w=lw(l, fam["post"][1]), gate=col(l, fam["gate"][1]), post_mode=int(fam["post"][1] is not None),
-            ld_mod=ld_mod, h="h", B=B, N=N, d=d, eps=eps, eps_next=1e-6, **nxt)
+        add(f"l{l}.grn_ffn", "grn", x="x", post_w=lw(l, fam["post"][-1]), gate=col(l, fam["gate"][-1]), post_mode=int(fam["post"][-1] is not None),
+            ld_mod=ld_mod, h="h", B=B, N=N, d=d, eps=eps, eps_next=1e-6, **last, **nxt)
     nfinal = pp * cfg.out_channels
     add("final.linear", "gemm", a=buf("h"), w=w("final_layer.linear.weight"), bias=w("final_layer.linear.bias"), dst="frows", M=M_, N=nfinal, K=d, epi=0,
         splitk=False)
@@ -296,6 +365,7 @@ def mutations(case, steps):
             if case.proportional_attn:
                 out.append((f"l{l}.text_scale_with_proportional", set_arg(f"prep.l{l}.ky", out_scale=fold(softmax_scale(case)))))
             out.append((f"l{l}.text_gate_heads_exchanged", set_arg(f"l{l}.attn", tgate=("rows", by[f"l{l}.attn"]["tgate"], [1, 0] + list(range(2, H))))))
+    out += moe_mutations(case, by)
     ada = by["adaln.linear"]
     out.append(("final_adaln_bias_dropped", set_arg("adaln.linear", b=("cat", ada["b"][1][:-1] + [zeros(len(fam["final"]) * d)]))))
     out.append(("norm_eps_1e-6", set_everywhere("eps", cfg.norm_eps, 1e-6)))
@@ -340,12 +410,90 @@ def mutations(case, steps):
     return out
 
 
+REFUSED_BY_OPERATOR = "fused_router_in_attention_closing_step"     # the float64 chain runs it; lt_op_gated_residual_norm_ex refuses it by name
+
+
+def moe_mutations(case, by):
+    """the wiring mistakes of a mixture-of-experts family, per layer where they are per layer, plus the "layer 1 reads layer 0's" forms"""
+    fam, L, out = case.fam, case.cfg.n_layers, []
+    moe = fam.get("moe", ())
+    if not moe:
+        return out
+    branches = [br for br, _ in moe]
+    both_ = len(moe) == 2
+    fused = both_ and "l0.space.route" not in by
+    swap = lambda step_a, arg_a, step_b, arg_b: both(set_arg(step_a, **{arg_a: by[step_b][arg_b]}), set_arg(step_b, **{arg_b: by[step_a][arg_a]}))
+    tgates = list(by["t.router"]["w"][1]) if "t.router" in by else None
+    tgate_set = lambda l, ref: set_arg("t.router", w=("cat", tgates[:l] + [ref] + tgates[l + 1:]))
+    # where layer l's space router takes its weight and its input: a step of its own, or the grn step that closes the time branch
+    srouter = lambda l: (f"l{l}.grn_time", "route_w") if fused else (f"l{l}.space.route", "gate_w")
+    for l in range(L):
+        if both_:
+            out.append((f"l{l}.time_space_expert_weights_exchanged", both(swap(f"l{l}.time.w13", "w", f"l{l}.space.w13", "w"),
+                                                                           swap(f"l{l}.time.w2", "w", f"l{l}.space.w2", "w"))))
+            step, arg = srouter(l)      # (both routers are [E, 384] at this size: min(dim, 1024) = dim)
+            out.append((f"l{l}.time_space_router_weights_exchanged", both(tgate_set(l, by[step][arg]), set_arg(step, **{arg: tgates[l]}))))
+            out.append((f"l{l}.ffn_norms_time_space_exchanged", swap(f"l{l}.grn_time", "post_w", f"l{l}.grn_ffn", "post_w")))
+            out.append((f"l{l}.ffn_branch_chunks_exchanged", both(swap(f"l{l}.grn_attn", "next_scale", f"l{l}.grn_time", "next_scale"),
+                                                                  swap(f"l{l}.grn_time", "gate", f"l{l}.grn_ffn", "gate"))))
+            out.append((f"l{l}.space_combined_through_time_plan", set_arg(f"l{l}.grn_ffn", moe_pos=by[f"l{l}.grn_time"]["moe_pos"],
+                                                                          moe_wts=by[f"l{l}.grn_time"]["moe_wts"])))
+            if fused:     # the router run by the attention branch's closing step: it routes the TIME branch's input instead of the space branch's
+                r = {k: v for k, v in by[f"l{l}.grn_time"].items() if k.startswith("route_")}
+                out.append((f"l{l}.fused_router_in_attention_closing_step", both(_add_args(f"l{l}.grn_attn", r), _del_args(f"l{l}.grn_time", list(r)))))
+        for br in branches:
+            nm = f"l{l}.{br}"
+            closing = f"l{l}.grn_time" if (both_ and br == "time") else f"l{l}.grn_ffn"
+            pairs = by[f"{nm}.w13"]["w"][1]
+            ex = [pairs[e ^ 1] for e in range(len(pairs))]      # experts (0, 1), (2, 3), ... exchanged - whichever of them the fixture uses
+            out.append((f"{nm}.experts_exchanged_in_w13_not_w2", set_arg(f"{nm}.w13", w=("experts13", ex))))
+            out.append((f"{nm}.w1_w3_exchanged_in_packing", set_arg(f"{nm}.w13", w=("experts13", [(b_, a_) for a_, b_ in pairs]))))
+            out.append((f"{nm}.combine_weights_exchanged", set_arg(closing, moe_wts=("swap2", by[closing]["moe_wts"]))))
+            if br == "time":
+                if len(set(case.inputs["t"].tolist())) > 1:        # (samples that share t share every time-routed choice)
+                    lg = by[f"{nm}.plan"]["logits"]
+                    out.append((f"{nm}.rows_per_sample_halved", set_arg(f"{nm}.plan", rows_per_sample=case.N // 2, logits=("cat", [lg, lg]))))
+            elif not fused:
+                out.append((f"{nm}.router_fed_residual_stream", set_arg(f"{nm}.route", x=("buf", "x"))))
+            if l > 0:
+                if br == "time":
+                    out.append((f"{nm}.logits_at_layer0_columns", set_arg(f"{nm}.plan", col0=0)))
+                    out.append((f"{nm}.router_weight_from_layer0", tgate_set(l, tgates[0])))
+                else:
+                    step, arg = srouter(l)
+                    out.append((f"{nm}.router_weight_from_layer0", set_arg(step, **{arg: by[srouter(0)[0]][arg]})))
+                out.append((f"{nm}.expert_stack_from_layer0", both(set_arg(f"{nm}.w13", w=by[f"l0.{br}.w13"]["w"]), set_arg(f"{nm}.w2", w=by[f"l0.{br}.w2"]["w"]))))
+    if tgates:
+        out.append(("time_router_fed_adaln_in", set_arg("t.router", a=("buf", "adaln_in"))))
+    return out
+
+
+def _add_args(step, new):
+    """hook: arguments the step did not have"""
+    def hook(name, args):
+        if name == step:
+            assert not any(k in args for k in new), (step, list(new))
+            args.update(new)
+        return args
+    return hook
+
+
+def _del_args(step, names):
+    def hook(name, args):
+        if name == step:
+            for k in names:
+                del args[k]
+        return args
+    return hook
+
+
 # ---- backend 1: float64 on the CPU ----------------------------------------------------------------------------------------------------------------
 class Torch64:
     """every operator in float64, no rounding: buffers are float64 tensors in their logical layout (q / k / v: [B, heads, N, hd])"""
 
     def __init__(self, case):
         self.case, self.b = case, {}
+        self.sel, self.logits = {}, {}      # per sel buffer name ("sel.l0.time", ...): int64 [rows, 2] ascending ids, and the float64 logits they came from
 
     def ref(self, r):
         if r is None:
@@ -353,6 +501,12 @@ class Torch64:
         kind = r[0]
         if kind == "buf":
             return self.b[r[1]]
+        if kind == "experts13":
+            return [(self.ref(a), self.ref(b)) for a, b in r[1]]
+        if kind == "swap2":
+            return self.ref(r[1]).reshape(-1, 2).flip(1)
+        if kind == "forced":
+            return torch.from_numpy(self.case.forced[r[1], r[2]]).long()
         if kind == "in":
             v = self.case.inputs[r[1]]
             return v.double() if v.is_floating_point() else v
@@ -395,7 +549,53 @@ class Torch64:
         x = self.ref(a).view(M, K)
         if act:
             x = x * torch.sigmoid(x)
-        self.b[dst] = x @ self.ref(w).t() + self.ref(b)
+        y = x @ self.ref(w).t()
+        self.b[dst] = y if b is None else y + self.ref(b)
+
+    # -- mixture of experts: unrounded logits, top-2 with the lowest index winning, softmax over the two, experts combined in ascending id ------
+    def _top2(self, logits, forced, sel, wts):
+        """logits float64 [rows, E] -> sel [rows, 2] ascending ids, wts [rows, 2] aligned (a forced table replaces the choice, not the weights)"""
+        i1 = logits.argmax(1)           # (torch.argmax returns the first maximum on the CPU for float64; ties are checked by the tests' margin)
+        rest = logits.clone()
+        rest[torch.arange(logits.shape[0]), i1] = float("-inf")
+        i2 = rest.argmax(1)
+        pick = torch.stack([i1, i2], 1) if forced is None else self.ref(forced)
+        pick = pick.sort(1).values
+        lg = torch.gather(logits, 1, pick)
+        self.b[sel], self.b[wts] = pick, torch.softmax(lg, 1)
+        self.sel[sel], self.logits[sel] = pick, logits
+
+    def op_moe_route(self, x, gate_w, forced, rows, rows_per_sample, d, E, max_tiles, sel, wts):
+        self._top2(self.ref(x).view(rows, d) @ self.ref(gate_w).t(), forced, sel, wts)
+
+    def op_moe_plan(self, logits, sample_ld, col0, sel_in, forced, rows, rows_per_sample, E, max_tiles, sel, wts, pos, src, te):
+        from oracle import moe_plan_oracle as MP
+        if logits is not None:
+            lg = self.ref(logits).reshape(-1, sample_ld)[:, col0:col0 + E]
+            self._top2(lg[torch.arange(rows) // rows_per_sample], forced, sel, wts)
+        p, s, t_ = MP.plan(self.b[sel].numpy().astype(np.int32), E, max_tiles)
+        self.b[pos], self.b[src], self.b[te] = torch.from_numpy(p).long(), torch.from_numpy(s).long(), torch.from_numpy(t_).long()
+
+    def _grouped(self, a, te, fn, cols):
+        out = torch.zeros(a.shape[0], cols, dtype=torch.float64)
+        for t_, e in enumerate(te.tolist()):
+            if e >= 0:
+                out[256 * t_:256 * t_ + 256] = fn(e, a[256 * t_:256 * t_ + 256])
+        return out
+
+    def op_gemm_grouped_gather(self, a, a_rows, src, te, w, E, dst, M, N, K):
+        x, s, ws = self.ref(a).view(a_rows, K), self.ref(src), self.ref(w)
+        g = torch.zeros(M, K, dtype=torch.float64)
+        g[s >= 0] = x[s[s >= 0]]
+
+        def swiglu(e, rows):
+            a1, a3 = rows @ ws[e][0].t(), rows @ ws[e][1].t()
+            return a1 * torch.sigmoid(a1) * a3
+        self.b[dst] = self._grouped(g, self.ref(te), swiglu, N // 2)
+
+    def op_gemm_grouped(self, a, te, w, E, dst, M, N, K):
+        ws = self.ref(w).view(E, N, K)
+        self.b[dst] = self._grouped(self.ref(a).view(M, K), self.ref(te), lambda e, rows: rows @ ws[e].t(), N)
 
     def op_rmsnorm_mod(self, x, w, scale, shift, dst, B, N, d, eps, ld_mod, scale_pre=0):
         v = self.ref(x).view(B * N, d)
@@ -515,14 +715,24 @@ class Torch64:
                          hd, table, 1.0, k_scale, 1, None, 0.0, grid_w, table_len)
         self.op_attention(("buf", "_q"), ("buf", "_k"), ("buf", "_v"), dst, B, H, Hkv, tokens, tokens, hd)
 
-    def op_grn(self, x, y, post_w, gate, post_mode, next_w, next_scale, next_shift, next_mode, ld_mod, h, B, N, d, eps, eps_next):
-        xv, yv = self.b[x].view(B * N, d), self.ref(y).view(B * N, d)
+    def op_grn(self, x, y, post_w, gate, post_mode, next_w, next_scale, next_shift, next_mode, ld_mod, h, B, N, d, eps, eps_next, moe_ys=None,
+               moe_pos=None, moe_wts=None, route_w=None, route_E=0, route_sel=None, route_wts=None, route_forced=None):
+        xv = self.b[x].view(B * N, d)
+        if moe_ys is None:
+            yv = self.ref(y).view(B * N, d)
+        else:       # the top-2 combine, ascending expert id (= _moe_combine's loop order; in float64 the order does not round)
+            ys, ps, wt = self.ref(moe_ys), self.ref(moe_pos).reshape(-1, 2), self.ref(moe_wts).reshape(-1, 2)
+            yv = wt[:, 0, None] * ys[ps[:, 0]] + wt[:, 1, None] * ys[ps[:, 1]]
+        if route_w is not None:
+            assert next_mode == 1
         if post_mode == 1:
             yv = yv * R.rms_rinv(yv, eps) * self.ref(post_w)
         xv = xv + self.ref(gate).repeat_interleave(N, 0) * yv
         self.b[x] = xv
         if next_mode == 1:
             self.op_rmsnorm_mod(("buf", x), next_w, next_scale, next_shift, h, B, N, d, eps, ld_mod, scale_pre=1)
+            if route_w is not None:
+                self._top2(self.b[h] @ self.ref(route_w).t(), route_forced, route_sel, route_wts)
             return
         mean, rstd, _ = R.ln_stats(xv, eps_next)
         v = (xv - mean) * rstd * self.ref(next_scale).repeat_interleave(N, 0)
@@ -550,6 +760,7 @@ class Ops:
         from gpu_util import P, lib, ok, stream
         self.case, self.P, self.L, self.ok, self.stream = case, P, lib(), ok, stream
         self.g, self.b, self.keep, self.cache = {}, {}, [], {}
+        self.kernels = {}     # grouped GEMM steps: (M, N, K, epilogue) -> the kernel's name (lt_op_gemm_describe; see _grouped_kernel)
         self.part = torch.zeros(256 * 2 * 64 * 128, dtype=torch.float32, device="cuda")     # split-K workspace: 256 slots, counters zero
         self.cnt = torch.zeros(256, dtype=torch.int32, device="cuda")
 
@@ -580,6 +791,8 @@ class Ops:
             return self.b[r[1]]
         if kind == "col":
             return self.b[r[1]].view(-1)[r[2]:]
+        if kind == "swap2":
+            return self.ref(r[1], dtype).reshape(-1, 2).flip(1).contiguous()
         key = repr((r, dtype))
         if key not in self.cache:
             self.cache[key] = self._make(r, dtype)
@@ -603,6 +816,10 @@ class Ops:
             return torch.cat([v, torch.zeros(v.shape[0], r[2] - v.shape[1], dtype=dtype, device="cuda")], 1).contiguous()
         if kind == "rows":
             return self.ref(r[1], dtype)[torch.tensor(r[2], device="cuda")].contiguous()
+        if kind == "experts13":
+            return torch.cat([self.ref(("w13", a, b)) for a, b in r[1]], 0).contiguous()
+        if kind == "forced":
+            return torch.from_numpy(self.case.forced[r[1], r[2]]).to("cuda", torch.int32).contiguous()
         if kind == "w13":
             w1, w3 = self.ref(r[1]), self.ref(r[2])
             F, K = w1.shape
@@ -699,8 +916,57 @@ class Ops:
                                                  f(table), table_len, grid_w, k_scale, self.P(ws), self.P(self.new(dst, (M, H * hd))), self.stream()),
                 "qkv_attention_small")
 
-    def op_grn(self, x, y, post_w, gate, post_mode, next_w, next_scale, next_shift, next_mode, ld_mod, h, B, N, d, eps, eps_next):
+    # -- mixture of experts --------------------------------------------------------------------------------------------------------------------
+    def _plan_bufs(self, rows, sel, wts):
+        """sel / wts of a router: int32 / bf16 [rows][2] with the 4 words of slack the plan kernel's 16-byte accesses may touch (lumina_dit.h)"""
+        return self.new(sel, (2 * rows + 4,), torch.int32, fill=-1), self.new(wts, (2 * rows + 4,), fill=0.0)
+
+    def op_moe_route(self, x, gate_w, forced, rows, rows_per_sample, d, E, max_tiles, sel, wts):
+        s, w_ = self._plan_bufs(rows, sel, wts)
+        self.ok(self.L.lt_op_moe_route(self.P(self.ref(x)), self.P(self.ref(gate_w)), self.P(self.ref(forced)), rows, rows_per_sample, d, E, self.P(s), self.P(w_),
+                                       max_tiles, self.stream()), "moe_route")
+
+    def op_moe_plan(self, logits, sample_ld, col0, sel_in, forced, rows, rows_per_sample, E, max_tiles, sel, wts, pos, src, te):
+        if logits is not None:
+            s, w_ = self._plan_bufs(rows, sel, wts)
+            lp = ctypes.c_void_p(self.ref(logits).data_ptr() + 2 * col0)
+        else:
+            s, w_, lp = self.ref(sel_in), None, self.P(None)
+        p_ = self.new(pos, (2 * rows + 4,), torch.int32, fill=-1)
+        self.ok(self.L.lt_op_moe_plan_ex(self.P(s), lp, sample_ld, self.P(self.ref(forced)), self.P(w_), rows, rows_per_sample, E, self.P(p_),
+                                         self.P(self.new(src, (max_tiles * 256,), torch.int32, fill=-2)), self.P(self.new(te, (max_tiles,), torch.int32, fill=-2)),
+                                         max_tiles, 1, 0, 0, 0, self.stream()), "moe_plan_ex")
+
+    def _grouped_kernel(self, step, M, N, K, epi):
+        """variant 0: the launcher chooses as it does for the engine.  A grouped problem goes through the same choose() as a dense one of its
+        shape unless the persistent kernel's grouped mode takes it, from 1.5 tiles of 256 x 256 per CU on (gemm_bf16.hip) - asserted not to be
+        the case here, so lt_op_gemm_describe names the kernel"""
+        cus = torch.cuda.get_device_properties(0).multi_processor_count
+        assert 2 * (M // 256) * (-(-N // 256)) < 3 * cus, ("the persistent grouped kernel would take this problem", M, N, cus)
+        buf = ctypes.create_string_buffer(200)
+        self.ok(self.L.lt_op_gemm_describe(M, N, K, epi, 0, buf, 200), "gemm_describe")
+        self.kernels[step] = buf.value.decode()
+
+    def op_gemm_grouped_gather(self, a, a_rows, src, te, w, E, dst, M, N, K):
+        self._grouped_kernel(("w13", M, N, K), M, N, K, 1)
+        self.ok(self.L.lt_op_gemm_grouped_gather(self.P(self.ref(a)), a_rows, self.P(self.ref(src)), self.P(self.ref(w)), self.P(self.ref(te)), N * K,
+                                                 self.P(self.new(dst, (M, N // 2))), M, N, K, 1, 0, self.stream()), "gemm_grouped_gather")
+
+    def op_gemm_grouped(self, a, te, w, E, dst, M, N, K):
+        self._grouped_kernel(("w2", M, N, K), M, N, K, 0)
+        self.ok(self.L.lt_op_gemm_grouped(self.P(self.ref(a)), self.P(self.ref(w)), self.P(self.ref(te)), N * K, self.P(self.new(dst, (M, N))), M, N, K, 0, 0,
+                                          self.stream()), "gemm_grouped")
+
+    def op_grn(self, x, y, post_w, gate, post_mode, next_w, next_scale, next_shift, next_mode, ld_mod, h, B, N, d, eps, eps_next, moe_ys=None,
+               moe_pos=None, moe_wts=None, route_w=None, route_E=0, route_sel=None, route_wts=None, route_forced=None):
         f = lambda r: self.P(self.ref(r))
+        if moe_ys is not None or route_w is not None:
+            rs, rw = self._plan_bufs(B * N, route_sel, route_wts) if route_w is not None else (None, None)
+            self.ok(self.L.lt_op_gated_residual_norm_ex(self.P(self.b[x]), f(y), f(post_w), f(gate), post_mode, 0, f(next_w), f(next_scale), f(next_shift), next_mode,
+                                                        ld_mod, self.P(self.new(h, (B * N, d))), B, N, d, eps, eps_next, 1, 0, self.P(None), 0, f(moe_ys),
+                                                        f(moe_pos), f(moe_wts), f(route_w), route_E, self.P(rs), self.P(rw), f(route_forced), self.stream()),
+                    "gated_residual_norm_ex")
+            return
         self.ok(self.L.lt_op_gated_residual_norm(self.P(self.b[x]), f(y), f(post_w), f(gate), post_mode, 0, f(next_w), f(next_scale), f(next_shift), next_mode,
                                                  ld_mod, self.P(self.new(h, (B * N, d))), B, N, d, eps, eps_next, 1, self.stream()), "gated_residual_norm")
 
@@ -719,7 +985,9 @@ def rel_l2(a, b):
 
 
 # ---- the fixtures' cases ------------------------------------------------------------------------------------------------------------------------
-GOLDENS = {"next_t2i": ("nextdit_tiny", "nextdit_tiny_rect", "nextdit_tiny_gqa"), "imagenet": ("imagenet_tiny",), "flag_t2i": ("flag_tiny",)}
+GOLDENS = {"next_t2i": ("nextdit_tiny", "nextdit_tiny_rect", "nextdit_tiny_gqa"), "imagenet": ("imagenet_tiny",), "flag_t2i": ("flag_tiny",),
+           "moe_time": ("moe_time_tiny",), "moe_space": ("moe_space_tiny",), "moe": ("moe_tiny",)}
+MOE_GOLDENS = ("moe_time_tiny", "moe_space_tiny", "moe_tiny")
 
 
 def load_golden(golden_dir, name):
@@ -735,7 +1003,8 @@ def load_golden(golden_dir, name):
 def golden_case(golden_dir, name, mode, **over):
     """mode 'forward': the plain forward as the public classes make it after construction (NTK branch at scale factor 1: watershed 0, no
     proportional attention); 'cfg4': forward_with_cfg at scale 4 with proportional attention against base_seqlen 16 where the family has it;
-    'lin2' / 'ntk2' (next_t2i): cfg4 at scale_factor 2, watershed 0.3, t = 0.1 / 0.8 - the two RoPE branches"""
+    'lin2' / 'ntk2' (next_t2i): cfg4 at scale_factor 2, watershed 0.3, t = 0.1 / 0.8 - the two RoPE branches; 'cfg4-t2' (the MoE fixtures, whose
+    two samples share t = 0.5 and with it every time-routed choice): cfg4 with t = (0.35, 0.8), so that the samples' time routers differ"""
     g, cfg, sd = load_golden(golden_dir, name)
     x, t = torch.from_numpy(g["z"]), torch.from_numpy(g["t"])
     kw = dict(name=f"{name}-{mode}")
@@ -749,6 +1018,8 @@ def golden_case(golden_dir, name, mode, **over):
         kw.update(use_cfg=True, cfg_scale=4.0)
         if FAMILY[cfg.family]["prop"]:
             kw.update(base_seqlen=16, proportional_attn=True)
+        if mode == "cfg4-t2":
+            t = torch.tensor([0.35, 0.8])
         if mode in ("lin2", "ntk2"):
             kw.update(scale_factor=2.0, scale_watershed=0.3)
             t = torch.full_like(t, 0.1 if mode == "lin2" else 0.8)
@@ -756,8 +1027,9 @@ def golden_case(golden_dir, name, mode, **over):
     return Case(cfg, sd, kw.pop("x", x), kw.pop("t", t), **kw)
 
 
-def oracle_fp32(case):
-    """the fp32 oracle on the case's (bf16-valued) weights and inputs; guidance on channels [:3] as the reference has it"""
+def oracle_fp32(case, moe_hook=None):
+    """the fp32 oracle on the case's (bf16-valued) weights and inputs; guidance on channels [:3] as the reference has it.  moe_hook: a
+    variants_oracle.MoeRouting that records (or forces) the experts of every layer and branch"""
     from oracle import nextdit_oracle as O
     from oracle import variants_oracle as V
     i, fam = case.inputs, case.cfg.family
@@ -769,10 +1041,10 @@ def oracle_fp32(case):
                                       scale_watershed=case.scale_watershed, **kw)
         table = O.rope_table(case.cfg.head_dim, 384, scale_factor=case.scale_factor, scale_watershed=case.scale_watershed, timestep=float(i["t"][0]))
         return O.forward(case.sd, case.cfg, i["x"], i["t"], i["cap"], i["mask"], freqs_table=table, **kw)
-    if fam == "imagenet":
+    if fam in ("imagenet", "moe_time", "moe_space", "moe"):
         if case.use_cfg:
-            return V.imagenet_forward_with_cfg(case.sd, case.cfg, i["x"], i["t"], i["labels"].long(), case.cfg_scale)
-        return V.imagenet_forward(case.sd, case.cfg, i["x"], i["t"], i["labels"].long())
+            return V.imagenet_forward_with_cfg(case.sd, case.cfg, i["x"], i["t"], i["labels"].long(), case.cfg_scale, moe_hook=moe_hook)
+        return V.imagenet_forward(case.sd, case.cfg, i["x"], i["t"], i["labels"].long(), moe_hook=moe_hook)
     kw = dict(proportional_attn=case.proportional_attn, base_seqlen=case.base_seqlen)
     if case.use_cfg:
         return V.flag_forward_with_cfg(case.sd, case.cfg, i["x"], i["t"], i["cap"], i["mask"], case.cfg_scale, **kw)

@@ -6,8 +6,15 @@ weights and inputs) has fp32's: rel_l2(torch64, oracle) measures the oracle's ow
 (profiles/forward_chain/CPU_DISTANCES.md is the same table); GATE is 4 times the largest.  A chain that states one argument differently from
 the reference moves the output by far more: the second test runs every mutation of forward_chain.mutations through the float64 backend and
 requires each to move the output by MORE than the gate - which shows both that the gate can see the argument and that the output of the
-fixture depends on it (the condition under which bit equality on the GPU, tests/test_gpu_forward_chain.py, proves anything about it)."""
+fixture depends on it (the condition under which bit equality on the GPU, tests/test_gpu_forward_chain.py, proves anything about it).
+
+Mixture-of-experts cases.  Routing is discrete, so before any output is compared the chain's selections must equal the ones the fp32 oracle
+records (variants_oracle.MoeRouting) for EVERY row of every layer and branch; a mismatch names the row and the margin between its second
+and third logit.  On the fixtures used here float64 and fp32 agree on every row (smallest margin 4e-3 against fp32's 1e-6), so the distance
+measured is the oracle's rounding alone, as for the dense families."""
 import pytest
+
+import numpy as np
 
 import forward_chain as FC
 
@@ -18,16 +25,23 @@ MEASURED = {
     "nextdit_tiny_rect-ntk2": 1.216e-06, "nextdit_tiny_gqa-forward": 9.629e-07, "nextdit_tiny_gqa-cfg4": 1.180e-06,
     "nextdit_tiny_gqa-lin2": 1.080e-06, "nextdit_tiny_gqa-ntk2": 1.111e-06, "imagenet_tiny-forward": 6.833e-07, "imagenet_tiny-cfg4": 2.362e-06,
     "flag_tiny-forward": 8.041e-07, "flag_tiny-cfg4": 8.164e-07,
+    "moe_time_tiny-forward": 7.748e-07, "moe_time_tiny-cfg4": 2.447e-06, "moe_time_tiny-cfg4-t2": 1.843e-06, "moe_time_tiny-eps": 2.040e-06,
+    "moe_space_tiny-forward": 9.345e-07, "moe_space_tiny-cfg4": 2.882e-06, "moe_space_tiny-cfg4-t2": 3.264e-06, "moe_space_tiny-eps": 2.219e-06,
+    "moe_tiny-forward": 1.064e-06, "moe_tiny-cfg4": 2.821e-06, "moe_tiny-cfg4-t2": 2.948e-06, "moe_tiny-eps": 2.376e-06,
 }
-GATE = 4 * max(MEASURED.values())     # 9.45e-6
+GATE = 4 * max(MEASURED.values())     # 1.31e-5 (moe_space_tiny-cfg4-t2; 9.45e-6 before the mixture-of-experts cases)
 
 MODEL_CASES = [(name, mode) for fam, names in FC.GOLDENS.items() for name in names
-               for mode in ("forward", "cfg4") + (("lin2", "ntk2") if fam == "next_t2i" else ())]
+               for mode in ("forward", "cfg4") + (("lin2", "ntk2") if fam == "next_t2i" else ())] + \
+              [(name, mode) for name in FC.MOE_GOLDENS for mode in ("cfg4-t2", "eps")]
 # the cases the mutations run on: guidance 4 on every fixture, both RoPE branches where the family has them, the batch of three images, and
 # the small-row cases of the eps entries
 MUTATION_CASES = [(name, "cfg4") for names in FC.GOLDENS.values() for name in names] + \
                  [(name, mode) for name in FC.GOLDENS["next_t2i"] for mode in ("lin2", "ntk2")] + \
-                 [("nextdit_tiny", "batch6"), ("nextdit_tiny", "eps"), ("imagenet_tiny", "eps"), ("imagenet_tiny", "eps-unfused"), ("flag_tiny", "eps")]
+                 [("nextdit_tiny", "batch6"), ("nextdit_tiny", "eps"), ("imagenet_tiny", "eps"), ("imagenet_tiny", "eps-unfused"), ("flag_tiny", "eps")] + \
+                 [(name, mode) for name in FC.MOE_GOLDENS for mode in ("cfg4-t2", "eps")] + [("moe_tiny", "cfg4-t2-unrouted")]
+# (cfg4-t2: the two samples at different timesteps, so that their time routers differ; cfg4-t2-unrouted: family moe with the space router as a
+# step of its own, paths route_fused False - the form in which the router's input is an argument)
 
 
 def make_case(golden_dir, name, mode):
@@ -36,14 +50,38 @@ def make_case(golden_dir, name, mode):
         return FC.batch6_case(golden_dir), {}
     if mode.startswith("eps"):
         return FC.eps_case(golden_dir, name), {"small_fused": mode == "eps"}
+    if mode.endswith("-unrouted"):
+        return FC.golden_case(golden_dir, name, mode[:-len("-unrouted")]), {"route_fused": False}
     return FC.golden_case(golden_dir, name, mode), {}
+
+
+def run_against_oracle(case, steps):
+    """-> (the float64 chain's output, rel_l2 to the fp32 oracle); a mixture-of-experts case first has every row's selection compared"""
+    from oracle import variants_oracle as V
+    be = FC.Torch64(case)
+    got = FC.run(be, steps)
+    hook = V.MoeRouting(case.cfg.n_layers) if case.fam.get("moe") else None
+    want = FC.oracle_fp32(case, hook) if hook else FC.oracle_fp32(case)
+    if hook:
+        branches = {0: "time", 1: "space"}
+        assert sorted(hook.rec) == sorted((l, b) for l in range(case.cfg.n_layers) for b in branches if any(br == branches[b] for br, _ in case.fam["moe"]))
+        assert len(be.sel) == len(hook.rec)
+        for (l, b), rec in hook.rec.items():
+            key = f"sel.l{l}.{branches[b]}"
+            mine = be.sel[key].numpy()
+            assert mine.shape == rec.shape == (case.B * case.N, 2), (case.name, key, mine.shape, rec.shape)
+            bad = np.nonzero((mine != rec).any(1))[0]
+            if bad.size:
+                top = be.logits[key][int(bad[0])].topk(3).values
+                raise AssertionError(f"{case.name} {key}: {bad.size} rows select differently, first row {int(bad[0])}: chain {mine[bad[0]].tolist()}, oracle "
+                                     f"{rec[bad[0]].tolist()}, margin between its second and third logit {float(top[1] - top[2]):.3e}")
+    return got, FC.rel_l2(got, want)
 
 
 @pytest.mark.parametrize("name,mode", MODEL_CASES)
 def test_float64_chain_is_the_oracle(golden_dir, name, mode):
     case, paths = make_case(golden_dir, name, mode)
-    got = FC.run(FC.Torch64(case), FC.build(case, paths))
-    err = FC.rel_l2(got, FC.oracle_fp32(case))
+    _, err = run_against_oracle(case, FC.build(case, paths))
     print(f"{case.name}: rel_l2(torch64, oracle fp32) = {err:.3e} (recorded {MEASURED[case.name]:.3e}, gate {GATE:.3e})")
     assert err < GATE, (case.name, err, GATE)
 
@@ -52,8 +90,7 @@ def test_float64_chain_is_the_oracle(golden_dir, name, mode):
 def test_every_mutation_moves_the_float64_chain_past_the_gate(golden_dir, name, mode):
     case, paths = make_case(golden_dir, name, mode)
     steps = FC.build(case, paths)
-    base = FC.run(FC.Torch64(case), steps)
-    err = FC.rel_l2(base, FC.oracle_fp32(case))
+    base, err = run_against_oracle(case, steps)
     assert err < GATE, (case.name, "unmutated", err)     # (also the cases that are no fixture call: the batch of three, the small rows)
     muts = FC.mutations(case, steps)
     assert muts, case.name
@@ -82,5 +119,13 @@ def test_mutation_list_covers_the_issue(golden_dir):
             "final_shift_scale_exchanged", "gate_without_tanh:attn", "gate_without_tanh:ffn", "one_plus_scale_as_scale:attn",
             "one_plus_scale_as_scale:ffn", "one_plus_scale_as_scale:final", "text_bias_from_other_row", "rope_row_col_exchanged", "cfg_channels_3_4", "cfg_pairing_shifted",
             "eol_token_omitted", "x_embedder_bias_dropped"]
+    # the mixture-of-experts wirings: per layer, per layer and branch, and the "layer 1 reads layer 0's" forms
+    per_layer += ["time_space_expert_weights_exchanged", "time_space_router_weights_exchanged", "ffn_norms_time_space_exchanged",
+                  "ffn_branch_chunks_exchanged", "space_combined_through_time_plan", "fused_router_in_attention_closing_step",
+                  "time.experts_exchanged_in_w13_not_w2", "space.experts_exchanged_in_w13_not_w2", "time.w1_w3_exchanged_in_packing",
+                  "space.w1_w3_exchanged_in_packing", "time.combine_weights_exchanged", "space.combine_weights_exchanged", "time.rows_per_sample_halved",
+                  "space.router_fed_residual_stream"]
+    once += ["l1.time.logits_at_layer0_columns", "l1.time.router_weight_from_layer0", "l1.space.router_weight_from_layer0",
+             "l1.time.expert_stack_from_layer0", "l1.space.expert_stack_from_layer0", "time_router_fed_adaln_in"]
     want = {f"l{l}.{m}" for m in per_layer for l in (0, 1)} | set(once)
     assert want <= seen, sorted(want - seen)

@@ -1,6 +1,12 @@
 """The MoE routing plan (integer / index work): oracle/moe_plan_oracle.py against the reference's expert loop semantics (CPU), and
 lt_op_moe_plan against the oracle BIT FOR BIT (GPU) - every register form of the kernel (4 / 8 / 16 / 32 entries per thread), the
-generic walk beyond 16 384 rows, empty experts, everything on two experts, one row, ragged counts, ties in the time router."""
+generic walk beyond 16 384 rows, empty experts, everything on two experts, one row, ragged counts, ties in the time router.
+lt_op_moe_plan_ex (every field of MoeArgs) reaches what lt_op_moe_plan cannot: the time router on the single-workgroup kernel (more than 64
+samples, or a forced table whose rows choose differently inside a sample) in every register form and the generic walk, and the all-layers
+form of the closed-form time plan (three layers, padded strides with sentinels between the slices, each layer against the single-layer
+call on its own logit columns) with its refusals."""
+import ctypes as C
+
 import numpy as np
 import pytest
 import torch
@@ -122,3 +128,136 @@ def test_plan_kernel_time_branch_routes_like_the_oracle(B, rps, E):
     assert np.abs(wts - want_wts).max() <= 2.0 ** -8  # bf16 weights; the kernel's exp is the hardware's v_exp_f32: <= one bf16 ulp
     want_pos, want_src, want_te = MP.plan(want_sel, E, max_tiles)
     assert np.array_equal(pos, want_pos) and np.array_equal(src, want_src) and np.array_equal(te, want_te)
+
+
+# ---- lt_op_moe_plan_ex: the time router on the single-workgroup kernel, the forced table, the all-layers form ------------------------
+def _logits(B, cols, seed):
+    """bf16-valued logits with an exact tie for sample 0's maximum (lowest index wins)"""
+    rng = np.random.default_rng(seed)
+    lg = torch.from_numpy(rng.normal(size=(B, cols)).astype(np.float32)).to(torch.bfloat16).float().numpy()
+    lg[0, 1] = lg[0, 0] = max(float(lg[0].max()), 1.0)
+    return lg
+
+
+def _run_plan_ex(logits, rps, E, forced=None, sample_ld=0, col0=0, layers=1, stride_pad=(0, 0, 0)):
+    """lt_op_moe_plan_ex on buffers whose every word outside a layer's slice holds a sentinel.  -> per layer (sel, wts, pos, src, te), max_tiles"""
+    from gpu_util import P, lib, ok, stream
+    B = logits.shape[0]
+    rows = B * rps
+    max_tiles = (2 * rows + E * 255 + 255) // 256          # moe_ffn's bound for the call's rows (csrc/engine.hip, kernels.h MoeArgs::max_tiles)
+    sr, ss, st = 2 * rows + 4 + stride_pad[0], max_tiles * 256 + stride_pad[1], max_tiles + stride_pad[2]
+    dsel = torch.full((layers * sr,), -7, dtype=torch.int32, device="cuda")
+    pos = torch.full((layers * sr,), -9, dtype=torch.int32, device="cuda")
+    wts = torch.full((layers * sr,), -3.0, dtype=torch.bfloat16, device="cuda")
+    src = torch.full((layers * ss,), -5, dtype=torch.int32, device="cuda")
+    te = torch.full((layers * st,), -5, dtype=torch.int32, device="cuda")
+    dl = torch.from_numpy(logits).to("cuda", torch.bfloat16).contiguous()
+    df = None if forced is None else torch.from_numpy(np.ascontiguousarray(forced, dtype=np.int32)).cuda()
+    lp = C.c_void_p(dl.data_ptr() + 2 * col0)
+    ok(lib().lt_op_moe_plan_ex(P(dsel), lp, sample_ld, P(df), P(wts), rows, rps, E, P(pos), P(src), P(te), max_tiles, layers, sr, ss, st, stream()),
+       "moe_plan_ex")
+    torch.cuda.synchronize()
+    out = []
+    for l in range(layers):
+        a, b, c = dsel[l * sr:(l + 1) * sr], pos[l * sr:(l + 1) * sr], wts[l * sr:(l + 1) * sr]
+        assert (a[2 * rows:] == -7).all() and (b[2 * rows:] == -9).all() and (c[2 * rows:] == -3.0).all(), f"layer {l}: a word behind the rows was written"
+        s, t_ = src[l * ss:(l + 1) * ss], te[l * st:(l + 1) * st]
+        assert (s[max_tiles * 256:] == -5).all() and (t_[max_tiles:] == -5).all(), f"layer {l}: a word behind the sorted positions / tiles was written"
+        out.append((a[:2 * rows].view(rows, 2).cpu().numpy(), c[:2 * rows].float().view(rows, 2).cpu().numpy(), b[:2 * rows].view(rows, 2).cpu().numpy(),
+                    s[:max_tiles * 256].cpu().numpy(), t_[:max_tiles].cpu().numpy()))
+    return out, max_tiles
+
+
+def _assert_plan(got, want_sel, want_wts, E, max_tiles, what):
+    sel, wts, pos, src, te = got
+    assert np.array_equal(sel, want_sel), what
+    assert np.abs(wts - want_wts).max() <= 2.0 ** -8, what     # (the one bf16 ulp derived above: v_exp_f32 against numpy's exp)
+    want_pos, want_src, want_te = MP.plan(want_sel, E, max_tiles)
+    assert np.array_equal(pos, want_pos) and np.array_equal(src, want_src) and np.array_equal(te, want_te), what
+
+
+@gpu
+@pytest.mark.parametrize("B,rps,E,per", [(66, 4, 4, 4), (65, 40, 4, 8), (80, 64, 8, 16), (70, 200, 8, 32), (65, 300, 8, 0)])
+def test_time_router_on_the_single_workgroup_kernel(B, rps, E, per):
+    """more than 64 samples: launch_moe_plan cannot use the closed-form kernel, so moe_plan_kernel<PER> routes - the 8-byte sel stores and the
+    packed weight store of the register forms, the entry-by-entry walk with its barrier of PER == 0"""
+    n = 2 * B * rps
+    assert B > 64 and {4: n <= 4096, 8: 4096 < n <= 8192, 16: 8192 < n <= 16384, 32: 16384 < n <= 32768, 0: n > 32768}[per]     # launch_moe_plan's dispatch
+    logits = _logits(B, E, B * rps + E)
+    (got,), max_tiles = _run_plan_ex(logits, rps, E)
+    want_sel, want_wts = MP.route_time(logits, rps)
+    _assert_plan(got, want_sel, want_wts, E, max_tiles, (B, rps, E))
+
+
+def _forced_table(rows, E, seed):
+    """two different experts per row, rows of one sample choosing differently, a third of the rows in descending order"""
+    rng = np.random.default_rng(seed)
+    a = rng.integers(0, E, rows)
+    b = (a + rng.integers(1, E, rows)) % E
+    f = np.sort(np.stack([a, b], 1), axis=1)
+    flip = rng.integers(0, 3, rows) == 0
+    f[flip] = f[flip][:, ::-1]
+    return f.astype(np.int32)
+
+
+@gpu
+@pytest.mark.parametrize("B,rps,E", [(3, 100, 8), (8, 700, 4), (2, 9000, 8)])
+def test_time_router_with_a_forced_table(B, rps, E):
+    """at most 8 samples, whole samples: only the forced table keeps the call off the closed-form kernel.  Neighbouring rows of one sample take
+    different experts, so a routing cached per sample would show; the weights are the softmax of the sample's logits of the FORCED experts"""
+    rows = B * rps
+    logits = _logits(B, E, rows + E)
+    forced = _forced_table(rows, E, rows)
+    assert (forced[:-1] != forced[1:]).any(1).sum() > rows // 2
+    (got,), max_tiles = _run_plan_ex(logits, rps, E, forced=forced)
+    want_sel, want_wts = MP.route_time_forced(logits, rps, forced)
+    free_sel, _ = MP.route_time(logits, rps)
+    assert (want_sel != free_sel).any(1).sum() > rows // 2        # (the table is not the free choice)
+    _assert_plan(got, want_sel, want_wts, E, max_tiles, (B, rps, E))
+
+
+@gpu
+@pytest.mark.parametrize("B,rps,E,pad_cols", [(5, 100, 4, 0), (64, 7, 8, 5), (2, 1000, 8, 3)])
+def test_all_layers_time_plan(B, rps, E, pad_cols):
+    """L = 3 in one launch (blockIdx.y = layer): strides larger than a layer needs with sentinels between the slices, every layer equal to the
+    oracle on its own E logit columns and, word for word, to the single-layer call on those columns; the logit rows are longer than L * E and the
+    extra columns hold values that would win every top-2"""
+    L = 3
+    ld = L * E + pad_cols
+    logits = _logits(B, ld, B * rps + E)
+    logits[:, L * E:] = 64.0
+    logits[1 % B, E + 2] = logits[1 % B, E + 1] = 8.0          # a tie inside layer 1's columns as well
+    layers, max_tiles = _run_plan_ex(logits, rps, E, sample_ld=ld, layers=L, stride_pad=(6, 256 + 3, 5))
+    for l in range(L):
+        cols = np.ascontiguousarray(logits[:, l * E:(l + 1) * E])
+        want_sel, want_wts = MP.route_time(cols, rps)
+        _assert_plan(layers[l], want_sel, want_wts, E, max_tiles, ("layer", l))
+        (single,), _ = _run_plan_ex(logits, rps, E, sample_ld=ld, col0=l * E)
+        for got, one, name in zip(layers[l], single, ("sel", "wts", "pos", "src", "tile_expert")):
+            assert np.array_equal(got, one), ("layer", l, name)
+    if B > 1:    # (the layers are different plans: the check above could not pass by reading one layer's columns three times)
+        assert any(not np.array_equal(layers[0][0], layers[l][0]) for l in (1, 2))
+
+
+@gpu
+def test_all_layers_form_refusals():
+    from gpu_util import P, lib, stream
+    E, rps, L = 4, 8, 2
+
+    def call(B, forced):
+        rows = B * rps
+        max_tiles = (2 * rows + E * 255 + 255) // 256
+        sr = 2 * rows + 4
+        i32 = lambda n: torch.zeros(n, dtype=torch.int32, device="cuda")
+        lg = torch.zeros(B, L * E, dtype=torch.bfloat16, device="cuda")
+        f = torch.tensor([[0, 1]] * rows, dtype=torch.int32, device="cuda") if forced else None
+        rc = lib().lt_op_moe_plan_ex(P(i32(L * sr)), P(lg), L * E, P(f), P(torch.zeros(L * sr, dtype=torch.bfloat16, device="cuda")), rows, rps, E, P(i32(L * sr)),
+                                     P(i32(L * max_tiles * 256)), P(i32(L * max_tiles)), max_tiles, L, sr, max_tiles * 256, max_tiles, stream())
+        return rc, lib().lt_last_error().decode()
+
+    for B, forced in ((4, True), (65, False)):
+        rc, msg = call(B, forced)
+        assert rc != 0 and "moe_plan: the all-layers form is the time router's closed-form plan" in msg, (B, forced, rc, msg)
+    rc, msg = call(4, False)
+    assert rc == 0, msg
+    torch.cuda.synchronize()
