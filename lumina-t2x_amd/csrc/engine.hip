@@ -32,19 +32,10 @@ extern "C" const char* lt_version(void) { return "lumina_dit gfx950 r5"; }
 namespace {
 
 constexpr float LOG2E = 1.44269504088896340736f;
-// Kernel-selection options (options.h; lt_set_option = process default, lt_engine_set_option = per-engine override):
-//   qkv_post_fused   1 = one launch for q / k post-processing + V transpose, 0 = three launches, 2 (default) = one launch where the
-//                    problem is launch-bound (fewer than 2048 rows: the three passes are 5 us each at 512 rows, i.e. pure launch latency -
-//                    profiles/r02/rocprofv3_kernel_stats_cfg1_r02.csv), three where it is bandwidth-bound (in-situ A/B at cfg 2 with the
-//                    LDS-staged row kernels, profiles/r01/bench_ab_qkv_post_fused.log: three launches 0.1-0.2 ms / NFE faster)
-//   qkv_vt_epilogue  1 = the V projection is its own GEMM launch whose epilogue writes the attention kernels' V^T image (no v_transpose
-//                    pass: 15.6 us per layer at cfg 2, and the 37.7 MB V slice is never written row-major / re-read)
-//   qkv_fused_gemm   Q | K | V in one launch of the persistent kernel where the shapes allow it
-//   attn_q_fused     q_norm + RoPE of the queries inside the attention prologue (hd 72 one-wave kernel, fused QKV GEMM)
-//   qk_post_pair     1 = q and k post-processing share one persistent launch (large problems)
-//   graph            1 = a model evaluation (~250 launches) is captured into a HIP graph per (arguments, shapes) and replayed; 2 (default) = above
-//                    1024 rows only (forward_graphed).  Every option
-//                    change moves lt_opt_generation(), which is part of the graph key (kernel selection is baked into a captured graph).
+// Kernel-selection options (options.h; lt_set_option = process default, lt_engine_set_option = per-engine override): those that pick a transformer
+// block's launches are described at the routes they pick (QkvRoute, PostRoute, BlockPlan below).  graph: 1 = a model evaluation (~250 launches) is
+// captured into a HIP graph per (arguments, shapes) and replayed; 2 (default) = above 1024 rows only (forward_graphed).  Every option change moves
+// lt_opt_generation(), which is part of the graph key (kernel selection is baked into a captured graph).
 
 VariantDesc variant_desc(int variant) {
     VariantDesc v{};
@@ -114,6 +105,12 @@ void prefetch_rider(lt_engine* e, PrefetchRider* r, const u16* A, int lda, const
     if (!gemm_prefetch_rider(g, epi, r)) *r = PrefetchRider();
 }
 
+// one GEMM launch in the profile's class 0; the dispatch packet carries the event pair itself
+int profiled_gemm(lt_engine* e, const GemmArgs& g, int epi, double flops, hipStream_t s) {
+    ProfScope ps(e, 0, flops, s, true);
+    return launch_gemm_bf16(g, epi, 0, s, ps.ev0(), ps.ev1());
+}
+
 // ystat_slots (optional, out): > 0 when the launch left the rows' sum-of-squares partials in e->ystat (option grn_ystat; GemmArgs::ystat)
 int gemm(lt_engine* e, const u16* A, int lda, const u16* W, int ldw, u16* C, int ldc, int M, int N, int K,
          const u16* bias, int epi, hipStream_t s, int* ystat_slots = nullptr, int pair_ab = 0, int pair_c = 0) {
@@ -128,8 +125,7 @@ int gemm(lt_engine* e, const u16* A, int lda, const u16* W, int ldw, u16* C, int
         if (ys > 0 && ys <= e->ystat_cap) { g.ystat = e->ystat; g.ystat_slots = ys; *ystat_slots = ys; }
     }
     if (lt_opt(OPT_GEMM_PREFETCH) == 1 && M <= 1024 && launch_gemm_prefetch_w(g, epi, s)) return 1;
-    ProfScope ps(e, 0, 2.0 * M * (double)N * K, s, true);
-    return launch_gemm_bf16(g, epi, 0, s, ps.ev0(), ps.ev1());
+    return profiled_gemm(e, g, epi, 2.0 * M * (double)N * K, s);
 }
 
 int attention(lt_engine* e, const AttnArgs& a, hipStream_t s) {
@@ -282,6 +278,21 @@ int ensure_rope(lt_engine* e, const lt_step_args* a, hipStream_t s) {
     return 0;
 }
 
+// tile bound of THIS call's row count, not of the engine's capacity: a capacity-sized launch would be mostly padding tiles, and the XCD-contiguous
+// tile order would put every real tile on XCD 0 (measured: 255 us instead of 60 us per expert GEMM at 512 rows in an engine sized for 8192)
+int moe_tiles_for(const lt_engine* e, int M) { return (int)((2 * (size_t)M + (size_t)e->E * 255 + 255) / 256); }
+// the two grouped GEMMs of a MoE feed-forward of M rows, as launched and as plan_block asks the dispatch about them: SwiGLU on the un-sorted
+// FFN input e->h (the GEMM gathers its rows through the plan's inverse map `src`, no expert-sorted copy), then W2
+void moe_gemm_args(const lt_engine* e, const u16* w13, const u16* w2, const int* tile_expert, const int* src, int M, GemmArgs& g13, GemmArgs& g2) {
+    const int d = e->d, F = e->F;
+    g13 = GemmArgs{};
+    g13.bias_dtype = -1; g13.tile_expert = tile_expert; g13.M = moe_tiles_for(e, M) * 256;
+    g2 = g13;
+    g13.A = e->h; g13.a_row_map = src; g13.a_map_rows = M; g13.W = w13; g13.C = e->moe_us; g13.N = 2 * F; g13.K = d; g13.lda = d; g13.ldw = d; g13.ldc = F;
+    g13.w_expert_stride = (long long)2 * F * d;
+    g2.A = e->moe_us; g2.W = w2; g2.C = e->moe_ys; g2.N = d; g2.K = F; g2.lda = F; g2.ldw = F; g2.ldc = d; g2.w_expert_stride = (long long)d * F;
+}
+
 // one MoE feed-forward (branch 0 = TimeMoeLayer on the timestep embedding, 1 = SpaceMoeLayer on the tokens;
 // models2.py:451-506): e->h -> e->o
 // routed: sel / wts of this (token-routed) branch were already written by the row kernel that produced its input (GatedResArgs::route_*)
@@ -290,12 +301,8 @@ int moe_ffn(lt_engine* e, LayerW& w, int layer, int branch, int M, int N, int B,
     const int d = e->d, F = e->F;
     MoeArgs m;
     m.x = e->h; m.rows = M; m.rows_per_sample = N; m.d = d; m.E = e->E;
-    // tile bound of THIS call's row count, not of the engine's capacity: a capacity-sized launch would be mostly padding
-    // tiles, and the XCD-contiguous tile order would put every real tile on XCD 0 (measured: 255 us instead of 60 us per
-    // expert GEMM at 512 rows in an engine sized for 8192)
-    const int tiles = (int)((2 * (size_t)M + (size_t)e->E * 255 + 255) / 256);
     const bool hoisted = branch == 0 && e->moe_tp_live;  // this layer's time plan was written at the top of the evaluation (run_forward)
-    m.sel = e->moe_sel; m.wts = e->moe_wts; m.pos = e->moe_pos; m.tile_expert = e->moe_tile_expert; m.max_tiles = tiles;
+    m.sel = e->moe_sel; m.wts = e->moe_wts; m.pos = e->moe_pos; m.tile_expert = e->moe_tile_expert; m.max_tiles = moe_tiles_for(e, M);
     m.src = e->moe_src;
     if (hoisted) {
         m.sel = e->moe_tp_sel + (size_t)layer * e->moe_tp_stride_rows; m.pos = e->moe_tp_pos + (size_t)layer * e->moe_tp_stride_rows;
@@ -323,25 +330,14 @@ int moe_ffn(lt_engine* e, LayerW& w, int layer, int branch, int M, int N, int B,
             e->moe_rec_rows = M;
         }
     }
-    const int P = tiles * 256;
-    GemmArgs g;
-    g.bias = nullptr; g.bias_dtype = -1; g.tile_expert = m.tile_expert;
-    {   // grouped SwiGLU GEMM: each 256-row tile multiplies with its expert's packed w1|w3
-        // (A = the un-sorted FFN input: the GEMM gathers its rows through the plan's inverse map, no expert-sorted copy)
-        g.A = e->h; g.a_row_map = m.src; g.a_map_rows = M; g.W = branch == 0 ? w.w13_t : w.w13_s; g.C = e->moe_us; g.M = P; g.N = 2 * F; g.K = d;
-        g.lda = d; g.ldw = d; g.ldc = F; g.w_expert_stride = (long long)2 * F * d;
-        g.pair_ab = pair ? 2 : 0; g.pair_c = pair;  // (A is gathered row by row from e->h: row-major)
-        ProfScope ps(e, 0, 2.0 * (2.0 * M) * (2.0 * F) * d, s, true);  // algorithmic: every token visits two experts
-        if (launch_gemm_bf16(g, 1, 0, s, ps.ev0(), ps.ev1())) return 1;
-    }
-    {
-        g.A = e->moe_us; g.a_row_map = nullptr; g.a_map_rows = 0; g.W = branch == 0 ? w.w2_t : w.w2_s; g.C = e->moe_ys; g.M = P; g.N = d; g.K = F;
-        if (lt_opt(OPT_GEMM_TAIL_SPLIT) && e->tail_part) { g.tail_part = e->tail_part; g.tail_cnt = e->tail_cnt; g.tail_cap_parts = e->tail_cap_parts; g.tail_max_parts = lt_opt(OPT_GEMM_TAIL_SPLIT) == 2 ? 2 : 4; }
-        g.lda = F; g.ldw = F; g.ldc = d; g.w_expert_stride = (long long)d * F;
-        g.pair_ab = pair ? 3 : 0; g.pair_c = 0;
-        ProfScope ps(e, 0, 2.0 * (2.0 * M) * (double)d * F, s, true);
-        if (launch_gemm_bf16(g, 0, 0, s, ps.ev0(), ps.ev1())) return 1;
-    }
+    // grouped SwiGLU GEMM: each 256-row tile multiplies with its expert's packed w1|w3 - then the experts' W2
+    GemmArgs g13, g2;
+    moe_gemm_args(e, branch == 0 ? w.w13_t : w.w13_s, branch == 0 ? w.w2_t : w.w2_s, m.tile_expert, m.src, M, g13, g2);
+    g13.pair_ab = pair ? 2 : 0; g13.pair_c = pair;  // (A is gathered row by row from e->h: row-major)
+    if (profiled_gemm(e, g13, 1, 2.0 * (2.0 * M) * (2.0 * F) * d, s)) return 1;  // algorithmic: every token visits two experts
+    if (lt_opt(OPT_GEMM_TAIL_SPLIT) && e->tail_part) { g2.tail_part = e->tail_part; g2.tail_cnt = e->tail_cnt; g2.tail_cap_parts = e->tail_cap_parts; g2.tail_max_parts = lt_opt(OPT_GEMM_TAIL_SPLIT) == 2 ? 2 : 4; }
+    g2.pair_ab = pair ? 3 : 0;
+    if (profiled_gemm(e, g2, 0, 2.0 * (2.0 * M) * (double)d * F, s)) return 1;
     // (the top-2 combine of e->moe_ys is formed by the gated_residual_norm launch that consumes this branch: moe_y() below)
     return 0;
 }
@@ -402,13 +398,37 @@ int ensure_weight_layout(lt_engine* e, bool want, hipStream_t s, bool recording 
     return 0;
 }
 
+// ---- one model evaluation: run_forward and its stages.  They share Dims, the shapes of the call, and BlockPlan (below), the launch route of a
+// transformer block: neither depends on the layer - shapes, family, prompt state and the option snapshot (LtOptScope) are constant for the call
+struct Dims {
+    int B, N, Npad, M, Hp, Wp, Wrow;  // M = B x N rows; a packed batch: N / Hp / Wp of its longest sample.  Wrow: tokens per latent row
+    float sm_scale;
+    // packed batches: per-sample token count / grid width for the rotary positions and the key mask, on the host and on the device (null: a
+    // tensor state); nk_dev: the key counts the self-attention masks by (null also in the flat form when every sample has the longest length)
+    int ntok[64], gw[64];
+    const int *ntok_dev = nullptr, *gw_dev = nullptr, *nk_dev = nullptr;
+    bool pk_full = true;  // no sample is shorter than the longest one: no padded keys to mask
+};
+const u16* mod_chunk(const lt_engine* e, int layer, int idx) { return idx < 0 ? nullptr : e->mod + ((size_t)layer * e->chunks + idx) * e->d; }
+// the final layer's modulation, behind the L layers' chunks: [shift,] scale (model.py:657-661 / models.py:829-832)
+const u16* final_shift(const lt_engine* e) { return e->v.final_chunks == 2 ? mod_chunk(e, e->L, 0) : nullptr; }
+const u16* final_scale(const lt_engine* e) { return mod_chunk(e, e->L, 0) + (e->v.final_chunks == 2 ? e->d : 0); }
+int cfg_channels(const lt_step_args* a) { return a->cfg_channels > 0 ? a->cfg_channels : 3; }
+// what every closing step of a branch shares: x += gate' * post(y); h = the next pre-norm of x, modulated
+GatedResArgs gated_res_args(const lt_engine* e, const Dims& dm) {
+    GatedResArgs g{};
+    g.x = e->x; g.h = e->h; g.rows = dm.M; g.rows_per_batch = dm.N; g.d = e->d; g.ld_mod = e->ld_mod;
+    g.eps = e->cfg.norm_eps; g.eps_next = 1e-6f; g.scale_pre = 1;
+    return g;
+}
+
 // The closing step of an evaluation on a tensor state: frows -> `out` in the caller's layout, guided as the kind says.  The kinds that read
 // their scale from device memory find it in e->g_cfg[0], the rule's blend and limit in [1..2], the skip-layer scale in [3]; a half-row kind
 // ran B rows and writes 2 B (the kernels count output rows)
 int close_forward(lt_engine* e, void* out, const lt_step_args* a, int use_cfg, int B, int Wrow, LtEvalKind kind, hipStream_t s) {
     const lt_config& c = e->cfg;
     const int p = c.patch_size, Bout = lt_eval_traits(kind).half ? 2 * B : B;
-    const int cfg_ch = a->cfg_channels > 0 ? a->cfg_channels : 3;
+    const int cfg_ch = cfg_channels(a);
     const int guided_ch = cfg_ch < c.in_channels ? cfg_ch : c.in_channels;  // (the channels the closing kernel guides)
     const float* g = e->g_cfg;
     switch (kind) {
@@ -433,17 +453,13 @@ int close_forward(lt_engine* e, void* out, const lt_step_args* a, int use_cfg, i
     LT_REQUIRE(false, "model evaluation: kind %d has no closing step", (int)kind);
 }
 
-// kind (eval_kind.h): other than LT_KIND_WHOLE for a tensor state only.  The three parts of an evaluation under step caching are cut behind
-// the first pre-norm and behind the last block
-int run_forward(lt_engine* e, const void* x_in, const float* t_dev, void* out, const lt_step_args* a, int use_cfg,
-                hipStream_t s, const PackedDesc* pk = nullptr, LtEvalKind kind = LT_KIND_WHOLE) {
-    const lt_config& c = e->cfg;
-    const VariantDesc& v = e->v;
+// the refusals of an evaluation up to its softmax scale - nothing is launched before the last of them - and the shapes they are made on
+int forward_dims(lt_engine* e, const lt_step_args* a, int use_cfg, hipStream_t s, const PackedDesc* pk, LtEvalKind kind, Dims& dm) {
+    const lt_config& c = e->cfg; const VariantDesc& v = e->v;
     const LtEvalTraits kt = lt_eval_traits(kind);
     const int B = a->batch, p = c.patch_size;
     if (pk) {
-        LT_REQUIRE(c.variant == LT_VARIANT_NEXT_T2I, "packed batches: the text-conditional Next-DiT (LT_VARIANT_NEXT_T2I) only; this engine is variant %d",
-                   c.variant);
+        LT_REQUIRE(c.variant == LT_VARIANT_NEXT_T2I, "packed batches: the text-conditional Next-DiT (LT_VARIANT_NEXT_T2I) only; this engine is variant %d", c.variant);
         LT_REQUIRE(pk->tab || !use_cfg, "packed batches: lt_forward_packed is the plain forward (guidance on a size list: lt_forward_cfg_packed)");
         LT_REQUIRE(B >= 1 && B <= c.max_batch && B <= 64, "packed batch of %d exceeds max_batch %d (or 64)", B, c.max_batch);
     }
@@ -451,22 +467,23 @@ int run_forward(lt_engine* e, const void* x_in, const float* t_dev, void* out, c
     LT_REQUIRE(!use_cfg || B % 2 == 0, "forward_with_cfg needs an even batch (cond+uncond)");
     LT_REQUIRE(a->latent_h % p == 0 && a->latent_w % p == 0, "latent %dx%d not divisible by patch", a->latent_h, a->latent_w);
     int Hp = a->latent_h / p, Wp = a->latent_w / p;
-    const int Wrow = v.eol ? Wp + 1 : Wp;  // tokens per latent row (Flag-DiT appends one eol token, model.py:779-786)
-    int N = Hp * Wrow;
-    int pk_ntok[64], pk_gw[64];
-    bool pk_full = true;  // no sample is shorter than the longest one: no padded keys to mask
+    dm.Wrow = v.eol ? Wp + 1 : Wp;  // (Flag-DiT appends one eol token per latent row, model.py:779-786)
+    int N = Hp * dm.Wrow;
     if (pk) {  // N = the longest sequence; a->latent_h / latent_w are ignored
         N = 0; Hp = 0; Wp = 0;
         for (int b = 0; b < B; ++b) {
             const int hb = pk->hw[2 * b], wb = pk->hw[2 * b + 1];
             LT_REQUIRE(hb > 0 && wb > 0 && hb % p == 0 && wb % p == 0, "packed sample %d: latent %dx%d not divisible by patch", b, hb, wb);
-            pk_ntok[b] = (hb / p) * (wb / p);
-            pk_gw[b] = wb / p;
-            N = std::max(N, pk_ntok[b]); Hp = std::max(Hp, hb / p); Wp = std::max(Wp, wb / p);
+            dm.ntok[b] = (hb / p) * (wb / p);
+            dm.gw[b] = wb / p;
+            N = std::max(N, dm.ntok[b]); Hp = std::max(Hp, hb / p); Wp = std::max(Wp, wb / p);
         }
-        for (int b = 0; b < B; ++b) pk_full = pk_full && pk_ntok[b] == N;
+        for (int b = 0; b < B; ++b) dm.pk_full = dm.pk_full && dm.ntok[b] == N;
+        dm.ntok_dev = pk->tab ? pk->tab + LT_PK_NTOK * LT_PK_MAX : e->pk_dev;  // (flat form: the entry point stored the table; pointer form: embed_patches copies)
+        dm.gw_dev = pk->tab ? pk->tab + LT_PK_GW * LT_PK_MAX : e->pk_dev + 64;
+        dm.nk_dev = pk->tab && dm.pk_full ? nullptr : dm.ntok_dev;
     }
-    const int M = B * N;
+    dm.B = B; dm.N = N; dm.Npad = round_up(N, 64); dm.M = B * N; dm.Hp = Hp; dm.Wp = Wp;
     LT_REQUIRE(N <= c.max_tokens, "%d latent tokens exceed max_tokens %d", N, c.max_tokens);
     if (v.rope_1d) LT_REQUIRE(N <= e->rope_len, "sequence of %d tokens exceeds the 1-D RoPE table (%d)", N, e->rope_len);
     else LT_REQUIRE(Hp <= e->rope_len && Wp <= e->rope_len, "latent grid exceeds the RoPE table (%d)", e->rope_len);
@@ -479,7 +496,6 @@ int run_forward(lt_engine* e, const void* x_in, const float* t_dev, void* out, c
     LT_REQUIRE(e->skip.empty() || kt.skip_ok, "layer skip: a layer-skip set is not served by an evaluation of kind %d", (int)kind);
     if (lt_slg_kernel_mode(kind) >= 0) LT_REQUIRE(e->g_skip, "skip-layer guidance: the buffer is not allocated (ensure_skip_buf)");
     if (kind == LT_KIND_REUSE_STORE || kind == LT_KIND_REUSE_AGAIN) LT_REQUIRE(e->g_delta, "guidance reuse: the buffer is not allocated (ensure_delta)");
-    const bool do_head = kt.reads_x, do_blocks = kind != LT_KIND_CACHE_HEAD && kind != LT_KIND_CACHE_APPLY;
     e->cache_head[0] = 0;  // (this evaluation rewrites e->x / e->h / e->mod, or uses them up; forward_graphed sets it behind a head)
     if (kt.cached) {
         LT_REQUIRE(!e->moe_rec_on && !e->moe_force_rows, "step caching: MoE routing record / force is not served");
@@ -488,170 +504,349 @@ int run_forward(lt_engine* e, const void* x_in, const float* t_dev, void* out, c
         LT_REQUIRE(e->c_hprev && e->c_x0 && e->c_r && e->c_ws, "step caching: the buffers are not allocated (ensure_step_cache)");
     }
     if (!e->weights_ok && lt_weights_ready(e)) return 2;
-    const int d = e->d, L = e->L, H = e->H, Hkv = e->Hkv, hd = e->hd, F = e->F, dkv = e->dkv, A = e->A;
-    const int Npad = round_up(N, 64);
-    const int cd = e->chunks * d;
+    return 0;
+}
+
+// patchify + x_embedder (model.py:777-779) in the three input forms [+ eol token per row] -> e->x
+int embed_patches(lt_engine* e, const Dims& dm, const void* x_in, const lt_step_args* a, int use_cfg, const PackedDesc* pk, hipStream_t s) {
+    const lt_config& c = e->cfg;
+    const int B = dm.B, N = dm.N, p = c.patch_size;
+    if (ProfScope ps(e, 2, 0, s); !pk) {
+        if (launch_patchify(x_in, a->io_dtype, e->patches, B, c.in_channels, a->latent_h, a->latent_w, p, e->kpad, use_cfg, dm.Wrow, s)) return 1;
+    } else if (pk->tab) {  // one launch for all samples
+        if (launch_patchify_packed(pk->x_flat, a->io_dtype, e->patches, pk->tab, B, c.in_channels, p, e->kpad, N, use_cfg, s)) return 1;
+    } else {
+        for (int b = 0; b < B; ++b)
+            if (launch_patchify(pk->x_ptrs[b], a->io_dtype, e->patches + (size_t)b * N * e->kpad, 1, c.in_channels, pk->hw[2 * b], pk->hw[2 * b + 1], p, e->kpad, 0, 0, s)) return 1;
+        memcpy(e->pk_host, dm.ntok, B * sizeof(int)); memcpy(e->pk_host + 64, dm.gw, B * sizeof(int));
+        LT_CHECK_HIP(hipMemcpyAsync(e->pk_dev, e->pk_host, 128 * sizeof(int), hipMemcpyHostToDevice, s));
+    }
+    if (gemm(e, e->patches, e->kpad, e->xemb_w, e->kpad, e->x, e->d, dm.M, e->d, e->kpad, e->xemb_b, 0, s)) return 1;
+    if (pk) {  // padded positions hold the learned pad_token, not an embedded patch (model.py:811-817)
+        ProfScope ps(e, 2, 0, s);
+        if (pk->tab && !dm.pk_full && launch_fill_pad_packed(e->x, e->pad_token, pk->tab, B, N, e->d, s)) return 1;
+        for (int b = 0; !pk->tab && b < B; ++b)
+            if (dm.ntok[b] < N && launch_fill_rows_bf16(e->x + ((size_t)b * N + dm.ntok[b]) * e->d, e->pad_token, N - dm.ntok[b], e->d, s)) return 1;
+    }
+    if (e->v.eol) {
+        ProfScope ps(e, 2, 0, s);
+        if (launch_eol_fill(e->x, e->eol_token, B * dm.Hp, dm.Wp, e->d, s)) return 1;
+    }
+    return 0;
+}
+
+// conditioning: t_embedder (model.py:84-87) + caption / label embedding (hoisted) -> adaLN vectors of every layer + final (e->mod)
+int condition(lt_engine* e, const Dims& dm, const float* t_dev, hipStream_t s) {
+    const VariantDesc& v = e->v;
+    const int B = dm.B, L = e->L, A = e->A;
+    ProfScope ps(e, 2, 0, s);
+    const int fused_pro = lt_opt(OPT_PROLOGUE_FUSED);  // round 6, bit mask: 1 timestep features, 2 temb + embedding, 4 prep_mod - each one launch less, bit-identical (LinearSmallMExtra)
+    if (fused_pro & 1) { LinearSmallMExtra x; x.t = t_dev; if (launch_linear_small_m_ext(nullptr, e->t0_w, e->t0_b, e->t1, B, A, 256, 0, x, s)) return 1; }
+    else if (launch_timestep_features(t_dev, 0, e->tfeat, B, 256, s) || launch_linear_small_m(e->tfeat, e->t0_w, e->t0_b, e->t1, B, A, 256, 0, s)) return 1;
+    if (launch_linear_small_m(e->t1, e->t2_w, e->t2_b, e->temb, B, A, A, 1, s)) return 1;
+    if (e->gate_t_all && launch_linear_small_m(e->temb, e->gate_t_all, nullptr, e->moe_logits, B, L * e->E, A, 0, s)) return 1;  // every layer's time-router logits
+    if (e->moe_tp_live) {  // ... and every layer's time plan: they depend on nothing else (one launch instead of L)
+        MoeArgs m;
+        m.x = nullptr; m.gate_w = nullptr; m.forced = nullptr; m.sample_logits = e->moe_logits; m.sample_ld = L * e->E;
+        m.rows = dm.M; m.rows_per_sample = dm.N; m.d = e->d; m.E = e->E;
+        m.sel = e->moe_tp_sel; m.pos = e->moe_tp_pos; m.wts = e->moe_tp_wts; m.src = e->moe_tp_src; m.tile_expert = e->moe_tp_tile_expert;
+        m.max_tiles = moe_tiles_for(e, dm.M);
+        m.layers = L; m.layer_stride_rows = (long long)e->moe_tp_stride_rows; m.layer_stride_src = (long long)e->moe_tp_stride_src; m.layer_stride_tiles = e->moe_tiles;
+        if (launch_moe_plan(m, s)) return 1;
+    }
+    // once per (sample, channel) instead of once per token inside the row kernels: tanh of the gate chunks (where the
+    // family has it) and bf16(1 + scale) of every scale chunk
+    unsigned tanh_mask = 0, scale_mask = 0;
+    for (int i = 0; i < 2; ++i) {
+        if (v.gate_tanh && v.i_gate[i] >= 0) tanh_mask |= 1u << v.i_gate[i];
+        if (v.i_scale[i] >= 0) scale_mask |= 1u << v.i_scale[i];
+    }
+    if (e->cfg.variant == LT_VARIANT_NEXT_MOE) { tanh_mask |= 1u << 5; scale_mask |= 1u << 4; }  // the space branch's chunks
+    const int fin2 = v.final_chunks == 2 ? 1 : 0;
+    LinearSmallMExtra x;
+    const u16* in = e->temb;
+    if (fused_pro & 2) x.a2 = e->cap_emb;
+    else { if (launch_add_bf16(e->temb, e->cap_emb, e->adaln_in, (long long)B * A, s)) return 1; in = e->adaln_in; }
+    if (fused_pro & 4) { x.pm_L = L; x.pm_chunks = e->chunks; x.pm_d = e->d; x.pm_final = fin2; x.pm_tanh = tanh_mask; x.pm_scale = scale_mask; }
+    if (fused_pro & 6 ? launch_linear_small_m_ext(in, e->adaln_w, e->adaln_b, e->mod, B, e->ld_mod, A, 1, x, s)
+                      : launch_linear_small_m(in, e->adaln_w, e->adaln_b, e->mod, B, e->ld_mod, A, 1, s)) return 1;
+    if (!(fused_pro & 4) && launch_prep_mod(e->mod, B, e->ld_mod, L, e->chunks, e->d, tanh_mask, scale_mask, fin2, s)) return 1;
+    return 0;
+}
+
+// ---- the route of a transformer block ------------------------------------------------------------------
+// text keys ride in the self-attention launch (zero-init gated text cross-attention, model.py:420-434); a regional prompt has its own launches
+bool fuses_text(const lt_engine* e) { return e->v.text && !(e->reg_Y > 0) && attention_fuses_text(e->hd); }
+// the self-attention call of the layer with weights w, as the dispatch predicates and the block see it (raw queries: the block adds q_raw)
+AttnArgs self_attn_args(const lt_engine* e, const Dims& dm, const LayerW& w) {
+    AttnArgs at;
+    at.q = e->q; at.k = e->k; at.vt = e->vt; at.bias = nullptr; at.out = e->attn; at.gate = nullptr; at.accumulate = 0;
+    at.B = dm.B; at.H = e->H; at.Hkv = e->Hkv; at.N = dm.N; at.Nk = dm.N; at.Nkpad = dm.Npad; at.hd = e->hd; at.scale = dm.sm_scale; at.k_prescaled = 1;
+    at.nk_batch = dm.nk_dev; at.tail_ws = e->attn_tail_ws; at.tail_ws_bytes = e->attn_tail_ws_bytes;
+    if (fuses_text(e)) { at.tk = w.ky; at.tvt = w.vty; at.tbias = e->txt_bias; at.tgate = w.gate; at.Tk = e->prompt_T; at.Tkpad = e->prompt_Tpad; }
+    return at;
+}
+// ... and its Q | K | V projection with the V^T image as the second output (the routes that do not take it clear VT)
+GemmArgs qkv_gemm_args(const lt_engine* e, const Dims& dm, const LayerW& w) {
+    GemmArgs gq;
+    gq.A = e->h; gq.W = w.wqkv; gq.C = e->qkv; gq.bias = nullptr; gq.bias_dtype = -1; gq.M = dm.M; gq.N = e->d + 2 * e->dkv; gq.K = e->d;
+    gq.lda = e->d; gq.ldw = e->d; gq.ldc = e->qkvn; gq.VT = e->vt; gq.vt_split = e->d + e->dkv; gq.vt_tokens = dm.N; gq.vt_hd = e->hd; gq.vt_npad = dm.Npad;
+    return gq;
+}
+
+// Kernel-selection options (options.h; lt_set_option = process default, lt_engine_set_option = per-engine override) pick among these:
+// QKV_SMALL_FUSED  attn_small_fused, round 5, the class-conditional 600M models at <= 512 tokens: q_norm, k_norm, RoPE, the V transpose and the
+//                  attention are ONE launch behind the small-M QKV GEMM, whose epilogue leaves the LayerNorm partials (AttnSmallArgs / GemmArgs::rowstat)
+// QKV_FUSED        qkv_fused_gemm: Q | K | V in ONE launch where the shapes are whole tiles of the persistent 256 x 288 kernel: Q | K tiles with the
+//                  plain epilogue, V tiles with swapped MFMA operands and the V^T epilogue
+// QKV_QK_AND_VT    qkv_vt_epilogue: the V projection is its own GEMM launch whose epilogue writes the attention kernels' V^T image (no v_transpose
+//                  pass: 15.6 us per layer at cfg 2, and the 37.7 MB V slice is never written row-major / re-read);  QKV_PLAIN  one GEMM, V transposed behind it
+enum QkvRoute { QKV_SMALL_FUSED, QKV_FUSED, QKV_QK_AND_VT, QKV_PLAIN };
+// POST_K_ONLY      raw_q: the attention prologue does the queries, the K pass reduces their LayerNorm partials
+// POST_ONE_LAUNCH  qkv_post_fused 1, or 2 (default) below 2048 rows: q / k post-processing + V transpose in one launch where the problem is
+//                  launch-bound (the three passes are 5 us each at 512 rows - profiles/r02/rocprofv3_kernel_stats_cfg1_r02.csv; bandwidth-bound
+//                  problems: three launches are 0.1-0.2 ms / NFE faster, profiles/r01/bench_ab_qkv_post_fused.log)
+// POST_QK_PAIR     qk_post_pair, from 2048 rows: q and k share one persistent launch [+ V transpose];  POST_SEPARATE  one launch each
+enum PostRoute { POST_K_ONLY, POST_ONE_LAUNCH, POST_QK_PAIR, POST_SEPARATE };
+struct BlockPlan {
+    bool regional, fuse_text;  // compositional Next-DiT: per-caption text attention + region combine / text keys inside the self-attention launch
+    bool pk_one_wave;  // a packed batch whose attention runs on the hd-72 one-wave kernel (the PerSampleKeys instantiation of attention_v4.hip)
+    // V^T epilogue: large problems only (a second launch of a latency-bound 512-row GEMM costs more than the transpose), whole 64-key tiles per
+    // sample (no key padding to zero); packed batches: when the attention masks their pad rows' keys itself (pk_one_wave), else the transpose kernels
+    bool vt_epi;
+    QkvRoute qkv;
+    // attn_q_fused, round 4: with the fused launch the Q columns' LayerNorm partial sums leave the GEMM epilogue (qstat_slots per row; bn: the tile width) and
+    // the attention prologue does q_norm + RoPE itself (AttnArgs::q_raw) - where the hd-72 one-wave kernel takes the call (whole tiles, no packed batch: one
+    // rope_grid_w per launch), the RoPE is 2-D, qk_norm is on, the text keys are fused into the launch or absent, and the prompt is not regional
+    bool raw_q;
+    int bn, qstat_slots;
+    PostRoute post;
+    // pair_layout, round 6: when every GEMM of the dense block runs on the persistent kernel (>= one tile per CU: the fused QKV launch,
+    // O, W1 | W3, W2) and the attention on a one-wave kernel, their A operands and the four weights are kept in the row-pair-interleaved layout
+    // (GemmArgs::pair_ab) - bit-identical to the row-major path.  Packed batches take it, and the V^T epilogue, under pk_one_wave: the pad rows'
+    // K / V words are pad_token pushed through finite weights and a masked key's weight is an exact zero, so nothing has to zero them.
+    bool pair;
+    // the MoE families: the experts' grouped GEMMs on the persistent kernel (>= 1.5 tiles per CU) read their weights, and e->moe_us between the
+    // two, in the pair layout; the W1 | W3 launch gathers its A rows from e->h, which stays row-major (a gathered row's line mate is no neighbour)
+    bool pair_moe;
+};
+
+// Decided once, before the first block, on layer 0's weights: the dispatch predicates ask about shapes, which all layers share
+int plan_block(const lt_engine* e, const Dims& dm, bool packed, BlockPlan& p) {
+    const lt_config& c = e->cfg; const VariantDesc& v = e->v;
+    const int M = dm.M, N = dm.N, d = e->d, dkv = e->dkv, hd = e->hd, F = e->F;
+    const LayerW& w = e->lw[0];
+    p = BlockPlan{}; p.regional = v.text && e->reg_Y > 0; p.fuse_text = fuses_text(e);
+    const AttnArgs at = self_attn_args(e, dm, w);
+    const GemmArgs gq = qkv_gemm_args(e, dm, w);
+    // (head_dim 72 only: a packed batch at another head dim keeps the launches it had, also when every sample has the longest length)
+    p.pk_one_wave = packed && hd == 72 && N % 64 == 0 && attention_one_wave_hd72(at);
+    p.vt_epi = lt_opt(OPT_QKV_VT_EPILOGUE) && (!packed || p.pk_one_wave) && N % 64 == 0 && (long long)((M + 255) / 256) * ((dkv + 255) / 256) >= 128;
+    GemmArgs gs = gq;
+    gs.VT = nullptr;  // (the small-M launch has no second output)
+    const bool small_fused = lt_opt(OPT_ATTN_SMALL_FUSED) && !v.text && c.qk_norm && !v.rope_1d && !packed && !p.vt_epi &&
+                             attention_small_fusable(hd, N, e->H, e->Hkv, d, dkv) && gemm_is_small_m(gs, 0);
+    p.qkv = small_fused ? QKV_SMALL_FUSED : p.vt_epi && lt_opt(OPT_QKV_FUSED_GEMM) && gemm_qkv_fusable(gq) ? QKV_FUSED : p.vt_epi ? QKV_QK_AND_VT : QKV_PLAIN;
+    if (p.qkv == QKV_FUSED) {
+        p.bn = gemm_qkv_tile_width(gq);
+        p.raw_q = lt_opt(OPT_ATTN_Q_FUSED) && c.qk_norm && !v.rope_1d && !packed && !p.regional && (p.fuse_text || !v.text) && attention_takes_raw_q(at) &&
+                  p.bn > 0 && d % p.bn == 0 && 2 * d / p.bn <= 32;
+        if (p.raw_q) p.qstat_slots = 2 * d / p.bn;
+    }
+    p.post = p.raw_q ? POST_K_ONLY
+             : !p.vt_epi && (lt_opt(OPT_QKV_POST_FUSED) == 1 || (lt_opt(OPT_QKV_POST_FUSED) == 2 && M < 2048)) ? POST_ONE_LAUNCH
+             : lt_opt(OPT_QK_POST_PAIR) && M >= 2048 ? POST_QK_PAIR : POST_SEPARATE;
+    if (lt_opt(OPT_PAIR_LAYOUT) && e->E == 0 && (!packed || p.pk_one_wave) && M % 2 == 0 && d % 32 == 0 && F % 32 == 0 && F <= 16384 && d <= 16384 && !p.regional &&
+        (!v.text || attention_fuses_text(hd))) {
+        GemmArgs go, g13, g2;
+        go.A = e->attn; go.W = w.wo; go.C = e->o; go.bias = nullptr; go.bias_dtype = -1; go.M = M; go.N = d; go.K = d; go.lda = d; go.ldw = d; go.ldc = d;
+        g13 = go; g13.A = e->h; g13.W = w.w13; g13.C = e->u; g13.N = 2 * F; g13.ldc = F;
+        g2 = go; g2.A = e->u; g2.W = w.w2; g2.K = F; g2.lda = F; g2.ldw = F;
+        p.pair = p.qkv == QKV_FUSED && gemm_runs_w4q_dense(go, 0) && gemm_runs_w4q_dense(g13, 1) && gemm_runs_w4q_dense(g2, 0) && attention_is_one_wave(at);
+    }
+    if (lt_opt(OPT_PAIR_LAYOUT) && e->E > 0 && d % 32 == 0 && F % 32 == 0 && F <= 16384 && d <= 16384) {
+        GemmArgs g13, g2;
+        moe_gemm_args(e, w.w13_t ? w.w13_t : w.w13_s, w.w2_t ? w.w2_t : w.w2_s, e->moe_tile_expert, e->moe_src, M, g13, g2);
+        p.pair_moe = gemm_runs_w4q_grouped(g13, 1) && gemm_runs_w4q_grouped(g2, 0);
+    }
+    // a graph the caller recorded replays without the engine hearing of it, so it must never meet weights in the other layout: from the first
+    // recorded evaluation on (layout_pinned, set by run_forward) every evaluation runs on row-major weights (ensure_weight_layout)
+    if (e->layout_pinned) { p.pair = false; p.pair_moe = false; }
+    LT_REQUIRE(!p.pair || (p.qkv == QKV_FUSED && !p.regional && (p.fuse_text || !v.text)), "pair layout: the block left the path it was chosen for");
+    return 0;
+}
+
+// the attention branch of a block up to e->attn: QKV projection, q / k post-processing, self-attention [+ text keys], on the plan's route
+int block_attention(lt_engine* e, const Dims& dm, const BlockPlan& bp, LayerW& w, const float* t_dev, const lt_step_args* a, hipStream_t s) {
+    const lt_config& c = e->cfg; const VariantDesc& v = e->v;
+    const int B = dm.B, N = dm.N, Npad = dm.Npad, M = dm.M, d = e->d, dkv = e->dkv, H = e->H, Hkv = e->Hkv, hd = e->hd;
+    GemmArgs gq = qkv_gemm_args(e, dm, w);
+    AttnArgs at = self_attn_args(e, dm, w);
+    if (bp.qkv == QKV_SMALL_FUSED) {
+        gq.VT = nullptr; gq.rowstat = e->qstat; gq.rowstat_slots = e->qstat_slots;
+        if (profiled_gemm(e, gq, 0, 2.0 * M * (double)(d + 2 * dkv) * d, s)) return 1;
+        AttnSmallArgs as;
+        as.qkv = e->qkv; as.ld = e->qkvn; as.q_col0 = 0; as.k_col0 = d; as.v_col0 = d + dkv; as.out = e->attn; as.B = B; as.H = H; as.Hkv = Hkv; as.N = N; as.hd = hd;
+        as.rowstat = e->qstat; as.slots = e->qstat_slots; as.q_slot0 = 0; as.q_nslot = d / 128; as.k_slot0 = d / 128; as.k_nslot = dkv / 128;
+        as.q_ln_w = w.q_norm_w; as.q_ln_b = w.q_norm_b; as.k_ln_w = w.k_norm_w; as.k_ln_b = w.k_norm_b; as.ln_eps = 1e-5f;
+        as.cs = e->rope; as.t = t_dev; as.watershed = 0.f; as.cs_len = e->rope_len; as.grid_w = dm.Wp; as.k_scale = dm.sm_scale * LOG2E;
+        prefetch_rider(e, &as.pf, e->attn, d, w.wo, d, e->o, d, M, d, d, 0);
+        ProfScope ps(e, 1, 4.0 * B * H * (double)N * N * hd, s);
+        return launch_attention_small(as, s) ? 1 : 0;  // (class-conditional: no text keys behind it)
+    }
+    if (bp.qkv == QKV_FUSED) {
+        if (bp.raw_q) { gq.qstat = e->qstat; gq.qstat_cols = d; gq.qstat_slots = bp.qstat_slots; }
+        gq.pair_ab = bp.pair ? 3 : 0;
+        if (profiled_gemm(e, gq, 3, 2.0 * M * (double)(d + 2 * dkv) * d, s)) return 1;
+    } else if (bp.qkv == QKV_QK_AND_VT) {
+        if (gemm(e, e->h, d, w.wqkv, d, e->qkv, e->qkvn, M, d + dkv, d, nullptr, 0, s)) return 1;
+        GemmArgs g;
+        g.A = e->h; g.W = w.wqkv + (size_t)(d + dkv) * d; g.C = e->vt; g.bias = nullptr; g.bias_dtype = -1;
+        g.M = M; g.N = dkv; g.K = d; g.lda = d; g.ldw = d; g.ldc = 0; g.vt_tokens = N; g.vt_hd = hd; g.vt_npad = Npad;
+        if (profiled_gemm(e, g, 2, 2.0 * M * (double)dkv * d, s)) return 1;
+    } else if (gemm(e, e->h, d, w.wqkv, d, e->qkv, e->qkvn, M, e->qkvn, d, nullptr, 0, s)) return 1;
+    {
+        ProfScope ps(e, 2, 0, s);
+        QkPostArgs qa;
+        qa.src = e->qkv; qa.ld_src = e->qkvn; qa.B = B; qa.N = N; qa.hd = hd; qa.rope_mode = v.rope_1d ? 2 : 1;
+        qa.cs = e->rope; qa.t = t_dev; qa.grid_w = dm.Wp; qa.cs_len = e->rope_len; qa.ln_eps = 1e-5f;
+        qa.n_tok_b = dm.ntok_dev; qa.grid_w_b = dm.gw_dev;
+        qa.watershed = c.variant == LT_VARIANT_NEXT_T2I ? a->scale_watershed : 0.f;  // other families: one table (branch 1)
+        QkvPostArgs pa;
+        qa.col0 = 0; qa.heads = H; qa.dst = e->q; qa.ln_w = c.qk_norm ? w.q_norm_w : nullptr; qa.ln_b = c.qk_norm ? w.q_norm_b : nullptr;
+        pa.q = qa;
+        qa.col0 = d; qa.heads = Hkv; qa.dst = e->k; qa.ln_w = c.qk_norm ? w.k_norm_w : nullptr; qa.ln_b = c.qk_norm ? w.k_norm_b : nullptr;
+        qa.out_scale = dm.sm_scale * LOG2E;  // softmax scale folded into K's one bf16 rounding (scores in log2 units)
+        pa.k = qa;
+        pa.v_src = e->qkv; pa.v_dst = e->vt; pa.v_ld_src = e->qkvn; pa.v_col0 = d + dkv; pa.v_B = B; pa.v_N = N; pa.v_Npad = Npad; pa.v_kv_heads = Hkv; pa.v_hd = hd;
+        if (bp.post == POST_K_ONLY) {
+            pa.k.qstat_in = e->qstat; pa.k.qstat_out = e->qmr; pa.k.qstat_slots = bp.qstat_slots; pa.k.qstat_width = d;
+            if (launch_qk_norm_rope(pa.k, s)) return 1;
+            at.q = nullptr; at.q_raw = e->qkv; at.q_ld = e->qkvn; at.q_col0 = 0; at.q_stat = e->qmr; at.q_ln_w = w.q_norm_w; at.q_ln_b = w.q_norm_b;
+            at.rope_cs = e->rope; at.rope_cs_t = e->rope_tr; at.rope_t = t_dev; at.rope_watershed = pa.q.watershed; at.rope_cs_len = e->rope_len; at.rope_grid_w = dm.Wp;
+        } else if (bp.post == POST_ONE_LAUNCH) {
+            if (!bp.regional && (bp.fuse_text || !v.text)) prefetch_rider(e, &pa.pf, e->attn, d, w.wo, d, e->o, d, M, d, d, 0);
+            if (launch_qkv_post(pa, s)) return 1;
+        } else {
+            if (bp.post == POST_QK_PAIR) { if (launch_qk_norm_rope_pair(pa.q, pa.k, s)) return 1; }
+            else if (launch_qk_norm_rope(pa.q, s) || launch_qk_norm_rope(pa.k, s)) return 1;
+            if (!bp.vt_epi && launch_v_transpose(e->qkv, e->qkvn, d + dkv, e->vt, B, N, Npad, Hkv, hd, s)) return 1;
+        }
+    }
+    at.out_pair = bp.pair;
+    if (attention(e, at, s)) return 1;
+    if (bp.regional || (v.text && !bp.fuse_text)) {  // the text keys in launches of their own
+        AttnArgs tx = at;
+        tx.k = w.ky; tx.vt = w.vty; tx.bias = e->txt_bias; tx.nk_batch = nullptr;
+        tx.Nk = e->prompt_T; tx.Nkpad = e->prompt_Tpad; tx.scale = (float)(1.0 / std::sqrt((double)hd));
+        if (!bp.regional) { tx.gate = w.gate; tx.accumulate = 1; return attention(e, tx, s) ? 1 : 0; }
+        // compositional Next-DiT (lumina_next_compositional_generation/models/model.py:422-446): every caption attends the queries of its row (regional
+        // captions -> cond row 0, last -> uncond row 1) into its own buffer, then one pass applies region masks, tanh(gate), the caption sum and the residual add
+        tx.B = e->reg_Y; tx.q_batch_map = e->reg_qmap; tx.gate = nullptr; tx.accumulate = 0; tx.out = e->reg_txt;
+        if (attention(e, tx, s)) return 1;
+        ProfScope ps(e, 2, 0, s);
+        if (launch_region_text_combine(e->attn, e->reg_txt, w.gate, e->reg_Y, N, H, hd, dm.Hp, dm.Wp, e->reg_h, e->reg_w, s)) return 1;
+    }
+    return 0;
+}
+
+// block l on the plan's route; h leaves prepared for layer nl, the next one that runs (L: none does - the final layer's form)
+int run_block(lt_engine* e, const Dims& dm, const BlockPlan& bp, int l, int nl, const float* t_dev, const lt_step_args* a, hipStream_t s) {
+    const VariantDesc& v = e->v;
+    const int B = dm.B, N = dm.N, M = dm.M, d = e->d, F = e->F, pair = bp.pair;
+    const int post_mode = v.post ? 1 : 0, gate_mode = 0;  // gates arrive ready (tanh applied by the conditioning where the family has it)
+    LayerW& w = e->lw[l];
+    if (block_attention(e, dm, bp, w, t_dev, a, s)) return 1;
+    int ys_o = 0, ys_f = 0;
+    if (gemm(e, e->attn, d, w.wo, d, e->o, d, M, d, d, nullptr, 0, s, &ys_o, pair ? 3 : 0)) return 1;
+    {   // x += gate' * post(attn) ; h = pre_ffn(x) * (1 + scale) [+ shift]
+        ProfScope ps(e, 2, 0, s);
+        GatedResArgs g = gated_res_args(e, dm);
+        if (ys_o) { g.ystat = e->ystat; g.ystat_slots = ys_o; }
+        g.y = e->o; g.post_w = v.post ? w.attn_norm2 : nullptr; g.gate = mod_chunk(e, l, v.i_gate[0]);
+        g.post_mode = post_mode; g.gate_mode = gate_mode; g.next_mode = 1; g.h_pair = pair;
+        g.next_w = v.pre_w ? w.ffn_norm1 : nullptr; g.next_scale = mod_chunk(e, l, v.i_scale[1]); g.next_shift = mod_chunk(e, l, v.i_shift[1]);
+        if (e->E == 0) prefetch_rider(e, &g.pf, e->h, d, w.w13, d, e->u, F, M, 2 * F, d, 1);
+        if (launch_gated_residual_norm(g, s)) return 1;
+    }
+    if (e->E == 0) {
+        if (gemm(e, e->h, d, w.w13, d, e->u, F, M, 2 * F, d, nullptr, 1, s, nullptr, pair ? 3 : 0, pair)) return 1;
+        if (gemm(e, e->u, F, w.w2, F, e->o, d, M, d, F, nullptr, 0, s, &ys_f, pair ? 3 : 0)) return 1;
+    } else if (e->moe_mode != 0) {  // one MoE FFN in the ImageNet block (models.py:755-758: time-routed; models1.py: per token)
+        if (moe_ffn(e, w, l, e->moe_mode == 1 ? 0 : 1, M, N, B, s, false, bp.pair_moe)) return 1;
+    } else {  // time MoE -> residual -> space MoE (models2.py:793-800)
+        if (moe_ffn(e, w, l, 0, M, N, B, s, false, bp.pair_moe)) return 1;
+        {
+            ProfScope ps(e, 2, 0, s);
+            GatedResArgs g = gated_res_args(e, dm);
+            moe_y(e, g, l); g.post_w = w.norm_time; g.gate = mod_chunk(e, l, 3); g.post_mode = 1; g.gate_mode = 0; g.next_scale = mod_chunk(e, l, 4); g.next_mode = 1;
+            // round 5 (option moe_route_fused): h is the space router's input and this kernel holds the row - it routes on its way out
+            // (one launch less per layer; moe_route_kernel's arithmetic, statement for statement)
+            if (lt_opt(OPT_MOE_ROUTE_FUSED)) {
+                g.route_w = w.gate_s; g.route_E = e->E; g.route_sel = e->moe_sel; g.route_wts = e->moe_wts;
+                if (e->moe_force_rows) {
+                    LT_REQUIRE(e->moe_force_rows == M, "forced MoE routing was given for %d rows, this call has %d", e->moe_force_rows, M);
+                    g.route_forced = e->moe_force + ((size_t)l * 2 + 1) * (size_t)e->cfg.max_batch * e->cfg.max_tokens * 2;
+                }
+            }
+            if (launch_gated_residual_norm(g, s)) return 1;
+        }
+        if (moe_ffn(e, w, l, 1, M, N, B, s, lt_opt(OPT_MOE_ROUTE_FUSED) != 0, bp.pair_moe)) return 1;
+    }
+    // x += gate' * post(ffn) ; h = next layer's pre-norm + modulate, or the final layer's LayerNorm(no affine, 1e-6) * (1 + scale) [+ shift]
+    ProfScope ps(e, 2, 0, s);
+    GatedResArgs g = gated_res_args(e, dm);
+    g.y = e->o; g.post_w = e->E == 0 ? (v.post ? w.ffn_norm2 : nullptr) : e->moe_mode != 0 ? w.ffn_norm2 : w.norm_space;
+    g.gate = mod_chunk(e, l, e->E != 0 && e->moe_mode == 0 ? 5 : v.i_gate[1]);
+    if (ys_f) { g.ystat = e->ystat; g.ystat_slots = ys_f; }
+    if (e->E != 0) moe_y(e, g, e->moe_mode == 1 ? l : -1);
+    g.post_mode = post_mode; g.gate_mode = gate_mode;
+    if (nl < e->L) {
+        g.next_w = v.pre_w ? e->lw[nl].attn_norm1 : nullptr; g.next_scale = mod_chunk(e, nl, v.i_scale[0]);
+        g.next_shift = mod_chunk(e, nl, v.i_shift[0]); g.next_mode = 1; g.h_pair = pair;
+        prefetch_rider(e, &g.pf, e->h, d, e->lw[nl].wqkv, d, e->qkv, e->qkvn, M, e->qkvn, d, 0);
+    } else { g.next_w = nullptr; g.next_mode = 2; g.next_shift = final_shift(e); g.next_scale = final_scale(e); }
+    return launch_gated_residual_norm(g, s) ? 1 : 0;
+}
+
+// One evaluation as plain launches: the refusals (forward_dims), [a head: embed_patches, condition,] plan_block + weight layout, [a head: the first
+// pre-norm,] run_block for every layer that is not skipped, [a step-caching cut,] the final linear and the closing step.  kind (eval_kind.h): other than
+// LT_KIND_WHOLE for a tensor state only.  The three parts of an evaluation under step caching are cut behind the first pre-norm and the last block
+int run_forward(lt_engine* e, const void* x_in, const float* t_dev, void* out, const lt_step_args* a, int use_cfg,
+                hipStream_t s, const PackedDesc* pk = nullptr, LtEvalKind kind = LT_KIND_WHOLE) {
+    const lt_config& c = e->cfg; const VariantDesc& v = e->v;
+    const int L = e->L, d = e->d;
+    Dims dm;
+    if (int rc = forward_dims(e, a, use_cfg, s, pk, kind, dm)) return rc;
+    const int B = dm.B, N = dm.N, M = dm.M;
+    const bool do_head = lt_eval_traits(kind).reads_x, do_blocks = kind != LT_KIND_CACHE_HEAD && kind != LT_KIND_CACHE_APPLY;
     // the CALLER is recording this evaluation into a graph of its own (e->tally: the capture is the engine's, forward_graphed).  Nothing was
     // launched yet: what cannot be recorded is refused here, and the capture stays valid
     const bool caller_cap = !e->tally && stream_capturing(s);
     if (caller_cap && refuse_profile_if_capturing(e, s, "model evaluation")) return 2;
-    float sm_scale;
-    if (softmax_scale_for(e, a, N, &sm_scale)) return 1;
+    if (softmax_scale_for(e, a, N, &dm.sm_scale)) return 1;
     // the last refusal is behind us and the first launch ahead: only an evaluation that IS recorded pins the engine (and before ensure_rope:
     // the table's rebuild is recorded whatever the host believes the table holds)
     if (caller_cap) e->layout_pinned = true;
     if (ensure_rope(e, a, s)) return 1;
-
-    // patchify + x_embedder (model.py:777-779) [+ eol token per row]
-    const int *ntok_dev = nullptr, *gw_dev = nullptr;
-    if (!do_head) {  // (a part behind the head: x_0, h and the modulation are in place)
-    } else if (!pk) {
-        ProfScope ps(e, 2, 0, s);
-        if (launch_patchify(x_in, a->io_dtype, e->patches, B, c.in_channels, a->latent_h, a->latent_w, p, e->kpad, use_cfg, Wrow, s)) return 1;
-    } else if (pk->tab) {  // one launch for all samples; the table was stored by the entry point
-        ProfScope ps(e, 2, 0, s);
-        if (launch_patchify_packed(pk->x_flat, a->io_dtype, e->patches, pk->tab, B, c.in_channels, p, e->kpad, N, use_cfg, s)) return 1;
-        ntok_dev = pk->tab + LT_PK_NTOK * LT_PK_MAX; gw_dev = pk->tab + LT_PK_GW * LT_PK_MAX;
-    } else {
-        ProfScope ps(e, 2, 0, s);
-        for (int b = 0; b < B; ++b)
-            if (launch_patchify(pk->x_ptrs[b], a->io_dtype, e->patches + (size_t)b * N * e->kpad, 1, c.in_channels, pk->hw[2 * b],
-                                pk->hw[2 * b + 1], p, e->kpad, 0, 0, s)) return 1;
-        // per-sample token count / grid width for the rotary positions and the key mask
-        memcpy(e->pk_host, pk_ntok, B * sizeof(int));
-        memcpy(e->pk_host + 64, pk_gw, B * sizeof(int));
-        LT_CHECK_HIP(hipMemcpyAsync(e->pk_dev, e->pk_host, 128 * sizeof(int), hipMemcpyHostToDevice, s));
-        ntok_dev = e->pk_dev; gw_dev = e->pk_dev + 64;
-    }
-    if (do_head && gemm(e, e->patches, e->kpad, e->xemb_w, e->kpad, e->x, d, M, d, e->kpad, e->xemb_b, 0, s)) return 1;
-    if (pk && pk->tab) {
-        ProfScope ps(e, 2, 0, s);
-        if (!pk_full && launch_fill_pad_packed(e->x, e->pad_token, pk->tab, B, N, d, s)) return 1;
-    } else if (pk) {  // padded positions hold the learned pad_token, not an embedded patch (model.py:811-817)
-        ProfScope ps(e, 2, 0, s);
-        for (int b = 0; b < B; ++b)
-            if (pk_ntok[b] < N && launch_fill_rows_bf16(e->x + ((size_t)b * N + pk_ntok[b]) * d, e->pad_token, N - pk_ntok[b], d, s)) return 1;
-    }
-    if (v.eol && do_head) {
-        ProfScope ps(e, 2, 0, s);
-        if (launch_eol_fill(e->x, e->eol_token, B * Hp, Wp, d, s)) return 1;
-    }
+    if (do_head && embed_patches(e, dm, x_in, a, use_cfg, pk, s)) return 1;  // (a part behind the head: x_0, h and the modulation are in place)
     // (host state the blocks read: the same for every part of an evaluation, whichever of them ran as plain launches)
     e->moe_tp_live = e->gate_t_all && e->moe_tp_sel && lt_opt(OPT_MOE_TIME_PLAN_HOIST) && !e->moe_force_rows && B <= LT_MOE_PLAN_TIME_MAX_SAMPLES;
-    // conditioning: t_embedder (model.py:84-87) + caption / label embedding (hoisted) -> adaLN vectors of every layer + final
-    if (do_head) {
-        ProfScope ps(e, 2, 0, s);
-        const int fused_pro = lt_opt(OPT_PROLOGUE_FUSED);  // round 6, bit mask: 1 timestep features, 2 temb + embedding, 4 prep_mod - each one launch less, bit-identical (LinearSmallMExtra)
-        if (fused_pro & 1) {
-            LinearSmallMExtra x;
-            x.t = t_dev;
-            if (launch_linear_small_m_ext(nullptr, e->t0_w, e->t0_b, e->t1, B, A, 256, 0, x, s)) return 1;
-        } else {
-            if (launch_timestep_features(t_dev, 0, e->tfeat, B, 256, s)) return 1;
-            if (launch_linear_small_m(e->tfeat, e->t0_w, e->t0_b, e->t1, B, A, 256, 0, s)) return 1;
-        }
-        if (launch_linear_small_m(e->t1, e->t2_w, e->t2_b, e->temb, B, A, A, 1, s)) return 1;
-        if (e->gate_t_all && launch_linear_small_m(e->temb, e->gate_t_all, nullptr, e->moe_logits, B, L * e->E, A, 0, s)) return 1;  // every layer's time-router logits
-        if (e->moe_tp_live) {  // ... and every layer's time plan: they depend on nothing else (one launch instead of L)
-            MoeArgs m;
-            m.x = nullptr; m.gate_w = nullptr; m.forced = nullptr; m.sample_logits = e->moe_logits; m.sample_ld = L * e->E;
-            m.rows = M; m.rows_per_sample = N; m.d = d; m.E = e->E;
-            m.sel = e->moe_tp_sel; m.pos = e->moe_tp_pos; m.wts = e->moe_tp_wts; m.src = e->moe_tp_src; m.tile_expert = e->moe_tp_tile_expert;
-            m.max_tiles = (int)((2 * (size_t)M + (size_t)e->E * 255 + 255) / 256);  // = moe_ffn's bound for this call's rows
-            m.layers = L; m.layer_stride_rows = (long long)e->moe_tp_stride_rows; m.layer_stride_src = (long long)e->moe_tp_stride_src;
-            m.layer_stride_tiles = e->moe_tiles;
-            if (launch_moe_plan(m, s)) return 1;
-        }
-        // once per (sample, channel) instead of once per token inside the row kernels: tanh of the gate chunks (where the
-        // family has it) and bf16(1 + scale) of every scale chunk
-        unsigned tanh_mask = 0, scale_mask = 0;
-        for (int i = 0; i < 2; ++i) {
-            if (v.gate_tanh && v.i_gate[i] >= 0) tanh_mask |= 1u << v.i_gate[i];
-            if (v.i_scale[i] >= 0) scale_mask |= 1u << v.i_scale[i];
-        }
-        if (c.variant == LT_VARIANT_NEXT_MOE) { tanh_mask |= 1u << 5; scale_mask |= 1u << 4; }  // the space branch's chunks
-        if (fused_pro & 6) {
-            LinearSmallMExtra x;
-            const u16* in = e->temb;
-            if (fused_pro & 2) x.a2 = e->cap_emb;
-            else { if (launch_add_bf16(e->temb, e->cap_emb, e->adaln_in, (long long)B * A, s)) return 1; in = e->adaln_in; }
-            if (fused_pro & 4) { x.pm_L = L; x.pm_chunks = e->chunks; x.pm_d = e->d; x.pm_final = v.final_chunks == 2 ? 1 : 0; x.pm_tanh = tanh_mask; x.pm_scale = scale_mask; }
-            if (launch_linear_small_m_ext(in, e->adaln_w, e->adaln_b, e->mod, B, e->ld_mod, A, 1, x, s)) return 1;
-            if (!(fused_pro & 4) && launch_prep_mod(e->mod, B, e->ld_mod, L, e->chunks, e->d, tanh_mask, scale_mask, v.final_chunks == 2 ? 1 : 0, s)) return 1;
-        } else {
-            if (launch_add_bf16(e->temb, e->cap_emb, e->adaln_in, (long long)B * A, s)) return 1;
-            if (launch_linear_small_m(e->adaln_in, e->adaln_w, e->adaln_b, e->mod, B, e->ld_mod, A, 1, s)) return 1;
-            if (launch_prep_mod(e->mod, B, e->ld_mod, L, e->chunks, e->d, tanh_mask, scale_mask, v.final_chunks == 2 ? 1 : 0, s)) return 1;
-        }
-    }
-    auto chunk = [&](int layer, int idx) -> const u16* { return idx < 0 ? nullptr : e->mod + (size_t)layer * cd + (size_t)idx * d; };
-    // round 6, option pair_layout: when every GEMM of the dense block runs on the persistent kernel (>= one tile per CU: the fused QKV launch,
-    // O, W1 | W3, W2) and the attention on a one-wave kernel, their A operands (h, the attention output, the SwiGLU output) and the four
-    // weights are kept in the row-pair-interleaved layout (GemmArgs::pair_ab): the GEMM's LDS-DMA stream then asks the L2 for whole 128-byte
-    // lines - half the requests.  Same products in the same order: bit-identical to the row-major path.
-    // Packed batches take both this regime and the V^T epilogue below when their attention call runs on a one-wave kernel (hd 72: the
-    // PerSampleKeys instantiation of attention_v4.hip) and the longest sequence is whole 64-key tiles: the pad rows' K / V words are
-    // pad_token pushed through finite weights, and the kernel gives a masked key an exact zero weight (0 x finite = 0), so nothing has
-    // to zero them.  raw_q stays off for packed batches (one rope_grid_w per launch): qk_norm_rope does Q with n_tok_b / grid_w_b.
-    AttnArgs at0;  // the layer loop's self-attention call, as far as the dispatch looks at it
-    at0.q = e->q; at0.k = e->k; at0.vt = e->vt; at0.bias = nullptr; at0.out = e->attn; at0.gate = nullptr; at0.accumulate = 0;
-    at0.B = B; at0.H = H; at0.Hkv = Hkv; at0.N = N; at0.Nk = N; at0.Nkpad = Npad; at0.hd = hd; at0.scale = sm_scale; at0.k_prescaled = 1;
-    at0.nk_batch = pk && pk->tab && pk_full ? nullptr : ntok_dev;
-    if (v.text && !(e->reg_Y > 0) && attention_fuses_text(hd)) {
-        at0.tk = e->lw[0].ky; at0.tvt = e->lw[0].vty; at0.tbias = e->txt_bias; at0.tgate = e->lw[0].gate; at0.Tk = e->prompt_T; at0.Tkpad = e->prompt_Tpad;
-    }
-    // (head_dim 72 only: a packed batch at another head dim keeps the launches it had, also when every sample has the longest length)
-    const bool pk_one_wave = pk && hd == 72 && N % 64 == 0 && attention_one_wave_hd72(at0);
-    bool pair = false;
-    if (lt_opt(OPT_PAIR_LAYOUT) && e->E == 0 && (!pk || pk_one_wave) && M % 2 == 0 && d % 32 == 0 && F % 32 == 0 && F <= 16384 && d <= 16384 && !(v.text && e->reg_Y > 0) &&
-        (!v.text || attention_fuses_text(hd))) {
-        GemmArgs gq;
-        gq.A = e->h; gq.W = e->lw[0].wqkv; gq.C = e->qkv; gq.bias = nullptr; gq.bias_dtype = -1; gq.M = M; gq.N = d + 2 * dkv; gq.K = d;
-        gq.lda = d; gq.ldw = d; gq.ldc = e->qkvn; gq.VT = e->vt; gq.vt_split = d + dkv; gq.vt_tokens = N; gq.vt_hd = hd; gq.vt_npad = Npad;
-        const bool vt_epi0 = lt_opt(OPT_QKV_VT_EPILOGUE) && N % 64 == 0 && (long long)((M + 255) / 256) * ((dkv + 255) / 256) >= 128;
-        GemmArgs go, g13, g2;
-        go.A = e->attn; go.W = e->lw[0].wo; go.C = e->o; go.bias = nullptr; go.bias_dtype = -1; go.M = M; go.N = d; go.K = d; go.lda = d; go.ldw = d; go.ldc = d;
-        g13 = go; g13.A = e->h; g13.W = e->lw[0].w13; g13.C = e->u; g13.N = 2 * F; g13.ldc = F;
-        g2 = go; g2.A = e->u; g2.W = e->lw[0].w2; g2.K = F; g2.lda = F; g2.ldw = F;
-        pair = vt_epi0 && lt_opt(OPT_QKV_FUSED_GEMM) && gemm_qkv_fusable(gq) && gemm_runs_w4q_dense(go, 0) && gemm_runs_w4q_dense(g13, 1) &&
-               gemm_runs_w4q_dense(g2, 0) && attention_is_one_wave(at0);
-    }
-    // the MoE families: the experts' grouped GEMMs on the persistent kernel (>= 1.5 tiles per CU: the 600M MoE at 1024^2) read their weights in the
-    // pair layout, and the SwiGLU output between the two (e->moe_us) is written / read in it; the W1 | W3 launch gathers its A rows one by one
-    // from e->h, which stays row-major (a gathered row's line mate is not its neighbour in the tile)
-    bool pair_moe = false;
-    if (lt_opt(OPT_PAIR_LAYOUT) && e->E > 0 && d % 32 == 0 && F % 32 == 0 && F <= 16384 && d <= 16384) {
-        const int tiles = (int)((2 * (size_t)M + (size_t)e->E * 255 + 255) / 256);
-        GemmArgs g13, g2;
-        g13.bias = nullptr; g13.bias_dtype = -1; g13.tile_expert = e->moe_tile_expert;
-        g13.A = e->h; g13.a_row_map = e->moe_src; g13.a_map_rows = M; g13.W = e->lw[0].w13_t ? e->lw[0].w13_t : e->lw[0].w13_s; g13.C = e->moe_us;
-        g13.M = tiles * 256; g13.N = 2 * F; g13.K = d; g13.lda = d; g13.ldw = d; g13.ldc = F; g13.w_expert_stride = (long long)2 * F * d;
-        g2 = g13;
-        g2.A = e->moe_us; g2.a_row_map = nullptr; g2.a_map_rows = 0; g2.W = e->lw[0].w2_t ? e->lw[0].w2_t : e->lw[0].w2_s; g2.C = e->moe_ys;
-        g2.N = d; g2.K = F; g2.lda = F; g2.ldw = F; g2.ldc = d; g2.w_expert_stride = (long long)d * F;
-        pair_moe = gemm_runs_w4q_grouped(g13, 1) && gemm_runs_w4q_grouped(g2, 0);
-    }
-    // a graph the caller recorded replays without the engine hearing of it, so it must never meet weights in the other layout: a recorded
-    // evaluation runs on row-major weights, and from the first one on (layout_pinned, set above) so does every other evaluation - the weights
-    // stay row-major for the engine's life.  Weights found in the pair layout by the recording are converted by the graph itself, once
-    // (ensure_weight_layout, recording).  The engine's own graphs are captured after their key's eager run and follow the same rule.
-    if (e->layout_pinned) { pair = false; pair_moe = false; }
-    if (ensure_weight_layout(e, pair || pair_moe, s, caller_cap)) return 1;
-    e->last_pair = pair || pair_moe;
-    // layer skip: the blocks in e->skip (ascending; a SkipScope of the entry point stored it, checked) are the identity on e->x -
-    // they launch nothing, and whoever prepares h prepares it for nx(l), the next layer that runs (L: none does, the final layer's form).
-    // Empty set: nx(l) = l + 1, first = 0 - the launches of always.  (The lw[0] probes above ask about shapes, which all layers share.)
-    const std::vector<int32_t>& skip = e->skip;
-    auto skipped = [&](int l) { return std::binary_search(skip.begin(), skip.end(), l); };
+    if (do_head && condition(e, dm, t_dev, s)) return 1;
+    BlockPlan bp;
+    if (int rc = plan_block(e, dm, pk != nullptr, bp)) return rc;
+    if (ensure_weight_layout(e, bp.pair || bp.pair_moe, s, caller_cap)) return 1;
+    e->last_pair = bp.pair || bp.pair_moe;
+    // layer skip: the blocks in e->skip (ascending; a SkipScope of the entry point stored it, checked) are the identity on e->x - they launch
+    // nothing, and whoever prepares h prepares it for nx(l), the next layer that runs (L: none does).  Empty set: nx(l) = l + 1, first = 0
+    auto skipped = [&](int l) { return std::binary_search(e->skip.begin(), e->skip.end(), l); };
     auto nx = [&](int l) { int n = l + 1; while (n < L && skipped(n)) ++n; return n; };
     const int first = nx(-1);  // (< L: the set is distinct and shorter than L, checked before the first launch)
-    // first pre-norm: modulate(attention_norm(x), [shift,] scale) (model.py:599 / models.py:785 / lumina_t2i model.py:600)
-    if (do_head) {
+    if (do_head) {  // first pre-norm: modulate(attention_norm(x), [shift,] scale) (model.py:599 / models.py:785 / lumina_t2i model.py:600)
         ProfScope ps(e, 2, 0, s);
         NormModArgs n;
-        n.x = e->x; n.w = v.pre_w ? e->lw[first].attn_norm1 : nullptr; n.scale = chunk(first, v.i_scale[0]); n.shift = chunk(first, v.i_shift[0]);
-        n.out = e->h; n.rows = M; n.rows_per_batch = N; n.d = d; n.ld_mod = e->ld_mod; n.eps = c.norm_eps; n.scale_pre = 1;
-        n.out_pair = pair;
+        n.x = e->x; n.w = v.pre_w ? e->lw[first].attn_norm1 : nullptr; n.scale = mod_chunk(e, first, v.i_scale[0]); n.shift = mod_chunk(e, first, v.i_shift[0]);
+        n.out = e->h; n.rows = M; n.rows_per_batch = N; n.d = d; n.ld_mod = e->ld_mod; n.eps = c.norm_eps; n.scale_pre = 1; n.out_pair = bp.pair;
         if (launch_rmsnorm_mod(n, s)) return 1;
     }
     if (kind == LT_KIND_CACHE_HEAD) {  // step caching, first cut: the indicator on h (in the layout this key's evaluations leave it in), x_0 kept
@@ -660,221 +855,24 @@ int run_forward(lt_engine* e, const void* x_in, const float* t_dev, void* out, c
         LT_CHECK_HIP(hipMemcpyAsync(e->c_x0, e->x, (size_t)M * d * sizeof(u16), hipMemcpyDeviceToDevice, s));
         return 0;
     }
-    const int post_mode = v.post ? 1 : 0, gate_mode = 0;  // gates arrive ready (tanh applied above where the family has it)
-    for (int l = do_blocks ? first : L; l < L; l = nx(l)) {
-        LayerW& w = e->lw[l];
-        const int nl = nx(l);  // the layer h is prepared for at this block's end
-        // V^T epilogue path: q | k columns in one GEMM, the V columns in a second one that writes e->vt directly.  Large problems
-        // only (a second launch of a latency-bound 512-row GEMM costs more than the transpose), whole 64-key tiles per sample
-        // (no key padding to zero); packed batches: when the attention masks their pad rows' keys itself (pk_one_wave above), else the
-        // transpose kernels
-        const bool vt_epi = lt_opt(OPT_QKV_VT_EPILOGUE) && (!pk || pk_one_wave) && N % 64 == 0 && (long long)((M + 255) / 256) * ((dkv + 255) / 256) >= 128;
-        // ... and ONE launch for all three when the shapes are whole tiles of the persistent 256 x 288 kernel (lt_set_option
-        // "qkv_fused_gemm"): Q | K tiles with the plain epilogue, V tiles with swapped MFMA operands and the V^T epilogue
-        GemmArgs gq;
-        gq.A = e->h; gq.W = w.wqkv; gq.C = e->qkv; gq.bias = nullptr; gq.bias_dtype = -1; gq.M = M; gq.N = d + 2 * dkv; gq.K = d;
-        gq.lda = d; gq.ldw = d; gq.ldc = e->qkvn; gq.VT = e->vt; gq.vt_split = d + dkv; gq.vt_tokens = N; gq.vt_hd = hd; gq.vt_npad = Npad;
-        // round 4: with the fused launch the Q columns' LayerNorm partial sums leave the GEMM epilogue and the attention kernel's prologue
-        // does q_norm + RoPE itself (AttnArgs::q_raw): qk_norm_rope then runs for K only.  Conditions: the hd-72 one-wave kernel takes
-        // the call (whole tiles, no packed batch), 2-D RoPE, qk_norm on, text keys fused into the launch or absent, not regional.
-        const bool regional = v.text && e->reg_Y > 0;
-        const bool fuse_text = v.text && !regional && attention_fuses_text(hd);
-        AttnArgs at;
-        at.q = e->q; at.k = e->k; at.vt = e->vt; at.bias = nullptr; at.out = e->attn; at.gate = nullptr; at.accumulate = 0;
-        at.B = B; at.H = H; at.Hkv = Hkv; at.N = N; at.Nk = N; at.Nkpad = Npad; at.hd = hd; at.scale = sm_scale;
-        at.k_prescaled = 1;
-        at.nk_batch = pk && pk->tab && pk_full ? nullptr : ntok_dev;  // (flat form, every sample of the longest length: no key to mask)
-        at.tail_ws = e->attn_tail_ws; at.tail_ws_bytes = e->attn_tail_ws_bytes;
-        if (fuse_text) {  // zero-init gated text cross-attention (model.py:420-434) inside the same launch
-            at.tk = w.ky; at.tvt = w.vty; at.tbias = e->txt_bias; at.tgate = w.gate; at.Tk = e->prompt_T; at.Tkpad = e->prompt_Tpad;
-        }
-        bool raw_q = false;
-        // round 5, the class-conditional 600M models at <= 512 tokens: q_norm, k_norm, RoPE, the V transpose and the attention are ONE
-        // launch behind the small-M QKV GEMM, whose epilogue leaves the LayerNorm partials (AttnSmallArgs / GemmArgs::rowstat)
-        gq.VT = nullptr;
-        const bool small_fused = lt_opt(OPT_ATTN_SMALL_FUSED) && !v.text && c.qk_norm && !v.rope_1d && !pk && !vt_epi &&
-                                 attention_small_fusable(hd, N, H, Hkv, d, dkv) && gemm_is_small_m(gq, 0);
-        gq.VT = e->vt;
-        if (small_fused) {
-            gq.VT = nullptr; gq.rowstat = e->qstat; gq.rowstat_slots = e->qstat_slots;
-            {
-                ProfScope ps(e, 0, 2.0 * M * (double)(d + 2 * dkv) * d, s, true);
-                if (launch_gemm_bf16(gq, 0, 0, s, ps.ev0(), ps.ev1())) return 1;
-            }
-            AttnSmallArgs as;
-            as.qkv = e->qkv; as.ld = e->qkvn; as.q_col0 = 0; as.k_col0 = d; as.v_col0 = d + dkv;
-            as.rowstat = e->qstat; as.slots = e->qstat_slots; as.q_slot0 = 0; as.q_nslot = d / 128; as.k_slot0 = d / 128; as.k_nslot = dkv / 128;
-            as.q_ln_w = w.q_norm_w; as.q_ln_b = w.q_norm_b; as.k_ln_w = w.k_norm_w; as.k_ln_b = w.k_norm_b; as.ln_eps = 1e-5f;
-            as.cs = e->rope; as.t = t_dev; as.watershed = 0.f; as.cs_len = e->rope_len; as.grid_w = Wp;
-            as.k_scale = sm_scale * LOG2E; as.out = e->attn; as.B = B; as.H = H; as.Hkv = Hkv; as.N = N; as.hd = hd;
-            prefetch_rider(e, &as.pf, e->attn, d, w.wo, d, e->o, d, M, d, d, 0);
-            ProfScope ps(e, 1, 4.0 * B * H * (double)N * N * hd, s);
-            if (launch_attention_small(as, s)) return 1;
-        } else
-        if (vt_epi && lt_opt(OPT_QKV_FUSED_GEMM) && gemm_qkv_fusable(gq)) {
-            const int bn = gemm_qkv_tile_width(gq);
-            raw_q = lt_opt(OPT_ATTN_Q_FUSED) && c.qk_norm && !v.rope_1d && !pk && !regional && (fuse_text || !v.text) && attention_takes_raw_q(at) &&
-                    bn > 0 && d % bn == 0 && 2 * d / bn <= 32;
-            if (raw_q) { gq.qstat = e->qstat; gq.qstat_cols = d; gq.qstat_slots = 2 * d / bn; }
-            gq.pair_ab = pair ? 3 : 0;
-            ProfScope ps(e, 0, 2.0 * M * (double)(d + 2 * dkv) * d, s, true);
-            if (launch_gemm_bf16(gq, 3, 0, s, ps.ev0(), ps.ev1())) return 1;
-        } else if (vt_epi) {
-            if (gemm(e, e->h, d, w.wqkv, d, e->qkv, e->qkvn, M, d + dkv, d, nullptr, 0, s)) return 1;
-            GemmArgs g;
-            g.A = e->h; g.W = w.wqkv + (size_t)(d + dkv) * d; g.C = e->vt; g.bias = nullptr; g.bias_dtype = -1;
-            g.M = M; g.N = dkv; g.K = d; g.lda = d; g.ldw = d; g.ldc = 0; g.vt_tokens = N; g.vt_hd = hd; g.vt_npad = Npad;
-            ProfScope ps(e, 0, 2.0 * M * (double)dkv * d, s, true);
-            if (launch_gemm_bf16(g, 2, 0, s, ps.ev0(), ps.ev1())) return 1;
-        } else if (gemm(e, e->h, d, w.wqkv, d, e->qkv, e->qkvn, M, e->qkvn, d, nullptr, 0, s)) return 1;
-        if (!small_fused) {
-            ProfScope ps(e, 2, 0, s);
-            QkPostArgs qa;
-            qa.src = e->qkv; qa.ld_src = e->qkvn; qa.B = B; qa.N = N; qa.hd = hd; qa.rope_mode = v.rope_1d ? 2 : 1;
-            qa.cs = e->rope; qa.t = t_dev; qa.grid_w = Wp; qa.cs_len = e->rope_len; qa.ln_eps = 1e-5f;
-            qa.n_tok_b = ntok_dev; qa.grid_w_b = gw_dev;
-            qa.watershed = c.variant == LT_VARIANT_NEXT_T2I ? a->scale_watershed : 0.f;  // other families: one table (branch 1)
-            QkvPostArgs pa;
-            qa.col0 = 0; qa.heads = H; qa.dst = e->q;
-            qa.ln_w = c.qk_norm ? w.q_norm_w : nullptr; qa.ln_b = c.qk_norm ? w.q_norm_b : nullptr;
-            pa.q = qa;
-            qa.col0 = d; qa.heads = Hkv; qa.dst = e->k;
-            qa.ln_w = c.qk_norm ? w.k_norm_w : nullptr; qa.ln_b = c.qk_norm ? w.k_norm_b : nullptr;
-            qa.out_scale = sm_scale * LOG2E;  // softmax scale folded into K's one bf16 rounding (scores in log2 units)
-            pa.k = qa;
-            pa.v_src = e->qkv; pa.v_dst = e->vt; pa.v_ld_src = e->qkvn; pa.v_col0 = d + dkv; pa.v_B = B; pa.v_N = N;
-            pa.v_Npad = Npad; pa.v_kv_heads = Hkv; pa.v_hd = hd;
-            if (raw_q) {
-                // K only: the queries are normalised and rotated by the attention prologue; the K pass reduces their LayerNorm partials
-                pa.k.qstat_in = e->qstat; pa.k.qstat_out = e->qmr; pa.k.qstat_slots = gq.qstat_slots; pa.k.qstat_width = d;
-                if (launch_qk_norm_rope(pa.k, s)) return 1;
-                at.q = nullptr; at.q_raw = e->qkv; at.q_ld = e->qkvn; at.q_col0 = 0; at.q_stat = e->qmr;
-                at.q_ln_w = w.q_norm_w; at.q_ln_b = w.q_norm_b;
-                at.rope_cs = e->rope; at.rope_cs_t = e->rope_tr; at.rope_t = t_dev; at.rope_watershed = pa.q.watershed;
-                at.rope_cs_len = e->rope_len; at.rope_grid_w = Wp;
-            } else if (!vt_epi && (lt_opt(OPT_QKV_POST_FUSED) == 1 || (lt_opt(OPT_QKV_POST_FUSED) == 2 && M < 2048))) {
-                if (!regional && (fuse_text || !v.text)) prefetch_rider(e, &pa.pf, e->attn, d, w.wo, d, e->o, d, M, d, d, 0);
-                if (launch_qkv_post(pa, s)) return 1;  // q, k post-processing and the V transpose in one launch
-            } else if (lt_opt(OPT_QK_POST_PAIR) && M >= 2048) {
-                if (launch_qk_norm_rope_pair(pa.q, pa.k, s)) return 1;  // q and k in one persistent launch
-                if (!vt_epi && launch_v_transpose(e->qkv, e->qkvn, d + dkv, e->vt, B, N, Npad, Hkv, hd, s)) return 1;
-            } else {
-                if (launch_qk_norm_rope(pa.q, s)) return 1;
-                if (launch_qk_norm_rope(pa.k, s)) return 1;
-                if (!vt_epi && launch_v_transpose(e->qkv, e->qkvn, d + dkv, e->vt, B, N, Npad, Hkv, hd, s)) return 1;
-            }
-        }
-        LT_REQUIRE(!pair || (!small_fused && vt_epi && gq.pair_ab && !regional && (fuse_text || !v.text)), "pair layout: the block left the path it was chosen for");
-        at.out_pair = pair;
-        if (!small_fused && attention(e, at, s)) return 1;
-        if (regional) {
-            // compositional Next-DiT (lumina_next_compositional_generation/models/model.py:422-446): every caption attends the
-            // queries of its row (regional captions -> cond row 0, last caption -> uncond row 1) into its own buffer, then one
-            // pass applies region masks, tanh(gate), the caption sum and the residual add with the reference's rounding points
-            AttnArgs rt = at;
-            rt.B = e->reg_Y; rt.q_batch_map = e->reg_qmap; rt.k = w.ky; rt.vt = w.vty; rt.bias = e->txt_bias; rt.gate = nullptr;
-            rt.accumulate = 0; rt.out = e->reg_txt; rt.nk_batch = nullptr;
-            rt.Nk = e->prompt_T; rt.Nkpad = e->prompt_Tpad; rt.scale = (float)(1.0 / std::sqrt((double)hd));
-            if (attention(e, rt, s)) return 1;
-            ProfScope ps(e, 2, 0, s);
-            if (launch_region_text_combine(e->attn, e->reg_txt, w.gate, e->reg_Y, N, H, hd, Hp, Wp, e->reg_h, e->reg_w, s)) return 1;
-        } else if (v.text && !fuse_text) {
-            at.k = w.ky; at.vt = w.vty; at.bias = e->txt_bias; at.gate = w.gate; at.accumulate = 1; at.nk_batch = nullptr;
-            at.Nk = e->prompt_T; at.Nkpad = e->prompt_Tpad; at.scale = (float)(1.0 / std::sqrt((double)hd));
-            if (attention(e, at, s)) return 1;
-        }
-        int ys_o = 0, ys_f = 0;
-        if (gemm(e, e->attn, d, w.wo, d, e->o, d, M, d, d, nullptr, 0, s, &ys_o, pair ? 3 : 0)) return 1;
-        {   // x += gate' * post(attn) ; h = pre_ffn(x) * (1 + scale) [+ shift]
-            ProfScope ps(e, 2, 0, s);
-            GatedResArgs g;
-            if (ys_o) { g.ystat = e->ystat; g.ystat_slots = ys_o; }
-            g.x = e->x; g.y = e->o; g.post_w = v.post ? w.attn_norm2 : nullptr; g.gate = chunk(l, v.i_gate[0]);
-            g.post_mode = post_mode; g.gate_mode = gate_mode;
-            g.next_w = v.pre_w ? w.ffn_norm1 : nullptr; g.next_scale = chunk(l, v.i_scale[1]); g.next_shift = chunk(l, v.i_shift[1]);
-            g.next_mode = 1; g.h = e->h; g.h_pair = pair;
-            g.rows = M; g.rows_per_batch = N; g.d = d; g.ld_mod = e->ld_mod; g.eps = c.norm_eps; g.eps_next = 1e-6f; g.scale_pre = 1;
-            if (e->E == 0) prefetch_rider(e, &g.pf, e->h, d, w.w13, d, e->u, F, M, 2 * F, d, 1);
-            if (launch_gated_residual_norm(g, s)) return 1;
-        }
-        const u16 *last_post_w, *last_gate;
-        if (e->E == 0) {
-            if (gemm(e, e->h, d, w.w13, d, e->u, F, M, 2 * F, d, nullptr, 1, s, nullptr, pair ? 3 : 0, pair)) return 1;
-            if (gemm(e, e->u, F, w.w2, F, e->o, d, M, d, F, nullptr, 0, s, &ys_f, pair ? 3 : 0)) return 1;
-            last_post_w = v.post ? w.ffn_norm2 : nullptr;
-            last_gate = chunk(l, v.i_gate[1]);
-        } else if (e->moe_mode != 0) {  // one MoE FFN in the ImageNet block (models.py:755-758: time-routed; models1.py: per token)
-            if (moe_ffn(e, w, l, e->moe_mode == 1 ? 0 : 1, M, N, B, s, false, pair_moe)) return 1;
-            last_post_w = w.ffn_norm2;
-            last_gate = chunk(l, v.i_gate[1]);
-        } else {  // time MoE -> residual -> space MoE (models2.py:793-800)
-            if (moe_ffn(e, w, l, 0, M, N, B, s, false, pair_moe)) return 1;
-            {
-                ProfScope ps(e, 2, 0, s);
-                GatedResArgs g;
-                g.x = e->x; moe_y(e, g, l); g.post_w = w.norm_time; g.gate = chunk(l, 3); g.post_mode = 1; g.gate_mode = 0;
-                g.next_w = nullptr; g.next_scale = chunk(l, 4); g.next_shift = nullptr; g.next_mode = 1; g.h = e->h;
-                g.rows = M; g.rows_per_batch = N; g.d = d; g.ld_mod = e->ld_mod; g.eps = c.norm_eps; g.eps_next = 1e-6f; g.scale_pre = 1;
-                // round 5 (option moe_route_fused): h is the space router's input and this kernel holds the row - it routes on its way out
-                // (one launch less per layer; moe_route_kernel's arithmetic, statement for statement)
-                if (lt_opt(OPT_MOE_ROUTE_FUSED)) {
-                    g.route_w = w.gate_s; g.route_E = e->E; g.route_sel = e->moe_sel; g.route_wts = e->moe_wts;
-                    if (e->moe_force_rows) {
-                        LT_REQUIRE(e->moe_force_rows == M, "forced MoE routing was given for %d rows, this call has %d", e->moe_force_rows, M);
-                        g.route_forced = e->moe_force + ((size_t)l * 2 + 1) * (size_t)e->cfg.max_batch * e->cfg.max_tokens * 2;
-                    }
-                }
-                if (launch_gated_residual_norm(g, s)) return 1;
-            }
-            if (moe_ffn(e, w, l, 1, M, N, B, s, lt_opt(OPT_MOE_ROUTE_FUSED) != 0, pair_moe)) return 1;
-            last_post_w = w.norm_space;
-            last_gate = chunk(l, 5);
-        }
-        {   // x += gate' * post(ffn) ; h = next layer's pre-norm + modulate, or the final layer's LayerNorm + modulate
-            ProfScope ps(e, 2, 0, s);
-            GatedResArgs g;
-            g.x = e->x; g.y = e->o; g.post_w = last_post_w; g.gate = last_gate;
-            if (ys_f) { g.ystat = e->ystat; g.ystat_slots = ys_f; }
-            if (e->E != 0) moe_y(e, g, e->moe_mode == 1 ? l : -1);
-            g.post_mode = post_mode; g.gate_mode = gate_mode; g.h = e->h;
-            g.rows = M; g.rows_per_batch = N; g.d = d; g.ld_mod = e->ld_mod; g.eps = c.norm_eps; g.eps_next = 1e-6f; g.scale_pre = 1;
-            if (nl < L) {
-                g.next_w = v.pre_w ? e->lw[nl].attn_norm1 : nullptr; g.next_scale = chunk(nl, v.i_scale[0]);
-                g.next_shift = chunk(nl, v.i_shift[0]); g.next_mode = 1; g.h_pair = pair;
-            } else {  // final layer: LayerNorm(no affine, 1e-6) * (1 + scale) [+ shift] (model.py:657-661 / models.py:829-832)
-                const u16* fin = e->mod + (size_t)L * cd;
-                g.next_w = nullptr; g.next_mode = 2;
-                g.next_shift = v.final_chunks == 2 ? fin : nullptr;
-                g.next_scale = v.final_chunks == 2 ? fin + d : fin;
-            }
-            if (nl < L) prefetch_rider(e, &g.pf, e->h, d, e->lw[nl].wqkv, d, e->qkv, e->qkvn, M, e->qkvn, d, 0);
-            if (launch_gated_residual_norm(g, s)) return 1;
-        }
-    }
+    for (int l = do_blocks ? first : L; l < L; l = nx(l))
+        if (int rc = run_block(e, dm, bp, l, nx(l), t_dev, a, s)) return rc;
     if (kind == LT_KIND_CACHE_BLOCKS) {  // step caching, second cut: r = bfr(x_L - x_0) for the evaluations that leave the stack out
         ProfScope ps(e, 2, 0, s);
         if (launch_cache_residual_store(e->x, e->c_x0, e->c_r, (long long)M * d, s)) return 1;
     } else if (kind == LT_KIND_CACHE_APPLY) {  // ... and such an evaluation: x = bfr(x_0 + r), then what the last block's closing kernel does to x_L
         ProfScope ps(e, 2, 0, s);
-        const u16* fin = e->mod + (size_t)L * cd;
-        if (launch_cache_residual_apply(e->x, e->c_r, v.final_chunks == 2 ? fin + d : fin, v.final_chunks == 2 ? fin : nullptr, e->ld_mod, e->h, M, N, d, s))
-            return 1;
+        if (launch_cache_residual_apply(e->x, e->c_r, final_scale(e), final_shift(e), e->ld_mod, e->h, M, N, d, s)) return 1;
     }
     if (gemm(e, e->h, d, e->final_w, d, e->frows, e->nfinal, M, e->nfinal, d, e->final_b, 0, s)) return 1;
-    {
-        ProfScope ps(e, 2, 0, s);
-        const int cfg_ch = a->cfg_channels > 0 ? a->cfg_channels : 3;
-        if (!pk) {
-            if (close_forward(e, out, a, use_cfg, B, Wrow, kind, s)) return 1;
-        } else if (pk->tab) {
-            if (launch_unpatchify_packed(e->frows, e->nfinal, pk->out_flat, a->io_dtype, pk->tab, B, c.in_channels, c.out_channels, p, N, use_cfg,
-                                         a->cfg_scale, cfg_ch, s)) return 1;
-        } else {
-            for (int b = 0; b < B; ++b)  // x[i][:L] -> [C, H_b, W_b], sigma half dropped (model.py:757-768, :859-864)
-                if (launch_unpatchify_cfg(e->frows + (size_t)b * N * e->nfinal, e->nfinal, pk->out_ptrs[b], a->io_dtype, 1, c.in_channels,
-                                          c.out_channels, pk->hw[2 * b], pk->hw[2 * b + 1], p, 0, 1.0f, cfg_ch, 0, s)) return 1;
-        }
-    }
+    ProfScope ps(e, 2, 0, s);  // the closing step, in the input's form
+    if (!pk) return close_forward(e, out, a, use_cfg, B, dm.Wrow, kind, s) ? 1 : 0;
+    if (pk->tab)
+        return launch_unpatchify_packed(e->frows, e->nfinal, pk->out_flat, a->io_dtype, pk->tab, B, c.in_channels, c.out_channels, c.patch_size, N, use_cfg,
+                                        a->cfg_scale, cfg_channels(a), s) ? 1 : 0;
+    for (int b = 0; b < B; ++b)  // x[i][:L] -> [C, H_b, W_b], sigma half dropped (model.py:757-768, :859-864)
+        if (launch_unpatchify_cfg(e->frows + (size_t)b * N * e->nfinal, e->nfinal, pk->out_ptrs[b], a->io_dtype, 1, c.in_channels,
+                                  c.out_channels, pk->hw[2 * b], pk->hw[2 * b + 1], c.patch_size, 0, 1.0f, cfg_channels(a), 0, s)) return 1;
     return 0;
 }
 
