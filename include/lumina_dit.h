@@ -535,6 +535,31 @@ int lt_forward_cached(lt_engine* e, const void* x_dev, const float* t_dev, void*
 /* the evaluations of the last lt_sample_ode_cached call that reused the residual */
 int64_t lt_last_cache_hits(lt_engine* e);
 
+/* Perturbed-attention guidance (transport/guidance.py: sample_cfg_pag is the definition).  An evaluation can run a set P of
+ * blocks PERTURBED: their self-attention map is replaced by the identity, so every query's output is its own value row,
+ *   attn[b, n, h, :] = V[b, n, h / (H / Hkv), :]      V: the bf16 V projection of that layer (no norm, no RoPE), copied word for word;
+ * the text families (Next-DiT T2I, Flag-DiT) keep their zero-init gated text cross-attention on top - the stand-alone text launch: q_norm + RoPE
+ * queries, the key bias, tanh(gate), accumulated onto those rows with that route's rounding points.  The self keys are not used; everything
+ * behind (O projection, both gated-residual-norm steps, feed-forward / MoE) is the block as it is.  perturb_host: n_perturb layer indices on
+ * the host, in any order; P may hold every layer.  skip_host / n_skip: the set S of lt_forward_skip; S and P are disjoint, either may be empty.
+ * The sets belong to the call: no entry point returns with one left behind, error returns included.
+ * lt_forward_perturb: lt_forward with the blocks of S left out and the blocks of P perturbed; both empty IS lt_forward.  With a set the call
+ * is refused on a stream under capture.
+ * lt_forward_cfg_pag: lt_forward_cfg_slg with the third prediction taken under (S, P): R(R(u + R(w R(c - u))) + R(s R(c - p))), at w == 1
+ * R(c + R(s R(c - p))); pag_scale == 0: lt_forward_cfg at cfg_scale.
+ * lt_sample_ode_cfg_pag: lt_sample_ode_cfg_slg's arguments, behaviour, counters and graph keys with both sets; ONE scale table (pag_host).
+ * The perturb set's words join the HIP-graph key behind a mark of their own (-2; the skip set's: -1): skip {1} and perturb {1} are two keys.
+ * Refused by name with nothing written: everything the skip-layer entries refuse; for P an index outside 0 .. n_layers - 1, a repeated index,
+ * more indices than layers; an index in both sets; both sets empty at a non-zero scale (lt_forward_cfg_pag / lt_sample_ode_cfg_pag); a
+ * regional prompt; a stream under capture when a set is given.  Packed batches (size lists) have no entry point that takes a set. */
+int lt_forward_perturb(lt_engine* e, const void* x_dev, const float* t_dev, void* out_dev, const lt_step_args* a, const int32_t* skip_host,
+                       int32_t n_skip, const int32_t* perturb_host, int32_t n_perturb, void* stream);
+int lt_forward_cfg_pag(lt_engine* e, const void* x_dev, const float* t_dev, void* out_dev, float cfg_scale, float pag_scale,
+                       const int32_t* skip_host, int32_t n_skip, const int32_t* perturb_host, int32_t n_perturb, const lt_step_args* a, void* stream);
+int lt_sample_ode_cfg_pag(lt_engine* e, const void* z_dev, void* traj_dev, void* final_dev, const float* tgrid_host, int32_t n_grid, int32_t method,
+                          const float* cfg_host, const float* pag_host, const int32_t* skip_host, int32_t n_skip, const int32_t* perturb_host,
+                          int32_t n_perturb, int32_t t_round_to_state_dtype, const lt_step_args* a, void* stream);
+
 /* number of model evaluations issued by the last lt_sample_ode /lt_sample_ode_packed / lt_sample_views / lt_sample_views_guided / lt_sample_sde / lt_sample_ode_adaptive call */
 int64_t lt_last_nfe(lt_engine* e);
 /* the rows those evaluations ran, summed: nfe * batch for every sampler but lt_sample_ode_cfg_schedule, whose conditional-only stages run half */

@@ -244,6 +244,14 @@ int lt_op_unpatchify_cfg_reuse(const void* rows, int32_t ld, void* out, int32_t 
 int lt_op_unpatchify_cfg_slg(const void* rows, int32_t ld, void* out, int32_t out_dtype, int32_t B, int32_t C, int32_t out_ch, int32_t H, int32_t W,
                              int32_t patch, const float* cfg_scale_dev, const float* slg_scale_dev, int32_t cfg_channels, int32_t wp_stride,
                              void* skip_dev, int32_t mode, void* stream);
+/* Perturbed attention (csrc/attention_identity.hip), for tests/test_gpu_pag.py: self-attention with the attention map replaced
+ * by the identity.  src: the row-major QKV projection, [B * N][ld_src] bf16, its V columns at col0 .. col0 + Hkv * hd; out: [B * N][H * hd] bf16,
+ *   out[b, n, h, :] = V[b, n, h / (H / Hkv), :]
+ * copied word for word (no rounding), row-major or - out_pair 1 - in the row-pair-interleaved layout (lt_op_pair_layout).  16-byte accesses.
+ * Refused by name: a null pointer, H % Hkv != 0, a head_dim other than 48 / 72 / 96 / 128, col0 or ld_src no multiple of 8, V columns that
+ * leave the row, a pointer not aligned to 16 bytes, out_pair with an odd B * N or H * hd % 32 != 0. */
+int lt_op_attention_identity(const void* src, int32_t ld_src, int32_t col0, void* out, int32_t B, int32_t N, int32_t H, int32_t Hkv, int32_t hd,
+                             int32_t out_pair, void* stream);
 /* Step caching (csrc/step_cache.hip), for tests/test_gpu_teacache.py.  n: bf16 words, a positive multiple of 8; fixed launch
  * geometry, so the sums are a function of the operands alone.
  *   lt_op_cache_indicator: sums_dev[0] = sum |h - h_prev|, sums_dev[1] = sum |h_prev|, every difference and sum in float64; then h_prev <- h.

@@ -145,6 +145,10 @@ _SIGNATURES: Dict[str, tuple] = {
     "lt_op_cache_indicator": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp]),
     "lt_op_cache_residual_store": (_i32, [_vp, _vp, _vp, _i64, _vp]),
     "lt_op_cache_residual_apply": (_i32, [_vp, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _vp]),
+    "lt_forward_perturb": (_i32, [_vp, _vp, _vp, _vp, C.POINTER(LtStepArgs), C.POINTER(_i32), _i32, C.POINTER(_i32), _i32, _vp]),
+    "lt_forward_cfg_pag": (_i32, [_vp, _vp, _vp, _vp, _f32, _f32, C.POINTER(_i32), _i32, C.POINTER(_i32), _i32, C.POINTER(LtStepArgs), _vp]),
+    "lt_sample_ode_cfg_pag": (_i32, [_vp, _vp, _vp, _vp, C.POINTER(_f32), _i32, _i32, C.POINTER(_f32), C.POINTER(_f32), C.POINTER(_i32), _i32,
+                                     C.POINTER(_i32), _i32, _i32, C.POINTER(LtStepArgs), _vp]),
     "lt_last_nfe": (_i64, [_vp]),
     "lt_last_eval_rows": (_i64, [_vp]),
     "lt_graph_replays": (_i64, [_vp]),
@@ -176,6 +180,7 @@ _SIGNATURES: Dict[str, tuple] = {
     "lt_op_prep_mod": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, C.c_uint32, C.c_uint32, _i32, _vp]),
     "lt_op_qk_norm_rope": (_i32, [_vp, _i32, _i32, _vp, _vp, _f32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _f32, _vp]),
     "lt_op_v_transpose": (_i32, [_vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "lt_op_attention_identity": (_i32, [_vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "lt_op_attention": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _vp]),
     "lt_op_qkv_attention_small": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _f32, _vp, _vp, _vp]),
     "lt_op_attention_describe": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, C.c_char_p, _i32]),

@@ -232,6 +232,9 @@ struct lt_engine {
     // the layers THIS call's evaluation leaves out (ascending, distinct, inside 0 .. L-1, not all of them): an argument of the call that
     // travels here to run_forward.  Only SkipScope writes it, and its destructor empties it on every exit path
     std::vector<int32_t> skip;
+    // perturbed-attention guidance: the layers THIS call's evaluation runs with the identity in place of their self-attention map
+    // (ascending, distinct, inside 0 .. L-1, disjoint from `skip`; may hold every layer).  Kept like `skip`: SkipScope writes and empties it
+    std::vector<int32_t> perturb;
     // step caching: the modulated input of the first block of the previous evaluation, the token stream before block 0 and the
     // residual r = bfr(x_L - x_0) of the last evaluation that ran the stack - max_batch * max_tokens x d bf16 each; behind them the indicator's
     // partial sums and its two float64 result words, and the page-locked pair the host reads them from.  Allocated by the first call that needs
@@ -281,17 +284,20 @@ int ensure_step_cache(lt_engine* e);
 int ensure_delta(lt_engine* e);
 // ... and the skip buffer of skip-layer guidance (engine.hip)
 int ensure_skip_buf(lt_engine* e);
-// The layer set of one call.  set() refuses by name - an index outside 0 .. L-1, a repeated index, more indices than L, a set that
-// leaves no layer - and otherwise stores the set in ascending order; the destructor empties it, so no entry point returns with a set left behind
+// The layer sets of one call: the blocks left out and the blocks whose self-attention is perturbed.  set() refuses by
+// name - an index outside 0 .. L-1, a repeated index, more indices than L, a skip set that leaves no layer, an index in both sets - and
+// otherwise stores each set in ascending order; the destructor empties both, so no entry point returns with a set left behind
 struct SkipScope {
     lt_engine* e;
     explicit SkipScope(lt_engine* eng) : e(eng) {}
     SkipScope(const SkipScope&) = delete;
     SkipScope& operator=(const SkipScope&) = delete;
-    ~SkipScope() { e->skip.clear(); }
-    int set(const char* who, const int32_t* skip_host, int n_skip);
+    ~SkipScope() { e->skip.clear(); e->perturb.clear(); }
+    int set(const char* who, const int32_t* skip_host, int n_skip, const int32_t* perturb_host = nullptr, int n_perturb = 0);
 };
-// the refusals of SkipScope::set alone (nothing stored)
+// the refusals of SkipScope::set alone (nothing stored): both sets, and that they are disjoint
+int check_layer_sets(const lt_engine* e, const char* who, const int32_t* skip_host, int n_skip, const int32_t* perturb_host, int n_perturb);
+// ... of a call that takes a skip set only
 int check_skip_set(const lt_engine* e, const char* who, const int32_t* skip_host, int n_skip);
 // true while stream s records into a graph (the caller's torch.cuda.graph / hipStreamBeginCapture, or the engine's own cache)
 bool stream_capturing(hipStream_t s);

@@ -106,14 +106,14 @@ void prefetch_rider(lt_engine* e, PrefetchRider* r, const u16* A, int lda, const
 }
 
 // one GEMM launch in the profile's class 0; the dispatch packet carries the event pair itself
-int profiled_gemm(lt_engine* e, const GemmArgs& g, int epi, double flops, hipStream_t s) {
+int profiled_gemm(lt_engine* e, const GemmArgs& g, int epi, double flops, hipStream_t s, int variant = 0) {
     ProfScope ps(e, 0, flops, s, true);
-    return launch_gemm_bf16(g, epi, 0, s, ps.ev0(), ps.ev1());
+    return launch_gemm_bf16(g, epi, variant, s, ps.ev0(), ps.ev1());
 }
 
 // ystat_slots (optional, out): > 0 when the launch left the rows' sum-of-squares partials in e->ystat (option grn_ystat; GemmArgs::ystat)
 int gemm(lt_engine* e, const u16* A, int lda, const u16* W, int ldw, u16* C, int ldc, int M, int N, int K,
-         const u16* bias, int epi, hipStream_t s, int* ystat_slots = nullptr, int pair_ab = 0, int pair_c = 0) {
+         const u16* bias, int epi, hipStream_t s, int* ystat_slots = nullptr, int pair_ab = 0, int pair_c = 0, int variant = 0) {
     GemmArgs g;
     g.A = A; g.W = W; g.C = C; g.bias = bias; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldw = ldw; g.ldc = ldc;
     g.bias_dtype = bias ? 1 : -1;
@@ -125,7 +125,7 @@ int gemm(lt_engine* e, const u16* A, int lda, const u16* W, int ldw, u16* C, int
         if (ys > 0 && ys <= e->ystat_cap) { g.ystat = e->ystat; g.ystat_slots = ys; *ystat_slots = ys; }
     }
     if (lt_opt(OPT_GEMM_PREFETCH) == 1 && M <= 1024 && launch_gemm_prefetch_w(g, epi, s)) return 1;
-    return profiled_gemm(e, g, epi, 2.0 * M * (double)N * K, s);
+    return profiled_gemm(e, g, epi, 2.0 * M * (double)N * K, s, variant);
 }
 
 int attention(lt_engine* e, const AttnArgs& a, hipStream_t s) {
@@ -494,6 +494,9 @@ int forward_dims(lt_engine* e, const lt_step_args* a, int use_cfg, hipStream_t s
     LT_REQUIRE(e->reg_Y == 0 || (B == 2 && !pk), "regional captions: one image per call (batch 2 = cond + uncond row), tensor input");
     LT_REQUIRE(e->skip.empty() || (!pk && (int)e->skip.size() < e->L), "layer skip: a tensor input and a set that leaves a layer (SkipScope::set)");
     LT_REQUIRE(e->skip.empty() || kt.skip_ok, "layer skip: a layer-skip set is not served by an evaluation of kind %d", (int)kind);
+    LT_REQUIRE(e->perturb.empty() || !pk, "perturbed attention: a packed batch is not served (tensor input only)");
+    LT_REQUIRE(e->perturb.empty() || kt.skip_ok, "perturbed attention: a perturb set is not served by an evaluation of kind %d", (int)kind);
+    LT_REQUIRE(e->perturb.empty() || e->reg_Y == 0, "perturbed attention: a regional prompt is prepared (lt_prepare_prompt_regional), which is not served");
     if (lt_slg_kernel_mode(kind) >= 0) LT_REQUIRE(e->g_skip, "skip-layer guidance: the buffer is not allocated (ensure_skip_buf)");
     if (kind == LT_KIND_REUSE_STORE || kind == LT_KIND_REUSE_AGAIN) LT_REQUIRE(e->g_delta, "guidance reuse: the buffer is not allocated (ensure_delta)");
     e->cache_head[0] = 0;  // (this evaluation rewrites e->x / e->h / e->mod, or uses them up; forward_graphed sets it behind a head)
@@ -676,6 +679,64 @@ int plan_block(const lt_engine* e, const Dims& dm, bool packed, BlockPlan& p) {
     return 0;
 }
 
+// Perturbed attention: the deviations of a layer whose self-attention map is the identity, decided once next to the block's plan.
+// Such a layer never takes a V^T-epilogue route (QKV_FUSED / QKV_QK_AND_VT leave V as the transposed image only): it projects plainly -
+//   no text:  V alone (the dkv rows of wqkv from row d + dkv on) -> e->qkv as [M][dkv]; the identity launch -> e->attn
+//   text:     Q | K | V in one plain launch (K is computed and not read: Q's and V's rows of wqkv are not adjacent, and one launch over the
+//             contiguous matrix costs less than two), q_norm + RoPE on Q, the identity launch, then the stand-alone text launch in accumulate mode
+// Where the block's plan is QKV_FUSED the projection runs on the persistent kernel (variant 15) in BOTH operand layouts, so the pair plan and
+// the row-major plan launch one kernel and their words agree; elsewhere the launcher chooses as always.  Under the pair plan e->h and the
+// weights are in the pair layout (pair_ab 3); without text the identity launch writes e->attn in that layout, with text the generic text
+// launch accumulates into row-major rows and the O projection reads a row-major A (pair_ab bit 1 alone) - the same products in the same order.
+struct PerturbPlan {
+    bool text = false;
+    int variant = 0, pair_ab = 0;
+    bool out_pair = false;     // e->attn leaves the identity launch in the pair layout
+    bool attn_rowmajor = false;  // the pair plan's O projection reads e->attn row-major in this layer
+};
+int plan_perturbed(const lt_engine* e, const BlockPlan& bp, PerturbPlan& pp) {
+    pp = PerturbPlan{};
+    pp.text = e->v.text;
+    LT_REQUIRE(!bp.regional, "perturbed attention: a regional prompt is not served");
+    if (bp.qkv == QKV_FUSED) {
+        LT_REQUIRE(e->d % 64 == 0 && e->d >= 192, "perturbed attention: d = %d does not fit the persistent kernel the fused plan runs on", e->d);
+        pp.variant = 15;
+    }
+    if (bp.pair) {
+        LT_REQUIRE(pp.variant == 15 && (e->d + e->dkv) % 2 == 0, "perturbed attention: the pair plan left the route it was chosen for");
+        pp.pair_ab = 3; pp.out_pair = !pp.text; pp.attn_rowmajor = pp.text;
+    }
+    return 0;
+}
+
+int block_attention_perturbed(lt_engine* e, const Dims& dm, const PerturbPlan& pp, LayerW& w, const float* t_dev, const lt_step_args* a, hipStream_t s) {
+    const lt_config& c = e->cfg; const VariantDesc& v = e->v;
+    const int B = dm.B, N = dm.N, M = dm.M, d = e->d, dkv = e->dkv, H = e->H, Hkv = e->Hkv, hd = e->hd;
+    if (!pp.text) {
+        if (gemm(e, e->h, d, w.wqkv + (size_t)(d + dkv) * d, d, e->qkv, dkv, M, dkv, d, nullptr, 0, s, nullptr, pp.pair_ab, 0, pp.variant)) return 1;
+        ProfScope ps(e, 2, 0, s);
+        return launch_attention_identity(e->qkv, dkv, 0, e->attn, B, N, H, Hkv, hd, pp.out_pair, s) ? 1 : 0;
+    }
+    if (gemm(e, e->h, d, w.wqkv, d, e->qkv, e->qkvn, M, e->qkvn, d, nullptr, 0, s, nullptr, pp.pair_ab, 0, pp.variant)) return 1;
+    {
+        ProfScope ps(e, 2, 0, s);
+        QkPostArgs qa;
+        qa.src = e->qkv; qa.ld_src = e->qkvn; qa.B = B; qa.N = N; qa.hd = hd; qa.rope_mode = v.rope_1d ? 2 : 1;
+        qa.cs = e->rope; qa.t = t_dev; qa.grid_w = dm.Wp; qa.cs_len = e->rope_len; qa.ln_eps = 1e-5f;
+        qa.n_tok_b = dm.ntok_dev; qa.grid_w_b = dm.gw_dev;
+        qa.watershed = c.variant == LT_VARIANT_NEXT_T2I ? a->scale_watershed : 0.f;
+        qa.col0 = 0; qa.heads = H; qa.dst = e->q; qa.ln_w = c.qk_norm ? w.q_norm_w : nullptr; qa.ln_b = c.qk_norm ? w.q_norm_b : nullptr;
+        if (launch_qk_norm_rope(qa, s)) return 1;
+        if (launch_attention_identity(e->qkv, e->qkvn, d + dkv, e->attn, B, N, H, Hkv, hd, 0, s)) return 1;
+    }
+    // the zero-init gated text cross-attention on top, as the stand-alone text launch of block_attention does it
+    AttnArgs tx;
+    tx.q = e->q; tx.k = w.ky; tx.vt = w.vty; tx.bias = e->txt_bias; tx.out = e->attn; tx.gate = w.gate; tx.accumulate = 1;
+    tx.B = B; tx.H = H; tx.Hkv = Hkv; tx.N = N; tx.Nk = e->prompt_T; tx.Nkpad = e->prompt_Tpad; tx.hd = hd; tx.k_prescaled = 1;
+    tx.scale = (float)(1.0 / std::sqrt((double)hd)); tx.nk_batch = nullptr;
+    return attention(e, tx, s) ? 1 : 0;
+}
+
 // the attention branch of a block up to e->attn: QKV projection, q / k post-processing, self-attention [+ text keys], on the plan's route
 int block_attention(lt_engine* e, const Dims& dm, const BlockPlan& bp, LayerW& w, const float* t_dev, const lt_step_args* a, hipStream_t s) {
     const lt_config& c = e->cfg; const VariantDesc& v = e->v;
@@ -751,14 +812,16 @@ int block_attention(lt_engine* e, const Dims& dm, const BlockPlan& bp, LayerW& w
 }
 
 // block l on the plan's route; h leaves prepared for layer nl, the next one that runs (L: none does - the final layer's form)
-int run_block(lt_engine* e, const Dims& dm, const BlockPlan& bp, int l, int nl, const float* t_dev, const lt_step_args* a, hipStream_t s) {
+// pp: the layer is perturbed - its attention branch up to e->attn is block_attention_perturbed's; everything behind is the block as it is
+int run_block(lt_engine* e, const Dims& dm, const BlockPlan& bp, int l, int nl, const float* t_dev, const lt_step_args* a, hipStream_t s,
+              const PerturbPlan* pp = nullptr) {
     const VariantDesc& v = e->v;
     const int B = dm.B, N = dm.N, M = dm.M, d = e->d, F = e->F, pair = bp.pair;
     const int post_mode = v.post ? 1 : 0, gate_mode = 0;  // gates arrive ready (tanh applied by the conditioning where the family has it)
     LayerW& w = e->lw[l];
-    if (block_attention(e, dm, bp, w, t_dev, a, s)) return 1;
+    if (pp ? block_attention_perturbed(e, dm, *pp, w, t_dev, a, s) : block_attention(e, dm, bp, w, t_dev, a, s)) return 1;
     int ys_o = 0, ys_f = 0;
-    if (gemm(e, e->attn, d, w.wo, d, e->o, d, M, d, d, nullptr, 0, s, &ys_o, pair ? 3 : 0)) return 1;
+    if (gemm(e, e->attn, d, w.wo, d, e->o, d, M, d, d, nullptr, 0, s, &ys_o, pair ? (pp && pp->attn_rowmajor ? 2 : 3) : 0)) return 1;
     {   // x += gate' * post(attn) ; h = pre_ffn(x) * (1 + scale) [+ shift]
         ProfScope ps(e, 2, 0, s);
         GatedResArgs g = gated_res_args(e, dm);
@@ -842,6 +905,11 @@ int run_forward(lt_engine* e, const void* x_in, const float* t_dev, void* out, c
     auto skipped = [&](int l) { return std::binary_search(e->skip.begin(), e->skip.end(), l); };
     auto nx = [&](int l) { int n = l + 1; while (n < L && skipped(n)) ++n; return n; };
     const int first = nx(-1);  // (< L: the set is distinct and shorter than L, checked before the first launch)
+    // perturbed attention: the blocks in e->perturb (ascending, disjoint from e->skip) run with the identity as their attention map
+    PerturbPlan pp;
+    if (!e->perturb.empty())
+        if (int rc = plan_perturbed(e, bp, pp)) return rc;
+    auto perturbed = [&](int l) { return std::binary_search(e->perturb.begin(), e->perturb.end(), l); };
     if (do_head) {  // first pre-norm: modulate(attention_norm(x), [shift,] scale) (model.py:599 / models.py:785 / lumina_t2i model.py:600)
         ProfScope ps(e, 2, 0, s);
         NormModArgs n;
@@ -856,7 +924,7 @@ int run_forward(lt_engine* e, const void* x_in, const float* t_dev, void* out, c
         return 0;
     }
     for (int l = do_blocks ? first : L; l < L; l = nx(l))
-        if (int rc = run_block(e, dm, bp, l, nx(l), t_dev, a, s)) return rc;
+        if (int rc = run_block(e, dm, bp, l, nx(l), t_dev, a, s, perturbed(l) ? &pp : nullptr)) return rc;
     if (kind == LT_KIND_CACHE_BLOCKS) {  // step caching, second cut: r = bfr(x_L - x_0) for the evaluations that leave the stack out
         ProfScope ps(e, 2, 0, s);
         if (launch_cache_residual_store(e->x, e->c_x0, e->c_r, (long long)M * d, s)) return 1;
@@ -924,22 +992,38 @@ static int ensure_half_state(lt_engine* e, u16** buf, const char* what) {
 int ensure_delta(lt_engine* e) { return ensure_half_state(e, &e->g_delta, "guidance reuse"); }
 int ensure_skip_buf(lt_engine* e) { return ensure_half_state(e, &e->g_skip, "skip-layer guidance"); }
 
-int check_skip_set(const lt_engine* e, const char* who, const int32_t* skip_host, int n_skip) {
-    LT_REQUIRE(n_skip >= 0, "%s: n_skip %d is negative", who, n_skip);
-    LT_REQUIRE(n_skip == 0 || skip_host, "%s: null argument (skip_host: %d layer indices)", who, n_skip);
-    LT_REQUIRE(n_skip <= e->L, "%s: %d skip indices, the model has %d layers", who, n_skip, e->L);
-    for (int i = 0; i < n_skip; ++i) {
-        LT_REQUIRE(skip_host[i] >= 0 && skip_host[i] < e->L, "%s: skip index %d (entry %d) is outside 0..%d", who, skip_host[i], i, e->L - 1);
-        for (int j = 0; j < i; ++j) LT_REQUIRE(skip_host[j] != skip_host[i], "%s: skip index %d is repeated (entries %d and %d)", who, skip_host[i], j, i);
+// one layer set (what: "skip" / "perturb"): count, range, repeats
+static int check_layer_set(const lt_engine* e, const char* who, const char* what, const int32_t* host, int n) {
+    LT_REQUIRE(n >= 0, "%s: n_%s %d is negative", who, what, n);
+    LT_REQUIRE(n == 0 || host, "%s: null argument (%s_host: %d layer indices)", who, what, n);
+    LT_REQUIRE(n <= e->L, "%s: %d %s indices, the model has %d layers", who, n, what, e->L);
+    for (int i = 0; i < n; ++i) {
+        LT_REQUIRE(host[i] >= 0 && host[i] < e->L, "%s: %s index %d (entry %d) is outside 0..%d", who, what, host[i], i, e->L - 1);
+        for (int j = 0; j < i; ++j) LT_REQUIRE(host[j] != host[i], "%s: %s index %d is repeated (entries %d and %d)", who, what, host[i], j, i);
     }
-    LT_REQUIRE(n_skip < e->L, "%s: the skip set leaves no layer (all %d are in it)", who, e->L);
     return 0;
 }
 
-int SkipScope::set(const char* who, const int32_t* skip_host, int n_skip) {
-    if (check_skip_set(e, who, skip_host, n_skip)) return 2;
+int check_layer_sets(const lt_engine* e, const char* who, const int32_t* skip_host, int n_skip, const int32_t* perturb_host, int n_perturb) {
+    if (check_layer_set(e, who, "skip", skip_host, n_skip)) return 2;
+    LT_REQUIRE(n_skip < e->L, "%s: the skip set leaves no layer (all %d are in it)", who, e->L);
+    if (check_layer_set(e, who, "perturb", perturb_host, n_perturb)) return 2;  // (may hold every layer)
+    for (int i = 0; i < n_perturb; ++i)
+        for (int j = 0; j < n_skip; ++j)
+            LT_REQUIRE(perturb_host[i] != skip_host[j], "%s: layer %d is in the skip set and in the perturb set (the sets are disjoint)", who, perturb_host[i]);
+    return 0;
+}
+
+int check_skip_set(const lt_engine* e, const char* who, const int32_t* skip_host, int n_skip) {
+    return check_layer_sets(e, who, skip_host, n_skip, nullptr, 0);
+}
+
+int SkipScope::set(const char* who, const int32_t* skip_host, int n_skip, const int32_t* perturb_host, int n_perturb) {
+    if (check_layer_sets(e, who, skip_host, n_skip, perturb_host, n_perturb)) return 2;
     e->skip.assign(skip_host, skip_host + n_skip);
     std::sort(e->skip.begin(), e->skip.end());
+    e->perturb.assign(perturb_host, perturb_host + n_perturb);
+    std::sort(e->perturb.begin(), e->perturb.end());
     return 0;
 }
 
@@ -1031,6 +1115,11 @@ static int forward_graphed_body(lt_engine* e, const void* x_in, const float* t_d
         const int32_t mark[2] = {-1, (int32_t)e->skip.size()};
         key.insert(key.end(), (const char*)mark, (const char*)(mark + 2));
         key.insert(key.end(), (const char*)e->skip.data(), (const char*)(e->skip.data() + e->skip.size()));
+    }
+    if (!e->perturb.empty()) {  // the layers perturbed, behind a mark of their own: skip {1} and perturb {1} are two keys
+        const int32_t mark[2] = {-2, (int32_t)e->perturb.size()};
+        key.insert(key.end(), (const char*)mark, (const char*)(mark + 2));
+        key.insert(key.end(), (const char*)e->perturb.data(), (const char*)(e->perturb.data() + e->perturb.size()));
     }
     lt_engine::GraphEntry* ge = nullptr;
     for (auto& g : e->graphs) if (g.key == key) { ge = &g; break; }
@@ -1518,14 +1607,26 @@ extern "C" int lt_forward(lt_engine* e, const void* x_dev, const float* t_dev, v
 
 // lt_forward with the blocks of a layer set left out.  Empty set: lt_forward, capturable as it is; with a set the call is refused
 // on a stream under capture (a recorded evaluation of this kind has no test behind it)
-extern "C" int lt_forward_skip(lt_engine* e, const void* x_dev, const float* t_dev, void* out_dev, const lt_step_args* a, const int32_t* skip_host,
-                               int32_t n_skip, void* stream) {
-    LT_REQUIRE(e && x_dev && t_dev && out_dev && a, "lt_forward_skip: null argument");
+static int forward_sets(lt_engine* e, const char* who, const void* x_dev, const float* t_dev, void* out_dev, const lt_step_args* a,
+                        const int32_t* skip_host, int32_t n_skip, const int32_t* perturb_host, int32_t n_perturb, void* stream) {
+    LT_REQUIRE(e && x_dev && t_dev && out_dev && a, "%s: null argument", who);
     SkipScope scope(e);
-    if (scope.set("lt_forward_skip", skip_host, n_skip)) return 2;
-    if (n_skip > 0 && refuse_if_capturing((hipStream_t)stream, "lt_forward_skip")) return 2;
+    if (scope.set(who, skip_host, n_skip, perturb_host, n_perturb)) return 2;
+    if ((n_skip > 0 || n_perturb > 0) && refuse_if_capturing((hipStream_t)stream, who)) return 2;
+    LT_REQUIRE(n_perturb == 0 || e->reg_Y == 0, "%s: a regional prompt is prepared (lt_prepare_prompt_regional): perturbed attention does not serve it", who);
     LtOptScope opt_scope(&e->opts);
     return forward_graphed(e, x_dev, t_dev, out_dev, a, 0, (hipStream_t)stream);
+}
+
+extern "C" int lt_forward_skip(lt_engine* e, const void* x_dev, const float* t_dev, void* out_dev, const lt_step_args* a, const int32_t* skip_host,
+                               int32_t n_skip, void* stream) {
+    return forward_sets(e, "lt_forward_skip", x_dev, t_dev, out_dev, a, skip_host, n_skip, nullptr, 0, stream);
+}
+
+// lt_forward with the blocks of S left out and the blocks of P perturbed.  Both sets empty: lt_forward, capturable as it is
+extern "C" int lt_forward_perturb(lt_engine* e, const void* x_dev, const float* t_dev, void* out_dev, const lt_step_args* a, const int32_t* skip_host,
+                                  int32_t n_skip, const int32_t* perturb_host, int32_t n_perturb, void* stream) {
+    return forward_sets(e, "lt_forward_perturb", x_dev, t_dev, out_dev, a, skip_host, n_skip, perturb_host, n_perturb, stream);
 }
 
 extern "C" int lt_forward_packed(lt_engine* e, const void* const* x_ptrs, const int32_t* hw_host, const float* t_dev,

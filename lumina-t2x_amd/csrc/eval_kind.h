@@ -9,7 +9,7 @@ enum LtEvalKind {
     LT_KIND_RULE,          // guided, times the per-sample factor of the rescale / norm-limit rule whose parameters are in e->g_cfg[1..2]
     LT_KIND_REUSE_STORE,   // guided, the cond - uncond difference of the guided channels also stored in e->g_delta
     LT_KIND_REUSE_AGAIN,   // the cond rows, guided with the stored difference, both halves written
-    LT_KIND_SLG_STORE,     // skip-layer guidance: the cond rows under the caller's SkipScope, guided channels to e->g_skip, `out` unused
+    LT_KIND_SLG_STORE,     // skip-layer / perturbed-attention guidance: the cond rows under the caller's SkipScope (blocks left out and / or perturbed), guided channels to e->g_skip, `out` unused
     LT_KIND_SLG_GUIDED,    // ... all rows, the closing kernel adds s (cond - skip) with s from e->g_cfg[3]
     LT_KIND_SLG_COND,      // ... the cond rows alone, cond + s (cond - skip), both halves written
     LT_KIND_CACHE_HEAD,    // step caching: patchify .. the first pre-norm + modulate, the indicator sums (e->c_ws), x_0 kept; `out` unused
@@ -24,13 +24,13 @@ struct LtEvalTraits {
     bool reads_x;     // reads the state x_in (and runs patchify .. the first pre-norm)
     bool writes_out;  // writes `out`
     bool rule;        // the rule's parameters e->g_cfg[1..2] are used
-    bool skip_ok;     // may run under a layer-skip set (SkipScope)
+    bool skip_ok;     // may run under a layer-skip set and / or a perturbed-attention set (SkipScope)
     bool cached;      // a part of an evaluation under step caching: hands e->x / e->h / e->mod to the next part
 };
 
 constexpr LtEvalTraits lt_eval_traits(LtEvalKind k) {
     switch (k) {  //                     dev    half   reads  writes rule   skip   cached
-    case LT_KIND_WHOLE:        return {false, false, true,  true,  false, true,  false};  // (a set: lt_forward_skip)
+    case LT_KIND_WHOLE:        return {false, false, true,  true,  false, true,  false};  // (a set: lt_forward_skip / lt_forward_perturb)
     case LT_KIND_DEV_GUIDED:   return {true,  false, true,  true,  false, false, false};
     case LT_KIND_COND_ONLY:    return {true,  true,  true,  true,  false, false, false};
     case LT_KIND_RULE:         return {true,  false, true,  true,  true,  false, false};

@@ -171,6 +171,9 @@ int launch_qk_norm_rope(const QkPostArgs& a, hipStream_t stream);
 int launch_qk_norm_rope_pair(const QkPostArgs& q, const QkPostArgs& k, hipStream_t stream);  // both in one persistent launch
 int launch_v_transpose(const u16* src, int ld_src, int col0, u16* dst, int B, int N, int Npad, int kv_heads,
                        int hd, hipStream_t stream);
+// perturbed attention (attention_identity.hip): out[b, n, h, :] = V[b, n, h / (H / Hkv), :], the V columns of the row-major QKV buffer
+// copied word for word into [B * N][H * hd], row-major or (out_pair) in the row-pair-interleaved layout the O projection reads
+int launch_attention_identity(const u16* src, int ld_src, int col0, u16* out, int B, int N, int H, int Hkv, int hd, int out_pair, hipStream_t stream);
 // the three passes above in one launch (engine path)
 struct QkvPostArgs {
     QkPostArgs q, k;

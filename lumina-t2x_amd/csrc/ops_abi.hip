@@ -385,6 +385,11 @@ extern "C" int lt_op_v_transpose(const void* src, int32_t ld_src, int32_t col0, 
     return launch_v_transpose((const u16*)src, ld_src, col0, (u16*)dst, B, N, Npad, kv_heads, hd, (hipStream_t)stream);
 }
 
+extern "C" int lt_op_attention_identity(const void* src, int32_t ld_src, int32_t col0, void* out, int32_t B, int32_t N, int32_t H, int32_t Hkv,
+                                        int32_t hd, int32_t out_pair, void* stream) {
+    return launch_attention_identity((const u16*)src, ld_src, col0, (u16*)out, B, N, H, Hkv, hd, out_pair, (hipStream_t)stream);
+}
+
 extern "C" int lt_op_attention(const void* q, const void* k, const void* vt, const float* bias, void* out, const void* gate,
                                int32_t accumulate, int32_t B, int32_t H, int32_t Hkv, int32_t N, int32_t Nk, int32_t Nkpad,
                                int32_t hd, float scale, int32_t k_prescaled, void* stream) {

@@ -65,6 +65,9 @@ struct Trajectory {
     const float *slg_host = nullptr, *slg_dev = nullptr;
     const int32_t* skip_host = nullptr;
     int n_skip = 0;
+    // ... and the layers those evaluations perturb (lt_sample_ode_cfg_pag; empty: skip-layer guidance as it was)
+    const int32_t* perturb_host = nullptr;
+    int n_perturb = 0;
     // step caching (lt_sample_ode_cached): the controller, the evaluations of the trajectory, those that reused the residual
     CacheControl* cache = nullptr;
     int ncalls = 0;
@@ -128,7 +131,7 @@ struct Trajectory {
         ++nfe;
         {
             SkipScope scope(e);
-            if (scope.set("skip-layer guidance", skip_host, n_skip)) return 2;
+            if (scope.set("skip-layer guidance", skip_host, n_skip, perturb_host, n_perturb)) return 2;
             if (int rc = eval_kind(LT_KIND_SLG_STORE, y, t, nullptr, e->g_cfg)) return rc;
         }
         LT_CHECK_HIP(hipMemcpyAsync(e->g_cfg + 3, slg_dev + call, sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -182,7 +185,8 @@ float bf16_round_host(float f) {
 struct MaskedBlend { const void *mask, *x1, *noise; };
 // host: (n_grid - 1) * stages scales; { rescale, norm limit } or null; the reuse flags of lt_sample_ode_cfg_reuse, one per scale, or null
 // ... ; skip-layer guidance (lt_sample_ode_cfg_slg): one scale s per scale w and the layer set, or null
-struct SlgCall { const float* table; const int32_t* skip; int n_skip; };
+// (lt_sample_ode_cfg_pag: the layers perturbed in the same evaluation; pag: the entry that takes both sets, either of which may be empty)
+struct SlgCall { const float* table; const int32_t* skip; int n_skip; const int32_t* perturb = nullptr; int n_perturb = 0; bool pag = false; };
 struct CfgSchedule { const float* table; const float* rule = nullptr; const int32_t* reuse = nullptr; const SlgCall* slg = nullptr; };
 
 int ode_fixed_grid(lt_engine* e, const void* z_dev, void* traj_dev, void* final_dev, const float* tgrid_host, int n_grid, int method, int use_cfg,
@@ -224,6 +228,7 @@ int ode_fixed_grid(lt_engine* e, const void* z_dev, void* traj_dev, void* final_
     if (cs && cs->slg) {
         tr.slg_host = cs->slg->table; tr.slg_dev = e->times.dev + (size_t)ncalls * B + ncalls;
         tr.skip_host = cs->slg->skip; tr.n_skip = cs->slg->n_skip;
+        tr.perturb_host = cs->slg->perturb; tr.n_perturb = cs->slg->n_perturb;
     }
     if (tr.start(z_dev, traj_dev, true)) return 1;
     const int dt_code = bf ? 1 : 0;
@@ -460,7 +465,11 @@ int sample_cfg_table(lt_engine* e, const char* who, const void* z_dev, void* tra
     if (slg) {
         for (int i = 0; i < (n_grid - 1) * stages; ++i)
             LT_REQUIRE(std::isfinite(slg->table[i]), "%s: the skip-layer scale of stage %d of interval %d is not finite", who, i % stages, i / stages);
-        if (check_skip_set(e, who, slg->skip, slg->n_skip)) return 2;
+        if (check_layer_sets(e, who, slg->skip, slg->n_skip, slg->perturb, slg->n_perturb)) return 2;
+        if (slg->pag && slg->n_skip == 0 && slg->n_perturb == 0)
+            for (int i = 0; i < (n_grid - 1) * stages; ++i)
+                LT_REQUIRE(slg->table[i] == 0.0f, "%s: both layer sets are empty, and stage %d of interval %d has a non-zero scale: the third "
+                           "prediction would be the conditional one", who, i % stages, i / stages);
         if (ensure_skip_buf(e)) return 1;
     }
     const long long n = (long long)a->batch * e->cfg.in_channels * a->latent_h * a->latent_w;
@@ -549,20 +558,32 @@ extern "C" int lt_sample_ode_cfg_slg(lt_engine* e, const void* z_dev, void* traj
                             (hipStream_t)stream, nullptr, false, &slg);
 }
 
-// One guided evaluation at (cfg_scale, slg_scale): the skip evaluation of the cond rows, then all rows (the cond rows alone at cfg_scale 1
-// exactly).  slg_scale 0: lt_forward_cfg at cfg_scale.  The scales reach the engine's fixed device words through a launch in front.
-extern "C" int lt_forward_cfg_slg(lt_engine* e, const void* x_dev, const float* t_dev, void* out_dev, float cfg_scale, float slg_scale,
-                                  const int32_t* skip_host, int32_t n_skip, const lt_step_args* a, void* stream) {
-    const char* who = "lt_forward_cfg_slg";
+// ---- perturbed-attention guidance: the third prediction runs the blocks of P with the identity as their attention map -----------
+extern "C" int lt_sample_ode_cfg_pag(lt_engine* e, const void* z_dev, void* traj_dev, void* final_dev, const float* tgrid_host, int32_t n_grid,
+                                     int32_t method, const float* cfg_host, const float* pag_host, const int32_t* skip_host, int32_t n_skip,
+                                     const int32_t* perturb_host, int32_t n_perturb, int32_t t_round, const lt_step_args* a, void* stream) {
+    const SlgCall slg{pag_host, skip_host, n_skip, perturb_host, n_perturb, true};
+    return sample_cfg_table(e, "lt_sample_ode_cfg_pag", z_dev, traj_dev, final_dev, tgrid_host, n_grid, method, cfg_host, nullptr, t_round, a,
+                            (hipStream_t)stream, nullptr, false, &slg);
+}
+
+// One guided evaluation at (cfg_scale, slg_scale): the degraded evaluation of the cond rows - the blocks of S left out, the blocks of P
+// perturbed - then all rows (the cond rows alone at cfg_scale 1 exactly).  slg_scale 0: lt_forward_cfg at cfg_scale.  The scales reach the
+// engine's fixed device words through a launch in front.  pag: lt_forward_cfg_pag (both sets, either may be empty, not both at a scale != 0)
+static int forward_cfg_sets(lt_engine* e, const char* who, bool pag, const void* x_dev, const float* t_dev, void* out_dev, float cfg_scale,
+                            float slg_scale, const int32_t* skip_host, int32_t n_skip, const int32_t* perturb_host, int32_t n_perturb,
+                            const lt_step_args* a, void* stream) {
     hipStream_t s = (hipStream_t)stream;
     LT_REQUIRE(e && x_dev && t_dev && out_dev && a, "%s: null argument", who);
     if (refuse_if_capturing(s, who)) return 2;  // (the first call allocates the skip buffer)
     LtOptScope opt_scope(&e->opts);
     if (check_step_shape(e, who, a)) return 2;
     LT_REQUIRE(std::isfinite(cfg_scale), "%s: the scale is not finite", who);
-    LT_REQUIRE(std::isfinite(slg_scale), "%s: the skip-layer scale is not finite", who);
+    LT_REQUIRE(std::isfinite(slg_scale), "%s: the %s scale is not finite", who, pag ? "perturbed-attention" : "skip-layer");
     if (check_guided_halves(e, who, a)) return 2;
-    if (check_skip_set(e, who, skip_host, n_skip)) return 2;
+    if (check_layer_sets(e, who, skip_host, n_skip, perturb_host, n_perturb)) return 2;
+    LT_REQUIRE(!pag || n_skip > 0 || n_perturb > 0 || slg_scale == 0.f, "%s: both layer sets are empty at a non-zero scale: the third prediction "
+               "would be the conditional one", who);
     lt_step_args own = *a;
     own.cfg_scale = cfg_scale;
     if (slg_scale == 0.f) return forward_graphed(e, x_dev, t_dev, out_dev, &own, 1, s);  // lt_forward_cfg's launches and result
@@ -570,10 +591,22 @@ extern "C" int lt_forward_cfg_slg(lt_engine* e, const void* x_dev, const float* 
     if (launch_slg_params_store(e->g_cfg, cfg_scale, slg_scale, s)) return 1;
     {
         SkipScope scope(e);
-        if (scope.set(who, skip_host, n_skip)) return 2;
+        if (scope.set(who, skip_host, n_skip, perturb_host, n_perturb)) return 2;
         if (int rc = forward_graphed(e, x_dev, t_dev, nullptr, &own, 1, s, {LT_KIND_SLG_STORE, nullptr, e->g_cfg})) return rc;
     }
     return forward_graphed(e, x_dev, t_dev, out_dev, &own, 1, s, {cfg_scale == 1.0f ? LT_KIND_SLG_COND : LT_KIND_SLG_GUIDED, nullptr, e->g_cfg});
+}
+
+extern "C" int lt_forward_cfg_slg(lt_engine* e, const void* x_dev, const float* t_dev, void* out_dev, float cfg_scale, float slg_scale,
+                                  const int32_t* skip_host, int32_t n_skip, const lt_step_args* a, void* stream) {
+    return forward_cfg_sets(e, "lt_forward_cfg_slg", false, x_dev, t_dev, out_dev, cfg_scale, slg_scale, skip_host, n_skip, nullptr, 0, a, stream);
+}
+
+extern "C" int lt_forward_cfg_pag(lt_engine* e, const void* x_dev, const float* t_dev, void* out_dev, float cfg_scale, float pag_scale,
+                                  const int32_t* skip_host, int32_t n_skip, const int32_t* perturb_host, int32_t n_perturb, const lt_step_args* a,
+                                  void* stream) {
+    return forward_cfg_sets(e, "lt_forward_cfg_pag", true, x_dev, t_dev, out_dev, cfg_scale, pag_scale, skip_host, n_skip, perturb_host, n_perturb, a,
+                            stream);
 }
 
 // ---- linear multistep sampling: one evaluation per interval, the earlier slopes reused (multistep.hip) -------------------------

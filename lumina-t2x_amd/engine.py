@@ -237,14 +237,24 @@ class DiTEngine:
 
     def forward(self, x: torch.Tensor, t: torch.Tensor, *, use_cfg: bool, cfg_scale: float = 1.0,
                 scale_factor: float = 1.0, scale_watershed: float = 1.0, base_seqlen: Optional[int] = None,
-                proportional_attn: bool = False, ntk_factor: float = 1.0, skip_layers=()) -> torch.Tensor:
-        """one evaluation; ``skip_layers`` (plain forward only): the blocks left out (lt_forward_skip); empty: the call it was"""
+                proportional_attn: bool = False, ntk_factor: float = 1.0, skip_layers=(), perturb_layers=()) -> torch.Tensor:
+        """one evaluation; ``skip_layers`` (plain forward only): the blocks left out (lt_forward_skip); ``perturb_layers`` (plain
+        forward only): the blocks whose self-attention map is the identity (lt_forward_perturb); both empty: the call it was"""
         _require_gpu(x, "x")
         x = x.contiguous()
         t32 = t.to(device=x.device, dtype=torch.float32).contiguous()
         out = torch.empty_like(x)
         a = self._step_args(x, cfg_scale, scale_factor, scale_watershed, base_seqlen, proportional_attn, ntk_factor=ntk_factor)
         skip = self._skip_array(skip_layers, "forward")
+        perturb = self._skip_array(perturb_layers, "forward", "perturb")
+        if len(perturb):
+            if use_cfg:
+                raise LuminaLibError("forward: perturb_layers belongs to the plain forward (guided: forward_cfg_pag)")
+            with torch.cuda.device(self.device):
+                rc = self.lib.lt_forward_perturb(self.handle, C.c_void_p(x.data_ptr()), C.c_void_p(t32.data_ptr()), C.c_void_p(out.data_ptr()),
+                                                 C.byref(a), skip, len(skip), perturb, len(perturb), C.c_void_p(_stream_ptr(self.device)))
+            _lib.check(rc, "lt_forward_perturb")
+            return out
         if len(skip):
             if use_cfg:
                 raise LuminaLibError("forward: skip_layers belongs to the plain forward (guided: forward_cfg_slg)")
@@ -520,14 +530,14 @@ class DiTEngine:
 
     # ---- skip-layer guidance: a third prediction with a set of blocks left out -------------
     @staticmethod
-    def _skip_array(skip_layers, what: str):
+    def _skip_array(skip_layers, what: str, kind: str = "skip"):
         """the layer set as a ctypes int32 array (its contents are the C entry's to check)"""
         if isinstance(skip_layers, torch.Tensor):
             skip_layers = skip_layers.reshape(-1).tolist()
         idx = list(skip_layers) if skip_layers is not None else []
         for v in idx:
             if isinstance(v, bool) or int(v) != v:
-                raise LuminaLibError(f"{what}: skip layer {v!r} is not an integer index")
+                raise LuminaLibError(f"{what}: {kind} layer {v!r} is not an integer index")
         return (C.c_int32 * len(idx))(*[int(v) for v in idx])
 
     def forward_cfg_slg(self, x: torch.Tensor, t: torch.Tensor, *, cfg_scale: float, slg_scale: float, slg_layers, scale_factor: float = 1.0,
@@ -548,18 +558,45 @@ class DiTEngine:
         _lib.check(rc, "lt_forward_cfg_slg")
         return out
 
+    # ---- perturbed-attention guidance: the third prediction runs a set of blocks with the identity as their attention map -----
+    def forward_cfg_pag(self, x: torch.Tensor, t: torch.Tensor, *, cfg_scale: float, pag_scale: float, pag_layers, skip_layers=(),
+                        scale_factor: float = 1.0, scale_watershed: float = 1.0, base_seqlen: Optional[int] = None,
+                        proportional_attn: bool = False, ntk_factor: float = 1.0) -> torch.Tensor:
+        """one guided evaluation with perturbed-attention guidance (lt_forward_cfg_pag): ``u + w (c - u) + s (c - p)`` on the guided channels,
+        ``p`` the cond rows evaluated with the blocks ``pag_layers`` perturbed (and ``skip_layers`` left out).  ``pag_scale == 0`` is
+        ``forward(use_cfg=True)``."""
+        _require_gpu(x, "x")
+        x = x.contiguous()
+        t32 = t.to(device=x.device, dtype=torch.float32).contiguous()
+        out = torch.empty_like(x)
+        a = self._step_args(x, cfg_scale, scale_factor, scale_watershed, base_seqlen, proportional_attn, ntk_factor=ntk_factor)
+        skip = self._skip_array(skip_layers, "forward_cfg_pag")
+        perturb = self._skip_array(pag_layers, "forward_cfg_pag", "perturb")
+        with torch.cuda.device(self.device):
+            rc = self.lib.lt_forward_cfg_pag(self.handle, C.c_void_p(x.data_ptr()), C.c_void_p(t32.data_ptr()), C.c_void_p(out.data_ptr()),
+                                             float(cfg_scale), float(pag_scale), skip, len(skip), perturb, len(perturb), C.byref(a),
+                                             C.c_void_p(_stream_ptr(self.device)))
+        _lib.check(rc, "lt_forward_cfg_pag")
+        return out
+
+    def sample_ode_cfg_pag(self, z: torch.Tensor, tgrid, table, pag, pag_layers, method: str, *, skip_layers=(), **kw) -> torch.Tensor:
+        """``sample_ode_cfg_slg`` with the third prediction taken with the blocks ``pag_layers`` perturbed and ``skip_layers`` left out, under
+        the one scale table ``pag`` (lt_sample_ode_cfg_pag).  ``transport.guidance.sample_cfg_pag`` is the definition."""
+        return self.sample_ode_cfg_slg(z, tgrid, table, pag, skip_layers, method, pag_layers=pag_layers, _who="sample_ode_cfg_pag", **kw)
+
     def sample_ode_cfg_slg(self, z: torch.Tensor, tgrid, table, slg, slg_layers, method: str, *, scale_factor: float = 1.0,
                            scale_watershed: float = 1.0, base_seqlen: Optional[int] = None, proportional_attn: bool = False,
                            t_round_to_state_dtype: bool = True, return_trajectory: bool = True, ntk_factor: float = 1.0,
-                           cfg_scale=None) -> torch.Tensor:
+                           cfg_scale=None, pag_layers=None, _who: str = "sample_ode_cfg_slg") -> torch.Tensor:
         """``sample_ode_cfg_schedule`` with a skip-layer scale per stage (lt_sample_ode_cfg_slg): a stage with ``slg != 0`` also evaluates the
         cond rows with the blocks ``slg_layers`` left out and pushes the guided output away from that prediction.
         ``transport.guidance.sample_cfg_slg`` is the definition, ``slg_table`` builds the scale tables."""
+        what = "skip-layer guidance" if pag_layers is None else "perturbed-attention guidance"
         if isinstance(z, (list, tuple)):
-            raise LuminaLibError("sample_ode_cfg_slg: a packed batch (a list of latents) is not served")
+            raise LuminaLibError(f"{_who}: a packed batch (a list of latents) is not served")
         _require_gpu(z, "z")
         if method not in _lib.ODE_METHODS:
-            raise LuminaLibError(f"sample_ode_cfg_slg: skip-layer guidance is built for the fixed-grid methods {sorted(_lib.ODE_METHODS)}, not "
+            raise LuminaLibError(f"{_who}: {what} is built for the fixed-grid methods {sorted(_lib.ODE_METHODS)}, not "
                                  f"'{method}'")
         z = z.contiguous()
         garr, n = _grid_array(tgrid)
@@ -572,13 +609,22 @@ class DiTEngine:
             sl = slg if isinstance(slg, torch.Tensor) else torch.tensor(list(slg), dtype=torch.float32)
             sl = sl.detach().to("cpu", torch.float32).reshape(-1).contiguous()
             if sl.numel() != count:
-                raise LuminaLibError(f"sample_ode_cfg_slg: the slg table has {sl.numel()} entries, the grid has {count} evaluations")
+                raise LuminaLibError(f"{_who}: the {'slg' if pag_layers is None else 'pag'} table has {sl.numel()} entries, the grid has {count} "
+                                     "evaluations")
             sl_ptr = C.cast(sl.data_ptr(), C.POINTER(C.c_float))
         if tab.numel() != count:
-            raise LuminaLibError(f"sample_ode_cfg_slg: the guidance table has {tab.numel()} entries, the grid has {count} evaluations")
-        skip = self._skip_array(slg_layers, "sample_ode_cfg_slg")
+            raise LuminaLibError(f"{_who}: the guidance table has {tab.numel()} entries, the grid has {count} evaluations")
+        skip = self._skip_array(slg_layers, _who)
         a = self._step_args(z, 0.0, scale_factor, scale_watershed, base_seqlen, proportional_attn, ntk_factor=ntk_factor)
         out, traj_ptr, fin_ptr = _traj_or_final(z, max(n, 1), z.shape, return_trajectory)
+        if pag_layers is not None:
+            perturb = self._skip_array(pag_layers, _who, "perturb")
+            with torch.cuda.device(self.device):
+                rc = self.lib.lt_sample_ode_cfg_pag(self.handle, C.c_void_p(z.data_ptr()), traj_ptr, fin_ptr, garr, n, _lib.ODE_METHODS[method],
+                                                    C.cast(tab.data_ptr(), C.POINTER(C.c_float)), sl_ptr, skip, len(skip), perturb, len(perturb),
+                                                    int(t_round_to_state_dtype), C.byref(a), C.c_void_p(_stream_ptr(self.device)))
+            _lib.check(rc, "lt_sample_ode_cfg_pag")
+            return out
         with torch.cuda.device(self.device):
             rc = self.lib.lt_sample_ode_cfg_slg(self.handle, C.c_void_p(z.data_ptr()), traj_ptr, fin_ptr, garr, n, _lib.ODE_METHODS[method],
                                                 C.cast(tab.data_ptr(), C.POINTER(C.c_float)), sl_ptr, skip, len(skip), int(t_round_to_state_dtype),

@@ -95,11 +95,19 @@ class EngineSamplers:
         return eng.sample_ode_masked(x, tgrid, mask, x1, noise, method, use_cfg=use_cfg, t_round_to_state_dtype=t_round, **args)
 
     def _engine_sample_ode_cfg_schedule(self, x, tgrid, method, t_round, table, kw, return_trajectory=True, rescale=0.0, norm_limit=math.inf,
-                                        reuse=None, slg=None, slg_layers=()):
+                                        reuse=None, slg=None, slg_layers=(), pag=None, pag_layers=()):
         """kwargs of forward_with_cfg -> lt_sample_ode_cfg_schedule (guidance schedules; ``cfg_scale`` in kw is ignored), or - with a
         rescale blend or a norm limit - lt_sample_ode_cfg_rule, or - with a reuse table - lt_sample_ode_cfg_reuse, or -
-        with a table of skip-layer scales - lt_sample_ode_cfg_slg"""
-        from ..transport.guidance import refuse_rule_with_reuse, refuse_with_slg, rule_is_off
+        with a table of skip-layer scales - lt_sample_ode_cfg_slg, or - with a table of perturbed-attention scales -
+        lt_sample_ode_cfg_pag (``slg_layers`` then join the same third prediction)"""
+        from ..transport.guidance import refuse_rule_with_reuse, refuse_with_pag, refuse_with_slg, rule_is_off
+        if pag is not None:
+            if not isinstance(x, torch.Tensor):
+                raise _lib.LuminaLibError("perturbed-attention guidance: a packed batch (a list of latents) is not served")
+            try:
+                refuse_with_pag(pag, method=method, rescale=rescale, norm_limit=norm_limit, reuse=reuse, slg=slg)
+            except ValueError as exc:
+                raise _lib.LuminaLibError(str(exc)) from None
         if slg is not None:
             if not isinstance(x, torch.Tensor):
                 raise _lib.LuminaLibError("skip-layer guidance: a packed batch (a list of latents) is not served")
@@ -117,6 +125,9 @@ class EngineSamplers:
         kw.setdefault("cfg_scale", 1.0)
         eng, args = self._engine_sampler_args(x, True, kw)
         args.pop("cfg_scale", None)
+        if pag is not None:
+            return eng.sample_ode_cfg_pag(x, tgrid, table, pag, pag_layers, method, skip_layers=slg_layers, t_round_to_state_dtype=t_round,
+                                          return_trajectory=return_trajectory, **args)
         if slg is not None:
             return eng.sample_ode_cfg_slg(x, tgrid, table, slg, slg_layers, method, t_round_to_state_dtype=t_round,
                                           return_trajectory=return_trajectory, **args)
@@ -137,7 +148,7 @@ class EngineSamplers:
 
     @torch.no_grad()
     def sample_ode_cfg_schedule(self, z, tgrid, table, *cond, method: str = "midpoint", return_trajectory: bool = False, rescale: float = 0.0,
-                                norm_limit: float = math.inf, reuse=None, slg=None, slg_layers=(), **step_kw):
+                                norm_limit: float = math.inf, reuse=None, slg=None, slg_layers=(), pag=None, pag_layers=(), **step_kw):
         """A guided fixed-grid trajectory with a scale per stage in ONE engine call (lt_sample_ode_cfg_schedule): stage k of interval
         i evaluates ``forward_with_cfg`` at ``table[i * stages + k]``, or - at scale 1 exactly - the plain forward of the cond rows alone, at
         half the rows.  ``cond``: the family's conditioning as ``forward_with_cfg`` takes it (``cap_feats, cap_mask`` or ``y``) for all
@@ -150,13 +161,17 @@ class EngineSamplers:
         DESIGN 7k; refused together with a rule); ``None``: the call made without it.  ``slg`` (one skip-layer scale per table entry;
         ``transport.guidance.slg_table``) with ``slg_layers``: stages with ``slg != 0`` also evaluate the cond rows with those blocks left out
         and add ``slg * (cond - skip)`` (lt_sample_ode_cfg_slg; euler / midpoint / rk4; refused together with a rule or ``reuse``).
+        ``pag`` (one perturbed-attention scale per table entry; ``transport.guidance.pag_table``) with ``pag_layers``: the third prediction
+        runs those blocks with the identity as their self-attention map - and ``slg_layers``, if given, left out - under the one table
+        (lt_sample_ode_cfg_pag; an ``slg`` table beside a ``pag`` table is refused by name).
         Returns the last state, or all ``len(tgrid)`` states."""
         if len(cond) > len(self._cond_names):
             raise TypeError(f"sample_ode_cfg_schedule takes the conditioning {self._cond_names}, got {len(cond)} positional arguments")
         kw = dict(zip(self._cond_names, cond), **step_kw)
         self._mirror_attention_flags(kw)
         return self._engine_sample_ode_cfg_schedule(z, tgrid, method, True, table, kw, return_trajectory=return_trajectory, rescale=rescale,
-                                                    norm_limit=norm_limit, reuse=reuse, slg=slg, slg_layers=slg_layers)
+                                                    norm_limit=norm_limit, reuse=reuse, slg=slg, slg_layers=slg_layers, pag=pag,
+                                                    pag_layers=pag_layers)
 
     @torch.no_grad()
     def sample_ode_teacache(self, z, tgrid, *cond, method: str = "euler", threshold: float = 0.0, coefficients=(0.0, 0.0, 0.0, 1.0, 0.0),
@@ -320,6 +335,24 @@ class EngineSamplers:
         self._mirror_attention_flags(kw)
         eng, args = self._engine_sampler_args(x, True, kw)
         return eng.forward_cfg_slg(x, t, slg_scale=slg_scale, slg_layers=slg_layers, **args)
+
+    @torch.no_grad()
+    def forward_with_cfg_pag(self, x, t, *cond, pag_scale: float = 0.0, pag_layers=(), skip_layers=(), **step_kw):
+        """``forward_with_cfg(x, t, <conditioning>, cfg_scale, **step_kw)`` with perturbed-attention guidance in ONE engine call
+        (lt_forward_cfg_pag): the cond rows are also evaluated with the blocks ``pag_layers`` perturbed - their self-attention map
+        replaced by the identity - and the blocks ``skip_layers`` left out (``p``), and the guided channels become
+        ``u + cfg_scale (c - u) + pag_scale (c - p)``.  ``pag_scale == 0`` is ``forward_with_cfg``.  Tensor states only."""
+        if not isinstance(x, torch.Tensor):
+            raise _lib.LuminaLibError("forward_with_cfg_pag: a packed batch (a list of latents) is not served by perturbed-attention guidance")
+        names = self._cond_names + ("cfg_scale",)
+        if len(cond) > len(names):
+            raise TypeError(f"forward_with_cfg_pag takes {names}, got {len(cond)} positional arguments")
+        kw = dict(zip(names, cond), **step_kw)
+        if "cfg_scale" not in kw:
+            raise TypeError("forward_with_cfg_pag needs cfg_scale")
+        self._mirror_attention_flags(kw)
+        eng, args = self._engine_sampler_args(x, True, kw)
+        return eng.forward_cfg_pag(x, t, pag_scale=pag_scale, pag_layers=pag_layers, skip_layers=skip_layers, **args)
 
     def _engine_sample_ode_adaptive(self, x, tgrid, method, use_cfg, t_round, kw, *, rtol, atol, first_step=None, max_steps=2 ** 31 - 1):
         """kwargs of forward_with_cfg / forward -> lt_sample_ode_adaptive; returns (states [len(tgrid), *x.shape], stats dict)"""

@@ -193,16 +193,20 @@ class NextDiT(EngineSamplers, WeightWatch, nn.Module):
                 raise TypeError("forward_with_cfg takes a [B, C, H, W] tensor (reference model.py:901-902)")
             if len(kw.pop("skip_layers", ())):
                 raise _lib.LuminaLibError("forward: skip_layers on a packed batch (a list of latents) is not served")
+            if len(kw.pop("perturb_layers", ())):
+                raise _lib.LuminaLibError("forward: perturb_layers on a packed batch (a list of latents) is not served")
             return eng.forward_packed(list(x), t, **kw)
         return eng.forward(x, t, use_cfg=use_cfg, **kw)
 
     # ---- reference call surface ---------------------------------------------------------------------------
     @torch.no_grad()
-    def forward(self, x, t, cap_feats, cap_mask, skip_layers=()):
+    def forward(self, x, t, cap_feats, cap_mask, skip_layers=(), perturb_layers=()):
         """reference model.py:836-864; ``x`` is a [B, C, H, W] tensor or a list of [C, H_b, W_b] tensors of different sizes
         (returns a list then).  ``skip_layers`` (not in the reference; tensor input): the blocks left out of this evaluation, which are then
-        the identity on the residual stream (lt_forward_skip); empty: the call it was"""
-        return self._call(x, t, cap_feats, cap_mask, False, skip_layers=tuple(skip_layers), **self._plain_forward_args())
+        the identity on the residual stream (lt_forward_skip); ``perturb_layers`` (likewise): the blocks whose self-attention map is
+        replaced by the identity, the text cross-attention kept (lt_forward_perturb); both empty: the call it was"""
+        return self._call(x, t, cap_feats, cap_mask, False, skip_layers=tuple(skip_layers), perturb_layers=tuple(perturb_layers),
+                          **self._plain_forward_args())
 
     def _plain_forward_args(self) -> dict:
         """what the reference's plain ``forward`` reads off the module (model.py:836-864): the attention flags left on the

@@ -173,9 +173,18 @@ def run(args, *, encode_fn=None, cap_feat_dim=None, decode_fn=None, model=None) 
         table = guidance_table(args, sample_fn.__self__.t)
         rule = guidance_rule(args)
         reuse = guidance_reuse(args, sample_fn.__self__.t, table)
-        slg = guidance_slg(args, sample_fn.__self__.t)
+        pag = guidance_pag(args, sample_fn.__self__.t)
+        slg = None if pag is not None else guidance_slg(args, sample_fn.__self__.t)
         tea = step_cache(args)
-        if tea:  # evaluations whose first-block input barely moved leave the block stack out (the TeaCache rule)
+        if pag is not None:  # a third evaluation of the prompt row with some blocks' self-attention map replaced by the identity
+            if tea:
+                raise SystemExit("--pag_layers is not served together with --teacache")
+            if table is None:
+                from .transport import guidance
+                table = guidance.cfg_table(sample_fn.__self__.t, args.sampling_method, args.cfg_scale)
+            latent = sample_fn(z, model.forward_with_cfg, cfg_table=table, pag_table=pag, pag_layers=list(args.pag_layers),
+                               slg_layers=list(getattr(args, "slg_layers", None) or []), **kw)[-1][:1]
+        elif tea:  # evaluations whose first-block input barely moved leave the block stack out (the TeaCache rule)
             latent = sample_fn(z, model.forward_with_cfg, **tea, **kw)[-1][:1]
         elif slg is not None:  # stages that also evaluate the prompt row with some blocks left out and push away from it
             if table is None:
@@ -271,6 +280,36 @@ def guidance_slg(args, tgrid):
         raise SystemExit(f"--slg_*: {exc}") from None
 
 
+def guidance_pag(args, tgrid):
+    """``--pag_layers`` / ``--pag_scale`` / ``--pag_interval`` as the table of ``transport.guidance.pag_table``; None at the defaults (no layers,
+    or scale 0): the call it was.  ``--slg_layers`` beside it joins the same third evaluation (those blocks are left out) under this one table;
+    a second table (``--slg_scale`` / ``--slg_interval``) is refused by name, as are ``--cfg_rescale`` / ``--cfg_norm_limit``, ``--cfg_reuse*``
+    and a sampling method that is not euler / midpoint / rk4."""
+    layers, scale = list(getattr(args, "pag_layers", None) or []), float(getattr(args, "pag_scale", 0.0) or 0.0)
+    interval = getattr(args, "pag_interval", None)
+    if not layers and scale == 0.0 and interval is None:
+        return None
+    if not layers:
+        raise SystemExit("--pag_scale / --pag_interval need --pag_layers: the blocks the third evaluation perturbs")
+    if float(getattr(args, "slg_scale", 0.0) or 0.0) != 0.0 or getattr(args, "slg_interval", None) is not None:
+        raise SystemExit("--pag_layers together with --slg_scale / --slg_interval is not served: one third evaluation, one scale table "
+                         "(--slg_layers beside --pag_layers joins it under --pag_scale)")
+    if guidance_rule(args):
+        raise SystemExit("--pag_layers is not served together with --cfg_rescale / --cfg_norm_limit")
+    if int(getattr(args, "cfg_reuse", 0) or 0) != 0 or bool(getattr(args, "cfg_reuse_per_step", False)):
+        raise SystemExit("--pag_layers is not served together with --cfg_reuse / --cfg_reuse_per_step")
+    from .transport import guidance
+    if args.sampling_method not in guidance.FIXED_GRID_METHODS:
+        raise SystemExit(f"--pag_layers is built for the sampling methods {', '.join(guidance.FIXED_GRID_METHODS)}, not '{args.sampling_method}'")
+    try:
+        guidance.check_pag_layers(layers, list(getattr(args, "slg_layers", None) or []))
+        if scale == 0.0:
+            return None
+        return guidance.pag_table(tgrid, args.sampling_method, scale, interval=interval)
+    except ValueError as exc:
+        raise SystemExit(f"--pag_*: {exc}") from None
+
+
 def step_cache(args) -> dict:
     """``--teacache THR`` / ``--teacache_coefficients`` as the sampler's keyword arguments; empty when off: the call it was.  Refused by name
     together with the guidance options, the multistep and adaptive solvers (combining them is later work)."""
@@ -318,6 +357,13 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--slg_scale", type=float, default=0.0, metavar="S",
                    help="... whose prediction the guided output is pushed away from: + S * (prompt row - skip row) (0: off)")
     p.add_argument("--slg_interval", type=float, nargs=2, default=None, metavar=("LO", "HI"),
+                   help="... on the stages with LO <= t < HI only (t = 0 noise, 1 data; default: all stages)")
+    p.add_argument("--pag_layers", type=int, nargs="+", default=None, metavar="L",
+                   help="perturbed-attention guidance: the blocks a third evaluation of the prompt row runs with the identity as their "
+                        "self-attention map (default: off; --slg_layers beside it: blocks the same evaluation leaves out)")
+    p.add_argument("--pag_scale", type=float, default=0.0, metavar="S",
+                   help="... whose prediction the guided output is pushed away from: + S * (prompt row - perturbed row) (0: off)")
+    p.add_argument("--pag_interval", type=float, nargs=2, default=None, metavar=("LO", "HI"),
                    help="... on the stages with LO <= t < HI only (t = 0 noise, 1 data; default: all stages)")
     p.add_argument("--teacache", type=float, default=None, metavar="THR",
                    help="step caching (the TeaCache rule): leave the block stack out of an evaluation while the accumulated relative change of its "

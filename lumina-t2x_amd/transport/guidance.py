@@ -31,7 +31,11 @@ which evaluate the cond rows alone: ``sample_cfg_reuse`` / ``sample_cfg_reuse_mu
 ``lt_sample_ode_multistep_cfg_reuse`` are held to, ``cfg_reuse_table`` builds the flag tables and ``check_reuse`` refuses what the engine refuses.
 
 Skip-layer guidance adds ``s (cond - skip)``, ``skip`` the cond rows evaluated with a set of blocks left out: ``sample_cfg_slg`` is
-the definition ``lt_sample_ode_cfg_slg`` is held to, ``slg_table`` builds the table of ``s`` and ``slg_combine`` is the chain of roundings."""
+the definition ``lt_sample_ode_cfg_slg`` is held to, ``slg_table`` builds the table of ``s`` and ``slg_combine`` is the chain of roundings.
+
+Perturbed-attention guidance takes the third prediction with a set of blocks PERTURBED - their self-attention map replaced by the
+identity, so every query's output is its own value row - and, if wanted, another set left out: ``sample_cfg_pag`` is the definition
+``lt_sample_ode_cfg_pag`` is held to, ``pag_table`` builds the table, and the chain of roundings is ``slg_combine`` unchanged."""
 from __future__ import annotations
 
 import math
@@ -659,6 +663,151 @@ def sample_cfg_slg(model, z, tgrid, table, slg, slg_layers, method="euler", *, c
             o = model.forward(y[:half], tvec[:half], **half_kw)
             return th.cat([o, o])
         k = model.forward(y[:half], tvec[:half], **half_kw, skip_layers=layers).to(th.bfloat16)
+        ch = min(ch_model, k.size(1))
+        if scale != 1.0:
+            o = model.forward(th.cat([y[:half]] * 2), tvec, **cond_kw).to(th.bfloat16)
+            g = slg_combine(o[:half, :ch], o[half:, :ch], k[:, :ch], scale, s)
+            return th.cat([th.cat([g, o[:half, ch:]], 1), th.cat([g, o[half:, ch:]], 1)]).to(y.dtype)
+        o = model.forward(y[:half], tvec[:half], **half_kw).to(th.bfloat16)
+        g = slg_combine(o[:, :ch], None, k[:, :ch], scale, s)
+        r = th.cat([g, o[:, ch:]], 1)
+        return th.cat([r, r]).to(y.dtype)
+
+    def f(tt, y):
+        return _call(func, tt, y) if t_round else func(tt, y)
+
+    # fixed_grid_odeint's loop (integrators.py), statement for statement
+    out = th.empty((len(t),) + tuple(z.shape), dtype=z.dtype, device=device)
+    out[0] = z
+    y = z
+    third, two_thirds = 1.0 / 3.0, 2.0 / 3.0
+    for j in range(len(t) - 1):
+        t0, t1 = t[j], t[j + 1]
+        dt = t1 - t0
+        k1 = f(t0, y)
+        if method == "euler":
+            dy = dt * k1
+        elif method == "midpoint":
+            half = 0.5 * dt
+            dy = dt * f(t0 + half, y + k1 * half)
+        else:
+            k2 = f(t0 + dt * third, y + dt * k1 * third)
+            k3 = f(t0 + dt * two_thirds, y + dt * (k2 - k1 * third))
+            k4 = f(t1, y + dt * (k1 - k2 + k3))
+            dy = (k1 + 3 * (k2 + k3) + k4) * dt * 0.125
+        y = y + dy
+        out[j + 1] = y
+    assert call[0] == (len(t) - 1) * stages
+    return out
+
+
+# ---- perturbed-attention guidance: the third prediction runs a set of blocks with the identity as their attention map -----------
+def pag_table(tgrid, method, pag_scale, interval=None):
+    """The fp32 table of perturbed-attention scales of a trajectory, one per evaluation: ``slg_table``'s rule - ``pag_scale`` where
+    ``lo <= t_stage < hi`` for ``interval = (lo, hi)`` (default: everywhere), 0 elsewhere, on the unrounded fp32 stage times"""
+    try:
+        return slg_table(tgrid, method, pag_scale, interval=interval)
+    except ValueError as exc:
+        raise ValueError(str(exc).replace("skip-layer", "perturbed-attention")) from None
+
+
+def check_pag(pag, tgrid, method):
+    """``pag`` as an fp32 CPU tensor of ``(len(tgrid) - 1) * stages`` finite entries"""
+    if pag is None:
+        raise ValueError("perturbed-attention table is None (one scale per evaluation; pag_table builds one)")
+    try:
+        return check_slg(pag, tgrid, method)
+    except ValueError as exc:
+        raise ValueError(str(exc).replace("skip-layer", "perturbed-attention")) from None
+
+
+def check_pag_layers(pag_layers, skip_layers=(), n_layers=None):
+    """-> (perturb set, skip set) as lists of ints.  Refused: an entry that is no integer, a repeated index, an index in both sets, and -
+    when the depth is known - an index outside ``0 .. n_layers - 1`` and a SKIP set that leaves no layer (the perturb set may hold every
+    layer): what the engine refuses"""
+    skip = check_slg_layers(skip_layers if skip_layers is not None else (), n_layers)
+    out = []
+    for v in (pag_layers.reshape(-1).tolist() if isinstance(pag_layers, th.Tensor) else list(pag_layers if pag_layers is not None else ())):
+        if isinstance(v, bool) or int(v) != v:
+            raise ValueError(f"perturb layer {v!r} is not an integer index")
+        if int(v) in out:
+            raise ValueError(f"perturb index {int(v)} is repeated")
+        if n_layers is not None and not 0 <= int(v) < n_layers:
+            raise ValueError(f"perturb index {int(v)} is outside 0..{n_layers - 1}")
+        if int(v) in skip:
+            raise ValueError(f"layer {int(v)} is in the skip set and in the perturb set (the sets are disjoint)")
+        out.append(int(v))
+    return out, skip
+
+
+def refuse_with_pag(pag, method="euler", rescale=0.0, norm_limit=math.inf, reuse=None, slg=None, teacache=None, mask=None):
+    """what perturbed-attention guidance is not served with, by name: the companions skip-layer guidance refuses - a rescale / norm-limit rule,
+    a reuse table, a method that is not fixed-grid (multistep and adaptive solvers), step caching, an inpainting mask - and a second scale
+    table (``slg`` beside ``pag``: the skip set joins the ONE third prediction under the ``pag`` table)"""
+    if pag is None:
+        return
+    if slg is not None:
+        raise ValueError("perturbed-attention guidance (a pag table) together with an slg table is not served: one third prediction, one scale "
+                         "table - give slg_layers beside pag_layers under the pag table")
+    if method not in FIXED_GRID_METHODS:
+        raise ValueError(f"perturbed-attention guidance is built for the fixed-grid methods {', '.join(FIXED_GRID_METHODS)}, not '{method}'")
+    if not rule_is_off(rescale, norm_limit):
+        raise ValueError("perturbed-attention guidance (a pag table) together with a rescale / norm_limit rule is not served")
+    if reuse is not None:
+        raise ValueError("perturbed-attention guidance (a pag table) together with guidance reuse (a reuse table) is not served")
+    if teacache is not None:
+        raise ValueError("perturbed-attention guidance (a pag table) together with step caching (teacache) is not served")
+    if mask is not None:
+        raise ValueError("perturbed-attention guidance (a pag table) together with an inpainting mask is not served")
+
+
+def sample_cfg_pag(model, z, tgrid, table, pag, pag_layers, skip_layers=(), method="euler", *, cond=None, t_round=True, **kw):
+    """The trajectory of perturbed-attention guidance on the host: every state ``[len(tgrid), *z.shape]``.  This IS the definition
+    ``lt_sample_ode_cfg_pag`` is held to, state for state.  Per evaluation ``table`` gives the scale ``w`` and ``pag`` the scale ``s``:
+
+        s == 0            what sample_cfg_schedule does (forward_with_cfg at w, or the cond rows alone at w == 1)
+        s != 0            k = bf16(model.forward(x[:B'], t[:B'], <cond half>, skip_layers=S, perturb_layers=P))
+                          o = bf16(model.forward(cat([x[:B']] * 2), t, <conditioning>))    (w == 1: the B' cond rows alone)
+                          g = (u + w * (c - u)) + s * (c - k)                                (w == 1: g = c + s * (c - k))
+
+    ``P``: the blocks whose self-attention map is replaced by the identity (every query's output is its own value row; the text
+    cross-attention stays), ``S``: the blocks left out; disjoint, either may be empty.  Everything else is ``sample_cfg_slg``, statement for
+    statement: the chain of roundings is ``slg_combine``."""
+    if isinstance(z, (list, tuple)):
+        raise ValueError("perturbed-attention guidance takes a tensor state; a packed batch (a list of latents) is not served")
+    stages = _check_method(method)
+    table = check_table(table, tgrid, method)
+    pag = check_pag(pag, tgrid, method)
+    perturb, layers = check_pag_layers(pag_layers, skip_layers, getattr(model, "n_layers", None))
+    if not perturb and not layers and bool((pag != 0).any()):
+        raise ValueError("both layer sets are empty and the table has a non-zero scale: the third prediction would be the conditional one")
+    B = z.size(0)
+    if B % 2:
+        raise ValueError(f"guidance needs an even batch (cond + uncond rows), got {B}")
+    kw = dict(kw)
+    kw.pop("cfg_scale", None)  # the table is the scale
+    refuse_with_pag(pag, method, kw.pop("rescale", 0.0), kw.pop("norm_limit", math.inf), kw.pop("reuse", None))
+    if cond is None:
+        cond = [k for k, v in kw.items() if isinstance(v, th.Tensor) and v.dim() >= 1 and v.shape[0] == B]
+    cond_kw = {k: kw.pop(k) for k in cond}
+    half_kw = {k: _cond_half(v, B) for k, v in cond_kw.items()}
+    ch_model = int(getattr(model, "cfg_channels", 3))
+    device = z.device
+    t = _grid32(tgrid).to(device)
+    w, sl = table.tolist(), pag.tolist()
+    call = [0]
+
+    def func(tt, y):
+        scale, s = w[call[0]], sl[call[0]]
+        call[0] += 1
+        half = B // 2
+        tvec = th.ones(B).to(device) * tt  # fp32 [B] (reference integrators.py:108)
+        if s == 0.0:  # sample_cfg_schedule's stage
+            if scale != 1.0:
+                return model.forward_with_cfg(y, tvec, **cond_kw, cfg_scale=scale, **kw)
+            o = model.forward(y[:half], tvec[:half], **half_kw)
+            return th.cat([o, o])
+        k = model.forward(y[:half], tvec[:half], **half_kw, skip_layers=layers, perturb_layers=perturb).to(th.bfloat16)
         ch = min(ch_model, k.size(1))
         if scale != 1.0:
             o = model.forward(th.cat([y[:half]] * 2), tvec, **cond_kw).to(th.bfloat16)

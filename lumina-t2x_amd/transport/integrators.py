@@ -321,7 +321,7 @@ class ode:
         self.max_num_steps = 2 ** 31 - 1
         self.stats = None         # adaptive methods: nfe / accepted / rejected / first_step / dt of the last sample() call
 
-    def _sample_cfg_schedule(self, x, model, table, model_kwargs, rescale=0.0, norm_limit=math.inf, reuse=None, slg=None, slg_layers=()):
+    def _sample_cfg_schedule(self, x, model, table, model_kwargs, rescale=0.0, norm_limit=math.inf, reuse=None, slg=None, slg_layers=(), pag=None, pag_layers=()):
         """a guidance schedule (transport/guidance.py): one engine call for an engine-backed forward_with_cfg, else the host loop"""
         from .guidance import (cfg_table, refuse_rule_with_reuse, rule_is_off, sample_cfg_multistep, sample_cfg_reuse, sample_cfg_reuse_multistep,
                                sample_cfg_rule, sample_cfg_schedule)
@@ -340,8 +340,16 @@ class ode:
             if isinstance(x, (list, tuple)):
                 raise ValueError("skip-layer guidance (slg_table) takes a tensor state; a packed batch (a list of latents) is not served")
             refuse_with_slg(slg, self.sampler_type, rescale, norm_limit, reuse)
+        if pag is not None:  # perturbed-attention guidance: refused by name with what skip-layer guidance refuses, and with an slg table
+            from .guidance import refuse_with_pag, sample_cfg_pag
+            if isinstance(x, (list, tuple)):
+                raise ValueError("perturbed-attention guidance (pag_table) takes a tensor state; a packed batch (a list of latents) is not served")
+            refuse_with_pag(pag, self.sampler_type, rescale, norm_limit, reuse, slg)
         target = _engine_target(model)
         if target is not None and target[1] and x.is_cuda and self.use_engine and hasattr(target[0], "_engine_sample_ode_cfg_schedule"):
+            if pag is not None:
+                return target[0]._engine_sample_ode_cfg_schedule(x, self.t, self.sampler_type, self.t_round_to_state_dtype, table, dict(model_kwargs),
+                                                                 pag=pag, pag_layers=pag_layers, slg_layers=slg_layers)
             if slg is not None:
                 return target[0]._engine_sample_ode_cfg_schedule(x, self.t, self.sampler_type, self.t_round_to_state_dtype, table, dict(model_kwargs),
                                                                  slg=slg, slg_layers=slg_layers)
@@ -355,6 +363,9 @@ class ode:
         owner = getattr(model, "__self__", None)
         if owner is None or getattr(model, "__name__", "") != "forward_with_cfg" or not hasattr(owner, "forward"):
             raise TypeError("cfg_table needs the bound forward_with_cfg of a model that also has forward (the conditional-only stages call it)")
+        if pag is not None:
+            return sample_cfg_pag(owner, x, self.t, table, pag, pag_layers, slg_layers, self.sampler_type, t_round=self.t_round_to_state_dtype,
+                                  **model_kwargs)
         if slg is not None:
             return sample_cfg_slg(owner, x, self.t, table, slg, slg_layers, self.sampler_type, t_round=self.t_round_to_state_dtype, **model_kwargs)
         if reuse is not None and self.sampler_type in MULTISTEP_METHODS:
@@ -386,7 +397,12 @@ class ode:
                                                  IDENTITY if coefficients is None else coefficients)
 
     def sample(self, x, model, cfg_table=None, cfg_rescale=0.0, cfg_norm_limit=math.inf, cfg_reuse=None, slg_table=None, slg_layers=(),
-               teacache=None, teacache_coefficients=None, **model_kwargs):
+               teacache=None, teacache_coefficients=None, pag_table=None, pag_layers=(), **model_kwargs):
+        if pag_table is not None:  # perturbed-attention guidance: its refusals come first, by name
+            from .guidance import refuse_with_pag
+            refuse_with_pag(pag_table, self.sampler_type, cfg_rescale, cfg_norm_limit, cfg_reuse, slg_table, teacache)
+            return self._sample_cfg_schedule(x, model, cfg_table, model_kwargs, cfg_rescale, cfg_norm_limit, cfg_reuse, None, slg_layers,
+                                             pag_table, pag_layers)
         if teacache is not None:  # (None: the call made without it)
             return self._sample_teacache(x, model, teacache, teacache_coefficients, model_kwargs, cfg_table=cfg_table, cfg_rescale=cfg_rescale,
                                          cfg_norm_limit=cfg_norm_limit, cfg_reuse=cfg_reuse, slg=slg_table)
