@@ -381,6 +381,41 @@ int lt_sample_ode_cfg_rule(lt_engine* e, const void* z_dev, void* traj_dev, void
 int lt_forward_cfg_rule(lt_engine* e, const void* x_dev, const float* t_dev, void* out_dev, float rescale, float norm_limit, const lt_step_args* a,
                         void* stream);
 
+/* Projected guidance (transport/guidance.py: guided_project / sample_cfg_project are the definition, held bit for bit): two
+ * published forms of the guided output that need inner products between the cond rows' output c and the uncond rows' output u, on the first
+ * cfg_channels channels.  Sums run over one sample's n = cfg_channels H W elements in float64; the coefficients are float64 scalar arithmetic
+ * without contraction, each rounded once to fp32; every elementwise operation is one fp32 operation that rounds on its own.
+ *   form LT_PROJECT_APG (Sadat et al. 2024), parameters eta (finite), momentum beta (|beta| < 1), norm_threshold r (> 0, +inf = off):
+ *     d = bf16(c - u);  m = d + beta m_prev  (fp32, kept in an engine buffer [B', cfg_channels, H, W] from one guided evaluation to the next)
+ *     tn = min(1, r / sqrt(sum m^2)) if r < inf and sum m^2 > 0, else 1;   p = tn sum m c / sum c^2 if sum c^2 > 0, else 0
+ *     a = fp32((w - 1) tn);  b = fp32((w - 1)(eta - 1) p);  g = bf16(c + (a m + b c))
+ *     i.e. c + (w - 1)(orthogonal part + eta parallel part) of the clipped m, the projection taken on the model's velocity output.
+ *     At eta = 1, beta = 0, r = +inf this is c + (w - 1)(c - u): plain guidance in ANOTHER rounding chain, not lt_forward_cfg's words.
+ *   form LT_PROJECT_ZERO_STAR (Fan et al. 2025): s = fp32(sum c u / sum u^2) if sum u^2 > 0, else 1;  g = bf16(s u + w (c - s u));
+ *     zero_init K >= 0: the first K grid intervals take zero velocity - their trajectory slots receive the state unchanged, NO evaluation is
+ *     launched for them, lt_last_nfe / lt_last_eval_rows do not count them, their table entries are not read.  K >= n_grid - 1 is refused.
+ * g goes to both halves; the channels at or past cfg_channels pass through row by row, as in lt_forward_cfg.
+ * lt_sample_ode_cfg_project: lt_sample_ode_cfg_schedule's arguments and behaviour with the form on every stage whose scale is not 1; a stage
+ * at scale 1 exactly is that call's conditional-only stage and neither reads nor writes the momentum.  The momentum is zeroed once, in stream
+ * order, in front of the first evaluation of EVERY call; the guided evaluations advance it in evaluation order (the stages of midpoint / rk4
+ * count).  The parameters are committed with the scale table and read from device memory: a trajectory uses at most two HIP-graph keys (the
+ * projected evaluation of its form, the conditional one) whatever the table and the parameters hold.  The parameters of the form not chosen
+ * are ignored (zero_init belongs to Zero*, and must be 0 under APG).  No synchronisation, no host read.
+ * lt_forward_cfg_project: ONE evaluation, always guided, at a->cfg_scale.  keep_momentum 0: the momentum is zeroed first; 1: it continues
+ * from the one the last projected APG evaluation left - refused by name when none is stored for this shape (none yet, another shape, or
+ * lt_prepare_prompt* / lt_prepare_labels was called since).  Under Zero* keep_momentum must be 0.
+ * Both calls are refused on a stream under capture.  Not served: packed batches, regional prompts, views, the rescale / norm-limit rule,
+ * reuse, skip-layer and perturbed-attention guidance, step caching, masks, the multistep and adaptive solvers (each of those is another entry
+ * point; none takes a form).  Refused by name with nothing written: what lt_sample_ode_cfg_schedule refuses; a form other than 1 / 2; eta not
+ * finite; |momentum| >= 1 or NaN; norm_threshold not above 0, or NaN; zero_init < 0, or >= n_grid - 1, or non-zero under APG. */
+#define LT_PROJECT_APG 1
+#define LT_PROJECT_ZERO_STAR 2
+int lt_sample_ode_cfg_project(lt_engine* e, const void* z_dev, void* traj_dev, void* final_dev, const float* tgrid_host, int32_t n_grid,
+                              int32_t method, const float* cfg_host, int32_t form, float eta, float momentum, float norm_threshold,
+                              int32_t zero_init, int32_t t_round_to_state_dtype, const lt_step_args* a, void* stream);
+int lt_forward_cfg_project(lt_engine* e, const void* x_dev, const float* t_dev, void* out_dev, int32_t form, float eta, float momentum,
+                           float norm_threshold, int32_t keep_momentum, const lt_step_args* a, void* stream);
+
 /* Linear multistep sampling (transport/multistep.py states the loop in torch ops and the engine is held to it bit for bit):
  * Adams-Bashforth predictors of 2 or 3 slopes (ab2, ab3) and the same with an Adams-Moulton corrector that costs no evaluation (abm2, abm3).
  * Exactly N = n_grid - 1 model evaluations, one per interval, none at the last grid point (lt_last_nfe).  With f_i = model(p_i, t_i):

@@ -227,6 +227,21 @@ int lt_op_unpatchify_cfg_rule(const void* rows, int32_t ld, void* out, int32_t o
                               int32_t patch, int32_t use_cfg, const float* cfg_scale_dev, int32_t cfg_channels, int32_t wp_stride, int32_t dup,
                               const double* partials_dev, const float* rescale_dev, const float* norm_limit_dev, float* factor_out_dev,
                               void* stream);
+/* Projected guidance (csrc/guidance_project.hip), for tests/test_gpu_cfg_project.py.  form: LT_PROJECT_APG (1) /
+ * LT_PROJECT_ZERO_STAR (2).  B counts the 2 B' rows of the evaluation; S = lt_op_guidance_slices(); par_dev: four floats { scale, eta, beta, r }.
+ *   guidance_project_stats: partials_dev [B' * S * 3] doubles, slice s of sample b at [(b * S + s) * 3]: APG { sum m^2, sum m c, sum c^2 } with
+ *   m = bf16(c - u) + beta * mom, which REPLACES mom_dev (fp32 [B', cfg_channels, H, W]) word by word; Zero* { sum c u, sum u^2, 0 }, par_dev and
+ *   mom_dev may be NULL.  Products and sums in float64 in an order the launch fixes; every one of the B' * S * 3 words is written, nothing behind.
+ *   unpatchify_cfg_project: lt_op_unpatchify_cfg_dev whose guided values are APG's bf16(c + (a m + b c)) with m read from mom_dev, or Zero*'s
+ *   bf16(s u + w (c - s u)), the coefficients formed in float64 from the partials summed in slice order (lumina_dit.h has the expressions).
+ *   coef_out_dev (may be NULL): APG 2 B' floats (a, b) per sample, Zero* B' floats s.  With dup, or use_cfg 0, the result is
+ *   lt_op_unpatchify_cfg_dev's and the pointers behind dup may be NULL.  Refused: an odd B, more than 256 samples, another form. */
+int lt_op_guidance_project_stats(const void* rows, int32_t ld, int32_t B, int32_t out_ch, int32_t H, int32_t W, int32_t patch, int32_t cfg_channels,
+                                 int32_t wp_stride, int32_t form, const float* par_dev, float* mom_dev, double* partials_dev, void* stream);
+int lt_op_unpatchify_cfg_project(const void* rows, int32_t ld, void* out, int32_t out_dtype, int32_t B, int32_t C, int32_t out_ch, int32_t H,
+                                 int32_t W, int32_t patch, int32_t use_cfg, const float* cfg_scale_dev, int32_t cfg_channels, int32_t wp_stride,
+                                 int32_t dup, int32_t form, const double* partials_dev, const float* par_dev, const float* mom_dev,
+                                 float* coef_out_dev, void* stream);
 /* Guidance reuse (csrc/guidance_reuse.hip), for tests/test_gpu_cfg_reuse.py.  B counts the 2 B' rows of out; delta_dev: bf16
  * [B', cfg_channels, H, W]; the scale is one float of device memory.  mode 0: lt_op_unpatchify_cfg_dev at use_cfg 1, dup 0 on the 2 B' rows,
  * and delta = bf16(c - u) of the channels < cfg_channels is written.  mode 1: rows holds B' samples; the channels < cfg_channels become

@@ -23,6 +23,8 @@ LT_VARIANT_NEXT_T2I, LT_VARIANT_NEXT_IMAGENET, LT_VARIANT_FLAG_T2I, LT_VARIANT_N
 LT_VARIANT_NEXT_MOE_TIME, LT_VARIANT_NEXT_MOE_SPACE = 4, 5
 LT_SOFTMAX_T2I, LT_SOFTMAX_ANAGRAM = 0, 1
 SOFTMAX_RULES = {"t2i": LT_SOFTMAX_T2I, "anagram": LT_SOFTMAX_ANAGRAM}
+LT_PROJECT_APG, LT_PROJECT_ZERO_STAR = 1, 2  # the projected forms of lt_sample_ode_cfg_project / lt_forward_cfg_project
+PROJECT_FORMS = {"apg": LT_PROJECT_APG, "zero_star": LT_PROJECT_ZERO_STAR}
 LT_ODE_EULER, LT_ODE_MIDPOINT, LT_ODE_RK4 = 0, 1, 2
 ODE_METHODS = {"euler": LT_ODE_EULER, "midpoint": LT_ODE_MIDPOINT, "rk4": LT_ODE_RK4}
 LT_ODE_DOPRI5, LT_ODE_BOSH3, LT_ODE_FEHLBERG2, LT_ODE_ADAPTIVE_HEUN = 3, 4, 5, 6
@@ -120,6 +122,9 @@ _SIGNATURES: Dict[str, tuple] = {
     "lt_sample_ode_cfg_schedule": (_i32, [_vp, _vp, _vp, _vp, C.POINTER(_f32), _i32, _i32, C.POINTER(_f32), _i32, C.POINTER(LtStepArgs), _vp]),
     "lt_sample_ode_cfg_rule": (_i32, [_vp, _vp, _vp, _vp, C.POINTER(_f32), _i32, _i32, C.POINTER(_f32), _f32, _f32, _i32, C.POINTER(LtStepArgs), _vp]),
     "lt_forward_cfg_rule": (_i32, [_vp, _vp, _vp, _vp, _f32, _f32, C.POINTER(LtStepArgs), _vp]),
+    "lt_sample_ode_cfg_project": (_i32, [_vp, _vp, _vp, _vp, C.POINTER(_f32), _i32, _i32, C.POINTER(_f32), _i32, _f32, _f32, _f32, _i32, _i32,
+                                         C.POINTER(LtStepArgs), _vp]),
+    "lt_forward_cfg_project": (_i32, [_vp, _vp, _vp, _vp, _i32, _f32, _f32, _f32, _i32, C.POINTER(LtStepArgs), _vp]),
     "lt_sample_ode_multistep": (_i32, [_vp, _vp, _vp, _vp, C.POINTER(_f32), _i32, C.POINTER(_f32), _i32, C.POINTER(_f32), _f32, _f32, _i32, _i32,
                                        C.POINTER(LtStepArgs), _vp]),
     "lt_sample_ode_multistep_packed": (_i32, [_vp, _vp, C.POINTER(_i32), _vp, _vp, C.POINTER(_f32), _i32, C.POINTER(_f32), _i32, _i32, _i32,
@@ -214,6 +219,9 @@ _SIGNATURES: Dict[str, tuple] = {
     "lt_op_guidance_slices": (_i32, []),
     "lt_op_guidance_stats": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _vp, _vp]),
     "lt_op_unpatchify_cfg_rule": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "lt_op_guidance_project_stats": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "lt_op_unpatchify_cfg_project": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp,
+                                            _vp, _vp]),
     "lt_op_unpatchify_cfg_reuse": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _vp, _i32, _vp]),
     "lt_op_unpatchify_cfg_slg": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _i32, _vp]),
     "lt_op_unpatchify_cfg": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _i32, _vp]),

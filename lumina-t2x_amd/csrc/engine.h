@@ -229,6 +229,17 @@ struct lt_engine {
     // skip-layer guidance: the guided channels of the last skip evaluation, bf16 [B', ch, H, W]; sized and allocated like g_delta
     // (ensure_skip_buf).  Written and read inside one entry-point call only, so it carries no signature
     u16* g_skip = nullptr;
+    // projected guidance: which two kernels close an LT_KIND_RULE evaluation - 0 the rescale / norm-limit rule, LT_PROJECT_APG,
+    // LT_PROJECT_ZERO_STAR.  An argument of the call that travels here to close_forward, as `skip` does: only ProjectScope writes it, and its
+    // destructor puts 0 back on every exit path.  Part of the graph key when it is not 0.
+    int rule_form = 0;
+    // ... its buffers, allocated by the first call that needs them (ensure_project) and kept for the engine's life - captured graphs hold the
+    // pointers: APG's momentum, fp32 [B', ch, H, W] (g_delta's element count); the partial sums, max_batch / 2 x LT_GUIDANCE_SLICES x
+    // LT_PROJECT_SUMS; the parameter words { scale, eta, beta, r }.  proj_sig: { B', H, W, ch } of what the momentum holds, B' = 0: nothing;
+    // every lt_prepare_prompt* / lt_prepare_labels call zeroes it
+    float *p_mom = nullptr, *p_par = nullptr;
+    double* p_stats = nullptr;
+    int proj_sig[4] = {0, 0, 0, 0};
     // the layers THIS call's evaluation leaves out (ascending, distinct, inside 0 .. L-1, not all of them): an argument of the call that
     // travels here to run_forward.  Only SkipScope writes it, and its destructor empties it on every exit path
     std::vector<int32_t> skip;
@@ -284,6 +295,16 @@ int ensure_step_cache(lt_engine* e);
 int ensure_delta(lt_engine* e);
 // ... and the skip buffer of skip-layer guidance (engine.hip)
 int ensure_skip_buf(lt_engine* e);
+// ... and the buffers of projected guidance (engine.hip)
+int ensure_project(lt_engine* e);
+// The rule form of one call's LT_KIND_RULE evaluations: set for the scope, 0 again behind it
+struct ProjectScope {
+    lt_engine* e;
+    ProjectScope(lt_engine* eng, int form) : e(eng) { e->rule_form = form; }
+    ProjectScope(const ProjectScope&) = delete;
+    ProjectScope& operator=(const ProjectScope&) = delete;
+    ~ProjectScope() { e->rule_form = 0; }
+};
 // The layer sets of one call: the blocks left out and the blocks whose self-attention is perturbed.  set() refuses by
 // name - an index outside 0 .. L-1, a repeated index, more indices than L, a skip set that leaves no layer, an index in both sets - and
 // otherwise stores each set in ascending order; the destructor empties both, so no entry point returns with a set left behind

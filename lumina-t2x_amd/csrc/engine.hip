@@ -438,7 +438,13 @@ int close_forward(lt_engine* e, void* out, const lt_step_args* a, int use_cfg, i
     case LT_KIND_DEV_GUIDED: case LT_KIND_COND_ONLY:
         return launch_unpatchify_cfg_dev(e->frows, e->nfinal, out, a->io_dtype, Bout, c.in_channels, c.out_channels, a->latent_h, a->latent_w, p,
                                          use_cfg, g, cfg_ch, Wrow, kind == LT_KIND_COND_ONLY ? 1 : 0, s);
-    case LT_KIND_RULE:  // guidance_stats, then the kernel that multiplies by the per-sample factor
+    case LT_KIND_RULE:  // guidance_stats, then the kernel that multiplies by the per-sample factor - or the two kernels of a projected form
+        if (e->rule_form != 0) {  // (the scale in g[0] as ever, eta / beta / r in e->p_par[1..3], APG's momentum advanced in place)
+            if (launch_guidance_project_stats(e->frows, e->nfinal, B, c.out_channels, a->latent_h, a->latent_w, p, guided_ch, Wrow, e->rule_form,
+                                              e->p_par, e->p_mom, e->p_stats, s)) return 1;
+            return launch_unpatchify_cfg_project(e->frows, e->nfinal, out, a->io_dtype, B, c.in_channels, c.out_channels, a->latent_h, a->latent_w,
+                                                 p, use_cfg, g, guided_ch, Wrow, 0, e->rule_form, e->p_stats, e->p_par, e->p_mom, nullptr, s);
+        }
         if (launch_guidance_stats(e->frows, e->nfinal, B, c.out_channels, a->latent_h, a->latent_w, p, g, guided_ch, Wrow, e->g_stats, s)) return 1;
         return launch_unpatchify_cfg_rule(e->frows, e->nfinal, out, a->io_dtype, B, c.in_channels, c.out_channels, a->latent_h, a->latent_w, p,
                                           use_cfg, g, guided_ch, Wrow, 0, e->g_stats, g + 1, g + 2, nullptr, s);
@@ -499,6 +505,8 @@ int forward_dims(lt_engine* e, const lt_step_args* a, int use_cfg, hipStream_t s
     LT_REQUIRE(e->perturb.empty() || e->reg_Y == 0, "perturbed attention: a regional prompt is prepared (lt_prepare_prompt_regional), which is not served");
     if (lt_slg_kernel_mode(kind) >= 0) LT_REQUIRE(e->g_skip, "skip-layer guidance: the buffer is not allocated (ensure_skip_buf)");
     if (kind == LT_KIND_REUSE_STORE || kind == LT_KIND_REUSE_AGAIN) LT_REQUIRE(e->g_delta, "guidance reuse: the buffer is not allocated (ensure_delta)");
+    LT_REQUIRE(e->rule_form == 0 || (kind == LT_KIND_RULE && e->p_mom && e->p_par && e->p_stats) || kind == LT_KIND_COND_ONLY,
+               "projected guidance: form %d on an evaluation of kind %d, or the buffers are not allocated (ensure_project)", e->rule_form, (int)kind);
     e->cache_head[0] = 0;  // (this evaluation rewrites e->x / e->h / e->mod, or uses them up; forward_graphed sets it behind a head)
     if (kt.cached) {
         LT_REQUIRE(!e->moe_rec_on && !e->moe_force_rows, "step caching: MoE routing record / force is not served");
@@ -989,6 +997,19 @@ static int ensure_half_state(lt_engine* e, u16** buf, const char* what) {
     return 0;
 }
 
+// the buffers of projected guidance: the momentum (zeroed by every call that starts one), the partial sums and the parameter words
+int ensure_project(lt_engine* e) {
+    if (e->p_mom && e->p_stats && e->p_par) return 0;
+    const lt_config& c = e->cfg;
+    const size_t words = (size_t)(c.max_batch / 2) * c.in_channels * c.max_tokens * c.patch_size * c.patch_size;
+    LT_REQUIRE(words > 0, "projected guidance: an engine of max_batch %d holds no cond + uncond pair", c.max_batch);
+    void* q = nullptr;
+    if (!e->p_mom) { if (dev_alloc(e, &q, words * sizeof(float))) return 1; e->p_mom = (float*)q; }
+    if (!e->p_stats) { if (dev_alloc(e, &q, (size_t)(c.max_batch / 2) * LT_GUIDANCE_SLICES * LT_PROJECT_SUMS * sizeof(double))) return 1; e->p_stats = (double*)q; }
+    if (!e->p_par) { if (dev_alloc(e, &q, 4 * sizeof(float))) return 1; e->p_par = (float*)q; }
+    return 0;
+}
+
 int ensure_delta(lt_engine* e) { return ensure_half_state(e, &e->g_delta, "guidance reuse"); }
 int ensure_skip_buf(lt_engine* e) { return ensure_half_state(e, &e->g_skip, "skip-layer guidance"); }
 
@@ -1120,6 +1141,10 @@ static int forward_graphed_body(lt_engine* e, const void* x_in, const float* t_d
         const int32_t mark[2] = {-2, (int32_t)e->perturb.size()};
         key.insert(key.end(), (const char*)mark, (const char*)(mark + 2));
         key.insert(key.end(), (const char*)e->perturb.data(), (const char*)(e->perturb.data() + e->perturb.size()));
+    }
+    if (e->rule_form != 0 && kind == LT_KIND_RULE) {  // a projected form: other closing kernels.  Form 0: the key of always
+        const int32_t mark[2] = {-3, (int32_t)e->rule_form};
+        key.insert(key.end(), (const char*)mark, (const char*)(mark + 2));
     }
     lt_engine::GraphEntry* ge = nullptr;
     for (auto& g : e->graphs) if (g.key == key) { ge = &g; break; }
@@ -1512,6 +1537,7 @@ extern "C" int lt_prepare_prompt(lt_engine* e, const void* cap_feats_dev, int32_
                                  int32_t B, int32_t T, void* stream) {
     LT_REQUIRE(e && cap_feats_dev && cap_mask_dev, "lt_prepare_prompt: null argument");
     e->delta_sig[0] = 0;  // (guidance reuse: a stored difference belongs to the conditioning it was taken on)
+    e->proj_sig[0] = 0;   // (projected guidance: so does a stored momentum)
     e->cache_res[0] = 0; e->cache_head[0] = 0;  // (step caching: so does a stored residual, and a probe)
     LtOptScope opt_scope(&e->opts);
     LT_REQUIRE(e->v.text, "lt_prepare_prompt: this variant is class-conditional (use lt_prepare_labels)");
@@ -1540,6 +1566,7 @@ extern "C" int lt_prepare_prompt_regional(lt_engine* e, const void* cap_feats_de
                                           int32_t Tg, int32_t h_split, int32_t w_split, void* stream) {
     LT_REQUIRE(e && cap_feats_dev && cap_mask_dev && global_feats_dev && global_mask_dev, "lt_prepare_prompt_regional: null argument");
     e->delta_sig[0] = 0;  // (guidance reuse: a stored difference belongs to the conditioning it was taken on)
+    e->proj_sig[0] = 0;   // (projected guidance: so does a stored momentum)
     e->cache_res[0] = 0; e->cache_head[0] = 0;  // (step caching: so does a stored residual, and a probe)
     if (refuse_if_capturing((hipStream_t)stream, "lt_prepare_prompt_regional")) return 2;  // (allocates, uploads a host table, synchronises)
     LtOptScope opt_scope(&e->opts);
@@ -1586,6 +1613,7 @@ extern "C" int lt_prepare_prompt_regional(lt_engine* e, const void* cap_feats_de
 extern "C" int lt_prepare_labels(lt_engine* e, const int32_t* labels_dev, int32_t B, void* stream) {
     LT_REQUIRE(e && labels_dev, "lt_prepare_labels: null argument");
     e->delta_sig[0] = 0;  // (guidance reuse: a stored difference belongs to the conditioning it was taken on)
+    e->proj_sig[0] = 0;   // (projected guidance: so does a stored momentum)
     e->cache_res[0] = 0; e->cache_head[0] = 0;  // (step caching: so does a stored residual, and a probe)
     LtOptScope opt_scope(&e->opts);
     LT_REQUIRE(e->v.labels, "lt_prepare_labels: this variant is text-conditional (use lt_prepare_prompt)");

@@ -372,6 +372,21 @@ int launch_unpatchify_cfg_rule(const u16* rows, int ld, void* out, int out_dtype
                                const float* cfg_scale_dev, int cfg_channels, int wp_stride, int dup, const double* partials,
                                const float* rescale_dev, const float* limit_dev, float* factor_out, hipStream_t stream);
 int launch_guidance_params_store(float* dst, float scale, float rescale, float limit, hipStream_t stream);
+// projected guidance (guidance_project.hip).  form: LT_PROJECT_APG / LT_PROJECT_ZERO_STAR (include/lumina_dit.h).  B counts the 2 B'
+// rows of the evaluation; partials: B' * LT_GUIDANCE_SLICES * LT_PROJECT_SUMS doubles - APG { sum m^2, sum m c, sum c^2 }, Zero* { sum c u,
+// sum u^2, 0 } - every one written by every launch; par_dev: { scale, eta, beta, r } (the kernels read the scale from cfg_scale_dev, which may
+// be par_dev); mom: fp32 [B', cfg_channels, H, W], APG's momentum (Zero*: may be null)
+//   guidance_project_stats: APG replaces mom by d + beta mom, d = bfr(c - u), and sums over the new values
+//   unpatchify_cfg_project: launch_unpatchify_cfg_dev whose guided values are APG's bfr(c + (a m + b c)) or Zero*'s bfr(s u + w (c - s u));
+//   coef_out (may be null) receives the B' pairs (a, b), or the B' values s
+//   guidance_project_params_store: dst[0..3] = scale, eta, beta, r
+constexpr int LT_PROJECT_SUMS = 3;
+int launch_guidance_project_stats(const u16* rows, int ld, int B, int out_ch, int H, int W, int patch, int cfg_channels, int wp_stride, int form,
+                                  const float* par_dev, float* mom, double* partials, hipStream_t stream);
+int launch_unpatchify_cfg_project(const u16* rows, int ld, void* out, int out_dtype, int B, int C, int out_ch, int H, int W, int patch, int use_cfg,
+                                  const float* cfg_scale_dev, int cfg_channels, int wp_stride, int dup, int form, const double* partials,
+                                  const float* par_dev, const float* mom, float* coef_out, hipStream_t stream);
+int launch_guidance_project_params_store(float* dst, float scale, float eta, float beta, float r, hipStream_t stream);
 // guidance reuse (guidance_reuse.hip).  B counts the 2 B' OUTPUT rows; delta: bf16 [B', cfg_channels, H, W]; the scale is read
 // from device memory.  mode 0: launch_unpatchify_cfg_dev at use_cfg = 1, dup = 0 on 2 B' rows, and d = bfr(cond - uncond) of the guided
 // channels is stored; mode 1: `rows` holds the B' cond rows, the guided channels become bfr(bfr(c' - d) + bfr(w d)) with the stored d (not

@@ -714,6 +714,19 @@ extern "C" int lt_op_unpatchify_cfg_rule(const void* rows, int32_t ld, void* out
     return launch_unpatchify_cfg_rule((const u16*)rows, ld, out, out_dtype, B, C, out_ch, H, W, patch, use_cfg, cfg_scale_dev, cfg_channels, wp_stride,
                                       dup, partials_dev, rescale_dev, norm_limit_dev, factor_out_dev, (hipStream_t)stream);
 }
+extern "C" int lt_op_guidance_project_stats(const void* rows, int32_t ld, int32_t B, int32_t out_ch, int32_t H, int32_t W, int32_t patch,
+                                            int32_t cfg_channels, int32_t wp_stride, int32_t form, const float* par_dev, float* mom_dev,
+                                            double* partials_dev, void* stream) {
+    return launch_guidance_project_stats((const u16*)rows, ld, B, out_ch, H, W, patch, cfg_channels, wp_stride, form, par_dev, mom_dev, partials_dev,
+                                         (hipStream_t)stream);
+}
+extern "C" int lt_op_unpatchify_cfg_project(const void* rows, int32_t ld, void* out, int32_t out_dtype, int32_t B, int32_t C, int32_t out_ch,
+                                            int32_t H, int32_t W, int32_t patch, int32_t use_cfg, const float* cfg_scale_dev, int32_t cfg_channels,
+                                            int32_t wp_stride, int32_t dup, int32_t form, const double* partials_dev, const float* par_dev,
+                                            const float* mom_dev, float* coef_out_dev, void* stream) {
+    return launch_unpatchify_cfg_project((const u16*)rows, ld, out, out_dtype, B, C, out_ch, H, W, patch, use_cfg, cfg_scale_dev, cfg_channels,
+                                         wp_stride, dup, form, partials_dev, par_dev, mom_dev, coef_out_dev, (hipStream_t)stream);
+}
 extern "C" int lt_op_unpatchify_cfg_reuse(const void* rows, int32_t ld, void* out, int32_t out_dtype, int32_t B, int32_t C, int32_t out_ch, int32_t H,
                                           int32_t W, int32_t patch, const float* cfg_scale_dev, int32_t cfg_channels, int32_t wp_stride,
                                           void* delta_dev, int32_t mode, void* stream) {

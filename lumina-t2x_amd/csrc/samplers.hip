@@ -91,7 +91,15 @@ struct Trajectory {
         const bool cond_only = cfg_host[call] == 1.0f;
         if (reuse_host && !cond_only) return eval_reuse(y, t, call, out);
         if (slg_host && slg_host[call] != 0.0f) return eval_slg(y, t, call, out, cond_only);
+        if (!cond_only && cfg_rule && e->rule_form == LT_PROJECT_APG) return eval_momentum(y, t, out, cfg_dev + call);
         return eval_kind(cond_only ? LT_KIND_COND_ONLY : cfg_rule ? LT_KIND_RULE : LT_KIND_DEV_GUIDED, y, t, out, cfg_dev + call);
+    }
+    // a guided evaluation under APG: it advances the momentum buffer, which holds nothing until the evaluation has been issued whole
+    int eval_momentum(const void* y, const float* t, void* out, const float* scale) {
+        e->proj_sig[0] = 0;
+        if (int rc = eval_kind(LT_KIND_RULE, y, t, out, scale)) return rc;
+        delta_sig_of(e, a, e->proj_sig);
+        return 0;
     }
     // an evaluation of one kind, its rows counted.  scale: where a kind that reads its guidance scale from device memory finds it
     int eval_kind(LtEvalKind kind, const void* y, const float* t, void* out, const float* scale = nullptr) {
@@ -187,7 +195,10 @@ struct MaskedBlend { const void *mask, *x1, *noise; };
 // ... ; skip-layer guidance (lt_sample_ode_cfg_slg): one scale s per scale w and the layer set, or null
 // (lt_sample_ode_cfg_pag: the layers perturbed in the same evaluation; pag: the entry that takes both sets, either of which may be empty)
 struct SlgCall { const float* table; const int32_t* skip; int n_skip; const int32_t* perturb = nullptr; int n_perturb = 0; bool pag = false; };
-struct CfgSchedule { const float* table; const float* rule = nullptr; const int32_t* reuse = nullptr; const SlgCall* slg = nullptr; };
+// projected guidance (lt_sample_ode_cfg_project): the form, { eta, beta, r } and the intervals of zero velocity at the start
+struct ProjectCall { int form; float par[3]; int zero_init; };
+struct CfgSchedule { const float* table; const float* rule = nullptr; const int32_t* reuse = nullptr; const SlgCall* slg = nullptr;
+                     const ProjectCall* project = nullptr; };
 
 int ode_fixed_grid(lt_engine* e, const void* z_dev, void* traj_dev, void* final_dev, const float* tgrid_host, int n_grid, int method, int use_cfg,
                    int t_round, const lt_step_args* a, hipStream_t s, long long n, const PackedCall* pc, const MaskedBlend* mb = nullptr,
@@ -198,7 +209,8 @@ int ode_fixed_grid(lt_engine* e, const void* z_dev, void* traj_dev, void* final_
     const bool bf = a->io_dtype == LT_BF16;
     // stage times; torchdiffeq's _PerturbFunc casts t to the state dtype before calling the model, then
     // integrators.py:108 broadcasts it to an fp32 [B] vector
-    const int nsent = ncalls * B + (cs ? ncalls : 0) + (cs && cs->rule ? 2 : 0) + (cs && cs->slg ? ncalls : 0);  // (a rule and slg never meet)
+    // (a rule, slg and a projected form never meet)
+    const int nsent = ncalls * B + (cs ? ncalls : 0) + (cs && cs->rule ? 2 : 0) + (cs && cs->slg ? ncalls : 0) + (cs && cs->project ? 3 : 0);
     float* tp = e->times.begin(nsent, s);
     if (!tp) return 1;
     std::vector<float> dts(n_grid - 1);
@@ -218,13 +230,24 @@ int ode_fixed_grid(lt_engine* e, const void* z_dev, void* traj_dev, void* final_
     if (cs) memcpy(tp + (size_t)ncalls * B, cs->table, (size_t)ncalls * sizeof(float));
     if (cs && cs->rule) memcpy(tp + (size_t)ncalls * B + ncalls, cs->rule, 2 * sizeof(float));
     if (cs && cs->slg) memcpy(tp + (size_t)ncalls * B + ncalls, cs->slg->table, (size_t)ncalls * sizeof(float));
+    if (cs && cs->project) memcpy(tp + (size_t)ncalls * B + ncalls, cs->project->par, 3 * sizeof(float));
     if (e->times.commit(nsent, s)) return 1;
+    const int zero_init = cs && cs->project ? cs->project->zero_init : 0;
+    if (cs && cs->project) {  // eta, beta, r into their fixed words; APG's momentum starts every trajectory at zero
+        LT_CHECK_HIP(hipMemcpyAsync(e->p_par + 1, e->times.dev + (size_t)ncalls * B + ncalls, 3 * sizeof(float), hipMemcpyDeviceToDevice, s));
+        if (cs->project->form == LT_PROJECT_APG) {
+            int sig[4];
+            Trajectory::delta_sig_of(e, a, sig);
+            e->proj_sig[0] = 0;
+            LT_CHECK_HIP(hipMemsetAsync(e->p_mom, 0, (size_t)sig[0] * sig[3] * sig[1] * sig[2] * sizeof(float), s));
+        }
+    }
     if (cs && cs->rule)
         LT_CHECK_HIP(hipMemcpyAsync(e->g_cfg + 1, e->times.dev + (size_t)ncalls * B + ncalls, 2 * sizeof(float), hipMemcpyDeviceToDevice, s));
     Trajectory tr{e, a, use_cfg, s, (size_t)n * (bf ? 2 : 4)};
     tr.pc = pc;
     tr.cache = cc; tr.ncalls = ncalls;
-    if (cs) { tr.cfg_host = cs->table; tr.cfg_dev = e->times.dev + (size_t)ncalls * B; tr.cfg_rule = cs->rule != nullptr; tr.reuse_host = cs->reuse; }
+    if (cs) { tr.cfg_host = cs->table; tr.cfg_dev = e->times.dev + (size_t)ncalls * B; tr.cfg_rule = cs->rule != nullptr || cs->project != nullptr; tr.reuse_host = cs->reuse; }
     if (cs && cs->slg) {
         tr.slg_host = cs->slg->table; tr.slg_dev = e->times.dev + (size_t)ncalls * B + ncalls;
         tr.skip_host = cs->slg->skip; tr.n_skip = cs->slg->n_skip;
@@ -234,6 +257,10 @@ int ode_fixed_grid(lt_engine* e, const void* z_dev, void* traj_dev, void* final_
     const int dt_code = bf ? 1 : 0;
     for (int i = 0; i + 1 < n_grid; ++i) {
         void *y0 = tr.y0(), *y1 = tr.y1();
+        if (i < zero_init) {  // CFG-Zero*'s zero-init: zero velocity, so the state stays where it is; no evaluation, nothing counted
+            if (tr.traj) LT_CHECK_HIP(hipMemcpyAsync((char*)tr.traj + (size_t)(i + 1) * tr.sbytes, y0, tr.sbytes, hipMemcpyDeviceToDevice, s));
+            continue;
+        }
         // torchdiffeq multiplies the 0-dim DEVICE tensor dt = t1 - t0 (fp32) with the bf16 state / slopes; PyTorch's type
         // promotion keeps bf16 and casts the 0-dim operand to it first, so with a bf16 state every `dt * k` of the reference
         // sees bf16(dt) (0.5 dt is exact after that).  The stage TIMES above stay fp32 (t0 + dt / 2 is fp32 arithmetic).
@@ -422,6 +449,17 @@ int check_rule(const char* who, float rescale, float norm_limit) {
     return 0;
 }
 
+// the form and the parameters of projected guidance
+int check_project(const char* who, int form, float eta, float momentum, float norm_threshold) {
+    LT_REQUIRE(form == LT_PROJECT_APG || form == LT_PROJECT_ZERO_STAR, "%s: form %d is not LT_PROJECT_APG (1) or LT_PROJECT_ZERO_STAR (2)", who, form);
+    if (form != LT_PROJECT_APG) return 0;  // (CFG-Zero* reads none of the three)
+    LT_REQUIRE(std::isfinite(eta), "%s: eta %g is not finite", who, (double)eta);
+    LT_REQUIRE(std::fabs(momentum) < 1.f, "%s: momentum %g is not inside (-1, 1)", who, (double)momentum);
+    LT_REQUIRE(!std::isnan(norm_threshold) && norm_threshold > 0.f, "%s: norm_threshold %g is not above 0 (+inf switches the clip off)", who,
+               (double)norm_threshold);
+    return 0;
+}
+
 // what every call with a scale per evaluation checks behind the shape, before anything is written: the batch, the `intervals * stages` scales,
 // the rule's parameters (`rule` = { rescale, norm limit } or null) and the prepared conditioning
 int check_guided_table(const lt_engine* e, const char* who, const lt_step_args* a, const float* cfg_host, int intervals, int stages, const float* rule) {
@@ -449,7 +487,7 @@ int check_reuse_flags(const char* who, const float* cfg_host, const int32_t* reu
 // lt_sample_ode_cfg_schedule, with `rule` = { rescale, norm limit } lt_sample_ode_cfg_rule, with `reuse_call` lt_sample_ode_cfg_reuse
 int sample_cfg_table(lt_engine* e, const char* who, const void* z_dev, void* traj_dev, void* final_dev, const float* tgrid_host, int n_grid, int method,
                      const float* cfg_host, const float* rule, int t_round, const lt_step_args* a, hipStream_t s, const int32_t* reuse_host = nullptr,
-                     bool reuse_call = false, const SlgCall* slg = nullptr) {
+                     bool reuse_call = false, const SlgCall* slg = nullptr, const ProjectCall* project = nullptr) {
     LT_REQUIRE(e && z_dev && tgrid_host && cfg_host && a, "%s: null argument", who);
     LT_REQUIRE(!reuse_call || reuse_host, "%s: null argument (reuse_host: one int32 flag per stage)", who);
     LT_REQUIRE(!slg || slg->table, "%s: null argument (slg_host: one skip-layer scale per stage)", who);
@@ -462,6 +500,14 @@ int sample_cfg_table(lt_engine* e, const char* who, const void* z_dev, void* tra
     if (check_guided_table(e, who, a, cfg_host, n_grid - 1, stages, rule)) return 2;
     if (reuse_call && check_reuse_flags(who, cfg_host, reuse_host, (n_grid - 1) * stages)) return 2;
     if (reuse_call && ensure_delta(e)) return 1;
+    if (project) {
+        if (check_project(who, project->form, project->par[0], project->par[1], project->par[2])) return 2;
+        LT_REQUIRE(project->zero_init >= 0 && project->zero_init < n_grid - 1, "%s: zero_init %d leaves no interval of the %d to integrate "
+                   "(0 .. n_grid - 2)", who, project->zero_init, n_grid - 1);
+        LT_REQUIRE(project->form == LT_PROJECT_ZERO_STAR || project->zero_init == 0, "%s: zero_init %d belongs to CFG-Zero* (form %d), not to "
+                   "APG", who, project->zero_init, LT_PROJECT_ZERO_STAR);
+        if (ensure_project(e)) return 1;
+    }
     if (slg) {
         for (int i = 0; i < (n_grid - 1) * stages; ++i)
             LT_REQUIRE(std::isfinite(slg->table[i]), "%s: the skip-layer scale of stage %d of interval %d is not finite", who, i % stages, i / stages);
@@ -473,7 +519,8 @@ int sample_cfg_table(lt_engine* e, const char* who, const void* z_dev, void* tra
         if (ensure_skip_buf(e)) return 1;
     }
     const long long n = (long long)a->batch * e->cfg.in_channels * a->latent_h * a->latent_w;
-    const CfgSchedule cs{cfg_host, rule, reuse_host, slg};
+    const CfgSchedule cs{cfg_host, rule, reuse_host, slg, project};
+    ProjectScope form_scope(e, project ? project->form : 0);
     return ode_fixed_grid(e, z_dev, traj_dev, final_dev, tgrid_host, n_grid, method, 1, t_round, a, s, n, nullptr, nullptr, &cs);
 }
 
@@ -508,6 +555,54 @@ extern "C" int lt_forward_cfg_rule(lt_engine* e, const void* x_dev, const float*
     if (check_guided_halves(e, who, a)) return 2;
     if (launch_guidance_params_store(e->g_cfg, a->cfg_scale, rescale, norm_limit, (hipStream_t)stream)) return 1;
     return forward_graphed(e, x_dev, t_dev, out_dev, a, 1, (hipStream_t)stream, {LT_KIND_RULE, nullptr, e->g_cfg});
+}
+
+// ---- projected guidance: APG and CFG-Zero*, the forms that need inner products of the two predictions ------------------------
+extern "C" int lt_sample_ode_cfg_project(lt_engine* e, const void* z_dev, void* traj_dev, void* final_dev, const float* tgrid_host, int32_t n_grid,
+                                         int32_t method, const float* cfg_host, int32_t form, float eta, float momentum, float norm_threshold,
+                                         int32_t zero_init, int32_t t_round, const lt_step_args* a, void* stream) {
+    const ProjectCall pr{form, {eta, momentum, norm_threshold}, zero_init};
+    return sample_cfg_table(e, "lt_sample_ode_cfg_project", z_dev, traj_dev, final_dev, tgrid_host, n_grid, method, cfg_host, nullptr, t_round, a,
+                            (hipStream_t)stream, nullptr, false, nullptr, &pr);
+}
+
+// One guided evaluation under a projected form, at a->cfg_scale.  The four parameters reach the engine's fixed device words through a launch
+// in front of the evaluation (the scale from there into e->g_cfg[0], as every device scale travels).  keep_momentum: 0 zeroes APG's momentum
+// first, 1 continues from the stored one - which must be of this call's shape.
+extern "C" int lt_forward_cfg_project(lt_engine* e, const void* x_dev, const float* t_dev, void* out_dev, int32_t form, float eta, float momentum,
+                                      float norm_threshold, int32_t keep_momentum, const lt_step_args* a, void* stream) {
+    const char* who = "lt_forward_cfg_project";
+    hipStream_t s = (hipStream_t)stream;
+    LT_REQUIRE(e && x_dev && t_dev && out_dev && a, "%s: null argument", who);
+    if (refuse_if_capturing(s, who)) return 2;  // (the first call allocates the buffers)
+    LtOptScope opt_scope(&e->opts);
+    if (check_step_shape(e, who, a)) return 2;
+    LT_REQUIRE(std::isfinite(a->cfg_scale), "%s: the scale is not finite", who);
+    if (check_project(who, form, eta, momentum, norm_threshold)) return 2;
+    LT_REQUIRE(keep_momentum == 0 || keep_momentum == 1, "%s: keep_momentum %d is not 0 (start from zero) or 1 (continue)", who, keep_momentum);
+    LT_REQUIRE(form == LT_PROJECT_APG || keep_momentum == 0, "%s: keep_momentum belongs to APG; CFG-Zero* carries no momentum", who);
+    if (check_guided_halves(e, who, a)) return 2;
+    int want[4];
+    Trajectory::delta_sig_of(e, a, want);
+    if (keep_momentum) {
+        const int* have = e->proj_sig;
+        LT_REQUIRE(have[0] != 0, "%s: no stored momentum to continue from: no projected APG evaluation was made, or lt_prepare_prompt / "
+                   "lt_prepare_labels was called since", who);
+        LT_REQUIRE(have[0] == want[0] && have[1] == want[1] && have[2] == want[2] && have[3] == want[3],
+                   "%s: the stored momentum is of another shape: %d samples of %d channels at %dx%d, the call has %d samples of %d channels at "
+                   "%dx%d", who, have[0], have[3], have[1], have[2], want[0], want[3], want[1], want[2]);
+    }
+    if (ensure_project(e)) return 1;
+    if (form != LT_PROJECT_APG) { eta = 1.f; momentum = 0.f; norm_threshold = INFINITY; }  // (not read; the words hold no leftovers)
+    if (launch_guidance_project_params_store(e->p_par, a->cfg_scale, eta, momentum, norm_threshold, s)) return 1;
+    if (form == LT_PROJECT_APG) {
+        e->proj_sig[0] = 0;  // (until the evaluation that rewrites it has been issued whole)
+        if (!keep_momentum) LT_CHECK_HIP(hipMemsetAsync(e->p_mom, 0, (size_t)want[0] * want[3] * want[1] * want[2] * sizeof(float), s));
+    }
+    ProjectScope form_scope(e, form);
+    if (int rc = forward_graphed(e, x_dev, t_dev, out_dev, a, 1, s, {LT_KIND_RULE, nullptr, e->p_par})) return rc;
+    if (form == LT_PROJECT_APG) Trajectory::delta_sig_of(e, a, e->proj_sig);
+    return 0;
 }
 
 // ---- guidance reuse: the cond - uncond difference taken on refresh stages, reused on half-row stages in between ----------------

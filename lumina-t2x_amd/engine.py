@@ -687,6 +687,70 @@ class DiTEngine:
         _lib.check(rc, "lt_forward_cfg_rule")
         return out
 
+    # ---- projected guidance: APG and CFG-Zero*  -------------
+    @staticmethod
+    def _project(apg, zero_star, zero_init, what: str, n_grid=None):
+        from .transport.guidance import check_project
+        try:
+            form, eta, beta, r, zero_init = check_project(apg, zero_star, zero_init, n_grid=n_grid)
+        except ValueError as exc:
+            raise LuminaLibError(f"{what}: {exc}") from None
+        if form is None:
+            raise LuminaLibError(f"{what}: needs a projected form - apg=dict(eta=, momentum=, norm_threshold=) or zero_star=True")
+        return _lib.PROJECT_FORMS[form], eta, beta, r, zero_init
+
+    def sample_ode_cfg_project(self, z: torch.Tensor, tgrid, table, method: str, *, apg=None, zero_star: bool = False, zero_init: int = 0,
+                               scale_factor: float = 1.0, scale_watershed: float = 1.0, base_seqlen: Optional[int] = None,
+                               proportional_attn: bool = False, t_round_to_state_dtype: bool = True, return_trajectory: bool = True,
+                               ntk_factor: float = 1.0, cfg_scale=None) -> torch.Tensor:
+        """``sample_ode_cfg_schedule`` whose guided stages form their output by ``transport.guidance.guided_project``
+        (lt_sample_ode_cfg_project): ``apg=dict(eta=, momentum=, norm_threshold=)`` - the update ``c - u`` with momentum, a norm clip and its
+        part parallel to ``c`` damped by ``eta`` - or ``zero_star=True`` - the unconditional row rescaled by ``<c, u> / <u, u>``, with
+        ``zero_init`` grid intervals of zero velocity at the start, for which nothing is evaluated.  Stages at scale 1 exactly are
+        conditional-only.  ``transport.guidance.sample_cfg_project`` is the definition."""
+        if isinstance(z, (list, tuple)):
+            raise LuminaLibError("sample_ode_cfg_project: a packed batch (a list of latents) is not served")
+        _require_gpu(z, "z")
+        if method not in _lib.ODE_METHODS:
+            raise LuminaLibError(f"sample_ode_cfg_project: projected guidance is built for the fixed-grid methods {sorted(_lib.ODE_METHODS)}, "
+                                 f"not '{method}'")
+        z = z.contiguous()
+        garr, n = _grid_array(tgrid)
+        form, eta, beta, r, zero_init = self._project(apg, zero_star, zero_init, "sample_ode_cfg_project", n_grid=n)
+        tab = table if isinstance(table, torch.Tensor) else torch.tensor(list(table), dtype=torch.float32)
+        tab = tab.detach().to("cpu", torch.float32).reshape(-1).contiguous()
+        stages = {"euler": 1, "midpoint": 2, "rk4": 4}[method]
+        if tab.numel() != max(n - 1, 0) * stages:
+            raise LuminaLibError(f"sample_ode_cfg_project: the table has {tab.numel()} entries, a {n}-point {method} grid has "
+                                 f"{max(n - 1, 0) * stages} stages")
+        a = self._step_args(z, 0.0, scale_factor, scale_watershed, base_seqlen, proportional_attn, ntk_factor=ntk_factor)
+        out, traj_ptr, fin_ptr = _traj_or_final(z, max(n, 1), z.shape, return_trajectory)
+        with torch.cuda.device(self.device):
+            rc = self.lib.lt_sample_ode_cfg_project(self.handle, C.c_void_p(z.data_ptr()), traj_ptr, fin_ptr, garr, n, _lib.ODE_METHODS[method],
+                                                    C.cast(tab.data_ptr(), C.POINTER(C.c_float)), form, eta, beta, r, zero_init,
+                                                    int(t_round_to_state_dtype), C.byref(a), C.c_void_p(_stream_ptr(self.device)))
+        _lib.check(rc, "lt_sample_ode_cfg_project")
+        return out
+
+    def forward_cfg_project(self, x: torch.Tensor, t: torch.Tensor, *, cfg_scale: float, apg=None, zero_star: bool = False,
+                            keep_momentum: bool = False, scale_factor: float = 1.0, scale_watershed: float = 1.0,
+                            base_seqlen: Optional[int] = None, proportional_attn: bool = False, ntk_factor: float = 1.0) -> torch.Tensor:
+        """one guided evaluation at ``cfg_scale`` under a projected form (lt_forward_cfg_project): ``guided_project`` on the model's output of
+        all rows.  ``keep_momentum`` (APG): continue from the momentum the last projected evaluation of this shape left, instead of zero."""
+        if isinstance(x, (list, tuple)):
+            raise LuminaLibError("forward_cfg_project: a packed batch (a list of latents) is not served")
+        _require_gpu(x, "x")
+        form, eta, beta, r, _ = self._project(apg, zero_star, 0, "forward_cfg_project")
+        x = x.contiguous()
+        t32 = t.to(device=x.device, dtype=torch.float32).contiguous()
+        out = torch.empty_like(x)
+        a = self._step_args(x, cfg_scale, scale_factor, scale_watershed, base_seqlen, proportional_attn, ntk_factor=ntk_factor)
+        with torch.cuda.device(self.device):
+            rc = self.lib.lt_forward_cfg_project(self.handle, C.c_void_p(x.data_ptr()), C.c_void_p(t32.data_ptr()), C.c_void_p(out.data_ptr()),
+                                                 form, eta, beta, r, int(bool(keep_momentum)), C.byref(a), C.c_void_p(_stream_ptr(self.device)))
+        _lib.check(rc, "lt_forward_cfg_project")
+        return out
+
     # ---- guidance reuse: the cond - uncond difference taken on refresh stages, reused on half-row stages (DESIGN 7k) -------------
     @staticmethod
     def _reuse_tables(table, reuse, count: int, what: str):

@@ -95,12 +95,19 @@ class EngineSamplers:
         return eng.sample_ode_masked(x, tgrid, mask, x1, noise, method, use_cfg=use_cfg, t_round_to_state_dtype=t_round, **args)
 
     def _engine_sample_ode_cfg_schedule(self, x, tgrid, method, t_round, table, kw, return_trajectory=True, rescale=0.0, norm_limit=math.inf,
-                                        reuse=None, slg=None, slg_layers=(), pag=None, pag_layers=()):
+                                        reuse=None, slg=None, slg_layers=(), pag=None, pag_layers=(), apg=None, zero_star=False, zero_init=0):
         """kwargs of forward_with_cfg -> lt_sample_ode_cfg_schedule (guidance schedules; ``cfg_scale`` in kw is ignored), or - with a
         rescale blend or a norm limit - lt_sample_ode_cfg_rule, or - with a reuse table - lt_sample_ode_cfg_reuse, or -
         with a table of skip-layer scales - lt_sample_ode_cfg_slg, or - with a table of perturbed-attention scales -
-        lt_sample_ode_cfg_pag (``slg_layers`` then join the same third prediction)"""
-        from ..transport.guidance import refuse_rule_with_reuse, refuse_with_pag, refuse_with_slg, rule_is_off
+        lt_sample_ode_cfg_pag (``slg_layers`` then join the same third prediction), or - with ``apg`` / ``zero_star`` -
+        lt_sample_ode_cfg_project"""
+        from ..transport.guidance import check_project, refuse_rule_with_reuse, refuse_with_pag, refuse_with_project, refuse_with_slg, rule_is_off
+        try:
+            form = check_project(apg, zero_star, zero_init)[0]
+            refuse_with_project(form, method=method, rescale=rescale, norm_limit=norm_limit, reuse=reuse, slg=slg, pag=pag,
+                                packed=not isinstance(x, torch.Tensor))
+        except ValueError as exc:
+            raise _lib.LuminaLibError(str(exc)) from None
         if pag is not None:
             if not isinstance(x, torch.Tensor):
                 raise _lib.LuminaLibError("perturbed-attention guidance: a packed batch (a list of latents) is not served")
@@ -125,6 +132,9 @@ class EngineSamplers:
         kw.setdefault("cfg_scale", 1.0)
         eng, args = self._engine_sampler_args(x, True, kw)
         args.pop("cfg_scale", None)
+        if form is not None:
+            return eng.sample_ode_cfg_project(x, tgrid, table, method, apg=apg, zero_star=zero_star, zero_init=zero_init,
+                                              t_round_to_state_dtype=t_round, return_trajectory=return_trajectory, **args)
         if pag is not None:
             return eng.sample_ode_cfg_pag(x, tgrid, table, pag, pag_layers, method, skip_layers=slg_layers, t_round_to_state_dtype=t_round,
                                           return_trajectory=return_trajectory, **args)
@@ -148,7 +158,8 @@ class EngineSamplers:
 
     @torch.no_grad()
     def sample_ode_cfg_schedule(self, z, tgrid, table, *cond, method: str = "midpoint", return_trajectory: bool = False, rescale: float = 0.0,
-                                norm_limit: float = math.inf, reuse=None, slg=None, slg_layers=(), pag=None, pag_layers=(), **step_kw):
+                                norm_limit: float = math.inf, reuse=None, slg=None, slg_layers=(), pag=None, pag_layers=(), apg=None,
+                                zero_star: bool = False, zero_init: int = 0, **step_kw):
         """A guided fixed-grid trajectory with a scale per stage in ONE engine call (lt_sample_ode_cfg_schedule): stage k of interval
         i evaluates ``forward_with_cfg`` at ``table[i * stages + k]``, or - at scale 1 exactly - the plain forward of the cond rows alone, at
         half the rows.  ``cond``: the family's conditioning as ``forward_with_cfg`` takes it (``cap_feats, cap_mask`` or ``y``) for all
@@ -164,6 +175,10 @@ class EngineSamplers:
         ``pag`` (one perturbed-attention scale per table entry; ``transport.guidance.pag_table``) with ``pag_layers``: the third prediction
         runs those blocks with the identity as their self-attention map - and ``slg_layers``, if given, left out - under the one table
         (lt_sample_ode_cfg_pag; an ``slg`` table beside a ``pag`` table is refused by name).
+        ``apg=dict(eta=, momentum=, norm_threshold=)`` or ``zero_star=True`` (with ``zero_init=K``): the guided stages form their output by
+        ``transport.guidance.guided_project`` - APG's momentum / norm clip / damped parallel part, or CFG-Zero*'s rescaled unconditional row
+        with ``K`` intervals of zero velocity that evaluate nothing (lt_sample_ode_cfg_project; euler / midpoint / rk4; exclusive,
+        and refused by name together with any of the companions above).
         Returns the last state, or all ``len(tgrid)`` states."""
         if len(cond) > len(self._cond_names):
             raise TypeError(f"sample_ode_cfg_schedule takes the conditioning {self._cond_names}, got {len(cond)} positional arguments")
@@ -171,7 +186,7 @@ class EngineSamplers:
         self._mirror_attention_flags(kw)
         return self._engine_sample_ode_cfg_schedule(z, tgrid, method, True, table, kw, return_trajectory=return_trajectory, rescale=rescale,
                                                     norm_limit=norm_limit, reuse=reuse, slg=slg, slg_layers=slg_layers, pag=pag,
-                                                    pag_layers=pag_layers)
+                                                    pag_layers=pag_layers, apg=apg, zero_star=zero_star, zero_init=zero_init)
 
     @torch.no_grad()
     def sample_ode_teacache(self, z, tgrid, *cond, method: str = "euler", threshold: float = 0.0, coefficients=(0.0, 0.0, 0.0, 1.0, 0.0),
@@ -299,6 +314,34 @@ class EngineSamplers:
         self._mirror_attention_flags(kw)
         eng, args = self._engine_sampler_args(x, True, kw)
         return eng.forward_cfg_rule(x, t, rescale=rescale, norm_limit=norm_limit, **args)
+
+    @torch.no_grad()
+    def forward_with_cfg_project(self, x, t, *cond, apg=None, zero_star: bool = False, keep_momentum: bool = False, **step_kw):
+        """``forward_with_cfg(x, t, <conditioning>, cfg_scale, **step_kw)`` under a projected form in ONE engine call (lt_forward_cfg_project,
+        DESIGN 7q): ``transport.guidance.guided_project`` on the model's output of all rows.  ``cond``: the conditioning, then ``cfg_scale`` (or
+        ``cfg_scale=`` by keyword).  ``keep_momentum`` (APG): continue from the momentum the last projected evaluation left - refused by name
+        when none of this shape is stored, or the conditioning was prepared anew since.  With neither form the call is ``forward_with_cfg``.
+        Tensor states only."""
+        from ..transport.guidance import check_project
+        if not isinstance(x, torch.Tensor):
+            raise _lib.LuminaLibError("forward_with_cfg_project: a packed batch (a list of latents) is not served by projected guidance")
+        names = self._cond_names + ("cfg_scale",)
+        if len(cond) > len(names):
+            raise TypeError(f"forward_with_cfg_project takes {names}, got {len(cond)} positional arguments")
+        kw = dict(zip(names, cond), **step_kw)
+        try:
+            form = check_project(apg, zero_star)[0]
+        except ValueError as exc:
+            raise _lib.LuminaLibError(f"forward_with_cfg_project: {exc}") from None
+        if form is None:
+            if keep_momentum:
+                raise _lib.LuminaLibError("forward_with_cfg_project: keep_momentum belongs to APG (apg=dict(...))")
+            return self.forward_with_cfg(x, t, **kw)
+        if "cfg_scale" not in kw:
+            raise TypeError("forward_with_cfg_project needs cfg_scale")
+        self._mirror_attention_flags(kw)
+        eng, args = self._engine_sampler_args(x, True, kw)
+        return eng.forward_cfg_project(x, t, apg=apg, zero_star=zero_star, keep_momentum=keep_momentum, **args)
 
     @torch.no_grad()
     def forward_with_cfg_reuse(self, x, t, *cond, reuse: bool = False, **step_kw):

@@ -176,7 +176,13 @@ def run(args, *, encode_fn=None, cap_feat_dim=None, decode_fn=None, model=None) 
         pag = guidance_pag(args, sample_fn.__self__.t)
         slg = None if pag is not None else guidance_slg(args, sample_fn.__self__.t)
         tea = step_cache(args)
-        if pag is not None:  # a third evaluation of the prompt row with some blocks' self-attention map replaced by the identity
+        proj = guidance_project(args)
+        if proj:  # APG / CFG-Zero*: the guided stages built on inner products of the two rows; combines with the scale table alone
+            if rule or reuse is not None or pag is not None or slg is not None or tea:
+                raise SystemExit("--apg_* / --cfg_zero_star are not served together with --cfg_rescale / --cfg_norm_limit, --cfg_reuse*, "
+                                 "--slg_*, --pag_* or --teacache")
+            latent = sample_fn(z, model.forward_with_cfg, cfg_table=table, **proj, **kw)[-1][:1]
+        elif pag is not None:  # a third evaluation of the prompt row with some blocks' self-attention map replaced by the identity
             if tea:
                 raise SystemExit("--pag_layers is not served together with --teacache")
             if table is None:
@@ -235,6 +241,27 @@ def guidance_rule(args) -> dict:
     from .transport import guidance
     rescale, limit = guidance.check_rule(rescale, limit)
     return dict(cfg_rescale=rescale, cfg_norm_limit=limit)
+
+
+def guidance_project(args) -> dict:
+    """``--apg_eta`` / ``--apg_momentum`` / ``--apg_norm_threshold`` or ``--cfg_zero_star`` / ``--cfg_zero_init K`` as the sampler's keyword
+    arguments; empty at the defaults: the call it was.  The two forms are exclusive, and built for euler / midpoint / rk4."""
+    eta, beta, r = getattr(args, "apg_eta", None), getattr(args, "apg_momentum", None), getattr(args, "apg_norm_threshold", None)
+    zero, K = bool(getattr(args, "cfg_zero_star", False)), int(getattr(args, "cfg_zero_init", 0) or 0)
+    apg = None
+    if eta is not None or beta is not None or r is not None:
+        apg = dict(eta=1.0 if eta is None else eta, momentum=0.0 if beta is None else beta, norm_threshold=math.inf if r is None else r)
+    if apg is None and not zero and K == 0:
+        return {}
+    from .transport import guidance
+    try:
+        form, eta, beta, r, K = guidance.check_project(apg, zero, K)
+        guidance.refuse_with_project(form, args.sampling_method)
+    except ValueError as exc:
+        raise SystemExit(f"--apg_* / --cfg_zero_*: {exc}") from None
+    if form == "apg":
+        return dict(cfg_apg=dict(eta=eta, momentum=beta, norm_threshold=r))
+    return dict(cfg_zero_star=True, cfg_zero_init=K)
 
 
 def guidance_reuse(args, tgrid, table):
@@ -347,6 +374,17 @@ def build_parser() -> argparse.ArgumentParser:
                    help="guidance rescale: blend PHI in [0, 1] of the guided output's std towards the prompt row's (0: off)")
     p.add_argument("--cfg_norm_limit", type=float, default=None, metavar="R",
                    help="cap the guided output's L2 norm per sample at R times the prompt row's (default: no limit)")
+    p.add_argument("--apg_eta", type=float, default=None, metavar="ETA",
+                   help="adaptive projected guidance (APG): the part of the guidance update parallel to the prompt row's output is scaled by "
+                        "ETA (0 drops it, 1 keeps it; any --apg_* option switches APG on)")
+    p.add_argument("--apg_momentum", type=float, default=None, metavar="BETA",
+                   help="... the update carries BETA times the previous guided stage's update, |BETA| < 1 (the paper uses negative values)")
+    p.add_argument("--apg_norm_threshold", type=float, default=None, metavar="R",
+                   help="... and its L2 norm per sample is clipped to R (default: no clip)")
+    p.add_argument("--cfg_zero_star", action="store_true",
+                   help="CFG-Zero*: rescale the negative row's output by <prompt row, negative row> / |negative row|^2 before guidance")
+    p.add_argument("--cfg_zero_init", type=int, default=0, metavar="K",
+                   help="... and take zero velocity on the first K steps, which then evaluate nothing (needs --cfg_zero_star)")
     p.add_argument("--cfg_reuse", type=int, default=0, metavar="K",
                    help="take the guidance difference (prompt row - negative row) on every K-th guided stage and reuse it on the stages in "
                         "between, which then evaluate the prompt row alone (0: off)")

@@ -35,7 +35,11 @@ the definition ``lt_sample_ode_cfg_slg`` is held to, ``slg_table`` builds the ta
 
 Perturbed-attention guidance takes the third prediction with a set of blocks PERTURBED - their self-attention map replaced by the
 identity, so every query's output is its own value row - and, if wanted, another set left out: ``sample_cfg_pag`` is the definition
-``lt_sample_ode_cfg_pag`` is held to, ``pag_table`` builds the table, and the chain of roundings is ``slg_combine`` unchanged."""
+``lt_sample_ode_cfg_pag`` is held to, ``pag_table`` builds the table, and the chain of roundings is ``slg_combine`` unchanged.
+
+Projected guidance replaces the guided expression by one built on inner products of the two predictions - APG's
+momentum / norm-clip / projection, CFG-Zero*'s rescaled unconditional row and zero-init: ``guided_project`` is the form, ``sample_cfg_project`` the
+loop ``lt_sample_ode_cfg_project`` is held to, ``check_project`` / ``refuse_with_project`` refuse what the engine refuses."""
 from __future__ import annotations
 
 import math
@@ -844,3 +848,240 @@ def sample_cfg_pag(model, z, tgrid, table, pag, pag_layers, skip_layers=(), meth
         out[j + 1] = y
     assert call[0] == (len(t) - 1) * stages
     return out
+
+
+# ---- projected guidance: APG and CFG-Zero*, the forms that need inner products of the two predictions ---------------------------
+PROJECT_FORMS = {"apg": 1, "zero_star": 2}  # LT_PROJECT_APG / LT_PROJECT_ZERO_STAR
+
+
+def _f32(v):
+    return float(th.tensor(float(v), dtype=th.float32))
+
+
+def check_project(apg=None, zero_star=False, zero_init=0, n_grid=None):
+    """``(form, eta, momentum, norm_threshold, zero_init)``: ``form`` None (off: neither given), ``"apg"`` or ``"zero_star"``; the three
+    parameters as the fp32 values the engine reads, as Python floats.  ``apg``: a dict with any of ``eta`` (default 1), ``momentum``
+    (default 0), ``norm_threshold`` (default inf: off).  Refused: both forms at once; an unknown key; ``eta`` not finite; ``|momentum| >= 1``;
+    ``norm_threshold`` not above 0; ``zero_init`` without ``zero_star``, negative, no integer, or - when the grid is known - ``>= n_grid - 1``."""
+    if isinstance(zero_init, bool) or int(zero_init) != zero_init:
+        raise ValueError(f"zero_init {zero_init!r} is not an integer count of grid intervals")
+    zero_init = int(zero_init)
+    if zero_init < 0:
+        raise ValueError(f"zero_init {zero_init} is negative")
+    if apg is not None and zero_star:
+        raise ValueError("APG (apg=...) and CFG-Zero* (zero_star) are exclusive: one projected form per call")
+    if zero_init and not zero_star:
+        raise ValueError(f"zero_init {zero_init} belongs to CFG-Zero* (zero_star=True)")
+    if n_grid is not None and zero_init >= n_grid - 1 and zero_init:
+        raise ValueError(f"zero_init {zero_init} leaves no interval of the {n_grid - 1} to integrate")
+    if apg is None:
+        return ("zero_star" if zero_star else None), 1.0, 0.0, math.inf, zero_init
+    apg = dict(apg)
+    unknown = sorted(set(apg) - {"eta", "momentum", "norm_threshold"})
+    if unknown:
+        raise ValueError(f"apg takes eta, momentum and norm_threshold, not {unknown}")
+    eta, beta, r = float(apg.get("eta", 1.0)), float(apg.get("momentum", 0.0)), float(apg.get("norm_threshold", math.inf))
+    if not math.isfinite(eta):
+        raise ValueError(f"apg eta {eta} is not finite")
+    if not abs(beta) < 1.0:
+        raise ValueError(f"apg momentum {beta} is not inside (-1, 1)")
+    if math.isnan(r) or not r > 0.0:
+        raise ValueError(f"apg norm_threshold {r} is not above 0 (inf switches the clip off)")
+    eta, beta, r = _f32(eta), _f32(beta), _f32(r)
+    if not abs(beta) < 1.0:  # (a value that rounds to 1 in fp32)
+        raise ValueError(f"apg momentum {beta} is not inside (-1, 1) as an fp32 value")
+    return "apg", eta, beta, r, zero_init
+
+
+def refuse_with_project(form, method="euler", rescale=0.0, norm_limit=math.inf, reuse=None, slg=None, pag=None, teacache=None, mask=None,
+                        packed=False):
+    """what a projected form is not served with, by name: a rescale / norm-limit rule, a reuse table, skip-layer and perturbed-attention
+    guidance, step caching, an inpainting mask, a packed batch, and a method that is not fixed-grid - the multistep solvers (zero velocity and
+    the slope ring are not defined together) and the adaptive ones"""
+    if form is None:
+        return
+    what = "projected guidance (APG)" if form == "apg" else "projected guidance (CFG-Zero*)"
+    if packed:
+        raise ValueError(f"{what}: a packed batch (a list of latents) is not served")
+    if method not in FIXED_GRID_METHODS:
+        raise ValueError(f"{what} is built for the fixed-grid methods {', '.join(FIXED_GRID_METHODS)}, not '{method}'")
+    if not rule_is_off(rescale, norm_limit):
+        raise ValueError(f"{what} together with a rescale / norm_limit rule is not served")
+    for name, v in (("guidance reuse (a reuse table)", reuse), ("skip-layer guidance (an slg table)", slg),
+                    ("perturbed-attention guidance (a pag table)", pag), ("step caching (teacache)", teacache), ("an inpainting mask", mask)):
+        if v is not None:
+            raise ValueError(f"{what} together with {name} is not served")
+
+
+def apg_coefficients(Smm, Smc, Scc, w, eta, norm_threshold):
+    """``(a, b, tn, p)`` of one sample from its three float64 sums: float64 arithmetic operation by operation (Python floats: no fused
+    multiply-add), ``a`` and ``b`` each rounded once to fp32"""
+    tn = min(1.0, norm_threshold / math.sqrt(Smm)) if (norm_threshold < math.inf and Smm > 0.0) else 1.0
+    p = tn * Smc / Scc if Scc > 0.0 else 0.0
+    w1 = w - 1.0
+    return _f32(w1 * tn), _f32(w1 * (eta - 1.0) * p), tn, p
+
+
+def guided_project(o, w, ch, form, *, eta=1.0, momentum=0.0, norm_threshold=math.inf, m_prev=None, sums=None, parts=None):
+    """A projected form at scale ``w`` on a model output ``o [B, C, H, W]`` (cond rows ``c``, then uncond rows ``u``; taken as bf16, returned in
+    its own dtype): ``(out, coef, m)``.  Sums run over a sample's ``ch H W`` guided elements in float64; the coefficients are float64 scalar
+    arithmetic, each rounded once to fp32; every tensor operation rounds on its own.  ``w`` and the parameters are taken as fp32 values.
+
+    ``form="apg"`` (Sadat et al. 2024): ``d = bf16(c - u)``; ``m = d + momentum * m_prev`` in fp32 (``m_prev [B / 2, ch, H, W]``, None: zeros)
+    is the returned state; ``tn = min(1, r / |m|)``, ``p = tn <m, c> / <c, c>``, ``a = fp32((w - 1) tn)``, ``b = fp32((w - 1)(eta - 1) p)``
+    (``apg_coefficients``); ``g = bf16(c + (a m + b c))``.  This is ``c + (w - 1)(orth + eta par)`` of the published algorithm with
+    ``par = (<m', c> / <c, c>) c`` and ``m' = tn m`` - the projection is taken on the model's VELOCITY output, where the paper takes it on the
+    denoised prediction; for this family's linear path the two differ by a multiple of the state, and the velocity is what the engine holds.
+    With ``eta = 1, momentum = 0, r = inf`` it is ``c + (w - 1)(c - u)``: plain guidance in another rounding chain - NOT the words of
+    ``forward_with_cfg`` / lt_forward_cfg, which form ``u + w (c - u)`` in bf16 steps.
+    ``form="zero_star"`` (Fan et al. 2025): ``s = fp32(<c, u> / <u, u>)`` (1 where ``<u, u>`` is 0); ``g = bf16(s u + w (c - s u))``; ``m`` is None.
+
+    ``g`` goes to both halves; the channels past ``ch`` pass through row by row.  ``coef``: fp32 ``[B / 2, 2]`` (a, b), or ``[B / 2]`` s, on
+    ``o``'s device.  ``sums`` (a list of per-sample tuples - (Smm, Smc, Scc) or (Scu, Suu)): taken in place of the reductions here;
+    ``parts`` (a list): receives per sample ``(Smm, Smc, Scc, tn, p)`` or ``(Scu, Suu)``."""
+    if form not in PROJECT_FORMS:
+        raise ValueError(f"projected form {form!r} is not one of {sorted(PROJECT_FORMS)}")
+    B = o.size(0)
+    if B % 2:
+        raise ValueError(f"guidance needs an even batch (cond + uncond rows), got {B}")
+    half = B // 2
+    ch = min(int(ch), o.size(1))
+    dtype = o.dtype
+    w = _f32(w)
+    o = o.to(th.bfloat16)  # the model's output is bf16 (an engine-backed model hands an fp32 state the same values in fp32)
+    c, u = o[:half, :ch], o[half:, :ch]
+    cf = c.float()
+    if form == "apg":
+        _, eta, beta, r, _ = check_project(dict(eta=eta, momentum=momentum, norm_threshold=norm_threshold))
+        d = c - u
+        m_prev = th.zeros(d.shape, dtype=th.float32, device=o.device) if m_prev is None else m_prev.to(o.device, th.float32)
+        m = d.float() + beta * m_prev  # (from zeros too: the same two operations, so the same signed zeros)
+        if sums is None:
+            md, cd = m.double().reshape(half, -1), c.double().reshape(half, -1)
+            sums = th.stack([(md * md).sum(1), (md * cd).sum(1), (cd * cd).sum(1)], dim=1).tolist()
+        coef = []
+        for Smm, Smc, Scc in sums:
+            a, b, tn, p = apg_coefficients(Smm, Smc, Scc, w, eta, r)
+            coef.append((a, b))
+            if parts is not None:
+                parts.append((Smm, Smc, Scc, tn, p))
+        coef = th.tensor(coef, dtype=th.float32, device=o.device).reshape(half, 2)
+        a, b = coef[:, 0].view(-1, 1, 1, 1), coef[:, 1].view(-1, 1, 1, 1)
+        gg = (cf + (a * m + b * cf)).to(th.bfloat16)
+    else:
+        m = None
+        if sums is None:
+            cd, ud = c.double().reshape(half, -1), u.double().reshape(half, -1)
+            sums = th.stack([(cd * ud).sum(1), (ud * ud).sum(1)], dim=1).tolist()
+        coef = []
+        for Scu, Suu in sums:
+            coef.append(_f32(Scu / Suu if Suu > 0.0 else 1.0))
+            if parts is not None:
+                parts.append((Scu, Suu))
+        coef = th.tensor(coef, dtype=th.float32, device=o.device)
+        su = coef.view(-1, 1, 1, 1) * u.float()
+        gg = (su + w * (cf - su)).to(th.bfloat16)
+    out = th.cat([th.cat([gg, o[:half, ch:]], 1), th.cat([gg, o[half:, ch:]], 1)])
+    return out.to(dtype), coef, m
+
+
+def sample_cfg_project(model, z, tgrid, table, method="euler", *, apg=None, zero_star=False, zero_init=0, cond=None, t_round=True,
+                       factors=None, parts=None, calls=None, **kw):
+    """``sample_cfg_schedule`` whose stages at a scale other than 1 run ``guided_project`` on ``model.forward`` of all ``B`` rows (both halves
+    of the input are the first half, as ``forward_with_cfg`` makes them); a stage at scale 1 exactly is the conditional-only stage and leaves
+    the momentum alone.  This IS the definition ``lt_sample_ode_cfg_project`` is held to, state for state.  APG's momentum is zero at the start
+    of the call and advances with every guided evaluation, in evaluation order (the stages of midpoint / rk4 count).  ``zero_init = K``
+    (CFG-Zero*): the first ``K`` grid intervals take zero velocity - the state is copied into their slots, the model is not called and their
+    table entries are not read.  ``factors`` (a list): receives the coefficient tensor of every guided stage, ``parts`` (a list) what
+    ``guided_project`` reports per sample; ``calls`` (a list): receives the number of model calls."""
+    stages = _check_method(method)
+    table = check_table(table, tgrid, method)
+    form, eta, beta, r, zero_init = check_project(apg, zero_star, zero_init, n_grid=len(_grid32(tgrid)))
+    if form is None:
+        raise ValueError("sample_cfg_project needs a projected form: apg=dict(...) or zero_star=True")
+    B = z.size(0)
+    if B % 2:
+        raise ValueError(f"guidance needs an even batch (cond + uncond rows), got {B}")
+    kw = dict(kw)
+    kw.pop("cfg_scale", None)  # the table is the scale
+    refuse_with_project(form, method, kw.pop("rescale", 0.0), kw.pop("norm_limit", math.inf), kw.pop("reuse", None))
+    if cond is None:
+        cond = [k for k, v in kw.items() if isinstance(v, th.Tensor) and v.dim() >= 1 and v.shape[0] == B]
+    cond_kw = {k: kw.pop(k) for k in cond}
+    half_kw = {k: _cond_half(v, B) for k, v in cond_kw.items()}
+    ch = int(getattr(model, "cfg_channels", 3))
+    device = z.device
+    t = _grid32(tgrid).to(device)
+    w = table.tolist()
+    call = [zero_init * stages]
+    made = [0]
+    mom = [None]
+
+    def func(tt, y):
+        scale = w[call[0]]
+        call[0] += 1
+        made[0] += 1
+        tvec = th.ones(B).to(device) * tt  # fp32 [B] (reference integrators.py:108)
+        if scale != 1.0:
+            o = model.forward(th.cat([y[: B // 2]] * 2), tvec, **cond_kw)
+            out, coef, m = guided_project(o, scale, ch, form, eta=eta, momentum=beta, norm_threshold=r, m_prev=mom[0], parts=parts)
+            mom[0] = m
+            if factors is not None:
+                factors.append(coef)
+            return out.to(y.dtype)
+        o = model.forward(y[: B // 2], tvec[: B // 2], **half_kw)
+        return th.cat([o, o])
+
+    def f(tt, y):
+        return _call(func, tt, y) if t_round else func(tt, y)
+
+    # fixed_grid_odeint's loop (integrators.py), statement for statement - behind the intervals of zero velocity
+    out = th.empty((len(t),) + tuple(z.shape), dtype=z.dtype, device=device)
+    out[0] = z
+    y = z
+    third, two_thirds = 1.0 / 3.0, 2.0 / 3.0
+    for j in range(len(t) - 1):
+        if j < zero_init:  # y + dt * 0
+            out[j + 1] = y
+            continue
+        t0, t1 = t[j], t[j + 1]
+        dt = t1 - t0
+        k1 = f(t0, y)
+        if method == "euler":
+            dy = dt * k1
+        elif method == "midpoint":
+            half = 0.5 * dt
+            dy = dt * f(t0 + half, y + k1 * half)
+        else:
+            k2 = f(t0 + dt * third, y + dt * k1 * third)
+            k3 = f(t0 + dt * two_thirds, y + dt * (k2 - k1 * third))
+            k4 = f(t1, y + dt * (k1 - k2 + k3))
+            dy = (k1 + 3 * (k2 + k3) + k4) * dt * 0.125
+        y = y + dy
+        out[j + 1] = y
+    assert call[0] == (len(t) - 1) * stages and made[0] == (len(t) - 1 - zero_init) * stages
+    if calls is not None:
+        calls.append(made[0])
+    return out
+
+
+def sample_project_front(x, model, tgrid, method, table, model_kwargs, *, apg=None, zero_star=False, zero_init=0, t_round=True, use_engine=True,
+                         **companions):
+    """what ``ODE.sample`` / ``ode.sample`` do with ``cfg_apg=`` / ``cfg_zero_star=`` / ``cfg_zero_init=``: the refusals by name
+    (``companions``: the keyword arguments of ``refuse_with_project``), then ONE engine call for the bound ``forward_with_cfg`` of an
+    engine-backed model on a ROCm state, else the host loop ``sample_cfg_project``.  Without a table ``cfg_scale`` holds at every stage."""
+    from .integrators import _engine_target
+    if isinstance(x, tuple):
+        raise NotImplementedError("tuple states are not part of the sampling path of projected guidance")
+    form = check_project(apg, zero_star, zero_init, n_grid=len(_grid32(tgrid)))[0]
+    refuse_with_project(form, method, packed=isinstance(x, list), **companions)
+    if table is None:
+        table = cfg_table(tgrid, method, model_kwargs.get("cfg_scale", 1.0))
+    target = _engine_target(model)
+    if target is not None and target[1] and x.is_cuda and use_engine and hasattr(target[0], "_engine_sample_ode_cfg_schedule"):
+        return target[0]._engine_sample_ode_cfg_schedule(x, tgrid, method, t_round, table, dict(model_kwargs), apg=apg, zero_star=zero_star,
+                                                         zero_init=zero_init)
+    owner = getattr(model, "__self__", None)
+    if owner is None or getattr(model, "__name__", "") != "forward_with_cfg" or not hasattr(owner, "forward"):
+        raise TypeError("projected guidance needs the bound forward_with_cfg of a model that also has forward (every stage calls it)")
+    return sample_cfg_project(owner, x, tgrid, table, method, apg=apg, zero_star=zero_star, zero_init=zero_init, t_round=t_round, **model_kwargs)

@@ -397,7 +397,16 @@ class ode:
                                                  IDENTITY if coefficients is None else coefficients)
 
     def sample(self, x, model, cfg_table=None, cfg_rescale=0.0, cfg_norm_limit=math.inf, cfg_reuse=None, slg_table=None, slg_layers=(),
-               teacache=None, teacache_coefficients=None, pag_table=None, pag_layers=(), **model_kwargs):
+               teacache=None, teacache_coefficients=None, pag_table=None, pag_layers=(), cfg_apg=None, cfg_zero_star=False, cfg_zero_init=0,
+               **model_kwargs):
+        if cfg_apg is not None or cfg_zero_star or cfg_zero_init:  # projected guidance: its refusals come first, by name
+            from .guidance import sample_project_front
+            if not getattr(self.drift, "is_plain_velocity", False):
+                raise NotImplementedError("projected guidance is built for the plain velocity as drift")
+            return sample_project_front(x, model, self.t, self.sampler_type, cfg_table, model_kwargs, apg=cfg_apg, zero_star=cfg_zero_star,
+                                        zero_init=cfg_zero_init, t_round=self.t_round_to_state_dtype, use_engine=self.use_engine,
+                                        rescale=cfg_rescale, norm_limit=cfg_norm_limit, reuse=cfg_reuse, slg=slg_table, pag=pag_table,
+                                        teacache=teacache)
         if pag_table is not None:  # perturbed-attention guidance: its refusals come first, by name
             from .guidance import refuse_with_pag
             refuse_with_pag(pag_table, self.sampler_type, cfg_rescale, cfg_norm_limit, cfg_reuse, slg_table, teacache)

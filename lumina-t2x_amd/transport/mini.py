@@ -10,6 +10,8 @@ for an engine-backed callable, the host loop ``sample_masked`` otherwise.  ``sam
 (transport/multistep.py; not in the reference): one model evaluation per interval, one ``lt_sample_ode_multistep`` call or the host loop
 ``multistep_odeint``; with an inpainting mask they are refused by name.  ``cfg_reuse=`` (one 0 / 1 flag per evaluation, ``guidance.cfg_reuse_table``)
 is guidance reuse: one ``lt_sample_ode_cfg_reuse`` call or the host loop ``sample_cfg_reuse``; refused together with a rescale / norm limit.
+``cfg_apg=dict(eta=, momentum=, norm_threshold=)`` / ``cfg_zero_star=True`` (with ``cfg_zero_init=K``) are the projected forms of
+``guidance.guided_project``: one ``lt_sample_ode_cfg_project`` call or the host loop ``sample_cfg_project``.
 
 Not mirrored: ``use_sd3=True`` (drives a diffusers SD3Transformer2DModel, not a Lumina model - out of scope)."""
 from __future__ import annotations
@@ -120,9 +122,16 @@ class ODE:
                                t_round=self.t_round_to_state_dtype, **model_kwargs)
 
     def sample(self, x, model, mask=None, x1=None, noise=None, cfg_table=None, cfg_rescale=0.0, cfg_norm_limit=math.inf, cfg_reuse=None,
-               slg_table=None, slg_layers=(), teacache=None, teacache_coefficients=None, pag_table=None, pag_layers=(), **model_kwargs):
+               slg_table=None, slg_layers=(), teacache=None, teacache_coefficients=None, pag_table=None, pag_layers=(), cfg_apg=None,
+               cfg_zero_star=False, cfg_zero_init=0, **model_kwargs):
         if isinstance(x, tuple):
             raise NotImplementedError("tuple states are not part of the sampling path")
+        if cfg_apg is not None or cfg_zero_star or cfg_zero_init:  # projected guidance: its refusals come first, by name
+            from .guidance import sample_project_front
+            return sample_project_front(x, model, self.t, self.sampler_type, cfg_table, model_kwargs, apg=cfg_apg, zero_star=cfg_zero_star,
+                                        zero_init=cfg_zero_init, t_round=self.t_round_to_state_dtype, use_engine=self.use_engine,
+                                        rescale=cfg_rescale, norm_limit=cfg_norm_limit, reuse=cfg_reuse, slg=slg_table, pag=pag_table,
+                                        teacache=teacache, mask=next((m for m in (mask, x1, noise) if m is not None), None))
         if pag_table is not None:  # perturbed-attention guidance: its refusals come first, by name
             from .guidance import refuse_with_pag
             refuse_with_pag(pag_table, self.sampler_type, cfg_rescale, cfg_norm_limit, cfg_reuse, slg_table, teacache,
