@@ -2,7 +2,7 @@
 // euler / midpoint / rk4; with an inpainting mask; with a guidance scale per stage), multi-view (visual-anagram) sampling, the SDE loop and the
 // adaptive Runge-Kutta loop.  One call per trajectory, no
 // host<->device sync inside it (the adaptive loop reads one error ratio per attempted step).  All
-// are written against one scaffold - check_step_shape, StageTimes (engine.h), Trajectory - and a new sampler is too: what a sampler
+// are written against one scaffold - check_step_shape, StageTimes (engine.h), Trajectory, GuidancePlan (guidance_plan.h) - and a new sampler is too: what a sampler
 // owns is its stage-time fill loop and its stepping body, where the reference's rounding points are.
 #include <algorithm>
 #include <cmath>
@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "engine.h"
+#include "guidance_plan.h"
 #include "kernels.h"
 
 namespace {
@@ -30,48 +31,93 @@ int check_step_shape(const lt_engine* e, const char* who, const lt_step_args* a)
     return 0;
 }
 
-// Step caching (transport/cache.py: CacheController is the definition): the accumulator of one trajectory, in C++ doubles without
-// contraction.  step() takes the indicator sums of an evaluation that is neither the first nor the last and says whether the stack runs
-struct CacheControl {
-    double thr = 0.0, c[5] = {0, 0, 0, 1, 0}, acc = 0.0;
-    double* stats = nullptr;  // null, or ncalls x 3: rel, acc after the add, ran
-    bool step(double s1, double s0, double* rel_out) {
-#pragma clang fp contract(off)
-        if (s0 == 0.0) { *rel_out = INFINITY; return true; }  // (nothing to compare with: the stack runs, the accumulator takes nothing)
-        const double rel = s1 / s0;
-        double p = c[0];
-        for (int k = 1; k < 5; ++k) p = p * rel + c[k];
-        acc += p;
-        *rel_out = rel;
-        return !(acc < thr);
-    }
-};
+// masked sampling refuses the multistep methods by name, in front of the method range
+int refuse_masked_multistep(const char* who, int method) {
+    LT_REQUIRE(!(method >= LT_ODE_AB2 && method <= LT_ODE_ABM3), "%s: masked sampling with a multistep method (ab2, ab3, abm2, abm3) is refused: the blend "
+               "makes the state discontinuous, so the history's slopes no longer belong to it", who);
+    return 0;
+}
+// the grid and the method of a fixed-grid call, in this order; `note`: what the call adds to the method's refusal
+int check_grid_method(const char* who, int n_grid, int method, bool masked, const char* note) {
+    LT_REQUIRE(n_grid >= 2, "%s: need at least 2 grid points", who);
+    if (masked && refuse_masked_multistep(who, method)) return 2;
+    LT_REQUIRE(method >= LT_ODE_EULER && method <= LT_ODE_RK4, "%s: unknown method %d%s", who, method, note);
+    return 0;
+}
 
-// The state of one trajectory: the ping-pong pair e->ys, the caller's record of the states (if any), the evaluation and row counts.
+// ---- the buffers an evaluation stores for a later one (LtStoredBuffer, guidance_plan.h): the cond - uncond difference e->g_delta,
+// APG's momentum e->p_mom (7q), the block stack's residual e->c_r (7n).  Each has a signature in the engine, and one protocol, written here once
+int* stored_sig(lt_engine* e, LtStoredBuffer buf) {
+    return buf == LT_STORED_DELTA ? e->delta_sig : buf == LT_STORED_MOMENTUM ? e->proj_sig : buf == LT_STORED_RESIDUAL ? e->cache_res : nullptr;
+}
+// what the buffer holds after an evaluation of these step arguments that rewrites it: the difference and the momentum { B', H, W, ch } of the
+// guided channels, the residual { B, H, W, use_cfg }
+void stored_sig_of(const lt_engine* e, LtStoredBuffer buf, const lt_step_args* a, int use_cfg, int sig[4]) {
+    const int cfg_ch = a->cfg_channels > 0 ? a->cfg_channels : 3;
+    const bool res = buf == LT_STORED_RESIDUAL;
+    sig[0] = res ? a->batch : a->batch / 2; sig[1] = a->latent_h; sig[2] = a->latent_w;
+    sig[3] = res ? (use_cfg ? 1 : 0) : std::min(cfg_ch, (int)e->cfg.in_channels);
+}
+bool same_sig(const int have[4], const int want[4]) { return have[0] == want[0] && have[1] == want[1] && have[2] == want[2] && have[3] == want[3]; }
+// one evaluation that rewrites `buf` (LT_STORED_NONE: none): the signature is forgotten until the evaluation has been issued whole
+int forward_rewriting(lt_engine* e, LtStoredBuffer buf, const void* x, const float* t, void* out, const lt_step_args* a, int use_cfg, hipStream_t s,
+                      const EvalSpec& spec) {
+    int* sig = stored_sig(e, buf);
+    if (sig) sig[0] = 0;
+    if (int rc = forward_graphed(e, x, t, out, a, use_cfg, s, spec)) return rc;
+    if (sig) stored_sig_of(e, buf, a, use_cfg, sig);
+    return 0;
+}
+// a call that continues from the stored difference or momentum: refused by name unless the buffer holds one of this call's shape
+int check_stored(lt_engine* e, const char* who, LtStoredBuffer buf, const lt_step_args* a, const char* what, const char* use, const char* absent) {
+    int want[4];
+    stored_sig_of(e, buf, a, 1, want);
+    const int* have = stored_sig(e, buf);
+    LT_REQUIRE(have[0] != 0, "%s: no stored %s to %s: %s, or lt_prepare_prompt / lt_prepare_labels was called since", who, what, use, absent);
+    LT_REQUIRE(same_sig(have, want), "%s: the stored %s is of another shape: %d samples of %d channels at %dx%d, the call has %d samples of %d "
+               "channels at %dx%d", who, what, have[0], have[3], have[1], have[2], want[0], want[3], want[1], want[2]);
+    return 0;
+}
+// APG's momentum starts at zero: every trajectory, and a single evaluation that does not continue
+int zero_momentum(lt_engine* e, const lt_step_args* a, hipStream_t s) {
+    int sig[4];
+    stored_sig_of(e, LT_STORED_MOMENTUM, a, 1, sig);
+    e->proj_sig[0] = 0;
+    LT_CHECK_HIP(hipMemsetAsync(e->p_mom, 0, (size_t)sig[0] * sig[3] * sig[1] * sig[2] * sizeof(float), s));
+    return 0;
+}
+// the head of a step-cached evaluation and its two indicator sums in e->c_sums_host: one synchronisation
+int cache_probe(lt_engine* e, const void* x, const float* t, const lt_step_args* a, int use_cfg, hipStream_t s) {
+    if (int rc = forward_graphed(e, x, t, nullptr, a, use_cfg, s, {LT_KIND_CACHE_HEAD})) return rc;
+    LT_CHECK_HIP(hipMemcpyAsync(e->c_sums_host, e->c_ws + 2 * LT_CACHE_BLOCKS, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
+    LT_CHECK_HIP(hipStreamSynchronize(s));
+    return 0;
+}
+// A stage of skip-layer guidance with s != 0: the cond rows with the blocks of `sets` left out / perturbed, their guided
+// channels kept; then the stage's own evaluation `closing` - all rows, or the cond rows at scale 1 - whose closing kernel adds s (cond - skip).
+// s_dev: where s is, to be put into its fixed word between the two; null: it is in place
+int forward_slg_pair(lt_engine* e, const char* who, const GuidancePlan& sets, const void* x, const float* t, void* out, const lt_step_args* a,
+                     hipStream_t s, LtEvalKind closing, const float* closing_scale, const float* s_dev) {
+    {
+        SkipScope scope(e);
+        if (scope.set(who, sets.skip, sets.n_skip, sets.perturb, sets.n_perturb)) return 2;
+        if (int rc = forward_graphed(e, x, t, nullptr, a, 1, s, {LT_KIND_SLG_STORE, nullptr, e->g_cfg})) return rc;
+    }
+    if (s_dev) LT_CHECK_HIP(hipMemcpyAsync(e->g_cfg + 3, s_dev, sizeof(float), hipMemcpyDeviceToDevice, s));
+    return forward_graphed(e, x, t, out, a, 1, s, {closing, nullptr, closing_scale});
+}
+
+// The state of one trajectory: the ping-pong pair e->ys, the caller's record of the states (if any), the evaluation and row counts, and the
+// plan (guidance_plan.h) that says what evaluation number `call` issues - the empty plan: every one whole.
 struct Trajectory {
     lt_engine* e; const lt_step_args* a; int use_cfg; hipStream_t s;
     size_t sbytes;  // one state
+    const PackedCall* pc = nullptr;  // a packed batch: the states are flat buffers (lt_sample_ode_packed)
+    GuidancePlan plan;
+    int ncalls = 0;  // the evaluations of the committed table: the plan's tail lies behind their stage times
     void* traj = nullptr;
     int cur = 0;
-    long long nfe = 0, rows = 0, flips0 = 0;
-    const PackedCall* pc = nullptr;  // a packed batch: the states are flat buffers (lt_sample_ode_packed)
-    // a guidance schedule (lt_sample_ode_cfg_schedule): the scale of evaluation number `call`, on the host and where commit sent it
-    const float *cfg_host = nullptr, *cfg_dev = nullptr;
-    bool cfg_rule = false;  // ... under a rescale / norm-limit rule (lt_sample_ode_cfg_rule): its parameters are in e->g_cfg[1..2]
-    // guidance reuse (lt_sample_ode_cfg_reuse): the flag of evaluation number `call` - 0 take and store the cond - uncond difference, 1 reuse it
-    const int32_t* reuse_host = nullptr;
-    // skip-layer guidance (lt_sample_ode_cfg_slg): the scale s of evaluation number `call`, on the host and where commit sent it, and the
-    // layer set of the skip evaluations (checked by the entry point)
-    const float *slg_host = nullptr, *slg_dev = nullptr;
-    const int32_t* skip_host = nullptr;
-    int n_skip = 0;
-    // ... and the layers those evaluations perturb (lt_sample_ode_cfg_pag; empty: skip-layer guidance as it was)
-    const int32_t* perturb_host = nullptr;
-    int n_perturb = 0;
-    // step caching (lt_sample_ode_cached): the controller, the evaluations of the trajectory, those that reused the residual
-    CacheControl* cache = nullptr;
-    int ncalls = 0;
-    long long hits = 0;
+    long long nfe = 0, rows = 0, flips0 = 0, hits = 0;  // hits: the step-cached evaluations that reused the residual
     int start(const void* z, void* traj_dev, bool z_in_slot0) {
         traj = traj_dev;
         flips0 = e->layout_flips_total;
@@ -81,85 +127,43 @@ struct Trajectory {
     }
     void* y0() const { return e->ys[cur]; }      // the current state
     void* y1() const { return e->ys[cur ^ 1]; }  // where the step writes the next one
-    // one model evaluation at stage time number `call` of the committed table
+    // one model evaluation at stage time number `call` of the committed table: the plan's step, its evaluations and rows counted
     int eval(const void* y, int call, void* out) {
         ++nfe;
         const float* t = e->times.dev + (size_t)call * a->batch;
-        if (cache) return eval_cached(y, t, call, out);
-        if (!cfg_host) return eval_kind(LT_KIND_WHOLE, y, t, out);
-        // scale 1 exactly: the guided output is the conditional one - the cond rows alone, written to both halves
-        const bool cond_only = cfg_host[call] == 1.0f;
-        if (reuse_host && !cond_only) return eval_reuse(y, t, call, out);
-        if (slg_host && slg_host[call] != 0.0f) return eval_slg(y, t, call, out, cond_only);
-        if (!cond_only && cfg_rule && e->rule_form == LT_PROJECT_APG) return eval_momentum(y, t, out, cfg_dev + call);
-        return eval_kind(cond_only ? LT_KIND_COND_ONLY : cfg_rule ? LT_KIND_RULE : LT_KIND_DEV_GUIDED, y, t, out, cfg_dev + call);
+        const GuidanceStep st = plan.step_of(call);
+        if (st.kinds[0] == LT_KIND_CACHE_HEAD) return eval_cached(y, t, call, out);
+        const float* scale = st.scale == LT_SCALE_TABLE ? e->times.dev + GuidancePlan::table_offset(ncalls, a->batch) + call
+                             : st.scale == LT_SCALE_FIXED ? e->g_cfg : nullptr;
+        for (int k = 0; k < st.n_kinds; ++k) rows += lt_eval_traits(st.kinds[k]).half ? a->batch / 2 : a->batch;
+        if (st.n_kinds == 2) {  // (the sets were checked by the entry point)
+            ++nfe;
+            return forward_slg_pair(e, "skip-layer guidance", plan, y, t, out, a, s, st.kinds[1], scale,
+                                    e->times.dev + GuidancePlan::second_offset(ncalls, a->batch) + call);
+        }
+        return forward_rewriting(e, st.rewrites, y, t, out, a, lt_eval_traits(st.kinds[0]).dev_scale ? 1 : use_cfg, s, {st.kinds[0], pc, scale});
     }
-    // a guided evaluation under APG: it advances the momentum buffer, which holds nothing until the evaluation has been issued whole
-    int eval_momentum(const void* y, const float* t, void* out, const float* scale) {
-        e->proj_sig[0] = 0;
-        if (int rc = eval_kind(LT_KIND_RULE, y, t, out, scale)) return rc;
-        delta_sig_of(e, a, e->proj_sig);
-        return 0;
-    }
-    // an evaluation of one kind, its rows counted.  scale: where a kind that reads its guidance scale from device memory finds it
-    int eval_kind(LtEvalKind kind, const void* y, const float* t, void* out, const float* scale = nullptr) {
-        const LtEvalTraits kt = lt_eval_traits(kind);
-        rows += kt.half ? a->batch / 2 : a->batch;
-        return forward_graphed(e, y, t, out, a, kt.dev_scale ? 1 : use_cfg, s, {kind, pc, scale});
-    }
-    // an evaluation under step caching: the head, the two indicator sums to the host (one synchronisation; the first and the last
-    // evaluation run the stack whatever they are and read nothing), the controller, then the stack + tail or the stored residual + tail
+    // an evaluation under step caching: the head, the two indicator sums to the host (the first and the last evaluation run the stack
+    // whatever they are and read nothing), the controller, then the stack + tail or the stored residual + tail
     int eval_cached(const void* y, const float* t, int call, void* out) {
-        if (int rc = forward_graphed(e, y, t, nullptr, a, use_cfg, s, {LT_KIND_CACHE_HEAD})) return rc;
+        CacheControl* cache = plan.cache;
         bool run = true;
         double rel = 0.0;
         if (call > 0 && call < ncalls - 1) {
-            LT_CHECK_HIP(hipMemcpyAsync(e->c_sums_host, e->c_ws + 2 * LT_CACHE_BLOCKS, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
-            LT_CHECK_HIP(hipStreamSynchronize(s));
+            if (int rc = cache_probe(e, y, t, a, use_cfg, s)) return rc;
             run = cache->step(e->c_sums_host[0], e->c_sums_host[1], &rel);
+        } else if (int rc = forward_graphed(e, y, t, nullptr, a, use_cfg, s, {LT_KIND_CACHE_HEAD})) {
+            return rc;
         }
         if (cache->stats) { cache->stats[3 * call] = rel; cache->stats[3 * call + 1] = cache->acc; cache->stats[3 * call + 2] = run ? 1.0 : 0.0; }
-        if (run) {
-            cache->acc = 0.0;
-            rows += a->batch;  // (the head and the blocks are one evaluation; a reuse counts no rows)
-            e->cache_res[0] = 0;  // (until the evaluation that rewrites the residual has been issued whole)
-            if (int rc = forward_graphed(e, y, t, out, a, use_cfg, s, {LT_KIND_CACHE_BLOCKS})) return rc;
-            set_cache_res(e, a, use_cfg);
-            return 0;
+        if (!run) {
+            ++hits;
+            return forward_graphed(e, y, t, out, a, use_cfg, s, {LT_KIND_CACHE_APPLY});
         }
-        ++hits;
-        return forward_graphed(e, y, t, out, a, use_cfg, s, {LT_KIND_CACHE_APPLY});
+        cache->acc = 0.0;
+        rows += a->batch;  // (the head and the blocks are one evaluation; a reuse counts no rows)
+        return forward_rewriting(e, LT_STORED_RESIDUAL, y, t, out, a, use_cfg, s, {LT_KIND_CACHE_BLOCKS});
     }
-    static void set_cache_res(lt_engine* e, const lt_step_args* a, int use_cfg) {
-        e->cache_res[0] = a->batch; e->cache_res[1] = a->latent_h; e->cache_res[2] = a->latent_w; e->cache_res[3] = use_cfg ? 1 : 0;
-    }
-    // a stage of skip-layer guidance with s != 0: the cond rows with the set's blocks left out, their guided channels kept; then
-    // the stage's own evaluation - all rows, or the cond rows at scale 1 - whose closing kernel adds s (cond - skip).  Two evaluations
-    int eval_slg(const void* y, const float* t, int call, void* out, bool cond_only) {
-        ++nfe;
-        {
-            SkipScope scope(e);
-            if (scope.set("skip-layer guidance", skip_host, n_skip, perturb_host, n_perturb)) return 2;
-            if (int rc = eval_kind(LT_KIND_SLG_STORE, y, t, nullptr, e->g_cfg)) return rc;
-        }
-        LT_CHECK_HIP(hipMemcpyAsync(e->g_cfg + 3, slg_dev + call, sizeof(float), hipMemcpyDeviceToDevice, s));
-        return cond_only ? eval_kind(LT_KIND_SLG_COND, y, t, out, e->g_cfg) : eval_kind(LT_KIND_SLG_GUIDED, y, t, out, cfg_dev + call);
-    }
-    // a guided evaluation of a reuse table: all rows and the difference stored, or the cond rows and the stored difference (the caller has
-    // checked that a refresh comes first and has run ensure_delta)
-    int eval_reuse(const void* y, const float* t, int call, void* out) {
-        const bool again = reuse_host[call] != 0;
-        if (!again) e->delta_sig[0] = 0;  // (until the evaluation that rewrites it has been issued whole)
-        if (int rc = eval_kind(again ? LT_KIND_REUSE_AGAIN : LT_KIND_REUSE_STORE, y, t, out, cfg_dev + call)) return rc;
-        if (!again) set_delta_sig(e, a);
-        return 0;
-    }
-    // what the difference buffer holds after a refresh evaluation of these step arguments: { B', H, W, ch }
-    static void delta_sig_of(const lt_engine* e, const lt_step_args* a, int sig[4]) {
-        const int cfg_ch = a->cfg_channels > 0 ? a->cfg_channels : 3;
-        sig[0] = a->batch / 2; sig[1] = a->latent_h; sig[2] = a->latent_w; sig[3] = std::min(cfg_ch, (int)e->cfg.in_channels);
-    }
-    static void set_delta_sig(lt_engine* e, const lt_step_args* a) { delta_sig_of(e, a, e->delta_sig); }
     int advance(int traj_slot) {  // y1 is the current state now [and slot `traj_slot` of the record]
         if (traj) LT_CHECK_HIP(hipMemcpyAsync((char*)traj + (size_t)traj_slot * sbytes, y1(), sbytes, hipMemcpyDeviceToDevice, s));
         cur ^= 1;
@@ -169,7 +173,7 @@ struct Trajectory {
         if (final_dev) LT_CHECK_HIP(hipMemcpyAsync(final_dev, y0(), sbytes, hipMemcpyDeviceToDevice, s));
         e->last_nfe = nfe;
         e->last_eval_rows = rows;
-        if (cache) e->last_cache_hits = hits;
+        if (plan.form == LT_PLAN_CACHED) e->last_cache_hits = hits;
         e->layout_flips = e->layout_flips_total - flips0;
         return 0;
     }
@@ -184,33 +188,45 @@ float bf16_round_host(float f) {
     return f;
 }
 
-// The fixed-grid loop of lt_sample_ode and lt_sample_ode_packed: stage-time fill and the euler / midpoint / rk4 stepping body on a state of
-// n elements (the stage arithmetic is elementwise, so a packed batch's flat state runs through it as it is).  The callers have validated
-// the grid, the method and the shape.  With `mb` (lt_sample_ode_masked) the LAST combine of every step is the masked launcher - the same
-// arithmetic followed by the inpainting blend at the step's end time - and nothing else changes.  With `cs` (lt_sample_ode_cfg_schedule)
-// evaluation i * stages + k takes its guidance scale from cs->table: the scales are committed behind the stage times, one float per stage;
-// cs->rule (lt_sample_ode_cfg_rule): the rescale blend and the norm limit travel behind the scales and are put into e->g_cfg[1..2] once.
+// One call of a grid loop: the states, the grid, the stepping rule - `method` (ode_fixed_grid) or the weight table and `corrector`
+// (ode_multistep) - and the state's n elements (the stage arithmetic is elementwise, so a packed batch's flat state, `pc`, runs as it is)
+struct GridCall {
+    const void* z; void *traj, *final;
+    const float* tgrid; int n_grid, use_cfg, t_round;
+    const lt_step_args* a; hipStream_t s; long long n; const PackedCall* pc;
+    int method = 0; const float* coef = nullptr; int corrector = 0;
+};
 struct MaskedBlend { const void *mask, *x1, *noise; };
-// host: (n_grid - 1) * stages scales; { rescale, norm limit } or null; the reuse flags of lt_sample_ode_cfg_reuse, one per scale, or null
-// ... ; skip-layer guidance (lt_sample_ode_cfg_slg): one scale s per scale w and the layer set, or null
-// (lt_sample_ode_cfg_pag: the layers perturbed in the same evaluation; pag: the entry that takes both sets, either of which may be empty)
-struct SlgCall { const float* table; const int32_t* skip; int n_skip; const int32_t* perturb = nullptr; int n_perturb = 0; bool pag = false; };
-// projected guidance (lt_sample_ode_cfg_project): the form, { eta, beta, r } and the intervals of zero velocity at the start
-struct ProjectCall { int form; float par[3]; int zero_init; };
-struct CfgSchedule { const float* table; const float* rule = nullptr; const int32_t* reuse = nullptr; const SlgCall* slg = nullptr;
-                     const ProjectCall* project = nullptr; };
 
-int ode_fixed_grid(lt_engine* e, const void* z_dev, void* traj_dev, void* final_dev, const float* tgrid_host, int n_grid, int method, int use_cfg,
-                   int t_round, const lt_step_args* a, hipStream_t s, long long n, const PackedCall* pc, const MaskedBlend* mb = nullptr,
-                   const CfgSchedule* cs = nullptr, CacheControl* cc = nullptr) {
-    const int B = a->batch;
+// the state of a dense batch, in elements
+long long dense_elems(const lt_engine* e, const lt_step_args* a) { return (long long)a->batch * e->cfg.in_channels * a->latent_h * a->latent_w; }
+
+// What a plan puts on the device once, behind the commit of its tail: the rule pair into e->g_cfg[1..2]; eta, beta, r into their fixed words,
+// and APG's momentum starts every trajectory at zero
+int apply_plan(lt_engine* e, const GuidancePlan& plan, const lt_step_args* a, int ncalls, hipStream_t s) {
+    const float* second = e->times.dev + GuidancePlan::second_offset(ncalls, a->batch);
+    if (plan.projected()) LT_CHECK_HIP(hipMemcpyAsync(e->p_par + 1, second, 3 * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (plan.form == LT_PLAN_PROJECT_APG && zero_momentum(e, a, s)) return 1;
+    if (plan.form == LT_PLAN_RULE) LT_CHECK_HIP(hipMemcpyAsync(e->g_cfg + 1, second, 2 * sizeof(float), hipMemcpyDeviceToDevice, s));
+    return 0;
+}
+
+// The fixed-grid loop: stage-time fill and the euler / midpoint / rk4 stepping body.  The callers have validated the grid, the method and the
+// shape.  With `mb` (lt_sample_ode_masked; null: none) the LAST combine of every step is the masked launcher - the same arithmetic followed by
+// the inpainting blend at the step's end time - and nothing else changes.  Evaluation i * stages + k is what the plan says: its tables are
+// committed behind the stage times (GuidancePlan: the tail) and its fixed parameters put in place once (apply_plan).
+int ode_fixed_grid(lt_engine* e, const GridCall& c, const GuidancePlan& plan, const MaskedBlend* mb) {
+    const lt_step_args* a = c.a;
+    hipStream_t s = c.s;
+    const float* tgrid_host = c.tgrid;
+    const int B = a->batch, n_grid = c.n_grid, method = c.method;
+    const long long n = c.n;
     const int stages = method == LT_ODE_EULER ? 1 : (method == LT_ODE_MIDPOINT ? 2 : 4);
     const int ncalls = (n_grid - 1) * stages;
     const bool bf = a->io_dtype == LT_BF16;
     // stage times; torchdiffeq's _PerturbFunc casts t to the state dtype before calling the model, then
     // integrators.py:108 broadcasts it to an fp32 [B] vector
-    // (a rule, slg and a projected form never meet)
-    const int nsent = ncalls * B + (cs ? ncalls : 0) + (cs && cs->rule ? 2 : 0) + (cs && cs->slg ? ncalls : 0) + (cs && cs->project ? 3 : 0);
+    const int nsent = ncalls * B + plan.tail_floats(ncalls);
     float* tp = e->times.begin(nsent, s);
     if (!tp) return 1;
     std::vector<float> dts(n_grid - 1);
@@ -223,41 +239,18 @@ int ode_fixed_grid(lt_engine* e, const void* z_dev, void* traj_dev, void* final_
         else if (method == LT_ODE_MIDPOINT) { ts[0] = t0; ts[1] = t0 + 0.5f * dt; }
         else { ts[0] = t0; ts[1] = t0 + dt * (float)(1.0 / 3.0); ts[2] = t0 + dt * (float)(2.0 / 3.0); ts[3] = t1; }
         for (int k = 0; k < stages; ++k) {
-            const float tv = (t_round && bf) ? bf16_round_host(ts[k]) : ts[k];
+            const float tv = (c.t_round && bf) ? bf16_round_host(ts[k]) : ts[k];
             for (int b = 0; b < B; ++b) tp[((size_t)i * stages + k) * B + b] = tv;
         }
     }
-    if (cs) memcpy(tp + (size_t)ncalls * B, cs->table, (size_t)ncalls * sizeof(float));
-    if (cs && cs->rule) memcpy(tp + (size_t)ncalls * B + ncalls, cs->rule, 2 * sizeof(float));
-    if (cs && cs->slg) memcpy(tp + (size_t)ncalls * B + ncalls, cs->slg->table, (size_t)ncalls * sizeof(float));
-    if (cs && cs->project) memcpy(tp + (size_t)ncalls * B + ncalls, cs->project->par, 3 * sizeof(float));
-    if (e->times.commit(nsent, s)) return 1;
-    const int zero_init = cs && cs->project ? cs->project->zero_init : 0;
-    if (cs && cs->project) {  // eta, beta, r into their fixed words; APG's momentum starts every trajectory at zero
-        LT_CHECK_HIP(hipMemcpyAsync(e->p_par + 1, e->times.dev + (size_t)ncalls * B + ncalls, 3 * sizeof(float), hipMemcpyDeviceToDevice, s));
-        if (cs->project->form == LT_PROJECT_APG) {
-            int sig[4];
-            Trajectory::delta_sig_of(e, a, sig);
-            e->proj_sig[0] = 0;
-            LT_CHECK_HIP(hipMemsetAsync(e->p_mom, 0, (size_t)sig[0] * sig[3] * sig[1] * sig[2] * sizeof(float), s));
-        }
-    }
-    if (cs && cs->rule)
-        LT_CHECK_HIP(hipMemcpyAsync(e->g_cfg + 1, e->times.dev + (size_t)ncalls * B + ncalls, 2 * sizeof(float), hipMemcpyDeviceToDevice, s));
-    Trajectory tr{e, a, use_cfg, s, (size_t)n * (bf ? 2 : 4)};
-    tr.pc = pc;
-    tr.cache = cc; tr.ncalls = ncalls;
-    if (cs) { tr.cfg_host = cs->table; tr.cfg_dev = e->times.dev + (size_t)ncalls * B; tr.cfg_rule = cs->rule != nullptr || cs->project != nullptr; tr.reuse_host = cs->reuse; }
-    if (cs && cs->slg) {
-        tr.slg_host = cs->slg->table; tr.slg_dev = e->times.dev + (size_t)ncalls * B + ncalls;
-        tr.skip_host = cs->slg->skip; tr.n_skip = cs->slg->n_skip;
-        tr.perturb_host = cs->slg->perturb; tr.n_perturb = cs->slg->n_perturb;
-    }
-    if (tr.start(z_dev, traj_dev, true)) return 1;
+    plan.fill_tail(tp + GuidancePlan::table_offset(ncalls, B), ncalls);
+    if (e->times.commit(nsent, s) || apply_plan(e, plan, a, ncalls, s)) return 1;
+    Trajectory tr{e, a, c.use_cfg, s, (size_t)n * (bf ? 2 : 4), c.pc, plan, ncalls};
+    if (tr.start(c.z, c.traj, true)) return 1;
     const int dt_code = bf ? 1 : 0;
     for (int i = 0; i + 1 < n_grid; ++i) {
         void *y0 = tr.y0(), *y1 = tr.y1();
-        if (i < zero_init) {  // CFG-Zero*'s zero-init: zero velocity, so the state stays where it is; no evaluation, nothing counted
+        if (i < plan.zero_init) {  // CFG-Zero*'s zero-init: zero velocity, so the state stays where it is; no evaluation, nothing counted
             if (tr.traj) LT_CHECK_HIP(hipMemcpyAsync((char*)tr.traj + (size_t)(i + 1) * tr.sbytes, y0, tr.sbytes, hipMemcpyDeviceToDevice, s));
             continue;
         }
@@ -293,22 +286,37 @@ int ode_fixed_grid(lt_engine* e, const void* z_dev, void* traj_dev, void* final_
         }
         if (tr.advance(i + 1)) return 1;
     }
-    return tr.finish(final_dev);
+    return tr.finish(c.final);
 }
 
 }  // namespace
 
+// lt_sample_ode and its packed (`hw_host`; null: a dense batch) and masked (`mb`; null: no blend) forms, which differ in what they check
+static int sample_plain(lt_engine* e, const char* who, GridCall c, const int32_t* hw_host, bool packed, const MaskedBlend* mb) {
+    // (the mask pointers before e: the tests pin the first error)
+    LT_REQUIRE(!mb || (mb->mask && mb->x1 && mb->noise), "%s: null mask, source or noise", who);
+    LT_REQUIRE(e && c.z && c.tgrid && c.a && (hw_host || !packed), "%s: null argument", who);
+    if (refuse_if_capturing(c.s, who)) return 2;  // (the stage times travel through a host staging buffer that the next call rewrites)
+    LtOptScope opt_scope(&e->opts);
+    if (check_grid_method(who, c.n_grid, c.method, mb != nullptr, "")) return 2;
+    PackedCall pc{};
+    if (packed) {
+        if (int rc = packed_call_begin(e, who, hw_host, c.a, c.use_cfg, &pc, c.s)) return rc;
+        c.n = pc.elems; c.pc = &pc;
+    } else {
+        if (check_step_shape(e, who, c.a)) return 2;
+        // (lt_sample_ode leaves this to the first evaluation, after z has been copied; a masked call writes nothing)
+        LT_REQUIRE(!mb || !c.use_cfg || c.a->batch % 2 == 0, "%s: guidance needs an even batch (cond + uncond rows), got %d", who, c.a->batch);
+        c.n = dense_elems(e, c.a);
+    }
+    return ode_fixed_grid(e, c, {}, mb);
+}
+
 extern "C" int lt_sample_ode(lt_engine* e, const void* z_dev, void* traj_dev, void* final_dev, const float* tgrid_host,
                              int32_t n_grid, int32_t method, int32_t use_cfg, int32_t t_round, const lt_step_args* a,
                              void* stream) {
-    LT_REQUIRE(e && z_dev && tgrid_host && a, "lt_sample_ode: null argument");
-    if (refuse_if_capturing((hipStream_t)stream, "lt_sample_ode")) return 2;  // (the stage times travel through a host staging buffer that the next call rewrites)
-    LtOptScope opt_scope(&e->opts);
-    LT_REQUIRE(n_grid >= 2, "lt_sample_ode: need at least 2 grid points");
-    LT_REQUIRE(method >= LT_ODE_EULER && method <= LT_ODE_RK4, "lt_sample_ode: unknown method %d", method);
-    if (check_step_shape(e, "lt_sample_ode", a)) return 2;
-    const long long n = (long long)a->batch * e->cfg.in_channels * a->latent_h * a->latent_w;
-    return ode_fixed_grid(e, z_dev, traj_dev, final_dev, tgrid_host, n_grid, method, use_cfg, t_round, a, (hipStream_t)stream, n, nullptr);
+    return sample_plain(e, "lt_sample_ode", {z_dev, traj_dev, final_dev, tgrid_host, n_grid, use_cfg, t_round, a, (hipStream_t)stream, 0, nullptr, method}, nullptr,
+                        false, nullptr);
 }
 
 // Step caching: what the cached entry points refuse beyond lt_sample_ode's refusals, by name, before anything is launched
@@ -329,20 +337,15 @@ extern "C" int lt_sample_ode_cached(lt_engine* e, const void* z_dev, void* traj_
     LT_REQUIRE(e && z_dev && tgrid_host && a && coef_host, "lt_sample_ode_cached: null argument");
     if (refuse_if_capturing((hipStream_t)stream, "lt_sample_ode_cached")) return 2;  // (the controller reads the indicator on the host)
     LtOptScope opt_scope(&e->opts);
-    LT_REQUIRE(n_grid >= 2, "lt_sample_ode_cached: need at least 2 grid points");
-    LT_REQUIRE(method >= LT_ODE_EULER && method <= LT_ODE_RK4, "lt_sample_ode_cached: unknown method %d (step caching serves the fixed-grid methods "
-               "euler, midpoint, rk4; not the multistep and adaptive solvers)", method);
+    if (check_grid_method("lt_sample_ode_cached", n_grid, method, false, " (step caching serves the fixed-grid methods euler, midpoint, rk4; not the "
+                          "multistep and adaptive solvers)")) return 2;
     LT_REQUIRE(threshold >= 0.0f, "lt_sample_ode_cached: threshold %g is not a number >= 0", (double)threshold);
     for (int k = 0; k < 5; ++k) LT_REQUIRE(std::isfinite(coef_host[k]), "lt_sample_ode_cached: coefficient %d is not finite", k);
     if (check_cached_call(e, "lt_sample_ode_cached", a, use_cfg)) return 2;
     if (ensure_step_cache(e)) return 1;
-    CacheControl cc;
-    cc.thr = (double)threshold;
-    for (int k = 0; k < 5; ++k) cc.c[k] = coef_host[k];
-    cc.stats = stats_host;
-    const long long n = (long long)a->batch * e->cfg.in_channels * a->latent_h * a->latent_w;
-    return ode_fixed_grid(e, z_dev, traj_dev, final_dev, tgrid_host, n_grid, method, use_cfg, t_round, a, (hipStream_t)stream, n, nullptr, nullptr, nullptr,
-                          &cc);
+    CacheControl cc{(double)threshold, {coef_host[0], coef_host[1], coef_host[2], coef_host[3], coef_host[4]}, 0.0, stats_host};
+    return ode_fixed_grid(e, {z_dev, traj_dev, final_dev, tgrid_host, n_grid, use_cfg, t_round, a, (hipStream_t)stream, dense_elems(e, a), nullptr, method},
+                          GuidancePlan::of_cache(&cc), nullptr);
 }
 
 // the single evaluations the host loop of transport/cache.py is built from
@@ -356,77 +359,45 @@ extern "C" int lt_forward_cached(lt_engine* e, const void* x_dev, const float* t
     if (refuse_if_capturing(s, "lt_forward_cached")) return 2;
     LtOptScope opt_scope(&e->opts);
     if (check_cached_call(e, "lt_forward_cached", a, use_cfg)) return 2;
+    int want[4];
+    stored_sig_of(e, LT_STORED_RESIDUAL, a, use_cfg, want);
     if (mode == LT_CACHE_REUSE)
-        LT_REQUIRE(e->cache_res[0] == a->batch && e->cache_res[1] == a->latent_h && e->cache_res[2] == a->latent_w && e->cache_res[3] == (use_cfg ? 1 : 0),
-                   "lt_forward_cached: LT_CACHE_REUSE without a stored residual of this shape (batch %d, latent %dx%d, cfg %d): an LT_CACHE_RUN "
+        LT_REQUIRE(same_sig(e->cache_res, want), "lt_forward_cached: LT_CACHE_REUSE without a stored residual of this shape (batch %d, latent %dx%d, cfg %d): an LT_CACHE_RUN "
                    "evaluation under the same conditioning comes first", a->batch, a->latent_h, a->latent_w, use_cfg ? 1 : 0);
     if (ensure_step_cache(e)) return 1;
     if (mode == LT_CACHE_PROBE) {
-        if (int rc = forward_graphed(e, x_dev, t_dev, nullptr, a, use_cfg, s, {LT_KIND_CACHE_HEAD})) return rc;
-        LT_CHECK_HIP(hipMemcpyAsync(e->c_sums_host, e->c_ws + 2 * LT_CACHE_BLOCKS, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
-        LT_CHECK_HIP(hipStreamSynchronize(s));
+        if (int rc = cache_probe(e, x_dev, t_dev, a, use_cfg, s)) return rc;
         sums_host[0] = e->c_sums_host[0]; sums_host[1] = e->c_sums_host[1];
         return 0;
     }
     if (mode == LT_CACHE_REUSE) return forward_graphed(e, x_dev, t_dev, out_dev, a, use_cfg, s, {LT_KIND_CACHE_APPLY});
-    e->cache_res[0] = 0;
-    if (int rc = forward_graphed(e, x_dev, t_dev, out_dev, a, use_cfg, s, {LT_KIND_CACHE_BLOCKS})) return rc;
-    Trajectory::set_cache_res(e, a, use_cfg);
-    return 0;
+    return forward_rewriting(e, LT_STORED_RESIDUAL, x_dev, t_dev, out_dev, a, use_cfg, s, {LT_KIND_CACHE_BLOCKS});
 }
 
 // lt_sample_ode on a packed batch: z, every trajectory slot and the final state are flat buffers of the size list's layout (packed.hip)
 extern "C" int lt_sample_ode_packed(lt_engine* e, const void* z_flat_dev, const int32_t* hw_host, void* traj_flat_dev, void* final_flat_dev,
                                     const float* tgrid_host, int32_t n_grid, int32_t method, int32_t use_cfg, int32_t t_round, const lt_step_args* a,
                                     void* stream) {
-    LT_REQUIRE(e && z_flat_dev && hw_host && tgrid_host && a, "lt_sample_ode_packed: null argument");
-    if (refuse_if_capturing((hipStream_t)stream, "lt_sample_ode_packed")) return 2;  // (the stage times travel through a host staging buffer that the next call rewrites)
-    LtOptScope opt_scope(&e->opts);
-    LT_REQUIRE(n_grid >= 2, "lt_sample_ode_packed: need at least 2 grid points");
-    LT_REQUIRE(method >= LT_ODE_EULER && method <= LT_ODE_RK4, "lt_sample_ode_packed: unknown method %d", method);
-    PackedCall pc{};
-    if (int rc = packed_call_begin(e, "lt_sample_ode_packed", hw_host, a, use_cfg, &pc, (hipStream_t)stream)) return rc;
-    return ode_fixed_grid(e, z_flat_dev, traj_flat_dev, final_flat_dev, tgrid_host, n_grid, method, use_cfg, t_round, a, (hipStream_t)stream, pc.elems,
-                          &pc);
+    return sample_plain(e, "lt_sample_ode_packed", {z_flat_dev, traj_flat_dev, final_flat_dev, tgrid_host, n_grid, use_cfg, t_round, a, (hipStream_t)stream, 0,
+                        nullptr, method}, hw_host, true, nullptr);
 }
 
 // ---- inpainting: the fixed-grid loop with the blend in each step's closing combine --------------------------------------
 extern "C" int lt_sample_ode_masked(lt_engine* e, const void* z_dev, const void* mask_dev, const void* x1_dev, const void* noise_dev, void* traj_dev,
                                     void* final_dev, const float* tgrid_host, int32_t n_grid, int32_t method, int32_t use_cfg, int32_t t_round,
                                     const lt_step_args* a, void* stream) {
-    LT_REQUIRE(mask_dev && x1_dev && noise_dev, "lt_sample_ode_masked: null mask, source or noise");
-    LT_REQUIRE(e && z_dev && tgrid_host && a, "lt_sample_ode_masked: null argument");
-    if (refuse_if_capturing((hipStream_t)stream, "lt_sample_ode_masked")) return 2;  // (the stage times travel through a host staging buffer that the next call rewrites)
-    LtOptScope opt_scope(&e->opts);
-    LT_REQUIRE(n_grid >= 2, "lt_sample_ode_masked: need at least 2 grid points");
-    LT_REQUIRE(!(method >= LT_ODE_AB2 && method <= LT_ODE_ABM3), "%s: masked sampling with a multistep method (ab2, ab3, abm2, abm3) is refused: the blend "
-               "makes the state discontinuous, so the history's slopes no longer belong to it", "lt_sample_ode_masked");
-    LT_REQUIRE(method >= LT_ODE_EULER && method <= LT_ODE_RK4, "lt_sample_ode_masked: unknown method %d", method);
-    if (check_step_shape(e, "lt_sample_ode_masked", a)) return 2;
-    // (lt_sample_ode leaves this to the first evaluation, after z has been copied; here nothing is written)
-    LT_REQUIRE(!use_cfg || a->batch % 2 == 0, "lt_sample_ode_masked: guidance needs an even batch (cond + uncond rows), got %d", a->batch);
-    const long long n = (long long)a->batch * e->cfg.in_channels * a->latent_h * a->latent_w;
     const MaskedBlend mb{mask_dev, x1_dev, noise_dev};
-    return ode_fixed_grid(e, z_dev, traj_dev, final_dev, tgrid_host, n_grid, method, use_cfg, t_round, a, (hipStream_t)stream, n, nullptr, &mb);
+    return sample_plain(e, "lt_sample_ode_masked", {z_dev, traj_dev, final_dev, tgrid_host, n_grid, use_cfg, t_round, a, (hipStream_t)stream, 0, nullptr, method},
+                        nullptr, false, &mb);
 }
 
 extern "C" int lt_sample_ode_masked_packed(lt_engine* e, const void* z_flat_dev, const int32_t* hw_host, const void* mask_flat_dev,
                                            const void* x1_flat_dev, const void* noise_flat_dev, void* traj_flat_dev, void* final_flat_dev,
                                            const float* tgrid_host, int32_t n_grid, int32_t method, int32_t use_cfg, int32_t t_round,
                                            const lt_step_args* a, void* stream) {
-    LT_REQUIRE(mask_flat_dev && x1_flat_dev && noise_flat_dev, "lt_sample_ode_masked_packed: null mask, source or noise");
-    LT_REQUIRE(e && z_flat_dev && hw_host && tgrid_host && a, "lt_sample_ode_masked_packed: null argument");
-    if (refuse_if_capturing((hipStream_t)stream, "lt_sample_ode_masked_packed")) return 2;  // (the stage times travel through a host staging buffer that the next call rewrites)
-    LtOptScope opt_scope(&e->opts);
-    LT_REQUIRE(n_grid >= 2, "lt_sample_ode_masked_packed: need at least 2 grid points");
-    LT_REQUIRE(!(method >= LT_ODE_AB2 && method <= LT_ODE_ABM3), "%s: masked sampling with a multistep method (ab2, ab3, abm2, abm3) is refused: the blend "
-               "makes the state discontinuous, so the history's slopes no longer belong to it", "lt_sample_ode_masked_packed");
-    LT_REQUIRE(method >= LT_ODE_EULER && method <= LT_ODE_RK4, "lt_sample_ode_masked_packed: unknown method %d", method);
-    PackedCall pc{};
-    if (int rc = packed_call_begin(e, "lt_sample_ode_masked_packed", hw_host, a, use_cfg, &pc, (hipStream_t)stream)) return rc;
     const MaskedBlend mb{mask_flat_dev, x1_flat_dev, noise_flat_dev};
-    return ode_fixed_grid(e, z_flat_dev, traj_flat_dev, final_flat_dev, tgrid_host, n_grid, method, use_cfg, t_round, a, (hipStream_t)stream, pc.elems,
-                          &pc, &mb);
+    return sample_plain(e, "lt_sample_ode_masked_packed", {z_flat_dev, traj_flat_dev, final_flat_dev, tgrid_host, n_grid, use_cfg, t_round, a,
+                        (hipStream_t)stream, 0, nullptr, method}, hw_host, true, &mb);
 }
 
 // ---- guidance schedules: a scale per stage, conditional-only stages at half the rows --------------------------------------
@@ -484,52 +455,49 @@ int check_reuse_flags(const char* who, const float* cfg_host, const int32_t* reu
     return 0;
 }
 
-// lt_sample_ode_cfg_schedule, with `rule` = { rescale, norm limit } lt_sample_ode_cfg_rule, with `reuse_call` lt_sample_ode_cfg_reuse
+// Every fixed-grid call with a scale per evaluation: the plan's form says which (lt_sample_ode_cfg_schedule, _rule, _reuse, _slg, _pag, _project)
 int sample_cfg_table(lt_engine* e, const char* who, const void* z_dev, void* traj_dev, void* final_dev, const float* tgrid_host, int n_grid, int method,
-                     const float* cfg_host, const float* rule, int t_round, const lt_step_args* a, hipStream_t s, const int32_t* reuse_host = nullptr,
-                     bool reuse_call = false, const SlgCall* slg = nullptr, const ProjectCall* project = nullptr) {
-    LT_REQUIRE(e && z_dev && tgrid_host && cfg_host && a, "%s: null argument", who);
-    LT_REQUIRE(!reuse_call || reuse_host, "%s: null argument (reuse_host: one int32 flag per stage)", who);
-    LT_REQUIRE(!slg || slg->table, "%s: null argument (slg_host: one skip-layer scale per stage)", who);
+                     const GuidancePlan& plan, int t_round, const lt_step_args* a, hipStream_t s) {
+    LT_REQUIRE(e && z_dev && tgrid_host && plan.table && a, "%s: null argument", who);
+    LT_REQUIRE(plan.form != LT_PLAN_REUSE || plan.reuse, "%s: null argument (reuse_host: one int32 flag per stage)", who);
+    LT_REQUIRE(plan.form != LT_PLAN_SLG || plan.slg, "%s: null argument (slg_host: one skip-layer scale per stage)", who);
     if (refuse_if_capturing(s, who)) return 2;  // (the stage times travel through a host staging buffer that the next call rewrites)
     LtOptScope opt_scope(&e->opts);
-    LT_REQUIRE(n_grid >= 2, "%s: need at least 2 grid points", who);
-    LT_REQUIRE(method >= LT_ODE_EULER && method <= LT_ODE_RK4, "%s: unknown method %d", who, method);
+    if (check_grid_method(who, n_grid, method, false, "")) return 2;
     if (check_step_shape(e, who, a)) return 2;
     const int stages = method == LT_ODE_EULER ? 1 : (method == LT_ODE_MIDPOINT ? 2 : 4);
-    if (check_guided_table(e, who, a, cfg_host, n_grid - 1, stages, rule)) return 2;
-    if (reuse_call && check_reuse_flags(who, cfg_host, reuse_host, (n_grid - 1) * stages)) return 2;
-    if (reuse_call && ensure_delta(e)) return 1;
-    if (project) {
-        if (check_project(who, project->form, project->par[0], project->par[1], project->par[2])) return 2;
-        LT_REQUIRE(project->zero_init >= 0 && project->zero_init < n_grid - 1, "%s: zero_init %d leaves no interval of the %d to integrate "
-                   "(0 .. n_grid - 2)", who, project->zero_init, n_grid - 1);
-        LT_REQUIRE(project->form == LT_PROJECT_ZERO_STAR || project->zero_init == 0, "%s: zero_init %d belongs to CFG-Zero* (form %d), not to "
-                   "APG", who, project->zero_init, LT_PROJECT_ZERO_STAR);
+    const int ncalls = (n_grid - 1) * stages;
+    if (check_guided_table(e, who, a, plan.table, n_grid - 1, stages, plan.rule)) return 2;
+    if (plan.form == LT_PLAN_REUSE && check_reuse_flags(who, plan.table, plan.reuse, ncalls)) return 2;
+    if (plan.form == LT_PLAN_REUSE && ensure_delta(e)) return 1;
+    if (plan.projected()) {
+        if (check_project(who, plan.project_form, plan.par[0], plan.par[1], plan.par[2])) return 2;
+        LT_REQUIRE(plan.zero_init >= 0 && plan.zero_init < n_grid - 1, "%s: zero_init %d leaves no interval of the %d to integrate "
+                   "(0 .. n_grid - 2)", who, plan.zero_init, n_grid - 1);
+        LT_REQUIRE(plan.form == LT_PLAN_PROJECT_ZERO_STAR || plan.zero_init == 0, "%s: zero_init %d belongs to CFG-Zero* (form %d), not to "
+                   "APG", who, plan.zero_init, LT_PROJECT_ZERO_STAR);
         if (ensure_project(e)) return 1;
     }
-    if (slg) {
-        for (int i = 0; i < (n_grid - 1) * stages; ++i)
-            LT_REQUIRE(std::isfinite(slg->table[i]), "%s: the skip-layer scale of stage %d of interval %d is not finite", who, i % stages, i / stages);
-        if (check_layer_sets(e, who, slg->skip, slg->n_skip, slg->perturb, slg->n_perturb)) return 2;
-        if (slg->pag && slg->n_skip == 0 && slg->n_perturb == 0)
-            for (int i = 0; i < (n_grid - 1) * stages; ++i)
-                LT_REQUIRE(slg->table[i] == 0.0f, "%s: both layer sets are empty, and stage %d of interval %d has a non-zero scale: the third "
+    if (plan.form == LT_PLAN_SLG) {
+        for (int i = 0; i < ncalls; ++i)
+            LT_REQUIRE(std::isfinite(plan.slg[i]), "%s: the skip-layer scale of stage %d of interval %d is not finite", who, i % stages, i / stages);
+        if (check_layer_sets(e, who, plan.skip, plan.n_skip, plan.perturb, plan.n_perturb)) return 2;
+        if (plan.pag && plan.n_skip == 0 && plan.n_perturb == 0)
+            for (int i = 0; i < ncalls; ++i)
+                LT_REQUIRE(plan.slg[i] == 0.0f, "%s: both layer sets are empty, and stage %d of interval %d has a non-zero scale: the third "
                            "prediction would be the conditional one", who, i % stages, i / stages);
         if (ensure_skip_buf(e)) return 1;
     }
-    const long long n = (long long)a->batch * e->cfg.in_channels * a->latent_h * a->latent_w;
-    const CfgSchedule cs{cfg_host, rule, reuse_host, slg, project};
-    ProjectScope form_scope(e, project ? project->form : 0);
-    return ode_fixed_grid(e, z_dev, traj_dev, final_dev, tgrid_host, n_grid, method, 1, t_round, a, s, n, nullptr, nullptr, &cs);
+    ProjectScope form_scope(e, plan.project_form);
+    return ode_fixed_grid(e, {z_dev, traj_dev, final_dev, tgrid_host, n_grid, 1, t_round, a, s, dense_elems(e, a), nullptr, method}, plan, nullptr);
 }
 
 }  // namespace
 
 extern "C" int lt_sample_ode_cfg_schedule(lt_engine* e, const void* z_dev, void* traj_dev, void* final_dev, const float* tgrid_host, int32_t n_grid,
                                           int32_t method, const float* cfg_host, int32_t t_round, const lt_step_args* a, void* stream) {
-    return sample_cfg_table(e, "lt_sample_ode_cfg_schedule", z_dev, traj_dev, final_dev, tgrid_host, n_grid, method, cfg_host, nullptr, t_round, a,
-                            (hipStream_t)stream);
+    return sample_cfg_table(e, "lt_sample_ode_cfg_schedule", z_dev, traj_dev, final_dev, tgrid_host, n_grid, method, GuidancePlan::of_table(cfg_host),
+                            t_round, a, (hipStream_t)stream);
 }
 
 // ---- rescaled and norm-limited guidance: a per-sample factor on every guided stage -------------------------------------------
@@ -537,8 +505,8 @@ extern "C" int lt_sample_ode_cfg_rule(lt_engine* e, const void* z_dev, void* tra
                                       int32_t method, const float* cfg_host, float rescale, float norm_limit, int32_t t_round, const lt_step_args* a,
                                       void* stream) {
     const float rule[2] = {rescale, norm_limit};
-    return sample_cfg_table(e, "lt_sample_ode_cfg_rule", z_dev, traj_dev, final_dev, tgrid_host, n_grid, method, cfg_host, rule, t_round, a,
-                            (hipStream_t)stream);
+    return sample_cfg_table(e, "lt_sample_ode_cfg_rule", z_dev, traj_dev, final_dev, tgrid_host, n_grid, method, GuidancePlan::of_rule(cfg_host, rule),
+                            t_round, a, (hipStream_t)stream);
 }
 
 // One guided evaluation under the rule, at a->cfg_scale.  The three parameters reach the engine's fixed device words through a launch in
@@ -561,9 +529,8 @@ extern "C" int lt_forward_cfg_rule(lt_engine* e, const void* x_dev, const float*
 extern "C" int lt_sample_ode_cfg_project(lt_engine* e, const void* z_dev, void* traj_dev, void* final_dev, const float* tgrid_host, int32_t n_grid,
                                          int32_t method, const float* cfg_host, int32_t form, float eta, float momentum, float norm_threshold,
                                          int32_t zero_init, int32_t t_round, const lt_step_args* a, void* stream) {
-    const ProjectCall pr{form, {eta, momentum, norm_threshold}, zero_init};
-    return sample_cfg_table(e, "lt_sample_ode_cfg_project", z_dev, traj_dev, final_dev, tgrid_host, n_grid, method, cfg_host, nullptr, t_round, a,
-                            (hipStream_t)stream, nullptr, false, nullptr, &pr);
+    const GuidancePlan plan = GuidancePlan::of_project(cfg_host, form == LT_PROJECT_APG, form, eta, momentum, norm_threshold, zero_init);
+    return sample_cfg_table(e, "lt_sample_ode_cfg_project", z_dev, traj_dev, final_dev, tgrid_host, n_grid, method, plan, t_round, a, (hipStream_t)stream);
 }
 
 // One guided evaluation under a projected form, at a->cfg_scale.  The four parameters reach the engine's fixed device words through a launch
@@ -582,35 +549,21 @@ extern "C" int lt_forward_cfg_project(lt_engine* e, const void* x_dev, const flo
     LT_REQUIRE(keep_momentum == 0 || keep_momentum == 1, "%s: keep_momentum %d is not 0 (start from zero) or 1 (continue)", who, keep_momentum);
     LT_REQUIRE(form == LT_PROJECT_APG || keep_momentum == 0, "%s: keep_momentum belongs to APG; CFG-Zero* carries no momentum", who);
     if (check_guided_halves(e, who, a)) return 2;
-    int want[4];
-    Trajectory::delta_sig_of(e, a, want);
-    if (keep_momentum) {
-        const int* have = e->proj_sig;
-        LT_REQUIRE(have[0] != 0, "%s: no stored momentum to continue from: no projected APG evaluation was made, or lt_prepare_prompt / "
-                   "lt_prepare_labels was called since", who);
-        LT_REQUIRE(have[0] == want[0] && have[1] == want[1] && have[2] == want[2] && have[3] == want[3],
-                   "%s: the stored momentum is of another shape: %d samples of %d channels at %dx%d, the call has %d samples of %d channels at "
-                   "%dx%d", who, have[0], have[3], have[1], have[2], want[0], want[3], want[1], want[2]);
-    }
+    if (keep_momentum && check_stored(e, who, LT_STORED_MOMENTUM, a, "momentum", "continue from", "no projected APG evaluation was made")) return 2;
     if (ensure_project(e)) return 1;
     if (form != LT_PROJECT_APG) { eta = 1.f; momentum = 0.f; norm_threshold = INFINITY; }  // (not read; the words hold no leftovers)
     if (launch_guidance_project_params_store(e->p_par, a->cfg_scale, eta, momentum, norm_threshold, s)) return 1;
-    if (form == LT_PROJECT_APG) {
-        e->proj_sig[0] = 0;  // (until the evaluation that rewrites it has been issued whole)
-        if (!keep_momentum) LT_CHECK_HIP(hipMemsetAsync(e->p_mom, 0, (size_t)want[0] * want[3] * want[1] * want[2] * sizeof(float), s));
-    }
+    if (form == LT_PROJECT_APG && !keep_momentum && zero_momentum(e, a, s)) return 1;
     ProjectScope form_scope(e, form);
-    if (int rc = forward_graphed(e, x_dev, t_dev, out_dev, a, 1, s, {LT_KIND_RULE, nullptr, e->p_par})) return rc;
-    if (form == LT_PROJECT_APG) Trajectory::delta_sig_of(e, a, e->proj_sig);
-    return 0;
+    return forward_rewriting(e, form == LT_PROJECT_APG ? LT_STORED_MOMENTUM : LT_STORED_NONE, x_dev, t_dev, out_dev, a, 1, s, {LT_KIND_RULE, nullptr, e->p_par});
 }
 
 // ---- guidance reuse: the cond - uncond difference taken on refresh stages, reused on half-row stages in between ----------------
 extern "C" int lt_sample_ode_cfg_reuse(lt_engine* e, const void* z_dev, void* traj_dev, void* final_dev, const float* tgrid_host, int32_t n_grid,
                                        int32_t method, const float* cfg_host, const int32_t* reuse_host, int32_t t_round, const lt_step_args* a,
                                        void* stream) {
-    return sample_cfg_table(e, "lt_sample_ode_cfg_reuse", z_dev, traj_dev, final_dev, tgrid_host, n_grid, method, cfg_host, nullptr, t_round, a,
-                            (hipStream_t)stream, reuse_host, true);
+    return sample_cfg_table(e, "lt_sample_ode_cfg_reuse", z_dev, traj_dev, final_dev, tgrid_host, n_grid, method,
+                            GuidancePlan::of_reuse(cfg_host, reuse_host), t_round, a, (hipStream_t)stream);
 }
 
 // One guided evaluation at a->cfg_scale that stores the difference (mode 0: lt_forward_cfg's result) or evaluates the cond rows and reuses it
@@ -625,41 +578,27 @@ extern "C" int lt_forward_cfg_reuse(lt_engine* e, const void* x_dev, const float
     if (check_step_shape(e, who, a)) return 2;
     LT_REQUIRE(std::isfinite(a->cfg_scale), "%s: the scale is not finite", who);
     if (check_guided_halves(e, who, a)) return 2;
-    if (mode == 1) {
-        int want[4];
-        Trajectory::delta_sig_of(e, a, want);
-        const int* have = e->delta_sig;
-        LT_REQUIRE(have[0] != 0, "%s: no stored cond - uncond difference to reuse: none was taken (mode 0), or lt_prepare_prompt / "
-                   "lt_prepare_labels was called since", who);
-        LT_REQUIRE(have[0] == want[0] && have[1] == want[1] && have[2] == want[2] && have[3] == want[3],
-                   "%s: the stored cond - uncond difference is of another shape: %d samples of %d channels at %dx%d, the call has %d samples of %d "
-                   "channels at %dx%d", who, have[0], have[3], have[1], have[2], want[0], want[3], want[1], want[2]);
-    }
+    if (mode == 1 && check_stored(e, who, LT_STORED_DELTA, a, "cond - uncond difference", "reuse", "none was taken (mode 0)")) return 2;
     if (ensure_delta(e)) return 1;
     if (launch_guidance_params_store(e->g_cfg, a->cfg_scale, 0.f, INFINITY, (hipStream_t)stream)) return 1;
-    if (mode == 0) e->delta_sig[0] = 0;  // (until the evaluation that rewrites it has been issued whole)
-    if (int rc = forward_graphed(e, x_dev, t_dev, out_dev, a, 1, (hipStream_t)stream, {mode ? LT_KIND_REUSE_AGAIN : LT_KIND_REUSE_STORE, nullptr, e->g_cfg}))
-        return rc;
-    if (mode == 0) Trajectory::set_delta_sig(e, a);
-    return 0;
+    return forward_rewriting(e, mode ? LT_STORED_NONE : LT_STORED_DELTA, x_dev, t_dev, out_dev, a, 1, (hipStream_t)stream,
+                             {mode ? LT_KIND_REUSE_AGAIN : LT_KIND_REUSE_STORE, nullptr, e->g_cfg});
 }
 
 // ---- skip-layer guidance: a third prediction with a set of blocks left out, pushed away from -----------------------------------
 extern "C" int lt_sample_ode_cfg_slg(lt_engine* e, const void* z_dev, void* traj_dev, void* final_dev, const float* tgrid_host, int32_t n_grid,
                                      int32_t method, const float* cfg_host, const float* slg_host, const int32_t* skip_host, int32_t n_skip,
                                      int32_t t_round, const lt_step_args* a, void* stream) {
-    const SlgCall slg{slg_host, skip_host, n_skip};
-    return sample_cfg_table(e, "lt_sample_ode_cfg_slg", z_dev, traj_dev, final_dev, tgrid_host, n_grid, method, cfg_host, nullptr, t_round, a,
-                            (hipStream_t)stream, nullptr, false, &slg);
+    return sample_cfg_table(e, "lt_sample_ode_cfg_slg", z_dev, traj_dev, final_dev, tgrid_host, n_grid, method,
+                            GuidancePlan::of_slg(cfg_host, slg_host, skip_host, n_skip, nullptr, 0, false), t_round, a, (hipStream_t)stream);
 }
 
 // ---- perturbed-attention guidance: the third prediction runs the blocks of P with the identity as their attention map -----------
 extern "C" int lt_sample_ode_cfg_pag(lt_engine* e, const void* z_dev, void* traj_dev, void* final_dev, const float* tgrid_host, int32_t n_grid,
                                      int32_t method, const float* cfg_host, const float* pag_host, const int32_t* skip_host, int32_t n_skip,
                                      const int32_t* perturb_host, int32_t n_perturb, int32_t t_round, const lt_step_args* a, void* stream) {
-    const SlgCall slg{pag_host, skip_host, n_skip, perturb_host, n_perturb, true};
-    return sample_cfg_table(e, "lt_sample_ode_cfg_pag", z_dev, traj_dev, final_dev, tgrid_host, n_grid, method, cfg_host, nullptr, t_round, a,
-                            (hipStream_t)stream, nullptr, false, &slg);
+    return sample_cfg_table(e, "lt_sample_ode_cfg_pag", z_dev, traj_dev, final_dev, tgrid_host, n_grid, method,
+                            GuidancePlan::of_slg(cfg_host, pag_host, skip_host, n_skip, perturb_host, n_perturb, true), t_round, a, (hipStream_t)stream);
 }
 
 // One guided evaluation at (cfg_scale, slg_scale): the degraded evaluation of the cond rows - the blocks of S left out, the blocks of P
@@ -684,12 +623,8 @@ static int forward_cfg_sets(lt_engine* e, const char* who, bool pag, const void*
     if (slg_scale == 0.f) return forward_graphed(e, x_dev, t_dev, out_dev, &own, 1, s);  // lt_forward_cfg's launches and result
     if (ensure_skip_buf(e)) return 1;
     if (launch_slg_params_store(e->g_cfg, cfg_scale, slg_scale, s)) return 1;
-    {
-        SkipScope scope(e);
-        if (scope.set(who, skip_host, n_skip, perturb_host, n_perturb)) return 2;
-        if (int rc = forward_graphed(e, x_dev, t_dev, nullptr, &own, 1, s, {LT_KIND_SLG_STORE, nullptr, e->g_cfg})) return rc;
-    }
-    return forward_graphed(e, x_dev, t_dev, out_dev, &own, 1, s, {cfg_scale == 1.0f ? LT_KIND_SLG_COND : LT_KIND_SLG_GUIDED, nullptr, e->g_cfg});
+    return forward_slg_pair(e, who, GuidancePlan::of_slg(nullptr, nullptr, skip_host, n_skip, perturb_host, n_perturb, pag), x_dev, t_dev, out_dev, &own, s,
+                            cfg_scale == 1.0f ? LT_KIND_SLG_COND : LT_KIND_SLG_GUIDED, e->g_cfg, nullptr);
 }
 
 extern "C" int lt_forward_cfg_slg(lt_engine* e, const void* x_dev, const float* t_dev, void* out_dev, float cfg_scale, float slg_scale,
@@ -724,29 +659,25 @@ int check_multistep(const char* who, int n_grid, const float* coef_host, int cor
 // The multistep loop on a state of n elements (elementwise, so a packed batch's flat state runs through it as it is).  Evaluation i runs at
 // tgrid[i] on the predicted state and overwrites ring slot i % 4 of e->kbuf, the slot of f_{i-4}.  Without a corrector the state ping-pongs
 // through e->ys like a fixed-grid step; with one, ys holds the corrected states y_i and e->ymid the predictor p_{i+1} the next evaluation
-// reads.  Guidance scales and rule parameters are committed behind the stage times exactly as ode_fixed_grid does (stages = 1).
-int ode_multistep(lt_engine* e, const void* z_dev, void* traj_dev, void* final_dev, const float* tgrid_host, int n_grid, const float* coef_host,
-                  int corrector, int use_cfg, int t_round, const lt_step_args* a, hipStream_t s, long long n, const PackedCall* pc,
-                  const CfgSchedule* cs = nullptr) {
-    const int B = a->batch;
-    const int ncalls = n_grid - 1;
+// reads.  The plan's tail is committed behind the stage times and applied exactly as ode_fixed_grid does (stages = 1).
+int ode_multistep(lt_engine* e, const GridCall& c, const GuidancePlan& plan) {
+    const lt_step_args* a = c.a;
+    hipStream_t s = c.s;
+    const float *tgrid_host = c.tgrid, *coef_host = c.coef;
+    const int B = a->batch, ncalls = c.n_grid - 1, corrector = c.corrector;
+    const long long n = c.n;
     const bool bf = a->io_dtype == LT_BF16;
-    const int nsent = ncalls * B + (cs ? ncalls : 0) + (cs && cs->rule ? 2 : 0);
+    const int nsent = ncalls * B + plan.tail_floats(ncalls);
     float* tp = e->times.begin(nsent, s);
     if (!tp) return 1;
     for (int i = 0; i < ncalls; ++i) {
-        const float tv = (t_round && bf) ? bf16_round_host(tgrid_host[i]) : tgrid_host[i];
+        const float tv = (c.t_round && bf) ? bf16_round_host(tgrid_host[i]) : tgrid_host[i];
         for (int b = 0; b < B; ++b) tp[(size_t)i * B + b] = tv;
     }
-    if (cs) memcpy(tp + (size_t)ncalls * B, cs->table, (size_t)ncalls * sizeof(float));
-    if (cs && cs->rule) memcpy(tp + (size_t)ncalls * B + ncalls, cs->rule, 2 * sizeof(float));
-    if (e->times.commit(nsent, s)) return 1;
-    if (cs && cs->rule)
-        LT_CHECK_HIP(hipMemcpyAsync(e->g_cfg + 1, e->times.dev + (size_t)ncalls * B + ncalls, 2 * sizeof(float), hipMemcpyDeviceToDevice, s));
-    Trajectory tr{e, a, use_cfg, s, (size_t)n * (bf ? 2 : 4)};
-    tr.pc = pc;
-    if (cs) { tr.cfg_host = cs->table; tr.cfg_dev = e->times.dev + (size_t)ncalls * B; tr.cfg_rule = cs->rule != nullptr; tr.reuse_host = cs->reuse; }
-    if (tr.start(z_dev, traj_dev, true)) return 1;
+    plan.fill_tail(tp + GuidancePlan::table_offset(ncalls, B), ncalls);
+    if (e->times.commit(nsent, s) || apply_plan(e, plan, a, ncalls, s)) return 1;
+    Trajectory tr{e, a, c.use_cfg, s, (size_t)n * (bf ? 2 : 4), c.pc, plan, ncalls};
+    if (tr.start(c.z, c.traj, true)) return 1;
     const int dt_code = bf ? 1 : 0;
     const void* p = tr.y0();  // p_i, the state evaluation i reads: p_0 = z
     for (int i = 0; i < ncalls; ++i) {
@@ -772,10 +703,10 @@ int ode_multistep(lt_engine* e, const void* z_dev, void* traj_dev, void* final_d
             p = e->ymid;
         }
     }
-    if (!corrector) return tr.finish(final_dev);
+    if (!corrector) return tr.finish(c.final);
     // the result p_N lies in ymid: the last slot of the record, and the final state
-    if (traj_dev) LT_CHECK_HIP(hipMemcpyAsync((char*)traj_dev + (size_t)ncalls * tr.sbytes, e->ymid, tr.sbytes, hipMemcpyDeviceToDevice, s));
-    if (final_dev) LT_CHECK_HIP(hipMemcpyAsync(final_dev, e->ymid, tr.sbytes, hipMemcpyDeviceToDevice, s));
+    if (c.traj) LT_CHECK_HIP(hipMemcpyAsync((char*)c.traj + (size_t)ncalls * tr.sbytes, e->ymid, tr.sbytes, hipMemcpyDeviceToDevice, s));
+    if (c.final) LT_CHECK_HIP(hipMemcpyAsync(c.final, e->ymid, tr.sbytes, hipMemcpyDeviceToDevice, s));
     return tr.finish(nullptr);
 }
 
@@ -793,9 +724,8 @@ extern "C" int lt_sample_ode_multistep(lt_engine* e, const void* z_dev, void* tr
     if (refuse_if_capturing((hipStream_t)stream, who)) return 2;  // (the stage times travel through a host staging buffer that the next call rewrites)
     LtOptScope opt_scope(&e->opts);
     if (check_step_shape(e, who, a)) return 2;
-    const long long n = (long long)a->batch * e->cfg.in_channels * a->latent_h * a->latent_w;
-    if (!cfg_host && !rule_on)
-        return ode_multistep(e, z_dev, traj_dev, final_dev, tgrid_host, n_grid, coef_host, corrector, use_cfg, t_round, a, (hipStream_t)stream, n, nullptr);
+    GridCall c{z_dev, traj_dev, final_dev, tgrid_host, n_grid, use_cfg, t_round, a, (hipStream_t)stream, dense_elems(e, a), nullptr, 0, coef_host, corrector};
+    if (!cfg_host && !rule_on) return ode_multistep(e, c, {});
     // a scale per evaluation [and the rule]: the checks of sample_cfg_table
     std::vector<float> constant;
     if (!cfg_host) {  // the rule at one scale
@@ -804,8 +734,8 @@ extern "C" int lt_sample_ode_multistep(lt_engine* e, const void* z_dev, void* tr
     }
     const float rule[2] = {rescale, norm_limit};
     if (check_guided_table(e, who, a, cfg_host, n_grid - 1, 1, rule_on ? rule : nullptr)) return 2;
-    const CfgSchedule cs{cfg_host, rule_on ? rule : nullptr};
-    return ode_multistep(e, z_dev, traj_dev, final_dev, tgrid_host, n_grid, coef_host, corrector, 1, t_round, a, (hipStream_t)stream, n, nullptr, &cs);
+    c.use_cfg = 1;
+    return ode_multistep(e, c, rule_on ? GuidancePlan::of_rule(cfg_host, rule) : GuidancePlan::of_table(cfg_host));
 }
 
 // lt_sample_ode_multistep with a scale and a reuse flag per evaluation: the same body, the checks of lt_sample_ode_cfg_reuse
@@ -822,9 +752,8 @@ extern "C" int lt_sample_ode_multistep_cfg_reuse(lt_engine* e, const void* z_dev
     if (check_guided_table(e, who, a, cfg_host, n_grid - 1, 1, nullptr)) return 2;
     if (check_reuse_flags(who, cfg_host, reuse_host, n_grid - 1)) return 2;
     if (ensure_delta(e)) return 1;
-    const long long n = (long long)a->batch * e->cfg.in_channels * a->latent_h * a->latent_w;
-    const CfgSchedule cs{cfg_host, nullptr, reuse_host};
-    return ode_multistep(e, z_dev, traj_dev, final_dev, tgrid_host, n_grid, coef_host, corrector, 1, t_round, a, (hipStream_t)stream, n, nullptr, &cs);
+    return ode_multistep(e, {z_dev, traj_dev, final_dev, tgrid_host, n_grid, 1, t_round, a, (hipStream_t)stream, dense_elems(e, a), nullptr, 0, coef_host, corrector},
+                         GuidancePlan::of_reuse(cfg_host, reuse_host));
 }
 
 // lt_sample_ode_multistep on a packed batch: z, every trajectory slot and the final state are flat buffers of the size list's layout (packed.hip)
@@ -838,8 +767,8 @@ extern "C" int lt_sample_ode_multistep_packed(lt_engine* e, const void* z_flat_d
     LtOptScope opt_scope(&e->opts);
     PackedCall pc{};
     if (int rc = packed_call_begin(e, who, hw_host, a, use_cfg, &pc, (hipStream_t)stream)) return rc;
-    return ode_multistep(e, z_flat_dev, traj_flat_dev, final_flat_dev, tgrid_host, n_grid, coef_host, corrector, use_cfg, t_round, a, (hipStream_t)stream,
-                         pc.elems, &pc);
+    return ode_multistep(e, {z_flat_dev, traj_flat_dev, final_flat_dev, tgrid_host, n_grid, use_cfg, t_round, a, (hipStream_t)stream, pc.elems, &pc, 0, coef_host,
+                          corrector}, {});
 }
 
 // ---- multi-view (visual-anagram) sampling ------------------------------------------------------------------------------------------
