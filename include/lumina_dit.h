@@ -253,6 +253,38 @@ int lt_set_views(lt_engine* e, const int32_t* perm_dev, const float* vsign_host,
 int lt_sample_views(lt_engine* e, const void* z_dev, void* traj_dev, void* final_dev, const float* tgrid_host, int32_t n_grid,
                     int32_t method, const lt_step_args* a, void* stream);
 
+/* ---- tiled (MultiDiffusion, Bar-Tal et al. 2023) sampling: one canvas latent, the model on overlapping windows of it --------------------------
+ * ONE canvas latent [1, C, Hc, Wc] is kept.  Every evaluation crops n windows of one size h x w out of it, evaluates them as ONE
+ * forward_with_cfg of 2 n rows at the window size (rows 0 .. n-1 the crops with the window prompts, rows n .. 2n-1 the negative prompts), and
+ * fuses the n predictions into the canvas velocity: per pixel, the sum over the windows that hold it of weight * prediction, divided by the
+ * sum of those weights.  lumina-t2x_amd/transport/tiled.py is the definition (the reference has no such sampler): fuse states the arithmetic -
+ * every product and sum one fp32 operation in window order, one division, one rounding to the state dtype - and the calls equal it bit for bit.
+ * Nothing in the calls is family-specific: every variant is served, with labels prepared by lt_prepare_labels in the same row layout.
+ * lt_set_windows: offsets_host int32 [n][2] = (top, left) of each window in latent pixels (HOST), weight_dev float [win_h * win_w] (DEVICE) or
+ * NULL for all ones.  The table goes into engine-owned memory (allocated by the first call: the weights, the per-pixel weight sums and the
+ * window rows going into and coming out of the model), the sums are formed on the device and the call SYNCHRONISES the stream once, to refuse
+ * a canvas with a pixel that lies under no window or under weights whose sum is not finite and above 0.  n = 0 drops the table.  Refused by
+ * name, with the table in force left as it was: a null engine or offset table; n < 0, n > 64 or 2 n > max_batch; sizes or offsets that are
+ * not multiples of the patch size; a window larger than, or outside, the canvas; a window of more than max_tokens tokens or with a grid above
+ * the RoPE table; a canvas with more pixels than its n windows; a stream under capture.
+ * The canvas always fits the engine's state buffers: a covered canvas has at most n * h * w pixels, n <= max_batch / 2 and h * w pixels are
+ * at most max_tokens tokens, and the state buffers hold max_batch samples of max_tokens tokens.
+ * lt_forward_tiled: one canvas evaluation.  y_dev / v_dev [1, C, Hc, Wc] in a->io_dtype, t_dev float [2 n]; a->latent_h / latent_w are the
+ * WINDOW's, a->batch = 2 n.  Three steps: the gather, forward_with_cfg of the 2 n rows through the evaluation's own graph cache (no new graph
+ * key: it IS an lt_forward_cfg of that shape), the fusion.
+ * lt_sample_ode_tiled: lt_sample_ode(use_cfg = 1) with the canvas as the state and lt_forward_tiled's three steps as every stage's velocity:
+ * stage times, dt handling and every stage / closing combine are lt_sample_ode's.  z [1, C, Hc, Wc]; traj_dev (may be NULL) receives the n_grid
+ * canvases, final_dev (may be NULL) the last.  lt_last_nfe = (n_grid - 1) * stages, lt_last_eval_rows = 2 n times that.  No synchronisation,
+ * no host read.
+ * Both refuse by name, before anything is launched: no window table; a->batch other than 2 n or a latent other than the table's window; a
+ * regional prompt; a layer-skip or perturb set; a conditioning prepared for another batch; lt_sample_ode_tiled also a stream under capture, a
+ * grid of fewer than 2 points and an unknown method. */
+int lt_set_windows(lt_engine* e, const int32_t* offsets_host, int32_t n, int32_t win_h, int32_t win_w, int32_t canvas_h, int32_t canvas_w,
+                   const float* weight_dev, void* stream);
+int lt_forward_tiled(lt_engine* e, const void* y_dev, const float* t_dev, void* v_dev, const lt_step_args* a, void* stream);
+int lt_sample_ode_tiled(lt_engine* e, const void* z_dev, void* traj_dev, void* final_dev, const float* tgrid_host, int32_t n_grid, int32_t method,
+                        int32_t t_round_to_state_dtype, const lt_step_args* a, void* stream);
+
 /* ---- multi-view sampling, Phase Upscale: visual_anagrams/generate.py:465-494 with midpoint_solver_extra (:222-262) -------------------------
  * lt_set_softmax_rule: the model of that phase is visual_anagrams/models/nextdit.py, which differs from LT_VARIANT_NEXT_T2I's model in ONE
  * scalar: under proportional_attn its self-attention softmax scale is log(N, base_seqlen) / sqrt(head_dim) (LT_SOFTMAX_ANAGRAM) where the T2I
@@ -818,6 +850,19 @@ int lt_op_views_gather(const void* y_dev, const int32_t* perm_dev, const float* 
                        int32_t V, int32_t C, int32_t HW, int32_t dtype, void* stream);
 int lt_op_views_reduce(const void* y_dev, const void* f_dev, const int32_t* iperm_dev, const float* isign_dev, void* out_dev, float dt,
                        int32_t V, int32_t C, int32_t HW, int32_t dtype, void* stream);
+/* the three kernels of lt_forward_tiled on caller-owned buffers.  offsets_host int32 [n][2] = (top, left) (HOST), 1 <= n <= 64 windows of
+ * win_h x win_w, every one inside the canvas (refused by name otherwise, before anything is launched); weight_dev float [win_h * win_w]
+ * (NULL: ones), dtype LT_F32 or LT_BF16.
+ *   gather: out [n, C, win_h, win_w] = the crops of y [C, canvas_h, canvas_w] (exact copies; nothing behind row n - 1 is written)
+ *   cover:  wsum float [canvas_h * canvas_w] = per pixel the fp32 sum, in window order, of the weights of the windows that hold it; bad (one
+ *           int32, zeroed by the call) counts the pixels whose sum is not finite and above 0
+ *   reduce: out [C, canvas_h, canvas_w] = R((sum_k weight * f [n, C, win_h, win_w]) / wsum): transport/tiled.py fuse (R: round to dtype) */
+int lt_op_windows_gather(const void* y_dev, const int32_t* offsets_host, int32_t n, int32_t win_h, int32_t win_w, int32_t canvas_h, int32_t canvas_w,
+                         void* out_dev, int32_t C, int32_t dtype, void* stream);
+int lt_op_windows_reduce(const void* f_dev, const int32_t* offsets_host, int32_t n, int32_t win_h, int32_t win_w, int32_t canvas_h, int32_t canvas_w,
+                         const float* weight_dev, const float* wsum_dev, void* out_dev, int32_t C, int32_t dtype, void* stream);
+int lt_op_windows_cover(const int32_t* offsets_host, int32_t n, int32_t win_h, int32_t win_w, int32_t canvas_h, int32_t canvas_w,
+                        const float* weight_dev, float* wsum_dev, int32_t* bad_dev, void* stream);
 /* one fused step kernel of lt_sample_sde on caller-owned buffers of n elements (any n >= 1; buffers that are not 16-byte aligned take the
  * one-element-per-thread form).  op = LT_SDE_OP_*, rec_host = the stage's LT_SDE_REC floats, dtype LT_F32 or LT_BF16 (R: round to dtype):
  *   EULER      out = R(R(x + R(drift(x, v) * dt)) + R(q * R(w * sqrt_dt)))       drift(x, v) = R(v + R(D * R(R(R(r * v) - x) / var)))

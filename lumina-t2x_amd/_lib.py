@@ -114,6 +114,9 @@ _SIGNATURES: Dict[str, tuple] = {
                                            C.POINTER(LtStepArgs), _vp]),
     "lt_set_views": (_i32, [_vp, _vp, C.POINTER(_f32), C.POINTER(_f32), _i32, _i32, _i32, _vp]),
     "lt_sample_views": (_i32, [_vp, _vp, _vp, _vp, C.POINTER(_f32), _i32, _i32, C.POINTER(LtStepArgs), _vp]),
+    "lt_set_windows": (_i32, [_vp, C.POINTER(_i32), _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "lt_forward_tiled": (_i32, [_vp, _vp, _vp, _vp, C.POINTER(LtStepArgs), _vp]),
+    "lt_sample_ode_tiled": (_i32, [_vp, _vp, _vp, _vp, C.POINTER(_f32), _i32, _i32, _i32, C.POINTER(LtStepArgs), _vp]),
     "lt_set_softmax_rule": (_i32, [_vp, _i32]),
     "lt_sample_views_guided": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_f32), C.POINTER(_f32), _i32, C.POINTER(LtStepArgs), _vp]),
     "lt_sample_sde": (_i32, [_vp, _vp, _vp, _vp, _vp, C.POINTER(_f32), _i32, _i32, _i32, C.POINTER(_f32), _i32, C.POINTER(LtStepArgs), _vp]),
@@ -197,6 +200,9 @@ _SIGNATURES: Dict[str, tuple] = {
     "lt_op_views_invert": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp]),
     "lt_op_views_gather": (_i32, [_vp, _vp, _vp, _vp, _vp, _f32, _i32, _i32, _i32, _i32, _vp]),
     "lt_op_views_reduce": (_i32, [_vp, _vp, _vp, _vp, _vp, _f32, _i32, _i32, _i32, _i32, _vp]),
+    "lt_op_windows_gather": (_i32, [_vp, C.POINTER(_i32), _i32, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _vp]),
+    "lt_op_windows_reduce": (_i32, [_vp, C.POINTER(_i32), _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _vp]),
+    "lt_op_windows_cover": (_i32, [C.POINTER(_i32), _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "lt_op_views_guided_gather": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, C.POINTER(_f32), _i32, _i32, _i32, _i32, _vp]),
     "lt_op_sde_step": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_f32), _i64, _i32, _vp]),
     "lt_op_rk_stage": (_i32, [_vp, C.POINTER(_vp), C.POINTER(_f32), _i32, _f32, _vp, _i64, _i32, _vp]),

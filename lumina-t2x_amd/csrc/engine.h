@@ -8,6 +8,7 @@
 #include "../../include/lumina_dit.h"
 #include "common.h"
 #include "eval_kind.h"
+#include "kernels.h"
 #include "options.h"
 
 struct DevBuf {
@@ -209,6 +210,16 @@ struct lt_engine {
     int *vw_perm = nullptr, *vw_iperm = nullptr, *vw_hits = nullptr;  // [V][h w], [V][h w], [V h w + 1]
     float *vw_vsign = nullptr, *vw_isign = nullptr;                   // [V][in_channels]
     int vw_V = 0, vw_h = 0, vw_w = 0;
+    // tiled (MultiDiffusion) sampling (lt_set_windows / lt_forward_tiled / lt_sample_ode_tiled, tiled.hip): the window table
+    // (tw.n = 0: none; it travels as a kernel argument), the engine's copy of the window weights (tw_has_weight false: all ones, not read) and
+    // the per-pixel weight sums, and the window rows going into and coming out of the model.  The four buffers are allocated by the first
+    // lt_set_windows at their largest size - weights: one window of max_tokens tokens; sums: max_batch / 2 such windows; rows: max_batch such
+    // samples - and kept for the engine's life (a graph the caller recorded around lt_forward_tiled holds the pointers)
+    WindowTable tw = {};
+    bool tw_has_weight = false;
+    float *tw_weight = nullptr, *tw_wsum = nullptr;
+    int* tw_bad = nullptr;
+    void *tw_in = nullptr, *tw_out = nullptr;
     // HIP graphs of one model evaluation (forward_graphed): fixed staging buffers the captured kernels read / write, a private
     // stream to capture on (the caller's stream may be the legacy null stream, which cannot capture), cached executables
     struct GraphTally { double flops[3] = {0, 0, 0}; long long launches[3] = {0, 0, 0}; };  // what one replay stands for, per kernel class
@@ -333,3 +344,5 @@ int refuse_profile_if_capturing(const lt_engine* e, hipStream_t s, const char* w
 int softmax_scale_for(const lt_engine* e, const lt_step_args* a, int N, float* scale);
 // frees the tables of lt_set_views (samplers.hip)
 void drop_views(lt_engine* e);
+// frees the buffers of lt_set_windows (samplers.hip)
+void drop_windows(lt_engine* e);

@@ -1470,6 +1470,7 @@ extern "C" void lt_destroy(lt_engine* e) {
     if (e->reg_txt) (void)hipFree(e->reg_txt);
     if (e->reg_qmap) (void)hipFree(e->reg_qmap);
     drop_views(e);
+    drop_windows(e);
     if (e->moe_rec) (void)hipFree(e->moe_rec);
     if (e->moe_force) (void)hipFree(e->moe_force);
     for (int k = 0; k < 3; ++k)

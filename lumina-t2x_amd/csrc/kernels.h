@@ -441,6 +441,23 @@ int launch_views_reduce(const void* y, const void* f, const int* iperm, const fl
 //   R(y + inverse_view_v(R(f0 * half_dt))); guidance / noise [C, HW] like y; coef = { ft, f1t, kc, k1c } on the HOST
 int launch_views_guided_gather(const void* y, const void* guidance, const void* noise, const int* perm, const float* vsign, const float* isign,
                                const void* f0, void* out, float half_dt, const float* coef, int V, int C, int HW, int dtype, hipStream_t stream);
+// tiled (MultiDiffusion) sampling (tiled.hip): n <= LT_WINDOWS_MAX windows of one size h x w at (top, left) offsets into one canvas latent
+// [C, Hc, Wc].  The table travels as a kernel argument; window_table_build is the one place that fills it and checks it (every window inside
+// the canvas), and every launcher runs that check again on the table it is given.  State dtype 0 f32, 1 bf16
+//   gather: out [n, C, h, w] = the crops of y [C, Hc, Wc], exact copies
+//   cover:  wsum float [Hc * Wc] = the sum over the windows that hold a pixel of weight [h * w] (null: ones), fp32 in window order; bad (one
+//           int, zeroed by the call) counts the pixels whose sum is not finite and strictly positive
+//   reduce: out [C, Hc, Wc] = R((sum_k weight * f[k]) / wsum), f [n, C, h, w]; each product and sum one fp32 operation, in window order
+#define LT_WINDOWS_MAX 64
+struct WindowTable {
+    int n, win_h, win_w, canvas_h, canvas_w;
+    int off[2 * LT_WINDOWS_MAX];  // (top, left) of window k at [2 k], [2 k + 1]
+};
+int window_table_build(const char* who, const int32_t* offsets_host, int n, int win_h, int win_w, int canvas_h, int canvas_w, WindowTable* out);
+int launch_windows_gather(const void* y, const WindowTable& t, void* out, int C, int dtype, hipStream_t stream);
+int launch_windows_cover(const WindowTable& t, const float* weight, float* wsum, int* bad, hipStream_t stream);
+int launch_windows_reduce(const void* f, const WindowTable& t, const float* weight, const float* wsum, void* out, int C, int dtype,
+                          hipStream_t stream);
 // SDE sampling (sde.hip): one fused elementwise step on n elements, op = LT_SDE_OP_*, rec = the stage's 8-float record (host), state dtype
 // 0 f32, 1 bf16; operands an op does not read may be null.  out is fp32 for LT_SDE_OP_LAST_MEAN / LAST_TWEEDIE, the state dtype otherwise
 int launch_sde_step(int op, const void* x, const void* v, const void* w, const void* k1, const void* xp, void* out, void* out2, const float* rec,

@@ -610,6 +610,26 @@ extern "C" int lt_op_views_reduce(const void* y_dev, const void* f_dev, const in
                                   int32_t V, int32_t C, int32_t HW, int32_t dtype, void* stream) {
     return launch_views_reduce(y_dev, f_dev, iperm_dev, isign_dev, out_dev, dt, V, C, HW, dtype, (hipStream_t)stream);
 }
+// tiled sampling (tiled.hip): the offsets are a HOST table here, checked into a WindowTable before anything is launched
+extern "C" int lt_op_windows_gather(const void* y_dev, const int32_t* offsets_host, int32_t n, int32_t win_h, int32_t win_w, int32_t canvas_h,
+                                    int32_t canvas_w, void* out_dev, int32_t C, int32_t dtype, void* stream) {
+    WindowTable t;
+    if (window_table_build("lt_op_windows_gather", offsets_host, n, win_h, win_w, canvas_h, canvas_w, &t)) return 2;
+    return launch_windows_gather(y_dev, t, out_dev, C, dtype, (hipStream_t)stream);
+}
+extern "C" int lt_op_windows_reduce(const void* f_dev, const int32_t* offsets_host, int32_t n, int32_t win_h, int32_t win_w, int32_t canvas_h,
+                                    int32_t canvas_w, const float* weight_dev, const float* wsum_dev, void* out_dev, int32_t C, int32_t dtype,
+                                    void* stream) {
+    WindowTable t;
+    if (window_table_build("lt_op_windows_reduce", offsets_host, n, win_h, win_w, canvas_h, canvas_w, &t)) return 2;
+    return launch_windows_reduce(f_dev, t, weight_dev, wsum_dev, out_dev, C, dtype, (hipStream_t)stream);
+}
+extern "C" int lt_op_windows_cover(const int32_t* offsets_host, int32_t n, int32_t win_h, int32_t win_w, int32_t canvas_h, int32_t canvas_w,
+                                   const float* weight_dev, float* wsum_dev, int32_t* bad_dev, void* stream) {
+    WindowTable t;
+    if (window_table_build("lt_op_windows_cover", offsets_host, n, win_h, win_w, canvas_h, canvas_w, &t)) return 2;
+    return launch_windows_cover(t, weight_dev, wsum_dev, bad_dev, (hipStream_t)stream);
+}
 extern "C" int lt_op_views_guided_gather(const void* y_dev, const void* guidance_dev, const void* noise_dev, const int32_t* perm_dev,
                                          const float* vsign_dev, const float* isign_dev, const void* f0_dev, void* out_dev, float half_dt,
                                          const float* coef_host, int32_t V, int32_t C, int32_t HW, int32_t dtype, void* stream) {

@@ -195,6 +195,7 @@ struct GridCall {
     const float* tgrid; int n_grid, use_cfg, t_round;
     const lt_step_args* a; hipStream_t s; long long n; const PackedCall* pc;
     int method = 0; const float* coef = nullptr; int corrector = 0;
+    bool tiled = false;  // lt_sample_ode_tiled: the state is the canvas, an evaluation is e->tw's windows gathered, evaluated and fused
 };
 struct MaskedBlend { const void *mask, *x1, *noise; };
 
@@ -248,6 +249,13 @@ int ode_fixed_grid(lt_engine* e, const GridCall& c, const GuidancePlan& plan, co
     Trajectory tr{e, a, c.use_cfg, s, (size_t)n * (bf ? 2 : 4), c.pc, plan, ncalls};
     if (tr.start(c.z, c.traj, true)) return 1;
     const int dt_code = bf ? 1 : 0;
+    // one velocity of the state: the model on it, or (tiled) on its windows, whose predictions are fused into `out`
+    auto eval = [&](const void* y, int call, void* out) -> int {
+        if (!c.tiled) return tr.eval(y, call, out);
+        if (launch_windows_gather(y, e->tw, e->tw_in, e->cfg.in_channels, dt_code, s)) return 1;
+        if (tr.eval(e->tw_in, call, e->tw_out)) return 1;
+        return launch_windows_reduce(e->tw_out, e->tw, e->tw_has_weight ? e->tw_weight : nullptr, e->tw_wsum, out, e->cfg.in_channels, dt_code, s);
+    };
     for (int i = 0; i + 1 < n_grid; ++i) {
         void *y0 = tr.y0(), *y1 = tr.y1();
         if (i < plan.zero_init) {  // CFG-Zero*'s zero-init: zero velocity, so the state stays where it is; no evaluation, nothing counted
@@ -267,21 +275,21 @@ int ode_fixed_grid(lt_engine* e, const GridCall& c, const GuidancePlan& plan, co
             return launch_ode_combine_masked(mode, y0, k1, k2, k3, k4, mb->mask, mb->x1, mb->noise, y1, dt_code, dt, t1, (float)(1.0 - (double)t1), n, s);
         };
         if (method == LT_ODE_EULER) {
-            if (tr.eval(y0, c0, e->kbuf[0])) return 1;
+            if (eval(y0, c0, e->kbuf[0])) return 1;
             if (close(0, e->kbuf[0], nullptr, nullptr, nullptr)) return 1;
         } else if (method == LT_ODE_MIDPOINT) {
-            if (tr.eval(y0, c0, e->kbuf[0])) return 1;
+            if (eval(y0, c0, e->kbuf[0])) return 1;
             if (launch_ode_combine(0, y0, e->kbuf[0], nullptr, nullptr, nullptr, e->ymid, dt_code, 0.5f * dt, n, s)) return 1;
-            if (tr.eval(e->ymid, c0 + 1, e->kbuf[1])) return 1;
+            if (eval(e->ymid, c0 + 1, e->kbuf[1])) return 1;
             if (close(0, e->kbuf[1], nullptr, nullptr, nullptr)) return 1;
         } else {
-            if (tr.eval(y0, c0, e->kbuf[0])) return 1;
+            if (eval(y0, c0, e->kbuf[0])) return 1;
             if (launch_ode_combine(1, y0, e->kbuf[0], nullptr, nullptr, nullptr, e->ymid, dt_code, dt, n, s)) return 1;
-            if (tr.eval(e->ymid, c0 + 1, e->kbuf[1])) return 1;
+            if (eval(e->ymid, c0 + 1, e->kbuf[1])) return 1;
             if (launch_ode_combine(2, y0, e->kbuf[0], e->kbuf[1], nullptr, nullptr, e->ymid, dt_code, dt, n, s)) return 1;
-            if (tr.eval(e->ymid, c0 + 2, e->kbuf[2])) return 1;
+            if (eval(e->ymid, c0 + 2, e->kbuf[2])) return 1;
             if (launch_ode_combine(3, y0, e->kbuf[0], e->kbuf[1], e->kbuf[2], nullptr, e->ymid, dt_code, dt, n, s)) return 1;
-            if (tr.eval(e->ymid, c0 + 3, e->kbuf[3])) return 1;
+            if (eval(e->ymid, c0 + 3, e->kbuf[3])) return 1;
             if (close(4, e->kbuf[0], e->kbuf[1], e->kbuf[2], e->kbuf[3])) return 1;
         }
         if (tr.advance(i + 1)) return 1;
@@ -1295,3 +1303,114 @@ extern "C" int lt_debug_cache_read(lt_engine* e, int32_t which, void* dst_dev, i
     return 0;
 }
 extern "C" int64_t lt_last_cache_hits(lt_engine* e) { return e ? e->last_cache_hits : -1; }
+
+// ---- tiled (MultiDiffusion) sampling: one canvas latent, the model on overlapping windows of it, their predictions fused ------
+void drop_windows(lt_engine* e) {
+    if (e->tw_weight) (void)hipFree(e->tw_weight);
+    if (e->tw_wsum) (void)hipFree(e->tw_wsum);
+    if (e->tw_bad) (void)hipFree(e->tw_bad);
+    if (e->tw_in) (void)hipFree(e->tw_in);
+    if (e->tw_out) (void)hipFree(e->tw_out);
+    e->tw_weight = e->tw_wsum = nullptr; e->tw_bad = nullptr; e->tw_in = e->tw_out = nullptr;
+    e->tw.n = 0;
+}
+
+extern "C" int lt_set_windows(lt_engine* e, const int32_t* offsets_host, int32_t n, int32_t win_h, int32_t win_w, int32_t canvas_h, int32_t canvas_w,
+                              const float* weight_dev, void* stream) {
+    const char* who = "lt_set_windows";
+    LT_REQUIRE(e, "%s: null engine", who);
+    hipStream_t s = (hipStream_t)stream;
+    if (refuse_if_capturing(s, who)) return 2;  // (allocates, synchronises)
+    const lt_config& c = e->cfg;
+    if (n == 0) {  // drop the table (the buffers stay: a graph the caller recorded may hold them)
+        LT_CHECK_HIP(hipStreamSynchronize(s));
+        e->tw.n = 0;
+        return 0;
+    }
+    LT_REQUIRE(offsets_host, "%s: null argument (offsets_host: n rows of (top, left))", who);
+    LT_REQUIRE(n >= 1 && n <= LT_WINDOWS_MAX, "%s: n = %d windows (1 .. %d; 0 drops the table)", who, n, LT_WINDOWS_MAX);
+    LT_REQUIRE(2 * (long long)n <= c.max_batch, "%s: %d windows need a batch of 2 n = %d rows (window prompts + negative prompts), max_batch is %d", who,
+               n, 2 * n, c.max_batch);
+    const int p = c.patch_size;
+    LT_REQUIRE(win_h > 0 && win_w > 0 && canvas_h > 0 && canvas_w > 0 && win_h % p == 0 && win_w % p == 0 && canvas_h % p == 0 && canvas_w % p == 0,
+               "%s: window %dx%d / canvas %dx%d: sizes must be positive multiples of the patch size %d", who, win_h, win_w, canvas_h, canvas_w, p);
+    for (int k = 0; k < n; ++k)
+        LT_REQUIRE(offsets_host[2 * k] % p == 0 && offsets_host[2 * k + 1] % p == 0, "%s: the offset (%d, %d) of window %d is not a multiple of the "
+                   "patch size %d", who, offsets_host[2 * k], offsets_host[2 * k + 1], k, p);
+    WindowTable t;
+    if (window_table_build(who, offsets_host, n, win_h, win_w, canvas_h, canvas_w, &t)) return 2;  // (every window inside the canvas)
+    const int hp = win_h / p, wp = win_w / p, wrow = e->v.eol ? wp + 1 : wp;
+    LT_REQUIRE((long long)hp * wrow <= c.max_tokens, "%s: a window of %dx%d has %d latent tokens, max_tokens is %d", who, win_h, win_w, hp * wrow,
+               c.max_tokens);
+    LT_REQUIRE(e->v.rope_1d ? hp * wrow <= e->rope_len : (hp <= e->rope_len && wp <= e->rope_len),
+               "%s: a window grid of %dx%d tokens exceeds the RoPE table (%d)", who, hp, wp, e->rope_len);
+    // a covered canvas has no more pixels than its windows: the bound that keeps the cover kernel inside the sums (and the canvas inside the
+    // state buffers, lumina_dit.h)
+    LT_REQUIRE((long long)canvas_h * canvas_w <= (long long)n * win_h * win_w, "%s: a canvas of %dx%d cannot be covered by %d windows of %dx%d", who,
+               canvas_h, canvas_w, n, win_h, win_w);
+    if (!e->tw_out) {
+        const size_t win_px = (size_t)c.max_tokens * p * p, rows = (size_t)c.max_batch * c.in_channels * win_px * sizeof(float);
+        auto fail = [&]() { drop_windows(e); lt_set_error("%s: out of device memory for the window buffers", who); return 1; };
+        if (hipMalloc((void**)&e->tw_weight, win_px * sizeof(float)) != hipSuccess ||
+            hipMalloc((void**)&e->tw_wsum, (size_t)((c.max_batch + 1) / 2) * win_px * sizeof(float)) != hipSuccess ||
+            hipMalloc((void**)&e->tw_bad, sizeof(int)) != hipSuccess || hipMalloc(&e->tw_in, rows) != hipSuccess ||
+            hipMalloc(&e->tw_out, rows) != hipSuccess)
+            return fail();
+    }
+    // the sums are formed in e->tw_out, which no call is using, from the caller's weights: a refused table leaves the one in force as it was
+    int bad = -1;
+    if (launch_windows_cover(t, weight_dev, (float*)e->tw_out, e->tw_bad, s)) return 1;
+    LT_CHECK_HIP(hipMemcpyAsync(&bad, e->tw_bad, sizeof(int), hipMemcpyDeviceToHost, s));
+    LT_CHECK_HIP(hipStreamSynchronize(s));  // (also: no kernel of an earlier call still reads the tables that are rewritten below)
+    LT_REQUIRE(bad == 0, "%s: the canvas is not covered: %d of its %d pixels lie under no window, or under weights whose sum is not finite and "
+               "above 0", who, bad, canvas_h * canvas_w);
+    LT_CHECK_HIP(hipMemcpyAsync(e->tw_wsum, e->tw_out, (size_t)canvas_h * canvas_w * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (weight_dev) LT_CHECK_HIP(hipMemcpyAsync(e->tw_weight, weight_dev, (size_t)win_h * win_w * sizeof(float), hipMemcpyDeviceToDevice, s));
+    e->tw = t;
+    e->tw_has_weight = weight_dev != nullptr;
+    return 0;
+}
+
+namespace {
+// what both tiled evaluation entries refuse, by name, before anything is launched
+int check_tiled_call(const lt_engine* e, const char* who, const lt_step_args* a) {
+    LT_REQUIRE(e->tw.n >= 1, "%s: no window table (call lt_set_windows first)", who);
+    const int n = e->tw.n;
+    LT_REQUIRE(a->batch == 2 * n, "%s: %d windows need a->batch = 2 n = %d (window prompts + negative prompts), got %d", who, n, 2 * n, a->batch);
+    LT_REQUIRE(a->latent_h == e->tw.win_h && a->latent_w == e->tw.win_w, "%s: the window table is for windows of %dx%d, the call has a latent of %dx%d",
+               who, e->tw.win_h, e->tw.win_w, a->latent_h, a->latent_w);
+    LT_REQUIRE(a->io_dtype == LT_BF16 || a->io_dtype == LT_F32, "io_dtype must be bf16 or f32");
+    LT_REQUIRE(e->reg_Y == 0, "%s: a regional prompt is prepared (lt_prepare_prompt_regional): its captions belong to one image, not to a row per "
+               "window", who);
+    LT_REQUIRE(e->skip.empty() && e->perturb.empty(), "%s: a layer-skip or perturb set is not served", who);
+    LT_REQUIRE(e->prompt_B == 2 * n, "%s: %s was called for batch %d, %d windows need %d rows (the window prompts, then the negative prompts)", who,
+               e->v.labels ? "lt_prepare_labels" : "lt_prepare_prompt", e->prompt_B, n, 2 * n);
+    return 0;
+}
+}  // namespace
+
+extern "C" int lt_forward_tiled(lt_engine* e, const void* y_dev, const float* t_dev, void* v_dev, const lt_step_args* a, void* stream) {
+    const char* who = "lt_forward_tiled";
+    LT_REQUIRE(e && y_dev && t_dev && v_dev && a, "%s: null argument", who);
+    hipStream_t s = (hipStream_t)stream;
+    LtOptScope opt_scope(&e->opts);
+    if (check_tiled_call(e, who, a)) return 2;
+    const int C = e->cfg.in_channels, dt_code = a->io_dtype == LT_BF16 ? 1 : 0;
+    if (launch_windows_gather(y_dev, e->tw, e->tw_in, C, dt_code, s)) return 1;
+    if (int rc = forward_graphed(e, e->tw_in, t_dev, e->tw_out, a, 1, s)) return rc;
+    return launch_windows_reduce(e->tw_out, e->tw, e->tw_has_weight ? e->tw_weight : nullptr, e->tw_wsum, v_dev, C, dt_code, s);
+}
+
+extern "C" int lt_sample_ode_tiled(lt_engine* e, const void* z_dev, void* traj_dev, void* final_dev, const float* tgrid_host, int32_t n_grid,
+                                   int32_t method, int32_t t_round, const lt_step_args* a, void* stream) {
+    const char* who = "lt_sample_ode_tiled";
+    LT_REQUIRE(e && z_dev && tgrid_host && a, "%s: null argument", who);
+    if (refuse_if_capturing((hipStream_t)stream, who)) return 2;  // (the stage times travel through a host staging buffer that the next call rewrites)
+    LtOptScope opt_scope(&e->opts);
+    if (check_grid_method(who, n_grid, method, false, " (tiled sampling serves the fixed-grid methods euler, midpoint, rk4)")) return 2;
+    if (check_tiled_call(e, who, a)) return 2;
+    GridCall c{z_dev, traj_dev, final_dev, tgrid_host, n_grid, 1, t_round, a, (hipStream_t)stream,
+               (long long)e->cfg.in_channels * e->tw.canvas_h * e->tw.canvas_w, nullptr, method};
+    c.tiled = true;
+    return ode_fixed_grid(e, c, {}, nullptr);
+}

@@ -1111,6 +1111,80 @@ class DiTEngine:
         _lib.check(rc, "lt_sample_views_guided")
         return out
 
+    # ---- tiled (MultiDiffusion) sampling: one canvas, the model on overlapping windows of it ---------------------
+    def set_windows(self, offsets, win_hw, canvas_hw, weights: Optional[torch.Tensor] = None) -> None:
+        """upload a window table (lt_set_windows): ``offsets`` ``[(top, left), ...]`` in latent pixels (``transport.tiled.window_grid``), every
+        window ``win_hw``, on a canvas ``canvas_hw``; ``weights`` fp32 ``[win_h, win_w]`` (``transport.tiled.window_weights``; ``None``: ones).
+        The engine refuses, by name, a table it cannot serve or that leaves a pixel of the canvas uncovered.  ``offsets=None`` drops the
+        table.  Synchronises the stream once (the cover check), unlike the sampling loop."""
+        s = C.c_void_p(_stream_ptr(self.device))
+        if offsets is None:
+            with torch.cuda.device(self.device):
+                _lib.check(self.lib.lt_set_windows(self.handle, None, 0, 0, 0, 0, 0, None, s), "lt_set_windows")
+            self._windows_key = None
+            return
+        offs = [(int(t), int(l)) for t, l in (offsets.tolist() if isinstance(offsets, torch.Tensor) else offsets)]
+        (h, w), (Hc, Wc) = (int(v) for v in win_hw), (int(v) for v in canvas_hw)
+        wd = None
+        if weights is not None:
+            if not isinstance(weights, torch.Tensor) or tuple(weights.shape) != (h, w):
+                raise LuminaLibError(f"set_windows: weights must be a tensor [{h}, {w}] (transport.tiled.window_weights)")
+            wd = weights.detach().to(device=self.device, dtype=torch.float32).contiguous()
+        arr = (C.c_int32 * max(2 * len(offs), 1))(*[v for o in offs for v in o])
+        with torch.cuda.device(self.device):
+            rc = self.lib.lt_set_windows(self.handle, arr, len(offs), h, w, Hc, Wc, C.c_void_p(wd.data_ptr() if wd is not None else 0), s)
+        _lib.check(rc, "lt_set_windows")  # (a refusal leaves the table in force, and its key, as they were)
+        self._windows_key = (len(offs), h, w, Hc, Wc)
+
+    def _tiled_args(self, y: torch.Tensor, what: str, cfg_scale, scale_factor, scale_watershed, base_seqlen, proportional_attn, ntk_factor):
+        _require_gpu(y, "y")
+        key = getattr(self, "_windows_key", None)
+        if key is None:
+            raise LuminaLibError(f"{what}: no window table (call set_windows first)")
+        n, h, w, Hc, Wc = key
+        if y.dim() != 4 or tuple(y.shape) != (1, self.in_channels, Hc, Wc):
+            raise LuminaLibError(f"{what} takes ONE canvas latent [1, {self.in_channels}, {Hc}, {Wc}] (the window table's canvas), got "
+                                 f"{tuple(y.shape)}")
+        a = self._step_args(y, cfg_scale, scale_factor, scale_watershed, base_seqlen, proportional_attn, ntk_factor=ntk_factor)
+        a.batch, a.latent_h, a.latent_w = 2 * n, h, w
+        return a
+
+    def forward_tiled(self, y: torch.Tensor, t: torch.Tensor, *, cfg_scale: float = 1.0, scale_factor: float = 1.0, scale_watershed: float = 1.0,
+                      base_seqlen: Optional[int] = None, proportional_attn: bool = False, ntk_factor: float = 1.0) -> torch.Tensor:
+        """one canvas evaluation (lt_forward_tiled; ``transport.tiled.tiled_velocity`` is the definition): the n windows of ``y [1, C, Hc, Wc]``
+        as one ``forward_with_cfg`` of 2 n rows at ``t`` (2 n stage times), their predictions fused.  Needs ``set_windows`` and a conditioning
+        prepared at B = 2 n (rows 0 .. n-1 the window prompts, rows n .. 2n-1 the negative prompts)."""
+        a = self._tiled_args(y, "forward_tiled", cfg_scale, scale_factor, scale_watershed, base_seqlen, proportional_attn, ntk_factor)
+        y = y.contiguous()
+        t32 = t.to(device=y.device, dtype=torch.float32).contiguous()
+        if t32.numel() != a.batch:
+            raise LuminaLibError(f"forward_tiled: t has {t32.numel()} entries, the {a.batch // 2} windows are evaluated as {a.batch} rows")
+        out = torch.empty_like(y)
+        with torch.cuda.device(self.device):
+            rc = self.lib.lt_forward_tiled(self.handle, C.c_void_p(y.data_ptr()), C.c_void_p(t32.data_ptr()), C.c_void_p(out.data_ptr()), C.byref(a),
+                                           C.c_void_p(_stream_ptr(self.device)))
+        _lib.check(rc, "lt_forward_tiled")
+        return out
+
+    def sample_ode_tiled(self, z: torch.Tensor, tgrid, method: str = "midpoint", *, cfg_scale: float = 1.0, scale_factor: float = 1.0,
+                         scale_watershed: float = 1.0, base_seqlen: Optional[int] = None, proportional_attn: bool = False,
+                         t_round_to_state_dtype: bool = True, return_trajectory: bool = True, ntk_factor: float = 1.0) -> torch.Tensor:
+        """the fixed-grid trajectory of ONE canvas latent ``z [1, C, Hc, Wc]`` in one call (lt_sample_ode_tiled;
+        ``transport.tiled.sample_tiled`` is the definition): every stage is ``forward_tiled``, the steps are ``sample_ode``'s.  Returns
+        ``[n_grid, 1, C, Hc, Wc]`` or the last canvas."""
+        if method not in _lib.ODE_METHODS:
+            raise LuminaLibError(f"sample_ode_tiled: tiled sampling is built for the fixed-grid methods {sorted(_lib.ODE_METHODS)}, not '{method}' "
+                                 "(the multistep and adaptive solvers are not served)")
+        a = self._tiled_args(z, "sample_ode_tiled", cfg_scale, scale_factor, scale_watershed, base_seqlen, proportional_attn, ntk_factor)
+        z = z.contiguous()
+        garr, n = _grid_array(tgrid)
+        out, traj_ptr, fin_ptr = _traj_or_final(z, max(n, 1), z.shape, return_trajectory)
+        with torch.cuda.device(self.device):
+            rc = self.lib.lt_sample_ode_tiled(self.handle, C.c_void_p(z.data_ptr()), traj_ptr, fin_ptr, garr, n, _lib.ODE_METHODS[method],
+                                              int(t_round_to_state_dtype), C.byref(a), C.c_void_p(_stream_ptr(self.device)))
+        _lib.check(rc, "lt_sample_ode_tiled")
+        return out
+
     def last_nfe(self) -> int:
         return int(self.lib.lt_last_nfe(self.handle))
 

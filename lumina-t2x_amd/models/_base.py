@@ -397,6 +397,79 @@ class EngineSamplers:
         eng, args = self._engine_sampler_args(x, True, kw)
         return eng.forward_cfg_pag(x, t, pag_scale=pag_scale, pag_layers=pag_layers, skip_layers=skip_layers, **args)
 
+    # ---- tiled (MultiDiffusion) sampling: one canvas, the model on overlapping windows of it ---------------------
+    def _tiled_engine(self, what, y, windows, weights, kw):
+        """the engine with the window table ``windows = (offsets, (win_h, win_w))`` set for the canvas ``y [1, C, Hc, Wc]`` and the conditioning
+        in ``kw`` prepared for the 2 n rows - rows 0 .. n-1 the window prompts, rows n .. 2n-1 the negative prompts; a conditioning of two rows
+        (one prompt, one negative prompt) is expanded to n of each.  Returns (engine, step kwargs, n)."""
+        from ..transport import tiled as T
+        if not isinstance(y, torch.Tensor):
+            raise _lib.LuminaLibError(f"{what}: a packed batch (a list of latents) is not served by tiled sampling")
+        if "cfg_scale" not in kw:
+            raise TypeError(f"{what} needs cfg_scale")
+        if y.dim() != 4 or y.shape[0] != 1:
+            raise _lib.LuminaLibError(f"{what} takes ONE canvas latent [1, C, Hc, Wc], got {tuple(y.shape)}")
+        try:
+            offsets, win_hw = windows
+            win_hw = (int(win_hw[0]), int(win_hw[1]))
+            offs = T.check_windows(offsets, win_hw, tuple(y.shape[2:]), None)
+        except (TypeError, ValueError) as exc:
+            raise _lib.LuminaLibError(f"{what}: windows = (offsets, (win_h, win_w)): {exc}") from None
+        n = len(offs)
+        for name in self._cond_names:
+            v = kw[name]
+            if v.shape[0] == 2 and n > 1:
+                kw[name] = v.repeat_interleave(n, dim=0)
+            elif v.shape[0] != 2 * n:
+                raise _lib.LuminaLibError(f"{what}: {n} windows need 2 n = {2 * n} rows of {name} (the window prompts, then the negative prompts) or "
+                                          f"2 rows (one of each, for every window), got {v.shape[0]}")
+        self._mirror_attention_flags(kw)
+        rows = torch.empty((2 * n, y.shape[1]) + win_hw, dtype=y.dtype, device=y.device)  # the evaluation's shape
+        eng, args = self._engine_sampler_args(rows, True, kw)
+        src = (tuple(offs), win_hw, tuple(y.shape[2:]), None if weights is None else (weights.data_ptr(), weights._version))
+        if getattr(eng, "_windows_src", (None,))[0] != src or getattr(eng, "_windows_key", None) is None:
+            eng._windows_src = (None,)
+            eng.set_windows(offs, win_hw, tuple(y.shape[2:]), weights)
+            eng._windows_src = (src, weights)  # (the tensor is kept: its address cannot pass to other weights)
+        return eng, args, n
+
+    @torch.no_grad()
+    def forward_with_cfg_tiled(self, y, t, windows, *cond, weights=None, **step_kw):
+        """One evaluation of a canvas ``y [1, C, Hc, Wc]`` through overlapping windows in ONE engine call (lt_forward_tiled, DESIGN 7r;
+        ``transport.tiled.tiled_velocity`` around ``forward_with_cfg`` is the definition): ``windows = (offsets, (win_h, win_w))``
+        (``transport.tiled.window_grid``), ``weights`` fp32 ``[win_h, win_w]`` (``window_weights``; ``None``: ones).  ``cond``: the family's
+        conditioning for the 2 n rows (or for 2: one prompt and one negative prompt for every window), then ``cfg_scale``; ``step_kw``: the
+        other keyword arguments of ``forward_with_cfg``.  ``t``: one stage time, or 2 n."""
+        names = self._cond_names + ("cfg_scale",)
+        if len(cond) > len(names):
+            raise TypeError(f"forward_with_cfg_tiled takes {names}, got {len(cond)} positional arguments")
+        eng, args, n = self._tiled_engine("forward_with_cfg_tiled", y, windows, weights, dict(zip(names, cond), **step_kw))
+        tv = torch.as_tensor(t, dtype=torch.float32, device=y.device).reshape(-1)
+        return eng.forward_tiled(y, tv.expand(2 * n) if tv.numel() == 1 else tv, **args)
+
+    @torch.no_grad()
+    def sample_ode_tiled(self, z, tgrid, windows, *cond, method: str = "midpoint", weights=None, return_trajectory: bool = False,
+                         t_round: bool = True, **step_kw):
+        """The fixed-grid trajectory of ONE canvas latent ``z [1, C, Hc, Wc]`` in ONE engine call (lt_sample_ode_tiled, DESIGN 7r;
+        ``transport.tiled.sample_tiled`` around ``forward_with_cfg`` is the definition): every stage evaluates the windows as one
+        ``forward_with_cfg`` of 2 n rows and fuses their predictions; euler / midpoint / rk4 step the canvas.  Arguments as
+        ``forward_with_cfg_tiled``.  Returns the last canvas, or all ``len(tgrid)`` canvases."""
+        from ..transport.tiled import refuse_with_tiled
+        names = self._cond_names + ("cfg_scale",)
+        if len(cond) > len(names):
+            raise TypeError(f"sample_ode_tiled takes {names}, got {len(cond)} positional arguments")
+        try:
+            refuse_with_tiled(method)
+        except NotImplementedError as exc:
+            raise _lib.LuminaLibError(f"sample_ode_tiled: {exc}") from None
+        eng, args, _ = self._tiled_engine("sample_ode_tiled", z, windows, weights, dict(zip(names, cond), **step_kw))
+        return eng.sample_ode_tiled(z, tgrid, method, t_round_to_state_dtype=t_round, return_trajectory=return_trajectory, **args)
+
+    def _engine_sample_ode_tiled(self, x, tgrid, method, t_round, windows, weights, kw):
+        """kwargs of forward_with_cfg -> lt_sample_ode_tiled; all states"""
+        eng, args, _ = self._tiled_engine("tiled sampling", x, windows, weights, kw)
+        return eng.sample_ode_tiled(x, tgrid, method, t_round_to_state_dtype=t_round, **args)
+
     def _engine_sample_ode_adaptive(self, x, tgrid, method, use_cfg, t_round, kw, *, rtol, atol, first_step=None, max_steps=2 ** 31 - 1):
         """kwargs of forward_with_cfg / forward -> lt_sample_ode_adaptive; returns (states [len(tgrid), *x.shape], stats dict)"""
         eng, args = self._engine_sampler_args(x, use_cfg, kw)

@@ -122,6 +122,27 @@ def save_png(img: torch.Tensor, path: str) -> None:
                 chunk(b"IDAT", zlib.compress(raw, 6)) + chunk(b"IEND", b""))
 
 
+def tile_windows(args, canvas_hw, patch_size: int = 2):
+    """``--tile H W [--tile_stride SH SW] [--tile_weights KIND]`` (pixels) on a canvas latent of ``canvas_hw`` -> ``((offsets, (win_h, win_w)),
+    weights)`` in latent pixels.  The driver draws its latent width first (``[1, 4, w / 8, h / 8]``, as the reference does), so W goes with the
+    latent's first spatial axis and H with its second, like the resolution; a tile larger than the canvas is clamped to it; the default
+    stride is half the tile."""
+    from .transport.tiled import window_grid, window_weights
+    th_px, tw_px = args.tile
+    stride = getattr(args, "tile_stride", None) or (th_px // 2, tw_px // 2)
+    unit = 8 * patch_size
+    for name, v in (("--tile", (th_px, tw_px)), ("--tile_stride", tuple(stride))):
+        if any(int(x) < unit or int(x) % unit for x in v):
+            raise SystemExit(f"{name} {v[0]} {v[1]}: sizes are pixels, positive multiples of {unit} (8 per latent pixel x the patch size {patch_size})")
+    win = (min(tw_px // 8, canvas_hw[0]), min(th_px // 8, canvas_hw[1]))
+    st = (min(stride[1] // 8, win[0]), min(stride[0] // 8, win[1]))
+    try:
+        offsets = window_grid(canvas_hw[0], canvas_hw[1], win[0], win[1], st[0], st[1], patch_size)
+    except ValueError as exc:
+        raise SystemExit(f"--tile: {exc}") from None
+    return (offsets, win), window_weights(win[0], win[1], getattr(args, "tile_weights", "uniform") or "uniform")
+
+
 def run(args, *, encode_fn=None, cap_feat_dim=None, decode_fn=None, model=None) -> List[dict]:
     """Sample every (resolution, caption) pair of this rank's shard.  ``encode_fn`` / ``decode_fn`` / ``model`` can be injected
     (tests, or a caller that already holds the encoder / VAE); otherwise they are built from the command-line paths."""
@@ -170,6 +191,11 @@ def run(args, *, encode_fn=None, cap_feat_dim=None, decode_fn=None, model=None) 
             kw.update(scale_factor=math.sqrt(w * h / train_args.image_size ** 2), scale_watershed=args.scaling_watershed)
         else:
             kw.update(scale_factor=1.0, scale_watershed=1.0)
+        tile = getattr(args, "tile", None)
+        if tile:  # the model sees windows of the tile's size, not the canvas
+            kw.update(scale_factor=1.0, scale_watershed=1.0)
+            if tile[0] * tile[1] > train_args.image_size ** 2 and args.scaling_method == "Time-aware":
+                kw.update(scale_factor=math.sqrt(tile[0] * tile[1] / train_args.image_size ** 2), scale_watershed=args.scaling_watershed)
         table = guidance_table(args, sample_fn.__self__.t)
         rule = guidance_rule(args)
         reuse = guidance_reuse(args, sample_fn.__self__.t, table)
@@ -177,7 +203,13 @@ def run(args, *, encode_fn=None, cap_feat_dim=None, decode_fn=None, model=None) 
         slg = None if pag is not None else guidance_slg(args, sample_fn.__self__.t)
         tea = step_cache(args)
         proj = guidance_project(args)
-        if proj:  # APG / CFG-Zero*: the guided stages built on inner products of the two rows; combines with the scale table alone
+        if tile:  # MultiDiffusion: ONE canvas latent, every stage the model on overlapping windows of it, their predictions fused
+            if table is not None or rule or reuse is not None or pag is not None or slg is not None or tea or proj:
+                raise SystemExit("--tile is not served together with --cfg_interval / --cfg_schedule, --cfg_rescale / --cfg_norm_limit, --cfg_reuse*, "
+                                 "--slg_*, --pag_*, --teacache, --apg_* or --cfg_zero_star")
+            windows, weights = tile_windows(args, tuple(z.shape[2:]), getattr(model, "patch_size", 2))
+            latent = sample_fn(z[:1], model.forward_with_cfg, windows=windows, window_weights=weights, **kw)[-1][:1]
+        elif proj:  # APG / CFG-Zero*: the guided stages built on inner products of the two rows; combines with the scale table alone
             if rule or reuse is not None or pag is not None or slg is not None or tea:
                 raise SystemExit("--apg_* / --cfg_zero_star are not served together with --cfg_rescale / --cfg_norm_limit, --cfg_reuse*, "
                                  "--slg_*, --pag_* or --teacache")
@@ -408,6 +440,12 @@ def build_parser() -> argparse.ArgumentParser:
                         "first-block input stays below THR, and add the residual the stack produced the last time it ran (default: off)")
     p.add_argument("--teacache_coefficients", type=float, nargs=5, default=None, metavar=("C4", "C3", "C2", "C1", "C0"),
                    help="... the polynomial the relative change goes through before it is accumulated, highest power first (default: identity)")
+    p.add_argument("--tile", type=int, nargs=2, default=None, metavar=("H", "W"),
+                   help="tiled (MultiDiffusion) sampling: --resolution names the canvas, the model runs on overlapping windows of H x W pixels "
+                        "whose predictions are averaged where they overlap (one engine call per image)")
+    p.add_argument("--tile_stride", type=int, nargs=2, default=None, metavar=("SH", "SW"), help="window stride in pixels (default: half the tile)")
+    p.add_argument("--tile_weights", type=str, default="uniform", choices=["uniform", "cosine"],
+                   help="weight of a window's pixels in the average: uniform, or a cosine bump that fades towards the window's border")
     p.add_argument("--num_sampling_steps", type=int, default=250)
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--ckpt", type=str, required=True)
