@@ -16,6 +16,7 @@ from . import _lib
 from ._lib import LtConfig, LtStepArgs, LuminaLibError
 
 _DT = {torch.float32: _lib.LT_F32, torch.bfloat16: _lib.LT_BF16, torch.float16: _lib.LT_F16}
+_STAGES = {"euler": 1, "midpoint": 2, "rk4": 4}  # model evaluations per interval of the fixed-grid methods
 
 
 def _stream_ptr(device: torch.device) -> int:
@@ -36,6 +37,15 @@ def _require_gpu(t: torch.Tensor, name: str) -> None:
             f"{name} lives on {t.device}; the MI355X denoising engine only runs on a ROCm device "
             "(there is no CPU fallback - use oracle/ for CPU reference numbers in tests)"
         )
+
+
+def _refusing(check, *args, who: Optional[str] = None, **kw):
+    """the result of a host-side check of the transport package (``check_*`` / ``refuse_*``: they raise ``ValueError``); what it objects to is
+    the engine's refusal, a ``LuminaLibError`` of the same words behind an optional ``"{who}: "``"""
+    try:
+        return check(*args, **kw)
+    except ValueError as exc:
+        raise LuminaLibError(f"{who}: {exc}" if who else str(exc)) from None
 
 
 def _grid_array(tgrid):
@@ -135,6 +145,76 @@ class DiTEngine:
                 pass
             self.handle = None
 
+    # ---- the binding: the one way into the library, and what a call is given ------------------------
+    def _call(self, name: str, *args) -> None:
+        """``name(handle, *args)`` on this engine's device; a non-zero status is raised under the entry's own name"""
+        with torch.cuda.device(self.device):
+            rc = getattr(self.lib, name)(self.handle, *args)
+        _lib.check(rc, name)
+
+    def _stream(self) -> C.c_void_p:
+        """the caller's current stream on this engine's device, for the place the entry's signature gives the stream"""
+        return C.c_void_p(_stream_ptr(self.device))
+
+    @staticmethod
+    def _dev(t: Optional[torch.Tensor]) -> C.c_void_p:
+        """a device tensor's address; null for ``None``.  (The callers keep the tensor: it is their argument, their result or ``_keep``.)"""
+        return C.c_void_p(t.data_ptr() if t is not None else 0)
+
+    @staticmethod
+    def _host(t: Optional[torch.Tensor]):
+        """a contiguous fp32 / int32 CPU tensor as the ``float *`` / ``int32_t *`` the entry reads during the call; ``None`` (null) for
+        ``None``.  The pointer object holds the tensor (``_tensor``) and the call's argument list holds the pointer object, so the memory
+        stays allocated until the call returns, also when the tensor was a temporary of the caller's expression."""
+        if t is None:
+            return None
+        ptr = C.cast(t.data_ptr(), C.POINTER(C.c_int32 if t.dtype == torch.int32 else C.c_float))
+        ptr._tensor = t
+        return ptr
+
+    @staticmethod
+    def _table(values, count: Optional[int] = None, wrong=None, dtype=torch.float32) -> torch.Tensor:
+        """a host table (a tensor or a sequence) as a flat contiguous CPU tensor of ``dtype``; ``count``: the entries it must have, and
+        ``wrong(entries)`` the words of the refusal when it has another number (its contents are the C entry's to check).  A sequence is
+        read as fp32 numbers, whatever ``dtype``: a table of another type (the int32 reuse flags) comes in as a tensor."""
+        tab = values if isinstance(values, torch.Tensor) else torch.tensor(list(values), dtype=torch.float32)
+        tab = tab.detach().to("cpu", dtype).reshape(-1).contiguous()
+        if count is not None and tab.numel() != count:
+            raise LuminaLibError(wrong(tab.numel()))
+        return tab
+
+    @staticmethod
+    def _eval_io(x: torch.Tensor, t: torch.Tensor, *, out: Optional[torch.Tensor] = None, writes: bool = True, name: str = "x"):
+        """the operands of one evaluation: ``(x contiguous, t in fp32 on x's device, the tensor to write)`` - the caller's ``out``, else a
+        new one like ``x``, or none for an evaluation that writes no tensor (``writes=False``); ``name``: what a refusal calls ``x``"""
+        _require_gpu(x, name)
+        x = x.contiguous()
+        t32 = t.to(device=x.device, dtype=torch.float32).contiguous()
+        if out is None and writes:
+            out = torch.empty_like(x)
+        return x, t32, out
+
+    @staticmethod
+    def _fixed_grid(method: str, tgrid, refusal: Optional[str] = None):
+        """a fixed-grid trajectory's ``(grid array, grid points n, method code, model evaluations)``; ``refusal``: the entry's own words
+        for a method that is not euler / midpoint / rk4"""
+        if method not in _lib.ODE_METHODS:
+            raise LuminaLibError(refusal or f"fixed-grid method '{method}' not in {sorted(_lib.ODE_METHODS)}")
+        garr, n = _grid_array(tgrid)
+        return garr, n, _lib.ODE_METHODS[method], max(n - 1, 0) * _STAGES[method]
+
+    def _stage_table(self, table, who: str, n: int, method: str, count: int) -> torch.Tensor:
+        """the guidance scale of every stage of a fixed-grid trajectory"""
+        return self._table(table, count, lambda got: f"{who}: the table has {got} entries, a {n}-point {method} grid has {count} stages")
+
+    @staticmethod
+    def _unpacked(out: torch.Tensor, spans, n: Optional[int] = None):
+        """a packed result as one tensor per sample, views of the one allocation: ``[n, *shape]`` of the trajectory ``out [n, total]``, or
+        (``n=None``) ``shape`` of the flat ``out``"""
+        if n is not None:
+            return [out[:, off:off + math.prod(shape)].view((n,) + shape) for off, shape in spans]
+        return [out[off:off + math.prod(shape)].view(shape) for off, shape in spans]
+
     # ---- options (include/lumina_dit_debug.h) ----------------------------------------------------------
     def set_option(self, name: str, value: Optional[int]) -> None:
         """override one kernel-selection option for THIS engine only (``None`` drops the override: the process default set by
@@ -156,7 +236,7 @@ class DiTEngine:
         # forget which tensors it came from, so the next call prepares it again (lt_set_weight also invalidates it engine-side)
         _refuse_if_capturing("load_state_dict (lt_set_weight)")
         self._prompt.clear()
-        s = _stream_ptr(self.device)
+        s = self._stream()
         skip = set(skip)
         with torch.cuda.device(self.device):
             for key, t in state.items():
@@ -167,11 +247,10 @@ class DiTEngine:
                     dt = t.dtype if t.dtype in _DT else torch.float32
                     t = t.to(device=self.device, dtype=dt).contiguous()
                 shape = (C.c_int64 * max(t.dim(), 1))(*(t.shape if t.dim() else (1,)))
-                rc = self.lib.lt_set_weight(self.handle, key.encode(), C.c_void_p(t.data_ptr()), _DT[t.dtype], shape,
-                                            max(t.dim(), 1), C.c_void_p(s))
+                rc = self.lib.lt_set_weight(self.handle, key.encode(), self._dev(t), _DT[t.dtype], shape, max(t.dim(), 1), s)
                 _lib.check(rc, f"lt_set_weight({key})")
             torch.cuda.current_stream(self.device).synchronize()  # sources may be temporaries
-            _lib.check(self.lib.lt_weights_ready(self.handle), "lt_weights_ready")
+            self._call("lt_weights_ready")
 
     # ---- prompt ----------------------------------------------------------------------------------
     def prepare_prompt(self, cap_feats: torch.Tensor, cap_mask: torch.Tensor) -> None:
@@ -182,10 +261,7 @@ class DiTEngine:
         feats = feats.contiguous()
         mask = cap_mask.to(device=feats.device, dtype=torch.int32).contiguous()
         B, T, _ = feats.shape
-        with torch.cuda.device(self.device):
-            rc = self.lib.lt_prepare_prompt(self.handle, C.c_void_p(feats.data_ptr()), _DT[feats.dtype],
-                                            C.c_void_p(mask.data_ptr()), B, T, C.c_void_p(_stream_ptr(self.device)))
-        _lib.check(rc, "lt_prepare_prompt")
+        self._call("lt_prepare_prompt", self._dev(feats), _DT[feats.dtype], self._dev(mask), B, T, self._stream())
         self._keep = (feats, mask)  # keep the temporaries alive until the stream has consumed them
         self._prompt.store((cap_feats, cap_mask), ("prompt",))
 
@@ -202,12 +278,8 @@ class DiTEngine:
         mask = cap_mask.to(device=feats.device, dtype=torch.int32).contiguous()
         gmask = global_mask.to(device=feats.device, dtype=torch.int32).contiguous()
         Y, T, _ = feats.shape
-        with torch.cuda.device(self.device):
-            rc = self.lib.lt_prepare_prompt_regional(self.handle, C.c_void_p(feats.data_ptr()), _DT[feats.dtype],
-                                                     C.c_void_p(mask.data_ptr()), Y, T, C.c_void_p(gfeats.data_ptr()),
-                                                     C.c_void_p(gmask.data_ptr()), gfeats.shape[1], int(h_split), int(w_split),
-                                                     C.c_void_p(_stream_ptr(self.device)))
-        _lib.check(rc, "lt_prepare_prompt_regional")
+        self._call("lt_prepare_prompt_regional", self._dev(feats), _DT[feats.dtype], self._dev(mask), Y, T, self._dev(gfeats),
+                   self._dev(gmask), gfeats.shape[1], int(h_split), int(w_split), self._stream())
         self._keep = (feats, mask, gfeats, gmask)
         self._prompt.store(src, extra)
 
@@ -217,9 +289,7 @@ class DiTEngine:
         if self._prompt.hit((y,), ("labels",)):
             return
         lab = y.to(dtype=torch.int32).contiguous()
-        with torch.cuda.device(self.device):
-            rc = self.lib.lt_prepare_labels(self.handle, C.c_void_p(lab.data_ptr()), lab.numel(), C.c_void_p(_stream_ptr(self.device)))
-        _lib.check(rc, "lt_prepare_labels")
+        self._call("lt_prepare_labels", self._dev(lab), lab.numel(), self._stream())
         self._keep = (lab,)
         self._prompt.store((y,), ("labels",))
 
@@ -240,34 +310,21 @@ class DiTEngine:
                 proportional_attn: bool = False, ntk_factor: float = 1.0, skip_layers=(), perturb_layers=()) -> torch.Tensor:
         """one evaluation; ``skip_layers`` (plain forward only): the blocks left out (lt_forward_skip); ``perturb_layers`` (plain
         forward only): the blocks whose self-attention map is the identity (lt_forward_perturb); both empty: the call it was"""
-        _require_gpu(x, "x")
-        x = x.contiguous()
-        t32 = t.to(device=x.device, dtype=torch.float32).contiguous()
-        out = torch.empty_like(x)
+        x, t32, out = self._eval_io(x, t)
         a = self._step_args(x, cfg_scale, scale_factor, scale_watershed, base_seqlen, proportional_attn, ntk_factor=ntk_factor)
         skip = self._skip_array(skip_layers, "forward")
         perturb = self._skip_array(perturb_layers, "forward", "perturb")
         if len(perturb):
             if use_cfg:
                 raise LuminaLibError("forward: perturb_layers belongs to the plain forward (guided: forward_cfg_pag)")
-            with torch.cuda.device(self.device):
-                rc = self.lib.lt_forward_perturb(self.handle, C.c_void_p(x.data_ptr()), C.c_void_p(t32.data_ptr()), C.c_void_p(out.data_ptr()),
-                                                 C.byref(a), skip, len(skip), perturb, len(perturb), C.c_void_p(_stream_ptr(self.device)))
-            _lib.check(rc, "lt_forward_perturb")
-            return out
-        if len(skip):
+            name, layers = "lt_forward_perturb", (skip, len(skip), perturb, len(perturb))
+        elif len(skip):
             if use_cfg:
                 raise LuminaLibError("forward: skip_layers belongs to the plain forward (guided: forward_cfg_slg)")
-            with torch.cuda.device(self.device):
-                rc = self.lib.lt_forward_skip(self.handle, C.c_void_p(x.data_ptr()), C.c_void_p(t32.data_ptr()), C.c_void_p(out.data_ptr()),
-                                              C.byref(a), skip, len(skip), C.c_void_p(_stream_ptr(self.device)))
-            _lib.check(rc, "lt_forward_skip")
-            return out
-        fn = self.lib.lt_forward_cfg if use_cfg else self.lib.lt_forward
-        with torch.cuda.device(self.device):
-            rc = fn(self.handle, C.c_void_p(x.data_ptr()), C.c_void_p(t32.data_ptr()), C.c_void_p(out.data_ptr()),
-                    C.byref(a), C.c_void_p(_stream_ptr(self.device)))
-        _lib.check(rc, "lt_forward_cfg" if use_cfg else "lt_forward")
+            name, layers = "lt_forward_skip", (skip, len(skip))
+        else:
+            name, layers = "lt_forward_cfg" if use_cfg else "lt_forward", ()
+        self._call(name, self._dev(x), self._dev(t32), self._dev(out), C.byref(a), *layers, self._stream())
         return out
 
     def forward_packed(self, xs, t: torch.Tensor, *, scale_factor: float = 1.0, scale_watershed: float = 0.0,
@@ -284,13 +341,10 @@ class DiTEngine:
         outs = [torch.empty((self.in_channels,) + tuple(x.shape[1:]), dtype=x.dtype, device=x.device) for x in xs]
         a = self._step_args(xs[0].unsqueeze(0), 1.0, scale_factor, scale_watershed, base_seqlen, proportional_attn)
         a.batch, a.latent_h, a.latent_w = B, 0, 0
-        xp = (C.c_void_p * B)(*[x.data_ptr() for x in xs])
-        op = (C.c_void_p * B)(*[o.data_ptr() for o in outs])
+        xp = (C.c_void_p * B)(*[self._dev(x) for x in xs])
+        op = (C.c_void_p * B)(*[self._dev(o) for o in outs])
         hw = (C.c_int32 * (2 * B))(*[v for x in xs for v in x.shape[1:]])
-        with torch.cuda.device(self.device):
-            rc = self.lib.lt_forward_packed(self.handle, xp, hw, C.c_void_p(t32.data_ptr()), op, C.byref(a),
-                                            C.c_void_p(_stream_ptr(self.device)))
-        _lib.check(rc, "lt_forward_packed")
+        self._call("lt_forward_packed", xp, hw, self._dev(t32), op, C.byref(a), self._stream())
         return outs
 
     def _pack(self, xs, what: str):
@@ -325,11 +379,8 @@ class DiTEngine:
         t32 = t.to(device=flat.device, dtype=torch.float32).contiguous()
         out = torch.empty_like(flat)
         a = self._packed_step_args(flat, len(spans), cfg_scale, scale_factor, scale_watershed, base_seqlen, proportional_attn)
-        with torch.cuda.device(self.device):
-            rc = self.lib.lt_forward_cfg_packed(self.handle, C.c_void_p(flat.data_ptr()), hw, C.c_void_p(t32.data_ptr()),
-                                                C.c_void_p(out.data_ptr()), C.byref(a), C.c_void_p(_stream_ptr(self.device)))
-        _lib.check(rc, "lt_forward_cfg_packed")
-        return [out[off:off + math.prod(shape)].view(shape) for off, shape in spans]
+        self._call("lt_forward_cfg_packed", self._dev(flat), hw, self._dev(t32), self._dev(out), C.byref(a), self._stream())
+        return self._unpacked(out, spans)
 
     # ---- whole trajectory -------------------------------------------------------------------------
     def sample_ode(self, z: torch.Tensor, tgrid: torch.Tensor, method: str, *, use_cfg: bool, cfg_scale: float = 1.0,
@@ -337,17 +388,12 @@ class DiTEngine:
                    proportional_attn: bool = False, t_round_to_state_dtype: bool = True,
                    return_trajectory: bool = True, ntk_factor: float = 1.0) -> torch.Tensor:
         _require_gpu(z, "z")
-        if method not in _lib.ODE_METHODS:
-            raise LuminaLibError(f"fixed-grid method '{method}' not in {sorted(_lib.ODE_METHODS)}")
+        garr, n, code, _ = self._fixed_grid(method, tgrid)
         z = z.contiguous()
-        garr, n = _grid_array(tgrid)
         a = self._step_args(z, cfg_scale, scale_factor, scale_watershed, base_seqlen, proportional_attn, ntk_factor=ntk_factor)
         out, traj_ptr, fin_ptr = _traj_or_final(z, n, z.shape, return_trajectory)
-        with torch.cuda.device(self.device):
-            rc = self.lib.lt_sample_ode(self.handle, C.c_void_p(z.data_ptr()), traj_ptr, fin_ptr, garr, n,
-                                        _lib.ODE_METHODS[method], int(use_cfg), int(t_round_to_state_dtype), C.byref(a),
-                                        C.c_void_p(_stream_ptr(self.device)))
-        _lib.check(rc, "lt_sample_ode")
+        self._call("lt_sample_ode", self._dev(z), traj_ptr, fin_ptr, garr, n, code, int(use_cfg), int(t_round_to_state_dtype), C.byref(a),
+                   self._stream())
         return out
 
     def sample_ode_cached(self, z: torch.Tensor, tgrid, method: str, *, use_cfg: bool, threshold: float, coefficients=(0.0, 0.0, 0.0, 1.0, 0.0),
@@ -361,25 +407,17 @@ class DiTEngine:
         if not isinstance(z, torch.Tensor):
             raise LuminaLibError("sample_ode_cached: a packed batch (a list of latents) is not served by step caching")
         _require_gpu(z, "z")
-        if method not in _lib.ODE_METHODS:
-            raise LuminaLibError(f"sample_ode_cached: step caching is built for the fixed-grid methods {sorted(_lib.ODE_METHODS)}, not '{method}' "
-                                 "(the multistep and adaptive solvers are not served)")
-        try:
-            thr, coef = check_cache_args(threshold, coefficients)
-        except ValueError as exc:
-            raise LuminaLibError(f"sample_ode_cached: {exc}") from None
+        garr, n, code, ncalls = self._fixed_grid(
+            method, tgrid, f"sample_ode_cached: step caching is built for the fixed-grid methods {sorted(_lib.ODE_METHODS)}, not '{method}' "
+                           "(the multistep and adaptive solvers are not served)")
+        thr, coef = _refusing(check_cache_args, threshold, coefficients, who="sample_ode_cached")
         z = z.contiguous()
-        garr, n = _grid_array(tgrid)
         a = self._step_args(z, cfg_scale, scale_factor, scale_watershed, base_seqlen, proportional_attn, ntk_factor=ntk_factor)
         out, traj_ptr, fin_ptr = _traj_or_final(z, n, z.shape, return_trajectory)
-        ncalls = max(n - 1, 0) * {"euler": 1, "midpoint": 2, "rk4": 4}[method]
         stats = (C.c_double * (3 * max(ncalls, 1)))()
-        with torch.cuda.device(self.device):
-            rc = self.lib.lt_sample_ode_cached(self.handle, C.c_void_p(z.data_ptr()), traj_ptr, fin_ptr, garr, n, _lib.ODE_METHODS[method],
-                                               int(use_cfg), int(t_round_to_state_dtype), C.byref(a), thr, (C.c_double * 5)(*coef), stats,
-                                               C.c_void_p(_stream_ptr(self.device)))
-        _lib.check(rc, "lt_sample_ode_cached")
-        return out, torch.tensor(list(stats)[:3 * ncalls], dtype=torch.float64).reshape(ncalls, 3)
+        self._call("lt_sample_ode_cached", self._dev(z), traj_ptr, fin_ptr, garr, n, code, int(use_cfg), int(t_round_to_state_dtype),
+                   C.byref(a), thr, (C.c_double * 5)(*coef), stats, self._stream())
+        return out, torch.tensor(stats[:3 * ncalls], dtype=torch.float64).reshape(ncalls, 3)
 
     def forward_cached(self, x: torch.Tensor, t: torch.Tensor, mode: str, *, use_cfg: bool, cfg_scale: float = 1.0, scale_factor: float = 1.0,
                        scale_watershed: float = 1.0, base_seqlen: Optional[int] = None, proportional_attn: bool = False, ntk_factor: float = 1.0):
@@ -391,17 +429,11 @@ class DiTEngine:
             raise LuminaLibError(f"forward_cached: mode '{mode}' not in {sorted(modes)}")
         if not isinstance(x, torch.Tensor):
             raise LuminaLibError("forward_cached: a packed batch (a list of latents) is not served by step caching")
-        _require_gpu(x, "x")
-        x = x.contiguous()
-        t32 = t.to(device=x.device, dtype=torch.float32).contiguous()
+        x, t32, out = self._eval_io(x, t, writes=mode != "probe")
         a = self._step_args(x, cfg_scale, scale_factor, scale_watershed, base_seqlen, proportional_attn, ntk_factor=ntk_factor)
-        out = None if mode == "probe" else torch.empty_like(x)
         sums = (C.c_double * 2)()
-        with torch.cuda.device(self.device):
-            rc = self.lib.lt_forward_cached(self.handle, C.c_void_p(x.data_ptr()), C.c_void_p(t32.data_ptr()),
-                                            C.c_void_p(out.data_ptr() if out is not None else 0), modes[mode], int(use_cfg), C.byref(a), sums,
-                                            C.c_void_p(_stream_ptr(self.device)))
-        _lib.check(rc, "lt_forward_cached")
+        self._call("lt_forward_cached", self._dev(x), self._dev(t32), self._dev(out), modes[mode], int(use_cfg), C.byref(a), sums,
+                   self._stream())
         return (float(sums[0]), float(sums[1])) if mode == "probe" else out
 
     def last_cache_hits(self) -> int:
@@ -414,19 +446,13 @@ class DiTEngine:
         """the fixed-grid trajectory of a LIST of differently sized latents in ONE call (lt_sample_ode_packed): every evaluation is the packed
         forward_with_cfg (``use_cfg``: 2 B' samples, halves of equal sizes) or the packed forward.  Returns one tensor per sample -
         ``[n_grid, C, H_b, W_b]`` or the last state ``[C, H_b, W_b]`` - all views of one allocation."""
-        if method not in _lib.ODE_METHODS:
-            raise LuminaLibError(f"fixed-grid method '{method}' not in {sorted(_lib.ODE_METHODS)}")
+        garr, n, code, _ = self._fixed_grid(method, tgrid)
         flat, hw, spans = self._pack(zs, "sample_ode_packed")
-        garr, n = _grid_array(tgrid)
         a = self._packed_step_args(flat, len(spans), cfg_scale, scale_factor, scale_watershed, base_seqlen, proportional_attn)
         out, traj_ptr, fin_ptr = _traj_or_final(flat, n, flat.shape, return_trajectory)
-        with torch.cuda.device(self.device):
-            rc = self.lib.lt_sample_ode_packed(self.handle, C.c_void_p(flat.data_ptr()), hw, traj_ptr, fin_ptr, garr, n, _lib.ODE_METHODS[method],
-                                               int(use_cfg), int(t_round_to_state_dtype), C.byref(a), C.c_void_p(_stream_ptr(self.device)))
-        _lib.check(rc, "lt_sample_ode_packed")
-        if return_trajectory:
-            return [out[:, off:off + math.prod(shape)].view((n,) + shape) for off, shape in spans]
-        return [out[off:off + math.prod(shape)].view(shape) for off, shape in spans]
+        self._call("lt_sample_ode_packed", self._dev(flat), hw, traj_ptr, fin_ptr, garr, n, code, int(use_cfg), int(t_round_to_state_dtype),
+                   C.byref(a), self._stream())
+        return self._unpacked(out, spans, n if return_trajectory else None)
 
     # ---- inpainting: the fixed-grid trajectory with a per-element blend after every step (DESIGN 7f) -------------
     @staticmethod
@@ -456,18 +482,13 @@ class DiTEngine:
         source latent ``x1`` and the ``noise`` the trajectory started from, all shaped and typed like ``z``"""
         _require_gpu(z, "z")
         self._refuse_masked_multistep(method, "sample_ode_masked")
-        if method not in _lib.ODE_METHODS:
-            raise LuminaLibError(f"fixed-grid method '{method}' not in {sorted(_lib.ODE_METHODS)}")
+        garr, n, code, _ = self._fixed_grid(method, tgrid)
         z = z.contiguous()
         m, src, nz = self._masked_operands(z, mask, x1, noise, "sample_ode_masked")
-        garr, n = _grid_array(tgrid)
         a = self._step_args(z, cfg_scale, scale_factor, scale_watershed, base_seqlen, proportional_attn, ntk_factor=ntk_factor)
         out, traj_ptr, fin_ptr = _traj_or_final(z, n, z.shape, return_trajectory)
-        with torch.cuda.device(self.device):
-            rc = self.lib.lt_sample_ode_masked(self.handle, C.c_void_p(z.data_ptr()), C.c_void_p(m.data_ptr()), C.c_void_p(src.data_ptr()),
-                                               C.c_void_p(nz.data_ptr()), traj_ptr, fin_ptr, garr, n, _lib.ODE_METHODS[method], int(use_cfg),
-                                               int(t_round_to_state_dtype), C.byref(a), C.c_void_p(_stream_ptr(self.device)))
-        _lib.check(rc, "lt_sample_ode_masked")
+        self._call("lt_sample_ode_masked", self._dev(z), self._dev(m), self._dev(src), self._dev(nz), traj_ptr, fin_ptr, garr, n, code,
+                   int(use_cfg), int(t_round_to_state_dtype), C.byref(a), self._stream())
         return out
 
     def sample_ode_masked_packed(self, zs, tgrid, masks, x1s, noises, method: str, *, use_cfg: bool, cfg_scale: float = 1.0,
@@ -476,8 +497,7 @@ class DiTEngine:
         """``sample_ode_packed`` with the inpainting blend (lt_sample_ode_masked_packed): ``masks``, ``x1s`` and ``noises`` are lists like
         ``zs``, sample b of each shaped like ``zs[b]``"""
         self._refuse_masked_multistep(method, "sample_ode_masked_packed")
-        if method not in _lib.ODE_METHODS:
-            raise LuminaLibError(f"fixed-grid method '{method}' not in {sorted(_lib.ODE_METHODS)}")
+        garr, n, code, _ = self._fixed_grid(method, tgrid)
         zs = list(zs)
         flat, hw, spans = self._pack(zs, "sample_ode_masked_packed")
         flats = []
@@ -488,18 +508,11 @@ class DiTEngine:
                 raise LuminaLibError(f"sample_ode_masked_packed: {name} must be a list of {len(zs)} tensors, each with the shape, dtype and "
                                      "device of its sample")
             flats.append(torch.cat([v.reshape(-1) for v in vs]))
-        garr, n = _grid_array(tgrid)
         a = self._packed_step_args(flat, len(spans), cfg_scale, scale_factor, scale_watershed, base_seqlen, proportional_attn)
         out, traj_ptr, fin_ptr = _traj_or_final(flat, n, flat.shape, return_trajectory)
-        with torch.cuda.device(self.device):
-            rc = self.lib.lt_sample_ode_masked_packed(self.handle, C.c_void_p(flat.data_ptr()), hw, C.c_void_p(flats[0].data_ptr()),
-                                                      C.c_void_p(flats[1].data_ptr()), C.c_void_p(flats[2].data_ptr()), traj_ptr, fin_ptr, garr, n,
-                                                      _lib.ODE_METHODS[method], int(use_cfg), int(t_round_to_state_dtype), C.byref(a),
-                                                      C.c_void_p(_stream_ptr(self.device)))
-        _lib.check(rc, "lt_sample_ode_masked_packed")
-        if return_trajectory:
-            return [out[:, off:off + math.prod(shape)].view((n,) + shape) for off, shape in spans]
-        return [out[off:off + math.prod(shape)].view(shape) for off, shape in spans]
+        self._call("lt_sample_ode_masked_packed", self._dev(flat), hw, *[self._dev(f) for f in flats], traj_ptr, fin_ptr, garr, n, code,
+                   int(use_cfg), int(t_round_to_state_dtype), C.byref(a), self._stream())
+        return self._unpacked(out, spans, n if return_trajectory else None)
 
     # ---- guidance schedules: a scale per stage, conditional-only stages at half the rows -------------
     def sample_ode_cfg_schedule(self, z: torch.Tensor, tgrid, table, method: str, *, scale_factor: float = 1.0, scale_watershed: float = 1.0,
@@ -509,23 +522,13 @@ class DiTEngine:
         at scale 1 exactly evaluate the ``z.size(0) / 2`` cond rows alone.  ``table``: ``(len(tgrid) - 1) * stages`` fp32 values (a tensor or a
         sequence; ``transport.guidance.cfg_table`` builds one).  The conditioning was prepared for all rows, once.  ``cfg_scale`` is ignored."""
         _require_gpu(z, "z")
-        if method not in _lib.ODE_METHODS:
-            raise LuminaLibError(f"fixed-grid method '{method}' not in {sorted(_lib.ODE_METHODS)}")
+        garr, n, code, count = self._fixed_grid(method, tgrid)
         z = z.contiguous()
-        garr, n = _grid_array(tgrid)
-        tab = table if isinstance(table, torch.Tensor) else torch.tensor(list(table), dtype=torch.float32)
-        tab = tab.detach().to("cpu", torch.float32).reshape(-1).contiguous()
-        stages = {"euler": 1, "midpoint": 2, "rk4": 4}[method]
-        if tab.numel() != max(n - 1, 0) * stages:
-            raise LuminaLibError(f"sample_ode_cfg_schedule: the table has {tab.numel()} entries, a {n}-point {method} grid has "
-                                 f"{max(n - 1, 0) * stages} stages")
+        tab = self._stage_table(table, "sample_ode_cfg_schedule", n, method, count)
         a = self._step_args(z, 0.0, scale_factor, scale_watershed, base_seqlen, proportional_attn, ntk_factor=ntk_factor)
         out, traj_ptr, fin_ptr = _traj_or_final(z, max(n, 1), z.shape, return_trajectory)
-        with torch.cuda.device(self.device):
-            rc = self.lib.lt_sample_ode_cfg_schedule(self.handle, C.c_void_p(z.data_ptr()), traj_ptr, fin_ptr, garr, n, _lib.ODE_METHODS[method],
-                                                     C.cast(tab.data_ptr(), C.POINTER(C.c_float)), int(t_round_to_state_dtype), C.byref(a),
-                                                     C.c_void_p(_stream_ptr(self.device)))
-        _lib.check(rc, "lt_sample_ode_cfg_schedule")
+        self._call("lt_sample_ode_cfg_schedule", self._dev(z), traj_ptr, fin_ptr, garr, n, code, self._host(tab), int(t_round_to_state_dtype),
+                   C.byref(a), self._stream())
         return out
 
     # ---- skip-layer guidance: a third prediction with a set of blocks left out (DESIGN 7m) -------------
@@ -545,17 +548,11 @@ class DiTEngine:
                         ntk_factor: float = 1.0) -> torch.Tensor:
         """one guided evaluation with skip-layer guidance (lt_forward_cfg_slg): ``u + w (c - u) + s (c - k)`` on the guided channels, ``k`` the
         cond rows evaluated with the blocks ``slg_layers`` left out.  ``slg_scale == 0`` is ``forward(use_cfg=True)``."""
-        _require_gpu(x, "x")
-        x = x.contiguous()
-        t32 = t.to(device=x.device, dtype=torch.float32).contiguous()
-        out = torch.empty_like(x)
+        x, t32, out = self._eval_io(x, t)
         a = self._step_args(x, cfg_scale, scale_factor, scale_watershed, base_seqlen, proportional_attn, ntk_factor=ntk_factor)
         skip = self._skip_array(slg_layers, "forward_cfg_slg")
-        with torch.cuda.device(self.device):
-            rc = self.lib.lt_forward_cfg_slg(self.handle, C.c_void_p(x.data_ptr()), C.c_void_p(t32.data_ptr()), C.c_void_p(out.data_ptr()),
-                                             float(cfg_scale), float(slg_scale), skip, len(skip), C.byref(a),
-                                             C.c_void_p(_stream_ptr(self.device)))
-        _lib.check(rc, "lt_forward_cfg_slg")
+        self._call("lt_forward_cfg_slg", self._dev(x), self._dev(t32), self._dev(out), float(cfg_scale), float(slg_scale), skip, len(skip),
+                   C.byref(a), self._stream())
         return out
 
     # ---- perturbed-attention guidance: the third prediction runs a set of blocks with the identity as their attention map (DESIGN 7o) -----
@@ -565,81 +562,64 @@ class DiTEngine:
         """one guided evaluation with perturbed-attention guidance (lt_forward_cfg_pag): ``u + w (c - u) + s (c - p)`` on the guided channels,
         ``p`` the cond rows evaluated with the blocks ``pag_layers`` perturbed (and ``skip_layers`` left out).  ``pag_scale == 0`` is
         ``forward(use_cfg=True)``."""
-        _require_gpu(x, "x")
-        x = x.contiguous()
-        t32 = t.to(device=x.device, dtype=torch.float32).contiguous()
-        out = torch.empty_like(x)
+        x, t32, out = self._eval_io(x, t)
         a = self._step_args(x, cfg_scale, scale_factor, scale_watershed, base_seqlen, proportional_attn, ntk_factor=ntk_factor)
         skip = self._skip_array(skip_layers, "forward_cfg_pag")
         perturb = self._skip_array(pag_layers, "forward_cfg_pag", "perturb")
-        with torch.cuda.device(self.device):
-            rc = self.lib.lt_forward_cfg_pag(self.handle, C.c_void_p(x.data_ptr()), C.c_void_p(t32.data_ptr()), C.c_void_p(out.data_ptr()),
-                                             float(cfg_scale), float(pag_scale), skip, len(skip), perturb, len(perturb), C.byref(a),
-                                             C.c_void_p(_stream_ptr(self.device)))
-        _lib.check(rc, "lt_forward_cfg_pag")
+        self._call("lt_forward_cfg_pag", self._dev(x), self._dev(t32), self._dev(out), float(cfg_scale), float(pag_scale), skip, len(skip),
+                   perturb, len(perturb), C.byref(a), self._stream())
         return out
 
     def sample_ode_cfg_pag(self, z: torch.Tensor, tgrid, table, pag, pag_layers, method: str, *, skip_layers=(), **kw) -> torch.Tensor:
         """``sample_ode_cfg_slg`` with the third prediction taken with the blocks ``pag_layers`` perturbed and ``skip_layers`` left out, under
         the one scale table ``pag`` (lt_sample_ode_cfg_pag).  ``transport.guidance.sample_cfg_pag`` is the definition."""
-        return self.sample_ode_cfg_slg(z, tgrid, table, pag, skip_layers, method, pag_layers=pag_layers, _who="sample_ode_cfg_pag", **kw)
+        return self._sample_ode_cfg_third("sample_ode_cfg_pag", z, tgrid, table, pag, skip_layers, pag_layers, method, **kw)
 
     def sample_ode_cfg_slg(self, z: torch.Tensor, tgrid, table, slg, slg_layers, method: str, *, scale_factor: float = 1.0,
                            scale_watershed: float = 1.0, base_seqlen: Optional[int] = None, proportional_attn: bool = False,
                            t_round_to_state_dtype: bool = True, return_trajectory: bool = True, ntk_factor: float = 1.0,
-                           cfg_scale=None, pag_layers=None, _who: str = "sample_ode_cfg_slg") -> torch.Tensor:
+                           cfg_scale=None) -> torch.Tensor:
         """``sample_ode_cfg_schedule`` with a skip-layer scale per stage (lt_sample_ode_cfg_slg): a stage with ``slg != 0`` also evaluates the
         cond rows with the blocks ``slg_layers`` left out and pushes the guided output away from that prediction.
         ``transport.guidance.sample_cfg_slg`` is the definition, ``slg_table`` builds the scale tables."""
-        what = "skip-layer guidance" if pag_layers is None else "perturbed-attention guidance"
+        return self._sample_ode_cfg_third("sample_ode_cfg_slg", z, tgrid, table, slg, slg_layers, None, method, scale_factor=scale_factor,
+                                          scale_watershed=scale_watershed, base_seqlen=base_seqlen, proportional_attn=proportional_attn,
+                                          t_round_to_state_dtype=t_round_to_state_dtype, return_trajectory=return_trajectory,
+                                          ntk_factor=ntk_factor, cfg_scale=cfg_scale)
+
+    def _sample_ode_cfg_third(self, who: str, z, tgrid, table, third, skip_layers, pag_layers, method: str, *, scale_factor: float = 1.0,
+                              scale_watershed: float = 1.0, base_seqlen: Optional[int] = None, proportional_attn: bool = False,
+                              t_round_to_state_dtype: bool = True, return_trajectory: bool = True, ntk_factor: float = 1.0,
+                              cfg_scale=None) -> torch.Tensor:
+        """the guided trajectory with a third prediction per stage under the scale table ``third``: the cond rows with ``skip_layers`` left
+        out (``pag_layers=None``: lt_sample_ode_cfg_slg) or, besides, ``pag_layers`` perturbed (lt_sample_ode_cfg_pag)"""
+        what, short = ("skip-layer guidance", "slg") if pag_layers is None else ("perturbed-attention guidance", "pag")
         if isinstance(z, (list, tuple)):
-            raise LuminaLibError(f"{_who}: a packed batch (a list of latents) is not served")
+            raise LuminaLibError(f"{who}: a packed batch (a list of latents) is not served")
         _require_gpu(z, "z")
-        if method not in _lib.ODE_METHODS:
-            raise LuminaLibError(f"{_who}: {what} is built for the fixed-grid methods {sorted(_lib.ODE_METHODS)}, not "
-                                 f"'{method}'")
+        garr, n, code, count = self._fixed_grid(
+            method, tgrid, f"{who}: {what} is built for the fixed-grid methods {sorted(_lib.ODE_METHODS)}, not '{method}'")
         z = z.contiguous()
-        garr, n = _grid_array(tgrid)
-        stages = {"euler": 1, "midpoint": 2, "rk4": 4}[method]
-        count = max(n - 1, 0) * stages
-        tab = table if isinstance(table, torch.Tensor) else torch.tensor(list(table), dtype=torch.float32)
-        tab = tab.detach().to("cpu", torch.float32).reshape(-1).contiguous()
-        sl_ptr = None  # (None: the C entry refuses the null table by name)
-        if slg is not None:
-            sl = slg if isinstance(slg, torch.Tensor) else torch.tensor(list(slg), dtype=torch.float32)
-            sl = sl.detach().to("cpu", torch.float32).reshape(-1).contiguous()
-            if sl.numel() != count:
-                raise LuminaLibError(f"{_who}: the {'slg' if pag_layers is None else 'pag'} table has {sl.numel()} entries, the grid has {count} "
-                                     "evaluations")
-            sl_ptr = C.cast(sl.data_ptr(), C.POINTER(C.c_float))
-        if tab.numel() != count:
-            raise LuminaLibError(f"{_who}: the guidance table has {tab.numel()} entries, the grid has {count} evaluations")
-        skip = self._skip_array(slg_layers, _who)
+        # (third=None: the C entry refuses the null table by name)
+        sl = None if third is None else self._table(
+            third, count, lambda got: f"{who}: the {short} table has {got} entries, the grid has {count} evaluations")
+        tab = self._table(table, count, lambda got: f"{who}: the guidance table has {got} entries, the grid has {count} evaluations")
+        skip = self._skip_array(skip_layers, who)
         a = self._step_args(z, 0.0, scale_factor, scale_watershed, base_seqlen, proportional_attn, ntk_factor=ntk_factor)
         out, traj_ptr, fin_ptr = _traj_or_final(z, max(n, 1), z.shape, return_trajectory)
+        layers = (skip, len(skip))
         if pag_layers is not None:
-            perturb = self._skip_array(pag_layers, _who, "perturb")
-            with torch.cuda.device(self.device):
-                rc = self.lib.lt_sample_ode_cfg_pag(self.handle, C.c_void_p(z.data_ptr()), traj_ptr, fin_ptr, garr, n, _lib.ODE_METHODS[method],
-                                                    C.cast(tab.data_ptr(), C.POINTER(C.c_float)), sl_ptr, skip, len(skip), perturb, len(perturb),
-                                                    int(t_round_to_state_dtype), C.byref(a), C.c_void_p(_stream_ptr(self.device)))
-            _lib.check(rc, "lt_sample_ode_cfg_pag")
-            return out
-        with torch.cuda.device(self.device):
-            rc = self.lib.lt_sample_ode_cfg_slg(self.handle, C.c_void_p(z.data_ptr()), traj_ptr, fin_ptr, garr, n, _lib.ODE_METHODS[method],
-                                                C.cast(tab.data_ptr(), C.POINTER(C.c_float)), sl_ptr, skip, len(skip), int(t_round_to_state_dtype),
-                                                C.byref(a), C.c_void_p(_stream_ptr(self.device)))
-        _lib.check(rc, "lt_sample_ode_cfg_slg")
+            perturb = self._skip_array(pag_layers, who, "perturb")
+            layers += (perturb, len(perturb))
+        self._call(f"lt_sample_ode_cfg_{short}", self._dev(z), traj_ptr, fin_ptr, garr, n, code, self._host(tab), self._host(sl), *layers,
+                   int(t_round_to_state_dtype), C.byref(a), self._stream())
         return out
 
     # ---- rescaled and norm-limited guidance: a per-sample factor on every guided stage (DESIGN 7i) -------------
     @staticmethod
     def _rule(rescale, norm_limit, what: str):
         from .transport.guidance import check_rule
-        try:
-            return check_rule(rescale, norm_limit)
-        except ValueError as exc:
-            raise LuminaLibError(f"{what}: {exc}") from None
+        return _refusing(check_rule, rescale, norm_limit, who=what)
 
     def sample_ode_cfg_rule(self, z: torch.Tensor, tgrid, table, method: str, *, rescale: float = 0.0, norm_limit: float = math.inf,
                             scale_factor: float = 1.0, scale_watershed: float = 1.0, base_seqlen: Optional[int] = None,
@@ -651,50 +631,31 @@ class DiTEngine:
         conditional-only and skip the rule.  This IS the rule call, at any parameters; ``model.sample_ode_cfg_schedule`` routes the defaults to
         the schedule call."""
         _require_gpu(z, "z")
-        if method not in _lib.ODE_METHODS:
-            raise LuminaLibError(f"fixed-grid method '{method}' not in {sorted(_lib.ODE_METHODS)}")
+        garr, n, code, count = self._fixed_grid(method, tgrid)
         rescale, norm_limit = self._rule(rescale, norm_limit, "sample_ode_cfg_rule")
         z = z.contiguous()
-        garr, n = _grid_array(tgrid)
-        tab = table if isinstance(table, torch.Tensor) else torch.tensor(list(table), dtype=torch.float32)
-        tab = tab.detach().to("cpu", torch.float32).reshape(-1).contiguous()
-        stages = {"euler": 1, "midpoint": 2, "rk4": 4}[method]
-        if tab.numel() != max(n - 1, 0) * stages:
-            raise LuminaLibError(f"sample_ode_cfg_rule: the table has {tab.numel()} entries, a {n}-point {method} grid has "
-                                 f"{max(n - 1, 0) * stages} stages")
+        tab = self._stage_table(table, "sample_ode_cfg_rule", n, method, count)
         a = self._step_args(z, 0.0, scale_factor, scale_watershed, base_seqlen, proportional_attn, ntk_factor=ntk_factor)
         out, traj_ptr, fin_ptr = _traj_or_final(z, max(n, 1), z.shape, return_trajectory)
-        with torch.cuda.device(self.device):
-            rc = self.lib.lt_sample_ode_cfg_rule(self.handle, C.c_void_p(z.data_ptr()), traj_ptr, fin_ptr, garr, n, _lib.ODE_METHODS[method],
-                                                 C.cast(tab.data_ptr(), C.POINTER(C.c_float)), rescale, norm_limit, int(t_round_to_state_dtype),
-                                                 C.byref(a), C.c_void_p(_stream_ptr(self.device)))
-        _lib.check(rc, "lt_sample_ode_cfg_rule")
+        self._call("lt_sample_ode_cfg_rule", self._dev(z), traj_ptr, fin_ptr, garr, n, code, self._host(tab), rescale, norm_limit,
+                   int(t_round_to_state_dtype), C.byref(a), self._stream())
         return out
 
     def forward_cfg_rule(self, x: torch.Tensor, t: torch.Tensor, *, cfg_scale: float, rescale: float = 0.0, norm_limit: float = math.inf,
                          scale_factor: float = 1.0, scale_watershed: float = 1.0, base_seqlen: Optional[int] = None,
                          proportional_attn: bool = False, ntk_factor: float = 1.0) -> torch.Tensor:
         """one guided evaluation at ``cfg_scale`` under the rule (lt_forward_cfg_rule): ``guided_rule`` on the model's output of all rows"""
-        _require_gpu(x, "x")
+        x, t32, out = self._eval_io(x, t)
         rescale, norm_limit = self._rule(rescale, norm_limit, "forward_cfg_rule")
-        x = x.contiguous()
-        t32 = t.to(device=x.device, dtype=torch.float32).contiguous()
-        out = torch.empty_like(x)
         a = self._step_args(x, cfg_scale, scale_factor, scale_watershed, base_seqlen, proportional_attn, ntk_factor=ntk_factor)
-        with torch.cuda.device(self.device):
-            rc = self.lib.lt_forward_cfg_rule(self.handle, C.c_void_p(x.data_ptr()), C.c_void_p(t32.data_ptr()), C.c_void_p(out.data_ptr()),
-                                              rescale, norm_limit, C.byref(a), C.c_void_p(_stream_ptr(self.device)))
-        _lib.check(rc, "lt_forward_cfg_rule")
+        self._call("lt_forward_cfg_rule", self._dev(x), self._dev(t32), self._dev(out), rescale, norm_limit, C.byref(a), self._stream())
         return out
 
     # ---- projected guidance: APG and CFG-Zero* (DESIGN 7q) -------------
     @staticmethod
     def _project(apg, zero_star, zero_init, what: str, n_grid=None):
         from .transport.guidance import check_project
-        try:
-            form, eta, beta, r, zero_init = check_project(apg, zero_star, zero_init, n_grid=n_grid)
-        except ValueError as exc:
-            raise LuminaLibError(f"{what}: {exc}") from None
+        form, eta, beta, r, zero_init = _refusing(check_project, apg, zero_star, zero_init, n_grid=n_grid, who=what)
         if form is None:
             raise LuminaLibError(f"{what}: needs a projected form - apg=dict(eta=, momentum=, norm_threshold=) or zero_star=True")
         return _lib.PROJECT_FORMS[form], eta, beta, r, zero_init
@@ -711,25 +672,16 @@ class DiTEngine:
         if isinstance(z, (list, tuple)):
             raise LuminaLibError("sample_ode_cfg_project: a packed batch (a list of latents) is not served")
         _require_gpu(z, "z")
-        if method not in _lib.ODE_METHODS:
-            raise LuminaLibError(f"sample_ode_cfg_project: projected guidance is built for the fixed-grid methods {sorted(_lib.ODE_METHODS)}, "
-                                 f"not '{method}'")
+        garr, n, code, count = self._fixed_grid(
+            method, tgrid, f"sample_ode_cfg_project: projected guidance is built for the fixed-grid methods {sorted(_lib.ODE_METHODS)}, "
+                           f"not '{method}'")
         z = z.contiguous()
-        garr, n = _grid_array(tgrid)
         form, eta, beta, r, zero_init = self._project(apg, zero_star, zero_init, "sample_ode_cfg_project", n_grid=n)
-        tab = table if isinstance(table, torch.Tensor) else torch.tensor(list(table), dtype=torch.float32)
-        tab = tab.detach().to("cpu", torch.float32).reshape(-1).contiguous()
-        stages = {"euler": 1, "midpoint": 2, "rk4": 4}[method]
-        if tab.numel() != max(n - 1, 0) * stages:
-            raise LuminaLibError(f"sample_ode_cfg_project: the table has {tab.numel()} entries, a {n}-point {method} grid has "
-                                 f"{max(n - 1, 0) * stages} stages")
+        tab = self._stage_table(table, "sample_ode_cfg_project", n, method, count)
         a = self._step_args(z, 0.0, scale_factor, scale_watershed, base_seqlen, proportional_attn, ntk_factor=ntk_factor)
         out, traj_ptr, fin_ptr = _traj_or_final(z, max(n, 1), z.shape, return_trajectory)
-        with torch.cuda.device(self.device):
-            rc = self.lib.lt_sample_ode_cfg_project(self.handle, C.c_void_p(z.data_ptr()), traj_ptr, fin_ptr, garr, n, _lib.ODE_METHODS[method],
-                                                    C.cast(tab.data_ptr(), C.POINTER(C.c_float)), form, eta, beta, r, zero_init,
-                                                    int(t_round_to_state_dtype), C.byref(a), C.c_void_p(_stream_ptr(self.device)))
-        _lib.check(rc, "lt_sample_ode_cfg_project")
+        self._call("lt_sample_ode_cfg_project", self._dev(z), traj_ptr, fin_ptr, garr, n, code, self._host(tab), form, eta, beta, r, zero_init,
+                   int(t_round_to_state_dtype), C.byref(a), self._stream())
         return out
 
     def forward_cfg_project(self, x: torch.Tensor, t: torch.Tensor, *, cfg_scale: float, apg=None, zero_star: bool = False,
@@ -739,31 +691,25 @@ class DiTEngine:
         all rows.  ``keep_momentum`` (APG): continue from the momentum the last projected evaluation of this shape left, instead of zero."""
         if isinstance(x, (list, tuple)):
             raise LuminaLibError("forward_cfg_project: a packed batch (a list of latents) is not served")
-        _require_gpu(x, "x")
+        x, t32, out = self._eval_io(x, t)
         form, eta, beta, r, _ = self._project(apg, zero_star, 0, "forward_cfg_project")
-        x = x.contiguous()
-        t32 = t.to(device=x.device, dtype=torch.float32).contiguous()
-        out = torch.empty_like(x)
         a = self._step_args(x, cfg_scale, scale_factor, scale_watershed, base_seqlen, proportional_attn, ntk_factor=ntk_factor)
-        with torch.cuda.device(self.device):
-            rc = self.lib.lt_forward_cfg_project(self.handle, C.c_void_p(x.data_ptr()), C.c_void_p(t32.data_ptr()), C.c_void_p(out.data_ptr()),
-                                                 form, eta, beta, r, int(bool(keep_momentum)), C.byref(a), C.c_void_p(_stream_ptr(self.device)))
-        _lib.check(rc, "lt_forward_cfg_project")
+        self._call("lt_forward_cfg_project", self._dev(x), self._dev(t32), self._dev(out), form, eta, beta, r, int(bool(keep_momentum)),
+                   C.byref(a), self._stream())
         return out
 
     # ---- guidance reuse: the cond - uncond difference taken on refresh stages, reused on half-row stages (DESIGN 7k) -------------
-    @staticmethod
-    def _reuse_tables(table, reuse, count: int, what: str):
+    @classmethod
+    def _reuse_tables(cls, table, reuse, count: int, what: str):
         """the scale table and the flag table as contiguous fp32 / int32 CPU tensors of ``count`` entries (their contents are the C entry's to
         check)"""
-        tab = table if isinstance(table, torch.Tensor) else torch.tensor(list(table), dtype=torch.float32)
-        tab = tab.detach().to("cpu", torch.float32).reshape(-1).contiguous()
+        tab = cls._table(table)
         if reuse is None:
             raise LuminaLibError(f"{what}: reuse is None (one 0 / 1 flag per evaluation; transport.guidance.cfg_reuse_table builds one)")
         flg = reuse if isinstance(reuse, torch.Tensor) else torch.tensor(list(reuse))
         if flg.is_floating_point() and not bool((flg == flg.round()).all()):
             raise LuminaLibError(f"{what}: a reuse flag is not 0 (refresh) or 1 (reuse)")
-        flg = flg.detach().to("cpu", torch.int32).reshape(-1).contiguous()
+        flg = cls._table(flg, dtype=torch.int32)
         if tab.numel() != count or flg.numel() != count:
             raise LuminaLibError(f"{what}: the guidance table has {tab.numel()} entries and the reuse table {flg.numel()}, the grid has {count} "
                                  "evaluations")
@@ -778,19 +724,13 @@ class DiTEngine:
         if isinstance(z, (list, tuple)):
             raise LuminaLibError("sample_ode_cfg_reuse: a packed batch (a list of latents) is not served")
         _require_gpu(z, "z")
-        if method not in _lib.ODE_METHODS:
-            raise LuminaLibError(f"fixed-grid method '{method}' not in {sorted(_lib.ODE_METHODS)}")
+        garr, n, code, count = self._fixed_grid(method, tgrid)
         z = z.contiguous()
-        garr, n = _grid_array(tgrid)
-        stages = {"euler": 1, "midpoint": 2, "rk4": 4}[method]
-        tab, flg = self._reuse_tables(table, reuse, max(n - 1, 0) * stages, "sample_ode_cfg_reuse")
+        tab, flg = self._reuse_tables(table, reuse, count, "sample_ode_cfg_reuse")
         a = self._step_args(z, 0.0, scale_factor, scale_watershed, base_seqlen, proportional_attn, ntk_factor=ntk_factor)
         out, traj_ptr, fin_ptr = _traj_or_final(z, max(n, 1), z.shape, return_trajectory)
-        with torch.cuda.device(self.device):
-            rc = self.lib.lt_sample_ode_cfg_reuse(self.handle, C.c_void_p(z.data_ptr()), traj_ptr, fin_ptr, garr, n, _lib.ODE_METHODS[method],
-                                                  C.cast(tab.data_ptr(), C.POINTER(C.c_float)), C.cast(flg.data_ptr(), C.POINTER(C.c_int32)),
-                                                  int(t_round_to_state_dtype), C.byref(a), C.c_void_p(_stream_ptr(self.device)))
-        _lib.check(rc, "lt_sample_ode_cfg_reuse")
+        self._call("lt_sample_ode_cfg_reuse", self._dev(z), traj_ptr, fin_ptr, garr, n, code, self._host(tab), self._host(flg),
+                   int(t_round_to_state_dtype), C.byref(a), self._stream())
         return out
 
     def sample_ode_multistep_cfg_reuse(self, z: torch.Tensor, tgrid, method: Optional[str], table, reuse, *, coef=None, scale_factor: float = 1.0,
@@ -806,12 +746,8 @@ class DiTEngine:
         tab, flg = self._reuse_tables(table, reuse, n - 1, "sample_ode_multistep_cfg_reuse")
         a = self._step_args(z, 0.0, scale_factor, scale_watershed, base_seqlen, proportional_attn, ntk_factor=ntk_factor)
         out, traj_ptr, fin_ptr = _traj_or_final(z, n, z.shape, return_trajectory)
-        with torch.cuda.device(self.device):
-            rc = self.lib.lt_sample_ode_multistep_cfg_reuse(self.handle, C.c_void_p(z.data_ptr()), traj_ptr, fin_ptr, garr, n,
-                                                            C.cast(coef.data_ptr(), C.POINTER(C.c_float)), corrector,
-                                                            C.cast(tab.data_ptr(), C.POINTER(C.c_float)), C.cast(flg.data_ptr(), C.POINTER(C.c_int32)),
-                                                            int(t_round_to_state_dtype), C.byref(a), C.c_void_p(_stream_ptr(self.device)))
-        _lib.check(rc, "lt_sample_ode_multistep_cfg_reuse")
+        self._call("lt_sample_ode_multistep_cfg_reuse", self._dev(z), traj_ptr, fin_ptr, garr, n, self._host(coef), corrector, self._host(tab),
+                   self._host(flg), int(t_round_to_state_dtype), C.byref(a), self._stream())
         return out
 
     def forward_cfg_reuse(self, x: torch.Tensor, t: torch.Tensor, *, cfg_scale: float, reuse: bool = False, scale_factor: float = 1.0,
@@ -820,18 +756,11 @@ class DiTEngine:
         """one guided evaluation at ``cfg_scale`` (lt_forward_cfg_reuse): ``reuse=False`` is ``forward_with_cfg`` and keeps the cond - uncond
         difference, ``reuse=True`` evaluates the cond rows alone and guides them with the difference kept - refused by name when none of this
         shape is there.  ``out`` (optional): the tensor to write, shaped and typed like ``x``."""
-        _require_gpu(x, "x")
-        x = x.contiguous()
-        t32 = t.to(device=x.device, dtype=torch.float32).contiguous()
-        if out is None:
-            out = torch.empty_like(x)
-        elif out.shape != x.shape or out.dtype != x.dtype or out.device != x.device or not out.is_contiguous():
+        x, t32, out = self._eval_io(x, t, out=out)
+        if out.shape != x.shape or out.dtype != x.dtype or out.device != x.device or not out.is_contiguous():
             raise LuminaLibError("forward_cfg_reuse: out must be contiguous and shaped and typed like x")
         a = self._step_args(x, cfg_scale, scale_factor, scale_watershed, base_seqlen, proportional_attn, ntk_factor=ntk_factor)
-        with torch.cuda.device(self.device):
-            rc = self.lib.lt_forward_cfg_reuse(self.handle, C.c_void_p(x.data_ptr()), C.c_void_p(t32.data_ptr()), C.c_void_p(out.data_ptr()),
-                                               int(bool(reuse)), C.byref(a), C.c_void_p(_stream_ptr(self.device)))
-        _lib.check(rc, "lt_forward_cfg_reuse")
+        self._call("lt_forward_cfg_reuse", self._dev(x), self._dev(t32), self._dev(out), int(bool(reuse)), C.byref(a), self._stream())
         return out
 
     # ---- linear multistep sampling: one evaluation per interval (DESIGN 7j) -------------
@@ -851,11 +780,7 @@ class DiTEngine:
             raise LuminaLibError(f"{what}: multistep method '{method}' not in {list(multistep.MULTISTEP_METHODS)}")
         if n < 2:
             raise LuminaLibError(f"{what}: need at least 2 grid points")
-        try:
-            tab = multistep.multistep_table(tgrid, method).contiguous()
-        except ValueError as exc:
-            raise LuminaLibError(f"{what}: {exc}") from None
-        return tab, int(multistep.is_corrector(method))
+        return _refusing(multistep.multistep_table, tgrid, method, who=what).contiguous(), int(multistep.is_corrector(method))
 
     def sample_ode_multistep(self, z: torch.Tensor, tgrid, method: Optional[str], *, use_cfg: bool, cfg_scale: float = 1.0, table=None, coef=None,
                              rescale: float = 0.0,
@@ -873,20 +798,12 @@ class DiTEngine:
         garr, n = _grid_array(tgrid)
         coef, corrector = self._multistep_table(tgrid, method, n, "sample_ode_multistep", coef)
         rescale, norm_limit = self._rule(rescale, norm_limit, "sample_ode_multistep")
-        tab_ptr = None
-        if table is not None:
-            tab = table if isinstance(table, torch.Tensor) else torch.tensor(list(table), dtype=torch.float32)
-            tab = tab.detach().to("cpu", torch.float32).reshape(-1).contiguous()
-            if tab.numel() != n - 1:
-                raise LuminaLibError(f"sample_ode_multistep: the guidance table has {tab.numel()} entries, a {n}-point grid has {n - 1} evaluations")
-            tab_ptr = C.cast(tab.data_ptr(), C.POINTER(C.c_float))
+        tab = None if table is None else self._table(
+            table, n - 1, lambda got: f"sample_ode_multistep: the guidance table has {got} entries, a {n}-point grid has {n - 1} evaluations")
         a = self._step_args(z, cfg_scale, scale_factor, scale_watershed, base_seqlen, proportional_attn, ntk_factor=ntk_factor)
         out, traj_ptr, fin_ptr = _traj_or_final(z, n, z.shape, return_trajectory)
-        with torch.cuda.device(self.device):
-            rc = self.lib.lt_sample_ode_multistep(self.handle, C.c_void_p(z.data_ptr()), traj_ptr, fin_ptr, garr, n,
-                                                  C.cast(coef.data_ptr(), C.POINTER(C.c_float)), corrector, tab_ptr, rescale, norm_limit, int(use_cfg),
-                                                  int(t_round_to_state_dtype), C.byref(a), C.c_void_p(_stream_ptr(self.device)))
-        _lib.check(rc, "lt_sample_ode_multistep")
+        self._call("lt_sample_ode_multistep", self._dev(z), traj_ptr, fin_ptr, garr, n, self._host(coef), corrector, self._host(tab), rescale,
+                   norm_limit, int(use_cfg), int(t_round_to_state_dtype), C.byref(a), self._stream())
         return out
 
     def sample_ode_multistep_packed(self, zs, tgrid, method: str, *, use_cfg: bool, cfg_scale: float = 1.0, scale_factor: float = 1.0,
@@ -899,14 +816,9 @@ class DiTEngine:
         coef, corrector = self._multistep_table(tgrid, method, n, "sample_ode_multistep_packed")
         a = self._packed_step_args(flat, len(spans), cfg_scale, scale_factor, scale_watershed, base_seqlen, proportional_attn)
         out, traj_ptr, fin_ptr = _traj_or_final(flat, n, flat.shape, return_trajectory)
-        with torch.cuda.device(self.device):
-            rc = self.lib.lt_sample_ode_multistep_packed(self.handle, C.c_void_p(flat.data_ptr()), hw, traj_ptr, fin_ptr, garr, n,
-                                                         C.cast(coef.data_ptr(), C.POINTER(C.c_float)), corrector, int(use_cfg),
-                                                         int(t_round_to_state_dtype), C.byref(a), C.c_void_p(_stream_ptr(self.device)))
-        _lib.check(rc, "lt_sample_ode_multistep_packed")
-        if return_trajectory:
-            return [out[:, off:off + math.prod(shape)].view((n,) + shape) for off, shape in spans]
-        return [out[off:off + math.prod(shape)].view(shape) for off, shape in spans]
+        self._call("lt_sample_ode_multistep_packed", self._dev(flat), hw, traj_ptr, fin_ptr, garr, n, self._host(coef), corrector, int(use_cfg),
+                   int(t_round_to_state_dtype), C.byref(a), self._stream())
+        return self._unpacked(out, spans, n if return_trajectory else None)
 
     def sample_ode_adaptive(self, z: torch.Tensor, tgrid: torch.Tensor, method: str, *, rtol: float, atol: float,
                             first_step: Optional[float] = None, max_steps: int = 2 ** 31 - 1, use_cfg: bool, cfg_scale: float = 1.0,
@@ -925,14 +837,10 @@ class DiTEngine:
         a = self._step_args(z, cfg_scale, scale_factor, scale_watershed, base_seqlen, proportional_attn, ntk_factor=ntk_factor)
         out = torch.empty((max(n, 1),) + tuple(z.shape), dtype=z.dtype, device=z.device)
         dts = (C.c_float * max_recorded_steps)()
-        st = _lib.LtOdeAdaptiveStats(dt_cap=max_recorded_steps, dt_host=C.cast(dts, C.POINTER(C.c_float)))
-        with torch.cuda.device(self.device):
-            rc = self.lib.lt_sample_ode_adaptive(self.handle, C.c_void_p(z.data_ptr()), C.c_void_p(out.data_ptr()), garr, n,
-                                                 _lib.ODE_ADAPTIVE_METHODS[method], float(rtol), float(atol),
-                                                 0.0 if first_step is None else float(first_step), int(min(max_steps, 2 ** 31 - 1)),
-                                                 int(use_cfg), int(t_round_to_state_dtype), C.byref(a),
-                                                 C.c_void_p(_stream_ptr(self.device)), C.byref(st))
-        _lib.check(rc, "lt_sample_ode_adaptive")
+        st = _lib.LtOdeAdaptiveStats(dt_cap=max_recorded_steps, dt_host=dts)
+        self._call("lt_sample_ode_adaptive", self._dev(z), self._dev(out), garr, n, _lib.ODE_ADAPTIVE_METHODS[method], float(rtol), float(atol),
+                   0.0 if first_step is None else float(first_step), int(min(max_steps, 2 ** 31 - 1)), int(use_cfg),
+                   int(t_round_to_state_dtype), C.byref(a), self._stream(), C.byref(st))
         stats = dict(nfe=int(st.nfe), accepted=int(st.accepted), rejected=int(st.rejected), first_step=float(st.first_step),
                      dt=[float(dts[i]) for i in range(min(st.dt_count, max_recorded_steps))])
         return out, stats
@@ -963,20 +871,16 @@ class DiTEngine:
         noise = noise.contiguous()
         a = self._step_args(z, cfg_scale, scale_factor, scale_watershed, base_seqlen, proportional_attn, ntk_factor=ntk_factor)
         traj = torch.empty_like(noise)
-        final, fin_ptr, last_ptr = None, C.c_void_p(0), None
+        final = last = None
         if last_step is not None:
             if last_coef is None:
                 raise LuminaLibError("sample_sde: a last step needs its coefficient record")
-            last_coef = last_coef.detach().to("cpu", torch.float32).contiguous()
-            if last_coef.numel() != _lib.LT_SDE_REC:
-                raise LuminaLibError(f"sample_sde: last_coef must hold {_lib.LT_SDE_REC} floats, got {last_coef.numel()}")
+            last = last_coef.detach().to("cpu", torch.float32).contiguous()
+            if last.numel() != _lib.LT_SDE_REC:
+                raise LuminaLibError(f"sample_sde: last_coef must hold {_lib.LT_SDE_REC} floats, got {last.numel()}")
             final = torch.empty_like(z, dtype=z.dtype if last_step == "Euler" else torch.float32)
-            fin_ptr, last_ptr = C.c_void_p(final.data_ptr()), C.cast(last_coef.data_ptr(), C.POINTER(C.c_float))
-        with torch.cuda.device(self.device):
-            rc = self.lib.lt_sample_sde(self.handle, C.c_void_p(z.data_ptr()), C.c_void_p(noise.data_ptr()), C.c_void_p(traj.data_ptr()), fin_ptr,
-                                        C.cast(steps.data_ptr(), C.POINTER(C.c_float)), n_loop + 1, _lib.SDE_METHODS[method],
-                                        _lib.SDE_LAST_STEPS[last_step], last_ptr, int(use_cfg), C.byref(a), C.c_void_p(_stream_ptr(self.device)))
-        _lib.check(rc, "lt_sample_sde")
+        self._call("lt_sample_sde", self._dev(z), self._dev(noise), self._dev(traj), self._dev(final), self._host(steps), n_loop + 1,
+                   _lib.SDE_METHODS[method], _lib.SDE_LAST_STEPS[last_step], self._host(last), int(use_cfg), C.byref(a), self._stream())
         return traj, final
 
     # ---- prompt-driven editing (FlowEdit) ---------------------------------------------------------------
@@ -992,21 +896,15 @@ class DiTEngine:
         garr, n = _grid_array(tgrid)
         if n < 2:
             raise LuminaLibError("sample_flowedit: need at least 2 grid points")
-        try:
-            x_src, z, noise = check_edit_operands(x_src, z, noise, n - 1)
-            sc = check_scales(scales, n - 1)
-        except ValueError as exc:
-            raise LuminaLibError(f"sample_flowedit: {exc}") from None
+        x_src, z, noise = _refusing(check_edit_operands, x_src, z, noise, n - 1, who="sample_flowedit")
+        sc = _refusing(check_scales, scales, n - 1, who="sample_flowedit")
         x_src, z, noise = x_src.contiguous(), z.contiguous(), noise.contiguous()
         a = self._step_args(x_src, 1.0, scale_factor, scale_watershed, base_seqlen, proportional_attn, cfg_channels=int(cfg_channels),
                             ntk_factor=ntk_factor)
         a.batch = 4 * x_src.shape[0]
         out, traj_ptr, fin_ptr = _traj_or_final(x_src, n, x_src.shape, return_trajectory)
-        with torch.cuda.device(self.device):
-            rc = self.lib.lt_sample_flowedit(self.handle, C.c_void_p(z.data_ptr()), C.c_void_p(x_src.data_ptr()), C.c_void_p(noise.data_ptr()),
-                                             traj_ptr, fin_ptr, garr, C.cast(sc.data_ptr(), C.POINTER(C.c_float)), n, C.byref(a),
-                                             C.c_void_p(_stream_ptr(self.device)))
-        _lib.check(rc, "lt_sample_flowedit")
+        self._call("lt_sample_flowedit", self._dev(z), self._dev(x_src), self._dev(noise), traj_ptr, fin_ptr, garr, self._host(sc), n,
+                   C.byref(a), self._stream())
         return out
 
     # ---- multi-view (visual-anagram) sampling -------------------------------------------------------------------
@@ -1015,10 +913,9 @@ class DiTEngine:
         an ``latent_h x latent_w`` latent; the engine builds the inverse permutations and rejects a table that is not a bijection.
         ``views=None`` drops them.  May synchronise the stream (table upload), unlike the sampling loop."""
         from . import views as _views
-        s = C.c_void_p(_stream_ptr(self.device))
+        s = self._stream()
         if views is None:
-            with torch.cuda.device(self.device):
-                _lib.check(self.lib.lt_set_views(self.handle, None, None, None, 0, 0, 0, s), "lt_set_views")
+            self._call("lt_set_views", None, None, None, 0, 0, 0, s)
             self._views_key = None
             return
         if isinstance(views, tuple) and len(views) == 3 and all(isinstance(t, torch.Tensor) for t in views):
@@ -1035,10 +932,7 @@ class DiTEngine:
         vs = vsign.detach().to("cpu", torch.float32).contiguous()
         isg = isign.detach().to("cpu", torch.float32).contiguous()
         self._views_key = None
-        with torch.cuda.device(self.device):
-            rc = self.lib.lt_set_views(self.handle, C.c_void_p(perm_d.data_ptr()), C.cast(vs.data_ptr(), C.POINTER(C.c_float)),
-                                       C.cast(isg.data_ptr(), C.POINTER(C.c_float)), V, int(latent_h), int(latent_w), s)
-        _lib.check(rc, "lt_set_views")
+        self._call("lt_set_views", self._dev(perm_d), self._host(vs), self._host(isg), V, int(latent_h), int(latent_w), s)
         self._views_key = (V, int(latent_h), int(latent_w))
 
     def sample_views(self, z: torch.Tensor, tgrid, method: str = "midpoint", *, cfg_scale: float = 1.0, scale_factor: float = 1.0,
@@ -1049,22 +943,17 @@ class DiTEngine:
         B = 2 V (rows 0..V-1 the view prompts, rows V..2V-1 the negative prompt).  Returns ``[n_grid, C, H, W]`` (or the last latent
         ``[1, C, H, W]``)."""
         _require_gpu(z, "z")
-        if method not in _lib.ODE_METHODS:
-            raise LuminaLibError(f"fixed-grid method '{method}' not in {sorted(_lib.ODE_METHODS)}")
+        garr, n, code, _ = self._fixed_grid(method, tgrid)
         if z.dim() != 4 or z.shape[0] != 1:
             raise LuminaLibError(f"sample_views takes ONE latent [1, C, H, W], got {tuple(z.shape)}")
         key = getattr(self, "_views_key", None)
         if key is None:
             raise LuminaLibError("sample_views: no views uploaded (call set_views first)")
         z = z.contiguous()
-        garr, n = _grid_array(tgrid)
         a = self._step_args(z, cfg_scale, scale_factor, scale_watershed, base_seqlen, proportional_attn)
         a.batch = 2 * key[0]
         out, traj_ptr, fin_ptr = _traj_or_final(z, n, z.shape[1:], return_trajectory)
-        with torch.cuda.device(self.device):
-            rc = self.lib.lt_sample_views(self.handle, C.c_void_p(z.data_ptr()), traj_ptr, fin_ptr, garr, n, _lib.ODE_METHODS[method],
-                                          C.byref(a), C.c_void_p(_stream_ptr(self.device)))
-        _lib.check(rc, "lt_sample_views")
+        self._call("lt_sample_views", self._dev(z), traj_ptr, fin_ptr, garr, n, code, C.byref(a), self._stream())
         return out
 
     def set_softmax_rule(self, rule) -> None:
@@ -1073,7 +962,7 @@ class DiTEngine:
         code = _lib.SOFTMAX_RULES.get(rule, rule) if isinstance(rule, str) else rule
         if isinstance(code, str):
             raise LuminaLibError(f"softmax rule '{rule}' not in {sorted(_lib.SOFTMAX_RULES)}")
-        _lib.check(self.lib.lt_set_softmax_rule(self.handle, int(code)), "lt_set_softmax_rule")
+        self._call("lt_set_softmax_rule", int(code))
         self.softmax_rule = int(code)
 
     def sample_views_guided(self, z: torch.Tensor, guidance: torch.Tensor, tgrid, coef: torch.Tensor, *, noise: Optional[torch.Tensor] = None,
@@ -1104,11 +993,8 @@ class DiTEngine:
         a = self._step_args(z, cfg_scale, scale_factor, scale_watershed, base_seqlen, proportional_attn)
         a.batch = 2 * key[0]
         out, traj_ptr, fin_ptr = _traj_or_final(z, n, z.shape[1:], return_trajectory)
-        with torch.cuda.device(self.device):
-            rc = self.lib.lt_sample_views_guided(self.handle, C.c_void_p(z.data_ptr()), C.c_void_p(guidance.data_ptr()), C.c_void_p(noise.data_ptr()),
-                                                 traj_ptr, fin_ptr, garr, C.cast(coef.data_ptr(), C.POINTER(C.c_float)), n, C.byref(a),
-                                                 C.c_void_p(_stream_ptr(self.device)))
-        _lib.check(rc, "lt_sample_views_guided")
+        self._call("lt_sample_views_guided", self._dev(z), self._dev(guidance), self._dev(noise), traj_ptr, fin_ptr, garr, self._host(coef), n,
+                   C.byref(a), self._stream())
         return out
 
     # ---- tiled (MultiDiffusion) sampling: one canvas, the model on overlapping windows of it ---------------------
@@ -1117,10 +1003,9 @@ class DiTEngine:
         window ``win_hw``, on a canvas ``canvas_hw``; ``weights`` fp32 ``[win_h, win_w]`` (``transport.tiled.window_weights``; ``None``: ones).
         The engine refuses, by name, a table it cannot serve or that leaves a pixel of the canvas uncovered.  ``offsets=None`` drops the
         table.  Synchronises the stream once (the cover check), unlike the sampling loop."""
-        s = C.c_void_p(_stream_ptr(self.device))
+        s = self._stream()
         if offsets is None:
-            with torch.cuda.device(self.device):
-                _lib.check(self.lib.lt_set_windows(self.handle, None, 0, 0, 0, 0, 0, None, s), "lt_set_windows")
+            self._call("lt_set_windows", None, 0, 0, 0, 0, 0, None, s)
             self._windows_key = None
             return
         offs = [(int(t), int(l)) for t, l in (offsets.tolist() if isinstance(offsets, torch.Tensor) else offsets)]
@@ -1131,9 +1016,7 @@ class DiTEngine:
                 raise LuminaLibError(f"set_windows: weights must be a tensor [{h}, {w}] (transport.tiled.window_weights)")
             wd = weights.detach().to(device=self.device, dtype=torch.float32).contiguous()
         arr = (C.c_int32 * max(2 * len(offs), 1))(*[v for o in offs for v in o])
-        with torch.cuda.device(self.device):
-            rc = self.lib.lt_set_windows(self.handle, arr, len(offs), h, w, Hc, Wc, C.c_void_p(wd.data_ptr() if wd is not None else 0), s)
-        _lib.check(rc, "lt_set_windows")  # (a refusal leaves the table in force, and its key, as they were)
+        self._call("lt_set_windows", arr, len(offs), h, w, Hc, Wc, self._dev(wd), s)  # (a refusal leaves the table in force, and its key)
         self._windows_key = (len(offs), h, w, Hc, Wc)
 
     def _tiled_args(self, y: torch.Tensor, what: str, cfg_scale, scale_factor, scale_watershed, base_seqlen, proportional_attn, ntk_factor):
@@ -1155,15 +1038,10 @@ class DiTEngine:
         as one ``forward_with_cfg`` of 2 n rows at ``t`` (2 n stage times), their predictions fused.  Needs ``set_windows`` and a conditioning
         prepared at B = 2 n (rows 0 .. n-1 the window prompts, rows n .. 2n-1 the negative prompts)."""
         a = self._tiled_args(y, "forward_tiled", cfg_scale, scale_factor, scale_watershed, base_seqlen, proportional_attn, ntk_factor)
-        y = y.contiguous()
-        t32 = t.to(device=y.device, dtype=torch.float32).contiguous()
+        y, t32, out = self._eval_io(y, t, name="y")
         if t32.numel() != a.batch:
             raise LuminaLibError(f"forward_tiled: t has {t32.numel()} entries, the {a.batch // 2} windows are evaluated as {a.batch} rows")
-        out = torch.empty_like(y)
-        with torch.cuda.device(self.device):
-            rc = self.lib.lt_forward_tiled(self.handle, C.c_void_p(y.data_ptr()), C.c_void_p(t32.data_ptr()), C.c_void_p(out.data_ptr()), C.byref(a),
-                                           C.c_void_p(_stream_ptr(self.device)))
-        _lib.check(rc, "lt_forward_tiled")
+        self._call("lt_forward_tiled", self._dev(y), self._dev(t32), self._dev(out), C.byref(a), self._stream())
         return out
 
     def sample_ode_tiled(self, z: torch.Tensor, tgrid, method: str = "midpoint", *, cfg_scale: float = 1.0, scale_factor: float = 1.0,
@@ -1172,17 +1050,14 @@ class DiTEngine:
         """the fixed-grid trajectory of ONE canvas latent ``z [1, C, Hc, Wc]`` in one call (lt_sample_ode_tiled;
         ``transport.tiled.sample_tiled`` is the definition): every stage is ``forward_tiled``, the steps are ``sample_ode``'s.  Returns
         ``[n_grid, 1, C, Hc, Wc]`` or the last canvas."""
-        if method not in _lib.ODE_METHODS:
-            raise LuminaLibError(f"sample_ode_tiled: tiled sampling is built for the fixed-grid methods {sorted(_lib.ODE_METHODS)}, not '{method}' "
-                                 "(the multistep and adaptive solvers are not served)")
+        garr, n, code, _ = self._fixed_grid(
+            method, tgrid, f"sample_ode_tiled: tiled sampling is built for the fixed-grid methods {sorted(_lib.ODE_METHODS)}, not '{method}' "
+                           "(the multistep and adaptive solvers are not served)")
         a = self._tiled_args(z, "sample_ode_tiled", cfg_scale, scale_factor, scale_watershed, base_seqlen, proportional_attn, ntk_factor)
         z = z.contiguous()
-        garr, n = _grid_array(tgrid)
         out, traj_ptr, fin_ptr = _traj_or_final(z, max(n, 1), z.shape, return_trajectory)
-        with torch.cuda.device(self.device):
-            rc = self.lib.lt_sample_ode_tiled(self.handle, C.c_void_p(z.data_ptr()), traj_ptr, fin_ptr, garr, n, _lib.ODE_METHODS[method],
-                                              int(t_round_to_state_dtype), C.byref(a), C.c_void_p(_stream_ptr(self.device)))
-        _lib.check(rc, "lt_sample_ode_tiled")
+        self._call("lt_sample_ode_tiled", self._dev(z), traj_ptr, fin_ptr, garr, n, code, int(t_round_to_state_dtype), C.byref(a),
+                   self._stream())
         return out
 
     def last_nfe(self) -> int:
@@ -1198,13 +1073,13 @@ class DiTEngine:
 
     # ---- mixture-of-experts routing hooks (parity tests) ----------------------------------------------
     def moe_routing_record(self, on: bool = True) -> None:
-        _lib.check(self.lib.lt_moe_routing_record(self.handle, 1 if on else 0), "lt_moe_routing_record")
+        self._call("lt_moe_routing_record", 1 if on else 0)
 
     def moe_routing_read(self, rows: int):
         """experts the last forward picked: int32 array [n_layers, 2 (time, token branch), rows, 2]; -1 = branch not run"""
         import numpy as np
         out = np.empty((int(self.cfg.n_layers), 2, rows, 2), dtype=np.int32)
-        _lib.check(self.lib.lt_moe_routing_read(self.handle, out.ctypes.data_as(C.POINTER(C.c_int32)), rows), "lt_moe_routing_read")
+        self._call("lt_moe_routing_read", out.ctypes.data_as(C.POINTER(C.c_int32)), rows)
         return out
 
     def moe_routing_force(self, sel=None) -> None:
@@ -1212,31 +1087,29 @@ class DiTEngine:
         None ends it"""
         import numpy as np
         if sel is None:
-            _lib.check(self.lib.lt_moe_routing_force(self.handle, None, 0), "lt_moe_routing_force")
+            self._call("lt_moe_routing_force", None, 0)
             return
         sel = np.ascontiguousarray(sel, dtype=np.int32)
         assert sel.ndim == 4 and sel.shape[0] == int(self.cfg.n_layers) and sel.shape[1] == 2 and sel.shape[3] == 2, sel.shape
-        _lib.check(self.lib.lt_moe_routing_force(self.handle, sel.ctypes.data_as(C.POINTER(C.c_int32)), sel.shape[2]),
-                   "lt_moe_routing_force")
+        self._call("lt_moe_routing_force", sel.ctypes.data_as(C.POINTER(C.c_int32)), sel.shape[2])
 
     # ---- profiling hooks used by bench.py -----------------------------------------------------------
     def profile_enable(self, on) -> None:
         """False / 0: off; True: every kernel class; int: bit mask (1 GEMM, 2 attention, 4 other)"""
-        mask = 7 if on is True else int(on)
-        _lib.check(self.lib.lt_profile_enable_mask(self.handle, mask), "lt_profile_enable_mask")
+        self._call("lt_profile_enable_mask", 7 if on is True else int(on))
 
     def profile_set_budget(self, klass: int, max_event_launches: int) -> None:
-        _lib.check(self.lib.lt_profile_set_budget(self.handle, klass, max_event_launches), "lt_profile_set_budget")
+        self._call("lt_profile_set_budget", klass, max_event_launches)
 
     def profile_set_window(self, klass: int, skip_launches: int, max_event_launches: int) -> None:
-        _lib.check(self.lib.lt_profile_set_window(self.handle, klass, skip_launches, max_event_launches), "lt_profile_set_window")
+        self._call("lt_profile_set_window", klass, skip_launches, max_event_launches)
 
     def profile_reset(self) -> None:
-        _lib.check(self.lib.lt_profile_reset(self.handle), "lt_profile_reset")
+        self._call("lt_profile_reset")
 
     def profile_read(self, klass: int) -> Tuple[float, int, float]:
         ms, n, fl = C.c_double(), C.c_int64(), C.c_double()
-        _lib.check(self.lib.lt_profile_read(self.handle, klass, C.byref(ms), C.byref(n), C.byref(fl)), "lt_profile_read")
+        self._call("lt_profile_read", klass, C.byref(ms), C.byref(n), C.byref(fl))
         return ms.value, n.value, fl.value
 
 

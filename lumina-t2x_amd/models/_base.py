@@ -10,7 +10,7 @@ import torch
 import torch.nn as nn
 
 from .. import _lib
-from ..engine import DiTEngine, EngineLimits, _refuse_if_capturing
+from ..engine import DiTEngine, EngineLimits, _refuse_if_capturing, _refusing
 
 
 # Any (re-)registration of a Parameter OR of a sub-module anywhere (setattr of an nn.Parameter, load_state_dict(assign=True),
@@ -102,33 +102,22 @@ class EngineSamplers:
         lt_sample_ode_cfg_pag (``slg_layers`` then join the same third prediction), or - with ``apg`` / ``zero_star`` -
         lt_sample_ode_cfg_project"""
         from ..transport.guidance import check_project, refuse_rule_with_reuse, refuse_with_pag, refuse_with_project, refuse_with_slg, rule_is_off
-        try:
-            form = check_project(apg, zero_star, zero_init)[0]
-            refuse_with_project(form, method=method, rescale=rescale, norm_limit=norm_limit, reuse=reuse, slg=slg, pag=pag,
-                                packed=not isinstance(x, torch.Tensor))
-        except ValueError as exc:
-            raise _lib.LuminaLibError(str(exc)) from None
-        if pag is not None:
-            if not isinstance(x, torch.Tensor):
-                raise _lib.LuminaLibError("perturbed-attention guidance: a packed batch (a list of latents) is not served")
-            try:
-                refuse_with_pag(pag, method=method, rescale=rescale, norm_limit=norm_limit, reuse=reuse, slg=slg)
-            except ValueError as exc:
-                raise _lib.LuminaLibError(str(exc)) from None
-        if slg is not None:
-            if not isinstance(x, torch.Tensor):
-                raise _lib.LuminaLibError("skip-layer guidance: a packed batch (a list of latents) is not served")
-            try:
-                refuse_with_slg(slg, method=method, rescale=rescale, norm_limit=norm_limit, reuse=reuse)
-            except ValueError as exc:
-                raise _lib.LuminaLibError(str(exc)) from None
-        if reuse is not None:
-            if not isinstance(x, torch.Tensor):
-                raise _lib.LuminaLibError("guidance reuse: a packed batch (a list of latents) is not served")
-            try:
-                refuse_rule_with_reuse(rescale, norm_limit)
-            except ValueError as exc:
-                raise _lib.LuminaLibError(str(exc)) from None
+        packed = not isinstance(x, torch.Tensor)
+        form = _refusing(check_project, apg, zero_star, zero_init)[0]
+        _refusing(refuse_with_project, form, method=method, rescale=rescale, norm_limit=norm_limit, reuse=reuse, slg=slg, pag=pag, packed=packed)
+        companions = (
+            (pag, "perturbed-attention guidance",
+             lambda: refuse_with_pag(pag, method=method, rescale=rescale, norm_limit=norm_limit, reuse=reuse, slg=slg)),
+            (slg, "skip-layer guidance",
+             lambda: refuse_with_slg(slg, method=method, rescale=rescale, norm_limit=norm_limit, reuse=reuse)),
+            (reuse, "guidance reuse",
+             lambda: refuse_rule_with_reuse(rescale, norm_limit)),
+        )
+        for given, name, check in companions:
+            if given is not None:  # a companion table: tensor states only, and not beside what its check names
+                if packed:
+                    raise _lib.LuminaLibError(f"{name}: a packed batch (a list of latents) is not served")
+                _refusing(check)
         kw.setdefault("cfg_scale", 1.0)
         eng, args = self._engine_sampler_args(x, True, kw)
         args.pop("cfg_scale", None)
@@ -200,17 +189,9 @@ class EngineSamplers:
         ``self.last_cache_stats`` = dict(stats [ncalls, 3] float64: rel, acc after the add, ran; hits; nfe; rows).  Returns the last state, or
         all ``len(tgrid)`` states."""
         from ..transport import cache as TC
-        if not isinstance(z, torch.Tensor):
-            raise _lib.LuminaLibError("sample_ode_teacache: a packed batch (a list of latents) is not served by step caching")
-        names = self._cond_names + ("cfg_scale",)
-        if len(cond) > len(names):
-            raise TypeError(f"sample_ode_teacache takes {names}, got {len(cond)} positional arguments")
-        kw = dict(zip(names, cond), **step_kw)
-        try:
-            TC.check_cache_method(method)
-            TC.check_cache_args(threshold, coefficients)
-        except ValueError as exc:
-            raise _lib.LuminaLibError(str(exc)) from None
+        kw = self._guided_kw("sample_ode_teacache", z, cond, step_kw, "by step caching")
+        _refusing(TC.check_cache_method, method)
+        _refusing(TC.check_cache_args, threshold, coefficients)
         use_cfg = "cfg_scale" in kw
         if use_cfg:
             self._mirror_attention_flags(kw)
@@ -235,6 +216,23 @@ class EngineSamplers:
                                            t_round_to_state_dtype=t_round, **args)
         self.last_cache_stats = dict(stats=stats, hits=eng.last_cache_hits(), nfe=eng.last_nfe(), rows=eng.last_eval_rows())
         return out
+
+    def _guided_kw(self, who, x, cond, step_kw, served=None):
+        """the keyword arguments of ``forward_with_cfg`` from the call ``who(x, t, *cond, **step_kw)``: ``cond`` is the family's conditioning,
+        then ``cfg_scale``.  ``served`` (``None``: not tested here): the closing words of the refusal of a packed batch."""
+        if served is not None and not isinstance(x, torch.Tensor):
+            raise _lib.LuminaLibError(f"{who}: a packed batch (a list of latents) is not served {served}")
+        names = self._cond_names + ("cfg_scale",)
+        if len(cond) > len(names):
+            raise TypeError(f"{who} takes {names}, got {len(cond)} positional arguments")
+        return dict(zip(names, cond), **step_kw)
+
+    def _guided_engine(self, who, x, kw, needs_scale=True):
+        """(engine, step kwargs) of one guided evaluation, the module left as ``forward_with_cfg`` leaves it"""
+        if needs_scale and "cfg_scale" not in kw:
+            raise TypeError(f"{who} needs cfg_scale")
+        self._mirror_attention_flags(kw)
+        return self._engine_sampler_args(x, True, kw)
 
     def _mirror_attention_flags(self, kw):
         if hasattr(self, "layers") and "proportional_attn" in kw and len(self.layers) and hasattr(self.layers[0], "attention"):
@@ -303,16 +301,10 @@ class EngineSamplers:
         (lt_forward_cfg_rule): ``transport.guidance.guided_rule`` on the model's output of all rows.  ``cond``: the conditioning,
         then ``cfg_scale`` (or ``cfg_scale=`` by keyword).  At the defaults the call is ``forward_with_cfg``.  Tensor states only."""
         from ..transport.guidance import rule_is_off
-        if not isinstance(x, torch.Tensor):
-            raise _lib.LuminaLibError("forward_with_cfg_rule: a packed batch (a list of latents) is not served under a guidance rule")
-        names = self._cond_names + ("cfg_scale",)
-        if len(cond) > len(names):
-            raise TypeError(f"forward_with_cfg_rule takes {names}, got {len(cond)} positional arguments")
-        kw = dict(zip(names, cond), **step_kw)
+        kw = self._guided_kw("forward_with_cfg_rule", x, cond, step_kw, "under a guidance rule")
         if rule_is_off(rescale, norm_limit):
             return self.forward_with_cfg(x, t, **kw)
-        self._mirror_attention_flags(kw)
-        eng, args = self._engine_sampler_args(x, True, kw)
+        eng, args = self._guided_engine("forward_with_cfg_rule", x, kw, needs_scale=False)
         return eng.forward_cfg_rule(x, t, rescale=rescale, norm_limit=norm_limit, **args)
 
     @torch.no_grad()
@@ -323,24 +315,12 @@ class EngineSamplers:
         when none of this shape is stored, or the conditioning was prepared anew since.  With neither form the call is ``forward_with_cfg``.
         Tensor states only."""
         from ..transport.guidance import check_project
-        if not isinstance(x, torch.Tensor):
-            raise _lib.LuminaLibError("forward_with_cfg_project: a packed batch (a list of latents) is not served by projected guidance")
-        names = self._cond_names + ("cfg_scale",)
-        if len(cond) > len(names):
-            raise TypeError(f"forward_with_cfg_project takes {names}, got {len(cond)} positional arguments")
-        kw = dict(zip(names, cond), **step_kw)
-        try:
-            form = check_project(apg, zero_star)[0]
-        except ValueError as exc:
-            raise _lib.LuminaLibError(f"forward_with_cfg_project: {exc}") from None
-        if form is None:
+        kw = self._guided_kw("forward_with_cfg_project", x, cond, step_kw, "by projected guidance")
+        if _refusing(check_project, apg, zero_star, who="forward_with_cfg_project")[0] is None:
             if keep_momentum:
                 raise _lib.LuminaLibError("forward_with_cfg_project: keep_momentum belongs to APG (apg=dict(...))")
             return self.forward_with_cfg(x, t, **kw)
-        if "cfg_scale" not in kw:
-            raise TypeError("forward_with_cfg_project needs cfg_scale")
-        self._mirror_attention_flags(kw)
-        eng, args = self._engine_sampler_args(x, True, kw)
+        eng, args = self._guided_engine("forward_with_cfg_project", x, kw)
         return eng.forward_cfg_project(x, t, apg=apg, zero_star=zero_star, keep_momentum=keep_momentum, **args)
 
     @torch.no_grad()
@@ -349,16 +329,8 @@ class EngineSamplers:
         ``forward_with_cfg``'s) or reuses (``reuse=True``: the cond rows alone are evaluated) the cond - uncond difference of the guided channels
         (lt_forward_cfg_reuse).  ``cond``: the conditioning for all ``x.size(0)`` rows, then ``cfg_scale`` (or ``cfg_scale=`` by
         keyword).  A reuse with no difference of this shape kept since the conditioning was last prepared is refused by name.  Tensor states only."""
-        if not isinstance(x, torch.Tensor):
-            raise _lib.LuminaLibError("forward_with_cfg_reuse: a packed batch (a list of latents) is not served by guidance reuse")
-        names = self._cond_names + ("cfg_scale",)
-        if len(cond) > len(names):
-            raise TypeError(f"forward_with_cfg_reuse takes {names}, got {len(cond)} positional arguments")
-        kw = dict(zip(names, cond), **step_kw)
-        if "cfg_scale" not in kw:
-            raise TypeError("forward_with_cfg_reuse needs cfg_scale")
-        self._mirror_attention_flags(kw)
-        eng, args = self._engine_sampler_args(x, True, kw)
+        kw = self._guided_kw("forward_with_cfg_reuse", x, cond, step_kw, "by guidance reuse")
+        eng, args = self._guided_engine("forward_with_cfg_reuse", x, kw)
         return eng.forward_cfg_reuse(x, t, reuse=reuse, **args)
 
     @torch.no_grad()
@@ -367,16 +339,8 @@ class EngineSamplers:
         DESIGN 7m): the cond rows are also evaluated with the blocks ``slg_layers`` left out (``k``), and the guided channels become
         ``u + cfg_scale (c - u) + slg_scale (c - k)``.  ``cond``: the conditioning for all ``x.size(0)`` rows, then ``cfg_scale`` (or by
         keyword).  ``slg_scale == 0`` is ``forward_with_cfg``.  Tensor states only."""
-        if not isinstance(x, torch.Tensor):
-            raise _lib.LuminaLibError("forward_with_cfg_slg: a packed batch (a list of latents) is not served by skip-layer guidance")
-        names = self._cond_names + ("cfg_scale",)
-        if len(cond) > len(names):
-            raise TypeError(f"forward_with_cfg_slg takes {names}, got {len(cond)} positional arguments")
-        kw = dict(zip(names, cond), **step_kw)
-        if "cfg_scale" not in kw:
-            raise TypeError("forward_with_cfg_slg needs cfg_scale")
-        self._mirror_attention_flags(kw)
-        eng, args = self._engine_sampler_args(x, True, kw)
+        kw = self._guided_kw("forward_with_cfg_slg", x, cond, step_kw, "by skip-layer guidance")
+        eng, args = self._guided_engine("forward_with_cfg_slg", x, kw)
         return eng.forward_cfg_slg(x, t, slg_scale=slg_scale, slg_layers=slg_layers, **args)
 
     @torch.no_grad()
@@ -385,16 +349,8 @@ class EngineSamplers:
         (lt_forward_cfg_pag): the cond rows are also evaluated with the blocks ``pag_layers`` perturbed - their self-attention map
         replaced by the identity - and the blocks ``skip_layers`` left out (``p``), and the guided channels become
         ``u + cfg_scale (c - u) + pag_scale (c - p)``.  ``pag_scale == 0`` is ``forward_with_cfg``.  Tensor states only."""
-        if not isinstance(x, torch.Tensor):
-            raise _lib.LuminaLibError("forward_with_cfg_pag: a packed batch (a list of latents) is not served by perturbed-attention guidance")
-        names = self._cond_names + ("cfg_scale",)
-        if len(cond) > len(names):
-            raise TypeError(f"forward_with_cfg_pag takes {names}, got {len(cond)} positional arguments")
-        kw = dict(zip(names, cond), **step_kw)
-        if "cfg_scale" not in kw:
-            raise TypeError("forward_with_cfg_pag needs cfg_scale")
-        self._mirror_attention_flags(kw)
-        eng, args = self._engine_sampler_args(x, True, kw)
+        kw = self._guided_kw("forward_with_cfg_pag", x, cond, step_kw, "by perturbed-attention guidance")
+        eng, args = self._guided_engine("forward_with_cfg_pag", x, kw)
         return eng.forward_cfg_pag(x, t, pag_scale=pag_scale, pag_layers=pag_layers, skip_layers=skip_layers, **args)
 
     # ---- tiled (MultiDiffusion) sampling: one canvas, the model on overlapping windows of it (DESIGN 7r) ---------------------
@@ -440,10 +396,8 @@ class EngineSamplers:
         (``transport.tiled.window_grid``), ``weights`` fp32 ``[win_h, win_w]`` (``window_weights``; ``None``: ones).  ``cond``: the family's
         conditioning for the 2 n rows (or for 2: one prompt and one negative prompt for every window), then ``cfg_scale``; ``step_kw``: the
         other keyword arguments of ``forward_with_cfg``.  ``t``: one stage time, or 2 n."""
-        names = self._cond_names + ("cfg_scale",)
-        if len(cond) > len(names):
-            raise TypeError(f"forward_with_cfg_tiled takes {names}, got {len(cond)} positional arguments")
-        eng, args, n = self._tiled_engine("forward_with_cfg_tiled", y, windows, weights, dict(zip(names, cond), **step_kw))
+        kw = self._guided_kw("forward_with_cfg_tiled", y, cond, step_kw)
+        eng, args, n = self._tiled_engine("forward_with_cfg_tiled", y, windows, weights, kw)
         tv = torch.as_tensor(t, dtype=torch.float32, device=y.device).reshape(-1)
         return eng.forward_tiled(y, tv.expand(2 * n) if tv.numel() == 1 else tv, **args)
 
@@ -455,14 +409,12 @@ class EngineSamplers:
         ``forward_with_cfg`` of 2 n rows and fuses their predictions; euler / midpoint / rk4 step the canvas.  Arguments as
         ``forward_with_cfg_tiled``.  Returns the last canvas, or all ``len(tgrid)`` canvases."""
         from ..transport.tiled import refuse_with_tiled
-        names = self._cond_names + ("cfg_scale",)
-        if len(cond) > len(names):
-            raise TypeError(f"sample_ode_tiled takes {names}, got {len(cond)} positional arguments")
+        kw = self._guided_kw("sample_ode_tiled", z, cond, step_kw)
         try:
             refuse_with_tiled(method)
         except NotImplementedError as exc:
             raise _lib.LuminaLibError(f"sample_ode_tiled: {exc}") from None
-        eng, args, _ = self._tiled_engine("sample_ode_tiled", z, windows, weights, dict(zip(names, cond), **step_kw))
+        eng, args, _ = self._tiled_engine("sample_ode_tiled", z, windows, weights, kw)
         return eng.sample_ode_tiled(z, tgrid, method, t_round_to_state_dtype=t_round, return_trajectory=return_trajectory, **args)
 
     def _engine_sample_ode_tiled(self, x, tgrid, method, t_round, windows, weights, kw):
