@@ -285,6 +285,36 @@ int lt_forward_tiled(lt_engine* e, const void* y_dev, const float* t_dev, void* 
 int lt_sample_ode_tiled(lt_engine* e, const void* z_dev, void* traj_dev, void* final_dev, const float* tgrid_host, int32_t n_grid, int32_t method,
                         int32_t t_round_to_state_dtype, const lt_step_args* a, void* stream);
 
+/* ---- composed guidance (Composable Diffusion, Liu et al. 2022): K weighted prompts and one base prompt per image in one call ----------------
+ *     g = u + sum_{k = 1 .. K} w_k (c_k - u)            a negative w_k is a negation ("A but NOT C"), K = 1 is classifier-free guidance
+ * The state has B' rows.  Every evaluation replicates them K + 1 times and runs ONE plain forward (use_cfg = 0) of a->batch = (K + 1) B' rows
+ * through the evaluation's own graph cache - no new graph key, no new evaluation kind: it IS an lt_forward of that shape.  Row layout of the
+ * conditioning (lt_prepare_prompt / lt_prepare_labels at (K + 1) B' rows, every variant) and of the model's output: rows k B' + b belong to
+ * prompt k of image b (k = 0 .. K-1), rows K B' + b to the base (negative / empty) prompt.  lumina-t2x_amd/transport/guidance.py is the
+ * definition (the reference has no such sampler) and the calls equal it bit for bit: guided_compose on channels < a->cfg_channels, with R =
+ * round to bf16 (the model's output dtype, whatever a->io_dtype) and every difference, product and sum one fp32 operation,
+ *     acc = R(w_1 R(c_1 - u));   acc = R(acc + R(w_k R(c_k - u)))  for k = 2 .. K in this order;   g = R(u + acc)
+ * which at K = 1 is lt_forward_cfg's chain word for word; channels >= a->cfg_channels are prompt 1's row, copied (the first half of
+ * lt_forward_cfg's output under the reference's cfg_channels = 3 quirk).  The K weights are read on the HOST during the call and travel as a
+ * kernel argument: no graph is re-recorded when they change.  A prompt of weight 0 is still evaluated (leaving its rows out would change the
+ * row count, and with it the graph key).
+ * lt_forward_compose: one evaluation.  x_dev / out_dev [B', C, H, W] in a->io_dtype, t_dev float [(K + 1) B'], w_host float [K].
+ * lt_sample_ode_compose: lt_sample_ode(use_cfg = 0) on the B' rows with the three steps above as every stage's velocity: stage times, dt
+ * handling, t_round and every stage / closing combine are lt_sample_ode's.  w_host float [(n_grid - 1) * stages][K]: stage s of interval i
+ * uses row i * stages + s (transport/guidance.py compose_table).  traj_dev (may be NULL) receives the n_grid states [B', C, H, W], final_dev
+ * (may be NULL) the last.  lt_last_nfe = (n_grid - 1) * stages, lt_last_eval_rows = (K + 1) B' times that.  No synchronisation, no host read.
+ * The replicated rows and the model's outputs live in the engine-owned window-row buffers of the tiled calls (max_batch samples wide),
+ * allocated by the first call that needs them (that call is refused on a stream under capture).
+ * Both refuse by name, before anything is launched and with the outputs untouched: a null argument; K < 1 or K > LT_COMPOSE_MAX; a->batch not a
+ * positive multiple of K + 1, or above max_batch; a weight that is not finite; a->cfg_channels outside 1 .. in_channels; what lt_forward
+ * refuses of the shape; a regional prompt; a layer-skip or perturb set; a conditioning prepared for another batch; lt_sample_ode_compose also
+ * a stream under capture, a grid of fewer than 2 points and an unknown method. */
+#define LT_COMPOSE_MAX 7
+int lt_forward_compose(lt_engine* e, const void* x_dev, const float* t_dev, void* out_dev, const float* w_host, int32_t K, const lt_step_args* a,
+                       void* stream);
+int lt_sample_ode_compose(lt_engine* e, const void* z_dev, void* traj_dev, void* final_dev, const float* tgrid_host, int32_t n_grid, int32_t method,
+                          const float* w_host, int32_t K, int32_t t_round_to_state_dtype, const lt_step_args* a, void* stream);
+
 /* ---- multi-view sampling, Phase Upscale: visual_anagrams/generate.py:465-494 with midpoint_solver_extra (:222-262) -------------------------
  * lt_set_softmax_rule: the model of that phase is visual_anagrams/models/nextdit.py, which differs from LT_VARIANT_NEXT_T2I's model in ONE
  * scalar: under proportional_attn its self-attention softmax scale is log(N, base_seqlen) / sqrt(head_dim) (LT_SOFTMAX_ANAGRAM) where the T2I
@@ -863,6 +893,14 @@ int lt_op_windows_reduce(const void* f_dev, const int32_t* offsets_host, int32_t
                          const float* weight_dev, const float* wsum_dev, void* out_dev, int32_t C, int32_t dtype, void* stream);
 int lt_op_windows_cover(const int32_t* offsets_host, int32_t n, int32_t win_h, int32_t win_w, int32_t canvas_h, int32_t canvas_w,
                         const float* weight_dev, float* wsum_dev, int32_t* bad_dev, void* stream);
+/* the two kernels of lt_forward_compose on caller-owned buffers.  1 <= K <= LT_COMPOSE_MAX, Bp = B' >= 1, HW = H * W, dtype LT_F32 or LT_BF16;
+ * buffers of any element alignment (the group width 4 / 2 / 1 follows HW and the addresses).  Refused by name before anything is launched: a
+ * null argument, a count out of range, cfg_channels outside 1 .. C, a weight that is not finite, an output inside the input's row groups.
+ *   replicate: out [(K + 1) Bp, C, HW] = K + 1 exact copies of y [Bp, C, HW]
+ *   guidance:  out [Bp, C, HW] = guided_compose (transport/guidance.py) of f [(K + 1) Bp, C, HW] with w_host float [K] (HOST) */
+int lt_op_compose_replicate(const void* y_dev, void* out_dev, int32_t K, int32_t Bp, int32_t C, int32_t HW, int32_t dtype, void* stream);
+int lt_op_compose_guidance(const void* f_dev, void* out_dev, const float* w_host, int32_t K, int32_t Bp, int32_t C, int32_t HW, int32_t cfg_channels,
+                           int32_t dtype, void* stream);
 /* one fused step kernel of lt_sample_sde on caller-owned buffers of n elements (any n >= 1; buffers that are not 16-byte aligned take the
  * one-element-per-thread form).  op = LT_SDE_OP_*, rec_host = the stage's LT_SDE_REC floats, dtype LT_F32 or LT_BF16 (R: round to dtype):
  *   EULER      out = R(R(x + R(drift(x, v) * dt)) + R(q * R(w * sqrt_dt)))       drift(x, v) = R(v + R(D * R(R(R(r * v) - x) / var)))

@@ -32,6 +32,7 @@ ODE_ADAPTIVE_METHODS = {"dopri5": LT_ODE_DOPRI5, "bosh3": LT_ODE_BOSH3, "fehlber
 LT_ODE_AB2, LT_ODE_AB3, LT_ODE_ABM2, LT_ODE_ABM3 = 32, 33, 34, 35  # named where a call refuses them; lt_sample_ode_multistep takes the weight table
 ODE_MULTISTEP_METHODS = {"ab2": LT_ODE_AB2, "ab3": LT_ODE_AB3, "abm2": LT_ODE_ABM2, "abm3": LT_ODE_ABM3}
 LT_CACHE_PROBE, LT_CACHE_RUN, LT_CACHE_REUSE = 0, 1, 2
+LT_COMPOSE_MAX = 7  # prompts of a composed-guidance call beside the base prompt (lt_forward_compose / lt_sample_ode_compose)
 LT_RK_MAX_SLOPES, LT_RK_WS_BYTES = 7, 8192
 LT_SDE_EULER, LT_SDE_HEUN = 0, 1
 SDE_METHODS = {"Euler": LT_SDE_EULER, "Heun": LT_SDE_HEUN}
@@ -117,6 +118,8 @@ _SIGNATURES: Dict[str, tuple] = {
     "lt_set_windows": (_i32, [_vp, C.POINTER(_i32), _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "lt_forward_tiled": (_i32, [_vp, _vp, _vp, _vp, C.POINTER(LtStepArgs), _vp]),
     "lt_sample_ode_tiled": (_i32, [_vp, _vp, _vp, _vp, C.POINTER(_f32), _i32, _i32, _i32, C.POINTER(LtStepArgs), _vp]),
+    "lt_forward_compose": (_i32, [_vp, _vp, _vp, _vp, C.POINTER(_f32), _i32, C.POINTER(LtStepArgs), _vp]),
+    "lt_sample_ode_compose": (_i32, [_vp, _vp, _vp, _vp, C.POINTER(_f32), _i32, _i32, C.POINTER(_f32), _i32, _i32, C.POINTER(LtStepArgs), _vp]),
     "lt_set_softmax_rule": (_i32, [_vp, _i32]),
     "lt_sample_views_guided": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_f32), C.POINTER(_f32), _i32, C.POINTER(LtStepArgs), _vp]),
     "lt_sample_sde": (_i32, [_vp, _vp, _vp, _vp, _vp, C.POINTER(_f32), _i32, _i32, _i32, C.POINTER(_f32), _i32, C.POINTER(LtStepArgs), _vp]),
@@ -203,6 +206,8 @@ _SIGNATURES: Dict[str, tuple] = {
     "lt_op_windows_gather": (_i32, [_vp, C.POINTER(_i32), _i32, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _vp]),
     "lt_op_windows_reduce": (_i32, [_vp, C.POINTER(_i32), _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _vp]),
     "lt_op_windows_cover": (_i32, [C.POINTER(_i32), _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "lt_op_compose_replicate": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "lt_op_compose_guidance": (_i32, [_vp, _vp, C.POINTER(_f32), _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "lt_op_views_guided_gather": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, C.POINTER(_f32), _i32, _i32, _i32, _i32, _vp]),
     "lt_op_sde_step": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_f32), _i64, _i32, _vp]),
     "lt_op_rk_stage": (_i32, [_vp, C.POINTER(_vp), C.POINTER(_f32), _i32, _f32, _vp, _i64, _i32, _vp]),

@@ -214,7 +214,9 @@ struct lt_engine {
     // (tw.n = 0: none; it travels as a kernel argument), the engine's copy of the window weights (tw_has_weight false: all ones, not read) and
     // the per-pixel weight sums, and the window rows going into and coming out of the model.  The four buffers are allocated by the first
     // lt_set_windows at their largest size - weights: one window of max_tokens tokens; sums: max_batch / 2 such windows; rows: max_batch such
-    // samples - and kept for the engine's life (a graph the caller recorded around lt_forward_tiled holds the pointers)
+    // samples - and kept for the engine's life (a graph the caller recorded around lt_forward_tiled holds the pointers).  The composed calls
+    // (lt_forward_compose / lt_sample_ode_compose) keep their (K + 1) B' <= max_batch replicated rows and model outputs in tw_in /
+    // tw_out, which are exactly that size, and allocate the set the same way when no tiled call has
     WindowTable tw = {};
     bool tw_has_weight = false;
     float *tw_weight = nullptr, *tw_wsum = nullptr;

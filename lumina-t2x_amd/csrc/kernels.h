@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "../../include/lumina_dit.h"
 #include "common.h"
 
 struct GemmArgs {
@@ -458,6 +459,13 @@ int launch_windows_gather(const void* y, const WindowTable& t, void* out, int C,
 int launch_windows_cover(const WindowTable& t, const float* weight, float* wsum, int* bad, hipStream_t stream);
 int launch_windows_reduce(const void* f, const WindowTable& t, const float* weight, const float* wsum, void* out, int C, int dtype,
                           hipStream_t stream);
+// composed guidance (compose.hip; rounding points there): a state of B' rows, an evaluation of (K + 1) B' rows - K <= LT_COMPOSE_MAX prompt row
+// groups, then the base row group.  State dtype 0 f32, 1 bf16; w_host the K weights on the HOST (they travel as a kernel argument)
+//   replicate: out [(K+1) B', C, HW] = K + 1 exact copies of y [B', C, HW]
+//   guidance:  out [B', C, HW] = the chain of transport/guidance.py guided_compose on f [(K+1) B', C, HW], channels >= ch prompt 1's row
+struct ComposeWeights { float w[LT_COMPOSE_MAX]; };
+int launch_compose_replicate(const void* y, void* out, int K, int Bp, int C, int HW, int dtype, hipStream_t stream);
+int launch_compose_guidance(const void* f, void* out, const float* w_host, int K, int Bp, int C, int HW, int ch, int dtype, hipStream_t stream);
 // SDE sampling (sde.hip): one fused elementwise step on n elements, op = LT_SDE_OP_*, rec = the stage's 8-float record (host), state dtype
 // 0 f32, 1 bf16; operands an op does not read may be null.  out is fp32 for LT_SDE_OP_LAST_MEAN / LAST_TWEEDIE, the state dtype otherwise
 int launch_sde_step(int op, const void* x, const void* v, const void* w, const void* k1, const void* xp, void* out, void* out2, const float* rec,

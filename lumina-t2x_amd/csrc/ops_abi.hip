@@ -630,6 +630,14 @@ extern "C" int lt_op_windows_cover(const int32_t* offsets_host, int32_t n, int32
     if (window_table_build("lt_op_windows_cover", offsets_host, n, win_h, win_w, canvas_h, canvas_w, &t)) return 2;
     return launch_windows_cover(t, weight_dev, wsum_dev, bad_dev, (hipStream_t)stream);
 }
+// composed guidance (compose.hip): the weights are a HOST table here; the launchers check everything before anything is launched
+extern "C" int lt_op_compose_replicate(const void* y_dev, void* out_dev, int32_t K, int32_t Bp, int32_t C, int32_t HW, int32_t dtype, void* stream) {
+    return launch_compose_replicate(y_dev, out_dev, K, Bp, C, HW, dtype, (hipStream_t)stream);
+}
+extern "C" int lt_op_compose_guidance(const void* f_dev, void* out_dev, const float* w_host, int32_t K, int32_t Bp, int32_t C, int32_t HW,
+                                      int32_t cfg_channels, int32_t dtype, void* stream) {
+    return launch_compose_guidance(f_dev, out_dev, w_host, K, Bp, C, HW, cfg_channels, dtype, (hipStream_t)stream);
+}
 extern "C" int lt_op_views_guided_gather(const void* y_dev, const void* guidance_dev, const void* noise_dev, const int32_t* perm_dev,
                                          const float* vsign_dev, const float* isign_dev, const void* f0_dev, void* out_dev, float half_dt,
                                          const float* coef_host, int32_t V, int32_t C, int32_t HW, int32_t dtype, void* stream) {

@@ -196,6 +196,9 @@ struct GridCall {
     const lt_step_args* a; hipStream_t s; long long n; const PackedCall* pc;
     int method = 0; const float* coef = nullptr; int corrector = 0;
     bool tiled = false;  // lt_sample_ode_tiled: the state is the canvas, an evaluation is e->tw's windows gathered, evaluated and fused
+    // lt_sample_ode_compose (compose_K > 0): the state has a->batch / (K + 1) rows, an evaluation is the state replicated under the K + 1 prompts,
+    // evaluated and composed with row `call` of the [ncalls][K] weight table
+    int compose_K = 0; const float* compose_w = nullptr;
 };
 struct MaskedBlend { const void *mask, *x1, *noise; };
 
@@ -249,8 +252,15 @@ int ode_fixed_grid(lt_engine* e, const GridCall& c, const GuidancePlan& plan, co
     Trajectory tr{e, a, c.use_cfg, s, (size_t)n * (bf ? 2 : 4), c.pc, plan, ncalls};
     if (tr.start(c.z, c.traj, true)) return 1;
     const int dt_code = bf ? 1 : 0;
-    // one velocity of the state: the model on it, or (tiled) on its windows, whose predictions are fused into `out`
+    // one velocity of the state: the model on it, or (tiled) on its windows, whose predictions are fused into `out`, or (composed,
+    // DESIGN 7s) on its copies under K + 1 prompts, whose predictions are composed into `out`
     auto eval = [&](const void* y, int call, void* out) -> int {
+        if (c.compose_K) {  // 
+            const int K = c.compose_K, Bp = B / (K + 1), C = e->cfg.in_channels, HW = a->latent_h * a->latent_w;
+            if (launch_compose_replicate(y, e->tw_in, K, Bp, C, HW, dt_code, s)) return 1;
+            if (tr.eval(e->tw_in, call, e->tw_out)) return 1;
+            return launch_compose_guidance(e->tw_out, out, c.compose_w + (size_t)call * K, K, Bp, C, HW, a->cfg_channels, dt_code, s);
+        }
         if (!c.tiled) return tr.eval(y, call, out);
         if (launch_windows_gather(y, e->tw, e->tw_in, e->cfg.in_channels, dt_code, s)) return 1;
         if (tr.eval(e->tw_in, call, e->tw_out)) return 1;
@@ -1315,6 +1325,22 @@ void drop_windows(lt_engine* e) {
     e->tw.n = 0;
 }
 
+// the buffers of the tiled calls, allocated once at their largest size (engine.h); the composed calls use the two row buffers
+static int ensure_window_buffers(lt_engine* e, const char* who) {
+    if (e->tw_out) return 0;
+    const lt_config& c = e->cfg;
+    const size_t win_px = (size_t)c.max_tokens * c.patch_size * c.patch_size, rows = (size_t)c.max_batch * c.in_channels * win_px * sizeof(float);
+    if (hipMalloc((void**)&e->tw_weight, win_px * sizeof(float)) != hipSuccess ||
+        hipMalloc((void**)&e->tw_wsum, (size_t)((c.max_batch + 1) / 2) * win_px * sizeof(float)) != hipSuccess ||
+        hipMalloc((void**)&e->tw_bad, sizeof(int)) != hipSuccess || hipMalloc(&e->tw_in, rows) != hipSuccess ||
+        hipMalloc(&e->tw_out, rows) != hipSuccess) {
+        drop_windows(e);
+        lt_set_error("%s: out of device memory for the window buffers", who);
+        return 1;
+    }
+    return 0;
+}
+
 extern "C" int lt_set_windows(lt_engine* e, const int32_t* offsets_host, int32_t n, int32_t win_h, int32_t win_w, int32_t canvas_h, int32_t canvas_w,
                               const float* weight_dev, void* stream) {
     const char* who = "lt_set_windows";
@@ -1348,15 +1374,7 @@ extern "C" int lt_set_windows(lt_engine* e, const int32_t* offsets_host, int32_t
     // state buffers, lumina_dit.h)
     LT_REQUIRE((long long)canvas_h * canvas_w <= (long long)n * win_h * win_w, "%s: a canvas of %dx%d cannot be covered by %d windows of %dx%d", who,
                canvas_h, canvas_w, n, win_h, win_w);
-    if (!e->tw_out) {
-        const size_t win_px = (size_t)c.max_tokens * p * p, rows = (size_t)c.max_batch * c.in_channels * win_px * sizeof(float);
-        auto fail = [&]() { drop_windows(e); lt_set_error("%s: out of device memory for the window buffers", who); return 1; };
-        if (hipMalloc((void**)&e->tw_weight, win_px * sizeof(float)) != hipSuccess ||
-            hipMalloc((void**)&e->tw_wsum, (size_t)((c.max_batch + 1) / 2) * win_px * sizeof(float)) != hipSuccess ||
-            hipMalloc((void**)&e->tw_bad, sizeof(int)) != hipSuccess || hipMalloc(&e->tw_in, rows) != hipSuccess ||
-            hipMalloc(&e->tw_out, rows) != hipSuccess)
-            return fail();
-    }
+    if (ensure_window_buffers(e, who)) return 1;
     // the sums are formed in e->tw_out, which no call is using, from the caller's weights: a refused table leaves the one in force as it was
     int bad = -1;
     if (launch_windows_cover(t, weight_dev, (float*)e->tw_out, e->tw_bad, s)) return 1;
@@ -1412,5 +1430,63 @@ extern "C" int lt_sample_ode_tiled(lt_engine* e, const void* z_dev, void* traj_d
     GridCall c{z_dev, traj_dev, final_dev, tgrid_host, n_grid, 1, t_round, a, (hipStream_t)stream,
                (long long)e->cfg.in_channels * e->tw.canvas_h * e->tw.canvas_w, nullptr, method};
     c.tiled = true;
+    return ode_fixed_grid(e, c, {}, nullptr);
+}
+
+// ---- composed guidance: K weighted prompts and one base prompt per image (compose.hip; transport/guidance.py: guided_compose /
+// sample_cfg_compose are the definition).  a->batch = (K + 1) B' rows per evaluation around a state of B' rows; the evaluation is a plain
+// forward (LT_KIND_WHOLE, use_cfg = 0) under the graph key an lt_forward of that shape has, the two kernels run outside the graph -----------
+namespace {
+// what both composed entries refuse, by name, before anything is launched
+int check_compose_call(lt_engine* e, const char* who, const lt_step_args* a, const float* w_host, int K, int rows_of_weights) {
+    LT_REQUIRE(K >= 1 && K <= LT_COMPOSE_MAX, "%s: K = %d prompts (1 .. %d)", who, K, LT_COMPOSE_MAX);
+    LT_REQUIRE(a->batch >= K + 1 && a->batch % (K + 1) == 0, "%s: batch %d is not a positive multiple of K + 1 = %d (K prompt rows and the base row per "
+               "image)", who, a->batch, K + 1);
+    if (check_step_shape(e, who, a)) return 2;
+    for (int i = 0; i < rows_of_weights * K; ++i)
+        LT_REQUIRE(std::isfinite(w_host[i]), "%s: the weight of prompt %d at evaluation %d is not finite", who, i % K, i / K);
+    LT_REQUIRE(a->cfg_channels >= 1 && a->cfg_channels <= e->cfg.in_channels, "%s: cfg_channels %d outside 1..in_channels %d", who, a->cfg_channels,
+               e->cfg.in_channels);
+    LT_REQUIRE(e->reg_Y == 0, "%s: a regional prompt is prepared (lt_prepare_prompt_regional): its captions belong to one cond and one uncond row, "
+               "not to the K + 1 rows of a composition", who);
+    LT_REQUIRE(e->skip.empty() && e->perturb.empty(), "%s: a layer-skip or perturb set is not served", who);
+    LT_REQUIRE(e->prompt_B == a->batch, "%s: %s was called for batch %d, step has batch %d", who, e->v.labels ? "lt_prepare_labels" : "lt_prepare_prompt",
+               e->prompt_B, a->batch);
+    {  // the model's own refusal of this shape, before anything is copied (no partial result)
+        const int p = e->cfg.patch_size;
+        float unused;
+        if (softmax_scale_for(e, a, (a->latent_h / p) * (a->latent_w / p), &unused)) return 1;
+    }
+    return 0;
+}
+}  // namespace
+
+extern "C" int lt_forward_compose(lt_engine* e, const void* x_dev, const float* t_dev, void* out_dev, const float* w_host, int32_t K,
+                                  const lt_step_args* a, void* stream) {
+    const char* who = "lt_forward_compose";
+    LT_REQUIRE(e && x_dev && t_dev && out_dev && w_host && a, "%s: null argument", who);
+    hipStream_t s = (hipStream_t)stream;
+    LtOptScope opt_scope(&e->opts);
+    if (check_compose_call(e, who, a, w_host, K, 1)) return 2;
+    if (!e->tw_out && refuse_if_capturing(s, who)) return 2;  // (the first composed or tiled call of an engine allocates the row buffers)
+    if (ensure_window_buffers(e, who)) return 1;
+    const int Bp = a->batch / (K + 1), C = e->cfg.in_channels, HW = a->latent_h * a->latent_w, dt_code = a->io_dtype == LT_BF16 ? 1 : 0;
+    if (launch_compose_replicate(x_dev, e->tw_in, K, Bp, C, HW, dt_code, s)) return 1;
+    if (int rc = forward_graphed(e, e->tw_in, t_dev, e->tw_out, a, 0, s)) return rc;
+    return launch_compose_guidance(e->tw_out, out_dev, w_host, K, Bp, C, HW, a->cfg_channels, dt_code, s);
+}
+
+extern "C" int lt_sample_ode_compose(lt_engine* e, const void* z_dev, void* traj_dev, void* final_dev, const float* tgrid_host, int32_t n_grid,
+                                     int32_t method, const float* w_host, int32_t K, int32_t t_round, const lt_step_args* a, void* stream) {
+    const char* who = "lt_sample_ode_compose";
+    LT_REQUIRE(e && z_dev && tgrid_host && w_host && a, "%s: null argument", who);
+    if (refuse_if_capturing((hipStream_t)stream, who)) return 2;  // (the stage times travel through a host staging buffer that the next call rewrites)
+    LtOptScope opt_scope(&e->opts);
+    if (check_grid_method(who, n_grid, method, false, " (composed guidance serves the fixed-grid methods euler, midpoint, rk4)")) return 2;
+    const int stages = method == LT_ODE_EULER ? 1 : (method == LT_ODE_MIDPOINT ? 2 : 4);
+    if (check_compose_call(e, who, a, w_host, K, (n_grid - 1) * stages)) return 2;
+    if (ensure_window_buffers(e, who)) return 1;
+    GridCall c{z_dev, traj_dev, final_dev, tgrid_host, n_grid, 0, t_round, a, (hipStream_t)stream, dense_elems(e, a) / (K + 1), nullptr, method};
+    c.compose_K = K; c.compose_w = w_host;
     return ode_fixed_grid(e, c, {}, nullptr);
 }

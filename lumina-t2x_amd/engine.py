@@ -1060,6 +1060,53 @@ class DiTEngine:
                    self._stream())
         return out
 
+    # ---- composed guidance: K weighted prompts and one base prompt per image --------------------------------------
+    def _compose_args(self, x: torch.Tensor, K: int, what: str, scale_factor, scale_watershed, base_seqlen, proportional_attn, ntk_factor,
+                      cfg_channels) -> LtStepArgs:
+        _require_gpu(x, "x")
+        if x.dim() != 4:
+            raise LuminaLibError(f"{what} takes a state [B', C, H, W], got {tuple(x.shape)}")
+        a = self._step_args(x, 1.0, scale_factor, scale_watershed, base_seqlen, proportional_attn, cfg_channels=int(cfg_channels),
+                            ntk_factor=ntk_factor)
+        a.batch = (K + 1) * x.shape[0]
+        return a
+
+    def forward_compose(self, x: torch.Tensor, t: torch.Tensor, weights, *, scale_factor: float = 1.0, scale_watershed: float = 1.0,
+                        base_seqlen: Optional[int] = None, proportional_attn: bool = False, ntk_factor: float = 1.0,
+                        cfg_channels: int = 3) -> torch.Tensor:
+        """one composed evaluation (lt_forward_compose; ``transport.guidance.guided_compose`` around the plain forward is the definition): the
+        state ``x [B', C, H, W]`` under the K prompts and the base prompt as ONE plain forward of ``(K + 1) B'`` rows at ``t`` (that many stage
+        times), composed with the K ``weights``.  Needs the conditioning prepared for ``(K + 1) B'`` rows: prompt 1's, ..., prompt K's, the base."""
+        from .transport.guidance import check_compose
+        w = _refusing(check_compose, weights, rows=1, who="forward_compose")
+        K = w.shape[1]
+        a = self._compose_args(x, K, "forward_compose", scale_factor, scale_watershed, base_seqlen, proportional_attn, ntk_factor, cfg_channels)
+        x, t32, out = self._eval_io(x, t)
+        if t32.numel() != a.batch:
+            raise LuminaLibError(f"forward_compose: t has {t32.numel()} entries, {x.shape[0]} image(s) under K = {K} prompts are evaluated as "
+                                 f"{a.batch} rows")
+        self._call("lt_forward_compose", self._dev(x), self._dev(t32), self._dev(out), self._host(w), K, C.byref(a), self._stream())
+        return out
+
+    def sample_ode_compose(self, z: torch.Tensor, tgrid, table, method: str = "midpoint", *, scale_factor: float = 1.0, scale_watershed: float = 1.0,
+                           base_seqlen: Optional[int] = None, proportional_attn: bool = False, t_round_to_state_dtype: bool = True,
+                           return_trajectory: bool = True, ntk_factor: float = 1.0, cfg_channels: int = 3) -> torch.Tensor:
+        """the composed fixed-grid trajectory of ``z [B', C, H, W]`` in one call (lt_sample_ode_compose; ``transport.guidance.sample_cfg_compose``
+        is the definition): every stage is ``forward_compose`` with its row of ``table [(len(tgrid) - 1) * stages, K]``
+        (``transport.guidance.compose_table``), the steps are ``sample_ode``'s.  Returns ``[n_grid, B', C, H, W]`` or the last state."""
+        from .transport.guidance import check_compose
+        garr, n, code, ncalls = self._fixed_grid(
+            method, tgrid, f"sample_ode_compose: composed guidance is built for the fixed-grid methods {sorted(_lib.ODE_METHODS)}, not '{method}' "
+                           "(the multistep and adaptive solvers are not served)")
+        w = _refusing(check_compose, table, rows=max(ncalls, 1), who="sample_ode_compose")
+        K = w.shape[1]
+        a = self._compose_args(z, K, "sample_ode_compose", scale_factor, scale_watershed, base_seqlen, proportional_attn, ntk_factor, cfg_channels)
+        z = z.contiguous()
+        out, traj_ptr, fin_ptr = _traj_or_final(z, max(n, 1), z.shape, return_trajectory)
+        self._call("lt_sample_ode_compose", self._dev(z), traj_ptr, fin_ptr, garr, n, code, self._host(w), K, int(t_round_to_state_dtype),
+                   C.byref(a), self._stream())
+        return out
+
     def last_nfe(self) -> int:
         return int(self.lib.lt_last_nfe(self.handle))
 

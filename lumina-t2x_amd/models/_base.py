@@ -422,6 +422,93 @@ class EngineSamplers:
         eng, args, _ = self._tiled_engine("tiled sampling", x, windows, weights, kw)
         return eng.sample_ode_tiled(x, tgrid, method, t_round_to_state_dtype=t_round, **args)
 
+    # ---- composed guidance: K weighted prompts and one base prompt per image --------------------------------------
+    def _compose_engine(self, what, x, K, kw):
+        """the engine with the conditioning in ``kw`` prepared for the ``(K + 1) B'`` rows of a composed evaluation of ``x [B', C, H, W]`` - prompt
+        1's rows, ..., prompt K's, the base prompt's - and the step kwargs of the plain forward that evaluation is: the step flags of
+        ``forward_with_cfg`` in ``kw`` are left on the module as that call leaves them (``_leave_step_flags``), as FlowEdit does."""
+        if not isinstance(x, torch.Tensor):
+            raise _lib.LuminaLibError(f"{what}: a packed batch (a list of latents) is not served by composed guidance")
+        if x.dim() != 4:
+            raise _lib.LuminaLibError(f"{what} takes a state [B', C, H, W], got {tuple(x.shape)}")
+        rows = (K + 1) * x.shape[0]
+        for name in self._cond_names:
+            if name not in kw:
+                raise TypeError(f"{what} needs the conditioning {self._cond_names}")
+            if kw[name].shape[0] != rows:
+                raise _lib.LuminaLibError(f"{what}: {x.shape[0]} image(s) under K = {K} prompts need (K + 1) B' = {rows} rows of {name} (prompt 1's, "
+                                          f"..., prompt K's, the base prompt's), got {kw[name].shape[0]}")
+        kw.pop("cfg_scale", None)  # the weights are the scales
+        override = self._leave_step_flags(kw)
+        shape = torch.empty((rows,) + tuple(x.shape[1:]), dtype=x.dtype, device=x.device)  # the evaluation's shape
+        eng, args = self._engine_sampler_args(shape, False, kw)
+        args.pop("cfg_scale", None)
+        att = self.layers[0].attention if hasattr(self, "layers") and len(self.layers) and hasattr(self.layers[0], "attention") else None
+        if att is not None and hasattr(att, "proportional_attn") and "proportional_attn" not in args:  # what this family's plain forward passes on
+            args.update(proportional_attn=bool(att.proportional_attn), base_seqlen=att.base_seqlen)
+        args.update(override)
+        return eng, args
+
+    @torch.no_grad()
+    def forward_with_compose(self, x, t, *cond, weights, cfg_channels: int = 3, **step_kw):
+        """One composed evaluation of ``x [B', C, H, W]`` in ONE engine call (lt_forward_compose; ``transport.guidance.guided_compose``
+        on this model's plain ``forward`` of the replicated rows is the definition): ``g = u + sum_k w_k (c_k - u)`` on the guided channels.
+        ``cond``: the family's conditioning (``cap_feats, cap_mask`` or ``y``) for ``(K + 1) B'`` rows - prompt 1's rows, ..., prompt K's, then
+        the base (negative / empty) prompt's; ``weights``: the K weights (a negative one negates its prompt); ``step_kw``: the step flags of
+        ``forward_with_cfg``.  ``t``: one stage time, or ``(K + 1) B'``.  A state that is not on a ROCm device runs the host definition."""
+        from ..transport import guidance as G
+        if len(cond) > len(self._cond_names):
+            raise TypeError(f"forward_with_compose takes the conditioning {self._cond_names}, got {len(cond)} positional arguments")
+        kw = dict(zip(self._cond_names, cond), **step_kw)
+        w = _refusing(G.check_compose, weights, rows=1, who="forward_with_compose")
+        K = w.shape[1]
+        if isinstance(x, torch.Tensor) and not x.is_cuda:
+            return self._compose_host(x, kw, K, lambda fn, c: G.guided_compose(
+                fn(x.repeat(K + 1, 1, 1, 1), torch.as_tensor(t, dtype=torch.float32).reshape(-1).expand((K + 1) * x.shape[0]), **c), w, cfg_channels))
+        eng, args = self._compose_engine("forward_with_compose", x, K, kw)
+        tv = torch.as_tensor(t, dtype=torch.float32, device=x.device).reshape(-1)
+        return eng.forward_compose(x, tv.expand((K + 1) * x.shape[0]) if tv.numel() == 1 else tv, w, cfg_channels=cfg_channels, **args)
+
+    @torch.no_grad()
+    def sample_ode_compose(self, z, tgrid, table, *cond, method: str = "midpoint", return_trajectory: bool = False, t_round: bool = True,
+                           cfg_channels: int = 3, **step_kw):
+        """The composed fixed-grid trajectory of ``z [B', C, H, W]`` in ONE engine call (lt_sample_ode_compose, DESIGN 7s;
+        ``transport.guidance.sample_cfg_compose`` around this model's plain ``forward`` is the definition): every stage evaluates the state
+        under the K prompts and the base prompt as one plain forward of ``(K + 1) B'`` rows and composes the predictions with its row of
+        ``table [(len(tgrid) - 1) * stages, K]`` (``transport.guidance.compose_table``); euler / midpoint / rk4 step the ``B'`` rows.
+        Arguments as ``forward_with_compose``.  Returns the last state, or all ``len(tgrid)`` states."""
+        from ..transport import guidance as G
+        if len(cond) > len(self._cond_names):
+            raise TypeError(f"sample_ode_compose takes the conditioning {self._cond_names}, got {len(cond)} positional arguments")
+        kw = dict(zip(self._cond_names, cond), **step_kw)
+        try:
+            G.refuse_with_compose(method, packed=True if not isinstance(z, torch.Tensor) else None)
+        except NotImplementedError as exc:
+            raise _lib.LuminaLibError(f"sample_ode_compose: {exc}") from None
+        w = _refusing(G.check_compose, table, who="sample_ode_compose")
+        K = w.shape[1]
+        if not z.is_cuda:
+            out = self._compose_host(z, kw, K, lambda fn, c: G.sample_cfg_compose(fn, z, tgrid, w, K, method, cfg_channels=cfg_channels, **c))
+            return out if return_trajectory else out[-1]
+        eng, args = self._compose_engine("sample_ode_compose", z, K, kw)
+        return eng.sample_ode_compose(z, tgrid, w, method, t_round_to_state_dtype=t_round, return_trajectory=return_trajectory,
+                                      cfg_channels=cfg_channels, **args)
+
+    def _compose_host(self, x, kw, K, run):
+        """the host definition around this model's plain ``forward``: the conditioning alone reaches it (a plain forward takes no step flags)"""
+        kw.pop("cfg_scale", None)
+        cond_kw = {k: kw.pop(k) for k in self._cond_names if k in kw}
+        if kw:
+            raise TypeError(f"composed guidance: {sorted(kw)} reach the engine alone; the plain forward of the host loop takes none")
+        return run(self.forward, cond_kw)
+
+    def _engine_sample_ode_compose(self, x, tgrid, method, t_round, table, kw):
+        """kwargs of forward_with_cfg / forward -> lt_sample_ode_compose; all states"""
+        from ..transport.guidance import check_compose
+        w = _refusing(check_compose, table)
+        eng, args = self._compose_engine("composed guidance", x, w.shape[1], kw)
+        return eng.sample_ode_compose(x, tgrid, w, method, t_round_to_state_dtype=t_round, **args)
+
     def _engine_sample_ode_adaptive(self, x, tgrid, method, use_cfg, t_round, kw, *, rtol, atol, first_step=None, max_steps=2 ** 31 - 1):
         """kwargs of forward_with_cfg / forward -> lt_sample_ode_adaptive; returns (states [len(tgrid), *x.shape], stats dict)"""
         eng, args = self._engine_sampler_args(x, use_cfg, kw)

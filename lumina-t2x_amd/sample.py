@@ -143,6 +143,31 @@ def tile_windows(args, canvas_hw, patch_size: int = 2):
     return (offsets, win), window_weights(win[0], win[1], getattr(args, "tile_weights", "uniform") or "uniform")
 
 
+def compose_plan(args, tgrid):
+    """``--compose_prompts P1 .. PK --compose_weights W1 .. WK [--compose_interval K LO HI]...`` -> ``(prompts, table)`` with the weight table
+    of ``transport.guidance.compose_table`` (prompt K, counted from 1, weighs 0 outside its interval); ``None`` without ``--compose_prompts``"""
+    prompts = getattr(args, "compose_prompts", None)
+    weights, intervals = getattr(args, "compose_weights", None), getattr(args, "compose_interval", None) or []
+    if not prompts:
+        if weights or intervals:
+            raise SystemExit("--compose_weights / --compose_interval belong to --compose_prompts")
+        return None
+    from .transport import guidance
+    if not weights or len(weights) != len(prompts):
+        raise SystemExit(f"--compose_prompts names {len(prompts)} prompts: --compose_weights needs as many weights, got {len(weights or [])}")
+    if len(prompts) > guidance.COMPOSE_MAX:
+        raise SystemExit(f"--compose_prompts: {len(prompts)} prompts, at most {guidance.COMPOSE_MAX} are served")
+    per = [None] * len(prompts)
+    for k, lo, hi in intervals:
+        if k != int(k) or not 1 <= int(k) <= len(prompts):
+            raise SystemExit(f"--compose_interval {k:g} {lo:g} {hi:g}: the prompt is counted from 1 to {len(prompts)}")
+        per[int(k) - 1] = (lo, hi)
+    try:
+        return list(prompts), guidance.compose_table(tgrid, args.sampling_method, [float(w) for w in weights], per)
+    except ValueError as exc:
+        raise SystemExit(f"--compose_prompts: {exc}") from None
+
+
 def run(args, *, encode_fn=None, cap_feat_dim=None, decode_fn=None, model=None) -> List[dict]:
     """Sample every (resolution, caption) pair of this rank's shard.  ``encode_fn`` / ``decode_fn`` / ``model`` can be injected
     (tests, or a caller that already holds the encoder / VAE); otherwise they are built from the command-line paths."""
@@ -203,7 +228,15 @@ def run(args, *, encode_fn=None, cap_feat_dim=None, decode_fn=None, model=None) 
         slg = None if pag is not None else guidance_slg(args, sample_fn.__self__.t)
         tea = step_cache(args)
         proj = guidance_project(args)
-        if tile:  # MultiDiffusion: ONE canvas latent, every stage the model on overlapping windows of it, their predictions fused
+        comp = compose_plan(args, sample_fn.__self__.t)
+        if comp:  # composed guidance: the K prompts of --compose_prompts stand in for the caption, the negative prompt is the base row
+            if tile or table is not None or rule or reuse is not None or pag is not None or slg is not None or tea or proj:
+                raise SystemExit("--compose_prompts is not served together with --tile, --cfg_interval / --cfg_schedule, --cfg_rescale / "
+                                 "--cfg_norm_limit, --cfg_reuse*, --slg_*, --pag_*, --teacache, --apg_* or --cfg_zero_star")
+            feats, cmask = encode_fn(comp[0] + [""])
+            ckw = dict(kw, cap_feats=feats, cap_mask=cmask.to(feats.device))
+            latent = sample_fn(z[:1], model.forward_with_cfg, compose=comp[1], **ckw)[-1][:1]
+        elif tile:  # MultiDiffusion: ONE canvas latent, every stage the model on overlapping windows of it, their predictions fused
             if table is not None or rule or reuse is not None or pag is not None or slg is not None or tea or proj:
                 raise SystemExit("--tile is not served together with --cfg_interval / --cfg_schedule, --cfg_rescale / --cfg_norm_limit, --cfg_reuse*, "
                                  "--slg_*, --pag_*, --teacache, --apg_* or --cfg_zero_star")
@@ -446,6 +479,14 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--tile_stride", type=int, nargs=2, default=None, metavar=("SH", "SW"), help="window stride in pixels (default: half the tile)")
     p.add_argument("--tile_weights", type=str, default="uniform", choices=["uniform", "cosine"],
                    help="weight of a window's pixels in the average: uniform, or a cosine bump that fades towards the window's border")
+    p.add_argument("--compose_prompts", type=str, nargs="+", default=None, metavar="P",
+                   help="composed guidance: every image is guided by these K <= 7 prompts at once, g = u + sum_k W_k (c_k - u), in place of the "
+                        "caption file's line (which still names the output); the negative (empty) prompt is the base row u; one engine call "
+                        "per image")
+    p.add_argument("--compose_weights", type=float, nargs="+", default=None, metavar="W",
+                   help="... the weight of each prompt, as many as prompts; a negative weight pushes away from its prompt")
+    p.add_argument("--compose_interval", type=float, nargs=3, action="append", default=None, metavar=("K", "LO", "HI"),
+                   help="... prompt K (counted from 1) weighs 0 at the stages whose time is not in [LO, HI) (may be given once per prompt)")
     p.add_argument("--num_sampling_steps", type=int, default=250)
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--ckpt", type=str, required=True)

@@ -39,14 +39,19 @@ identity, so every query's output is its own value row - and, if wanted, another
 
 Projected guidance replaces the guided expression by one built on inner products of the two predictions - APG's
 momentum / norm-clip / projection, CFG-Zero*'s rescaled unconditional row and zero-init: ``guided_project`` is the form, ``sample_cfg_project`` the
-loop ``lt_sample_ode_cfg_project`` is held to, ``check_project`` / ``refuse_with_project`` refuse what the engine refuses."""
+loop ``lt_sample_ode_cfg_project`` is held to, ``check_project`` / ``refuse_with_project`` refuse what the engine refuses.
+
+Composed guidance (Composable Diffusion, Liu et al. 2022) puts K weighted prompts and one base prompt on one image,
+``g = u + sum_k w_k (c_k - u)``: the state has ``B'`` rows - there is no second half to carry - and every stage is ONE plain ``forward`` of
+``(K + 1) B'`` rows.  ``guided_compose`` is the chain of roundings, ``sample_cfg_compose`` the loop ``lt_sample_ode_compose`` is held to,
+``compose_table`` builds the per-stage weights and ``check_compose`` / ``refuse_with_compose`` refuse what the engine refuses."""
 from __future__ import annotations
 
 import math
 
 import torch as th
 
-from .integrators import FIXED_GRID_METHODS, _call
+from .integrators import FIXED_GRID_METHODS, _call, fixed_grid_odeint
 from .multistep import MULTISTEP_METHODS
 
 _STAGES = {"euler": 1, "midpoint": 2, "rk4": 4}
@@ -1085,3 +1090,152 @@ def sample_project_front(x, model, tgrid, method, table, model_kwargs, *, apg=No
     if owner is None or getattr(model, "__name__", "") != "forward_with_cfg" or not hasattr(owner, "forward"):
         raise TypeError("projected guidance needs the bound forward_with_cfg of a model that also has forward (every stage calls it)")
     return sample_cfg_project(owner, x, tgrid, table, method, apg=apg, zero_star=zero_star, zero_init=zero_init, t_round=t_round, **model_kwargs)
+
+
+# ---- composed guidance -----------------------------------------------------------------------------------------------------
+COMPOSE_MAX = 7  # prompts beside the base prompt (LT_COMPOSE_MAX); the engine's row budget is (K + 1) B' <= max_batch <= 8
+
+
+def check_compose(weights, K=None, rows=None):
+    """``weights`` as an fp32 CPU tensor ``[rows, K]`` of finite entries (a 1-D table is one row); ``K`` / ``rows``: what it must have"""
+    w = weights if isinstance(weights, th.Tensor) else th.tensor(weights, dtype=th.float32)
+    w = w.detach().to("cpu", th.float32)
+    if w.dim() == 1:
+        w = w[None]
+    if w.dim() != 2 or w.shape[0] < 1:
+        raise ValueError(f"composed guidance: the weights must be [K] or [stages, K], got {tuple(w.shape)}")
+    if not 1 <= w.shape[1] <= COMPOSE_MAX:
+        raise ValueError(f"composed guidance: K = {w.shape[1]} prompts (1 .. {COMPOSE_MAX})")
+    if K is not None and w.shape[1] != K:
+        raise ValueError(f"composed guidance: the weights are for {w.shape[1]} prompts, the call has K = {K}")
+    if rows is not None and w.shape[0] != rows:
+        raise ValueError(f"composed guidance: the weight table has {w.shape[0]} rows, the grid has {rows} stages")
+    if not bool(th.isfinite(w).all()):
+        raise ValueError("composed guidance: a weight is not finite")
+    return w.contiguous()
+
+
+def compose_table(tgrid, method, weights, intervals=None):
+    """The fp32 weight table ``[(len(tgrid) - 1) * stages, K]`` of a composed trajectory: stage ``k`` of interval ``i`` uses row
+    ``i * stages + k``.  ``weights``: the K weights.  ``intervals[k] = (lo, hi)`` (``None``: everywhere) sets prompt ``k``'s weight to 0 where
+    not ``lo <= t_stage < hi`` - ``cfg_table``'s test, on the UNROUNDED fp32 stage time."""
+    _check_method(method)
+    w = check_compose(weights)
+    if w.shape[0] != 1:
+        raise ValueError("compose_table takes the K weights of the prompts, one each")
+    K = w.shape[1]
+    ts = stage_times(tgrid, method, th.float32, False).tolist()
+    intervals = [None] * K if intervals is None else list(intervals)
+    if len(intervals) != K:
+        raise ValueError(f"compose_table: {len(intervals)} intervals for K = {K} prompts (one each; None: everywhere)")
+    table = w.repeat(len(ts), 1)
+    for k, iv in enumerate(intervals):
+        if iv is None:
+            continue
+        lo, hi = float(iv[0]), float(iv[1])
+        if not lo <= hi:
+            raise ValueError(f"guidance interval [{lo}, {hi}) of prompt {k} is empty or not ordered")
+        for i, t in enumerate(ts):
+            if not lo <= t < hi:
+                table[i, k] = 0.0
+    return table.contiguous()
+
+
+def guided_compose(outs, weights, cfg_channels=3):
+    """The composed output ``[B', C, H, W]`` of one plain ``forward`` of ``(K + 1) B'`` rows ``outs``: rows ``k B' + b`` belong to prompt ``k`` of
+    image ``b`` (``k = 0 .. K-1``), rows ``K B' + b`` to the base prompt.  On channels ``< cfg_channels``, with R = round to bf16 - the model's
+    output dtype, whatever the dtype ``outs`` arrives in - and every difference, product and sum one fp32 operation that rounds on its own::
+
+        acc = R(w_1 * R(c_1 - u))
+        acc = R(acc + R(w_k * R(c_k - u)))    for k = 2 .. K, in this order
+        g   = R(u + acc)
+
+    (torch's bf16 elementwise kernels compute in fp32 and round once; a Python float weight enters as its fp32 value).  At ``K = 1`` this is
+    ``forward_with_cfg``'s ``u + w * (c - u)``.  Channels at or past ``cfg_channels`` are prompt 1's rows, copied."""
+    w = check_compose(weights)
+    if w.shape[0] != 1:
+        raise ValueError("guided_compose takes the K weights of ONE evaluation")
+    K = w.shape[1]
+    if outs.dim() != 4 or outs.shape[0] % (K + 1):
+        raise ValueError(f"guided_compose: {outs.shape[0]} rows are not a multiple of K + 1 = {K + 1} (K prompt rows and the base row per image)")
+    C = outs.shape[1]
+    if not 1 <= int(cfg_channels) <= C:
+        raise ValueError(f"composed guidance: cfg_channels {cfg_channels} outside 1..{C}")
+    ch = int(cfg_channels)
+    rows = outs.to(th.bfloat16).chunk(K + 1)
+    u = rows[K][:, :ch]
+    wk = w[0].tolist()
+    acc = wk[0] * (rows[0][:, :ch] - u)
+    for k in range(1, K):
+        acc = acc + wk[k] * (rows[k][:, :ch] - u)
+    g = u + acc
+    return th.cat([g, rows[0][:, ch:]], 1).to(outs.dtype)
+
+
+def sample_cfg_compose(model_fn, z, tgrid, table, K, method="euler", *, cfg_channels=3, **cond_kw):
+    """The composed trajectory on the host: all ``len(tgrid)`` states ``[len(tgrid), B', C, H, W]``.  The stepping is ``fixed_grid_odeint`` itself
+    - the stage times, the dt handling and every rounding point of the loop ``lt_sample_ode`` is pinned to - and its velocity is: the ``B'`` state
+    rows replicated ``K + 1`` times, ONE ``model_fn(rows, t fp32 [(K + 1) B'], **cond_kw)`` (a plain forward whose conditioning carries the rows
+    of ``guided_compose``'s layout), ``guided_compose`` with row ``i * stages + k`` of ``table`` at stage ``k`` of interval ``i``."""
+    stages = _check_method(method)
+    K = int(K)
+    t = _grid32(tgrid)
+    table = check_compose(table, K, (len(t) - 1) * stages)
+    if z.dim() != 4:
+        raise ValueError(f"composed guidance takes a state [B', C, H, W], got {tuple(z.shape)}")
+    rows = (K + 1) * z.shape[0]
+    for k, v in cond_kw.items():
+        if isinstance(v, th.Tensor) and v.dim() >= 1 and v.shape[0] != rows:
+            raise ValueError(f"composed guidance: conditioning '{k}' has {v.shape[0]} rows; {z.shape[0]} image(s) under K = {K} prompts need "
+                             f"(K + 1) B' = {rows} rows (prompt 1's, ..., prompt K's, the base prompt's)")
+    device = z.device
+    w = table.tolist()
+    call = [0]
+
+    def _fn(tt, y):
+        wk = w[call[0]]
+        call[0] += 1
+        tvec = th.ones(rows).to(device) * tt  # fp32 [(K + 1) B'] (reference integrators.py:108)
+        return guided_compose(model_fn(y.repeat(K + 1, 1, 1, 1), tvec, **cond_kw), wk, cfg_channels)
+
+    out = fixed_grid_odeint(_fn, z, t.to(device), method=method)
+    assert call[0] == (len(t) - 1) * stages
+    return out
+
+
+# what the composed call does not combine with, refused by name in the Python wrappers (the C entries take none of them)
+def refuse_with_compose(method, **others):
+    """``others``: name -> value of the features a call was given beside ``compose``; any that is set is refused by name"""
+    names = {"cfg_table": "a guidance table (cfg_table)", "rule": "a rescale / norm limit (cfg_rescale, cfg_norm_limit)",
+             "cfg_reuse": "guidance reuse (cfg_reuse)", "slg": "skip-layer guidance (slg_table)", "pag": "perturbed-attention guidance (pag_table)",
+             "project": "projected guidance (cfg_apg, cfg_zero_star)", "teacache": "step caching (teacache)", "mask": "an inpainting mask",
+             "windows": "tiled sampling (windows)", "packed": "a packed batch (a list of latents)"}
+    for key, v in others.items():
+        if v is not None and v is not False:
+            raise NotImplementedError(f"composed guidance (compose) and {names.get(key, key)} are not served together")
+    if method not in FIXED_GRID_METHODS:
+        raise NotImplementedError(f"composed guidance (compose) is built for the fixed-grid methods {', '.join(FIXED_GRID_METHODS)}, not '{method}' "
+                                  "(the multistep and adaptive solvers are not served)")
+
+
+def sample_compose_front(x, model, tgrid, method, model_kwargs, table, *, t_round=True, use_engine=True, **others):
+    """``sample(..., compose=table)`` of both ODE front ends: the refusals by name, then ONE ``lt_sample_ode_compose`` call for an engine-backed
+    model on a ROCm state, the host loop ``sample_cfg_compose`` around the plain ``forward`` otherwise.  ``x [B', C, H, W]``; ``table``
+    ``[stages, K]`` (``compose_table``); the conditioning in ``model_kwargs`` carries ``(K + 1) B'`` rows.  ``model``: the bound ``forward`` or
+    ``forward_with_cfg`` of the model (the step flags of the latter reach the engine; ``cfg_scale`` is ignored: the table holds the weights)."""
+    from .integrators import _engine_target
+    refuse_with_compose(method, packed=True if isinstance(x, (list, tuple)) else None, **others)
+    table = check_compose(table)
+    K = table.shape[1]
+    kw = dict(model_kwargs)
+    kw.pop("cfg_scale", None)
+    target = _engine_target(model)
+    if target is not None and x.is_cuda and use_engine and hasattr(target[0], "_engine_sample_ode_compose"):
+        return target[0]._engine_sample_ode_compose(x, tgrid, method, t_round, table, kw)
+    owner = getattr(model, "__self__", None)
+    fn = owner.forward if owner is not None and getattr(model, "__name__", "") == "forward_with_cfg" and hasattr(owner, "forward") else model
+    rows = (K + 1) * x.shape[0]
+    cond = {k: v for k, v in kw.items() if isinstance(v, th.Tensor) and v.dim() >= 1 and v.shape[0] == rows}
+    if len(cond) != len(kw):
+        raise TypeError(f"composed guidance: the host loop's plain forward takes the conditioning of {rows} rows alone, not {sorted(set(kw) - set(cond))}")
+    return sample_cfg_compose(fn, x, tgrid, table, K, method, **cond)

@@ -398,7 +398,17 @@ class ode:
 
     def sample(self, x, model, cfg_table=None, cfg_rescale=0.0, cfg_norm_limit=math.inf, cfg_reuse=None, slg_table=None, slg_layers=(),
                teacache=None, teacache_coefficients=None, pag_table=None, pag_layers=(), cfg_apg=None, cfg_zero_star=False, cfg_zero_init=0,
-               windows=None, window_weights=None, **model_kwargs):
+               windows=None, window_weights=None, compose=None, **model_kwargs):
+        if compose is not None:  # composed guidance (transport/guidance.py): its refusals come first, by name
+            from .guidance import sample_compose_front
+            if isinstance(x, tuple) or not getattr(self.drift, "is_plain_velocity", False):
+                raise NotImplementedError("composed guidance is built for a tensor state with the plain velocity as drift")
+            return sample_compose_front(x, model, self.t, self.sampler_type, model_kwargs, compose, t_round=self.t_round_to_state_dtype,
+                                        use_engine=self.use_engine, cfg_table=cfg_table,
+                                        rule=None if (float(cfg_rescale) == 0.0 and float(cfg_norm_limit) == math.inf) else True,
+                                        cfg_reuse=cfg_reuse, slg=slg_table, pag=pag_table,
+                                        project=True if (cfg_apg is not None or cfg_zero_star or cfg_zero_init) else None, teacache=teacache,
+                                        windows=windows)
         if windows is not None:  # tiled (MultiDiffusion) sampling (transport/tiled.py): its refusals come first, by name
             from .tiled import sample_tiled_front
             if isinstance(x, tuple) or not getattr(self.drift, "is_plain_velocity", False):

@@ -15,6 +15,10 @@ is guidance reuse: one ``lt_sample_ode_cfg_reuse`` call or the host loop ``sampl
 ``windows=(offsets, (win_h, win_w))`` / ``window_weights=`` is tiled (MultiDiffusion) sampling (transport/tiled.py; not in the reference):
 ``x`` is ONE canvas latent, every stage evaluates its windows as one ``forward_with_cfg`` of 2 n rows and fuses their predictions - one
 ``lt_sample_ode_tiled`` call or the host loop ``sample_tiled``; refused by name together with any of the features above.
+``compose=table`` (``guidance.compose_table``: fp32 ``[stages, K]``) is composed guidance (transport/guidance.py; not in the reference):
+``x`` has ``B'`` rows and the conditioning ``(K + 1) B'`` - K weighted prompts, then the base prompt; every stage is one plain ``forward`` of those
+rows composed by ``guided_compose`` - one ``lt_sample_ode_compose`` call or the host loop ``sample_cfg_compose``; refused by name together with any
+of the features above.
 
 Not mirrored: ``use_sd3=True`` (drives a diffusers SD3Transformer2DModel, not a Lumina model - out of scope)."""
 from __future__ import annotations
@@ -126,9 +130,16 @@ class ODE:
 
     def sample(self, x, model, mask=None, x1=None, noise=None, cfg_table=None, cfg_rescale=0.0, cfg_norm_limit=math.inf, cfg_reuse=None,
                slg_table=None, slg_layers=(), teacache=None, teacache_coefficients=None, pag_table=None, pag_layers=(), cfg_apg=None,
-               cfg_zero_star=False, cfg_zero_init=0, windows=None, window_weights=None, **model_kwargs):
+               cfg_zero_star=False, cfg_zero_init=0, windows=None, window_weights=None, compose=None, **model_kwargs):
         if isinstance(x, tuple):
             raise NotImplementedError("tuple states are not part of the sampling path")
+        if compose is not None:  # composed guidance (transport/guidance.py): its refusals come first, by name
+            from .guidance import sample_compose_front
+            return sample_compose_front(x, model, self.t, self.sampler_type, model_kwargs, compose, t_round=self.t_round_to_state_dtype,
+                                        use_engine=self.use_engine, cfg_table=cfg_table,
+                                        rule=None if rule_is_off(cfg_rescale, cfg_norm_limit) else True, cfg_reuse=cfg_reuse, slg=slg_table,
+                                        pag=pag_table, project=True if (cfg_apg is not None or cfg_zero_star or cfg_zero_init) else None,
+                                        teacache=teacache, mask=next((m for m in (mask, x1, noise) if m is not None), None), windows=windows)
         if windows is not None:  # tiled (MultiDiffusion) sampling (transport/tiled.py): its refusals come first, by name
             from .tiled import sample_tiled_front
             return sample_tiled_front(x, model, self.t, self.sampler_type, model_kwargs, windows, window_weights,
