@@ -148,6 +148,14 @@ int lt_op_gated_residual_norm_ex(void* x, const void* y, const void* post_w, con
 int lt_op_gated_residual_norm_describe(int32_t post_mode, int32_t gate_mode, int32_t next_mode, int32_t d, int32_t has_next_w,
                                        int32_t has_next_scale, int32_t has_next_shift, int32_t scale_pre, int32_t has_ystat,
                                        int32_t ystat_slots, int32_t has_moe, char* out, int32_t cap);
+/* The projection half of lt_op_proj_gated_residual_norm (lumina_dit.h) on its own, as the engine launches O and W2 at large M: C[M, N] = A[M, K] W[N, K]^T,
+ * the plain dense GEMM, variant 0, no bias, whose epilogue also leaves every row's partial sums of squares in ystat_ws (float [M][*slots_out];
+ * GemmArgs::ystat) - so that a closing step lt_op_proj_gated_residual_norm does not have (a shift, next_mode 2, Flag-DiT's form without post-norm)
+ * can follow through lt_op_gated_residual_norm_ex with ystat / ystat_slots.  *slots_out = 2 x the column tiles of 288 or 256 the launch runs on;
+ * ystat_cap (floats per row of the workspace) >= that.  Refused by name where the problem does not take the persistent kernel's plain dense tiles
+ * (fewer than one 256-row tile per CU): nothing would fill ystat.  tests/forward_chain.py */
+int lt_op_gemm_ystat(const void* A, const void* W, void* C, void* ystat_ws, int32_t ystat_cap, int32_t M, int32_t N, int32_t K, int32_t* slots_out,
+                     void* stream);
 int lt_op_qk_norm_rope_ex(const void* src, int32_t ld_src, int32_t col0, const void* ln_w, const void* ln_b, float ln_eps, void* dst,
                           int32_t B, int32_t N, int32_t heads, int32_t hd, int32_t rope_mode, const void* cs_table, int32_t cs_len,
                           const void* t, float watershed, int32_t grid_w, const void* n_tok_b, const void* grid_w_b, float out_scale,

@@ -262,6 +262,7 @@ _SIGNATURES: Dict[str, tuple] = {
     "lt_op_rmsnorm_mod_ex": (_i32, [_vp, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _f32, _i32, _i32, _vp]),
     "lt_op_gated_residual_norm_ex": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _f32, _f32, _i32, _i32,
                                             _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "lt_op_gemm_ystat": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, C.POINTER(_i32), _vp]),
     "lt_op_gated_residual_norm_describe": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, C.c_char_p, _i32]),
     "lt_op_qk_norm_rope_ex": (_i32, [_vp, _i32, _i32, _vp, _vp, _f32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _f32, _i32, _vp, _vp, _f32,
                                      _vp, _vp, _i32, _i32, _vp]),

@@ -236,6 +236,23 @@ extern "C" int lt_op_proj_gated_residual_norm(const void* A, const void* W, void
     return launch_gated_residual_norm(r, (hipStream_t)stream);
 }
 
+// The projection of lt_op_proj_gated_residual_norm ALONE, as the engine's gemm() launches O and W2 at large M: the plain dense GEMM, variant 0,
+// with GemmArgs::ystat.  Every closing step the families have (shift, next_mode 2, Flag-DiT's gate form) can then follow through
+// lt_op_gated_residual_norm_ex; tests/forward_chain.py
+extern "C" int lt_op_gemm_ystat(const void* A, const void* W, void* C, void* ystat_ws, int32_t ystat_cap, int32_t M, int32_t N, int32_t K,
+                                int32_t* slots_out, void* stream) {
+    LT_REQUIRE(A && W && C && ystat_ws && slots_out, "lt_op_gemm_ystat: null pointer");
+    GemmArgs g;
+    g.A = (const u16*)A; g.W = (const u16*)W; g.C = (u16*)C; g.bias = nullptr; g.M = M; g.N = N; g.K = K; g.lda = K; g.ldw = K; g.ldc = N;
+    g.bias_dtype = -1;
+    const int ys = gemm_ystat_slots(g, 0);
+    LT_REQUIRE(ys > 0, "lt_op_gemm_ystat: this problem does not run on the persistent kernel's plain dense tiles (no ystat)");
+    LT_REQUIRE(ystat_cap >= ys, "lt_op_gemm_ystat: ystat workspace of %d floats per row, the launch fills %d", ystat_cap, ys);
+    g.ystat = (float*)ystat_ws; g.ystat_slots = ys;
+    *slots_out = ys;
+    return launch_gemm_bf16(g, 0, 0, (hipStream_t)stream);
+}
+
 extern "C" int lt_op_prep_mod(void* mod, int32_t B, int32_t ld_mod, int32_t L, int32_t chunks, int32_t d, uint32_t tanh_mask,
                               uint32_t scale_mask, int32_t final_scale_chunk, void* stream) {
     LT_REQUIRE(mod, "lt_op_prep_mod: null pointer");

@@ -27,6 +27,7 @@ Operand references inside `args`:
   ("col", name, off)       d columns of buffer `name` (the modulation matrix) starting at column off, one row per sample
   ("experts13", [(ref, ref), ...])  the experts' packed W1 | W3 operands stacked [E][2F][d]   ("swap2", ref)  the two words of every pair exchanged
   ("forced", layer, branch)         the case's forced routing table of that layer and branch ([rows][2] expert ids), None without one
+  ("flipbr", ref)          the two branches of a RoPE table exchanged   ("slots", name[, delta])  the slot count the launch that wrote ystat buffer `name` returned [+ delta]
 
 Mixture-of-experts families.  A routed feed-forward is: router logits -> top-2 + softmax weights (`sel`, `wts`) -> plan (`pos`, `src`,
 `te`: kernels.h MoeArgs) -> grouped W1 | W3 GEMM with SwiGLU that gathers its rows of h through `src` -> grouped W2 GEMM -> the closing grn
@@ -125,8 +126,18 @@ def build(case, paths=None):
     the default at head_dim 48 / <= 512 tokens, or projection + lt_op_qkv_post + lt_op_attention); {"route_fused": bool} - family moe: the
     space router runs inside the grn step that closes the time branch (the engine's option moe_route_fused, default on) or as a step of its own;
     {"time_plan_hoist": bool} - the engine's option moe_time_plan_hoist: the engine then writes every layer's time plan in one launch; the chain
-    plans layer by layer either way (the key is recorded for the tests, the steps do not change)."""
-    paths = {"small_fused": True, "route_fused": True, "time_plan_hoist": True, **(paths or {})}
+    plans layer by layer either way (the key is recorded for the tests, the steps do not change).
+    The large-row regime of the dense families (from one 256-row tile per CU on; csrc/engine.hip plan_block decides, the tests assert it):
+    {"qkv": "plain" | "fused" | "qk_vt"} - one plain projection, lt_op_gemm_qkv (Q | K plain, V as the V^T image only), or Q | K plain plus
+    lt_op_gemm_vt; {"raw_q": bool} (with "fused", head_dim 72) - lt_op_qkv_qstat (projection with the Q partial sums + the K pass) and the
+    attention that builds its queries itself (lt_op_attention_qraw_ex); {"post": "one" | "pair"} - lt_op_qkv_post, or lt_op_qk_norm_rope_pair
+    [+ lt_op_v_transpose behind a plain projection]; {"ystat": 0 | 1} - O and W2 through lt_op_gemm_ystat and every closing step through
+    lt_op_gated_residual_norm_ex with the partial sums that launch left.  The float64 meaning of every one of these is that of the default list."""
+    paths = {"small_fused": True, "route_fused": True, "time_plan_hoist": True, "qkv": "plain", "raw_q": False, "post": "one", "ystat": 0,
+             **(paths or {})}
+    assert paths["qkv"] in ("plain", "fused", "qk_vt") and paths["post"] in ("one", "pair") and (not paths["raw_q"] or paths["qkv"] == "fused")
+    assert paths["post"] == "pair" or paths["raw_q"] or paths["qkv"] == "plain", "lt_op_qkv_post transposes V itself: a plain projection only"
+    large = paths["qkv"] != "plain" or paths["post"] != "one"
     cfg, fam = case.cfg, case.fam
     d, L, H, Hkv, hd, F = cfg.dim, cfg.n_layers, cfg.n_heads, cfg.kv_heads, cfg.head_dim, cfg.ffn_hidden
     A, cap, dkv, ch = min(d, 1024), cfg.cap_feat_dim, cfg.kv_heads * cfg.head_dim, fam["chunks"]
@@ -192,13 +203,14 @@ def build(case, paths=None):
         final_scale_chunk=fam["final"].index("scale"))
     if fam["rope"] == "2d_watershed":   # nextdit_oracle.rope_table: t < watershed -> positions / scale_factor, else theta * scale_factor
         sf = case.scale_factor
-        add("rope", "rope_table", dst="rope", len=384, hd=hd, step=4, theta0=10000.0, lin0=sf, theta1=10000.0 * sf, lin1=1.0, lin_on_pos=0)
+        add("rope", "rope_table", dst="rope", len=384, hd=hd, step=4, theta0=10000.0, lin0=sf, theta1=10000.0 * sf, lin1=1.0, lin_on_pos=0,
+            **({"dst_t": "rope_t"} if paths["raw_q"] else {}))
         rope = dict(rope_mode=1, t=("in", "t"), watershed=case.scale_watershed, grid_w=case.Wp, cs_len=384)
     else:                               # rope_table_2d_general / rope_table_1d: theta * ntk_factor, positions / rope_scaling_factor, one table
         th, step = 10000.0 * case.ntk_factor, 2 if fam["rope"] == "1d" else 4
         ln = Npad if fam["rope"] == "1d" else 384
         add("rope", "rope_table", dst="rope", len=ln, hd=hd, step=step, theta0=th, lin0=case.scale_factor, theta1=th, lin1=case.scale_factor,
-            lin_on_pos=1)
+            lin_on_pos=1, **({"dst_t": "rope_t"} if paths["raw_q"] else {}))
         rope = dict(rope_mode=2 if fam["rope"] == "1d" else 1, t=None, watershed=0.0, grid_w=case.Wp, cs_len=ln)
     add("l0.prenorm", "rmsnorm_mod", x=buf("x"), w=lw(0, fam["pre"][0]), scale=col(0, fam["scale"][0]), shift=col(0, fam["shift"][0]), dst="h", B=B,
         N=N, d=d, eps=eps, ld_mod=ld_mod, scale_pre=1)
@@ -208,22 +220,52 @@ def build(case, paths=None):
         wqkv = ("cat", [w(p + "wq.weight"), w(p + "wk.weight"), w(p + "wv.weight")])
         ln = {k: (w(p + k.replace("_w", ".weight").replace("_b", ".bias")) if cfg.qk_norm else None)
               for k in ("q_norm_w", "q_norm_b", "k_norm_w", "k_norm_b")}
-        if not fam["text"] and paths["small_fused"]:
+        if not fam["text"] and paths["small_fused"] and not large:
             add(f"l{l}.qkv_attn", "qkv_attention_small", a=buf("h"), w=wqkv, qkv="qkv", M=M_, K=d, H=H, Hkv=Hkv, tokens=N, hd=hd, q_ln_w=ln["q_norm_w"],
                 q_ln_b=ln["q_norm_b"], k_ln_w=ln["k_norm_w"], k_ln_b=ln["k_norm_b"], table=buf("rope"), table_len=rope["cs_len"], grid_w=rope["grid_w"],
                 k_scale=fold(sm), dst="attn")
         else:
-            add(f"l{l}.qkv", "gemm", a=buf("h"), w=wqkv, bias=None, dst="qkv", M=M_, N=d + 2 * dkv, K=d, epi=0, splitk=True)
-            add(f"l{l}.qkv_post", "qkv_post", qkv=buf("qkv"), ld=d + 2 * dkv, q_col0=0, k_col0=d, v_col0=d + dkv, q_ln_w=ln["q_norm_w"],
-                q_ln_b=ln["q_norm_b"], k_ln_w=ln["k_norm_w"], k_ln_b=ln["k_norm_b"], ln_eps=1e-5, q="q", k="k", vt="vt", B=B, N=N, Npad=Npad, H=H,
-                Hkv=Hkv, hd=hd, table=buf("rope"), q_scale=1.0, k_scale=fold(sm), **rope)
-            if fam["text"]:
-                add(f"l{l}.attn", "attention_fused", q=buf("q"), k=buf("k"), vt=buf("vt"), tk=buf(f"ky{l}"), tvt=buf(f"vty{l}"), tbias=buf("tbias"),
-                    tgate=w(p + "gate"), dst="attn", B=B, H=H, Hkv=Hkv, N=N, Npad=Npad, T=T, Tpad=Tpad, hd=hd)
+            ld = d + dkv if paths["qkv"] == "qk_vt" else d + 2 * dkv       # the row stride of the buffer that holds Q | K [| V]
+            if paths["raw_q"]:     # the projection whose epilogue leaves the Q columns' partial sums, and the K pass that reduces them
+                add(f"l{l}.qkv", "qkv_qstat", a=buf("h"), w=wqkv, qkv="qkv", vt="vt", M=M_, N=d + 2 * dkv, K=d, split=d + dkv, tokens=N, hd=hd, q_cols=d,
+                    k_ln_w=ln["k_norm_w"], k_ln_b=ln["k_norm_b"], table=buf("rope"), t=rope["t"], watershed=rope["watershed"], grid_w=rope["grid_w"],
+                    k_scale=fold(sm), k="k", qmr="qmr")
+            elif paths["qkv"] == "fused":
+                add(f"l{l}.qkv", "gemm_qkv", a=buf("h"), w=wqkv, qkv="qkv", vt="vt", M=M_, N=d + 2 * dkv, K=d, split=d + dkv, tokens=N, hd=hd)
+            elif paths["qkv"] == "qk_vt":
+                add(f"l{l}.qkv", "gemm", a=buf("h"), w=("cat", [w(p + "wq.weight"), w(p + "wk.weight")]), bias=None, dst="qkv", M=M_, N=d + dkv, K=d, epi=0,
+                    splitk=True)
+                add(f"l{l}.v_vt", "gemm_vt", a=buf("h"), w=w(p + "wv.weight"), dst="vt", M=M_, N=dkv, K=d, tokens=N, hd=hd)
+            else:
+                add(f"l{l}.qkv", "gemm", a=buf("h"), w=wqkv, bias=None, dst="qkv", M=M_, N=d + 2 * dkv, K=d, epi=0, splitk=True)
+            if paths["raw_q"]:
+                pass
+            elif paths["post"] == "pair":
+                add(f"l{l}.qk_post", "qk_post_pair", qkv=buf("qkv"), ld=ld, q_col0=0, k_col0=d, q_ln_w=ln["q_norm_w"], q_ln_b=ln["q_norm_b"],
+                    k_ln_w=ln["k_norm_w"], k_ln_b=ln["k_norm_b"], ln_eps=1e-5, q="q", k="k", B=B, N=N, H=H, Hkv=Hkv, hd=hd, table=buf("rope"), q_scale=1.0,
+                    k_scale=fold(sm), **rope)
+                if paths["qkv"] == "plain":
+                    add(f"l{l}.v_t", "v_transpose", src=buf("qkv"), ld=ld, col0=d + dkv, dst="vt", B=B, N=N, Npad=Npad, kvh=Hkv, hd=hd)
+            else:
+                add(f"l{l}.qkv_post", "qkv_post", qkv=buf("qkv"), ld=d + 2 * dkv, q_col0=0, k_col0=d, v_col0=d + dkv, q_ln_w=ln["q_norm_w"],
+                    q_ln_b=ln["q_norm_b"], k_ln_w=ln["k_norm_w"], k_ln_b=ln["k_norm_b"], ln_eps=1e-5, q="q", k="k", vt="vt", B=B, N=N, Npad=Npad, H=H,
+                    Hkv=Hkv, hd=hd, table=buf("rope"), q_scale=1.0, k_scale=fold(sm), **rope)
+            text = dict(tk=buf(f"ky{l}"), tvt=buf(f"vty{l}"), tbias=buf("tbias"), tgate=w(p + "gate"), T=T, Tpad=Tpad) if fam["text"] else {}
+            if paths["raw_q"]:     # q_norm + RoPE in the attention's prologue, from the projection's rows; the KERNEL selects the table branch
+                none = dict(tk=None, tvt=None, tbias=None, tgate=None, T=0, Tpad=0)
+                add(f"l{l}.attn", "attention_qraw", qkv=buf("qkv"), ld=ld, q_col0=0, qmr=buf("qmr"), q_ln_w=ln["q_norm_w"], q_ln_b=ln["q_norm_b"],
+                    table=buf("rope"), table_t=buf("rope_t"), table_len=rope["cs_len"], grid_w=rope["grid_w"], t=rope["t"], watershed=rope["watershed"],
+                    k=buf("k"), vt=buf("vt"), dst="attn", B=B, H=H, Hkv=Hkv, N=N, Npad=Npad, hd=hd, **(text or none))
+            elif fam["text"]:
+                add(f"l{l}.attn", "attention_fused", q=buf("q"), k=buf("k"), vt=buf("vt"), dst="attn", B=B, H=H, Hkv=Hkv, N=N, Npad=Npad, hd=hd, **text)
             else:
                 add(f"l{l}.attn", "attention", q=buf("q"), k=buf("k"), vt=buf("vt"), dst="attn", B=B, H=H, Hkv=Hkv, N=N, Npad=Npad, hd=hd)
-        add(f"l{l}.wo", "gemm", a=buf("attn"), w=w(p + "wo.weight"), bias=None, dst="o", M=M_, N=d, K=d, epi=0, splitk=True)
-        add(f"l{l}.grn_attn", "grn", x="x", y=buf("o"), post_w=lw(l, fam["post"][0]), gate=col(l, fam["gate"][0]), post_mode=int(fam["post"][0] is not None),
+        ys = lambda br: dict(ystat=buf(f"ystat.l{l}.{br}"), ystat_slots=("slots", f"ystat.l{l}.{br}")) if paths["ystat"] else {}
+        if paths["ystat"]:
+            add(f"l{l}.wo", "gemm_ystat", a=buf("attn"), w=w(p + "wo.weight"), dst="o", ystat=f"ystat.l{l}.o", M=M_, N=d, K=d)
+        else:
+            add(f"l{l}.wo", "gemm", a=buf("attn"), w=w(p + "wo.weight"), bias=None, dst="o", M=M_, N=d, K=d, epi=0, splitk=True)
+        add(f"l{l}.grn_attn", "grn", **ys("o"), x="x", y=buf("o"), post_w=lw(l, fam["post"][0]), gate=col(l, fam["gate"][0]), post_mode=int(fam["post"][0] is not None),
             next_w=lw(l, fam["pre"][1]), next_scale=col(l, fam["scale"][1]), next_shift=col(l, fam["shift"][1]), next_mode=1, ld_mod=ld_mod, h="h", B=B, N=N,
             d=d, eps=eps, eps_next=1e-6)
         for i, (br, key) in enumerate(moe):
@@ -259,14 +301,17 @@ def build(case, paths=None):
         f = f"layers.{l}.feed_forward."
         if not moe:
             add(f"l{l}.w13", "gemm", a=buf("h"), w=("w13", w(f + "w1.weight"), w(f + "w3.weight")), bias=None, dst="u", M=M_, N=2 * F, K=d, epi=1, splitk=False)
-            add(f"l{l}.w2", "gemm", a=buf("u"), w=w(f + "w2.weight"), bias=None, dst="o", M=M_, N=d, K=F, epi=0, splitk=True)
+            if paths["ystat"]:
+                add(f"l{l}.w2", "gemm_ystat", a=buf("u"), w=w(f + "w2.weight"), dst="o", ystat=f"ystat.l{l}.f", M=M_, N=d, K=F)
+            else:
+                add(f"l{l}.w2", "gemm", a=buf("u"), w=w(f + "w2.weight"), bias=None, dst="o", M=M_, N=d, K=F, epi=0, splitk=True)
         if l + 1 < L:
             nxt = dict(next_w=lw(l + 1, fam["pre"][0]), next_scale=col(l + 1, fam["scale"][0]), next_shift=col(l + 1, fam["shift"][0]), next_mode=1)
         else:    # final layer: affine-free LayerNorm, eps 1e-6, * (1 + scale) [+ shift] (forward() :208-211, _final_shift_scale)
             fin = {nm: ("col", "mod", L * cd + i * d) for i, nm in enumerate(fam["final"])}
             nxt = dict(next_w=None, next_scale=fin["scale"], next_shift=fin.get("shift"), next_mode=2)
         add(f"l{l}.grn_ffn", "grn", x="x", post_w=lw(l, fam["post"][-1]), gate=col(l, fam["gate"][-1]), post_mode=int(fam["post"][-1] is not None),
-            ld_mod=ld_mod, h="h", B=B, N=N, d=d, eps=eps, eps_next=1e-6, **last, **nxt)
+            ld_mod=ld_mod, h="h", B=B, N=N, d=d, eps=eps, eps_next=1e-6, **last, **nxt, **({} if moe else ys("f")))
     nfinal = pp * cfg.out_channels
     add("final.linear", "gemm", a=buf("h"), w=w("final_layer.linear.weight"), bias=w("final_layer.linear.bias"), dst="frows", M=M_, N=nfinal, K=d, epi=0,
         splitk=False)
@@ -279,6 +324,7 @@ def run(backend, steps, hook=None):
     for s in steps:
         args = dict(s.args) if hook is None else hook(s.name, dict(s.args))
         if args is not None:
+            backend.step = s.name
             getattr(backend, "op_" + s.op)(**args)
     return backend.result()
 
@@ -410,6 +456,72 @@ def mutations(case, steps):
     return out
 
 
+def large_mutations(case, steps):
+    """[(name, hook)]: one-argument mutations of the steps the large-row regime ADDS (`mutations` covers the steps both lists share).  Names that
+    start with "gpu:" change an operand float64 does not model - the transposed table, the partial sums of a projection - so only the GPU
+    backend can see them; the "gpu:ystat" entries change words only where the closing step's launcher streams on ystat (Ops.grn_kernels says).
+    No entry that is LAUNCHED moves a column block or a buffer's extent: a mutated launch writes exactly where the unmutated one does.  The two
+    that would - the qstat width one head short of whole tiles, the V^T split column one head up - are "gpu:refused:" entries: lt_op_qkv_qstat
+    refuses them by name (LARGE_REFUSAL) before anything is launched, and the GPU test asserts that refusal."""
+    cfg, fam = case.cfg, case.fam
+    d, L, hd, H, dkv = cfg.dim, cfg.n_layers, cfg.head_dim, cfg.n_heads, cfg.kv_heads * cfg.head_dim
+    by = {s.name: s for s in steps}
+    out = []
+    two_tables = fam["rope"] == "2d_watershed" and case.scale_factor != 1.0
+    if two_tables:
+        t0 = float(case.inputs["t"][0])
+        flipped = 0.0 if t0 < case.scale_watershed else 1.0 + t0
+    plain_scale = fold(np.float32(math.sqrt(1.0 / hd)))
+    for l in range(L):
+        a = by[f"l{l}.attn"]
+        q = by[f"l{l}.qkv"]
+        if a.op == "attention_qraw":
+            kw, kb = q.args["k_ln_w"], q.args["k_ln_b"]
+            out.append((f"l{l}.prologue_q_norm_from_k", set_arg(a.name, q_ln_w=("cat", [kw] * (d // dkv)), q_ln_b=("cat", [kb] * (d // dkv)))))
+            out.append((f"l{l}.prologue_q_norm_bias_dropped", set_arg(a.name, q_ln_b=("zeros", d))))
+            out.append((f"l{l}.prologue_q_norm_from_other_layer", set_arg(a.name, q_ln_w=by[f"l{(l + 1) % L}.attn"].args["q_ln_w"])))
+            if case.Hp != case.Wp:
+                out.append((f"l{l}.prologue_grid_w_is_grid_h", set_arg(a.name, grid_w=case.Hp)))
+                out.append((f"l{l}.kpass_grid_w_is_grid_h", set_arg(q.name, grid_w=case.Hp)))
+            if two_tables:
+                out.append((f"l{l}.prologue_watershed_side", set_arg(a.name, watershed=flipped)))
+                out.append((f"l{l}.kpass_watershed_side", set_arg(q.name, watershed=flipped)))
+                out.append((f"gpu:l{l}.prologue_transposed_table_other_branch", set_arg(a.name, table_t=("flipbr", a.args["table_t"]))))
+                out.append((f"l{l}.prologue_table_other_branch", set_arg(a.name, table=("flipbr", a.args["table"]), table_t=("flipbr", a.args["table_t"]))))
+            out.append((f"gpu:refused:l{l}.qstat_width_a_head_short_of_whole_tiles", set_arg(q.name, q_cols=d - hd)))
+            out.append((f"gpu:refused:l{l}.vt_split_a_head_up", set_arg(q.name, split=d + dkv + hd)))
+            if fam["prop"] and case.proportional_attn:
+                out.append((f"l{l}.kpass_k_out_scale_without_proportional", set_arg(q.name, k_scale=plain_scale)))
+            if fam["text"]:
+                out.append((f"l{l}.prologue_text_gate_heads_exchanged", set_arg(a.name, tgate=("rows", a.args["tgate"], [1, 0] + list(range(2, H))))))
+                out.append((f"l{l}.prologue_text_keys_from_other_layer", set_arg(a.name, tk=by[f"l{(l + 1) % L}.attn"].args["tk"])))
+        p = by.get(f"l{l}.qk_post")
+        if p is not None:
+            if p.args["q_ln_b"] is not None:
+                out.append((f"l{l}.pair_q_norm_bias_dropped", set_arg(p.name, q_ln_b=("zeros", d))))
+                out.append((f"l{l}.pair_k_norm_from_other_layer", set_arg(p.name, k_ln_w=by[f"l{(l + 1) % L}.qk_post"].args["k_ln_w"])))
+            if fam["prop"] and case.proportional_attn:
+                out.append((f"l{l}.pair_k_scale_without_proportional", set_arg(p.name, k_scale=plain_scale)))
+            else:
+                # (the same product in float64: only the place of the one bf16 rounding the scale is folded into moves)
+                out.append((f"gpu:l{l}.pair_q_k_scales_exchanged", set_arg(p.name, q_scale=p.args["k_scale"], k_scale=p.args["q_scale"])))
+            if fam["rope"] != "1d" and case.Hp != case.Wp:
+                out.append((f"l{l}.pair_grid_w_is_grid_h", set_arg(p.name, grid_w=case.Hp)))
+            if two_tables:
+                out.append((f"l{l}.pair_watershed_side", set_arg(p.name, watershed=flipped)))
+        if f"l{l}.v_vt" in by:     # the V^T launch reading K's rows of the projection weight
+            out.append((f"l{l}.vt_from_k_weight", set_arg(f"l{l}.v_vt", w=("w", f"layers.{l}.attention.wk.weight"))))
+        if by[f"l{l}.wo"].op == "gemm_ystat":
+            ga, gf = by[f"l{l}.grn_attn"].args, by[f"l{l}.grn_ffn"].args
+            out.append((f"gpu:ystat:l{l}.grn_ffn:from_the_o_projection", set_arg(f"l{l}.grn_ffn", ystat=ga["ystat"])))
+            out.append((f"gpu:ystat:l{l}.grn_attn:from_the_w2_projection_of_the_layer_before" if l else f"gpu:ystat:l{l}.grn_attn:slots_less_a_tile",
+                        set_arg(f"l{l}.grn_attn", ystat=by[f"l{l - 1}.grn_ffn"].args["ystat"]) if l else
+                        set_arg(f"l{l}.grn_attn", ystat_slots=ga["ystat_slots"] + (-2,))))
+            out.append((f"gpu:ystat:l{l}.grn_ffn:slots_less_a_tile", set_arg(f"l{l}.grn_ffn", ystat_slots=gf["ystat_slots"] + (-2,))))
+    return out
+
+
+LARGE_REFUSAL = "lt_op_qkv_qstat: the problem does not take the fused QKV launch with whole Q tiles"
 REFUSED_BY_OPERATOR = "fused_router_in_attention_closing_step"     # the float64 chain runs it; lt_op_gated_residual_norm_ex refuses it by name
 
 
@@ -507,6 +619,10 @@ class Torch64:
             return self.ref(r[1]).reshape(-1, 2).flip(1)
         if kind == "forced":
             return torch.from_numpy(self.case.forced[r[1], r[2]]).long()
+        if kind == "flipbr":
+            return None if self.ref(r[1]) is None else self.ref(r[1]).flip(0)
+        if kind == "slots":
+            return None
         if kind == "in":
             v = self.case.inputs[r[1]]
             return v.double() if v.is_floating_point() else v
@@ -666,8 +782,10 @@ class Torch64:
             v = m[:, (L * chunks + final_scale_chunk) * d:(L * chunks + final_scale_chunk + 1) * d]
             v.copy_(1.0 + v)
 
-    def op_rope_table(self, dst, len, hd, step, theta0, lin0, theta1, lin1, lin_on_pos):
+    def op_rope_table(self, dst, len, hd, step, theta0, lin0, theta1, lin1, lin_on_pos, dst_t=None):
         self.b[dst] = M.ref_rope_table(len, hd, step, theta0, lin0, theta1, lin1, lin_on_pos)[0]
+        if dst_t:        # (the transposed copy the attention prologue reads: the same numbers, float64 reads `table` alone)
+            self.b[dst_t] = self.b[dst]
 
     def _branch(self, t, watershed):
         return 1 if t is None or not float(self.ref(t)[0]) < R.f32(watershed) else 0
@@ -685,6 +803,41 @@ class Torch64:
         self.b[q] = self._rope(self._ln(src[:, q_col0:q_col0 + H * hd], q_ln_w, q_ln_b, ln_eps), B, N, H, hd, table, rope_mode, br, grid_w, q_scale)
         self.b[k] = self._rope(self._ln(src[:, k_col0:k_col0 + Hkv * hd], k_ln_w, k_ln_b, ln_eps), B, N, Hkv, hd, table, rope_mode, br, grid_w, k_scale)
         self.b[vt] = src[:, v_col0:v_col0 + Hkv * hd].view(B, N, Hkv, hd).permute(0, 2, 1, 3)
+
+    # -- the large-row launches: the float64 meaning of the steps they replace (the qstat / ystat partial sums are not modelled) ----------------
+    def op_gemm_qkv(self, a, w, qkv, vt, M, N, K, split, tokens, hd):
+        self.op_gemm(a, w, None, qkv, M, N, K, 0, False)
+        self.b[vt] = self.b[qkv][:, split:].view(M // tokens, tokens, (N - split) // hd, hd).permute(0, 2, 1, 3)
+
+    def op_qkv_qstat(self, a, w, qkv, vt, M, N, K, split, tokens, hd, q_cols, k_ln_w, k_ln_b, table, t, watershed, grid_w, k_scale, k, qmr):
+        self.op_gemm_qkv(a, w, qkv, vt, M, N, K, split, tokens, hd)
+        B, kvh = M // tokens, (split - q_cols) // hd
+        self.b[k] = self._rope(self._ln(self.b[qkv][:, q_cols:split], k_ln_w, k_ln_b, 1e-5), B, tokens, kvh, hd, table, 1, self._branch(t, watershed),
+                               grid_w, k_scale)
+        self.b[qmr] = None
+
+    def op_gemm_vt(self, a, w, dst, M, N, K, tokens, hd):
+        self.b[dst] = (self.ref(a).view(M, K) @ self.ref(w).t()).view(M // tokens, tokens, N // hd, hd).permute(0, 2, 1, 3)
+
+    def op_qk_post_pair(self, qkv, ld, q_col0, k_col0, q_ln_w, q_ln_b, k_ln_w, k_ln_b, ln_eps, q, k, B, N, H, Hkv, hd, table, q_scale, k_scale, rope_mode,
+                        t, watershed, grid_w, cs_len):
+        src, br = self.ref(qkv).view(B * N, ld), self._branch(t, watershed)
+        self.b[q] = self._rope(self._ln(src[:, q_col0:q_col0 + H * hd], q_ln_w, q_ln_b, ln_eps), B, N, H, hd, table, rope_mode, br, grid_w, q_scale)
+        self.b[k] = self._rope(self._ln(src[:, k_col0:k_col0 + Hkv * hd], k_ln_w, k_ln_b, ln_eps), B, N, Hkv, hd, table, rope_mode, br, grid_w, k_scale)
+
+    def op_attention_qraw(self, qkv, ld, q_col0, qmr, q_ln_w, q_ln_b, table, table_t, table_len, grid_w, t, watershed, k, vt, tk, tvt, tbias, tgate,
+                          T, Tpad, dst, B, H, Hkv, N, Npad, hd):
+        src = self.ref(qkv).view(B * N, ld)
+        self.b["_q"] = self._rope(self._ln(src[:, q_col0:q_col0 + H * hd], q_ln_w, q_ln_b, 1e-5), B, N, H, hd, table, 1, self._branch(t, watershed),
+                                  grid_w, 1.0)
+        if tk is None:
+            self.op_attention(("buf", "_q"), k, vt, dst, B, H, Hkv, N, Npad, hd)
+        else:
+            self.op_attention_fused(("buf", "_q"), k, vt, tk, tvt, tbias, tgate, dst, B, H, Hkv, N, Npad, T, Tpad, hd)
+
+    def op_gemm_ystat(self, a, w, dst, ystat, M, N, K):
+        self.op_gemm(a, w, None, dst, M, N, K, 0, False)
+        self.b[ystat] = None
 
     @staticmethod
     def _attend(q, k, v, bias=None):
@@ -716,7 +869,7 @@ class Torch64:
         self.op_attention(("buf", "_q"), ("buf", "_k"), ("buf", "_v"), dst, B, H, Hkv, tokens, tokens, hd)
 
     def op_grn(self, x, y, post_w, gate, post_mode, next_w, next_scale, next_shift, next_mode, ld_mod, h, B, N, d, eps, eps_next, moe_ys=None,
-               moe_pos=None, moe_wts=None, route_w=None, route_E=0, route_sel=None, route_wts=None, route_forced=None):
+               moe_pos=None, moe_wts=None, route_w=None, route_E=0, route_sel=None, route_wts=None, route_forced=None, ystat=None, ystat_slots=None):
         xv = self.b[x].view(B * N, d)
         if moe_ys is None:
             yv = self.ref(y).view(B * N, d)
@@ -760,6 +913,7 @@ class Ops:
         from gpu_util import P, lib, ok, stream
         self.case, self.P, self.L, self.ok, self.stream = case, P, lib(), ok, stream
         self.g, self.b, self.keep, self.cache = {}, {}, [], {}
+        self.slots, self.grn_kernels, self.step = {}, {}, None     # ystat buffer -> slots its launch filled; closing step on ystat -> its row kernel's name
         self.kernels = {}     # grouped GEMM steps: (M, N, K, epilogue) -> the kernel's name (lt_op_gemm_describe; see _grouped_kernel)
         self.part = torch.zeros(256 * 2 * 64 * 128, dtype=torch.float32, device="cuda")     # split-K workspace: 256 slots, counters zero
         self.cnt = torch.zeros(256, dtype=torch.int32, device="cuda")
@@ -793,6 +947,8 @@ class Ops:
             return self.b[r[1]].view(-1)[r[2]:]
         if kind == "swap2":
             return self.ref(r[1], dtype).reshape(-1, 2).flip(1).contiguous()
+        if kind == "flipbr":
+            return self.ref(r[1], dtype).flip(0).contiguous()
         key = repr((r, dtype))
         if key not in self.cache:
             self.cache[key] = self._make(r, dtype)
@@ -885,9 +1041,10 @@ class Ops:
     def op_prep_mod(self, mod, B, ld_mod, L, chunks, d, tanh_mask, scale_mask, final_scale_chunk):
         self.ok(self.L.lt_op_prep_mod(self.P(self.b[mod]), B, ld_mod, L, chunks, d, tanh_mask, scale_mask, final_scale_chunk, self.stream()), "prep_mod")
 
-    def op_rope_table(self, dst, len, hd, step, theta0, lin0, theta1, lin1, lin_on_pos):
+    def op_rope_table(self, dst, len, hd, step, theta0, lin0, theta1, lin1, lin_on_pos, dst_t=None):
         out = self.new(dst, (2, len, hd // step, 2), torch.float32)
-        self.ok(self.L.lt_op_rope_table(self.P(out), len, hd, step, theta0, lin0, theta1, lin1, lin_on_pos, self.stream(), self.P(None)), "rope_table")
+        out_t = self.new(dst_t, (2, hd // step, len, 2), torch.float32) if dst_t else None
+        self.ok(self.L.lt_op_rope_table(self.P(out), len, hd, step, theta0, lin0, theta1, lin1, lin_on_pos, self.stream(), self.P(out_t)), "rope_table")
 
     def op_qkv_post(self, qkv, ld, q_col0, k_col0, v_col0, q_ln_w, q_ln_b, k_ln_w, k_ln_b, ln_eps, q, k, vt, B, N, Npad, H, Hkv, hd, table, q_scale,
                     k_scale, rope_mode, t, watershed, grid_w, cs_len):
@@ -915,6 +1072,55 @@ class Ops:
         self.ok(self.L.lt_op_qkv_attention_small(f(a), f(w), self.P(self.new(qkv, (M, n))), M, K, H, Hkv, tokens, hd, f(q_ln_w), f(q_ln_b), f(k_ln_w), f(k_ln_b),
                                                  f(table), table_len, grid_w, k_scale, self.P(ws), self.P(self.new(dst, (M, H * hd))), self.stream()),
                 "qkv_attention_small")
+
+    # -- the large-row launches -----------------------------------------------------------------------------------------------------------------
+    def _host_branch(self, t, watershed):
+        """the table branch an entry that takes ONE branch's table is handed: 0 when t[0] < watershed (fp32), else - and without t - 1"""
+        return 1 if t is None or not float(np.float32(self.case.inputs[t[1]][0])) < float(np.float32(watershed)) else 0
+
+    def op_gemm_qkv(self, a, w, qkv, vt, M, N, K, split, tokens, hd):
+        out = self.new(qkv, (M, N))       # (the V columns stay NaN: the launch leaves them untouched and nothing may read them)
+        v = self.new(vt, (M // tokens, (N - split) // hd, hd, tokens))
+        self.ok(self.L.lt_op_gemm_qkv(self.P(self.ref(a)), self.P(self.ref(w)), self.P(out), self.P(v), M, N, K, split, tokens, hd, self.stream()), "gemm_qkv")
+
+    def op_qkv_qstat(self, a, w, qkv, vt, M, N, K, split, tokens, hd, q_cols, k_ln_w, k_ln_b, table, t, watershed, grid_w, k_scale, k, qmr):
+        assert t is None or t[0] == "in"
+        f = lambda r: self.P(self.ref(r))
+        out, v = self.new(qkv, (M, N)), self.new(vt, (M // tokens, (N - split) // hd, hd, tokens))
+        kk = self.new(k, (M // tokens, (split - q_cols) // hd, tokens, hd))
+        ws, mr = self.new("qstat", (M, 32, 2), torch.float32), self.new(qmr, (M, 2), torch.float32)
+        tab = self.ref(table)[self._host_branch(t, watershed)]
+        assert tab.is_contiguous()
+        self.ok(self.L.lt_op_qkv_qstat(f(a), f(w), self.P(out), self.P(v), M, N, K, split, tokens, hd, q_cols, f(k_ln_w), f(k_ln_b), self.P(tab), grid_w,
+                                       k_scale, self.P(kk), self.P(ws), self.P(mr), self.stream()), "qkv_qstat")
+
+    def op_gemm_vt(self, a, w, dst, M, N, K, tokens, hd):
+        v = self.new(dst, (M // tokens, N // hd, hd, tokens))
+        self.ok(self.L.lt_op_gemm_vt(self.P(self.ref(a)), self.P(self.ref(w)), self.P(v), M, N, K, tokens, hd, 0, self.stream()), "gemm_vt")
+
+    def op_qk_post_pair(self, qkv, ld, q_col0, k_col0, q_ln_w, q_ln_b, k_ln_w, k_ln_b, ln_eps, q, k, B, N, H, Hkv, hd, table, q_scale, k_scale, rope_mode,
+                        t, watershed, grid_w, cs_len):
+        f = lambda r: self.P(self.ref(r))
+        tt = None if t is None else self.ref(t)
+        self.ok(self.L.lt_op_qk_norm_rope_pair(f(qkv), ld, q_col0, k_col0, f(q_ln_w), f(q_ln_b), f(k_ln_w), f(k_ln_b), ln_eps, self.P(self.new(q, (B, H, N, hd))),
+                                               self.P(self.new(k, (B, Hkv, N, hd))), B, N, H, Hkv, hd, rope_mode, f(table), cs_len, self.P(tt), watershed,
+                                               grid_w, self.P(None), self.P(None), q_scale, k_scale, self.stream()), "qk_norm_rope_pair")
+
+    def op_attention_qraw(self, qkv, ld, q_col0, qmr, q_ln_w, q_ln_b, table, table_t, table_len, grid_w, t, watershed, k, vt, tk, tvt, tbias, tgate,
+                          T, Tpad, dst, B, H, Hkv, N, Npad, hd):
+        f = lambda r: self.P(self.ref(r))
+        tt = None if t is None else self.ref(t)
+        self.ok(self.L.lt_op_attention_qraw_ex(f(qkv), ld, q_col0, f(qmr), f(q_ln_w), f(q_ln_b), f(table), f(table_t), table_len, grid_w, self.P(tt),
+                                               watershed, f(k), f(vt), f(tk), f(tvt), f(tbias), f(tgate), T, Tpad, self.P(self.new(dst, (B * N, H * hd))),
+                                               B, H, Hkv, N, Npad, hd, self.stream()), "attention_qraw_ex")
+
+    def op_gemm_ystat(self, a, w, dst, ystat, M, N, K):
+        cap = 2 * (-(-N // 256))
+        ws, n = self.new(ystat, (M, cap), torch.float32), ctypes.c_int32(0)
+        self.ok(self.L.lt_op_gemm_ystat(self.P(self.ref(a)), self.P(self.ref(w)), self.P(self.new(dst, (M, N))), self.P(ws), cap, M, N, K, ctypes.byref(n),
+                                        self.stream()), "gemm_ystat")
+        assert 0 < n.value <= cap and n.value % 2 == 0, (ystat, n.value, cap)
+        self.slots[ystat] = n.value
 
     # -- mixture of experts --------------------------------------------------------------------------------------------------------------------
     def _plan_bufs(self, rows, sel, wts):
@@ -958,8 +1164,19 @@ class Ops:
                                           self.stream()), "gemm_grouped")
 
     def op_grn(self, x, y, post_w, gate, post_mode, next_w, next_scale, next_shift, next_mode, ld_mod, h, B, N, d, eps, eps_next, moe_ys=None,
-               moe_pos=None, moe_wts=None, route_w=None, route_E=0, route_sel=None, route_wts=None, route_forced=None):
+               moe_pos=None, moe_wts=None, route_w=None, route_E=0, route_sel=None, route_wts=None, route_forced=None, ystat=None, ystat_slots=None):
         f = lambda r: self.P(self.ref(r))
+        if ystat is not None:      # the partial sums the projection left: the launcher streams on them where it has that form, else reduces y itself
+            slots = self.slots[ystat_slots[1]] + (ystat_slots[2] if len(ystat_slots) > 2 else 0)
+            name = ctypes.create_string_buffer(100)
+            self.ok(self.L.lt_op_gated_residual_norm_describe(post_mode, 0, next_mode, d, int(next_w is not None), int(next_scale is not None),
+                                                              int(next_shift is not None), 1, 1, slots, 0, name, 100), "gated_residual_norm_describe")
+            self.grn_kernels[self.step] = name.value.decode()
+            self.ok(self.L.lt_op_gated_residual_norm_ex(self.P(self.b[x]), f(y), f(post_w), f(gate), post_mode, 0, f(next_w), f(next_scale), f(next_shift), next_mode,
+                                                        ld_mod, self.P(self.new(h, (B * N, d))), B, N, d, eps, eps_next, 1, 0, f(ystat), slots, self.P(None),
+                                                        self.P(None), self.P(None), self.P(None), 0, self.P(None), self.P(None), self.P(None), self.stream()),
+                    "gated_residual_norm_ex (ystat)")
+            return
         if moe_ys is not None or route_w is not None:
             rs, rw = self._plan_bufs(B * N, route_sel, route_wts) if route_w is not None else (None, None)
             self.ok(self.L.lt_op_gated_residual_norm_ex(self.P(self.b[x]), f(y), f(post_w), f(gate), post_mode, 0, f(next_w), f(next_scale), f(next_shift), next_mode,

@@ -113,6 +113,7 @@ def test_null_arguments_are_errors_not_crashes(lib):
                                        1, 1, 1, 64, 64, 72, None) != 0 and b"lt_op_attention_qraw_ex: null" in lib.lt_last_error()
     assert lib.lt_op_attention_small(None, 0, 0, 0, 0, None, 0, 0, 0, 0, 0, None, None, None, None, None, 0, 0, None, 0.0, 1.0, None, 1, 8, 8, 64, 48,
                                      None) != 0 and b"lt_op_attention_small: null" in lib.lt_last_error()
+    assert lib.lt_op_gemm_ystat(None, None, None, None, 0, 256, 256, 256, None, None) != 0 and b"lt_op_gemm_ystat: null" in lib.lt_last_error()
     assert lib.lt_set_option(b"no_such_knob", 1) != 0 and b"no_such_knob" in lib.lt_last_error()
 
 

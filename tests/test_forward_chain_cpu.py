@@ -103,6 +103,55 @@ def test_every_mutation_moves_the_float64_chain_past_the_gate(golden_dir, name, 
     assert not missed, (case.name, GATE, missed)
 
 
+# ---- the large-row regime's step list, at the tiny fixtures' shapes ---------------------------------------------------------------------------
+# Which launch runs is a property of the GPU launchers (from one 256-row tile per CU on); what the steps MEAN is not, so the float64 backend
+# runs every large-regime list on the fixtures and is held to the oracle by the same gate (tests/test_gpu_forward_chain_large.py runs the same
+# lists on the GPU at the sizes where the engine takes these routes).
+LARGE_PATHS = {
+    "qraw": {"qkv": "fused", "raw_q": True, "ystat": 1},                    # QKV_FUSED + raw_q / POST_K_ONLY: next_t2i at head_dim 72
+    "pair": {"qkv": "fused", "post": "pair", "ystat": 1},                   # QKV_FUSED + POST_QK_PAIR: head_dim 48 / 96 / 128, or attn_q_fused 0
+    "qk_vt": {"qkv": "qk_vt", "post": "pair", "ystat": 1},                  # qkv_fused_gemm 0: Q | K plain + the V^T launch
+    "pair_reduce": {"qkv": "fused", "post": "pair", "ystat": 0},            # grn_ystat 0: the closing steps reduce y themselves
+    "qraw_reduce": {"qkv": "fused", "raw_q": True, "ystat": 0},
+}
+LARGE_CASES = [(name, mode, key) for name in FC.GOLDENS["next_t2i"] for mode in ("cfg4", "lin2", "ntk2") for key in ("qraw", "pair")] + \
+              [("nextdit_tiny_gqa", "forward", "qraw"), ("nextdit_tiny_rect", "cfg4", "qk_vt"), ("nextdit_tiny", "cfg4", "pair_reduce"),
+               ("nextdit_tiny_gqa", "cfg4", "qraw_reduce")] + \
+              [(name, mode, key) for name in ("imagenet_tiny", "flag_tiny") for mode in ("forward", "cfg4") for key in ("pair", "qk_vt")]
+LARGE_MUTATION_CASES = [("nextdit_tiny_rect", "lin2", "qraw"), ("nextdit_tiny_gqa", "ntk2", "qraw"), ("nextdit_tiny_rect", "ntk2", "pair"),
+                        ("nextdit_tiny_rect", "cfg4", "qk_vt"), ("imagenet_tiny", "cfg4", "pair"),
+                        ("flag_tiny", "cfg4", "qk_vt")]
+
+
+@pytest.mark.parametrize("name,mode,key", LARGE_CASES)
+def test_large_regime_step_list_is_the_oracle(golden_dir, name, mode, key):
+    case, _ = make_case(golden_dir, name, mode)
+    steps = FC.build(case, LARGE_PATHS[key])
+    default = {s.name for s in FC.build(case, {"small_fused": False})}
+    assert {s.name for s in steps} != default, "the paths changed no step"
+    _, err = run_against_oracle(case, steps)
+    print(f"{case.name} [{key}]: rel_l2(torch64, oracle fp32) = {err:.3e} (default list: {MEASURED[case.name]:.3e}, gate {GATE:.3e})")
+    assert err < GATE, (case.name, key, err, GATE)
+
+
+@pytest.mark.parametrize("name,mode,key", LARGE_MUTATION_CASES)
+def test_large_regime_mutations_move_the_float64_chain_past_the_gate(golden_dir, name, mode, key):
+    """every mutation of the new steps that float64 models ("gpu:" entries change operands it does not: the GPU module runs those)"""
+    case, _ = make_case(golden_dir, name, mode)
+    steps = FC.build(case, LARGE_PATHS[key])
+    base, err = run_against_oracle(case, steps)
+    assert err < GATE, (case.name, key, "unmutated", err)
+    muts = [(m, h) for m, h in FC.large_mutations(case, steps) if not m.startswith("gpu:")]
+    assert muts, (case.name, key)
+    missed = []
+    for mname, hook in muts:
+        moved = FC.rel_l2(FC.run(FC.Torch64(case), steps, hook), base)
+        print(f"{case.name} [{key}]: {mname}: moved {moved:.3e}")
+        if not moved > GATE:
+            missed.append((mname, moved))
+    assert not missed, (case.name, key, GATE, missed)
+
+
 def test_mutation_list_covers_the_issue(golden_dir):
     """every entry of the list appears on at least one case, in layer 0 and layer 1 where it is per layer"""
     seen = set()

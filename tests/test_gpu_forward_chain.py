@@ -32,8 +32,8 @@ Launches, at the fixtures' shapes (64 / 60 / 104 tokens, 128 / 120 / 208 rows, 3
                      refuses routing outside its MoE kernel, and the test asserts that refusal by name.
                      Out of reach at these sizes: the grouped mode of the persistent kernel and the pair layout of the expert weights (both need
                      1.5 tiles of 256 x 256 per CU), the tail split, the plan kernel's larger register forms and generic walk (tests/test_moe_plan.py).
-gemm_prefetch riders read only.  Gated by shape and not reached at these sizes, so not covered here: the fused QKV launch, the V^T epilogue,
-attn_q_fused, the pair layout, the row-statistics (ystat) form of the closing steps.
+gemm_prefetch riders read only.  Gated by shape and not reached at these sizes: the fused QKV launch, the V^T epilogue, attn_q_fused, the pair
+layout, the row-statistics (ystat) form of the closing steps - tests/test_gpu_forward_chain_large.py runs the same comparison where they are.
 Graph replay: the default ("graph" 2) captures above 1024 rows only, so the call-order cases set "graph" 1 on their engine
 (lt_engine_set_option, per engine) and check lt_graph_replays: the first call of the key is eager, the second captures and launches the
 graph, the third replays it - staging copies, the RoPE table rebuilt in front of a replay after another key changed it.
