@@ -657,6 +657,36 @@ int lt_sample_ode_cfg_pag(lt_engine* e, const void* z_dev, void* traj_dev, void*
                           const float* cfg_host, const float* pag_host, const int32_t* skip_host, int32_t n_skip, const int32_t* perturb_host,
                           int32_t n_perturb, int32_t t_round_to_state_dtype, const lt_step_args* a, void* stream);
 
+/* Smoothed-energy guidance (SEG; transport/guidance.py: sample_cfg_seg is the definition).  An evaluation can run a set Q of
+ * blocks BLURRED: their self-attention reads Gaussian-blurred queries.  The blur acts on the POST-RoPE queries q[B, H, N, hd] (q_norm + RoPE
+ * applied, bf16) as an image over the 2-D token grid, per (sample, head, channel), separably: a horizontal pass kept in fp32, a vertical pass
+ * on it, ONE rounding to bf16; reflection without repeating the edge; Flag-DiT's end-of-line tokens are copied and are nobody's neighbour.
+ * sigma > 0 gives the taps (transport/guidance.py: seg_taps - Gaussian in float64, normalised, rounded once to fp32; radius
+ * min(ceil(3 sigma), LT_SEG_MAX_RADIUS)); sigma == +inf: every image query becomes the mean query, RN_bf16 of the float64 sum over the count.
+ * Keys, values, and the text families' gated text cross-attention (which reads the UNBLURRED queries, on top, as the stand-alone text launch
+ * does) are the block's as it is; so is everything behind the attention.  blur_host: n_blur layer indices on the host, in any order, disjoint
+ * from the skip set; Q may hold every layer.  No entry combines a blur set with a perturb set.  The sets belong to the call: no entry point
+ * returns with one left behind, error returns included.
+ * lt_forward_blur: lt_forward with the blocks of S left out and the blocks of Q blurred; both empty IS lt_forward.
+ * lt_forward_cfg_seg: lt_forward_cfg_slg with the third prediction b taken under (S, Q): R(R(u + R(w R(c - u))) + R(s R(c - b))), at w == 1
+ * R(c + R(s R(c - b))); seg_scale == 0: lt_forward_cfg at cfg_scale.
+ * lt_sample_ode_cfg_seg: lt_sample_ode_cfg_pag's arguments, behaviour, counters and stage rules with the blur set and sigma in place of the
+ * perturb set; ONE scale table (seg_host); a stage whose scale is 0 launches no third evaluation; at most five HIP-graph keys per trajectory.
+ * The blur set's words join the HIP-graph key behind a mark of their own (-4) with the mode and the radius; the taps live in a device buffer
+ * the call writes, so another sigma of the same radius records nothing anew.
+ * Refused by name with nothing written: everything the perturbed-attention entries refuse (with "blur" for "perturb"); sigma not positive or
+ * NaN; a radius the call's grid cannot reflect (radius > min(rows, columns) - 1 of the image tokens); a packed batch; a regional prompt; a
+ * stream under capture when a set is given. */
+#define LT_SEG_MAX_RADIUS 31
+int lt_forward_blur(lt_engine* e, const void* x_dev, const float* t_dev, void* out_dev, const lt_step_args* a, const int32_t* skip_host,
+                    int32_t n_skip, const int32_t* blur_host, int32_t n_blur, float sigma, void* stream);
+int lt_forward_cfg_seg(lt_engine* e, const void* x_dev, const float* t_dev, void* out_dev, float cfg_scale, float seg_scale,
+                       const int32_t* skip_host, int32_t n_skip, const int32_t* blur_host, int32_t n_blur, float sigma, const lt_step_args* a,
+                       void* stream);
+int lt_sample_ode_cfg_seg(lt_engine* e, const void* z_dev, void* traj_dev, void* final_dev, const float* tgrid_host, int32_t n_grid, int32_t method,
+                          const float* cfg_host, const float* seg_host, const int32_t* skip_host, int32_t n_skip, const int32_t* blur_host,
+                          int32_t n_blur, float sigma, int32_t t_round_to_state_dtype, const lt_step_args* a, void* stream);
+
 /* number of model evaluations issued by the last lt_sample_ode /lt_sample_ode_packed / lt_sample_views / lt_sample_views_guided / lt_sample_sde / lt_sample_ode_adaptive call */
 int64_t lt_last_nfe(lt_engine* e);
 /* the rows those evaluations ran, summed: nfe * batch for every sampler but lt_sample_ode_cfg_schedule, whose conditional-only stages run half */

@@ -275,6 +275,19 @@ int lt_op_unpatchify_cfg_slg(const void* rows, int32_t ld, void* out, int32_t ou
  * leave the row, a pointer not aligned to 16 bytes, out_pair with an odd B * N or H * hd % 32 != 0. */
 int lt_op_attention_identity(const void* src, int32_t ld_src, int32_t col0, void* out, int32_t B, int32_t N, int32_t H, int32_t Hkv, int32_t hd,
                              int32_t out_pair, void* stream);
+/* Smoothed-energy guidance (csrc/query_blur.hip), for tests/test_gpu_seg.py: the separable 2-D blur of the query image.
+ * q, out: bf16 [B, H, N, hd], two buffers (not in place).  grid_w: tokens per grid row, Hp = N / grid_w rows; blur_w <= grid_w: the columns
+ * that are image tokens - the others are copied word for word and are nobody's neighbour.  Per (b, h, channel):
+ *   mode 0  a[y][x] = sum_{k=-r..r} w[k] q[y][refl(x + k)] in fp32, one fused multiply-add per tap from k = -r upward, starting from 0.f;
+ *           out[y][x] = RN_bf16(the same over y on the fp32 a);  refl: -i -> i, n - 1 + i -> n - 1 - i.  taps_dev: 2 r + 1 fp32 words.
+ *   mode 1  out[y][x] = RN_bf16(S / n), S the float64 sum of the n = Hp * blur_w words (taps_dev unused, may be NULL).
+ * Refused by name with nothing written: a null pointer, a head_dim other than 48 / 72 / 96 / 128, N % grid_w != 0, blur_w outside 1..grid_w,
+ * radius outside 0..LT_SEG_MAX_RADIUS, radius >= min(Hp, blur_w) in mode 0, a misaligned pointer (16 bytes; the taps 4), q == out.
+ * lt_op_seg_taps: what the engine derives from sigma, on the host - mode (0 taps / 1 mean), radius, and the 2 r + 1 taps (taps_host: room for
+ * 2 * LT_SEG_MAX_RADIUS + 1 floats; mode 1 writes none).  Equal to transport/guidance.py: seg_taps word for word.  Refused: sigma <= 0 or NaN. */
+int lt_op_query_blur(const void* q, void* out, const float* taps_dev, int32_t B, int32_t H, int32_t N, int32_t hd, int32_t grid_w, int32_t blur_w,
+                     int32_t radius, int32_t mode, void* stream);
+int lt_op_seg_taps(float sigma, float* taps_host, int32_t* radius, int32_t* mode);
 /* Step caching (csrc/step_cache.hip), for tests/test_gpu_teacache.py.  n: bf16 words, a positive multiple of 8; fixed launch
  * geometry, so the sums are a function of the operands alone.
  *   lt_op_cache_indicator: sums_dev[0] = sum |h - h_prev|, sums_dev[1] = sum |h_prev|, every difference and sum in float64; then h_prev <- h.

@@ -160,6 +160,12 @@ _SIGNATURES: Dict[str, tuple] = {
     "lt_forward_cfg_pag": (_i32, [_vp, _vp, _vp, _vp, _f32, _f32, C.POINTER(_i32), _i32, C.POINTER(_i32), _i32, C.POINTER(LtStepArgs), _vp]),
     "lt_sample_ode_cfg_pag": (_i32, [_vp, _vp, _vp, _vp, C.POINTER(_f32), _i32, _i32, C.POINTER(_f32), C.POINTER(_f32), C.POINTER(_i32), _i32,
                                      C.POINTER(_i32), _i32, _i32, C.POINTER(LtStepArgs), _vp]),
+    "lt_forward_blur": (_i32, [_vp, _vp, _vp, _vp, C.POINTER(LtStepArgs), C.POINTER(_i32), _i32, C.POINTER(_i32), _i32, _f32, _vp]),
+    "lt_forward_cfg_seg": (_i32, [_vp, _vp, _vp, _vp, _f32, _f32, C.POINTER(_i32), _i32, C.POINTER(_i32), _i32, _f32, C.POINTER(LtStepArgs), _vp]),
+    "lt_sample_ode_cfg_seg": (_i32, [_vp, _vp, _vp, _vp, C.POINTER(_f32), _i32, _i32, C.POINTER(_f32), C.POINTER(_f32), C.POINTER(_i32), _i32,
+                                     C.POINTER(_i32), _i32, _f32, _i32, C.POINTER(LtStepArgs), _vp]),
+    "lt_op_query_blur": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "lt_op_seg_taps": (_i32, [_f32, C.POINTER(_f32), C.POINTER(_i32), C.POINTER(_i32)]),
     "lt_last_nfe": (_i64, [_vp]),
     "lt_last_eval_rows": (_i64, [_vp]),
     "lt_graph_replays": (_i64, [_vp]),

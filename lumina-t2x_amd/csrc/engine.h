@@ -259,6 +259,15 @@ struct lt_engine {
     // perturbed-attention guidance: the layers THIS call's evaluation runs with the identity in place of their self-attention map
     // (ascending, distinct, inside 0 .. L-1, disjoint from `skip`; may hold every layer).  Kept like `skip`: SkipScope writes and empties it
     std::vector<int32_t> perturb;
+    // smoothed-energy guidance: the layers THIS call's evaluation runs with blurred queries in their self-attention (ascending,
+    // distinct, inside 0 .. L-1, disjoint from `skip`; may hold every layer; never together with `perturb`).  Kept like `skip`.  blur_mode /
+    // blur_radius: what the call's sigma stands for (seg_taps_host), part of the graph key beside the set; the taps themselves are in blur_taps,
+    // 2 * LT_SEG_MAX_RADIUS + 1 fp32 words on the device that ensure_blur writes on the call's stream - no part of the key.  q_blur: the blurred
+    // query image, the size of q.  Both buffers are allocated by the first call that needs them (ensure_blur) and kept for the engine's life
+    std::vector<int32_t> blur;
+    int blur_mode = 0, blur_radius = 0;
+    float* blur_taps = nullptr;
+    u16* q_blur = nullptr;
     // step caching: the modulated input of the first block of the previous evaluation, the token stream before block 0 and the
     // residual r = bfr(x_L - x_0) of the last evaluation that ran the stack - max_batch * max_tokens x d bf16 each; behind them the indicator's
     // partial sums and its two float64 result words, and the page-locked pair the host reads them from.  Allocated by the first call that needs
@@ -326,9 +335,18 @@ struct SkipScope {
     explicit SkipScope(lt_engine* eng) : e(eng) {}
     SkipScope(const SkipScope&) = delete;
     SkipScope& operator=(const SkipScope&) = delete;
-    ~SkipScope() { e->skip.clear(); e->perturb.clear(); }
+    ~SkipScope() { e->skip.clear(); e->perturb.clear(); e->blur.clear(); }
     int set(const char* who, const int32_t* skip_host, int n_skip, const int32_t* perturb_host = nullptr, int n_perturb = 0);
+    // the skip set and the set of blurred blocks (the perturb set stays empty); the call has run ensure_blur for its sigma
+    int set_blur(const char* who, const int32_t* skip_host, int n_skip, const int32_t* blur_host, int n_blur);
 };
+// the refusals of SkipScope::set_blur alone (nothing stored): both sets, that they are disjoint, and sigma
+int check_blur_sets(const lt_engine* e, const char* who, const int32_t* skip_host, int n_skip, const int32_t* blur_host, int n_blur, float sigma);
+// ... and of the call's grid: the radius sigma stands for must be reflectable on latent_h / patch x latent_w / patch image tokens (n_blur 0: nothing)
+int check_blur_radius(const lt_engine* e, const char* who, const lt_step_args* a, int n_blur, float sigma);
+// smoothed-energy guidance: the blurred-query buffer and the tap words, allocated on the first call, before anything is launched; then the taps
+// of this call's sigma put in place on stream s (one synchronisation: they come from pageable memory) and mode / radius stored (engine.hip)
+int ensure_blur(lt_engine* e, float sigma, hipStream_t s);
 // the refusals of SkipScope::set alone (nothing stored): both sets, and that they are disjoint
 int check_layer_sets(const lt_engine* e, const char* who, const int32_t* skip_host, int n_skip, const int32_t* perturb_host, int n_perturb);
 // ... of a call that takes a skip set only

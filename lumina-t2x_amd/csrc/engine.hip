@@ -503,6 +503,13 @@ int forward_dims(lt_engine* e, const lt_step_args* a, int use_cfg, hipStream_t s
     LT_REQUIRE(e->perturb.empty() || !pk, "perturbed attention: a packed batch is not served (tensor input only)");
     LT_REQUIRE(e->perturb.empty() || kt.skip_ok, "perturbed attention: a perturb set is not served by an evaluation of kind %d", (int)kind);
     LT_REQUIRE(e->perturb.empty() || e->reg_Y == 0, "perturbed attention: a regional prompt is prepared (lt_prepare_prompt_regional), which is not served");
+    LT_REQUIRE(e->blur.empty() || !pk, "blurred queries: a packed batch is not served (tensor input only)");
+    LT_REQUIRE(e->blur.empty() || kt.skip_ok, "blurred queries: a blur set is not served by an evaluation of kind %d", (int)kind);
+    LT_REQUIRE(e->blur.empty() || e->reg_Y == 0, "blurred queries: a regional prompt is prepared (lt_prepare_prompt_regional), which is not served");
+    LT_REQUIRE(e->blur.empty() || e->perturb.empty(), "blurred queries: a blur set together with a perturb set is not served");
+    LT_REQUIRE(e->blur.empty() || (e->q_blur && e->blur_taps), "blurred queries: the buffers are not allocated (ensure_blur)");
+    LT_REQUIRE(e->blur.empty() || e->blur_mode == 1 || e->blur_radius < std::min(Hp, Wp), "blurred queries: radius %d cannot be reflected on this "
+               "call's grid of %d x %d image tokens (radius <= min(rows, columns) - 1)", e->blur_radius, Hp, Wp);
     if (lt_slg_kernel_mode(kind) >= 0) LT_REQUIRE(e->g_skip, "skip-layer guidance: the buffer is not allocated (ensure_skip_buf)");
     if (kind == LT_KIND_REUSE_STORE || kind == LT_KIND_REUSE_AGAIN) LT_REQUIRE(e->g_delta, "guidance reuse: the buffer is not allocated (ensure_delta)");
     LT_REQUIRE(e->rule_form == 0 || (kind == LT_KIND_RULE && e->p_mom && e->p_par && e->p_stats) || kind == LT_KIND_COND_ONLY,
@@ -745,13 +752,50 @@ int block_attention_perturbed(lt_engine* e, const Dims& dm, const PerturbPlan& p
     return attention(e, tx, s) ? 1 : 0;
 }
 
+// Blurred queries (smoothed-energy guidance): the deviations of a layer whose self-attention reads Gaussian-blurred queries, decided
+// once next to the block's plan.  Such a layer projects Q | K | V on the plan's GEMM route (QKV_SMALL_FUSED: the plain GEMM and the ordinary
+// post-processing - the one-launch attention has its queries in registers only), never hands raw queries to the attention prologue (the K pass
+// runs alone, q_norm + RoPE on Q is the stand-alone launch into e->q), blurs e->q into e->q_blur and runs the self-attention on that.  The text
+// keys do not ride in that launch: the stand-alone text launch accumulates on top with the UNBLURRED e->q, as a perturbed layer's does - and
+// as there it accumulates into row-major rows, so under the pair plan a text layer's self launch writes row-major and the O projection reads
+// a row-major A (pair_ab bit 1 alone); without text the attention writes out_pair as the plan does.
+struct BlurPlan {
+    QkvRoute qkv = QKV_PLAIN;
+    PostRoute post = POST_SEPARATE;
+    bool text = false;
+    bool out_pair = false;       // e->attn leaves the self-attention launch in the pair layout
+    bool attn_rowmajor = false;  // the pair plan's O projection reads e->attn row-major in this layer
+};
+int plan_blurred(const lt_engine* e, const Dims& dm, const BlockPlan& bp, BlurPlan& bl) {
+    bl = BlurPlan{};
+    bl.text = e->v.text;
+    LT_REQUIRE(!bp.regional, "blurred queries: a regional prompt is not served");
+    bl.qkv = bp.qkv == QKV_SMALL_FUSED ? QKV_PLAIN : bp.qkv;
+    // (what plan_block chooses without raw queries; POST_K_ONLY stays: there it names "the K pass alone", and Q gets its own launch)
+    bl.post = bp.post == POST_K_ONLY ? POST_K_ONLY
+              : !bp.vt_epi && (lt_opt(OPT_QKV_POST_FUSED) == 1 || (lt_opt(OPT_QKV_POST_FUSED) == 2 && dm.M < 2048)) ? POST_ONE_LAUNCH
+              : lt_opt(OPT_QK_POST_PAIR) && dm.M >= 2048 ? POST_QK_PAIR : POST_SEPARATE;
+    if (bp.pair) {
+        AttnArgs at = self_attn_args(e, dm, e->lw[0]);
+        at.q = e->q_blur; at.tk = nullptr; at.tvt = nullptr; at.tbias = nullptr; at.tgate = nullptr; at.Tk = 0; at.Tkpad = 0;
+        bl.out_pair = !bl.text && attention_is_one_wave(at);
+        bl.attn_rowmajor = !bl.out_pair;
+    }
+    return 0;
+}
+
 // the attention branch of a block up to e->attn: QKV projection, q / k post-processing, self-attention [+ text keys], on the plan's route
-int block_attention(lt_engine* e, const Dims& dm, const BlockPlan& bp, LayerW& w, const float* t_dev, const lt_step_args* a, hipStream_t s) {
+// bl: the layer's queries are blurred - the deviations of BlurPlan; null: the block as it is
+int block_attention(lt_engine* e, const Dims& dm, const BlockPlan& bp, LayerW& w, const float* t_dev, const lt_step_args* a, hipStream_t s,
+                    const BlurPlan* bl = nullptr) {
     const lt_config& c = e->cfg; const VariantDesc& v = e->v;
     const int B = dm.B, N = dm.N, Npad = dm.Npad, M = dm.M, d = e->d, dkv = e->dkv, H = e->H, Hkv = e->Hkv, hd = e->hd;
     GemmArgs gq = qkv_gemm_args(e, dm, w);
     AttnArgs at = self_attn_args(e, dm, w);
-    if (bp.qkv == QKV_SMALL_FUSED) {
+    const QkvRoute qkv = bl ? bl->qkv : bp.qkv;
+    const PostRoute post = bl ? bl->post : bp.post;
+    const bool raw_q = bp.raw_q && !bl;
+    if (qkv == QKV_SMALL_FUSED) {
         gq.VT = nullptr; gq.rowstat = e->qstat; gq.rowstat_slots = e->qstat_slots;
         if (profiled_gemm(e, gq, 0, 2.0 * M * (double)(d + 2 * dkv) * d, s)) return 1;
         AttnSmallArgs as;
@@ -763,11 +807,11 @@ int block_attention(lt_engine* e, const Dims& dm, const BlockPlan& bp, LayerW& w
         ProfScope ps(e, 1, 4.0 * B * H * (double)N * N * hd, s);
         return launch_attention_small(as, s) ? 1 : 0;  // (class-conditional: no text keys behind it)
     }
-    if (bp.qkv == QKV_FUSED) {
-        if (bp.raw_q) { gq.qstat = e->qstat; gq.qstat_cols = d; gq.qstat_slots = bp.qstat_slots; }
+    if (qkv == QKV_FUSED) {
+        if (raw_q) { gq.qstat = e->qstat; gq.qstat_cols = d; gq.qstat_slots = bp.qstat_slots; }
         gq.pair_ab = bp.pair ? 3 : 0;
         if (profiled_gemm(e, gq, 3, 2.0 * M * (double)(d + 2 * dkv) * d, s)) return 1;
-    } else if (bp.qkv == QKV_QK_AND_VT) {
+    } else if (qkv == QKV_QK_AND_VT) {
         if (gemm(e, e->h, d, w.wqkv, d, e->qkv, e->qkvn, M, d + dkv, d, nullptr, 0, s)) return 1;
         GemmArgs g;
         g.A = e->h; g.W = w.wqkv + (size_t)(d + dkv) * d; g.C = e->vt; g.bias = nullptr; g.bias_dtype = -1;
@@ -788,24 +832,32 @@ int block_attention(lt_engine* e, const Dims& dm, const BlockPlan& bp, LayerW& w
         qa.out_scale = dm.sm_scale * LOG2E;  // softmax scale folded into K's one bf16 rounding (scores in log2 units)
         pa.k = qa;
         pa.v_src = e->qkv; pa.v_dst = e->vt; pa.v_ld_src = e->qkvn; pa.v_col0 = d + dkv; pa.v_B = B; pa.v_N = N; pa.v_Npad = Npad; pa.v_kv_heads = Hkv; pa.v_hd = hd;
-        if (bp.post == POST_K_ONLY) {
+        if (post == POST_K_ONLY && !raw_q) {  // a blurred layer of the raw-query plan: the K pass alone, the queries in a launch of their own
+            if (launch_qk_norm_rope(pa.k, s) || launch_qk_norm_rope(pa.q, s)) return 1;
+        } else if (post == POST_K_ONLY) {
             pa.k.qstat_in = e->qstat; pa.k.qstat_out = e->qmr; pa.k.qstat_slots = bp.qstat_slots; pa.k.qstat_width = d;
             if (launch_qk_norm_rope(pa.k, s)) return 1;
             at.q = nullptr; at.q_raw = e->qkv; at.q_ld = e->qkvn; at.q_col0 = 0; at.q_stat = e->qmr; at.q_ln_w = w.q_norm_w; at.q_ln_b = w.q_norm_b;
             at.rope_cs = e->rope; at.rope_cs_t = e->rope_tr; at.rope_t = t_dev; at.rope_watershed = pa.q.watershed; at.rope_cs_len = e->rope_len; at.rope_grid_w = dm.Wp;
-        } else if (bp.post == POST_ONE_LAUNCH) {
-            if (!bp.regional && (bp.fuse_text || !v.text)) prefetch_rider(e, &pa.pf, e->attn, d, w.wo, d, e->o, d, M, d, d, 0);
+        } else if (post == POST_ONE_LAUNCH) {
+            if (!bl && !bp.regional && (bp.fuse_text || !v.text)) prefetch_rider(e, &pa.pf, e->attn, d, w.wo, d, e->o, d, M, d, d, 0);
             if (launch_qkv_post(pa, s)) return 1;
         } else {
-            if (bp.post == POST_QK_PAIR) { if (launch_qk_norm_rope_pair(pa.q, pa.k, s)) return 1; }
+            if (post == POST_QK_PAIR) { if (launch_qk_norm_rope_pair(pa.q, pa.k, s)) return 1; }
             else if (launch_qk_norm_rope(pa.q, s) || launch_qk_norm_rope(pa.k, s)) return 1;
             if (!bp.vt_epi && launch_v_transpose(e->qkv, e->qkvn, d + dkv, e->vt, B, N, Npad, Hkv, hd, s)) return 1;
         }
     }
-    at.out_pair = bp.pair;
+    at.out_pair = bl ? bl->out_pair : bp.pair;
+    if (bl) {  // e->q -> e->q_blur, the self-attention on the blurred queries without the text keys
+        ProfScope ps(e, 2, 0, s);
+        if (launch_query_blur(e->q, e->q_blur, e->blur_taps, B, H, N, hd, dm.Wrow, dm.Wp, e->blur_radius, e->blur_mode, s)) return 1;
+        at.q = e->q_blur; at.tk = nullptr; at.tvt = nullptr; at.tbias = nullptr; at.tgate = nullptr; at.Tk = 0; at.Tkpad = 0;
+    }
     if (attention(e, at, s)) return 1;
-    if (bp.regional || (v.text && !bp.fuse_text)) {  // the text keys in launches of their own
+    if (bp.regional || (v.text && (bl || !bp.fuse_text))) {  // the text keys in launches of their own
         AttnArgs tx = at;
+        tx.q = e->q; tx.out_pair = 0;  // (a blurred layer: the text keys see the queries as they are)
         tx.k = w.ky; tx.vt = w.vty; tx.bias = e->txt_bias; tx.nk_batch = nullptr;
         tx.Nk = e->prompt_T; tx.Nkpad = e->prompt_Tpad; tx.scale = (float)(1.0 / std::sqrt((double)hd));
         if (!bp.regional) { tx.gate = w.gate; tx.accumulate = 1; return attention(e, tx, s) ? 1 : 0; }
@@ -822,14 +874,14 @@ int block_attention(lt_engine* e, const Dims& dm, const BlockPlan& bp, LayerW& w
 // block l on the plan's route; h leaves prepared for layer nl, the next one that runs (L: none does - the final layer's form)
 // pp: the layer is perturbed - its attention branch up to e->attn is block_attention_perturbed's; everything behind is the block as it is
 int run_block(lt_engine* e, const Dims& dm, const BlockPlan& bp, int l, int nl, const float* t_dev, const lt_step_args* a, hipStream_t s,
-              const PerturbPlan* pp = nullptr) {
+              const PerturbPlan* pp = nullptr, const BlurPlan* bl = nullptr) {
     const VariantDesc& v = e->v;
     const int B = dm.B, N = dm.N, M = dm.M, d = e->d, F = e->F, pair = bp.pair;
     const int post_mode = v.post ? 1 : 0, gate_mode = 0;  // gates arrive ready (tanh applied by the conditioning where the family has it)
     LayerW& w = e->lw[l];
-    if (pp ? block_attention_perturbed(e, dm, *pp, w, t_dev, a, s) : block_attention(e, dm, bp, w, t_dev, a, s)) return 1;
+    if (pp ? block_attention_perturbed(e, dm, *pp, w, t_dev, a, s) : block_attention(e, dm, bp, w, t_dev, a, s, bl)) return 1;
     int ys_o = 0, ys_f = 0;
-    if (gemm(e, e->attn, d, w.wo, d, e->o, d, M, d, d, nullptr, 0, s, &ys_o, pair ? (pp && pp->attn_rowmajor ? 2 : 3) : 0)) return 1;
+    if (gemm(e, e->attn, d, w.wo, d, e->o, d, M, d, d, nullptr, 0, s, &ys_o, pair ? ((pp && pp->attn_rowmajor) || (bl && bl->attn_rowmajor) ? 2 : 3) : 0)) return 1;
     {   // x += gate' * post(attn) ; h = pre_ffn(x) * (1 + scale) [+ shift]
         ProfScope ps(e, 2, 0, s);
         GatedResArgs g = gated_res_args(e, dm);
@@ -918,6 +970,11 @@ int run_forward(lt_engine* e, const void* x_in, const float* t_dev, void* out, c
     if (!e->perturb.empty())
         if (int rc = plan_perturbed(e, bp, pp)) return rc;
     auto perturbed = [&](int l) { return std::binary_search(e->perturb.begin(), e->perturb.end(), l); };
+    // blurred queries: the blocks in e->blur (ascending, disjoint from e->skip; e->perturb is empty then) blur their queries
+    BlurPlan bl;
+    if (!e->blur.empty())
+        if (int rc = plan_blurred(e, dm, bp, bl)) return rc;
+    auto blurred = [&](int l) { return std::binary_search(e->blur.begin(), e->blur.end(), l); };
     if (do_head) {  // first pre-norm: modulate(attention_norm(x), [shift,] scale) (model.py:599 / models.py:785 / lumina_t2i model.py:600)
         ProfScope ps(e, 2, 0, s);
         NormModArgs n;
@@ -932,7 +989,7 @@ int run_forward(lt_engine* e, const void* x_in, const float* t_dev, void* out, c
         return 0;
     }
     for (int l = do_blocks ? first : L; l < L; l = nx(l))
-        if (int rc = run_block(e, dm, bp, l, nx(l), t_dev, a, s, perturbed(l) ? &pp : nullptr)) return rc;
+        if (int rc = run_block(e, dm, bp, l, nx(l), t_dev, a, s, perturbed(l) ? &pp : nullptr, blurred(l) ? &bl : nullptr)) return rc;
     if (kind == LT_KIND_CACHE_BLOCKS) {  // step caching, second cut: r = bfr(x_L - x_0) for the evaluations that leave the stack out
         ProfScope ps(e, 2, 0, s);
         if (launch_cache_residual_store(e->x, e->c_x0, e->c_r, (long long)M * d, s)) return 1;
@@ -1048,6 +1105,53 @@ int SkipScope::set(const char* who, const int32_t* skip_host, int n_skip, const 
     return 0;
 }
 
+int check_blur_sets(const lt_engine* e, const char* who, const int32_t* skip_host, int n_skip, const int32_t* blur_host, int n_blur, float sigma) {
+    if (check_layer_set(e, who, "skip", skip_host, n_skip)) return 2;
+    LT_REQUIRE(n_skip < e->L, "%s: the skip set leaves no layer (all %d are in it)", who, e->L);
+    if (check_layer_set(e, who, "blur", blur_host, n_blur)) return 2;  // (may hold every layer)
+    for (int i = 0; i < n_blur; ++i)
+        for (int j = 0; j < n_skip; ++j)
+            LT_REQUIRE(blur_host[i] != skip_host[j], "%s: layer %d is in the skip set and in the blur set (the sets are disjoint)", who, blur_host[i]);
+    LT_REQUIRE(n_blur == 0 || sigma > 0.f, "%s: blur sigma %g is not positive (+inf is the mean query)", who, (double)sigma);
+    return 0;
+}
+
+int check_blur_radius(const lt_engine* e, const char* who, const lt_step_args* a, int n_blur, float sigma) {
+    if (n_blur <= 0) return 0;
+    float taps[2 * LT_SEG_MAX_RADIUS + 1];
+    int r = 0, mode = 0;
+    LT_REQUIRE(seg_taps_host(sigma, taps, &r, &mode) == 0, "%s: blur sigma %g is not positive (+inf is the mean query)", who, (double)sigma);
+    const int p = e->cfg.patch_size, Hp = p > 0 ? a->latent_h / p : 0, Wp = p > 0 ? a->latent_w / p : 0;
+    LT_REQUIRE(mode == 1 || r < std::min(Hp, Wp), "%s: blur radius %d (sigma %g) cannot be reflected on this call's grid of %d x %d image tokens "
+               "(radius <= min(rows, columns) - 1)", who, r, (double)sigma, Hp, Wp);
+    return 0;
+}
+
+int SkipScope::set_blur(const char* who, const int32_t* skip_host, int n_skip, const int32_t* blur_host, int n_blur) {
+    if (check_blur_sets(e, who, skip_host, n_skip, blur_host, n_blur, 1.f)) return 2;
+    e->skip.assign(skip_host, skip_host + n_skip);
+    std::sort(e->skip.begin(), e->skip.end());
+    e->blur.assign(blur_host, blur_host + n_blur);
+    std::sort(e->blur.begin(), e->blur.end());
+    return 0;
+}
+
+int ensure_blur(lt_engine* e, float sigma, hipStream_t s) {
+    float taps[2 * LT_SEG_MAX_RADIUS + 1] = {0.f};
+    int r = 0, mode = 0;
+    LT_REQUIRE(seg_taps_host(sigma, taps, &r, &mode) == 0, "blurred queries: sigma %g is not positive", (double)sigma);
+    void* q = nullptr;
+    if (!e->q_blur) {  // (never read before the blur of the same layer wrote it)
+        if (dev_alloc(e, &q, (size_t)e->cfg.max_batch * e->cfg.max_tokens * e->d * sizeof(u16), false)) return 1;
+        e->q_blur = (u16*)q;
+    }
+    if (!e->blur_taps) { if (dev_alloc(e, &q, sizeof taps)) return 1; e->blur_taps = (float*)q; }
+    LT_CHECK_HIP(hipMemcpyAsync(e->blur_taps, taps, sizeof taps, hipMemcpyHostToDevice, s));
+    LT_CHECK_HIP(hipStreamSynchronize(s));  // taps is a stack temporary
+    e->blur_mode = mode; e->blur_radius = r;
+    return 0;
+}
+
 int refuse_profile_if_capturing(const lt_engine* e, hipStream_t s, const char* who) {
     if (!(e->prof_on && e->prof_mask)) return 0;
     LT_REQUIRE(!stream_capturing(s), "%s: refused on a stream under capture while lt_profile_enable is on (the profile brackets launches with "
@@ -1141,6 +1245,11 @@ static int forward_graphed_body(lt_engine* e, const void* x_in, const float* t_d
         const int32_t mark[2] = {-2, (int32_t)e->perturb.size()};
         key.insert(key.end(), (const char*)mark, (const char*)(mark + 2));
         key.insert(key.end(), (const char*)e->perturb.data(), (const char*)(e->perturb.data() + e->perturb.size()));
+    }
+    if (!e->blur.empty()) {  // the layers with blurred queries, behind a mark of their own, with what sigma stands for but the taps
+        const int32_t mark[4] = {-4, (int32_t)e->blur.size(), (int32_t)e->blur_mode, (int32_t)e->blur_radius};
+        key.insert(key.end(), (const char*)mark, (const char*)(mark + 4));
+        key.insert(key.end(), (const char*)e->blur.data(), (const char*)(e->blur.data() + e->blur.size()));
     }
     if (e->rule_form != 0 && kind == LT_KIND_RULE) {  // a projected form: other closing kernels.  Form 0: the key of always
         const int32_t mark[2] = {-3, (int32_t)e->rule_form};
@@ -1656,6 +1765,22 @@ extern "C" int lt_forward_skip(lt_engine* e, const void* x_dev, const float* t_d
 extern "C" int lt_forward_perturb(lt_engine* e, const void* x_dev, const float* t_dev, void* out_dev, const lt_step_args* a, const int32_t* skip_host,
                                   int32_t n_skip, const int32_t* perturb_host, int32_t n_perturb, void* stream) {
     return forward_sets(e, "lt_forward_perturb", x_dev, t_dev, out_dev, a, skip_host, n_skip, perturb_host, n_perturb, stream);
+}
+
+// lt_forward with the blocks of S left out and the blocks of Q run on blurred queries.  Both sets empty: lt_forward, capturable as it is
+extern "C" int lt_forward_blur(lt_engine* e, const void* x_dev, const float* t_dev, void* out_dev, const lt_step_args* a, const int32_t* skip_host,
+                               int32_t n_skip, const int32_t* blur_host, int32_t n_blur, float sigma, void* stream) {
+    const char* who = "lt_forward_blur";
+    LT_REQUIRE(e && x_dev && t_dev && out_dev && a, "%s: null argument", who);
+    if (check_blur_sets(e, who, skip_host, n_skip, blur_host, n_blur, sigma)) return 2;
+    if ((n_skip > 0 || n_blur > 0) && refuse_if_capturing((hipStream_t)stream, who)) return 2;
+    LT_REQUIRE(n_blur == 0 || e->reg_Y == 0, "%s: a regional prompt is prepared (lt_prepare_prompt_regional): blurred queries do not serve it", who);
+    if (check_blur_radius(e, who, a, n_blur, sigma)) return 2;
+    if (n_blur > 0 && ensure_blur(e, sigma, (hipStream_t)stream)) return 1;
+    SkipScope scope(e);
+    if (scope.set_blur(who, skip_host, n_skip, blur_host, n_blur)) return 2;
+    LtOptScope opt_scope(&e->opts);
+    return forward_graphed(e, x_dev, t_dev, out_dev, a, 0, (hipStream_t)stream);
 }
 
 extern "C" int lt_forward_packed(lt_engine* e, const void* const* x_ptrs, const int32_t* hw_host, const float* t_dev,

@@ -54,6 +54,7 @@ struct GuidancePlan {
     const float* slg = nullptr;      // LT_PLAN_SLG: one scale s per evaluation; the blocks left out and the blocks perturbed;
     const int32_t *skip = nullptr, *perturb = nullptr; int n_skip = 0, n_perturb = 0;
     bool pag = false;                // ... the entry that takes both sets, either of which may be empty
+    const int32_t* blur = nullptr; int n_blur = 0; float blur_sigma = 0.f;  // ... smoothed-energy guidance: the blocks run on blurred queries
     int project_form = 0;            // projected: the form as the caller passed it (checked behind the shape), { eta, beta, r }, and
     float par[3] = {0.f, 0.f, 0.f}; int zero_init = 0;  // ... the intervals of zero velocity at the start
     CacheControl* cache = nullptr;   // LT_PLAN_CACHED
@@ -64,6 +65,11 @@ struct GuidancePlan {
     static GuidancePlan of_slg(const float* table, const float* slg, const int32_t* skip, int n_skip, const int32_t* perturb, int n_perturb, bool pag) {
         GuidancePlan p = of_table(table);
         p.form = LT_PLAN_SLG; p.slg = slg; p.skip = skip; p.n_skip = n_skip; p.perturb = perturb; p.n_perturb = n_perturb; p.pag = pag;
+        return p;
+    }
+    static GuidancePlan of_seg(const float* table, const float* seg, const int32_t* skip, int n_skip, const int32_t* blur, int n_blur, float sigma) {
+        GuidancePlan p = of_slg(table, seg, skip, n_skip, nullptr, 0, true);
+        p.blur = blur; p.n_blur = n_blur; p.blur_sigma = sigma;
         return p;
     }
     static GuidancePlan of_project(const float* table, bool apg, int form_passed, float eta, float beta, float r, int zero_init) {

@@ -175,6 +175,15 @@ int launch_v_transpose(const u16* src, int ld_src, int col0, u16* dst, int B, in
 // perturbed attention (attention_identity.hip): out[b, n, h, :] = V[b, n, h / (H / Hkv), :], the V columns of the row-major QKV buffer
 // copied word for word into [B * N][H * hd], row-major or (out_pair) in the row-pair-interleaved layout the O projection reads
 int launch_attention_identity(const u16* src, int ld_src, int col0, u16* out, int B, int N, int H, int Hkv, int hd, int out_pair, hipStream_t stream);
+// smoothed-energy guidance (query_blur.hip): the separable 2-D blur of the post-RoPE query image q[B, H, N, hd] over the token grid
+// (grid_w tokens per grid row, the first blur_w of them image tokens, the rest copied) into `out`, a second buffer.  taps: 2 * radius + 1 fp32
+// words on the device (mode 0); mode 1: every image token becomes the mean.  Refusals by name before the launch
+int launch_query_blur(const u16* q, u16* out, const float* taps, int B, int H, int N, int hd, int grid_w, int blur_w, int radius, int mode,
+                      hipStream_t stream);
+// what a blur width sigma stands for (transport/guidance.py: seg_taps, word for word): mode 1 at +inf; else mode 0, radius min(ceil(3 sigma),
+// LT_SEG_MAX_RADIUS) and the 2 r + 1 taps - the Gaussian in float64, summed from k = -r upward, every tap divided by the sum and rounded once
+// to fp32.  Non-zero: sigma is not positive (or NaN); nothing written.  Host only
+int seg_taps_host(float sigma, float* taps, int* radius, int* mode);
 // the three passes above in one launch (engine path)
 struct QkvPostArgs {
     QkPostArgs q, k;

@@ -407,6 +407,19 @@ extern "C" int lt_op_attention_identity(const void* src, int32_t ld_src, int32_t
     return launch_attention_identity((const u16*)src, ld_src, col0, (u16*)out, B, N, H, Hkv, hd, out_pair, (hipStream_t)stream);
 }
 
+extern "C" int lt_op_query_blur(const void* q, void* out, const float* taps_dev, int32_t B, int32_t H, int32_t N, int32_t hd, int32_t grid_w,
+                                int32_t blur_w, int32_t radius, int32_t mode, void* stream) {
+    return launch_query_blur((const u16*)q, (u16*)out, taps_dev, B, H, N, hd, grid_w, blur_w, radius, mode, (hipStream_t)stream);
+}
+
+extern "C" int lt_op_seg_taps(float sigma, float* taps_host, int32_t* radius, int32_t* mode) {
+    LT_REQUIRE(taps_host && radius && mode, "lt_op_seg_taps: null argument");
+    int r = 0, m = 0;
+    if (seg_taps_host(sigma, taps_host, &r, &m)) { lt_set_error("lt_op_seg_taps: sigma %g is not positive", (double)sigma); return 2; }
+    *radius = r; *mode = m;
+    return 0;
+}
+
 extern "C" int lt_op_attention(const void* q, const void* k, const void* vt, const float* bias, void* out, const void* gate,
                                int32_t accumulate, int32_t B, int32_t H, int32_t Hkv, int32_t N, int32_t Nk, int32_t Nkpad,
                                int32_t hd, float scale, int32_t k_prescaled, void* stream) {

@@ -100,7 +100,8 @@ int forward_slg_pair(lt_engine* e, const char* who, const GuidancePlan& sets, co
                      hipStream_t s, LtEvalKind closing, const float* closing_scale, const float* s_dev) {
     {
         SkipScope scope(e);
-        if (scope.set(who, sets.skip, sets.n_skip, sets.perturb, sets.n_perturb)) return 2;
+        if (sets.n_blur > 0 ? scope.set_blur(who, sets.skip, sets.n_skip, sets.blur, sets.n_blur)  // (the entry point has run ensure_blur)
+                            : scope.set(who, sets.skip, sets.n_skip, sets.perturb, sets.n_perturb)) return 2;
         if (int rc = forward_graphed(e, x, t, nullptr, a, 1, s, {LT_KIND_SLG_STORE, nullptr, e->g_cfg})) return rc;
     }
     if (s_dev) LT_CHECK_HIP(hipMemcpyAsync(e->g_cfg + 3, s_dev, sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -500,11 +501,15 @@ int sample_cfg_table(lt_engine* e, const char* who, const void* z_dev, void* tra
         for (int i = 0; i < ncalls; ++i)
             LT_REQUIRE(std::isfinite(plan.slg[i]), "%s: the skip-layer scale of stage %d of interval %d is not finite", who, i % stages, i / stages);
         if (check_layer_sets(e, who, plan.skip, plan.n_skip, plan.perturb, plan.n_perturb)) return 2;
-        if (plan.pag && plan.n_skip == 0 && plan.n_perturb == 0)
+        if (check_blur_sets(e, who, plan.skip, plan.n_skip, plan.blur, plan.n_blur, plan.blur_sigma)) return 2;
+        if (check_blur_radius(e, who, a, plan.n_blur, plan.blur_sigma)) return 2;  // (before the first stage, whatever its scale)
+        LT_REQUIRE(plan.n_blur == 0 || e->reg_Y == 0, "%s: a regional prompt is prepared (lt_prepare_prompt_regional): blurred queries do not serve it", who);
+        if (plan.pag && plan.n_skip == 0 && plan.n_perturb == 0 && plan.n_blur == 0)
             for (int i = 0; i < ncalls; ++i)
                 LT_REQUIRE(plan.slg[i] == 0.0f, "%s: both layer sets are empty, and stage %d of interval %d has a non-zero scale: the third "
                            "prediction would be the conditional one", who, i % stages, i / stages);
         if (ensure_skip_buf(e)) return 1;
+        if (plan.n_blur > 0 && ensure_blur(e, plan.blur_sigma, s)) return 1;
     }
     ProjectScope form_scope(e, plan.project_form);
     return ode_fixed_grid(e, {z_dev, traj_dev, final_dev, tgrid_host, n_grid, 1, t_round, a, s, dense_elems(e, a), nullptr, method}, plan, nullptr);
@@ -619,30 +624,52 @@ extern "C" int lt_sample_ode_cfg_pag(lt_engine* e, const void* z_dev, void* traj
                             GuidancePlan::of_slg(cfg_host, pag_host, skip_host, n_skip, perturb_host, n_perturb, true), t_round, a, (hipStream_t)stream);
 }
 
+// ---- smoothed-energy guidance: the third prediction runs the blocks of Q on Gaussian-blurred queries ----------------------------
+extern "C" int lt_sample_ode_cfg_seg(lt_engine* e, const void* z_dev, void* traj_dev, void* final_dev, const float* tgrid_host, int32_t n_grid,
+                                     int32_t method, const float* cfg_host, const float* seg_host, const int32_t* skip_host, int32_t n_skip,
+                                     const int32_t* blur_host, int32_t n_blur, float sigma, int32_t t_round, const lt_step_args* a, void* stream) {
+    return sample_cfg_table(e, "lt_sample_ode_cfg_seg", z_dev, traj_dev, final_dev, tgrid_host, n_grid, method,
+                            GuidancePlan::of_seg(cfg_host, seg_host, skip_host, n_skip, blur_host, n_blur, sigma), t_round, a, (hipStream_t)stream);
+}
+
 // One guided evaluation at (cfg_scale, slg_scale): the degraded evaluation of the cond rows - the blocks of S left out, the blocks of P
 // perturbed - then all rows (the cond rows alone at cfg_scale 1 exactly).  slg_scale 0: lt_forward_cfg at cfg_scale.  The scales reach the
 // engine's fixed device words through a launch in front.  pag: lt_forward_cfg_pag (both sets, either may be empty, not both at a scale != 0)
+// seg: lt_forward_cfg_seg - the blur set at width sigma in place of the perturb set
 static int forward_cfg_sets(lt_engine* e, const char* who, bool pag, const void* x_dev, const float* t_dev, void* out_dev, float cfg_scale,
                             float slg_scale, const int32_t* skip_host, int32_t n_skip, const int32_t* perturb_host, int32_t n_perturb,
-                            const lt_step_args* a, void* stream) {
+                            const lt_step_args* a, void* stream, const int32_t* blur_host = nullptr, int32_t n_blur = 0, float sigma = 0.f,
+                            bool seg = false) {
     hipStream_t s = (hipStream_t)stream;
     LT_REQUIRE(e && x_dev && t_dev && out_dev && a, "%s: null argument", who);
     if (refuse_if_capturing(s, who)) return 2;  // (the first call allocates the skip buffer)
     LtOptScope opt_scope(&e->opts);
     if (check_step_shape(e, who, a)) return 2;
     LT_REQUIRE(std::isfinite(cfg_scale), "%s: the scale is not finite", who);
-    LT_REQUIRE(std::isfinite(slg_scale), "%s: the %s scale is not finite", who, pag ? "perturbed-attention" : "skip-layer");
+    LT_REQUIRE(std::isfinite(slg_scale), "%s: the %s scale is not finite", who, seg ? "smoothed-energy" : pag ? "perturbed-attention" : "skip-layer");
     if (check_guided_halves(e, who, a)) return 2;
     if (check_layer_sets(e, who, skip_host, n_skip, perturb_host, n_perturb)) return 2;
-    LT_REQUIRE(!pag || n_skip > 0 || n_perturb > 0 || slg_scale == 0.f, "%s: both layer sets are empty at a non-zero scale: the third prediction "
+    if (seg && check_blur_sets(e, who, skip_host, n_skip, blur_host, n_blur, sigma)) return 2;
+    if (seg && check_blur_radius(e, who, a, n_blur, sigma)) return 2;
+    LT_REQUIRE(n_blur == 0 || e->reg_Y == 0, "%s: a regional prompt is prepared (lt_prepare_prompt_regional): blurred queries do not serve it", who);
+    LT_REQUIRE(!pag || n_skip > 0 || n_perturb > 0 || n_blur > 0 || slg_scale == 0.f, "%s: both layer sets are empty at a non-zero scale: the third prediction "
                "would be the conditional one", who);
     lt_step_args own = *a;
     own.cfg_scale = cfg_scale;
     if (slg_scale == 0.f) return forward_graphed(e, x_dev, t_dev, out_dev, &own, 1, s);  // lt_forward_cfg's launches and result
     if (ensure_skip_buf(e)) return 1;
+    if (n_blur > 0 && ensure_blur(e, sigma, s)) return 1;
     if (launch_slg_params_store(e->g_cfg, cfg_scale, slg_scale, s)) return 1;
-    return forward_slg_pair(e, who, GuidancePlan::of_slg(nullptr, nullptr, skip_host, n_skip, perturb_host, n_perturb, pag), x_dev, t_dev, out_dev, &own, s,
-                            cfg_scale == 1.0f ? LT_KIND_SLG_COND : LT_KIND_SLG_GUIDED, e->g_cfg, nullptr);
+    const GuidancePlan sets = seg ? GuidancePlan::of_seg(nullptr, nullptr, skip_host, n_skip, blur_host, n_blur, sigma)
+                                  : GuidancePlan::of_slg(nullptr, nullptr, skip_host, n_skip, perturb_host, n_perturb, pag);
+    return forward_slg_pair(e, who, sets, x_dev, t_dev, out_dev, &own, s, cfg_scale == 1.0f ? LT_KIND_SLG_COND : LT_KIND_SLG_GUIDED, e->g_cfg, nullptr);
+}
+
+extern "C" int lt_forward_cfg_seg(lt_engine* e, const void* x_dev, const float* t_dev, void* out_dev, float cfg_scale, float seg_scale,
+                                  const int32_t* skip_host, int32_t n_skip, const int32_t* blur_host, int32_t n_blur, float sigma, const lt_step_args* a,
+                                  void* stream) {
+    return forward_cfg_sets(e, "lt_forward_cfg_seg", true, x_dev, t_dev, out_dev, cfg_scale, seg_scale, skip_host, n_skip, nullptr, 0, a, stream,
+                            blur_host, n_blur, sigma, true);
 }
 
 extern "C" int lt_forward_cfg_slg(lt_engine* e, const void* x_dev, const float* t_dev, void* out_dev, float cfg_scale, float slg_scale,

@@ -307,14 +307,26 @@ class DiTEngine:
 
     def forward(self, x: torch.Tensor, t: torch.Tensor, *, use_cfg: bool, cfg_scale: float = 1.0,
                 scale_factor: float = 1.0, scale_watershed: float = 1.0, base_seqlen: Optional[int] = None,
-                proportional_attn: bool = False, ntk_factor: float = 1.0, skip_layers=(), perturb_layers=()) -> torch.Tensor:
+                proportional_attn: bool = False, ntk_factor: float = 1.0, skip_layers=(), perturb_layers=(), blur_layers=(),
+                blur_sigma=None) -> torch.Tensor:
         """one evaluation; ``skip_layers`` (plain forward only): the blocks left out (lt_forward_skip); ``perturb_layers`` (plain
-        forward only): the blocks whose self-attention map is the identity (lt_forward_perturb); both empty: the call it was"""
+        forward only): the blocks whose self-attention map is the identity (lt_forward_perturb); ``blur_layers`` (plain forward only,
+        not beside ``perturb_layers``): the blocks whose self-attention reads queries blurred at width ``blur_sigma`` (lt_forward_blur, DESIGN
+        7t); all empty: the call it was"""
         x, t32, out = self._eval_io(x, t)
         a = self._step_args(x, cfg_scale, scale_factor, scale_watershed, base_seqlen, proportional_attn, ntk_factor=ntk_factor)
         skip = self._skip_array(skip_layers, "forward")
         perturb = self._skip_array(perturb_layers, "forward", "perturb")
-        if len(perturb):
+        blur = self._skip_array(blur_layers, "forward", "blur")
+        if len(blur):
+            if use_cfg:
+                raise LuminaLibError("forward: blur_layers belongs to the plain forward (guided: forward_cfg_seg)")
+            if len(perturb):
+                raise LuminaLibError("forward: blur_layers together with perturb_layers is not served")
+            if blur_sigma is None:
+                raise LuminaLibError("forward: blur_layers needs blur_sigma (> 0; inf: the mean query)")
+            name, layers = "lt_forward_blur", (skip, len(skip), blur, len(blur), float(blur_sigma))
+        elif len(perturb):
             if use_cfg:
                 raise LuminaLibError("forward: perturb_layers belongs to the plain forward (guided: forward_cfg_pag)")
             name, layers = "lt_forward_perturb", (skip, len(skip), perturb, len(perturb))
@@ -570,6 +582,27 @@ class DiTEngine:
                    perturb, len(perturb), C.byref(a), self._stream())
         return out
 
+    # ---- smoothed-energy guidance: the third prediction runs a set of blocks on Gaussian-blurred queries -----
+    def forward_cfg_seg(self, x: torch.Tensor, t: torch.Tensor, *, cfg_scale: float, seg_scale: float, seg_layers, seg_sigma: float,
+                        skip_layers=(), scale_factor: float = 1.0, scale_watershed: float = 1.0, base_seqlen: Optional[int] = None,
+                        proportional_attn: bool = False, ntk_factor: float = 1.0) -> torch.Tensor:
+        """one guided evaluation with smoothed-energy guidance (lt_forward_cfg_seg): ``u + w (c - u) + s (c - b)`` on the guided channels,
+        ``b`` the cond rows evaluated with the queries of the blocks ``seg_layers`` blurred at width ``seg_sigma`` (and ``skip_layers`` left
+        out).  ``seg_scale == 0`` is ``forward(use_cfg=True)``."""
+        x, t32, out = self._eval_io(x, t)
+        a = self._step_args(x, cfg_scale, scale_factor, scale_watershed, base_seqlen, proportional_attn, ntk_factor=ntk_factor)
+        skip = self._skip_array(skip_layers, "forward_cfg_seg")
+        blur = self._skip_array(seg_layers, "forward_cfg_seg", "blur")
+        self._call("lt_forward_cfg_seg", self._dev(x), self._dev(t32), self._dev(out), float(cfg_scale), float(seg_scale), skip, len(skip),
+                   blur, len(blur), float(seg_sigma), C.byref(a), self._stream())
+        return out
+
+    def sample_ode_cfg_seg(self, z: torch.Tensor, tgrid, table, seg, seg_layers, seg_sigma: float, method: str, *, skip_layers=(),
+                           **kw) -> torch.Tensor:
+        """``sample_ode_cfg_pag`` with the third prediction taken with the queries of the blocks ``seg_layers`` blurred at width ``seg_sigma``
+        (lt_sample_ode_cfg_seg).  ``transport.guidance.sample_cfg_seg`` is the definition."""
+        return self._sample_ode_cfg_third("sample_ode_cfg_seg", z, tgrid, table, seg, skip_layers, seg_layers, method, seg_sigma=seg_sigma, **kw)
+
     def sample_ode_cfg_pag(self, z: torch.Tensor, tgrid, table, pag, pag_layers, method: str, *, skip_layers=(), **kw) -> torch.Tensor:
         """``sample_ode_cfg_slg`` with the third prediction taken with the blocks ``pag_layers`` perturbed and ``skip_layers`` left out, under
         the one scale table ``pag`` (lt_sample_ode_cfg_pag).  ``transport.guidance.sample_cfg_pag`` is the definition."""
@@ -590,10 +623,13 @@ class DiTEngine:
     def _sample_ode_cfg_third(self, who: str, z, tgrid, table, third, skip_layers, pag_layers, method: str, *, scale_factor: float = 1.0,
                               scale_watershed: float = 1.0, base_seqlen: Optional[int] = None, proportional_attn: bool = False,
                               t_round_to_state_dtype: bool = True, return_trajectory: bool = True, ntk_factor: float = 1.0,
-                              cfg_scale=None) -> torch.Tensor:
+                              cfg_scale=None, seg_sigma=None) -> torch.Tensor:
         """the guided trajectory with a third prediction per stage under the scale table ``third``: the cond rows with ``skip_layers`` left
-        out (``pag_layers=None``: lt_sample_ode_cfg_slg) or, besides, ``pag_layers`` perturbed (lt_sample_ode_cfg_pag)"""
+        out (``pag_layers=None``: lt_sample_ode_cfg_slg) or, besides, ``pag_layers`` perturbed (lt_sample_ode_cfg_pag) or - ``seg_sigma``
+        given - run on queries blurred at that width (lt_sample_ode_cfg_seg)"""
         what, short = ("skip-layer guidance", "slg") if pag_layers is None else ("perturbed-attention guidance", "pag")
+        if seg_sigma is not None:
+            what, short = "smoothed-energy guidance", "seg"
         if isinstance(z, (list, tuple)):
             raise LuminaLibError(f"{who}: a packed batch (a list of latents) is not served")
         _require_gpu(z, "z")
@@ -609,8 +645,10 @@ class DiTEngine:
         out, traj_ptr, fin_ptr = _traj_or_final(z, max(n, 1), z.shape, return_trajectory)
         layers = (skip, len(skip))
         if pag_layers is not None:
-            perturb = self._skip_array(pag_layers, who, "perturb")
+            perturb = self._skip_array(pag_layers, who, "blur" if seg_sigma is not None else "perturb")
             layers += (perturb, len(perturb))
+        if seg_sigma is not None:
+            layers += (float(seg_sigma),)
         self._call(f"lt_sample_ode_cfg_{short}", self._dev(z), traj_ptr, fin_ptr, garr, n, code, self._host(tab), self._host(sl), *layers,
                    int(t_round_to_state_dtype), C.byref(a), self._stream())
         return out

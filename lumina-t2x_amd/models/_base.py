@@ -95,17 +95,23 @@ class EngineSamplers:
         return eng.sample_ode_masked(x, tgrid, mask, x1, noise, method, use_cfg=use_cfg, t_round_to_state_dtype=t_round, **args)
 
     def _engine_sample_ode_cfg_schedule(self, x, tgrid, method, t_round, table, kw, return_trajectory=True, rescale=0.0, norm_limit=math.inf,
-                                        reuse=None, slg=None, slg_layers=(), pag=None, pag_layers=(), apg=None, zero_star=False, zero_init=0):
+                                        reuse=None, slg=None, slg_layers=(), pag=None, pag_layers=(), apg=None, zero_star=False, zero_init=0,
+                                        seg=None, seg_layers=(), seg_sigma=None):
         """kwargs of forward_with_cfg -> lt_sample_ode_cfg_schedule (guidance schedules; ``cfg_scale`` in kw is ignored), or - with a
         rescale blend or a norm limit - lt_sample_ode_cfg_rule, or - with a reuse table - lt_sample_ode_cfg_reuse, or -
         with a table of skip-layer scales - lt_sample_ode_cfg_slg, or - with a table of perturbed-attention scales -
-        lt_sample_ode_cfg_pag (``slg_layers`` then join the same third prediction), or - with ``apg`` / ``zero_star`` -
-        lt_sample_ode_cfg_project"""
-        from ..transport.guidance import check_project, refuse_rule_with_reuse, refuse_with_pag, refuse_with_project, refuse_with_slg, rule_is_off
+        lt_sample_ode_cfg_pag (``slg_layers`` then join the same third prediction), or - with a table of smoothed-energy scales -
+        lt_sample_ode_cfg_seg (likewise), or - with ``apg`` / ``zero_star`` - lt_sample_ode_cfg_project"""
+        from ..transport.guidance import (check_project, refuse_rule_with_reuse, refuse_with_pag, refuse_with_project, refuse_with_seg,
+                                          refuse_with_slg, rule_is_off)
         packed = not isinstance(x, torch.Tensor)
         form = _refusing(check_project, apg, zero_star, zero_init)[0]
         _refusing(refuse_with_project, form, method=method, rescale=rescale, norm_limit=norm_limit, reuse=reuse, slg=slg, pag=pag, packed=packed)
+        if seg is not None and form is not None:
+            raise _lib.LuminaLibError("smoothed-energy guidance (a seg table) together with projected guidance is not served")
         companions = (
+            (seg, "smoothed-energy guidance",
+             lambda: refuse_with_seg(seg, method=method, rescale=rescale, norm_limit=norm_limit, reuse=reuse, slg=slg, pag=pag)),
             (pag, "perturbed-attention guidance",
              lambda: refuse_with_pag(pag, method=method, rescale=rescale, norm_limit=norm_limit, reuse=reuse, slg=slg)),
             (slg, "skip-layer guidance",
@@ -124,6 +130,11 @@ class EngineSamplers:
         if form is not None:
             return eng.sample_ode_cfg_project(x, tgrid, table, method, apg=apg, zero_star=zero_star, zero_init=zero_init,
                                               t_round_to_state_dtype=t_round, return_trajectory=return_trajectory, **args)
+        if seg is not None:
+            if seg_sigma is None:
+                raise _lib.LuminaLibError("smoothed-energy guidance: a seg table needs seg_sigma (> 0; inf: the mean query)")
+            return eng.sample_ode_cfg_seg(x, tgrid, table, seg, seg_layers, seg_sigma, method, skip_layers=slg_layers,
+                                          t_round_to_state_dtype=t_round, return_trajectory=return_trajectory, **args)
         if pag is not None:
             return eng.sample_ode_cfg_pag(x, tgrid, table, pag, pag_layers, method, skip_layers=slg_layers, t_round_to_state_dtype=t_round,
                                           return_trajectory=return_trajectory, **args)
@@ -148,7 +159,7 @@ class EngineSamplers:
     @torch.no_grad()
     def sample_ode_cfg_schedule(self, z, tgrid, table, *cond, method: str = "midpoint", return_trajectory: bool = False, rescale: float = 0.0,
                                 norm_limit: float = math.inf, reuse=None, slg=None, slg_layers=(), pag=None, pag_layers=(), apg=None,
-                                zero_star: bool = False, zero_init: int = 0, **step_kw):
+                                zero_star: bool = False, zero_init: int = 0, seg=None, seg_layers=(), seg_sigma=None, **step_kw):
         """A guided fixed-grid trajectory with a scale per stage in ONE engine call (lt_sample_ode_cfg_schedule): stage k of interval
         i evaluates ``forward_with_cfg`` at ``table[i * stages + k]``, or - at scale 1 exactly - the plain forward of the cond rows alone, at
         half the rows.  ``cond``: the family's conditioning as ``forward_with_cfg`` takes it (``cap_feats, cap_mask`` or ``y``) for all
@@ -164,6 +175,9 @@ class EngineSamplers:
         ``pag`` (one perturbed-attention scale per table entry; ``transport.guidance.pag_table``) with ``pag_layers``: the third prediction
         runs those blocks with the identity as their self-attention map - and ``slg_layers``, if given, left out - under the one table
         (lt_sample_ode_cfg_pag; an ``slg`` table beside a ``pag`` table is refused by name).
+        ``seg`` (one smoothed-energy scale per table entry; ``transport.guidance.seg_table``) with ``seg_layers`` and ``seg_sigma``: the third
+        prediction runs those blocks' self-attention on queries Gaussian-blurred over the token grid at that width (``inf``: the mean query) -
+        and ``slg_layers``, if given, left out (lt_sample_ode_cfg_seg; refused by name with what ``pag`` is refused with, and with ``pag``).
         ``apg=dict(eta=, momentum=, norm_threshold=)`` or ``zero_star=True`` (with ``zero_init=K``): the guided stages form their output by
         ``transport.guidance.guided_project`` - APG's momentum / norm clip / damped parallel part, or CFG-Zero*'s rescaled unconditional row
         with ``K`` intervals of zero velocity that evaluate nothing (lt_sample_ode_cfg_project; euler / midpoint / rk4; exclusive,
@@ -175,7 +189,8 @@ class EngineSamplers:
         self._mirror_attention_flags(kw)
         return self._engine_sample_ode_cfg_schedule(z, tgrid, method, True, table, kw, return_trajectory=return_trajectory, rescale=rescale,
                                                     norm_limit=norm_limit, reuse=reuse, slg=slg, slg_layers=slg_layers, pag=pag,
-                                                    pag_layers=pag_layers, apg=apg, zero_star=zero_star, zero_init=zero_init)
+                                                    pag_layers=pag_layers, apg=apg, zero_star=zero_star, zero_init=zero_init, seg=seg,
+                                                    seg_layers=seg_layers, seg_sigma=seg_sigma)
 
     @torch.no_grad()
     def sample_ode_teacache(self, z, tgrid, *cond, method: str = "euler", threshold: float = 0.0, coefficients=(0.0, 0.0, 0.0, 1.0, 0.0),
@@ -342,6 +357,16 @@ class EngineSamplers:
         kw = self._guided_kw("forward_with_cfg_slg", x, cond, step_kw, "by skip-layer guidance")
         eng, args = self._guided_engine("forward_with_cfg_slg", x, kw)
         return eng.forward_cfg_slg(x, t, slg_scale=slg_scale, slg_layers=slg_layers, **args)
+
+    @torch.no_grad()
+    def forward_with_cfg_seg(self, x, t, *cond, seg_scale: float = 0.0, seg_layers=(), seg_sigma: float = math.inf, skip_layers=(), **step_kw):
+        """``forward_with_cfg(x, t, <conditioning>, cfg_scale, **step_kw)`` with smoothed-energy guidance in ONE engine call
+        (lt_forward_cfg_seg): the cond rows are also evaluated with the blocks ``seg_layers`` run on queries blurred at width
+        ``seg_sigma`` (and ``skip_layers`` left out), prediction ``b``; the guided channels are ``u + cfg_scale (c - u) + seg_scale (c - b)``.
+        ``seg_scale == 0`` is ``forward_with_cfg``.  Tensor states only."""
+        kw = self._guided_kw("forward_with_cfg_seg", x, cond, step_kw, "by smoothed-energy guidance")
+        eng, args = self._guided_engine("forward_with_cfg_seg", x, kw)
+        return eng.forward_cfg_seg(x, t, seg_scale=seg_scale, seg_layers=seg_layers, seg_sigma=seg_sigma, skip_layers=skip_layers, **args)
 
     @torch.no_grad()
     def forward_with_cfg_pag(self, x, t, *cond, pag_scale: float = 0.0, pag_layers=(), skip_layers=(), **step_kw):

@@ -30,14 +30,18 @@ class NextDiT(_base.NextDiT):
         return eng
 
     @torch.no_grad()
-    def forward(self, x, t, cap_feats, cap_mask, global_cap_feats=None, global_cap_mask=None, h_split_num=1, w_split_num=1, skip_layers=(), perturb_layers=()):
+    def forward(self, x, t, cap_feats, cap_mask, global_cap_feats=None, global_cap_mask=None, h_split_num=1, w_split_num=1, skip_layers=(), perturb_layers=(),
+                blur_layers=(), blur_sigma=None):
         """reference models/model.py:852-899; ``skip_layers``: the plain Next-DiT call's (a regional prompt with a layer set is refused)"""
         if global_cap_feats is None:  # plain Next-DiT call
-            return super().forward(x, t, cap_feats, cap_mask, skip_layers=skip_layers, perturb_layers=perturb_layers)
+            return super().forward(x, t, cap_feats, cap_mask, skip_layers=skip_layers, perturb_layers=perturb_layers, blur_layers=blur_layers,
+                                   blur_sigma=blur_sigma)
         if len(tuple(skip_layers)):
             raise _base._lib.LuminaLibError("forward: skip_layers together with a regional prompt is not served")
         if len(tuple(perturb_layers)):
             raise _base._lib.LuminaLibError("forward: perturb_layers together with a regional prompt is not served")
+        if len(tuple(blur_layers)):
+            raise _base._lib.LuminaLibError("forward: blur_layers together with a regional prompt is not served")
         eng = self._regional_engine(x, cap_feats, cap_mask, global_cap_feats, global_cap_mask, h_split_num, w_split_num)
         pa = self.layers[0].attention.proportional_attn if self.n_layers else False
         bs = self.layers[0].attention.base_seqlen if self.n_layers else None

@@ -99,12 +99,14 @@ class DiT_Llama(EngineBackedModel):
         return eng, dict(scale_factor=self.rope_scaling_factor, ntk_factor=self.ntk_factor, **args)
 
     @torch.no_grad()
-    def forward(self, x, t, cap_feats, cap_mask, skip_layers=(), perturb_layers=()):
+    def forward(self, x, t, cap_feats, cap_mask, skip_layers=(), perturb_layers=(), blur_layers=(), blur_sigma=None):
         """reference model.py:829-864.  ``skip_layers`` (not in the reference): the blocks left out of this evaluation (lt_forward_skip,
-        DESIGN 7m); empty: the call it was"""
+        DESIGN 7m); ``blur_layers`` with ``blur_sigma``: the blocks run on blurred queries (lt_forward_blur; the end-of-line
+        tokens are no part of the image); empty: the call it was"""
         a = self.layers[0].attention if self.n_layers else None
         return self._call(x, t, cap_feats, cap_mask, False, proportional_attn=bool(a and a.proportional_attn),
-                          base_seqlen=a.base_seqlen if a else None, skip_layers=tuple(skip_layers), perturb_layers=tuple(perturb_layers))
+                          base_seqlen=a.base_seqlen if a else None, skip_layers=tuple(skip_layers), perturb_layers=tuple(perturb_layers),
+                          blur_layers=tuple(blur_layers), blur_sigma=blur_sigma)
 
     @torch.no_grad()
     def forward_with_cfg(self, x, t, cap_feats, cap_mask, cfg_scale, rope_scaling_factor=None, ntk_factor=None,

@@ -107,11 +107,11 @@ class DiT_Llama(EngineBackedModel):
 
     _cond_names = ("y",)
 
-    def _call(self, x, t, y, use_cfg, cfg_scale=1.0, skip_layers=(), perturb_layers=()):
+    def _call(self, x, t, y, use_cfg, cfg_scale=1.0, skip_layers=(), perturb_layers=(), blur_layers=(), blur_sigma=None):
         eng = self.engine(x)
         eng.prepare_labels(y)
         return eng.forward(x, t, use_cfg=use_cfg, cfg_scale=cfg_scale, scale_factor=self._rope[0], ntk_factor=self._rope[1],
-                           skip_layers=skip_layers, perturb_layers=perturb_layers)
+                           skip_layers=skip_layers, perturb_layers=perturb_layers, blur_layers=blur_layers, blur_sigma=blur_sigma)
 
     def _engine_sampler_args(self, x, use_cfg, kw):
         """transport fast paths (models/_base.py: EngineSamplers): kwargs of forward_with_cfg / forward -> engine + step kwargs"""
@@ -128,10 +128,11 @@ class DiT_Llama(EngineBackedModel):
         return eng, dict(cfg_scale=cfg_scale, scale_factor=self._rope[0], ntk_factor=self._rope[1])
 
     @torch.no_grad()
-    def forward(self, x, t, y, skip_layers=(), perturb_layers=()):
+    def forward(self, x, t, y, skip_layers=(), perturb_layers=(), blur_layers=(), blur_sigma=None):
         """reference models.py:920-944.  ``skip_layers`` (not in the reference): the blocks left out of this evaluation (lt_forward_skip,
-        DESIGN 7m); empty: the call it was"""
-        return self._call(x, t, y, False, skip_layers=tuple(skip_layers), perturb_layers=tuple(perturb_layers))
+        DESIGN 7m); ``blur_layers`` with ``blur_sigma``: the blocks run on blurred queries (lt_forward_blur); empty: the call it was"""
+        return self._call(x, t, y, False, skip_layers=tuple(skip_layers), perturb_layers=tuple(perturb_layers),
+                          blur_layers=tuple(blur_layers), blur_sigma=blur_sigma)
 
     @torch.no_grad()
     def forward_with_cfg(self, x, t, y, cfg_scale, rope_scaling_factor=None, ntk_factor=None):

@@ -225,11 +225,20 @@ def run(args, *, encode_fn=None, cap_feat_dim=None, decode_fn=None, model=None) 
         rule = guidance_rule(args)
         reuse = guidance_reuse(args, sample_fn.__self__.t, table)
         pag = guidance_pag(args, sample_fn.__self__.t)
-        slg = None if pag is not None else guidance_slg(args, sample_fn.__self__.t)
+        seg = guidance_seg(args, sample_fn.__self__.t)
+        slg = None if (pag is not None or seg is not None) else guidance_slg(args, sample_fn.__self__.t)
         tea = step_cache(args)
         proj = guidance_project(args)
         comp = compose_plan(args, sample_fn.__self__.t)
-        if comp:  # composed guidance: the K prompts of --compose_prompts stand in for the caption, the negative prompt is the base row
+        if seg is not None:  # a third evaluation of the prompt row with some blocks' queries blurred; with the scale table and --slg_layers alone
+            if comp or tile or proj or tea or pag is not None:
+                raise SystemExit("--seg_layers is not served together with --compose_prompts, --tile, --apg_* / --cfg_zero_star, --teacache or --pag_*")
+            if table is None:
+                from .transport import guidance
+                table = guidance.cfg_table(sample_fn.__self__.t, args.sampling_method, args.cfg_scale)
+            latent = sample_fn(z, model.forward_with_cfg, cfg_table=table, seg_table=seg, seg_layers=list(args.seg_layers),
+                               seg_sigma=float(args.seg_sigma), slg_layers=list(getattr(args, "slg_layers", None) or []), **kw)[-1][:1]
+        elif comp:  # composed guidance: the K prompts of --compose_prompts stand in for the caption, the negative prompt is the base row
             if tile or table is not None or rule or reuse is not None or pag is not None or slg is not None or tea or proj:
                 raise SystemExit("--compose_prompts is not served together with --tile, --cfg_interval / --cfg_schedule, --cfg_rescale / "
                                  "--cfg_norm_limit, --cfg_reuse*, --slg_*, --pag_*, --teacache, --apg_* or --cfg_zero_star")
@@ -372,6 +381,40 @@ def guidance_slg(args, tgrid):
         raise SystemExit(f"--slg_*: {exc}") from None
 
 
+def guidance_seg(args, tgrid):
+    """``--seg_layers`` / ``--seg_scale`` / ``--seg_sigma`` / ``--seg_interval`` as the table of ``transport.guidance.seg_table``; None at the
+    defaults (no layers, or scale 0): the call it was.  ``--slg_layers`` beside it joins the same third evaluation under this one table.  Refused
+    by name with what ``--pag_*`` is refused with, and with ``--pag_*``."""
+    layers, scale = list(getattr(args, "seg_layers", None) or []), float(getattr(args, "seg_scale", 0.0) or 0.0)
+    interval, sigma = getattr(args, "seg_interval", None), getattr(args, "seg_sigma", None)
+    if not layers and scale == 0.0 and interval is None and sigma is None:
+        return None
+    if not layers:
+        raise SystemExit("--seg_scale / --seg_sigma / --seg_interval need --seg_layers: the blocks whose queries the third evaluation blurs")
+    if getattr(args, "pag_layers", None) or float(getattr(args, "pag_scale", 0.0) or 0.0) != 0.0 or getattr(args, "pag_interval", None) is not None:
+        raise SystemExit("--seg_layers together with --pag_* is not served: one third evaluation, and no block is blurred and perturbed")
+    if float(getattr(args, "slg_scale", 0.0) or 0.0) != 0.0 or getattr(args, "slg_interval", None) is not None:
+        raise SystemExit("--seg_layers together with --slg_scale / --slg_interval is not served: one third evaluation, one scale table "
+                         "(--slg_layers beside --seg_layers joins it under --seg_scale)")
+    if guidance_rule(args):
+        raise SystemExit("--seg_layers is not served together with --cfg_rescale / --cfg_norm_limit")
+    if int(getattr(args, "cfg_reuse", 0) or 0) != 0 or bool(getattr(args, "cfg_reuse_per_step", False)):
+        raise SystemExit("--seg_layers is not served together with --cfg_reuse / --cfg_reuse_per_step")
+    from .transport import guidance
+    if args.sampling_method not in guidance.FIXED_GRID_METHODS:
+        raise SystemExit(f"--seg_layers is built for the sampling methods {', '.join(guidance.FIXED_GRID_METHODS)}, not '{args.sampling_method}'")
+    if sigma is None:
+        raise SystemExit("--seg_layers needs --seg_sigma: the width of the blur in tokens (> 0; inf: the mean query)")
+    try:
+        guidance.check_seg_layers(layers, list(getattr(args, "slg_layers", None) or []))
+        guidance.seg_taps(sigma)
+        if scale == 0.0:
+            return None
+        return guidance.seg_table(tgrid, args.sampling_method, scale, interval=interval)
+    except ValueError as exc:
+        raise SystemExit(f"--seg_*: {exc}") from None
+
+
 def guidance_pag(args, tgrid):
     """``--pag_layers`` / ``--pag_scale`` / ``--pag_interval`` as the table of ``transport.guidance.pag_table``; None at the defaults (no layers,
     or scale 0): the call it was.  ``--slg_layers`` beside it joins the same third evaluation (those blocks are left out) under this one table;
@@ -467,6 +510,15 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--pag_scale", type=float, default=0.0, metavar="S",
                    help="... whose prediction the guided output is pushed away from: + S * (prompt row - perturbed row) (0: off)")
     p.add_argument("--pag_interval", type=float, nargs=2, default=None, metavar=("LO", "HI"),
+                   help="... on the stages with LO <= t < HI only (t = 0 noise, 1 data; default: all stages)")
+    p.add_argument("--seg_layers", type=int, nargs="+", default=None, metavar="L",
+                   help="smoothed-energy guidance: the blocks a third evaluation of the prompt row runs on Gaussian-blurred queries "
+                        "(default: off; --slg_layers beside it: blocks the same evaluation leaves out)")
+    p.add_argument("--seg_scale", type=float, default=0.0, metavar="S",
+                   help="... whose prediction the guided output is pushed away from: + S * (prompt row - blurred row) (0: off)")
+    p.add_argument("--seg_sigma", type=float, default=None, metavar="SIGMA",
+                   help="... the width of the blur over the token grid, in tokens (> 0; inf: every query becomes the mean query)")
+    p.add_argument("--seg_interval", type=float, nargs=2, default=None, metavar=("LO", "HI"),
                    help="... on the stages with LO <= t < HI only (t = 0 noise, 1 data; default: all stages)")
     p.add_argument("--teacache", type=float, default=None, metavar="THR",
                    help="step caching (the TeaCache rule): leave the block stack out of an evaluation while the accumulated relative change of its "

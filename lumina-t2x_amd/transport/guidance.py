@@ -559,32 +559,32 @@ def sample_cfg_reuse_multistep(model, z, tgrid, table, reuse, method="abm2", *, 
 
 
 # ---- skip-layer guidance: a third prediction with a set of blocks left out, pushed away from -----------------------------------
-def slg_table(tgrid, method, slg_scale, interval=None):
+def slg_table(tgrid, method, slg_scale, interval=None, what="skip-layer"):
     """The fp32 table of skip-layer scales of a trajectory, one per evaluation: ``slg_scale`` where ``lo <= t_stage < hi`` for
     ``interval = (lo, hi)`` (default: everywhere), 0 elsewhere.  ``t_stage`` is the UNROUNDED fp32 stage time, as in ``cfg_table``; an empty
     interval (``lo == hi``) gives all zeros."""
     ts = stage_times(tgrid, method, th.float32, False).tolist()
     lo, hi = (-math.inf, math.inf) if interval is None else (float(interval[0]), float(interval[1]))
     if not lo <= hi:
-        raise ValueError(f"skip-layer interval [{lo}, {hi}) is not ordered")
+        raise ValueError(f"{what} interval [{lo}, {hi}) is not ordered")
     table = th.tensor([float(slg_scale) if lo <= t < hi else 0.0 for t in ts], dtype=th.float32)
     if not bool(th.isfinite(table).all()):
-        raise ValueError("skip-layer table has an entry that is not finite")
+        raise ValueError(f"{what} table has an entry that is not finite")
     return table
 
 
-def check_slg(slg, tgrid, method):
+def check_slg(slg, tgrid, method, what="skip-layer"):
     """``slg`` as an fp32 CPU tensor of ``(len(tgrid) - 1) * stages`` finite entries"""
     stages = _check_method(method)
     n = len(_grid32(tgrid))
     if slg is None:
-        raise ValueError("skip-layer table is None (one scale per evaluation; slg_table builds one)")
+        raise ValueError(f"{what} table is None (one scale per evaluation; slg_table builds one)")
     t = slg if isinstance(slg, th.Tensor) else th.tensor(list(slg), dtype=th.float32)
     t = t.detach().to("cpu", th.float32).reshape(-1).contiguous()
     if t.numel() != (n - 1) * stages:
-        raise ValueError(f"skip-layer table has {t.numel()} entries, a {n}-point {method} grid has {(n - 1) * stages} stages")
+        raise ValueError(f"{what} table has {t.numel()} entries, a {n}-point {method} grid has {(n - 1) * stages} stages")
     if not bool(th.isfinite(t).all()):
-        raise ValueError("skip-layer table has an entry that is not finite")
+        raise ValueError(f"{what} table has an entry that is not finite")
     return t
 
 
@@ -714,23 +714,17 @@ def sample_cfg_slg(model, z, tgrid, table, slg, slg_layers, method="euler", *, c
 def pag_table(tgrid, method, pag_scale, interval=None):
     """The fp32 table of perturbed-attention scales of a trajectory, one per evaluation: ``slg_table``'s rule - ``pag_scale`` where
     ``lo <= t_stage < hi`` for ``interval = (lo, hi)`` (default: everywhere), 0 elsewhere, on the unrounded fp32 stage times"""
-    try:
-        return slg_table(tgrid, method, pag_scale, interval=interval)
-    except ValueError as exc:
-        raise ValueError(str(exc).replace("skip-layer", "perturbed-attention")) from None
+    return slg_table(tgrid, method, pag_scale, interval=interval, what="perturbed-attention")
 
 
 def check_pag(pag, tgrid, method):
     """``pag`` as an fp32 CPU tensor of ``(len(tgrid) - 1) * stages`` finite entries"""
     if pag is None:
         raise ValueError("perturbed-attention table is None (one scale per evaluation; pag_table builds one)")
-    try:
-        return check_slg(pag, tgrid, method)
-    except ValueError as exc:
-        raise ValueError(str(exc).replace("skip-layer", "perturbed-attention")) from None
+    return check_slg(pag, tgrid, method, what="perturbed-attention")
 
 
-def check_pag_layers(pag_layers, skip_layers=(), n_layers=None):
+def check_pag_layers(pag_layers, skip_layers=(), n_layers=None, name="perturb"):
     """-> (perturb set, skip set) as lists of ints.  Refused: an entry that is no integer, a repeated index, an index in both sets, and -
     when the depth is known - an index outside ``0 .. n_layers - 1`` and a SKIP set that leaves no layer (the perturb set may hold every
     layer): what the engine refuses"""
@@ -738,36 +732,37 @@ def check_pag_layers(pag_layers, skip_layers=(), n_layers=None):
     out = []
     for v in (pag_layers.reshape(-1).tolist() if isinstance(pag_layers, th.Tensor) else list(pag_layers if pag_layers is not None else ())):
         if isinstance(v, bool) or int(v) != v:
-            raise ValueError(f"perturb layer {v!r} is not an integer index")
+            raise ValueError(f"{name} layer {v!r} is not an integer index")
         if int(v) in out:
-            raise ValueError(f"perturb index {int(v)} is repeated")
+            raise ValueError(f"{name} index {int(v)} is repeated")
         if n_layers is not None and not 0 <= int(v) < n_layers:
-            raise ValueError(f"perturb index {int(v)} is outside 0..{n_layers - 1}")
+            raise ValueError(f"{name} index {int(v)} is outside 0..{n_layers - 1}")
         if int(v) in skip:
-            raise ValueError(f"layer {int(v)} is in the skip set and in the perturb set (the sets are disjoint)")
+            raise ValueError(f"layer {int(v)} is in the skip set and in the {name} set (the sets are disjoint)")
         out.append(int(v))
     return out, skip
 
 
-def refuse_with_pag(pag, method="euler", rescale=0.0, norm_limit=math.inf, reuse=None, slg=None, teacache=None, mask=None):
+def refuse_with_pag(pag, method="euler", rescale=0.0, norm_limit=math.inf, reuse=None, slg=None, teacache=None, mask=None,
+                    what="perturbed-attention guidance", table="a pag table", layers="pag_layers"):
     """what perturbed-attention guidance is not served with, by name: the companions skip-layer guidance refuses - a rescale / norm-limit rule,
     a reuse table, a method that is not fixed-grid (multistep and adaptive solvers), step caching, an inpainting mask - and a second scale
     table (``slg`` beside ``pag``: the skip set joins the ONE third prediction under the ``pag`` table)"""
     if pag is None:
         return
     if slg is not None:
-        raise ValueError("perturbed-attention guidance (a pag table) together with an slg table is not served: one third prediction, one scale "
-                         "table - give slg_layers beside pag_layers under the pag table")
+        raise ValueError(f"{what} ({table}) together with an slg table is not served: one third prediction, one scale "
+                         f"table - give slg_layers beside {layers} under the {table[2:]}")
     if method not in FIXED_GRID_METHODS:
-        raise ValueError(f"perturbed-attention guidance is built for the fixed-grid methods {', '.join(FIXED_GRID_METHODS)}, not '{method}'")
+        raise ValueError(f"{what} is built for the fixed-grid methods {', '.join(FIXED_GRID_METHODS)}, not '{method}'")
     if not rule_is_off(rescale, norm_limit):
-        raise ValueError("perturbed-attention guidance (a pag table) together with a rescale / norm_limit rule is not served")
+        raise ValueError(f"{what} ({table}) together with a rescale / norm_limit rule is not served")
     if reuse is not None:
-        raise ValueError("perturbed-attention guidance (a pag table) together with guidance reuse (a reuse table) is not served")
+        raise ValueError(f"{what} ({table}) together with guidance reuse (a reuse table) is not served")
     if teacache is not None:
-        raise ValueError("perturbed-attention guidance (a pag table) together with step caching (teacache) is not served")
+        raise ValueError(f"{what} ({table}) together with step caching (teacache) is not served")
     if mask is not None:
-        raise ValueError("perturbed-attention guidance (a pag table) together with an inpainting mask is not served")
+        raise ValueError(f"{what} ({table}) together with an inpainting mask is not served")
 
 
 def sample_cfg_pag(model, z, tgrid, table, pag, pag_layers, skip_layers=(), method="euler", *, cond=None, t_round=True, **kw):
@@ -796,6 +791,14 @@ def sample_cfg_pag(model, z, tgrid, table, pag, pag_layers, skip_layers=(), meth
     kw = dict(kw)
     kw.pop("cfg_scale", None)  # the table is the scale
     refuse_with_pag(pag, method, kw.pop("rescale", 0.0), kw.pop("norm_limit", math.inf), kw.pop("reuse", None))
+    return _sample_third(model, z, tgrid, table, pag, dict(skip_layers=layers, perturb_layers=perturb), method, stages, cond, t_round, kw)
+
+
+def _sample_third(model, z, tgrid, table, s_table, third_kw, method, stages, cond, t_round, kw):
+    """the loop ``sample_cfg_pag`` and ``sample_cfg_seg`` share: ``third_kw`` are the keywords that make ``model.forward`` the third
+    prediction (the layer sets; the blur width), ``s_table`` its checked scale table, ``kw`` the caller's keywords with the refused ones taken
+    out.  Everything is ``sample_cfg_slg``, statement for statement"""
+    B = z.size(0)
     if cond is None:
         cond = [k for k, v in kw.items() if isinstance(v, th.Tensor) and v.dim() >= 1 and v.shape[0] == B]
     cond_kw = {k: kw.pop(k) for k in cond}
@@ -803,7 +806,7 @@ def sample_cfg_pag(model, z, tgrid, table, pag, pag_layers, skip_layers=(), meth
     ch_model = int(getattr(model, "cfg_channels", 3))
     device = z.device
     t = _grid32(tgrid).to(device)
-    w, sl = table.tolist(), pag.tolist()
+    w, sl = table.tolist(), s_table.tolist()
     call = [0]
 
     def func(tt, y):
@@ -816,7 +819,7 @@ def sample_cfg_pag(model, z, tgrid, table, pag, pag_layers, skip_layers=(), meth
                 return model.forward_with_cfg(y, tvec, **cond_kw, cfg_scale=scale, **kw)
             o = model.forward(y[:half], tvec[:half], **half_kw)
             return th.cat([o, o])
-        k = model.forward(y[:half], tvec[:half], **half_kw, skip_layers=layers, perturb_layers=perturb).to(th.bfloat16)
+        k = model.forward(y[:half], tvec[:half], **half_kw, **third_kw).to(th.bfloat16)
         ch = min(ch_model, k.size(1))
         if scale != 1.0:
             o = model.forward(th.cat([y[:half]] * 2), tvec, **cond_kw).to(th.bfloat16)
@@ -853,6 +856,112 @@ def sample_cfg_pag(model, z, tgrid, table, pag, pag_layers, skip_layers=(), meth
         out[j + 1] = y
     assert call[0] == (len(t) - 1) * stages
     return out
+
+
+# ---- smoothed-energy guidance: the third prediction runs a set of blocks on Gaussian-blurred queries ---------------------------
+SEG_MAX_RADIUS = 31  # LT_SEG_MAX_RADIUS
+
+
+def seg_taps(sigma):
+    """What a blur width stands for: ``(mode, radius, taps)``.  ``sigma`` is taken as the fp32 value the engine receives.  ``+inf``: mode 1
+    (every image query becomes the mean query), radius 0, no taps.  Otherwise mode 0, ``radius = min(ceil(3 sigma), 31)`` and the
+    ``2 radius + 1`` taps as an fp32 tensor: the Gaussian ``exp(-k^2 / (2 sigma^2))`` in float64 (``math.exp``), summed from ``k = -radius``
+    upward, every tap divided by the sum and rounded once to fp32.  ``lt_op_seg_taps`` is held to this word for word."""
+    sg = float(th.tensor(float(sigma), dtype=th.float32))
+    if not sg > 0.0:
+        raise ValueError(f"blur sigma {sigma!r} is not positive (+inf is the mean query)")
+    if math.isinf(sg):
+        return 1, 0, th.zeros(0, dtype=th.float32)
+    r = int(min(math.ceil(3.0 * sg), SEG_MAX_RADIUS))
+    den = 2.0 * sg * sg
+    g = [math.exp(-float(k * k) / den) for k in range(-r, r + 1)]
+    total = 0.0
+    for v in g:
+        total += v
+    return 0, r, th.tensor([v / total for v in g], dtype=th.float64).to(th.float32)
+
+
+def seg_table(tgrid, method, seg_scale, interval=None):
+    """The fp32 table of smoothed-energy scales of a trajectory, one per evaluation: ``slg_table``'s rule"""
+    return slg_table(tgrid, method, seg_scale, interval=interval, what="smoothed-energy")
+
+
+def check_seg(seg, tgrid, method):
+    """``seg`` as an fp32 CPU tensor of ``(len(tgrid) - 1) * stages`` finite entries"""
+    if seg is None:
+        raise ValueError("smoothed-energy table is None (one scale per evaluation; seg_table builds one)")
+    return check_slg(seg, tgrid, method, what="smoothed-energy")
+
+
+def check_seg_layers(seg_layers, skip_layers=(), n_layers=None):
+    """-> (blur set, skip set) as lists of ints: ``check_pag_layers``' refusals with "blur" for "perturb" (the blur set may hold every layer)"""
+    return check_pag_layers(seg_layers, skip_layers, n_layers, name="blur")
+
+
+def refuse_with_seg(seg, method="euler", rescale=0.0, norm_limit=math.inf, reuse=None, slg=None, teacache=None, mask=None, pag=None):
+    """what smoothed-energy guidance is not served with, by name: everything perturbed-attention guidance refuses, and ``pag`` itself (one
+    third prediction, and no evaluation runs a blur set beside a perturb set)"""
+    if seg is None:
+        return
+    if pag is not None:
+        raise ValueError("smoothed-energy guidance (a seg table) together with perturbed-attention guidance (a pag table) is not served: one "
+                         "third prediction, and no evaluation blurs and perturbs")
+    refuse_with_pag(seg, method, rescale, norm_limit, reuse, slg, teacache, mask, what="smoothed-energy guidance", table="a seg table",
+                    layers="seg_layers")
+
+
+def sample_cfg_seg(model, z, tgrid, table, seg, seg_layers, seg_sigma, skip_layers=(), method="euler", *, cond=None, t_round=True, **kw):
+    """The trajectory of smoothed-energy guidance on the host: every state ``[len(tgrid), *z.shape]``.  This IS the definition
+    ``lt_sample_ode_cfg_seg`` is held to, state for state.  It is ``sample_cfg_pag`` with
+
+        k = bf16(model.forward(x[:B'], t[:B'], <cond half>, skip_layers=S, blur_layers=Q, blur_sigma=sigma))
+
+    as the third evaluation: the blocks of ``Q`` run their self-attention on queries blurred over the 2-D token grid (``seg_taps``; the
+    post-RoPE queries; the text cross-attention reads the queries as they are), ``S``: the blocks left out; disjoint, either may be empty."""
+    if isinstance(z, (list, tuple)):
+        raise ValueError("smoothed-energy guidance takes a tensor state; a packed batch (a list of latents) is not served")
+    stages = _check_method(method)
+    table = check_table(table, tgrid, method)
+    seg = check_seg(seg, tgrid, method)
+    blur, layers = check_seg_layers(seg_layers, skip_layers, getattr(model, "n_layers", None))
+    if blur:
+        seg_taps(seg_sigma)
+    if not blur and not layers and bool((seg != 0).any()):
+        raise ValueError("both layer sets are empty and the table has a non-zero scale: the third prediction would be the conditional one")
+    if z.size(0) % 2:
+        raise ValueError(f"guidance needs an even batch (cond + uncond rows), got {z.size(0)}")
+    kw = dict(kw)
+    kw.pop("cfg_scale", None)  # the table is the scale
+    refuse_with_seg(seg, method, kw.pop("rescale", 0.0), kw.pop("norm_limit", math.inf), kw.pop("reuse", None))
+    third_kw = dict(skip_layers=layers, blur_layers=blur, blur_sigma=seg_sigma)
+    return _sample_third(model, z, tgrid, table, seg, third_kw, method, stages, cond, t_round, kw)
+
+
+def sample_seg_front(x, model, tgrid, method, table, model_kwargs, seg, seg_layers, seg_sigma, slg_layers=(), *, t_round=True, use_engine=True,
+                     project=None, compose=None, windows=None, **companions):
+    """what ``ODE.sample`` / ``ode.sample`` do with ``seg_table=``: the refusals by name (``companions``: the keyword arguments of
+    ``refuse_with_seg``; projected / composed guidance and windows besides), then ONE engine call for the bound ``forward_with_cfg`` of an
+    engine-backed model on a ROCm state, else the host loop ``sample_cfg_seg``.  Without a table ``cfg_scale`` holds at every stage."""
+    from .integrators import _engine_target
+    if isinstance(x, (list, tuple)):
+        raise ValueError("smoothed-energy guidance (seg_table) takes a tensor state; a packed batch (a list of latents) is not served")
+    for given, name in ((project, "projected guidance (cfg_apg / cfg_zero_star)"), (compose, "composed guidance (compose)"),
+                        (windows, "tiled sampling (windows)")):
+        if given is not None:
+            raise ValueError(f"smoothed-energy guidance (a seg table) together with {name} is not served")
+    refuse_with_seg(seg, method, **companions)
+    if seg_sigma is None:
+        raise ValueError("smoothed-energy guidance: seg_table needs seg_sigma (> 0; inf: the mean query)")
+    if table is None:
+        table = cfg_table(tgrid, method, model_kwargs.get("cfg_scale", 1.0))
+    target = _engine_target(model)
+    if target is not None and target[1] and x.is_cuda and use_engine and hasattr(target[0], "_engine_sample_ode_cfg_schedule"):
+        return target[0]._engine_sample_ode_cfg_schedule(x, tgrid, method, t_round, table, dict(model_kwargs), seg=seg, seg_layers=seg_layers,
+                                                         seg_sigma=seg_sigma, slg_layers=slg_layers)
+    owner = getattr(model, "__self__", None)
+    if owner is None or getattr(model, "__name__", "") != "forward_with_cfg" or not hasattr(owner, "forward"):
+        raise TypeError("seg_table needs the bound forward_with_cfg of a model that also has forward (the third evaluation calls it)")
+    return sample_cfg_seg(owner, x, tgrid, table, seg, seg_layers, seg_sigma, slg_layers, method, t_round=t_round, **model_kwargs)
 
 
 # ---- projected guidance: APG and CFG-Zero*, the forms that need inner products of the two predictions (DESIGN.md 7q) ---------------------------

@@ -398,7 +398,16 @@ class ode:
 
     def sample(self, x, model, cfg_table=None, cfg_rescale=0.0, cfg_norm_limit=math.inf, cfg_reuse=None, slg_table=None, slg_layers=(),
                teacache=None, teacache_coefficients=None, pag_table=None, pag_layers=(), cfg_apg=None, cfg_zero_star=False, cfg_zero_init=0,
-               windows=None, window_weights=None, compose=None, **model_kwargs):
+               windows=None, window_weights=None, compose=None, seg_table=None, seg_layers=(), seg_sigma=None, **model_kwargs):
+        if seg_table is not None:  # smoothed-energy guidance (transport/guidance.py): its refusals come first, by name; None: the call it was
+            from .guidance import sample_seg_front
+            if isinstance(x, tuple) or not getattr(self.drift, "is_plain_velocity", False):
+                raise NotImplementedError("smoothed-energy guidance is built for a tensor state with the plain velocity as drift")
+            return sample_seg_front(x, model, self.t, self.sampler_type, cfg_table, model_kwargs, seg_table, seg_layers, seg_sigma, slg_layers,
+                                    t_round=self.t_round_to_state_dtype, use_engine=self.use_engine,
+                                    project=True if (cfg_apg is not None or cfg_zero_star or cfg_zero_init) else None, compose=compose,
+                                    windows=windows, rescale=cfg_rescale, norm_limit=cfg_norm_limit, reuse=cfg_reuse, slg=slg_table,
+                                    teacache=teacache, pag=pag_table)
         if compose is not None:  # composed guidance (transport/guidance.py): its refusals come first, by name
             from .guidance import sample_compose_front
             if isinstance(x, tuple) or not getattr(self.drift, "is_plain_velocity", False):

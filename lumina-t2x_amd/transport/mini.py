@@ -130,9 +130,17 @@ class ODE:
 
     def sample(self, x, model, mask=None, x1=None, noise=None, cfg_table=None, cfg_rescale=0.0, cfg_norm_limit=math.inf, cfg_reuse=None,
                slg_table=None, slg_layers=(), teacache=None, teacache_coefficients=None, pag_table=None, pag_layers=(), cfg_apg=None,
-               cfg_zero_star=False, cfg_zero_init=0, windows=None, window_weights=None, compose=None, **model_kwargs):
+               cfg_zero_star=False, cfg_zero_init=0, windows=None, window_weights=None, compose=None, seg_table=None, seg_layers=(),
+               seg_sigma=None, **model_kwargs):
         if isinstance(x, tuple):
             raise NotImplementedError("tuple states are not part of the sampling path")
+        if seg_table is not None:  # smoothed-energy guidance (transport/guidance.py): its refusals come first, by name; None: the call it was
+            from .guidance import sample_seg_front
+            return sample_seg_front(x, model, self.t, self.sampler_type, cfg_table, model_kwargs, seg_table, seg_layers, seg_sigma, slg_layers,
+                                    t_round=self.t_round_to_state_dtype, use_engine=self.use_engine,
+                                    project=True if (cfg_apg is not None or cfg_zero_star or cfg_zero_init) else None, compose=compose,
+                                    windows=windows, rescale=cfg_rescale, norm_limit=cfg_norm_limit, reuse=cfg_reuse, slg=slg_table,
+                                    teacache=teacache, mask=next((m for m in (mask, x1, noise) if m is not None), None), pag=pag_table)
         if compose is not None:  # composed guidance (transport/guidance.py): its refusals come first, by name
             from .guidance import sample_compose_front
             return sample_compose_front(x, model, self.t, self.sampler_type, model_kwargs, compose, t_round=self.t_round_to_state_dtype,
